@@ -15,11 +15,22 @@ A "step" is one pass of that path over the rank's 1024 windows (one `ape_lstm_fo
 `ape_fk` launch).  Streams are sharded contiguously over the ranks (weak scaling, no data-path
 collective); the only collective is the start-up broadcast of the weight blob (RCCL).
 
-Prints ONE JSON line on rank 0 (see the task contract), with two extra objects:
+Prints ONE JSON line on rank 0 (see the task contract), with one extra object:
   roofline      dominant kernel (the LSTM) -- algorithmic FLOP per launch / its mean duration,
                 measured live with HIP events on the launch stream, vs the dense f32 MFMA peak
-  cpu_baseline  the oracle's reference-equivalent CPU path (torch nn.LSTM + per-row eigh FK) timed
-                on this host's cores on a bounded sample (rank 0, N=1 only)
+
+A plain run does only what that line needs: set-up, warm-up, the K timed steps, the line.
+  --full              also runs every secondary leg and writes the full result to bench_detail.json:
+                      batch-1 latency, the drop-in Estimator loop, the stream banks, the other
+                      regressors, AUTO's dispatch boundaries, the LSTM beside a memory-bound
+                      neighbour, fp16 configs[4] and `cpu_baseline` (the oracle's reference-
+                      equivalent CPU path, torch nn.LSTM + per-row eigh FK, timed on this host's
+                      cores on a bounded sample; rank 0, N=1 only, unless --no-cpu-baseline); in an
+                      N-rank run every rank's Monte-Carlo bank frames
+  --dump-outputs DIR  after the timed steps, writes what the last timed step computed -- all ranks'
+                      windows in stream order -- as DIR/targets.npy (the regressor's normalised
+                      targets, [windows, 14] float32) and DIR/est.npy (the de-normalised FK rows,
+                      [windows, 21] float32)
 """
 import argparse
 import ctypes as C
@@ -1065,6 +1076,10 @@ def spawn_ranks(args):
            "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
+    if args.full:
+        cmd.append("--full")
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", str(Path(args.dump_outputs).resolve())]
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", "8")
@@ -1086,10 +1101,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--full", action="store_true", help="also run every secondary leg (see the module docstring)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs as DIR/<name>.npy")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
 
     if "WORLD_SIZE" not in os.environ and "RANK" not in os.environ:
         if args.gpus > 1:
@@ -1216,14 +1235,23 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     model.check()           # blocking health check of the cluster kernel (bounded spins never expired)
+    dumped = None
+    if args.dump_outputs:   # the last timed step's y / est, taken before any --full leg runs; every rank's shard, in stream order
+        dumped = {}
+        for name, t in (("targets", y), ("est", est)):
+            parts = [t.to(comm_dev)]
+            if use_dist:
+                parts = [torch.empty_like(parts[0]) for _ in range(world)]
+                dist.all_gather(parts, t.to(comm_dev))
+            dumped[name] = torch.cat(parts).cpu().numpy().astype(np.float32)
 
     kernel_ms = float(np.mean([a.elapsed_time(b) for a, b in ev_k]))
     # BASELINE configs[3] literally: 8192 independent streams, one shard of 1024 per GPU, in the estimators' default Monte-Carlo mode --
-    # in an N-rank run every rank also steps ITS 1024-stream x 25-sample bank (device-side frame: rows in, datagram rows out) and
+    # in an N-rank --full run every rank also steps ITS 1024-stream x 25-sample bank (device-side frame: rows in, datagram rows out) and
     # reports the frame time, so that the per-node load of configs[3] is in the line rank by rank
     # (round 5: all three deployed estimators' shards -- pocket 25 samples, upper-arm 50 samples, watch-only 25 samples / smooth 10)
     bank_ms = bank_uarm_ms = bank_watch_ms = float("nan")
-    if use_dist:
+    if use_dist and args.full:
         bk = stream_bank_numbers(model, stats, cases=[("S1024_mc25", "pocket", 1024, 25, 1, 20), ("uarm_S1024_mc50_T6", "uarm", 1024, 50, 1, 10),
                                                       ("watch_S1024_mc25_T8", "watch", 1024, 25, 10, 10)])
         bank_ms = float(bk.get("S1024_mc25", {}).get("ms_per_frame_of_all_streams", float("nan")))
@@ -1263,7 +1291,7 @@ def main():
                                                   "bank_watch_S1024_mc25_T8_smooth10_ms_per_frame": nn_(rank_times[int(s_[0])][4])} for s_ in shards],
                                     "bank_note": "per rank: one frame of its 1024-stream Monte-Carlo bank for each of the three deployed estimators in "
                                                  "their default modes (configs[3]'s shard: pocket 25 samples, upper-arm 50 samples, watch-only 25 samples "
-                                                 "with smooth 10); null in a 1-rank run, where stream_bank_T6 carries them"},
+                                                 "with smooth 10); null without --full and in a 1-rank run, where stream_bank_T6 carries them"},
                        "preroll_steps": PREROLL},
             "roofline": {"bound": "mfma", "achieved": achieved_tf, "peak": PEAK_F32_MFMA_TFLOPS, "unit": "TFLOP/s",
                          "frac": achieved_tf / PEAK_F32_MFMA_TFLOPS, "traffic": traffic, "traffic_from": ttag,
@@ -1280,7 +1308,7 @@ def main():
         }
         if len({round(s_[4], 6) for s_ in shards}) != 1:
             raise SystemExit("bench.py: ranks hold different weight blobs after the broadcast")
-        if world == 1:
+        if world == 1 and args.full:
             out["batch1"] = batch1_latency(model, stats)
             out["batch1"]["estimator_loop"] = estimator_loop(sd)
             out["stream_bank_T6"] = stream_bank_numbers(model, stats)
@@ -1310,7 +1338,15 @@ def main():
                     if best and key in out["batch1"].get("estimator_loop", {}):
                         out["batch1"]["estimator_loop"][key]["cpu_frames_per_s"] = cb["legs"][best[0]]["frames_per_s"]
                         out["batch1"]["estimator_loop"][key]["cpu_leg"] = best[0]
-        emit(out, _JSON_FD)
+        if dumped is not None:
+            d = Path(args.dump_outputs)
+            d.mkdir(parents=True, exist_ok=True)
+            for name, a in dumped.items():
+                np.save(d / f"{name}.npy", a)
+        if args.full:
+            emit(out, _JSON_FD)
+        else:
+            os.write(_JSON_FD, (compact_line(out) + "\n").encode())
     if use_dist:
         dist.barrier()
         dist.destroy_process_group()

@@ -24,6 +24,38 @@ def test_gpus_flag_must_match_the_launchers_world_size():
     assert r.returncode != 0 and "WORLD_SIZE=4" in r.stderr
 
 
+def test_full_and_dump_outputs_are_options_and_steps_must_be_positive(tmp_path):
+    r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--full", "--dump-outputs", str(tmp_path / "o")],
+             {"RANK": "0", "WORLD_SIZE": "1", "LOCAL_RANK": "0"})
+    assert r.returncode != 0 and "WORLD_SIZE=1" in r.stderr          # parsed, then refused before anything is measured
+    assert not (tmp_path / "o").exists()
+    r = _run(["--gpus", "1", "--steps", "0", "--warmup", "0"], {})
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
+    assert '{"metric"' not in r.stdout
+
+
+def test_self_spawn_passes_full_and_dump_outputs_to_the_ranks(tmp_path, monkeypatch, capfd):
+    import argparse
+    import subprocess
+    sys.path.insert(0, str(REPO))
+    import bench
+    seen = {}
+
+    def fake_run(cmd, **kw):
+        seen["cmd"] = cmd
+        return subprocess.CompletedProcess(cmd, 0, stdout=b'{"metric":"x"}\n')
+    monkeypatch.setattr(bench, "visible_gpus_without_opening_them", lambda: 2)
+    monkeypatch.setattr(subprocess, "run", fake_run)
+    monkeypatch.chdir(tmp_path)
+    bench.spawn_ranks(argparse.Namespace(gpus=2, steps=5, warmup=1, no_cpu_baseline=False, full=True, dump_outputs="o"))
+    cmd = seen["cmd"]
+    assert cmd[cmd.index("--steps") + 1] == "5" and "--full" in cmd
+    assert cmd[cmd.index("--dump-outputs") + 1] == str(tmp_path / "o")
+    assert capfd.readouterr().out == '{"metric":"x"}\n'
+    bench.spawn_ranks(argparse.Namespace(gpus=2, steps=5, warmup=1, no_cpu_baseline=False, full=False, dump_outputs=None))
+    assert "--full" not in seen["cmd"] and "--dump-outputs" not in seen["cmd"]
+
+
 def test_self_spawn_refuses_more_ranks_than_gpus():
     import torch
     if torch.cuda.device_count() >= 2:
