@@ -802,7 +802,9 @@ static int mc_small_launch(ape_model_t* m, const float* x, size_t x_stream_strid
 // x_ring: time step t of every window lives in slot (t + x_ring) mod T (0 = the linear layout of the public entry)
 static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t flags,
                              const float* masks_dev, float dropout_p, uint64_t seed, float* y_dev, void* stream,
-                             int x_ring, const float* h0_dev = nullptr, const float* c0_dev = nullptr, FkTail* fk = nullptr) {
+                             int x_ring, const float* h0_dev = nullptr, const float* c0_dev = nullptr, FkTail* fk = nullptr,
+                             long long row_base = 0) {
+    // row_base (DROPOUT_PHILOX, a multiple of 16): the global row of x_dev's row 0 when a caller serves one batch in several calls
     if (!m || !x_dev || !y_dev) return fail(APE_ERR_INVALID_ARG, "lstm_forward: NULL argument");
     if (B < 1 || T < 1) return fail(APE_ERR_INVALID_ARG, "lstm_forward: B=%d T=%d must be >= 1", B, T);
     flags &= ~(uint32_t)APE_FLAG_XCD_CLASSES;            // (the launcher's own bit)
@@ -990,6 +992,7 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
         p.dropout_p = dropout_p;
         p.seed = seed;
         p.h0 = h0_dev; p.c0 = c0_dev; p.hs_rows = B;
+        p.row_base = row_base;
         m->last_kernel = "ape_lstm_tile16";
         hipError_t e = ape_launch_lstm_tile16(H, L, p, (hipStream_t)stream);
         if (e != hipSuccess) return fail(APE_ERR_HIP, "lstm kernel launch failed: %s", hipGetErrorString(e));
@@ -1159,7 +1162,7 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
             }
             if ((flags & APE_FLAG_DROPOUT_MASKS) && b0 + nb < B && cdrop)
                 return fail(APE_ERR_UNSUPPORTED, "lstm_forward: injected masks with B=%d exceed one cluster launch", B);
-            c.row_base = b0;                          // Philox counters over the call's global rows, whatever the split
+            c.row_base = (int)(row_base + b0);        // Philox counters over the call's global rows, whatever the split
             int clusters = (nb + 16 * nmt - 1) / (16 * nmt);
             // f32 first-generation kernel: whole groups of 8 clusters (if the device holds them) form XCD-local clusters and hand
             // their slices over inside that XCD's L2 (lstm_cluster.hip, APE_FLAG_XCD_CLASSES); the extra clusters own no rows
@@ -2102,6 +2105,145 @@ int ape_streams_profile_read(ape_streams_t* b, double* kernel_ms_sum, int32_t* l
     *kernel_ms_sum = sum; *launches = b->prof_n;
     b->prof_n = 0;
     return APE_OK;
+}
+
+// ---- offline replay: every frame of one or more recordings in one call --------------------------------------
+// Chunks of sample rows [r0, r0 + R): windows (replay.hip) -> regressor (lstm_forward_impl with the chunk's global row base, so that the
+// Philox masks are those of ONE call over all F * n_mc rows) -> FK with de-normalisation into f64 est rows -> the messages of every frame
+// whose rows are all there.  The est buffer of a chunk starts with the last `carry` rows of the one before (two buffers, ping-pong): the
+// stacks of the chunk's first frames reach back into them.
+#ifndef APE_REPLAY_WINDOW_BYTES
+#define APE_REPLAY_WINDOW_BYTES (64ll << 20)      // default bound of a chunk's window image
+#endif
+
+struct ApeDeviceScratch {                         // the call's device workspaces, freed on every way out
+    std::vector<void*> bufs;
+    ~ApeDeviceScratch() { for (void* b : bufs) (void)hipFree(b); }
+    hipError_t alloc(void** out, size_t bytes) {
+        *out = nullptr;
+        hipError_t e = hipMalloc(out, bytes > 0 ? bytes : 1);
+        if (e == hipSuccess) bufs.push_back(*out);
+        return e;
+    }
+};
+
+int ape_replay(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+               int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+               void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream) {
+    // the arguments on their own first (no device needed to refuse them)
+    if (!rows_dev || !out_dev) return fail(APE_ERR_INVALID_ARG, "replay: NULL argument");
+    int width, I;
+    const int big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
+    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return fail(APE_ERR_INVALID_ARG, "replay: unknown kind %d", kind);
+    if (F < 1) return fail(APE_ERR_INVALID_ARG, "replay: F=%d must be >= 1", F);
+    if (R < 1 || R > F) return fail(APE_ERR_INVALID_ARG, "replay: %d recording starts for %d frames (1 <= R <= F)", R, F);
+    if (!seg_starts_host) return fail(APE_ERR_INVALID_ARG, "replay: NULL seg_starts");
+    if (seg_starts_host[0] != 0) return fail(APE_ERR_INVALID_ARG, "replay: seg_starts[0] = %d, must be 0", seg_starts_host[0]);
+    for (int i = 1; i < R; ++i)
+        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
+            return fail(APE_ERR_INVALID_ARG, "replay: seg_starts[%d] = %d (strictly rising, below F = %d)", i, seg_starts_host[i], F);
+    if (seq_len < 1) return fail(APE_ERR_INVALID_ARG, "replay: seq_len=%d must be >= 1", seq_len);
+    if (smooth < 1 || smooth > 64) return fail(APE_ERR_UNSUPPORTED, "replay: smooth %d outside 1..64", smooth);
+    if (n_mc < 1 || (long long)n_mc * smooth > 4096)
+        return fail(APE_ERR_INVALID_ARG, "replay: n_mc=%d with smooth=%d (1 <= smooth*n_mc <= 4096)", n_mc, smooth);
+    if ((long long)F * n_mc >= (1ll << 31)) return fail(APE_ERR_UNSUPPORTED, "replay: F*n_mc = %lld sample rows (< 2^31)", (long long)F * n_mc);
+    if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return fail(APE_ERR_INVALID_ARG, "replay: dropout_p %g outside [0,1)", (double)dropout_p);
+    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG))
+        return fail(APE_ERR_INVALID_ARG, "replay: only NORMALIZE_INPUT and PACKED_MSG are accepted");
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "replay: unknown dtype selector");
+    if (max_rows_per_launch < 0 || (max_rows_per_launch > 0 && max_rows_per_launch < 16))
+        return fail(APE_ERR_INVALID_ARG, "replay: max_rows_per_launch=%d (0 = default, else >= 16)", max_rows_per_launch);
+    if (!m) return fail(ape_device_count() == 0 ? APE_ERR_NO_DEVICE : APE_ERR_INVALID_ARG,
+                        "replay: NULL model (no gfx950 device: there is no CPU fallback)");
+    // ... then against the model
+    if (m->dims.model_kind != APE_MODEL_LSTM) return fail(APE_ERR_UNSUPPORTED, "replay: LSTM estimator models only (not FF / ImuPose)");
+    if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "replay: model has no target layout");
+    if (m->precision != APE_PRECISION_F32) return fail(APE_ERR_UNSUPPORTED, "replay: fp16 precision is set on the model (float32 only)");
+    if (I != m->dims.input_size)
+        return fail(APE_ERR_INVALID_ARG, "replay: kind %d builds %d features, the model takes %d", kind & ~APE_PARSE_BIG_ENDIAN, I, m->dims.input_size);
+    if (!m->has_weights) return fail(APE_ERR_NOT_READY, "replay: weights not loaded");
+    const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
+    if (norm && !m->has_stats) return fail(APE_ERR_NOT_READY, "replay: NORMALIZE_INPUT without norm stats");
+    HIP_TRY(hipSetDevice(m->dims.device));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "replay: blocking call on a capturing stream");
+    // what was issued on the handle before is healthy (and off the journal) before the replay's launches follow it
+    if (int rc = ape_model_recover(m)) return rc;
+
+    const hipStream_t st = (hipStream_t)stream;
+    const int T = seq_len, O = m->dims.output_size, W = layout_est_width(m->dims.target_layout);
+    const int N = smooth * n_mc;
+    const long long total = (long long)F * n_mc;
+    const bool tail = (flags & APE_FLAG_PACKED_MSG) && N > 1;
+    const long long out_stride = tail ? 25 + 6ll * N : 25;
+    // sample rows per chunk: a multiple of 16 (the cluster kernels' row base), the window image bounded
+    long long rmax = max_rows_per_launch > 0 ? max_rows_per_launch : APE_REPLAY_WINDOW_BYTES / ((long long)T * I * sizeof(float));
+    rmax = rmax / 16 * 16;
+    if (rmax < 16) rmax = 16;
+    if (rmax > (total + 15) / 16 * 16) rmax = (total + 15) / 16 * 16;
+    const long long carry = N;                    // >= (smooth - 1) * n_mc rows of older frames + the newest frame's first n_mc - 1
+    ApeDeviceScratch ws;
+    float *xx, *xw, *yws = nullptr;
+    int *starts_d, *seg_of;
+    double* est[2];
+    HIP_TRY(ws.alloc((void**)&xx, (size_t)F * I * sizeof(float)));
+    HIP_TRY(ws.alloc((void**)&seg_of, (size_t)F * sizeof(int)));
+    HIP_TRY(ws.alloc((void**)&starts_d, (size_t)R * sizeof(int)));
+    HIP_TRY(ws.alloc((void**)&xw, (size_t)rmax * T * I * sizeof(float)));
+    if (!y_dev) HIP_TRY(ws.alloc((void**)&yws, (size_t)rmax * O * sizeof(float)));
+    HIP_TRY(ws.alloc((void**)&est[0], (size_t)(carry + rmax) * W * sizeof(double)));
+    HIP_TRY(ws.alloc((void**)&est[1], (size_t)(carry + rmax) * W * sizeof(double)));
+    HIP_TRY(hipMemcpyAsync(starts_d, seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st));
+
+    const bool drop = dropout_p > 0.0f && m->dims.num_layers > 1;
+    const uint32_t lflags = (norm ? APE_FLAG_NORMALIZE_INPUT : 0u) | (drop ? APE_FLAG_DROPOUT_PHILOX : 0u);
+    auto pass = [&]() -> int {
+        hipError_t e = ape_launch_parse_rows(rows_dev, F, width, kind & ~APE_PARSE_BIG_ENDIAN, xx, APE_F32, I, (size_t)I, 1, 0, big_endian, st);
+        if (e == hipSuccess) e = ape_launch_replay_segments(starts_d, R, F, seg_of, st);
+        if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: feature launch failed: %s", hipGetErrorString(e));
+        long long prev_rows = 0;
+        for (long long r0 = 0, c = 0; r0 < total; r0 += rmax, ++c) {
+            const int rows = (int)(total - r0 < rmax ? total - r0 : rmax);
+            ReplayWindowParams wp{};
+            wp.xx = xx; wp.seg_of = seg_of; wp.xw = xw; wp.r0 = r0; wp.R = rows; wp.T = T; wp.I = I; wp.n_mc = n_mc;
+            e = ape_launch_replay_windows(wp, st);
+            if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: window launch failed: %s", hipGetErrorString(e));
+            float* y = y_dev ? y_dev + (size_t)r0 * O : yws;
+            if (int rc = lstm_forward_impl(m, xw, rows, T, lflags, nullptr, drop ? dropout_p : 0.0f, seed, y, stream, 0, nullptr, nullptr,
+                                           nullptr, r0))
+                return rc;
+            double* cur = est[c & 1];
+            if (c > 0)
+                HIP_TRY(hipMemcpyAsync(cur, est[(c + 1) & 1] + (size_t)prev_rows * W, (size_t)carry * W * sizeof(double),
+                                       hipMemcpyDeviceToDevice, st));
+            if (int rc = fk_impl(m, y, APE_F32, rows, norm ? 1 : 0, cur + (size_t)carry * W, APE_F64, stream)) return rc;
+            ReplayMsgParams mp{};
+            mp.est = cur; mp.est_base = r0 - carry; mp.seg_of = seg_of; mp.out = out_dev; mp.out_stride = out_stride;
+            mp.f_lo = r0 / n_mc; mp.f_hi = (r0 + rows) / n_mc;
+            memcpy(mp.body, m->body, sizeof(mp.body));
+            mp.W = W; mp.layout = m->dims.target_layout; mp.smooth = smooth; mp.n_mc = n_mc; mp.out_dtype = out_dtype;
+            e = ape_launch_replay_msg(mp, tail, st);
+            if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: message launch failed: %s", hipGetErrorString(e));
+            prev_rows = rows;
+        }
+        return APE_OK;
+    };
+    if (int rc = pass()) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    // blocking and healthy on return: a weight-stationary launch that gave up is run again on the kernels that need no co-residency
+    int rc = check_and_reset(m);
+    if (rc == APE_ERR_HIP) {
+        m->stats_counts.aborted_checks += 1;
+        m->replaying = true;
+        rc = pass();
+        m->replaying = false;
+        if (rc != APE_OK) { m->stats_counts.lost_calls += 1; return rc; }
+        HIP_TRY(hipStreamSynchronize(st));
+        m->stats_counts.reissued_calls += 1;
+        rc = check_and_reset(m);
+    }
+    return rc;
 }
 
 // one journaled call again, on the kernels that need no co-residency (m->replaying is set)

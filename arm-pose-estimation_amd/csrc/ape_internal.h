@@ -56,6 +56,8 @@ struct LstmParams {
     const float* h0;                    // [L,hs_rows,H] initial hidden state (DropoutLSTM.forward(x, hs), nn_models.py:180-189)
     const float* c0;                    // [L,hs_rows,H] initial cell state; both nullptr: zeros
     int hs_rows;                        // batch size of h0 / c0
+    long long row_base;                 // DROPOUT_PHILOX: global index of this launch's row 0 in the caller's batch (a multiple of 4;
+                                        // 0 for every caller but a chunked one -- ape_replay -- whose chunks must draw the masks of ONE call)
 };
 
 // Kernel arguments of the weight-stationary cluster LSTM kernel.
@@ -232,6 +234,25 @@ struct MsgParams {
     int N, W, layout;
 };
 
+// Offline replay (replay.hip, ape_replay): a chunk of sample rows [r0, r0 + R) of a call over F frames x n_mc samples
+struct ReplayWindowParams {
+    const float* xx;     // [F,I] features of every frame of the call
+    const int* seg_of;   // [F] first frame of each frame's recording
+    float* xw;           // [R,T,I] windows of the chunk's sample rows
+    long long r0;
+    int R, T, I, n_mc;
+};
+struct ReplayMsgParams {
+    const double* est;   // f64 est rows; row `est_base` of the call's sample rows is est[0]
+    long long est_base;
+    const int* seg_of;   // [F]
+    void* out;           // [F, out_stride] of out_dtype: message, then (tail) 6 values per stacked row
+    long long out_stride;
+    long long f_lo, f_hi;   // frames [f_lo, f_hi) whose stacks are complete in this chunk
+    double body[9];
+    int W, layout, smooth, n_mc, out_dtype;
+};
+
 // Kernel arguments of the Monte-Carlo latency kernel (lstm_mc_small.hip): n_streams windows x n_mc dropout samples, dealt over the
 // 8 XCDs -- cluster c serves stream c / cps, sample rows [part * R, part * R + R) of it (part = c % cps).
 struct McSmallParams {
@@ -372,3 +393,6 @@ hipError_t ape_launch_head_rows(const float* hseq, int N, int H, int O, const fl
                                 hipStream_t stream);
 hipError_t ape_launch_fk(const FkParams& p, int preds_dtype, int est_dtype, hipStream_t stream);
 hipError_t ape_launch_msg_reduce(const MsgParams& p, hipStream_t stream);
+hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, int* seg_of, hipStream_t stream);
+hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t stream);
+hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream);

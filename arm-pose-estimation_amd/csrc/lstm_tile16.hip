@@ -154,7 +154,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_tile16(const LstmParams p) {
                 const int grp = gi * NP + part;
                 uint32_t rnd[4] = {0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu, 0xFFFFFFFFu};
                 if (drop_philox)
-                    philox4x32((uint32_t)(row0 + 4 * grp), (uint32_t)x_step, (uint32_t)unit, below, (uint32_t)p.seed,
+                    philox4x32((uint32_t)(p.row_base + row0 + 4 * grp), (uint32_t)x_step, (uint32_t)unit, below, (uint32_t)p.seed,
                                (uint32_t)(p.seed >> 32), rnd);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
@@ -309,7 +309,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_tile16(const LstmParams p) {
                 const int unit = wave * (H / 4) + u * 16 + r;
                 uint32_t rnd[4] = {0, 0, 0, 0};
                 if (drop_philox && l < L - 1)
-                    philox4x32((uint32_t)(row0 + 4 * g), (uint32_t)t, (uint32_t)unit, (uint32_t)(l + p.layer_base),
+                    philox4x32((uint32_t)(p.row_base + row0 + 4 * g), (uint32_t)t, (uint32_t)unit, (uint32_t)(l + p.layer_base),
                                (uint32_t)p.seed, (uint32_t)(p.seed >> 32), rnd);
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {

@@ -1,0 +1,144 @@
+// Offline replay (ape_replay): the kernels a whole recording needs beyond the per-frame ones --
+//
+// ape_replay_seg_kernel     frame -> first frame of its recording (the cold-start boundary), once per call
+// ape_replay_window_kernel  the windows of a chunk of sample rows, [R][T][I], every row's window assembled by the clamped-index rule of
+//                           Estimator._push_padded (estimator.py:96-100): window row t of frame f is feature row max(seg, f - T + 1 + t);
+//                           sample row r is sample r % n_mc of frame r / n_mc, so a frame's n_mc windows are copies
+// ape_replay_msg_kernel     the sliding smoothing stack of every frame whose rows are complete (estimator.py:112-118) reduced to its message
+//                           (compose_msg.py:13-108): stack row i = sample i % n_mc of frame max(seg, f - smooth + 1 + i / n_mc)
+// ape_replay_tail_kernel    the hand / elbow xyz of every stacked row behind the message (estimator.py:131-137)
+//
+// float64 with separate roundings for a * b + c, like numpy (and the bank's post-filter): contraction is off in this file.
+#include "ape_internal.h"
+#include "../../include/ape_hip.h"
+#include "stream_post_device.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace ape_postdev;
+
+// first frame of the recording frame f belongs to: the last start <= f (starts[0] == 0, strictly rising)
+__global__ __launch_bounds__(256) void ape_replay_seg_kernel(const int* __restrict__ starts, int n_starts, int F, int* __restrict__ seg_of) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    int lo = 0, hi = n_starts - 1;                      // invariant: starts[lo] <= f
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (starts[mid] <= f) lo = mid; else hi = mid - 1;
+    }
+    seg_of[f] = starts[lo];
+}
+
+// one thread per output float: consecutive threads write consecutive floats and read the same feature row's columns
+__global__ __launch_bounds__(256) void ape_replay_window_kernel(const ReplayWindowParams p) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    const long long per_row = (long long)p.T * p.I;
+    if (idx >= (long long)p.R * per_row) return;
+    const long long r = p.r0 + idx / per_row;
+    const int rem = (int)(idx % per_row);
+    const int t = rem / p.I, i = rem - t * p.I;
+    const int f = (int)(r / p.n_mc);
+    const int seg = p.seg_of[f];
+    int src = f - p.T + 1 + t;
+    if (src < seg) src = seg;
+    p.xw[idx] = p.xx[(size_t)src * p.I + i];
+}
+
+// One lane per frame, the stack's rows in the reference's order (average_quaternions, transformations.py:32-51: row 0 times 1/N, then
+// every further row added with +-1/N by the strict `dot < 0.0` rule against row 0).  Adjacent frames share all but n_mc of their rows:
+// the est rows come from L2.
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_replay_msg_kernel(const ReplayMsgParams p) {
+    const long long f = p.f_lo + (long long)blockIdx.x * 256 + threadIdx.x;
+    if (f >= p.f_hi) return;
+    const int M = p.n_mc, N = p.smooth * M, W = p.W;
+    const long long seg = p.seg_of[f];
+    auto row = [&](int i) -> const double* {
+        const int j = i / M, k = i - j * M;
+        long long h = f - p.smooth + 1 + j;
+        if (h < seg) h = seg;
+        return p.est + (h * M + k - p.est_base) * W;
+    };
+    const double* e0 = row(0);
+    double out_q[3][4] = {}, orig_mean[9] = {};
+    if (N > 1) {
+        const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
+        const int nq = hips ? 3 : 2;
+        const int qc[3] = {hips ? 9 : 6, hips ? 13 : 10, 17};
+        const double wgt = 1.0 / (double)N;
+        for (int q = 0; q < nq; ++q) {
+            const double r0 = e0[qc[q]], r1 = e0[qc[q] + 1], r2 = e0[qc[q] + 2], r3 = e0[qc[q] + 3];
+            double a0 = r0 * wgt, a1 = r1 * wgt, a2 = r2 * wgt, a3 = r3 * wgt;
+            for (int i = 1; i < N; ++i) {
+                const double* qi = row(i) + qc[q];
+                // the FMA chain of ape_msg_kernel: numpy's dot hands the 4 products to BLAS ddot (fk.hip)
+                const double d = fma(qi[3], r3, fma(qi[2], r2, fma(qi[1], r1, qi[0] * r0)));
+                const double sg = d < 0.0 ? -wgt : wgt;
+                a0 = a0 + qi[0] * sg; a1 = a1 + qi[1] * sg; a2 = a2 + qi[2] * sg; a3 = a3 + qi[3] * sg;
+            }
+            const double nrm = sqrt(a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3);
+            out_q[q][0] = a0 / nrm; out_q[q][1] = a1 / nrm; out_q[q][2] = a2 / nrm; out_q[q][3] = a3 / nrm;
+        }
+        if (p.layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS) {       // compose_msg.py:26-29: plain means of the three origins
+            for (int i = 0; i < N; ++i) {
+                const double* e = row(i);
+#pragma unroll
+                for (int c = 0; c < 9; ++c) orig_mean[c] += e[c];
+            }
+#pragma unroll
+            for (int c = 0; c < 9; ++c) orig_mean[c] /= (double)N;
+        }
+    }
+    double m[25];
+    finish_msg(p.layout, N, out_q, orig_mean, e0, p.body, m);
+    TMsg* dst = static_cast<TMsg*>(p.out) + f * p.out_stride;
+#pragma unroll
+    for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
+}
+
+// one thread per (frame, stacked row): six values each, neighbouring threads write neighbouring groups
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_replay_tail_kernel(const ReplayMsgParams p) {
+    const int M = p.n_mc, N = p.smooth * M;
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (p.f_hi - p.f_lo) * N) return;
+    const long long f = p.f_lo + idx / N;
+    const int i = (int)(idx % N);
+    const int j = i / M, k = i - j * M;
+    long long h = f - p.smooth + 1 + j;
+    const long long seg = p.seg_of[f];
+    if (h < seg) h = seg;
+    const double* e = p.est + (h * M + k - p.est_base) * p.W;
+    TMsg* dst = static_cast<TMsg*>(p.out) + f * p.out_stride + 25 + (long long)i * 6;
+#pragma unroll
+    for (int c = 0; c < 6; ++c) dst[c] = (TMsg)e[c];
+}
+
+unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
+
+}  // namespace
+
+hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, int* seg_of, hipStream_t stream) {
+    hipLaunchKernelGGL(ape_replay_seg_kernel, dim3(blocks_for(F)), dim3(256), 0, stream, starts, n_starts, F, seg_of);
+    return hipGetLastError();
+}
+
+hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL(ape_replay_window_kernel, dim3(blocks_for((long long)p.R * p.T * p.I)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
+
+hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream) {
+    const long long frames = p.f_hi - p.f_lo;
+    if (frames <= 0) return hipSuccess;
+    if (p.out_dtype == APE_F32) hipLaunchKernelGGL(ape_replay_msg_kernel<float>, dim3(blocks_for(frames)), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(ape_replay_msg_kernel<double>, dim3(blocks_for(frames)), dim3(256), 0, stream, p);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess || !tail) return e;
+    const long long n = frames * p.smooth * p.n_mc;
+    if (p.out_dtype == APE_F32) hipLaunchKernelGGL(ape_replay_tail_kernel<float>, dim3(blocks_for(n)), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL(ape_replay_tail_kernel<double>, dim3(blocks_for(n)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}

@@ -318,6 +318,48 @@ class Estimator:
                 del model._pending[0]
         return (est, y) if return_targets else est
 
+    # ---- offline replay: every frame of recorded sessions in one call ----
+    def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64,
+                          return_targets: bool = False, seed: int = 0x5EED, max_rows_per_launch: int = 0):
+        """rows: float32 ``[F, 55|28]`` raw messages of one or more recordings back to back (host array or CUDA
+        tensor); ``starts``: the recordings' first rows (default ``[0]``: one recording).  Returns, on the device,
+        what ``process_row`` returns for every row of a fresh estimator fed each recording in order (no row skipped):
+        ``[F, 25 + 6N]`` with ``add_mc_samples`` and N = smooth x Monte-Carlo samples > 1, else ``[F, 25]``.  With
+        ``return_targets`` also the normalised NN targets float32 ``[F, n_mc, O]``.  The Monte-Carlo samples are those
+        of one dropout forward keyed by ``seed`` over the repeated windows (``ape_replay``); ``max_rows_per_launch``
+        bounds the sample rows of one regressor launch (0: the library's default) and with it the device workspace."""
+        import ctypes as C
+        from wear_mocap_ape_amd import _hip
+        model, n_mc = self._hip_model(), self._frame_samples()
+        if model is None or n_mc is None or self._parse_kind is None:
+            raise UserWarning("this estimator has no HIP regressor or no batched feature builder")
+        width = _hip.PARSE_SHAPES[self._parse_kind][0]
+        if out_dtype not in (torch.float32, torch.float64):
+            raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+        n_mc = int(n_mc)
+        n_rows = self._smooth * n_mc
+        dev = model.torch_device
+        with torch.cuda.device(dev):
+            rd = torch.as_tensor(rows, dtype=torch.float32).to(dev).contiguous()
+            if rd.dim() != 2 or rd.shape[1] != width or rd.shape[0] < 1:
+                raise UserWarning(f"expected rows [F>=1,{width}], got {tuple(rd.shape)}")
+            F = int(rd.shape[0])
+            st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
+            packed = self._add_mc_samples and n_rows > 1
+            out = torch.empty((F, 25 + 6 * n_rows if packed else 25), dtype=out_dtype, device=dev)
+            y = torch.empty((F, n_mc, model.output_size), dtype=torch.float32, device=dev) if return_targets else None
+            flags = (_hip.FLAG_NORMALIZE_INPUT if self._normalize else 0) | (_hip.FLAG_PACKED_MSG if packed else 0)
+            kind = self._parse_kind | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _hip.check(_hip.lib().ape_replay(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
+                                             int(st.shape[0]), self._sequence_len, self._smooth, n_mc, float(model.dropout),
+                                             int(seed) & (2 ** 64 - 1), flags, C.c_void_p(out.data_ptr()),
+                                             _hip.F64 if out_dtype == torch.float64 else _hip.F32,
+                                             C.c_void_p(y.data_ptr()) if y is not None else None,
+                                             int(max_rows_per_launch), stream), "ape_replay")
+            model._pending.clear()         # the call is blocking and checked the handle (its journal is empty)
+        return (out, y) if return_targets else out
+
     # read-only views, same names as the reference's properties (estimator.py:188-218)
     sequence_len = property(lambda self: self._sequence_len)
     body_measurements = property(lambda self: self._body_measurements)

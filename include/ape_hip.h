@@ -302,6 +302,31 @@ int ape_streams_profile_read(ape_streams_t* bank, double* kernel_ms_sum, int32_t
 int ape_infer(ape_model_t* model, const float* x_dev, int32_t B, int32_t T, uint32_t flags,
               float* y_dev, void* est_dev, int32_t est_dtype, void* stream);
 
+/* offline replay (additive in ABI 7).  replaces, for every row of one or more recordings, what
+ * Estimator.processing_loop does per row (parse_row_to_xx -> add_xx_to_row_hist_and_make_prediction -> msg_from_pred,
+ * estimator.py:93-137), with no row skipped (the live loop's queue skip-ahead, estimator.py:159-161, is not applied).
+ *   kind            ape_parse_rows kind, may carry APE_PARSE_BIG_ENDIAN
+ *   rows_dev        f32 [F, 55|28] raw rows, the recordings back to back
+ *   seg_starts_host R >= 1 recording starts (host memory): [0] == 0, strictly rising, < F.  Every recording starts cold, as
+ *                   after ape_streams_reset: windows and smoothing stacks never reach across a start
+ *   seq_len, smooth window length and smoothing stack (smooth <= 64, smooth*n_mc <= 4096)
+ *   n_mc, dropout_p, seed  Monte-Carlo samples: those of ONE ape_lstm_forward(APE_FLAG_DROPOUT_PHILOX, dropout_p, seed) over the
+ *                   explicitly repeated windows [F*n_mc, T, I], sample row f*n_mc + k = sample k of frame f (F*n_mc < 2^31);
+ *                   independent of max_rows_per_launch and of the kernel route.  dropout_p = 0 (or one layer): no dropout
+ *   flags           APE_FLAG_NORMALIZE_INPUT, APE_FLAG_PACKED_MSG
+ *   out_dev         [F, 25] of out_dtype; with APE_FLAG_PACKED_MSG and N = smooth*n_mc > 1, [F, 25+6N]: row f is what a fresh
+ *                   estimator fed that recording's rows in order returns for its row f (message + hand / elbow xyz of every
+ *                   stacked row, the layout of ape_streams_step's PACKED_MSG rows)
+ *   y_dev           optional f32 [F, n_mc, O]: the normalised NN targets
+ *   max_rows_per_launch  bound on the sample rows of one regressor launch (0 = default, else >= 16): device workspace is
+ *                   O(F) for the features plus O(max_rows_per_launch), whatever F*n_mc
+ * BLOCKING: returns after the model's health check; an aborted weight-stationary launch is run again on the kernels that
+ * need no co-residency before the call returns.  Refused (non-zero, ape_last_error): bad kind / width, F < 1, bad starts,
+ * fp16 precision on the model, APE_MODEL_FF / APE_MODEL_IMUPOSE models, a capturing stream. */
+int ape_replay(ape_model_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+               int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+               void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream);
+
 /* kernel selection for A/B runs and tests; no effect on results beyond float32 summation order */
 int ape_model_set_kernel(ape_model_t* model, int32_t choice);
 int ape_model_set_precision(ape_model_t* model, int32_t precision);
