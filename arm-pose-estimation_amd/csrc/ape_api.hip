@@ -1270,6 +1270,7 @@ int ape_model_stats(const ape_model_t* m, ape_model_stats_t* out) {
 }
 
 static int replay_entry(ape_model_t* m, const ApeJournalEntry& e);
+static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_dev, int out_dtype, void* stream, unsigned long long mc_call);
 
 int ape_model_recover(ape_model_t* m) {
     if (!m) return fail(APE_ERR_INVALID_ARG, "recover: NULL model");
@@ -1552,6 +1553,22 @@ static int bank_launch_a_form(int route, int H, int KX, int n_cus, int S, bool c
     return BANK_A_TILE16;
 }
 
+// the subset frames' device workspaces (sized for the bank's S and n_mc); a pending subset frame of the bank can no longer be re-issued
+static void subset_free(ape_streams* b) {
+    if (b->sub_x) (void)hipFree(b->sub_x);
+    if (b->sub_y) (void)hipFree(b->sub_y);
+    if (b->sub_desc) (void)hipFree(b->sub_desc);
+    b->sub_x = b->sub_y = nullptr; b->sub_desc = nullptr; b->sub_n_mc = 0;
+    if (ape_model* m = b->model) {
+        int k = 0;
+        for (int i = 0; i < m->journal_n; ++i) {
+            if (m->journal[i].kind == ApeJournalEntry::SUBSET && m->journal[i].bank == b) { m->journal_overflow = true; continue; }
+            m->journal[k++] = m->journal[i];
+        }
+        m->journal_n = k;
+    }
+}
+
 int ape_streams_set_mc(ape_streams_t* b, int32_t n_mc, float dropout_p, uint64_t seed) {
     if (!b) return fail(APE_ERR_INVALID_ARG, "streams_set_mc: NULL bank");
     if (n_mc < 1 || (long long)n_mc * b->smooth > 4096)
@@ -1561,6 +1578,8 @@ int ape_streams_set_mc(ape_streams_t* b, int32_t n_mc, float dropout_p, uint64_t
     HIP_TRY(hipDeviceSynchronize());             // the rings may still be read by an earlier step
     b->n_mc = n_mc; b->mc = true; b->dropout_p = dropout_p; b->seed = seed; b->mc_calls = 0;
     b->frames = 0; b->steps = 0;
+    b->per_stream = false;
+    subset_free(b);
     hipError_t e = bank_alloc(b);
     if (e != hipSuccess) {
         // the old rings are gone and the new ones are incomplete: the bank stays unusable (every push / step refuses)
@@ -1643,6 +1662,9 @@ int ape_streams_destroy(ape_streams_t* b) {
     if (b->h_status) (void)hipHostFree(b->h_status);
     if (b->h_done) (void)hipHostFree(b->h_done);
     for (auto ev : b->prof_ev) if (ev) (void)hipEventDestroy(ev);
+    subset_free(b);                     // (drops the bank's pending subset frame as below)
+    for (auto ev : b->sub_ev) if (ev) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
+    if (b->sub_stage) (void)hipHostFree(b->sub_stage);
     if (ape_model* m = b->model) {      // pending steps of this bank can no longer be re-issued
         int k = 0;
         for (int i = 0; i < m->journal_n; ++i) {
@@ -1658,6 +1680,7 @@ int ape_streams_destroy(ape_streams_t* b) {
 int ape_streams_reset(ape_streams_t* b) {
     if (!b) return fail(APE_ERR_INVALID_ARG, "streams_reset: NULL bank");
     b->frames = 0; b->steps = 0;
+    b->per_stream = false;                       // every stream cold: the lockstep calls serve the bank again
     return APE_OK;
 }
 
@@ -1674,6 +1697,7 @@ static void next_slot(const ape_streams* b, size_t I, float** out, int* rep, siz
 int ape_streams_push_rows(ape_streams_t* b, int32_t kind, const float* rows_dev, void* stream) {
     if (!b || !rows_dev) return fail(APE_ERR_INVALID_ARG, "streams_push_rows: NULL argument");
     if (!b->xring) return fail(APE_ERR_NOT_READY, "streams_push_rows: the bank lost its rings in a failed ape_streams_set_mc");
+    if (b->per_stream) return fail(APE_ERR_NOT_READY, "streams_push_rows: the bank is in per-stream mode (subset frames); ape_streams_reset first");
     int width, I;
     const int big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
     kind &= ~APE_PARSE_BIG_ENDIAN;
@@ -1693,6 +1717,7 @@ int ape_streams_push_rows(ape_streams_t* b, int32_t kind, const float* rows_dev,
 int ape_streams_push_features(ape_streams_t* b, const float* xx_dev, void* stream) {
     if (!b || !xx_dev) return fail(APE_ERR_INVALID_ARG, "streams_push_features: NULL argument");
     if (!b->xring) return fail(APE_ERR_NOT_READY, "streams_push_features: the bank lost its rings in a failed ape_streams_set_mc");
+    if (b->per_stream) return fail(APE_ERR_NOT_READY, "streams_push_features: the bank is in per-stream mode (subset frames); ape_streams_reset first");
     const int I = b->model->dims.input_size;
     float* out; int rep; size_t rep_stride;
     next_slot(b, (size_t)I, &out, &rep, &rep_stride);
@@ -1723,6 +1748,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
     if (!b || !msg_dev) return fail(APE_ERR_INVALID_ARG, "streams_step: NULL argument");
     if (!b->xring || !b->yring || !b->y_new)
         return fail(APE_ERR_NOT_READY, "streams_step: the bank lost its rings in a failed ape_streams_set_mc");
+    if (b->per_stream) return fail(APE_ERR_NOT_READY, "streams_step: the bank is in per-stream mode (subset frames); ape_streams_reset first");
     if (b->frames == 0) return fail(APE_ERR_NOT_READY, "streams_step: no row pushed since the last reset");
     // the exchange-form selectors of include/ape_hip.h travel to the frame's LSTM launches unchanged (same bits whichever is set)
     const uint32_t diag_wt = flags & (APE_FLAG_ANY_PLACEMENT | APE_FLAG_IN_XCD_PLAIN | APE_FLAG_NO_XCD_CLASSES);
@@ -1970,6 +1996,7 @@ static inline double now_us() {
 int ape_streams_frame_host(ape_streams_t* b, int32_t kind, const float* rows_host, uint32_t flags, void* out_host,
                            int32_t out_dtype, void* stream) {
     if (!b || !rows_host || !out_host) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: NULL argument");
+    if (b->per_stream) return fail(APE_ERR_NOT_READY, "streams_frame_host: the bank is in per-stream mode (subset frames); ape_streams_reset first");
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: unknown dtype selector");
     if (flags & ~(uint32_t)APE_FLAG_NORMALIZE_INPUT) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: only NORMALIZE_INPUT is accepted");
     int width, I;
@@ -2104,6 +2131,142 @@ int ape_streams_profile_read(ape_streams_t* b, double* kernel_ms_sum, int32_t* l
     }
     *kernel_ms_sum = sum; *launches = b->prof_n;
     b->prof_n = 0;
+    return APE_OK;
+}
+
+// ---- subset frames: per-stream rows, slots and cold starts -----------------------------------------------------------
+// A frame names K distinct streams with one raw row each; every listed stream does what one Estimator.process_row does, the others stay
+// untouched.  Three launches: rows -> rings + compact windows (streams_subset.hip), the regressor over the K * n_mc compact rows
+// (lstm_forward_impl, x_ring = 0: every route applies), the indexed post-filter.  Window slot, stack slot and cold flags come from
+// per-stream counters on the host (per-stream mode), sent as one descriptor per entry.
+
+// validates a list of K stream indices of the bank: in range, distinct
+static int subset_check_list(const ape_streams* b, const int32_t* streams_host, int32_t K, const char* what) {
+    if (K < 0 || K > b->S) return fail(APE_ERR_INVALID_ARG, "%s: K=%d outside [0, S=%d]", what, K, b->S);
+    std::vector<char> seen((size_t)b->S, 0);
+    for (int j = 0; j < K; ++j) {
+        const int s = streams_host[j];
+        if (s < 0 || s >= b->S) return fail(APE_ERR_INVALID_ARG, "%s: stream index %d (entry %d) outside [0, %d)", what, s, j, b->S);
+        if (seen[s]) return fail(APE_ERR_INVALID_ARG, "%s: stream %d listed twice", what, s);
+        seen[s] = 1;
+    }
+    return APE_OK;
+}
+
+// the first subset call: per-stream counters seeded from the lockstep ones, so that a lockstep history carries on
+static void subset_enter(ape_streams* b) {
+    if (b->per_stream) return;
+    b->s_frames.assign((size_t)b->S, b->frames);
+    b->s_steps.assign((size_t)b->S, b->steps);
+    b->per_stream = true;
+}
+
+int ape_streams_reset_subset(ape_streams_t* b, const int32_t* streams_host, int32_t K) {
+    if (!b || !streams_host) return fail(APE_ERR_INVALID_ARG, "streams_reset_subset: NULL argument");
+    if (int rc = subset_check_list(b, streams_host, K, "streams_reset_subset")) return rc;
+    if (K == 0) return APE_OK;
+    subset_enter(b);
+    for (int j = 0; j < K; ++j) { b->s_frames[streams_host[j]] = 0; b->s_steps[streams_host[j]] = 0; }
+    return APE_OK;
+}
+
+// launches 2 and 3 of a subset frame over the compact windows and descriptors in the bank's workspace (also the journal's re-issue)
+static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_dev, int out_dtype, void* stream, unsigned long long mc_call) {
+    ape_model* m = b->model;
+    const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
+    const bool packed = (flags & APE_FLAG_PACKED_MSG) != 0 && b->smooth * b->n_mc > 1;
+    const bool drop = b->mc && b->dropout_p > 0.0f && m->dims.num_layers > 1;
+    if (int rc = lstm_forward_impl(m, b->sub_x, K * b->n_mc, b->T, (norm ? APE_FLAG_NORMALIZE_INPUT : 0u) | (drop ? APE_FLAG_DROPOUT_PHILOX : 0u),
+                                   nullptr, drop ? b->dropout_p : 0.0f, b->seed + mc_call, b->sub_y, stream, 0))
+        return rc;
+    StreamPostParams q{};
+    q.y_new = b->sub_y; q.yring = b->yring; q.msg = out_dev; q.tail = nullptr;
+    q.yy_m = norm ? m->stats + 2 * m->dims.input_size : nullptr;
+    q.yy_s = norm ? m->stats + 2 * m->dims.input_size + m->dims.output_size : nullptr;
+    memcpy(q.body, m->body, sizeof(q.body));
+    q.S = K; q.O = m->dims.output_size; q.W = layout_est_width(m->dims.target_layout); q.layout = m->dims.target_layout;
+    q.smooth = b->smooth; q.n_mc = b->n_mc;
+    q.msg_dtype = out_dtype; q.packed = packed ? 1 : 0;
+    q.part = b->post_part; q.part_cnt = b->post_cnt;     // (sized for S >= K entries)
+    hipError_t e = ape_launch_stream_post_subset(q, b->sub_desc, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset: post-filter launch failed: %s", hipGetErrorString(e));
+    return APE_OK;
+}
+
+int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
+                             uint32_t flags, void* out_dev, int32_t out_dtype, void* stream) {
+    if (!b || !rows_dev || !streams_host || !out_dev) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: NULL argument");
+    if (int rc = subset_check_list(b, streams_host, K, "streams_frame_subset")) return rc;
+    int width, I;
+    const int big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
+    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: unknown kind %d", kind);
+    ape_model* m = b->model;
+    if (I != m->dims.input_size)
+        return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: kind %d builds %d features, the model takes %d", kind & ~APE_PARSE_BIG_ENDIAN, I,
+                    m->dims.input_size);
+    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG))
+        return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: only NORMALIZE_INPUT and PACKED_MSG are accepted");
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: unknown dtype selector");
+    if (!b->xring || !b->yring) return fail(APE_ERR_NOT_READY, "streams_frame_subset: the bank lost its rings in a failed ape_streams_set_mc");
+    const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
+    if (norm && !m->has_stats) return fail(APE_ERR_NOT_READY, "streams_frame_subset: NORMALIZE_INPUT without norm stats");
+    if (!m->has_weights) return fail(APE_ERR_NOT_READY, "streams_frame_subset: weights not loaded");
+    if (b->inj_masks) return fail(APE_ERR_UNSUPPORTED, "streams_frame_subset: injected masks (test hook) are indexed by the lockstep rows");
+    HIP_TRY(hipSetDevice(m->dims.device));
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: the stream is capturing (the descriptors are staged per call)");
+    if (K == 0) return APE_OK;
+    // workspaces on the first subset call, sized for K = S
+    const size_t R = (size_t)b->S * b->n_mc;
+    if (b->sub_n_mc != b->n_mc || !b->sub_x) {
+        subset_free(b);
+        HIP_TRY(hipMalloc((void**)&b->sub_x, R * b->T * I * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&b->sub_y, R * m->dims.output_size * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&b->sub_desc, (size_t)b->S * sizeof(SubsetDesc)));
+        b->sub_n_mc = b->n_mc;
+    }
+    if (!b->sub_stage) {
+        HIP_TRY(hipHostMalloc((void**)&b->sub_stage, (size_t)APE_SUBSET_STAGES * b->S * sizeof(SubsetDesc), hipHostMallocDefault));
+        for (int i = 0; i < APE_SUBSET_STAGES; ++i) HIP_TRY(hipEventCreateWithFlags(&b->sub_ev[i], hipEventDisableTiming));
+    }
+    subset_enter(b);
+    // the descriptors into the next pinned slot -- once the copy that last read it has completed (frames go back to back, no host sync)
+    const int k = b->sub_next;
+    HIP_TRY(hipEventSynchronize(b->sub_ev[k]));
+    SubsetDesc* h = b->sub_stage + (size_t)k * b->S;
+    for (int j = 0; j < K; ++j) {
+        const int s = streams_host[j];
+        const long long f = b->s_frames[s], p = b->s_steps[s];
+        h[j].stream = s;
+        h[j].slot = (int)(f % b->T); h[j].cold = f == 0 ? 1 : 0;
+        h[j].pos = (int)(p % b->smooth); h[j].pcold = p == 0 ? 1 : 0;
+    }
+    HIP_TRY(hipMemcpyAsync(b->sub_desc, h, (size_t)K * sizeof(SubsetDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(b->sub_ev[k], st));
+    b->sub_next = (k + 1) % APE_SUBSET_STAGES;
+    SubsetRowsParams rp{};
+    rp.rows = rows_dev; rp.desc = b->sub_desc; rp.xring = b->xring; rp.xw = b->sub_x;
+    rp.K = K; rp.width = width; rp.kind = kind & ~APE_PARSE_BIG_ENDIAN; rp.big_endian = big_endian; rp.T = b->T; rp.I = I; rp.n_mc = b->n_mc;
+    hipError_t e = ape_launch_subset_rows(rp, st);
+    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset: row launch failed: %s", hipGetErrorString(e));
+    // the rows are in the rings: the counters move on whatever the regressor does (a failed launch is reported, the rows stay pushed)
+    for (int j = 0; j < K; ++j) { b->s_frames[streams_host[j]] += 1; b->s_steps[streams_host[j]] += 1; }
+    const unsigned long long mc_call = b->mc_calls++;
+    if (int rc = subset_regress_post(b, K, flags, out_dev, out_dtype, stream, mc_call)) return rc;
+    // journaled like a step: re-issued by ape_model_recover while it is the bank's newest frame (an older pending one is lost)
+    int n = 0;
+    for (int i = 0; i < m->journal_n; ++i) {
+        const ApeJournalEntry& o = m->journal[i];
+        if ((o.kind == ApeJournalEntry::SUBSET || o.kind == ApeJournalEntry::STEP) && o.bank == b) { m->journal_overflow = true; continue; }
+        m->journal[n++] = o;
+    }
+    m->journal_n = n;
+    ApeJournalEntry je{};
+    je.kind = ApeJournalEntry::SUBSET; je.out0 = out_dev; je.B = K; je.flags = flags; je.i2 = out_dtype; je.stream = stream;
+    je.bank = b; je.bank_mc_calls = mc_call;
+    journal_add(m, je);
     return APE_OK;
 }
 
@@ -2265,6 +2428,8 @@ static int replay_entry(ape_model_t* m, const ApeJournalEntry& e) {
             b->steps = e.bank_steps; b->mc_calls = e.bank_mc_calls;         // (frames unchanged: checked by the caller)
             return ape_streams_step(b, e.flags, e.out0, e.out1, e.i2, e.stream);
         }
+        case ApeJournalEntry::SUBSET:        // regressor + post-filter again over the windows and descriptors the frame left behind
+            return subset_regress_post(e.bank, e.B, e.flags, e.out0, e.i2, e.stream, e.bank_mc_calls);
     }
     return fail(APE_ERR_INVALID_ARG, "recover: unknown journal entry");
 }

@@ -89,4 +89,13 @@ int ape_debug_bank_buffer(ape_streams_t* b, int which, void* out_host, size_t by
     return APE_OK;
 }
 
+// the NN targets of a bank's newest subset frame, [K * n_mc, O] float32 in list order, copied to y_dev on `stream` (ape_streams_frame_subset
+// keeps them in its workspace): the Monte-Carlo contract of subset frames against ape_lstm_forward over the repeated compact windows
+int ape_debug_subset_targets(ape_streams_t* b, int K, float* y_dev, void* stream) {
+    if (!b || !y_dev || !b->sub_y || K < 1 || K > b->S) return APE_ERR_INVALID_ARG;
+    APE_DBG_TRY(hipMemcpyAsync(y_dev, b->sub_y, (size_t)K * b->n_mc * b->model->dims.output_size * sizeof(float), hipMemcpyDeviceToDevice,
+                               (hipStream_t)stream));
+    return APE_OK;
+}
+
 }  // extern "C"

@@ -253,6 +253,22 @@ struct ReplayMsgParams {
     int W, layout, smooth, n_mc, out_dtype;
 };
 
+// Subset frames of the stream bank (streams_subset.hip, ape_streams_frame_subset): one descriptor per listed stream, built on the host
+struct SubsetDesc {
+    int stream;          // the bank's stream index
+    int slot;            // window-ring slot of this frame's row (rows since the stream's cold start, mod T)
+    int cold;            // 1: first row since the cold start -- the row fills all T slots
+    int pos;             // smoothing-stack slot of this frame's prediction (predictions since the cold start, mod smooth)
+    int pcold;           // 1: first prediction since the cold start -- it fills the whole stack
+};
+struct SubsetRowsParams {
+    const float* rows;   // [K, width] raw rows, row j for desc[j]
+    const SubsetDesc* desc;
+    float* xring;        // the bank's [S, n_mc, T, I] window rings: only copy 0 of a stream is read and written
+    float* xw;           // [K * n_mc, T, I] compact windows, time-ordered, list order, each window n_mc times
+    int K, width, kind, big_endian, T, I, n_mc;
+};
+
 // Kernel arguments of the Monte-Carlo latency kernel (lstm_mc_small.hip): n_streams windows x n_mc dropout samples, dealt over the
 // 8 XCDs -- cluster c serves stream c / cps, sample rows [part * R, part * R + R) of it (part = c % cps).
 struct McSmallParams {
@@ -396,3 +412,6 @@ hipError_t ape_launch_msg_reduce(const MsgParams& p, hipStream_t stream);
 hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, int* seg_of, hipStream_t stream);
 hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t stream);
 hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream);
+hipError_t ape_launch_subset_rows(const SubsetRowsParams& p, hipStream_t stream);
+// the bank's post-filter over a list: p.S = K entries, y_new / msg in list order, stack slot and cold flag of entry j from desc[j]
+hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const SubsetDesc* desc, hipStream_t stream);

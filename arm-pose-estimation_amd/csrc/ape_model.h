@@ -12,7 +12,7 @@ struct ape_streams;
 // One compute call on a model since its last successful check, kept so that ape_model_recover can re-issue it on the
 // kernels that need no co-residency when a weight-stationary launch gave up (include/ape_hip.h, "Aborted launches").
 struct ApeJournalEntry {
-    enum Kind { FORWARD, FORWARD_HS, FK, MSG, INFER, STEP } kind;
+    enum Kind { FORWARD, FORWARD_HS, FK, MSG, INFER, STEP, SUBSET } kind;
     const void* in0;                 // x / preds / est
     const void* in1;                 // masks / h0
     const void* in2;                 // c0
@@ -23,7 +23,7 @@ struct ApeJournalEntry {
     float dropout_p;
     uint64_t seed;
     void* stream;
-    ape_streams* bank;               // STEP: the bank and its counters in front of the step
+    ape_streams* bank;               // STEP / SUBSET: the bank and its counters in front of the step (SUBSET: B = list length)
     long long bank_frames, bank_steps;
     unsigned long long bank_mc_calls;
 };
@@ -110,6 +110,8 @@ struct ape_model {
     ape_model_stats_t stats_counts{};
 };
 
+#define APE_SUBSET_STAGES 8      // pinned descriptor slots of a bank's subset frames
+
 struct ape_streams {
     ape_model* model = nullptr;
     int S = 0, T = 0, smooth = 0;
@@ -150,4 +152,15 @@ struct ape_streams {
     // where a host frame's time goes (ape_streams_frame_stats): a ring of the last 4096 frames' {launch, wait, copy} microseconds
     std::vector<float> fs_trace;
     uint64_t fs_frames = 0, fs_fallback = 0, fs_recovered = 0;
+    // subset frames (ape_streams_frame_subset): per-stream mode and its per-stream counters
+    bool per_stream = false;     // set by the first subset call; ape_streams_reset / set_mc return the bank to lockstep
+    std::vector<long long> s_frames, s_steps;   // [S] rows / predictions since each stream's cold start
+    float* sub_x = nullptr;      // [S * n_mc, T, I] compact windows of the newest subset frame (lazily, sized for K = S)
+    float* sub_y = nullptr;      // [S * n_mc, O] its targets
+    SubsetDesc* sub_desc = nullptr;   // [S] its descriptors on the device
+    int sub_n_mc = 0;            // n_mc the three were sized for
+    // host staging of the descriptors: a ring of pinned slots, each reused only once the copy out of it has completed
+    SubsetDesc* sub_stage = nullptr;  // [APE_SUBSET_STAGES][S]
+    hipEvent_t sub_ev[APE_SUBSET_STAGES] = {};
+    int sub_next = 0;
 };

@@ -80,8 +80,11 @@ __device__ __forceinline__ double wave_sum(double v) {
 // once more: its quaternions are the sign reference of the means (transformations.py:44).  Partial sums go to `p.part`, the last
 // workgroup of a stream to arrive (ticket in `p.part_cnt`, release / acquire fences around it) adds them in chunk order and
 // writes the message; the counter is left at zero.
-template <typename TMsg, bool SPLIT>
-__device__ inline void stream_post(const StreamPostParams& p, const int s, const int chunk, const int C) {
+// IDX (subset frames, streams_subset.hip): `s` is a position in a list of p.S entries -- its targets in y_new, its message row, its
+// partial sums -- and the stream whose stack it reads and writes, that stack's slot and cold flag come from d[s] instead of the uniform
+// p.pos / p.cold.  IDX = false is the bank's lockstep step, unchanged.
+template <typename TMsg, bool SPLIT, bool IDX = false>
+__device__ inline void stream_post(const StreamPostParams& p, const int s, const int chunk, const int C, const SubsetDesc* d = nullptr) {
 #pragma clang fp contract(off)
 
     __shared__ double rot[64][3][3];                        // per row of a 64-row chunk: rotated lower-arm bone, upper-arm bone, shoulder origin
@@ -121,9 +124,11 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
         if (act || refrow) {
             j = i / M; k = i - j * M;
             // the newest prediction sits in ring slot `pos`, the oldest one slot further
-            fresh = p.cold || j == p.smooth - 1;
-            const int slot = (p.pos + 1 + j) % p.smooth;
-            src = fresh ? p.y_new + ((size_t)s * M + k) * O : p.yring + (((size_t)s * p.smooth + slot) * M + k) * O;
+            // (IDX: read at the point of use, so that the lockstep form's object code stays what it was)
+            fresh = (IDX ? d[s].pcold : p.cold) || j == p.smooth - 1;
+            const int slot = ((IDX ? d[s].pos : p.pos) + 1 + j) % p.smooth;
+            src = fresh ? p.y_new + ((size_t)s * M + k) * O
+                        : p.yring + (((size_t)(IDX ? d[s].stream : s) * p.smooth + slot) * M + k) * O;
         }
         auto load = [&](int c) -> double {
             double v = (double)src[c];
@@ -155,7 +160,7 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
                 if (i == 0 && act && hips) { e0_s[6] = uo.x; e0_s[7] = uo.y; e0_s[8] = uo.z; }
             }
         } else if (act && fresh) {                          // keep the prediction for the next frames
-            float* dst = p.yring + (((size_t)s * p.smooth + (p.cold ? j : p.pos)) * M + k) * O;
+            float* dst = p.yring + (((size_t)(IDX ? d[s].stream : s) * p.smooth + ((IDX ? d[s].pcold : p.cold) ? j : (IDX ? d[s].pos : p.pos))) * M + k) * O;
 #pragma unroll
             for (int c = 0; c < 20; ++c)
                 if (c < O) dst[c] = src[c];
@@ -274,8 +279,9 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
 // per workgroup, the four role waves as above.  stream_post() gives every stream a workgroup of its own whose waves then run with ONE
 // active lane -- 4096 waves at 1024 streams, four per SIMD, each a chain of ~500 float64 instructions: the kernel was bound by their
 // issue slots (13.6 us at 1024 streams against 6 us for one stream).  Same device functions in the same order: bit-identical outputs.
-template <typename TMsg>
-__device__ inline void stream_post_wide(const StreamPostParams& p, const int s0) {
+// IDX: lane = list position (targets, message row), the stream's one ring slot from d
+template <typename TMsg, bool IDX = false>
+__device__ inline void stream_post_wide(const StreamPostParams& p, const int s0, const SubsetDesc* d = nullptr) {
 #pragma clang fp contract(off)
 
     __shared__ double rot[64][3][3];
@@ -320,7 +326,7 @@ __device__ inline void stream_post_wide(const StreamPostParams& p, const int s0)
             rot[lane][2][0] = uo.x; rot[lane][2][1] = uo.y; rot[lane][2][2] = uo.z;
         }
     } else if (act) {                                       // keep the prediction (the one ring slot of a bank without stacking)
-        float* dst = p.yring + (size_t)s * O;
+        float* dst = p.yring + (size_t)(IDX ? d[s].stream : s) * O;
 #pragma unroll
         for (int c = 0; c < 20; ++c)
             if (c < O) dst[c] = src[c];

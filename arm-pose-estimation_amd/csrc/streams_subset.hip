@@ -1,0 +1,111 @@
+// Subset frames of the stream bank (ape_streams_frame_subset): K listed streams, one raw row each, every stream with its
+// own window slot, stack slot and cold flags (a SubsetDesc per list entry, built on the host from per-stream counters).
+//
+// Launch 1 (here): row -> features (parse_device.h) -> copy 0 of the stream's window ring (all T slots on a cold start) AND the stream's
+// time-ordered window, n_mc times, into a compact [K * n_mc][T][I] workspace: the newest row from the block's LDS, the older ones from
+// the ring.  The regressor (launch 2) is lstm_forward_impl over those rows with x_ring = 0, every existing route unchanged.
+// Launch 3 (here): the bank's post-filter (stream_post_device.h) in its indexed form.
+#include "ape_internal.h"
+#include "../../include/ape_hip.h"
+#include "parse_device.h"
+#include "stream_post_device.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace ape_parsedev;
+using namespace ape_postdev;
+
+constexpr int SB_BLOCK = 128;                   // threads per workgroup
+constexpr int SB_ROWS = 8;                      // list entries per workgroup: a row's features are one dependent f64 chain (parse_rows.hip),
+                                                // few entries per block = more CUs busy and a short copy loop behind the chain
+constexpr int XW = 39;                          // feature row stride in LDS (odd: conflict-free per-thread rows)
+
+__global__ __launch_bounds__(SB_BLOCK) void ape_subset_rows_kernel(const SubsetRowsParams p) {
+    __shared__ float slab[SB_ROWS * 57];
+    __shared__ double xout[SB_ROWS * XW];
+    __shared__ int dsc[SB_ROWS][3];             // stream, ring slot, cold
+    const int tid = threadIdx.x;
+    const int r0 = (int)blockIdx.x * SB_ROWS;
+    const int n = min(SB_ROWS, p.K - r0);
+    for (int idx = tid; idx < n * p.width; idx += SB_BLOCK) {
+        const int rr = idx / p.width, c = idx - rr * p.width;
+        float v = p.rows[(size_t)r0 * p.width + idx];
+        if (p.big_endian) v = __builtin_bit_cast(float, __builtin_bswap32(__builtin_bit_cast(unsigned, v)));
+        slab[rr * 57 + c] = v;
+    }
+    if (tid < n) {
+        const SubsetDesc d = p.desc[r0 + tid];
+        dsc[tid][0] = d.stream; dsc[tid][1] = d.slot; dsc[tid][2] = d.cold;
+    }
+    __syncthreads();
+    if (tid < n) parse_row(slab + tid * 57, p.width, p.kind, xout + tid * XW);
+    __syncthreads();
+    // element (entry rr, step t, feature i) of the time-ordered window: step T-1 is the new row, step t < T-1 ring slot slot+1+t (mod T);
+    // consecutive threads = consecutive elements of one window, so every copy's stores are contiguous
+    const int T = p.T, I = p.I, per = T * I;
+    const size_t ring_stride = (size_t)p.n_mc * per;
+    for (int idx = tid; idx < n * per; idx += SB_BLOCK) {
+        const int rr = idx / per, rem = idx - rr * per, t = rem / I, i = rem - t * I;
+        const int slot = dsc[rr][1], cold = dsc[rr][2];
+        float* ring = p.xring + (size_t)dsc[rr][0] * ring_stride;          // copy 0 of the stream's windows
+        const float fresh = (float)xout[rr * XW + i];
+        float v;
+        if (cold) {                                 // first row since the cold start: every slot (estimator.py:96-97)
+            ring[rem] = fresh;
+            v = fresh;
+        } else if (t == T - 1) {
+            ring[slot * I + i] = fresh;
+            v = fresh;
+        } else {
+            int sl = slot + 1 + t;
+            if (sl >= T) sl -= T;
+            v = ring[sl * I + i];                   // (never the slot written above: sl != slot for t < T - 1)
+        }
+        float* w = p.xw + (size_t)(r0 + rr) * p.n_mc * per + rem;
+        for (int c = 0; c < p.n_mc; ++c) w[(size_t)c * per] = v;
+    }
+}
+
+// the post-filter's three forms over a list: workgroup / lane = list position (stream_post_device.h, IDX = true)
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_subset_post_kernel(const StreamPostParams p, const SubsetDesc* d) {
+    stream_post<TMsg, false, true>(p, (int)blockIdx.x, 0, 1, d);
+}
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_subset_post_split_kernel(const StreamPostParams p, const int chunks, const SubsetDesc* d) {
+    stream_post<TMsg, true, true>(p, (int)blockIdx.x / chunks, (int)blockIdx.x % chunks, chunks, d);
+}
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_subset_post_wide_kernel(const StreamPostParams p, const SubsetDesc* d) {
+    stream_post_wide<TMsg, true>(p, (int)blockIdx.x * 64, d);
+}
+
+}  // namespace
+
+hipError_t ape_launch_subset_rows(const SubsetRowsParams& p, hipStream_t stream) {
+    if (p.K < 1) return hipSuccess;
+    hipLaunchKernelGGL(ape_subset_rows_kernel, dim3((p.K + SB_ROWS - 1) / SB_ROWS), dim3(SB_BLOCK), 0, stream, p);
+    return hipGetLastError();
+}
+
+// the same choice of form as ape_launch_stream_post (fk.hip), with p.S = the list's length
+hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const SubsetDesc* d, hipStream_t stream) {
+    if (p.S < 1) return hipSuccess;
+    if (p.smooth == 1 && p.n_mc == 1 && p.S >= 8) {
+        const int wide = (p.S + 63) / 64;
+        if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_subset_post_wide_kernel<float>, dim3(wide), dim3(256), 0, stream, p, d);
+        else hipLaunchKernelGGL(ape_subset_post_wide_kernel<double>, dim3(wide), dim3(256), 0, stream, p, d);
+        return hipGetLastError();
+    }
+    const int chunks = ape_stream_post_chunks(p.smooth * p.n_mc);
+    if (p.part != nullptr && chunks > 1) {
+        if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_subset_post_split_kernel<float>, dim3(p.S * chunks), dim3(256), 0, stream, p, chunks, d);
+        else hipLaunchKernelGGL(ape_subset_post_split_kernel<double>, dim3(p.S * chunks), dim3(256), 0, stream, p, chunks, d);
+        return hipGetLastError();
+    }
+    if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_subset_post_kernel<float>, dim3(p.S), dim3(256), 0, stream, p, d);
+    else hipLaunchKernelGGL(ape_subset_post_kernel<double>, dim3(p.S), dim3(256), 0, stream, p, d);
+    return hipGetLastError();
+}

@@ -85,6 +85,9 @@ SIGNATURES = {
     "ape_replay": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32,
                              C.c_int32, C.c_float, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                              C.c_void_p]),
+    "ape_streams_reset_subset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "ape_streams_frame_subset": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p,
+                                           C.c_int32, C.c_void_p]),
     "ape_model_set_kernel": (C.c_int, [C.c_void_p, C.c_int32]),
     "ape_model_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "ape_model_check": (C.c_int, [C.c_void_p]),

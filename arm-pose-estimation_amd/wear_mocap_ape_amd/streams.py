@@ -108,8 +108,65 @@ class StreamBank:
     def _stream(self):
         return self._C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
 
-    def reset(self):
-        self._hip.check(self._hip.lib().ape_streams_reset(self._handle), "ape_streams_reset")
+    def reset(self, streams=None):
+        """cold start.  ``streams=None``: every stream, and the bank is back in lockstep mode; a sequence of distinct stream
+        indices: only those (``ape_streams_reset_subset``) -- the bank is then in per-stream mode, see ``frame``"""
+        if streams is None:
+            self._hip.check(self._hip.lib().ape_streams_reset(self._handle), "ape_streams_reset")
+            return
+        idx = self._indices(streams)
+        self._hip.check(self._hip.lib().ape_streams_reset_subset(self._handle, self._C.c_void_p(idx.ctypes.data), int(idx.shape[0])),
+                        "ape_streams_reset_subset")
+
+    def _indices(self, streams) -> np.ndarray:
+        a = np.asarray(streams)
+        if a.ndim != 1 or (a.size and not np.issubdtype(a.dtype, np.integer)):
+            raise UserWarning(f"streams must be a sequence of stream indices, got {streams!r}")
+        if a.size and (a.min() < 0 or a.max() >= self._n):
+            raise UserWarning(f"stream indices must lie in [0, {self._n})")
+        if np.unique(a).size != a.size:
+            raise UserWarning("stream indices must be distinct")
+        return np.ascontiguousarray(a, dtype=np.int32)
+
+    def frame(self, rows, streams, kind: int, big_endian: bool = False, datagrams: bool = False):
+        """One ``process_row`` for each listed stream (``ape_streams_frame_subset``): ``rows`` float32
+        ``[K, 55|28]`` (host array or device tensor), row j for stream ``streams[j]``; ``streams`` K distinct indices.
+        Streams not listed are untouched; each stream keeps its own window, stack and cold start (``reset(streams=...)``).
+        -> ``[K, 25]`` of the bank's dtype in list order, or with ``datagrams`` float32 ``[K, 25 + 6N]`` (N = smooth x
+        samples > 1): per listed stream the ``PoseEstPublisherUDP`` payload, as ``step_datagrams``.  The returned tensor is
+        the bank's own buffer, overwritten by the next call.  The first call puts the bank into per-stream mode: ``push_rows``,
+        ``push_features`` and ``step`` are refused until ``reset()``.  Monte-Carlo samples depend on a stream's list position."""
+        hip, C = self._hip, self._C
+        if kind not in hip.PARSE_SHAPES:
+            raise UserWarning(f"unknown row kind {kind}")
+        width = hip.PARSE_SHAPES[kind][0]
+        idx = self._indices(streams)
+        K = int(idx.shape[0])
+        if isinstance(rows, torch.Tensor):
+            rd = rows
+            if rd.is_cuda and rd.device != self._device:
+                raise UserWarning(f"rows live on {rd.device}, the bank on {self._device}")
+        else:
+            rd = torch.from_numpy(np.asarray(rows))
+        if rd.dtype != torch.float32 or tuple(rd.shape) != (K, width):
+            raise UserWarning(f"frame wants float32 rows [{K},{width}] for {K} streams, got {rd.dtype} {tuple(rd.shape)}")
+        rd = rd.to(self._device).contiguous()
+        n = self._smooth * self._n_mc
+        packed = datagrams and n > 1
+        if datagrams:
+            key, dtype, sel, w = "_sub_dgram", torch.float32, hip.F32, (25 + 6 * n if packed else 25)
+        else:
+            key, dtype, sel, w = "_sub_msg", self._dtype, self._sel, 25
+        if getattr(self, key, None) is None:
+            setattr(self, key, torch.empty((self._n, w), dtype=dtype, device=self._device))
+        out = getattr(self, key)[:K]
+        if K == 0:
+            return out
+        flags = self._flags | (hip.FLAG_PACKED_MSG if packed else 0)
+        k = kind | (hip.PARSE_BIG_ENDIAN if big_endian else 0)
+        hip.check(hip.lib().ape_streams_frame_subset(self._handle, k, C.c_void_p(rd.data_ptr()), C.c_void_p(idx.ctypes.data), K, flags,
+                                                     C.c_void_p(out.data_ptr()), sel, self._stream()), "ape_streams_frame_subset")
+        return out
 
     def check(self):
         """blocking health check of the model's launches (``ape_model_check``): the bank's outputs stay on the device,

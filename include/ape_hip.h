@@ -327,6 +327,32 @@ int ape_replay(ape_model_t* model, int32_t kind, const float* rows_dev, int32_t 
                int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
                void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream);
 
+/* subset frames of a stream bank (additive in ABI 7): each stream behaves like its own reference Estimator fed only
+ * the rows addressed to it -- its own window, its own smoothing stack, its own cold start (estimator.py:93-137).
+ * ape_streams_frame_subset: for each of K DISTINCT streams listed in streams_host (host memory), what process_row does with one row:
+ * parse it, push it onto that stream's window (the first row since its cold start pads the whole window), run the regressor (n_mc
+ * samples in Monte-Carlo mode), push the prediction onto that stream's stack (the first since its cold start pads the whole stack),
+ * reduce the stack to the message.  Streams not listed stay bit for bit untouched.
+ *   kind           ape_parse_rows kind, may carry APE_PARSE_BIG_ENDIAN
+ *   rows_dev       f32 [K, 55|28] on the device: row j belongs to stream streams_host[j]
+ *   flags          APE_FLAG_NORMALIZE_INPUT, APE_FLAG_PACKED_MSG
+ *   out_dev        [K, 25] of out_dtype in list order; with APE_FLAG_PACKED_MSG and N = smooth*n_mc > 1, [K, 25+6N] in the packed-row
+ *                  layout of ape_streams_step
+ * Monte-Carlo samples: those of ONE ape_lstm_forward(APE_FLAG_DROPOUT_PHILOX, dropout_p, seed + c) over the explicitly repeated
+ * windows [K*n_mc, T, I] in list order, c = the bank's call counter (one per frame) -- a stream's samples depend on its position in
+ * the list.  K = 0 is a no-op.  Asynchronous on `stream` (frames may be enqueued back to back); journaled like a step:
+ * ape_model_recover re-issues the newest subset frame of a bank (regressor and post-filter only) when called behind it, before the
+ * bank's next frame is enqueued.
+ * Per-stream mode: the first subset call (either entry) seeds per-stream counters from the bank's lockstep ones, so that a lockstep
+ * history carries on; from then on ape_streams_push_rows / push_features / step / frame_host are refused with APE_ERR_NOT_READY until
+ * ape_streams_reset (or ape_streams_set_mc) cold-starts every stream and returns the bank to lockstep.
+ * ape_streams_reset_subset: cold-starts the K listed streams only.
+ * Refused (non-zero, ape_last_error): NULL arguments, K < 0 or K > S, an index outside [0, S), a duplicate index, an unknown kind or
+ * one whose feature width does not match the model, a bank that lost its rings in a failed set_mc, a capturing stream. */
+int ape_streams_reset_subset(ape_streams_t* bank, const int32_t* streams_host, int32_t K);
+int ape_streams_frame_subset(ape_streams_t* bank, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
+                             uint32_t flags, void* out_dev, int32_t out_dtype, void* stream);
+
 /* kernel selection for A/B runs and tests; no effect on results beyond float32 summation order */
 int ape_model_set_kernel(ape_model_t* model, int32_t choice);
 int ape_model_set_precision(ape_model_t* model, int32_t precision);
