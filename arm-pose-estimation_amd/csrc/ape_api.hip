@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <cstring>
@@ -145,7 +146,7 @@ static int rest_kernel(int rest, int T, int gen2, int n_cus) {
     return PLAN_GEN1;
 }
 static int gen2_of(const ape_model* m) {
-    return (m->c32_ok && m->c32_on) ? 32 : (m->c16_ok && m->c32_on) ? (m->lv16_ok ? 48 : 16) : 0;
+    return (m->c32_ok && m->c32_split && m->c32_on) ? 32 : (m->c16_ok && m->c32_on) ? (m->lv16_ok ? 48 : 16) : 0;
 }
 
 static int auto_tile16_waves(const ape_dims_t* dims, int n_cus, int B, int T, bool cdrop, int gen2 = 0, bool wide = false) {
@@ -188,6 +189,66 @@ static void journal_add(ape_model* m, const ApeJournalEntry& e) {
     else m->journal_overflow = true;
 }
 static void journal_clear(ape_model* m) { m->journal_n = 0; m->journal_overflow = false; }
+
+// Split register image of lstm_cluster32.hip (the recurrent products on v_mfma_f32_32x32x16_f16): the same size and the same
+// [member 8][wave 4][group][lane 64][4 dwords] order as the f32 image (m->wcl32), one wave's 32 columns ordered gate * 8 + unit (column
+// m = lane & 31, half hh = lane >> 5).  The first `kx_f32` columns of Wcat = [W_ih | W_hh] (layer 0's input columns) stay f32, as in
+// the f32 image: group kb, dword j = Wcat[row][8 kb + 4 hh + j] * 2^S.  The remaining columns come in K = 16 slices s, two groups each:
+// group kx_f32 / 8 + 2 s holds hi = f16(W * 2^sw) and group + 1 lo = f16(W * 2^sw - hi), both in the 32x32x16 A-fragment order -- element
+// e = 0..7 of lane (m, hh) is k = kx_f32 + 16 s + 8 hh + e, element 2 d in the low half of dword d.  The power-of-two 2^sw puts max|W| of
+// the split columns in [2^14, 2^15), so every lo of a weight above max|W| * 2^-17 is a normal f16 and hi + lo = W * 2^sw to 2^-22 relative.
+// The kernel stores h * 2^APE_C32_HSHIFT in the same split (|h| <= 1), so its accumulators hold 2^S times the gate pre-activations,
+// S = sw + APE_C32_HSHIFT; it starts them at 2^S (b_ih + b_hh) and folds 2^-S into the gate constants.
+// Returns S, or -1 when the layer cannot take the split: a non-finite weight, or a scale outside [0, 64] / f32 input columns that would
+// overflow (the model then stays off this kernel).
+static int pack_c32_split(const float* w_ih, int in_l, const float* w_hh, int H, int KXl, int kx_f32, unsigned* out) {
+    auto wcat = [&](int row, int k) -> float {
+        if (k < KXl) return (k < in_l) ? w_ih[(size_t)row * in_l + k] : 0.0f;
+        return w_hh[(size_t)row * H + (k - KXl)];
+    };
+    const int K = KXl + H;
+    float wmax = 0.0f, xmax = 0.0f;
+    for (int row = 0; row < 4 * H; ++row)
+        for (int k = 0; k < K; ++k) {
+            const float v = wcat(row, k);
+            if (!std::isfinite(v)) return -1;
+            if (k < kx_f32) xmax = std::max(xmax, std::fabs(v));
+            else wmax = std::max(wmax, std::fabs(v));
+        }
+    int ex = 0;
+    if (wmax > 0.0f) (void)std::frexp(wmax, &ex);          // wmax in [2^(ex-1), 2^ex)
+    const int sw = (wmax > 0.0f) ? 15 - ex : 0;
+    const int S = sw + APE_C32_HSHIFT;
+    if (S < 0 || S > 64 || std::ldexp((double)xmax, S) >= 0x1p100) return -1;
+    const int NG = kx_f32 / 8 + 2 * ((K - kx_f32) / 16);
+    for (int mem = 0; mem < 8; ++mem)
+        for (int w = 0; w < 4; ++w)
+            for (int g = 0; g < NG; ++g)
+                for (int lane = 0; lane < 64; ++lane) {
+                    const int mcol = lane & 31, hh = lane >> 5;
+                    const int row = (mcol >> 3) * H + mem * 32 + w * 8 + (mcol & 7);
+                    unsigned* dst = out + ((((size_t)(mem * 4 + w) * NG) + g) * 64 + lane) * 4;
+                    if (g < kx_f32 / 8) {
+                        for (int j = 0; j < 4; ++j) {
+                            const float v = std::ldexp(wcat(row, 8 * g + 4 * hh + j), S);
+                            std::memcpy(&dst[j], &v, 4);
+                        }
+                        continue;
+                    }
+                    const int s = (g - kx_f32 / 8) / 2, lo = (g - kx_f32 / 8) & 1;
+                    for (int d = 0; d < 4; ++d) {
+                        unsigned short hw[2];
+                        for (int e2 = 0; e2 < 2; ++e2) {
+                            const float v = std::ldexp(wcat(row, kx_f32 + 16 * s + 8 * hh + 2 * d + e2), sw);     // exact: |v| < 2^15
+                            const _Float16 hi = (_Float16)v;
+                            const _Float16 part = lo ? (_Float16)(v - (float)hi) : hi;
+                            std::memcpy(&hw[e2], &part, 2);
+                        }
+                        dst[d] = (unsigned)hw[0] | ((unsigned)hw[1] << 16);
+                    }
+                }
+    return S;
+}
 
 extern "C" {
 
@@ -399,6 +460,8 @@ int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
         if (ape_cluster32_supported(H, L, m->KX) && f16v2_capacity(m->n_cus) > 0) {
             for (int l = 0; l < L && e == hipSuccess; ++l)
                 e = plan((void**)&m->wcl32[l], (size_t)4 * H * ((l == 0 ? m->KX : H) + H) * sizeof(float));
+            for (int l = 0; l < L && e == hipSuccess; ++l)         // the f16 hi / lo image of lstm_cluster32.hip (same size, pack_c32_split)
+                e = plan((void**)&m->wcl32s[l], (size_t)4 * H * ((l == 0 ? m->KX : H) + H) * sizeof(float));
             if (e == hipSuccess) e = ape_prepare_lstm_cluster32(H, L, m->KX);
             m->c32_ok = true;
             if (ape_upper32_supported(H, L, O) && !imupose) {       // shares the layer-1 register image, the exchange buffer and the flags
@@ -681,6 +744,17 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                             pc[((((size_t)(mem * 4 + w) * (NW / 4)) + i / 4) * 64 + lane) * 4 + (i % 4)] = v;
                         }
             HIP_TRY(hipMemcpy(m->wcl32[l], pc.data(), pc.size() * sizeof(float), hipMemcpyHostToDevice));
+        }
+        if (m->wcl32s[l] != nullptr) {
+            std::vector<unsigned> ps((size_t)8 * 4 * ((KXl + H) / 2) * 64);
+            const int S = pack_c32_split(w_ih, in_l, w_hh, H, KXl, l == 0 ? KXl : 0, ps.data());
+            if (l == 0) m->c32_split = true;
+            if (S < 0) m->c32_split = false;
+            else {
+                m->c32_scale[l] = std::ldexp(1.0f, S);
+                m->c32_descale[l] = std::ldexp(1.0f, -S);
+                HIP_TRY(hipMemcpy(m->wcl32s[l], ps.data(), ps.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+            }
         }
         if (m->up128_ok && l >= 1) {
             // lstm_upper128.hip: four members x 4 waves, a wave owns 8 units = 32 columns ordered gate * 8 + unit (v_mfma_f32_32x32x2_f32,
@@ -1014,7 +1088,10 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
                 ClusterParams c{};
                 c.x = (flags & APE_FLAG_BROADCAST_X) ? x_dev : x_dev + (size_t)b0 * T * m->dims.input_size;
                 c.y = y_dev + (size_t)b0 * m->dims.output_size;
-                for (int l = 0; l < L; ++l) { c.wcl[l] = m->wcl32[l]; c.bias[l] = m->bias[l]; }
+                for (int l = 0; l < L; ++l) {
+                    c.wcl[l] = reinterpret_cast<const float*>(m->wcl32s[l]); c.bias[l] = m->bias[l];
+                    c.gate_scale[l] = m->c32_scale[l]; c.gate_descale[l] = m->c32_descale[l];
+                }
                 c.w_out = m->w_out; c.b_out = m->b_out;
                 c.xx_m = m->stats; c.xx_s = m->stats + m->dims.input_size;
                 c.xx_r = m->stats + 2 * m->dims.input_size + 2 * m->dims.output_size;
@@ -2456,6 +2533,12 @@ int ape_debug_peek_pipe(ape_model_t* m, int first, unsigned* out, int n) {
     return APE_OK;
 }
 
+// internal: pack_c32_split for one layer (no GPU needed); `out` holds (KXl + H) / 2 * 8 * 4 * 64 dwords.  Returns S or -1.
+int ape_debug_pack_c32_split(const float* w_ih, int in_l, const float* w_hh, int H, int KXl, int kx_f32, unsigned* out) {
+    if (!w_ih || !w_hh || !out || H < 32 || H % 32 != 0 || KXl % 8 != 0 || kx_f32 % 8 != 0 || (KXl + H - kx_f32) % 16 != 0) return -1;
+    return pack_c32_split(w_ih, in_l, w_hh, H, KXl, kx_f32, out);
+}
+
 // internal: the batch split of lstm_forward for a device with `n_cus` CUs, no GPU needed.
 // out = {rows to the batch-tile kernel, row tiles per cluster, clusters per launch, cluster launches, cluster capacity}
 // `c32`: the model / call is eligible for the second-generation f32 kernel (what lstm_forward_impl passes for an eval-mode,
@@ -2553,7 +2636,7 @@ const char* ape_lstm_kernel_name(const ape_model_t* m, int32_t B, int32_t T) {
     if (m->kernel_choice == APE_KERNEL_AUTO && B > 4 && T >= 1) {
         if (2LL * tile16_wave_rows(m->n_cus) * auto_tile16_waves(&m->dims, m->n_cus, B, T, false, gen2_of(m), m->wide_cluster) > B) return m->kernel_name.c_str();
     }
-    if (m->c32_ok && m->c32_on && m->precision == APE_PRECISION_F32 && B > 512)      // (two instantiations: lstm_cluster32.hip on ENDS)
+    if (m->c32_ok && m->c32_split && m->c32_on && m->precision == APE_PRECISION_F32 && B > 512)      // (two instantiations: lstm_cluster32.hip on ENDS)
         return T <= APE_C32_ENDS_MAX_T ? "ape_lstm_cluster32<256, 2, 32, true>" : "ape_lstm_cluster32<256, 2, 32, false>";
     if (m->c16_ok && m->c32_on && m->precision == APE_PRECISION_F32) {
         const int k = rest_kernel(B, T, gen2_of(m), m->n_cus);

@@ -9,6 +9,7 @@
 #define APE_MAX_OUTPUT 32
 #define APE_TILE_ROWS 16          // windows per workgroup in the batch-tile LSTM kernel
 #define APE_XCC_WORDS 1024
+#define APE_C32_HSHIFT 15         // lstm_cluster32.hip: exchanged h values are split as f16 hi / lo of h * 2^15 (|h| <= 1: hi stays below 65504)
 #define APE_C32_ENDS_MAX_T 8      // lstm_cluster32.hip: windows of up to this many steps run the instantiation with the end forms
 #define APE_LDS_BYTES (160 * 1024) // LDS of a gfx950 CU: the dynamic-LDS limit every kernel instantiation is raised to, once
 // internal timing-only ablation switches: the diagnostic builds alone (make diag / make ablate) read them, outputs are wrong.  Their bit
@@ -97,6 +98,8 @@ struct ClusterParams {
     const double* fk_yy_s;
     double fk_body[9];                  // larm_vec, uarm_vec, uarm_orig_rh
     int fk_layout, fk_W, fk_est_dtype;
+    float gate_scale[APE_MAX_LAYERS];   // lstm_cluster32.hip: 2^S of layer l's split weights (its accumulators start at 2^S (b_ih + b_hh))
+    float gate_descale[APE_MAX_LAYERS]; //                     2^-S, folded into the gate constants
     unsigned* xcc_slots;                // APE_XCC_WORDS words, zero between launches.  [0,64): small-batch kernel, (0x10 | XCC id) of
                                         // its members; [64,192): fp16 v2 kernel's 8 class tickets, one per 64-byte line;
                                         // [192, ...): its per-workgroup XCD words

@@ -56,6 +56,10 @@ struct ape_model {
     float* wcl[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};
     void* wcl16[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};   // binary16 fragments of the fp16 variant
     float* wcl32[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};  // 32x32x2 fragments of the second-generation f32 cluster kernel
+    unsigned* wcl32s[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};  // ... the same image with the recurrent columns as f16 hi / lo (lstm_cluster32.hip)
+    float c32_scale[APE_MAX_LAYERS] = {1.0f, 1.0f, 1.0f};          // ... 2^S per layer (pack_c32_split)
+    float c32_descale[APE_MAX_LAYERS] = {1.0f, 1.0f, 1.0f};
+    bool c32_split = true;          // the loaded weights took the split (finite, scale in range); else the model stays off lstm_cluster32.hip
     float* wcls[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};   // the latency kernel's H/8-member form (two units per wave)
     char* hxs = nullptr;             // latency kernel: [256 B: launch number][granules {h, tag}: layer, parity, 4 rows, H units]
     size_t hxs_bytes = 0;

@@ -28,6 +28,9 @@
 //     XCD's L2, else sc1 write-through stores; flags always agent-scope stores; loads of handed-off bytes always sc1
 //     (MI355X guide G16 / visibility table row 1).  Bounded spins, sticky status word, self-cleaning -- as
 //     lstm_cluster_f16v2.hip, whose exchange this is.
+//   * split form (end): every product but layer 0's input columns runs on v_mfma_f32_32x32x16_f16 as
+//     W_hi h_hi + W_hi h_lo + W_lo h_hi of power-of-two scaled f16 hi / lo pairs (each product exact in the f32 accumulator), 96 cycles
+//     per K = 16 instead of 512; weights in the split image of ape_api.hip (pack_c32_split), h exchanged in the split layout.
 // Eval mode, last-step output (what the estimators' batched path and the benchmark use); dropout, all-steps output and
 // other shapes stay on the first-generation kernels.
 #include <type_traits>
@@ -63,6 +66,13 @@ __device__ __forceinline__ void mfma32(f32x16& acc, float w, float a) {
     else asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(a));
 }
 __device__ __forceinline__ void mfma_drain(f32x16& acc) { asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc)); }
+// v_mfma_f32_32x32x16_f16 on the same accumulator: the recurrent products.  A 32x32x2_f32 in front of it on the same, fully
+// overlapping accumulator needs no wait states (SrcC = the previous vDst exactly; hipcc's hazard recognizer pads none for the builtins)
+template <bool AG>
+__device__ __forceinline__ void mfma16(f32x16& acc, const u32x4& w, const u32x4& b) {
+    if constexpr (AG) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(b));
+    else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
+}
 
 // NB k-blocks of 8: acc += W (registers w[w0 ...]) x activations (LDS, one ds_read_b128 per block: this lane's window,
 // units 4 hh .. 4 hh + 3 of the block; `stride` floats between blocks), fragments fetched two blocks ahead.
@@ -80,6 +90,34 @@ __device__ __forceinline__ void span32(f32x16& acc, const float* __restrict__ sr
         mid(kb);
         a0 = a1;
         a1 = a2;
+    }
+}
+
+// NS K = 16 slices of h columns in the split form: acc += W_hi h_hi + W_hi h_lo + W_lo h_hi (each f16 x f16 product exact in the f32
+// accumulator).  Weights: groups w[g0 + 2 s] (hi) / w[g0 + 2 s + 1] (lo) in the A-fragment order (ape_api.hip, pack_c32_split).
+// Activations: the split exchange layout [block of 8 units][hi, lo][window 32][8 units as f16] (1 KiB per block); slice s = blocks
+// 2 s, 2 s + 1, lane (n, hh) reads block 2 s + hh -- `src` = this lane's hi fragment of slice 0, hi / lo one ds_read_b128 each
+// (conflict-free: 16 consecutive windows per lane group), fetched two slices ahead.  `mid(q)` runs with q = 2 s behind the second
+// MFMA of slice s and q = 2 s + 1 behind the third: the k-block numbering of the f32 form (one slice = two blocks of 8).
+template <int NS, bool AG, int NG, typename Mid>
+__device__ __forceinline__ void span16(f32x16& acc, const float* __restrict__ src, const u32x4 (&w)[NG], int g0, Mid&& mid) {
+    constexpr int SL = 2 * 2 * 32 * 4;      // floats per slice (two blocks)
+    u32x4 h0 = *reinterpret_cast<const u32x4*>(src), l0 = *reinterpret_cast<const u32x4*>(src + 128);
+    u32x4 h1 = (NS > 1) ? *reinterpret_cast<const u32x4*>(src + SL) : h0, l1 = (NS > 1) ? *reinterpret_cast<const u32x4*>(src + SL + 128) : l0;
+    u32x4 h2 = h1, l2 = l1;
+#pragma unroll
+    for (int s = 0; s < NS; ++s) {
+        if (s + 2 < NS) {
+            h2 = *reinterpret_cast<const u32x4*>(src + SL * (s + 2));
+            l2 = *reinterpret_cast<const u32x4*>(src + SL * (s + 2) + 128);
+        }
+        mfma16<AG>(acc, w[g0 + 2 * s], h0);
+        mfma16<AG>(acc, w[g0 + 2 * s], l0);
+        mid(2 * s);
+        mfma16<AG>(acc, w[g0 + 2 * s + 1], h0);
+        mid(2 * s + 1);
+        h0 = h1; l0 = l1;
+        h1 = h2; l1 = l2;
     }
 }
 
@@ -230,10 +268,13 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     //      lane (column m = lane & 31, half hh) = W[gate(m) * H + unit(m)][8 kb + 4 hh + j] with m = gate * 8 + local unit
     //      Only layer 0's input columns (16 registers) are loaded here: step 0 of layer 0 needs nothing else (h_{-1} = 0), and its hand-over
     //      then travels while the other 384 registers come in (`load_weights`, called behind it).
-    float w0[NW0];
-    float w1[NW1];
+    //      The image is the split one (pack_c32_split): layer 0's input columns as above times 2^S, every recurrent / layer-1 column as
+    //      K = 16 slices of f16 hi / lo A fragments, two groups of four registers each -- the same 400 registers.
+    float w0[4 * BX];
+    u32x4 w0h[NW0 / 4 - BX];
+    u32x4 w1[NW1 / 4];
     const f32x4* const s0 = reinterpret_cast<const f32x4*>(p.wcl[0]) + ((size_t)(member * 4 + wave) * (NW0 / 4)) * 64 + lane;
-    const f32x4* const s1 = reinterpret_cast<const f32x4*>(p.wcl[1]) + ((size_t)(member * 4 + wave) * (NW1 / 4)) * 64 + lane;
+    const u32x4* const s1 = reinterpret_cast<const u32x4*>(p.wcl[1]) + ((size_t)(member * 4 + wave) * (NW1 / 4)) * 64 + lane;
 #pragma unroll
     for (int i = 0; i < BX; ++i) {
         const f32x4 v = s0[i * 64];
@@ -241,15 +282,9 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     }
     auto load_weights = [&]() {
 #pragma unroll
-        for (int i = BX; i < NW0 / 4; ++i) {
-            const f32x4 v = s0[i * 64];
-            w0[4 * i] = v[0]; w0[4 * i + 1] = v[1]; w0[4 * i + 2] = v[2]; w0[4 * i + 3] = v[3];
-        }
+        for (int i = BX; i < NW0 / 4; ++i) w0h[i - BX] = reinterpret_cast<const u32x4*>(s0)[i * 64];
 #pragma unroll
-        for (int i = 0; i < NW1 / 4; ++i) {
-            const f32x4 v = s1[i * 64];
-            w1[4 * i] = v[0]; w1[4 * i + 1] = v[1]; w1[4 * i + 2] = v[2]; w1[4 * i + 3] = v[3];
-        }
+        for (int i = 0; i < NW1 / 4; ++i) w1[i] = s1[i * 64];
     };
     // accumulator start values (b_ih + b_hh) of this lane: registers 4 gate + j <-> unit member*32 + wave*8 + 4 hh + j; in LDS,
     // not in 32 more registers
@@ -259,7 +294,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         for (int gate = 0; gate < 4; ++gate) {
             f32x4 bv;
 #pragma unroll
-            for (int j = 0; j < 4; ++j) bv[j] = p.bias[l][gate * H + member * 32 + wave * 8 + 4 * hh + j];
+            for (int j = 0; j < 4; ++j) bv[j] = p.bias[l][gate * H + member * 32 + wave * 8 + 4 * hh + j] * p.gate_scale[l];   // (exact: 2^S)
             bias_s[((wave * L + l) * 4 + gate) * 64 + lane] = bv;
         }
     float cst[L][4];
@@ -364,17 +399,20 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     // ---- gates + cell update, lane-local: registers 4 gate + j = gate of unit 4 hh + j, window n ---------------------------
     // (two cells at a time, the plain arithmetic on float2 values: v_pk_mul / v_pk_add / v_pk_fma_f32 do both cells in one issue
     //  slot -- VALU work is serial with the MFMAs, tools/experiments/mfma_chain_rate.hip; the transcendentals stay one by one)
-    auto cell_update = [&](const f32x16& acc, float (&c_)[4], float (&hn)[4]) {
+    // (the accumulators hold 2^S times the pre-activations: 2^-S sits in the gate constants, a product with a power of two, exact --
+    //  the gate values are those of the unscaled sums)
+    auto cell_update = [&](const f32x16& acc, int l, float (&c_)[4], float (&hn)[4]) {
+        const float ks = -1.4426950408889634f * p.gate_descale[l], kt = -2.885390081777927f * p.gate_descale[l];
 #pragma unroll
         for (int j = 0; j < 4; j += 2) {
             typedef float f32x2 __attribute__((ext_vector_type(2)));
             auto exp2_2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_exp2f(v[0]), __builtin_amdgcn_exp2f(v[1])}; };
             auto rcp_2 = [](f32x2 v) { return f32x2{__builtin_amdgcn_rcpf(v[0]), __builtin_amdgcn_rcpf(v[1])}; };
             const f32x2 ai = {acc[j], acc[j + 1]}, af = {acc[4 + j], acc[5 + j]}, ag = {acc[8 + j], acc[9 + j]}, ao = {acc[12 + j], acc[13 + j]};
-            const f32x2 iv = rcp_2(1.0f + exp2_2(-1.4426950408889634f * ai));
-            const f32x2 fv = rcp_2(1.0f + exp2_2(-1.4426950408889634f * af));
-            const f32x2 gv = 2.0f * rcp_2(1.0f + exp2_2(-2.885390081777927f * ag)) - 1.0f;
-            const f32x2 ov = rcp_2(1.0f + exp2_2(-1.4426950408889634f * ao));
+            const f32x2 iv = rcp_2(1.0f + exp2_2(ks * ai));
+            const f32x2 fv = rcp_2(1.0f + exp2_2(ks * af));
+            const f32x2 gv = 2.0f * rcp_2(1.0f + exp2_2(kt * ag)) - 1.0f;
+            const f32x2 ov = rcp_2(1.0f + exp2_2(ks * ao));
             const f32x2 c = fv * f32x2{c_[j], c_[j + 1]} + iv * gv;
             c_[j] = c[0]; c_[j + 1] = c[1];
             const f32x2 h = ov * (2.0f * rcp_2(1.0f + exp2_2(-2.885390081777927f * c)) - 1.0f);
@@ -382,6 +420,31 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         }
     };
     const unsigned pub_off = (unsigned)((((member * 4 + wave) * MR + n) * 8 + 4 * hh) * sizeof(float));    // this lane's 16 bytes of a slice set
+    // The split exchange layout (what span16 reads): per block of 8 units [hi, lo][window][8 units as f16].  A lane's four fresh h
+    // (units 4 hh .. 4 hh + 3) become f16 hi / lo of h * 2^APE_C32_HSHIFT (exact scaling; |h| <= 1), two dwords each; one
+    // v_permlane32_swap per dword pair gives lanes 0-31 the hi of all eight units [own | upper's] and lanes 32-63 the lo [lower's | own]:
+    // one 16-byte store per lane, at window n of the hi (hh = 0) / lo (hh = 1) half.
+    // The LAST step of the top layer is read only by the head and is published as f32 at pub_off (the f32 layout [window][8 units]).
+    const unsigned pub_off_split = (unsigned)(((member * 4 + wave) * 2 * MR + hh * MR + n) * 16);
+    auto split_h = [&](const float (&h)[4]) -> u32x4 {
+        unsigned hw[2], lw[2];
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            const float a = h[2 * d] * (float)(1 << APE_C32_HSHIFT), b = h[2 * d + 1] * (float)(1 << APE_C32_HSHIFT);
+            const _Float16 ah = (_Float16)a, bh = (_Float16)b;
+            const _Float16 al = (_Float16)(a - (float)ah), bl = (_Float16)(b - (float)bh);
+            hw[d] = (unsigned)__builtin_bit_cast(unsigned short, ah) | ((unsigned)__builtin_bit_cast(unsigned short, bh) << 16);
+            lw[d] = (unsigned)__builtin_bit_cast(unsigned short, al) | ((unsigned)__builtin_bit_cast(unsigned short, bl) << 16);
+        }
+        u32x4 r;
+#pragma unroll
+        for (int d = 0; d < 2; ++d) {
+            const auto sw = __builtin_amdgcn_permlane32_swap(hw[d], lw[d], false, false);
+            r[d] = sw[0];
+            r[2 + d] = sw[1];
+        }
+        return r;
+    };
 
     // ---- step 0 of layer 0 IN FRONT of the bulk of the weights: its product is the input span alone (4 k-blocks, 16 weight registers),
     //      and its hand-over -- store, acknowledgement, flag, the peers' flags -- would otherwise be the first thing the launch waits
@@ -396,14 +459,13 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             const f32x4 bv = bias_s[((wave * L + 0) * 4 + gate) * 64 + lane];
             acc[4 * gate] = bv[0]; acc[4 * gate + 1] = bv[1]; acc[4 * gate + 2] = bv[2]; acc[4 * gate + 3] = bv[3];
         }
-        span32<BX, false, NW0>(acc, xin + n * SX + hh * 4, 8, w0, 0, [&](int) {});
+        span32<BX, false, 4 * BX>(acc, xin + n * SX + hh * 4, 8, w0, 0, [&](int) {});
         mfma_drain(acc);
         float h0[4];
-        cell_update(acc, cst[0], h0);
-        const u32x4 hv = {__builtin_bit_cast(unsigned, h0[0]), __builtin_bit_cast(unsigned, h0[1]),
-                          __builtin_bit_cast(unsigned, h0[2]), __builtin_bit_cast(unsigned, h0[3])};
-        if (in_l2) __builtin_amdgcn_raw_buffer_store_b128(hv, hx_rsrc, hx_base(0, 0) + pub_off, 0, 0);
-        else __builtin_amdgcn_raw_buffer_store_b128(hv, hx_rsrc, hx_base(0, 0) + pub_off, 0, 16 /* sc1: write-through */);
+        cell_update(acc, 0, cst[0], h0);
+        const u32x4 hv = split_h(h0);
+        if (in_l2) __builtin_amdgcn_raw_buffer_store_b128(hv, hx_rsrc, hx_base(0, 0) + pub_off_split, 0, 0);
+        else __builtin_amdgcn_raw_buffer_store_b128(hv, hx_rsrc, hx_base(0, 0) + pub_off_split, 0, 16 /* sc1: write-through */);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) __hip_atomic_store(flags_of + member * 4 + wave, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("" ::: "memory");
@@ -582,10 +644,10 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
                 const f32x4 bv = bias_s[((wave * L + l) * 4 + gate) * 64 + lane];
                 acc[4 * gate] = bv[0]; acc[4 * gate + 1] = bv[1]; acc[4 * gate + 2] = bv[2]; acc[4 * gate + 3] = bv[3];
             }
-            const int frag = n * 8 + hh * 4;                      // this lane's 16 bytes inside a [window][8 units] block
+            const int frag = hh * 2 * MR * 4 + n * 4;             // this lane's hi fragment of slice 0: block hh, window n
             if constexpr (l == 0) {
-                span32<BX, false, NW0>(acc, xin + n * SX + hh * 4, 8, w0, 0, [&](int q) { mid(q); });
-                if (ST || t > 0) span32<BH, false, NW0>(acc, hb0 + ((t - 1) & 1) * HL + frag, MR * 8, w0, 4 * BX, [&](int q) { mid(BX + q); });
+                span32<BX, false, 4 * BX>(acc, xin + n * SX + hh * 4, 8, w0, 0, [&](int q) { mid(q); });
+                if (ST || t > 0) span16<BH / 2, false, NW0 / 4 - BX>(acc, hb0 + ((t - 1) & 1) * HL + frag, w0h, 0, [&](int q) { mid(BX + q); });
             } else if constexpr (MODE == 3) {
                 // input span: the common hooks (flag owed at QF, the look for the NEXT section at QP) + the look at the OWN layer's flags at
                 // QO, the judge four blocks on, the gather behind it; outside the steady state a second look twelve blocks after the first
@@ -593,7 +655,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
                 static_assert(QO2 + 4 + NDMA <= QP && QP < BH, "the own gather's hooks sit in front of the look for the next section");
                 unsigned pk = (unsigned)t;
                 bool got1 = false, got2 = false;
-                span32<BH, true, NW1>(acc, hb0 + (t & 1) * HL + frag, MR * 8, w1, 0, [&](int q) {
+                span16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) {
                     mid(q);
                     if (q == QO) look_issue(look_lds, look_voff, fl_desc, fl_off + (unsigned)(l * NFL * sizeof(unsigned)));
                     if (q == QO + 3) {
@@ -634,10 +696,10 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
                 if (ST) { lc_top[l] += __builtin_amdgcn_s_memtime() - lc_t0; lc_n[l] += 1u; }
 #endif
                 if (ctl[0] != 0) return false;
-                span32<BH, true, NW1>(acc, hb1 + frag, MR * 8, w1, 4 * BH, [&](int q) { mid(BH + q); });
+                span16<BH / 2, true, NW1 / 4>(acc, hb1 + frag, w1, BH, [&](int q) { mid(BH + q); });
             } else {
-                span32<BH, true, NW1>(acc, hb0 + (t & 1) * HL + frag, MR * 8, w1, 0, [&](int q) { mid(q); });
-                if (ST || t > 0) span32<BH, true, NW1>(acc, hb1 + frag, MR * 8, w1, 4 * BH, [&](int q) { mid(BH + q); });
+                span16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) { mid(q); });
+                if (ST || t > 0) span16<BH / 2, true, NW1 / 4>(acc, hb1 + frag, w1, BH, [&](int q) { mid(BH + q); });
                 // (a section without a recurrent span -- step 0 of the long-window instantiation -- issues its look at block QP and never
                 //  reaches the judge at QJ.  With a register destination that look stayed in flight over whatever hipcc gave the register to
                 //  next: 2-4 % of the launches beside a memory-bound kernel returned a 32-window cluster off by 1e-2 at step 0 of layer 1,
@@ -648,7 +710,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             if (ST) { dgc[l][0] += c1 - c0; dgc[l][1] += c2 - c1; dgc[l][2] += c3 - c2; }
 #endif
             mfma_drain(acc);
-            cell_update(acc, cst[l], hnew);
+            cell_update(acc, l, cst[l], hnew);
         }
         if (abort_word != 0) return false;                        // (a wave of this workgroup gave up in a blocking wait)
         if (!ST && pend_idx >= 0) {                               // (a section too short to reach block QF, or an idle one)
@@ -673,9 +735,11 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         // ---- publish: this lane's four fresh h values are one 16-byte piece of the exchange layout ----------------------------
         //      (exactly ONE store instruction per wave and section: the counted wait at the top of the next section relies on it)
         {
-            const u32x4 hv = {__builtin_bit_cast(unsigned, hnew[0]), __builtin_bit_cast(unsigned, hnew[1]),
-                              __builtin_bit_cast(unsigned, hnew[2]), __builtin_bit_cast(unsigned, hnew[3])};
-            const unsigned off = active ? hx_base(l, t & 1) + pub_off : 0x80000000u;
+            const bool head_only = (l == L - 1) && !ST && t == T - 1;        // h^{L-1}_{T-1}: f32 for the head
+            const u32x4 hs = split_h(hnew);
+            const u32x4 hv = head_only ? u32x4{__builtin_bit_cast(unsigned, hnew[0]), __builtin_bit_cast(unsigned, hnew[1]),
+                                               __builtin_bit_cast(unsigned, hnew[2]), __builtin_bit_cast(unsigned, hnew[3])} : hs;
+            const unsigned off = active ? hx_base(l, t & 1) + (head_only ? pub_off : pub_off_split) : 0x80000000u;
             if (in_l2) __builtin_amdgcn_raw_buffer_store_b128(hv, hx_rsrc, off, 0, 0);
             else __builtin_amdgcn_raw_buffer_store_b128(hv, hx_rsrc, off, 0, 16 /* sc1: write-through */);
             if (active) {
