@@ -1,0 +1,439 @@
+// The estimator without a regressor (WatchPhoneUarm, reference estimate/watch_phone_uarm.py:10-108): a frame is the
+// feature builder (parse_row), the two calibrated 6D columns of the features turned into quaternions, the smoothing stack
+// (estimator.py:112-118) and the message (Estimator.msg_from_pred with est_to_ori_cal_larm_uarm, compose_msg.py:82-108).
+//
+// ape_fk_bank_kernel         one frame for K listed streams of a bank (lane per stream): parse, the row's two quaternions into the
+//                            stream's ring slot (all `smooth` slots on a cold start), the ring reduced in stack order to the message
+// ape_fk_replay_rows_kernel  every frame of recordings: the frame's two quaternions into an [F, 8] workspace, once
+// ape_fk_replay_msg_kernel   ... and per frame the stack, row i = frame max(seg, f - smooth + 1 + i), to the message
+//
+// The ring keeps quaternions (8 doubles a row), not the 6D columns: a row's 6D -> quaternion chain runs once, with the same function on
+// the same inputs, so the bits are those of recomputing it.  Lane per stream, not a workgroup per stream: one-lane waves of float64
+// chains are issue-bound (stream_post_wide).  No co-residency: no journal, no recovery.
+// float64 with separate roundings for a * b + c, like numpy: contraction is off in this file.
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "ape_internal.h"
+#include "../../include/ape_hip.h"
+#include "parse_device.h"
+#include "stream_post_device.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace ape_postdev;
+
+constexpr int FK_BLOCK = 64;          // lanes = streams (frames); one wave per workgroup spreads the chains over the CUs
+constexpr int FK_WIDTH = 55;          // APE_PARSE_WATCH_PHONE_UARM message
+constexpr int FK_STAGES = 4;          // pinned descriptor slots (frames go back to back)
+
+struct FkDesc { int stream, pos, cold, pad; };
+
+struct FkBankParams {
+    const float* rows;                // [K, 55]
+    const FkDesc* desc;               // [K] or nullptr: lane j = stream j, uniform pos / cold
+    double* ring;                     // [S, smooth, 8]
+    void* out;                        // [K, 25]
+    unsigned* done;                   // host frames: a word per lane written behind its message (nullptr: none)
+    unsigned done_val;
+    int K, smooth, pos, cold, big_endian;
+    double body[9];
+};
+
+struct FkReplayParams {
+    const float* rows;                // [F, 55]
+    const int* seg_of;                // [F]
+    double* ws;                       // [F, 8]
+    void* out;                        // [F, 25]
+    int F, smooth, big_endian;
+    double body[9];
+};
+
+// raw message -> the row's lower-arm and upper-arm quaternions (watch_phone_uarm.py:64-108: features 13:19 and 32:38)
+__device__ inline void row_quats(const float* src, int big_endian, double* q8) {
+    float r[FK_WIDTH];
+#pragma unroll
+    for (int c = 0; c < FK_WIDTH; ++c) {
+        float v = src[c];
+        if (big_endian) v = __builtin_bit_cast(float, __builtin_bswap32(__builtin_bit_cast(unsigned, v)));
+        r[c] = v;
+    }
+    double xx[38];
+    ape_parsedev::parse_row(r, FK_WIDTH, APE_PARSE_WATCH_PHONE_UARM, xx);
+    const Quat lq = six_drr_to_quat(xx + 13), uq = six_drr_to_quat(xx + 32);
+    put_q(q8, lq);
+    put_q(q8 + 4, uq);
+}
+
+// the stack (row i via `row(i)`, oldest first) -> message: for N > 1 the mean sequence of ape_replay_msg_kernel (row 0 times 1/N, every
+// further row added with +-1/N by the strict `dot < 0.0` rule against row 0), for N == 1 est row 0 (estimate_joints.py:74-92)
+template <typename Row>
+__device__ inline void stack_msg(int N, Row row, const double* body, double* m) {
+    const double* q0 = row(0);
+    double out_q[3][4] = {}, orig_mean[9] = {}, e0[21] = {};
+    if (N > 1) {
+        const double wgt = 1.0 / (double)N;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const double r0 = q0[4 * q], r1 = q0[4 * q + 1], r2 = q0[4 * q + 2], r3 = q0[4 * q + 3];
+            double a0 = r0 * wgt, a1 = r1 * wgt, a2 = r2 * wgt, a3 = r3 * wgt;
+            for (int i = 1; i < N; ++i) {
+                const double* qi = row(i) + 4 * q;
+                const double d = fma(qi[3], r3, fma(qi[2], r2, fma(qi[1], r1, qi[0] * r0)));
+                const double sg = d < 0.0 ? -wgt : wgt;
+                a0 = a0 + qi[0] * sg; a1 = a1 + qi[1] * sg; a2 = a2 + qi[2] * sg; a3 = a3 + qi[3] * sg;
+            }
+            const double nrm = sqrt(a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3);
+            out_q[q][0] = a0 / nrm; out_q[q][1] = a1 / nrm; out_q[q][2] = a2 / nrm; out_q[q][3] = a3 / nrm;
+        }
+    } else {
+        const Quat lq{q0[0], q0[1], q0[2], q0[3]}, uq{q0[4], q0[5], q0[6], q0[7]};
+        const Vec3 lo = vadd(qrot(uq, Vec3{body[3], body[4], body[5]}), Vec3{body[6], body[7], body[8]});
+        const Vec3 ho = vadd(qrot(lq, Vec3{body[0], body[1], body[2]}), lo);
+        put_v(e0, ho); put_v(e0 + 3, lo); put_q(e0 + 6, lq); put_q(e0 + 10, uq);
+    }
+    finish_msg(APE_LAYOUT_ORI_CAL_LARM_UARM, N, out_q, orig_mean, e0, body, m);
+}
+
+template <typename TMsg>
+__global__ __launch_bounds__(FK_BLOCK) void ape_fk_bank_kernel(const FkBankParams p) {
+    const int j = blockIdx.x * FK_BLOCK + threadIdx.x;
+    if (j >= p.K) return;
+    const int s = p.desc ? p.desc[j].stream : j;
+    const int pos = p.desc ? p.desc[j].pos : p.pos;
+    const bool cold = p.desc ? p.desc[j].cold != 0 : p.cold != 0;
+    const int S8 = p.smooth * 8;
+    double* ring = p.ring + (size_t)s * S8;
+    double q8[8];
+    row_quats(p.rows + (size_t)j * FK_WIDTH, p.big_endian, q8);
+    for (int t = cold ? 0 : pos; t < (cold ? p.smooth : pos + 1); ++t)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) ring[t * 8 + c] = q8[c];
+    // stack row i (oldest first) sits in slot (pos + 1 + i) mod smooth: the newest in `pos`, on a cold start copies everywhere
+    double m[25];
+    stack_msg(p.smooth, [&](int i) -> const double* { int t = pos + 1 + i; if (t >= p.smooth) t -= p.smooth; return ring + t * 8; },
+              p.body, m);
+    TMsg* dst = static_cast<TMsg*>(p.out) + (size_t)j * 25;
+#pragma unroll
+    for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
+    if (p.done != nullptr) {                                   // host frames: the message first (system scope), then the word
+        __threadfence_system();
+        __hip_atomic_store(p.done + j, p.done_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
+__global__ __launch_bounds__(FK_BLOCK) void ape_fk_replay_rows_kernel(const FkReplayParams p) {
+    const int f = blockIdx.x * FK_BLOCK + threadIdx.x;
+    if (f >= p.F) return;
+    row_quats(p.rows + (size_t)f * FK_WIDTH, p.big_endian, p.ws + (size_t)f * 8);
+}
+
+template <typename TMsg>
+__global__ __launch_bounds__(FK_BLOCK) void ape_fk_replay_msg_kernel(const FkReplayParams p) {
+    const int f = blockIdx.x * FK_BLOCK + threadIdx.x;
+    if (f >= p.F) return;
+    const int seg = p.seg_of[f];
+    double m[25];
+    stack_msg(p.smooth, [&](int i) -> const double* { int h = f - p.smooth + 1 + i; if (h < seg) h = seg; return p.ws + (size_t)h * 8; },
+              p.body, m);
+    TMsg* dst = static_cast<TMsg*>(p.out) + (size_t)f * 25;
+#pragma unroll
+    for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
+}
+
+unsigned blocks_for(long long n) { return (unsigned)((n + FK_BLOCK - 1) / FK_BLOCK); }
+
+int ffail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return ape_set_error(code, buf);
+}
+
+#define FK_TRY(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t _e = (expr);                                                                        \
+        if (_e != hipSuccess) return ffail(APE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+int check_device(int32_t device, const char* what) {
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
+        (void)hipGetLastError();
+        return ffail(APE_ERR_NO_DEVICE, "%s: no HIP device visible: libape_hip has no CPU fallback", what);
+    }
+    if (device < 0 || device >= n) return ffail(APE_ERR_INVALID_ARG, "%s: device %d of %d", what, device, n);
+    hipDeviceProp_t prop;
+    FK_TRY(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return ffail(APE_ERR_NO_DEVICE, "%s: device %d is %s; this library is built for gfx950 only", what, device, prop.gcnArchName);
+    return APE_OK;
+}
+
+int check_kind(int32_t kind, const char* what) {
+    if ((kind & ~APE_PARSE_BIG_ENDIAN) != APE_PARSE_WATCH_PHONE_UARM)
+        return ffail(APE_ERR_INVALID_ARG, "%s: kind %d: the forward-kinematics estimator reads APE_PARSE_WATCH_PHONE_UARM rows only", what, kind);
+    return APE_OK;
+}
+
+int check_capture(hipStream_t st, const char* what) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    FK_TRY(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return ffail(APE_ERR_INVALID_ARG, "%s: the stream is capturing (ring positions and stream lists are staged per call)", what);
+    return APE_OK;
+}
+
+template <typename P, typename K32, typename K64>
+hipError_t launch_typed(K32 k32, K64 k64, int out_dtype, long long n, const P& p, hipStream_t st) {
+    if (out_dtype == APE_F32) hipLaunchKernelGGL(k32, dim3(blocks_for(n)), dim3(FK_BLOCK), 0, st, p);
+    else hipLaunchKernelGGL(k64, dim3(blocks_for(n)), dim3(FK_BLOCK), 0, st, p);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// ---- the bank: ring on the device, per-stream row counts since the cold start on the host --------------------------------------
+struct ape_fk_bank {
+    int S = 0, smooth = 1, device = 0;
+    double body[9] = {};
+    double* ring = nullptr;            // [S, smooth, 8]
+    FkDesc* desc = nullptr;            // [S] device descriptors of the current frame
+    // uniform: every stream has seen `ucount` rows since its cold start (lockstep history) -- frames then carry pos / cold as arguments
+    bool uniform = true;
+    long long ucount = 0;
+    std::vector<long long> cnt;        // per stream, once the history is not uniform
+    FkDesc* stage = nullptr;           // FK_STAGES pinned slots of S descriptors
+    hipEvent_t ev[FK_STAGES] = {};
+    int next = 0;
+    float* h_rows = nullptr;           // frame_host: pinned rows, message words and completion words
+    void* h_out = nullptr;
+    unsigned* h_done = nullptr;
+    unsigned done_val = 0;
+};
+
+namespace {
+
+void bank_free(ape_fk_bank* b) {
+    if (b->ring) (void)hipFree(b->ring);
+    if (b->desc) (void)hipFree(b->desc);
+    if (b->stage) (void)hipHostFree(b->stage);
+    for (int i = 0; i < FK_STAGES; ++i)
+        if (b->ev[i]) (void)hipEventDestroy(b->ev[i]);
+    if (b->h_rows) (void)hipHostFree(b->h_rows);
+    if (b->h_out) (void)hipHostFree(b->h_out);
+    if (b->h_done) (void)hipHostFree(b->h_done);
+    delete b;
+}
+
+int check_list(const ape_fk_bank* b, const int32_t* streams_host, int32_t K, const char* what) {
+    if (K < 0 || K > b->S) return ffail(APE_ERR_INVALID_ARG, "%s: K=%d outside [0, S=%d]", what, K, b->S);
+    if (!streams_host) {
+        if (K != b->S) return ffail(APE_ERR_INVALID_ARG, "%s: no stream list: K=%d must be S=%d", what, K, b->S);
+        return APE_OK;
+    }
+    std::vector<char> seen((size_t)b->S, 0);
+    for (int j = 0; j < K; ++j) {
+        const int s = streams_host[j];
+        if (s < 0 || s >= b->S) return ffail(APE_ERR_INVALID_ARG, "%s: stream index %d (entry %d) outside [0, %d)", what, s, j, b->S);
+        if (seen[s]) return ffail(APE_ERR_INVALID_ARG, "%s: stream %d listed twice", what, s);
+        seen[s] = 1;
+    }
+    return APE_OK;
+}
+
+void leave_uniform(ape_fk_bank* b) {
+    if (!b->uniform) return;
+    b->cnt.assign((size_t)b->S, b->ucount);
+    b->uniform = false;
+}
+
+// one frame for K streams (streams_host nullptr: all S in order) on `st`; the counters move on once the launch is enqueued
+int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* streams_host, int32_t K, void* out, int32_t out_dtype,
+               hipStream_t st, unsigned* done, const char* what) {
+    FkBankParams p{};
+    p.rows = rows; p.ring = b->ring; p.out = out; p.K = K; p.smooth = b->smooth;
+    p.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
+    p.done = done; p.done_val = b->done_val;
+    memcpy(p.body, b->body, sizeof(p.body));
+    if (!streams_host && b->uniform) {
+        p.desc = nullptr;
+        p.pos = (int)(b->ucount % b->smooth); p.cold = b->ucount == 0 ? 1 : 0;
+    } else {
+        if (streams_host) leave_uniform(b);
+        // the descriptors into the next pinned slot -- once the copy that last read it has completed
+        const int k = b->next;
+        FK_TRY(hipEventSynchronize(b->ev[k]));
+        FkDesc* h = b->stage + (size_t)k * b->S;
+        for (int j = 0; j < K; ++j) {
+            const int s = streams_host ? streams_host[j] : j;
+            const long long c = b->cnt[s];
+            h[j] = FkDesc{s, (int)(c % b->smooth), c == 0 ? 1 : 0, 0};
+        }
+        FK_TRY(hipMemcpyAsync(b->desc, h, (size_t)K * sizeof(FkDesc), hipMemcpyHostToDevice, st));
+        FK_TRY(hipEventRecord(b->ev[k], st));
+        b->next = (k + 1) % FK_STAGES;
+        p.desc = b->desc;
+    }
+    hipError_t e = launch_typed(ape_fk_bank_kernel<float>, ape_fk_bank_kernel<double>, out_dtype, K, p, st);
+    if (e != hipSuccess) return ffail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+    if (p.desc == nullptr) b->ucount += 1;
+    else if (streams_host) for (int j = 0; j < K; ++j) b->cnt[streams_host[j]] += 1;
+    else for (int j = 0; j < K; ++j) b->cnt[j] += 1;
+    return APE_OK;
+}
+
+}  // namespace
+
+int ape_fk_bank_create(int32_t n_streams, int32_t smooth, const double body9[9], int32_t device, ape_fk_bank_t** out) {
+    if (!out || !body9) return ffail(APE_ERR_INVALID_ARG, "fk_bank_create: NULL argument");
+    *out = nullptr;
+    if (n_streams < 1) return ffail(APE_ERR_INVALID_ARG, "fk_bank_create: n_streams=%d must be >= 1", n_streams);
+    if (smooth < 1) smooth = 1;                                 // estimator.py:45: max(1, smooth)
+    if (smooth > 64) return ffail(APE_ERR_UNSUPPORTED, "fk_bank_create: smooth %d outside 1..64", smooth);
+    if (int rc = check_device(device, "fk_bank_create")) return rc;
+    FK_TRY(hipSetDevice(device));
+    ape_fk_bank* b = new (std::nothrow) ape_fk_bank();
+    if (!b) return ffail(APE_ERR_HIP, "fk_bank_create: out of host memory");
+    b->S = n_streams; b->smooth = smooth; b->device = device;
+    memcpy(b->body, body9, sizeof(b->body));
+    hipError_t e = hipMalloc((void**)&b->ring, (size_t)n_streams * smooth * 8 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->desc, (size_t)n_streams * sizeof(FkDesc));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&b->stage, (size_t)FK_STAGES * n_streams * sizeof(FkDesc), hipHostMallocDefault);
+    for (int i = 0; i < FK_STAGES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&b->ev[i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+        bank_free(b);
+        return ffail(APE_ERR_HIP, "fk_bank_create: allocation failed: %s", hipGetErrorString(e));
+    }
+    *out = b;
+    return APE_OK;
+}
+
+int ape_fk_bank_destroy(ape_fk_bank_t* b) {
+    if (!b) return APE_OK;
+    (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();          // frames may still read the ring and the staged descriptors
+    bank_free(b);
+    return APE_OK;
+}
+
+int ape_fk_bank_reset(ape_fk_bank_t* b) {
+    if (!b) return ffail(APE_ERR_INVALID_ARG, "fk_bank_reset: NULL bank");
+    b->uniform = true;
+    b->ucount = 0;
+    b->cnt.clear();
+    return APE_OK;
+}
+
+int ape_fk_bank_reset_subset(ape_fk_bank_t* b, const int32_t* streams_host, int32_t K) {
+    if (!b || !streams_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_reset_subset: NULL argument");
+    if (int rc = check_list(b, streams_host, K, "fk_bank_reset_subset")) return rc;
+    if (K == 0) return APE_OK;
+    leave_uniform(b);
+    for (int j = 0; j < K; ++j) b->cnt[streams_host[j]] = 0;
+    return APE_OK;
+}
+
+int ape_fk_bank_frame(ape_fk_bank_t* b, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K, void* out_dev,
+                      int32_t out_dtype, void* stream) {
+    if (!b || !rows_dev || !out_dev) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame: NULL argument");
+    if (int rc = check_kind(kind, "fk_bank_frame")) return rc;
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame: unknown dtype selector");
+    if (int rc = check_list(b, streams_host, K, "fk_bank_frame")) return rc;
+    FK_TRY(hipSetDevice(b->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "fk_bank_frame")) return rc;
+    if (K == 0) return APE_OK;
+    return bank_frame(b, kind, rows_dev, streams_host, K, out_dev, out_dtype, st, nullptr, "fk_bank_frame");
+}
+
+int ape_fk_bank_frame_host(ape_fk_bank_t* b, int32_t kind, const float* rows_host, void* out_host, int32_t out_dtype, void* stream) {
+    if (!b || !rows_host || !out_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame_host: NULL argument");
+    if (int rc = check_kind(kind, "fk_bank_frame_host")) return rc;
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame_host: unknown dtype selector");
+    FK_TRY(hipSetDevice(b->device));                         // (the consumer thread of an estimator starts on device 0)
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "fk_bank_frame_host")) return rc;
+    const size_t rows_bytes = (size_t)b->S * FK_WIDTH * sizeof(float);
+    const size_t out_bytes = (size_t)b->S * 25 * sizeof(double);
+    // the kernel reads the rows from and writes the messages to pinned host memory; up to 64 streams it writes a word per stream
+    // behind its message, and the host takes the frame when all are there instead of waiting for the stream (as ape_streams_frame_host)
+    if (!b->h_rows) FK_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, hipHostMallocCoherent | hipHostMallocMapped));
+    if (!b->h_out) FK_TRY(hipHostMalloc(&b->h_out, out_bytes, hipHostMallocCoherent | hipHostMallocMapped));
+    if (!b->h_done && b->S <= 64) {
+        FK_TRY(hipHostMalloc((void**)&b->h_done, 64 * sizeof(unsigned), hipHostMallocCoherent | hipHostMallocMapped));
+        memset(b->h_done, 0, 64 * sizeof(unsigned));
+    }
+    b->done_val += 1;
+    if (b->done_val == 0) b->done_val = 1;
+    memcpy(b->h_rows, rows_host, rows_bytes);
+    if (int rc = bank_frame(b, kind, b->h_rows, nullptr, b->S, b->h_out, out_dtype, st, b->h_done, "fk_bank_frame_host")) return rc;
+    bool seen = false;
+    if (b->h_done) {
+        // ~50 ms of looking (a frame takes microseconds); then the stream's own completion
+        volatile unsigned* dw = b->h_done;
+        for (long spin = 0; spin < 20000000L && !seen; ++spin) {
+            seen = true;
+            for (int k = 0; k < b->S; ++k) seen = seen && dw[k] == b->done_val;
+            if (!seen) __builtin_ia32_pause();
+        }
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    }
+    if (!seen) FK_TRY(hipStreamSynchronize(st));
+    memcpy(out_host, b->h_out, (size_t)b->S * 25 * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
+    return APE_OK;
+}
+
+int ape_fk_replay(int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t smooth,
+                  const double body9[9], int32_t device, void* out_dev, int32_t out_dtype, void* stream) {
+    if (!rows_dev || !out_dev || !body9) return ffail(APE_ERR_INVALID_ARG, "fk_replay: NULL argument");
+    if (int rc = check_kind(kind, "fk_replay")) return rc;
+    if (F < 1) return ffail(APE_ERR_INVALID_ARG, "fk_replay: F=%d must be >= 1", F);
+    if (R < 1 || R > F) return ffail(APE_ERR_INVALID_ARG, "fk_replay: %d recording starts for %d frames (1 <= R <= F)", R, F);
+    if (!seg_starts_host) return ffail(APE_ERR_INVALID_ARG, "fk_replay: NULL seg_starts");
+    if (seg_starts_host[0] != 0) return ffail(APE_ERR_INVALID_ARG, "fk_replay: seg_starts[0] = %d, must be 0", seg_starts_host[0]);
+    for (int i = 1; i < R; ++i)
+        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
+            return ffail(APE_ERR_INVALID_ARG, "fk_replay: seg_starts[%d] = %d (strictly rising, below F = %d)", i, seg_starts_host[i], F);
+    if (smooth < 1) smooth = 1;
+    if (smooth > 64) return ffail(APE_ERR_UNSUPPORTED, "fk_replay: smooth %d outside 1..64", smooth);
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ffail(APE_ERR_INVALID_ARG, "fk_replay: unknown dtype selector");
+    if (int rc = check_device(device, "fk_replay")) return rc;
+    FK_TRY(hipSetDevice(device));
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    FK_TRY(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return ffail(APE_ERR_INVALID_ARG, "fk_replay: blocking call on a capturing stream");
+    // workspaces: the frames' quaternions, their recording starts; freed behind the call's own synchronisation
+    struct Scratch {
+        void* p[3] = {};
+        ~Scratch() { for (void* q : p) if (q) (void)hipFree(q); }
+    } ws;
+    FK_TRY(hipMalloc(&ws.p[0], (size_t)F * 8 * sizeof(double)));
+    FK_TRY(hipMalloc(&ws.p[1], (size_t)F * sizeof(int)));
+    FK_TRY(hipMalloc(&ws.p[2], (size_t)R * sizeof(int)));
+    FK_TRY(hipMemcpyAsync(ws.p[2], seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st));
+    FkReplayParams p{};
+    p.rows = rows_dev; p.seg_of = (const int*)ws.p[1]; p.ws = (double*)ws.p[0]; p.out = out_dev;
+    p.F = F; p.smooth = smooth; p.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
+    memcpy(p.body, body9, sizeof(p.body));
+    hipError_t e = ape_launch_replay_segments((const int*)ws.p[2], R, F, (int*)ws.p[1], st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(ape_fk_replay_rows_kernel, dim3(blocks_for(F)), dim3(FK_BLOCK), 0, st, p);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = launch_typed(ape_fk_replay_msg_kernel<float>, ape_fk_replay_msg_kernel<double>, out_dtype, F, p, st);
+    if (e != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        return ffail(APE_ERR_HIP, "fk_replay: launch failed: %s", hipGetErrorString(e));
+    }
+    FK_TRY(hipStreamSynchronize(st));
+    return APE_OK;
+}

@@ -88,6 +88,14 @@ SIGNATURES = {
     "ape_streams_reset_subset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
     "ape_streams_frame_subset": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p,
                                            C.c_int32, C.c_void_p]),
+    "ape_fk_bank_create": (C.c_int, [C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_int32, C.POINTER(C.c_void_p)]),
+    "ape_fk_bank_destroy": (C.c_int, [C.c_void_p]),
+    "ape_fk_bank_reset": (C.c_int, [C.c_void_p]),
+    "ape_fk_bank_reset_subset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "ape_fk_bank_frame": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ape_fk_bank_frame_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
+    "ape_fk_replay": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
     "ape_model_set_kernel": (C.c_int, [C.c_void_p, C.c_int32]),
     "ape_model_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "ape_model_check": (C.c_int, [C.c_void_p]),

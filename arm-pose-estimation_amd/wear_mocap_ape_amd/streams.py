@@ -230,3 +230,100 @@ class StreamBank:
                                                          self._C.c_void_p(self._packed.data_ptr()), None, self._hip.F32,
                                                          self._stream()), "ape_streams_step")
         return self._packed
+
+
+class FkStreamBank:
+    """The per-frame step of many independent ``WatchPhoneUarm`` streams (the estimator without a regressor) with the smoothing
+    stacks on the device (C ABI ``ape_fk_bank_*``): for every stream what one ``WatchPhoneUarm.process_row`` does,
+    one launch per frame.  Each stream keeps its own count of rows since its cold start, so lockstep frames (``step_rows``) and
+    subset frames (``frame``) mix freely.  Rank-local: give each rank its ``shard_range`` of streams.
+
+    ``bonemap``: an object with ``left_lower_arm_length``, ``left_upper_arm_length`` and ``left_upper_arm_origin_rh`` (None: the
+    defaults), as ``Estimator``.  ``dtype``: of the messages, float32 (the ``PoseEstPublisherUDP`` payload) or float64."""
+
+    def __init__(self, n_streams: int, smooth: int = 5, bonemap=None, dtype: torch.dtype = torch.float32, device=None):
+        from . import _hip
+        from .data_types.bone_map import BoneMap
+        import ctypes as C
+        self._hip, self._C = _hip, C
+        if dtype not in (torch.float32, torch.float64):
+            raise UserWarning(f"FkStreamBank messages are float32 or float64, not {dtype}")
+        if int(n_streams) < 1:
+            raise UserWarning(f"FkStreamBank needs n_streams >= 1, got {n_streams}")
+        self._n, self._smooth = int(n_streams), max(1, int(smooth))
+        self._dtype, self._sel = dtype, (_hip.F32 if dtype == torch.float32 else _hip.F64)
+        if device is None:
+            device = torch.cuda.current_device()
+        self._device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+        if self._device.index is None:
+            self._device = torch.device("cuda", torch.cuda.current_device())
+        larm = BoneMap.DEFAULT_LARM_LEN if bonemap is None else bonemap.left_lower_arm_length
+        uarm = BoneMap.DEFAULT_UARM_LEN if bonemap is None else bonemap.left_upper_arm_length
+        orig = BoneMap.DEFAULT_UARM_ORIG_RH if bonemap is None else bonemap.left_upper_arm_origin_rh
+        self._body = np.ascontiguousarray(np.r_[[-larm, 0, 0], [-uarm, 0, 0], orig], dtype=np.float64)
+        handle = C.c_void_p()
+        _hip.check(_hip.lib().ape_fk_bank_create(self._n, self._smooth, _hip.dptr(self._body, C.c_double), self._device.index,
+                                                 C.byref(handle)), "ape_fk_bank_create")
+        self._handle = handle
+        self._msg = torch.empty((self._n, 25), dtype=dtype, device=self._device)
+        self._sub_msg = torch.empty((self._n, 25), dtype=dtype, device=self._device)
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        try:
+            if h:
+                self._hip.lib().ape_fk_bank_destroy(h)
+        except Exception:          # interpreter shutdown
+            pass
+
+    body_measurements = property(lambda self: self._body[np.newaxis, :].copy())
+
+    def _stream(self):
+        return self._C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+
+    _indices = StreamBank._indices          # in range, distinct, int32
+
+    def _rows(self, rows, K: int):
+        if isinstance(rows, torch.Tensor):
+            rd = rows
+            if rd.is_cuda and rd.device != self._device:
+                raise UserWarning(f"rows live on {rd.device}, the bank on {self._device}")
+        else:
+            rd = torch.from_numpy(np.asarray(rows))
+        if rd.dtype != torch.float32 or tuple(rd.shape) != (K, 55):
+            raise UserWarning(f"the bank wants float32 rows [{K},55] (WATCH_PHONE_IMU messages), got {rd.dtype} {tuple(rd.shape)}")
+        return rd.to(self._device).contiguous()
+
+    def reset(self, streams=None):
+        """cold start: ``streams=None`` every stream, else only the listed (distinct) ones"""
+        if streams is None:
+            self._hip.check(self._hip.lib().ape_fk_bank_reset(self._handle), "ape_fk_bank_reset")
+            return
+        idx = self._indices(streams)
+        self._hip.check(self._hip.lib().ape_fk_bank_reset_subset(self._handle, self._C.c_void_p(idx.ctypes.data), int(idx.shape[0])),
+                        "ape_fk_bank_reset_subset")
+
+    def step_rows(self, rows, big_endian: bool = False):
+        """lockstep frame: float32 ``[S, 55]`` rows (host array or device tensor), row s for stream s -> ``[S, 25]`` messages (the
+        bank's own buffer, overwritten by the next lockstep frame)"""
+        hip, C = self._hip, self._C
+        rd = self._rows(rows, self._n)
+        kind = hip.PARSE_WATCH_PHONE_UARM | (hip.PARSE_BIG_ENDIAN if big_endian else 0)
+        hip.check(hip.lib().ape_fk_bank_frame(self._handle, kind, C.c_void_p(rd.data_ptr()), None, self._n,
+                                              C.c_void_p(self._msg.data_ptr()), self._sel, self._stream()), "ape_fk_bank_frame")
+        return self._msg
+
+    def frame(self, rows, streams, big_endian: bool = False):
+        """subset frame: float32 ``[K, 55]`` rows, row j for stream ``streams[j]`` (K distinct indices) -> ``[K, 25]`` in list order
+        (the bank's own buffer, overwritten by the next subset frame).  Streams not listed are untouched."""
+        hip, C = self._hip, self._C
+        idx = self._indices(streams)
+        K = int(idx.shape[0])
+        rd = self._rows(rows, K)
+        out = self._sub_msg[:K]
+        if K == 0:
+            return out
+        kind = hip.PARSE_WATCH_PHONE_UARM | (hip.PARSE_BIG_ENDIAN if big_endian else 0)
+        hip.check(hip.lib().ape_fk_bank_frame(self._handle, kind, C.c_void_p(rd.data_ptr()), C.c_void_p(idx.ctypes.data), K,
+                                              C.c_void_p(out.data_ptr()), self._sel, self._stream()), "ape_fk_bank_frame")
+        return out

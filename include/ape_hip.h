@@ -353,6 +353,35 @@ int ape_streams_reset_subset(ape_streams_t* bank, const int32_t* streams_host, i
 int ape_streams_frame_subset(ape_streams_t* bank, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
                              uint32_t flags, void* out_dev, int32_t out_dtype, void* stream);
 
+/* ---- the estimator without a regressor: WatchPhoneUarm (additive in ABI 7) -------------------------------------
+ * Replaces estimate/watch_phone_uarm.py:10-108 behind Estimator (estimator.py:93-137): per frame the 38 features of
+ * APE_PARSE_WATCH_PHONE_UARM, the watch's and the phone's calibrated 6D columns (features 13:19 and 32:38) as the 12 targets of
+ * APE_LAYOUT_ORI_CAL_LARM_UARM, float64 with no model and no de-normalisation, the smoothing stack (`smooth` rows, padded with the
+ * newest on a cold start, estimator.py:112-118) and the 25-value message (compose_msg.py:82-108).  float64 throughout; an F32 output
+ * is the float64 message rounded (the PoseEstPublisherUDP payload, pose_est_udp.py:47).
+ * A bank holds S streams, each with its own stack and its own count of rows since its cold start: lockstep frames (all S in order)
+ * and subset frames mix freely.  smooth is clamped to max(1, smooth) like the reference; smooth <= 64.  body9 = [larm_vec, uarm_vec,
+ * uarm_orig_rh] (Estimator.body_measurements).
+ * ape_fk_bank_frame: rows_dev f32 [K,55] on the device (kind APE_PARSE_WATCH_PHONE_UARM, may carry APE_PARSE_BIG_ENDIAN), row j for
+ *   stream streams_host[j] (K distinct indices in host memory; NULL => K == S, all streams in order); out_dev [K,25] of out_dtype in
+ *   list order.  Streams not listed stay untouched.  K = 0 is a no-op.  Asynchronous on `stream`; ONE bank serialises on ONE stream.
+ * ape_fk_bank_frame_host: one lockstep frame from host rows [S,55] to host messages [S,25]; BLOCKING (what process_row calls).
+ * ape_fk_bank_reset: cold-starts every stream; ape_fk_bank_reset_subset: the K listed streams only.
+ * ape_fk_replay: every frame of R recordings back to back in rows_dev [F,55] (seg_starts_host: their first rows, [0] first,
+ *   strictly rising, below F), each from a cold start -> out_dev [F,25]: what a fresh bank stream fed each recording returns.  BLOCKING.
+ * Refused (non-zero, ape_last_error): NULL arguments, a kind other than APE_PARSE_WATCH_PHONE_UARM, K < 0 or K > S, an index outside
+ * [0, S), a duplicate index, bad replay starts, F < 1, smooth > 64, a capturing stream (frames stage ring positions per call). */
+typedef struct ape_fk_bank ape_fk_bank_t;
+int ape_fk_bank_create(int32_t n_streams, int32_t smooth, const double body9[9], int32_t device, ape_fk_bank_t** out);
+int ape_fk_bank_destroy(ape_fk_bank_t* bank);
+int ape_fk_bank_reset(ape_fk_bank_t* bank);
+int ape_fk_bank_reset_subset(ape_fk_bank_t* bank, const int32_t* streams_host, int32_t K);
+int ape_fk_bank_frame(ape_fk_bank_t* bank, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
+                      void* out_dev, int32_t out_dtype, void* stream);
+int ape_fk_bank_frame_host(ape_fk_bank_t* bank, int32_t kind, const float* rows_host, void* out_host, int32_t out_dtype, void* stream);
+int ape_fk_replay(int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t smooth,
+                  const double body9[9], int32_t device, void* out_dev, int32_t out_dtype, void* stream);
+
 /* kernel selection for A/B runs and tests; no effect on results beyond float32 summation order */
 int ape_model_set_kernel(ape_model_t* model, int32_t choice);
 int ape_model_set_precision(ape_model_t* model, int32_t precision);
