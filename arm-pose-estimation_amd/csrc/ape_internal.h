@@ -337,6 +337,11 @@ __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2
 // sets the thread's error string (ape_last_error) and returns `code`: for the entry points outside ape_api.hip
 int ape_set_error(int code, const char* msg);
 
+// kalman.hip's model as kalman_bank.hip sees it
+struct ape_kalman;
+struct ApeKalmanInfo { int E, W, device, has_weights; };
+void ape_kalman_info(const ape_kalman* m, ApeKalmanInfo* out);
+
 // launchers implemented in the .hip files --------------------------------------------------
 // returns hipSuccess or the launch error; `smem_bytes` out for diagnostics
 hipError_t ape_launch_lstm_tile16(int H, int L, const LstmParams& p, hipStream_t stream);

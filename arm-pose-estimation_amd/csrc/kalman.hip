@@ -24,6 +24,7 @@
 
 #include "../../include/ape_hip.h"
 #include "ape_internal.h"
+#include "kalman_device.h"
 
 namespace {
 
@@ -43,17 +44,7 @@ struct KfPerturbParams {
     unsigned long long seed;
 };
 
-__device__ __forceinline__ float u01(uint32_t x) { return ((float)(x >> 8) + 1.0f) * 5.9604644775390625e-08f; }   // (0, 1], 24 bits
-
-// standard normal number `idx` of stream (tag, seed): Box-Muller on Philox words
-__device__ __forceinline__ float philox_normal(unsigned idx, unsigned tag, unsigned long long seed) {
-    uint32_t w[4];
-    philox4x32(idx >> 2, tag, 0x4B414C4Du, 0u, (uint32_t)seed, (uint32_t)(seed >> 32), w);
-    const int pair = (idx >> 1) & 1;
-    const float r = sqrtf(-2.0f * logf(u01(w[2 * pair])));
-    const float a = 6.283185307179586f * (float)w[2 * pair + 1] * 2.3283064365386963e-10f;
-    return (idx & 1) ? r * sinf(a) : r * cosf(a);
-}
+using ape_kfdev::philox_normal;        // kalman_device.h: shared with the bank's frame tail (kalman_bank.hip)
 
 __global__ void kf_perturb_kernel(const KfPerturbParams p) {
     const unsigned i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -365,6 +356,11 @@ hipError_t launch_linear(const ape_kalman* m, int li, const float* X, int x_grou
 }
 
 }  // namespace
+
+// what kalman_bank.hip needs to know of a model (the struct stays private to this file)
+void ape_kalman_info(const ape_kalman* m, ApeKalmanInfo* out) {
+    out->E = m->E; out->W = m->W; out->device = m->device; out->has_weights = m->has_weights ? 1 : 0;
+}
 
 extern "C" {
 

@@ -1,0 +1,611 @@
+// The frame of WatchPhonePocketKalman (reference estimate/watch_phone_pocket_kalman.py:57-63, 133-169 inside Estimator, estimator.py:93-137)
+// for a bank of S streams with every history on the device.  PARITY UNPINNED like kalman.hip: the checker of the
+// bookkeeping here is oracle/kalman_oracle.py's KalmanFrameLogic chained with oracle/ape_oracle.py's WindowOracle and post-filter.
+//
+// A frame for K listed streams is three parts on one stream, nothing returns to the host in between:
+//   ape_kalman_bank_head_kernel   (workgroup per list entry) raw row -> 22 features (parse_device.h) -> the stream's window ring (all W
+//                                 slots on a cold start) -> float64 z-score -> the model's dense [K, 22 W] input; and the stream's state
+//                                 ring [E, W, 14], read in time order through its head, into the model's dense [K E, 14 W] input (zeros,
+//                                 and a zeroed ring, on a cold start).  This gather is both the row indirection of subset frames and the
+//                                 state shift: the ring is never moved, the copy the model needs anyway is rotated.
+//   ape_kalman_forward            kalman.hip's eight launches on the dense inputs, untouched: one flipout draw per call, signs per dense
+//                                 row (list position j, member e), the update per list entry
+//   ape_kalman_bank_tail_kernel   (workgroup per list entry) the sensor mean z (the stream's first W + 1 frames; format_state of it into
+//                                 the state ring) or the corrected ensemble (afterwards; itself into the ring), the smoothing stack with
+//                                 ragged entries (1 or E rows, padded with the newest on a cold start), float64 de-normalisation, FK of
+//                                 every stacked row (thread per row), the sign-aligned quaternion means and the 25-value message
+//                                 (stream_post_device.h's finish_msg), the packed tail, n_rows, and the stream's frame counter.
+// Frame counters live on the device; the host only remembers which streams have a cold start pending and hands that over in the
+// staged stream list (or, for lockstep frames, as one kernel argument).
+// float64 with separate roundings for a * b + c, like numpy: contraction is off in this file.
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "ape_internal.h"
+#include "../../include/ape_hip.h"
+#include "parse_device.h"
+#include "stream_post_device.h"
+#include "kalman_device.h"
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace ape_postdev;
+
+constexpr int DX = 14, RAW = 22;
+constexpr int KB_WIDTH = 55;          // APE_PARSE_WATCH_PHONE_POCKET message
+constexpr int KB_BLOCK = 256;
+constexpr int KB_STAGES = 4;          // pinned stream-list slots (frames go back to back)
+constexpr int KB_MAX_SMOOTH = 64;     // the post-filter's limits (ape_streams_create)
+constexpr int KB_MAX_ROWS = 4096;
+
+// one list entry of a frame: the stream, whether this is its first frame since a cold start, the row it reads and the row it writes
+struct KbDesc { int stream, cold, row_in, row_out; };
+
+struct KbHeadParams {
+    const float* rows;                // [*, 55] raw messages, entry j reads row desc[j].row_in
+    const KbDesc* desc;               // [K] or nullptr: entry j = stream j, row j, cold = cold_all
+    const int* cnt;                   // [S] frames since the stream's cold start
+    double* xwin;                     // [S, W, 22] window rings (features as parse_row_to_xx returns them: float64)
+    float* state;                     // [S, E, W, 14] state rings
+    float* raw;                       // [K, W, 22] the model's sensor input
+    float* dense;                     // [K, E, W, 14] the model's state input
+    int K, E, W, big_endian, normalize, cold_all;
+    double xx_m[RAW], xx_s[RAW];
+};
+
+struct KbTailParams {
+    const KbDesc* desc;
+    int* cnt;
+    const float* z;                   // [K, 14] sensor-model mean of this frame
+    const float* corrected;           // [K, E, 14]
+    const float* init_noise;          // [K, E, 14] injected format_state draws, or nullptr: Philox
+    unsigned long long seed;
+    float* state;
+    float* yring;                     // [S, smooth, E, 14] the last `smooth` predictions (normalised), 1 or E rows each
+    int* nring;                       // [S, smooth] their row counts
+    void* out;                        // [*, out_stride]
+    int* n_rows;                      // [*]
+    float* y_out;                     // [*, E, 14] or nullptr
+    int K, E, W, smooth, packed, normalize, cold_all, out_stride, wrap;
+    double yy_m[DX], yy_s[DX], body[9];
+};
+
+__global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_head_kernel(const KbHeadParams p) {
+    __shared__ double xx[RAW];
+    const int j = blockIdx.x, tid = threadIdx.x;
+    const KbDesc d = p.desc ? p.desc[j] : KbDesc{j, p.cold_all, j, j};
+    const bool cold = d.cold != 0;
+    const int c = cold ? 0 : p.cnt[d.stream];
+    const int E = p.E, W = p.W;
+    if (tid == 0) {                                     // the feature chain: one lane (parse_rows.hip)
+        float r[KB_WIDTH];
+        const float* src = p.rows + (size_t)d.row_in * KB_WIDTH;
+#pragma unroll
+        for (int k = 0; k < KB_WIDTH; ++k) {
+            float v = src[k];
+            if (p.big_endian) v = __builtin_bit_cast(float, __builtin_bswap32(__builtin_bit_cast(unsigned, v)));
+            r[k] = v;
+        }
+        ape_parsedev::parse_row(r, KB_WIDTH, APE_PARSE_WATCH_PHONE_POCKET, xx);
+    } else if (tid >= 64) {
+        // beside it, waves 1-3: the state history in time order.  The ring's oldest entry sits in slot c mod W (the slot this frame's
+        // tail overwrites); 8-byte pieces (a state is 14 floats = 56 bytes).  Cold start: zeros, and the ring is zeroed for the frames to come.
+        const int per = W * 7, n = E * per, h = c % W;
+        float2* ring = reinterpret_cast<float2*>(p.state + (size_t)d.stream * E * W * DX);
+        float2* dst = reinterpret_cast<float2*>(p.dense + (size_t)j * E * W * DX);
+        for (int idx = tid - 64; idx < n; idx += KB_BLOCK - 64) {
+            float2 v = {0.0f, 0.0f};
+            if (cold) ring[idx] = v;
+            else {
+                const int e = idx / per, rem = idx - e * per, i = rem / 7, q = rem - i * 7;
+                int sl = h + i;
+                if (sl >= W) sl -= W;
+                v = ring[e * per + sl * 7 + q];
+            }
+            dst[idx] = v;
+        }
+    }
+    __syncthreads();
+    // the window: step W-1 is the new row, step t < W-1 ring slot slot+1+t (mod W); z-score in float64, cast (estimator.py:96-104)
+    const int slot = c % W;
+    double* win = p.xwin + (size_t)d.stream * W * RAW;
+    float* raw = p.raw + (size_t)j * W * RAW;
+    for (int idx = tid; idx < W * RAW; idx += KB_BLOCK) {
+        const int t = idx / RAW, f = idx - t * RAW;
+        double v;
+        if (cold) { v = xx[f]; win[idx] = v; }
+        else if (t == W - 1) { v = xx[f]; win[slot * RAW + f] = v; }
+        else {
+            int sl = slot + 1 + t;
+            if (sl >= W) sl -= W;
+            v = win[sl * RAW + f];                  // (never the slot written above: sl != slot for t < W - 1)
+        }
+        if (p.normalize) v = (v - p.xx_m[f]) / p.xx_s[f];
+        raw[idx] = (float)v;
+    }
+}
+
+template <typename TMsg>
+__global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const KbTailParams p) {
+    __shared__ int ent_slot[KB_MAX_SMOOTH], ent_first[KB_MAX_SMOOTH + 1];   // stack entries, oldest first: ring slot (-1: this frame's), first stacked row
+    __shared__ double ref_s[3][4], e0_s[21], red[KB_BLOCK / 64][12];
+    const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const KbDesc d = p.desc ? p.desc[j] : KbDesc{j, p.cold_all, j, j};
+    const bool cold = d.cold != 0;
+    const int s = d.stream, E = p.E, W = p.W, smooth = p.smooth;
+    const int c = cold ? 0 : p.cnt[s];
+    // watch_phone_pocket_kalman.py:141-156: the first W + 1 frames return the sensor model's mean and feed format_state of it back
+    const bool init = c <= W;
+    const int n_new = init ? 1 : E;
+    const int pos = c % smooth;
+    const float* src_new = init ? p.z + (size_t)j * DX : p.corrected + (size_t)j * E * DX;
+    {   // this frame's entry of the state history (slot c mod W: the oldest one's)
+        float* ring = p.state + (size_t)s * E * W * DX;
+        const int slot = c % W;
+        for (int idx = tid; idx < E * DX; idx += KB_BLOCK) {
+            const int e = idx / DX, cc = idx - e * DX;
+            float v;
+            if (init) {                             // kalman_models.py:164-173: N(0, 0.1 I) around z, a draw per (list entry, member)
+                const size_t g = (size_t)j * E * DX + idx;
+                const float nz = p.init_noise ? p.init_noise[g] : ape_kfdev::philox_normal((unsigned)g, 0x300u, p.seed);
+                v = p.z[(size_t)j * DX + cc] + 0.31622776601683794f * nz;
+            } else v = p.corrected[(size_t)j * E * DX + idx];
+            ring[(e * W + slot) * DX + cc] = v;
+        }
+    }
+    // the prediction: to the caller and into the smoothing stack (every slot on a cold start, estimator.py:114-115)
+    for (int idx = tid; idx < n_new * DX; idx += KB_BLOCK) {
+        const float v = src_new[idx];
+        if (p.y_out) p.y_out[(size_t)d.row_out * E * DX + idx] = v;
+        for (int t = cold ? 0 : pos; t < (cold ? smooth : pos + 1); ++t) p.yring[((size_t)(s * smooth + t) * E) * DX + idx] = v;
+    }
+    if (tid < smooth) {
+        int sl = pos + 1 + tid;
+        if (sl >= smooth) sl -= smooth;
+        const bool fresh = cold || tid == smooth - 1;
+        ent_slot[tid] = fresh ? -1 : sl;
+        ent_first[tid + 1] = fresh ? n_new : p.nring[s * smooth + sl];      // (row counts; summed below)
+    }
+    __syncthreads();
+    if (tid == 0) {
+        ent_first[0] = 0;
+        for (int k = 0; k < smooth; ++k) ent_first[k + 1] += ent_first[k];
+        for (int t = cold ? 0 : pos; t < (cold ? smooth : pos + 1); ++t) p.nring[s * smooth + t] = n_new;
+    }
+    __syncthreads();
+    const int N = ent_first[smooth];
+    const double wgt = 1.0 / (double)N;
+    const Vec3 larm_vec{p.body[0], p.body[1], p.body[2]}, uarm_vec{p.body[3], p.body[4], p.body[5]}, orig{p.body[6], p.body[7], p.body[8]};
+    TMsg* out = static_cast<TMsg*>(p.out) + (size_t)d.row_out * p.out_stride;
+    double acc[12] = {};
+    for (int base = 0; base < N; base += KB_BLOCK) {        // thread per stacked row, oldest entry first (trip count uniform)
+        const int i = base + tid;
+        const bool act = i < N;
+        double q[12] = {};
+        if (act) {
+            int k = 0;
+            while (i >= ent_first[k + 1]) ++k;
+            const int r = i - ent_first[k];
+            const float* src = ent_slot[k] < 0 ? src_new + (size_t)r * DX : p.yring + ((size_t)(s * smooth + ent_slot[k]) * E + r) * DX;
+            double y[DX];
+#pragma unroll
+            for (int cc = 0; cc < DX; ++cc) {
+                double v = (double)src[cc];
+                if (p.normalize) v = v * p.yy_s[cc] + p.yy_m[cc];              // estimator.py:108-109
+                y[cc] = v;
+            }
+            // estimate_joints.py:48-71 (ORI_CAL_LARM_UARM_HIPS)
+            const Quat lq = six_drr_to_quat(y), uq = six_drr_to_quat(y + 6), hq = hips_quat(y[12], y[13]);
+            const Vec3 uo = qrot(hq, orig);
+            const Vec3 lo = vadd(qrot(uq, uarm_vec), uo);
+            const Vec3 ho = vadd(qrot(lq, larm_vec), lo);
+            put_q(q, lq); put_q(q + 4, uq); put_q(q + 8, hq);
+            if (p.packed) {                                                  // estimator.py:131-137: est[i, :6] of every row
+                TMsg* t = out + 25 + (size_t)i * 6;
+                t[0] = (TMsg)ho.x; t[1] = (TMsg)ho.y; t[2] = (TMsg)ho.z; t[3] = (TMsg)lo.x; t[4] = (TMsg)lo.y; t[5] = (TMsg)lo.z;
+            }
+            if (i == 0) {                                                    // row 0: the sign reference, and the N == 1 message
+#pragma unroll
+                for (int cc = 0; cc < 12; ++cc) ref_s[cc >> 2][cc & 3] = q[cc];
+                put_v(e0_s, ho); put_v(e0_s + 3, lo); put_v(e0_s + 6, uo);
+#pragma unroll
+                for (int cc = 0; cc < 12; ++cc) e0_s[9 + cc] = q[cc];
+            }
+        }
+        if (base == 0) __syncthreads();
+        if (act && N > 1) {                                                  // transformations.py:32-51
+#pragma unroll
+            for (int g = 0; g < 3; ++g) {
+                const double r0 = ref_s[g][0], r1 = ref_s[g][1], r2 = ref_s[g][2], r3 = ref_s[g][3];
+                const double dt = fma(q[4 * g + 3], r3, fma(q[4 * g + 2], r2, fma(q[4 * g + 1], r1, q[4 * g] * r0)));
+                const double sg = (i > 0 && dt < 0.0) ? -wgt : wgt;
+#pragma unroll
+                for (int cc = 0; cc < 4; ++cc) acc[4 * g + cc] += q[4 * g + cc] * sg;
+            }
+        }
+    }
+    if (N > 1) {
+#pragma unroll
+        for (int cc = 0; cc < 12; ++cc) {
+            const double v = wave_sum(acc[cc]);
+            if (lane == 0) red[wave][cc] = v;
+        }
+    }
+    if (p.packed)                                                            // beyond the stacked rows: zeros
+        for (int idx = 25 + 6 * N + tid; idx < p.out_stride; idx += KB_BLOCK) out[idx] = (TMsg)0.0;
+    __syncthreads();
+    if (tid == 0) {
+        double out_q[3][4] = {}, orig_mean[9] = {}, e0[21], m[25];
+        if (N > 1) {
+#pragma unroll
+            for (int g = 0; g < 3; ++g) {
+                double a[4];
+#pragma unroll
+                for (int cc = 0; cc < 4; ++cc) a[cc] = ((red[0][4 * g + cc] + red[1][4 * g + cc]) + red[2][4 * g + cc]) + red[3][4 * g + cc];
+                const double nrm = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + a[3] * a[3]);
+#pragma unroll
+                for (int cc = 0; cc < 4; ++cc) out_q[g][cc] = a[cc] / nrm;
+            }
+        }
+#pragma unroll
+        for (int cc = 0; cc < 21; ++cc) e0[cc] = e0_s[cc];
+        finish_msg(APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS, N, out_q, orig_mean, e0, p.body, m);
+#pragma unroll
+        for (int cc = 0; cc < 25; ++cc) out[cc] = (TMsg)m[cc];
+        p.n_rows[d.row_out] = N;
+        int next = c + 1;                           // (kept below 2^30 with its residues mod W and mod smooth, and above W)
+        if (next >= (1 << 30)) next -= p.wrap;
+        p.cnt[s] = next;
+    }
+}
+
+int bfail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return ape_set_error(code, buf);
+}
+
+#define KB_TRY(expr)                                                                                   \
+    do {                                                                                               \
+        hipError_t _e = (expr);                                                                        \
+        if (_e != hipSuccess) return bfail(APE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+int check_kind(int32_t kind, const char* what) {
+    if ((kind & ~APE_PARSE_BIG_ENDIAN) != APE_PARSE_WATCH_PHONE_POCKET)
+        return bfail(APE_ERR_INVALID_ARG, "%s: kind %d: the Kalman estimator reads APE_PARSE_WATCH_PHONE_POCKET rows only", what, kind);
+    return APE_OK;
+}
+
+int check_capture(hipStream_t st, const char* what) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    KB_TRY(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone)
+        return bfail(APE_ERR_INVALID_ARG, "%s: the stream is capturing (stream lists and draw keys are staged per call)", what);
+    return APE_OK;
+}
+
+}  // namespace
+
+struct ape_kalman_bank {
+    ape_kalman* model = nullptr;
+    int S = 0, E = 0, W = 0, smooth = 1, device = 0;
+    bool normalize = false;
+    double xx_m[RAW] = {}, xx_s[RAW] = {}, yy_m[DX] = {}, yy_s[DX] = {}, body[9] = {};
+    unsigned long long seed = 0x5EED, calls = 0;
+    // per-stream state
+    double* xwin = nullptr;
+    float* state = nullptr;
+    float* yring = nullptr;
+    int* nring = nullptr;
+    int* cnt = nullptr;
+    // per-frame images and the model's outputs
+    float *raw = nullptr, *dense = nullptr, *corrected = nullptr, *ensz = nullptr, *mcorr = nullptr, *mpred = nullptr, *z = nullptr;
+    // cold starts not yet handed to the device (a fresh bank: all), the staged stream lists
+    std::vector<char> pending;
+    int n_pending = 0;
+    KbDesc* desc = nullptr;
+    KbDesc* stage = nullptr;
+    hipEvent_t ev[KB_STAGES] = {};
+    int next = 0;
+    // frame_host: pinned rows, messages and row counts
+    float* h_rows = nullptr;
+    void* h_out = nullptr;
+    int* h_n = nullptr;
+};
+
+namespace {
+
+void bank_free(ape_kalman_bank* b) {
+    void* dev[] = {b->xwin, b->state, b->yring, b->nring, b->cnt, b->raw, b->dense, b->corrected, b->ensz, b->mcorr, b->mpred, b->z, b->desc};
+    for (void* q : dev) if (q) (void)hipFree(q);
+    void* host[] = {b->stage, b->h_rows, b->h_out, b->h_n};
+    for (void* q : host) if (q) (void)hipHostFree(q);
+    for (int i = 0; i < KB_STAGES; ++i)
+        if (b->ev[i]) (void)hipEventDestroy(b->ev[i]);
+    delete b;
+}
+
+// argument checks that need no device, then the allocations; `what` names the entry in messages
+int bank_make(ape_kalman* model, int32_t n_streams, int32_t smooth, const char* what, ape_kalman_bank** out) {
+    if (n_streams < 1 || n_streams > 65535) return bfail(APE_ERR_INVALID_ARG, "%s: n_streams=%d outside [1, 65535]", what, n_streams);
+    if (smooth < 1) smooth = 1;                                 // estimator.py:45: max(1, smooth)
+    if (smooth > KB_MAX_SMOOTH) return bfail(APE_ERR_UNSUPPORTED, "%s: smooth %d outside 1..%d", what, smooth, KB_MAX_SMOOTH);
+    ApeKalmanInfo mi;
+    ape_kalman_info(model, &mi);
+    if (!mi.has_weights) return bfail(APE_ERR_NOT_READY, "%s: the model's weights are not loaded", what);
+    if (smooth * mi.E > KB_MAX_ROWS)
+        return bfail(APE_ERR_UNSUPPORTED, "%s: smooth %d x %d members = %d stacked rows, more than %d", what, smooth, mi.E, smooth * mi.E, KB_MAX_ROWS);
+    KB_TRY(hipSetDevice(mi.device));
+    ape_kalman_bank* b = new (std::nothrow) ape_kalman_bank();
+    if (!b) return bfail(APE_ERR_HIP, "%s: out of host memory", what);
+    b->model = model; b->S = n_streams; b->E = mi.E; b->W = mi.W; b->smooth = smooth; b->device = mi.device;
+    b->pending.assign((size_t)n_streams, 1);
+    b->n_pending = n_streams;
+    const size_t S = (size_t)n_streams, E = (size_t)mi.E, W = (size_t)mi.W;
+    hipError_t e = hipMalloc((void**)&b->xwin, S * W * RAW * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->state, S * E * W * DX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->yring, S * smooth * E * DX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->nring, S * smooth * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->cnt, S * sizeof(int));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->raw, S * W * RAW * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->dense, S * E * W * DX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->corrected, S * E * DX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->ensz, S * E * DX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->mcorr, S * DX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->mpred, S * DX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->z, S * DX * sizeof(float));
+    if (e == hipSuccess) e = hipMalloc((void**)&b->desc, S * sizeof(KbDesc));
+    if (e == hipSuccess) e = hipHostMalloc((void**)&b->stage, (size_t)KB_STAGES * S * sizeof(KbDesc), hipHostMallocDefault);
+    for (int i = 0; i < KB_STAGES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&b->ev[i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+        bank_free(b);
+        return bfail(APE_ERR_HIP, "%s: allocation failed: %s", what, hipGetErrorString(e));
+    }
+    *out = b;
+    return APE_OK;
+}
+
+int check_list(const ape_kalman_bank* b, const int32_t* streams_host, int32_t K, const char* what) {
+    if (K < 0 || K > b->S) return bfail(APE_ERR_INVALID_ARG, "%s: K=%d outside [0, S=%d]", what, K, b->S);
+    if (!streams_host) {
+        if (K != b->S) return bfail(APE_ERR_INVALID_ARG, "%s: no stream list: K=%d must be S=%d", what, K, b->S);
+        return APE_OK;
+    }
+    std::vector<char> seen((size_t)b->S, 0);
+    for (int j = 0; j < K; ++j) {
+        const int s = streams_host[j];
+        if (s < 0 || s >= b->S) return bfail(APE_ERR_INVALID_ARG, "%s: stream index %d (entry %d) outside [0, %d)", what, s, j, b->S);
+        if (seen[s]) return bfail(APE_ERR_INVALID_ARG, "%s: stream %d listed twice", what, s);
+        seen[s] = 1;
+    }
+    return APE_OK;
+}
+
+// head -> model -> tail for K list entries on `st`.  desc_dev nullptr: entry j = stream j, row j, all cold or none
+int frame_launch(ape_kalman_bank* b, int big_endian, const float* rows, const KbDesc* desc_dev, int cold_all, int32_t K,
+                 const float* noise, const float* init_noise, uint32_t flags, void* out, int32_t out_dtype, int* n_rows, float* y,
+                 hipStream_t st, const char* what) {
+    b->calls += 1;
+    const unsigned long long seed = b->seed + 0xD1342543DE82EF95ull * b->calls;       // a key per call
+    KbHeadParams h{};
+    h.rows = rows; h.desc = desc_dev; h.cnt = b->cnt; h.xwin = b->xwin; h.state = b->state; h.raw = b->raw; h.dense = b->dense;
+    h.K = K; h.E = b->E; h.W = b->W; h.big_endian = big_endian; h.normalize = b->normalize ? 1 : 0; h.cold_all = cold_all;
+    memcpy(h.xx_m, b->xx_m, sizeof(h.xx_m));
+    memcpy(h.xx_s, b->xx_s, sizeof(h.xx_s));
+    hipLaunchKernelGGL(ape_kalman_bank_head_kernel, dim3(K), dim3(KB_BLOCK), 0, st, h);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: head launch failed: %s", what, hipGetErrorString(e));
+    if (int rc = ape_kalman_forward(b->model, b->raw, b->dense, K, seed, noise, b->corrected, b->mcorr, b->mpred, b->z, b->ensz, st)) return rc;
+    KbTailParams t{};
+    t.desc = desc_dev; t.cnt = b->cnt; t.z = b->z; t.corrected = b->corrected; t.init_noise = init_noise; t.seed = seed;
+    t.state = b->state; t.yring = b->yring; t.nring = b->nring; t.out = out; t.n_rows = n_rows; t.y_out = y;
+    t.K = K; t.E = b->E; t.W = b->W; t.smooth = b->smooth; t.packed = (flags & APE_FLAG_PACKED_MSG) ? 1 : 0;
+    t.normalize = h.normalize; t.cold_all = cold_all;
+    t.out_stride = t.packed ? 25 + 6 * b->smooth * b->E : 25;
+    const int period = b->W * b->smooth;
+    t.wrap = period * ((1 << 29) / period);
+    memcpy(t.yy_m, b->yy_m, sizeof(t.yy_m));
+    memcpy(t.yy_s, b->yy_s, sizeof(t.yy_s));
+    memcpy(t.body, b->body, sizeof(t.body));
+    if (out_dtype == APE_F32) hipLaunchKernelGGL(ape_kalman_bank_tail_kernel<float>, dim3(K), dim3(KB_BLOCK), 0, st, t);
+    else hipLaunchKernelGGL(ape_kalman_bank_tail_kernel<double>, dim3(K), dim3(KB_BLOCK), 0, st, t);
+    e = hipGetLastError();
+    if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: tail launch failed: %s", what, hipGetErrorString(e));
+    return APE_OK;
+}
+
+// one frame of a bank: the pending cold starts of the listed streams travel with the list
+int bank_frame(ape_kalman_bank* b, int32_t kind, const float* rows, const int32_t* streams_host, int32_t K, const float* noise,
+               const float* init_noise, uint32_t flags, void* out, int32_t out_dtype, int* n_rows, float* y, hipStream_t st, const char* what) {
+    const KbDesc* desc_dev = nullptr;
+    int cold_all = 0;
+    if (!streams_host && (b->n_pending == 0 || b->n_pending == b->S)) cold_all = b->n_pending ? 1 : 0;
+    else {
+        // the list into the next pinned slot -- once the copy that last read it has completed
+        const int k = b->next;
+        KB_TRY(hipEventSynchronize(b->ev[k]));
+        KbDesc* h = b->stage + (size_t)k * b->S;
+        for (int j = 0; j < K; ++j) {
+            const int s = streams_host ? streams_host[j] : j;
+            h[j] = KbDesc{s, b->pending[s] ? 1 : 0, j, j};
+        }
+        KB_TRY(hipMemcpyAsync(b->desc, h, (size_t)K * sizeof(KbDesc), hipMemcpyHostToDevice, st));
+        KB_TRY(hipEventRecord(b->ev[k], st));
+        b->next = (k + 1) % KB_STAGES;
+        desc_dev = b->desc;
+    }
+    if (int rc = frame_launch(b, (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0, rows, desc_dev, cold_all, K, noise, init_noise, flags, out, out_dtype,
+                              n_rows, y, st, what))
+        return rc;
+    for (int j = 0; j < K; ++j) {
+        const int s = streams_host ? streams_host[j] : j;
+        if (b->pending[s]) { b->pending[s] = 0; b->n_pending -= 1; }
+    }
+    return APE_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ape_kalman_bank_create(ape_kalman_t* model, int32_t n_streams, int32_t smooth, ape_kalman_bank_t** out) {
+    if (!model || !out) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_create: NULL argument");
+    *out = nullptr;
+    return bank_make(model, n_streams, smooth, "kalman_bank_create", out);
+}
+
+int ape_kalman_bank_destroy(ape_kalman_bank_t* b) {
+    if (!b) return APE_OK;
+    (void)hipSetDevice(b->device);
+    (void)hipDeviceSynchronize();          // frames may still read the rings and the staged lists
+    bank_free(b);
+    return APE_OK;
+}
+
+int ape_kalman_bank_reset(ape_kalman_bank_t* b) {
+    if (!b) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_reset: NULL bank");
+    b->pending.assign((size_t)b->S, 1);
+    b->n_pending = b->S;
+    return APE_OK;
+}
+
+int ape_kalman_bank_reset_subset(ape_kalman_bank_t* b, const int32_t* streams_host, int32_t K) {
+    if (!b || !streams_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_reset_subset: NULL argument");
+    if (int rc = check_list(b, streams_host, K, "kalman_bank_reset_subset")) return rc;
+    for (int j = 0; j < K; ++j)
+        if (!b->pending[streams_host[j]]) { b->pending[streams_host[j]] = 1; b->n_pending += 1; }
+    return APE_OK;
+}
+
+int ape_kalman_bank_set_norm_stats(ape_kalman_bank_t* b, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s) {
+    if (!b || !xx_m || !xx_s || !yy_m || !yy_s) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_norm_stats: NULL argument");
+    memcpy(b->xx_m, xx_m, sizeof(b->xx_m));
+    memcpy(b->xx_s, xx_s, sizeof(b->xx_s));
+    memcpy(b->yy_m, yy_m, sizeof(b->yy_m));
+    memcpy(b->yy_s, yy_s, sizeof(b->yy_s));
+    b->normalize = true;
+    return APE_OK;
+}
+
+int ape_kalman_bank_set_body(ape_kalman_bank_t* b, const double body9[9]) {
+    if (!b || !body9) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_body: NULL argument");
+    memcpy(b->body, body9, sizeof(b->body));
+    return APE_OK;
+}
+
+int ape_kalman_bank_set_seed(ape_kalman_bank_t* b, uint64_t seed) {
+    if (!b) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_seed: NULL bank");
+    b->seed = seed;
+    b->calls = 0;
+    return APE_OK;
+}
+
+int ape_kalman_bank_frame(ape_kalman_bank_t* b, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
+                          const float* noise_dev, const float* init_noise_dev, uint32_t flags, void* out_dev, int32_t out_dtype,
+                          int32_t* n_rows_dev, float* y_dev, void* stream) {
+    if (!b || !rows_dev || !out_dev || !n_rows_dev) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: NULL argument");
+    if (int rc = check_kind(kind, "kalman_bank_frame")) return rc;
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: unknown dtype selector");
+    if (flags & ~APE_FLAG_PACKED_MSG) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: flags 0x%x: APE_FLAG_PACKED_MSG or 0", flags);
+    if (int rc = check_list(b, streams_host, K, "kalman_bank_frame")) return rc;
+    KB_TRY(hipSetDevice(b->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "kalman_bank_frame")) return rc;
+    if (K == 0) return APE_OK;
+    return bank_frame(b, kind, rows_dev, streams_host, K, noise_dev, init_noise_dev, flags, out_dev, out_dtype, n_rows_dev, y_dev, st,
+                      "kalman_bank_frame");
+}
+
+int ape_kalman_bank_frame_host(ape_kalman_bank_t* b, int32_t kind, const float* rows_host, uint32_t flags, void* out_host, int32_t out_dtype,
+                               int32_t* n_rows_host, void* stream) {
+    if (!b || !rows_host || !out_host || !n_rows_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: NULL argument");
+    if (int rc = check_kind(kind, "kalman_bank_frame_host")) return rc;
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: unknown dtype selector");
+    if (flags & ~APE_FLAG_PACKED_MSG) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: flags 0x%x: APE_FLAG_PACKED_MSG or 0", flags);
+    KB_TRY(hipSetDevice(b->device));                         // (the consumer thread of an estimator starts on device 0)
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "kalman_bank_frame_host")) return rc;
+    // the head kernel reads the rows from and the tail kernel writes the messages to pinned host memory: no copy commands in the frame
+    const size_t rows_bytes = (size_t)b->S * KB_WIDTH * sizeof(float);
+    const size_t width = 25 + 6 * (size_t)b->smooth * b->E;
+    if (!b->h_rows) KB_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, hipHostMallocCoherent | hipHostMallocMapped));
+    if (!b->h_out) KB_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * width * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
+    if (!b->h_n) KB_TRY(hipHostMalloc((void**)&b->h_n, (size_t)b->S * sizeof(int), hipHostMallocCoherent | hipHostMallocMapped));
+    memcpy(b->h_rows, rows_host, rows_bytes);
+    if (int rc = bank_frame(b, kind, b->h_rows, nullptr, b->S, nullptr, nullptr, flags, b->h_out, out_dtype, b->h_n, nullptr, st,
+                            "kalman_bank_frame_host"))
+        return rc;
+    KB_TRY(hipStreamSynchronize(st));
+    const size_t w = (flags & APE_FLAG_PACKED_MSG) ? width : 25;
+    memcpy(out_host, b->h_out, (size_t)b->S * w * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
+    memcpy(n_rows_host, b->h_n, (size_t)b->S * sizeof(int));
+    return APE_OK;
+}
+
+int ape_kalman_replay(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                      int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s, const double body9[9],
+                      uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev, float* y_dev, void* stream) {
+    if (!model || !rows_dev || !out_dev || !n_rows_dev || !body9) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: NULL argument");
+    if (int rc = check_kind(kind, "kalman_replay")) return rc;
+    if (F < 1) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: F=%d must be >= 1", F);
+    if (R < 1 || R > F) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: %d recording starts for %d frames (1 <= R <= F)", R, F);
+    if (!seg_starts_host) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: NULL seg_starts");
+    if (seg_starts_host[0] != 0) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: seg_starts[0] = %d, must be 0", seg_starts_host[0]);
+    for (int i = 1; i < R; ++i)
+        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
+            return bfail(APE_ERR_INVALID_ARG, "kalman_replay: seg_starts[%d] = %d (strictly rising, below F = %d)", i, seg_starts_host[i], F);
+    if (smooth > KB_MAX_SMOOTH) return bfail(APE_ERR_UNSUPPORTED, "kalman_replay: smooth %d outside 1..%d", smooth, KB_MAX_SMOOTH);
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: unknown dtype selector");
+    if (flags & ~APE_FLAG_PACKED_MSG) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: flags 0x%x: APE_FLAG_PACKED_MSG or 0", flags);
+    const bool any = xx_m || xx_s || yy_m || yy_s;
+    if (any && !(xx_m && xx_s && yy_m && yy_s)) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: all four statistics or none");
+    if (R > 65535) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: %d recordings, at most 65535 in one call", R);
+    // ---- from here on the model is read.  The replay is a fresh bank of R streams: frame t lists the recordings that have a row t
+    struct Holder {
+        ape_kalman_bank* b = nullptr;
+        void* descs = nullptr;
+        ~Holder() { if (descs) (void)hipFree(descs); if (b) bank_free(b); }
+    } hold;
+    if (int rc = bank_make(model, R, smooth, "kalman_replay", &hold.b)) return rc;
+    ape_kalman_bank* b = hold.b;
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "kalman_replay")) return rc;
+    if (any) (void)ape_kalman_bank_set_norm_stats(b, xx_m, xx_s, yy_m, yy_s);
+    memcpy(b->body, body9, sizeof(b->body));
+    b->seed = seed;
+    std::vector<int> len((size_t)R);
+    int longest = 0;
+    for (int r = 0; r < R; ++r) {
+        len[r] = (r + 1 < R ? seg_starts_host[r + 1] : F) - seg_starts_host[r];
+        if (len[r] > longest) longest = len[r];
+    }
+    std::vector<KbDesc> descs;
+    descs.reserve((size_t)F);
+    std::vector<int> first((size_t)longest + 1, 0);
+    for (int t = 0; t < longest; ++t) {
+        for (int r = 0; r < R; ++r)
+            if (len[r] > t) descs.push_back(KbDesc{r, t == 0 ? 1 : 0, seg_starts_host[r] + t, seg_starts_host[r] + t});
+        first[t + 1] = (int)descs.size();
+    }
+    KB_TRY(hipMalloc(&hold.descs, descs.size() * sizeof(KbDesc)));
+    KB_TRY(hipMemcpyAsync(hold.descs, descs.data(), descs.size() * sizeof(KbDesc), hipMemcpyHostToDevice, st));
+    int rc = APE_OK;
+    for (int t = 0; t < longest && rc == APE_OK; ++t)
+        rc = frame_launch(b, (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0, rows_dev, (const KbDesc*)hold.descs + first[t], 0, first[t + 1] - first[t],
+                          nullptr, nullptr, flags, out_dev, out_dtype, n_rows_dev, y_dev, st, "kalman_replay");
+    const hipError_t e = hipStreamSynchronize(st);            // the bank and the lists are freed behind this
+    if (rc != APE_OK) return rc;
+    if (e != hipSuccess) return bfail(APE_ERR_HIP, "kalman_replay: synchronise failed: %s", hipGetErrorString(e));
+    return APE_OK;
+}
+
+}  // extern "C"

@@ -114,6 +114,18 @@ SIGNATURES = {
     "ape_kalman_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p] + [C.c_void_p] * 6),
     "ape_kalman_format_state": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "ape_kalman_check": (C.c_int, [C.c_void_p]),
+    "ape_kalman_bank_create": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "ape_kalman_bank_destroy": (C.c_int, [C.c_void_p]),
+    "ape_kalman_bank_reset": (C.c_int, [C.c_void_p]),
+    "ape_kalman_bank_reset_subset": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32]),
+    "ape_kalman_bank_set_norm_stats": (C.c_int, [C.c_void_p] + [C.POINTER(C.c_double)] * 4),
+    "ape_kalman_bank_set_body": (C.c_int, [C.c_void_p, C.POINTER(C.c_double)]),
+    "ape_kalman_bank_set_seed": (C.c_int, [C.c_void_p, C.c_uint64]),
+    "ape_kalman_bank_frame": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_uint32,
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "ape_kalman_bank_frame_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ape_kalman_replay": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] +
+                          [C.POINTER(C.c_double)] * 5 + [C.c_uint64, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

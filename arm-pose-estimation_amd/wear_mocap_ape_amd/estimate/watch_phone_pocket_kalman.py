@@ -2,8 +2,10 @@
 (``estimate/watch_phone_pocket_kalman.py:12-169``, ``example_scripts/stream/watch_phone_pocket.py``): same features and
 targets as ``WatchPhonePocketNN``, the regressor replaced by ``KalmanSmartwatchModel``; the corrected ensemble takes the
 place of the Monte-Carlo samples.  PARITY UNPINNED (see ``estimate/kalman_models.py``)."""
+import ctypes as C
 from pathlib import Path
 
+import numpy as np
 import torch
 
 from wear_mocap_ape_amd import _hip
@@ -12,6 +14,56 @@ from wear_mocap_ape_amd.estimate import kalman_models
 from wear_mocap_ape_amd.estimate.estimator import Estimator
 from wear_mocap_ape_amd.estimate.watch_phone_pocket_nn import features_from_row
 from wear_mocap_ape_amd.utility.names import NNS_INPUTS, NNS_TARGETS
+
+
+class _KalmanDeviceFrame:
+    """One iteration of the consumer loop as ONE call into libape_hip.so: a one-stream bank (``ape_kalman_bank_*``)
+    keeps the window, the state history and the smoothing stack on the device; ``ape_kalman_bank_frame_host`` takes the raw 55-float
+    message and returns the packed message row and its stacked-row count.  PARITY UNPINNED like the model it runs."""
+
+    def __init__(self, model, smooth: int, stats, body, add_mc_samples: bool, seed: int):
+        self._lib, self._model, self._seed = _hip.lib(), model, int(seed) & (2 ** 64 - 1)
+        self._bank = C.c_void_p()
+        _hip.check(self._lib.ape_kalman_bank_create(model.handle, 1, smooth, C.byref(self._bank)), "ape_kalman_bank_create")
+        b = np.ascontiguousarray(np.asarray(body, dtype=np.float64).reshape(9))
+        _hip.check(self._lib.ape_kalman_bank_set_body(self._bank, _hip.dptr(b, C.c_double)), "ape_kalman_bank_set_body")
+        if stats is not None:
+            self.set_norm_stats(stats)
+        self.manual_seed(self._seed)
+        self._flags = _hip.FLAG_PACKED_MSG if add_mc_samples else 0
+        self._row = np.empty((55,), dtype=np.float32)
+        self._out = np.zeros((25 + 6 * max(1, smooth) * model._num_ensemble,), dtype=np.float64)
+        self._n = np.zeros((1,), dtype=np.int32)
+        self._row_p, self._out_p, self._n_p = (C.c_void_p(a.ctypes.data) for a in (self._row, self._out, self._n))
+
+    def __del__(self):
+        bank, self._bank = getattr(self, "_bank", None), None
+        try:
+            if bank:
+                self._lib.ape_kalman_bank_destroy(bank)
+        except Exception:          # interpreter shutdown
+            pass
+
+    def set_norm_stats(self, stats):
+        a = [np.ascontiguousarray(np.asarray(stats[k], dtype=np.float64).reshape(-1)) for k in ("xx_m", "xx_s", "yy_m", "yy_s")]
+        _hip.check(self._lib.ape_kalman_bank_set_norm_stats(self._bank, *[_hip.dptr(v, C.c_double) for v in a]),
+                   "ape_kalman_bank_set_norm_stats")
+
+    def manual_seed(self, seed: int):
+        self._seed = int(seed) & (2 ** 64 - 1)
+        _hip.check(self._lib.ape_kalman_bank_set_seed(self._bank, self._seed), "ape_kalman_bank_set_seed")
+
+    def reset(self):
+        """cold start, and the draws start again: a reset estimator repeats its run"""
+        _hip.check(self._lib.ape_kalman_bank_reset(self._bank), "ape_kalman_bank_reset")
+        self.manual_seed(self._seed)
+
+    def frame(self, row):
+        """raw message -> (float64 packed row, stacked-row count); a view of this object's buffer, overwritten by the next frame"""
+        self._row[:] = row
+        _hip.check(self._lib.ape_kalman_bank_frame_host(self._bank, _hip.PARSE_WATCH_PHONE_POCKET, self._row_p, self._flags, self._out_p,
+                                                        _hip.F64, self._n_p, None), "ape_kalman_bank_frame_host")
+        return self._out, int(self._n[0])
 
 
 class WatchPhonePocketKalman(Estimator):
@@ -79,3 +131,80 @@ class WatchPhonePocketKalman(Estimator):
         ensemble = output[0]
         self.__input_state = torch.cat((self.__input_state[:, :, 1:, :], ensemble[:, :, None, :]), axis=2)
         return ensemble.cpu().numpy()[0][:, :14]
+
+    # ---- the device-resident frame and the offline replay; PARITY UNPINNED like everything above ----------------
+    frame_seed = 0x5EED        # seed of the device frame's draws (manual_seed)
+
+    def manual_seed(self, seed: int):
+        """seed of the device-resident frame's draws (flipout perturbations, signs, format_state); the call counter starts again"""
+        self.frame_seed = int(seed)
+        if getattr(self, "_device_frame", None) is not None:
+            self._device_frame.manual_seed(seed)
+        return self
+
+    def _stats(self):
+        return {"xx_m": self._xx_m, "xx_s": self._xx_s, "yy_m": self._yy_m, "yy_s": self._yy_s} if self._normalize else None
+
+    def set_norm_stats(self, stats: dict):
+        super().set_norm_stats(stats)
+        if getattr(self, "_device_frame", None) is not None:
+            self._device_frame.set_norm_stats(stats)
+
+    def _frame_runner(self):
+        if not self.use_device_frame:
+            return None
+        if getattr(self, "_device_frame", None) is None:
+            self._device_frame = _KalmanDeviceFrame(self.__model, self._smooth, self._stats(), self._body_measurements,
+                                                    self._add_mc_samples, self.frame_seed)
+        return self._device_frame
+
+    def process_row(self, row):
+        """one iteration of the consumer loop (estimator.py:174-177) as one ``ape_kalman_bank_frame_host`` call: the same types and
+        lengths as the staged path (``use_device_frame = False``) -- 25 values while the stack holds one row, 25 + 6 n for n > 1
+        stacked rows (n grows from ``smooth`` to ``smooth * num_ensemble`` once the filter is initialised)"""
+        frame = self._frame_runner()
+        if frame is None:
+            return super().process_row(row)
+        out, n = frame.frame(row)
+        self._last_msg = out[:25].copy()
+        if not self._add_mc_samples:
+            return self._last_msg.copy()
+        cut = out[:25 + 6 * n] if n > 1 else out[:25]
+        return cut.copy() if self.msg_as_array else cut.tolist()
+
+    def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64, return_targets: bool = False,
+                          seed: int = 0x5EED):
+        """rows: float32 ``[F, 55]`` raw messages of one or more recordings back to back (host array or CUDA tensor); ``starts``: the
+        recordings' first rows (default ``[0]``).  Returns ``(out, n_rows)`` on the device -- for every row what ``process_row`` of a
+        fresh estimator with ``manual_seed(seed)`` fed that recording returns (no row skipped; several recordings share the flipout
+        draw of a frame, ``ape_kalman_replay``): ``out`` is ``[F, 25 + 6 * smooth * num_ensemble]`` with ``add_mc_samples`` (message,
+        hand and elbow xyz of the ``n_rows[f]`` stacked rows, zeros; ``streams.trim_packed`` cuts a row), else ``[F, 25]``.  With
+        ``return_targets`` also the normalised predictions float32 ``[F, num_ensemble, 14]`` (row 0 alone on a recording's first
+        W + 1 frames)."""
+        if out_dtype not in (torch.float32, torch.float64):
+            raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+        model = self.__model
+        dev = model.torch_device
+        with torch.cuda.device(dev):
+            rd = torch.as_tensor(rows, dtype=torch.float32).to(dev).contiguous()
+            if rd.dim() != 2 or rd.shape[1] != 55 or rd.shape[0] < 1:
+                raise UserWarning(f"expected rows [F>=1,55], got {tuple(rd.shape)}")
+            F = int(rd.shape[0])
+            st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
+            packed = bool(self._add_mc_samples)
+            out = torch.empty((F, 25 + 6 * self._smooth * self.__num_ensemble if packed else 25), dtype=out_dtype, device=dev)
+            n_rows = torch.empty((F,), dtype=torch.int32, device=dev)
+            y = torch.empty((F, self.__num_ensemble, 14), dtype=torch.float32, device=dev) if return_targets else None
+            stats = self._stats()
+            sp = [None] * 4 if stats is None else [_hip.dptr(np.ascontiguousarray(stats[k], dtype=np.float64), C.c_double)
+                                                   for k in ("xx_m", "xx_s", "yy_m", "yy_s")]
+            body = np.ascontiguousarray(self._body_measurements.reshape(9), dtype=np.float64)
+            kind = _hip.PARSE_WATCH_PHONE_POCKET | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _hip.check(_hip.lib().ape_kalman_replay(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
+                                                    int(st.shape[0]), self._smooth, *sp, _hip.dptr(body, C.c_double),
+                                                    int(seed) & (2 ** 64 - 1), _hip.FLAG_PACKED_MSG if packed else 0,
+                                                    C.c_void_p(out.data_ptr()), _hip.F64 if out_dtype == torch.float64 else _hip.F32,
+                                                    C.c_void_p(n_rows.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
+                                                    stream), "ape_kalman_replay")
+        return (out, n_rows, y) if return_targets else (out, n_rows)

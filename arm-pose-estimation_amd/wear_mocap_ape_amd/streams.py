@@ -327,3 +327,152 @@ class FkStreamBank:
         hip.check(hip.lib().ape_fk_bank_frame(self._handle, kind, C.c_void_p(rd.data_ptr()), C.c_void_p(idx.ctypes.data), K,
                                               C.c_void_p(out.data_ptr()), self._sel, self._stream()), "ape_fk_bank_frame")
         return out
+
+
+def trim_packed(row, n_rows: int):
+    """a packed row ``[25 + 6 * smooth * E]`` of a Kalman bank cut to what the reference sends (estimator.py:131-137): the 25-value
+    message, followed by hand and elbow xyz of the ``n_rows`` stacked rows when there is more than one"""
+    n = int(n_rows)
+    return row[:25 + 6 * n] if n > 1 else row[:25]
+
+
+class KalmanStreamBank:
+    """The per-frame step of many independent ``WatchPhonePocketKalman`` streams with every history on the device (C ABI
+    ``ape_kalman_bank_*``): for every listed stream what one ``WatchPhonePocketKalman.process_row`` does -- feature
+    builder, window, float64 z-score, the ensemble Kalman model on the stream's own state history, the sensor mean on the stream's
+    first W + 1 frames and the corrected ensemble afterwards, de-normalisation, the smoothing stack with its ragged entries, FK and
+    message.  PARITY UNPINNED (see ``estimate/kalman_models.py``): the checker is the oracle's restatement.
+
+    ``model``: a loaded ``kalman_models.KalmanSmartwatchModel`` (the bank keeps it alive).  Each stream keeps its own count of frames
+    since its cold start, so lockstep frames (``step_rows``) and subset frames (``frame``) mix freely.  One flipout draw per call is
+    shared by the call's streams; the signs and ``format_state`` draws of a stream depend on its list position.  ``seed`` keys the
+    device-side draws together with the number of the call: two banks with one seed fed the same calls return the same bits."""
+
+    def __init__(self, model, n_streams: int, smooth: int = 1, normalize: bool = True, bonemap=None, seed: int = 0x5EED,
+                 dtype: torch.dtype = torch.float64):
+        from . import _hip
+        from .data_types.bone_map import BoneMap
+        import ctypes as C
+        self._hip, self._C = _hip, C
+        if dtype not in (torch.float32, torch.float64):
+            raise UserWarning(f"KalmanStreamBank messages are float32 or float64, not {dtype}")
+        if int(n_streams) < 1:
+            raise UserWarning(f"KalmanStreamBank needs n_streams >= 1, got {n_streams}")
+        self._model = model
+        self._n, self._smooth = int(n_streams), max(1, int(smooth))
+        self._E, self._W = int(model._num_ensemble), int(model.win_size)
+        self._dtype, self._sel = dtype, (_hip.F32 if dtype == torch.float32 else _hip.F64)
+        self._device = model.torch_device
+        handle = C.c_void_p()
+        _hip.check(_hip.lib().ape_kalman_bank_create(model.handle, self._n, self._smooth, C.byref(handle)), "ape_kalman_bank_create")
+        self._handle = handle
+        larm = BoneMap.DEFAULT_LARM_LEN if bonemap is None else bonemap.left_lower_arm_length
+        uarm = BoneMap.DEFAULT_UARM_LEN if bonemap is None else bonemap.left_upper_arm_length
+        orig = BoneMap.DEFAULT_UARM_ORIG_RH if bonemap is None else bonemap.left_upper_arm_origin_rh
+        self.set_body(np.r_[[-larm, 0, 0], [-uarm, 0, 0], orig])
+        if normalize:
+            from .utility import data_stats
+            from .utility.names import NNS_INPUTS, NNS_TARGETS
+            self.set_norm_stats(data_stats.get_norm_stats(x_inputs=NNS_INPUTS.WATCH_PHONE_CAL_HIP, y_targets=NNS_TARGETS.ORI_CAL_LARM_UARM_HIPS))
+        self.manual_seed(seed)
+        self._width = 25 + 6 * self._smooth * self._E
+        self._bufs = {}
+
+    def __del__(self):
+        h, self._handle = getattr(self, "_handle", None), None
+        try:
+            if h:
+                self._hip.lib().ape_kalman_bank_destroy(h)
+        except Exception:          # interpreter shutdown
+            pass
+
+    n_streams = property(lambda self: self._n)
+    packed_width = property(lambda self: self._width)
+    body_measurements = property(lambda self: self._body[np.newaxis, :].copy())
+
+    def set_body(self, body9):
+        self._body = np.ascontiguousarray(np.asarray(body9, dtype=np.float64).reshape(9))
+        self._hip.check(self._hip.lib().ape_kalman_bank_set_body(self._handle, self._hip.dptr(self._body, self._C.c_double)),
+                        "ape_kalman_bank_set_body")
+
+    def set_norm_stats(self, stats: dict):
+        """float64 statistics ``xx_m, xx_s`` [22] and ``yy_m, yy_s`` [14]; from the next frame on"""
+        a = [np.ascontiguousarray(np.asarray(stats[k], dtype=np.float64).reshape(-1)) for k in ("xx_m", "xx_s", "yy_m", "yy_s")]
+        if [v.size for v in a] != [22, 22, 14, 14]:
+            raise UserWarning(f"the Kalman bank wants 22 input and 14 target statistics, got {[v.size for v in a]}")
+        self._hip.check(self._hip.lib().ape_kalman_bank_set_norm_stats(self._handle, *[self._hip.dptr(v, self._C.c_double) for v in a]),
+                        "ape_kalman_bank_set_norm_stats")
+
+    def manual_seed(self, seed: int):
+        """seed of the device-side draws; the call counter starts again"""
+        self._hip.check(self._hip.lib().ape_kalman_bank_set_seed(self._handle, int(seed) & (2 ** 64 - 1)), "ape_kalman_bank_set_seed")
+        return self
+
+    def _stream(self):
+        return self._C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
+
+    _indices = StreamBank._indices          # in range, distinct, int32
+    _rows = FkStreamBank._rows
+
+    def reset(self, streams=None):
+        """cold start: ``streams=None`` every stream, else only the listed (distinct) ones"""
+        if streams is None:
+            self._hip.check(self._hip.lib().ape_kalman_bank_reset(self._handle), "ape_kalman_bank_reset")
+            return
+        idx = self._indices(streams)
+        self._hip.check(self._hip.lib().ape_kalman_bank_reset_subset(self._handle, self._C.c_void_p(idx.ctypes.data), int(idx.shape[0])),
+                        "ape_kalman_bank_reset_subset")
+
+    def _buf(self, key, shape, dtype):
+        if key not in self._bufs:
+            self._bufs[key] = torch.empty(shape, dtype=dtype, device=self._device)
+        return self._bufs[key]
+
+    def _frame(self, rows, idx, big_endian, datagrams, noise, init_noise, return_targets, tag):
+        hip, C = self._hip, self._C
+        K = self._n if idx is None else int(idx.shape[0])
+        rd = self._rows(rows, K)
+        w = self._width if datagrams else 25
+        out = self._buf((tag, "out", datagrams), (self._n, w), self._dtype)[:K]
+        n_rows = self._buf((tag, "n"), (self._n,), torch.int32)[:K]
+        y = self._buf((tag, "y"), (self._n, self._E, 14), torch.float32)[:K] if return_targets else None
+        res = (out, n_rows) if datagrams else out
+        if return_targets:
+            res = (res + (y,)) if datagrams else (out, y)
+        if K == 0:
+            return res
+        p = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None      # noqa: E731
+        nz = ini = None
+        if noise is not None:
+            nz = torch.as_tensor(noise, dtype=torch.float32).to(self._device).contiguous()
+            if nz.numel() != self._model.noise_floats(K):
+                raise UserWarning(f"frame noise must hold {self._model.noise_floats(K)} values for {K} streams")
+        if init_noise is not None:
+            ini = torch.as_tensor(init_noise, dtype=torch.float32).to(self._device).contiguous()
+            if ini.numel() != K * self._E * 14:
+                raise UserWarning(f"frame init_noise must hold [{K},{self._E},14] values")
+        kind = hip.PARSE_WATCH_PHONE_POCKET | (hip.PARSE_BIG_ENDIAN if big_endian else 0)
+        hip.check(hip.lib().ape_kalman_bank_frame(self._handle, kind, p(rd), C.c_void_p(idx.ctypes.data) if idx is not None else None, K,
+                                                  p(nz), p(ini), hip.FLAG_PACKED_MSG if datagrams else 0, p(out), self._sel, p(n_rows),
+                                                  p(y), self._stream()), "ape_kalman_bank_frame")
+        self._keep = (rd, nz, ini)           # the launches read them behind this call
+        return res
+
+    def step_rows(self, rows, big_endian: bool = False, datagrams: bool = False, noise=None, init_noise=None, return_targets: bool = False):
+        """lockstep frame: float32 ``[S, 55]`` rows (host array or device tensor), row s for stream s -> ``[S, 25]`` messages of the
+        bank's dtype; see ``frame`` for the other arguments.  The bank's own buffers, overwritten by the next lockstep frame."""
+        return self._frame(rows, None, big_endian, datagrams, noise, init_noise, return_targets, "step")
+
+    def frame(self, rows, streams, big_endian: bool = False, datagrams: bool = False, noise=None, init_noise=None,
+              return_targets: bool = False):
+        """subset frame: float32 ``[K, 55]`` rows, row j for stream ``streams[j]`` (K distinct indices) -> ``[K, 25]`` in list order.
+        Streams not listed are untouched.  ``datagrams``: ``([K, 25 + 6 * smooth * E], n_rows int32 [K])`` instead -- the message,
+        hand and elbow xyz of the ``n_rows[j]`` stacked rows, zeros; ``trim_packed(row, n)`` cuts a row to the reference's length.
+        ``return_targets`` appends the frame's normalised predictions float32 ``[K, E, 14]`` (row 0 alone while a stream is in its
+        first W + 1 frames).  ``noise`` / ``init_noise`` inject the draws of this call (``ape_kalman_noise_floats(K)`` values and
+        ``[K, E, 14]``): tests.  The bank's own buffers, overwritten by the next subset frame."""
+        return self._frame(rows, self._indices(streams), big_endian, datagrams, noise, init_noise, return_targets, "sub")
+
+    def check(self):
+        """blocking: raises if a frame met an exactly singular innovation matrix (``ape_kalman_check``)"""
+        self._model.check()

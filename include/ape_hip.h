@@ -458,6 +458,58 @@ int ape_kalman_format_state(ape_kalman_t* model, const float* state_dev, int32_t
 /* BLOCKING: non-zero if a forward since the last check met an exactly singular innovation matrix (torch.linalg.inv raises) */
 int ape_kalman_check(ape_kalman_t* model);
 
+/* ---- the Kalman estimator's frame: device stream bank, one-call frames, offline replay (additive in ABI 7) --------
+ * PARITY UNPINNED like the entries above: what is added is the bookkeeping around ape_kalman_forward -- the frame of
+ * WatchPhonePocketKalman (watch_phone_pocket_kalman.py:57-63, 133-169) inside Estimator (estimator.py:93-137) -- and its checker is
+ * oracle/kalman_oracle.py's KalmanFrameLogic chained with oracle/ape_oracle.py's WindowOracle and post-filter.
+ * A bank is bound to a loaded ape_kalman_t (which must outlive it) and holds S streams, each with its own window of W feature rows,
+ * state history [E,W,14], smoothing stack and count of frames since its cold start, all on the device.  For every listed stream a
+ * frame parses the row (APE_PARSE_WATCH_PHONE_POCKET, may carry APE_PARSE_BIG_ENDIAN), pushes the features (the first row after a
+ * cold start fills the window), z-scores in float64, runs the model on the window and the stream's state history (zeros after a
+ * cold start), takes the sensor model's mean z [1,14] on the stream's first W + 1 frames (format_state(z) joins the history) and
+ * the corrected ensemble [E,14] afterwards (it joins the history), de-normalises in float64, pushes onto the stack of `smooth`
+ * entries (padded with the newest on a cold start; entries have 1 or E rows) and runs FK (APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS) and
+ * the 25-value message over all stacked rows.
+ *   rows_dev     f32 [K,55], row j for stream streams_host[j] (K distinct indices in host memory; NULL => K == S, all in order).
+ *                Lockstep and subset frames mix freely; streams not listed stay bit for bit untouched.  K = 0 is a no-op.
+ *   noise_dev    NULL (Philox) or ape_kalman_noise_floats(K) injected draws of this call, rows = (list position j, member e)
+ *   init_noise_dev  NULL (Philox) or f32 [K,E,14] standard-normal draws for format_state
+ *   flags        0 or APE_FLAG_PACKED_MSG
+ *   out_dev      [K,25] of out_dtype; APE_FLAG_PACKED_MSG: [K, 25 + 6*smooth*E], the message, then hand and elbow xyz of the
+ *                n_rows[j] stacked rows, oldest entry first (estimator.py:131-137), then zeros.  F32 is the float64 message rounded.
+ *   n_rows_dev   int32 [K]: stacked rows of entry j, between smooth and smooth*E
+ *   y_dev        NULL or f32 [K,E,14]: the frame's normalised prediction (row 0 alone on the first W + 1 frames, the rest unspecified)
+ * One flipout perturbation draw per call, shared by all its rows (as ape_kalman_forward for S > 1).  Device draws are keyed by the
+ * bank's seed (ape_kalman_bank_set_seed, which also restarts the call counter) and the number of the call: no two frames of a bank
+ * share a key, two banks with one seed fed the same calls give the same bits.  ape_kalman_bank_set_norm_stats: xx [22], yy [14];
+ * never called = no normalisation.  ape_kalman_bank_set_body: [larm_vec, uarm_vec, uarm_orig_rh]; zeros until set.
+ * ape_kalman_bank_frame is asynchronous on `stream` (ONE bank serialises on ONE stream); ape_kalman_bank_frame_host is one lockstep
+ * frame from host rows [S,55] to host messages and row counts, BLOCKING (what process_row calls).
+ * ape_kalman_replay: every frame of R recordings back to back in rows_dev [F,55] (seg_starts_host: their first rows, [0] first,
+ *   strictly rising, below F): a fresh bank of R streams with seed `seed`, frame t lists in ascending order the recordings that have
+ *   a row t; outputs in recording order (row seg_starts[r] + t of out_dev [F, 25 | 25 + 6*smooth*E], n_rows_dev [F], y_dev
+ *   [F,E,14]).  xx_m .. yy_s all NULL: no normalisation.  BLOCKING.
+ * Refused (non-zero, ape_last_error): NULL arguments, weights not loaded, a kind other than APE_PARSE_WATCH_PHONE_POCKET, K < 0 or
+ * K > S, an index outside [0, S) or listed twice, smooth > 64 or smooth*E > 4096, bad replay starts, F < 1, a capturing stream.
+ * ape_kalman_check reports a singular innovation of any bank frame. */
+typedef struct ape_kalman_bank ape_kalman_bank_t;
+int ape_kalman_bank_create(ape_kalman_t* model, int32_t n_streams, int32_t smooth, ape_kalman_bank_t** out);
+int ape_kalman_bank_destroy(ape_kalman_bank_t* bank);
+int ape_kalman_bank_reset(ape_kalman_bank_t* bank);
+int ape_kalman_bank_reset_subset(ape_kalman_bank_t* bank, const int32_t* streams_host, int32_t K);
+int ape_kalman_bank_set_norm_stats(ape_kalman_bank_t* bank, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s);
+int ape_kalman_bank_set_body(ape_kalman_bank_t* bank, const double body9[9]);
+int ape_kalman_bank_set_seed(ape_kalman_bank_t* bank, uint64_t seed);
+int ape_kalman_bank_frame(ape_kalman_bank_t* bank, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
+                          const float* noise_dev, const float* init_noise_dev, uint32_t flags, void* out_dev, int32_t out_dtype,
+                          int32_t* n_rows_dev, float* y_dev, void* stream);
+int ape_kalman_bank_frame_host(ape_kalman_bank_t* bank, int32_t kind, const float* rows_host, uint32_t flags, void* out_host,
+                               int32_t out_dtype, int32_t* n_rows_host, void* stream);
+int ape_kalman_replay(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                      int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
+                      const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
+                      float* y_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
