@@ -1428,7 +1428,7 @@ static int check_and_reset(ape_model_t* m) {
 }
 
 static int fk_impl(ape_model_t* m, const void* preds_dev, int32_t preds_dtype, int32_t N, int32_t denormalize, void* est_dev,
-                   int32_t est_dtype, void* stream);
+                   int32_t est_dtype, void* stream, const FkBodyRows* bodies = nullptr);
 
 int ape_fk(ape_model_t* m, const void* preds_dev, int32_t preds_dtype, int32_t N, int32_t denormalize, void* est_dev,
            int32_t est_dtype, void* stream) {
@@ -1443,7 +1443,7 @@ int ape_fk(ape_model_t* m, const void* preds_dev, int32_t preds_dtype, int32_t N
 }
 
 static int fk_impl(ape_model_t* m, const void* preds_dev, int32_t preds_dtype, int32_t N, int32_t denormalize, void* est_dev,
-                   int32_t est_dtype, void* stream) {
+                   int32_t est_dtype, void* stream, const FkBodyRows* bodies) {
     if (!m || !preds_dev || !est_dev) return fail(APE_ERR_INVALID_ARG, "fk: NULL argument");
     if (N < 1) return fail(APE_ERR_INVALID_ARG, "fk: N=%d must be >= 1", N);
     if ((preds_dtype != APE_F32 && preds_dtype != APE_F64) || (est_dtype != APE_F32 && est_dtype != APE_F64))
@@ -1459,7 +1459,7 @@ static int fk_impl(ape_model_t* m, const void* preds_dev, int32_t preds_dtype, i
     }
     memcpy(p.body, m->body, sizeof(p.body));
     p.N = N; p.O = m->dims.output_size; p.layout = m->dims.target_layout; p.W = layout_est_width(p.layout);
-    hipError_t e = ape_launch_fk(p, preds_dtype, est_dtype, (hipStream_t)stream);
+    hipError_t e = ape_launch_fk(p, preds_dtype, est_dtype, (hipStream_t)stream, bodies);
     if (e != hipSuccess) return fail(APE_ERR_HIP, "fk kernel launch failed: %s", hipGetErrorString(e));
     return APE_OK;
 }
@@ -1740,6 +1740,7 @@ int ape_streams_destroy(ape_streams_t* b) {
     if (b->h_done) (void)hipHostFree(b->h_done);
     for (auto ev : b->prof_ev) if (ev) (void)hipEventDestroy(ev);
     subset_free(b);                     // (drops the bank's pending subset frame as below)
+    ape_body_table_free(b->bodies);
     for (auto ev : b->sub_ev) if (ev) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
     if (b->sub_stage) (void)hipHostFree(b->sub_stage);
     if (ape_model* m = b->model) {      // pending steps of this bank can no longer be re-issued
@@ -1758,6 +1759,29 @@ int ape_streams_reset(ape_streams_t* b) {
     if (!b) return fail(APE_ERR_INVALID_ARG, "streams_reset: NULL bank");
     b->frames = 0; b->steps = 0;
     b->per_stream = false;                       // every stream cold: the lockstep calls serve the bank again
+    return APE_OK;
+}
+
+static int subset_check_list(const ape_streams* b, const int32_t* streams_host, int32_t K, const char* what);
+
+// per-stream body measurements: replaces the bonemap every reference Estimator is built with (estimator.py:57-68).
+// No cold start: windows and stacks hold features and NN targets, which do not depend on the body.
+int ape_streams_set_bodies(ape_streams_t* b, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream) {
+    if (!b || !body9s_host) return fail(APE_ERR_INVALID_ARG, "streams_set_bodies: NULL argument");
+    if (streams_host) {
+        if (int rc = subset_check_list(b, streams_host, K, "streams_set_bodies")) return rc;
+    } else if (K != b->S) return fail(APE_ERR_INVALID_ARG, "streams_set_bodies: no stream list: K=%d must be S=%d", K, b->S);
+    HIP_TRY(hipSetDevice(b->model->dims.device));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "streams_set_bodies: the stream is capturing (the table's image is staged per call)");
+    HIP_TRY(ape_body_table_set(b->bodies, b->S, false, b->model->body, streams_host, K, body9s_host, (hipStream_t)stream));
+    return APE_OK;
+}
+
+int ape_streams_get_bodies(ape_streams_t* b, double* out_host) {
+    if (!b || !out_host) return fail(APE_ERR_INVALID_ARG, "streams_get_bodies: NULL argument");
+    ape_body_table_get(b->bodies, b->S, b->model->body, out_host);
     return APE_OK;
 }
 
@@ -2051,7 +2075,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         ++b->mc_calls;
     }
     StreamPostParams q = post_params();
-    hipError_t e = ape_launch_stream_post(q, (hipStream_t)stream);
+    hipError_t e = ape_launch_stream_post(q, (hipStream_t)stream, b->bodies.dev);      // (table mode: row s for stream s, q.body unread)
     if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step launch failed: %s", hipGetErrorString(e));
     ++b->steps;
     journal_add(m, je);
@@ -2265,7 +2289,7 @@ static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_
     q.smooth = b->smooth; q.n_mc = b->n_mc;
     q.msg_dtype = out_dtype; q.packed = packed ? 1 : 0;
     q.part = b->post_part; q.part_cnt = b->post_cnt;     // (sized for S >= K entries)
-    hipError_t e = ape_launch_stream_post_subset(q, b->sub_desc, (hipStream_t)stream);
+    hipError_t e = ape_launch_stream_post_subset(q, b->sub_desc, (hipStream_t)stream, b->bodies.dev);
     if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset: post-filter launch failed: %s", hipGetErrorString(e));
     return APE_OK;
 }
@@ -2370,6 +2394,15 @@ struct ApeDeviceScratch {                         // the call's device workspace
 int ape_replay(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
                void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream) {
+    return ape_replay_bodies(m, kind, rows_dev, F, seg_starts_host, R, seq_len, smooth, n_mc, dropout_p, seed, flags, out_dev, out_dtype, y_dev,
+                             max_rows_per_launch, stream, nullptr);
+}
+
+// bodies_host [R,9]: recording r's rows as a fresh estimator BUILT WITH recording r's bonemap returns them (estimator.py:57-68); NULL: the
+// model's body for every recording, on the kernels ape_replay always ran
+int ape_replay_bodies(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                      int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+                      void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream, const double* bodies_host) {
     // the arguments on their own first (no device needed to refuse them)
     if (!rows_dev || !out_dev) return fail(APE_ERR_INVALID_ARG, "replay: NULL argument");
     int width, I;
@@ -2435,12 +2468,19 @@ int ape_replay(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, c
     HIP_TRY(ws.alloc((void**)&est[0], (size_t)(carry + rmax) * W * sizeof(double)));
     HIP_TRY(ws.alloc((void**)&est[1], (size_t)(carry + rmax) * W * sizeof(double)));
     HIP_TRY(hipMemcpyAsync(starts_d, seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st));
+    double* bodies_d = nullptr;                   // one body per recording: the values and every frame's recording index
+    int* rec_of = nullptr;
+    if (bodies_host) {
+        HIP_TRY(ws.alloc((void**)&bodies_d, (size_t)R * 9 * sizeof(double)));
+        HIP_TRY(ws.alloc((void**)&rec_of, (size_t)F * sizeof(int)));
+        HIP_TRY(hipMemcpyAsync(bodies_d, bodies_host, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
 
     const bool drop = dropout_p > 0.0f && m->dims.num_layers > 1;
     const uint32_t lflags = (norm ? APE_FLAG_NORMALIZE_INPUT : 0u) | (drop ? APE_FLAG_DROPOUT_PHILOX : 0u);
     auto pass = [&]() -> int {
         hipError_t e = ape_launch_parse_rows(rows_dev, F, width, kind & ~APE_PARSE_BIG_ENDIAN, xx, APE_F32, I, (size_t)I, 1, 0, big_endian, st);
-        if (e == hipSuccess) e = ape_launch_replay_segments(starts_d, R, F, seg_of, st);
+        if (e == hipSuccess) e = ape_launch_replay_segments(starts_d, R, F, seg_of, st, rec_of);
         if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: feature launch failed: %s", hipGetErrorString(e));
         long long prev_rows = 0;
         for (long long r0 = 0, c = 0; r0 < total; r0 += rmax, ++c) {
@@ -2457,13 +2497,14 @@ int ape_replay(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, c
             if (c > 0)
                 HIP_TRY(hipMemcpyAsync(cur, est[(c + 1) & 1] + (size_t)prev_rows * W, (size_t)carry * W * sizeof(double),
                                        hipMemcpyDeviceToDevice, st));
-            if (int rc = fk_impl(m, y, APE_F32, rows, norm ? 1 : 0, cur + (size_t)carry * W, APE_F64, stream)) return rc;
+            const FkBodyRows fb{bodies_d, rec_of, r0, n_mc};
+            if (int rc = fk_impl(m, y, APE_F32, rows, norm ? 1 : 0, cur + (size_t)carry * W, APE_F64, stream, bodies_d ? &fb : nullptr)) return rc;
             ReplayMsgParams mp{};
             mp.est = cur; mp.est_base = r0 - carry; mp.seg_of = seg_of; mp.out = out_dev; mp.out_stride = out_stride;
             mp.f_lo = r0 / n_mc; mp.f_hi = (r0 + rows) / n_mc;
             memcpy(mp.body, m->body, sizeof(mp.body));
             mp.W = W; mp.layout = m->dims.target_layout; mp.smooth = smooth; mp.n_mc = n_mc; mp.out_dtype = out_dtype;
-            e = ape_launch_replay_msg(mp, tail, st);
+            e = ape_launch_replay_msg(mp, tail, st, bodies_d, rec_of);
             if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: message launch failed: %s", hipGetErrorString(e));
             prev_rows = rows;
         }

@@ -205,6 +205,15 @@ struct FkParams {
     int N, O, W, layout;
 };
 
+// ape_replay_bodies: which body a row of an FK launch takes -- sample row row_base + r belongs to frame (row_base + r) / n_mc, that
+// frame to recording rec_of[frame], whose nine values are row rec_of[frame] of bodies [R,9]
+struct FkBodyRows {
+    const double* bodies;
+    const int* rec_of;   // [F]
+    long long row_base;
+    int n_mc;
+};
+
 // Kernel arguments of the per-stream smoothing + message kernel (stream bank).
 struct StreamPostParams {
     const float* y_new;  // [S,n_mc,O] NN targets of this step (model output, still normalised)
@@ -403,7 +412,8 @@ hipError_t ape_launch_parse_rows(const float* rows, int N, int width, int kind, 
                                  size_t out_stride, int rep, size_t rep_stride, int big_endian, hipStream_t stream);
 hipError_t ape_launch_ring_write(const float* xx, int N, int I, float* out, size_t out_stride, int rep,
                                  size_t rep_stride, hipStream_t stream);
-hipError_t ape_launch_stream_post(const StreamPostParams& p, hipStream_t stream);
+// bodies: nullptr (every stream p.body) or the bank's device table [S,9] of per-stream body measurements
+hipError_t ape_launch_stream_post(const StreamPostParams& p, hipStream_t stream, const double* bodies = nullptr);
 hipError_t ape_launch_mlp_tile16(int H, const MlpParams& p, hipStream_t stream, int n_cus = 0);
 hipError_t ape_prepare_mlp_tile16(int H);     // per device: dynamic-LDS limits of the MLP and head-rows kernels (from ape_model_create)
 // two-stage weight-stationary pipeline for chip-filling eval batches of the 2-hidden-layer MLP (mlp_pipe.hip)
@@ -415,11 +425,15 @@ hipError_t ape_launch_mlp_pipe(const MlpParams& q, const float* wa0, const float
                                size_t ring_bytes, unsigned* ctl, int n_cus, hipStream_t stream);
 hipError_t ape_launch_head_rows(const float* hseq, int N, int H, int O, const float* w_out, const float* b_out, float* y,
                                 hipStream_t stream);
-hipError_t ape_launch_fk(const FkParams& p, int preds_dtype, int est_dtype, hipStream_t stream);
+hipError_t ape_launch_fk(const FkParams& p, int preds_dtype, int est_dtype, hipStream_t stream, const FkBodyRows* bodies = nullptr);
 hipError_t ape_launch_msg_reduce(const MsgParams& p, hipStream_t stream);
-hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, int* seg_of, hipStream_t stream);
+// rec_of (optional): [F] index of each frame's recording, for the replays with one body per recording
+hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, int* seg_of, hipStream_t stream, int* rec_of = nullptr);
 hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t stream);
-hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream);
+// bodies / rec_of: nullptr (p.body for every frame) or [R,9] values and [F] recording indices
+hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream, const double* bodies = nullptr,
+                                 const int* rec_of = nullptr);
 hipError_t ape_launch_subset_rows(const SubsetRowsParams& p, hipStream_t stream);
 // the bank's post-filter over a list: p.S = K entries, y_new / msg in list order, stack slot and cold flag of entry j from desc[j]
-hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const SubsetDesc* desc, hipStream_t stream);
+// (bodies: as ape_launch_stream_post -- indexed by desc[j].stream)
+hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const SubsetDesc* desc, hipStream_t stream, const double* bodies = nullptr);

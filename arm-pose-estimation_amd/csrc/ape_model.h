@@ -6,6 +6,7 @@
 
 #include "../../include/ape_hip.h"
 #include "ape_internal.h"
+#include "body_table.h"
 
 struct ape_streams;
 
@@ -167,4 +168,6 @@ struct ape_streams {
     SubsetDesc* sub_stage = nullptr;  // [APE_SUBSET_STAGES][S]
     hipEvent_t sub_ev[APE_SUBSET_STAGES] = {};
     int sub_next = 0;
+    // per-stream body measurements (ape_streams_set_bodies): off until the first call -- the frames then read model->body
+    ApeBodyTable bodies;         // [S,9] on the device
 };

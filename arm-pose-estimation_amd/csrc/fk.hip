@@ -65,10 +65,16 @@ __device__ void fk_row(const double* pr, const double* body, int layout, double*
 // 7.1 us for 1024 rows against 2-3 here, 4.2 us for the one row of the latency path -- through an LDS slab -- against ~3.)
 constexpr int FK3_ROWS = 32;
 
-template <typename TIn, typename TOut>
-__global__ __launch_bounds__(128) void ape_fk3_kernel(const FkParams p) {
+// TAB (ape_replay_bodies): row r is sample row t.row_base + r of a replay call, its body the row of t.bodies [R,9] of
+// the recording its frame belongs to (t.rec_of); else the uniform p.body, as ever.
+template <typename TIn, typename TOut, bool TAB = false>
+__global__ __launch_bounds__(128) void ape_fk3_kernel(const FkParams p, const FkBodyRows t) {
     __shared__ double rot[FK3_ROWS][3][3];                 // [row][lower arm, upper arm, shoulder origin][xyz]
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    auto body_of = [&](size_t row) -> const double* {
+        if constexpr (TAB) return t.bodies + 9 * (size_t)t.rec_of[(t.row_base + (long long)row) / t.n_mc];
+        else return p.body;
+    };
     const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
     const bool full = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS && hips;      // the 20-column layout (estimate_joints.py:20-45)
     // column of the first 6D value of the lower / upper arm, of the hips' sine; est columns of the quaternions
@@ -89,7 +95,8 @@ __global__ __launch_bounds__(128) void ape_fk3_kernel(const FkParams p) {
 #pragma unroll
             for (int c = 0; c < 6; ++c) s6[c] = load(src, (sub ? c_u : c_l) + c);
             const Quat q = six_drr_to_quat(s6);
-            const Vec3 bone = sub ? Vec3{p.body[3], p.body[4], p.body[5]} : Vec3{p.body[0], p.body[1], p.body[2]};
+            const double* const body = body_of(row);
+            const Vec3 bone = sub ? Vec3{body[3], body[4], body[5]} : Vec3{body[0], body[1], body[2]};
             const Vec3 v = qrot(q, bone);
             rot[r][sub][0] = v.x; rot[r][sub][1] = v.y; rot[r][sub][2] = v.z;
             const int eq = sub ? e_uq : e_lq;
@@ -102,7 +109,8 @@ __global__ __launch_bounds__(128) void ape_fk3_kernel(const FkParams p) {
             const TIn* src = static_cast<const TIn*>(p.preds) + row * p.O;
             TOut* dst = static_cast<TOut*>(p.est) + row * p.W;
             if (lane < 32) {
-                Vec3 uo{p.body[6], p.body[7], p.body[8]};
+                const double* const body = body_of(row);
+                Vec3 uo{body[6], body[7], body[8]};
                 if (hips) {
                     const Quat hq = hips_quat(load(src, c_h), load(src, c_h + 1));
                     uo = qrot(hq, uo);
@@ -131,6 +139,7 @@ __global__ __launch_bounds__(128) void ape_fk3_kernel(const FkParams p) {
         }
     }
 }
+
 
 // ---- message: N est rows -> 25 doubles ------------------------------------------------------
 __device__ __forceinline__ double block_sum(double v, double* scratch) {
@@ -212,15 +221,34 @@ __global__ __launch_bounds__(256) void ape_stream_post_wide_kernel(const StreamP
     stream_post_wide<TMsg>(p, (int)blockIdx.x * 64);
 }
 
+// ... the three forms reading the bank's body table (stream_post_device.h, TAB): launched only once a bank was given per-stream bodies
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_stream_post_bodies_kernel(const StreamPostParams p, const double* bodies) {
+    stream_post<TMsg, false, false, true>(p, (int)blockIdx.x, 0, 1, nullptr, bodies);
+}
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_stream_post_split_bodies_kernel(const StreamPostParams p, const int chunks, const double* bodies) {
+    stream_post<TMsg, true, false, true>(p, (int)blockIdx.x / chunks, (int)blockIdx.x % chunks, chunks, nullptr, bodies);
+}
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_stream_post_wide_bodies_kernel(const StreamPostParams p, const double* bodies) {
+    stream_post_wide<TMsg, false, true>(p, (int)blockIdx.x * 64, nullptr, bodies);
+}
+
 template <typename TIn, typename TOut>
 hipError_t launch_fk(const FkParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL((ape_fk3_kernel<TIn, TOut>), dim3((p.N + FK3_ROWS - 1) / FK3_ROWS), dim3(128), 0, stream, p);
+    hipLaunchKernelGGL((ape_fk3_kernel<TIn, TOut, false>), dim3((p.N + FK3_ROWS - 1) / FK3_ROWS), dim3(128), 0, stream, p, FkBodyRows{});
     return hipGetLastError();
 }
 
 }  // namespace
 
-hipError_t ape_launch_fk(const FkParams& p, int preds_dtype, int est_dtype, hipStream_t stream) {
+hipError_t ape_launch_fk(const FkParams& p, int preds_dtype, int est_dtype, hipStream_t stream, const FkBodyRows* bodies) {
+    if (bodies != nullptr) {                               // replay with one body per recording: f32 targets -> f64 est rows only
+        if (preds_dtype != APE_F32 || est_dtype != APE_F64) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((ape_fk3_kernel<float, double, true>), dim3((p.N + FK3_ROWS - 1) / FK3_ROWS), dim3(128), 0, stream, p, *bodies);
+        return hipGetLastError();
+    }
     if (preds_dtype == APE_F32 && est_dtype == APE_F32) return launch_fk<float, float>(p, stream);
     if (preds_dtype == APE_F32 && est_dtype == APE_F64) return launch_fk<float, double>(p, stream);
     if (preds_dtype == APE_F64 && est_dtype == APE_F32) return launch_fk<double, float>(p, stream);
@@ -233,7 +261,27 @@ hipError_t ape_launch_msg_reduce(const MsgParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
-hipError_t ape_launch_stream_post(const StreamPostParams& p, hipStream_t stream) {
+// the same choice of form with the table-reading instantiations
+static hipError_t launch_stream_post_bodies(const StreamPostParams& p, const double* bodies, hipStream_t stream) {
+    if (p.smooth == 1 && p.n_mc == 1 && p.S >= 8) {
+        const int wide = (p.S + 63) / 64;
+        if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_stream_post_wide_bodies_kernel<float>, dim3(wide), dim3(256), 0, stream, p, bodies);
+        else hipLaunchKernelGGL(ape_stream_post_wide_bodies_kernel<double>, dim3(wide), dim3(256), 0, stream, p, bodies);
+        return hipGetLastError();
+    }
+    const int chunks = ape_stream_post_chunks(p.smooth * p.n_mc);
+    if (p.part != nullptr && chunks > 1) {
+        if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_stream_post_split_bodies_kernel<float>, dim3(p.S * chunks), dim3(256), 0, stream, p, chunks, bodies);
+        else hipLaunchKernelGGL(ape_stream_post_split_bodies_kernel<double>, dim3(p.S * chunks), dim3(256), 0, stream, p, chunks, bodies);
+        return hipGetLastError();
+    }
+    if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_stream_post_bodies_kernel<float>, dim3(p.S), dim3(256), 0, stream, p, bodies);
+    else hipLaunchKernelGGL(ape_stream_post_bodies_kernel<double>, dim3(p.S), dim3(256), 0, stream, p, bodies);
+    return hipGetLastError();
+}
+
+hipError_t ape_launch_stream_post(const StreamPostParams& p, hipStream_t stream, const double* bodies) {
+    if (bodies != nullptr) return launch_stream_post_bodies(p, bodies, stream);
     if (p.smooth == 1 && p.n_mc == 1 && p.S >= 8) {        // no stacking: lanes = streams
         const int wide = (p.S + 63) / 64;
         if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_stream_post_wide_kernel<float>, dim3(wide), dim3(256), 0, stream, p);

@@ -21,6 +21,7 @@
 #include "../../include/ape_hip.h"
 #include "parse_device.h"
 #include "stream_post_device.h"
+#include "body_table.h"
 
 #pragma clang fp contract(off)
 
@@ -100,8 +101,11 @@ __device__ inline void stack_msg(int N, Row row, const double* body, double* m) 
     finish_msg(APE_LAYOUT_ORI_CAL_LARM_UARM, N, out_q, orig_mean, e0, body, m);
 }
 
-template <typename TMsg>
-__global__ __launch_bounds__(FK_BLOCK) void ape_fk_bank_kernel(const FkBankParams p) {
+// TAB (per-stream bodies): stream s takes bodies[c * S + s], c = 0 .. 8 -- the table is component-major [9,S], so that
+// the 64 lanes of a lockstep wave read nine runs of 512 contiguous bytes (a row-major [S,9] would be nine 72-byte-strided gathers);
+// indexed by the stream, never by the list position.  Else the uniform p.body.
+template <typename TMsg, bool TAB = false>
+__global__ __launch_bounds__(FK_BLOCK) void ape_fk_bank_kernel(const FkBankParams p, const double* __restrict__ bodies, const int S) {
     const int j = blockIdx.x * FK_BLOCK + threadIdx.x;
     if (j >= p.K) return;
     const int s = p.desc ? p.desc[j].stream : j;
@@ -115,9 +119,13 @@ __global__ __launch_bounds__(FK_BLOCK) void ape_fk_bank_kernel(const FkBankParam
 #pragma unroll
         for (int c = 0; c < 8; ++c) ring[t * 8 + c] = q8[c];
     // stack row i (oldest first) sits in slot (pos + 1 + i) mod smooth: the newest in `pos`, on a cold start copies everywhere
-    double m[25];
+    double m[25], own[9];
+    if constexpr (TAB) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) own[c] = bodies[(size_t)c * S + s];
+    }
     stack_msg(p.smooth, [&](int i) -> const double* { int t = pos + 1 + i; if (t >= p.smooth) t -= p.smooth; return ring + t * 8; },
-              p.body, m);
+              TAB ? own : p.body, m);
     TMsg* dst = static_cast<TMsg*>(p.out) + (size_t)j * 25;
 #pragma unroll
     for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
@@ -133,14 +141,16 @@ __global__ __launch_bounds__(FK_BLOCK) void ape_fk_replay_rows_kernel(const FkRe
     row_quats(p.rows + (size_t)f * FK_WIDTH, p.big_endian, p.ws + (size_t)f * 8);
 }
 
-template <typename TMsg>
-__global__ __launch_bounds__(FK_BLOCK) void ape_fk_replay_msg_kernel(const FkReplayParams p) {
+// TAB (ape_fk_replay_bodies): the frame's body is row rec_of[f] of bodies [R,9] -- neighbouring lanes mostly share it
+template <typename TMsg, bool TAB = false>
+__global__ __launch_bounds__(FK_BLOCK) void ape_fk_replay_msg_kernel(const FkReplayParams p, const double* __restrict__ bodies,
+                                                                     const int* __restrict__ rec_of) {
     const int f = blockIdx.x * FK_BLOCK + threadIdx.x;
     if (f >= p.F) return;
     const int seg = p.seg_of[f];
     double m[25];
     stack_msg(p.smooth, [&](int i) -> const double* { int h = f - p.smooth + 1 + i; if (h < seg) h = seg; return p.ws + (size_t)h * 8; },
-              p.body, m);
+              TAB ? bodies + 9 * (size_t)rec_of[f] : p.body, m);
     TMsg* dst = static_cast<TMsg*>(p.out) + (size_t)f * 25;
 #pragma unroll
     for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
@@ -191,10 +201,10 @@ int check_capture(hipStream_t st, const char* what) {
     return APE_OK;
 }
 
-template <typename P, typename K32, typename K64>
-hipError_t launch_typed(K32 k32, K64 k64, int out_dtype, long long n, const P& p, hipStream_t st) {
-    if (out_dtype == APE_F32) hipLaunchKernelGGL(k32, dim3(blocks_for(n)), dim3(FK_BLOCK), 0, st, p);
-    else hipLaunchKernelGGL(k64, dim3(blocks_for(n)), dim3(FK_BLOCK), 0, st, p);
+template <typename K32, typename K64, typename... Args>
+hipError_t launch_typed(K32 k32, K64 k64, int out_dtype, long long n, hipStream_t st, Args... args) {
+    if (out_dtype == APE_F32) hipLaunchKernelGGL(k32, dim3(blocks_for(n)), dim3(FK_BLOCK), 0, st, args...);
+    else hipLaunchKernelGGL(k64, dim3(blocks_for(n)), dim3(FK_BLOCK), 0, st, args...);
     return hipGetLastError();
 }
 
@@ -217,11 +227,13 @@ struct ape_fk_bank {
     void* h_out = nullptr;
     unsigned* h_done = nullptr;
     unsigned done_val = 0;
+    ApeBodyTable bodies;               // per-stream bodies, component-major [9,S] on the device (off until ape_fk_bank_set_bodies)
 };
 
 namespace {
 
 void bank_free(ape_fk_bank* b) {
+    ape_body_table_free(b->bodies);
     if (b->ring) (void)hipFree(b->ring);
     if (b->desc) (void)hipFree(b->desc);
     if (b->stage) (void)hipHostFree(b->stage);
@@ -282,7 +294,9 @@ int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* s
         b->next = (k + 1) % FK_STAGES;
         p.desc = b->desc;
     }
-    hipError_t e = launch_typed(ape_fk_bank_kernel<float>, ape_fk_bank_kernel<double>, out_dtype, K, p, st);
+    const double* const none = nullptr;
+    const hipError_t e = b->bodies.on() ? launch_typed(ape_fk_bank_kernel<float, true>, ape_fk_bank_kernel<double, true>, out_dtype, K, st, p, (const double*)b->bodies.dev, b->S)
+                                        : launch_typed(ape_fk_bank_kernel<float, false>, ape_fk_bank_kernel<double, false>, out_dtype, K, st, p, none, 0);
     if (e != hipSuccess) return ffail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
     if (p.desc == nullptr) b->ucount += 1;
     else if (streams_host) for (int j = 0; j < K; ++j) b->cnt[streams_host[j]] += 1;
@@ -391,9 +405,30 @@ int ape_fk_bank_frame_host(ape_fk_bank_t* b, int32_t kind, const float* rows_hos
     return APE_OK;
 }
 
+int ape_fk_bank_set_bodies(ape_fk_bank_t* b, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream) {
+    if (!b || !body9s_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_set_bodies: NULL argument");
+    if (int rc = check_list(b, streams_host, K, "fk_bank_set_bodies")) return rc;
+    FK_TRY(hipSetDevice(b->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "fk_bank_set_bodies")) return rc;
+    FK_TRY(ape_body_table_set(b->bodies, b->S, true, b->body, streams_host, K, body9s_host, st));
+    return APE_OK;
+}
+
+int ape_fk_bank_get_bodies(ape_fk_bank_t* b, double* out_host) {
+    if (!b || !out_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_get_bodies: NULL argument");
+    ape_body_table_get(b->bodies, b->S, b->body, out_host);
+    return APE_OK;
+}
+
 int ape_fk_replay(int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t smooth,
                   const double body9[9], int32_t device, void* out_dev, int32_t out_dtype, void* stream) {
-    if (!rows_dev || !out_dev || !body9) return ffail(APE_ERR_INVALID_ARG, "fk_replay: NULL argument");
+    return ape_fk_replay_bodies(kind, rows_dev, F, seg_starts_host, R, smooth, body9, device, out_dev, out_dtype, stream, nullptr);
+}
+
+int ape_fk_replay_bodies(int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t smooth,
+                         const double body9[9], int32_t device, void* out_dev, int32_t out_dtype, void* stream, const double* bodies_host) {
+    if (!rows_dev || !out_dev || (!body9 && !bodies_host)) return ffail(APE_ERR_INVALID_ARG, "fk_replay: NULL argument");
     if (int rc = check_kind(kind, "fk_replay")) return rc;
     if (F < 1) return ffail(APE_ERR_INVALID_ARG, "fk_replay: F=%d must be >= 1", F);
     if (R < 1 || R > F) return ffail(APE_ERR_INVALID_ARG, "fk_replay: %d recording starts for %d frames (1 <= R <= F)", R, F);
@@ -413,7 +448,7 @@ int ape_fk_replay(int32_t kind, const float* rows_dev, int32_t F, const int32_t*
     if (cap != hipStreamCaptureStatusNone) return ffail(APE_ERR_INVALID_ARG, "fk_replay: blocking call on a capturing stream");
     // workspaces: the frames' quaternions, their recording starts; freed behind the call's own synchronisation
     struct Scratch {
-        void* p[3] = {};
+        void* p[5] = {};
         ~Scratch() { for (void* q : p) if (q) (void)hipFree(q); }
     } ws;
     FK_TRY(hipMalloc(&ws.p[0], (size_t)F * 8 * sizeof(double)));
@@ -423,13 +458,22 @@ int ape_fk_replay(int32_t kind, const float* rows_dev, int32_t F, const int32_t*
     FkReplayParams p{};
     p.rows = rows_dev; p.seg_of = (const int*)ws.p[1]; p.ws = (double*)ws.p[0]; p.out = out_dev;
     p.F = F; p.smooth = smooth; p.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
-    memcpy(p.body, body9, sizeof(p.body));
-    hipError_t e = ape_launch_replay_segments((const int*)ws.p[2], R, F, (int*)ws.p[1], st);
+    if (body9) memcpy(p.body, body9, sizeof(p.body));
+    if (bodies_host) {                                        // one body per recording: the values and every frame's recording index
+        FK_TRY(hipMalloc(&ws.p[3], (size_t)R * 9 * sizeof(double)));
+        FK_TRY(hipMalloc(&ws.p[4], (size_t)F * sizeof(int)));
+        FK_TRY(hipMemcpyAsync(ws.p[3], bodies_host, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, st));
+    }
+    hipError_t e = ape_launch_replay_segments((const int*)ws.p[2], R, F, (int*)ws.p[1], st, (int*)ws.p[4]);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(ape_fk_replay_rows_kernel, dim3(blocks_for(F)), dim3(FK_BLOCK), 0, st, p);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = launch_typed(ape_fk_replay_msg_kernel<float>, ape_fk_replay_msg_kernel<double>, out_dtype, F, p, st);
+    if (e == hipSuccess)
+        e = bodies_host ? launch_typed(ape_fk_replay_msg_kernel<float, true>, ape_fk_replay_msg_kernel<double, true>, out_dtype, F, st, p,
+                                       (const double*)ws.p[3], (const int*)ws.p[4])
+                        : launch_typed(ape_fk_replay_msg_kernel<float, false>, ape_fk_replay_msg_kernel<double, false>, out_dtype, F, st, p,
+                                       (const double*)nullptr, (const int*)nullptr);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
         return ffail(APE_ERR_HIP, "fk_replay: launch failed: %s", hipGetErrorString(e));

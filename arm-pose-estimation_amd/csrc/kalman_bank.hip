@@ -28,6 +28,7 @@
 #include "../../include/ape_hip.h"
 #include "parse_device.h"
 #include "stream_post_device.h"
+#include "body_table.h"
 #include "kalman_device.h"
 
 #pragma clang fp contract(off)
@@ -130,8 +131,10 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_head_kernel(const Kb
     }
 }
 
-template <typename TMsg>
-__global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const KbTailParams p) {
+// TAB (per-stream bodies): the nine body values are row `stream` of bodies [S,9], uniform over the workgroup, instead of
+// the uniform p.body
+template <typename TMsg, bool TAB = false>
+__global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const KbTailParams p, const double* __restrict__ bodies) {
     __shared__ int ent_slot[KB_MAX_SMOOTH], ent_first[KB_MAX_SMOOTH + 1];   // stack entries, oldest first: ring slot (-1: this frame's), first stacked row
     __shared__ double ref_s[3][4], e0_s[21], red[KB_BLOCK / 64][12];
     const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -180,7 +183,8 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const Kb
     __syncthreads();
     const int N = ent_first[smooth];
     const double wgt = 1.0 / (double)N;
-    const Vec3 larm_vec{p.body[0], p.body[1], p.body[2]}, uarm_vec{p.body[3], p.body[4], p.body[5]}, orig{p.body[6], p.body[7], p.body[8]};
+    const double* const body = TAB ? bodies + 9 * (size_t)s : p.body;
+    const Vec3 larm_vec{body[0], body[1], body[2]}, uarm_vec{body[3], body[4], body[5]}, orig{body[6], body[7], body[8]};
     TMsg* out = static_cast<TMsg*>(p.out) + (size_t)d.row_out * p.out_stride;
     double acc[12] = {};
     for (int base = 0; base < N; base += KB_BLOCK) {        // thread per stacked row, oldest entry first (trip count uniform)
@@ -254,7 +258,7 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const Kb
         }
 #pragma unroll
         for (int cc = 0; cc < 21; ++cc) e0[cc] = e0_s[cc];
-        finish_msg(APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS, N, out_q, orig_mean, e0, p.body, m);
+        finish_msg(APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS, N, out_q, orig_mean, e0, body, m);
 #pragma unroll
         for (int cc = 0; cc < 25; ++cc) out[cc] = (TMsg)m[cc];
         p.n_rows[d.row_out] = N;
@@ -263,6 +267,7 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const Kb
         p.cnt[s] = next;
     }
 }
+
 
 int bfail(int code, const char* fmt, ...) {
     char buf[512];
@@ -320,11 +325,13 @@ struct ape_kalman_bank {
     float* h_rows = nullptr;
     void* h_out = nullptr;
     int* h_n = nullptr;
+    ApeBodyTable bodies;              // per-stream bodies [S,9] (off until ape_kalman_bank_set_bodies)
 };
 
 namespace {
 
 void bank_free(ape_kalman_bank* b) {
+    ape_body_table_free(b->bodies);
     void* dev[] = {b->xwin, b->state, b->yring, b->nring, b->cnt, b->raw, b->dense, b->corrected, b->ensz, b->mcorr, b->mpred, b->z, b->desc};
     for (void* q : dev) if (q) (void)hipFree(q);
     void* host[] = {b->stage, b->h_rows, b->h_out, b->h_n};
@@ -416,8 +423,11 @@ int frame_launch(ape_kalman_bank* b, int big_endian, const float* rows, const Kb
     memcpy(t.yy_m, b->yy_m, sizeof(t.yy_m));
     memcpy(t.yy_s, b->yy_s, sizeof(t.yy_s));
     memcpy(t.body, b->body, sizeof(t.body));
-    if (out_dtype == APE_F32) hipLaunchKernelGGL(ape_kalman_bank_tail_kernel<float>, dim3(K), dim3(KB_BLOCK), 0, st, t);
-    else hipLaunchKernelGGL(ape_kalman_bank_tail_kernel<double>, dim3(K), dim3(KB_BLOCK), 0, st, t);
+    if (b->bodies.on()) {
+        if (out_dtype == APE_F32) hipLaunchKernelGGL((ape_kalman_bank_tail_kernel<float, true>), dim3(K), dim3(KB_BLOCK), 0, st, t, b->bodies.dev);
+        else hipLaunchKernelGGL((ape_kalman_bank_tail_kernel<double, true>), dim3(K), dim3(KB_BLOCK), 0, st, t, b->bodies.dev);
+    } else if (out_dtype == APE_F32) hipLaunchKernelGGL((ape_kalman_bank_tail_kernel<float, false>), dim3(K), dim3(KB_BLOCK), 0, st, t, (const double*)nullptr);
+    else hipLaunchKernelGGL((ape_kalman_bank_tail_kernel<double, false>), dim3(K), dim3(KB_BLOCK), 0, st, t, (const double*)nullptr);
     e = hipGetLastError();
     if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: tail launch failed: %s", what, hipGetErrorString(e));
     return APE_OK;
@@ -499,6 +509,28 @@ int ape_kalman_bank_set_norm_stats(ape_kalman_bank_t* b, const double* xx_m, con
 int ape_kalman_bank_set_body(ape_kalman_bank_t* b, const double body9[9]) {
     if (!b || !body9) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_body: NULL argument");
     memcpy(b->body, body9, sizeof(b->body));
+    if (b->bodies.on()) {                          // table mode: every row (ordered on the null stream: behind every blocking stream's frames)
+        std::vector<double> all((size_t)b->S * 9);
+        for (int s = 0; s < b->S; ++s) memcpy(&all[(size_t)s * 9], body9, 9 * sizeof(double));
+        KB_TRY(hipSetDevice(b->device));
+        KB_TRY(ape_body_table_set(b->bodies, b->S, false, b->body, nullptr, b->S, all.data(), nullptr));
+    }
+    return APE_OK;
+}
+
+int ape_kalman_bank_set_bodies(ape_kalman_bank_t* b, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream) {
+    if (!b || !body9s_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_bodies: NULL argument");
+    if (int rc = check_list(b, streams_host, K, "kalman_bank_set_bodies")) return rc;
+    KB_TRY(hipSetDevice(b->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "kalman_bank_set_bodies")) return rc;
+    KB_TRY(ape_body_table_set(b->bodies, b->S, false, b->body, streams_host, K, body9s_host, st));
+    return APE_OK;
+}
+
+int ape_kalman_bank_get_bodies(ape_kalman_bank_t* b, double* out_host) {
+    if (!b || !out_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_get_bodies: NULL argument");
+    ape_body_table_get(b->bodies, b->S, b->body, out_host);
     return APE_OK;
 }
 
@@ -554,7 +586,15 @@ int ape_kalman_bank_frame_host(ape_kalman_bank_t* b, int32_t kind, const float* 
 int ape_kalman_replay(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                       int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s, const double body9[9],
                       uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev, float* y_dev, void* stream) {
-    if (!model || !rows_dev || !out_dev || !n_rows_dev || !body9) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: NULL argument");
+    return ape_kalman_replay_bodies(model, kind, rows_dev, F, seg_starts_host, R, smooth, xx_m, xx_s, yy_m, yy_s, body9, seed, flags, out_dev,
+                                    out_dtype, n_rows_dev, y_dev, stream, nullptr);
+}
+
+int ape_kalman_replay_bodies(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                             int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
+                             const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
+                             float* y_dev, void* stream, const double* bodies_host) {
+    if (!model || !rows_dev || !out_dev || !n_rows_dev || (!body9 && !bodies_host)) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: NULL argument");
     if (int rc = check_kind(kind, "kalman_replay")) return rc;
     if (F < 1) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: F=%d must be >= 1", F);
     if (R < 1 || R > F) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: %d recording starts for %d frames (1 <= R <= F)", R, F);
@@ -580,7 +620,9 @@ int ape_kalman_replay(ape_kalman_t* model, int32_t kind, const float* rows_dev, 
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "kalman_replay")) return rc;
     if (any) (void)ape_kalman_bank_set_norm_stats(b, xx_m, xx_s, yy_m, yy_s);
-    memcpy(b->body, body9, sizeof(b->body));
+    if (body9) memcpy(b->body, body9, sizeof(b->body));
+    // one body per recording: the replay's bank has a stream per recording, so the table's row r is recording r's
+    if (bodies_host) KB_TRY(ape_body_table_set(b->bodies, R, false, b->body, nullptr, R, bodies_host, st));
     b->seed = seed;
     std::vector<int> len((size_t)R);
     int longest = 0;

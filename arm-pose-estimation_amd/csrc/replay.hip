@@ -31,6 +31,19 @@ __global__ __launch_bounds__(256) void ape_replay_seg_kernel(const int* __restri
     seg_of[f] = starts[lo];
 }
 
+// the same search for the recording's index: the replays with one body per recording (ape_replay_bodies) read row
+// rec_of[f] of their [R,9] table
+__global__ __launch_bounds__(256) void ape_replay_rec_kernel(const int* __restrict__ starts, int n_starts, int F, int* __restrict__ rec_of) {
+    const int f = blockIdx.x * 256 + threadIdx.x;
+    if (f >= F) return;
+    int lo = 0, hi = n_starts - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if (starts[mid] <= f) lo = mid; else hi = mid - 1;
+    }
+    rec_of[f] = lo;
+}
+
 // one thread per output float: consecutive threads write consecutive floats and read the same feature row's columns
 __global__ __launch_bounds__(256) void ape_replay_window_kernel(const ReplayWindowParams p) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
@@ -49,8 +62,10 @@ __global__ __launch_bounds__(256) void ape_replay_window_kernel(const ReplayWind
 // One lane per frame, the stack's rows in the reference's order (average_quaternions, transformations.py:32-51: row 0 times 1/N, then
 // every further row added with +-1/N by the strict `dot < 0.0` rule against row 0).  Adjacent frames share all but n_mc of their rows:
 // the est rows come from L2.
-template <typename TMsg>
-__global__ __launch_bounds__(256) void ape_replay_msg_kernel(const ReplayMsgParams p) {
+// TAB: the frame's body is row rec_of[f] of bodies [R,9] (neighbouring lanes mostly share it), else the uniform p.body
+template <typename TMsg, bool TAB = false>
+__global__ __launch_bounds__(256) void ape_replay_msg_kernel(const ReplayMsgParams p, const double* __restrict__ bodies,
+                                                             const int* __restrict__ rec_of) {
     const long long f = p.f_lo + (long long)blockIdx.x * 256 + threadIdx.x;
     if (f >= p.f_hi) return;
     const int M = p.n_mc, N = p.smooth * M, W = p.W;
@@ -92,11 +107,12 @@ __global__ __launch_bounds__(256) void ape_replay_msg_kernel(const ReplayMsgPara
         }
     }
     double m[25];
-    finish_msg(p.layout, N, out_q, orig_mean, e0, p.body, m);
+    finish_msg(p.layout, N, out_q, orig_mean, e0, TAB ? bodies + 9 * (size_t)rec_of[f] : p.body, m);
     TMsg* dst = static_cast<TMsg*>(p.out) + f * p.out_stride;
 #pragma unroll
     for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
 }
+
 
 // one thread per (frame, stacked row): six values each, neighbouring threads write neighbouring groups
 template <typename TMsg>
@@ -120,8 +136,9 @@ unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
 
-hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, int* seg_of, hipStream_t stream) {
+hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, int* seg_of, hipStream_t stream, int* rec_of) {
     hipLaunchKernelGGL(ape_replay_seg_kernel, dim3(blocks_for(F)), dim3(256), 0, stream, starts, n_starts, F, seg_of);
+    if (rec_of != nullptr) hipLaunchKernelGGL(ape_replay_rec_kernel, dim3(blocks_for(F)), dim3(256), 0, stream, starts, n_starts, F, rec_of);
     return hipGetLastError();
 }
 
@@ -130,11 +147,14 @@ hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t st
     return hipGetLastError();
 }
 
-hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream) {
+hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream, const double* bodies, const int* rec_of) {
     const long long frames = p.f_hi - p.f_lo;
     if (frames <= 0) return hipSuccess;
-    if (p.out_dtype == APE_F32) hipLaunchKernelGGL(ape_replay_msg_kernel<float>, dim3(blocks_for(frames)), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(ape_replay_msg_kernel<double>, dim3(blocks_for(frames)), dim3(256), 0, stream, p);
+    if (bodies != nullptr) {
+        if (p.out_dtype == APE_F32) hipLaunchKernelGGL((ape_replay_msg_kernel<float, true>), dim3(blocks_for(frames)), dim3(256), 0, stream, p, bodies, rec_of);
+        else hipLaunchKernelGGL((ape_replay_msg_kernel<double, true>), dim3(blocks_for(frames)), dim3(256), 0, stream, p, bodies, rec_of);
+    } else if (p.out_dtype == APE_F32) hipLaunchKernelGGL((ape_replay_msg_kernel<float, false>), dim3(blocks_for(frames)), dim3(256), 0, stream, p, bodies, rec_of);
+    else hipLaunchKernelGGL((ape_replay_msg_kernel<double, false>), dim3(blocks_for(frames)), dim3(256), 0, stream, p, bodies, rec_of);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !tail) return e;
     const long long n = frames * p.smooth * p.n_mc;

@@ -83,8 +83,12 @@ __device__ __forceinline__ double wave_sum(double v) {
 // IDX (subset frames, streams_subset.hip): `s` is a position in a list of p.S entries -- its targets in y_new, its message row, its
 // partial sums -- and the stream whose stack it reads and writes, that stack's slot and cold flag come from d[s] instead of the uniform
 // p.pos / p.cold.  IDX = false is the bank's lockstep step, unchanged.
-template <typename TMsg, bool SPLIT, bool IDX = false>
-__device__ inline void stream_post(const StreamPostParams& p, const int s, const int chunk, const int C, const SubsetDesc* d = nullptr) {
+// TAB (per-stream bodies): the nine body values (Estimator.body_measurements, estimator.py:57-68) are row `stream` of
+// `bodies` [S,9] -- uniform over the workgroup, indexed by the STREAM (d[s].stream in a subset frame), never by the list position --
+// instead of the uniform p.body; chosen where the values are read, so that the other forms' object code stays what it was.
+template <typename TMsg, bool SPLIT, bool IDX = false, bool TAB = false>
+__device__ inline void stream_post(const StreamPostParams& p, const int s, const int chunk, const int C, const SubsetDesc* d = nullptr,
+                                   const double* __restrict__ bodies = nullptr) {
 #pragma clang fp contract(off)
 
     __shared__ double rot[64][3][3];                        // per row of a 64-row chunk: rotated lower-arm bone, upper-arm bone, shoulder origin
@@ -101,6 +105,7 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
     const int qc[3] = {hips ? 9 : 6, hips ? 13 : 10, 17};
     const int c_in[3] = {full ? 3 : 0, full ? 12 : 6, full ? 18 : 12};     // first input column of the role's chain
     const double wgt = 1.0 / (double)N;
+    const double* const body = TAB ? bodies + 9 * (size_t)(IDX ? d[s].stream : s) : p.body;
     double acc[4] = {0, 0, 0, 0};
     double osum[6] = {0, 0, 0, 0, 0, 0};
     if (threadIdx.x < 21) e0_s[threadIdx.x] = 0.0;
@@ -142,14 +147,14 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
 #pragma unroll
                 for (int c = 0; c < 6; ++c) s6[c] = load(c_in[role] + c);
                 const Quat qq = six_drr_to_quat(s6);
-                const Vec3 bone = role ? Vec3{p.body[3], p.body[4], p.body[5]} : Vec3{p.body[0], p.body[1], p.body[2]};
+                const Vec3 bone = role ? Vec3{body[3], body[4], body[5]} : Vec3{body[0], body[1], body[2]};
                 const Vec3 v = qrot(qq, bone);
                 rot[lane][role][0] = v.x; rot[lane][role][1] = v.y; rot[lane][role][2] = v.z;
                 q[0] = qq.w; q[1] = qq.x; q[2] = qq.y; q[3] = qq.z;
             }
         } else if (role == 2) {
             if (act || refrow) {
-                Vec3 uo{p.body[6], p.body[7], p.body[8]};
+                Vec3 uo{body[6], body[7], body[8]};
                 if (hips) {
                     const Quat hq = hips_quat(load(c_in[2]), load(c_in[2] + 1));
                     uo = qrot(hq, uo);
@@ -263,7 +268,7 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
     for (int c = 0; c < 9; ++c) orig_mean[c] = omean_s[c];
 #pragma unroll
     for (int c = 0; c < 21; ++c) e0[c] = e0_s[c];
-    finish_msg(p.layout, N, out_q, orig_mean, e0, p.body, m);
+    finish_msg(p.layout, N, out_q, orig_mean, e0, body, m);
     TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 25 + 6 * N : 25);
 #pragma unroll
     for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
@@ -280,8 +285,10 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
 // active lane -- 4096 waves at 1024 streams, four per SIMD, each a chain of ~500 float64 instructions: the kernel was bound by their
 // issue slots (13.6 us at 1024 streams against 6 us for one stream).  Same device functions in the same order: bit-identical outputs.
 // IDX: lane = list position (targets, message row), the stream's one ring slot from d
-template <typename TMsg, bool IDX = false>
-__device__ inline void stream_post_wide(const StreamPostParams& p, const int s0, const SubsetDesc* d = nullptr) {
+// TAB: every lane its own stream's row of `bodies` [S,9] (64 neighbouring rows = 4.5 KB of whole cache lines per workgroup)
+template <typename TMsg, bool IDX = false, bool TAB = false>
+__device__ inline void stream_post_wide(const StreamPostParams& p, const int s0, const SubsetDesc* d = nullptr,
+                                        const double* __restrict__ bodies = nullptr) {
 #pragma clang fp contract(off)
 
     __shared__ double rot[64][3][3];
@@ -293,6 +300,7 @@ __device__ inline void stream_post_wide(const StreamPostParams& p, const int s0,
     const bool full = p.layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS;
     const int qc[3] = {hips ? 9 : 6, hips ? 13 : 10, 17};
     const int c_in[3] = {full ? 3 : 0, full ? 12 : 6, full ? 18 : 12};
+    const double* const body = TAB ? bodies + 9 * (size_t)(act ? (IDX ? d[s].stream : s) : 0) : p.body;
     if (p.status_out != nullptr && s0 == 0 && threadIdx.x == 255)
         *p.status_out = __hip_atomic_load(p.status_in, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     for (int c = role; c < 21; c += 4) e0w[lane][c] = 0.0;
@@ -309,14 +317,14 @@ __device__ inline void stream_post_wide(const StreamPostParams& p, const int s0,
 #pragma unroll
             for (int c = 0; c < 6; ++c) s6[c] = load(c_in[role] + c);
             const Quat qq = six_drr_to_quat(s6);
-            const Vec3 bone = role ? Vec3{p.body[3], p.body[4], p.body[5]} : Vec3{p.body[0], p.body[1], p.body[2]};
+            const Vec3 bone = role ? Vec3{body[3], body[4], body[5]} : Vec3{body[0], body[1], body[2]};
             const Vec3 v = qrot(qq, bone);
             rot[lane][role][0] = v.x; rot[lane][role][1] = v.y; rot[lane][role][2] = v.z;
             e0w[lane][qc[role]] = qq.w; e0w[lane][qc[role] + 1] = qq.x; e0w[lane][qc[role] + 2] = qq.y; e0w[lane][qc[role] + 3] = qq.z;
         }
     } else if (role == 2) {
         if (act) {
-            Vec3 uo{p.body[6], p.body[7], p.body[8]};
+            Vec3 uo{body[6], body[7], body[8]};
             if (hips) {
                 const Quat hq = hips_quat(load(c_in[2]), load(c_in[2] + 1));
                 uo = qrot(hq, uo);
@@ -357,7 +365,7 @@ __device__ inline void stream_post_wide(const StreamPostParams& p, const int s0,
         double out_q[3][4] = {}, orig_mean[9] = {}, e0[21], m[25];
 #pragma unroll
         for (int c = 0; c < 21; ++c) e0[c] = e0w[lane][c];
-        finish_msg(p.layout, 1, out_q, orig_mean, e0, p.body, m);
+        finish_msg(p.layout, 1, out_q, orig_mean, e0, body, m);
         TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 31 : 25);
 #pragma unroll
         for (int c = 0; c < 25; ++c)

@@ -81,6 +81,38 @@ template <typename TMsg>
 __global__ __launch_bounds__(256) void ape_subset_post_wide_kernel(const StreamPostParams p, const SubsetDesc* d) {
     stream_post_wide<TMsg, true>(p, (int)blockIdx.x * 64, d);
 }
+// ... and over the bank's body table: row d[j].stream, whatever the list position (stream_post_device.h, TAB)
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_subset_post_bodies_kernel(const StreamPostParams p, const SubsetDesc* d, const double* bodies) {
+    stream_post<TMsg, false, true, true>(p, (int)blockIdx.x, 0, 1, d, bodies);
+}
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_subset_post_split_bodies_kernel(const StreamPostParams p, const int chunks, const SubsetDesc* d,
+                                                                         const double* bodies) {
+    stream_post<TMsg, true, true, true>(p, (int)blockIdx.x / chunks, (int)blockIdx.x % chunks, chunks, d, bodies);
+}
+template <typename TMsg>
+__global__ __launch_bounds__(256) void ape_subset_post_wide_bodies_kernel(const StreamPostParams p, const SubsetDesc* d, const double* bodies) {
+    stream_post_wide<TMsg, true, true>(p, (int)blockIdx.x * 64, d, bodies);
+}
+
+hipError_t launch_subset_post_bodies(const StreamPostParams& p, const SubsetDesc* d, const double* bodies, hipStream_t stream) {
+    if (p.smooth == 1 && p.n_mc == 1 && p.S >= 8) {
+        const int wide = (p.S + 63) / 64;
+        if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_subset_post_wide_bodies_kernel<float>, dim3(wide), dim3(256), 0, stream, p, d, bodies);
+        else hipLaunchKernelGGL(ape_subset_post_wide_bodies_kernel<double>, dim3(wide), dim3(256), 0, stream, p, d, bodies);
+        return hipGetLastError();
+    }
+    const int chunks = ape_stream_post_chunks(p.smooth * p.n_mc);
+    if (p.part != nullptr && chunks > 1) {
+        if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_subset_post_split_bodies_kernel<float>, dim3(p.S * chunks), dim3(256), 0, stream, p, chunks, d, bodies);
+        else hipLaunchKernelGGL(ape_subset_post_split_bodies_kernel<double>, dim3(p.S * chunks), dim3(256), 0, stream, p, chunks, d, bodies);
+        return hipGetLastError();
+    }
+    if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_subset_post_bodies_kernel<float>, dim3(p.S), dim3(256), 0, stream, p, d, bodies);
+    else hipLaunchKernelGGL(ape_subset_post_bodies_kernel<double>, dim3(p.S), dim3(256), 0, stream, p, d, bodies);
+    return hipGetLastError();
+}
 
 }  // namespace
 
@@ -91,8 +123,9 @@ hipError_t ape_launch_subset_rows(const SubsetRowsParams& p, hipStream_t stream)
 }
 
 // the same choice of form as ape_launch_stream_post (fk.hip), with p.S = the list's length
-hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const SubsetDesc* d, hipStream_t stream) {
+hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const SubsetDesc* d, hipStream_t stream, const double* bodies) {
     if (p.S < 1) return hipSuccess;
+    if (bodies != nullptr) return launch_subset_post_bodies(p, d, bodies, stream);
     if (p.smooth == 1 && p.n_mc == 1 && p.S >= 8) {
         const int wide = (p.S + 63) / 64;
         if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_subset_post_wide_kernel<float>, dim3(wide), dim3(256), 0, stream, p, d);

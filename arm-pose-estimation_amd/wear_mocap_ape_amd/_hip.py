@@ -96,6 +96,13 @@ SIGNATURES = {
     "ape_fk_bank_frame_host": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p]),
     "ape_fk_replay": (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.POINTER(C.c_double),
                                 C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]),
+    # per-stream body measurements: bank, stream list, K, [K,9] float64 values, HIP stream / bank, [S,9] out
+    "ape_streams_set_bodies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ape_streams_get_bodies": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ape_fk_bank_set_bodies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ape_fk_bank_get_bodies": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ape_kalman_bank_set_bodies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ape_kalman_bank_get_bodies": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ape_model_set_kernel": (C.c_int, [C.c_void_p, C.c_int32]),
     "ape_model_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "ape_model_check": (C.c_int, [C.c_void_p]),
@@ -127,6 +134,9 @@ SIGNATURES = {
     "ape_kalman_replay": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32] +
                           [C.POINTER(C.c_double)] * 5 + [C.c_uint64, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
+# the replays with one body per recording: every argument of the plain entry, then bodies_host [R,9] float64 (or NULL)
+for _name in ("ape_replay", "ape_fk_replay", "ape_kalman_replay"):
+    SIGNATURES[_name + "_bodies"] = (C.c_int, SIGNATURES[_name][1] + [C.c_void_p])
 
 _lib = None
 

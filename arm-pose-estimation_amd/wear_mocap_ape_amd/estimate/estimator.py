@@ -13,7 +13,7 @@ from datetime import datetime
 import numpy as np
 import torch
 
-from wear_mocap_ape_amd.data_types.bone_map import BoneMap
+from wear_mocap_ape_amd.data_types.bone_map import BoneMap, bodies_from, body9_from_bonemap
 from wear_mocap_ape_amd.estimate import _post
 from wear_mocap_ape_amd.utility import data_stats
 from wear_mocap_ape_amd.utility.names import NNS_INPUTS, NNS_TARGETS, TARGET_LAYOUT
@@ -105,11 +105,10 @@ class Estimator:
         self._add_mc_samples, self._last_msg = add_mc_samples, None
 
         # arm geometry: both arm bones point along -x; [[larm_vec, uarm_vec, uarm_orig_rh]] as one [1,9] row
-        larm_len = BoneMap.DEFAULT_LARM_LEN if bonemap is None else bonemap.left_lower_arm_length
-        uarm_len = BoneMap.DEFAULT_UARM_LEN if bonemap is None else bonemap.left_upper_arm_length
         self._uarm_orig = BoneMap.DEFAULT_UARM_ORIG_RH if bonemap is None else bonemap.left_upper_arm_origin_rh
-        self._larm_vec, self._uarm_vec = np.array([-larm_len, 0, 0]), np.array([-uarm_len, 0, 0])
-        self._body_measurements = np.r_[self._larm_vec, self._uarm_vec, self._uarm_orig][np.newaxis, :]
+        body9 = body9_from_bonemap(bonemap)
+        self._larm_vec, self._uarm_vec = body9[0:3].copy(), body9[3:6].copy()
+        self._body_measurements = body9[np.newaxis, :]
         self._sync_model_config()
 
     def _take_stats(self, stats: dict):
@@ -320,14 +319,17 @@ class Estimator:
 
     # ---- offline replay: every frame of recorded sessions in one call ----
     def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64,
-                          return_targets: bool = False, seed: int = 0x5EED, max_rows_per_launch: int = 0):
+                          return_targets: bool = False, seed: int = 0x5EED, max_rows_per_launch: int = 0, bonemaps=None):
         """rows: float32 ``[F, 55|28]`` raw messages of one or more recordings back to back (host array or CUDA
         tensor); ``starts``: the recordings' first rows (default ``[0]``: one recording).  Returns, on the device,
         what ``process_row`` returns for every row of a fresh estimator fed each recording in order (no row skipped):
         ``[F, 25 + 6N]`` with ``add_mc_samples`` and N = smooth x Monte-Carlo samples > 1, else ``[F, 25]``.  With
         ``return_targets`` also the normalised NN targets float32 ``[F, n_mc, O]``.  The Monte-Carlo samples are those
         of one dropout forward keyed by ``seed`` over the repeated windows (``ape_replay``); ``max_rows_per_launch``
-        bounds the sample rows of one regressor launch (0: the library's default) and with it the device workspace."""
+        bounds the sample rows of one regressor launch (0: the library's default) and with it the device workspace.
+        ``bonemaps``: one entry per recording (bonemap-like objects, ``None`` for the defaults, or float64 ``[R, 9]`` values) --
+        every recording is then replayed as by an estimator built with ITS bonemap (``ape_replay_bodies``, DESIGN.md 4.24);
+        default: this estimator's body for all."""
         import ctypes as C
         from wear_mocap_ape_amd import _hip
         model, n_mc = self._hip_model(), self._frame_samples()
@@ -351,12 +353,14 @@ class Estimator:
             flags = (_hip.FLAG_NORMALIZE_INPUT if self._normalize else 0) | (_hip.FLAG_PACKED_MSG if packed else 0)
             kind = self._parse_kind | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _hip.check(_hip.lib().ape_replay(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
-                                             int(st.shape[0]), self._sequence_len, self._smooth, n_mc, float(model.dropout),
-                                             int(seed) & (2 ** 64 - 1), flags, C.c_void_p(out.data_ptr()),
-                                             _hip.F64 if out_dtype == torch.float64 else _hip.F32,
-                                             C.c_void_p(y.data_ptr()) if y is not None else None,
-                                             int(max_rows_per_launch), stream), "ape_replay")
+            bodies = None if bonemaps is None else bodies_from(bonemaps, int(st.shape[0]), "process_recording bonemaps")
+            _hip.check(_hip.lib().ape_replay_bodies(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
+                                                    int(st.shape[0]), self._sequence_len, self._smooth, n_mc, float(model.dropout),
+                                                    int(seed) & (2 ** 64 - 1), flags, C.c_void_p(out.data_ptr()),
+                                                    _hip.F64 if out_dtype == torch.float64 else _hip.F32,
+                                                    C.c_void_p(y.data_ptr()) if y is not None else None,
+                                                    int(max_rows_per_launch), stream,
+                                                    C.c_void_p(bodies.ctypes.data) if bodies is not None else None), "ape_replay_bodies")
             model._pending.clear()         # the call is blocking and checked the handle (its journal is empty)
         return (out, y) if return_targets else out
 

@@ -10,6 +10,7 @@ import torch
 
 from wear_mocap_ape_amd import _hip
 from wear_mocap_ape_amd.data_types import messaging
+from wear_mocap_ape_amd.data_types.bone_map import bodies_from
 from wear_mocap_ape_amd.estimate import kalman_models
 from wear_mocap_ape_amd.estimate.estimator import Estimator
 from wear_mocap_ape_amd.estimate.watch_phone_pocket_nn import features_from_row
@@ -173,14 +174,16 @@ class WatchPhonePocketKalman(Estimator):
         return cut.copy() if self.msg_as_array else cut.tolist()
 
     def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64, return_targets: bool = False,
-                          seed: int = 0x5EED):
+                          seed: int = 0x5EED, bonemaps=None):
         """rows: float32 ``[F, 55]`` raw messages of one or more recordings back to back (host array or CUDA tensor); ``starts``: the
         recordings' first rows (default ``[0]``).  Returns ``(out, n_rows)`` on the device -- for every row what ``process_row`` of a
         fresh estimator with ``manual_seed(seed)`` fed that recording returns (no row skipped; several recordings share the flipout
         draw of a frame, ``ape_kalman_replay``): ``out`` is ``[F, 25 + 6 * smooth * num_ensemble]`` with ``add_mc_samples`` (message,
         hand and elbow xyz of the ``n_rows[f]`` stacked rows, zeros; ``streams.trim_packed`` cuts a row), else ``[F, 25]``.  With
         ``return_targets`` also the normalised predictions float32 ``[F, num_ensemble, 14]`` (row 0 alone on a recording's first
-        W + 1 frames)."""
+        W + 1 frames).  ``bonemaps``: one entry per recording (bonemap-like objects, ``None``, or float64 ``[R, 9]`` values): every
+        recording as by an estimator built with its bonemap (``ape_kalman_replay_bodies``); default: this
+        estimator's body for all."""
         if out_dtype not in (torch.float32, torch.float64):
             raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
         model = self.__model
@@ -201,10 +204,12 @@ class WatchPhonePocketKalman(Estimator):
             body = np.ascontiguousarray(self._body_measurements.reshape(9), dtype=np.float64)
             kind = _hip.PARSE_WATCH_PHONE_POCKET | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _hip.check(_hip.lib().ape_kalman_replay(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
+            bodies = None if bonemaps is None else bodies_from(bonemaps, int(st.shape[0]), "process_recording bonemaps")
+            _hip.check(_hip.lib().ape_kalman_replay_bodies(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
                                                     int(st.shape[0]), self._smooth, *sp, _hip.dptr(body, C.c_double),
                                                     int(seed) & (2 ** 64 - 1), _hip.FLAG_PACKED_MSG if packed else 0,
                                                     C.c_void_p(out.data_ptr()), _hip.F64 if out_dtype == torch.float64 else _hip.F32,
                                                     C.c_void_p(n_rows.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
-                                                    stream), "ape_kalman_replay")
+                                                    stream, C.c_void_p(bodies.ctypes.data) if bodies is not None else None),
+                       "ape_kalman_replay_bodies")
         return (out, n_rows, y) if return_targets else (out, n_rows)

@@ -12,7 +12,7 @@ import torch
 
 from wear_mocap_ape_amd import _hip
 from wear_mocap_ape_amd.data_types import messaging
-from wear_mocap_ape_amd.data_types.bone_map import BoneMap
+from wear_mocap_ape_amd.data_types.bone_map import BoneMap, bodies_from
 from wear_mocap_ape_amd.estimate.estimator import Estimator
 from wear_mocap_ape_amd.estimate.watch_phone_uarm_nn import _LARM_DST_G, _LEFT_HAND_CAL, _UARM_DST_G, features_from_row
 from wear_mocap_ape_amd.utility import transformations as ts
@@ -108,10 +108,12 @@ class WatchPhoneUarm(Estimator):
             self._device_frame = _FkFrame(self._smooth, self._body_measurements, torch.cuda.current_device())
         return self._device_frame
 
-    def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64):
+    def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64, bonemaps=None):
         """rows: float32 ``[F, 55]`` raw messages of one or more recordings back to back (host array or CUDA tensor);
         ``starts``: the recordings' first rows (default ``[0]``).  Returns, on the device, ``[F, 25]``: what ``process_row``
-        of a fresh estimator fed each recording in order returns for every row (``ape_fk_replay``, blocking)."""
+        of a fresh estimator fed each recording in order returns for every row (``ape_fk_replay``, blocking).  ``bonemaps``: one
+        entry per recording (bonemap-like objects, ``None``, or float64 ``[R, 9]`` values): every recording as by an estimator built
+        with its bonemap (``ape_fk_replay_bodies``); default: this estimator's body for all."""
         if out_dtype not in (torch.float32, torch.float64):
             raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
         if isinstance(rows, torch.Tensor) and rows.is_cuda:
@@ -128,7 +130,9 @@ class WatchPhoneUarm(Estimator):
             body = _body9(self._body_measurements)
             kind = self._parse_kind | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-            _hip.check(_hip.lib().ape_fk_replay(kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data), int(st.shape[0]),
-                                                self._smooth, _hip.dptr(body, C.c_double), dev.index, C.c_void_p(out.data_ptr()),
-                                                _hip.F64 if out_dtype == torch.float64 else _hip.F32, stream), "ape_fk_replay")
+            bodies = None if bonemaps is None else bodies_from(bonemaps, int(st.shape[0]), "process_recording bonemaps")
+            _hip.check(_hip.lib().ape_fk_replay_bodies(kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data), int(st.shape[0]),
+                                                       self._smooth, _hip.dptr(body, C.c_double), dev.index, C.c_void_p(out.data_ptr()),
+                                                       _hip.F64 if out_dtype == torch.float64 else _hip.F32, stream,
+                                                       C.c_void_p(bodies.ctypes.data) if bodies is not None else None), "ape_fk_replay_bodies")
         return out

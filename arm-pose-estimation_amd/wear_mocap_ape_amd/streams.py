@@ -63,6 +63,30 @@ def broadcast_stats(stats: dict, I: int, O: int, device: torch.device, src: int 
     return {"xx_m": h[:I], "xx_s": h[I:2 * I], "yy_m": h[2 * I:2 * I + O], "yy_s": h[2 * I + O:]}
 
 
+def _set_bodies(bank, entry: str, bodies, streams):
+    """the ``set_bodies`` of the three banks (C ABI ``ape_*_set_bodies``)"""
+    from .data_types.bone_map import bodies_from
+    C = bank._C
+    idx = None if streams is None else bank._indices(streams)
+    K = bank._n if idx is None else int(idx.shape[0])
+    vals = bodies_from(bodies, K, "set_bodies")
+    bank._hip.check(getattr(bank._hip.lib(), entry)(bank._handle, C.c_void_p(idx.ctypes.data) if idx is not None else None, K,
+                                                    C.c_void_p(vals.ctypes.data), bank._stream()), entry)
+
+
+def _get_bodies(bank, entry: str) -> np.ndarray:
+    out = np.empty((bank._n, 9), dtype=np.float64)
+    bank._hip.check(getattr(bank._hip.lib(), entry)(bank._handle, bank._C.c_void_p(out.ctypes.data)), entry)
+    return out
+
+
+_SET_BODIES_DOC = """Per-stream body measurements (DESIGN.md 4.24): ``bodies`` float64 ``[K, 9]`` (``[larm_vec, uarm_vec,
+        uarm_orig_rh]`` per row) or a sequence of K bonemap-like objects / ``None`` (the defaults); ``streams`` K distinct indices, or
+        ``None`` for all S streams in order.  From the next frame enqueued on the current stream on, stream s takes its body from row s
+        (frames already enqueued keep the old values).  NOT a cold start: the stream's next message is computed from its existing
+        window and stack with the new body -- handing a slot to a new wearer is ``set_bodies`` + ``reset(streams=[s])``."""
+
+
 class StreamBank:
     """The per-frame step of many independent wearable streams with all state on the device: window rings,
     smoothing stacks, regressor, FK and messages (C ABI ``ape_streams_*``).  For every stream it does what one
@@ -117,6 +141,13 @@ class StreamBank:
         idx = self._indices(streams)
         self._hip.check(self._hip.lib().ape_streams_reset_subset(self._handle, self._C.c_void_p(idx.ctypes.data), int(idx.shape[0])),
                         "ape_streams_reset_subset")
+
+    def set_bodies(self, bodies, streams=None):
+        _set_bodies(self, "ape_streams_set_bodies", bodies, streams)
+    set_bodies.__doc__ = _SET_BODIES_DOC
+
+    bodies = property(lambda self: _get_bodies(self, "ape_streams_get_bodies"),
+                      doc="float64 [S, 9] mirror of the per-stream bodies; S copies of the model's body before the first set_bodies")
 
     def _indices(self, streams) -> np.ndarray:
         a = np.asarray(streams)
@@ -243,7 +274,7 @@ class FkStreamBank:
 
     def __init__(self, n_streams: int, smooth: int = 5, bonemap=None, dtype: torch.dtype = torch.float32, device=None):
         from . import _hip
-        from .data_types.bone_map import BoneMap
+        from .data_types.bone_map import body9_from_bonemap
         import ctypes as C
         self._hip, self._C = _hip, C
         if dtype not in (torch.float32, torch.float64):
@@ -257,10 +288,7 @@ class FkStreamBank:
         self._device = torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
         if self._device.index is None:
             self._device = torch.device("cuda", torch.cuda.current_device())
-        larm = BoneMap.DEFAULT_LARM_LEN if bonemap is None else bonemap.left_lower_arm_length
-        uarm = BoneMap.DEFAULT_UARM_LEN if bonemap is None else bonemap.left_upper_arm_length
-        orig = BoneMap.DEFAULT_UARM_ORIG_RH if bonemap is None else bonemap.left_upper_arm_origin_rh
-        self._body = np.ascontiguousarray(np.r_[[-larm, 0, 0], [-uarm, 0, 0], orig], dtype=np.float64)
+        self._body = body9_from_bonemap(bonemap)
         handle = C.c_void_p()
         _hip.check(_hip.lib().ape_fk_bank_create(self._n, self._smooth, _hip.dptr(self._body, C.c_double), self._device.index,
                                                  C.byref(handle)), "ape_fk_bank_create")
@@ -277,6 +305,13 @@ class FkStreamBank:
             pass
 
     body_measurements = property(lambda self: self._body[np.newaxis, :].copy())
+
+    def set_bodies(self, bodies, streams=None):
+        _set_bodies(self, "ape_fk_bank_set_bodies", bodies, streams)
+    set_bodies.__doc__ = _SET_BODIES_DOC
+
+    bodies = property(lambda self: _get_bodies(self, "ape_fk_bank_get_bodies"),
+                      doc="float64 [S, 9] mirror of the per-stream bodies; S copies of ``body_measurements`` before the first set_bodies")
 
     def _stream(self):
         return self._C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
@@ -351,7 +386,7 @@ class KalmanStreamBank:
     def __init__(self, model, n_streams: int, smooth: int = 1, normalize: bool = True, bonemap=None, seed: int = 0x5EED,
                  dtype: torch.dtype = torch.float64):
         from . import _hip
-        from .data_types.bone_map import BoneMap
+        from .data_types.bone_map import body9_from_bonemap
         import ctypes as C
         self._hip, self._C = _hip, C
         if dtype not in (torch.float32, torch.float64):
@@ -366,10 +401,7 @@ class KalmanStreamBank:
         handle = C.c_void_p()
         _hip.check(_hip.lib().ape_kalman_bank_create(model.handle, self._n, self._smooth, C.byref(handle)), "ape_kalman_bank_create")
         self._handle = handle
-        larm = BoneMap.DEFAULT_LARM_LEN if bonemap is None else bonemap.left_lower_arm_length
-        uarm = BoneMap.DEFAULT_UARM_LEN if bonemap is None else bonemap.left_upper_arm_length
-        orig = BoneMap.DEFAULT_UARM_ORIG_RH if bonemap is None else bonemap.left_upper_arm_origin_rh
-        self.set_body(np.r_[[-larm, 0, 0], [-uarm, 0, 0], orig])
+        self.set_body(body9_from_bonemap(bonemap))
         if normalize:
             from .utility import data_stats
             from .utility.names import NNS_INPUTS, NNS_TARGETS
@@ -390,7 +422,15 @@ class KalmanStreamBank:
     packed_width = property(lambda self: self._width)
     body_measurements = property(lambda self: self._body[np.newaxis, :].copy())
 
+    def set_bodies(self, bodies, streams=None):
+        _set_bodies(self, "ape_kalman_bank_set_bodies", bodies, streams)
+    set_bodies.__doc__ = _SET_BODIES_DOC
+
+    bodies = property(lambda self: _get_bodies(self, "ape_kalman_bank_get_bodies"),
+                      doc="float64 [S, 9] mirror of the per-stream bodies; S copies of ``body_measurements`` before the first set_bodies")
+
     def set_body(self, body9):
+        """one body for every stream; on a bank that was given per-stream bodies it overwrites every row"""
         self._body = np.ascontiguousarray(np.asarray(body9, dtype=np.float64).reshape(9))
         self._hip.check(self._hip.lib().ape_kalman_bank_set_body(self._handle, self._hip.dptr(self._body, self._C.c_double)),
                         "ape_kalman_bank_set_body")

@@ -353,6 +353,33 @@ int ape_streams_reset_subset(ape_streams_t* bank, const int32_t* streams_host, i
 int ape_streams_frame_subset(ape_streams_t* bank, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
                              uint32_t flags, void* out_dev, int32_t out_dtype, void* stream);
 
+/* per-stream body measurements (additive in ABI 7).  replaces: the bonemap every reference Estimator is built with
+ * (estimator.py:57-68: lower-arm vector, upper-arm vector, shoulder origin), whose nine values enter every origin of its messages
+ * (estimate_joints.py:48-92, compose_msg.py:54-61,92-94) -- S estimators with S bonemaps in one bank.
+ * A bank that was never given bodies passes its uniform body (ape_model_set_body; body9 of ape_fk_bank_create; ape_kalman_bank_set_body)
+ * to its kernels by value, as before.  The first ape_*_set_bodies call gives the bank a device table of S rows, initialised from that
+ * uniform body, and overwrites the listed rows; from then on every frame of the bank (lockstep, subset, host frames, and the frames
+ * ape_model_recover issues again) takes stream s's body from row s, and a later ape_model_set_body no longer reaches the bank.
+ *   streams_host   K DISTINCT stream indices (host memory), or NULL: all S streams in order, K == S
+ *   body9s_host    f64 [K,9] (host memory): row j = [larm_vec, uarm_vec, uarm_orig_rh] of stream streams_host[j]; not validated (the
+ *                  reference does not either: NaN propagates as there); free for reuse on return
+ * Ordered on `stream`: frames enqueued before the call see the old values, frames enqueued after it the new ones.  NO cold start:
+ * windows, state histories and smoothing stacks hold features and NN targets, which do not depend on the body -- the stream's next
+ * message is computed from its existing stack with the new body; a slot handed to a new wearer is set_bodies + a reset of that stream.
+ * K = 0 changes no row (and still switches the bank to its table).  ape_kalman_bank_set_body on a bank in table mode overwrites every
+ * row (ordered on the null stream).  ape_*_get_bodies: the host mirror [S,9]; S copies of the uniform body before the first set.
+ * Refused (non-zero, ape_last_error): NULL bank or values, K < 0 or K > S, NULL list with K != S, an index outside [0, S), a duplicate
+ * index, a capturing stream.  ape_infer, ape_fk and ape_msg_reduce keep the model's one body. */
+int ape_streams_set_bodies(ape_streams_t* bank, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream);
+int ape_streams_get_bodies(ape_streams_t* bank, double* out_host);
+/* ape_replay with one body per recording: bodies_host f64 [R,9] (host memory), row r for the recording that starts at seg_starts_host[r];
+ * row f of out_dev is what a fresh estimator BUILT WITH that recording's bonemap returns for its row f.  NULL: ape_replay (the model's
+ * body for every recording, on the same kernels as before). */
+int ape_replay_bodies(ape_model_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                      int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+                      void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream,
+                      const double* bodies_host);
+
 /* ---- the estimator without a regressor: WatchPhoneUarm (additive in ABI 7) -------------------------------------
  * Replaces estimate/watch_phone_uarm.py:10-108 behind Estimator (estimator.py:93-137): per frame the 38 features of
  * APE_PARSE_WATCH_PHONE_UARM, the watch's and the phone's calibrated 6D columns (features 13:19 and 32:38) as the 12 targets of
@@ -381,6 +408,14 @@ int ape_fk_bank_frame(ape_fk_bank_t* bank, int32_t kind, const float* rows_dev, 
 int ape_fk_bank_frame_host(ape_fk_bank_t* bank, int32_t kind, const float* rows_host, void* out_host, int32_t out_dtype, void* stream);
 int ape_fk_replay(int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t smooth,
                   const double body9[9], int32_t device, void* out_dev, int32_t out_dtype, void* stream);
+/* per-stream bodies of the bank and one body per recording of a replay (semantics above at ape_streams_set_bodies):
+ * the FK-only estimator's bonemap (watch_phone_uarm.py behind estimator.py:57-68).  ape_fk_replay_bodies: bodies_host f64 [R,9] or
+ * NULL = body9 for every recording (ape_fk_replay); with bodies_host given body9 may be NULL. */
+int ape_fk_bank_set_bodies(ape_fk_bank_t* bank, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream);
+int ape_fk_bank_get_bodies(ape_fk_bank_t* bank, double* out_host);
+int ape_fk_replay_bodies(int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t smooth,
+                         const double body9[9], int32_t device, void* out_dev, int32_t out_dtype, void* stream,
+                         const double* bodies_host);
 
 /* kernel selection for A/B runs and tests; no effect on results beyond float32 summation order */
 int ape_model_set_kernel(ape_model_t* model, int32_t choice);
@@ -509,6 +544,15 @@ int ape_kalman_replay(ape_kalman_t* model, int32_t kind, const float* rows_dev, 
                       int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
                       const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
                       float* y_dev, void* stream);
+/* per-stream bodies of the Kalman bank and one body per recording of its replay (semantics above at
+ * ape_streams_set_bodies): the bonemap of WatchPhonePocketKalman's Estimator (estimator.py:57-68).  ape_kalman_replay_bodies:
+ * bodies_host f64 [R,9] or NULL = body9 for every recording (ape_kalman_replay); with bodies_host given body9 may be NULL. */
+int ape_kalman_bank_set_bodies(ape_kalman_bank_t* bank, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream);
+int ape_kalman_bank_get_bodies(ape_kalman_bank_t* bank, double* out_host);
+int ape_kalman_replay_bodies(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                             int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
+                             const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
+                             float* y_dev, void* stream, const double* bodies_host);
 
 #ifdef __cplusplus
 }
