@@ -165,7 +165,7 @@ __device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 r
 #ifndef C32_QPD
 #define C32_QPD 0
 #endif
-template <int H, int L, int KX, bool ENDS>
+template <int H, int L, int KX, bool ENDS, int BXU>
 __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams p) {
     constexpr int UPW = 8;                  // hidden units per wave (x 4 gates = the 32 columns of its tile)
     constexpr int GH = H / (4 * UPW);       // members per cluster
@@ -178,6 +178,9 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     constexpr int HL = GH * 4 * MR * 8;     // floats of one gathered slice set [member][wave][window][8 units] = 32 KB
     constexpr int NDMA = HL * 4 / 1024 / 4; // LDS-DMA instructions per wave and gather
     static_assert(H == 256 && L == 2 && KX == 32 && GH == 8 && NDMA == 8, "built for the 2 x 256 models");
+    // BXU: k-blocks of the x slab that layer 0's input span really multiplies -- ceil(I / 8) of the BX staged ones (the launcher's choice; columns
+    // I .. KX - 1 are zeros, a block of them adds +0.0 to every sum; the staging layout and the weight image stay those of KX = 32)
+    static_assert(BXU == BX || (BXU == BX - 1 && !ENDS), "the short-window instantiation keeps the four-block input span");
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -270,13 +273,13 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     //      then travels while the other 384 registers come in (`load_weights`, called behind it).
     //      The image is the split one (pack_c32_split): layer 0's input columns as above times 2^S, every recurrent / layer-1 column as
     //      K = 16 slices of f16 hi / lo A fragments, two groups of four registers each -- the same 400 registers.
-    float w0[4 * BX];
+    float w0[4 * BXU];
     u32x4 w0h[NW0 / 4 - BX];
     u32x4 w1[NW1 / 4];
     const f32x4* const s0 = reinterpret_cast<const f32x4*>(p.wcl[0]) + ((size_t)(member * 4 + wave) * (NW0 / 4)) * 64 + lane;
     const u32x4* const s1 = reinterpret_cast<const u32x4*>(p.wcl[1]) + ((size_t)(member * 4 + wave) * (NW1 / 4)) * 64 + lane;
 #pragma unroll
-    for (int i = 0; i < BX; ++i) {
+    for (int i = 0; i < BXU; ++i) {
         const f32x4 v = s0[i * 64];
         w0[4 * i] = v[0]; w0[4 * i + 1] = v[1]; w0[4 * i + 2] = v[2]; w0[4 * i + 3] = v[3];
     }
@@ -459,7 +462,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             const f32x4 bv = bias_s[((wave * L + 0) * 4 + gate) * 64 + lane];
             acc[4 * gate] = bv[0]; acc[4 * gate + 1] = bv[1]; acc[4 * gate + 2] = bv[2]; acc[4 * gate + 3] = bv[3];
         }
-        span32<BX, false, 4 * BX>(acc, xin + n * SX + hh * 4, 8, w0, 0, [&](int) {});
+        span32<BXU, false, 4 * BXU>(acc, xin + n * SX + hh * 4, 8, w0, 0, [&](int) {});
         mfma_drain(acc);
         float h0[4];
         cell_update(acc, 0, cst[0], h0);
@@ -582,7 +585,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         //       through THEIR next section, are in no hurry
         //   QP  look at the flags the next section needs (one load per lane)    QJ  judge
         //   QJ .. QJ+7  one piece of the next section's gather per block
-        constexpr int NBL = (l == 0) ? BX + BH : 2 * BH;
+        constexpr int NBL = (l == 0) ? BXU + BH : 2 * BH;
         // (positions swept on MI355X, 1024 x 64: QF 1 / 2 / 3 / 10 / 16 -> 826 / 833 / 819 / 828 / 858 us -- earlier stalls on the store's
         //  acknowledgement, later the peers' look finds nothing; look 12 blocks ahead of the judge instead of 4 -> 840: the flags are not up yet)
         constexpr int QF = C32_QF, QP = (MODE == 1) ? 16 : NBL / 2 - 2 + C32_QPD, QJ = (MODE == 1) ? 20 : NBL / 2 + 2 + C32_QPD;
@@ -646,8 +649,8 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             }
             const int frag = hh * 2 * MR * 4 + n * 4;             // this lane's hi fragment of slice 0: block hh, window n
             if constexpr (l == 0) {
-                span32<BX, false, 4 * BX>(acc, xin + n * SX + hh * 4, 8, w0, 0, [&](int q) { mid(q); });
-                if (ST || t > 0) span16<BH / 2, false, NW0 / 4 - BX>(acc, hb0 + ((t - 1) & 1) * HL + frag, w0h, 0, [&](int q) { mid(BX + q); });
+                span32<BXU, false, 4 * BXU>(acc, xin + n * SX + hh * 4, 8, w0, 0, [&](int q) { mid(q); });
+                if (ST || t > 0) span16<BH / 2, false, NW0 / 4 - BX>(acc, hb0 + ((t - 1) & 1) * HL + frag, w0h, 0, [&](int q) { mid(BXU + q); });
             } else if constexpr (MODE == 3) {
                 // input span: the common hooks (flag owed at QF, the look for the NEXT section at QP) + the look at the OWN layer's flags at
                 // QO, the judge four blocks on, the gather behind it; outside the steady state a second look twelve blocks after the first
@@ -882,10 +885,13 @@ bool ape_cluster32_supported(int H, int L, int KX) { return H == 256 && L == 2 &
 hipError_t ape_prepare_lstm_cluster32(int H, int L, int KX) {
     if (!ape_cluster32_supported(H, L, KX)) return hipSuccess;
     static_assert(smem_bytes32() <= APE_LDS_BYTES, "LDS layout exceeds a CU");
-    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_lstm_cluster32<256, 2, 32, false>),
+    hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_lstm_cluster32<256, 2, 32, false, 3>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, APE_LDS_BYTES);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_lstm_cluster32<256, 2, 32, true>),
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_lstm_cluster32<256, 2, 32, false, 4>),
+                            hipFuncAttributeMaxDynamicSharedMemorySize, APE_LDS_BYTES);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_lstm_cluster32<256, 2, 32, true, 4>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, APE_LDS_BYTES);
 }
 
@@ -895,7 +901,9 @@ hipError_t ape_launch_lstm_cluster32(int H, int L, int KX, int clusters, const C
     if (!ape_cluster32_supported(H, L, KX)) return hipErrorInvalidValue;
     const int grid_clusters = (clusters + 7) / 8 * 8;
     constexpr size_t smem = smem_bytes32();
-    if (p.T <= APE_C32_ENDS_MAX_T) hipLaunchKernelGGL((ape_lstm_cluster32<256, 2, 32, true>), dim3(grid_clusters * 8), dim3(256), smem, stream, p);
-    else hipLaunchKernelGGL((ape_lstm_cluster32<256, 2, 32, false>), dim3(grid_clusters * 8), dim3(256), smem, stream, p);
+    // (long windows: the input span skips the x slab's fourth k-block when it is all padding -- I = 22 / 20 of the deployed models)
+    if (p.T <= APE_C32_ENDS_MAX_T) hipLaunchKernelGGL((ape_lstm_cluster32<256, 2, 32, true, 4>), dim3(grid_clusters * 8), dim3(256), smem, stream, p);
+    else if (p.I <= 24) hipLaunchKernelGGL((ape_lstm_cluster32<256, 2, 32, false, 3>), dim3(grid_clusters * 8), dim3(256), smem, stream, p);
+    else hipLaunchKernelGGL((ape_lstm_cluster32<256, 2, 32, false, 4>), dim3(grid_clusters * 8), dim3(256), smem, stream, p);
     return hipGetLastError();
 }

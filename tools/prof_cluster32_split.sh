@@ -1,6 +1,6 @@
 # rocprofv3 passes behind profiles/r07_cluster32_split.md (run on a GPU machine from the repository root:
 # bash tools/prof_cluster32_split.sh [OUT_DIR]; OUT_DIR receives copies of the bench line, the trace log and the two records):
-# lstm_cluster32.hip with its recurrent products on f16 MFMAs.  Every pass runs under its own time limit and the chain stops at the
+# lstm_cluster32.hip with its recurrent products on f16 MFMAs (the kernel is named by the prefix its long-window instantiations `<..., false, 3 | 4>` share).  Every pass runs under its own time limit and the chain stops at the
 # first failure; counters are collected in runs of their own (no --pmc beside any other tracing).
 set -e
 R=$PWD
@@ -17,7 +17,7 @@ timeout -k 10 240 rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES GRBM_G
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc SQ_INSTS_VALU_MFMA_MOPS_F16 -d $P/mfma16 -- $B > /dev/null 2>&1
 timeout -k 10 240 rocprofv3 --kernel-trace --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY -d $P/wave -- $B > /dev/null 2>&1
 echo counters done
-python3 tools/summarize_prof.py r07_cluster32_split $P/trace $P/fetch $P/write "ape_lstm_cluster32<256, 2, 32, false>" 65536 1024 --model pocket --T 64 \
+python3 tools/summarize_prof.py r07_cluster32_split $P/trace $P/fetch $P/write "ape_lstm_cluster32<256, 2, 32, false" 65536 1024 --model pocket --T 64 \
     --pmc-dir $P/mfma --pmc-dir $P/mfma16 --pmc-dir $P/wave \
     --source csrc/lstm_cluster32.hip --lds 137232 --flop-per-launch 1.06039345152e11 --peak-tflops 157.3 --skip-first 90 --min-us 200 \
     --note "Command (MI355X, one GPU): \`rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 200 --warmup 50 --no-cpu-baseline\` (launches 91..290 of the 1024 x 64 shape are the timed ones); counters from separate \`--kernel-trace --pmc\` passes of \`bench.py --steps 20 --warmup 5 --no-cpu-baseline\` (FETCH_SIZE; WRITE_SIZE; SQ_VALU_MFMA_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_VALU_MFMA_MOPS_F32; SQ_INSTS_VALU_MFMA_MOPS_F16; SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_INST_ANY SQ_WAIT_ANY); recipe \`tools/prof_cluster32_split.sh\`, summarised on the GPU box by \`tools/summarize_prof.py\`. The peak and MfmaUtil are stated against the f32 matrix peak (157.3 TFLOP/s) like every earlier cluster32 profile; the recurrent products now run on f16 MFMAs."
