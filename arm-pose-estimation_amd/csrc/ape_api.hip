@@ -1531,13 +1531,61 @@ int ape_infer(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t
 // ---- stream bank ------------------------------------------------------------------------------------------
 
 // (re)allocates the three rings for the bank's current S, T, smooth, n_mc
+// window copies a stream keeps in the feature ring: n_mc for the LSTM banks ([S,n_mc,T,I], one window per sample row of the fused dropout
+// kernels), one for DropoutFF (the trunk runs once per stream) and ImuPoseLSTM (one row per stream)
+static int bank_copies(const ape_streams* b) { return b->model->dims.model_kind == APE_MODEL_LSTM ? b->n_mc : 1; }
+
+// The regressor of a DropoutFF frame or replay chunk (ff_bank.hip): sample rows [row_base, row_base + rows) of a call whose
+// global row r is sample r % n_mc of group (stream / frame) r / n_mc.  `x`: the newest feature row of group g_base + j at x + j * x_stride,
+// g_base = row_base / n_mc.  The trunk once per group (ape_mlp_tile16 with hidden_out: f64 z-score, input layer, hidden layers) into
+// `hid` [groups,H], then the n_mc masked heads.  No cooperative kernel: nothing here waits for another workgroup.
+static int ff_bank_forward(ape_model* m, const float* x, size_t x_stride, long long row_base, int rows, int n_mc, bool norm, const float* masks,
+                           float dropout_p, uint64_t seed, float* hid, float* y, void* stream, hipEvent_t ev_a = nullptr, hipEvent_t ev_z = nullptr) {
+    if (!m->has_weights) return fail(APE_ERR_NOT_READY, "ff bank: weights not loaded");
+    const int H = m->dims.hidden_size, L = m->dims.num_layers, I = m->dims.input_size;
+    const long long g_base = row_base / n_mc;
+    const int groups = (int)((row_base + rows + n_mc - 1) / n_mc - g_base);
+    MlpParams q{};
+    q.x = x; q.y = nullptr; q.hidden_out = hid;
+    for (int j = 0; j <= L; ++j) { q.wpack[j] = m->ff_wpack[j]; q.bias[j] = m->ff_bias[j]; }
+    q.w_out = m->w_out; q.b_out = m->b_out;
+    q.xx_m = m->stats; q.xx_s = m->stats + I;
+    q.row_stride = x_stride; q.row_offset = 0;
+    q.N = groups; q.I = I; q.O = m->dims.output_size; q.KX = m->KX; q.n_hidden = L;
+    q.flags = norm ? APE_FLAG_NORMALIZE_INPUT : 0u;
+    q.neg_slope = 0.01f;                      // torch's leaky_relu default (nn_models.py:347,349)
+    if (ev_a) (void)hipEventRecord(ev_a, (hipStream_t)stream);
+    hipError_t e = ape_launch_mlp_tile16(H, q, (hipStream_t)stream, m->n_cus);
+    if (e != hipSuccess) return fail(APE_ERR_HIP, "ff bank: trunk launch failed: %s", hipGetErrorString(e));
+    FfHeadParams hp{};
+    hp.hidden = hid; hp.w_out = m->w_out; hp.b_out = m->b_out; hp.masks = masks; hp.y = y;
+    hp.row_base = row_base; hp.g_base = g_base; hp.rows = rows; hp.n_mc = n_mc; hp.H = H; hp.O = m->dims.output_size;
+    hp.dropout_p = dropout_p; hp.seed = seed;
+    m->last_kernel = "ape_ff_bank_head";
+    e = ape_launch_ff_bank_head(hp, (hipStream_t)stream);
+    if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(APE_ERR_HIP, "ff bank: head launch failed: %s", hipGetErrorString(e));
+    return APE_OK;
+}
+
+static void bank_free_regressor_ws(ape_streams* b) {
+    if (b->ffhid) (void)hipFree(b->ffhid);
+    if (b->xwin) (void)hipFree(b->xwin);
+    b->ffhid = b->xwin = nullptr;
+}
+
 static hipError_t bank_alloc(ape_streams* b) {
     const size_t I = b->model->dims.input_size, O = b->model->dims.output_size, R = (size_t)b->S * b->n_mc;
     if (b->xring) (void)hipFree(b->xring);
     if (b->yring) (void)hipFree(b->yring);
     if (b->y_new) (void)hipFree(b->y_new);
     b->xring = b->yring = b->y_new = nullptr;
-    hipError_t e = hipMalloc((void**)&b->xring, R * b->T * I * sizeof(float));
+    bank_free_regressor_ws(b);
+    hipError_t e = hipMalloc((void**)&b->xring, (size_t)b->S * bank_copies(b) * b->T * I * sizeof(float));
+    if (e == hipSuccess && b->model->dims.model_kind == APE_MODEL_FF)
+        e = hipMalloc((void**)&b->ffhid, (size_t)b->S * b->model->dims.hidden_size * sizeof(float));
+    if (e == hipSuccess && b->model->dims.model_kind == APE_MODEL_IMUPOSE)
+        e = hipMalloc((void**)&b->xwin, (size_t)b->S * b->T * I * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&b->yring, R * b->smooth * O * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&b->y_new, R * O * sizeof(float));
     // a few streams with tall smoothing stacks: the post-filter deals a stream's stack over several workgroups (one CU each)
@@ -1557,13 +1605,15 @@ int ape_streams_create(ape_model_t* m, int32_t n_streams, int32_t seq_len, int32
     if (!out) return fail(APE_ERR_INVALID_ARG, "streams_create: out is NULL");
     *out = nullptr;
     if (!m) return fail(APE_ERR_INVALID_ARG, "streams_create: NULL model");
-    if (m->dims.model_kind != APE_MODEL_LSTM) return fail(APE_ERR_UNSUPPORTED, "streams_create: LSTM models only");
     if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "streams_create: model has no target layout");
     if (n_streams < 1 || seq_len < 1) return fail(APE_ERR_INVALID_ARG, "streams_create: n_streams=%d seq_len=%d", n_streams, seq_len);
     if (smooth < 1 || smooth > 64) return fail(APE_ERR_UNSUPPORTED, "streams_create: smooth %d outside 1..64", smooth);
     ape_streams* b = new (std::nothrow) ape_streams();
     if (!b) return fail(APE_ERR_HIP, "out of host memory");
     b->model = m; b->S = n_streams; b->T = seq_len; b->smooth = smooth;
+    // DropoutFF (nn_models.py:340-352 behind watch_phone_pocket_nn.py:111): [:, -1, :] of a row-wise MLP -- the window, its length and its
+    // cold-start padding have no influence on the output, so the bank keeps the newest row only
+    if (m->dims.model_kind == APE_MODEL_FF) b->T = 1;
     hipError_t e = hipSetDevice(m->dims.device);
     if (e == hipSuccess) e = bank_alloc(b);
     if (e != hipSuccess) {
@@ -1653,7 +1703,10 @@ int ape_streams_set_mc(ape_streams_t* b, int32_t n_mc, float dropout_p, uint64_t
     if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return fail(APE_ERR_INVALID_ARG, "streams_set_mc: dropout_p %g outside [0,1)", (double)dropout_p);
     HIP_TRY(hipSetDevice(b->model->dims.device));
     HIP_TRY(hipDeviceSynchronize());             // the rings may still be read by an earlier step
-    b->n_mc = n_mc; b->mc = true; b->dropout_p = dropout_p; b->seed = seed; b->mc_calls = 0;
+    // ImuPoseLSTM.monte_carlo_predictions(n_samples, x) is self(x, None) (nn_models.py:246-251): the count is ignored and there is no
+    // dropout -- the bank keeps one row per stream and frame (the call is still the cold start it is for the other banks)
+    if (b->model->dims.model_kind == APE_MODEL_IMUPOSE) { n_mc = 1; dropout_p = 0.0f; }
+    b->n_mc = n_mc; b->mc = b->model->dims.model_kind != APE_MODEL_IMUPOSE; b->dropout_p = dropout_p; b->seed = seed; b->mc_calls = 0;
     b->frames = 0; b->steps = 0;
     b->per_stream = false;
     subset_free(b);
@@ -1665,6 +1718,7 @@ int ape_streams_set_mc(ape_streams_t* b, int32_t n_mc, float dropout_p, uint64_t
         if (b->yring) (void)hipFree(b->yring);
         if (b->y_new) (void)hipFree(b->y_new);
         b->xring = b->yring = b->y_new = nullptr;
+        bank_free_regressor_ws(b);
         return fail(APE_ERR_HIP, "streams_set_mc: allocation failed: %s", hipGetErrorString(e));
     }
     // Layer 0 once per stream (nn.LSTM's dropout sits BETWEEN the layers, so h_0(t) is the same for all samples of a
@@ -1676,7 +1730,7 @@ int ape_streams_set_mc(ape_streams_t* b, int32_t n_mc, float dropout_p, uint64_t
     const long long sample_rows = (long long)b->S * n_mc;
     const bool can_up128 = m->up128_ok && m->c32_on;
     const bool can_up32 = (m->up32_ok && m->c32_on && f16v2_capacity(m->n_cus) >= 8) || can_up128;
-    b->shared_l0 = m->upper_ok && m->kernel_choice == APE_KERNEL_AUTO && m->precision == APE_PRECISION_F32 &&
+    b->shared_l0 = m->dims.model_kind == APE_MODEL_LSTM && m->upper_ok && m->kernel_choice == APE_KERNEL_AUTO && m->precision == APE_PRECISION_F32 &&
                    dropout_p > 0.0f && n_mc >= 2 &&
                    bank_shares_layer0(sample_rows, m->n_cus, can_up32, can_up128);
     if (b->xfrag) { (void)hipFree(b->xfrag); b->xfrag = nullptr; }
@@ -1729,6 +1783,7 @@ int ape_streams_destroy(ape_streams_t* b) {
     if (b->yring) (void)hipFree(b->yring);
     if (b->y_new) (void)hipFree(b->y_new);
     if (b->post_part) (void)hipFree(b->post_part);
+    bank_free_regressor_ws(b);
     if (b->xfrag) (void)hipFree(b->xfrag);
     if (b->ypart) (void)hipFree(b->ypart);
     if (b->xfrag0) (void)hipFree(b->xfrag0);
@@ -1790,7 +1845,7 @@ int ape_streams_get_bodies(ape_streams_t* b, double* out_host) {
 static void next_slot(const ape_streams* b, size_t I, float** out, int* rep, size_t* rep_stride) {
     const bool cold = b->frames == 0;
     *out = b->xring + (cold ? 0 : (size_t)(b->frames % b->T) * I);
-    const int copies = b->shared_l0 ? 1 : b->n_mc;      // layer 0 shared: only a stream's first window copy is ever read
+    const int copies = b->shared_l0 ? 1 : bank_copies(b);      // layer 0 shared: only a stream's first window copy is ever read
     *rep = cold ? b->T * copies : copies;
     *rep_stride = cold ? I : (size_t)b->T * I;
 }
@@ -1808,7 +1863,7 @@ int ape_streams_push_rows(ape_streams_t* b, int32_t kind, const float* rows_dev,
                     b->model->dims.input_size);
     float* out; int rep; size_t rep_stride;
     next_slot(b, (size_t)I, &out, &rep, &rep_stride);
-    hipError_t e = ape_launch_parse_rows(rows_dev, b->S, width, kind, out, APE_F32, I, (size_t)b->n_mc * b->T * I, rep,
+    hipError_t e = ape_launch_parse_rows(rows_dev, b->S, width, kind, out, APE_F32, I, (size_t)bank_copies(b) * b->T * I, rep,
                                          rep_stride, big_endian, (hipStream_t)stream);
     if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_push_rows launch failed: %s", hipGetErrorString(e));
     ++b->frames;
@@ -1822,7 +1877,7 @@ int ape_streams_push_features(ape_streams_t* b, const float* xx_dev, void* strea
     const int I = b->model->dims.input_size;
     float* out; int rep; size_t rep_stride;
     next_slot(b, (size_t)I, &out, &rep, &rep_stride);
-    hipError_t e = ape_launch_ring_write(xx_dev, b->S, I, out, (size_t)b->n_mc * b->T * I, rep, rep_stride, (hipStream_t)stream);
+    hipError_t e = ape_launch_ring_write(xx_dev, b->S, I, out, (size_t)bank_copies(b) * b->T * I, rep, rep_stride, (hipStream_t)stream);
     if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_push_features launch failed: %s", hipGetErrorString(e));
     ++b->frames;
     return APE_OK;
@@ -1840,7 +1895,7 @@ int ape_streams_step(ape_streams_t* b, uint32_t flags, void* msg_dev, void* tail
 // a few streams in Monte-Carlo mode (one estimator's frame: S = 1) step on the Monte-Carlo latency kernel
 static bool bank_on_mc_small(const ape_streams* b) {
     const ape_model* m = b->model;
-    return !b->shared_l0 && b->mc && b->dropout_p > 0.0f && m->dims.num_layers > 1 && b->S <= 8 && m->cluster_ok && b->T <= 64 &&
+    return m->dims.model_kind == APE_MODEL_LSTM && !b->shared_l0 && b->mc && b->dropout_p > 0.0f && m->dims.num_layers > 1 && b->S <= 8 && m->cluster_ok && b->T <= 64 &&
            mc_small_fits(m, b->S, b->n_mc);
 }
 
@@ -1894,7 +1949,31 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         q.part = b->post_part; q.part_cnt = b->post_cnt;
         return q;
     };
-    if (b->shared_l0) {
+    if (m->dims.model_kind == APE_MODEL_FF) {
+        // DropoutFF: the newest row of every stream (T = 1: slot 0) -> trunk once per stream -> n_mc masked heads -> y_new in the row
+        // order the post-filter reads.  Masks keyed by (seed + frame counter; row = stream * n_mc + sample; hidden unit)
+        if (!b->ffhid) return fail(APE_ERR_NOT_READY, "streams_step: the bank lost its rings in a failed ape_streams_set_mc");
+        if (b->inj_masks && !b->mc)
+            return fail(APE_ERR_UNSUPPORTED, "streams_step: injected masks (test hook) on a DropoutFF bank without ape_streams_set_mc");
+        hipEvent_t ev_a, ev_z;
+        prof_pair(&ev_a, &ev_z);
+        if (int rc = ff_bank_forward(m, b->xring, (size_t)m->dims.input_size, 0, b->S * b->n_mc, b->n_mc, norm, b->inj_masks,
+                                     b->mc ? b->dropout_p : 0.0f, b->seed + b->mc_calls, b->ffhid, b->y_new, stream, ev_a, ev_z))
+            return rc;
+        ++b->mc_calls;
+    } else if (m->dims.model_kind == APE_MODEL_IMUPOSE) {
+        // ImuPoseLSTM: the rings in time order (cold-start pad included), then the forward a subset frame runs over its compact windows
+        // (x_ring = 0: the layer-split route above 512 windows applies) -- the same launches, hence the same bits
+        if (!b->xwin) return fail(APE_ERR_NOT_READY, "streams_step: the bank lost its rings in a failed ape_streams_set_mc");
+        hipError_t e = ape_launch_ring_windows(b->xring, b->xwin, b->S, b->T, m->dims.input_size, x_ring, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: window launch failed: %s", hipGetErrorString(e));
+        hipEvent_t ev_a, ev_z;
+        prof_pair(&ev_a, &ev_z);
+        if (ev_a) (void)hipEventRecord(ev_a, (hipStream_t)stream);
+        if (int rc = lstm_forward_impl(m, b->xwin, b->S, b->T, flags | diag_wt, nullptr, 0.0f, 0, b->y_new, stream, 0)) return rc;
+        if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
+        ++b->mc_calls;
+    } else if (b->shared_l0) {
         if (!m->has_weights) return fail(APE_ERR_NOT_READY, "streams_step: weights not loaded");
         if ((size_t)b->S * b->T > m->hseq_cap) return fail(APE_ERR_CAPACITY, "streams_step: the layer-0 sequence workspace is gone");
         const int H = m->dims.hidden_size, I = m->dims.input_size, O = m->dims.output_size;
@@ -1907,7 +1986,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         // members, every step's output -> [S,T,H] in the model's sequence workspace, as the batch-tile launch writes it
         auto launch_a_one_layer = [&]() -> hipError_t {
             ClusterParams c{};
-            c.x = b->xring; c.x_row_stride = (size_t)b->n_mc * b->T * I;
+            c.x = b->xring; c.x_row_stride = (size_t)bank_copies(b) * b->T * I;
             c.y = nullptr; c.hseq = m->hseq_ws;
             c.wcl[0] = m->wcl[0]; c.bias[0] = m->bias[0];
             c.w_out = m->w_out; c.b_out = m->b_out;
@@ -1937,7 +2016,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
             // launch A on the weight-stationary structure (lstm_upper32.hip, SEQ form): S streams in tiles of 32 on the clusters,
             // every step's output in the fragment order launch B's input builder reads
             XFragParams xq{};
-            xq.x = b->xring; xq.xfrag = b->xfrag0; xq.x_row_stride = (size_t)b->n_mc * b->T * I;
+            xq.x = b->xring; xq.xfrag = b->xfrag0; xq.x_row_stride = (size_t)bank_copies(b) * b->T * I;
             xq.xx_m = norm ? m->stats : nullptr; xq.xx_s = norm ? m->stats + I : nullptr;
             xq.S = b->S; xq.T = b->T; xq.I = I; xq.x_ring = x_ring;
             UpperParams u{};
@@ -1960,7 +2039,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         } else {
         // launch A: layer 0 alone over the S windows (first copy of every stream's ring), all steps -> [S,T,H]
         LstmParams a{};
-        a.x = b->xring; a.x_row_stride = (size_t)b->n_mc * b->T * I;
+        a.x = b->xring; a.x_row_stride = (size_t)bank_copies(b) * b->T * I;
         a.y = nullptr; a.hseq = m->hseq_ws;
         a.wpack[0] = m->wpack[0]; a.bias[0] = m->bias[0];
         a.w_out = m->w_out; a.b_out = m->b_out;
@@ -2142,7 +2221,7 @@ int ape_streams_frame_host(ape_streams_t* b, int32_t kind, const float* rows_hos
         McFrameParts fr{};
         fr.raw_rows = b->h_rows; fr.raw_width = width; fr.raw_kind = kind & ~APE_PARSE_BIG_ENDIAN; fr.raw_big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
         fr.cold = b->frames == 0 ? 1 : 0;
-        fr.ring_out = slot_out; fr.ring_stream_stride = (size_t)b->n_mc * b->T * I; fr.ring_rep_stride = slot_rep_stride; fr.ring_rep = slot_rep;
+        fr.ring_out = slot_out; fr.ring_stream_stride = (size_t)bank_copies(b) * b->T * I; fr.ring_rep_stride = slot_rep_stride; fr.ring_rep = slot_rep;
         ++b->frames;                                   // (what ape_streams_push_rows does behind its launch)
         if (int rc = streams_step_impl(b, flags | APE_FLAG_PACKED_MSG, b->h_out, nullptr, out_dtype, stream, b->h_status, &fr)) { --b->frames; return rc; }
     } else {
@@ -2170,7 +2249,7 @@ int ape_streams_frame_host(ape_streams_t* b, int32_t kind, const float* rows_hos
         // the kernels that need no co-residency -- into the same pinned rows.  (Single-launch frame: the builder workgroup may not
         // have run; its row goes into the ring by the feature builder's own kernel first -- the same slot, the same values.)
         if (one_launch) {
-            hipError_t e = ape_launch_parse_rows(b->h_rows, b->S, width, kind & ~APE_PARSE_BIG_ENDIAN, slot_out, APE_F32, I, (size_t)b->n_mc * b->T * I,
+            hipError_t e = ape_launch_parse_rows(b->h_rows, b->S, width, kind & ~APE_PARSE_BIG_ENDIAN, slot_out, APE_F32, I, (size_t)bank_copies(b) * b->T * I,
                                                  slot_rep, slot_rep_stride, (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0, (hipStream_t)stream);
             if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_host: feature builder launch failed: %s", hipGetErrorString(e));
         }
@@ -2276,8 +2355,13 @@ static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_
     ape_model* m = b->model;
     const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
     const bool packed = (flags & APE_FLAG_PACKED_MSG) != 0 && b->smooth * b->n_mc > 1;
-    const bool drop = b->mc && b->dropout_p > 0.0f && m->dims.num_layers > 1;
-    if (int rc = lstm_forward_impl(m, b->sub_x, K * b->n_mc, b->T, (norm ? APE_FLAG_NORMALIZE_INPUT : 0u) | (drop ? APE_FLAG_DROPOUT_PHILOX : 0u),
+    const bool drop = b->mc && b->dropout_p > 0.0f && m->dims.num_layers > 1 && m->dims.model_kind == APE_MODEL_LSTM;
+    if (m->dims.model_kind == APE_MODEL_FF) {
+        // (the compact "windows" of a DropoutFF bank are the K newest rows [K,I]; masks keyed by list position)
+        if (int rc = ff_bank_forward(m, b->sub_x, (size_t)m->dims.input_size, 0, K * b->n_mc, b->n_mc, norm, nullptr, b->mc ? b->dropout_p : 0.0f,
+                                     b->seed + mc_call, b->ffhid, b->sub_y, stream))
+            return rc;
+    } else if (int rc = lstm_forward_impl(m, b->sub_x, K * b->n_mc, b->T, (norm ? APE_FLAG_NORMALIZE_INPUT : 0u) | (drop ? APE_FLAG_DROPOUT_PHILOX : 0u),
                                    nullptr, drop ? b->dropout_p : 0.0f, b->seed + mc_call, b->sub_y, stream, 0))
         return rc;
     StreamPostParams q{};
@@ -2308,7 +2392,8 @@ int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_d
     if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG))
         return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: only NORMALIZE_INPUT and PACKED_MSG are accepted");
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: unknown dtype selector");
-    if (!b->xring || !b->yring) return fail(APE_ERR_NOT_READY, "streams_frame_subset: the bank lost its rings in a failed ape_streams_set_mc");
+    if (!b->xring || !b->yring || (m->dims.model_kind == APE_MODEL_FF && !b->ffhid))
+        return fail(APE_ERR_NOT_READY, "streams_frame_subset: the bank lost its rings in a failed ape_streams_set_mc");
     const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
     if (norm && !m->has_stats) return fail(APE_ERR_NOT_READY, "streams_frame_subset: NORMALIZE_INPUT without norm stats");
     if (!m->has_weights) return fail(APE_ERR_NOT_READY, "streams_frame_subset: weights not loaded");
@@ -2323,7 +2408,7 @@ int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_d
     const size_t R = (size_t)b->S * b->n_mc;
     if (b->sub_n_mc != b->n_mc || !b->sub_x) {
         subset_free(b);
-        HIP_TRY(hipMalloc((void**)&b->sub_x, R * b->T * I * sizeof(float)));
+        HIP_TRY(hipMalloc((void**)&b->sub_x, (size_t)b->S * bank_copies(b) * b->T * I * sizeof(float)));
         HIP_TRY(hipMalloc((void**)&b->sub_y, R * m->dims.output_size * sizeof(float)));
         HIP_TRY(hipMalloc((void**)&b->sub_desc, (size_t)b->S * sizeof(SubsetDesc)));
         b->sub_n_mc = b->n_mc;
@@ -2349,7 +2434,7 @@ int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_d
     b->sub_next = (k + 1) % APE_SUBSET_STAGES;
     SubsetRowsParams rp{};
     rp.rows = rows_dev; rp.desc = b->sub_desc; rp.xring = b->xring; rp.xw = b->sub_x;
-    rp.K = K; rp.width = width; rp.kind = kind & ~APE_PARSE_BIG_ENDIAN; rp.big_endian = big_endian; rp.T = b->T; rp.I = I; rp.n_mc = b->n_mc;
+    rp.K = K; rp.width = width; rp.kind = kind & ~APE_PARSE_BIG_ENDIAN; rp.big_endian = big_endian; rp.T = b->T; rp.I = I; rp.n_mc = bank_copies(b);
     hipError_t e = ape_launch_subset_rows(rp, st);
     if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset: row launch failed: %s", hipGetErrorString(e));
     // the rows are in the rings: the counters move on whatever the regressor does (a failed launch is reported, the rows stay pushed)
@@ -2400,9 +2485,32 @@ int ape_replay(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, c
 
 // bodies_host [R,9]: recording r's rows as a fresh estimator BUILT WITH recording r's bonemap returns them (estimator.py:57-68); NULL: the
 // model's body for every recording, on the kernels ape_replay always ran
+static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                       int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+                       void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream, const double* bodies_host,
+                       bool any_regressor);
+
 int ape_replay_bodies(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                       int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
                       void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream, const double* bodies_host) {
+    return replay_impl(m, kind, rows_dev, F, seg_starts_host, R, seq_len, smooth, n_mc, dropout_p, seed, flags, out_dev, out_dtype, y_dev,
+                       max_rows_per_launch, stream, bodies_host, false);
+}
+
+// ape_replay_bodies for every regressor the loader dispatches: DropoutLSTM handles take the path above unchanged;
+// DropoutFF: no windows at all -- the trunk over the frames' own rows, the n_mc masked heads (masks those of ONE pass over all F * n_mc
+// rows, whatever the chunking); ImuPoseLSTM: one row per frame whatever n_mc says (nn_models.py:246-251), no dropout
+int ape_replay_regressor(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                         int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+                         void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream, const double* bodies_host) {
+    return replay_impl(m, kind, rows_dev, F, seg_starts_host, R, seq_len, smooth, n_mc, dropout_p, seed, flags, out_dev, out_dtype, y_dev,
+                       max_rows_per_launch, stream, bodies_host, true);
+}
+
+static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                       int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+                       void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream, const double* bodies_host,
+                       bool any_regressor) {
     // the arguments on their own first (no device needed to refuse them)
     if (!rows_dev || !out_dev) return fail(APE_ERR_INVALID_ARG, "replay: NULL argument");
     int width, I;
@@ -2429,7 +2537,10 @@ int ape_replay_bodies(ape_model_t* m, int32_t kind, const float* rows_dev, int32
     if (!m) return fail(ape_device_count() == 0 ? APE_ERR_NO_DEVICE : APE_ERR_INVALID_ARG,
                         "replay: NULL model (no gfx950 device: there is no CPU fallback)");
     // ... then against the model
-    if (m->dims.model_kind != APE_MODEL_LSTM) return fail(APE_ERR_UNSUPPORTED, "replay: LSTM estimator models only (not FF / ImuPose)");
+    if (m->dims.model_kind != APE_MODEL_LSTM && !any_regressor)
+        return fail(APE_ERR_UNSUPPORTED, "replay: LSTM estimator models only (not FF / ImuPose: ape_replay_regressor serves those)");
+    const bool is_ff = m->dims.model_kind == APE_MODEL_FF, is_imu = m->dims.model_kind == APE_MODEL_IMUPOSE;
+    if (is_imu) { n_mc = 1; dropout_p = 0.0f; }            // the reference ignores the sample count and has no dropout mode
     if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "replay: model has no target layout");
     if (m->precision != APE_PRECISION_F32) return fail(APE_ERR_UNSUPPORTED, "replay: fp16 precision is set on the model (float32 only)");
     if (I != m->dims.input_size)
@@ -2445,7 +2556,7 @@ int ape_replay_bodies(ape_model_t* m, int32_t kind, const float* rows_dev, int32
     if (int rc = ape_model_recover(m)) return rc;
 
     const hipStream_t st = (hipStream_t)stream;
-    const int T = seq_len, O = m->dims.output_size, W = layout_est_width(m->dims.target_layout);
+    const int T = is_ff ? 1 : seq_len, O = m->dims.output_size, W = layout_est_width(m->dims.target_layout);   // (DropoutFF: the newest row alone counts)
     const int N = smooth * n_mc;
     const long long total = (long long)F * n_mc;
     const bool tail = (flags & APE_FLAG_PACKED_MSG) && N > 1;
@@ -2457,13 +2568,14 @@ int ape_replay_bodies(ape_model_t* m, int32_t kind, const float* rows_dev, int32
     if (rmax > (total + 15) / 16 * 16) rmax = (total + 15) / 16 * 16;
     const long long carry = N;                    // >= (smooth - 1) * n_mc rows of older frames + the newest frame's first n_mc - 1
     ApeDeviceScratch ws;
-    float *xx, *xw, *yws = nullptr;
+    float *xx, *xw = nullptr, *yws = nullptr, *ffhid = nullptr;
     int *starts_d, *seg_of;
     double* est[2];
     HIP_TRY(ws.alloc((void**)&xx, (size_t)F * I * sizeof(float)));
     HIP_TRY(ws.alloc((void**)&seg_of, (size_t)F * sizeof(int)));
     HIP_TRY(ws.alloc((void**)&starts_d, (size_t)R * sizeof(int)));
-    HIP_TRY(ws.alloc((void**)&xw, (size_t)rmax * T * I * sizeof(float)));
+    if (!is_ff) HIP_TRY(ws.alloc((void**)&xw, (size_t)rmax * T * I * sizeof(float)));
+    else HIP_TRY(ws.alloc((void**)&ffhid, (size_t)(rmax / n_mc + 2) * m->dims.hidden_size * sizeof(float)));
     if (!y_dev) HIP_TRY(ws.alloc((void**)&yws, (size_t)rmax * O * sizeof(float)));
     HIP_TRY(ws.alloc((void**)&est[0], (size_t)(carry + rmax) * W * sizeof(double)));
     HIP_TRY(ws.alloc((void**)&est[1], (size_t)(carry + rmax) * W * sizeof(double)));
@@ -2476,7 +2588,7 @@ int ape_replay_bodies(ape_model_t* m, int32_t kind, const float* rows_dev, int32
         HIP_TRY(hipMemcpyAsync(bodies_d, bodies_host, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, st));
     }
 
-    const bool drop = dropout_p > 0.0f && m->dims.num_layers > 1;
+    const bool drop = dropout_p > 0.0f && m->dims.num_layers > 1 && !is_ff;
     const uint32_t lflags = (norm ? APE_FLAG_NORMALIZE_INPUT : 0u) | (drop ? APE_FLAG_DROPOUT_PHILOX : 0u);
     auto pass = [&]() -> int {
         hipError_t e = ape_launch_parse_rows(rows_dev, F, width, kind & ~APE_PARSE_BIG_ENDIAN, xx, APE_F32, I, (size_t)I, 1, 0, big_endian, st);
@@ -2485,14 +2597,19 @@ int ape_replay_bodies(ape_model_t* m, int32_t kind, const float* rows_dev, int32
         long long prev_rows = 0;
         for (long long r0 = 0, c = 0; r0 < total; r0 += rmax, ++c) {
             const int rows = (int)(total - r0 < rmax ? total - r0 : rmax);
+            float* y = y_dev ? y_dev + (size_t)r0 * O : yws;
+            if (is_ff) {
+                if (int rc = ff_bank_forward(m, xx + (size_t)(r0 / n_mc) * I, (size_t)I, r0, rows, n_mc, norm, nullptr, dropout_p, seed, ffhid, y, stream))
+                    return rc;
+            } else {
             ReplayWindowParams wp{};
             wp.xx = xx; wp.seg_of = seg_of; wp.xw = xw; wp.r0 = r0; wp.R = rows; wp.T = T; wp.I = I; wp.n_mc = n_mc;
             e = ape_launch_replay_windows(wp, st);
             if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: window launch failed: %s", hipGetErrorString(e));
-            float* y = y_dev ? y_dev + (size_t)r0 * O : yws;
             if (int rc = lstm_forward_impl(m, xw, rows, T, lflags, nullptr, drop ? dropout_p : 0.0f, seed, y, stream, 0, nullptr, nullptr,
                                            nullptr, r0))
                 return rc;
+            }
             double* cur = est[c & 1];
             if (c > 0)
                 HIP_TRY(hipMemcpyAsync(cur, est[(c + 1) & 1] + (size_t)prev_rows * W, (size_t)carry * W * sizeof(double),

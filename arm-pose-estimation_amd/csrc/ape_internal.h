@@ -196,6 +196,20 @@ struct MlpParams {
     unsigned long long seed;
 };
 
+// Kernel arguments of the masked heads of a DropoutFF bank frame / replay (ape_ff_bank_head, ff_bank.hip): `rows` sample rows, global row
+// row_base + r = sample (row_base + r) % n_mc of stream / frame (row_base + r) / n_mc, whose hidden row is hidden[that - g_base].
+struct FfHeadParams {
+    const float* hidden;                // [groups,H] last hidden activation (the trunk, once per stream); row 0 = group g_base
+    const float* w_out;                 // [O,H]
+    const float* b_out;                 // [O]
+    const float* masks;                 // injected multipliers [all rows, H] indexed by the GLOBAL row (test hooks), or nullptr
+    float* y;                           // [rows,O] normalised NN targets; row 0 = global row row_base
+    long long row_base, g_base;
+    int rows, n_mc, H, O;
+    float dropout_p;                    // > 0 without masks: Philox draws keyed by `seed`
+    unsigned long long seed;
+};
+
 struct FkParams {
     const void* preds;   // [N,O] f32 or f64
     void* est;           // [N,W] f32 or f64
@@ -434,6 +448,10 @@ hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t st
 hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream, const double* bodies = nullptr,
                                  const int* rec_of = nullptr);
 hipError_t ape_launch_subset_rows(const SubsetRowsParams& p, hipStream_t stream);
+// DropoutFF / ImuPoseLSTM banks (ff_bank.hip): the n_mc masked heads over a trunk computed once per stream; the time-ordered copy of the
+// window rings [S][T][I] (step t in slot (t + x_ring) mod T)
+hipError_t ape_launch_ff_bank_head(const FfHeadParams& p, hipStream_t stream);
+hipError_t ape_launch_ring_windows(const float* xring, float* xw, int S, int T, int I, int x_ring, hipStream_t stream);
 // the bank's post-filter over a list: p.S = K entries, y_new / msg in list order, stack slot and cold flag of entry j from desc[j]
 // (bodies: as ape_launch_stream_post -- indexed by desc[j].stream)
 hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const SubsetDesc* desc, hipStream_t stream, const double* bodies = nullptr);

@@ -140,6 +140,10 @@ struct ape_streams {
     float* ypart = nullptr;      // [chunk rows][8][16] head partial sums
     float* xfrag0 = nullptr;     // [S / 32][T][4 KB] layer 0's input tiles, fragment order
     float* hfrag = nullptr;      // [S / 32][T][32 KB] layer 0's output sequence, fragment order (launch B's input builder reads it)
+    // DropoutFF / ImuPoseLSTM banks (ff_bank.hip).  A DropoutFF bank keeps T = 1 whatever seq_len it was created with: the
+    // reference's [:, -1, :] leaves the newest row as the only one that counts; both kinds keep ONE window per stream (xring [S,T,I])
+    float* ffhid = nullptr;      // DropoutFF: [S,H] the trunk's last hidden activation, once per stream and frame
+    float* xwin = nullptr;       // ImuPoseLSTM: [S,T,I] the windows of a lockstep frame in time order
     bool prof_on = false;        // ape_streams_profile: event pairs around the dominant kernel's launches
     int prof_n = 0;
     std::vector<hipEvent_t> prof_ev;

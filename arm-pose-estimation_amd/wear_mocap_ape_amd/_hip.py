@@ -137,6 +137,8 @@ SIGNATURES = {
 # the replays with one body per recording: every argument of the plain entry, then bodies_host [R,9] float64 (or NULL)
 for _name in ("ape_replay", "ape_fk_replay", "ape_kalman_replay"):
     SIGNATURES[_name + "_bodies"] = (C.c_int, SIGNATURES[_name][1] + [C.c_void_p])
+# ape_replay_bodies for every regressor kind the loader dispatches (DropoutFF, ImuPoseLSTM)
+SIGNATURES["ape_replay_regressor"] = SIGNATURES["ape_replay_bodies"]
 
 _lib = None
 

@@ -30,14 +30,16 @@ class _DeviceFrame:
     def __init__(self, model, kind: int, seq_len: int, smooth: int, n_mc: int, normalize: bool, seed: int = 0x5EED):
         import ctypes as C
         from wear_mocap_ape_amd import _hip
+        from wear_mocap_ape_amd.estimate.nn_models import effective_mc
         self._C, self._hip, self._lib = C, _hip, _hip.lib()
         self._model, self._kind = model, kind
         self._width = _hip.PARSE_SHAPES[kind][0]
+        n_mc = effective_mc(model, n_mc)         # (ImuPoseLSTM ignores the sample count: one row per frame)
         self._rows = smooth * n_mc
         self._flags = _hip.FLAG_NORMALIZE_INPUT if normalize else 0
         self._bank = C.c_void_p()
         _hip.check(self._lib.ape_streams_create(model.handle, 1, seq_len, smooth, C.byref(self._bank)), "ape_streams_create")
-        # monte_carlo_predictions switches the inter-layer dropout on whatever n is (nn_models.py:204), also for one sample
+        # monte_carlo_predictions switches the dropout on whatever n is (nn_models.py:204, :367), also for one sample
         _hip.check(self._lib.ape_streams_set_mc(self._bank, n_mc, float(model.dropout), int(seed) & (2 ** 64 - 1)),
                    "ape_streams_set_mc")
         self._row = np.empty((self._width,), dtype=np.float32)
@@ -324,7 +326,9 @@ class Estimator:
         tensor); ``starts``: the recordings' first rows (default ``[0]``: one recording).  Returns, on the device,
         what ``process_row`` returns for every row of a fresh estimator fed each recording in order (no row skipped):
         ``[F, 25 + 6N]`` with ``add_mc_samples`` and N = smooth x Monte-Carlo samples > 1, else ``[F, 25]``.  With
-        ``return_targets`` also the normalised NN targets float32 ``[F, n_mc, O]``.  The Monte-Carlo samples are those
+        ``return_targets`` also the normalised NN targets float32 ``[F, n_mc, O]``.  Over an ``ImuPoseLSTM`` the sample count is
+        ignored as in the reference (n_mc = 1 in every shape above); ``DropoutFF`` and ``ImuPoseLSTM`` models go through
+        ``ape_replay_regressor``.  The Monte-Carlo samples are those
         of one dropout forward keyed by ``seed`` over the repeated windows (``ape_replay``); ``max_rows_per_launch``
         bounds the sample rows of one regressor launch (0: the library's default) and with it the device workspace.
         ``bonemaps``: one entry per recording (bonemap-like objects, ``None`` for the defaults, or float64 ``[R, 9]`` values) --
@@ -338,8 +342,11 @@ class Estimator:
         width = _hip.PARSE_SHAPES[self._parse_kind][0]
         if out_dtype not in (torch.float32, torch.float64):
             raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
-        n_mc = int(n_mc)
+        from wear_mocap_ape_amd.estimate.nn_models import DropoutFF, ImuPoseLSTM, effective_mc
+        n_mc = effective_mc(model, n_mc)
         n_rows = self._smooth * n_mc
+        # (DropoutLSTM models keep the entry they always took)
+        entry = "ape_replay_regressor" if isinstance(model, (DropoutFF, ImuPoseLSTM)) else "ape_replay_bodies"
         dev = model.torch_device
         with torch.cuda.device(dev):
             rd = torch.as_tensor(rows, dtype=torch.float32).to(dev).contiguous()
@@ -354,13 +361,13 @@ class Estimator:
             kind = self._parse_kind | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             bodies = None if bonemaps is None else bodies_from(bonemaps, int(st.shape[0]), "process_recording bonemaps")
-            _hip.check(_hip.lib().ape_replay_bodies(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
+            _hip.check(getattr(_hip.lib(), entry)(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
                                                     int(st.shape[0]), self._sequence_len, self._smooth, n_mc, float(model.dropout),
                                                     int(seed) & (2 ** 64 - 1), flags, C.c_void_p(out.data_ptr()),
                                                     _hip.F64 if out_dtype == torch.float64 else _hip.F32,
                                                     C.c_void_p(y.data_ptr()) if y is not None else None,
                                                     int(max_rows_per_launch), stream,
-                                                    C.c_void_p(bodies.ctypes.data) if bodies is not None else None), "ape_replay_bodies")
+                                                    C.c_void_p(bodies.ctypes.data) if bodies is not None else None), entry)
             model._pending.clear()         # the call is blocking and checked the handle (its journal is empty)
         return (out, y) if return_targets else out
 

@@ -461,6 +461,15 @@ class ImuPoseLSTM(DropoutLSTM):
         return self
 
 
+def effective_mc(model, n_mc) -> int:
+    """Monte-Carlo rows ONE frame of ``model`` (an instance or a class) contributes to the smoothing stack when the estimator asks for
+    ``n_mc`` samples: ``n_mc`` for ``DropoutLSTM`` and ``DropoutFF`` (``x.repeat((n_samples, 1, 1))``, nn_models.py:206 / :368), 1 for
+    ``ImuPoseLSTM``, whose ``monte_carlo_predictions(n_samples, x)`` is ``self(x, None)`` and ignores the count (nn_models.py:246-251).
+    The one place the device frames, banks and replays take their stacked-row count ``smooth * effective_mc`` from."""
+    cls = model if isinstance(model, type) else type(model)
+    return 1 if issubclass(cls, ImuPoseLSTM) else max(1, int(n_mc))
+
+
 def load_deployed_model_from_hash(hash_str: str):
     """``hash`` -> ``(model, params)`` exactly like nn_models.py:373-415: reads
     ``<deploy>/nn/<hash>/results.json`` and ``checkpoint.pt`` (a ``(model_state, optimizer_state)``

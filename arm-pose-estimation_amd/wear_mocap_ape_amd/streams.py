@@ -93,10 +93,13 @@ class StreamBank:
     ``Estimator`` does per frame (estimator.py:93-137), so S estimator threads of the reference become three kernel
     launches per frame.  Rank-local: give each rank its ``shard_range`` of streams.
 
-    ``model`` is a HIP-backed ``DropoutLSTM`` (nn_models.py) with weights, norm stats and body set.
+    ``model`` is a HIP-backed ``DropoutLSTM``, ``DropoutFF`` or ``ImuPoseLSTM`` (nn_models.py) with weights, norm stats and body set.
     ``monte_carlo_samples=None`` runs the regressor once per stream with deterministic weights; an integer n runs
-    it n times per stream and frame with inter-layer dropout ``dropout`` (default: the model's) like
-    ``monte_carlo_predictions`` (nn_models.py:191-207), and the stack / tail hold ``smooth * n`` rows per stream."""
+    it n times per stream and frame with dropout ``dropout`` (default: the model's) like ``monte_carlo_predictions``
+    (nn_models.py:191-207; ``DropoutFF``: the dropout in front of the output layer, :351, the trunk once per stream), and the
+    stack / tail hold ``smooth * n`` rows per stream.  An ``ImuPoseLSTM`` ignores n like the reference (nn_models.py:246-251): one
+    row per stream and frame, ``smooth`` stacked rows (``nn_models.effective_mc``).  For a ``DropoutFF`` the window has no influence
+    (``[:, -1, :]`` of a row-wise MLP): ``seq_len`` is accepted and only the newest row of a stream counts."""
 
     def __init__(self, model, n_streams: int, seq_len: int, smooth: int = 1, normalize: bool = True,
                  dtype: torch.dtype = torch.float32, monte_carlo_samples=None, dropout=None, seed: int = 0x5EED):
@@ -115,9 +118,10 @@ class StreamBank:
         self._handle = handle
         self._n_mc = 1
         if monte_carlo_samples is not None:
-            self._n_mc = int(monte_carlo_samples)
+            from .estimate.nn_models import effective_mc
+            self._n_mc = effective_mc(model, monte_carlo_samples)
             p = float(model.dropout if dropout is None else dropout)
-            _hip.check(_hip.lib().ape_streams_set_mc(handle, self._n_mc, p, int(seed) & (2 ** 64 - 1)), "ape_streams_set_mc")
+            _hip.check(_hip.lib().ape_streams_set_mc(handle, int(monte_carlo_samples), p, int(seed) & (2 ** 64 - 1)), "ape_streams_set_mc")
         self._msg = torch.empty((n_streams, 25), dtype=dtype, device=self._device)
         self._tail = torch.empty((n_streams, smooth * self._n_mc, 6), dtype=dtype, device=self._device)
 

@@ -322,7 +322,7 @@ int ape_infer(ape_model_t* model, const float* x_dev, int32_t B, int32_t T, uint
  *                   O(F) for the features plus O(max_rows_per_launch), whatever F*n_mc
  * BLOCKING: returns after the model's health check; an aborted weight-stationary launch is run again on the kernels that
  * need no co-residency before the call returns.  Refused (non-zero, ape_last_error): bad kind / width, F < 1, bad starts,
- * fp16 precision on the model, APE_MODEL_FF / APE_MODEL_IMUPOSE models, a capturing stream. */
+ * fp16 precision on the model, APE_MODEL_FF / APE_MODEL_IMUPOSE models (ape_replay_regressor below serves those), a capturing stream. */
 int ape_replay(ape_model_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
                void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream);
@@ -379,6 +379,34 @@ int ape_replay_bodies(ape_model_t* model, int32_t kind, const float* rows_dev, i
                       int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
                       void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream,
                       const double* bodies_host);
+
+/* ---- DropoutFF and ImuPoseLSTM behind the frames, banks and replays (additive in ABI 7) -----------------------------
+ * ape_streams_create accepts APE_MODEL_FF and APE_MODEL_IMUPOSE handles with a target layout, and every ape_streams_* entry above then
+ * works on such a bank with the contracts stated there (a bank without ape_streams_set_mc is the eval bank, one row per stream).
+ * What the reference does with these models inside Estimator.add_xx_to_row_hist_and_make_prediction (estimator.py:93-120,
+ * watch_phone_pocket_nn.py:98-112) and what the banks reproduce:
+ *   APE_MODEL_FF       nn_models.py:340-370: the MLP runs on every row of the repeated window and [:, -1, :] keeps the newest row, so
+ *                      the window, seq_len and the cold-start padding have no influence: the bank keeps the newest feature row per
+ *                      stream.  The n_mc samples of a stream differ only by an independent Bernoulli(1-p) mask, scaled 1/(1-p), over
+ *                      the H outputs of the last hidden layer; dropout_p = 0 gives n_mc identical rows.  The trunk runs once per stream,
+ *                      the n_mc masked heads behind it (ff_bank.hip).  Masks: in-kernel Philox keyed by (seed + the bank's frame
+ *                      counter; row = stream * n_mc + sample; hidden unit) -- in a subset frame `stream` is the list position, like the
+ *                      LSTM banks' samples.  Not DropoutFF.forward's own random stream.  No cooperative kernel: such frames need no
+ *                      co-residency and ape_model_recover finds nothing to re-issue.
+ *   APE_MODEL_IMUPOSE  monte_carlo_predictions(n_samples, x) is self(x, None) (nn_models.py:246-251): no repeat, no dropout, the sample
+ *                      count is IGNORED.  ape_streams_set_mc(n_mc, ...) succeeds and leaves the bank at one row per stream and frame
+ *                      (N = smooth stacked rows; packed rows are [25 + 6*smooth]); it is still a cold start.  The window matters: T rows,
+ *                      padded with the newest on a cold start.  Lockstep and subset frames of one schedule give the same bits.  Frames
+ *                      ride the cooperative LSTM kernels and are journaled and re-issued like the LSTM banks' (ape_model_recover).
+ * ape_replay_regressor: ape_replay_bodies (same arguments, same semantics; bodies_host may be NULL) for every model kind.  APE_MODEL_LSTM
+ * handles are forwarded to ape_replay_bodies.  APE_MODEL_FF: seq_len is accepted and has no influence; the masks are those of ONE pass
+ * over all F * n_mc sample rows keyed by `seed`, independent of max_rows_per_launch.  APE_MODEL_IMUPOSE: the effective n_mc is 1 --
+ * out_dev rows are [25] or, packed with smooth > 1, [25 + 6*smooth]; y_dev is [F, 1, O].  ape_replay / ape_replay_bodies keep refusing
+ * non-LSTM handles.  Refusals otherwise as ape_replay (fp16 precision, no target layout, bad starts, a capturing stream). */
+int ape_replay_regressor(ape_model_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                         int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+                         void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream,
+                         const double* bodies_host);
 
 /* ---- the estimator without a regressor: WatchPhoneUarm (additive in ABI 7) -------------------------------------
  * Replaces estimate/watch_phone_uarm.py:10-108 behind Estimator (estimator.py:93-137): per frame the 38 features of
