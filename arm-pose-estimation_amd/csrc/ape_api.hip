@@ -1540,7 +1540,8 @@ static int bank_copies(const ape_streams* b) { return b->model->dims.model_kind 
 // g_base = row_base / n_mc.  The trunk once per group (ape_mlp_tile16 with hidden_out: f64 z-score, input layer, hidden layers) into
 // `hid` [groups,H], then the n_mc masked heads.  No cooperative kernel: nothing here waits for another workgroup.
 static int ff_bank_forward(ape_model* m, const float* x, size_t x_stride, long long row_base, int rows, int n_mc, bool norm, const float* masks,
-                           float dropout_p, uint64_t seed, float* hid, float* y, void* stream, hipEvent_t ev_a = nullptr, hipEvent_t ev_z = nullptr) {
+                           float dropout_p, uint64_t seed, float* hid, float* y, void* stream, hipEvent_t ev_a = nullptr, hipEvent_t ev_z = nullptr,
+                           long long philox_base = 0) {
     if (!m->has_weights) return fail(APE_ERR_NOT_READY, "ff bank: weights not loaded");
     const int H = m->dims.hidden_size, L = m->dims.num_layers, I = m->dims.input_size;
     const long long g_base = row_base / n_mc;
@@ -1560,7 +1561,7 @@ static int ff_bank_forward(ape_model* m, const float* x, size_t x_stride, long l
     FfHeadParams hp{};
     hp.hidden = hid; hp.w_out = m->w_out; hp.b_out = m->b_out; hp.masks = masks; hp.y = y;
     hp.row_base = row_base; hp.g_base = g_base; hp.rows = rows; hp.n_mc = n_mc; hp.H = H; hp.O = m->dims.output_size;
-    hp.dropout_p = dropout_p; hp.seed = seed;
+    hp.dropout_p = dropout_p; hp.seed = seed; hp.philox_base = philox_base;
     m->last_kernel = "ape_ff_bank_head";
     e = ape_launch_ff_bank_head(hp, (hipStream_t)stream);
     if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
@@ -1798,6 +1799,7 @@ int ape_streams_destroy(ape_streams_t* b) {
     ape_body_table_free(b->bodies);
     for (auto ev : b->sub_ev) if (ev) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
     if (b->sub_stage) (void)hipHostFree(b->sub_stage);
+    if (b->state_desc) (void)hipFree(b->state_desc);
     if (ape_model* m = b->model) {      // pending steps of this bank can no longer be re-issued
         int k = 0;
         for (int i = 0; i < m->journal_n; ++i) {
@@ -2333,6 +2335,14 @@ static int subset_check_list(const ape_streams* b, const int32_t* streams_host, 
     return APE_OK;
 }
 
+// the pinned descriptor ring of the subset frames and the state hand-over, on first use
+static int subset_stage_alloc(ape_streams* b) {
+    if (b->sub_stage) return APE_OK;
+    HIP_TRY(hipHostMalloc((void**)&b->sub_stage, (size_t)APE_SUBSET_STAGES * b->S * sizeof(SubsetDesc), hipHostMallocDefault));
+    for (int i = 0; i < APE_SUBSET_STAGES; ++i) HIP_TRY(hipEventCreateWithFlags(&b->sub_ev[i], hipEventDisableTiming));
+    return APE_OK;
+}
+
 // the first subset call: per-stream counters seeded from the lockstep ones, so that a lockstep history carries on
 static void subset_enter(ape_streams* b) {
     if (b->per_stream) return;
@@ -2413,10 +2423,7 @@ int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_d
         HIP_TRY(hipMalloc((void**)&b->sub_desc, (size_t)b->S * sizeof(SubsetDesc)));
         b->sub_n_mc = b->n_mc;
     }
-    if (!b->sub_stage) {
-        HIP_TRY(hipHostMalloc((void**)&b->sub_stage, (size_t)APE_SUBSET_STAGES * b->S * sizeof(SubsetDesc), hipHostMallocDefault));
-        for (int i = 0; i < APE_SUBSET_STAGES; ++i) HIP_TRY(hipEventCreateWithFlags(&b->sub_ev[i], hipEventDisableTiming));
-    }
+    if (int rc = subset_stage_alloc(b)) return rc;
     subset_enter(b);
     // the descriptors into the next pinned slot -- once the copy that last read it has completed (frames go back to back, no host sync)
     const int k = b->sub_next;
@@ -2456,6 +2463,112 @@ int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_d
     return APE_OK;
 }
 
+// ---- stream state hand-over: the canonical record of a stream, out of and into the rings -------------------------
+// Slots and warm bits come from the host counters alone.  The descriptors travel through the subset frames' pinned ring into a device
+// buffer of their own (sub_desc still belongs to the newest subset frame, which ape_model_recover may re-issue).
+
+static void state_desc_of(const ape_streams* b, ape_stream_state_desc_t* d) {
+    d->version = APE_STATE_VERSION;
+    d->T = b->T; d->I = b->model->dims.input_size; d->smooth = b->smooth; d->n_mc = b->n_mc; d->O = b->model->dims.output_size;
+    d->words_per_stream = (d->T * d->I + d->smooth * d->n_mc * d->O + 3) & ~3;
+}
+
+int ape_streams_state_desc(ape_streams_t* b, ape_stream_state_desc_t* out) {
+    if (!b || !out) return fail(APE_ERR_INVALID_ARG, "streams_state_desc: NULL argument");
+    state_desc_of(b, out);
+    return APE_OK;
+}
+
+// the K descriptors `h` (next pinned slot, already filled by `fill`) to the device, then one launch
+extern "C++" template <typename Fill>
+static int state_launch(ape_streams* b, const char* what, int K, float* state, hipStream_t st, bool import, Fill fill) {
+    if (!b->state_desc) HIP_TRY(hipMalloc((void**)&b->state_desc, (size_t)b->S * sizeof(StateDesc)));
+    if (int rc = subset_stage_alloc(b)) return rc;
+    static_assert(sizeof(StateDesc) <= sizeof(SubsetDesc), "a pinned slot holds S descriptors of either kind");
+    const int k = b->sub_next;
+    HIP_TRY(hipEventSynchronize(b->sub_ev[k]));          // (the copy that read this slot APE_SUBSET_STAGES calls ago)
+    StateDesc* h = reinterpret_cast<StateDesc*>(b->sub_stage + (size_t)k * b->S);
+    for (int j = 0; j < K; ++j) fill(j, h[j]);
+    HIP_TRY(hipMemcpyAsync(b->state_desc, h, (size_t)K * sizeof(StateDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(b->sub_ev[k], st));
+    b->sub_next = (k + 1) % APE_SUBSET_STAGES;
+    ape_stream_state_desc_t d;
+    state_desc_of(b, &d);
+    StateParams p{};
+    p.xring = b->xring; p.yring = b->yring; p.state = state; p.desc = b->state_desc;
+    p.x_stream_stride = (size_t)bank_copies(b) * d.T * d.I;
+    p.K = K; p.T = d.T; p.I = d.I; p.smooth = d.smooth; p.MO = d.n_mc * d.O; p.words = d.words_per_stream;
+    const hipError_t e = import ? ape_launch_state_import(p, st) : ape_launch_state_export(p, st);
+    if (e != hipSuccess) return fail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+    return APE_OK;
+}
+
+static int state_check_call(ape_streams* b, const int32_t* streams_host, int32_t K, const void* state_dev, const void* warm_host, void* stream,
+                            const char* what) {
+    if (!b || !streams_host || !state_dev || !warm_host) return fail(APE_ERR_INVALID_ARG, "%s: NULL argument", what);
+    if (int rc = subset_check_list(b, streams_host, K, what)) return rc;
+    if (((uintptr_t)state_dev & 15u) != 0) return fail(APE_ERR_INVALID_ARG, "%s: state_dev must be 16-byte aligned", what);
+    if (!b->xring || !b->yring) return fail(APE_ERR_NOT_READY, "%s: the bank lost its rings in a failed ape_streams_set_mc", what);
+    HIP_TRY(hipSetDevice(b->model->dims.device));
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "%s: the stream is capturing (the descriptors are staged per call)", what);
+    return APE_OK;
+}
+
+int ape_streams_export(ape_streams_t* b, const int32_t* streams_host, int32_t K, void* state_dev, uint8_t* warm_host, void* stream) {
+    if (int rc = state_check_call(b, streams_host, K, state_dev, warm_host, stream, "streams_export")) return rc;
+    if (K == 0) return APE_OK;
+    // read-only: a lockstep bank stays in lockstep mode, its streams share the global counters
+    auto fill = [&](int j, StateDesc& d) {
+        const int s = streams_host[j];
+        const long long f = b->per_stream ? b->s_frames[s] : b->frames, p = b->per_stream ? b->s_steps[s] : b->steps;
+        // the newest row sits in slot (f - 1) mod T, so the oldest of the T rows in slot f mod T (all T slots are filled from the first row on)
+        d.stream = s; d.wslot = (int)(f % b->T); d.sslot = (int)(p % b->smooth);
+        d.warm = (f > 0 ? APE_STATE_WINDOW_WARM : 0) | (f > 0 && p > 0 ? APE_STATE_STACK_WARM : 0);
+        warm_host[j] = (uint8_t)d.warm;
+    };
+    return state_launch(b, "streams_export", K, (float*)state_dev, (hipStream_t)stream, false, fill);
+}
+
+int ape_streams_import(ape_streams_t* b, const ape_stream_state_desc_t* desc, const int32_t* streams_host, int32_t K,
+                       const void* state_dev, const uint8_t* warm_host, void* stream) {
+    if (!desc) return fail(APE_ERR_INVALID_ARG, "streams_import: NULL argument");
+    if (int rc = state_check_call(b, streams_host, K, state_dev, warm_host, stream, "streams_import")) return rc;
+    ape_stream_state_desc_t own;
+    state_desc_of(b, &own);
+    if (desc->version != own.version || desc->T != own.T || desc->I != own.I || desc->smooth != own.smooth || desc->n_mc != own.n_mc ||
+        desc->O != own.O || desc->words_per_stream != own.words_per_stream)
+        return fail(APE_ERR_INVALID_ARG, "streams_import: the records are {v%d T=%d I=%d smooth=%d n_mc=%d O=%d words=%d}, the bank's {v%d T=%d I=%d smooth=%d n_mc=%d O=%d words=%d}",
+                    desc->version, desc->T, desc->I, desc->smooth, desc->n_mc, desc->O, desc->words_per_stream, own.version, own.T, own.I,
+                    own.smooth, own.n_mc, own.O, own.words_per_stream);
+    if (K == 0) return APE_OK;
+    // time order = slot order: row t into slot t, the counters at T / smooth -- the next row lands on slot 0, the oldest
+    auto fill = [&](int j, StateDesc& d) {
+        const int w = warm_host[j] & APE_STATE_WINDOW_WARM;
+        d.stream = streams_host[j]; d.wslot = 0; d.sslot = 0;
+        d.warm = w ? (warm_host[j] & (APE_STATE_WINDOW_WARM | APE_STATE_STACK_WARM)) : 0;
+    };
+    if (int rc = state_launch(b, "streams_import", K, (float*)const_cast<void*>(state_dev), (hipStream_t)stream, true, fill)) return rc;
+    subset_enter(b);
+    for (int j = 0; j < K; ++j) {
+        const int s = streams_host[j];
+        const bool w = (warm_host[j] & APE_STATE_WINDOW_WARM) != 0, p = w && (warm_host[j] & APE_STATE_STACK_WARM) != 0;
+        b->s_frames[s] = w ? b->T : 0;
+        b->s_steps[s] = p ? b->smooth : 0;
+    }
+    // the rings changed behind the bank's pending frame: like a newer frame, the import takes it off the journal
+    ape_model* m = b->model;
+    int n = 0;
+    for (int i = 0; i < m->journal_n; ++i) {
+        const ApeJournalEntry& o = m->journal[i];
+        if ((o.kind == ApeJournalEntry::SUBSET || o.kind == ApeJournalEntry::STEP) && o.bank == b) { m->journal_overflow = true; continue; }
+        m->journal[n++] = o;
+    }
+    m->journal_n = n;
+    return APE_OK;
+}
+
 // ---- offline replay: every frame of one or more recordings in one call --------------------------------------
 // Chunks of sample rows [r0, r0 + R): windows (replay.hip) -> regressor (lstm_forward_impl with the chunk's global row base, so that the
 // Philox masks are those of ONE call over all F * n_mc rows) -> FK with de-normalisation into f64 est rows -> the messages of every frame
@@ -2483,12 +2596,17 @@ int ape_replay(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, c
                              max_rows_per_launch, stream, nullptr);
 }
 
+// ape_replay_resume's extra arguments; nullptr for the entries that start cold and keep no state
+struct ApeReplayResume {
+    const void* state_in; const uint8_t* warm_in; void* state_out; uint8_t* warm_out; uint64_t sample_row_base;
+};
+
 // bodies_host [R,9]: recording r's rows as a fresh estimator BUILT WITH recording r's bonemap returns them (estimator.py:57-68); NULL: the
 // model's body for every recording, on the kernels ape_replay always ran
 static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                        int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
                        void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream, const double* bodies_host,
-                       bool any_regressor);
+                       bool any_regressor, const ApeReplayResume* rs = nullptr);
 
 int ape_replay_bodies(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                       int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
@@ -2510,7 +2628,7 @@ int ape_replay_regressor(ape_model_t* m, int32_t kind, const float* rows_dev, in
 static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                        int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
                        void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream, const double* bodies_host,
-                       bool any_regressor) {
+                       bool any_regressor, const ApeReplayResume* rs) {
     // the arguments on their own first (no device needed to refuse them)
     if (!rows_dev || !out_dev) return fail(APE_ERR_INVALID_ARG, "replay: NULL argument");
     int width, I;
@@ -2534,6 +2652,14 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "replay: unknown dtype selector");
     if (max_rows_per_launch < 0 || (max_rows_per_launch > 0 && max_rows_per_launch < 16))
         return fail(APE_ERR_INVALID_ARG, "replay: max_rows_per_launch=%d (0 = default, else >= 16)", max_rows_per_launch);
+    const bool carry_in = rs && rs->state_in, keep_out = rs && rs->state_out;
+    const long long pbase = rs ? (long long)rs->sample_row_base : 0;
+    if (carry_in && !rs->warm_in) return fail(APE_ERR_INVALID_ARG, "replay_resume: state_in without warm_in");
+    if (keep_out && !rs->warm_out) return fail(APE_ERR_INVALID_ARG, "replay_resume: state_out without warm_out");
+    if (rs && (((uintptr_t)rs->state_in | (uintptr_t)rs->state_out) & 15u) != 0)
+        return fail(APE_ERR_INVALID_ARG, "replay_resume: state buffers must be 16-byte aligned");
+    if (pbase < 0 || pbase + (long long)F * n_mc >= (1ll << 31))
+        return fail(APE_ERR_INVALID_ARG, "replay_resume: sample_row_base %lld (base + F*n_mc < 2^31)", pbase);
     if (!m) return fail(ape_device_count() == 0 ? APE_ERR_NO_DEVICE : APE_ERR_INVALID_ARG,
                         "replay: NULL model (no gfx950 device: there is no CPU fallback)");
     // ... then against the model
@@ -2548,6 +2674,9 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
     if (!m->has_weights) return fail(APE_ERR_NOT_READY, "replay: weights not loaded");
     const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
     if (norm && !m->has_stats) return fail(APE_ERR_NOT_READY, "replay: NORMALIZE_INPUT without norm stats");
+    // (the LSTM kernels draw their masks per group of 4 rows; without dropout the base is not read)
+    if (dropout_p > 0.0f && m->dims.num_layers > 1 && !is_ff && pbase % 4 != 0)
+        return fail(APE_ERR_INVALID_ARG, "replay_resume: sample_row_base %lld must be a multiple of 4 with dropout on", pbase);
     HIP_TRY(hipSetDevice(m->dims.device));
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
@@ -2588,26 +2717,63 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
         HIP_TRY(hipMemcpyAsync(bodies_d, bodies_host, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, st));
     }
 
+    // resumable replay: the carried-in records' stacks as est rows (once per call), the whole call's targets for the records going out
+    const int x_words = T * I, stack_words = smooth * n_mc * O, words = (x_words + stack_words + 3) & ~3;
+    ReplayCarryParams cp{};
+    float* y_in = nullptr;
+    int* rec_carry = nullptr;
+    unsigned char* warm_d = nullptr;
+    std::vector<unsigned char> warm_h;
+    std::vector<int> rec_carry_h;
+    if (carry_in || keep_out) {
+        if (!rec_of) HIP_TRY(ws.alloc((void**)&rec_of, (size_t)F * sizeof(int)));
+        if (keep_out && !y_dev) { HIP_TRY(ws.alloc((void**)&y_dev, (size_t)total * O * sizeof(float))); yws = nullptr; }
+    }
+    if (carry_in) {
+        double* est_in;
+        HIP_TRY(ws.alloc((void**)&est_in, (size_t)R * N * W * sizeof(double)));
+        HIP_TRY(ws.alloc((void**)&y_in, (size_t)R * stack_words * sizeof(float)));
+        HIP_TRY(ws.alloc((void**)&warm_d, (size_t)R));
+        HIP_TRY(ws.alloc((void**)&rec_carry, (size_t)R * smooth * sizeof(int)));
+        warm_h.resize((size_t)R);
+        for (int r = 0; r < R; ++r)       // (a stack without a window does not exist: as ape_streams_import)
+            warm_h[r] = (rs->warm_in[r] & APE_STATE_WINDOW_WARM) ? (rs->warm_in[r] & (APE_STATE_WINDOW_WARM | APE_STATE_STACK_WARM)) : 0;
+        rec_carry_h.resize((size_t)R * smooth);
+        for (int r = 0; r < R; ++r) for (int j = 0; j < smooth; ++j) rec_carry_h[(size_t)r * smooth + j] = r;
+        HIP_TRY(hipMemcpyAsync(warm_d, warm_h.data(), (size_t)R, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(rec_carry, rec_carry_h.data(), (size_t)R * smooth * sizeof(int), hipMemcpyHostToDevice, st));
+        cp.state_in = (const float*)rs->state_in; cp.est_in = est_in; cp.rec_of = rec_of; cp.warm = warm_d; cp.words = words;
+    }
+    const ReplayCarryParams* cin = carry_in ? &cp : nullptr;
+
     const bool drop = dropout_p > 0.0f && m->dims.num_layers > 1 && !is_ff;
     const uint32_t lflags = (norm ? APE_FLAG_NORMALIZE_INPUT : 0u) | (drop ? APE_FLAG_DROPOUT_PHILOX : 0u);
     auto pass = [&]() -> int {
         hipError_t e = ape_launch_parse_rows(rows_dev, F, width, kind & ~APE_PARSE_BIG_ENDIAN, xx, APE_F32, I, (size_t)I, 1, 0, big_endian, st);
         if (e == hipSuccess) e = ape_launch_replay_segments(starts_d, R, F, seg_of, st, rec_of);
         if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: feature launch failed: %s", hipGetErrorString(e));
+        if (cin) {                        // the carried stacks through the same de-normalisation and FK as fresh rows, once
+            e = ape_launch_replay_carry_rows(cp.state_in, R, words, x_words, stack_words, y_in, st);
+            if (e != hipSuccess) return fail(APE_ERR_HIP, "replay_resume: carry launch failed: %s", hipGetErrorString(e));
+            const FkBodyRows fc{bodies_d, rec_carry, 0, n_mc};
+            if (int rc = fk_impl(m, y_in, APE_F32, R * N, norm ? 1 : 0, const_cast<double*>(cp.est_in), APE_F64, stream, bodies_d ? &fc : nullptr))
+                return rc;
+        }
         long long prev_rows = 0;
         for (long long r0 = 0, c = 0; r0 < total; r0 += rmax, ++c) {
             const int rows = (int)(total - r0 < rmax ? total - r0 : rmax);
             float* y = y_dev ? y_dev + (size_t)r0 * O : yws;
             if (is_ff) {
-                if (int rc = ff_bank_forward(m, xx + (size_t)(r0 / n_mc) * I, (size_t)I, r0, rows, n_mc, norm, nullptr, dropout_p, seed, ffhid, y, stream))
+                if (int rc = ff_bank_forward(m, xx + (size_t)(r0 / n_mc) * I, (size_t)I, r0, rows, n_mc, norm, nullptr, dropout_p, seed, ffhid, y, stream,
+                                             nullptr, nullptr, pbase))
                     return rc;
             } else {
             ReplayWindowParams wp{};
             wp.xx = xx; wp.seg_of = seg_of; wp.xw = xw; wp.r0 = r0; wp.R = rows; wp.T = T; wp.I = I; wp.n_mc = n_mc;
-            e = ape_launch_replay_windows(wp, st);
+            e = ape_launch_replay_windows(wp, st, cin);
             if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: window launch failed: %s", hipGetErrorString(e));
             if (int rc = lstm_forward_impl(m, xw, rows, T, lflags, nullptr, drop ? dropout_p : 0.0f, seed, y, stream, 0, nullptr, nullptr,
-                                           nullptr, r0))
+                                           nullptr, r0 + pbase))
                 return rc;
             }
             double* cur = est[c & 1];
@@ -2621,9 +2787,17 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
             mp.f_lo = r0 / n_mc; mp.f_hi = (r0 + rows) / n_mc;
             memcpy(mp.body, m->body, sizeof(mp.body));
             mp.W = W; mp.layout = m->dims.target_layout; mp.smooth = smooth; mp.n_mc = n_mc; mp.out_dtype = out_dtype;
-            e = ape_launch_replay_msg(mp, tail, st, bodies_d, rec_of);
+            e = ape_launch_replay_msg(mp, tail, st, bodies_d, bodies_d ? rec_of : nullptr, cin);
             if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: message launch failed: %s", hipGetErrorString(e));
             prev_rows = rows;
+        }
+        if (keep_out) {
+            ReplayStateOutParams sp{};
+            sp.xx = xx; sp.y = y_dev; sp.starts = starts_d; sp.state_in = cin ? cp.state_in : nullptr; sp.warm = cin ? cp.warm : nullptr;
+            sp.state_out = (float*)rs->state_out;
+            sp.R = R; sp.F = F; sp.T = T; sp.I = I; sp.smooth = smooth; sp.n_mc = n_mc; sp.O = O; sp.words = words;
+            e = ape_launch_replay_state_out(sp, st);
+            if (e != hipSuccess) return fail(APE_ERR_HIP, "replay_resume: state launch failed: %s", hipGetErrorString(e));
         }
         return APE_OK;
     };
@@ -2641,7 +2815,19 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
         m->stats_counts.reissued_calls += 1;
         rc = check_and_reset(m);
     }
+    if (rc == APE_OK && keep_out)
+        for (int r = 0; r < R; ++r) rs->warm_out[r] = (uint8_t)(APE_STATE_WINDOW_WARM | APE_STATE_STACK_WARM);   // every recording has a frame
     return rc;
+}
+
+int ape_replay_resume(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                      int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+                      void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream, const double* bodies_host,
+                      const void* state_in_dev, const uint8_t* warm_in_host, void* state_out_dev, uint8_t* warm_out_host,
+                      uint64_t sample_row_base) {
+    const ApeReplayResume rs{state_in_dev, warm_in_host, state_out_dev, warm_out_host, sample_row_base};
+    return replay_impl(m, kind, rows_dev, F, seg_starts_host, R, seq_len, smooth, n_mc, dropout_p, seed, flags, out_dev, out_dtype, y_dev,
+                       max_rows_per_launch, stream, bodies_host, true, &rs);
 }
 
 // one journaled call again, on the kernels that need no co-residency (m->replaying is set)

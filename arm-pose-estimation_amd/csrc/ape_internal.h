@@ -208,6 +208,7 @@ struct FfHeadParams {
     int rows, n_mc, H, O;
     float dropout_p;                    // > 0 without masks: Philox draws keyed by `seed`
     unsigned long long seed;
+    long long philox_base;              // added to the global row in the Philox counter only (ape_replay_resume's sample_row_base; else 0)
 };
 
 struct FkParams {
@@ -279,6 +280,26 @@ struct ReplayMsgParams {
     int W, layout, smooth, n_mc, out_dtype;
 };
 
+// Resumable replay (ape_replay_resume): what the CARRY instantiations of the replay kernels read where a window or a stack
+// reaches back before its recording's first frame of this call -- the canonical records the recordings came in with
+struct ReplayCarryParams {
+    const float* state_in;        // [R][words] canonical records
+    const double* est_in;         // [R][smooth][n_mc][W] the carried stacks de-normalised and through FK, once per call
+    const int* rec_of;            // [F] index of each frame's recording
+    const unsigned char* warm;    // [R] APE_STATE_WINDOW_WARM | APE_STATE_STACK_WARM (a clear bit: that part starts cold, as without carry)
+    int words;
+};
+// the recordings' final windows and stacks as canonical records (ape_replay_state_out_kernel)
+struct ReplayStateOutParams {
+    const float* xx;              // [F,I]
+    const float* y;               // [F*n_mc,O] normalised NN targets of the whole call
+    const int* starts;            // [R]
+    const float* state_in;        // [R][words] or nullptr
+    const unsigned char* warm;    // [R] or nullptr
+    float* state_out;             // [R][words]
+    int R, F, T, I, smooth, n_mc, O, words;
+};
+
 // Subset frames of the stream bank (streams_subset.hip, ape_streams_frame_subset): one descriptor per listed stream, built on the host
 struct SubsetDesc {
     int stream;          // the bank's stream index
@@ -293,6 +314,23 @@ struct SubsetRowsParams {
     float* xring;        // the bank's [S, n_mc, T, I] window rings: only copy 0 of a stream is read and written
     float* xw;           // [K * n_mc, T, I] compact windows, time-ordered, list order, each window n_mc times
     int K, width, kind, big_endian, T, I, n_mc;
+};
+
+// Stream state hand-over (stream_state.hip, ape_streams_export / ape_streams_import): one descriptor per listed stream,
+// built on the host from the stream's counters
+struct StateDesc {
+    int stream;          // the bank's stream index
+    int wslot;           // window-ring slot of the stream's OLDEST row (rows since the cold start, mod T)
+    int sslot;           // smoothing-stack slot of the stream's OLDEST prediction (predictions since the cold start, mod smooth)
+    int warm;            // APE_STATE_WINDOW_WARM | APE_STATE_STACK_WARM: a cold part is exported as zeros and not imported
+};
+struct StateParams {
+    float* xring;        // the bank's [S, copies, T, I] window rings: copy 0 of a stream is read / written
+    float* yring;        // [S, smooth, n_mc, O]
+    float* state;        // [K, words] canonical records, 16-byte aligned
+    const StateDesc* desc;
+    size_t x_stream_stride;   // floats between the rings of consecutive streams (copies * T * I)
+    int K, T, I, smooth, MO /* n_mc * O */, words;
 };
 
 // Kernel arguments of the Monte-Carlo latency kernel (lstm_mc_small.hip): n_streams windows x n_mc dropout samples, dealt over the
@@ -443,11 +481,18 @@ hipError_t ape_launch_fk(const FkParams& p, int preds_dtype, int est_dtype, hipS
 hipError_t ape_launch_msg_reduce(const MsgParams& p, hipStream_t stream);
 // rec_of (optional): [F] index of each frame's recording, for the replays with one body per recording
 hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, int* seg_of, hipStream_t stream, int* rec_of = nullptr);
-hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t stream);
+// carry: nullptr (every recording starts cold: the instantiations ape_replay always ran) or the carried-in state
+hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t stream, const ReplayCarryParams* carry = nullptr);
 // bodies / rec_of: nullptr (p.body for every frame) or [R,9] values and [F] recording indices
 hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream, const double* bodies = nullptr,
-                                 const int* rec_of = nullptr);
+                                 const int* rec_of = nullptr, const ReplayCarryParams* carry = nullptr);
+// the stacks of R records -> contiguous rows [R * smooth * n_mc, O] (the input of the carried rows' FK launch)
+hipError_t ape_launch_replay_carry_rows(const float* state_in, int R, int words, int x_words, int stack_words, float* y_in, hipStream_t stream);
+hipError_t ape_launch_replay_state_out(const ReplayStateOutParams& p, hipStream_t stream);
 hipError_t ape_launch_subset_rows(const SubsetRowsParams& p, hipStream_t stream);
+// ring order <-> the canonical time-ordered records of the listed streams, one launch each (stream_state.hip)
+hipError_t ape_launch_state_export(const StateParams& p, hipStream_t stream);
+hipError_t ape_launch_state_import(const StateParams& p, hipStream_t stream);
 // DropoutFF / ImuPoseLSTM banks (ff_bank.hip): the n_mc masked heads over a trunk computed once per stream; the time-ordered copy of the
 // window rings [S][T][I] (step t in slot (t + x_ring) mod T)
 hipError_t ape_launch_ff_bank_head(const FfHeadParams& p, hipStream_t stream);

@@ -172,6 +172,9 @@ struct ape_streams {
     SubsetDesc* sub_stage = nullptr;  // [APE_SUBSET_STAGES][S]
     hipEvent_t sub_ev[APE_SUBSET_STAGES] = {};
     int sub_next = 0;
+    // state hand-over (ape_streams_export / import): descriptors of their own on the device -- sub_desc belongs to the
+    // newest subset frame, which ape_model_recover may still re-issue; staged through the pinned ring above
+    StateDesc* state_desc = nullptr;  // [S]
     // per-stream body measurements (ape_streams_set_bodies): off until the first call -- the frames then read model->body
     ApeBodyTable bodies;         // [S,9] on the device
 };

@@ -59,7 +59,8 @@ __global__ __launch_bounds__(256) void ape_ff_bank_head(const FfHeadParams p) {
             a = a * mk;
         } else if (philox) {
             uint32_t rnd[4];
-            philox4x32((uint32_t)grow, (uint32_t)((unsigned long long)grow >> 32), (uint32_t)(k0 >> 2), 0xFEu, (uint32_t)p.seed,
+            const unsigned long long prow = (unsigned long long)(grow + p.philox_base);
+            philox4x32((uint32_t)prow, (uint32_t)(prow >> 32), (uint32_t)(k0 >> 2), 0xFEu, (uint32_t)p.seed,
                        (uint32_t)(p.seed >> 32), rnd);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {

@@ -156,6 +156,31 @@ __global__ __launch_bounds__(FK_BLOCK) void ape_fk_replay_msg_kernel(const FkRep
     for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
 }
 
+// State hand-over: the stacks of K listed streams between the ring and the canonical records [K][smooth][8] f64, oldest
+// row first.  One thread per 16 bytes (a pair of doubles) of a record: record row i lives in ring slot (desc.pos + i) mod smooth, desc.pos
+// = the slot of the stream's oldest row; desc.cold: the stream has no stack -- zeros out, nothing in.
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+template <bool IMPORT>
+__global__ __launch_bounds__(FK_BLOCK) void ape_fk_state_kernel(double* __restrict__ ring, double* __restrict__ state,
+                                                                const FkDesc* __restrict__ desc, const int K, const int smooth) {
+    const int units = smooth * 4;
+    const long long idx = (long long)blockIdx.x * FK_BLOCK + threadIdx.x;
+    if (idx >= (long long)K * units) return;
+    const int j = (int)(idx / units), u = (int)(idx - (long long)j * units);
+    const FkDesc d = desc[j];
+    const int i = u >> 2, c = (u & 3) * 2;
+    int slot = d.pos + i;
+    if (slot >= smooth) slot -= smooth;
+    f64x2* r = reinterpret_cast<f64x2*>(ring + ((size_t)d.stream * smooth + slot) * 8 + c);
+    f64x2* s = reinterpret_cast<f64x2*>(state) + idx;
+    if constexpr (IMPORT) {
+        if (!d.cold) *r = *s;
+    } else {
+        const f64x2 zero = {0.0, 0.0};
+        *s = d.cold ? zero : *r;
+    }
+}
+
 unsigned blocks_for(long long n) { return (unsigned)((n + FK_BLOCK - 1) / FK_BLOCK); }
 
 int ffail(int code, const char* fmt, ...) {
@@ -418,6 +443,84 @@ int ape_fk_bank_set_bodies(ape_fk_bank_t* b, const int32_t* streams_host, int32_
 int ape_fk_bank_get_bodies(ape_fk_bank_t* b, double* out_host) {
     if (!b || !out_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_get_bodies: NULL argument");
     ape_body_table_get(b->bodies, b->S, b->body, out_host);
+    return APE_OK;
+}
+
+// ---- state hand-over: the bank's record of a stream is its stack alone, [smooth][8] f64 ---------------------------
+namespace {
+
+void fk_state_desc_of(const ape_fk_bank* b, ape_stream_state_desc_t* d) {
+    d->version = APE_STATE_VERSION;
+    d->T = 0; d->I = 0; d->smooth = b->smooth; d->n_mc = 1; d->O = 8;
+    d->words_per_stream = 16 * b->smooth;
+}
+
+// descriptors through the next pinned slot (as bank_frame), then the one launch; fill(stream) -> {oldest slot, cold}
+template <bool IMPORT, typename Fill>
+int fk_state_launch(ape_fk_bank* b, const int32_t* streams_host, int32_t K, double* state, hipStream_t st, const char* what, Fill fill) {
+    const int k = b->next;
+    FK_TRY(hipEventSynchronize(b->ev[k]));
+    FkDesc* h = b->stage + (size_t)k * b->S;
+    for (int j = 0; j < K; ++j) h[j] = fill(j, streams_host[j]);
+    FK_TRY(hipMemcpyAsync(b->desc, h, (size_t)K * sizeof(FkDesc), hipMemcpyHostToDevice, st));
+    FK_TRY(hipEventRecord(b->ev[k], st));
+    b->next = (k + 1) % FK_STAGES;
+    hipLaunchKernelGGL(ape_fk_state_kernel<IMPORT>, dim3(blocks_for((long long)K * b->smooth * 4)), dim3(FK_BLOCK), 0, st, b->ring, state,
+                       (const FkDesc*)b->desc, (int)K, b->smooth);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return ffail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+    return APE_OK;
+}
+
+int fk_state_check_call(ape_fk_bank* b, const int32_t* streams_host, int32_t K, const void* state_dev, const void* warm_host, hipStream_t st,
+                        const char* what) {
+    if (!b || !streams_host || !state_dev || !warm_host) return ffail(APE_ERR_INVALID_ARG, "%s: NULL argument", what);
+    if (int rc = check_list(b, streams_host, K, what)) return rc;
+    if (((uintptr_t)state_dev & 15u) != 0) return ffail(APE_ERR_INVALID_ARG, "%s: state_dev must be 16-byte aligned", what);
+    FK_TRY(hipSetDevice(b->device));
+    return check_capture(st, what);
+}
+
+}  // namespace
+
+int ape_fk_bank_state_desc(ape_fk_bank_t* b, ape_stream_state_desc_t* out) {
+    if (!b || !out) return ffail(APE_ERR_INVALID_ARG, "fk_bank_state_desc: NULL argument");
+    fk_state_desc_of(b, out);
+    return APE_OK;
+}
+
+int ape_fk_bank_export(ape_fk_bank_t* b, const int32_t* streams_host, int32_t K, void* state_dev, uint8_t* warm_host, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = fk_state_check_call(b, streams_host, K, state_dev, warm_host, st, "fk_bank_export")) return rc;
+    if (K == 0) return APE_OK;
+    // read-only: a uniform bank stays uniform.  No window: a stream that has seen a row has both bits set
+    return fk_state_launch<false>(b, streams_host, K, (double*)state_dev, st, "fk_bank_export", [&](int j, int s) {
+        const long long c = b->uniform ? b->ucount : b->cnt[s];
+        warm_host[j] = c > 0 ? (uint8_t)(APE_STATE_WINDOW_WARM | APE_STATE_STACK_WARM) : (uint8_t)0;
+        return FkDesc{s, (int)(c % b->smooth), c == 0 ? 1 : 0, 0};
+    });
+}
+
+int ape_fk_bank_import(ape_fk_bank_t* b, const ape_stream_state_desc_t* desc, const int32_t* streams_host, int32_t K,
+                       const void* state_dev, const uint8_t* warm_host, void* stream) {
+    const hipStream_t st = (hipStream_t)stream;
+    if (!desc) return ffail(APE_ERR_INVALID_ARG, "fk_bank_import: NULL argument");
+    if (int rc = fk_state_check_call(b, streams_host, K, state_dev, warm_host, st, "fk_bank_import")) return rc;
+    ape_stream_state_desc_t own;
+    fk_state_desc_of(b, &own);
+    if (desc->version != own.version || desc->T != own.T || desc->I != own.I || desc->smooth != own.smooth || desc->n_mc != own.n_mc ||
+        desc->O != own.O || desc->words_per_stream != own.words_per_stream)
+        return ffail(APE_ERR_INVALID_ARG, "fk_bank_import: the records are {v%d T=%d I=%d smooth=%d n_mc=%d O=%d words=%d}, the bank's {v%d T=0 I=0 smooth=%d n_mc=1 O=8 words=%d}",
+                     desc->version, desc->T, desc->I, desc->smooth, desc->n_mc, desc->O, desc->words_per_stream, own.version, own.smooth,
+                     own.words_per_stream);
+    if (K == 0) return APE_OK;
+    // a stream needs both bits to carry a stack (the record has no window); time order = slot order, the count at `smooth`
+    auto warm = [&](int j) { return (warm_host[j] & APE_STATE_STACK_WARM) != 0 && (warm_host[j] & APE_STATE_WINDOW_WARM) != 0; };
+    if (int rc = fk_state_launch<true>(b, streams_host, K, (double*)const_cast<void*>(state_dev), st, "fk_bank_import",
+                                       [&](int j, int s) { return FkDesc{s, 0, warm(j) ? 0 : 1, 0}; }))
+        return rc;
+    leave_uniform(b);
+    for (int j = 0; j < K; ++j) b->cnt[streams_host[j]] = warm(j) ? b->smooth : 0;
     return APE_OK;
 }
 

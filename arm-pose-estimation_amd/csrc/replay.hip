@@ -45,7 +45,10 @@ __global__ __launch_bounds__(256) void ape_replay_rec_kernel(const int* __restri
 }
 
 // one thread per output float: consecutive threads write consecutive floats and read the same feature row's columns
-__global__ __launch_bounds__(256) void ape_replay_window_kernel(const ReplayWindowParams p) {
+// CARRY (ape_replay_resume): a row before the recording's first frame is the matching row of the record the recording came in with,
+// counted back from its newest; a recording whose window bit is clear is clamped as without carry
+template <bool CARRY = false>
+__global__ __launch_bounds__(256) void ape_replay_window_kernel(const ReplayWindowParams p, const ReplayCarryParams c) {
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     const long long per_row = (long long)p.T * p.I;
     if (idx >= (long long)p.R * per_row) return;
@@ -55,6 +58,15 @@ __global__ __launch_bounds__(256) void ape_replay_window_kernel(const ReplayWind
     const int f = (int)(r / p.n_mc);
     const int seg = p.seg_of[f];
     int src = f - p.T + 1 + t;
+    if constexpr (CARRY) {
+        if (src < seg) {
+            const int rec = c.rec_of[f];
+            if (c.warm[rec] & APE_STATE_WINDOW_WARM) {
+                p.xw[idx] = c.state_in[(size_t)rec * c.words + (size_t)(p.T + src - seg) * p.I + i];
+                return;
+            }
+        }
+    }
     if (src < seg) src = seg;
     p.xw[idx] = p.xx[(size_t)src * p.I + i];
 }
@@ -63,16 +75,26 @@ __global__ __launch_bounds__(256) void ape_replay_window_kernel(const ReplayWind
 // every further row added with +-1/N by the strict `dot < 0.0` rule against row 0).  Adjacent frames share all but n_mc of their rows:
 // the est rows come from L2.
 // TAB: the frame's body is row rec_of[f] of bodies [R,9] (neighbouring lanes mostly share it), else the uniform p.body
-template <typename TMsg, bool TAB = false>
+// CARRY (ape_replay_resume): a stack row before the recording's first frame is the matching est row of the stack the recording came in
+// with (c.est_in, counted back from its newest); a recording whose stack bit is clear is clamped as without carry
+template <typename TMsg, bool TAB = false, bool CARRY = false>
 __global__ __launch_bounds__(256) void ape_replay_msg_kernel(const ReplayMsgParams p, const double* __restrict__ bodies,
-                                                             const int* __restrict__ rec_of) {
+                                                             const int* __restrict__ rec_of, const ReplayCarryParams c) {
     const long long f = p.f_lo + (long long)blockIdx.x * 256 + threadIdx.x;
     if (f >= p.f_hi) return;
     const int M = p.n_mc, N = p.smooth * M, W = p.W;
     const long long seg = p.seg_of[f];
+    int crec = -1;                                      // CARRY: the frame's recording where it came in with a warm stack
+    if constexpr (CARRY) {
+        const int rec = c.rec_of[f];
+        if (c.warm[rec] & APE_STATE_STACK_WARM) crec = rec;
+    }
     auto row = [&](int i) -> const double* {
         const int j = i / M, k = i - j * M;
         long long h = f - p.smooth + 1 + j;
+        if constexpr (CARRY) {
+            if (h < seg && crec >= 0) return c.est_in + (((size_t)crec * p.smooth + (size_t)(p.smooth + h - seg)) * M + k) * W;
+        }
         if (h < seg) h = seg;
         return p.est + (h * M + k - p.est_base) * W;
     };
@@ -115,8 +137,8 @@ __global__ __launch_bounds__(256) void ape_replay_msg_kernel(const ReplayMsgPara
 
 
 // one thread per (frame, stacked row): six values each, neighbouring threads write neighbouring groups
-template <typename TMsg>
-__global__ __launch_bounds__(256) void ape_replay_tail_kernel(const ReplayMsgParams p) {
+template <typename TMsg, bool CARRY = false>
+__global__ __launch_bounds__(256) void ape_replay_tail_kernel(const ReplayMsgParams p, const ReplayCarryParams c) {
     const int M = p.n_mc, N = p.smooth * M;
     const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
     if (idx >= (p.f_hi - p.f_lo) * N) return;
@@ -125,16 +147,70 @@ __global__ __launch_bounds__(256) void ape_replay_tail_kernel(const ReplayMsgPar
     const int j = i / M, k = i - j * M;
     long long h = f - p.smooth + 1 + j;
     const long long seg = p.seg_of[f];
+    const double* e = nullptr;
+    if constexpr (CARRY) {
+        if (h < seg) {
+            const int rec = c.rec_of[f];
+            if (c.warm[rec] & APE_STATE_STACK_WARM) e = c.est_in + (((size_t)rec * p.smooth + (size_t)(p.smooth + h - seg)) * M + k) * p.W;
+        }
+    }
     if (h < seg) h = seg;
-    const double* e = p.est + (h * M + k - p.est_base) * p.W;
+    if (e == nullptr) e = p.est + (h * M + k - p.est_base) * p.W;
     TMsg* dst = static_cast<TMsg*>(p.out) + f * p.out_stride + 25 + (long long)i * 6;
 #pragma unroll
     for (int c = 0; c < 6; ++c) dst[c] = (TMsg)e[c];
 }
 
+// the stacks of R canonical records, [smooth][n_mc][O] behind each record's window words -> contiguous rows for the carried rows' FK launch
+__global__ __launch_bounds__(256) void ape_replay_carry_rows_kernel(const float* __restrict__ state_in, int R, int words, int x_words,
+                                                                    int stack_words, float* __restrict__ y_in) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)R * stack_words) return;
+    const int r = (int)(idx / stack_words), w = (int)(idx - (long long)r * stack_words);
+    y_in[idx] = state_in[(size_t)r * words + x_words + w];
+}
+
+// the recordings' final windows and stacks in the canonical form of the banks: one thread per word; a row before the recording's first
+// frame comes from the record it came in with, or -- cold -- is the clamped first frame, exactly what the kernels above read
+__global__ __launch_bounds__(256) void ape_replay_state_out_kernel(const ReplayStateOutParams p) {
+    const long long idx = (long long)blockIdx.x * 256 + threadIdx.x;
+    if (idx >= (long long)p.R * p.words) return;
+    const int r = (int)(idx / p.words), w = (int)(idx - (long long)r * p.words);
+    const int seg = p.starts[r], e = (r + 1 < p.R ? p.starts[r + 1] : p.F) - 1;
+    const int nx = p.T * p.I, MO = p.n_mc * p.O;
+    const int warm = p.warm != nullptr ? p.warm[r] : 0;
+    const float* in = p.state_in != nullptr ? p.state_in + (size_t)r * p.words : nullptr;
+    float v = 0.0f;
+    if (w < nx) {
+        const int t = w / p.I, i = w - t * p.I;
+        const int src = e - p.T + 1 + t;
+        if (src >= seg) v = p.xx[(size_t)src * p.I + i];
+        else if (warm & APE_STATE_WINDOW_WARM) v = in[(size_t)(p.T + src - seg) * p.I + i];
+        else v = p.xx[(size_t)seg * p.I + i];
+    } else if (w < nx + p.smooth * MO) {
+        const int q = w - nx, j = q / MO, ko = q - j * MO;
+        const int h = e - p.smooth + 1 + j;
+        if (h >= seg) v = p.y[(size_t)h * MO + ko];
+        else if ((warm & APE_STATE_STACK_WARM) && (warm & APE_STATE_WINDOW_WARM)) v = in[nx + (size_t)(p.smooth + h - seg) * MO + ko];
+        else v = p.y[(size_t)seg * MO + ko];
+    }
+    p.state_out[idx] = v;
+}
+
 unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256); }
 
 }  // namespace
+
+hipError_t ape_launch_replay_carry_rows(const float* state_in, int R, int words, int x_words, int stack_words, float* y_in, hipStream_t stream) {
+    hipLaunchKernelGGL(ape_replay_carry_rows_kernel, dim3(blocks_for((long long)R * stack_words)), dim3(256), 0, stream, state_in, R, words,
+                       x_words, stack_words, y_in);
+    return hipGetLastError();
+}
+
+hipError_t ape_launch_replay_state_out(const ReplayStateOutParams& p, hipStream_t stream) {
+    hipLaunchKernelGGL(ape_replay_state_out_kernel, dim3(blocks_for((long long)p.R * p.words)), dim3(256), 0, stream, p);
+    return hipGetLastError();
+}
 
 hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, int* seg_of, hipStream_t stream, int* rec_of) {
     hipLaunchKernelGGL(ape_replay_seg_kernel, dim3(blocks_for(F)), dim3(256), 0, stream, starts, n_starts, F, seg_of);
@@ -142,23 +218,39 @@ hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, in
     return hipGetLastError();
 }
 
-hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t stream) {
-    hipLaunchKernelGGL(ape_replay_window_kernel, dim3(blocks_for((long long)p.R * p.T * p.I)), dim3(256), 0, stream, p);
+hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t stream, const ReplayCarryParams* carry) {
+    const dim3 grid(blocks_for((long long)p.R * p.T * p.I));
+    if (carry != nullptr) hipLaunchKernelGGL(ape_replay_window_kernel<true>, grid, dim3(256), 0, stream, p, *carry);
+    else hipLaunchKernelGGL(ape_replay_window_kernel<false>, grid, dim3(256), 0, stream, p, ReplayCarryParams{});
     return hipGetLastError();
 }
 
-hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream, const double* bodies, const int* rec_of) {
+// one instantiation per (dtype, per-recording bodies, carry)
+template <typename TMsg>
+static void launch_replay_msg_typed(const ReplayMsgParams& p, unsigned blocks, hipStream_t stream, const double* bodies, const int* rec_of,
+                                    const ReplayCarryParams* carry) {
+    const ReplayCarryParams none{};
+    if (carry != nullptr) {
+        if (bodies != nullptr) hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, true, true>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, *carry);
+        else hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, false, true>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, *carry);
+    } else if (bodies != nullptr) hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, true, false>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, none);
+    else hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, false, false>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, none);
+}
+
+hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream, const double* bodies, const int* rec_of,
+                                 const ReplayCarryParams* carry) {
     const long long frames = p.f_hi - p.f_lo;
     if (frames <= 0) return hipSuccess;
-    if (bodies != nullptr) {
-        if (p.out_dtype == APE_F32) hipLaunchKernelGGL((ape_replay_msg_kernel<float, true>), dim3(blocks_for(frames)), dim3(256), 0, stream, p, bodies, rec_of);
-        else hipLaunchKernelGGL((ape_replay_msg_kernel<double, true>), dim3(blocks_for(frames)), dim3(256), 0, stream, p, bodies, rec_of);
-    } else if (p.out_dtype == APE_F32) hipLaunchKernelGGL((ape_replay_msg_kernel<float, false>), dim3(blocks_for(frames)), dim3(256), 0, stream, p, bodies, rec_of);
-    else hipLaunchKernelGGL((ape_replay_msg_kernel<double, false>), dim3(blocks_for(frames)), dim3(256), 0, stream, p, bodies, rec_of);
+    if (p.out_dtype == APE_F32) launch_replay_msg_typed<float>(p, blocks_for(frames), stream, bodies, rec_of, carry);
+    else launch_replay_msg_typed<double>(p, blocks_for(frames), stream, bodies, rec_of, carry);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !tail) return e;
     const long long n = frames * p.smooth * p.n_mc;
-    if (p.out_dtype == APE_F32) hipLaunchKernelGGL(ape_replay_tail_kernel<float>, dim3(blocks_for(n)), dim3(256), 0, stream, p);
-    else hipLaunchKernelGGL(ape_replay_tail_kernel<double>, dim3(blocks_for(n)), dim3(256), 0, stream, p);
+    const ReplayCarryParams none{};
+    if (carry != nullptr) {
+        if (p.out_dtype == APE_F32) hipLaunchKernelGGL((ape_replay_tail_kernel<float, true>), dim3(blocks_for(n)), dim3(256), 0, stream, p, *carry);
+        else hipLaunchKernelGGL((ape_replay_tail_kernel<double, true>), dim3(blocks_for(n)), dim3(256), 0, stream, p, *carry);
+    } else if (p.out_dtype == APE_F32) hipLaunchKernelGGL((ape_replay_tail_kernel<float, false>), dim3(blocks_for(n)), dim3(256), 0, stream, p, none);
+    else hipLaunchKernelGGL((ape_replay_tail_kernel<double, false>), dim3(blocks_for(n)), dim3(256), 0, stream, p, none);
     return hipGetLastError();
 }

@@ -52,6 +52,15 @@ class ApeKalmanDims(C.Structure):
     _fields_ = [("num_ensemble", C.c_int32), ("win_size", C.c_int32), ("device", C.c_int32)]
 
 
+STATE_VERSION, STATE_WINDOW_WARM, STATE_STACK_WARM = 1, 1, 2
+
+
+class ApeStreamStateDesc(C.Structure):
+    """``ape_stream_state_desc_t``: the shape of a bank's canonical per-stream record"""
+    _fields_ = [("version", C.c_int32), ("T", C.c_int32), ("I", C.c_int32), ("smooth", C.c_int32), ("n_mc", C.c_int32),
+                ("O", C.c_int32), ("words_per_stream", C.c_int32)]
+
+
 # every symbol include/ape_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ape_abi_version": (C.c_int, []),
@@ -139,6 +148,13 @@ for _name in ("ape_replay", "ape_fk_replay", "ape_kalman_replay"):
     SIGNATURES[_name + "_bodies"] = (C.c_int, SIGNATURES[_name][1] + [C.c_void_p])
 # ape_replay_bodies for every regressor kind the loader dispatches (DropoutFF, ImuPoseLSTM)
 SIGNATURES["ape_replay_regressor"] = SIGNATURES["ape_replay_bodies"]
+SIGNATURES["ape_replay_resume"] = (C.c_int, SIGNATURES["ape_replay_bodies"][1] + [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64])
+# stream state hand-over: the same trio on the regressor banks and the FK-only bank
+for _bank in ("ape_streams", "ape_fk_bank"):
+    SIGNATURES[_bank + "_state_desc"] = (C.c_int, [C.c_void_p, C.POINTER(ApeStreamStateDesc)])
+    SIGNATURES[_bank + "_export"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+    SIGNATURES[_bank + "_import"] = (C.c_int, [C.c_void_p, C.POINTER(ApeStreamStateDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                               C.c_void_p])
 
 _lib = None
 

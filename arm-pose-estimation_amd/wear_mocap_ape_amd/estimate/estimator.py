@@ -57,6 +57,67 @@ class _DeviceFrame:
 
     def reset(self):
         self._hip.check(self._lib.ape_streams_reset(self._bank), "ape_streams_reset")
+        self._per_stream = False
+
+    # ---- state hand-over: the one stream of this bank as a canonical record ----
+    _per_stream = False        # set_state puts the bank into per-stream mode: frames then run as subset frames until the next reset
+
+    def _device(self):
+        return torch.device("cuda", self._model.device_index)
+
+    def state_desc(self) -> dict:
+        from wear_mocap_ape_amd import stream_state
+        d = self._hip.ApeStreamStateDesc()
+        self._hip.check(self._lib.ape_streams_state_desc(self._bank, self._C.byref(d)), "ape_streams_state_desc")
+        return {k: int(getattr(d, k)) for k in stream_state.DESC_KEYS}
+
+    def get_state(self):
+        """-> (desc, float32 record [1, words] on the device, warm np.uint8 [1]) of the one stream"""
+        C, desc = self._C, self.state_desc()
+        dev = self._device()
+        state = torch.zeros((1, desc["words_per_stream"]), dtype=torch.float32, device=dev)
+        warm, idx = np.zeros((1,), dtype=np.uint8), np.zeros((1,), dtype=np.int32)
+        self._hip.check(self._lib.ape_streams_export(self._bank, C.c_void_p(idx.ctypes.data), 1, C.c_void_p(state.data_ptr()),
+                                                     C.c_void_p(warm.ctypes.data), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                        "ape_streams_export")
+        return desc, state, warm
+
+    def set_state(self, desc: dict, state, warm):
+        from wear_mocap_ape_amd import stream_state
+        C, dev = self._C, self._device()
+        d = self._hip.ApeStreamStateDesc(*[int(desc[k]) for k in stream_state.DESC_KEYS])
+        st = torch.as_tensor(state, dtype=torch.float32).reshape(1, -1).to(dev).contiguous()
+        if st.shape[1] != int(d.words_per_stream):
+            raise UserWarning(f"set_state wants one record of {int(d.words_per_stream)} words, got {st.shape[1]}")
+        w, idx = np.asarray(warm, dtype=np.uint8).reshape(1).copy(), np.zeros((1,), dtype=np.int32)
+        self._hip.check(self._lib.ape_streams_import(self._bank, C.byref(d), C.c_void_p(idx.ctypes.data), 1, C.c_void_p(st.data_ptr()),
+                                                     C.c_void_p(w.ctypes.data), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                        "ape_streams_import")
+        torch.cuda.current_stream(dev).synchronize()     # (the record is this call's own copy)
+        self._per_stream = True
+
+    def _frame_subset(self) -> np.ndarray:
+        """a frame of a bank in per-stream mode: ``ape_streams_frame_subset`` over the one stream (the host frame is lockstep-only)"""
+        C, hip, dev = self._C, self._hip, self._device()
+        packed = self._rows > 1
+        if getattr(self, "_sub_bufs", None) is None:         # once: the device row, the device message, pinned mirrors, the list [0]
+            w = 25 + 6 * self._rows if packed else 25
+            self._sub_bufs = (torch.empty((1, self._width), dtype=torch.float32, device=dev),
+                              torch.empty((1, w), dtype=torch.float64, device=dev),
+                              torch.empty((1, self._width), dtype=torch.float32).pin_memory(),
+                              torch.empty((1, w), dtype=torch.float64).pin_memory(), np.zeros((1,), dtype=np.int32))
+        rd, out, row_pin, out_pin, idx = self._sub_bufs
+        row_pin.numpy()[0, :] = self._row
+        rd.copy_(row_pin, non_blocking=True)
+        hip.check(self._lib.ape_streams_frame_subset(self._bank, self._kind, C.c_void_p(rd.data_ptr()), C.c_void_p(idx.ctypes.data), 1,
+                                                     self._flags | (hip.FLAG_PACKED_MSG if packed else 0), C.c_void_p(out.data_ptr()),
+                                                     hip.F64, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  "ape_streams_frame_subset")
+        self._model.recover()                            # blocking, like the host frame: the message is valid on return
+        out_pin.copy_(out)                                # (behind the blocking recover: the stream is idle)
+        self._out[:] = 0.0                                # N = 1: no tail behind the 25 values
+        self._out[:out.shape[1]] = out_pin.numpy()[0]
+        return self._out
 
     def frame_stats(self, reset: bool = False) -> dict:
         """where the frames' host time went (ape_streams_frame_stats, ABI 7): per-frame microseconds of the last <= 4096 frames in
@@ -78,6 +139,8 @@ class _DeviceFrame:
         """raw message -> float64 [25 + 6N]: the message followed by hand / elbow xyz of the N stacked rows (a view of
         this object's buffer, overwritten by the next frame)"""
         self._row[:] = row                       # array('f') (stream/listener/imu.py:68-70), list or ndarray
+        if self._per_stream:
+            return self._frame_subset()
         self._hip.check(self._lib.ape_streams_frame_host(self._bank, self._kind, self._row_p, self._flags, self._out_p,
                                                          self._hip.F64, None), "ape_streams_frame_host")
         return self._out
@@ -148,6 +211,93 @@ class Estimator:
         frame = getattr(self, "_device_frame", None)
         if frame is not None:
             frame.reset()
+
+    # ---- state hand-over: this estimator's window and stack as one canonical record ----------
+    def get_state(self) -> dict:
+        """The estimator's history as a canonical stream record (``stream_state``): ``{"desc", "window" [T, I], "stack" [smooth,
+        n, O], "warm", "form"}``, window and stack in time order (oldest first), ``warm`` the two bits ``WINDOW_WARM | STACK_WARM``.
+        Bodies are not part of the record.  Two forms, named in ``"form"``:
+
+        ``"device"`` (estimators whose frames run on the device, ``process_row``): read from the one-stream bank with
+        ``ape_streams_export``; the stack holds what the bank's ring holds -- the model's float32 outputs, still normalised.
+        ``"host"`` (the staged path: ``add_xx_to_row_hist_and_make_prediction``): read from ``_row_hist`` / ``_smooth_hist``; the
+        stack holds the DE-NORMALISED float64 predictions, as in the reference (estimator.py:108-118).  With ``smooth == 1`` that
+        path keeps no stack: the stack is zeros and its warm bit clear (a stack of one is rebuilt by the next frame).
+
+        ``state_record(state)`` converts either form to the device record a bank or a replay takes; ``set_state`` accepts both."""
+        from wear_mocap_ape_amd import stream_state as ss
+        frame = self._frame_runner()
+        if frame is not None:
+            desc, rec, warm = frame.get_state()
+            window, stack = ss.unpack(rec.cpu().numpy()[0], desc)
+            return {"desc": desc, "window": window, "stack": stack, "warm": int(warm[0]), "form": "device"}
+        T, smooth = self._sequence_len, self._smooth
+        warm = (ss.WINDOW_WARM if self._row_hist else 0) | (ss.STACK_WARM if self._row_hist and self._smooth_hist else 0)
+        window = np.vstack(self._row_hist) if self._row_hist else np.zeros((T, 0), dtype=np.float32)
+        stack = (np.stack([np.atleast_2d(p) for p in self._smooth_hist]) if warm & ss.STACK_WARM
+                 else np.zeros((smooth, 1, 0), dtype=np.float64))
+        desc = ss.make_desc(T, window.shape[1], smooth, stack.shape[1], stack.shape[2])
+        return {"desc": desc, "window": window, "stack": stack, "warm": warm, "form": "host"}
+
+    def _stack_to_form(self, stack, src: str, dst: str):
+        """the stack between the host form (de-normalised float64) and the device form (normalised float32), with this estimator's
+        own statistics (estimator.py:108-109 and its inverse)"""
+        if src == dst:
+            return stack
+        if dst == "host":
+            s = np.asarray(stack, dtype=np.float32)
+            return s * self._yy_s + self._yy_m if self._normalize else s.astype(np.float64)
+        s = np.asarray(stack, dtype=np.float64)
+        return ((s - self._yy_m) / self._yy_s if self._normalize else s).astype(np.float32)
+
+    def state_record(self, state: dict):
+        """a ``get_state`` dict -> ``(desc, float32 [1, words] host array, np.uint8 [1])`` in the device form: what
+        ``StreamBank.import_state`` takes"""
+        from wear_mocap_ape_amd import stream_state as ss
+        stack = self._stack_to_form(state["stack"], state["form"], "device")
+        window = np.asarray(state["window"], dtype=np.float32)
+        if not (state["warm"] & ss.STACK_WARM) and stack.shape[2] == 0:      # a host stack that was never filled has no width yet
+            raise UserWarning("state_record: this host-form state has no stack shape; use it with set_state on an estimator")
+        desc = ss.make_desc(window.shape[0], window.shape[1], *stack.shape)
+        return desc, ss.pack(window, stack)[np.newaxis, :], np.array([state["warm"]], dtype=np.uint8)
+
+    def set_state(self, state: dict):
+        """continue from a ``get_state`` dict of either form (from this estimator, another one, or built from a bank's or a
+        replay's record with ``stream_state.unpack``, ``"form": "device"``).  The stack is converted to this path's own form with
+        this estimator's statistics where the forms differ (float64 -> float32 rounds).  On the device path the one-stream bank is
+        then in per-stream mode: its frames run as subset frames until the next ``reset``."""
+        from wear_mocap_ape_amd import stream_state as ss
+        warm = int(state["warm"])
+        frame = self._frame_runner()
+        if frame is not None:
+            own = frame.state_desc()
+            if warm & ss.WINDOW_WARM:
+                shape = tuple(np.shape(state["window"])) + (tuple(np.shape(state["stack"])) if warm & ss.STACK_WARM else ())
+                want = (own["T"], own["I"]) + ((own["smooth"], own["n_mc"], own["O"]) if warm & ss.STACK_WARM else ())
+                if shape != want:
+                    raise UserWarning(f"set_state: window / stack of shape {shape}, this estimator keeps {want}")
+            if not warm & ss.WINDOW_WARM:
+                rec = np.zeros((1, own["words_per_stream"]), dtype=np.float32)
+            else:
+                stack = self._stack_to_form(state["stack"], state["form"], "device")
+                if not warm & ss.STACK_WARM:
+                    stack = np.zeros((own["smooth"], own["n_mc"], own["O"]), dtype=np.float32)
+                rec = ss.pack(state["window"], stack)[np.newaxis, :]
+            frame.set_state(own, rec, np.array([warm], dtype=np.uint8))
+            return
+        if not warm & ss.WINDOW_WARM:
+            self._row_hist, self._smooth_hist = [], []
+            return
+        window = np.asarray(state["window"])
+        if window.shape[0] != self._sequence_len:
+            raise UserWarning(f"set_state: a window of {window.shape[0]} rows, this estimator keeps {self._sequence_len}")
+        self._row_hist = [window[t].copy() for t in range(window.shape[0])]
+        self._smooth_hist = []
+        if warm & ss.STACK_WARM and self._smooth > 1:
+            stack = self._stack_to_form(state["stack"], state["form"], "host")
+            if stack.shape[0] != self._smooth:
+                raise UserWarning(f"set_state: a stack of {stack.shape[0]} predictions, this estimator keeps {self._smooth}")
+            self._smooth_hist = [stack[j].copy() for j in range(stack.shape[0])]
 
     # ---- the device-resident frame (processing_loop's fast path) ----------------------------------------------
     def _frame_samples(self):
@@ -321,7 +471,8 @@ class Estimator:
 
     # ---- offline replay: every frame of recorded sessions in one call ----
     def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64,
-                          return_targets: bool = False, seed: int = 0x5EED, max_rows_per_launch: int = 0, bonemaps=None):
+                          return_targets: bool = False, seed: int = 0x5EED, max_rows_per_launch: int = 0, bonemaps=None,
+                          state_in=None, warm_in=None, return_state: bool = False, sample_row_base: int = 0):
         """rows: float32 ``[F, 55|28]`` raw messages of one or more recordings back to back (host array or CUDA
         tensor); ``starts``: the recordings' first rows (default ``[0]``: one recording).  Returns, on the device,
         what ``process_row`` returns for every row of a fresh estimator fed each recording in order (no row skipped):
@@ -333,7 +484,17 @@ class Estimator:
         bounds the sample rows of one regressor launch (0: the library's default) and with it the device workspace.
         ``bonemaps``: one entry per recording (bonemap-like objects, ``None`` for the defaults, or float64 ``[R, 9]`` values) --
         every recording is then replayed as by an estimator built with ITS bonemap (``ape_replay_bodies``, DESIGN.md 4.24);
-        default: this estimator's body for all."""
+        default: this estimator's body for all.
+
+        Resumable replay (``ape_replay_resume``): ``state_in`` float32 ``[R, words]`` (device tensor or host array) with
+        ``warm_in`` uint8 ``[R]`` -- one canonical stream record per listed recording, from an earlier call's ``return_state``, a bank's
+        ``export_state`` or ``state_record(get_state())`` -- lets every recording continue instead of starting cold; ``return_state``
+        appends ``(state, warm)``, the recordings' final records in the same form, to the result (``StreamBank.import_state`` takes
+        them).  ``sample_row_base`` is added to the Philox row counter: one recording replayed over rows ``[0, a), [a, b), ...`` with
+        the states chained and ``sample_row_base = a * n_mc, ...`` returns the rows of the one call (a multiple of 4; Monte-Carlo
+        samples included where the regressor kernel's row granule divides it, see ``ape_hip.h``).  With several recordings the
+        deterministic results are equal and the samples are valid draws, not the one call's.  A recording that ended in an earlier call
+        is not listed.  Bodies are not part of a record.  With none of the four given the call is the old path, entry and all."""
         import ctypes as C
         from wear_mocap_ape_amd import _hip
         model, n_mc = self._hip_model(), self._frame_samples()
@@ -361,15 +522,39 @@ class Estimator:
             kind = self._parse_kind | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             bodies = None if bonemaps is None else bodies_from(bonemaps, int(st.shape[0]), "process_recording bonemaps")
+            extra, state_out, warm_out = (), None, None
+            if state_in is not None or return_state or sample_row_base:
+                from wear_mocap_ape_amd import stream_state as ss
+                entry, n_rec = "ape_replay_resume", int(st.shape[0])
+                words = ss.words_per_stream(1 if isinstance(model, DropoutFF) else self._sequence_len, model.input_size, self._smooth,
+                                            n_mc, model.output_size)
+                sin = win = None
+                if state_in is not None:
+                    if warm_in is None:
+                        raise UserWarning("process_recording: state_in needs warm_in")
+                    sin = torch.as_tensor(state_in, dtype=torch.float32).to(dev).contiguous()
+                    win = np.ascontiguousarray(np.asarray(warm_in, dtype=np.uint8).reshape(-1))
+                    if tuple(sin.shape) != (n_rec, words) or win.shape[0] != n_rec:
+                        raise UserWarning(f"process_recording: state_in must be [{n_rec},{words}] with {n_rec} warm bytes, got "
+                                          f"{tuple(sin.shape)} and {win.shape[0]}")
+                if return_state:
+                    state_out = torch.zeros((n_rec, words), dtype=torch.float32, device=dev)
+                    warm_out = np.zeros((n_rec,), dtype=np.uint8)
+                extra = (C.c_void_p(sin.data_ptr()) if sin is not None else None, C.c_void_p(win.ctypes.data) if win is not None else None,
+                         C.c_void_p(state_out.data_ptr()) if return_state else None,
+                         C.c_void_p(warm_out.ctypes.data) if return_state else None, int(sample_row_base))
             _hip.check(getattr(_hip.lib(), entry)(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
                                                     int(st.shape[0]), self._sequence_len, self._smooth, n_mc, float(model.dropout),
                                                     int(seed) & (2 ** 64 - 1), flags, C.c_void_p(out.data_ptr()),
                                                     _hip.F64 if out_dtype == torch.float64 else _hip.F32,
                                                     C.c_void_p(y.data_ptr()) if y is not None else None,
                                                     int(max_rows_per_launch), stream,
-                                                    C.c_void_p(bodies.ctypes.data) if bodies is not None else None), entry)
+                                                    C.c_void_p(bodies.ctypes.data) if bodies is not None else None, *extra), entry)
             model._pending.clear()         # the call is blocking and checked the handle (its journal is empty)
-        return (out, y) if return_targets else out
+        res = (out, y) if return_targets else out
+        if return_state:
+            res = (res if isinstance(res, tuple) else (res,)) + ((state_out, warm_out),)
+        return res
 
     # read-only views, same names as the reference's properties (estimator.py:188-218)
     sequence_len = property(lambda self: self._sequence_len)

@@ -11,6 +11,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import stream_state as _state
+
 
 def shard_range(n_streams: int, rank: int, world_size: int) -> Tuple[int, int]:
     """contiguous [lo, hi) of stream indices owned by ``rank``; sizes differ by at most one and
@@ -203,6 +205,19 @@ class StreamBank:
                                                      C.c_void_p(out.data_ptr()), sel, self._stream()), "ape_streams_frame_subset")
         return out
 
+    # ---- state hand-over: a stream's window and stack leave the bank and enter another ----
+    def state_desc(self) -> dict:
+        return _state.bank_state_desc(self, "ape_streams")
+    state_desc.__doc__ = _state.STATE_DESC_DOC
+
+    def export_state(self, streams):
+        return _state.bank_export_state(self, "ape_streams", streams)
+    export_state.__doc__ = _state.EXPORT_DOC
+
+    def import_state(self, streams, state, warm, desc=None):
+        _state.bank_import_state(self, "ape_streams", streams, state, warm, desc)
+    import_state.__doc__ = _state.IMPORT_DOC
+
     def check(self):
         """blocking health check of the model's launches (``ape_model_check``): the bank's outputs stay on the device,
         so the caller decides where to pay for the synchronisation -- e.g. once per batch of frames, before the
@@ -341,6 +356,19 @@ class FkStreamBank:
         idx = self._indices(streams)
         self._hip.check(self._hip.lib().ape_fk_bank_reset_subset(self._handle, self._C.c_void_p(idx.ctypes.data), int(idx.shape[0])),
                         "ape_fk_bank_reset_subset")
+
+    # ---- state hand-over: the record is the stack alone, [smooth][8] float64 quaternion pairs (T = I = 0) ----
+    def state_desc(self) -> dict:
+        return _state.bank_state_desc(self, "ape_fk_bank")
+    state_desc.__doc__ = _state.STATE_DESC_DOC
+
+    def export_state(self, streams):
+        return _state.bank_export_state(self, "ape_fk_bank", streams)
+    export_state.__doc__ = _state.EXPORT_DOC
+
+    def import_state(self, streams, state, warm, desc=None):
+        _state.bank_import_state(self, "ape_fk_bank", streams, state, warm, desc)
+    import_state.__doc__ = _state.IMPORT_DOC
 
     def step_rows(self, rows, big_endian: bool = False):
         """lockstep frame: float32 ``[S, 55]`` rows (host array or device tensor), row s for stream s -> ``[S, 25]`` messages (the

@@ -445,6 +445,81 @@ int ape_fk_replay_bodies(int32_t kind, const float* rows_dev, int32_t F, const i
                          const double body9[9], int32_t device, void* out_dev, int32_t out_dtype, void* stream,
                          const double* bodies_host);
 
+/* ---- stream state hand-over: a stream's history leaves its bank (additive in ABI 7) -------------------------------
+ * replaces: nothing in the reference, whose one Estimator keeps `_row_hist` / `_smooth_hist` (estimator.py:93-118) for its lifetime.
+ * After a stream's first row its window always holds T rows and its stack `smooth` predictions (the cold-start padding is
+ * materialised), so a stream's state is a time-ordered window, a time-ordered stack and two warm bits.  The canonical record of one
+ * stream is `words_per_stream` 4-byte words on the device, independent of ring phase, slot and bank:
+ *   window[T][I]            f32, the feature rows as copy 0 of the stream's window ring holds them, oldest first
+ *   stack[smooth][n_mc][O]  f32, the model outputs (normalised NN targets) as the smoothing ring holds them, oldest frame first
+ *   zero words up to the next multiple of 4 (records are 16-byte units; state_dev must be 16-byte aligned)
+ * words_per_stream = (T*I + smooth*n_mc*O + 3) & ~3.  APE_MODEL_FF banks have T = 1, APE_MODEL_IMUPOSE banks n_mc = 1.
+ * The FK-only bank's record is its stack alone: T = I = 0, n_mc = 1, O = 8, stack[smooth][8] of FLOAT64 quaternion pairs (lower arm,
+ * upper arm: what its ring holds), words_per_stream = 16*smooth.
+ * warm_host: one byte per stream in HOST memory, from the bank's host counters (nothing is read back from the device):
+ *   APE_STATE_WINDOW_WARM  at least one row since the cold start; clear: the window words are zeros on export, ignored on import
+ *   APE_STATE_STACK_WARM   at least one prediction since the cold start; clear: likewise for the stack words
+ * NOT in the record: the per-stream bodies (ape_*_get_bodies / ape_*_set_bodies move them) and the Philox position (seed and call
+ * counter stay properties of the bank: an imported stream draws the samples of its NEW bank and list position).
+ * ape_*_state_desc: the bank's own descriptor.
+ * ape_streams_export / ape_fk_bank_export: read-only, ONE launch on `stream`, no host synchronisation; the bank keeps its mode (a
+ *   lockstep bank derives the slots from its global counters).  Record j belongs to stream streams_host[j].  Like a frame, an export
+ *   behind a frame that ape_model_recover may still re-issue sees that frame's results only after the recover.
+ * ape_streams_import / ape_fk_bank_import: puts the bank into per-stream mode as the first subset call does (the other streams'
+ *   counters are seeded from the lockstep ones), writes copy 0 of the listed streams' window rings and their stack rings in ONE launch
+ *   and sets their host counters: a warm window behaves as after >= T rows, a warm stack as after >= smooth predictions; a stream
+ *   with APE_STATE_WINDOW_WARM clear is cold-started like ape_streams_reset_subset (its stack too); one with only
+ *   APE_STATE_STACK_WARM clear keeps the window and gets a cold stack.  Streams not listed stay bit for bit untouched.  Journal: as a
+ *   newer frame does, an import drops the bank's pending step / subset frame from the journal (recover BEFORE the import if that
+ *   frame's outputs are still wanted).
+ * K = 0 is a no-op.  Refused (non-zero, ape_last_error) before any launch: NULL arguments, a descriptor that differs from the bank's
+ * own in any field, K < 0 or K > S, an index outside [0, S), a duplicate index, a bank that lost its rings, a capturing stream.
+ * The Kalman bank has no such entries (its ragged stack and RNG position are not part of this record). */
+#define APE_STATE_VERSION 1
+#define APE_STATE_WINDOW_WARM 1
+#define APE_STATE_STACK_WARM 2
+typedef struct ape_stream_state_desc {
+    int32_t version;              /* APE_STATE_VERSION */
+    int32_t T, I, smooth, n_mc, O;
+    int32_t words_per_stream;
+} ape_stream_state_desc_t;
+int ape_streams_state_desc(ape_streams_t* bank, ape_stream_state_desc_t* out);
+int ape_streams_export(ape_streams_t* bank, const int32_t* streams_host, int32_t K, void* state_dev, uint8_t* warm_host, void* stream);
+int ape_streams_import(ape_streams_t* bank, const ape_stream_state_desc_t* desc, const int32_t* streams_host, int32_t K,
+                       const void* state_dev, const uint8_t* warm_host, void* stream);
+int ape_fk_bank_state_desc(ape_fk_bank_t* bank, ape_stream_state_desc_t* out);
+int ape_fk_bank_export(ape_fk_bank_t* bank, const int32_t* streams_host, int32_t K, void* state_dev, uint8_t* warm_host, void* stream);
+int ape_fk_bank_import(ape_fk_bank_t* bank, const ape_stream_state_desc_t* desc, const int32_t* streams_host, int32_t K,
+                       const void* state_dev, const uint8_t* warm_host, void* stream);
+/* One bank's exports and imports share one device descriptor buffer (as its subset frames share theirs): issue a bank's calls on ONE
+ * stream, or order the streams yourself.
+ *
+ * ape_replay_resume: ape_replay_regressor (every model kind; same arguments, same semantics, bodies_host may be NULL) that can start from
+ * and end in the canonical records above, so that a recording replayed in pieces, or handed over between a replay and a bank, continues
+ * without a cold start.  The records' shape is {T = seq_len (1 for APE_MODEL_FF), I, smooth, n_mc (1 for APE_MODEL_IMUPOSE), O} of the
+ * call; 16-byte aligned device buffers of [R][words_per_stream] words, warm bytes [R] in host memory.
+ *   state_in_dev / warm_in_host   NULL, or one record per LISTED recording: recording r does not start cold -- window row t of its frame
+ *                  f is feature row f - T + 1 + t where that is at or after the recording's first row of this call, else the matching row
+ *                  of the record's window counted back from its newest; its stack likewise (the carried model outputs go through the same
+ *                  de-normalisation and FK as fresh ones, once per call, with the recording's body).  A clear warm bit: that part starts
+ *                  cold exactly as in ape_replay.
+ *   state_out_dev / warm_out_host NULL, or they receive each recording's final window and stack (warm = 3: every listed recording has a
+ *                  row).  The call then keeps the targets of all F * n_mc rows on the device (O(F), like the features).
+ *   sample_row_base  added to the Philox row counter of every launch; base + F*n_mc < 2^31, and a multiple of 4 where an LSTM
+ *                  model runs with dropout (without dropout it is not read).
+ * Chunk contract, ONE recording (R = 1): calls over rows [0, a), [a, b), ... that chain each state_out into the next state_in with
+ * sample_row_base = a * n_mc, b * n_mc, ... return the rows of the single call over [0, F), Monte-Carlo samples included where the
+ * regressor kernel's row granule divides every base: 4 rows on the batch-tile kernel (ape_model_set_kernel(APE_KERNEL_TILE16)), 16 on
+ * the cluster kernels, 1 for APE_MODEL_FF.  For R > 1 the deterministic results are equal; the samples are valid draws but not those of
+ * the one call, whose row index is global over the concatenation.  A recording that ended in an earlier call is simply not listed:
+ * every listed recording has at least one row.  NULL states and base 0: ape_replay_regressor, on the instantiations it always ran.
+ * BLOCKING.  Refused as ape_replay, and: state_in without warm_in, state_out without warm_out, a misaligned buffer, a bad base. */
+int ape_replay_resume(ape_model_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                      int32_t seq_len, int32_t smooth, int32_t n_mc, float dropout_p, uint64_t seed, uint32_t flags,
+                      void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream,
+                      const double* bodies_host, const void* state_in_dev, const uint8_t* warm_in_host, void* state_out_dev,
+                      uint8_t* warm_out_host, uint64_t sample_row_base);
+
 /* kernel selection for A/B runs and tests; no effect on results beyond float32 summation order */
 int ape_model_set_kernel(ape_model_t* model, int32_t choice);
 int ape_model_set_precision(ape_model_t* model, int32_t precision);
