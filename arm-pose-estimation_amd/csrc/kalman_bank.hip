@@ -17,8 +17,12 @@
 //                                 (stream_post_device.h's finish_msg), the packed tail, n_rows, and the stream's frame counter.
 // Frame counters live on the device; the host only remembers which streams have a cold start pending and hands that over in the
 // staged stream list (or, for lockstep frames, as one kernel argument).
+//   ape_kalman_state_kernel       (thread per 16 bytes) a stream's rings <-> its canonical record: the state hand-over of DESIGN.md 4.27
+//                                 (ape_kalman_bank_export / _import, ape_kalman_replay_resume); for it the host also keeps each
+//                                 stream's age, min(frames since the cold start, W + 1)
 // float64 with separate roundings for a * b + c, like numpy: contraction is off in this file.
 #include <cstdarg>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <new>
@@ -268,6 +272,94 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const Kb
     }
 }
 
+// ---- state hand-over: a stream's rings <-> its canonical record, every part oldest first ---------------------------
+//   window  f64 [W][22]          44 W words, 11 W 16-byte units
+//   history f32 [E][W][14]       E W 7 8-byte pieces; entries older than the cold start (canonical index < W - age) are zeros
+//   stack   f32 [smooth][E][14]  smooth E 7 pieces; rows at or beyond the entry's count are zeros
+//   counts  i32 [smooth]         1 or E; then zero words up to a multiple of 4
+// One thread per 16-byte unit of a record, consecutive threads consecutive units (the canonical side: one 16-byte access).  A unit of
+// the window is one 16-byte access on the ring side too; every later unit is two 8-byte pieces, each of which lies in ONE part (the
+// history and the stack are whole pieces, the counts begin at an even word), so a unit that straddles two parts needs no special case.
+// With the stream's count c (export: read from p.cnt here; import: the descriptor's c', which the kernel also stores) canonical index i
+// of a part lives in ring slot (c + i) mod size: slot c mod size is the one the next frame overwrites, the oldest (head and tail above).
+struct KsDesc { int stream, age, c, pad; };   // age = min(frames since the cold start, W + 1); 0: export zeros / import nothing
+
+struct KsParams {
+    const KsDesc* desc;               // [K]
+    int* cnt;
+    double* xwin;
+    float* state;
+    float* yring;
+    int* nring;
+    float* rec;                       // [K, 4 * units] the records
+    int K, E, W, smooth, units;
+};
+
+template <bool IMPORT>
+__global__ __launch_bounds__(KB_BLOCK) void ape_kalman_state_kernel(const KsParams p) {
+    const long long idx = (long long)blockIdx.x * KB_BLOCK + threadIdx.x;
+    if (idx >= (long long)p.K * p.units) return;
+    const int j = (int)(idx / p.units), u = (int)(idx - (long long)j * p.units);
+    const KsDesc d = p.desc[j];
+    f32x4* rec = reinterpret_cast<f32x4*>(p.rec) + idx;
+    if (d.age <= 0) {
+        if (!IMPORT) *rec = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        return;
+    }
+    const int s = d.stream, E = p.E, W = p.W, smooth = p.smooth;
+    int c = IMPORT ? d.c : p.cnt[s];
+    if (c < 0) c = 0;
+    if (IMPORT && u == 0) p.cnt[s] = c;
+    const int nwin = 11 * W;
+    if (u < nwin) {                                     // a row is 22 doubles = 11 units
+        const int t = u / 11, q = u - 11 * t;
+        f32x4* ring = reinterpret_cast<f32x4*>(p.xwin + ((size_t)s * W + (c + t) % W) * RAW) + q;
+        if (IMPORT) *ring = *rec;
+        else *rec = *ring;
+        return;
+    }
+    const int nh = E * W * 7, ns = smooth * E * 7;
+    f32x4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (IMPORT) v = *rec;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int piece = 2 * (u - nwin) + h;
+        float2 x = {v[2 * h], v[2 * h + 1]};
+        if (piece < nh) {
+            const int e = piece / (W * 7), rem = piece - e * W * 7, i = rem / 7, q = rem - 7 * i;
+            const bool live = i >= W - d.age;
+            float2* ring = reinterpret_cast<float2*>(p.state + (((size_t)s * E + e) * W + (c + i) % W) * DX) + q;
+            if (IMPORT) *ring = live ? x : float2{0.0f, 0.0f};
+            else x = live ? *ring : float2{0.0f, 0.0f};
+        } else if (piece < nh + ns) {
+            const int r2 = piece - nh, k = r2 / (E * 7), rem = r2 - k * E * 7, r = rem / 7, q = rem - 7 * r;
+            const int slot = (c + k) % smooth;
+            // the entry's count: the ring's on export, the record's own count word on import
+            const int n = IMPORT ? reinterpret_cast<const int*>(p.rec)[(size_t)j * p.units * 4 + 4 * nwin + 2 * (nh + ns) + k]
+                                 : p.nring[s * smooth + slot];
+            const bool live = r < (n == E ? E : 1);
+            float2* ring = reinterpret_cast<float2*>(p.yring + (((size_t)s * smooth + slot) * E + r) * DX) + q;
+            if (IMPORT) *ring = live ? x : float2{0.0f, 0.0f};
+            else x = live ? *ring : float2{0.0f, 0.0f};
+        } else {
+            float w[2] = {x.x, x.y};
+#pragma unroll
+            for (int b = 0; b < 2; ++b) {
+                const int k = 2 * (piece - nh - ns) + b;
+                if (k < smooth) {                       // anything but E is stored as 1: the tail kernel never reads past an entry
+                    int* cell = p.nring + s * smooth + (c + k) % smooth;
+                    if (IMPORT) *cell = __builtin_bit_cast(int, w[b]) == E ? E : 1;
+                    else w[b] = __builtin_bit_cast(float, *cell == E ? E : 1);
+                } else w[b] = 0.0f;
+            }
+            x = float2{w[0], w[1]};
+        }
+        v[2 * h] = x.x;
+        v[2 * h + 1] = x.y;
+    }
+    if (!IMPORT) *rec = v;
+}
+
 
 int bfail(int code, const char* fmt, ...) {
     char buf[512];
@@ -326,18 +418,28 @@ struct ape_kalman_bank {
     void* h_out = nullptr;
     int* h_n = nullptr;
     ApeBodyTable bodies;              // per-stream bodies [S,9] (off until ape_kalman_bank_set_bodies)
+    // state hand-over: min(frames since the cold start, W + 1) per stream, kept where `pending` is kept, and the
+    // export / import kernel's own descriptors (b->desc may still be read by a frame in flight); allocated by the first hand-over
+    std::vector<int> age;
+    KsDesc* ks_desc = nullptr;
+    KsDesc* ks_stage = nullptr;
+    hipEvent_t ks_ev[KB_STAGES] = {};
+    int ks_next = 0;
 };
 
 namespace {
 
 void bank_free(ape_kalman_bank* b) {
     ape_body_table_free(b->bodies);
-    void* dev[] = {b->xwin, b->state, b->yring, b->nring, b->cnt, b->raw, b->dense, b->corrected, b->ensz, b->mcorr, b->mpred, b->z, b->desc};
+    void* dev[] = {b->xwin, b->state, b->yring, b->nring, b->cnt, b->raw, b->dense, b->corrected, b->ensz, b->mcorr, b->mpred, b->z, b->desc,
+                   b->ks_desc};
     for (void* q : dev) if (q) (void)hipFree(q);
-    void* host[] = {b->stage, b->h_rows, b->h_out, b->h_n};
+    void* host[] = {b->stage, b->h_rows, b->h_out, b->h_n, b->ks_stage};
     for (void* q : host) if (q) (void)hipHostFree(q);
-    for (int i = 0; i < KB_STAGES; ++i)
+    for (int i = 0; i < KB_STAGES; ++i) {
         if (b->ev[i]) (void)hipEventDestroy(b->ev[i]);
+        if (b->ks_ev[i]) (void)hipEventDestroy(b->ks_ev[i]);
+    }
     delete b;
 }
 
@@ -357,6 +459,7 @@ int bank_make(ape_kalman* model, int32_t n_streams, int32_t smooth, const char* 
     b->model = model; b->S = n_streams; b->E = mi.E; b->W = mi.W; b->smooth = smooth; b->device = mi.device;
     b->pending.assign((size_t)n_streams, 1);
     b->n_pending = n_streams;
+    b->age.assign((size_t)n_streams, 0);
     const size_t S = (size_t)n_streams, E = (size_t)mi.E, W = (size_t)mi.W;
     hipError_t e = hipMalloc((void**)&b->xwin, S * W * RAW * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&b->state, S * E * W * DX * sizeof(float));
@@ -458,9 +561,85 @@ int bank_frame(ape_kalman_bank* b, int32_t kind, const float* rows, const int32_
         return rc;
     for (int j = 0; j < K; ++j) {
         const int s = streams_host ? streams_host[j] : j;
-        if (b->pending[s]) { b->pending[s] = 0; b->n_pending -= 1; }
+        if (b->pending[s]) { b->pending[s] = 0; b->n_pending -= 1; b->age[s] = 1; }
+        else if (b->age[s] <= b->W) b->age[s] += 1;
     }
     return APE_OK;
+}
+
+// ---- state hand-over ------------------------------------------------------------------------------------------------
+int state_words(int E, int W, int smooth) { return (2 * W * RAW + E * W * DX + smooth * E * DX + smooth + 3) & ~3; }
+
+void state_desc_of(const ape_kalman_bank* b, ape_kalman_state_desc_t* d) {
+    d->version = APE_KALMAN_STATE_VERSION;
+    d->E = b->E; d->W = b->W; d->smooth = b->smooth;
+    d->words_per_stream = state_words(b->E, b->W, b->smooth);
+}
+
+// the count an imported stream of that age continues from: its true count while `init` depends on it, else the smallest positive
+// multiple of W * smooth above W -- every ring then has slot order = time order, and the tail kernel's wrap rule keeps its residues
+int import_count(const ape_kalman_bank* b, int age) {
+    if (age <= b->W) return age;
+    const int period = b->W * b->smooth;
+    return period * (b->W / period + 1);
+}
+
+// K records <-> the listed streams' rings in ONE launch on `st`; the ages are those of ages_host (validated by the caller).
+// streams_host nullptr: stream j (the replay's bank)
+template <bool IMPORT>
+int state_launch(ape_kalman_bank* b, const int32_t* streams_host, int32_t K, const int32_t* ages_host, float* rec, hipStream_t st,
+                 const char* what) {
+    if (!b->ks_desc) {
+        hipError_t e = hipMalloc((void**)&b->ks_desc, (size_t)b->S * sizeof(KsDesc));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&b->ks_stage, (size_t)KB_STAGES * b->S * sizeof(KsDesc), hipHostMallocDefault);
+        for (int i = 0; i < KB_STAGES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&b->ks_ev[i], hipEventDisableTiming);
+        if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: allocation failed: %s", what, hipGetErrorString(e));
+    }
+    // the descriptors into the next pinned slot -- once the copy that last read it has completed (as bank_frame's lists)
+    const int k = b->ks_next;
+    KB_TRY(hipEventSynchronize(b->ks_ev[k]));
+    KsDesc* h = b->ks_stage + (size_t)k * b->S;
+    for (int j = 0; j < K; ++j) h[j] = KsDesc{streams_host ? streams_host[j] : j, ages_host[j], IMPORT ? import_count(b, ages_host[j]) : 0, 0};
+    KB_TRY(hipMemcpyAsync(b->ks_desc, h, (size_t)K * sizeof(KsDesc), hipMemcpyHostToDevice, st));
+    KB_TRY(hipEventRecord(b->ks_ev[k], st));
+    b->ks_next = (k + 1) % KB_STAGES;
+    KsParams p{};
+    p.desc = b->ks_desc; p.cnt = b->cnt; p.xwin = b->xwin; p.state = b->state; p.yring = b->yring; p.nring = b->nring; p.rec = rec;
+    p.K = K; p.E = b->E; p.W = b->W; p.smooth = b->smooth; p.units = state_words(b->E, b->W, b->smooth) / 4;
+    const unsigned blocks = (unsigned)(((long long)K * p.units + KB_BLOCK - 1) / KB_BLOCK);
+    hipLaunchKernelGGL(ape_kalman_state_kernel<IMPORT>, dim3(blocks), dim3(KB_BLOCK), 0, st, p);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+    return APE_OK;
+}
+
+int check_ages(const ape_kalman_bank* b, const int32_t* ages_host, int32_t K, const char* what) {
+    for (int j = 0; j < K; ++j)
+        if (ages_host[j] < 0 || ages_host[j] > b->W + 1)
+            return bfail(APE_ERR_INVALID_ARG, "%s: age %d (entry %d) outside [0, W + 1 = %d]", what, ages_host[j], j, b->W + 1);
+    return APE_OK;
+}
+
+int check_state_desc(const ape_kalman_bank* b, const ape_kalman_state_desc_t* desc, const char* what) {
+    ape_kalman_state_desc_t own;
+    state_desc_of(b, &own);
+    if (desc->version != own.version || desc->E != own.E || desc->W != own.W || desc->smooth != own.smooth ||
+        desc->words_per_stream != own.words_per_stream)
+        return bfail(APE_ERR_INVALID_ARG, "%s: the records are {v%d E=%d W=%d smooth=%d words=%d}, the bank's {v%d E=%d W=%d smooth=%d words=%d}", what,
+                     desc->version, desc->E, desc->W, desc->smooth, desc->words_per_stream, own.version, own.E, own.W, own.smooth,
+                     own.words_per_stream);
+    return APE_OK;
+}
+
+// the host side of an import: what the device will hold once the launch has run
+void adopt_ages(ape_kalman_bank* b, const int32_t* streams_host, int32_t K, const int32_t* ages_host) {
+    for (int j = 0; j < K; ++j) {
+        const int s = streams_host ? streams_host[j] : j;
+        const char cold = ages_host[j] == 0 ? 1 : 0;
+        b->n_pending += (int)cold - (int)b->pending[s];
+        b->pending[s] = cold;
+        b->age[s] = ages_host[j];
+    }
 }
 
 }  // namespace
@@ -485,14 +664,17 @@ int ape_kalman_bank_reset(ape_kalman_bank_t* b) {
     if (!b) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_reset: NULL bank");
     b->pending.assign((size_t)b->S, 1);
     b->n_pending = b->S;
+    b->age.assign((size_t)b->S, 0);
     return APE_OK;
 }
 
 int ape_kalman_bank_reset_subset(ape_kalman_bank_t* b, const int32_t* streams_host, int32_t K) {
     if (!b || !streams_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_reset_subset: NULL argument");
     if (int rc = check_list(b, streams_host, K, "kalman_bank_reset_subset")) return rc;
-    for (int j = 0; j < K; ++j)
+    for (int j = 0; j < K; ++j) {
         if (!b->pending[streams_host[j]]) { b->pending[streams_host[j]] = 1; b->n_pending += 1; }
+        b->age[streams_host[j]] = 0;
+    }
     return APE_OK;
 }
 
@@ -541,6 +723,56 @@ int ape_kalman_bank_set_seed(ape_kalman_bank_t* b, uint64_t seed) {
     return APE_OK;
 }
 
+int ape_kalman_bank_get_draw_position(ape_kalman_bank_t* b, uint64_t* seed, uint64_t* calls) {
+    if (!b || !seed || !calls) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_get_draw_position: NULL argument");
+    *seed = b->seed;
+    *calls = b->calls;
+    return APE_OK;
+}
+
+int ape_kalman_bank_set_draw_position(ape_kalman_bank_t* b, uint64_t seed, uint64_t calls) {
+    if (!b) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_draw_position: NULL bank");
+    b->seed = seed;
+    b->calls = calls;
+    return APE_OK;
+}
+
+int ape_kalman_bank_state_desc(ape_kalman_bank_t* b, ape_kalman_state_desc_t* out) {
+    if (!b || !out) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_state_desc: NULL argument");
+    state_desc_of(b, out);
+    return APE_OK;
+}
+
+int ape_kalman_bank_export(ape_kalman_bank_t* b, const int32_t* streams_host, int32_t K, void* state_dev, int32_t* age_host, void* stream) {
+    if (!b || !streams_host || !state_dev || !age_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_export: NULL argument");
+    if (int rc = check_list(b, streams_host, K, "kalman_bank_export")) return rc;
+    if (((uintptr_t)state_dev & 15u) != 0) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_export: state_dev must be 16-byte aligned");
+    KB_TRY(hipSetDevice(b->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "kalman_bank_export")) return rc;
+    if (K == 0) return APE_OK;
+    for (int j = 0; j < K; ++j) age_host[j] = b->age[streams_host[j]];
+    return state_launch<false>(b, streams_host, K, age_host, (float*)state_dev, st, "kalman_bank_export");
+}
+
+int ape_kalman_bank_import(ape_kalman_bank_t* b, const ape_kalman_state_desc_t* desc, const int32_t* streams_host, int32_t K,
+                           const void* state_dev, const int32_t* age_host, void* stream) {
+    if (!b || !desc || !streams_host || !state_dev || !age_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_import: NULL argument");
+    if (int rc = check_state_desc(b, desc, "kalman_bank_import")) return rc;
+    if (int rc = check_list(b, streams_host, K, "kalman_bank_import")) return rc;
+    if (int rc = check_ages(b, age_host, K, "kalman_bank_import")) return rc;
+    if (((uintptr_t)state_dev & 15u) != 0) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_import: state_dev must be 16-byte aligned");
+    KB_TRY(hipSetDevice(b->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "kalman_bank_import")) return rc;
+    bool carried = false;
+    for (int j = 0; j < K; ++j) carried = carried || age_host[j] > 0;
+    if (carried)                                              // (age 0 everywhere: ape_kalman_bank_reset_subset, nothing to write)
+        if (int rc = state_launch<true>(b, streams_host, K, age_host, (float*)const_cast<void*>(state_dev), st, "kalman_bank_import")) return rc;
+    adopt_ages(b, streams_host, K, age_host);
+    return APE_OK;
+}
+
 int ape_kalman_bank_frame(ape_kalman_bank_t* b, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
                           const float* noise_dev, const float* init_noise_dev, uint32_t flags, void* out_dev, int32_t out_dtype,
                           int32_t* n_rows_dev, float* y_dev, void* stream) {
@@ -586,14 +818,23 @@ int ape_kalman_bank_frame_host(ape_kalman_bank_t* b, int32_t kind, const float* 
 int ape_kalman_replay(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                       int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s, const double body9[9],
                       uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev, float* y_dev, void* stream) {
-    return ape_kalman_replay_bodies(model, kind, rows_dev, F, seg_starts_host, R, smooth, xx_m, xx_s, yy_m, yy_s, body9, seed, flags, out_dev,
-                                    out_dtype, n_rows_dev, y_dev, stream, nullptr);
+    return ape_kalman_replay_resume(model, kind, rows_dev, F, seg_starts_host, R, smooth, xx_m, xx_s, yy_m, yy_s, body9, seed, flags, out_dev,
+                                    out_dtype, n_rows_dev, y_dev, stream, nullptr, nullptr, nullptr, nullptr, nullptr, 0);
 }
 
 int ape_kalman_replay_bodies(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                              int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
                              const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
                              float* y_dev, void* stream, const double* bodies_host) {
+    return ape_kalman_replay_resume(model, kind, rows_dev, F, seg_starts_host, R, smooth, xx_m, xx_s, yy_m, yy_s, body9, seed, flags, out_dev,
+                                    out_dtype, n_rows_dev, y_dev, stream, bodies_host, nullptr, nullptr, nullptr, nullptr, 0);
+}
+
+int ape_kalman_replay_resume(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                             int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
+                             const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
+                             float* y_dev, void* stream, const double* bodies_host, const void* state_in_dev, const int32_t* age_in_host,
+                             void* state_out_dev, int32_t* age_out_host, uint64_t call_base) {
     if (!model || !rows_dev || !out_dev || !n_rows_dev || (!body9 && !bodies_host)) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: NULL argument");
     if (int rc = check_kind(kind, "kalman_replay")) return rc;
     if (F < 1) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: F=%d must be >= 1", F);
@@ -609,6 +850,10 @@ int ape_kalman_replay_bodies(ape_kalman_t* model, int32_t kind, const float* row
     const bool any = xx_m || xx_s || yy_m || yy_s;
     if (any && !(xx_m && xx_s && yy_m && yy_s)) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: all four statistics or none");
     if (R > 65535) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: %d recordings, at most 65535 in one call", R);
+    if (!state_in_dev != !age_in_host) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: state_in and age_in come together or not at all");
+    if (!state_out_dev != !age_out_host) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: state_out and age_out come together or not at all");
+    if ((((uintptr_t)state_in_dev) | ((uintptr_t)state_out_dev)) & 15u)
+        return bfail(APE_ERR_INVALID_ARG, "kalman_replay: the record buffers must be 16-byte aligned");
     // ---- from here on the model is read.  The replay is a fresh bank of R streams: frame t lists the recordings that have a row t
     struct Holder {
         ape_kalman_bank* b = nullptr;
@@ -619,11 +864,19 @@ int ape_kalman_replay_bodies(ape_kalman_t* model, int32_t kind, const float* row
     ape_kalman_bank* b = hold.b;
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "kalman_replay")) return rc;
+    if (age_in_host)
+        if (int rc = check_ages(b, age_in_host, R, "kalman_replay")) return rc;
     if (any) (void)ape_kalman_bank_set_norm_stats(b, xx_m, xx_s, yy_m, yy_s);
     if (body9) memcpy(b->body, body9, sizeof(b->body));
     // one body per recording: the replay's bank has a stream per recording, so the table's row r is recording r's
     if (bodies_host) KB_TRY(ape_body_table_set(b->bodies, R, false, b->body, nullptr, R, bodies_host, st));
     b->seed = seed;
+    b->calls = call_base;
+    // recordings that carry a state continue from it: the import writes their rings and counts, their first frame is no cold start
+    bool carried = false;
+    for (int r = 0; r < R && age_in_host; ++r) carried = carried || age_in_host[r] > 0;
+    if (carried)
+        if (int rc = state_launch<true>(b, nullptr, R, age_in_host, (float*)const_cast<void*>(state_in_dev), st, "kalman_replay")) return rc;
     std::vector<int> len((size_t)R);
     int longest = 0;
     for (int r = 0; r < R; ++r) {
@@ -635,7 +888,8 @@ int ape_kalman_replay_bodies(ape_kalman_t* model, int32_t kind, const float* row
     std::vector<int> first((size_t)longest + 1, 0);
     for (int t = 0; t < longest; ++t) {
         for (int r = 0; r < R; ++r)
-            if (len[r] > t) descs.push_back(KbDesc{r, t == 0 ? 1 : 0, seg_starts_host[r] + t, seg_starts_host[r] + t});
+            if (len[r] > t)
+                descs.push_back(KbDesc{r, t == 0 && !(age_in_host && age_in_host[r] > 0) ? 1 : 0, seg_starts_host[r] + t, seg_starts_host[r] + t});
         first[t + 1] = (int)descs.size();
     }
     KB_TRY(hipMalloc(&hold.descs, descs.size() * sizeof(KbDesc)));
@@ -644,6 +898,13 @@ int ape_kalman_replay_bodies(ape_kalman_t* model, int32_t kind, const float* row
     for (int t = 0; t < longest && rc == APE_OK; ++t)
         rc = frame_launch(b, (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0, rows_dev, (const KbDesc*)hold.descs + first[t], 0, first[t + 1] - first[t],
                           nullptr, nullptr, flags, out_dev, out_dtype, n_rows_dev, y_dev, st, "kalman_replay");
+    if (rc == APE_OK && state_out_dev) {                      // every recording has a row: no age is 0
+        for (int r = 0; r < R; ++r) {
+            const long long a = (long long)(age_in_host ? age_in_host[r] : 0) + len[r];
+            age_out_host[r] = (int32_t)(a > b->W + 1 ? b->W + 1 : a);
+        }
+        rc = state_launch<false>(b, nullptr, R, age_out_host, (float*)state_out_dev, st, "kalman_replay");
+    }
     const hipError_t e = hipStreamSynchronize(st);            // the bank and the lists are freed behind this
     if (rc != APE_OK) return rc;
     if (e != hipSuccess) return bfail(APE_ERR_HIP, "kalman_replay: synchronise failed: %s", hipGetErrorString(e));

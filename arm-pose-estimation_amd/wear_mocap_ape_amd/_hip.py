@@ -61,6 +61,14 @@ class ApeStreamStateDesc(C.Structure):
                 ("O", C.c_int32), ("words_per_stream", C.c_int32)]
 
 
+KALMAN_STATE_VERSION = 1
+
+
+class ApeKalmanStateDesc(C.Structure):
+    """``ape_kalman_state_desc_t``: the shape of a Kalman bank's canonical per-stream record"""
+    _fields_ = [("version", C.c_int32), ("E", C.c_int32), ("W", C.c_int32), ("smooth", C.c_int32), ("words_per_stream", C.c_int32)]
+
+
 # every symbol include/ape_hip.h declares: name -> (restype, argtypes)
 SIGNATURES = {
     "ape_abi_version": (C.c_int, []),
@@ -155,6 +163,15 @@ for _bank in ("ape_streams", "ape_fk_bank"):
     SIGNATURES[_bank + "_export"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
     SIGNATURES[_bank + "_import"] = (C.c_int, [C.c_void_p, C.POINTER(ApeStreamStateDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
                                                C.c_void_p])
+# the Kalman bank's state hand-over: records with int32 ages, the bank's draw position, the resumable replay
+SIGNATURES["ape_kalman_bank_state_desc"] = (C.c_int, [C.c_void_p, C.POINTER(ApeKalmanStateDesc)])
+SIGNATURES["ape_kalman_bank_export"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+SIGNATURES["ape_kalman_bank_import"] = (C.c_int, [C.c_void_p, C.POINTER(ApeKalmanStateDesc), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p])
+SIGNATURES["ape_kalman_bank_get_draw_position"] = (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)])
+SIGNATURES["ape_kalman_bank_set_draw_position"] = (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64])
+SIGNATURES["ape_kalman_replay_resume"] = (C.c_int, SIGNATURES["ape_kalman_replay_bodies"][1] +
+                                          [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64])
 
 _lib = None
 

@@ -59,6 +59,40 @@ class _KalmanDeviceFrame:
         _hip.check(self._lib.ape_kalman_bank_reset(self._bank), "ape_kalman_bank_reset")
         self.manual_seed(self._seed)
 
+    # ---- state hand-over: the one stream of this bank as a canonical record, and the bank's draw position ----
+    def get_state(self):
+        from wear_mocap_ape_amd import stream_state as ss
+        d = _hip.ApeKalmanStateDesc()
+        _hip.check(self._lib.ape_kalman_bank_state_desc(self._bank, C.byref(d)), "ape_kalman_bank_state_desc")
+        desc = {k: int(getattr(d, k)) for k in ss.KALMAN_DESC_KEYS}
+        dev = self._model.torch_device
+        with torch.cuda.device(dev):
+            rec = torch.zeros((1, desc["words_per_stream"]), dtype=torch.float32, device=dev)
+            age, idx = np.zeros((1,), dtype=np.int32), np.zeros((1,), dtype=np.int32)
+            _hip.check(self._lib.ape_kalman_bank_export(self._bank, C.c_void_p(idx.ctypes.data), 1, C.c_void_p(rec.data_ptr()),
+                                                        C.c_void_p(age.ctypes.data), None), "ape_kalman_bank_export")
+            record = rec.cpu().numpy()[0].copy()              # (synchronises the null stream the export ran on)
+        seed, calls = C.c_uint64(), C.c_uint64()
+        _hip.check(self._lib.ape_kalman_bank_get_draw_position(self._bank, C.byref(seed), C.byref(calls)), "ape_kalman_bank_get_draw_position")
+        return {"form": "kalman-device", "desc": desc, "record": record, "age": int(age[0]), "seed": int(seed.value),
+                "calls": int(calls.value)}
+
+    def set_state(self, state):
+        from wear_mocap_ape_amd import stream_state as ss
+        desc = state["desc"]
+        d = _hip.ApeKalmanStateDesc(*[int(desc[k]) for k in ss.KALMAN_DESC_KEYS])
+        dev = self._model.torch_device
+        with torch.cuda.device(dev):
+            rec = ss.kalman_records_tensor(np.asarray(state["record"], dtype=np.float32).reshape(1, -1), 1, int(d.words_per_stream), dev)
+            age, idx = np.asarray([int(state["age"])], dtype=np.int32), np.zeros((1,), dtype=np.int32)
+            _hip.check(self._lib.ape_kalman_bank_import(self._bank, C.byref(d), C.c_void_p(idx.ctypes.data), 1, C.c_void_p(rec.data_ptr()),
+                                                        C.c_void_p(age.ctypes.data), None), "ape_kalman_bank_import")
+            torch.cuda.synchronize(dev)                       # the launch has read the record before it is released
+        if "seed" in state and "calls" in state:
+            self._seed = int(state["seed"]) & (2 ** 64 - 1)
+            _hip.check(self._lib.ape_kalman_bank_set_draw_position(self._bank, self._seed, int(state["calls"]) & (2 ** 64 - 1)),
+                       "ape_kalman_bank_set_draw_position")
+
     def frame(self, row):
         """raw message -> (float64 packed row, stacked-row count); a view of this object's buffer, overwritten by the next frame"""
         self._row[:] = row
@@ -159,6 +193,34 @@ class WatchPhonePocketKalman(Estimator):
                                                     self._add_mc_samples, self.frame_seed)
         return self._device_frame
 
+    # ---- state hand-over ----
+    def get_state(self) -> dict:
+        """The estimator's history on the device-frame path: ``{"form": "kalman-device", "desc", "record", "age", "seed", "calls"}``
+        -- the canonical record of its one-stream bank as float32 words on the host (``stream_state.kalman_unpack`` gives window, state
+        history, stack and row counts), ``age = min(frames since the cold start, W + 1)`` and the bank's draw position.  Bodies are not
+        part of it.  The staged host path (``use_device_frame = False``) keeps its history in the torch model's own tensors and has no
+        such record: there this raises ``UserWarning``."""
+        frame = self._frame_runner()
+        if frame is None:
+            raise UserWarning("WatchPhonePocketKalman.get_state needs the device frame: with use_device_frame = False the staged host "
+                              "path keeps no canonical record")
+        return frame.get_state()
+
+    def set_state(self, state: dict):
+        """continue from a ``get_state`` dict (of this estimator or another one, or built from a bank's ``export_state`` or a
+        replay's ``return_state``): the one-stream bank imports the record and takes over the draw position when the dict carries
+        ``"seed"`` and ``"calls"``, so ``process_row`` continues bit for bit.  Raises ``UserWarning`` with
+        ``use_device_frame = False``."""
+        frame = self._frame_runner()
+        if frame is None:
+            raise UserWarning("WatchPhonePocketKalman.set_state needs the device frame: with use_device_frame = False the staged host "
+                              "path keeps no canonical record")
+        if state.get("form") != "kalman-device":
+            raise UserWarning(f"WatchPhonePocketKalman.set_state wants a 'kalman-device' state, got form {state.get('form')!r}")
+        frame.set_state(state)
+        if "seed" in state:
+            self.frame_seed = int(state["seed"])
+
     def process_row(self, row):
         """one iteration of the consumer loop (estimator.py:174-177) as one ``ape_kalman_bank_frame_host`` call: the same types and
         lengths as the staged path (``use_device_frame = False``) -- 25 values while the stack holds one row, 25 + 6 n for n > 1
@@ -174,7 +236,7 @@ class WatchPhonePocketKalman(Estimator):
         return cut.copy() if self.msg_as_array else cut.tolist()
 
     def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64, return_targets: bool = False,
-                          seed: int = 0x5EED, bonemaps=None):
+                          seed: int = 0x5EED, bonemaps=None, state_in=None, age_in=None, return_state: bool = False, call_base: int = 0):
         """rows: float32 ``[F, 55]`` raw messages of one or more recordings back to back (host array or CUDA tensor); ``starts``: the
         recordings' first rows (default ``[0]``).  Returns ``(out, n_rows)`` on the device -- for every row what ``process_row`` of a
         fresh estimator with ``manual_seed(seed)`` fed that recording returns (no row skipped; several recordings share the flipout
@@ -183,7 +245,15 @@ class WatchPhonePocketKalman(Estimator):
         ``return_targets`` also the normalised predictions float32 ``[F, num_ensemble, 14]`` (row 0 alone on a recording's first
         W + 1 frames).  ``bonemaps``: one entry per recording (bonemap-like objects, ``None``, or float64 ``[R, 9]`` values): every
         recording as by an estimator built with its bonemap (``ape_kalman_replay_bodies``); default: this
-        estimator's body for all."""
+        estimator's body for all.
+
+        Resumable (``ape_kalman_replay_resume``): ``state_in`` float32 words ``[R, words]`` and ``age_in`` int32
+        ``[R]`` (from an earlier call's ``return_state``, a bank's ``export_state`` or ``get_state``) continue every recording with
+        age > 0 instead of starting it cold; ``return_state`` appends ``(state, age)`` -- the records after each recording's last
+        frame on the device and their ages -- to the result; ``call_base`` is the number of frames the recordings have already been
+        through: pieces ``[0, a), [a, b), ...`` of one recording that chain state and age with ``call_base = a, b, ...`` return the
+        rows of the one call, device draws included (several recordings: when every piece lists the same recordings cut at the same
+        offsets)."""
         if out_dtype not in (torch.float32, torch.float64):
             raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
         model = self.__model
@@ -205,11 +275,31 @@ class WatchPhonePocketKalman(Estimator):
             kind = _hip.PARSE_WATCH_PHONE_POCKET | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             bodies = None if bonemaps is None else bodies_from(bonemaps, int(st.shape[0]), "process_recording bonemaps")
-            _hip.check(_hip.lib().ape_kalman_replay_bodies(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
-                                                    int(st.shape[0]), self._smooth, *sp, _hip.dptr(body, C.c_double),
-                                                    int(seed) & (2 ** 64 - 1), _hip.FLAG_PACKED_MSG if packed else 0,
-                                                    C.c_void_p(out.data_ptr()), _hip.F64 if out_dtype == torch.float64 else _hip.F32,
-                                                    C.c_void_p(n_rows.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
-                                                    stream, C.c_void_p(bodies.ctypes.data) if bodies is not None else None),
-                       "ape_kalman_replay_bodies")
-        return (out, n_rows, y) if return_targets else (out, n_rows)
+            R = int(st.shape[0])
+            from wear_mocap_ape_amd import stream_state as ss
+            words = ss.kalman_words(self.__num_ensemble, self.__win_size, max(1, self._smooth))
+            if (state_in is None) != (age_in is None):
+                raise UserWarning("process_recording wants state_in and age_in together")
+            s_in = a_in = s_out = a_out = None
+            if state_in is not None:
+                s_in = ss.kalman_records_tensor(state_in, R, words, dev)
+                a_in = np.ascontiguousarray(np.asarray(age_in, dtype=np.int32).reshape(-1))
+                if a_in.shape[0] != R:
+                    raise UserWarning(f"process_recording wants {R} ages, got {a_in.shape[0]}")
+            if return_state:
+                s_out = torch.zeros((R, words), dtype=torch.float32, device=dev)
+                a_out = np.zeros((R,), dtype=np.int32)
+            vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
+            ap = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None         # noqa: E731
+            args = (model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data), R, self._smooth, *sp,
+                    _hip.dptr(body, C.c_double), int(seed) & (2 ** 64 - 1), _hip.FLAG_PACKED_MSG if packed else 0,
+                    C.c_void_p(out.data_ptr()), _hip.F64 if out_dtype == torch.float64 else _hip.F32, C.c_void_p(n_rows.data_ptr()),
+                    C.c_void_p(y.data_ptr()) if y is not None else None, stream,
+                    C.c_void_p(bodies.ctypes.data) if bodies is not None else None)
+            if s_in is None and s_out is None and not call_base:
+                _hip.check(_hip.lib().ape_kalman_replay_bodies(*args), "ape_kalman_replay_bodies")
+            else:
+                _hip.check(_hip.lib().ape_kalman_replay_resume(*args, vp(s_in), ap(a_in), vp(s_out), ap(a_out), int(call_base) & (2 ** 64 - 1)),
+                           "ape_kalman_replay_resume")
+        res = (out, n_rows, y) if return_targets else (out, n_rows)
+        return res + (s_out, a_out) if return_state else res

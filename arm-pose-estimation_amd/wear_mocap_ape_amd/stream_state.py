@@ -5,7 +5,10 @@ A record is ``words_per_stream`` 4-byte words: ``window[T][I]`` float32 (the str
 [n_mc][O]`` float32 (the model outputs of its last ``smooth`` frames, oldest first), zero words up to the next multiple of 4 (records
 are 16-byte units).  It does not depend on ring phase, slot or bank.  Two warm bits per stream travel beside it on the host:
 ``WINDOW_WARM`` (at least one row since the cold start) and ``STACK_WARM`` (at least one prediction).  Bodies and the Philox position
-are not part of it."""
+are not part of it.
+
+The Kalman bank's record (``ape_kalman_state_desc_t``) is restated at the end: ``kalman_words``, ``kalman_pack``,
+``kalman_unpack``."""
 import numpy as np
 
 VERSION = 1
@@ -112,3 +115,69 @@ IMPORT_DOC = """the reverse of ``export_state``: the listed streams continue fro
         window and gets a cold stack.  Puts the bank into per-stream mode like ``frame``; streams not listed stay untouched.  Bodies
         are NOT part of the record: move them with ``set_bodies``.  A pending frame that ``recover`` could still re-issue is dropped
         from the journal: recover first if its outputs are still wanted."""
+
+
+# ---- the Kalman bank's record (C ABI ``ape_kalman_state_desc_t``, DESIGN.md 4.27) -------------------------------------------------------
+# 4-byte words, every part oldest first: window float64 [W, 22], state history float32 [E, W, 14] (time step minor; entries that do not
+# exist yet are zeros), stack float32 [smooth, E, 14] (normalised predictions; rows at or beyond an entry's count are zeros), counts
+# int32 [smooth] (1 or E), zero words up to a multiple of 4.  Beside it on the host: ``age = min(frames since the cold start, W + 1)``.
+
+KALMAN_VERSION = 1
+KALMAN_DESC_KEYS = ("version", "E", "W", "smooth", "words_per_stream")
+
+
+def kalman_words(E: int, W: int, smooth: int) -> int:
+    """``2*W*22 + E*W*14 + smooth*E*14 + smooth`` rounded up to a multiple of 4 words (16 bytes)"""
+    return (2 * W * 22 + E * W * 14 + smooth * E * 14 + smooth + 3) & ~3
+
+
+def kalman_desc(E: int, W: int, smooth: int) -> dict:
+    return {"version": KALMAN_VERSION, "E": int(E), "W": int(W), "smooth": int(smooth), "words_per_stream": kalman_words(E, W, smooth)}
+
+
+def kalman_pack(window, history, stack, counts) -> np.ndarray:
+    """``window`` [W, 22] float64, ``history`` [E, W, 14], ``stack`` [smooth, E, 14] float32 and ``counts`` [smooth] int32 (time order,
+    oldest first) -> one record as float32 words [words] (the float64 and int32 parts keep their bits)"""
+    w = np.ascontiguousarray(window, dtype=np.float64)
+    h = np.ascontiguousarray(history, dtype=np.float32)
+    s = np.ascontiguousarray(stack, dtype=np.float32)
+    c = np.ascontiguousarray(counts, dtype=np.int32).reshape(-1)
+    if w.ndim != 2 or w.shape[1] != 22 or h.ndim != 3 or h.shape[1:] != (w.shape[0], 14) or s.shape != (c.shape[0], h.shape[0], 14):
+        raise UserWarning(f"kalman_pack wants window [W,22], history [E,W,14], stack [smooth,E,14], counts [smooth], got {w.shape}, "
+                          f"{h.shape}, {s.shape}, {c.shape}")
+    out = np.zeros((kalman_words(h.shape[0], w.shape[0], c.shape[0]),), dtype=np.float32)
+    parts = (w.reshape(-1).view(np.float32), h.reshape(-1), s.reshape(-1), c.view(np.float32))
+    at = 0
+    for part in parts:
+        out[at:at + part.size] = part
+        at += part.size
+    return out
+
+
+def kalman_unpack(record, desc: dict):
+    """one record -> (window float64 [W, 22], history float32 [E, W, 14], stack float32 [smooth, E, 14], counts int32 [smooth], padding
+    float32 words) as copies"""
+    r = np.ascontiguousarray(np.asarray(record).reshape(-1))
+    if r.dtype != np.float32:
+        raise UserWarning(f"a Kalman record is float32 words, got {r.dtype}")
+    E, W, smooth = (int(desc[k]) for k in ("E", "W", "smooth"))
+    if r.size != kalman_words(E, W, smooth):
+        raise UserWarning(f"a record of {r.size} words does not match {desc}")
+    nw, nh, ns = 2 * W * 22, E * W * 14, smooth * E * 14
+    window = r[:nw].view(np.float64).reshape(W, 22).copy()
+    history = r[nw:nw + nh].reshape(E, W, 14).copy()
+    stack = r[nw + nh:nw + nh + ns].reshape(smooth, E, 14).copy()
+    counts = r[nw + nh + ns:nw + nh + ns + smooth].view(np.int32).copy()
+    return window, history, stack, counts, r[nw + nh + ns + smooth:].copy()
+
+
+def kalman_records_tensor(state, K: int, words: int, device):
+    """records given as a device / host tensor or array -> contiguous float32 [K, words] on ``device``"""
+    import torch
+    if not isinstance(state, torch.Tensor):
+        state = torch.from_numpy(np.ascontiguousarray(state))
+    if state.dtype != torch.float32 or state.dim() != 2 or state.shape[0] != K or state.shape[1] != words:
+        raise UserWarning(f"wanted {K} records of {words} float32 words, got {state.dtype} {tuple(state.shape)}")
+    if state.is_cuda and state.device != device:
+        raise UserWarning(f"the records live on {state.device}, the bank on {device}")
+    return state.to(device).contiguous()

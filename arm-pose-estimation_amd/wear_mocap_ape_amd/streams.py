@@ -545,6 +545,70 @@ class KalmanStreamBank:
         ``[K, E, 14]``): tests.  The bank's own buffers, overwritten by the next subset frame."""
         return self._frame(rows, self._indices(streams), big_endian, datagrams, noise, init_noise, return_targets, "sub")
 
+    # ---- state hand-over (DESIGN.md 4.27) ----
+    def state_desc(self) -> dict:
+        """the bank's ``ape_kalman_state_desc_t`` as a dict: ``version, E, W, smooth, words_per_stream``"""
+        from . import stream_state as ss
+        d = self._hip.ApeKalmanStateDesc()
+        self._hip.check(self._hip.lib().ape_kalman_bank_state_desc(self._handle, self._C.byref(d)), "ape_kalman_bank_state_desc")
+        return {k: int(getattr(d, k)) for k in ss.KALMAN_DESC_KEYS}
+
+    def export_state(self, streams):
+        """-> ``(state, age)``: float32 words ``[K, words_per_stream]`` on the device, record j the canonical state of stream
+        ``streams[j]`` (``stream_state.kalman_unpack`` gives its time-ordered window, state history, stack and row counts), and
+        ``np.int32 [K]`` ages, ``min(frames since the cold start, W + 1)``: 0 cold (a zero record), 1..W the init phase, W + 1
+        mature.  Read-only, one launch on the current stream, no synchronisation.  Bodies are NOT part of the record (``bodies`` /
+        ``set_bodies`` move them), nor is the draw position (``get_draw_position``)."""
+        C = self._C
+        idx = self._indices(streams)
+        K = int(idx.shape[0])
+        # (the launch writes every word of every record: no fill in front of it)
+        state = torch.empty((K, self.state_desc()["words_per_stream"]), dtype=torch.float32, device=self._device)
+        age = np.zeros((K,), dtype=np.int32)
+        if K:
+            self._hip.check(self._hip.lib().ape_kalman_bank_export(self._handle, C.c_void_p(idx.ctypes.data), K, C.c_void_p(state.data_ptr()),
+                                                                   C.c_void_p(age.ctypes.data), self._stream()), "ape_kalman_bank_export")
+        return state, age
+
+    def import_state(self, streams, state, age, desc=None):
+        """the reverse of ``export_state``: the listed streams continue from the given records (from this bank, another bank or GPU,
+        a replay's ``return_state``, or ``WatchPhonePocketKalman.get_state``); ``desc`` (default: this bank's own) must equal this
+        bank's ``state_desc()``.  A stream with age 0 is cold-started as by ``reset(streams=)``.  Streams not listed stay untouched.
+        Bodies are NOT part of the record: move them with ``set_bodies``.  The imported stream draws the samples of THIS bank and its
+        list position; ``set_draw_position(*source.get_draw_position())`` continues the source bank's sequence."""
+        from . import stream_state as ss
+        C = self._C
+        idx = self._indices(streams)
+        K = int(idx.shape[0])
+        own = self.state_desc()
+        src = own if desc is None else desc
+        missing = [k for k in ss.KALMAN_DESC_KEYS if k not in src]
+        if missing:
+            raise UserWarning(f"state descriptor lacks {missing}")
+        d = self._hip.ApeKalmanStateDesc(*[int(src[k]) for k in ss.KALMAN_DESC_KEYS])
+        state = ss.kalman_records_tensor(state, K, int(d.words_per_stream), self._device)
+        a = np.ascontiguousarray(np.asarray(age, dtype=np.int32).reshape(-1))
+        if a.shape[0] != K:
+            raise UserWarning(f"import_state wants {K} ages, got {a.shape[0]}")
+        self._hip.check(self._hip.lib().ape_kalman_bank_import(self._handle, C.byref(d), C.c_void_p(idx.ctypes.data), K,
+                                                               C.c_void_p(state.data_ptr()), C.c_void_p(a.ctypes.data), self._stream()),
+                        "ape_kalman_bank_import")
+        self._state_keep = state           # the launch reads it behind this call
+
+    def get_draw_position(self):
+        """-> ``(seed, calls)``: the seed of the device-side draws and the number of frames this bank has issued since it was set"""
+        C = self._C
+        seed, calls = C.c_uint64(), C.c_uint64()
+        self._hip.check(self._hip.lib().ape_kalman_bank_get_draw_position(self._handle, C.byref(seed), C.byref(calls)),
+                        "ape_kalman_bank_get_draw_position")
+        return int(seed.value), int(calls.value)
+
+    def set_draw_position(self, seed: int, calls: int):
+        """continue another bank's draw sequence: the next frame draws with the key of call ``calls + 1`` under ``seed``"""
+        self._hip.check(self._hip.lib().ape_kalman_bank_set_draw_position(self._handle, int(seed) & (2 ** 64 - 1), int(calls) & (2 ** 64 - 1)),
+                        "ape_kalman_bank_set_draw_position")
+        return self
+
     def check(self):
         """blocking: raises if a frame met an exactly singular innovation matrix (``ape_kalman_check``)"""
         self._model.check()

@@ -474,7 +474,7 @@ int ape_fk_replay_bodies(int32_t kind, const float* rows_dev, int32_t F, const i
  *   frame's outputs are still wanted).
  * K = 0 is a no-op.  Refused (non-zero, ape_last_error) before any launch: NULL arguments, a descriptor that differs from the bank's
  * own in any field, K < 0 or K > S, an index outside [0, S), a duplicate index, a bank that lost its rings, a capturing stream.
- * The Kalman bank has no such entries (its ragged stack and RNG position are not part of this record). */
+ * The Kalman bank's record is its own (ragged stack, state history: ape_kalman_bank_export below). */
 #define APE_STATE_VERSION 1
 #define APE_STATE_WINDOW_WARM 1
 #define APE_STATE_STACK_WARM 2
@@ -656,6 +656,63 @@ int ape_kalman_replay_bodies(ape_kalman_t* model, int32_t kind, const float* row
                              int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
                              const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
                              float* y_dev, void* stream, const double* bodies_host);
+
+/* ---- the Kalman bank's state hand-over: a stream's history leaves its bank (additive in ABI 7) ----------------------
+ * replaces: nothing in the reference, whose one estimator keeps its window, `__input_state` and `__init_step`
+ * (watch_phone_pocket_kalman.py:57-63, 133-169) for its lifetime.  PARITY UNPINNED like the bank.
+ * The canonical record of one stream is `words_per_stream` 4-byte words on the device, independent of ring phase, slot and bank, every
+ * part oldest first:
+ *   window         f64 [W][22]          the W feature rows the stream's latest frame saw (the cold-start padding is materialised)
+ *   state history  f32 [E][W][14]       the last W entries, time step minor; entries that do not exist yet (age < W) are zeros
+ *   stack          f32 [smooth][E][14]  the last `smooth` predictions, normalised; rows at or beyond an entry's count are zeros
+ *   counts         i32 [smooth]         1 (a sensor-mean frame) or E (an ensemble frame) per stack entry
+ *   zero words up to the next multiple of 4 (records are 16-byte units; state_dev must be 16-byte aligned)
+ * words_per_stream = (2*W*22 + E*W*14 + smooth*E*14 + smooth + 3) & ~3  (E = 48, W = 10, smooth = 1: 7836 words).
+ * age_host: int32 per stream in HOST memory, min(frames since the stream's cold start, W + 1): 0 cold, 1..W the init phase (the
+ *   frame returns the sensor mean), W + 1 mature.  The bank keeps it on the host (advanced by every frame, zeroed by the resets), so
+ *   neither call reads anything back from the device.
+ * NOT in the record: the per-stream bodies (ape_kalman_bank_get_bodies / _set_bodies move them) and the draw position, which belongs to
+ *   the bank: the key of a bank's call n is seed + 0xD1342543DE82EF95 * n, draws are indexed by list position and member.
+ *   ape_kalman_bank_get_draw_position / _set_draw_position read and write (seed, number of calls so far).  A bank with the same seed
+ *   and call count that steps an imported stream at the same list position draws what the source bank would have drawn; anywhere else
+ *   the stream draws valid samples of its new bank.
+ * ape_kalman_bank_export: read-only, ONE launch on `stream`, no host synchronisation.  Record j and age_host[j] belong to stream
+ *   streams_host[j]; a cold stream gives a zero record and age 0.
+ * ape_kalman_bank_import: ONE launch that writes the listed streams' rings, row counts and frame counters (an imported mature stream
+ *   continues at the smallest multiple of W * smooth above W: slot order = time order); a count word that is not E is stored as 1.
+ *   Clears the pending cold start of streams with age > 0; age 0 is ape_kalman_bank_reset_subset for that stream and writes nothing.
+ *   Streams not listed stay bit for bit untouched.
+ * K = 0 is a no-op.  Refused (non-zero, ape_last_error) before any launch: NULL arguments, a descriptor that differs from the bank's
+ * own in any field, an age outside [0, W + 1], K < 0 or K > S, an index outside [0, S) or listed twice, a record buffer that is not
+ * 16-byte aligned, a capturing stream.  One bank's exports and imports share one device descriptor buffer: issue them on ONE stream.
+ *
+ * ape_kalman_replay_resume: ape_kalman_replay_bodies (same arguments, same semantics) that can start from and end in such records;
+ * [R][words_per_stream] words in 16-byte aligned device buffers, ages [R] in host memory, each pair NULL or given together.
+ *   state_in_dev / age_in_host    recording r with age > 0 does not start cold: the replay's fresh bank imports its record.  Age 0, or
+ *                  no state: a cold start as in ape_kalman_replay.
+ *   state_out_dev / age_out_host  receive every recording's record after its last frame, age_out = min(age_in + length, W + 1)
+ *   call_base      the bank's call count starts here (ape_kalman_replay: 0), so frame t of the call draws with key number
+ *                  call_base + t + 1
+ * Chunk contract, ONE recording: calls over rows [0, a), [a, b), ... that chain state and age with call_base = a, b, ... return the
+ * rows of the one call over [0, F), device draws included.  The same holds for R > 1 when every piece lists the same recordings cut at
+ * the same offsets (list positions and call numbers then agree); otherwise the results are valid draws but not the one call's. */
+#define APE_KALMAN_STATE_VERSION 1
+typedef struct ape_kalman_state_desc {
+    int32_t version;              /* APE_KALMAN_STATE_VERSION */
+    int32_t E, W, smooth;
+    int32_t words_per_stream;
+} ape_kalman_state_desc_t;
+int ape_kalman_bank_state_desc(ape_kalman_bank_t* bank, ape_kalman_state_desc_t* out);
+int ape_kalman_bank_export(ape_kalman_bank_t* bank, const int32_t* streams_host, int32_t K, void* state_dev, int32_t* age_host, void* stream);
+int ape_kalman_bank_import(ape_kalman_bank_t* bank, const ape_kalman_state_desc_t* desc, const int32_t* streams_host, int32_t K,
+                           const void* state_dev, const int32_t* age_host, void* stream);
+int ape_kalman_bank_get_draw_position(ape_kalman_bank_t* bank, uint64_t* seed, uint64_t* calls);
+int ape_kalman_bank_set_draw_position(ape_kalman_bank_t* bank, uint64_t seed, uint64_t calls);
+int ape_kalman_replay_resume(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                             int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
+                             const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
+                             float* y_dev, void* stream, const double* bodies_host, const void* state_in_dev, const int32_t* age_in_host,
+                             void* state_out_dev, int32_t* age_out_host, uint64_t call_base);
 
 #ifdef __cplusplus
 }
