@@ -822,6 +822,9 @@ struct FkTail {
 static bool mc_small_fits(const ape_model* m, int n_streams, int n_mc) {
     if (!m->mcs_ok || !m->c32_on || m->kernel_choice != APE_KERNEL_AUTO || m->precision != APE_PRECISION_F32 || m->replaying) return false;
     if (n_streams < 1 || n_streams > 8 || n_mc < 1) return false;
+    // (its head gives 16 lanes of a 256-thread workgroup to every target: targets 16 .. of the 20-target position layout would stay
+    //  unwritten -- such a bank steps on the general route)
+    if (m->dims.output_size > 16) return false;
     const int cps = 8 / n_streams;
     return (n_mc + cps - 1) / cps <= 16;
 }
@@ -1481,6 +1484,19 @@ int ape_msg_reduce(ape_model_t* m, const double* est_dev, int32_t N, double* msg
     return APE_OK;
 }
 
+int ape_spread_reduce(ape_model_t* m, const double* est_dev, int32_t N, const double* msg_dev, double* spread_dev, void* stream) {
+    if (!m || !est_dev || !msg_dev || !spread_dev) return fail(APE_ERR_INVALID_ARG, "spread_reduce: NULL argument");
+    if (N < 1) return fail(APE_ERR_INVALID_ARG, "spread_reduce: N=%d must be >= 1", N);
+    if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "spread_reduce: model has no target layout");
+    MsgParams p{};
+    p.est = est_dev;
+    p.N = N; p.layout = m->dims.target_layout; p.W = layout_est_width(p.layout);
+    // (not journaled: no cooperative kernel in front of it can abort it, and it reads what ape_fk / ape_msg_reduce re-issue into)
+    hipError_t e = ape_launch_spread_reduce(p, msg_dev, spread_dev, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(APE_ERR_HIP, "spread kernel launch failed: %s", hipGetErrorString(e));
+    return APE_OK;
+}
+
 int ape_parse_rows(int32_t kind, const float* rows_dev, int32_t N, void* xx_dev, int32_t xx_dtype, void* stream) {
     if (!rows_dev || !xx_dev) return fail(APE_ERR_INVALID_ARG, "parse_rows: NULL argument");
     if (N < 1) return fail(APE_ERR_INVALID_ARG, "parse_rows: N=%d must be >= 1", N);
@@ -1498,7 +1514,7 @@ int ape_parse_rows(int32_t kind, const float* rows_dev, int32_t N, void* xx_dev,
 int ape_infer(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t flags, float* y_dev, void* est_dev,
               int32_t est_dtype, void* stream) {
     if (!m || !x_dev || !est_dev) return fail(APE_ERR_INVALID_ARG, "infer: NULL argument");
-    if (flags & (APE_FLAG_ALL_STEPS | APE_FLAG_DROPOUT_MASKS | APE_FLAG_DROPOUT_PHILOX))
+    if (flags & (APE_FLAG_ALL_STEPS | APE_FLAG_DROPOUT_MASKS | APE_FLAG_DROPOUT_PHILOX | APE_FLAG_SPREAD))
         return fail(APE_ERR_INVALID_ARG, "infer: only NORMALIZE_INPUT is accepted (use ape_lstm_forward + ape_fk)");
     float* y = y_dev;
     if (!y) {
@@ -1591,13 +1607,17 @@ static hipError_t bank_alloc(ape_streams* b) {
     if (e == hipSuccess) e = hipMalloc((void**)&b->y_new, R * O * sizeof(float));
     // a few streams with tall smoothing stacks: the post-filter deals a stream's stack over several workgroups (one CU each)
     if (b->post_part) (void)hipFree(b->post_part);
-    b->post_part = nullptr; b->post_cnt = nullptr;
+    b->post_part = nullptr; b->post_cnt = nullptr; b->post_spread = nullptr;
     const int chunks = ape_stream_post_chunks(b->smooth * b->n_mc);
     if (e == hipSuccess && chunks > 1 && (long long)b->S * chunks <= b->model->n_cus) {
         const size_t part_bytes = (size_t)b->S * chunks * 21 * sizeof(double);
-        e = hipMalloc((void**)&b->post_part, part_bytes + (size_t)b->S * sizeof(unsigned));
-        if (e == hipSuccess) e = hipMemset(b->post_part, 0, part_bytes + (size_t)b->S * sizeof(unsigned));
+        // (behind the tickets, 8-byte aligned: the spread record's partial sums, four role waves x 18 per chunk -- APE_FLAG_SPREAD frames)
+        const size_t cnt_bytes = ((size_t)b->S * sizeof(unsigned) + 7) & ~(size_t)7;
+        const size_t spread_bytes = (size_t)b->S * chunks * 72 * sizeof(double);
+        e = hipMalloc((void**)&b->post_part, part_bytes + cnt_bytes + spread_bytes);
+        if (e == hipSuccess) e = hipMemset(b->post_part, 0, part_bytes + cnt_bytes + spread_bytes);
         if (e == hipSuccess) b->post_cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(b->post_part) + part_bytes);
+        if (e == hipSuccess) b->post_spread = reinterpret_cast<double*>(reinterpret_cast<char*>(b->post_part) + part_bytes + cnt_bytes);
     }
     return e;
 }
@@ -1911,9 +1931,11 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
     // the exchange-form selectors of include/ape_hip.h travel to the frame's LSTM launches unchanged (same bits whichever is set)
     const uint32_t diag_wt = flags & (APE_FLAG_ANY_PLACEMENT | APE_FLAG_IN_XCD_PLAIN | APE_FLAG_NO_XCD_CLASSES);
     flags &= ~diag_wt;
-    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG))
-        return fail(APE_ERR_INVALID_ARG, "streams_step: NORMALIZE_INPUT, PACKED_MSG and the exchange-form selectors ANY_PLACEMENT, "
+    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG | APE_FLAG_SPREAD))
+        return fail(APE_ERR_INVALID_ARG, "streams_step: NORMALIZE_INPUT, PACKED_MSG, SPREAD and the exchange-form selectors ANY_PLACEMENT, "
                     "IN_XCD_PLAIN, NO_XCD_CLASSES are accepted");
+    const bool spread = (flags & APE_FLAG_SPREAD) != 0;     // every msg row APE_SPREAD_WIDTH columns longer (post-filter, SPR forms)
+    flags &= ~(uint32_t)APE_FLAG_SPREAD;
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "streams_step: unknown dtype selector");
     const bool packed = (flags & APE_FLAG_PACKED_MSG) != 0;
     if (packed && tail_dev)
@@ -1926,7 +1948,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
     const int x_ring = (int)(b->frames % b->T);
     const bool drop = b->mc && b->dropout_p > 0.0f && m->dims.num_layers > 1;
     ApeJournalEntry je{};
-    je.kind = ApeJournalEntry::STEP; je.out0 = msg_dev; je.out1 = tail_dev; je.flags = flags | (packed ? APE_FLAG_PACKED_MSG : 0u);
+    je.kind = ApeJournalEntry::STEP; je.out0 = msg_dev; je.out1 = tail_dev; je.flags = flags | (packed ? APE_FLAG_PACKED_MSG : 0u) | (spread ? APE_FLAG_SPREAD : 0u);
     je.i2 = out_dtype; je.stream = stream; je.bank = b; je.bank_frames = b->frames; je.bank_steps = b->steps; je.bank_mc_calls = b->mc_calls;
     // measurement aid (ape_streams_profile): a pair of events around every launch of the step's dominant kernel
     auto prof_pair = [&](hipEvent_t* a, hipEvent_t* z) {
@@ -2156,7 +2178,9 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         ++b->mc_calls;
     }
     StreamPostParams q = post_params();
-    hipError_t e = ape_launch_stream_post(q, (hipStream_t)stream, b->bodies.dev);      // (table mode: row s for stream s, q.body unread)
+    b->last_post_form = ape_stream_post_form(q, q.part != nullptr && (!spread || b->post_spread != nullptr));
+    hipError_t e = spread ? ape_launch_stream_post_spread(q, SpreadArgs{b->post_spread}, b->last_post_form, (hipStream_t)stream, b->bodies.dev)
+                          : ape_launch_stream_post(q, (hipStream_t)stream, b->bodies.dev);      // (table mode: row s for stream s, q.body unread)
     if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step launch failed: %s", hipGetErrorString(e));
     ++b->steps;
     journal_add(m, je);
@@ -2180,14 +2204,16 @@ int ape_streams_frame_host(ape_streams_t* b, int32_t kind, const float* rows_hos
     if (!b || !rows_host || !out_host) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: NULL argument");
     if (b->per_stream) return fail(APE_ERR_NOT_READY, "streams_frame_host: the bank is in per-stream mode (subset frames); ape_streams_reset first");
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: unknown dtype selector");
-    if (flags & ~(uint32_t)APE_FLAG_NORMALIZE_INPUT) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: only NORMALIZE_INPUT is accepted");
+    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_SPREAD))
+        return fail(APE_ERR_INVALID_ARG, "streams_frame_host: only NORMALIZE_INPUT and SPREAD are accepted");
     int width, I;
     if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: unknown kind %d", kind);
     ape_model* m = b->model;
     HIP_TRY(hipSetDevice(m->dims.device));           // (the consumer thread of an estimator starts on device 0)
     const size_t N = (size_t)b->smooth * b->n_mc;
     const size_t rows_bytes = (size_t)b->S * width * sizeof(float);
-    const size_t out_bytes = (size_t)b->S * (25 + 6 * N) * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float));
+    const size_t out_bytes = (size_t)b->S * (25 + 6 * N + ((flags & APE_FLAG_SPREAD) ? APE_SPREAD_WIDTH : 0)) *
+                             (out_dtype == APE_F64 ? sizeof(double) : sizeof(float));
     if (rows_bytes > b->h_rows_bytes) {
         if (b->h_rows) { HIP_TRY(hipHostFree(b->h_rows)); b->h_rows = nullptr; b->h_rows_bytes = 0; }
         HIP_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, APE_PINNED));
@@ -2270,6 +2296,12 @@ int ape_streams_frame_host(ape_streams_t* b, int32_t kind, const float* rows_hos
     b->fs_frames += 1;
     b->fs_fallback += fell_through ? 1 : 0;
     b->fs_recovered += recovered ? 1 : 0;
+    return APE_OK;
+}
+
+int ape_streams_last_post_form(ape_streams_t* b, int32_t* form) {
+    if (!b || !form) return fail(APE_ERR_INVALID_ARG, "streams_last_post_form: NULL argument");
+    *form = b->last_post_form;
     return APE_OK;
 }
 
@@ -2383,7 +2415,11 @@ static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_
     q.smooth = b->smooth; q.n_mc = b->n_mc;
     q.msg_dtype = out_dtype; q.packed = packed ? 1 : 0;
     q.part = b->post_part; q.part_cnt = b->post_cnt;     // (sized for S >= K entries)
-    hipError_t e = ape_launch_stream_post_subset(q, b->sub_desc, (hipStream_t)stream, b->bodies.dev);
+    b->last_post_form = ape_stream_post_form(q, q.part != nullptr && (!(flags & APE_FLAG_SPREAD) || b->post_spread != nullptr));
+    hipError_t e = (flags & APE_FLAG_SPREAD)
+                       ? ape_launch_stream_post_subset_spread(q, b->sub_desc, SpreadArgs{b->post_spread}, b->last_post_form, (hipStream_t)stream,
+                                                              b->bodies.dev)
+                       : ape_launch_stream_post_subset(q, b->sub_desc, (hipStream_t)stream, b->bodies.dev);
     if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset: post-filter launch failed: %s", hipGetErrorString(e));
     return APE_OK;
 }
@@ -2399,8 +2435,8 @@ int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_d
     if (I != m->dims.input_size)
         return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: kind %d builds %d features, the model takes %d", kind & ~APE_PARSE_BIG_ENDIAN, I,
                     m->dims.input_size);
-    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG))
-        return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: only NORMALIZE_INPUT and PACKED_MSG are accepted");
+    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG | APE_FLAG_SPREAD))
+        return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: only NORMALIZE_INPUT, PACKED_MSG and SPREAD are accepted");
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: unknown dtype selector");
     if (!b->xring || !b->yring || (m->dims.model_kind == APE_MODEL_FF && !b->ffhid))
         return fail(APE_ERR_NOT_READY, "streams_frame_subset: the bank lost its rings in a failed ape_streams_set_mc");
@@ -2647,8 +2683,8 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
         return fail(APE_ERR_INVALID_ARG, "replay: n_mc=%d with smooth=%d (1 <= smooth*n_mc <= 4096)", n_mc, smooth);
     if ((long long)F * n_mc >= (1ll << 31)) return fail(APE_ERR_UNSUPPORTED, "replay: F*n_mc = %lld sample rows (< 2^31)", (long long)F * n_mc);
     if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return fail(APE_ERR_INVALID_ARG, "replay: dropout_p %g outside [0,1)", (double)dropout_p);
-    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG))
-        return fail(APE_ERR_INVALID_ARG, "replay: only NORMALIZE_INPUT and PACKED_MSG are accepted");
+    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG | APE_FLAG_SPREAD))
+        return fail(APE_ERR_INVALID_ARG, "replay: only NORMALIZE_INPUT, PACKED_MSG and SPREAD are accepted");
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "replay: unknown dtype selector");
     if (max_rows_per_launch < 0 || (max_rows_per_launch > 0 && max_rows_per_launch < 16))
         return fail(APE_ERR_INVALID_ARG, "replay: max_rows_per_launch=%d (0 = default, else >= 16)", max_rows_per_launch);
@@ -2689,7 +2725,8 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
     const int N = smooth * n_mc;
     const long long total = (long long)F * n_mc;
     const bool tail = (flags & APE_FLAG_PACKED_MSG) && N > 1;
-    const long long out_stride = tail ? 25 + 6ll * N : 25;
+    const bool spread = (flags & APE_FLAG_SPREAD) != 0;     // the record in the last APE_SPREAD_WIDTH columns of every row
+    const long long out_stride = (tail ? 25 + 6ll * N : 25) + (spread ? APE_SPREAD_WIDTH : 0);
     // sample rows per chunk: a multiple of 16 (the cluster kernels' row base), the window image bounded
     long long rmax = max_rows_per_launch > 0 ? max_rows_per_launch : APE_REPLAY_WINDOW_BYTES / ((long long)T * I * sizeof(float));
     rmax = rmax / 16 * 16;
@@ -2787,7 +2824,7 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
             mp.f_lo = r0 / n_mc; mp.f_hi = (r0 + rows) / n_mc;
             memcpy(mp.body, m->body, sizeof(mp.body));
             mp.W = W; mp.layout = m->dims.target_layout; mp.smooth = smooth; mp.n_mc = n_mc; mp.out_dtype = out_dtype;
-            e = ape_launch_replay_msg(mp, tail, st, bodies_d, bodies_d ? rec_of : nullptr, cin);
+            e = ape_launch_replay_msg(mp, tail, st, bodies_d, bodies_d ? rec_of : nullptr, cin, spread);
             if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: message launch failed: %s", hipGetErrorString(e));
             prev_rows = rows;
         }

@@ -254,6 +254,20 @@ struct StreamPostParams {
 // 64-row chunks of a stack of N rows in the split form: rows 0 .. 63, then 63 per chunk (lane 63 repeats row 0)
 static inline int ape_stream_post_chunks(int N) { return N <= 64 ? 1 : 1 + (N - 64 + 62) / 63; }
 
+// APE_FLAG_SPREAD forms of the post-filter (stream_post_device.h, SPR): what they need beyond StreamPostParams, as a kernel argument of
+// their own -- the struct above and with it the other forms' object code stay what they were
+struct SpreadArgs {
+    double* part;        // split form: [S][chunks][4 role waves][18] partial spread sums beside p.part, or nullptr
+};
+
+// the form the post-filter's launchers pick for a frame: 0 = wide (lanes = streams), 1 = one workgroup per stream, c > 1 = split over c
+// workgroups per stream (have_part: the bank holds the split form's workspaces)
+static inline int ape_stream_post_form(const StreamPostParams& p, bool have_part) {
+    if (p.smooth == 1 && p.n_mc == 1 && p.S >= 8) return 0;
+    const int chunks = ape_stream_post_chunks(p.smooth * p.n_mc);
+    return (have_part && chunks > 1) ? chunks : 1;
+}
+
 struct MsgParams {
     const double* est;   // [N,W]
     double* msg;         // [25]
@@ -466,6 +480,11 @@ hipError_t ape_launch_ring_write(const float* xx, int N, int I, float* out, size
                                  size_t rep_stride, hipStream_t stream);
 // bodies: nullptr (every stream p.body) or the bank's device table [S,9] of per-stream body measurements
 hipError_t ape_launch_stream_post(const StreamPostParams& p, hipStream_t stream, const double* bodies = nullptr);
+// ... with APE_FLAG_SPREAD: p.msg rows are APE_SPREAD_WIDTH columns longer and end in the spread record (the SPR instantiations)
+// (form: ape_stream_post_form's answer, which the caller keeps for ape_streams_last_post_form -- what is reported is what was launched)
+hipError_t ape_launch_stream_post_spread(const StreamPostParams& p, const SpreadArgs& sp, int form, hipStream_t stream, const double* bodies = nullptr);
+// stand-alone: est [N,W] f64 + msg [25] f64 -> spread [APE_SPREAD_WIDTH] f64 (ape_spread_reduce)
+hipError_t ape_launch_spread_reduce(const MsgParams& p, const double* msg, double* spread, hipStream_t stream);
 hipError_t ape_launch_mlp_tile16(int H, const MlpParams& p, hipStream_t stream, int n_cus = 0);
 hipError_t ape_prepare_mlp_tile16(int H);     // per device: dynamic-LDS limits of the MLP and head-rows kernels (from ape_model_create)
 // two-stage weight-stationary pipeline for chip-filling eval batches of the 2-hidden-layer MLP (mlp_pipe.hip)
@@ -485,7 +504,7 @@ hipError_t ape_launch_replay_segments(const int* starts, int n_starts, int F, in
 hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t stream, const ReplayCarryParams* carry = nullptr);
 // bodies / rec_of: nullptr (p.body for every frame) or [R,9] values and [F] recording indices
 hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream, const double* bodies = nullptr,
-                                 const int* rec_of = nullptr, const ReplayCarryParams* carry = nullptr);
+                                 const int* rec_of = nullptr, const ReplayCarryParams* carry = nullptr, bool spread = false);
 // the stacks of R records -> contiguous rows [R * smooth * n_mc, O] (the input of the carried rows' FK launch)
 hipError_t ape_launch_replay_carry_rows(const float* state_in, int R, int words, int x_words, int stack_words, float* y_in, hipStream_t stream);
 hipError_t ape_launch_replay_state_out(const ReplayStateOutParams& p, hipStream_t stream);
@@ -500,3 +519,5 @@ hipError_t ape_launch_ring_windows(const float* xring, float* xw, int S, int T, 
 // the bank's post-filter over a list: p.S = K entries, y_new / msg in list order, stack slot and cold flag of entry j from desc[j]
 // (bodies: as ape_launch_stream_post -- indexed by desc[j].stream)
 hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const SubsetDesc* desc, hipStream_t stream, const double* bodies = nullptr);
+hipError_t ape_launch_stream_post_subset_spread(const StreamPostParams& p, const SubsetDesc* desc, const SpreadArgs& sp, int form, hipStream_t stream,
+                                                const double* bodies = nullptr);

@@ -130,6 +130,8 @@ struct ape_streams {
     float* y_new = nullptr;      // [S,n_mc,O]
     double* post_part = nullptr; // split post-filter (stream_post_device.h): [S][chunks][21] partial sums + [S] tickets behind them, or
     unsigned* post_cnt = nullptr; //   nullptr where every stream keeps a workgroup of its own (many streams, or stacks of <= 64 rows)
+    int last_post_form = -1;     // ape_streams_last_post_form: -1 no frame yet, 0 wide, 1 one workgroup per stream, c > 1 split over c
+    double* post_spread = nullptr; // ... and, in the same allocation, [S][chunks][72] partial spread sums (APE_FLAG_SPREAD frames)
     // shared-layer-0 route on the weight-stationary upper-layer kernel (lstm_upper32.hip): the sample rows go through it in
     // chunks of `chunk_rows` (a multiple of 32), each expand -> LSTM -> head reduce over the two workspaces below
     bool up32 = false;

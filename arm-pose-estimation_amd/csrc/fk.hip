@@ -200,6 +200,44 @@ __global__ __launch_bounds__(256) void ape_msg_kernel(const MsgParams p) {
     finish_msg(p.layout, N, out_q, orig_mean, p.est, p.body, p.msg);
 }
 
+// ---- spread record: N est rows + their message -> APE_SPREAD_WIDTH doubles (ape_spread_reduce) ----------------------------------
+// The sibling of ape_msg_kernel for the record of include/ape_hip.h (no reference counterpart: the reference ships the rows'
+// est[:, :6] themselves, estimator.py:131-137).  A thread's rows in order (tid, tid + 256, ...), then the block tree; the same
+// sums and closing arithmetic as the post-filter's SPR forms (stream_post_device.h).
+__global__ __launch_bounds__(256) void ape_spread_kernel(const MsgParams p, const double* __restrict__ msg, double* __restrict__ spread) {
+    __shared__ double scratch[4];
+    const int tid = threadIdx.x;
+    const int W = p.W, N = p.N;
+    const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
+    const int nq = hips ? 3 : 2;
+    const int qc[3] = {hips ? 9 : 6, hips ? 13 : 10, 17};
+    if (N == 1) {                                          // by rule: the row's origins, zeros
+        if (tid < APE_SPREAD_WIDTH) spread[tid] = spread_single(p.est, tid);
+        return;
+    }
+    double pos[18] = {}, qq[3][10] = {};
+    for (int i = tid; i < N; i += 256) {
+        const double* e = p.est + (size_t)i * W;
+        spread_add_pos(pos, e); spread_add_pos(pos + 9, e + 3);
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k < nq) spread_add_quat(qq[k], e + qc[k]);
+    }
+#pragma unroll
+    for (int c = 0; c < 18; ++c) pos[c] = block_sum(pos[c], scratch);
+#pragma unroll
+    for (int k = 0; k < 3; ++k)
+#pragma unroll
+        for (int c = 0; c < 10; ++c) qq[k][c] = block_sum(qq[k][c], scratch);
+    if (tid != 0) return;
+    double out[APE_SPREAD_WIDTH];
+    spread_pos_out(pos, N, out); spread_pos_out(pos + 9, N, out + 9);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) out[18 + k] = k < nq ? spread_angle_out(qq[k], N, msg + 7 + 7 * k) : 0.0;
+#pragma unroll
+    for (int c = 0; c < APE_SPREAD_WIDTH; ++c) spread[c] = out[c];
+}
+
 // ---- stream bank: per stream, the smoothing stack + FK + message of one frame ---------------------
 // Replaces, for S streams at once, the tail of Estimator.add_xx_to_row_hist_and_make_prediction
 // (estimator.py:108-118: de-normalise, push onto the smoothing history -- padded with the newest prediction on a
@@ -235,6 +273,36 @@ __global__ __launch_bounds__(256) void ape_stream_post_wide_bodies_kernel(const 
     stream_post_wide<TMsg, false, true>(p, (int)blockIdx.x * 64, nullptr, bodies);
 }
 
+// ... and the three forms with the spread record behind every message row (stream_post_device.h, SPR; TAB: the bank's body table)
+template <typename TMsg, bool TAB>
+__global__ __launch_bounds__(256) void ape_stream_post_spread_kernel(const StreamPostParams p, const double* bodies, const SpreadArgs sp) {
+    stream_post<TMsg, false, false, TAB, true>(p, (int)blockIdx.x, 0, 1, nullptr, bodies, sp);
+}
+template <typename TMsg, bool TAB>
+__global__ __launch_bounds__(256) void ape_stream_post_split_spread_kernel(const StreamPostParams p, const int chunks, const double* bodies,
+                                                                           const SpreadArgs sp) {
+    stream_post<TMsg, true, false, TAB, true>(p, (int)blockIdx.x / chunks, (int)blockIdx.x % chunks, chunks, nullptr, bodies, sp);
+}
+template <typename TMsg, bool TAB>
+__global__ __launch_bounds__(256) void ape_stream_post_wide_spread_kernel(const StreamPostParams p, const double* bodies) {
+    stream_post_wide<TMsg, false, TAB, true>(p, (int)blockIdx.x * 64, nullptr, bodies);
+}
+
+template <typename TMsg, bool TAB>
+hipError_t launch_stream_post_spread(const StreamPostParams& p, const SpreadArgs& sp, int form, const double* bodies, hipStream_t stream) {
+    if (form == 0) {
+        hipLaunchKernelGGL((ape_stream_post_wide_spread_kernel<TMsg, TAB>), dim3((p.S + 63) / 64), dim3(256), 0, stream, p, bodies);
+        return hipGetLastError();
+    }
+    const int chunks = form;
+    if (chunks > 1) {
+        hipLaunchKernelGGL((ape_stream_post_split_spread_kernel<TMsg, TAB>), dim3(p.S * chunks), dim3(256), 0, stream, p, chunks, bodies, sp);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((ape_stream_post_spread_kernel<TMsg, TAB>), dim3(p.S), dim3(256), 0, stream, p, bodies, sp);
+    return hipGetLastError();
+}
+
 template <typename TIn, typename TOut>
 hipError_t launch_fk(const FkParams& p, hipStream_t stream) {
     hipLaunchKernelGGL((ape_fk3_kernel<TIn, TOut, false>), dim3((p.N + FK3_ROWS - 1) / FK3_ROWS), dim3(128), 0, stream, p, FkBodyRows{});
@@ -259,6 +327,21 @@ hipError_t ape_launch_fk(const FkParams& p, int preds_dtype, int est_dtype, hipS
 hipError_t ape_launch_msg_reduce(const MsgParams& p, hipStream_t stream) {
     hipLaunchKernelGGL(ape_msg_kernel, dim3(1), dim3(256), 0, stream, p);
     return hipGetLastError();
+}
+
+hipError_t ape_launch_spread_reduce(const MsgParams& p, const double* msg, double* spread, hipStream_t stream) {
+    hipLaunchKernelGGL(ape_spread_kernel, dim3(1), dim3(256), 0, stream, p, msg, spread);
+    return hipGetLastError();
+}
+
+// the same choice of form as ape_launch_stream_post below, on the SPR instantiations
+hipError_t ape_launch_stream_post_spread(const StreamPostParams& p, const SpreadArgs& sp, int form, hipStream_t stream, const double* bodies) {
+    if (form > 1 && (p.part == nullptr || sp.part == nullptr)) return hipErrorInvalidValue;
+    if (bodies != nullptr)
+        return p.msg_dtype == APE_F32 ? launch_stream_post_spread<float, true>(p, sp, form, bodies, stream)
+                                      : launch_stream_post_spread<double, true>(p, sp, form, bodies, stream);
+    return p.msg_dtype == APE_F32 ? launch_stream_post_spread<float, false>(p, sp, form, nullptr, stream)
+                                  : launch_stream_post_spread<double, false>(p, sp, form, nullptr, stream);
 }
 
 // the same choice of form with the table-reading instantiations

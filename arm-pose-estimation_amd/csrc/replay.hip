@@ -77,7 +77,10 @@ __global__ __launch_bounds__(256) void ape_replay_window_kernel(const ReplayWind
 // TAB: the frame's body is row rec_of[f] of bodies [R,9] (neighbouring lanes mostly share it), else the uniform p.body
 // CARRY (ape_replay_resume): a stack row before the recording's first frame is the matching est row of the stack the recording came in
 // with (c.est_in, counted back from its newest); a recording whose stack bit is clear is clamped as without carry
-template <typename TMsg, bool TAB = false, bool CARRY = false>
+// SPR (APE_FLAG_SPREAD): the frame's spread record (include/ape_hip.h, APE_SPREAD_WIDTH) in the last columns of its row, fused here
+// rather than a kernel of its own: the lane holds the message's float64 quaternions and the row accessor (CARRY included).  One more
+// pass over row(0 .. N-1) in order, so a recording replayed in pieces gives the bits of the one call.
+template <typename TMsg, bool TAB = false, bool CARRY = false, bool SPR = false>
 __global__ __launch_bounds__(256) void ape_replay_msg_kernel(const ReplayMsgParams p, const double* __restrict__ bodies,
                                                              const int* __restrict__ rec_of, const ReplayCarryParams c) {
     const long long f = p.f_lo + (long long)blockIdx.x * 256 + threadIdx.x;
@@ -133,6 +136,31 @@ __global__ __launch_bounds__(256) void ape_replay_msg_kernel(const ReplayMsgPara
     TMsg* dst = static_cast<TMsg*>(p.out) + f * p.out_stride;
 #pragma unroll
     for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
+    if constexpr (SPR) {
+        TMsg* sd = dst + (p.out_stride - APE_SPREAD_WIDTH);
+        if (N == 1) {
+#pragma unroll
+            for (int c = 0; c < APE_SPREAD_WIDTH; ++c) sd[c] = (TMsg)spread_single(e0, c);
+            return;
+        }
+        const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
+        const int nq = hips ? 3 : 2;
+        const int qc[3] = {hips ? 9 : 6, hips ? 13 : 10, 17};
+        double pos[18] = {}, qq[3][10] = {};
+        for (int i = 0; i < N; ++i) {
+            const double* e = row(i);
+            spread_add_pos(pos, e); spread_add_pos(pos + 9, e + 3);
+#pragma unroll
+            for (int k = 0; k < 3; ++k)
+                if (k < nq) spread_add_quat(qq[k], e + qc[k]);
+        }
+        double out[APE_SPREAD_WIDTH];
+        spread_pos_out(pos, N, out); spread_pos_out(pos + 9, N, out + 9);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) out[18 + k] = k < nq ? spread_angle_out(qq[k], N, m + 7 + 7 * k) : 0.0;
+#pragma unroll
+        for (int c = 0; c < APE_SPREAD_WIDTH; ++c) sd[c] = (TMsg)out[c];
+    }
 }
 
 
@@ -225,24 +253,27 @@ hipError_t ape_launch_replay_windows(const ReplayWindowParams& p, hipStream_t st
     return hipGetLastError();
 }
 
-// one instantiation per (dtype, per-recording bodies, carry)
-template <typename TMsg>
+// one instantiation per (dtype, per-recording bodies, carry, spread)
+template <typename TMsg, bool SPR>
 static void launch_replay_msg_typed(const ReplayMsgParams& p, unsigned blocks, hipStream_t stream, const double* bodies, const int* rec_of,
                                     const ReplayCarryParams* carry) {
     const ReplayCarryParams none{};
     if (carry != nullptr) {
-        if (bodies != nullptr) hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, true, true>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, *carry);
-        else hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, false, true>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, *carry);
-    } else if (bodies != nullptr) hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, true, false>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, none);
-    else hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, false, false>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, none);
+        if (bodies != nullptr) hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, true, true, SPR>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, *carry);
+        else hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, false, true, SPR>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, *carry);
+    } else if (bodies != nullptr) hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, true, false, SPR>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, none);
+    else hipLaunchKernelGGL((ape_replay_msg_kernel<TMsg, false, false, SPR>), dim3(blocks), dim3(256), 0, stream, p, bodies, rec_of, none);
 }
 
 hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_t stream, const double* bodies, const int* rec_of,
-                                 const ReplayCarryParams* carry) {
+                                 const ReplayCarryParams* carry, bool spread) {
     const long long frames = p.f_hi - p.f_lo;
     if (frames <= 0) return hipSuccess;
-    if (p.out_dtype == APE_F32) launch_replay_msg_typed<float>(p, blocks_for(frames), stream, bodies, rec_of, carry);
-    else launch_replay_msg_typed<double>(p, blocks_for(frames), stream, bodies, rec_of, carry);
+    if (spread) {                                      // (p.out_stride counts the record's columns: they are the row's last)
+        if (p.out_dtype == APE_F32) launch_replay_msg_typed<float, true>(p, blocks_for(frames), stream, bodies, rec_of, carry);
+        else launch_replay_msg_typed<double, true>(p, blocks_for(frames), stream, bodies, rec_of, carry);
+    } else if (p.out_dtype == APE_F32) launch_replay_msg_typed<float, false>(p, blocks_for(frames), stream, bodies, rec_of, carry);
+    else launch_replay_msg_typed<double, false>(p, blocks_for(frames), stream, bodies, rec_of, carry);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || !tail) return e;
     const long long n = frames * p.smooth * p.n_mc;

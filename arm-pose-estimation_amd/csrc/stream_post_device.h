@@ -66,6 +66,46 @@ __device__ __forceinline__ double wave_sum(double v) {
     return __shfl(v, 0, 64);
 }
 
+// ---- the Monte-Carlo spread record (include/ape_hip.h, APE_SPREAD_WIDTH) ------------------------------------------
+// One pass over the stacked rows: per origin 3 first and 6 second moments, per joint the 10 sums of q q^T (upper triangle: ww wx wy wz
+// xx xy xz yy yz zz).  The reference has no counterpart: it ships est[i, :6] of every row instead (estimator.py:131-137).
+__device__ __forceinline__ void spread_add_pos(double* t, const double* v) {
+#pragma clang fp contract(off)
+    t[0] += v[0]; t[1] += v[1]; t[2] += v[2];
+    t[3] += v[0] * v[0]; t[4] += v[0] * v[1]; t[5] += v[0] * v[2];
+    t[6] += v[1] * v[1]; t[7] += v[1] * v[2]; t[8] += v[2] * v[2];
+}
+__device__ __forceinline__ void spread_add_quat(double* t, const double* q) {
+#pragma clang fp contract(off)
+    t[0] += q[0] * q[0]; t[1] += q[0] * q[1]; t[2] += q[0] * q[2]; t[3] += q[0] * q[3];
+    t[4] += q[1] * q[1]; t[5] += q[1] * q[2]; t[6] += q[1] * q[3];
+    t[7] += q[2] * q[2]; t[8] += q[2] * q[3]; t[9] += q[3] * q[3];
+}
+// nine sums -> mean (3) and population covariance (6: xx xy xz yy yz zz) = mean of products - product of means
+__device__ __forceinline__ void spread_pos_out(const double* t, int N, double* o) {
+#pragma clang fp contract(off)
+    const double n = (double)N;
+    const double mx = t[0] / n, my = t[1] / n, mz = t[2] / n;
+    o[0] = mx; o[1] = my; o[2] = mz;
+    o[3] = t[3] / n - mx * mx; o[4] = t[4] / n - mx * my; o[5] = t[5] / n - mx * mz;
+    o[6] = t[6] / n - my * my; o[7] = t[7] / n - my * mz; o[8] = t[8] / n - mz * mz;
+}
+// ten sums and the message's quaternion qm -> 2 asin(sqrt(1 - qm^T (sum q q^T / N) qm)); the clamp to [0, 1] by comparisons, which let a
+// NaN through as numpy.clip does (fmax / fmin would not)
+__device__ __forceinline__ double spread_angle_out(const double* t, int N, const double* qm) {
+#pragma clang fp contract(off)
+    const double w = qm[0], x = qm[1], y = qm[2], z = qm[3];
+    const double diag = t[0] * (w * w) + t[4] * (x * x) + t[7] * (y * y) + t[9] * (z * z);
+    const double off = t[1] * (w * x) + t[2] * (w * y) + t[3] * (w * z) + t[5] * (x * y) + t[6] * (x * z) + t[8] * (y * z);
+    double a = 1.0 - (diag + 2.0 * off) / (double)N;
+    a = a < 0.0 ? 0.0 : (a > 1.0 ? 1.0 : a);
+    return 2.0 * asin(sqrt(a));
+}
+// the record of a single row: its two origins, zeros by rule
+__device__ __forceinline__ double spread_single(const double* e0, int c) {
+    return c < 3 ? e0[c] : ((c >= 9 && c < 12) ? e0[c - 6] : 0.0);
+}
+
 // One workgroup per stream, a wave per chain (as ape_fk3_kernel: one wave computing a whole row is a chain of ~1400 f64
 // instructions): wave 0 the lower arm's 6D -> quaternion chain, its rotated bone and its quaternion mean, wave 1 the upper arm's,
 // wave 2 the hips' and the shoulder origin, wave 3 the copy into the ring, the columns that pass through and -- behind a barrier
@@ -86,9 +126,15 @@ __device__ __forceinline__ double wave_sum(double v) {
 // TAB (per-stream bodies): the nine body values (Estimator.body_measurements, estimator.py:57-68) are row `stream` of
 // `bodies` [S,9] -- uniform over the workgroup, indexed by the STREAM (d[s].stream in a subset frame), never by the list position --
 // instead of the uniform p.body; chosen where the values are read, so that the other forms' object code stays what it was.
-template <typename TMsg, bool SPLIT, bool IDX = false, bool TAB = false>
+// SPR (APE_FLAG_SPREAD): every message row is APE_SPREAD_WIDTH columns longer and ends in the spread record.  Beside acc / osum every
+// role wave keeps 18 sums over its act rows (lane 63's repeated row 0 of a later chunk is no act row): role 3 the moments of the
+// two origins it holds in e6, roles 0 .. 2 the ten sums of q q^T of their joint (8 unused).  Reduced like the others -- a lane's rows in
+// order, the wave tree, SPLIT: the chunks in order through sp.part, a buffer of its own beside p.part.  Lane 0 of a quaternion role
+// holds qm the moment it has normalised it.  A parameter of the template and an argument of its own: StreamPostParams and the other
+// forms' object code stay what they were.
+template <typename TMsg, bool SPLIT, bool IDX = false, bool TAB = false, bool SPR = false>
 __device__ inline void stream_post(const StreamPostParams& p, const int s, const int chunk, const int C, const SubsetDesc* d = nullptr,
-                                   const double* __restrict__ bodies = nullptr) {
+                                   const double* __restrict__ bodies = nullptr, const SpreadArgs sp = SpreadArgs{}) {
 #pragma clang fp contract(off)
 
     __shared__ double rot[64][3][3];                        // per row of a 64-row chunk: rotated lower-arm bone, upper-arm bone, shoulder origin
@@ -97,6 +143,7 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
     __shared__ double outq_s[3][4];
     __shared__ double omean_s[9];
     __shared__ int last_s;
+    __shared__ double spr_s[SPR ? APE_SPREAD_WIDTH : 1];    // SPR: the record (unused otherwise)
     const int lane = threadIdx.x & 63, role = threadIdx.x >> 6;
     const int M = p.n_mc, N = p.smooth * M, O = p.O;
     const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
@@ -108,6 +155,11 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
     const double* const body = TAB ? bodies + 9 * (size_t)(IDX ? d[s].stream : s) : p.body;
     double acc[4] = {0, 0, 0, 0};
     double osum[6] = {0, 0, 0, 0, 0, 0};
+    double ss[18] = {};                                     // SPR: the role's spread sums
+    const size_t spr_off = SPR ? (size_t)s * APE_SPREAD_WIDTH : 0;     // SPR: the rows before this one are that much longer
+    if constexpr (SPR) {
+        if (threadIdx.x < APE_SPREAD_WIDTH) spr_s[threadIdx.x] = 0.0;
+    }
     if (threadIdx.x < 21) e0_s[threadIdx.x] = 0.0;
     if (threadIdx.x < 12) { outq_s[threadIdx.x >> 2][threadIdx.x & 3] = 0.0; ref_s[threadIdx.x >> 2][threadIdx.x & 3] = 0.0; }
     if (threadIdx.x < 9) omean_s[threadIdx.x] = 0.0;
@@ -184,6 +236,9 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
             const double d = fma(q[3], r3, fma(q[2], r2, fma(q[1], r1, q[0] * r0)));   // the sign rule of ape_msg_kernel
             const double sg = !act ? 0.0 : ((i > 0 && d < 0.0) ? -wgt : wgt);
             acc[0] += q[0] * sg; acc[1] += q[1] * sg; acc[2] += q[2] * sg; acc[3] += q[3] * sg;
+            if constexpr (SPR) {
+                if (act) spread_add_quat(ss, q);
+            }
         }
         if (role == 3 && act) {
             double e6[6];
@@ -203,8 +258,9 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
 #pragma unroll
                 for (int c = 0; c < 6; ++c) e0_s[c] = e6[c];
             }
+            if constexpr (SPR) { spread_add_pos(ss, e6); spread_add_pos(ss + 9, e6 + 3); }
             if (p.tail || p.packed) {                       // estimator.py:131-137: est[i, :6] of every row
-                TMsg* t = p.packed ? static_cast<TMsg*>(p.msg) + (size_t)s * (25 + 6 * N) + 25 + (size_t)i * 6
+                TMsg* t = p.packed ? static_cast<TMsg*>(p.msg) + (size_t)s * (25 + 6 * N) + spr_off + 25 + (size_t)i * 6
                                    : static_cast<TMsg*>(p.tail) + ((size_t)s * N + i) * 6;
 #pragma unroll
                 for (int c = 0; c < 6; ++c) t[c] = (TMsg)e6[c];
@@ -219,12 +275,23 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
         const int n_o = (role == 2) ? 3 : 6, o0 = (role == 2) ? 6 : 0;
         if (full && role >= 2)                              // compose_msg.py:26-29: plain means of the three origins
             for (int c = 0; c < n_o; ++c) om[c] = wave_sum(osum[c]);
+        if constexpr (SPR) {
+#pragma unroll
+            for (int c = 0; c < 18; ++c) ss[c] = wave_sum(ss[c]);
+        }
         if constexpr (SPLIT) {
             // partial sums out, release, ticket; the last chunk to arrive acquires and adds them in chunk order
             double* mine = p.part + ((size_t)s * C + chunk) * 21;
             if (lane == 0 && role < nq) { mine[role * 4] = a0; mine[role * 4 + 1] = a1; mine[role * 4 + 2] = a2; mine[role * 4 + 3] = a3; }
             if (lane == 0 && full && role >= 2)
                 for (int c = 0; c < n_o; ++c) mine[12 + o0 + c] = om[c];
+            if constexpr (SPR) {
+                if (lane == 0) {
+                    double* mine2 = sp.part + (((size_t)s * C + chunk) * 4 + role) * 18;
+#pragma unroll
+                    for (int c = 0; c < 18; ++c) mine2[c] = ss[c];
+                }
+            }
             if (p.done_out != nullptr) __threadfence_system();      // (this chunk's tail rows may sit in host memory: out before the ticket)
             else __threadfence();
             __syncthreads();
@@ -249,15 +316,40 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
                     om[k] = 0;
                     for (int c = 0; c < C; ++c) om[k] += all[c * 21 + 12 + o0 + k];
                 }
+            if constexpr (SPR) {
+                if (lane == 0) {
+                    const double* all2 = sp.part + ((size_t)s * C * 4 + role) * 18;
+#pragma unroll
+                    for (int k = 0; k < 18; ++k) {
+                        ss[k] = 0;
+                        for (int c = 0; c < C; ++c) ss[k] += all2[(size_t)c * 72 + k];
+                    }
+                }
+            }
         }
         if (lane == 0 && role < nq) {
             const double nrm = sqrt(a0 * a0 + a1 * a1 + a2 * a2 + a3 * a3);
             outq_s[role][0] = a0 / nrm; outq_s[role][1] = a1 / nrm; outq_s[role][2] = a2 / nrm; outq_s[role][3] = a3 / nrm;
+            if constexpr (SPR) {
+                const double qm[4] = {a0 / nrm, a1 / nrm, a2 / nrm, a3 / nrm};
+                spr_s[18 + role] = spread_angle_out(ss, N, qm);
+            }
         }
         if (lane == 0 && full && role >= 2)
             for (int c = 0; c < n_o; ++c) omean_s[o0 + c] = om[c] / (double)N;
+        if constexpr (SPR) {
+            if (lane == 0 && role == 3) { spread_pos_out(ss, N, spr_s); spread_pos_out(ss + 9, N, spr_s + 9); }
+        }
     }
     __syncthreads();
+    if constexpr (SPR) {                                    // wave 1 writes the record while thread 0 composes the message
+        if (threadIdx.x >= 64 && threadIdx.x < 64 + APE_SPREAD_WIDTH) {
+            const int c = threadIdx.x - 64;
+            const double v = N == 1 ? spread_single(e0_s, c) : spr_s[c];
+            TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 25 + 6 * N : 25) + spr_off + (p.packed ? 25 + 6 * N : 25);
+            dst[c] = (TMsg)v;
+        }
+    }
     if (threadIdx.x == 0) {
     double out_q[3][4], orig_mean[9], e0[21], m[25];
 #pragma unroll
@@ -269,7 +361,7 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
 #pragma unroll
     for (int c = 0; c < 21; ++c) e0[c] = e0_s[c];
     finish_msg(p.layout, N, out_q, orig_mean, e0, body, m);
-    TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 25 + 6 * N : 25);
+    TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 25 + 6 * N : 25) + spr_off;
 #pragma unroll
     for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
     }
@@ -286,7 +378,8 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
 // issue slots (13.6 us at 1024 streams against 6 us for one stream).  Same device functions in the same order: bit-identical outputs.
 // IDX: lane = list position (targets, message row), the stream's one ring slot from d
 // TAB: every lane its own stream's row of `bodies` [S,9] (64 neighbouring rows = 4.5 KB of whole cache lines per workgroup)
-template <typename TMsg, bool IDX = false, bool TAB = false>
+// SPR: every lane the trivial record of its one row behind its message (rows APE_SPREAD_WIDTH columns longer)
+template <typename TMsg, bool IDX = false, bool TAB = false, bool SPR = false>
 __device__ inline void stream_post_wide(const StreamPostParams& p, const int s0, const SubsetDesc* d = nullptr,
                                         const double* __restrict__ bodies = nullptr) {
 #pragma clang fp contract(off)
@@ -296,6 +389,7 @@ __device__ inline void stream_post_wide(const StreamPostParams& p, const int s0,
     const int lane = threadIdx.x & 63, role = threadIdx.x >> 6;
     const int s = s0 + lane, O = p.O;
     const bool act = s < p.S;
+    const size_t spr_off = SPR ? (size_t)s * APE_SPREAD_WIDTH : 0;
     const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
     const bool full = p.layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS;
     const int qc[3] = {hips ? 9 : 6, hips ? 13 : 10, 17};
@@ -355,7 +449,7 @@ __device__ inline void stream_post_wide(const StreamPostParams& p, const int s0,
 #pragma unroll
         for (int c = 0; c < 6; ++c) e0w[lane][c] = e6[c];
         if (p.tail || p.packed) {
-            TMsg* t = p.packed ? static_cast<TMsg*>(p.msg) + (size_t)s * 31 + 25 : static_cast<TMsg*>(p.tail) + (size_t)s * 6;
+            TMsg* t = p.packed ? static_cast<TMsg*>(p.msg) + (size_t)s * 31 + spr_off + 25 : static_cast<TMsg*>(p.tail) + (size_t)s * 6;
 #pragma unroll
             for (int c = 0; c < 6; ++c) t[c] = (TMsg)e6[c];
         }
@@ -366,10 +460,16 @@ __device__ inline void stream_post_wide(const StreamPostParams& p, const int s0,
 #pragma unroll
         for (int c = 0; c < 21; ++c) e0[c] = e0w[lane][c];
         finish_msg(p.layout, 1, out_q, orig_mean, e0, body, m);
-        TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 31 : 25);
+        TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 31 : 25) + spr_off;
 #pragma unroll
         for (int c = 0; c < 25; ++c)
             if (c / 7 == role) dst[c] = (TMsg)m[c];
+        if constexpr (SPR) {
+            TMsg* sd = dst + (p.packed ? 31 : 25);
+#pragma unroll
+            for (int c = 0; c < APE_SPREAD_WIDTH; ++c)
+                if ((c & 3) == role) sd[c] = (TMsg)spread_single(e0, c);
+        }
     }
     if (p.done_out != nullptr) {
         __threadfence_system();

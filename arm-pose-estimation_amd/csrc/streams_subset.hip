@@ -96,6 +96,38 @@ __global__ __launch_bounds__(256) void ape_subset_post_wide_bodies_kernel(const 
     stream_post_wide<TMsg, true, true>(p, (int)blockIdx.x * 64, d, bodies);
 }
 
+// ... and with the spread record behind every message row (stream_post_device.h, SPR; TAB: the bank's body table)
+template <typename TMsg, bool TAB>
+__global__ __launch_bounds__(256) void ape_subset_post_spread_kernel(const StreamPostParams p, const SubsetDesc* d, const double* bodies,
+                                                                     const SpreadArgs sp) {
+    stream_post<TMsg, false, true, TAB, true>(p, (int)blockIdx.x, 0, 1, d, bodies, sp);
+}
+template <typename TMsg, bool TAB>
+__global__ __launch_bounds__(256) void ape_subset_post_split_spread_kernel(const StreamPostParams p, const int chunks, const SubsetDesc* d,
+                                                                           const double* bodies, const SpreadArgs sp) {
+    stream_post<TMsg, true, true, TAB, true>(p, (int)blockIdx.x / chunks, (int)blockIdx.x % chunks, chunks, d, bodies, sp);
+}
+template <typename TMsg, bool TAB>
+__global__ __launch_bounds__(256) void ape_subset_post_wide_spread_kernel(const StreamPostParams p, const SubsetDesc* d, const double* bodies) {
+    stream_post_wide<TMsg, true, TAB, true>(p, (int)blockIdx.x * 64, d, bodies);
+}
+
+template <typename TMsg, bool TAB>
+hipError_t launch_subset_post_spread(const StreamPostParams& p, const SubsetDesc* d, const SpreadArgs& sp, int form, const double* bodies,
+                                     hipStream_t stream) {
+    if (form == 0) {
+        hipLaunchKernelGGL((ape_subset_post_wide_spread_kernel<TMsg, TAB>), dim3((p.S + 63) / 64), dim3(256), 0, stream, p, d, bodies);
+        return hipGetLastError();
+    }
+    const int chunks = form;
+    if (chunks > 1) {
+        hipLaunchKernelGGL((ape_subset_post_split_spread_kernel<TMsg, TAB>), dim3(p.S * chunks), dim3(256), 0, stream, p, chunks, d, bodies, sp);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL((ape_subset_post_spread_kernel<TMsg, TAB>), dim3(p.S), dim3(256), 0, stream, p, d, bodies, sp);
+    return hipGetLastError();
+}
+
 hipError_t launch_subset_post_bodies(const StreamPostParams& p, const SubsetDesc* d, const double* bodies, hipStream_t stream) {
     if (p.smooth == 1 && p.n_mc == 1 && p.S >= 8) {
         const int wide = (p.S + 63) / 64;
@@ -120,6 +152,18 @@ hipError_t ape_launch_subset_rows(const SubsetRowsParams& p, hipStream_t stream)
     if (p.K < 1) return hipSuccess;
     hipLaunchKernelGGL(ape_subset_rows_kernel, dim3((p.K + SB_ROWS - 1) / SB_ROWS), dim3(SB_BLOCK), 0, stream, p);
     return hipGetLastError();
+}
+
+// the same choice of form on the SPR instantiations
+hipError_t ape_launch_stream_post_subset_spread(const StreamPostParams& p, const SubsetDesc* d, const SpreadArgs& sp, int form, hipStream_t stream,
+                                                const double* bodies) {
+    if (p.S < 1) return hipSuccess;
+    if (form > 1 && (p.part == nullptr || sp.part == nullptr)) return hipErrorInvalidValue;
+    if (bodies != nullptr)
+        return p.msg_dtype == APE_F32 ? launch_subset_post_spread<float, true>(p, d, sp, form, bodies, stream)
+                                      : launch_subset_post_spread<double, true>(p, d, sp, form, bodies, stream);
+    return p.msg_dtype == APE_F32 ? launch_subset_post_spread<float, false>(p, d, sp, form, nullptr, stream)
+                                  : launch_subset_post_spread<double, false>(p, d, sp, form, nullptr, stream);
 }
 
 // the same choice of form as ape_launch_stream_post (fk.hip), with p.S = the list's length

@@ -46,6 +46,9 @@ class _DeviceFrame:
         self._out = np.empty((25 + 6 * self._rows,), dtype=np.float64)
         self._row_p = C.c_void_p(self._row.ctypes.data)
         self._out_p = C.c_void_p(self._out.ctypes.data)
+        # frames with the spread record behind the message list (APE_FLAG_SPREAD): a buffer of their own
+        self._out_spread = np.empty((25 + 6 * self._rows + _hip.SPREAD_WIDTH,), dtype=np.float64)
+        self._out_spread_p = C.c_void_p(self._out_spread.ctypes.data)
 
     def __del__(self):
         bank, self._bank = getattr(self, "_bank", None), None
@@ -96,10 +99,12 @@ class _DeviceFrame:
         torch.cuda.current_stream(dev).synchronize()     # (the record is this call's own copy)
         self._per_stream = True
 
-    def _frame_subset(self) -> np.ndarray:
+    def _frame_subset(self, spread: bool = False) -> np.ndarray:
         """a frame of a bank in per-stream mode: ``ape_streams_frame_subset`` over the one stream (the host frame is lockstep-only)"""
         C, hip, dev = self._C, self._hip, self._device()
         packed = self._rows > 1
+        if spread:
+            return self._frame_subset_spread(packed)
         if getattr(self, "_sub_bufs", None) is None:         # once: the device row, the device message, pinned mirrors, the list [0]
             w = 25 + 6 * self._rows if packed else 25
             self._sub_bufs = (torch.empty((1, self._width), dtype=torch.float32, device=dev),
@@ -119,6 +124,26 @@ class _DeviceFrame:
         self._out[:out.shape[1]] = out_pin.numpy()[0]
         return self._out
 
+    def _frame_subset_spread(self, packed: bool) -> np.ndarray:
+        """``_frame_subset`` with APE_FLAG_SPREAD: the row is 21 columns longer; returned in the host frame's layout [25 + 6N + 21]"""
+        C, hip, dev = self._C, self._hip, self._device()
+        w = (25 + 6 * self._rows if packed else 25) + hip.SPREAD_WIDTH
+        if getattr(self, "_sub_bufs_spread", None) is None:
+            self._sub_bufs_spread = (torch.empty((1, self._width), dtype=torch.float32, device=dev),
+                                     torch.empty((1, w), dtype=torch.float64, device=dev), np.zeros((1,), dtype=np.int32))
+        rd, out, idx = self._sub_bufs_spread
+        rd.copy_(torch.from_numpy(self._row).reshape(1, -1))
+        hip.check(self._lib.ape_streams_frame_subset(self._bank, self._kind, C.c_void_p(rd.data_ptr()), C.c_void_p(idx.ctypes.data), 1,
+                                                     self._flags | (hip.FLAG_PACKED_MSG if packed else 0) | hip.FLAG_SPREAD,
+                                                     C.c_void_p(out.data_ptr()), hip.F64, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  "ape_streams_frame_subset")
+        self._model.recover()                            # blocking, like the host frame
+        host = out.cpu().numpy()[0]
+        self._out_spread[:] = 0.0                        # N = 1: no tail between the 25 values and the record
+        self._out_spread[:w - hip.SPREAD_WIDTH] = host[:-hip.SPREAD_WIDTH]
+        self._out_spread[-hip.SPREAD_WIDTH:] = host[-hip.SPREAD_WIDTH:]
+        return self._out_spread
+
     def frame_stats(self, reset: bool = False) -> dict:
         """where the frames' host time went (ape_streams_frame_stats, ABI 7): per-frame microseconds of the last <= 4096 frames in
         `launch` (rows into pinned staging + the launch calls), `wait` (last launch call returned -> completion words seen) and `copy`
@@ -135,12 +160,16 @@ class _DeviceFrame:
         return {"frames": int(fs.frames), "fallback_syncs": int(fs.fallback_syncs), "recovered": int(fs.recovered),
                 "launch_us": t[:, 0].copy(), "wait_us": t[:, 1].copy(), "copy_us": t[:, 2].copy()}
 
-    def frame(self, row) -> np.ndarray:
+    def frame(self, row, spread: bool = False) -> np.ndarray:
         """raw message -> float64 [25 + 6N]: the message followed by hand / elbow xyz of the N stacked rows (a view of
-        this object's buffer, overwritten by the next frame)"""
+        this object's buffer, overwritten by the next frame); ``spread``: [25 + 6N + 21], the spread record behind them"""
         self._row[:] = row                       # array('f') (stream/listener/imu.py:68-70), list or ndarray
         if self._per_stream:
-            return self._frame_subset()
+            return self._frame_subset(spread)
+        if spread:
+            self._hip.check(self._lib.ape_streams_frame_host(self._bank, self._kind, self._row_p, self._flags | self._hip.FLAG_SPREAD,
+                                                             self._out_spread_p, self._hip.F64, None), "ape_streams_frame_host")
+            return self._out_spread
         self._hip.check(self._lib.ape_streams_frame_host(self._bank, self._kind, self._row_p, self._flags, self._out_p,
                                                          self._hip.F64, None), "ape_streams_frame_host")
         return self._out
@@ -200,6 +229,27 @@ class Estimator:
     def get_last_msg(self):
         return self._last_msg
 
+    # ---- Monte-Carlo spread record (the reference has no counterpart) ----
+    _spread, _last_spread = False, None
+
+    @property
+    def spread(self) -> bool:
+        """off by default.  On: every frame also reduces its stacked rows to the 21-value spread record (``_post.spread_rows``
+        states the layout), kept for ``get_last_spread()``; what ``process_row`` / ``processing_loop`` return is unchanged."""
+        return self._spread
+
+    @spread.setter
+    def spread(self, on):
+        if on and (self._frame_samples() is None or self._hip_model() is None):
+            raise UserWarning(f"{type(self).__name__} does not serve the spread record (estimators with a HIP regressor do)")
+        self._spread = bool(on)
+        if not self._spread:
+            self._last_spread = None                      # no record outlives the switch
+
+    def get_last_spread(self):
+        """float64 [21] record of the newest frame made with ``spread`` on since the last ``reset()``, or None"""
+        return self._last_spread
+
     def is_active(self):
         return self._active
 
@@ -208,6 +258,7 @@ class Estimator:
 
     def reset(self):
         self._active, self._row_hist, self._smooth_hist = False, [], []
+        self._last_spread = None
         frame = getattr(self, "_device_frame", None)
         if frame is not None:
             frame.reset()
@@ -328,7 +379,12 @@ class Estimator:
         if frame is None:
             pred = self.add_xx_to_row_hist_and_make_prediction(self.parse_row_to_xx(row))
             return self.msg_from_pred(pred, self._add_mc_samples)
-        out = frame.frame(row)
+        if self._spread:                          # the frame's record rides behind the row and is stripped here
+            out = frame.frame(row, spread=True)
+            self._last_spread = out[-_post.SPREAD_WIDTH:].copy()
+            out = out[:-_post.SPREAD_WIDTH]
+        else:
+            out = frame.frame(row)
         self._last_msg = out[:25].copy()
         if not self._add_mc_samples:
             return self._last_msg.copy()
@@ -364,6 +420,8 @@ class Estimator:
         with ctx.lock:
             est, msg = _post.fk_and_msg(ctx.handle, self._layout, ctx.device, pred, self._body_measurements)
         self._last_msg = msg.copy()
+        if self._spread:
+            self._last_spread = _post.spread_rows(est, msg, self._layout)
         if add_mc_samples:
             # list of 25 floats followed, for N > 1 rows, by every row's hand and elbow xyz (estimator.py:131-137)
             msg = list(msg)
@@ -472,7 +530,7 @@ class Estimator:
     # ---- offline replay: every frame of recorded sessions in one call ----
     def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64,
                           return_targets: bool = False, seed: int = 0x5EED, max_rows_per_launch: int = 0, bonemaps=None,
-                          state_in=None, warm_in=None, return_state: bool = False, sample_row_base: int = 0):
+                          state_in=None, warm_in=None, return_state: bool = False, sample_row_base: int = 0, spread: bool = False):
         """rows: float32 ``[F, 55|28]`` raw messages of one or more recordings back to back (host array or CUDA
         tensor); ``starts``: the recordings' first rows (default ``[0]``: one recording).  Returns, on the device,
         what ``process_row`` returns for every row of a fresh estimator fed each recording in order (no row skipped):
@@ -494,7 +552,11 @@ class Estimator:
         the states chained and ``sample_row_base = a * n_mc, ...`` returns the rows of the one call (a multiple of 4; Monte-Carlo
         samples included where the regressor kernel's row granule divides it, see ``ape_hip.h``).  With several recordings the
         deterministic results are equal and the samples are valid draws, not the one call's.  A recording that ended in an earlier call
-        is not listed.  Bodies are not part of a record.  With none of the four given the call is the old path, entry and all."""
+        is not listed.  Bodies are not part of a record.  With none of the four given the call is the old path, entry and all.
+
+        ``spread``: the result becomes ``(out, spread)`` (``(out, y, spread)`` with ``return_targets``; the state pair stays last) with
+        ``spread`` ``[F, 21]`` of ``out_dtype``, every frame's spread record (``_post.spread_rows``); both are views
+        of one wider device tensor.  Chained pieces give the records of the one call."""
         import ctypes as C
         from wear_mocap_ape_amd import _hip
         model, n_mc = self._hip_model(), self._frame_samples()
@@ -516,9 +578,10 @@ class Estimator:
             F = int(rd.shape[0])
             st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
             packed = self._add_mc_samples and n_rows > 1
-            out = torch.empty((F, 25 + 6 * n_rows if packed else 25), dtype=out_dtype, device=dev)
+            out = torch.empty((F, (25 + 6 * n_rows if packed else 25) + (_hip.SPREAD_WIDTH if spread else 0)), dtype=out_dtype, device=dev)
             y = torch.empty((F, n_mc, model.output_size), dtype=torch.float32, device=dev) if return_targets else None
-            flags = (_hip.FLAG_NORMALIZE_INPUT if self._normalize else 0) | (_hip.FLAG_PACKED_MSG if packed else 0)
+            flags = (_hip.FLAG_NORMALIZE_INPUT if self._normalize else 0) | (_hip.FLAG_PACKED_MSG if packed else 0) | \
+                    (_hip.FLAG_SPREAD if spread else 0)
             kind = self._parse_kind | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
             stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             bodies = None if bonemaps is None else bodies_from(bonemaps, int(st.shape[0]), "process_recording bonemaps")
@@ -551,7 +614,12 @@ class Estimator:
                                                     int(max_rows_per_launch), stream,
                                                     C.c_void_p(bodies.ctypes.data) if bodies is not None else None, *extra), entry)
             model._pending.clear()         # the call is blocking and checked the handle (its journal is empty)
+        rec = None
+        if spread:
+            out, rec = out[:, :-_hip.SPREAD_WIDTH], out[:, -_hip.SPREAD_WIDTH:]
         res = (out, y) if return_targets else out
+        if spread:
+            res = (res if isinstance(res, tuple) else (res,)) + (rec,)
         if return_state:
             res = (res if isinstance(res, tuple) else (res,)) + ((state_out, warm_out),)
         return res

@@ -165,14 +165,15 @@ class StreamBank:
             raise UserWarning("stream indices must be distinct")
         return np.ascontiguousarray(a, dtype=np.int32)
 
-    def frame(self, rows, streams, kind: int, big_endian: bool = False, datagrams: bool = False):
+    def frame(self, rows, streams, kind: int, big_endian: bool = False, datagrams: bool = False, spread: bool = False):
         """One ``process_row`` for each listed stream (``ape_streams_frame_subset``): ``rows`` float32
         ``[K, 55|28]`` (host array or device tensor), row j for stream ``streams[j]``; ``streams`` K distinct indices.
         Streams not listed are untouched; each stream keeps its own window, stack and cold start (``reset(streams=...)``).
         -> ``[K, 25]`` of the bank's dtype in list order, or with ``datagrams`` float32 ``[K, 25 + 6N]`` (N = smooth x
         samples > 1): per listed stream the ``PoseEstPublisherUDP`` payload, as ``step_datagrams``.  The returned tensor is
         the bank's own buffer, overwritten by the next call.  The first call puts the bank into per-stream mode: ``push_rows``,
-        ``push_features`` and ``step`` are refused until ``reset()``.  Monte-Carlo samples depend on a stream's list position."""
+        ``push_features`` and ``step`` are refused until ``reset()``.  Monte-Carlo samples depend on a stream's list position.
+        ``spread``: every row is ``SPREAD_WIDTH`` columns longer and ends in the stream's spread record (``split_spread``)."""
         hip, C = self._hip, self._C
         if kind not in hip.PARSE_SHAPES:
             raise UserWarning(f"unknown row kind {kind}")
@@ -194,12 +195,14 @@ class StreamBank:
             key, dtype, sel, w = "_sub_dgram", torch.float32, hip.F32, (25 + 6 * n if packed else 25)
         else:
             key, dtype, sel, w = "_sub_msg", self._dtype, self._sel, 25
+        if spread:
+            key, w = key + "_spread", w + hip.SPREAD_WIDTH
         if getattr(self, key, None) is None:
             setattr(self, key, torch.empty((self._n, w), dtype=dtype, device=self._device))
         out = getattr(self, key)[:K]
         if K == 0:
             return out
-        flags = self._flags | (hip.FLAG_PACKED_MSG if packed else 0)
+        flags = self._flags | (hip.FLAG_PACKED_MSG if packed else 0) | (hip.FLAG_SPREAD if spread else 0)
         k = kind | (hip.PARSE_BIG_ENDIAN if big_endian else 0)
         hip.check(hip.lib().ape_streams_frame_subset(self._handle, k, C.c_void_p(rd.data_ptr()), C.c_void_p(idx.ctypes.data), K, flags,
                                                      C.c_void_p(out.data_ptr()), sel, self._stream()), "ape_streams_frame_subset")
@@ -256,24 +259,59 @@ class StreamBank:
         self._hip.check(self._hip.lib().ape_streams_push_features(self._handle, self._C.c_void_p(xx.data_ptr()),
                                                                   self._stream()), "ape_streams_push_features")
 
-    def step(self, with_tail: bool = False):
-        """-> msg [S,25] (and, with_tail, the hand/elbow xyz of every stacked row [S,smooth*n_mc,6]); the returned
-        tensors are the bank's own buffers, overwritten by the next step"""
+    def last_post_form(self) -> str:
+        """the post-filter form the newest frame of this bank ran (``ape_streams_last_post_form``): ``"none"``, ``"wide"``,
+        ``"one workgroup"`` or ``"split xC"``"""
+        f = self._C.c_int32(-1)
+        self._hip.check(self._hip.lib().ape_streams_last_post_form(self._handle, self._C.byref(f)), "ape_streams_last_post_form")
+        return {-1: "none", 0: "wide", 1: "one workgroup"}.get(f.value, f"split x{f.value}")
+
+    @staticmethod
+    def split_spread(rows):
+        """rows of a ``spread=True`` call -> ``(rows[:, :-21], rows[:, -21:])``: what the call returns without the flag, and the
+        spread records (layout: ``estimate._post.spread_rows``)"""
+        from . import _hip
+        return rows[:, :-_hip.SPREAD_WIDTH], rows[:, -_hip.SPREAD_WIDTH:]
+
+    def step(self, with_tail: bool = False, with_spread: bool = False):
+        """-> msg [S,25] (and, with_tail, the hand/elbow xyz of every stacked row [S,smooth*n_mc,6]; and, with_spread, the spread
+        record of every stream [S,21] of the bank's dtype: the Monte-Carlo / smoothing spread of the same stacked rows, layout in
+        ``estimate._post.spread_rows``); the returned tensors are the bank's own buffers, overwritten by the next step"""
         tail = self._C.c_void_p(self._tail.data_ptr()) if with_tail else None
+        if with_spread:
+            if getattr(self, "_msg_spread", None) is None:
+                self._msg_spread = torch.empty((self._n, 25 + self._hip.SPREAD_WIDTH), dtype=self._dtype, device=self._device)
+            self._hip.check(self._hip.lib().ape_streams_step(self._handle, self._flags | self._hip.FLAG_SPREAD,
+                                                             self._C.c_void_p(self._msg_spread.data_ptr()), tail, self._sel, self._stream()),
+                            "ape_streams_step")
+            msg, rec = self.split_spread(self._msg_spread)
+            return (msg, self._tail, rec) if with_tail else (msg, rec)
         self._hip.check(self._hip.lib().ape_streams_step(self._handle, self._flags, self._C.c_void_p(self._msg.data_ptr()),
                                                          tail, self._sel, self._stream()), "ape_streams_step")
         return (self._msg, self._tail) if with_tail else self._msg
 
-    def step_datagrams(self):
+    def step_datagrams(self, spread: bool = False):
         """-> float32 [S, 25 + 6*smooth*n_mc]: per stream the message followed by the hand/elbow xyz of every stacked
         row -- byte for byte what ``PoseEstPublisherUDP`` sends for one estimator frame (pose_est_udp.py:47 packs
         the list of estimator.py:131-137 as native float32), so ``row.cpu().numpy().tobytes()`` is the datagram.
-        Like the reference, rows only carry the tail when there is more than one stacked row."""
+        Like the reference, rows only carry the tail when there is more than one stacked row.
+        ``spread``: every row is ``SPREAD_WIDTH`` columns longer and ends in the stream's spread record as float32
+        (``split_spread`` separates the two; the reference has no such record)."""
         n = self._smooth * self._n_mc
         if n == 1:
             if self._dtype != torch.float32:
                 raise UserWarning("step_datagrams wants a float32 bank")
+            if spread:
+                self.step(with_spread=True)
+                return self._msg_spread
             return self.step()
+        if spread:
+            if getattr(self, "_packed_spread", None) is None:
+                self._packed_spread = torch.empty((self._n, 25 + 6 * n + self._hip.SPREAD_WIDTH), dtype=torch.float32, device=self._device)
+            self._hip.check(self._hip.lib().ape_streams_step(self._handle, self._flags | self._hip.FLAG_PACKED_MSG | self._hip.FLAG_SPREAD,
+                                                             self._C.c_void_p(self._packed_spread.data_ptr()), None, self._hip.F32,
+                                                             self._stream()), "ape_streams_step")
+            return self._packed_spread
         if getattr(self, "_packed", None) is None:
             self._packed = torch.empty((self._n, 25 + 6 * n), dtype=torch.float32, device=self._device)
         self._hip.check(self._hip.lib().ape_streams_step(self._handle, self._flags | self._hip.FLAG_PACKED_MSG,

@@ -98,6 +98,8 @@ enum { APE_KERNEL_AUTO = 0, APE_KERNEL_TILE16 = 1, APE_KERNEL_CLUSTER = 2,
 enum { APE_PRECISION_F32 = 0, APE_PRECISION_F16 = 1, APE_PRECISION_F16_GEN1 = 2 };
 
 #define APE_FLAG_PACKED_MSG      0x20u /* ape_streams_step only: message and tail of a stream packed in one row  */
+#define APE_FLAG_SPREAD          0x40u /* frames, banks and replays (NOT ape_lstm_forward / ape_infer, which refuse it): every output row
+                                         grows by APE_SPREAD_WIDTH columns at its end, the Monte-Carlo spread record below             */
 #define APE_FLAG_BROADCAST_X     0x10u /* x_dev is ONE window [1,T,I] shared by all B rows: the x.repeat((n,1,1)) of
                                          monte_carlo_predictions (nn_models.py:206) without materialising it    */
 
@@ -519,6 +521,38 @@ int ape_replay_resume(ape_model_t* model, int32_t kind, const float* rows_dev, i
                       void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream,
                       const double* bodies_host, const void* state_in_dev, const uint8_t* warm_in_host, void* state_out_dev,
                       uint8_t* warm_out_host, uint64_t sample_row_base);
+
+/* ---- Monte-Carlo spread record (additive in ABI 7) --------------------------------------------------------------------
+ * replaces: nothing.  The reference has NO counterpart of this record: the only form in which it lets the sample spread out is the raw
+ * cloud, est[i, :6] of every stacked row appended to the message (estimator.py:131-137; APE_FLAG_PACKED_MSG / tail_dev here).  The
+ * record is a fixed-width summary of the same N = smooth * n_mc stacked est rows the message averages -- the rows
+ * arm_pose_from_nn_targets returns for the stack Estimator.add_xx_to_row_hist_and_make_prediction builds (estimator.py:112-118), reduced
+ * by msg_from_pred (estimator.py:122-137) through compose_msg.msg_from_nn_targets_est (compose_msg.py:48-108) -- in the reference's stack
+ * order.  APE_SPREAD_WIDTH values per stream and frame:
+ *   [0:3]    plain mean of est[:, 0:3], the hand origin.  Deliberately NOT msg[4:7]: for the two orientation layouts the message
+ *            recomputes its origins from the MEAN QUATERNIONS (compose_msg.py:54-61), which is not the mean of the rows' origins
+ *   [3:9]    population covariance (divisor 1/N) of the hand origin, upper triangle xx, xy, xz, yy, yz, zz
+ *   [9:12]   plain mean of est[:, 3:6], the elbow (lower-arm origin)
+ *   [12:18]  its covariance, same order
+ *   [18:21]  angular spread in radians of the lower-arm, upper-arm and hips quaternions about the message's quaternion qm of that joint
+ *            (msg[7:11], msg[14:18], msg[21:25]): 2 asin(sqrt(1 - (1/N) sum_i (q_i . qm)^2)), the angle whose sin^2(t/2) is the mean
+ *            sin^2(t_i/2) of the rows; independent of the sign of q_i.  The sqrt argument is clamped to [0, 1] letting NaN through
+ * N == 1: means are the row, covariances and angles exactly 0 by rule.  APE_LAYOUT_ORI_CAL_LARM_UARM (no hips): [20] is exactly 0.
+ * One pass in float64: covariance = mean of products - product of means, so its absolute error is ~N 2^-53 max(1, |x|^2); a NaN est
+ * row makes the entries it touches NaN.  An APE_F32 output is the float64 record rounded once.
+ * APE_FLAG_SPREAD is accepted by ape_streams_step, ape_streams_frame_subset, ape_streams_frame_host, ape_replay, ape_replay_bodies,
+ * ape_replay_regressor and ape_replay_resume: every output row grows by APE_SPREAD_WIDTH columns at its END -- plain rows become
+ * [., 25 + 21], PACKED_MSG rows [., 25 + 6N + 21]; where an entry writes 25-column rows for PACKED_MSG at N == 1 (subset frames, replays)
+ * the flagged row is [., 25 + 21].  A separate tail_dev stays separate.  The record is written for every N.  Without the flag nothing
+ * changes, and the unflagged calls run the kernels they always ran.
+ * ape_spread_reduce: the stand-alone reduction beside ape_msg_reduce.  est_dev f64 [N,W] rows of the model's layout, msg_dev f64 [25]
+ * the message of the same rows (ape_msg_reduce; only its three quaternions are read), spread_dev f64 [APE_SPREAD_WIDTH]. */
+#define APE_SPREAD_WIDTH 21
+/* which form of the post-filter the bank's newest lockstep or subset frame ran (tests, profiles): *form = -1 no frame yet, 0 the wide form
+ * (lanes = streams, banks without stacking), 1 one workgroup per stream, c > 1 a stream's stack split over c workgroups.  For a flagged
+ * frame it is the value the launch was made with; for an unflagged one, the same rule's answer. */
+int ape_streams_last_post_form(ape_streams_t* bank, int32_t* form);
+int ape_spread_reduce(ape_model_t* model, const double* est_dev, int32_t N, const double* msg_dev, double* spread_dev, void* stream);
 
 /* kernel selection for A/B runs and tests; no effect on results beyond float32 summation order */
 int ape_model_set_kernel(ape_model_t* model, int32_t choice);
