@@ -15,6 +15,7 @@
 //                                 ragged entries (1 or E rows, padded with the newest on a cold start), float64 de-normalisation, FK of
 //                                 every stacked row (thread per row), the sign-aligned quaternion means and the 25-value message
 //                                 (stream_post_device.h's finish_msg), the packed tail, n_rows, and the stream's frame counter.
+//                                 SPR (APE_FLAG_SPREAD): the spread record of the same stacked rows behind the row.
 // Frame counters live on the device; the host only remembers which streams have a cold start pending and hands that over in the
 // staged stream list (or, for lockstep frames, as one kernel argument).
 //   ape_kalman_state_kernel       (thread per 16 bytes) a stream's rings <-> its canonical record: the state hand-over of DESIGN.md 4.27
@@ -47,6 +48,7 @@ constexpr int KB_BLOCK = 256;
 constexpr int KB_STAGES = 4;          // pinned stream-list slots (frames go back to back)
 constexpr int KB_MAX_SMOOTH = 64;     // the post-filter's limits (ape_streams_create)
 constexpr int KB_MAX_ROWS = 4096;
+constexpr uint32_t KB_FLAGS = APE_FLAG_PACKED_MSG | APE_FLAG_SPREAD;      // what the frame and replay entries accept
 
 // one list entry of a frame: the stream, whether this is its first frame since a cold start, the row it reads and the row it writes
 struct KbDesc { int stream, cold, row_in, row_out; };
@@ -137,10 +139,18 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_head_kernel(const Kb
 
 // TAB (per-stream bodies): the nine body values are row `stream` of bodies [S,9], uniform over the workgroup, instead of
 // the uniform p.body
-template <typename TMsg, bool TAB = false>
+// SPR (APE_FLAG_SPREAD): the row is APE_SPREAD_WIDTH columns longer (p.out_stride counts them) and ENDS in the spread
+// record of the N stacked rows (stream_post_device.h).  Beside acc every thread keeps 48 sums over its act rows -- the
+// 9 + 9 moments of the hand and elbow origins, the 10 + 10 + 10 sums of q q^T of the three joints -- reduced like acc: a thread's rows
+// in order, the wave tree, the four waves in wave order, so the order of every sum is fixed by (N, thread, wave) alone.  Wave 1 closes
+// the record while thread 0 composes the message: lanes 0 / 1 the two origins, lanes 2 .. 4 one joint's angle each against the
+// message's quaternion, which they form from `red` by thread 0's very operations (IEEE operations, contraction off: the same bits).
+// A parameter of the template: KbTailParams and the other forms' object code stay what they were.
+template <typename TMsg, bool TAB = false, bool SPR = false>
 __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const KbTailParams p, const double* __restrict__ bodies) {
     __shared__ int ent_slot[KB_MAX_SMOOTH], ent_first[KB_MAX_SMOOTH + 1];   // stack entries, oldest first: ring slot (-1: this frame's), first stacked row
     __shared__ double ref_s[3][4], e0_s[21], red[KB_BLOCK / 64][12];
+    __shared__ double spr_red[SPR ? KB_BLOCK / 64 : 1][SPR ? 48 : 1];       // SPR: the waves' partial spread sums (unused otherwise)
     const int j = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const KbDesc d = p.desc ? p.desc[j] : KbDesc{j, p.cold_all, j, j};
     const bool cold = d.cold != 0;
@@ -191,6 +201,7 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const Kb
     const Vec3 larm_vec{body[0], body[1], body[2]}, uarm_vec{body[3], body[4], body[5]}, orig{body[6], body[7], body[8]};
     TMsg* out = static_cast<TMsg*>(p.out) + (size_t)d.row_out * p.out_stride;
     double acc[12] = {};
+    double ss[SPR ? 48 : 1] = {};                           // SPR: hand 0:9, elbow 9:18, lower arm 18:28, upper arm 28:38, hips 38:48
     for (int base = 0; base < N; base += KB_BLOCK) {        // thread per stacked row, oldest entry first (trip count uniform)
         const int i = base + tid;
         const bool act = i < N;
@@ -213,6 +224,12 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const Kb
             const Vec3 lo = vadd(qrot(uq, uarm_vec), uo);
             const Vec3 ho = vadd(qrot(lq, larm_vec), lo);
             put_q(q, lq); put_q(q + 4, uq); put_q(q + 8, hq);
+            if constexpr (SPR) {
+                double h3[3], l3[3];
+                put_v(h3, ho); put_v(l3, lo);
+                spread_add_pos(ss, h3); spread_add_pos(ss + 9, l3);
+                spread_add_quat(ss + 18, q); spread_add_quat(ss + 28, q + 4); spread_add_quat(ss + 38, q + 8);
+            }
             if (p.packed) {                                                  // estimator.py:131-137: est[i, :6] of every row
                 TMsg* t = out + 25 + (size_t)i * 6;
                 t[0] = (TMsg)ho.x; t[1] = (TMsg)ho.y; t[2] = (TMsg)ho.z; t[3] = (TMsg)lo.x; t[4] = (TMsg)lo.y; t[5] = (TMsg)lo.z;
@@ -243,10 +260,46 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const Kb
             const double v = wave_sum(acc[cc]);
             if (lane == 0) red[wave][cc] = v;
         }
+        if constexpr (SPR) {
+#pragma unroll
+            for (int cc = 0; cc < 48; ++cc) {
+                const double v = wave_sum(ss[cc]);
+                if (lane == 0) spr_red[wave][cc] = v;
+            }
+        }
     }
-    if (p.packed)                                                            // beyond the stacked rows: zeros
-        for (int idx = 25 + 6 * N + tid; idx < p.out_stride; idx += KB_BLOCK) out[idx] = (TMsg)0.0;
+    if (p.packed)                                                            // beyond the stacked rows: zeros (SPR: up to the record)
+        for (int idx = 25 + 6 * N + tid; idx < p.out_stride - (SPR ? APE_SPREAD_WIDTH : 0); idx += KB_BLOCK) out[idx] = (TMsg)0.0;
     __syncthreads();
+    if constexpr (SPR) {
+        TMsg* rec = out + (p.out_stride - APE_SPREAD_WIDTH);
+        const int u = tid - 64;
+        if (N == 1) {                                                        // the row's two origins, zeros by rule
+            if (u >= 0 && u < APE_SPREAD_WIDTH) rec[u] = (TMsg)spread_single(e0_s, u);
+        } else if (u == 0 || u == 1) {
+            double t[9], o[9];
+#pragma unroll
+            for (int cc = 0; cc < 9; ++cc)
+                t[cc] = ((spr_red[0][9 * u + cc] + spr_red[1][9 * u + cc]) + spr_red[2][9 * u + cc]) + spr_red[3][9 * u + cc];
+            spread_pos_out(t, N, o);
+#pragma unroll
+            for (int cc = 0; cc < 9; ++cc) rec[9 * u + cc] = (TMsg)o[cc];
+        } else if (u >= 2 && u < 5) {
+            const int g = u - 2;
+            double a[4], qm[4], t[10];
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) a[cc] = ((red[0][4 * g + cc] + red[1][4 * g + cc]) + red[2][4 * g + cc]) + red[3][4 * g + cc];
+            const double nrm = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2] + a[3] * a[3]);
+#pragma unroll
+            for (int cc = 0; cc < 4; ++cc) qm[cc] = a[cc] / nrm;
+#pragma unroll
+            for (int cc = 0; cc < 10; ++cc) {
+                const int k = 18 + 10 * g + cc;
+                t[cc] = ((spr_red[0][k] + spr_red[1][k]) + spr_red[2][k]) + spr_red[3][k];
+            }
+            rec[18 + g] = (TMsg)spread_angle_out(t, N, qm);
+        }
+    }
     if (tid == 0) {
         double out_q[3][4] = {}, orig_mean[9] = {}, e0[21], m[25];
         if (N > 1) {
@@ -520,17 +573,23 @@ int frame_launch(ape_kalman_bank* b, int big_endian, const float* rows, const Kb
     t.state = b->state; t.yring = b->yring; t.nring = b->nring; t.out = out; t.n_rows = n_rows; t.y_out = y;
     t.K = K; t.E = b->E; t.W = b->W; t.smooth = b->smooth; t.packed = (flags & APE_FLAG_PACKED_MSG) ? 1 : 0;
     t.normalize = h.normalize; t.cold_all = cold_all;
-    t.out_stride = t.packed ? 25 + 6 * b->smooth * b->E : 25;
+    const bool spr = (flags & APE_FLAG_SPREAD) != 0;                                   // the record: the row's last columns
+    t.out_stride = (t.packed ? 25 + 6 * b->smooth * b->E : 25) + (spr ? APE_SPREAD_WIDTH : 0);
     const int period = b->W * b->smooth;
     t.wrap = period * ((1 << 29) / period);
     memcpy(t.yy_m, b->yy_m, sizeof(t.yy_m));
     memcpy(t.yy_s, b->yy_s, sizeof(t.yy_s));
     memcpy(t.body, b->body, sizeof(t.body));
-    if (b->bodies.on()) {
-        if (out_dtype == APE_F32) hipLaunchKernelGGL((ape_kalman_bank_tail_kernel<float, true>), dim3(K), dim3(KB_BLOCK), 0, st, t, b->bodies.dev);
-        else hipLaunchKernelGGL((ape_kalman_bank_tail_kernel<double, true>), dim3(K), dim3(KB_BLOCK), 0, st, t, b->bodies.dev);
-    } else if (out_dtype == APE_F32) hipLaunchKernelGGL((ape_kalman_bank_tail_kernel<float, false>), dim3(K), dim3(KB_BLOCK), 0, st, t, (const double*)nullptr);
-    else hipLaunchKernelGGL((ape_kalman_bank_tail_kernel<double, false>), dim3(K), dim3(KB_BLOCK), 0, st, t, (const double*)nullptr);
+    // one instantiation per (message type, body table, record)
+    using TailFn = void (*)(const KbTailParams, const double*);
+    static const TailFn tails[2][2][2] = {
+        {{ape_kalman_bank_tail_kernel<double, false, false>, ape_kalman_bank_tail_kernel<double, false, true>},
+         {ape_kalman_bank_tail_kernel<double, true, false>, ape_kalman_bank_tail_kernel<double, true, true>}},
+        {{ape_kalman_bank_tail_kernel<float, false, false>, ape_kalman_bank_tail_kernel<float, false, true>},
+         {ape_kalman_bank_tail_kernel<float, true, false>, ape_kalman_bank_tail_kernel<float, true, true>}}};
+    const bool tab = b->bodies.on();
+    hipLaunchKernelGGL(tails[out_dtype == APE_F32 ? 1 : 0][tab ? 1 : 0][spr ? 1 : 0], dim3(K), dim3(KB_BLOCK), 0, st, t,
+                       tab ? (const double*)b->bodies.dev : (const double*)nullptr);
     e = hipGetLastError();
     if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: tail launch failed: %s", what, hipGetErrorString(e));
     return APE_OK;
@@ -779,7 +838,7 @@ int ape_kalman_bank_frame(ape_kalman_bank_t* b, int32_t kind, const float* rows_
     if (!b || !rows_dev || !out_dev || !n_rows_dev) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: NULL argument");
     if (int rc = check_kind(kind, "kalman_bank_frame")) return rc;
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: unknown dtype selector");
-    if (flags & ~APE_FLAG_PACKED_MSG) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: flags 0x%x: APE_FLAG_PACKED_MSG or 0", flags);
+    if (flags & ~KB_FLAGS) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
     if (int rc = check_list(b, streams_host, K, "kalman_bank_frame")) return rc;
     KB_TRY(hipSetDevice(b->device));
     const hipStream_t st = (hipStream_t)stream;
@@ -794,22 +853,22 @@ int ape_kalman_bank_frame_host(ape_kalman_bank_t* b, int32_t kind, const float* 
     if (!b || !rows_host || !out_host || !n_rows_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: NULL argument");
     if (int rc = check_kind(kind, "kalman_bank_frame_host")) return rc;
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: unknown dtype selector");
-    if (flags & ~APE_FLAG_PACKED_MSG) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: flags 0x%x: APE_FLAG_PACKED_MSG or 0", flags);
+    if (flags & ~KB_FLAGS) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
     KB_TRY(hipSetDevice(b->device));                         // (the consumer thread of an estimator starts on device 0)
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "kalman_bank_frame_host")) return rc;
     // the head kernel reads the rows from and the tail kernel writes the messages to pinned host memory: no copy commands in the frame
     const size_t rows_bytes = (size_t)b->S * KB_WIDTH * sizeof(float);
-    const size_t width = 25 + 6 * (size_t)b->smooth * b->E;
+    const size_t width = 25 + 6 * (size_t)b->smooth * b->E;                      // (h_out: room for the widest row, record included)
     if (!b->h_rows) KB_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, hipHostMallocCoherent | hipHostMallocMapped));
-    if (!b->h_out) KB_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * width * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
+    if (!b->h_out) KB_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * (width + APE_SPREAD_WIDTH) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
     if (!b->h_n) KB_TRY(hipHostMalloc((void**)&b->h_n, (size_t)b->S * sizeof(int), hipHostMallocCoherent | hipHostMallocMapped));
     memcpy(b->h_rows, rows_host, rows_bytes);
     if (int rc = bank_frame(b, kind, b->h_rows, nullptr, b->S, nullptr, nullptr, flags, b->h_out, out_dtype, b->h_n, nullptr, st,
                             "kalman_bank_frame_host"))
         return rc;
     KB_TRY(hipStreamSynchronize(st));
-    const size_t w = (flags & APE_FLAG_PACKED_MSG) ? width : 25;
+    const size_t w = ((flags & APE_FLAG_PACKED_MSG) ? width : 25) + ((flags & APE_FLAG_SPREAD) ? APE_SPREAD_WIDTH : 0);
     memcpy(out_host, b->h_out, (size_t)b->S * w * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
     memcpy(n_rows_host, b->h_n, (size_t)b->S * sizeof(int));
     return APE_OK;
@@ -846,7 +905,7 @@ int ape_kalman_replay_resume(ape_kalman_t* model, int32_t kind, const float* row
             return bfail(APE_ERR_INVALID_ARG, "kalman_replay: seg_starts[%d] = %d (strictly rising, below F = %d)", i, seg_starts_host[i], F);
     if (smooth > KB_MAX_SMOOTH) return bfail(APE_ERR_UNSUPPORTED, "kalman_replay: smooth %d outside 1..%d", smooth, KB_MAX_SMOOTH);
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: unknown dtype selector");
-    if (flags & ~APE_FLAG_PACKED_MSG) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: flags 0x%x: APE_FLAG_PACKED_MSG or 0", flags);
+    if (flags & ~KB_FLAGS) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
     const bool any = xx_m || xx_s || yy_m || yy_s;
     if (any && !(xx_m && xx_s && yy_m && yy_s)) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: all four statistics or none");
     if (R > 65535) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: %d recordings, at most 65535 in one call", R);

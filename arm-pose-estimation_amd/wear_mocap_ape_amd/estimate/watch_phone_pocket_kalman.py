@@ -36,6 +36,9 @@ class _KalmanDeviceFrame:
         self._out = np.zeros((25 + 6 * max(1, smooth) * model._num_ensemble,), dtype=np.float64)
         self._n = np.zeros((1,), dtype=np.int32)
         self._row_p, self._out_p, self._n_p = (C.c_void_p(a.ctypes.data) for a in (self._row, self._out, self._n))
+        # frames with the spread record behind the row (APE_FLAG_SPREAD): a buffer of their own
+        self._out_spread = np.zeros((self._out.shape[0] + _hip.SPREAD_WIDTH,), dtype=np.float64)
+        self._out_spread_p = C.c_void_p(self._out_spread.ctypes.data)
 
     def __del__(self):
         bank, self._bank = getattr(self, "_bank", None), None
@@ -93,9 +96,15 @@ class _KalmanDeviceFrame:
             _hip.check(self._lib.ape_kalman_bank_set_draw_position(self._bank, self._seed, int(state["calls"]) & (2 ** 64 - 1)),
                        "ape_kalman_bank_set_draw_position")
 
-    def frame(self, row):
-        """raw message -> (float64 packed row, stacked-row count); a view of this object's buffer, overwritten by the next frame"""
+    def frame(self, row, spread: bool = False):
+        """raw message -> (float64 packed row, stacked-row count); a view of this object's buffer, overwritten by the next frame.
+        ``spread``: the row is 21 columns longer and ends in the spread record of the frame's stacked rows (a buffer of its own)"""
         self._row[:] = row
+        if spread:
+            _hip.check(self._lib.ape_kalman_bank_frame_host(self._bank, _hip.PARSE_WATCH_PHONE_POCKET, self._row_p,
+                                                            self._flags | _hip.FLAG_SPREAD, self._out_spread_p, _hip.F64, self._n_p, None),
+                       "ape_kalman_bank_frame_host")
+            return (self._out_spread if self._flags else self._out_spread[:25 + _hip.SPREAD_WIDTH]), int(self._n[0])
         _hip.check(self._lib.ape_kalman_bank_frame_host(self._bank, _hip.PARSE_WATCH_PHONE_POCKET, self._row_p, self._flags, self._out_p,
                                                         _hip.F64, self._n_p, None), "ape_kalman_bank_frame_host")
         return self._out, int(self._n[0])
@@ -146,6 +155,22 @@ class WatchPhonePocketKalman(Estimator):
         self.__init_state()
 
     model = property(lambda self: self.__model)
+
+    # the spread record: the device frame serves it (the one-stream bank's tail kernel), the staged methods fill it from
+    # ``_post.spread_rows`` like the NN classes -- so this estimator accepts the switch on either path
+    @property
+    def spread(self) -> bool:
+        """off by default.  On: every frame also reduces its stacked rows to the 21-value spread record (``_post.spread_rows`` states
+        the layout), kept for ``get_last_spread()`` -- the corrected ensemble's spread once the filter is initialised, the smoothing
+        lag of the sensor means during the first W + 1 frames (origins and zeros at ``smooth`` 1); what ``process_row`` /
+        ``processing_loop`` return is unchanged."""
+        return self._spread
+
+    @spread.setter
+    def spread(self, on):
+        self._spread = bool(on)
+        if not self._spread:
+            self._last_spread = None                      # no record outlives the switch
 
     _parse_kind = _hip.PARSE_WATCH_PHONE_POCKET
 
@@ -228,7 +253,12 @@ class WatchPhonePocketKalman(Estimator):
         frame = self._frame_runner()
         if frame is None:
             return super().process_row(row)
-        out, n = frame.frame(row)
+        if self._spread:                          # the frame's record rides behind the row and is stripped here
+            out, n = frame.frame(row, spread=True)
+            self._last_spread = out[-_hip.SPREAD_WIDTH:].copy()
+            out = out[:-_hip.SPREAD_WIDTH]
+        else:
+            out, n = frame.frame(row)
         self._last_msg = out[:25].copy()
         if not self._add_mc_samples:
             return self._last_msg.copy()
@@ -236,7 +266,8 @@ class WatchPhonePocketKalman(Estimator):
         return cut.copy() if self.msg_as_array else cut.tolist()
 
     def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64, return_targets: bool = False,
-                          seed: int = 0x5EED, bonemaps=None, state_in=None, age_in=None, return_state: bool = False, call_base: int = 0):
+                          seed: int = 0x5EED, bonemaps=None, state_in=None, age_in=None, return_state: bool = False, call_base: int = 0,
+                          spread: bool = False):
         """rows: float32 ``[F, 55]`` raw messages of one or more recordings back to back (host array or CUDA tensor); ``starts``: the
         recordings' first rows (default ``[0]``).  Returns ``(out, n_rows)`` on the device -- for every row what ``process_row`` of a
         fresh estimator with ``manual_seed(seed)`` fed that recording returns (no row skipped; several recordings share the flipout
@@ -253,7 +284,12 @@ class WatchPhonePocketKalman(Estimator):
         frame on the device and their ages -- to the result; ``call_base`` is the number of frames the recordings have already been
         through: pieces ``[0, a), [a, b), ...`` of one recording that chain state and age with ``call_base = a, b, ...`` return the
         rows of the one call, device draws included (several recordings: when every piece lists the same recordings cut at the same
-        offsets)."""
+        offsets).
+
+        ``spread`` (``APE_FLAG_SPREAD``): the result becomes ``(out, n_rows, spread)`` (``(out, n_rows, y, spread)``
+        with ``return_targets``; the state / age pair stays last) with ``spread`` ``[F, 21]`` of ``out_dtype``, every frame's spread
+        record over its ``n_rows[f]`` stacked rows (``_post.spread_rows``); ``out`` and ``spread`` are views of one wider device
+        tensor.  Chained pieces give the records of the one call."""
         if out_dtype not in (torch.float32, torch.float64):
             raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
         model = self.__model
@@ -265,7 +301,8 @@ class WatchPhonePocketKalman(Estimator):
             F = int(rd.shape[0])
             st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
             packed = bool(self._add_mc_samples)
-            out = torch.empty((F, 25 + 6 * self._smooth * self.__num_ensemble if packed else 25), dtype=out_dtype, device=dev)
+            out = torch.empty((F, (25 + 6 * self._smooth * self.__num_ensemble if packed else 25) + (_hip.SPREAD_WIDTH if spread else 0)),
+                              dtype=out_dtype, device=dev)
             n_rows = torch.empty((F,), dtype=torch.int32, device=dev)
             y = torch.empty((F, self.__num_ensemble, 14), dtype=torch.float32, device=dev) if return_targets else None
             stats = self._stats()
@@ -292,7 +329,8 @@ class WatchPhonePocketKalman(Estimator):
             vp = lambda t: C.c_void_p(t.data_ptr()) if t is not None else None          # noqa: E731
             ap = lambda a: C.c_void_p(a.ctypes.data) if a is not None else None         # noqa: E731
             args = (model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data), R, self._smooth, *sp,
-                    _hip.dptr(body, C.c_double), int(seed) & (2 ** 64 - 1), _hip.FLAG_PACKED_MSG if packed else 0,
+                    _hip.dptr(body, C.c_double), int(seed) & (2 ** 64 - 1),
+                    (_hip.FLAG_PACKED_MSG if packed else 0) | (_hip.FLAG_SPREAD if spread else 0),
                     C.c_void_p(out.data_ptr()), _hip.F64 if out_dtype == torch.float64 else _hip.F32, C.c_void_p(n_rows.data_ptr()),
                     C.c_void_p(y.data_ptr()) if y is not None else None, stream,
                     C.c_void_p(bodies.ctypes.data) if bodies is not None else None)
@@ -301,5 +339,10 @@ class WatchPhonePocketKalman(Estimator):
             else:
                 _hip.check(_hip.lib().ape_kalman_replay_resume(*args, vp(s_in), ap(a_in), vp(s_out), ap(a_out), int(call_base) & (2 ** 64 - 1)),
                            "ape_kalman_replay_resume")
+        rec = None
+        if spread:
+            out, rec = out[:, :-_hip.SPREAD_WIDTH], out[:, -_hip.SPREAD_WIDTH:]
         res = (out, n_rows, y) if return_targets else (out, n_rows)
+        if spread:
+            res = res + (rec,)
         return res + (s_out, a_out) if return_state else res

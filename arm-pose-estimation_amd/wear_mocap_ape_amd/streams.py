@@ -521,9 +521,6 @@ class KalmanStreamBank:
     def _stream(self):
         return self._C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)
 
-    _indices = StreamBank._indices          # in range, distinct, int32
-    _rows = FkStreamBank._rows
-
     def reset(self, streams=None):
         """cold start: ``streams=None`` every stream, else only the listed (distinct) ones"""
         if streams is None:
@@ -538,12 +535,17 @@ class KalmanStreamBank:
             self._bufs[key] = torch.empty(shape, dtype=dtype, device=self._device)
         return self._bufs[key]
 
-    def _frame(self, rows, idx, big_endian, datagrams, noise, init_noise, return_targets, tag):
+    _indices = StreamBank._indices          # in range, distinct, int32
+    _rows = FkStreamBank._rows
+    split_spread = staticmethod(StreamBank.split_spread)      # rows of a ``spread=True`` call -> (unflagged part, records [., 21])
+
+    def _frame(self, rows, idx, big_endian, datagrams, noise, init_noise, return_targets, tag, spread=False):
         hip, C = self._hip, self._C
         K = self._n if idx is None else int(idx.shape[0])
         rd = self._rows(rows, K)
-        w = self._width if datagrams else 25
-        out = self._buf((tag, "out", datagrams), (self._n, w), self._dtype)[:K]
+        w = (self._width if datagrams else 25) + (hip.SPREAD_WIDTH if spread else 0)
+        # (flagged frames have buffers of their own: an unflagged call's buffer keeps its shape)
+        out = self._buf((tag, "out", datagrams) + (("spread",) if spread else ()), (self._n, w), self._dtype)[:K]
         n_rows = self._buf((tag, "n"), (self._n,), torch.int32)[:K]
         y = self._buf((tag, "y"), (self._n, self._E, 14), torch.float32)[:K] if return_targets else None
         res = (out, n_rows) if datagrams else out
@@ -563,25 +565,31 @@ class KalmanStreamBank:
                 raise UserWarning(f"frame init_noise must hold [{K},{self._E},14] values")
         kind = hip.PARSE_WATCH_PHONE_POCKET | (hip.PARSE_BIG_ENDIAN if big_endian else 0)
         hip.check(hip.lib().ape_kalman_bank_frame(self._handle, kind, p(rd), C.c_void_p(idx.ctypes.data) if idx is not None else None, K,
-                                                  p(nz), p(ini), hip.FLAG_PACKED_MSG if datagrams else 0, p(out), self._sel, p(n_rows),
+                                                  p(nz), p(ini), (hip.FLAG_PACKED_MSG if datagrams else 0) | (hip.FLAG_SPREAD if spread else 0),
+                                                  p(out), self._sel, p(n_rows),
                                                   p(y), self._stream()), "ape_kalman_bank_frame")
         self._keep = (rd, nz, ini)           # the launches read them behind this call
         return res
 
-    def step_rows(self, rows, big_endian: bool = False, datagrams: bool = False, noise=None, init_noise=None, return_targets: bool = False):
+    def step_rows(self, rows, big_endian: bool = False, datagrams: bool = False, noise=None, init_noise=None, return_targets: bool = False,
+                  spread: bool = False):
         """lockstep frame: float32 ``[S, 55]`` rows (host array or device tensor), row s for stream s -> ``[S, 25]`` messages of the
         bank's dtype; see ``frame`` for the other arguments.  The bank's own buffers, overwritten by the next lockstep frame."""
-        return self._frame(rows, None, big_endian, datagrams, noise, init_noise, return_targets, "step")
+        return self._frame(rows, None, big_endian, datagrams, noise, init_noise, return_targets, "step", spread)
 
     def frame(self, rows, streams, big_endian: bool = False, datagrams: bool = False, noise=None, init_noise=None,
-              return_targets: bool = False):
+              return_targets: bool = False, spread: bool = False):
         """subset frame: float32 ``[K, 55]`` rows, row j for stream ``streams[j]`` (K distinct indices) -> ``[K, 25]`` in list order.
         Streams not listed are untouched.  ``datagrams``: ``([K, 25 + 6 * smooth * E], n_rows int32 [K])`` instead -- the message,
         hand and elbow xyz of the ``n_rows[j]`` stacked rows, zeros; ``trim_packed(row, n)`` cuts a row to the reference's length.
         ``return_targets`` appends the frame's normalised predictions float32 ``[K, E, 14]`` (row 0 alone while a stream is in its
         first W + 1 frames).  ``noise`` / ``init_noise`` inject the draws of this call (``ape_kalman_noise_floats(K)`` values and
-        ``[K, E, 14]``): tests.  The bank's own buffers, overwritten by the next subset frame."""
-        return self._frame(rows, self._indices(streams), big_endian, datagrams, noise, init_noise, return_targets, "sub")
+        ``[K, E, 14]``): tests.  ``spread``: every row, message or datagram, is ``SPREAD_WIDTH`` = 21 columns longer
+        and ends in the spread record of the entry's ``n_rows[j]`` stacked rows (layout: ``estimate._post.spread_rows``;
+        ``split_spread(rows)`` separates the two, ``trim_packed`` takes the unflagged part) -- the corrected ensemble's spread once the
+        stream is past its first W + 1 frames, the smoothing lag of the sensor means before (one row: origins and zeros); flagged
+        frames use buffers of their own.  The bank's own buffers, overwritten by the next subset frame of the same kind."""
+        return self._frame(rows, self._indices(streams), big_endian, datagrams, noise, init_noise, return_targets, "sub", spread)
 
     # ---- state hand-over (DESIGN.md 4.27) ----
     def state_desc(self) -> dict:

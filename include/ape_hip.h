@@ -541,7 +541,7 @@ int ape_replay_resume(ape_model_t* model, int32_t kind, const float* rows_dev, i
  * One pass in float64: covariance = mean of products - product of means, so its absolute error is ~N 2^-53 max(1, |x|^2); a NaN est
  * row makes the entries it touches NaN.  An APE_F32 output is the float64 record rounded once.
  * APE_FLAG_SPREAD is accepted by ape_streams_step, ape_streams_frame_subset, ape_streams_frame_host, ape_replay, ape_replay_bodies,
- * ape_replay_regressor and ape_replay_resume: every output row grows by APE_SPREAD_WIDTH columns at its END -- plain rows become
+ * ape_replay_regressor and ape_replay_resume (and by the Kalman bank's frames and replays, see there): every output row grows by APE_SPREAD_WIDTH columns at its END -- plain rows become
  * [., 25 + 21], PACKED_MSG rows [., 25 + 6N + 21]; where an entry writes 25-column rows for PACKED_MSG at N == 1 (subset frames, replays)
  * the flagged row is [., 25 + 21].  A separate tail_dev stays separate.  The record is written for every N.  Without the flag nothing
  * changes, and the unflagged calls run the kernels they always ran.
@@ -646,9 +646,12 @@ int ape_kalman_check(ape_kalman_t* model);
  *                Lockstep and subset frames mix freely; streams not listed stay bit for bit untouched.  K = 0 is a no-op.
  *   noise_dev    NULL (Philox) or ape_kalman_noise_floats(K) injected draws of this call, rows = (list position j, member e)
  *   init_noise_dev  NULL (Philox) or f32 [K,E,14] standard-normal draws for format_state
- *   flags        0 or APE_FLAG_PACKED_MSG
+ *   flags        0, APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD (every other flag is refused)
  *   out_dev      [K,25] of out_dtype; APE_FLAG_PACKED_MSG: [K, 25 + 6*smooth*E], the message, then hand and elbow xyz of the
  *                n_rows[j] stacked rows, oldest entry first (estimator.py:131-137), then zeros.  F32 is the float64 message rounded.
+ *                APE_FLAG_SPREAD: every row is APE_SPREAD_WIDTH columns longer and ENDS in the spread record of its n_rows[j] stacked
+ *                rows (below, "the Kalman bank's spread record"): [K, 25 + 21], with APE_FLAG_PACKED_MSG [K, 25 + 6*smooth*E + 21]
+ *                (the zeros stop in front of the record).
  *   n_rows_dev   int32 [K]: stacked rows of entry j, between smooth and smooth*E
  *   y_dev        NULL or f32 [K,E,14]: the frame's normalised prediction (row 0 alone on the first W + 1 frames, the rest unspecified)
  * One flipout perturbation draw per call, shared by all its rows (as ape_kalman_forward for S > 1).  Device draws are keyed by the
@@ -660,7 +663,7 @@ int ape_kalman_check(ape_kalman_t* model);
  * ape_kalman_replay: every frame of R recordings back to back in rows_dev [F,55] (seg_starts_host: their first rows, [0] first,
  *   strictly rising, below F): a fresh bank of R streams with seed `seed`, frame t lists in ascending order the recordings that have
  *   a row t; outputs in recording order (row seg_starts[r] + t of out_dev [F, 25 | 25 + 6*smooth*E], n_rows_dev [F], y_dev
- *   [F,E,14]).  xx_m .. yy_s all NULL: no normalisation.  BLOCKING.
+ *   [F,E,14]).  xx_m .. yy_s all NULL: no normalisation.  BLOCKING.  Flags and row widths as ape_kalman_bank_frame.
  * Refused (non-zero, ape_last_error): NULL arguments, weights not loaded, a kind other than APE_PARSE_WATCH_PHONE_POCKET, K < 0 or
  * K > S, an index outside [0, S) or listed twice, smooth > 64 or smooth*E > 4096, bad replay starts, F < 1, a capturing stream.
  * ape_kalman_check reports a singular innovation of any bank frame. */
@@ -672,11 +675,25 @@ int ape_kalman_bank_reset_subset(ape_kalman_bank_t* bank, const int32_t* streams
 int ape_kalman_bank_set_norm_stats(ape_kalman_bank_t* bank, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s);
 int ape_kalman_bank_set_body(ape_kalman_bank_t* bank, const double body9[9]);
 int ape_kalman_bank_set_seed(ape_kalman_bank_t* bank, uint64_t seed);
+/* ---- the Kalman bank's spread record (additive in ABI 7) ----
+ * replaces: nothing (the record of DESIGN.md 4.28 above -- layout, rules and arithmetic unchanged, layout ORI_CAL_LARM_UARM_HIPS -- taken
+ * over the N = n_rows stacked rows the Kalman tail walks: 1 row per stack entry during a stream's first W + 1 frames, E rows per entry
+ * afterwards, entries oldest first, padded with the newest on a cold start).  Once the filter is initialised the rows are its corrected
+ * ensemble and the record is the filter's own spread; during the init frames with smooth > 1 they are the last `smooth` sensor means
+ * and the record is their smoothing lag; n_rows tells the phases apart.  N == 1: the row's two origins and exact zeros.
+ * APE_FLAG_SPREAD, alone or with APE_FLAG_PACKED_MSG, is accepted by the five entries below; every other flag stays refused.  The 21
+ * values are the LAST columns of each output row.  A flagged and an unflagged frame of the same bank state write the same message,
+ * tail, n_rows, y_dev and rings; draws, counters and the state hand-over do not know the flag.
+ * ape_kalman_bank_frame: flags 0, APE_FLAG_PACKED_MSG, APE_FLAG_SPREAD or both; rows [K, 25 (+ 6*smooth*E) (+ 21)]. */
 int ape_kalman_bank_frame(ape_kalman_bank_t* bank, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
                           const float* noise_dev, const float* init_noise_dev, uint32_t flags, void* out_dev, int32_t out_dtype,
                           int32_t* n_rows_dev, float* y_dev, void* stream);
+/* ape_kalman_bank_frame_host: the same flags; out_host is [S, 25 (+ 6*smooth*E with APE_FLAG_PACKED_MSG) (+ 21 with APE_FLAG_SPREAD)]
+ * of out_dtype, the width the flags of THIS call give (the bank's pinned row buffer has room for the widest). */
 int ape_kalman_bank_frame_host(ape_kalman_bank_t* bank, int32_t kind, const float* rows_host, uint32_t flags, void* out_host,
                                int32_t out_dtype, int32_t* n_rows_host, void* stream);
+/* ape_kalman_replay: flags 0, APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD; out_dev [F, 25 (+ 6*smooth*E) (+ 21)], the record of frame
+ * f in the last APE_SPREAD_WIDTH columns of row f. */
 int ape_kalman_replay(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                       int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
                       const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
@@ -686,6 +703,7 @@ int ape_kalman_replay(ape_kalman_t* model, int32_t kind, const float* rows_dev, 
  * bodies_host f64 [R,9] or NULL = body9 for every recording (ape_kalman_replay); with bodies_host given body9 may be NULL. */
 int ape_kalman_bank_set_bodies(ape_kalman_bank_t* bank, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream);
 int ape_kalman_bank_get_bodies(ape_kalman_bank_t* bank, double* out_host);
+/* ape_kalman_replay_bodies: flags and row widths as ape_kalman_replay (APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD: +21 columns) */
 int ape_kalman_replay_bodies(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                              int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
                              const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
@@ -742,6 +760,8 @@ int ape_kalman_bank_import(ape_kalman_bank_t* bank, const ape_kalman_state_desc_
                            const void* state_dev, const int32_t* age_host, void* stream);
 int ape_kalman_bank_get_draw_position(ape_kalman_bank_t* bank, uint64_t* seed, uint64_t* calls);
 int ape_kalman_bank_set_draw_position(ape_kalman_bank_t* bank, uint64_t seed, uint64_t calls);
+/* ape_kalman_replay_resume: flags and row widths as ape_kalman_replay (APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD: +21 columns); the
+ * order of every sum of the record depends on (N, thread, wave) alone, so chained pieces give the records of the one call bit for bit */
 int ape_kalman_replay_resume(ape_kalman_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
                              int32_t smooth, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s,
                              const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
