@@ -1350,7 +1350,11 @@ int ape_model_stats(const ape_model_t* m, ape_model_stats_t* out) {
 }
 
 static int replay_entry(ape_model_t* m, const ApeJournalEntry& e);
-static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_dev, int out_dtype, void* stream, unsigned long long mc_call);
+// (host subset frames: the pinned words the post-filter writes behind its rows -- the model's status word, a completion word per entry --
+//  and the entry's name for ape_last_error)
+struct SubsetHostWords { unsigned* status_out = nullptr; unsigned* done_out = nullptr; unsigned done_val = 0; const char* what = "streams_frame_subset"; };
+static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_dev, int out_dtype, void* stream, unsigned long long mc_call,
+                               const SubsetHostWords& hw = SubsetHostWords{});
 
 int ape_model_recover(ape_model_t* m) {
     if (!m) return fail(APE_ERR_INVALID_ARG, "recover: NULL model");
@@ -1814,6 +1818,7 @@ int ape_streams_destroy(ape_streams_t* b) {
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->h_status) (void)hipHostFree(b->h_status);
     if (b->h_done) (void)hipHostFree(b->h_done);
+    if (b->hs_block) (void)hipHostFree(b->hs_block);
     for (auto ev : b->prof_ev) if (ev) (void)hipEventDestroy(ev);
     subset_free(b);                     // (drops the bank's pending subset frame as below)
     ape_body_table_free(b->bodies);
@@ -2393,7 +2398,8 @@ int ape_streams_reset_subset(ape_streams_t* b, const int32_t* streams_host, int3
 }
 
 // launches 2 and 3 of a subset frame over the compact windows and descriptors in the bank's workspace (also the journal's re-issue)
-static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_dev, int out_dtype, void* stream, unsigned long long mc_call) {
+static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_dev, int out_dtype, void* stream, unsigned long long mc_call,
+                               const SubsetHostWords& hw) {
     ape_model* m = b->model;
     const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
     const bool packed = (flags & APE_FLAG_PACKED_MSG) != 0 && b->smooth * b->n_mc > 1;
@@ -2415,56 +2421,56 @@ static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_
     q.smooth = b->smooth; q.n_mc = b->n_mc;
     q.msg_dtype = out_dtype; q.packed = packed ? 1 : 0;
     q.part = b->post_part; q.part_cnt = b->post_cnt;     // (sized for S >= K entries)
+    if (hw.status_out != nullptr && m->cluster_ok) { q.status_in = m->xflags + m->xflag_bytes / sizeof(unsigned); q.status_out = hw.status_out; }
+    if (hw.done_out != nullptr) { q.done_out = hw.done_out; q.done_val = hw.done_val; }      // (word j behind list entry j's row)
     b->last_post_form = ape_stream_post_form(q, q.part != nullptr && (!(flags & APE_FLAG_SPREAD) || b->post_spread != nullptr));
     hipError_t e = (flags & APE_FLAG_SPREAD)
                        ? ape_launch_stream_post_subset_spread(q, b->sub_desc, SpreadArgs{b->post_spread}, b->last_post_form, (hipStream_t)stream,
                                                               b->bodies.dev)
                        : ape_launch_stream_post_subset(q, b->sub_desc, (hipStream_t)stream, b->bodies.dev);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset: post-filter launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(APE_ERR_HIP, "%s: post-filter launch failed: %s", hw.what, hipGetErrorString(e));
     return APE_OK;
 }
 
-int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
-                             uint32_t flags, void* out_dev, int32_t out_dtype, void* stream) {
-    if (!b || !rows_dev || !streams_host || !out_dev) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: NULL argument");
-    if (int rc = subset_check_list(b, streams_host, K, "streams_frame_subset")) return rc;
+// what both subset entries check before anything is launched or counted; `what` names the entry
+static int subset_frame_check(ape_streams* b, int32_t kind, const void* rows, const int32_t* streams_host, int32_t K, uint32_t flags, const void* out,
+                              int32_t out_dtype, void* stream, const char* what, int* width_out, int* I_out) {
+    if (!b || !rows || !streams_host || !out) return fail(APE_ERR_INVALID_ARG, "%s: NULL argument", what);
+    if (int rc = subset_check_list(b, streams_host, K, what)) return rc;
     int width, I;
-    const int big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
-    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: unknown kind %d", kind);
+    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return fail(APE_ERR_INVALID_ARG, "%s: unknown kind %d", what, kind);
     ape_model* m = b->model;
     if (I != m->dims.input_size)
-        return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: kind %d builds %d features, the model takes %d", kind & ~APE_PARSE_BIG_ENDIAN, I,
-                    m->dims.input_size);
+        return fail(APE_ERR_INVALID_ARG, "%s: kind %d builds %d features, the model takes %d", what, kind & ~APE_PARSE_BIG_ENDIAN, I, m->dims.input_size);
     if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG | APE_FLAG_SPREAD))
-        return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: only NORMALIZE_INPUT, PACKED_MSG and SPREAD are accepted");
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: unknown dtype selector");
+        return fail(APE_ERR_INVALID_ARG, "%s: only NORMALIZE_INPUT, PACKED_MSG and SPREAD are accepted", what);
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "%s: unknown dtype selector", what);
     if (!b->xring || !b->yring || (m->dims.model_kind == APE_MODEL_FF && !b->ffhid))
-        return fail(APE_ERR_NOT_READY, "streams_frame_subset: the bank lost its rings in a failed ape_streams_set_mc");
-    const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
-    if (norm && !m->has_stats) return fail(APE_ERR_NOT_READY, "streams_frame_subset: NORMALIZE_INPUT without norm stats");
-    if (!m->has_weights) return fail(APE_ERR_NOT_READY, "streams_frame_subset: weights not loaded");
-    if (b->inj_masks) return fail(APE_ERR_UNSUPPORTED, "streams_frame_subset: injected masks (test hook) are indexed by the lockstep rows");
+        return fail(APE_ERR_NOT_READY, "%s: the bank lost its rings in a failed ape_streams_set_mc", what);
+    if ((flags & APE_FLAG_NORMALIZE_INPUT) && !m->has_stats) return fail(APE_ERR_NOT_READY, "%s: NORMALIZE_INPUT without norm stats", what);
+    if (!m->has_weights) return fail(APE_ERR_NOT_READY, "%s: weights not loaded", what);
+    if (b->inj_masks) return fail(APE_ERR_UNSUPPORTED, "%s: injected masks (test hook) are indexed by the lockstep rows", what);
     HIP_TRY(hipSetDevice(m->dims.device));
-    const hipStream_t st = (hipStream_t)stream;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing(st, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "streams_frame_subset: the stream is capturing (the descriptors are staged per call)");
-    if (K == 0) return APE_OK;
-    // workspaces on the first subset call, sized for K = S
-    const size_t R = (size_t)b->S * b->n_mc;
-    if (b->sub_n_mc != b->n_mc || !b->sub_x) {
-        subset_free(b);
-        HIP_TRY(hipMalloc((void**)&b->sub_x, (size_t)b->S * bank_copies(b) * b->T * I * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&b->sub_y, R * m->dims.output_size * sizeof(float)));
-        HIP_TRY(hipMalloc((void**)&b->sub_desc, (size_t)b->S * sizeof(SubsetDesc)));
-        b->sub_n_mc = b->n_mc;
-    }
-    if (int rc = subset_stage_alloc(b)) return rc;
-    subset_enter(b);
-    // the descriptors into the next pinned slot -- once the copy that last read it has completed (frames go back to back, no host sync)
-    const int k = b->sub_next;
-    HIP_TRY(hipEventSynchronize(b->sub_ev[k]));
-    SubsetDesc* h = b->sub_stage + (size_t)k * b->S;
+    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
+    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "%s: the stream is capturing (the descriptors are staged per call)", what);
+    *width_out = width; *I_out = I;
+    return APE_OK;
+}
+
+// the subset frames' device workspaces on the first subset call, sized for K = S
+static int subset_workspace(ape_streams* b, int I) {
+    if (b->sub_n_mc == b->n_mc && b->sub_x) return APE_OK;
+    subset_free(b);
+    HIP_TRY(hipMalloc((void**)&b->sub_x, (size_t)b->S * bank_copies(b) * b->T * I * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&b->sub_y, (size_t)b->S * b->n_mc * b->model->dims.output_size * sizeof(float)));
+    HIP_TRY(hipMalloc((void**)&b->sub_desc, (size_t)b->S * sizeof(SubsetDesc)));
+    b->sub_n_mc = b->n_mc;
+    return APE_OK;
+}
+
+// the K descriptors of a frame from the per-stream counters, into `h`
+static void subset_fill_desc(const ape_streams* b, const int32_t* streams_host, int K, SubsetDesc* h) {
     for (int j = 0; j < K; ++j) {
         const int s = streams_host[j];
         const long long f = b->s_frames[s], p = b->s_steps[s];
@@ -2472,19 +2478,11 @@ int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_d
         h[j].slot = (int)(f % b->T); h[j].cold = f == 0 ? 1 : 0;
         h[j].pos = (int)(p % b->smooth); h[j].pcold = p == 0 ? 1 : 0;
     }
-    HIP_TRY(hipMemcpyAsync(b->sub_desc, h, (size_t)K * sizeof(SubsetDesc), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(b->sub_ev[k], st));
-    b->sub_next = (k + 1) % APE_SUBSET_STAGES;
-    SubsetRowsParams rp{};
-    rp.rows = rows_dev; rp.desc = b->sub_desc; rp.xring = b->xring; rp.xw = b->sub_x;
-    rp.K = K; rp.width = width; rp.kind = kind & ~APE_PARSE_BIG_ENDIAN; rp.big_endian = big_endian; rp.T = b->T; rp.I = I; rp.n_mc = bank_copies(b);
-    hipError_t e = ape_launch_subset_rows(rp, st);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset: row launch failed: %s", hipGetErrorString(e));
-    // the rows are in the rings: the counters move on whatever the regressor does (a failed launch is reported, the rows stay pushed)
-    for (int j = 0; j < K; ++j) { b->s_frames[streams_host[j]] += 1; b->s_steps[streams_host[j]] += 1; }
-    const unsigned long long mc_call = b->mc_calls++;
-    if (int rc = subset_regress_post(b, K, flags, out_dev, out_dtype, stream, mc_call)) return rc;
-    // journaled like a step: re-issued by ape_model_recover while it is the bank's newest frame (an older pending one is lost)
+}
+
+// journaled like a step: re-issued by ape_model_recover while it is the bank's newest frame (an older pending one is lost)
+static void subset_journal(ape_streams* b, int K, uint32_t flags, void* out, int out_dtype, void* stream, unsigned long long mc_call) {
+    ape_model* m = b->model;
     int n = 0;
     for (int i = 0; i < m->journal_n; ++i) {
         const ApeJournalEntry& o = m->journal[i];
@@ -2493,9 +2491,136 @@ int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_d
     }
     m->journal_n = n;
     ApeJournalEntry je{};
-    je.kind = ApeJournalEntry::SUBSET; je.out0 = out_dev; je.B = K; je.flags = flags; je.i2 = out_dtype; je.stream = stream;
+    je.kind = ApeJournalEntry::SUBSET; je.out0 = out; je.B = K; je.flags = flags; je.i2 = out_dtype; je.stream = stream;
     je.bank = b; je.bank_mc_calls = mc_call;
     journal_add(m, je);
+}
+
+int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
+                             uint32_t flags, void* out_dev, int32_t out_dtype, void* stream) {
+    int width, I;
+    if (int rc = subset_frame_check(b, kind, rows_dev, streams_host, K, flags, out_dev, out_dtype, stream, "streams_frame_subset", &width, &I)) return rc;
+    const hipStream_t st = (hipStream_t)stream;
+    if (K == 0) return APE_OK;
+    if (int rc = subset_workspace(b, I)) return rc;
+    if (int rc = subset_stage_alloc(b)) return rc;
+    subset_enter(b);
+    // the descriptors into the next pinned slot -- once the copy that last read it has completed (frames go back to back, no host sync)
+    const int k = b->sub_next;
+    HIP_TRY(hipEventSynchronize(b->sub_ev[k]));
+    SubsetDesc* h = b->sub_stage + (size_t)k * b->S;
+    subset_fill_desc(b, streams_host, K, h);
+    HIP_TRY(hipMemcpyAsync(b->sub_desc, h, (size_t)K * sizeof(SubsetDesc), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipEventRecord(b->sub_ev[k], st));
+    b->sub_next = (k + 1) % APE_SUBSET_STAGES;
+    SubsetRowsParams rp{};
+    rp.rows = rows_dev; rp.desc = b->sub_desc; rp.xring = b->xring; rp.xw = b->sub_x;
+    rp.K = K; rp.width = width; rp.kind = kind & ~APE_PARSE_BIG_ENDIAN; rp.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0; rp.T = b->T; rp.I = I;
+    rp.n_mc = bank_copies(b);
+    hipError_t e = ape_launch_subset_rows(rp, st);
+    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset: row launch failed: %s", hipGetErrorString(e));
+    // the rows are in the rings: the counters move on whatever the regressor does (a failed launch is reported, the rows stay pushed)
+    for (int j = 0; j < K; ++j) { b->s_frames[streams_host[j]] += 1; b->s_steps[streams_host[j]] += 1; }
+    const unsigned long long mc_call = b->mc_calls++;
+    if (int rc = subset_regress_post(b, K, flags, out_dev, out_dtype, stream, mc_call)) return rc;
+    subset_journal(b, K, flags, out_dev, out_dtype, stream, mc_call);
+    return APE_OK;
+}
+
+// Host subset frame: the device entry's frame with host rows in and host rows out, BLOCKING, and with no copy command
+// and no event on the stream.  The host writes rows and descriptors into one pinned block; launch 1 reads both from there and lands the
+// descriptors in sub_desc, so launches 2 and 3 -- and the journal's re-issue -- read device memory as ever; launch 3 writes the rows,
+// the model's status word and (K <= 64) a completion word per entry into pinned memory, as the lockstep host frame's post kernel does.
+// The block is reused every frame: the call returns only when the frame is done.  Layout: [64] completion words, [S] descriptors,
+// [S, 57] rows (57: the widest raw message).
+static constexpr int SUBSET_HOST_ROW_MAX = 57;
+int ape_streams_frame_subset_host(ape_streams_t* b, int32_t kind, const float* rows_host, const int32_t* streams_host, int32_t K,
+                                  uint32_t flags, void* out_host, int32_t out_dtype, void* stream) {
+    int width, I;
+    if (int rc = subset_frame_check(b, kind, rows_host, streams_host, K, flags, out_host, out_dtype, stream, "streams_frame_subset_host", &width, &I))
+        return rc;
+    if (width > SUBSET_HOST_ROW_MAX) return fail(APE_ERR_UNSUPPORTED, "streams_frame_subset_host: rows of %d columns", width);
+    const hipStream_t st = (hipStream_t)stream;
+    if (K == 0) return APE_OK;
+    ape_model* m = b->model;
+    if (int rc = subset_workspace(b, I)) return rc;
+    const size_t N = (size_t)b->smooth * b->n_mc;
+    const bool packed = (flags & APE_FLAG_PACKED_MSG) != 0 && N > 1;
+    const size_t row_w = (packed ? 25 + 6 * N : 25) + ((flags & APE_FLAG_SPREAD) ? APE_SPREAD_WIDTH : 0);
+    const size_t esz = out_dtype == APE_F64 ? sizeof(double) : sizeof(float);
+    if (!b->hs_block) {
+        const size_t bytes = 64 * sizeof(unsigned) + (size_t)b->S * sizeof(SubsetDesc) + (size_t)b->S * SUBSET_HOST_ROW_MAX * sizeof(float);
+        HIP_TRY(hipHostMalloc((void**)&b->hs_block, bytes, APE_PINNED));
+        memset(b->hs_block, 0, bytes);
+    }
+    const size_t out_cap = (size_t)b->S * row_w * esz;          // (sized for K = S, so that the buffer settles with the first frame of a kind)
+    if (out_cap > b->h_out_bytes) {
+        if (b->h_out) { HIP_TRY(hipHostFree(b->h_out)); b->h_out = nullptr; b->h_out_bytes = 0; }
+        HIP_TRY(hipHostMalloc(&b->h_out, out_cap, APE_PINNED));
+        b->h_out_bytes = out_cap;
+    }
+    if (!b->h_status) {
+        HIP_TRY(hipHostMalloc((void**)&b->h_status, 64, APE_PINNED));
+        *b->h_status = 0u;
+    }
+    unsigned* const h_done = reinterpret_cast<unsigned*>(b->hs_block);
+    SubsetDesc* const h_desc = reinterpret_cast<SubsetDesc*>(b->hs_block + 64 * sizeof(unsigned));
+    float* const h_rows = reinterpret_cast<float*>(b->hs_block + 64 * sizeof(unsigned) + (size_t)b->S * sizeof(SubsetDesc));
+    const bool words = K <= 64;                                  // a word per entry the host can watch; a longer list waits for the stream
+    b->hs_done_val += 1;
+    if (b->hs_done_val == 0) b->hs_done_val = 1;
+    subset_enter(b);
+    const double t_begin = now_us();
+    memcpy(h_rows, rows_host, (size_t)K * width * sizeof(float));
+    subset_fill_desc(b, streams_host, K, h_desc);
+    *b->h_status = m->cluster_ok ? 0xFFFFFFFFu : 0u;            // (as ape_streams_frame_host: a sentinel where a kernel writes the word)
+    SubsetRowsParams rp{};
+    rp.rows = h_rows; rp.desc = h_desc; rp.xring = b->xring; rp.xw = b->sub_x;
+    rp.K = K; rp.width = width; rp.kind = kind & ~APE_PARSE_BIG_ENDIAN; rp.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0; rp.T = b->T; rp.I = I;
+    rp.n_mc = bank_copies(b);
+    hipError_t e = ape_launch_subset_rows_host(rp, b->sub_desc, st);
+    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset_host: row launch failed: %s", hipGetErrorString(e));
+    for (int j = 0; j < K; ++j) { b->s_frames[streams_host[j]] += 1; b->s_steps[streams_host[j]] += 1; }
+    const unsigned long long mc_call = b->mc_calls++;
+    SubsetHostWords hw;
+    hw.status_out = b->h_status; hw.done_out = words ? h_done : nullptr; hw.done_val = b->hs_done_val; hw.what = "streams_frame_subset_host";
+    if (int rc = subset_regress_post(b, K, flags, b->h_out, out_dtype, stream, mc_call, hw)) {
+        (void)hipStreamSynchronize(st);                          // (launch 1 may still read the block the next call rewrites)
+        return rc;
+    }
+    subset_journal(b, K, flags, b->h_out, out_dtype, stream, mc_call);
+    const double t_launched = now_us();
+    bool seen = false, recovered = false;
+    if (words) {
+        // ~50 ms of looking, then the stream's own completion (as ape_streams_frame_host)
+        volatile unsigned* dw = h_done;
+        for (long spin = 0; spin < 20000000L && !seen; ++spin) {
+            seen = true;
+            for (int k = 0; k < K; ++k) seen = seen && dw[k] == b->hs_done_val;
+            if (!seen) __builtin_ia32_pause();
+        }
+        std::atomic_thread_fence(std::memory_order_acquire);
+    }
+    const bool fell_through = !seen && words;
+    if (!seen) HIP_TRY(hipStreamSynchronize(st));
+    if (*(volatile unsigned*)b->h_status != 0u) {
+        // the regressor launch gave up (bounded spins): the frame is the bank's newest, its windows and descriptors are on the device --
+        // regressor and post-filter again on the kernels that need no co-residency, into the same pinned rows
+        recovered = true;
+        HIP_TRY(hipStreamSynchronize(st));
+        if (int rc = ape_model_recover(m)) return rc;
+    } else {
+        journal_clear(m);                                        // (read behind the frame's kernels on the frame's stream: what the journal holds is done)
+    }
+    const double t_there = now_us();
+    memcpy(out_host, b->h_out, (size_t)K * row_w * esz);
+    const double t_end = now_us();
+    if (b->fs_trace.empty()) b->fs_trace.resize(4096 * 3, 0.0f);
+    float* tr = b->fs_trace.data() + (b->fs_frames % 4096) * 3;
+    tr[0] = (float)(t_launched - t_begin); tr[1] = (float)(t_there - t_launched); tr[2] = (float)(t_end - t_there);
+    b->fs_frames += 1;
+    b->fs_fallback += fell_through ? 1 : 0;
+    b->fs_recovered += recovered ? 1 : 0;
     return APE_OK;
 }
 

@@ -509,6 +509,7 @@ hipError_t ape_launch_replay_msg(const ReplayMsgParams& p, bool tail, hipStream_
 hipError_t ape_launch_replay_carry_rows(const float* state_in, int R, int words, int x_words, int stack_words, float* y_in, hipStream_t stream);
 hipError_t ape_launch_replay_state_out(const ReplayStateOutParams& p, hipStream_t stream);
 hipError_t ape_launch_subset_rows(const SubsetRowsParams& p, hipStream_t stream);
+hipError_t ape_launch_subset_rows_host(const SubsetRowsParams& p, SubsetDesc* land, hipStream_t stream);
 // ring order <-> the canonical time-ordered records of the listed streams, one launch each (stream_state.hip)
 hipError_t ape_launch_state_export(const StateParams& p, hipStream_t stream);
 hipError_t ape_launch_state_import(const StateParams& p, hipStream_t stream);

@@ -174,6 +174,10 @@ struct ape_streams {
     SubsetDesc* sub_stage = nullptr;  // [APE_SUBSET_STAGES][S]
     hipEvent_t sub_ev[APE_SUBSET_STAGES] = {};
     int sub_next = 0;
+    // host subset frames (ape_streams_frame_subset_host): ONE pinned, device-visible block the host writes and launch 1 reads --
+    // [64] completion words the post kernel writes, [S] descriptors, [S, 57] raw rows; reused every frame (the call is blocking)
+    char* hs_block = nullptr;
+    unsigned hs_done_val = 0;    // the value this frame's completion words are awaited with
     // state hand-over (ape_streams_export / import): descriptors of their own on the device -- sub_desc belongs to the
     // newest subset frame, which ape_model_recover may still re-issue; staged through the pinned ring above
     StateDesc* state_desc = nullptr;  // [S]

@@ -252,6 +252,7 @@ struct ape_fk_bank {
     void* h_out = nullptr;
     unsigned* h_done = nullptr;
     unsigned done_val = 0;
+    char* hs_block = nullptr;          // frame_subset_host: ONE pinned block of completion words, descriptors and rows
     ApeBodyTable bodies;               // per-stream bodies, component-major [9,S] on the device (off until ape_fk_bank_set_bodies)
 };
 
@@ -267,6 +268,7 @@ void bank_free(ape_fk_bank* b) {
     if (b->h_rows) (void)hipHostFree(b->h_rows);
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->h_done) (void)hipHostFree(b->h_done);
+    if (b->hs_block) (void)hipHostFree(b->hs_block);
     delete b;
 }
 
@@ -293,8 +295,9 @@ void leave_uniform(ape_fk_bank* b) {
 }
 
 // one frame for K streams (streams_host nullptr: all S in order) on `st`; the counters move on once the launch is enqueued
+// pinned_desc (host subset frames): the descriptors are written there and the kernel reads them from there -- no copy, no event
 int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* streams_host, int32_t K, void* out, int32_t out_dtype,
-               hipStream_t st, unsigned* done, const char* what) {
+               hipStream_t st, unsigned* done, const char* what, FkDesc* pinned_desc = nullptr) {
     FkBankParams p{};
     p.rows = rows; p.ring = b->ring; p.out = out; p.K = K; p.smooth = b->smooth;
     p.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
@@ -307,17 +310,20 @@ int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* s
         if (streams_host) leave_uniform(b);
         // the descriptors into the next pinned slot -- once the copy that last read it has completed
         const int k = b->next;
-        FK_TRY(hipEventSynchronize(b->ev[k]));
-        FkDesc* h = b->stage + (size_t)k * b->S;
+        if (!pinned_desc) FK_TRY(hipEventSynchronize(b->ev[k]));
+        FkDesc* h = pinned_desc ? pinned_desc : b->stage + (size_t)k * b->S;
         for (int j = 0; j < K; ++j) {
             const int s = streams_host ? streams_host[j] : j;
             const long long c = b->cnt[s];
             h[j] = FkDesc{s, (int)(c % b->smooth), c == 0 ? 1 : 0, 0};
         }
-        FK_TRY(hipMemcpyAsync(b->desc, h, (size_t)K * sizeof(FkDesc), hipMemcpyHostToDevice, st));
-        FK_TRY(hipEventRecord(b->ev[k], st));
-        b->next = (k + 1) % FK_STAGES;
-        p.desc = b->desc;
+        if (pinned_desc) p.desc = pinned_desc;
+        else {
+            FK_TRY(hipMemcpyAsync(b->desc, h, (size_t)K * sizeof(FkDesc), hipMemcpyHostToDevice, st));
+            FK_TRY(hipEventRecord(b->ev[k], st));
+            b->next = (k + 1) % FK_STAGES;
+            p.desc = b->desc;
+        }
     }
     const double* const none = nullptr;
     const hipError_t e = b->bodies.on() ? launch_typed(ape_fk_bank_kernel<float, true>, ape_fk_bank_kernel<double, true>, out_dtype, K, st, p, (const double*)b->bodies.dev, b->S)
@@ -427,6 +433,50 @@ int ape_fk_bank_frame_host(ape_fk_bank_t* b, int32_t kind, const float* rows_hos
     }
     if (!seen) FK_TRY(hipStreamSynchronize(st));
     memcpy(out_host, b->h_out, (size_t)b->S * 25 * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
+    return APE_OK;
+}
+
+// Host subset frame: the frame is ONE kernel, so the pinned block is all it reads -- rows and descriptors -- and all
+// it writes: the messages and, for K <= 64, a completion word per entry behind each.  Nothing runs behind that kernel, so the
+// descriptors need not land in b->desc.  Layout of the block: [64] words, [S] descriptors, [S, 55] rows; messages in h_out.
+int ape_fk_bank_frame_subset_host(ape_fk_bank_t* b, int32_t kind, const float* rows_host, const int32_t* streams_host, int32_t K,
+                                  void* out_host, int32_t out_dtype, void* stream) {
+    if (!b || !rows_host || !out_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame_subset_host: NULL argument");
+    if (int rc = check_kind(kind, "fk_bank_frame_subset_host")) return rc;
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame_subset_host: unknown dtype selector");
+    if (int rc = check_list(b, streams_host, K, "fk_bank_frame_subset_host")) return rc;
+    FK_TRY(hipSetDevice(b->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "fk_bank_frame_subset_host")) return rc;
+    if (K == 0) return APE_OK;
+    if (!b->hs_block) {
+        const size_t bytes = 64 * sizeof(unsigned) + (size_t)b->S * sizeof(FkDesc) + (size_t)b->S * FK_WIDTH * sizeof(float);
+        FK_TRY(hipHostMalloc((void**)&b->hs_block, bytes, hipHostMallocCoherent | hipHostMallocMapped));
+        memset(b->hs_block, 0, bytes);
+    }
+    if (!b->h_out) FK_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * 25 * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
+    unsigned* const h_done = reinterpret_cast<unsigned*>(b->hs_block);
+    FkDesc* const h_desc = reinterpret_cast<FkDesc*>(b->hs_block + 64 * sizeof(unsigned));
+    float* const h_rows = reinterpret_cast<float*>(b->hs_block + 64 * sizeof(unsigned) + (size_t)b->S * sizeof(FkDesc));
+    const bool words = K <= 64;
+    b->done_val += 1;
+    if (b->done_val == 0) b->done_val = 1;
+    memcpy(h_rows, rows_host, (size_t)K * FK_WIDTH * sizeof(float));
+    if (int rc = bank_frame(b, kind, h_rows, streams_host, K, b->h_out, out_dtype, st, words ? h_done : nullptr, "fk_bank_frame_subset_host", h_desc))
+        return rc;
+    bool seen = false;
+    if (words) {
+        // ~50 ms of looking (a frame takes microseconds); then the stream's own completion
+        volatile unsigned* dw = h_done;
+        for (long spin = 0; spin < 20000000L && !seen; ++spin) {
+            seen = true;
+            for (int k = 0; k < K; ++k) seen = seen && dw[k] == b->done_val;
+            if (!seen) __builtin_ia32_pause();
+        }
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    }
+    if (!seen) FK_TRY(hipStreamSynchronize(st));
+    memcpy(out_host, b->h_out, (size_t)K * 25 * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
     return APE_OK;
 }
 

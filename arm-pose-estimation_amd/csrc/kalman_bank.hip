@@ -82,10 +82,16 @@ struct KbTailParams {
     double yy_m[DX], yy_s[DX], body[9];
 };
 
-__global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_head_kernel(const KbHeadParams p) {
+// LAND (host subset frames): p.rows and p.desc are the frame's pinned staging block in host memory; entry j's descriptor
+// is also stored to land[j], the bank's device table, where the tail reads it
+template <bool LAND = false>
+__global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_head_kernel(const KbHeadParams p, KbDesc* __restrict__ land) {
     __shared__ double xx[RAW];
     const int j = blockIdx.x, tid = threadIdx.x;
     const KbDesc d = p.desc ? p.desc[j] : KbDesc{j, p.cold_all, j, j};
+    if constexpr (LAND) {
+        if (tid == 64) land[j] = d;
+    }
     const bool cold = d.cold != 0;
     const int c = cold ? 0 : p.cnt[d.stream];
     const int E = p.E, W = p.W;
@@ -98,7 +104,7 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_head_kernel(const Kb
             if (p.big_endian) v = __builtin_bit_cast(float, __builtin_bswap32(__builtin_bit_cast(unsigned, v)));
             r[k] = v;
         }
-        ape_parsedev::parse_row(r, KB_WIDTH, APE_PARSE_WATCH_PHONE_POCKET, xx);
+        [[clang::always_inline]] ape_parsedev::parse_row(r, KB_WIDTH, APE_PARSE_WATCH_PHONE_POCKET, xx);     // (inline in both instantiations, as in the one)
     } else if (tid >= 64) {
         // beside it, waves 1-3: the state history in time order.  The ring's oldest entry sits in slot c mod W (the slot this frame's
         // tail overwrites); 8-byte pieces (a state is 14 floats = 56 bytes).  Cold start: zeros, and the ring is zeroed for the frames to come.
@@ -146,8 +152,11 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_head_kernel(const Kb
 // the record while thread 0 composes the message: lanes 0 / 1 the two origins, lanes 2 .. 4 one joint's angle each against the
 // message's quaternion, which they form from `red` by thread 0's very operations (IEEE operations, contraction off: the same bits).
 // A parameter of the template: KbTailParams and the other forms' object code stay what they were.
-template <typename TMsg, bool TAB = false, bool SPR = false>
-__global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const KbTailParams p, const double* __restrict__ bodies) {
+// DONE (host subset frames of up to 64 entries): p.out and p.n_rows are pinned host memory; behind the entry's row and
+// count -- system-scope release -- the workgroup writes word j of dn.words, which the host is watching (stream_post_device.h, done_out)
+struct KbDone { unsigned* words; unsigned val; };
+template <typename TMsg, bool TAB = false, bool SPR = false, bool DONE = false>
+__global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const KbTailParams p, const double* __restrict__ bodies, const KbDone dn) {
     __shared__ int ent_slot[KB_MAX_SMOOTH], ent_first[KB_MAX_SMOOTH + 1];   // stack entries, oldest first: ring slot (-1: this frame's), first stacked row
     __shared__ double ref_s[3][4], e0_s[21], red[KB_BLOCK / 64][12];
     __shared__ double spr_red[SPR ? KB_BLOCK / 64 : 1][SPR ? 48 : 1];       // SPR: the waves' partial spread sums (unused otherwise)
@@ -323,6 +332,11 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_bank_tail_kernel(const Kb
         if (next >= (1 << 30)) next -= p.wrap;
         p.cnt[s] = next;
     }
+    if constexpr (DONE) {
+        __threadfence_system();
+        __syncthreads();
+        if (tid == 0) __hip_atomic_store(dn.words + j, dn.val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
 }
 
 // ---- state hand-over: a stream's rings <-> its canonical record, every part oldest first ---------------------------
@@ -470,6 +484,9 @@ struct ape_kalman_bank {
     float* h_rows = nullptr;
     void* h_out = nullptr;
     int* h_n = nullptr;
+    // frame_subset_host: ONE pinned block of [64] completion words, [S] descriptors and [S, 55] rows; the value awaited
+    char* hs_block = nullptr;
+    unsigned hs_done_val = 0;
     ApeBodyTable bodies;              // per-stream bodies [S,9] (off until ape_kalman_bank_set_bodies)
     // state hand-over: min(frames since the cold start, W + 1) per stream, kept where `pending` is kept, and the
     // export / import kernel's own descriptors (b->desc may still be read by a frame in flight); allocated by the first hand-over
@@ -487,7 +504,7 @@ void bank_free(ape_kalman_bank* b) {
     void* dev[] = {b->xwin, b->state, b->yring, b->nring, b->cnt, b->raw, b->dense, b->corrected, b->ensz, b->mcorr, b->mpred, b->z, b->desc,
                    b->ks_desc};
     for (void* q : dev) if (q) (void)hipFree(q);
-    void* host[] = {b->stage, b->h_rows, b->h_out, b->h_n, b->ks_stage};
+    void* host[] = {b->stage, b->h_rows, b->h_out, b->h_n, b->ks_stage, b->hs_block};
     for (void* q : host) if (q) (void)hipHostFree(q);
     for (int i = 0; i < KB_STAGES; ++i) {
         if (b->ev[i]) (void)hipEventDestroy(b->ev[i]);
@@ -554,9 +571,11 @@ int check_list(const ape_kalman_bank* b, const int32_t* streams_host, int32_t K,
 }
 
 // head -> model -> tail for K list entries on `st`.  desc_dev nullptr: entry j = stream j, row j, all cold or none
+// hf (host subset frames): the head reads hf->desc (pinned) and lands it in desc_dev; hf->done: the tail's completion words, or nullptr
+struct KbHostFrame { const KbDesc* desc; unsigned* done; unsigned done_val; };
 int frame_launch(ape_kalman_bank* b, int big_endian, const float* rows, const KbDesc* desc_dev, int cold_all, int32_t K,
                  const float* noise, const float* init_noise, uint32_t flags, void* out, int32_t out_dtype, int* n_rows, float* y,
-                 hipStream_t st, const char* what) {
+                 hipStream_t st, const char* what, const KbHostFrame* hf = nullptr) {
     b->calls += 1;
     const unsigned long long seed = b->seed + 0xD1342543DE82EF95ull * b->calls;       // a key per call
     KbHeadParams h{};
@@ -564,7 +583,10 @@ int frame_launch(ape_kalman_bank* b, int big_endian, const float* rows, const Kb
     h.K = K; h.E = b->E; h.W = b->W; h.big_endian = big_endian; h.normalize = b->normalize ? 1 : 0; h.cold_all = cold_all;
     memcpy(h.xx_m, b->xx_m, sizeof(h.xx_m));
     memcpy(h.xx_s, b->xx_s, sizeof(h.xx_s));
-    hipLaunchKernelGGL(ape_kalman_bank_head_kernel, dim3(K), dim3(KB_BLOCK), 0, st, h);
+    if (hf) {
+        h.desc = hf->desc;
+        hipLaunchKernelGGL(ape_kalman_bank_head_kernel<true>, dim3(K), dim3(KB_BLOCK), 0, st, h, const_cast<KbDesc*>(desc_dev));
+    } else hipLaunchKernelGGL(ape_kalman_bank_head_kernel<false>, dim3(K), dim3(KB_BLOCK), 0, st, h, (KbDesc*)nullptr);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: head launch failed: %s", what, hipGetErrorString(e));
     if (int rc = ape_kalman_forward(b->model, b->raw, b->dense, K, seed, noise, b->corrected, b->mcorr, b->mpred, b->z, b->ensz, st)) return rc;
@@ -581,15 +603,21 @@ int frame_launch(ape_kalman_bank* b, int big_endian, const float* rows, const Kb
     memcpy(t.yy_s, b->yy_s, sizeof(t.yy_s));
     memcpy(t.body, b->body, sizeof(t.body));
     // one instantiation per (message type, body table, record)
-    using TailFn = void (*)(const KbTailParams, const double*);
+    using TailFn = void (*)(const KbTailParams, const double*, const KbDone);
     static const TailFn tails[2][2][2] = {
         {{ape_kalman_bank_tail_kernel<double, false, false>, ape_kalman_bank_tail_kernel<double, false, true>},
          {ape_kalman_bank_tail_kernel<double, true, false>, ape_kalman_bank_tail_kernel<double, true, true>}},
         {{ape_kalman_bank_tail_kernel<float, false, false>, ape_kalman_bank_tail_kernel<float, false, true>},
          {ape_kalman_bank_tail_kernel<float, true, false>, ape_kalman_bank_tail_kernel<float, true, true>}}};
+    static const TailFn tails_done[2][2][2] = {
+        {{ape_kalman_bank_tail_kernel<double, false, false, true>, ape_kalman_bank_tail_kernel<double, false, true, true>},
+         {ape_kalman_bank_tail_kernel<double, true, false, true>, ape_kalman_bank_tail_kernel<double, true, true, true>}},
+        {{ape_kalman_bank_tail_kernel<float, false, false, true>, ape_kalman_bank_tail_kernel<float, false, true, true>},
+         {ape_kalman_bank_tail_kernel<float, true, false, true>, ape_kalman_bank_tail_kernel<float, true, true, true>}}};
     const bool tab = b->bodies.on();
-    hipLaunchKernelGGL(tails[out_dtype == APE_F32 ? 1 : 0][tab ? 1 : 0][spr ? 1 : 0], dim3(K), dim3(KB_BLOCK), 0, st, t,
-                       tab ? (const double*)b->bodies.dev : (const double*)nullptr);
+    const bool done = hf != nullptr && hf->done != nullptr;
+    hipLaunchKernelGGL((done ? tails_done : tails)[out_dtype == APE_F32 ? 1 : 0][tab ? 1 : 0][spr ? 1 : 0], dim3(K), dim3(KB_BLOCK), 0, st, t,
+                       tab ? (const double*)b->bodies.dev : (const double*)nullptr, done ? KbDone{hf->done, hf->done_val} : KbDone{nullptr, 0u});
     e = hipGetLastError();
     if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: tail launch failed: %s", what, hipGetErrorString(e));
     return APE_OK;
@@ -597,10 +625,19 @@ int frame_launch(ape_kalman_bank* b, int big_endian, const float* rows, const Kb
 
 // one frame of a bank: the pending cold starts of the listed streams travel with the list
 int bank_frame(ape_kalman_bank* b, int32_t kind, const float* rows, const int32_t* streams_host, int32_t K, const float* noise,
-               const float* init_noise, uint32_t flags, void* out, int32_t out_dtype, int* n_rows, float* y, hipStream_t st, const char* what) {
+               const float* init_noise, uint32_t flags, void* out, int32_t out_dtype, int* n_rows, float* y, hipStream_t st, const char* what,
+               KbDesc* pinned_desc = nullptr, unsigned* done = nullptr, unsigned done_val = 0) {
     const KbDesc* desc_dev = nullptr;
     int cold_all = 0;
-    if (!streams_host && (b->n_pending == 0 || b->n_pending == b->S)) cold_all = b->n_pending ? 1 : 0;
+    KbHostFrame hf{pinned_desc, done, done_val};
+    if (pinned_desc) {
+        // host subset frame: the list into the frame's pinned block, which the head kernel reads and lands in b->desc -- no copy, no event
+        for (int j = 0; j < K; ++j) {
+            const int s = streams_host ? streams_host[j] : j;
+            pinned_desc[j] = KbDesc{s, b->pending[s] ? 1 : 0, j, j};
+        }
+        desc_dev = b->desc;
+    } else if (!streams_host && (b->n_pending == 0 || b->n_pending == b->S)) cold_all = b->n_pending ? 1 : 0;
     else {
         // the list into the next pinned slot -- once the copy that last read it has completed
         const int k = b->next;
@@ -616,7 +653,7 @@ int bank_frame(ape_kalman_bank* b, int32_t kind, const float* rows, const int32_
         desc_dev = b->desc;
     }
     if (int rc = frame_launch(b, (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0, rows, desc_dev, cold_all, K, noise, init_noise, flags, out, out_dtype,
-                              n_rows, y, st, what))
+                              n_rows, y, st, what, pinned_desc ? &hf : nullptr))
         return rc;
     for (int j = 0; j < K; ++j) {
         const int s = streams_host ? streams_host[j] : j;
@@ -871,6 +908,58 @@ int ape_kalman_bank_frame_host(ape_kalman_bank_t* b, int32_t kind, const float* 
     const size_t w = ((flags & APE_FLAG_PACKED_MSG) ? width : 25) + ((flags & APE_FLAG_SPREAD) ? APE_SPREAD_WIDTH : 0);
     memcpy(out_host, b->h_out, (size_t)b->S * w * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
     memcpy(n_rows_host, b->h_n, (size_t)b->S * sizeof(int));
+    return APE_OK;
+}
+
+// Host subset frame: the head kernel reads rows and list from the pinned block and lands the list in b->desc for the
+// tail, which writes rows, counts and -- K <= 64 -- a completion word per entry into pinned memory.  BLOCKING; the block is reused.
+int ape_kalman_bank_frame_subset_host(ape_kalman_bank_t* b, int32_t kind, const float* rows_host, const int32_t* streams_host, int32_t K,
+                                      uint32_t flags, void* out_host, int32_t out_dtype, int32_t* n_rows_host, void* stream) {
+    if (!b || !rows_host || !out_host || !n_rows_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_subset_host: NULL argument");
+    if (int rc = check_kind(kind, "kalman_bank_frame_subset_host")) return rc;
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_subset_host: unknown dtype selector");
+    if (flags & ~KB_FLAGS)
+        return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_subset_host: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
+    if (int rc = check_list(b, streams_host, K, "kalman_bank_frame_subset_host")) return rc;
+    KB_TRY(hipSetDevice(b->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "kalman_bank_frame_subset_host")) return rc;
+    if (K == 0) return APE_OK;
+    const size_t width = 25 + 6 * (size_t)b->smooth * b->E;                      // (h_out: room for the widest row, record included)
+    if (!b->hs_block) {
+        const size_t bytes = 64 * sizeof(unsigned) + (size_t)b->S * sizeof(KbDesc) + (size_t)b->S * KB_WIDTH * sizeof(float);
+        KB_TRY(hipHostMalloc((void**)&b->hs_block, bytes, hipHostMallocCoherent | hipHostMallocMapped));
+        memset(b->hs_block, 0, bytes);
+    }
+    if (!b->h_out) KB_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * (width + APE_SPREAD_WIDTH) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
+    if (!b->h_n) KB_TRY(hipHostMalloc((void**)&b->h_n, (size_t)b->S * sizeof(int), hipHostMallocCoherent | hipHostMallocMapped));
+    unsigned* const h_done = reinterpret_cast<unsigned*>(b->hs_block);
+    KbDesc* const h_desc = reinterpret_cast<KbDesc*>(b->hs_block + 64 * sizeof(unsigned));
+    float* const h_rows = reinterpret_cast<float*>(b->hs_block + 64 * sizeof(unsigned) + (size_t)b->S * sizeof(KbDesc));
+    const bool words = K <= 64;
+    b->hs_done_val += 1;
+    if (b->hs_done_val == 0) b->hs_done_val = 1;
+    memcpy(h_rows, rows_host, (size_t)K * KB_WIDTH * sizeof(float));
+    if (int rc = bank_frame(b, kind, h_rows, streams_host, K, nullptr, nullptr, flags, b->h_out, out_dtype, b->h_n, nullptr, st,
+                            "kalman_bank_frame_subset_host", h_desc, words ? h_done : nullptr, b->hs_done_val)) {
+        (void)hipStreamSynchronize(st);                                          // (a launched head may still read the block the next call rewrites)
+        return rc;
+    }
+    bool seen = false;
+    if (words) {
+        // ~50 ms of looking, then the stream's own completion (as ape_streams_frame_host)
+        volatile unsigned* dw = h_done;
+        for (long spin = 0; spin < 20000000L && !seen; ++spin) {
+            seen = true;
+            for (int k = 0; k < K; ++k) seen = seen && dw[k] == b->hs_done_val;
+            if (!seen) __builtin_ia32_pause();
+        }
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    }
+    if (!seen) KB_TRY(hipStreamSynchronize(st));
+    const size_t w = ((flags & APE_FLAG_PACKED_MSG) ? width : 25) + ((flags & APE_FLAG_SPREAD) ? APE_SPREAD_WIDTH : 0);
+    memcpy(out_host, b->h_out, (size_t)K * w * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
+    memcpy(n_rows_host, b->h_n, (size_t)K * sizeof(int));
     return APE_OK;
 }
 

@@ -22,7 +22,10 @@ constexpr int SB_ROWS = 8;                      // list entries per workgroup: a
                                                 // few entries per block = more CUs busy and a short copy loop behind the chain
 constexpr int XW = 39;                          // feature row stride in LDS (odd: conflict-free per-thread rows)
 
-__global__ __launch_bounds__(SB_BLOCK) void ape_subset_rows_kernel(const SubsetRowsParams p) {
+// LAND (host subset frames): p.rows and p.desc are the frame's pinned staging block in host memory; the entries' descriptors
+// are also stored to `land`, the bank's device table, where the frame's later launches (and a re-issue) read them
+template <bool LAND>
+__global__ __launch_bounds__(SB_BLOCK) void ape_subset_rows_kernel(const SubsetRowsParams p, SubsetDesc* __restrict__ land) {
     __shared__ float slab[SB_ROWS * 57];
     __shared__ double xout[SB_ROWS * XW];
     __shared__ int dsc[SB_ROWS][3];             // stream, ring slot, cold
@@ -38,9 +41,10 @@ __global__ __launch_bounds__(SB_BLOCK) void ape_subset_rows_kernel(const SubsetR
     if (tid < n) {
         const SubsetDesc d = p.desc[r0 + tid];
         dsc[tid][0] = d.stream; dsc[tid][1] = d.slot; dsc[tid][2] = d.cold;
+        if constexpr (LAND) land[r0 + tid] = d;
     }
     __syncthreads();
-    if (tid < n) parse_row(slab + tid * 57, p.width, p.kind, xout + tid * XW);
+    if (tid < n) [[clang::always_inline]] parse_row(slab + tid * 57, p.width, p.kind, xout + tid * XW);     // (two kernels call it: inline in both, as in the one)
     __syncthreads();
     // element (entry rr, step t, feature i) of the time-ordered window: step T-1 is the new row, step t < T-1 ring slot slot+1+t (mod T);
     // consecutive threads = consecutive elements of one window, so every copy's stores are contiguous
@@ -150,7 +154,14 @@ hipError_t launch_subset_post_bodies(const StreamPostParams& p, const SubsetDesc
 
 hipError_t ape_launch_subset_rows(const SubsetRowsParams& p, hipStream_t stream) {
     if (p.K < 1) return hipSuccess;
-    hipLaunchKernelGGL(ape_subset_rows_kernel, dim3((p.K + SB_ROWS - 1) / SB_ROWS), dim3(SB_BLOCK), 0, stream, p);
+    hipLaunchKernelGGL(ape_subset_rows_kernel<false>, dim3((p.K + SB_ROWS - 1) / SB_ROWS), dim3(SB_BLOCK), 0, stream, p, (SubsetDesc*)nullptr);
+    return hipGetLastError();
+}
+
+// a host subset frame's first launch: rows and descriptors from pinned host memory, the descriptors landed in `land` [K] on the device
+hipError_t ape_launch_subset_rows_host(const SubsetRowsParams& p, SubsetDesc* land, hipStream_t stream) {
+    if (p.K < 1) return hipSuccess;
+    hipLaunchKernelGGL(ape_subset_rows_kernel<true>, dim3((p.K + SB_ROWS - 1) / SB_ROWS), dim3(SB_BLOCK), 0, stream, p, land);
     return hipGetLastError();
 }
 

@@ -176,6 +176,13 @@ SIGNATURES["ape_kalman_bank_get_draw_position"] = (C.c_int, [C.c_void_p, C.POINT
 SIGNATURES["ape_kalman_bank_set_draw_position"] = (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64])
 SIGNATURES["ape_kalman_replay_resume"] = (C.c_int, SIGNATURES["ape_kalman_replay_bodies"][1] +
                                           [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64])
+# host subset frames: bank, kind, rows_host, streams_host, K, [flags,] out_host, out_dtype, [n_rows_host,] HIP stream
+SIGNATURES["ape_streams_frame_subset_host"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p,
+                                                         C.c_int32, C.c_void_p])
+SIGNATURES["ape_fk_bank_frame_subset_host"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                                         C.c_void_p])
+SIGNATURES["ape_kalman_bank_frame_subset_host"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p,
+                                                             C.c_int32, C.c_void_p, C.c_void_p])
 
 _lib = None
 

@@ -82,6 +82,61 @@ def _get_bodies(bank, entry: str) -> np.ndarray:
     return out
 
 
+def _host_rows(rows, K: int, width: int) -> np.ndarray:
+    """the rows of a ``frame_host`` call: a contiguous float32 host array ``[K, width]``"""
+    if isinstance(rows, torch.Tensor):
+        raise UserWarning("frame_host takes host rows (a numpy array); device tensors go to frame()")
+    a = np.asarray(rows)
+    if a.dtype != np.float32 or a.shape != (K, width):
+        raise UserWarning(f"frame_host wants float32 rows [{K},{width}] for {K} streams, got {a.dtype} {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def tick_rounds(stream_ids):
+    """The round splitter of ``tick`` (pure: no bank, no GPU).  ``stream_ids``: the streams of a bag of rows in arrival order, repeats
+    allowed.  -> ``(rounds, order)``: ``rounds[r]`` int64 positions into the bag of the r-th row of every stream that has one, in
+    arrival order (so the streams of one round are distinct and every stream's rows keep their order over the rounds); ``order``
+    the inverse permutation: ``np.concatenate(rounds)[order]`` is ``arange(n)``, i.e. outputs concatenated round by round and
+    indexed with ``order`` are back in input order."""
+    ids = np.asarray(stream_ids)
+    if ids.ndim != 1 or (ids.size and not np.issubdtype(ids.dtype, np.integer)):
+        raise UserWarning(f"stream_ids must be a sequence of stream indices, got {stream_ids!r}")
+    n = int(ids.shape[0])
+    if n == 0:
+        return [], np.zeros((0,), dtype=np.int64)
+    # occurrence number of every entry among the entries of its stream (stable sort: arrival order within a stream)
+    by_stream = np.argsort(ids, kind="stable")
+    sorted_ids = ids[by_stream]
+    first = np.flatnonzero(np.r_[True, sorted_ids[1:] != sorted_ids[:-1]])
+    occ = np.empty((n,), dtype=np.int64)
+    occ[by_stream] = np.arange(n) - np.repeat(first, np.diff(np.r_[first, n]))
+    rounds = [np.flatnonzero(occ == r) for r in range(int(occ.max()) + 1)]
+    order = np.empty((n,), dtype=np.int64)
+    order[np.concatenate(rounds)] = np.arange(n)
+    return rounds, order
+
+
+def tick(bank, rows, stream_ids, **kw):
+    """The bag of one receive-loop iteration through a bank's ``frame_host``: ``rows`` float32 host ``[n, width]``, ``stream_ids`` the
+    stream of every row in ARRIVAL order -- a stream may appear more than once.  The bag is split into rounds (``tick_rounds``), one
+    ``frame_host(rows[round], stream_ids[round], **kw)`` runs per round, and the outputs come back in input order (a tuple of arrays
+    where ``frame_host`` returns one, e.g. ``(rows, n_rows)`` of a Kalman bank with ``datagrams``).  Every row is processed as
+    ``process_row`` would, in per-stream arrival order; the live loop's queue skip-ahead (estimator.py:166-173 drops all but the
+    newest queued row) is NOT applied, as in the replay.  Mode rules are ``frame_host``'s; Monte-Carlo samples depend on a row's
+    position within its round."""
+    ids = np.asarray(stream_ids)
+    rounds, order = tick_rounds(ids)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[0] != ids.shape[0]:
+        raise UserWarning(f"tick wants one row per stream id: {ids.shape[0]} ids, rows {rows.shape}")
+    if not rounds:
+        return bank.frame_host(rows, ids, **kw)
+    outs = [bank.frame_host(np.ascontiguousarray(rows[r]), ids[r], **kw) for r in rounds]
+    if isinstance(outs[0], tuple):
+        return tuple(np.concatenate([o[i] for o in outs])[order] for i in range(len(outs[0])))
+    return np.concatenate(outs)[order]
+
+
 _SET_BODIES_DOC = """Per-stream body measurements (DESIGN.md 4.24): ``bodies`` float64 ``[K, 9]`` (``[larm_vec, uarm_vec,
         uarm_orig_rh]`` per row) or a sequence of K bonemap-like objects / ``None`` (the defaults); ``streams`` K distinct indices, or
         ``None`` for all S streams in order.  From the next frame enqueued on the current stream on, stream s takes its body from row s
@@ -207,6 +262,48 @@ class StreamBank:
         hip.check(hip.lib().ape_streams_frame_subset(self._handle, k, C.c_void_p(rd.data_ptr()), C.c_void_p(idx.ctypes.data), K, flags,
                                                      C.c_void_p(out.data_ptr()), sel, self._stream()), "ape_streams_frame_subset")
         return out
+
+    def frame_host(self, rows, streams, kind: int, big_endian: bool = False, datagrams: bool = False, spread: bool = False) -> np.ndarray:
+        """``frame`` host to host (``ape_streams_frame_subset_host``): ``rows`` a float32 HOST array ``[K, 55|28]``,
+        row j for stream ``streams[j]`` (K distinct indices) -> a fresh host array with the widths, dtypes and bits of ``frame``.
+        BLOCKING: the datagrams are there when the call returns, an aborted cooperative launch has been re-issued (no ``recover()``
+        needed) and the frame is counted by ``frame_stats``.  No copy command and no event go onto the stream.  Mode rules are those
+        of ``frame``: the first call puts the bank into per-stream mode (``push_rows`` / ``push_features`` / ``step`` refused until
+        ``reset()``); ``frame`` and ``frame_host`` mix freely.  Monte-Carlo samples still depend on a stream's list position."""
+        hip, C = self._hip, self._C
+        if kind not in hip.PARSE_SHAPES:
+            raise UserWarning(f"unknown row kind {kind}")
+        idx = self._indices(streams)
+        K = int(idx.shape[0])
+        rh = _host_rows(rows, K, hip.PARSE_SHAPES[kind][0])
+        n = self._smooth * self._n_mc
+        packed = datagrams and n > 1
+        w = (25 + 6 * n if packed else 25) + (hip.SPREAD_WIDTH if spread else 0)
+        dtype, sel = (np.float32, hip.F32) if datagrams else ((np.float32 if self._dtype == torch.float32 else np.float64), self._sel)
+        out = np.empty((K, w), dtype=dtype)
+        if K == 0:
+            return out
+        flags = self._flags | (hip.FLAG_PACKED_MSG if packed else 0) | (hip.FLAG_SPREAD if spread else 0)
+        k = kind | (hip.PARSE_BIG_ENDIAN if big_endian else 0)
+        hip.check(hip.lib().ape_streams_frame_subset_host(self._handle, k, C.c_void_p(rh.ctypes.data), C.c_void_p(idx.ctypes.data), K, flags,
+                                                          C.c_void_p(out.ctypes.data), sel, self._stream()), "ape_streams_frame_subset_host")
+        return out
+
+    def frame_stats(self, reset: bool = False) -> dict:
+        """where the host frames' time went (``ape_streams_frame_stats``): frames counted, how many fell through to a stream
+        synchronisation, how many were recovered, and per frame (the last <= 4096) the microseconds of ``launch`` (rows and
+        descriptors into pinned staging + the launch calls), ``wait`` (until the completion words / the stream) and ``copy``"""
+        C = self._C
+
+        class _FS(C.Structure):
+            _fields_ = [("frames", C.c_uint64), ("fallback_syncs", C.c_uint64), ("recovered", C.c_uint64)]
+        fs, n = _FS(), C.c_int32(0)
+        trace = np.zeros((4096, 3), dtype=np.float32)
+        self._hip.check(self._hip.lib().ape_streams_frame_stats(self._handle, C.byref(fs), C.c_void_p(trace.ctypes.data), 4096, C.byref(n),
+                                                                1 if reset else 0), "ape_streams_frame_stats")
+        t = trace[:n.value]
+        return {"frames": int(fs.frames), "fallback_syncs": int(fs.fallback_syncs), "recovered": int(fs.recovered),
+                "launch_us": t[:, 0].copy(), "wait_us": t[:, 1].copy(), "copy_us": t[:, 2].copy()}
 
     # ---- state hand-over (DESIGN.md 4.26): a stream's window and stack leave the bank and enter another ----
     def state_desc(self) -> dict:
@@ -433,6 +530,23 @@ class FkStreamBank:
                                               C.c_void_p(out.data_ptr()), self._sel, self._stream()), "ape_fk_bank_frame")
         return out
 
+    def frame_host(self, rows, streams, big_endian: bool = False) -> np.ndarray:
+        """``frame`` host to host (``ape_fk_bank_frame_subset_host``): float32 HOST rows ``[K, 55]`` -> a fresh host
+        array ``[K, 25]`` of the bank's dtype with the bits of ``frame``.  BLOCKING; no copy command and no event on the stream.
+        Lockstep frames, ``frame`` and ``frame_host`` mix freely: every stream keeps its own count."""
+        hip, C = self._hip, self._C
+        idx = self._indices(streams)
+        K = int(idx.shape[0])
+        rh = _host_rows(rows, K, 55)
+        out = np.empty((K, 25), dtype=np.float32 if self._dtype == torch.float32 else np.float64)
+        if K == 0:
+            return out
+        kind = hip.PARSE_WATCH_PHONE_UARM | (hip.PARSE_BIG_ENDIAN if big_endian else 0)
+        hip.check(hip.lib().ape_fk_bank_frame_subset_host(self._handle, kind, C.c_void_p(rh.ctypes.data), C.c_void_p(idx.ctypes.data), K,
+                                                          C.c_void_p(out.ctypes.data), self._sel, self._stream()),
+                  "ape_fk_bank_frame_subset_host")
+        return out
+
 
 def trim_packed(row, n_rows: int):
     """a packed row ``[25 + 6 * smooth * E]`` of a Kalman bank cut to what the reference sends (estimator.py:131-137): the 25-value
@@ -590,6 +704,28 @@ class KalmanStreamBank:
         stream is past its first W + 1 frames, the smoothing lag of the sensor means before (one row: origins and zeros); flagged
         frames use buffers of their own.  The bank's own buffers, overwritten by the next subset frame of the same kind."""
         return self._frame(rows, self._indices(streams), big_endian, datagrams, noise, init_noise, return_targets, "sub", spread)
+
+    def frame_host(self, rows, streams, big_endian: bool = False, datagrams: bool = False, spread: bool = False):
+        """``frame`` host to host (``ape_kalman_bank_frame_subset_host``): float32 HOST rows ``[K, 55]`` -> a fresh
+        host array ``[K, 25]`` of the bank's dtype, or with ``datagrams`` ``([K, 25 + 6 * smooth * E], n_rows int32 [K])``, as
+        ``frame`` returns them (``spread``: 21 columns more) -- the same bits, the same call counter behind the draw keys.
+        BLOCKING; no copy command and no event on the stream; a singular innovation is still reported by ``check()``.  ``noise`` /
+        ``init_noise`` injection and ``return_targets`` stay on ``frame``.  Lockstep frames, ``frame`` and ``frame_host`` mix freely;
+        the signs and ``format_state`` draws of a stream depend on its list position."""
+        hip, C = self._hip, self._C
+        idx = self._indices(streams)
+        K = int(idx.shape[0])
+        rh = _host_rows(rows, K, 55)
+        w = (self._width if datagrams else 25) + (hip.SPREAD_WIDTH if spread else 0)
+        out = np.empty((K, w), dtype=np.float32 if self._dtype == torch.float32 else np.float64)
+        n_rows = np.zeros((K,), dtype=np.int32)
+        if K:
+            kind = hip.PARSE_WATCH_PHONE_POCKET | (hip.PARSE_BIG_ENDIAN if big_endian else 0)
+            hip.check(hip.lib().ape_kalman_bank_frame_subset_host(
+                self._handle, kind, C.c_void_p(rh.ctypes.data), C.c_void_p(idx.ctypes.data), K,
+                (hip.FLAG_PACKED_MSG if datagrams else 0) | (hip.FLAG_SPREAD if spread else 0), C.c_void_p(out.ctypes.data), self._sel,
+                C.c_void_p(n_rows.ctypes.data), self._stream()), "ape_kalman_bank_frame_subset_host")
+        return (out, n_rows) if datagrams else out
 
     # ---- state hand-over (DESIGN.md 4.27) ----
     def state_desc(self) -> dict:

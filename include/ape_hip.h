@@ -768,6 +768,33 @@ int ape_kalman_replay_resume(ape_kalman_t* model, int32_t kind, const float* row
                              float* y_dev, void* stream, const double* bodies_host, const void* state_in_dev, const int32_t* age_in_host,
                              void* state_out_dev, int32_t* age_out_host, uint64_t call_base);
 
+/* host subset frames (additive in ABI 7): any K of a bank's S streams, host rows in, host datagrams out.
+ * replaces: one iteration of the receive loop of a server that holds S reference Estimators -- for every datagram that arrived since
+ * the last tick one Estimator.process_row (estimator.py:93-137; WatchPhoneUarm.process_row, watch_phone_uarm.py:64-108;
+ * WatchPhonePocketKalman.process_row, watch_phone_pocket_kalman.py:141-156) and the message PoseEstPublisherUDP sends for it.
+ * Semantics: EXACTLY those of the matching device subset frame (ape_streams_frame_subset, ape_fk_bank_frame with a list,
+ * ape_kalman_bank_frame with a list and no injected draws) -- flags, row widths (25 columns at N == 1 whatever APE_FLAG_PACKED_MSG
+ * says on the NN bank), mode rules (the NN bank enters per-stream mode; the FK and Kalman banks mix lockstep and subset frames), the
+ * call counter behind the Monte-Carlo / Kalman draw keys, the refusals, K = 0 a no-op, unlisted streams bit for bit untouched: a bank
+ * fed by either entry returns the same bits.
+ *   rows_host      f32 [K, width] ordinary host memory: row j belongs to stream streams_host[j]
+ *   streams_host   K DISTINCT stream indices (NULL is refused on the NN bank; on the FK / Kalman banks NULL means all S in order)
+ *   out_host       [K, row width of the device entry] of out_dtype, ordinary host memory, list order
+ *   n_rows_host    i32 [K] (Kalman bank): the stacked rows behind each message
+ * BLOCKING, like the lockstep host frames: the call returns with out_host (and n_rows_host) filled.  On the NN bank an aborted
+ * cooperative launch has been re-issued first (as by ape_model_recover) and a clean frame clears the journal; the frame is counted and
+ * traced by ape_streams_frame_stats ({launch, wait, copy} microseconds).  On the Kalman bank a singular innovation is still reported
+ * by ape_kalman_check.  The frame puts NO copy command and NO event on the stream: rows and descriptors are read by the frame's
+ * first kernel from a pinned block, outputs are written by its last kernel into pinned memory followed -- for K <= 64 -- by one
+ * completion word per entry, which the host polls; a larger K waits for the stream.
+ * Refused (non-zero, ape_last_error) before any launch: what the device entry refuses. */
+int ape_streams_frame_subset_host(ape_streams_t* bank, int32_t kind, const float* rows_host, const int32_t* streams_host, int32_t K,
+                                  uint32_t flags, void* out_host, int32_t out_dtype, void* stream);
+int ape_fk_bank_frame_subset_host(ape_fk_bank_t* bank, int32_t kind, const float* rows_host, const int32_t* streams_host, int32_t K,
+                                  void* out_host, int32_t out_dtype, void* stream);
+int ape_kalman_bank_frame_subset_host(ape_kalman_bank_t* bank, int32_t kind, const float* rows_host, const int32_t* streams_host,
+                                      int32_t K, uint32_t flags, void* out_host, int32_t out_dtype, int32_t* n_rows_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
