@@ -1,0 +1,498 @@
+// Scoring replayed poses against ground truth (ape_score_rows; the reference has no counterpart).
+//
+// ape_score_kernel      one lane per frame: the truth pose (est columns as given, or NN targets through the float64 forward kinematics of
+//                       fk_device.h, its quaternions refined to the reference's eigenvector: truth_six_drr_to_quat), the five errors of
+//                       the frame's message against it, the two squared Mahalanobis distances under the frame's spread record; then the
+//                       workgroup's 256 frames reduced per recording into one partial record for every (workgroup, recording) pair
+// ape_score_acc_kernel  one workgroup per recording: its partial records combined in a fixed order
+//
+// Loads: a wave's 64 rows are fetched with the lanes running ALONG the rows (element i of the wave's rows x columns block is lane i % 64 of
+// load i / 64), so every load instruction reads whole runs of 25 / 21 / O neighbouring values and the 6N values between the message and
+// the record of a packed row are never touched; the block is staged in LDS and each lane then takes its own row from there.
+// Sums: no atomics.  Within a wave a segmented shuffle tree (lane l takes lane l + 1, 2, 4, ... while that lane is in the same recording),
+// across the four waves in wave order, across workgroups in the order of ape_score_acc_kernel: the same inputs give the same bits.
+//
+// float64 with separate roundings for a * b + c, like the numpy statement (score.py): contraction is off in this file.
+#include "ape_internal.h"
+#include "../../include/ape_hip.h"
+#include "fk_device.h"
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <mutex>
+#include <vector>
+
+#pragma clang fp contract(off)
+
+namespace {
+
+using namespace ape_fkdev;
+
+constexpr int SC_BLOCK = 256, SC_WAVES = SC_BLOCK / 64;
+constexpr int SC_LDS_ROW = 25;                          // widest staged row (the message); every staged stride is odd: no bank conflicts
+constexpr int ACC = APE_SCORE_ACC_WIDTH;
+constexpr double CHI2_3_Q50 = 2.3659738843753377, CHI2_3_Q90 = 6.251388631170325;
+
+struct ScoreParams {
+    const void* msg;
+    const void* spread;
+    const void* truth;
+    void* score;                                        // [F, 7] or NULL
+    double* part;                                       // [(workgroups + R), 25] partial records, pair (b, r) at row b + r; NULL: no accumulators
+    const int* starts;                                  // [R]
+    const double* bodies;                               // [n_bodies, 9] (APE_TRUTH_TARGETS)
+    long long msg_stride, spread_stride;
+    int F, R, skip, layout, n_bodies, truth_w, score_f32;
+};
+
+// rows row0 .. row0 + nrows - 1 (nrows >= 1), columns 0 .. ncols - 1 of src -> lds[r * lstride + c] as float64.  Every lane loads in
+// every round (the index is clamped, a partial wave reads its last element again): no branch between the loads
+template <typename T>
+__device__ __forceinline__ void stage_rows(double* lds, const T* src, long long stride, int ncols, int lstride, long long row0, int nrows,
+                                           int lane) {
+    const int last = nrows * ncols - 1;
+#pragma unroll
+    for (int it = 0; it < SC_LDS_ROW; ++it) {
+        if (it < ncols) {                               // uniform
+            int idx = it * 64 + lane;
+            idx = idx < last ? idx : last;
+            const int r = idx / ncols, c = idx - r * ncols;
+            lds[r * lstride + c] = (double)src[(row0 + r) * stride + c];
+        }
+    }
+}
+
+__device__ __forceinline__ bool fin(double v) { return isfinite(v); }
+
+__device__ __forceinline__ double dist3(const double* a, const Vec3 t) {
+    const double dx = a[0] - t.x, dy = a[1] - t.y, dz = a[2] - t.z;
+    return sqrt(dx * dx + dy * dy + dz * dz);
+}
+
+// 4 asin(min(1, |q - s qt| / 2)), s = -1 where q . qt < 0.0: well conditioned from 1e-9 rad to pi
+__device__ __forceinline__ double ang_err(const double* q, const Quat t) {
+    const double d = q[0] * t.w + q[1] * t.x + q[2] * t.y + q[3] * t.z;
+    const double s = d < 0.0 ? -1.0 : 1.0;
+    const double a = q[0] - s * t.w, b = q[1] - s * t.x, c = q[2] - s * t.y, e = q[3] - s * t.z;
+    const double h = sqrt(a * a + b * b + c * c + e * e) / 2.0;
+    return 4.0 * asin(h < 1.0 ? h : 1.0);
+}
+
+// (t - m)' S^-1 (t - m), S^-1 by the adjugate; NaN where the covariance is not usable (include/ape_hip.h)
+__device__ __forceinline__ double mahalanobis(const double* rec, const Vec3 t) {
+    const double a = rec[3], b = rec[4], c = rec[5], d = rec[6], e = rec[7], f = rec[8];
+    const double tr = a + d + f;
+    const double A00 = d * f - e * e, A01 = c * e - b * f, A02 = b * e - c * d;
+    const double A11 = a * f - c * c, A12 = b * c - a * e, A22 = a * d - b * b;
+    const double det = a * A00 + b * A01 + c * A02;
+    const double third = tr / 3.0;
+    const bool usable = fin(a) && fin(b) && fin(c) && fin(d) && fin(e) && fin(f) && tr > 0.0 && det > 1e-12 * (third * third * third);
+    if (!usable) return NAN;
+    const double x = t.x - rec[0], y = t.y - rec[1], z = t.z - rec[2];
+    const double quad = A00 * x * x + A11 * y * y + A22 * z * z + 2.0 * (A01 * x * y + A02 * x * z + A12 * y * z);
+    return quad / det;
+}
+
+// The truth's 6D rotation -> unit quaternion, in the reference's sense.  rot_mat_to_quat (transformations.py:521-545) takes the dominant
+// eigenvector of the symmetric 4x4 matrix K(R) / 3; six_drr_to_quat (fk_device.h) is its closed form for an orthonormal R.  Where the two
+// 6D columns are nearly parallel, Gram-Schmidt leaves R up to 1e-11 off orthonormal and the two pick quaternions up to 4e-12 apart --
+// nothing beside a prediction's own error, but truth is compared at 1e-13.  So the closed form is the start of two power steps on
+// K + I, whose eigenvalues are 4 and three of the size of R's defect: each step multiplies the distance to the eigenvector by that
+// defect, and the result is the reference's to rounding (7e-16 on the fixtures after one step).  NaN propagates as in six_drr_to_quat.
+__device__ inline Quat truth_six_drr_to_quat(const double* s) {
+    const Quat q0 = six_drr_to_quat(s);
+    // R = [b1 b2 b3] as columns, the arithmetic of six_drr_to_quat (transformations.py:602-637)
+    const double a1x = s[0], a1y = s[2], a1z = s[4], a2x = s[1], a2y = s[3], a2z = s[5];
+    const double n1 = sqrt(a1x * a1x + a1y * a1y + a1z * a1z);
+    const double m00 = a1x / n1, m10 = a1y / n1, m20 = a1z / n1;
+    const double d = m00 * a2x + m10 * a2y + m20 * a2z;
+    const double ux = a2x - d * m00, uy = a2y - d * m10, uz = a2z - d * m20;
+    const double n2 = sqrt(ux * ux + uy * uy + uz * uz);
+    const double m01 = ux / n2, m11 = uy / n2, m21 = uz / n2;
+    const double m02 = m10 * m21 - m20 * m11, m12 = m20 * m01 - m00 * m21, m22 = m00 * m11 - m10 * m01;
+    // K + I in the reference's (x, y, z, w) order (transformations.py:575-584, times 3)
+    const double k00 = m00 - m11 - m22 + 1.0, k11 = m11 - m00 - m22 + 1.0, k22 = m22 - m00 - m11 + 1.0, k33 = m00 + m11 + m22 + 1.0;
+    const double k01 = m01 + m10, k02 = m02 + m20, k12 = m12 + m21, k03 = m21 - m12, k13 = m02 - m20, k23 = m10 - m01;
+    double x = q0.x, y = q0.y, z = q0.z, w = q0.w;
+#pragma unroll
+    for (int it = 0; it < 2; ++it) {
+        const double nx = k00 * x + k01 * y + k02 * z + k03 * w, ny = k01 * x + k11 * y + k12 * z + k13 * w;
+        const double nz = k02 * x + k12 * y + k22 * z + k23 * w, nw = k03 * x + k13 * y + k23 * z + k33 * w;
+        const double nn = sqrt(nx * nx + ny * ny + nz * nz + nw * nw);
+        x = nx / nn; y = ny / nn; z = nz / nn; w = nw / nn;
+    }
+    return w < 0.0 ? Quat{-w, -x, -y, -z} : Quat{w, x, y, z};
+}
+
+__device__ __forceinline__ bool is_max_col(int c) { return c < 15 && c % 3 == 2; }
+
+__device__ __forceinline__ void acc_combine(double* v, const double* o) {
+#pragma unroll
+    for (int c = 0; c < ACC; ++c) v[c] = is_max_col(c) ? fmax(v[c], o[c]) : v[c] + o[c];
+}
+
+template <typename TM, typename TT, int KIND, bool SPR>
+__global__ __launch_bounds__(SC_BLOCK) void ape_score_kernel(const ScoreParams p) {
+    __shared__ double stage[SC_WAVES][64 * SC_LDS_ROW];
+    __shared__ double wfirst[SC_WAVES][ACC];
+    __shared__ int wrec[SC_WAVES][2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long row0 = (long long)blockIdx.x * SC_BLOCK + wave * 64;
+    const long long f = row0 + lane;
+    const bool valid = f < p.F;
+    const long long left = (long long)p.F - row0;
+    const int nrows = left >= 64 ? 64 : (left > 0 ? (int)left : 0);
+    double* lds = stage[wave];
+
+    // the frame's recording: the last start <= f (starts[0] == 0, strictly rising); lanes past F form a recording of their own
+    int rec = p.R, start = 0;
+    if (valid) {
+        int lo = 0, hi = p.R - 1;
+        while (lo < hi) {
+            const int mid = (lo + hi + 1) >> 1;
+            if ((long long)p.starts[mid] <= f) lo = mid; else hi = mid - 1;
+        }
+        rec = lo;
+        start = p.starts[lo];
+    }
+
+    // ---- truth pose ----
+    // (every wave stages into its own slice of `stage`, so a wave-level wait would do between the phases; the workgroup barrier is the
+    //  plain form of it and costs nothing measurable beside the loads)
+    const int tw = p.truth_w, tls = tw | 1;
+    if (nrows > 0) stage_rows(lds, static_cast<const TT*>(p.truth), (long long)tw, tw, tls, row0, nrows, lane);
+    __syncthreads();
+    double t[21];
+#pragma unroll
+    for (int c = 0; c < 21; ++c) t[c] = (valid && c < tw) ? lds[lane * tls + c] : 0.0;    // lanes past F, columns past tw: never-written LDS is not read
+    __syncthreads();
+    const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
+    Vec3 t_hand, t_elbow;
+    Quat t_lq, t_uq, t_hq{1.0, 0.0, 0.0, 0.0};
+    bool ok = valid;
+    if constexpr (KIND == APE_TRUTH_TARGETS) {
+#pragma unroll
+        for (int c = 0; c < 20; ++c)
+            if (c < tw) ok = ok && fin(t[c]);
+        const double* body = p.bodies + 9 * (size_t)(p.n_bodies > 1 && valid ? rec : 0);
+        const Vec3 larm_vec{body[0], body[1], body[2]}, uarm_vec{body[3], body[4], body[5]}, uarm_orig{body[6], body[7], body[8]};
+        if (p.layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS) {       // estimate_joints.py:20-45: positions are targets
+            t_lq = truth_six_drr_to_quat(t + 3); t_uq = truth_six_drr_to_quat(t + 12); t_hq = hips_quat(t[18], t[19]);
+            t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[9], t[10], t[11]};
+        } else {                                                       // estimate_joints.py:48-71, 74-92
+            t_lq = truth_six_drr_to_quat(t); t_uq = truth_six_drr_to_quat(t + 6);
+            Vec3 uo = uarm_orig;
+            if (hips) { t_hq = hips_quat(t[12], t[13]); uo = qrot(t_hq, uarm_orig); }
+            const Vec3 r1 = qrot(t_uq, uarm_vec);
+            t_elbow = Vec3{r1.x + uo.x, r1.y + uo.y, r1.z + uo.z};
+            const Vec3 r2 = qrot(t_lq, larm_vec);
+            t_hand = Vec3{r2.x + t_elbow.x, r2.y + t_elbow.y, r2.z + t_elbow.z};
+        }
+    } else {
+        const int ql = hips ? 9 : 6, qu = hips ? 13 : 10;
+        t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[3], t[4], t[5]};
+        t_lq = Quat{t[ql], t[ql + 1], t[ql + 2], t[ql + 3]};
+        t_uq = Quat{t[qu], t[qu + 1], t[qu + 2], t[qu + 3]};
+        if (hips) t_hq = Quat{t[17], t[18], t[19], t[20]};
+    }
+    ok = ok && fin(t_hand.x) && fin(t_hand.y) && fin(t_hand.z) && fin(t_elbow.x) && fin(t_elbow.y) && fin(t_elbow.z) &&
+         fin(t_lq.w) && fin(t_lq.x) && fin(t_lq.y) && fin(t_lq.z) && fin(t_uq.w) && fin(t_uq.x) && fin(t_uq.y) && fin(t_uq.z) &&
+         fin(t_hq.w) && fin(t_hq.x) && fin(t_hq.y) && fin(t_hq.z);
+
+    // ---- the message against it ----
+    if (nrows > 0) stage_rows(lds, static_cast<const TM*>(p.msg), p.msg_stride, 25, 25, row0, nrows, lane);
+    __syncthreads();
+    double m[25];
+#pragma unroll
+    for (int c = 0; c < 25; ++c) { m[c] = valid ? lds[lane * 25 + c] : 0.0; ok = ok && fin(m[c]); }
+    __syncthreads();
+    double s[APE_SCORE_WIDTH];
+    s[0] = dist3(m + 4, t_hand);
+    s[1] = dist3(m + 11, t_elbow);
+    s[2] = ang_err(m + 7, t_lq);
+    s[3] = ang_err(m + 14, t_uq);
+    s[4] = hips ? ang_err(m + 21, t_hq) : 0.0;
+    s[5] = NAN; s[6] = NAN;
+    if constexpr (SPR) {
+        if (nrows > 0) stage_rows(lds, static_cast<const TM*>(p.spread), p.spread_stride, 21, 21, row0, nrows, lane);
+        __syncthreads();
+        double r18[18];
+#pragma unroll
+        for (int c = 0; c < 18; ++c) r18[c] = valid ? lds[lane * 21 + c] : 0.0;
+        __syncthreads();
+        s[5] = mahalanobis(r18, t_hand);
+        s[6] = mahalanobis(r18 + 9, t_elbow);
+    }
+    if (!ok) {
+#pragma unroll
+        for (int c = 0; c < APE_SCORE_WIDTH; ++c) s[c] = NAN;
+    }
+
+    // ---- per-frame rows: through LDS so that the wave writes its 64 x 7 values as one run ----
+    if (p.score != nullptr) {
+#pragma unroll
+        for (int c = 0; c < APE_SCORE_WIDTH; ++c) lds[lane * APE_SCORE_WIDTH + c] = s[c];
+        __syncthreads();
+        const int total = nrows * APE_SCORE_WIDTH;
+#pragma unroll
+        for (int it = 0; it < APE_SCORE_WIDTH; ++it) {
+            const int idx = it * 64 + lane;
+            if (idx < total) {
+                const size_t o = (size_t)row0 * APE_SCORE_WIDTH + idx;
+                if (p.score_f32) static_cast<float*>(p.score)[o] = (float)lds[idx];
+                else static_cast<double*>(p.score)[o] = lds[idx];
+            }
+        }
+    }
+    if (p.part == nullptr) return;                      // (uniform)
+
+    // ---- the frame's contribution, then the workgroup's frames per recording ----
+    const bool past = valid && (f - start) >= (long long)p.skip;
+    const bool in = past && ok;
+    double v[ACC];
+#pragma unroll
+    for (int c = 0; c < 5; ++c) {
+        const double e = in ? s[c] : 0.0;
+        v[3 * c] = e; v[3 * c + 1] = e * e; v[3 * c + 2] = e;
+    }
+    v[15] = in ? 1.0 : 0.0;
+    v[16] = (past && !ok) ? 1.0 : 0.0;
+#pragma unroll
+    for (int k = 0; k < 2; ++k) {
+        const double d2 = s[5 + k];
+        const bool has = in && fin(d2);
+        v[17 + 4 * k] = has ? 1.0 : 0.0;
+        v[18 + 4 * k] = has ? d2 : 0.0;
+        v[19 + 4 * k] = (has && d2 <= CHI2_3_Q50) ? 1.0 : 0.0;
+        v[20 + 4 * k] = (has && d2 <= CHI2_3_Q90) ? 1.0 : 0.0;
+    }
+    // segmented tree: after the round with offset o, lane l holds the frames [l, l + 2 o) of its recording within the wave
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) {
+        const int orec = __shfl_down(rec, off, 64);
+        const bool take = lane + off < 64 && orec == rec;
+        double o[ACC];
+#pragma unroll
+        for (int c = 0; c < ACC; ++c) o[c] = __shfl_down(v[c], off, 64);
+        if (take) acc_combine(v, o);
+    }
+    if (lane == 0) {
+#pragma unroll
+        for (int c = 0; c < ACC; ++c) wfirst[wave][c] = v[c];
+        wrec[wave][0] = rec;
+    }
+    if (lane == 63) wrec[wave][1] = rec;
+    __syncthreads();
+    // the first frame of every (workgroup, recording) pair takes the following waves' leading pieces in wave order and writes the pair's record
+    if (valid && (f == start || threadIdx.x == 0)) {
+        if (wrec[wave][1] == rec) {
+            for (int w = wave + 1; w < SC_WAVES; ++w) {
+                if (wrec[w][0] != rec) break;
+                acc_combine(v, wfirst[w]);
+                if (wrec[w][1] != rec) break;
+            }
+        }
+        double* dst = p.part + ((size_t)blockIdx.x + (size_t)rec) * ACC;
+#pragma unroll
+        for (int c = 0; c < ACC; ++c) dst[c] = v[c];
+    }
+}
+
+// recording r = workgroup r: its pairs (b, r), b = first .. last workgroup of its frames, at rows b + r.  Thread (g, c): column c of the
+// pairs g, g + 8, ... in order; then the eight groups in order.
+__global__ __launch_bounds__(SC_BLOCK) void ape_score_acc_kernel(const double* __restrict__ part, const int* __restrict__ starts, int R, int F,
+                                                                 double* __restrict__ acc) {
+    __shared__ double grp[SC_BLOCK / 32][32];
+    const int r = blockIdx.x, c = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int s = starts[r], e = (r + 1 < R ? starts[r + 1] : F) - 1;
+    const int b0 = s / SC_BLOCK, n = e / SC_BLOCK - b0 + 1;
+    const bool mx = is_max_col(c);
+    double a = 0.0;
+    if (c < ACC) {
+        const double* src = part + ((size_t)b0 + (size_t)r) * ACC + c;
+        int i = g;
+        for (; i + 24 < n; i += 32) {                   // four independent loads in flight, combined in order
+            const double x0 = src[(size_t)i * ACC], x1 = src[(size_t)(i + 8) * ACC], x2 = src[(size_t)(i + 16) * ACC],
+                         x3 = src[(size_t)(i + 24) * ACC];
+            if (mx) a = fmax(fmax(fmax(fmax(a, x0), x1), x2), x3);
+            else a = (((a + x0) + x1) + x2) + x3;
+        }
+        for (; i < n; i += 8) {
+            const double x = src[(size_t)i * ACC];
+            a = mx ? fmax(a, x) : a + x;
+        }
+    }
+    grp[g][c] = a;
+    __syncthreads();
+    if (g == 0 && c < ACC) {
+        double o = grp[0][c];
+#pragma unroll
+        for (int k = 1; k < SC_BLOCK / 32; ++k) o = mx ? fmax(o, grp[k][c]) : o + grp[k][c];
+        acc[(size_t)r * ACC + c] = o;
+    }
+}
+
+int sfail(int code, const char* fmt, ...) {
+    char buf[512];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(buf, sizeof(buf), fmt, ap);
+    va_end(ap);
+    return ape_set_error(code, buf);
+}
+
+#define SC_TRY(expr)                                                                                              \
+    do {                                                                                                          \
+        hipError_t _e = (expr);                                                                                   \
+        if (_e != hipSuccess) return sfail(APE_ERR_HIP, "score_rows: %s failed: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+
+// The call's staging: a pinned block the host arrays are copied into (so they are consumed when the call returns and the copy to the
+// device needs no wait) and the device block behind it (starts, bodies, partial records).  A slot is taken again once the event recorded
+// behind its last call has completed; slots only grow, and live as long as the process.  The first call on a device, and any call whose
+// R or F outgrows the slot it takes, allocates (hipHostMalloc / hipMalloc, which may wait for the device): "the call does not wait" holds
+// from the second call of a size on.  Up to MAX_SLOTS calls may be in flight per device; one more waits for the oldest of them.
+struct Slot {
+    int device = -1;
+    void* pinned = nullptr;
+    void* dev = nullptr;
+    size_t pcap = 0, dcap = 0;
+    hipEvent_t done = nullptr;
+    bool used = false;
+    unsigned long long seq = 0;                         // order of the calls that took the slot
+};
+constexpr size_t MAX_SLOTS = 8;
+std::mutex g_mu;
+std::vector<Slot*> g_slots;
+unsigned long long g_seq = 0;
+
+int take_slot(int device, size_t pbytes, size_t dbytes, Slot** out) {
+    Slot* s = nullptr;
+    size_t mine = 0;
+    for (Slot* q : g_slots) {
+        if (q->device != device) continue;
+        ++mine;
+        if (!q->used || hipEventQuery(q->done) == hipSuccess) { s = q; break; }
+    }
+    (void)hipGetLastError();                            // hipErrorNotReady of a busy slot is no error of this call
+    if (s == nullptr && mine >= MAX_SLOTS) {            // every slot in flight: wait for the oldest
+        for (Slot* q : g_slots)
+            if (q->device == device && (s == nullptr || q->seq < s->seq)) s = q;
+        SC_TRY(hipEventSynchronize(s->done));
+    }
+    if (s == nullptr) {
+        s = new Slot();
+        s->device = device;
+        const hipError_t e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
+        if (e != hipSuccess) {
+            delete s;
+            return sfail(APE_ERR_HIP, "score_rows: hipEventCreate failed: %s", hipGetErrorString(e));
+        }
+        g_slots.push_back(s);
+    }
+    s->used = false;                                    // (its last call is complete; set again once this call has recorded its event)
+    if (s->pcap < pbytes) {
+        if (s->pinned) (void)hipHostFree(s->pinned);
+        s->pinned = nullptr; s->pcap = 0;
+        SC_TRY(hipHostMalloc(&s->pinned, pbytes, hipHostMallocDefault));
+        s->pcap = pbytes;
+    }
+    if (s->dcap < dbytes) {
+        if (s->dev) (void)hipFree(s->dev);
+        s->dev = nullptr; s->dcap = 0;
+        SC_TRY(hipMalloc(&s->dev, dbytes));
+        s->dcap = dbytes;
+    }
+    s->seq = ++g_seq;
+    *out = s;
+    return APE_OK;
+}
+
+template <typename TM, typename TT, int KIND>
+void launch_score(const ScoreParams& p, unsigned blocks, hipStream_t st) {
+    if (p.spread != nullptr) hipLaunchKernelGGL((ape_score_kernel<TM, TT, KIND, true>), dim3(blocks), dim3(SC_BLOCK), 0, st, p);
+    else hipLaunchKernelGGL((ape_score_kernel<TM, TT, KIND, false>), dim3(blocks), dim3(SC_BLOCK), 0, st, p);
+}
+
+template <typename TM, typename TT>
+void launch_score_kind(const ScoreParams& p, int kind, unsigned blocks, hipStream_t st) {
+    if (kind == APE_TRUTH_TARGETS) launch_score<TM, TT, APE_TRUTH_TARGETS>(p, blocks, st);
+    else launch_score<TM, TT, APE_TRUTH_EST>(p, blocks, st);
+}
+
+}  // namespace
+
+int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, const void* spread_dev, int32_t spread_stride,
+                   int32_t msg_dtype, const void* truth_dev, int32_t truth_kind, int32_t truth_dtype, int32_t F,
+                   const int32_t* seg_starts_host, int32_t R, int32_t skip, const double* bodies_host, int32_t n_bodies,
+                   void* score_dev, int32_t score_dtype, double* acc_dev, void* stream) {
+    if (!msg_dev || !truth_dev || !seg_starts_host || !bodies_host) return sfail(APE_ERR_INVALID_ARG, "score_rows: NULL argument");
+    if (!score_dev && !acc_dev) return sfail(APE_ERR_INVALID_ARG, "score_rows: score_dev and acc_dev are both NULL");
+    if (layout != APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS && layout != APE_LAYOUT_ORI_CAL_LARM_UARM && layout != APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS)
+        return sfail(APE_ERR_INVALID_ARG, "score_rows: layout %d has no pose to score", layout);
+    if (truth_kind != APE_TRUTH_TARGETS && truth_kind != APE_TRUTH_EST) return sfail(APE_ERR_INVALID_ARG, "score_rows: unknown truth kind %d", truth_kind);
+    if ((msg_dtype != APE_F32 && msg_dtype != APE_F64) || (truth_dtype != APE_F32 && truth_dtype != APE_F64) ||
+        (score_dtype != APE_F32 && score_dtype != APE_F64))
+        return sfail(APE_ERR_INVALID_ARG, "score_rows: unknown dtype selector");
+    if (F < 1) return sfail(APE_ERR_INVALID_ARG, "score_rows: F=%d must be >= 1", F);
+    if (R < 1 || R > F) return sfail(APE_ERR_INVALID_ARG, "score_rows: %d recording starts for %d frames (1 <= R <= F)", R, F);
+    if (seg_starts_host[0] != 0) return sfail(APE_ERR_INVALID_ARG, "score_rows: seg_starts[0] = %d, must be 0", seg_starts_host[0]);
+    for (int i = 1; i < R; ++i)
+        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
+            return sfail(APE_ERR_INVALID_ARG, "score_rows: seg_starts[%d] = %d (strictly rising, below F = %d)", i, seg_starts_host[i], F);
+    if (msg_stride < 25) return sfail(APE_ERR_INVALID_ARG, "score_rows: msg_stride %d below 25", msg_stride);
+    if (spread_dev && spread_stride < APE_SPREAD_WIDTH) return sfail(APE_ERR_INVALID_ARG, "score_rows: spread_stride %d below %d", spread_stride, APE_SPREAD_WIDTH);
+    if (skip < 0) return sfail(APE_ERR_INVALID_ARG, "score_rows: skip %d is negative", skip);
+    if (n_bodies != 1 && n_bodies != R) return sfail(APE_ERR_INVALID_ARG, "score_rows: n_bodies %d is neither 1 nor R = %d", n_bodies, R);
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    SC_TRY(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return sfail(APE_ERR_INVALID_ARG, "score_rows: the stream is capturing (host arrays are staged per call)");
+    int device = 0;
+    SC_TRY(hipGetDevice(&device));
+
+    const unsigned blocks = (unsigned)(((long long)F + SC_BLOCK - 1) / SC_BLOCK);
+    const size_t starts_bytes = (((size_t)R * sizeof(int)) + 7) & ~(size_t)7;
+    const size_t bodies_bytes = (size_t)n_bodies * 9 * sizeof(double);
+    const size_t host_bytes = starts_bytes + bodies_bytes;
+    const size_t part_bytes = acc_dev ? ((size_t)blocks + (size_t)R) * ACC * sizeof(double) : 0;
+
+    std::lock_guard<std::mutex> lock(g_mu);
+    Slot* slot = nullptr;
+    if (int rc = take_slot(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
+    memcpy(slot->pinned, seg_starts_host, (size_t)R * sizeof(int));
+    memcpy(static_cast<char*>(slot->pinned) + starts_bytes, bodies_host, bodies_bytes);
+    SC_TRY(hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
+
+    ScoreParams p{};
+    p.msg = msg_dev; p.spread = spread_dev; p.truth = truth_dev; p.score = score_dev;
+    p.starts = static_cast<const int*>(slot->dev);
+    p.bodies = reinterpret_cast<const double*>(static_cast<const char*>(slot->dev) + starts_bytes);
+    p.part = acc_dev ? reinterpret_cast<double*>(static_cast<char*>(slot->dev) + host_bytes) : nullptr;
+    p.msg_stride = msg_stride; p.spread_stride = spread_stride;
+    p.F = F; p.R = R; p.skip = skip; p.layout = layout; p.n_bodies = n_bodies;
+    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
+    if (truth_kind == APE_TRUTH_TARGETS) p.truth_w = layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS ? 20 : (hips ? 14 : 12);
+    else p.truth_w = hips ? 21 : 14;
+    p.score_f32 = score_dtype == APE_F32 ? 1 : 0;
+
+    if (msg_dtype == APE_F32 && truth_dtype == APE_F32) launch_score_kind<float, float>(p, truth_kind, blocks, st);
+    else if (msg_dtype == APE_F32) launch_score_kind<float, double>(p, truth_kind, blocks, st);
+    else if (truth_dtype == APE_F32) launch_score_kind<double, float>(p, truth_kind, blocks, st);
+    else launch_score_kind<double, double>(p, truth_kind, blocks, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && acc_dev) {
+        hipLaunchKernelGGL(ape_score_acc_kernel, dim3((unsigned)R), dim3(SC_BLOCK), 0, st, p.part, p.starts, R, F, acc_dev);
+        e = hipGetLastError();
+    }
+    const hipError_t er = hipEventRecord(slot->done, st);  // the slot is in flight whatever became of the launches
+    slot->used = er == hipSuccess;
+    if (e != hipSuccess) return sfail(APE_ERR_HIP, "score_rows: launch failed: %s", hipGetErrorString(e));
+    if (er != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        return sfail(APE_ERR_HIP, "score_rows: hipEventRecord failed: %s", hipGetErrorString(er));
+    }
+    return APE_OK;
+}

@@ -26,6 +26,8 @@ FLAG_PACKED_MSG = 0x20
 FLAG_BROADCAST_X = 0x10
 FLAG_SPREAD = 0x40                # frames, banks, replays: every output row ends in the spread record
 SPREAD_WIDTH = 21                 # APE_SPREAD_WIDTH
+SCORE_WIDTH, SCORE_ACC_WIDTH = 7, 25        # APE_SCORE_WIDTH, APE_SCORE_ACC_WIDTH (ape_score_rows)
+TRUTH_TARGETS, TRUTH_EST = 0, 1             # APE_TRUTH_*
 FLAG_ANY_PLACEMENT, FLAG_NO_XCD_CLASSES, FLAG_ALT_FORM = 0x08000000, 0x02000000, 0x01000000    # exchange-form selectors (A/B runs, tests)
 FLAG_IN_XCD_PLAIN = 0x00400000      # opt-in: plain hand-over stores inside an XCD-pure cluster (the default is write-through)
 KERNEL_AUTO, KERNEL_TILE16, KERNEL_CLUSTER, KERNEL_CLUSTER_GEN1, KERNEL_AUTO_GEN1 = 0, 1, 2, 3, 4
@@ -183,6 +185,11 @@ SIGNATURES["ape_fk_bank_frame_subset_host"] = (C.c_int, [C.c_void_p, C.c_int32, 
                                                          C.c_void_p])
 SIGNATURES["ape_kalman_bank_frame_subset_host"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p,
                                                              C.c_int32, C.c_void_p, C.c_void_p])
+# scoring against ground truth: layout, msg + stride, spread + stride, msg dtype, truth + kind + dtype, F, starts_host, R,
+# skip, bodies_host, n_bodies, score + dtype, acc, HIP stream
+SIGNATURES["ape_score_rows"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                          C.c_void_p, C.c_void_p])
 
 _lib = None
 

@@ -346,3 +346,8 @@ class WatchPhonePocketKalman(Estimator):
         if spread:
             res = res + (rec,)
         return res + (s_out, a_out) if return_state else res
+
+    def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets"):
+        """``Estimator.score_recording`` for Kalman replays: ``skip`` defaults to the ``window_size + 1`` frames every recording runs on
+        its first row alone, whose spread records have no usable covariance"""
+        return super().score_recording(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind)

@@ -136,3 +136,7 @@ class WatchPhoneUarm(Estimator):
                                                        _hip.F64 if out_dtype == torch.float64 else _hip.F32, stream,
                                                        C.c_void_p(bodies.ctypes.data) if bodies is not None else None), "ape_fk_replay_bodies")
         return out
+
+    def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets"):
+        """``Estimator.score_recording`` for ``[F, 25]`` FK replays (no cold-start frames: ``skip`` defaults to 0; no spread record)"""
+        return super().score_recording(out, truth, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind)

@@ -795,6 +795,52 @@ int ape_fk_bank_frame_subset_host(ape_fk_bank_t* bank, int32_t kind, const float
 int ape_kalman_bank_frame_subset_host(ape_kalman_bank_t* bank, int32_t kind, const float* rows_host, const int32_t* streams_host,
                                       int32_t K, uint32_t flags, void* out_host, int32_t out_dtype, int32_t* n_rows_host, void* stream);
 
+/* ---- scoring replayed poses against ground truth (additive in ABI 7) ---------------------------------------------------
+ * replaces: nothing.  The reference has NO counterpart: it never compares a message with the mocap truth its recordings carry (the gt_*
+ * columns NNS_TARGETS names).  ape_score_rows compares the message msg[25] (compose_msg.py:72-78) of every frame with the truth pose of
+ * that frame and, optionally, accumulates per recording.  float64 arithmetic with separate roundings for a * b + c.
+ * Per frame, APE_SCORE_WIDTH values:
+ *   [0]      |msg[4:7] - t_hand| (metres)              [1]  |msg[11:14] - t_larm_orig|
+ *   [2:5]    angular error in [0, pi] of the lower-arm, upper-arm and hips quaternions msg[7:11], msg[14:18], msg[21:25] against the
+ *            truth's: with s = -1 where q . q_t < 0.0, else +1 (the flip rule of average_quaternions), 4 asin(min(1, |q - s q_t| / 2)).
+ *            APE_LAYOUT_ORI_CAL_LARM_UARM (no hips): [4] is exactly 0
+ *   [5], [6] squared Mahalanobis distance (t - m)' S^-1 (t - m) of the true hand / elbow under the frame's spread record: m = record
+ *            [0:3] and S from [3:9] for the hand, [9:12] and [12:18] for the elbow; S^-1 by the adjugate of the symmetric 3x3.  A
+ *            covariance is usable iff its six entries are finite, its trace is > 0 and det > 1e-12 (trace / 3)^3 (so N = 1 records and
+ *            rank-deficient stacks are not); with spread_dev NULL or an unusable covariance the value is NaN
+ * A frame is scored iff every truth value it uses and all 25 message values are finite; otherwise its seven values are NaN.
+ * Truth, truth_dev of truth_dtype, one row per frame:
+ *   APE_TRUTH_TARGETS  [F, O] de-normalised NN targets in the layout's column order (O = 14 / 12 / 20), taken through the float64
+ *                      forward kinematics of ape_fk with the recording's body (arm_pose_from_nn_targets, estimate_joints.py:16-92);
+ *                      the closed-form quaternions are refined to the eigenvector rot_mat_to_quat takes (transformations.py:521-545),
+ *                      so ill-conditioned 6D columns give the reference's est rows to 1e-15, not to 4e-12
+ *   APE_TRUTH_EST      [F, 21 | 14] est rows in the layout's est columns, quaternions as given (the shoulder origin [6:9] is not read)
+ * Per recording, APE_SCORE_ACC_WIDTH raw accumulators (float64, so pieces of a recording merge on the host by adding sums and counts
+ * and taking the larger maximum): [3c], [3c+1], [3c+2] for c = 0..4 the sum, sum of squares and maximum of value c over the
+ * recording's scored frames; [15] scored frames; [16] frames that could not be scored; [17:21] hand: frames with a usable d^2, the
+ * sum of d^2, frames with d^2 <= 2.3659738843753377 and with d^2 <= 6.251388631170325 (the 50 % and 90 % quantiles of chi^2 with
+ * 3 degrees of freedom); [21:25] the same for the elbow.  The first `skip` frames of every recording (cold-start frames) are left out
+ * of all 25; they still get their per-frame values.  A recording with nothing scored gives zeros.  No floating-point atomics and a
+ * fixed order of summation: the same inputs give the same bits.
+ *   msg_dev / msg_stride        the message at the front of rows msg_stride (>= 25) elements apart, of msg_dtype: plain, packed or
+ *                               spread-flagged rows of any replay or bank go in as they are; nothing past column 24 is read
+ *   spread_dev / spread_stride  the frames' spread records (APE_SPREAD_WIDTH), spread_stride (>= 21) elements apart, of msg_dtype; or NULL
+ *   seg_starts_host             the R recordings' first frames: [0] == 0, strictly rising, below F
+ *   bodies_host                 f64 [n_bodies, 9], n_bodies 1 (one body for all) or R; read for APE_TRUTH_TARGETS only
+ *   score_dev                   [F, APE_SCORE_WIDTH] of score_dtype, or NULL;  acc_dev f64 [R, APE_SCORE_ACC_WIDTH], or NULL (not both)
+ * Needs no model handle and runs on the current HIP device.  The launches go on `stream` and the call does not wait for them; the host
+ * arrays have been consumed when it returns.  (The first call on a device, and a call with more recordings or frames than any before,
+ * allocates its staging block and workspace first, which may wait for the device; up to 8 calls may be in flight per device.)  Refused with APE_ERR_INVALID_ARG before anything is written: NULL msg_dev / truth_dev /
+ * seg_starts_host / bodies_host, F < 1, R < 1, bad starts, strides too small, skip < 0, n_bodies not 1 or R, APE_LAYOUT_NONE or an
+ * unknown layout / kind / dtype, a capturing stream. */
+#define APE_SCORE_WIDTH 7
+#define APE_SCORE_ACC_WIDTH 25
+enum { APE_TRUTH_TARGETS = 0, APE_TRUTH_EST = 1 };
+int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, const void* spread_dev, int32_t spread_stride,
+                   int32_t msg_dtype, const void* truth_dev, int32_t truth_kind, int32_t truth_dtype, int32_t F,
+                   const int32_t* seg_starts_host, int32_t R, int32_t skip, const double* bodies_host, int32_t n_bodies,
+                   void* score_dev, int32_t score_dtype, double* acc_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
