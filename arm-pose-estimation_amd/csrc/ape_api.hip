@@ -86,99 +86,113 @@ bool parse_kind_dims(int kind, int* width, int* I) {
 
 }  // namespace
 
-// ---- how a batch is split over the device's CUs (pure arithmetic: unit-tested on the CPU via ape_debug_plan) ----
-// A cluster is GH = H/16 workgroups, one per CU, so a device with n_cus CUs runs n_cus / GH clusters at once
-// (16 on a whole MI355X at H = 256); a batch-tile "wave" is one 16-row workgroup per CU (4096 rows on 256 CUs).
-static int cluster_capacity(int n_cus, int H) { return n_cus / (H / 16); }
-static int tile16_wave_rows(int n_cus) { return APE_TILE_ROWS * n_cus; }
-// smallest row-tile count (16 rows each) per cluster that fits `rows` into one launch; the dropout variants are
-// built for at most 2 tiles
-static int cluster_nmt(int n_cus, int H, int rows, bool cdrop) {
-    const int cap = cluster_capacity(n_cus, H);
-    for (int cand : {1, 2, 4})
-        if ((!cdrop || cand <= 2) && (rows + 16 * cand - 1) / (16 * cand) <= cap) return cand;
-    return cdrop ? 2 : 4;
-}
-// fp16 v2 kernel: 8-member clusters of 32 rows, formed within the 8 block-index classes, so a launch carries whole
-// groups of 8 clusters = 64 workgroups, all of which must be able to be resident together
-static int f16v2_capacity(int n_cus) { return (n_cus / 64) * 8; }
-static int cluster_rows_per_launch(int n_cus, int H, bool cdrop) { return 16 * (cdrop ? 2 : 4) * cluster_capacity(n_cus, H); }
+static_assert(APE_PLAN_TILE_ROWS == APE_TILE_ROWS, "ape_plan.h prices the batch-tile kernel's waves");
 
-// APE_KERNEL_AUTO: how many whole waves of the batch-tile kernel to peel off the front of a batch.  Measured on a
-// whole MI355X (microseconds): a batch-tile wave sustains 125 TFLOP/s at H = 256 and 109 at H = 128 whatever T and
-// the dropout mode (a partial wave costs a whole one); a cluster launch costs 25 + 13.7 T (12.5 + 8.3 T for the 2-tile
-// dropout variant with XCD-local clusters) however few of its rows are used.  Both rates scale with the CU count of the device.
-// `wide` (ImuPoseLSTM, 256-wide layer-0 input): a full batch-tile wave sustains 123 TFLOP/s, the two-tile cluster launch
-// (512 rows) costs 20 + 11 T -- 95 TFLOP/s when full, so whole waves go to the batch-tile kernel and the rest to the cluster.
-// which cluster kernel serves `rest` rows behind the batch-tile waves (the ONE rule lstm_forward_impl, the cost model and
-// ape_debug_plan share): the second-generation f32 kernel from 513 rows on where the model and the call allow it (`c32`:
-// a 2 x 256 model, eval mode, last-step output), else the first-generation kernel
-// `gen2`: the second-generation kernel the model and the call are eligible for -- 32: lstm_cluster32.hip (2 x 256), 16:
-// lstm_cluster16.hip (3 x 128: a launch costs 24.6 + 6.6 T against the first generation's 15.5 + 7.5 T at 513 .. 1024 rows -- with
-// its XCD-local clusters; 15.1 + 7.75 T before them --, so it serves windows of 12 steps and more), 0: none
-// (round 6) 48 = 16 + the level-synchronous kernel lstm_level16.hip: T + 2 hand-overs per launch instead of a three-layer pipeline with four
-// fill / drain phases.  It serves ONE launch's worth of rows: 5 .. 512 with one row tile per cluster at every window length, 513 .. 1024 with
-// two row tiles per cluster (two agents per workgroup) up to 48 steps; lstm_cluster16.hip keeps the longer windows and the larger batches
-enum { PLAN_NONE = 0, PLAN_GEN1 = 1, PLAN_C32 = 2, PLAN_SMALL = 3, PLAN_C16 = 4, PLAN_LV16 = 5 };
-#define APE_LV16_MIN_ROWS 5          // (up to 4 rows: the latency kernel)
-#define APE_LV16_MAX_T 48           // two row tiles per cluster, 513 .. 1024 rows: 170.6 / 222.2 / 327.8 us at 24 / 32 / 48 steps against
-                                    // lstm_cluster16.hip's 179.5 / 231.7 / 339.8; a tie at 64
-#define APE_LV16_MAX_T_SINGLE 4000  // one row tile per cluster, up to 512 rows: faster than the first generation at every window measured
-                                    // (512 rows: 40.0 / 66.9 / 123.2 / 231.5 / 304.9 us at 6 / 12 / 24 / 48 / 64 steps against 42.8 / 70.4 / 129.7 /
-                                    // 245.3 / 323.2; 5 rows: 34.3 against 42.8); a level's tag holds 12 bits of step count
-#define APE_LV16_COST_US0 14.0      // a launch of up to 1024 rows: microseconds = US0 + US_T x T (measured)
-#define APE_LV16_COST_US_T 6.8
-#define APE_LV16_COST1_US0 13.0     // ... of up to 512 rows (one row tile per cluster)
-#define APE_LV16_COST1_US_T 4.5
-static int rest_kernel(int rest, int T, int gen2, int n_cus) {
-    if (rest <= 0) return PLAN_NONE;
-    if (gen2 == 32 && rest > 512) return PLAN_C32;
-    static const int c16_min_t = getenv("APE_C16_MIN_T") ? atoi(getenv("APE_C16_MIN_T")) : 12;      // (diagnostic overrides for A/B runs)
-    static const int lv16_max_t = getenv("APE_LV16_MAX_T") ? atoi(getenv("APE_LV16_MAX_T")) : APE_LV16_MAX_T;
-    static const int lv16_min_rows = getenv("APE_LV16_MIN_ROWS") ? atoi(getenv("APE_LV16_MIN_ROWS")) : APE_LV16_MIN_ROWS;
-    // (ONE launch only: its workgroups take a CU's whole LDS, so a second launch cannot start under the first one's tail as the first
-    //  generation's do -- 2048 x 6: 108 us in two launches against 100)
-    if (gen2 == 48 && rest >= lv16_min_rows) {
-        if (rest <= 16 * ape_level16_max_clusters(n_cus) && T <= APE_LV16_MAX_T_SINGLE) return PLAN_LV16;       // one row tile per cluster
-        if (rest <= 32 * ape_level16_max_clusters(n_cus) && T <= lv16_max_t) return PLAN_LV16;
+// What a model of `dims` can run on a device with n_cus CUs: the kernels' own predicates, in ONE place (ape_model_create, which then
+// clears what failed to set up, and the ape_debug_* entry points).  The routing on top of it is csrc/ape_plan.h.
+static ApeCaps ape_caps(const ape_dims_t* dims, int n_cus) {
+    ApeCaps c;
+    const int H = dims->hidden_size, L = dims->num_layers, O = dims->output_size;
+    const bool imupose = dims->model_kind == APE_MODEL_IMUPOSE;
+    const int KX = padded_input(imupose ? H : dims->input_size);
+    c.n_cus = n_cus;
+    c.cluster_capacity = cluster_capacity(n_cus, H);
+    c.f16v2_capacity = f16v2_capacity(n_cus);
+    c.level16_max_clusters = ape_level16_max_clusters(n_cus);
+    c.up128_classes = (n_cus / 4) / 8 * 8;
+    plan_read_overrides(&c);
+    if (dims->model_kind == APE_MODEL_FF) return c;
+    c.upper_ok = !imupose && ((H == 256 && L == 2) || (H == 128 && L == 3));     // the deployed shapes: layers 1.. can run on their own
+    // the cluster kernels need one whole cluster (GH workgroups, one per CU) resident at once: a device with fewer
+    // CUs than that gets the batch-tile kernel only (set_kernel(CLUSTER) then answers APE_ERR_UNSUPPORTED)
+    c.cluster_ok = ape_cluster_supported(H, L, KX) && c.cluster_capacity >= 1;
+    if (!c.cluster_ok) return c;
+    c.wide = imupose;
+    c.layer0_one_layer = ape_cluster_layer0_supported(H, KX);
+    c.f16v2 = ape_cluster_f16v2_supported(H, L, KX) && c.f16v2_capacity > 0;
+    // Monte-Carlo latency kernel (lstm_mc_small.hip): 8 clusters of H/8 members, one per XCD, layer 0 on the latency kernel's
+    // H/8-member register image (only where an XCD has that many CUs)
+    c.mc_small = ape_mc_small_supported(H, L, KX) && n_cus / 8 >= H / 8 && n_cus >= 8 * (H / 8) && !imupose;
+    c.c32 = ape_cluster32_supported(H, L, KX) && c.f16v2_capacity > 0;
+    c.up32 = c.c32 && ape_upper32_supported(H, L, O) && !imupose;       // shares the layer-1 register image, the exchange buffer and the flags
+    // ImuPoseLSTM (2 x 256 behind a 256-wide input layer): each layer is exactly one register image of lstm_upper32.hip's clusters
+    // (K = 256 + 256); above 512 windows the LSTM runs there, one layer per launch
+    c.split32 = imupose && H == 256 && L == 2 && KX == 256 && ape_upper32_supported(H, L, O) && c.f16v2_capacity >= 8;
+    // the Monte-Carlo bank's weight-stationary route for the 3 x 128 model (lstm_upper128.hip): four-member clusters, whole classes of 8
+    c.up128 = ape_upper128_supported(H, L, O) && c.up128_classes >= 8 && !imupose;
+    c.c16 = ape_cluster16_supported(H, L, KX) && c.f16v2_capacity > 0 && !imupose;
+    // short windows: the level-synchronous kernel, if the device holds two of its workgroups per CU (else the first generation serves them)
+    c.lv16 = c.c16 && ape_level16_supported(H, L, KX) && c.level16_max_clusters > 0;
+    return c;
+}
+
+// plan_bank's `l0_bytes`: the larger of launch A's two buffers on lstm_upper32.hip
+static unsigned long long bank_l0_bytes(int S, int T) { return std::max(ape_lower32_hseq_bytes(S, T), ape_lower32_xfrag_bytes(S, T)); }
+// the call's switches as the planner reads them
+static LstmCall lstm_call(const ape_model* m, int B, int T, uint32_t flags, bool have_hs, int x_ring) {
+    LstmCall c;
+    c.B = B; c.T = T;
+    c.masks = (flags & APE_FLAG_DROPOUT_MASKS) != 0; c.philox = (flags & APE_FLAG_DROPOUT_PHILOX) != 0; c.drop = c.masks || c.philox;
+    c.all_steps = (flags & APE_FLAG_ALL_STEPS) != 0; c.broadcast = (flags & APE_FLAG_BROADCAST_X) != 0; c.alt_form = (flags & APE_FLAG_ALT_FORM) != 0;
+    c.have_hs = have_hs; c.x_ring = x_ring;
+    c.kernel_choice = m->kernel_choice; c.precision = m->precision; c.replaying = m->replaying;
+    c.c32_on = m->c32_on; c.small_batch_path = m->small_batch_path; c.f16_v2 = m->f16_v2;
+    return c;
+}
+
+// head and input statistics, as every kernel's parameter block names them
+template <typename P>
+static void head_and_stats(const ape_model* m, P* p) { p->w_out = m->w_out; p->b_out = m->b_out; p->xx_m = m->stats; p->xx_s = m->stats + m->dims.input_size; }
+// may a first-generation launch form XCD-local clusters?  (APE_FLAG_NO_XCD_CLASSES: selector, A/B on one box)
+static bool xcd_classes_on(const ape_model* m, uint32_t flags) { return m->gen1_classes && !(flags & APE_FLAG_NO_XCD_CLASSES); }
+// the fields every launch of a cluster kernel shares, with `layers` of the weight image of `route` (PLAN_* of ape_plan.h; lstm_x / lstm_in:
+// the LSTM's own input -- ImuPoseLSTM's is the 256-wide activation of its input layer).  No memset in the launch path: the kernels' last
+// workgroup re-zeroes every polled word (self-cleaning)
+static ClusterParams cluster_params(const ape_model* m, int route, int layers, const float* x, float* y, int B, int T, uint32_t flags, int x_ring) {
+    ClusterParams c{};
+    const bool f16 = route == PLAN_F16 || route == PLAN_F16V2, small2 = route == PLAN_SMALL && !(flags & APE_FLAG_ALT_FORM) && m->small_uw == 2;
+    c.x = x; c.y = y;
+    for (int l = 0; l < layers; ++l) {
+        const void* w = route == PLAN_C32 ? (const void*)m->wcl32s[l] : f16 ? m->wcl16[l] : small2 ? m->wcls[l] : m->wcl[l];
+        c.wcl[l] = static_cast<const float*>(w); c.bias[l] = m->bias[l];
     }
-    if ((gen2 == 16 || gen2 == 48) && rest > 512 && T >= c16_min_t) return PLAN_C16;
-    return PLAN_GEN1;
-}
-static int gen2_of(const ape_model* m) {
-    return (m->c32_ok && m->c32_split && m->c32_on) ? 32 : (m->c16_ok && m->c32_on) ? (m->lv16_ok ? 48 : 16) : 0;
-}
-
-static int auto_tile16_waves(const ape_dims_t* dims, int n_cus, int B, int T, bool cdrop, int gen2 = 0, bool wide = false) {
-    const int wave = tile16_wave_rows(n_cus), rpl = cluster_rows_per_launch(n_cus, dims->hidden_size, cdrop || wide);
-    if (rpl == 0) return (B + wave - 1) / wave;          // no cluster fits on this device
-    const double rate = (wide ? 1.23e14 : dims->hidden_size == 256 ? 1.25e14 : 1.09e14) * n_cus / 256.0;
-    const double t16 = (double)wave * ape_flops_per_window(dims, T) / rate * 1e6;
-    // first-generation launches: 25 + 13.7 T (12.5 + 8.3 T with dropout, 20 + 11 T wide); second-generation f32 kernel, eval mode:
-    // 16 + 12.4 T per launch of up to 32 x f16v2_capacity rows -- priced only where rest_kernel() really picks it
-    // (round 4: the dropout form is priced at what it measures with XCD-local clusters, 12.5 + 8.3 T -- the Philox counters name global
-    //  rows in every kernel now, so the route a Monte-Carlo call takes no longer decides which samples it draws)
-    const double tcl1 = wide ? 20.0 + 11.0 * T : cdrop ? 12.5 + 8.3 * T : 25.0 + 13.7 * T;
-    const int rpl2 = 32 * f16v2_capacity(n_cus);
-    auto cost = [&](int w) {
-        const int rest = B - wave * w;
-        if (rest <= 0) return w * t16;
-        const int k = rest_kernel(rest, T, (!cdrop && !wide && rpl2 > 0) ? gen2 : 0, n_cus);
-        if (k == PLAN_C32) return w * t16 + (double)((rest + rpl2 - 1) / rpl2) * (16.0 + 12.4 * T);
-        if (k == PLAN_C16) return w * t16 + (double)((rest + rpl2 - 1) / rpl2) * (24.6 + 6.6 * T);
-        if (k == PLAN_LV16) {
-            if (rest <= 16 * ape_level16_max_clusters(n_cus)) return w * t16 + APE_LV16_COST1_US0 + APE_LV16_COST1_US_T * T;
-            return w * t16 + APE_LV16_COST_US0 + APE_LV16_COST_US_T * T;
-        }
-        return w * t16 + (double)((rest + rpl - 1) / rpl) * tcl1;
-    };
-    int best = 0;
-    double best_cost = cost(0);
-    for (int w : {B / wave, (B + wave - 1) / wave})
-        if (w > 0 && cost(w) < best_cost) { best = w; best_cost = cost(w); }
-    return best;
+    head_and_stats(m, &c);
+    c.xx_r = m->stats + 2 * m->dims.input_size + 2 * m->dims.output_size;
+    c.hx = m->hx; c.hx_bytes = m->hx_bytes;
+    const CtlWords cw = ctl_words(m);
+    c.xflags = m->xflags; c.status = cw.status; c.ticket = cw.ticket; c.done = cw.done;
+    c.B = B; c.T = T; c.I = m->lstm_in; c.O = m->dims.output_size;
+    c.flags = flags; c.x_ring = x_ring;
+    c.xcc_slots = m->xcc_slots; c.dbg_wg = m->dbg_wg;
+    return c;
 }
 
+static bool stream_capturing(void* stream) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    (void)hipStreamIsCapturing((hipStream_t)stream, &st);
+    return st != hipStreamCaptureStatusNone;
+}
+// grow a device workspace to `need` elements of `elem_bytes`; a capturing stream cannot allocate: APE_ERR_CAPACITY with the message
+// `what_fmt`, a format with exactly one %zu, which receives `need`
+static int grow_ws(void* stream, void** ptr, size_t* cap, size_t need, size_t elem_bytes, const char* what_fmt) {
+    if (need <= *cap) return APE_OK;
+    if (stream_capturing(stream)) return fail(APE_ERR_CAPACITY, what_fmt, need);
+    if (*ptr) { HIP_TRY(hipFree(*ptr)); *ptr = nullptr; *cap = 0; }
+    HIP_TRY(hipMalloc(ptr, need * elem_bytes));
+    *cap = need;
+    return APE_OK;
+}
+// ... and of the persistent upper-layer clusters (lstm_upper32.hip, lstm_upper128.hip); the caller adds the layers' weights and buffers
+template <typename U = UpperParams>
+static U upper_params(const ape_model* m, int T, int tiles, uint32_t flags) {
+    U u{};
+    u.w_out = m->w_out;
+    u.hx = m->hx; u.hx_bytes = m->hx_bytes;
+    u.xflags = m->xflags; u.status = ctl_words(m).status; u.done = ctl_words(m).done;
+    u.xcc_slots = m->xcc_slots; u.dbg_wg = m->dbg_wg;
+    u.T = T; u.O = m->dims.output_size; u.n_tiles = tiles; u.flags = flags;
+    return u;
+}
 
 int ape_set_error(int code, const char* msg) { return fail(code, "%s", msg); }
 
@@ -279,13 +293,7 @@ size_t ape_weight_blob_floats(const ape_dims_t* d) {
 
 double ape_flops_per_window(const ape_dims_t* d, int32_t T) {
     if (check_dims(d) != APE_OK || T < 1) return 0.0;
-    const double H = d->hidden_size, I = d->input_size, O = d->output_size;
-    if (d->model_kind == APE_MODEL_FF) return 2.0 * (I * H + d->num_layers * H * H + O * H);   // last step only
-    double step = 0;
-    const double in0 = (d->model_kind == APE_MODEL_IMUPOSE) ? H : I;
-    if (d->model_kind == APE_MODEL_IMUPOSE) step += 2.0 * I * H;
-    for (int l = 0; l < d->num_layers; ++l) step += 2.0 * 4.0 * H * ((l == 0 ? in0 : H) + H);
-    return step * T + 2.0 * O * H;
+    return plan_flops_per_window(d, T);
 }
 
 int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
@@ -309,6 +317,7 @@ int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
     if (!m) return fail(APE_ERR_HIP, "out of host memory");
     m->dims = *dims;
     m->n_cus = prop.multiProcessorCount;            // 256 on a whole MI355X; fewer on a partitioned / CU-masked device
+    m->caps = ape_caps(dims, m->n_cus);             // (below: the bits whose set-up fails are cleared again)
     const bool imupose = dims->model_kind == APE_MODEL_IMUPOSE;
     m->lstm_in = imupose ? dims->hidden_size : dims->input_size;
     m->KX = padded_input(m->lstm_in);
@@ -388,43 +397,37 @@ int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
         ape_model_destroy(m);
         return fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
     }
-    if (!imupose && ((H == 256 && L == 2) || (H == 128 && L == 3))) {     // the deployed shapes: layers 1.. can run on their own
+    if (m->caps.upper_ok) {
         e = ape_prepare_lstm_tile16_upper(H, L - 1, ape_lstm_tile16_smem_bytes(H, L - 1, H, O, true));
         if (e != hipSuccess) {
             ape_model_destroy(m);
             return fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
         }
-        m->upper_ok = true;
     }
     char nm[64];
     snprintf(nm, sizeof(nm), "ape_lstm_tile16<%d, %d, %d>", H, L, imupose ? 16 : 4);
     m->kernel_name = nm;
     snprintf(nm, sizeof(nm), "ape_lstm_cluster<%d, %d, %d", H, L, m->KX);
     m->cluster_name = nm;
-    // the cluster kernels need one whole cluster (GH workgroups, one per CU) resident at once: a device with fewer
-    // CUs than that gets the batch-tile kernel only (set_kernel(CLUSTER) then answers APE_ERR_UNSUPPORTED)
-    if (ape_cluster_supported(H, L, m->KX) && cluster_capacity(m->n_cus, H) >= 1) {
-        const int GH = H / 16, max_clusters = cluster_capacity(m->n_cus, H);
+    if (m->caps.cluster_ok) {
+        const int GH = H / 16, max_clusters = m->caps.cluster_capacity;
         for (int l = 0; l < L && e == hipSuccess; ++l)
             e = plan((void**)&m->wcl[l], (size_t)4 * H * ((l == 0 ? m->KX : H) + H) * sizeof(float));
+        const size_t cap32 = (size_t)m->caps.f16v2_capacity;
         m->hx_bytes = (size_t)max_clusters * L * 2 * GH * 64 * 16 * sizeof(float);
-        // (upper-layer kernel: 32-row clusters x 2 sets x 2 parities x 32 KB)
-        if (ape_upper32_supported(H, L, O) && (size_t)f16v2_capacity(m->n_cus) * 2 * 2 * 32768 > m->hx_bytes)
-            m->hx_bytes = (size_t)f16v2_capacity(m->n_cus) * 2 * 2 * 32768;
-        // one flag per (cluster, layer, member, wave) -- or, fp16 v2 kernel, per (32-row cluster, row set, member wave) --
-        // + the ticket / departure words
+        // one flag per (cluster, layer, member, wave) + the ticket / departure words; on top of both what the other kernels need:
         size_t flag_words = (size_t)max_clusters * L * GH * 4;
-        if (ape_cluster_f16v2_supported(H, L, m->KX) && (size_t)f16v2_capacity(m->n_cus) * 2 * 64 > flag_words)
-            flag_words = (size_t)f16v2_capacity(m->n_cus) * 2 * 64;      // (64 flags per cluster and set in the 16-member form)
+        if (ape_upper32_supported(H, L, O)) {       // 32-row clusters x 2 sets x 2 parities x 32 KB; one flag per (cluster, set, member wave)
+            m->hx_bytes = std::max(m->hx_bytes, cap32 * 2 * 2 * 32768);
+            flag_words = std::max(flag_words, cap32 * 2 * 32);
+        }
+        // fp16 v2 kernel: per (32-row cluster, row set, member wave), 64 flags per cluster and set in the 16-member form
+        if (ape_cluster_f16v2_supported(H, L, m->KX)) flag_words = std::max(flag_words, cap32 * 2 * 64);
         // (second-generation kernel of the 3 x 128 model: one flag per (32-row cluster, layer, member, one of eight waves))
-        if (ape_cluster16_supported(H, L, m->KX) && (size_t)f16v2_capacity(m->n_cus) * L * 64 > flag_words)
-            flag_words = (size_t)f16v2_capacity(m->n_cus) * L * 64;
-        if (ape_upper32_supported(H, L, O) && (size_t)f16v2_capacity(m->n_cus) * 2 * 32 > flag_words)
-            flag_words = (size_t)f16v2_capacity(m->n_cus) * 2 * 32;      // (lstm_upper32.hip: one flag per (cluster, set, member wave))
+        if (ape_cluster16_supported(H, L, m->KX)) flag_words = std::max(flag_words, cap32 * L * 64);
         if (ape_upper128_supported(H, L, O) && !imupose) {
-            const int c128 = (m->n_cus / 4) / 8 * 8;
-            if (ape_upper128_flag_words(c128) > flag_words) flag_words = ape_upper128_flag_words(c128);
-            if (ape_upper128_hx_bytes(c128) > m->hx_bytes) m->hx_bytes = ape_upper128_hx_bytes(c128);
+            flag_words = std::max(flag_words, (size_t)ape_upper128_flag_words(m->caps.up128_classes));
+            m->hx_bytes = std::max(m->hx_bytes, (size_t)ape_upper128_hx_bytes(m->caps.up128_classes));
         }
         m->xflag_bytes = ((flag_words * sizeof(unsigned)) + 15) / 16 * 16 + 16;
         if (e == hipSuccess) e = plan((void**)&m->hx, m->hx_bytes);
@@ -433,7 +436,6 @@ int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
         if (e == hipSuccess) e = plan((void**)&m->xcc_slots, APE_XCC_WORDS * sizeof(unsigned));
         m->hxs_bytes = (size_t)L * 2 * 4 * H * 8;
         if (e == hipSuccess) e = plan((void**)&m->hxs, 256 + m->hxs_bytes);
-        m->wide_cluster = imupose;
         for (int l = 0; l < L && e == hipSuccess && !imupose; ++l)
             e = plan(&m->wcl16[l], (size_t)4 * H * ((l == 0 ? m->KX : H) + H) * sizeof(_Float16));
         if (e == hipSuccess) e = ape_prepare_lstm_cluster(H, L, m->KX);
@@ -447,58 +449,44 @@ int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
                 e = plan((void**)&m->wcls[l], (size_t)4 * H * ((l == 0 ? m->KX : H) + H) * sizeof(float));
             m->small_uw = 2;
         }
-        // Monte-Carlo latency kernel (lstm_mc_small.hip): 8 clusters of H/8 members, one per XCD, layer 0 on the latency kernel's
-        // H/8-member register image
-        if (ape_mc_small_supported(H, L, m->KX) && m->small_uw == 2 && m->n_cus >= 8 * (H / 8) && !imupose) {
+        if (m->caps.mc_small) {
             for (int l = 1; l < L && e == hipSuccess; ++l) e = plan((void**)&m->wmc[l], (size_t)8 * H * H * sizeof(float));
             for (int l = 1; l < L && e == hipSuccess; ++l) e = plan((void**)&m->wmc16[l], (size_t)8 * H * H * sizeof(float));
             m->gxm_cluster_bytes = ape_mc_small_cluster_bytes(H, L);
             if (e == hipSuccess) e = plan((void**)&m->gxm, 256 + 8 * m->gxm_cluster_bytes + 8 * 64 * 8);      // + the feature granules of 8 streams
             if (e == hipSuccess) e = ape_prepare_lstm_mc_small(H, L, m->KX);
-            m->mcs_ok = true;
         }
-        if (ape_cluster32_supported(H, L, m->KX) && f16v2_capacity(m->n_cus) > 0) {
+        if (m->caps.c32) {
             for (int l = 0; l < L && e == hipSuccess; ++l)
                 e = plan((void**)&m->wcl32[l], (size_t)4 * H * ((l == 0 ? m->KX : H) + H) * sizeof(float));
             for (int l = 0; l < L && e == hipSuccess; ++l)         // the f16 hi / lo image of lstm_cluster32.hip (same size, pack_c32_split)
                 e = plan((void**)&m->wcl32s[l], (size_t)4 * H * ((l == 0 ? m->KX : H) + H) * sizeof(float));
             if (e == hipSuccess) e = ape_prepare_lstm_cluster32(H, L, m->KX);
-            m->c32_ok = true;
-            if (ape_upper32_supported(H, L, O) && !imupose) {       // shares the layer-1 register image, the exchange buffer and the flags
-                if (e == hipSuccess) e = ape_prepare_lstm_upper32();
-                m->up32_ok = true;
-            }
+            if (e == hipSuccess && m->caps.up32) e = ape_prepare_lstm_upper32();
         }
-        // ImuPoseLSTM (2 x 256 behind a 256-wide input layer): each layer is exactly one register image of lstm_upper32.hip's clusters
-        // (K = 256 + 256); above 512 windows the LSTM runs there, one layer per launch (lstm_forward_impl)
-        if (imupose && H == 256 && L == 2 && m->KX == 256 && ape_upper32_supported(H, L, O) && f16v2_capacity(m->n_cus) >= 8) {
+        if (m->caps.split32) {
             for (int l = 0; l < L && e == hipSuccess; ++l)
                 e = plan((void**)&m->wcl32[l], (size_t)4 * H * (H + H) * sizeof(float));
             if (e == hipSuccess) e = ape_prepare_lstm_upper32();
-            m->split32_ok = (e == hipSuccess);
+            m->caps.split32 = (e == hipSuccess);
         }
-        // the Monte-Carlo bank's weight-stationary route for the 3 x 128 model (lstm_upper128.hip): four-member clusters, whole classes of 8
-        if (ape_upper128_supported(H, L, O) && (m->n_cus / 4) / 8 * 8 >= 8 && !imupose) {
+        if (m->caps.up128) {
             for (int l = 1; l < L && e == hipSuccess; ++l) e = plan((void**)&m->wup128[l], (size_t)4 * H * 2 * H * sizeof(float));
             if (e == hipSuccess) e = ape_prepare_lstm_upper128();
-            m->up128_ok = true;
         }
-        if (ape_cluster16_supported(H, L, m->KX) && f16v2_capacity(m->n_cus) > 0 && !imupose) {
+        if (m->caps.c16) {
             if (e == hipSuccess) e = ape_prepare_lstm_cluster16(H, L, m->KX);
-            m->c16_ok = true;
-            // short windows: the level-synchronous kernel, if the device holds two of its workgroups per CU (else the first generation serves them)
-            if (e == hipSuccess && ape_level16_supported(H, L, m->KX) && ape_level16_max_clusters(m->n_cus) > 0) {
+            if (e == hipSuccess && m->caps.lv16) {
                 m->gx16_bytes = ape_level16_gx_bytes(m->n_cus);
                 e = plan((void**)&m->gx16, 256 + m->gx16_bytes);
                 if (e == hipSuccess) e = ape_prepare_lstm_level16(H, L, m->KX);
-                m->lv16_ok = (e == hipSuccess);
+                m->caps.lv16 = (e == hipSuccess);
             }
         }
         if (e != hipSuccess) {
             ape_model_destroy(m);
             return fail(APE_ERR_HIP, "cluster kernel set-up failed: %s", hipGetErrorString(e));
         }
-        m->cluster_ok = true;
     }
     e = commit_plan();
     if (e != hipSuccess) {
@@ -634,7 +622,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                         }
                     }
                 }
-        if (m->cluster_ok) {
+        if (m->caps.cluster_ok) {
             // cluster kernel: [member GH][wave 4][i/4][lane][i%4] with i = 4q + j; lane = (g << 4) | (u << 2) | gate holds
             // Wcat[gate*H + member*16 + wave*4 + u][16q + 4g + j] -- the register file of that wave
             const int GH = H / 16, NW = (KXl + H) / 4;
@@ -672,7 +660,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                             }
                 HIP_TRY(hipMemcpy(m->wcls[l], ps.data(), ps.size() * sizeof(float), hipMemcpyHostToDevice));
             }
-            if (m->mcs_ok && l >= 1) {
+            if (m->caps.mc_small && l >= 1) {
                 // Monte-Carlo latency kernel, layers above layer 0 (v_mfma_f32_4x4x1_16b_f32): H/8 members x 4 waves, wave w = K quarter w of
                 // [W_ih | W_hh]; lane = (block b = lane >> 2: unit b & 7 of the member, k slice ks = b >> 3; gate = lane & 3) holds
                 // Wcat[gate*H + member*8 + (b & 7)][w*H/2 + 8 (i/4) + 4 ks + (i%4)] in register i; stored [member][wave][i/4][lane][i%4]
@@ -748,15 +736,15 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
         if (m->wcl32s[l] != nullptr) {
             std::vector<unsigned> ps((size_t)8 * 4 * ((KXl + H) / 2) * 64);
             const int S = pack_c32_split(w_ih, in_l, w_hh, H, KXl, l == 0 ? KXl : 0, ps.data());
-            if (l == 0) m->c32_split = true;
-            if (S < 0) m->c32_split = false;
+            if (l == 0) m->caps.c32 = true;        // (weights that refuse the split keep the model off lstm_cluster32.hip)
+            if (S < 0) m->caps.c32 = false;
             else {
                 m->c32_scale[l] = std::ldexp(1.0f, S);
                 m->c32_descale[l] = std::ldexp(1.0f, -S);
                 HIP_TRY(hipMemcpy(m->wcl32s[l], ps.data(), ps.size() * sizeof(unsigned), hipMemcpyHostToDevice));
             }
         }
-        if (m->up128_ok && l >= 1) {
+        if (m->caps.up128 && l >= 1) {
             // lstm_upper128.hip: four members x 4 waves, a wave owns 8 units = 32 columns ordered gate * 8 + unit (v_mfma_f32_32x32x2_f32,
             // weights = A operand); register i = 4 kb + j of lane (column mcol = lane & 31, half hh) = Wcat[gate(mcol) * H + member*32 +
             // wave*8 + (mcol & 7)][8 kb + 4 hh + j]; [member][wave][i / 4][lane][i % 4]
@@ -820,13 +808,7 @@ struct FkTail {
 // Monte-Carlo latency kernel (lstm_mc_small.hip): n_streams windows (stream s at x + s * x_stream_stride) x n_mc dropout samples each,
 // rows dealt over the 8 XCD clusters; y [n_streams * n_mc, O].  The caller has checked mc_small_fits().
 static bool mc_small_fits(const ape_model* m, int n_streams, int n_mc) {
-    if (!m->mcs_ok || !m->c32_on || m->kernel_choice != APE_KERNEL_AUTO || m->precision != APE_PRECISION_F32 || m->replaying) return false;
-    if (n_streams < 1 || n_streams > 8 || n_mc < 1) return false;
-    // (its head gives 16 lanes of a 256-thread workgroup to every target: targets 16 .. of the 20-target position layout would stay
-    //  unwritten -- such a bank steps on the general route)
-    if (m->dims.output_size > 16) return false;
-    const int cps = 8 / n_streams;
-    return (n_mc + cps - 1) / cps <= 16;
+    return mc_small_fits(m->caps, m->dims, m->kernel_choice, m->precision, m->c32_on, m->replaying, n_streams, n_mc);
 }
 // what a host frame adds to the regressor's launch: the raw rows of the frame (feature builder workgroups)
 struct McFrameParts {
@@ -851,11 +833,11 @@ static int mc_small_launch(ape_model_t* m, const float* x, size_t x_stream_strid
     q.x = x; q.x_stream_stride = x_stream_stride; q.y = y_dev;
     q.w0 = m->wcls[0];
     for (int l = 0; l < L; ++l) { q.w[l] = m->wmc[l]; q.w16[l] = m->wmc16[l]; q.bias[l] = m->bias[l]; }
-    q.w_out = m->w_out; q.b_out = m->b_out;
-    q.xx_m = m->stats; q.xx_s = m->stats + I; q.xx_r = m->stats + 2 * I + 2 * O;
+    head_and_stats(m, &q);
+    q.xx_r = m->stats + 2 * I + 2 * O;
     q.gx = m->gxm + 256; q.gx_cluster_bytes = (unsigned)m->gxm_cluster_bytes;
     q.seq = reinterpret_cast<unsigned*>(m->gxm);
-    q.status = m->xflags + m->xflag_bytes / sizeof(unsigned); q.done = q.status - 3;
+    q.status = ctl_words(m).status; q.done = ctl_words(m).done;
     q.xcc_slots = m->xcc_slots;
     q.masks = masks_dev;
     q.rows = n_streams * n_mc; q.n_mc = n_mc; q.n_streams = n_streams;
@@ -873,6 +855,41 @@ static int mc_small_launch(ape_model_t* m, const float* x, size_t x_stream_strid
     m->last_kernel = "ape_lstm_mc_small";
     hipError_t e = ape_launch_lstm_mc_small(m->dims.hidden_size, L, m->KX, q, (hipStream_t)stream);
     if (e != hipSuccess) return fail(APE_ERR_HIP, "Monte-Carlo latency kernel launch failed: %s", hipGetErrorString(e));
+    return APE_OK;
+}
+
+// ImuPoseLSTM on lstm_upper32.hip's persistent clusters (plan route PLAN_SPLIT32): z_ws holds the input layer's activations
+static int split32_forward(ape_model_t* m, const LstmPlan& plan, int B, int T, uint32_t flags, float* y_dev, void* stream) {
+    const int H = m->dims.hidden_size, chunk = plan.rows_per_launch;
+    const int tiles_max = ((B < chunk ? B : chunk) + 31) / 32;
+    if ((size_t)tiles_max > m->split_tiles_cap || (size_t)T > m->split_steps_cap) {
+        if (stream_capturing(stream))
+            return fail(APE_ERR_CAPACITY, "lstm_forward: the layer workspaces (%d tiles x %d steps) cannot grow during stream capture", tiles_max, T);
+        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        // (both dimensions only ever grow: a caller alternating between many short and few long windows does not reallocate)
+        const size_t tc = std::max((size_t)tiles_max, m->split_tiles_cap), sc = std::max((size_t)T, m->split_steps_cap);
+        m->split_tiles_cap = m->split_steps_cap = 0;
+        void** const ws[3] = {(void**)&m->zfrag_ws, (void**)&m->hfrag_ws, (void**)&m->ypart_ws};
+        const size_t bytes[3] = {tc * sc * 32768, tc * sc * 32768, ape_upper32_ypart_bytes((int)tc * 32)};
+        for (void** w : ws) if (*w) { HIP_TRY(hipFree(*w)); *w = nullptr; }
+        for (int i = 0; i < 3; ++i) HIP_TRY(hipMalloc(ws[i], bytes[i]));
+        m->split_tiles_cap = tc; m->split_steps_cap = sc;
+    }
+    for (int b0 = 0; b0 < B; b0 += chunk) {
+        const int nb = (B - b0 < chunk) ? B - b0 : chunk;
+        const int tiles = (nb + 31) / 32;
+        UpperParams u0 = upper_params(m, T, tiles, flags & APE_FLAG_ALT_FORM);      // (selector: one-tile clusters on the blocking form, for A/B)
+        u0.xfrag = m->zfrag_ws; u0.xfrag_bytes = (size_t)tiles * T * 32768;
+        u0.w = m->wcl32[0]; u0.bias = m->bias[0];
+        u0.hseq = m->hfrag_ws; u0.hseq_bytes = (size_t)tiles * T * 32768;
+        UpperParams u1 = u0;
+        u1.xfrag = m->hfrag_ws; u1.hseq = nullptr; u1.hseq_bytes = 0;
+        u1.w = m->wcl32[1]; u1.bias = m->bias[1]; u1.ypart = m->ypart_ws;
+        m->last_kernel = plan.last_kernel;
+        hipError_t e2 = ape_launch_lstm_split32(m->z_ws + (size_t)b0 * T * H, nb, u0, u1, m->b_out,
+                                                y_dev + (size_t)b0 * m->dims.output_size, m->caps.f16v2_capacity, (hipStream_t)stream);
+        if (e2 != hipSuccess) return fail(APE_ERR_HIP, "layer-split lstm launch failed: %s", hipGetErrorString(e2));
+    }
     return APE_OK;
 }
 
@@ -915,8 +932,7 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
         const bool all = (flags & APE_FLAG_ALL_STEPS) != 0;
         q.x = x_dev; q.y = y_dev;
         for (int j = 0; j <= L; ++j) { q.wpack[j] = m->ff_wpack[j]; q.bias[j] = m->ff_bias[j]; }
-        q.w_out = m->w_out; q.b_out = m->b_out;
-        q.xx_m = m->stats; q.xx_s = m->stats + m->dims.input_size;
+        head_and_stats(m, &q);
         q.mask = masks_dev;
         q.row_stride = all ? (size_t)m->dims.input_size : (size_t)T * m->dims.input_size;
         q.row_offset = all ? 0 : (size_t)(T - 1) * m->dims.input_size;
@@ -945,15 +961,8 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
         if (drop) return fail(APE_ERR_UNSUPPORTED, "lstm_forward: ImuPoseLSTM has no Monte-Carlo dropout mode "
                               "(its monte_carlo_predictions is the plain forward, nn_models.py:246-251)");
         const size_t rows = (size_t)((flags & APE_FLAG_BROADCAST_X) ? 1 : B) * T;
-        if (rows > m->z_cap) {
-            hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-            (void)hipStreamIsCapturing((hipStream_t)stream, &st);
-            if (st != hipStreamCaptureStatusNone)
-                return fail(APE_ERR_CAPACITY, "lstm_forward: %zu input-layer rows exceed the workspace during stream capture", rows);
-            if (m->z_ws) { HIP_TRY(hipFree(m->z_ws)); m->z_ws = nullptr; m->z_cap = 0; }
-            HIP_TRY(hipMalloc((void**)&m->z_ws, rows * H * sizeof(float)));
-            m->z_cap = rows;
-        }
+        if (int rc = grow_ws(stream, (void**)&m->z_ws, &m->z_cap, rows, H * sizeof(float),
+                             "lstm_forward: %zu input-layer rows exceed the workspace during stream capture")) return rc;
         MlpParams q{};
         q.x = x_dev; q.y = nullptr; q.hidden_out = m->z_ws;
         q.wpack[0] = m->ff_wpack[0]; q.bias[0] = m->ff_bias[0];
@@ -965,309 +974,93 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
         if (e != hipSuccess) return fail(APE_ERR_HIP, "input-layer kernel launch failed: %s", hipGetErrorString(e));
         lstm_x = m->z_ws;
         flags &= ~(uint32_t)APE_FLAG_NORMALIZE_INPUT;        // done in front of the input layer
-        // Above 512 windows (where the first-generation kernel needs a second launch: 1480 us for 513 .. 1024 windows x 64 steps against
-        // 1020-1060 here) the LSTM runs one layer per launch on the persistent clusters of lstm_upper32.hip: layer 0 in the SEQ form
-        // with the wide input, layer 1 reading its sequence as is -- K = 512 per layer is the clusters' whole register image; the
-        // first-generation kernel's 16-member clusters re-read nothing either but spend 16 CUs on 32 rows.
-        // Chunks of 4096 windows bound the workspaces.
-        if (m->split32_ok && B > 512 && m->kernel_choice == APE_KERNEL_AUTO && m->c32_on && m->precision == APE_PRECISION_F32 &&
-            !m->replaying && !have_hs && !(flags & (APE_FLAG_ALL_STEPS | APE_FLAG_BROADCAST_X)) && x_ring == 0 && T >= 1 &&
-            (size_t)128 * T * 32768 < ((size_t)1 << 32)) {
-            const int chunk = 4096;
-            const int tiles_max = ((B < chunk ? B : chunk) + 31) / 32;
-            if ((size_t)tiles_max > m->split_tiles_cap || (size_t)T > m->split_steps_cap) {
-                hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-                (void)hipStreamIsCapturing((hipStream_t)stream, &st);
-                if (st != hipStreamCaptureStatusNone)
-                    return fail(APE_ERR_CAPACITY, "lstm_forward: the layer workspaces (%d tiles x %d steps) cannot grow during stream capture", tiles_max, T);
-                HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
-                if (m->zfrag_ws) { HIP_TRY(hipFree(m->zfrag_ws)); m->zfrag_ws = nullptr; }
-                if (m->hfrag_ws) { HIP_TRY(hipFree(m->hfrag_ws)); m->hfrag_ws = nullptr; }
-                if (m->ypart_ws) { HIP_TRY(hipFree(m->ypart_ws)); m->ypart_ws = nullptr; }
-                // (both dimensions only ever grow: a caller alternating between many short and few long windows does not reallocate)
-                const size_t tc = (size_t)tiles_max > m->split_tiles_cap ? (size_t)tiles_max : m->split_tiles_cap;
-                const size_t sc = (size_t)T > m->split_steps_cap ? (size_t)T : m->split_steps_cap;
-                m->split_tiles_cap = m->split_steps_cap = 0;
-                HIP_TRY(hipMalloc((void**)&m->zfrag_ws, tc * sc * 32768));
-                HIP_TRY(hipMalloc((void**)&m->hfrag_ws, tc * sc * 32768));
-                HIP_TRY(hipMalloc((void**)&m->ypart_ws, ape_upper32_ypart_bytes((int)tc * 32)));
-                m->split_tiles_cap = tc; m->split_steps_cap = sc;
-            }
-            for (int b0 = 0; b0 < B; b0 += chunk) {
-                const int nb = (B - b0 < chunk) ? B - b0 : chunk;
-                const int tiles = (nb + 31) / 32;
-                UpperParams u0{};
-                u0.xfrag = m->zfrag_ws; u0.xfrag_bytes = (size_t)tiles * T * 32768;
-                u0.w = m->wcl32[0]; u0.bias = m->bias[0]; u0.w_out = m->w_out;
-                u0.hx = m->hx; u0.hx_bytes = m->hx_bytes;
-                u0.xflags = m->xflags; u0.status = m->xflags + m->xflag_bytes / sizeof(unsigned); u0.done = u0.status - 3;
-                u0.xcc_slots = m->xcc_slots; u0.dbg_wg = m->dbg_wg;
-                u0.hseq = m->hfrag_ws; u0.hseq_bytes = (size_t)tiles * T * 32768;
-                u0.T = T; u0.O = m->dims.output_size; u0.n_tiles = tiles; u0.flags = flags & APE_FLAG_ALT_FORM;      // (selector: one-tile clusters on the blocking form, for A/B)
-                UpperParams u1 = u0;
-                u1.xfrag = m->hfrag_ws; u1.hseq = nullptr; u1.hseq_bytes = 0;
-                u1.w = m->wcl32[1]; u1.bias = m->bias[1]; u1.ypart = m->ypart_ws;
-                m->last_kernel = "ape_lstm_upper32";
-                hipError_t e2 = ape_launch_lstm_split32(m->z_ws + (size_t)b0 * T * H, nb, u0, u1, m->b_out,
-                                                        y_dev + (size_t)b0 * m->dims.output_size, f16v2_capacity(m->n_cus), (hipStream_t)stream);
-                if (e2 != hipSuccess) return fail(APE_ERR_HIP, "layer-split lstm launch failed: %s", hipGetErrorString(e2));
-            }
-            return APE_OK;
-        }
     }
+    // which kernels serve the call: csrc/ape_plan.h; from here on the plan is executed
+    const LstmCall call = lstm_call(m, B, T, flags, have_hs, x_ring);
+    const LstmPlan plan = plan_lstm(m->caps, m->dims, call);
+    if (plan.route == PLAN_SPLIT32) return split32_forward(m, plan, B, T, flags, y_dev, stream);
     if (ape_lstm_tile16_smem_bytes(H, L, m->KX, m->dims.output_size, drop) > 160 * 1024)
         return fail(APE_ERR_UNSUPPORTED, "lstm_forward: H=%d L=%d with dropout exceeds the 160 KiB LDS of a CU", H, L);
-
-    // Two kernels serve an LSTM batch.  The weight-stationary cluster kernel fills the chip from one launch of
-    // 1..1024 rows (512 with inter-layer dropout) and is the faster one per row on long windows; the batch-tile kernel
-    // needs 4096 rows (256 workgroups x 16) to fill the chip, but then runs dropout at no extra cost and pays no
-    // per-launch prologue / head, which decides short windows.  Under APE_KERNEL_AUTO the front of the batch goes to
-    // the batch-tile kernel in whole 4096-row waves and the rest to the cluster kernel, by a cost model calibrated
-    // on MI355X (tests/tools/time_big_batch.py).
-    // (a re-issue by ape_model_recover runs on the batch-tile kernel, in exact float32 whatever the precision switch)
-    const bool f16 = m->precision == APE_PRECISION_F16 && !m->replaying;
-    // all-steps output: the cluster kernel also writes every step's top-layer output to a [B,T,H] workspace and the
-    // head runs over those rows in a second, HBM-bound launch
-    const bool all_steps = (flags & APE_FLAG_ALL_STEPS) != 0;
-    const bool cdrop_c = drop && L > 1;
-    const int rows_per_cluster_launch = cluster_rows_per_launch(m->n_cus, H, cdrop_c || m->wide_cluster);
-    // injected masks are indexed over the whole batch, so such a call is served by ONE launch of one kernel
-    const bool masks_fit = !(flags & APE_FLAG_DROPOUT_MASKS) || !cdrop_c || B <= rows_per_cluster_launch ||
-                           m->kernel_choice == APE_KERNEL_CLUSTER;
-    // a caller-given initial state (h0, c0) is served by the batch-tile kernel, which loads it at step 0
-    bool use_cluster = m->cluster_ok && masks_fit && m->kernel_choice != APE_KERNEL_TILE16 && !(all_steps && f16) && !have_hs &&
-                       !m->replaying;
-    if (have_hs && f16) return fail(APE_ERR_UNSUPPORTED, "lstm_forward: the fp16 variant starts from the zero state only");
-    if (f16 && (!m->cluster_ok || drop || (flags & APE_FLAG_ALL_STEPS)))
-        return fail(APE_ERR_UNSUPPORTED, "lstm_forward: the fp16 variant covers last-step output without dropout on "
-                    "the cluster-kernel shapes only");
-    if (f16) use_cluster = true;
-    if (m->kernel_choice == APE_KERNEL_CLUSTER && !use_cluster && !m->replaying)
-        return fail(APE_ERR_UNSUPPORTED, "lstm_forward: the cluster kernel does not cover this model / these flags");
-    // one window, n dropout samples (monte_carlo_predictions, nn_models.py:191-207) up to 128 rows: the Monte-Carlo latency kernel
-    if (use_cluster && cdrop_c && (flags & APE_FLAG_BROADCAST_X) && !all_steps && !f16 && B <= 128 && T <= 64 && mc_small_fits(m, 1, B))
+    if (plan.route == PLAN_UNSUPPORTED)        // (err == nullptr: the one message that names B)
+        return plan.err ? fail(plan.err_code, "%s", plan.err) : fail(plan.err_code, "lstm_forward: injected masks with B=%d exceed one cluster launch", B);
+    if (plan.route == PLAN_MC_SMALL)
         return mc_small_launch(m, x_dev, 0, 1, B, T, flags, masks_dev, dropout_p, seed, y_dev, stream, x_ring);
-    int n16 = use_cluster ? 0 : B;               // leading rows that go to the batch-tile kernel
-    if (use_cluster && m->kernel_choice == APE_KERNEL_AUTO && !f16 && !all_steps && !(flags & APE_FLAG_DROPOUT_MASKS) && B > 4) {
-        const int w = auto_tile16_waves(&m->dims, m->n_cus, B, T, cdrop_c, drop ? 0 : gen2_of(m), m->wide_cluster);
-        const long long front = (long long)tile16_wave_rows(m->n_cus) * w;
-        n16 = (front < B) ? (int)front : B;
-    }
-    if (n16 > 0) {
+    if (plan.n16 > 0) {
         LstmParams p{};
-        p.x = lstm_x;
-        p.y = y_dev;
+        p.x = lstm_x; p.y = y_dev;
         for (int l = 0; l < L; ++l) { p.wpack[l] = m->wpack[l]; p.bias[l] = m->bias[l]; }
-        p.w_out = m->w_out;
-        p.b_out = m->b_out;
-        p.xx_m = m->stats;
-        p.xx_s = m->stats + m->dims.input_size;
-        p.masks = masks_dev;
-        p.B = n16; p.T = T; p.I = m->lstm_in; p.O = m->dims.output_size; p.KX = m->KX;
-        p.x_ring = x_ring;
-        p.flags = flags;
-        p.dropout_p = dropout_p;
-        p.seed = seed;
-        p.h0 = h0_dev; p.c0 = c0_dev; p.hs_rows = B;
-        p.row_base = row_base;
+        head_and_stats(m, &p);
+        p.masks = masks_dev; p.flags = flags; p.dropout_p = dropout_p; p.seed = seed;
+        p.B = plan.n16; p.T = T; p.I = m->lstm_in; p.O = m->dims.output_size; p.KX = m->KX; p.x_ring = x_ring;
+        p.h0 = h0_dev; p.c0 = c0_dev; p.hs_rows = B; p.row_base = row_base;
         m->last_kernel = "ape_lstm_tile16";
         hipError_t e = ape_launch_lstm_tile16(H, L, p, (hipStream_t)stream);
         if (e != hipSuccess) return fail(APE_ERR_HIP, "lstm kernel launch failed: %s", hipGetErrorString(e));
-        if (n16 == B) return APE_OK;
+        if (plan.n16 == B) return APE_OK;
     }
-    if (use_cluster) {
-        // smallest row tile count that still fits the batch on the chip: more clusters = more CUs busy
-        const bool cdrop = drop && L > 1;
-        const int nmt = cluster_nmt(m->n_cus, H, B - n16, cdrop || m->wide_cluster);      // (wide: at most two row tiles, like dropout)
-        const int rows_per_launch = 16 * nmt * cluster_capacity(m->n_cus, H);
-        const bool small = !f16 && !cdrop && !all_steps && B <= 4 && T + L <= 4096 && m->small_batch_path && !m->wide_cluster;   // latency path: VALU GEMV, one exchange per phase
-        const int small_uw = (flags & APE_FLAG_ALT_FORM) ? 4 : m->small_uw;
-        const int rest_plan = (f16 || small) ? PLAN_NONE : rest_kernel(B - n16, T, (!cdrop && !drop && !all_steps) ? gen2_of(m) : 0, m->n_cus);
-        if (rest_plan == PLAN_C32) {
-            // second-generation f32 kernel: 8-member clusters of 32 windows, 32x32x2 MFMA chain (lstm_cluster32.hip)
-            const int rpl2 = 32 * f16v2_capacity(m->n_cus);
-            for (int b0 = n16; b0 < B; b0 += rpl2) {
-                const int nb = (B - b0 < rpl2) ? B - b0 : rpl2;
-                ClusterParams c{};
-                c.x = (flags & APE_FLAG_BROADCAST_X) ? x_dev : x_dev + (size_t)b0 * T * m->dims.input_size;
-                c.y = y_dev + (size_t)b0 * m->dims.output_size;
-                for (int l = 0; l < L; ++l) {
-                    c.wcl[l] = reinterpret_cast<const float*>(m->wcl32s[l]); c.bias[l] = m->bias[l];
-                    c.gate_scale[l] = m->c32_scale[l]; c.gate_descale[l] = m->c32_descale[l];
-                }
-                c.w_out = m->w_out; c.b_out = m->b_out;
-                c.xx_m = m->stats; c.xx_s = m->stats + m->dims.input_size;
-                c.xx_r = m->stats + 2 * m->dims.input_size + 2 * m->dims.output_size;
-                c.hx = m->hx; c.hx_bytes = m->hx_bytes;
-                c.xflags = m->xflags; c.status = m->xflags + m->xflag_bytes / sizeof(unsigned);
-                c.ticket = c.status - 4; c.done = c.status - 3;
-                c.B = nb; c.T = T; c.I = m->dims.input_size; c.O = m->dims.output_size;
-                c.flags = flags; c.x_ring = x_ring;
-                c.xcc_slots = m->xcc_slots;
-                c.dbg_wg = m->dbg_wg;
-                m->last_kernel = "ape_lstm_cluster32";
-                hipError_t e = ape_launch_lstm_cluster32(H, L, m->KX, (nb + 31) / 32, c, (hipStream_t)stream);
-                if (e != hipSuccess) return fail(APE_ERR_HIP, "cluster32 lstm launch failed: %s", hipGetErrorString(e));
-            }
-            return APE_OK;
-        }
-        if (rest_plan == PLAN_C16) {
-            // second-generation kernel of the 3 x 128 model: 8-member clusters of 32 windows (lstm_cluster16.hip)
-            const int rpl2 = 32 * f16v2_capacity(m->n_cus);
-            for (int b0 = n16; b0 < B; b0 += rpl2) {
-                const int nb = (B - b0 < rpl2) ? B - b0 : rpl2;
-                ClusterParams c{};
-                c.x = (flags & APE_FLAG_BROADCAST_X) ? x_dev : x_dev + (size_t)b0 * T * m->dims.input_size;
-                c.y = y_dev + (size_t)b0 * m->dims.output_size;
-                for (int l = 0; l < L; ++l) { c.wcl[l] = m->wcl[l]; c.bias[l] = m->bias[l]; }
-                c.w_out = m->w_out; c.b_out = m->b_out;
-                c.xx_m = m->stats; c.xx_s = m->stats + m->dims.input_size;
-                c.xx_r = m->stats + 2 * m->dims.input_size + 2 * m->dims.output_size;
-                c.hx = m->hx; c.hx_bytes = m->hx_bytes;
-                c.xflags = m->xflags; c.status = m->xflags + m->xflag_bytes / sizeof(unsigned);
-                c.ticket = c.status - 4; c.done = c.status - 3;
-                c.B = nb; c.T = T; c.I = m->dims.input_size; c.O = m->dims.output_size;
-                c.flags = flags; c.x_ring = x_ring;
-                c.xcc_slots = m->xcc_slots;
-                c.dbg_wg = m->dbg_wg;
-                m->last_kernel = "ape_lstm_cluster16";
-                hipError_t e = ape_launch_lstm_cluster16(H, L, m->KX, nb, c, (hipStream_t)stream);
-                if (e != hipSuccess) return fail(APE_ERR_HIP, "cluster16 lstm launch failed: %s", hipGetErrorString(e));
-            }
-            return APE_OK;
-        }
-        if (rest_plan == PLAN_LV16) {
-            // short windows of the 3 x 128 model: level-synchronous 16-window clusters, two workgroups per CU (lstm_level16.hip)
-            const int rpl3 = 32 * ape_level16_max_clusters(m->n_cus);
-            for (int b0 = n16; b0 < B; b0 += rpl3) {
-                const int nb = (B - b0 < rpl3) ? B - b0 : rpl3;
-                ClusterParams c{};
-                c.x = (flags & APE_FLAG_BROADCAST_X) ? x_dev : x_dev + (size_t)b0 * T * m->dims.input_size;
-                c.y = y_dev + (size_t)b0 * m->dims.output_size;
-                for (int l = 0; l < L; ++l) { c.wcl[l] = m->wcl[l]; c.bias[l] = m->bias[l]; }
-                c.w_out = m->w_out; c.b_out = m->b_out;
-                c.xx_m = m->stats; c.xx_s = m->stats + m->dims.input_size;
-                c.xx_r = m->stats + 2 * m->dims.input_size + 2 * m->dims.output_size;
+    // rows [n16, B) in launches of plan.rows_per_launch: each route brings its weight image, its exchange buffer and its launcher
+    const bool all_steps = call.all_steps, small = plan.route == PLAN_SMALL;
+    const int O = m->dims.output_size;
+    if (all_steps)
+        if (int rc = grow_ws(stream, (void**)&m->hseq_ws, &m->hseq_cap, (size_t)B * T, H * sizeof(float),
+                             "lstm_forward: the all-steps workspace (%zu rows) cannot grow during stream capture")) return rc;
+    const int small_uw = call.alt_form ? 4 : m->small_uw;
+    m->last_kernel = plan.last_kernel;
+    for (int b0 = plan.n16; b0 < B; b0 += plan.rows_per_launch) {
+        const int nb = (B - b0 < plan.rows_per_launch) ? B - b0 : plan.rows_per_launch;
+        const float* xb = call.broadcast ? lstm_x : lstm_x + (size_t)b0 * T * m->lstm_in;
+        float* yb = y_dev + (size_t)b0 * O;
+        ClusterParams c = cluster_params(m, plan.route, L, xb, yb, nb, T, flags, x_ring);
+        hipError_t e = hipSuccess;
+        const char* what = "cluster";
+        switch (plan.route) {
+            case PLAN_C32:
+                for (int l = 0; l < L; ++l) { c.gate_scale[l] = m->c32_scale[l]; c.gate_descale[l] = m->c32_descale[l]; }
+                e = ape_launch_lstm_cluster32(H, L, m->KX, (nb + 31) / 32, c, (hipStream_t)stream); what = "cluster32";
+                break;
+            case PLAN_C16:
+                e = ape_launch_lstm_cluster16(H, L, m->KX, nb, c, (hipStream_t)stream); what = "cluster16";
+                break;
+            case PLAN_LV16:
                 c.hx = reinterpret_cast<float*>(m->gx16 + 256); c.hx_bytes = m->gx16_bytes; c.seq = reinterpret_cast<unsigned*>(m->gx16);
-                c.xflags = m->xflags; c.status = m->xflags + m->xflag_bytes / sizeof(unsigned);
-                c.ticket = c.status - 4; c.done = c.status - 3;
-                c.B = nb; c.T = T; c.I = m->dims.input_size; c.O = m->dims.output_size;
-                c.flags = flags & ~APE_FLAG_LV16_SINGLE; c.x_ring = x_ring;
-                // up to 16 rows per cluster of the device: one row tile per cluster, so that the rows spread over every CU
-                if (nb <= 16 * ape_level16_max_clusters(m->n_cus)) c.flags |= APE_FLAG_LV16_SINGLE;
-                c.xcc_slots = m->xcc_slots;
-                c.dbg_wg = m->dbg_wg;
-                m->last_kernel = "ape_lstm_level16";
-                hipError_t e = ape_launch_lstm_level16(H, L, m->KX, nb, c, (hipStream_t)stream);
-                if (e != hipSuccess) return fail(APE_ERR_HIP, "level16 lstm launch failed: %s", hipGetErrorString(e));
-            }
-            return APE_OK;
-        }
-        if (f16 && m->f16_v2 && ape_cluster_f16v2_supported(H, L, m->KX) && f16v2_capacity(m->n_cus) > 0 && B > 256) {
-            // second-generation fp16 kernel: 8-member clusters x 2 row sets of 16 that take turns (lstm_cluster_f16v2.hip)
-            const int rpl2 = 32 * f16v2_capacity(m->n_cus);
-            for (int b0 = 0; b0 < B; b0 += rpl2) {
-                const int nb = (B - b0 < rpl2) ? B - b0 : rpl2;
-                ClusterParams c{};
-                c.x = (flags & APE_FLAG_BROADCAST_X) ? x_dev : x_dev + (size_t)b0 * T * m->dims.input_size;
-                c.y = y_dev + (size_t)b0 * m->dims.output_size;
-                for (int l = 0; l < L; ++l) { c.wcl[l] = reinterpret_cast<const float*>(m->wcl16[l]); c.bias[l] = m->bias[l]; }
-                c.w_out = m->w_out; c.b_out = m->b_out;
-                c.xx_m = m->stats; c.xx_s = m->stats + m->dims.input_size;
-                c.xx_r = m->stats + 2 * m->dims.input_size + 2 * m->dims.output_size;
-                c.hx = m->hx; c.hx_bytes = m->hx_bytes;
-                c.xflags = m->xflags; c.status = m->xflags + m->xflag_bytes / sizeof(unsigned);
-                c.ticket = c.status - 4; c.done = c.status - 3;
-                c.B = nb; c.T = T; c.I = m->dims.input_size; c.O = m->dims.output_size;
-                c.flags = flags; c.x_ring = x_ring;
-                c.xcc_slots = m->xcc_slots;
-                c.dbg_wg = m->dbg_wg;
-                m->last_kernel = "ape_lstm_cluster_f16v2";
-                // (APE_FLAG_ALT_FORM: the 16-unit-member form, two workgroups per CU -- needs 2 x 16 x clusters workgroups resident)
-                const bool duo = (flags & APE_FLAG_ALT_FORM) != 0 && m->n_cus * 2 >= 16 * (((nb + 31) / 32 + 7) / 8 * 8);
-                if (duo) m->last_kernel = "ape_lstm_cluster_f16v2<duo>";
-                hipError_t e = ape_launch_lstm_cluster_f16v2(H, L, m->KX, (nb + 31) / 32, c, (hipStream_t)stream, duo);
-                if (e != hipSuccess) return fail(APE_ERR_HIP, "fp16 cluster lstm launch failed: %s", hipGetErrorString(e));
-            }
-            return APE_OK;
-        }
-        if (all_steps) {
-            const size_t rows = (size_t)B * T;
-            if (rows > m->hseq_cap) {
-                hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-                (void)hipStreamIsCapturing((hipStream_t)stream, &st);
-                if (st != hipStreamCaptureStatusNone)
-                    return fail(APE_ERR_CAPACITY, "lstm_forward: the all-steps workspace (%zu rows) cannot grow during stream capture", rows);
-                if (m->hseq_ws) { HIP_TRY(hipFree(m->hseq_ws)); m->hseq_ws = nullptr; m->hseq_cap = 0; }
-                HIP_TRY(hipMalloc((void**)&m->hseq_ws, rows * H * sizeof(float)));
-                m->hseq_cap = rows;
-            }
-        }
-        for (int b0 = n16; b0 < B; b0 += rows_per_launch) {
-            const int nb = (B - b0 < rows_per_launch) ? B - b0 : rows_per_launch;
-            ClusterParams c{};
-            // (lstm_x / lstm_in: the LSTM's own input -- ImuPoseLSTM's is the 256-wide activation of its input layer)
-            c.x = (flags & APE_FLAG_BROADCAST_X) ? lstm_x : lstm_x + (size_t)b0 * T * m->lstm_in;
-            c.y = all_steps ? nullptr : y_dev + (size_t)b0 * m->dims.output_size;
-            c.hseq = all_steps ? m->hseq_ws + (size_t)b0 * T * H : nullptr;
-            for (int l = 0; l < L; ++l) {
-                c.wcl[l] = f16 ? reinterpret_cast<const float*>(m->wcl16[l]) : (small && small_uw == 2) ? m->wcls[l] : m->wcl[l];
-                c.bias[l] = m->bias[l];
-            }
-            c.w_out = m->w_out; c.b_out = m->b_out;
-            c.xx_m = m->stats; c.xx_s = m->stats + m->dims.input_size;
-            c.xx_r = m->stats + 2 * m->dims.input_size + 2 * m->dims.output_size;
-            c.hx = m->hx; c.hx_bytes = m->hx_bytes;
-            if (small) { c.hx = reinterpret_cast<float*>(m->hxs + 256); c.hx_bytes = m->hxs_bytes; c.seq = reinterpret_cast<unsigned*>(m->hxs); }
-            c.xflags = m->xflags; c.status = m->xflags + m->xflag_bytes / sizeof(unsigned);
-            c.ticket = m->xflags + m->xflag_bytes / sizeof(unsigned) - 4;
-            c.done = c.ticket + 1;
-            c.B = nb; c.T = T; c.I = m->lstm_in; c.O = m->dims.output_size;
-            c.flags = flags & ~(uint32_t)APE_FLAG_ALL_STEPS;
-            c.x_ring = x_ring;
-            // injected masks are indexed [L-1, B, T, H] over the WHOLE batch: chunks need the full B stride,
-            // so a masked call is served by one launch only (checked below)
-            c.masks = masks_dev; c.dropout_p = dropout_p; c.seed = seed;
-            c.dbg_wg = m->dbg_wg;
-            c.xcc_slots = m->xcc_slots;
-            if (small && fk != nullptr) {             // (B <= 4: one launch)
-                c.fk_est = fk->est; c.fk_est_dtype = fk->est_dtype;
-                if (fk->denormalize) {
-                    c.fk_yy_m = m->stats + 2 * m->dims.input_size;
-                    c.fk_yy_s = c.fk_yy_m + m->dims.output_size;
+                c.flags = (flags & ~APE_FLAG_LV16_SINGLE) | (plan.lv16_single ? APE_FLAG_LV16_SINGLE : 0u);
+                e = ape_launch_lstm_level16(H, L, m->KX, nb, c, (hipStream_t)stream); what = "level16";
+                break;
+            case PLAN_F16V2:
+                e = ape_launch_lstm_cluster_f16v2(H, L, m->KX, (nb + 31) / 32, c, (hipStream_t)stream, plan_f16v2_duo(m->caps, call, nb)); what = "fp16 cluster";
+                break;
+            default: {        // the first-generation kernel, its fp16 variant, the latency kernel
+                if (all_steps) { c.y = nullptr; c.hseq = m->hseq_ws + (size_t)b0 * T * H; }
+                if (small) { c.hx = reinterpret_cast<float*>(m->hxs + 256); c.hx_bytes = m->hxs_bytes; c.seq = reinterpret_cast<unsigned*>(m->hxs); }
+                c.flags = flags & ~(uint32_t)APE_FLAG_ALL_STEPS;
+                c.masks = masks_dev; c.dropout_p = dropout_p; c.seed = seed;
+                if (small && fk != nullptr) {             // (B <= 4: one launch)
+                    c.fk_est = fk->est; c.fk_est_dtype = fk->est_dtype;
+                    if (fk->denormalize) {
+                        c.fk_yy_m = m->stats + 2 * m->dims.input_size;
+                        c.fk_yy_s = c.fk_yy_m + O;
+                    }
+                    memcpy(c.fk_body, m->body, sizeof(c.fk_body));
+                    c.fk_layout = m->dims.target_layout; c.fk_W = layout_est_width(c.fk_layout);
+                    fk->done = true;
                 }
-                memcpy(c.fk_body, m->body, sizeof(c.fk_body));
-                c.fk_layout = m->dims.target_layout; c.fk_W = layout_est_width(c.fk_layout);
-                fk->done = true;
+                c.row_base = (int)(row_base + b0);        // Philox counters over the call's global rows, whatever the split
+                bool classes = false;
+                const int clusters = xcd_class_clusters((nb + 16 * plan.nmt - 1) / (16 * plan.nmt), plan.capacity,
+                                                        plan.xcd_classes && xcd_classes_on(m, flags), &classes);
+                if (classes) c.flags |= APE_FLAG_XCD_CLASSES;
+                e = small ? ape_launch_lstm_cluster_small(H, L, m->KX, B == 1 ? 1 : (B == 2 ? 2 : 4), small_uw, c, (hipStream_t)stream)
+                    : plan.route == PLAN_F16 ? ape_launch_lstm_cluster_f16(H, L, m->KX, plan.nmt, clusters, c, (hipStream_t)stream)
+                                             : ape_launch_lstm_cluster(H, L, m->KX, plan.nmt, plan.cdrop, clusters, c, (hipStream_t)stream);
             }
-            if ((flags & APE_FLAG_DROPOUT_MASKS) && b0 + nb < B && cdrop)
-                return fail(APE_ERR_UNSUPPORTED, "lstm_forward: injected masks with B=%d exceed one cluster launch", B);
-            c.row_base = (int)(row_base + b0);        // Philox counters over the call's global rows, whatever the split
-            int clusters = (nb + 16 * nmt - 1) / (16 * nmt);
-            // f32 first-generation kernel: whole groups of 8 clusters (if the device holds them) form XCD-local clusters and hand
-            // their slices over inside that XCD's L2 (lstm_cluster.hip, APE_FLAG_XCD_CLASSES); the extra clusters own no rows
-            if (!small && !f16 && m->gen1_classes && !(flags & APE_FLAG_NO_XCD_CLASSES)) {   // (selector: A/B on one box)
-                const int c8 = (clusters + 7) / 8 * 8;
-                // (a launch of fewer than four clusters -- one stream's 25 Monte-Carlo rows -- stays as it is: there the rendezvous costs
-                //  more than the shorter hops save, 44.7 vs 43.8 us)
-                if (clusters >= 4 && c8 <= cluster_capacity(m->n_cus, H)) { clusters = c8; c.flags |= APE_FLAG_XCD_CLASSES; }
-            }
-            // no memset in the launch path: the kernel's last workgroup re-zeroes every polled word (self-cleaning)
-            m->last_kernel = small ? "ape_lstm_cluster_small" : f16 ? "ape_lstm_cluster_f16" : "ape_lstm_cluster";
-            hipError_t e = small ? ape_launch_lstm_cluster_small(H, L, m->KX, B == 1 ? 1 : (B == 2 ? 2 : 4), small_uw, c, (hipStream_t)stream)
-                           : f16 ? ape_launch_lstm_cluster_f16(H, L, m->KX, nmt, clusters, c, (hipStream_t)stream)
-                                 : ape_launch_lstm_cluster(H, L, m->KX, nmt, cdrop, clusters, c, (hipStream_t)stream);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "cluster lstm launch failed: %s", hipGetErrorString(e));
         }
-        if (all_steps) {
-            hipError_t e = ape_launch_head_rows(m->hseq_ws, B * T, H, m->dims.output_size, m->w_out, m->b_out, y_dev,
-                                                (hipStream_t)stream);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "head kernel launch failed: %s", hipGetErrorString(e));
-        }
-        return APE_OK;
+        if (e != hipSuccess) return fail(APE_ERR_HIP, "%s lstm launch failed: %s", what, hipGetErrorString(e));
     }
-
-    return fail(APE_ERR_UNSUPPORTED, "lstm_forward: no kernel covers this call");     // not reached
+    if (all_steps) {
+        hipError_t e = ape_launch_head_rows(m->hseq_ws, B * T, H, O, m->w_out, m->b_out, y_dev, (hipStream_t)stream);
+        if (e != hipSuccess) return fail(APE_ERR_HIP, "head kernel launch failed: %s", hipGetErrorString(e));
+    }
+    return APE_OK;
 }
 
 int ape_lstm_forward(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t flags,
@@ -1307,7 +1100,7 @@ int ape_model_set_kernel(ape_model_t* m, int32_t choice) {
     m->ffp_on = choice != APE_KERNEL_TILE16;           // (MLP regressor: TILE16 pins the tile kernel)
     if (choice == APE_KERNEL_CLUSTER_GEN1) choice = APE_KERNEL_CLUSTER;
     if (choice == APE_KERNEL_AUTO_GEN1) choice = APE_KERNEL_AUTO;
-    if (choice == APE_KERNEL_CLUSTER && !m->cluster_ok)
+    if (choice == APE_KERNEL_CLUSTER && !m->caps.cluster_ok)
         return fail(APE_ERR_UNSUPPORTED, "set_kernel: no cluster kernel for H=%d L=%d on a device with %d CUs (a cluster "
                     "needs %d)", m->dims.hidden_size, m->dims.num_layers, m->n_cus, m->dims.hidden_size / 16);
     m->kernel_choice = choice;
@@ -1321,7 +1114,7 @@ int ape_model_set_precision(ape_model_t* m, int32_t precision) {
         return fail(APE_ERR_INVALID_ARG, "set_precision: unknown precision %d", precision);
     m->f16_v2 = precision != APE_PRECISION_F16_GEN1;
     if (precision == APE_PRECISION_F16_GEN1) precision = APE_PRECISION_F16;
-    if (precision == APE_PRECISION_F16 && (!m->cluster_ok || m->wide_cluster))
+    if (precision == APE_PRECISION_F16 && (!m->caps.cluster_ok || m->caps.wide))
         return fail(APE_ERR_UNSUPPORTED, "set_precision: no fp16 kernel for H=%d L=%d", m->dims.hidden_size,
                     m->dims.num_layers);
     m->precision = precision;
@@ -1409,13 +1202,13 @@ static int check_and_reset(ape_model_t* m) {
                         "is usable again", st);
         }
     }
-    if (!m->cluster_ok) return APE_OK;
+    if (!m->caps.cluster_ok) return APE_OK;
     HIP_TRY(hipSetDevice(m->dims.device));
     // every stream of the device, non-blocking ones included: a launch that is still spinning must have ended (its
     // status word written) before the word is read, and nothing may be in flight when the flags are reset below
     HIP_TRY(hipDeviceSynchronize());
     unsigned st = 0;
-    HIP_TRY(hipMemcpy(&st, m->xflags + m->xflag_bytes / sizeof(unsigned), sizeof(st), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(&st, ctl_words(m).status, sizeof(st), hipMemcpyDeviceToHost));
     if (st != 0) {
         // an aborted launch skipped its self-cleaning: reset flags, counters and the status word from the host
         HIP_TRY(hipMemset(m->xflags, 0, m->xflag_bytes + 16));
@@ -1653,58 +1446,6 @@ int ape_streams_create(ape_model_t* m, int32_t n_streams, int32_t seq_len, int32
 // The pre-laid input is T x 1 KiB per sample row of a 2 x 256 model (lstm_upper32.hip), T x 512 B of the 3 x 128 model
 // (lstm_upper128.hip); it and -- 2 x 256 models -- launch A's sequence and input tiles sit behind ONE 32-bit buffer descriptor each, so
 // a bank that outgrows 2 GiB of any of them is chunked (launch B) or keeps the batch-tile route (launch A: 65 536 streams of 64 steps).
-// Sample rows from which a Monte-Carlo bank of a 2 x 256 model takes the weight-stationary route (layer 0 once per stream, the layer above
-// over the sample rows, both on lstm_upper32.hip): above 512 -- where the fused first-generation dropout kernel needs a second launch.
-// (Until round 5: 2048, two tiles per cluster -- a cluster with ONE tile paid its exchange in the open; with the SOLO form it does not.
-//  Measured, pocket, T = 6, frame of all streams: 21 x 25 rows 159 -> 117 us, 41 x 25 221 -> 160, 80 x 25 290 -> 168, 34 x 60 318 -> 167;
-//  up to 512 rows the one fused launch stays ahead: 20 x 25 97.5 against 116.)
-// ---- which route a Monte-Carlo bank takes, as pure arithmetic on (model shape, CU count, bank size): used by ape_streams_set_mc /
-// streams_step_impl and, for the CPU tests of the thresholds, by ape_debug_bank_route ---------------------------------------------------
-enum { BANK_FUSED = 0, BANK_SHARED_TILE16 = 1, BANK_UPPER32 = 2, BANK_UPPER128 = 3 };              // route of the layers above layer 0
-enum { BANK_A_NONE = 0, BANK_A_TILE16 = 1, BANK_A_SEQ32 = 2, BANK_A_ONE_LAYER = 3 };                // kernel of launch A (layer 0 once per stream)
-static bool bank_shares_layer0(long long sample_rows, int n_cus, bool can_up32, bool can_up128);
-static int bank_launch_a_form(int route, int H, int KX, int n_cus, int S, bool cluster_ok);
-#ifndef APE_BANK_SHARE_MIN_ROWS_128
-// the 3 x 128 model's route (lstm_upper128.hip; no one-tile form, every exchange of a one-tile cluster is exposed): from where the fused
-// first-generation dropout kernel needs a THIRD launch.  Measured, T = 6, frame of all streams, fused launches / this route: 11 x 50 rows
-// 125.4 / 137.9 us -- 21 x 50 213.8 / 141.6, 30 x 50 213.8 / 146.1, 40 x 50 215.8 / 150.2, 64 x 25 179.9 / 147.2 (2048 until round 5)
-#define APE_BANK_SHARE_MIN_ROWS_128 1025
-#endif
-#ifndef APE_BANK_A_ONE_LAYER_MAX_STREAMS
-// 2 x 256 banks: launch A on the first-generation kernel's one-layer form up to this many streams (three any-placement clusters of 32;
-// from four clusters on that kernel forms XCD classes and the rendezvous eats the gain).  Measured, pocket, T = 6, frame of all streams,
-// one-layer form against the SEQ form of lstm_upper32.hip: 21 x 25 108.1 / 118.7 us, 41 x 25 155.3 / 165.7, 64 x 25 157.2 / 165.2,
-// 80 x 25 173.0 / 178.7 -- 100 x 25 220.3 / 215.8, 200 x 25 341.5 / 338.3, 512 x 25 767.4 / 748.4.
-#define APE_BANK_A_ONE_LAYER_MAX_STREAMS 96
-#endif
-#ifndef APE_BANK_SHARE_MIN_ROWS
-#define APE_BANK_SHARE_MIN_ROWS 513
-#endif
-static bool bank_chunk_plan(bool up128, int S, int T, int n_mc, long long* chunk_rows) {
-    const long long total = (long long)S * n_mc;
-    const long long max_chunk = ((2047ll << 20) / ((long long)T * (up128 ? 512 : 1024))) / 1024 * 1024;
-    const bool l0_fits = up128 || (ape_lower32_hseq_bytes(S, T) < (2047ull << 20) && ape_lower32_xfrag_bytes(S, T) < (2047ull << 20));
-    if (max_chunk < 1024 || total >= (1ll << 31) || !l0_fits) return false;       // (the input builder indexes sample rows with 32 bits)
-    const long long n_chunks = (total + max_chunk - 1) / max_chunk;
-    long long chunk = ((total + n_chunks - 1) / n_chunks + 1023) / 1024 * 1024;
-    if (chunk > total) chunk = (total + 31) / 32 * 32;
-    *chunk_rows = chunk;
-    return true;
-}
-
-static bool bank_shares_layer0(long long sample_rows, int n_cus, bool can_up32, bool can_up128) {
-    return sample_rows >= 2LL * tile16_wave_rows(n_cus) ||
-           (can_up32 && sample_rows >= (can_up128 ? APE_BANK_SHARE_MIN_ROWS_128 : APE_BANK_SHARE_MIN_ROWS));
-}
-// launch A of a bank on `route` (a cooperative step on a healthy model; a replay or a forced kernel takes the batch-tile launch)
-static int bank_launch_a_form(int route, int H, int KX, int n_cus, int S, bool cluster_ok) {
-    if (route == BANK_FUSED) return BANK_A_NONE;
-    const bool one_layer_fits = cluster_ok && ape_cluster_layer0_supported(H, KX) && (S + 31) / 32 <= cluster_capacity(n_cus, H);
-    if (route == BANK_UPPER32) return (one_layer_fits && S <= APE_BANK_A_ONE_LAYER_MAX_STREAMS) ? BANK_A_ONE_LAYER : BANK_A_SEQ32;
-    if (route == BANK_UPPER128) return one_layer_fits ? BANK_A_ONE_LAYER : BANK_A_TILE16;
-    return BANK_A_TILE16;
-}
-
 // the subset frames' device workspaces (sized for the bank's S and n_mc); a pending subset frame of the bank can no longer be re-issued
 static void subset_free(ape_streams* b) {
     if (b->sub_x) (void)hipFree(b->sub_x);
@@ -1746,58 +1487,36 @@ int ape_streams_set_mc(ape_streams_t* b, int32_t n_mc, float dropout_p, uint64_t
         bank_free_regressor_ws(b);
         return fail(APE_ERR_HIP, "streams_set_mc: allocation failed: %s", hipGetErrorString(e));
     }
-    // Layer 0 once per stream (nn.LSTM's dropout sits BETWEEN the layers, so h_0(t) is the same for all samples of a
-    // stream): worth its extra launch from two batch-tile waves of sample rows on.  The [S,T,H] sequence lives in the
-    // model's all-steps workspace, sized here so that the step itself never allocates.
+    // the route (csrc/ape_plan.h).  The [S,T,H] sequence of a shared layer 0 lives in the model's all-steps workspace, sized here so
+    // that the step itself never allocates.
     ape_model* m = b->model;
-    // (on the weight-stationary route -- lstm_upper32.hip, both launches -- the sharing pays from APE_BANK_SHARE_MIN_ROWS sample rows on;
-    //  the 3 x 128 model's route, lstm_upper128.hip, from APE_BANK_SHARE_MIN_ROWS_128)
-    const long long sample_rows = (long long)b->S * n_mc;
-    const bool can_up128 = m->up128_ok && m->c32_on;
-    const bool can_up32 = (m->up32_ok && m->c32_on && f16v2_capacity(m->n_cus) >= 8) || can_up128;
-    b->shared_l0 = m->dims.model_kind == APE_MODEL_LSTM && m->upper_ok && m->kernel_choice == APE_KERNEL_AUTO && m->precision == APE_PRECISION_F32 &&
-                   dropout_p > 0.0f && n_mc >= 2 &&
-                   bank_shares_layer0(sample_rows, m->n_cus, can_up32, can_up128);
-    if (b->xfrag) { (void)hipFree(b->xfrag); b->xfrag = nullptr; }
-    if (b->ypart) { (void)hipFree(b->ypart); b->ypart = nullptr; }
-    if (b->xfrag0) { (void)hipFree(b->xfrag0); b->xfrag0 = nullptr; }
-    if (b->hfrag) { (void)hipFree(b->hfrag); b->hfrag = nullptr; }
-    b->up32 = false;
-    b->up128 = false;
-    if (b->maskbits) { (void)hipFree(b->maskbits); b->maskbits = nullptr; }
-    if (b->shared_l0) {
+    const BankPlan want = plan_bank(m->caps, m->dims, b->S, b->T, n_mc, dropout_p, m->kernel_choice, m->precision, m->c32_on, bank_l0_bytes(b->S, b->T));
+    b->plan = want;
+    if (want.route == BANK_UPPER32 || want.route == BANK_UPPER128) { b->plan.route = BANK_SHARED_TILE16; b->plan.a_form = BANK_A_TILE16; }   // (until its workspaces exist)
+    for (void** ws : {(void**)&b->xfrag, (void**)&b->ypart, (void**)&b->xfrag0, (void**)&b->hfrag, (void**)&b->maskbits})
+        if (*ws) { (void)hipFree(*ws); *ws = nullptr; }
+    if (want.shared_l0) {
         const size_t rows = (size_t)b->S * b->T;
         if (rows > m->hseq_cap) {
             if (m->hseq_ws) { HIP_TRY(hipFree(m->hseq_ws)); m->hseq_ws = nullptr; m->hseq_cap = 0; }
             HIP_TRY(hipMalloc((void**)&m->hseq_ws, rows * m->dims.hidden_size * sizeof(float)));
             m->hseq_cap = rows;
         }
-        if (can_up32) {
-            // chunks of equal size whose expanded input (T KiB per sample row) stays under 2 GiB -- inside one 32-bit buffer
-            // descriptor with offsets to spare; whole 1024-row waves of clusters where that costs nothing.  (Measured at
-            // 8192 x 25, T = 6: one 1.26 GB chunk 9.30 ms per frame, five 256 MB chunks -- the Infinity Cache's size -- 9.38 ms: a
-            // launch's prologue and tail cost more than the cache residency of the tiles buys; 288 GB of HBM make the footprint
-            // a non-issue.)
-            long long chunk = 0;
-            if (bank_chunk_plan(can_up128, b->S, b->T, n_mc, &chunk)) {
-                b->chunk_rows = (int)chunk;
-                if (can_up128) {
-                    // the 3 x 128 model: launch A stays on the batch-tile kernel ([S,T,H] in the model's sequence workspace), launch B =
-                    // layers 1 and 2 on lstm_upper128.hip
-                    HIP_TRY(hipMalloc((void**)&b->xfrag, ape_upper128_xfrag_bytes(b->chunk_rows, b->T)));
-                    HIP_TRY(hipMalloc((void**)&b->ypart, ape_upper128_ypart_bytes(b->chunk_rows)));
-                    HIP_TRY(hipMalloc((void**)&b->maskbits, ape_upper128_maskbits_bytes(b->chunk_rows, b->T)));
-                    b->up128 = true;
-                } else {
-                HIP_TRY(hipMalloc((void**)&b->xfrag, ape_upper32_xfrag_bytes(b->chunk_rows, b->T)));
-                HIP_TRY(hipMalloc((void**)&b->ypart, ape_upper32_ypart_bytes(b->chunk_rows)));
-                // layer 0 on the same cluster structure (its SEQ form): input tiles and the [tile][step] sequence, fragment order
-                HIP_TRY(hipMalloc((void**)&b->xfrag0, ape_lower32_xfrag_bytes(b->S, b->T)));
-                HIP_TRY(hipMalloc((void**)&b->hfrag, ape_lower32_hseq_bytes(b->S, b->T)));
-                b->up32 = true;
-                }
-            }
+        const int chunk = (int)want.chunk_rows;
+        if (want.route == BANK_UPPER128) {
+            // the 3 x 128 model: launch A stays on the batch-tile kernel ([S,T,H] in the model's sequence workspace), launch B =
+            // layers 1 and 2 on lstm_upper128.hip
+            HIP_TRY(hipMalloc((void**)&b->xfrag, ape_upper128_xfrag_bytes(chunk, b->T)));
+            HIP_TRY(hipMalloc((void**)&b->ypart, ape_upper128_ypart_bytes(chunk)));
+            HIP_TRY(hipMalloc((void**)&b->maskbits, ape_upper128_maskbits_bytes(chunk, b->T)));
+        } else if (want.route == BANK_UPPER32) {
+            HIP_TRY(hipMalloc((void**)&b->xfrag, ape_upper32_xfrag_bytes(chunk, b->T)));
+            HIP_TRY(hipMalloc((void**)&b->ypart, ape_upper32_ypart_bytes(chunk)));
+            // layer 0 on the same cluster structure (its SEQ form): input tiles and the [tile][step] sequence, fragment order
+            HIP_TRY(hipMalloc((void**)&b->xfrag0, ape_lower32_xfrag_bytes(b->S, b->T)));
+            HIP_TRY(hipMalloc((void**)&b->hfrag, ape_lower32_hseq_bytes(b->S, b->T)));
         }
+        b->plan = want;
     }
     return APE_OK;
 }
@@ -1872,7 +1591,7 @@ int ape_streams_get_bodies(ape_streams_t* b, double* out_host) {
 static void next_slot(const ape_streams* b, size_t I, float** out, int* rep, size_t* rep_stride) {
     const bool cold = b->frames == 0;
     *out = b->xring + (cold ? 0 : (size_t)(b->frames % b->T) * I);
-    const int copies = b->shared_l0 ? 1 : bank_copies(b);      // layer 0 shared: only a stream's first window copy is ever read
+    const int copies = b->plan.shared_l0 ? 1 : bank_copies(b);      // layer 0 shared: only a stream's first window copy is ever read
     *rep = cold ? b->T * copies : copies;
     *rep_stride = cold ? I : (size_t)b->T * I;
 }
@@ -1922,7 +1641,7 @@ int ape_streams_step(ape_streams_t* b, uint32_t flags, void* msg_dev, void* tail
 // a few streams in Monte-Carlo mode (one estimator's frame: S = 1) step on the Monte-Carlo latency kernel
 static bool bank_on_mc_small(const ape_streams* b) {
     const ape_model* m = b->model;
-    return m->dims.model_kind == APE_MODEL_LSTM && !b->shared_l0 && b->mc && b->dropout_p > 0.0f && m->dims.num_layers > 1 && b->S <= 8 && m->cluster_ok && b->T <= 64 &&
+    return m->dims.model_kind == APE_MODEL_LSTM && !b->plan.shared_l0 && b->mc && b->dropout_p > 0.0f && m->dims.num_layers > 1 && b->S <= 8 && m->caps.cluster_ok && b->T <= 64 &&
            mc_small_fits(m, b->S, b->n_mc);
 }
 
@@ -1973,7 +1692,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         q.pos = (int)(b->steps % b->smooth);
         q.cold = b->steps == 0 ? 1 : 0;
         q.msg_dtype = out_dtype; q.packed = packed ? 1 : 0;
-        if (status_out != nullptr && m->cluster_ok) { q.status_in = m->xflags + m->xflag_bytes / sizeof(unsigned); q.status_out = status_out; }
+        if (status_out != nullptr && m->caps.cluster_ok) { q.status_in = ctl_words(m).status; q.status_out = status_out; }
         if (status_out != nullptr && b->h_done != nullptr) { q.done_out = b->h_done; q.done_val = b->h_done_val; }
         q.part = b->post_part; q.part_cnt = b->post_cnt;
         return q;
@@ -1989,7 +1708,6 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         if (int rc = ff_bank_forward(m, b->xring, (size_t)m->dims.input_size, 0, b->S * b->n_mc, b->n_mc, norm, b->inj_masks,
                                      b->mc ? b->dropout_p : 0.0f, b->seed + b->mc_calls, b->ffhid, b->y_new, stream, ev_a, ev_z))
             return rc;
-        ++b->mc_calls;
     } else if (m->dims.model_kind == APE_MODEL_IMUPOSE) {
         // ImuPoseLSTM: the rings in time order (cold-start pad included), then the forward a subset frame runs over its compact windows
         // (x_ring = 0: the layer-split route above 512 windows applies) -- the same launches, hence the same bits
@@ -2001,69 +1719,43 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         if (ev_a) (void)hipEventRecord(ev_a, (hipStream_t)stream);
         if (int rc = lstm_forward_impl(m, b->xwin, b->S, b->T, flags | diag_wt, nullptr, 0.0f, 0, b->y_new, stream, 0)) return rc;
         if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
-        ++b->mc_calls;
-    } else if (b->shared_l0) {
+    } else if (b->plan.shared_l0) {
         if (!m->has_weights) return fail(APE_ERR_NOT_READY, "streams_step: weights not loaded");
         if ((size_t)b->S * b->T > m->hseq_cap) return fail(APE_ERR_CAPACITY, "streams_step: the layer-0 sequence workspace is gone");
         const int H = m->dims.hidden_size, I = m->dims.input_size, O = m->dims.output_size;
         // (the cooperative routes were planned by ape_streams_set_mc; a later set_kernel(TILE16 / AUTO_GEN1 / CLUSTER) or set_precision --
         //  the documented ways to keep persistent clusters off a shared GPU -- sends the step to the batch-tile route like a replay)
         const bool coop = !m->replaying && m->kernel_choice == APE_KERNEL_AUTO && m->c32_on && m->precision == APE_PRECISION_F32;
-        const bool cluster_route = b->up32 && coop;
+        const int route = coop ? b->plan.route : BANK_SHARED_TILE16, a_form = coop ? b->plan.a_form : BANK_A_TILE16;
         hipError_t e = hipSuccess;
-        // launch A on the first-generation cluster kernel's one-layer form (lstm_cluster.hip <H, 1, KX, 2>): 32 streams per cluster of H / 16
-        // members, every step's output -> [S,T,H] in the model's sequence workspace, as the batch-tile launch writes it
-        auto launch_a_one_layer = [&]() -> hipError_t {
-            ClusterParams c{};
-            c.x = b->xring; c.x_row_stride = (size_t)bank_copies(b) * b->T * I;
-            c.y = nullptr; c.hseq = m->hseq_ws;
-            c.wcl[0] = m->wcl[0]; c.bias[0] = m->bias[0];
-            c.w_out = m->w_out; c.b_out = m->b_out;
-            c.xx_m = m->stats; c.xx_s = m->stats + I; c.xx_r = m->stats + 2 * I + 2 * O;
-            c.hx = m->hx; c.hx_bytes = m->hx_bytes;
-            c.xflags = m->xflags; c.status = m->xflags + m->xflag_bytes / sizeof(unsigned);
-            c.ticket = c.status - 4; c.done = c.ticket + 1;
-            c.B = b->S; c.T = b->T; c.I = I; c.O = O; c.x_ring = x_ring;
-            c.flags = (flags & APE_FLAG_NORMALIZE_INPUT) | diag_wt;
-            c.dbg_wg = m->dbg_wg; c.xcc_slots = m->xcc_slots;
-            int clusters = (b->S + 31) / 32;
-            if (m->gen1_classes && !(diag_wt & APE_FLAG_NO_XCD_CLASSES)) {
-                const int c8 = (clusters + 7) / 8 * 8;
-                if (clusters >= 4 && c8 <= cluster_capacity(m->n_cus, H)) { clusters = c8; c.flags |= APE_FLAG_XCD_CLASSES; }
-            }
-            return ape_launch_lstm_cluster(H, 1, m->KX, 2, false, clusters, c, (hipStream_t)stream);
-        };
-        const int a_form = !coop ? BANK_A_TILE16
-                                 : bank_launch_a_form(b->up32 ? BANK_UPPER32 : b->up128 ? BANK_UPPER128 : BANK_SHARED_TILE16, H, m->KX, m->n_cus, b->S, m->cluster_ok);
-        // (2 x 256 models, small banks: the one-layer form's 16-member clusters have half the matrix work per CU and step of the 8-member
-        //  SEQ form below and the same exposed exchange; APE_BANK_A_ONE_LAYER_MAX_STREAMS above)
-        const bool a_on_gen1 = cluster_route && a_form == BANK_A_ONE_LAYER;
-        if (a_on_gen1) {
-            e = launch_a_one_layer();
+        if (a_form == BANK_A_ONE_LAYER) {
+            // launch A on the first-generation cluster kernel's one-layer form (lstm_cluster.hip <H, 1, KX, 2>): 32 streams per cluster of H / 16
+            // members, every step's output -> [S,T,H] in the model's sequence workspace, as the batch-tile launch writes it
+            // (2 x 256 models, small banks: the one-layer form's 16-member clusters have half the matrix work per CU and step of the 8-member
+            //  SEQ form below and the same exposed exchange; APE_BANK_A_ONE_LAYER_MAX_STREAMS)
+            // (the 3 x 128 bank, round 5: 1024 streams are 64 tiles of the batch-tile kernel -- a quarter
+            // of the chip for 54 us; here every CU holds 16 units of a cluster: 30.8 us).  Every bank size that fits the chip's clusters:
+            // 21 x 50 rows 141.6 -> 121.0 us per frame, 100 x 25 188.1 -> 164.5, 127 x 25 190.2 -> 166.4 against the batch-tile launch.
+            ClusterParams c = cluster_params(m, PLAN_GEN1, 1, b->xring, nullptr, b->S, b->T, (flags & APE_FLAG_NORMALIZE_INPUT) | diag_wt, x_ring);
+            c.x_row_stride = (size_t)bank_copies(b) * b->T * I;
+            c.hseq = m->hseq_ws;
+            bool classes = false;
+            const int clusters = xcd_class_clusters((b->S + 31) / 32, m->caps.cluster_capacity, xcd_classes_on(m, diag_wt), &classes);
+            if (classes) c.flags |= APE_FLAG_XCD_CLASSES;
+            e = ape_launch_lstm_cluster(H, 1, m->KX, 2, false, clusters, c, (hipStream_t)stream);
             if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: layer-0 cluster launch failed: %s", hipGetErrorString(e));
-        } else if (cluster_route) {
+        } else if (a_form == BANK_A_SEQ32) {
             // launch A on the weight-stationary structure (lstm_upper32.hip, SEQ form): S streams in tiles of 32 on the clusters,
             // every step's output in the fragment order launch B's input builder reads
             XFragParams xq{};
             xq.x = b->xring; xq.xfrag = b->xfrag0; xq.x_row_stride = (size_t)bank_copies(b) * b->T * I;
             xq.xx_m = norm ? m->stats : nullptr; xq.xx_s = norm ? m->stats + I : nullptr;
             xq.S = b->S; xq.T = b->T; xq.I = I; xq.x_ring = x_ring;
-            UpperParams u{};
+            UpperParams u = upper_params(m, b->T, (b->S + 31) / 32, diag_wt);
             u.xfrag = b->xfrag0; u.xfrag_bytes = ape_lower32_xfrag_bytes(b->S, b->T);
-            u.w = m->wcl32[0]; u.bias = m->bias[0]; u.w_out = m->w_out;
-            u.hx = m->hx; u.hx_bytes = m->hx_bytes;
-            u.xflags = m->xflags; u.status = m->xflags + m->xflag_bytes / sizeof(unsigned); u.done = u.status - 3;
-            u.xcc_slots = m->xcc_slots; u.dbg_wg = m->dbg_wg;
+            u.w = m->wcl32[0]; u.bias = m->bias[0];
             u.hseq = b->hfrag; u.hseq_bytes = ape_lower32_hseq_bytes(b->S, b->T);
-            u.T = b->T; u.O = O; u.n_tiles = (b->S + 31) / 32;
-            u.flags = diag_wt;
-            e = ape_launch_lstm_lower32(u, xq, f16v2_capacity(m->n_cus), (hipStream_t)stream);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: layer-0 cluster launch failed: %s", hipGetErrorString(e));
-        } else if (b->up128 && a_form == BANK_A_ONE_LAYER) {
-            // launch A of the 3 x 128 bank on the one-layer form (round 5: 1024 streams are 64 tiles of the batch-tile kernel -- a quarter
-            // of the chip for 54 us; here every CU holds 16 units of a cluster: 30.8 us).  Every bank size that fits the chip's clusters:
-            // 21 x 50 rows 141.6 -> 121.0 us per frame, 100 x 25 188.1 -> 164.5, 127 x 25 190.2 -> 166.4 against the batch-tile launch.
-            e = launch_a_one_layer();
+            e = ape_launch_lstm_lower32(u, xq, m->caps.f16v2_capacity, (hipStream_t)stream);
             if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: layer-0 cluster launch failed: %s", hipGetErrorString(e));
         } else {
         // launch A: layer 0 alone over the S windows (first copy of every stream's ring), all steps -> [S,T,H]
@@ -2071,8 +1763,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         a.x = b->xring; a.x_row_stride = (size_t)bank_copies(b) * b->T * I;
         a.y = nullptr; a.hseq = m->hseq_ws;
         a.wpack[0] = m->wpack[0]; a.bias[0] = m->bias[0];
-        a.w_out = m->w_out; a.b_out = m->b_out;
-        a.xx_m = m->stats; a.xx_s = m->stats + I;
+        head_and_stats(m, &a);
         a.B = b->S; a.T = b->T; a.I = I; a.O = O; a.KX = m->KX; a.x_ring = x_ring;
         a.flags = flags & APE_FLAG_NORMALIZE_INPUT;
         e = ape_launch_lstm_tile16(H, 1, a, (hipStream_t)stream);
@@ -2080,62 +1771,39 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         }
         // launch B: the layers above as an LSTM of their own over the S x n_mc sample rows; row r reads stream
         // r / n_mc's sequence under its own Philox mask (the counters of a fused launch over the same rows)
-        if (cluster_route) {
-            // weight-stationary form (lstm_upper32.hip): per chunk of sample rows the masked input in fragment order, the
-            // persistent cluster kernel, the head reduce
+        if (route == BANK_UPPER32 || route == BANK_UPPER128) {
+            // weight-stationary forms, per chunk of sample rows: the masked input in fragment order, the persistent cluster kernel, the head reduce
             const long long total = (long long)b->S * b->n_mc;
-            for (long long r0 = 0; r0 < total; r0 += b->chunk_rows) {
-                const int rows = (int)((total - r0 < b->chunk_rows) ? total - r0 : b->chunk_rows);
+            const bool a_frag = a_form == BANK_A_SEQ32;          // (launch A left its sequence in fragment order: lstm_upper32.hip only)
+            for (long long r0 = 0; r0 < total; r0 += b->plan.chunk_rows) {
+                const int rows = (int)((total - r0 < b->plan.chunk_rows) ? total - r0 : b->plan.chunk_rows);
                 ExpandParams xq{};
-                xq.hseq = a_on_gen1 ? m->hseq_ws : b->hfrag; xq.hseq_frag = a_on_gen1 ? 0 : 1;
+                xq.hseq = a_frag ? b->hfrag : m->hseq_ws; xq.hseq_frag = a_frag ? 1 : 0;
                 xq.xfrag = b->xfrag; xq.row_base = r0; xq.rows = rows; xq.T = b->T; xq.n_mc = b->n_mc;
                 xq.layer = 0; xq.dropout_p = b->dropout_p; xq.seed = b->seed + b->mc_calls;
-                xq.masks = b->inj_masks; xq.masks_rows = total;
-                UpperParams u{};
-                u.xfrag = b->xfrag; u.xfrag_bytes = ape_upper32_xfrag_bytes(rows, b->T); u.ypart = b->ypart;
-                u.w = m->wcl32[1]; u.bias = m->bias[1]; u.w_out = m->w_out;
-                u.hx = m->hx; u.hx_bytes = m->hx_bytes;
-                u.xflags = m->xflags; u.status = m->xflags + m->xflag_bytes / sizeof(unsigned); u.done = u.status - 3;
-                u.xcc_slots = m->xcc_slots; u.dbg_wg = m->dbg_wg;
-                u.T = b->T; u.O = O; u.n_tiles = (rows + 31) / 32;
-                u.flags = diag_wt;
+                xq.masks = b->inj_masks; xq.masks_rows = total;      // (test hooks: the caller's masks for every mask layer)
+                hipEvent_t ev_a, ev_z;
+                prof_pair(&ev_a, &ev_z);
+                if (route == BANK_UPPER32) {
+                    UpperParams u = upper_params(m, b->T, (rows + 31) / 32, diag_wt);
+                    u.xfrag = b->xfrag; u.xfrag_bytes = ape_upper32_xfrag_bytes(rows, b->T); u.ypart = b->ypart;
+                    u.w = m->wcl32[1]; u.bias = m->bias[1];
 #ifdef APE_ABLATE
-                // timing experiments of the ablation library only (tests/tools/ablate_upper32.py; results are garbage)
-                if (const char* ab = getenv("APE_UP32_ABLATE")) u.flags = (unsigned)strtoul(ab, nullptr, 0);
+                    // timing experiments of the ablation library only (tests/tools/ablate_upper32.py; results are garbage)
+                    if (const char* ab = getenv("APE_UP32_ABLATE")) u.flags = (unsigned)strtoul(ab, nullptr, 0);
 #endif
-                hipEvent_t ev_a, ev_z;
-                prof_pair(&ev_a, &ev_z);
-                m->last_kernel = "ape_lstm_upper32";
-                e = ape_launch_lstm_upper32(u, xq, m->b_out, b->y_new + (size_t)r0 * O, f16v2_capacity(m->n_cus), (hipStream_t)stream,
-                                            ev_a, ev_z);
+                    m->last_kernel = "ape_lstm_upper32";
+                    e = ape_launch_lstm_upper32(u, xq, m->b_out, b->y_new + (size_t)r0 * O, m->caps.f16v2_capacity, (hipStream_t)stream, ev_a, ev_z);
+                } else {
+                    // the 3 x 128 model: layers 1 and 2 on the four-member clusters of lstm_upper128.hip, with layer 1's keep bits
+                    Upper128Params u = upper_params<Upper128Params>(m, b->T, (rows + 31) / 32, diag_wt);
+                    u.xfrag = b->xfrag; u.xfrag_bytes = ape_upper128_xfrag_bytes(rows, b->T); u.maskbits = b->maskbits; u.ypart = b->ypart;
+                    u.w[0] = m->wup128[1]; u.w[1] = m->wup128[2]; u.bias[0] = m->bias[1]; u.bias[1] = m->bias[2]; u.dropout_p = b->dropout_p;
+                    m->last_kernel = "ape_lstm_upper128";
+                    e = ape_launch_lstm_upper128(u, xq, m->b_out, b->y_new + (size_t)r0 * O, m->caps.up128_classes, (hipStream_t)stream, ev_a, ev_z);
+                }
                 if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: upper-layer cluster launch failed: %s", hipGetErrorString(e));
             }
-            ++b->mc_calls;
-        } else if (b->up128 && coop) {
-            // the 3 x 128 model: layers 1 and 2 on the four-member weight-stationary clusters (lstm_upper128.hip), per chunk of sample
-            // rows: masked input + layer-1 keep bits, the persistent kernel, the head reduce
-            const long long total = (long long)b->S * b->n_mc;
-            for (long long r0 = 0; r0 < total; r0 += b->chunk_rows) {
-                const int rows = (int)((total - r0 < b->chunk_rows) ? total - r0 : b->chunk_rows);
-                ExpandParams xq{};
-                xq.hseq = m->hseq_ws; xq.hseq_frag = 0; xq.xfrag = b->xfrag; xq.row_base = r0; xq.rows = rows; xq.T = b->T; xq.n_mc = b->n_mc;
-                xq.layer = 0; xq.dropout_p = b->dropout_p; xq.seed = b->seed + b->mc_calls;
-                xq.masks = b->inj_masks; xq.masks_rows = total;      // (test hooks: the caller's masks for both mask layers)
-                Upper128Params u{};
-                u.xfrag = b->xfrag; u.xfrag_bytes = ape_upper128_xfrag_bytes(rows, b->T); u.maskbits = b->maskbits; u.ypart = b->ypart;
-                u.w[0] = m->wup128[1]; u.w[1] = m->wup128[2]; u.bias[0] = m->bias[1]; u.bias[1] = m->bias[2]; u.w_out = m->w_out;
-                u.hx = m->hx; u.hx_bytes = m->hx_bytes;
-                u.xflags = m->xflags; u.status = m->xflags + m->xflag_bytes / sizeof(unsigned); u.done = u.status - 3;
-                u.xcc_slots = m->xcc_slots;
-                u.T = b->T; u.O = O; u.n_tiles = (rows + 31) / 32;
-                u.flags = diag_wt; u.dropout_p = b->dropout_p; u.dbg_wg = m->dbg_wg;
-                hipEvent_t ev_a, ev_z;
-                prof_pair(&ev_a, &ev_z);
-                m->last_kernel = "ape_lstm_upper128";
-                e = ape_launch_lstm_upper128(u, xq, m->b_out, b->y_new + (size_t)r0 * O, (m->n_cus / 4) / 8 * 8, (hipStream_t)stream, ev_a, ev_z);
-                if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: upper-layer cluster launch failed: %s", hipGetErrorString(e));
-            }
-            ++b->mc_calls;
         } else {
         if (b->inj_masks) return fail(APE_ERR_UNSUPPORTED, "streams_step: injected masks (test hook) on the batch-tile shared-layer-0 route");
         LstmParams q{};
@@ -2153,7 +1821,6 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         e = ape_launch_lstm_tile16(H, LU, q, (hipStream_t)stream);
         if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
         if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: upper-layer launch failed: %s", hipGetErrorString(e));
-        ++b->mc_calls;
         }
     } else if (bank_on_mc_small(b)) {
         // a few streams in Monte-Carlo mode (one estimator's frame: S = 1): the latency kernel reads the first copy of every
@@ -2170,7 +1837,6 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
                                      b->dropout_p, b->seed + b->mc_calls, b->y_new, stream, x_ring, &fr))
             return rc;
         if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
-        ++b->mc_calls;
     } else {
         hipEvent_t ev_a, ev_z;
         prof_pair(&ev_a, &ev_z);
@@ -2180,8 +1846,8 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
                                        drop ? b->inj_masks : nullptr, drop ? b->dropout_p : 0.0f, b->seed + b->mc_calls, b->y_new, stream, x_ring))
             return rc;
         if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
-        ++b->mc_calls;
     }
+    ++b->mc_calls;       // (every branch above enqueued one forward under seed + mc_calls)
     StreamPostParams q = post_params();
     b->last_post_form = ape_stream_post_form(q, q.part != nullptr && (!spread || b->post_spread != nullptr));
     hipError_t e = spread ? ape_launch_stream_post_spread(q, SpreadArgs{b->post_spread}, b->last_post_form, (hipStream_t)stream, b->bodies.dev)
@@ -2244,7 +1910,7 @@ int ape_streams_frame_host(ape_streams_t* b, int32_t kind, const float* rows_hos
     const double t_begin = now_us();
     memcpy(b->h_rows, rows_host, rows_bytes);
     // (a sentinel, not zero: in the single-launch frame an aborted launch never reaches the tail that writes the word)
-    *b->h_status = m->cluster_ok ? 0xFFFFFFFFu : 0u;       // (no cooperative kernel on this model: nothing writes the word, nothing can abort)
+    *b->h_status = m->caps.cluster_ok ? 0xFFFFFFFFu : 0u;       // (no cooperative kernel on this model: nothing writes the word, nothing can abort)
     // where the bank steps on the Monte-Carlo latency kernel its extra workgroups build the rows' features (two launches per frame);
     // else the feature builder's own launch in front of the step
     const bool one_launch = bank_on_mc_small(b) && b->inj_masks == nullptr && mc_small_builder_fits(m, b->S, b->n_mc, b->T) && I == m->dims.input_size && b->xring != nullptr;
@@ -2421,7 +2087,7 @@ static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_
     q.smooth = b->smooth; q.n_mc = b->n_mc;
     q.msg_dtype = out_dtype; q.packed = packed ? 1 : 0;
     q.part = b->post_part; q.part_cnt = b->post_cnt;     // (sized for S >= K entries)
-    if (hw.status_out != nullptr && m->cluster_ok) { q.status_in = m->xflags + m->xflag_bytes / sizeof(unsigned); q.status_out = hw.status_out; }
+    if (hw.status_out != nullptr && m->caps.cluster_ok) { q.status_in = ctl_words(m).status; q.status_out = hw.status_out; }
     if (hw.done_out != nullptr) { q.done_out = hw.done_out; q.done_val = hw.done_val; }      // (word j behind list entry j's row)
     b->last_post_form = ape_stream_post_form(q, q.part != nullptr && (!(flags & APE_FLAG_SPREAD) || b->post_spread != nullptr));
     hipError_t e = (flags & APE_FLAG_SPREAD)
@@ -2573,7 +2239,7 @@ int ape_streams_frame_subset_host(ape_streams_t* b, int32_t kind, const float* r
     const double t_begin = now_us();
     memcpy(h_rows, rows_host, (size_t)K * width * sizeof(float));
     subset_fill_desc(b, streams_host, K, h_desc);
-    *b->h_status = m->cluster_ok ? 0xFFFFFFFFu : 0u;            // (as ape_streams_frame_host: a sentinel where a kernel writes the word)
+    *b->h_status = m->caps.cluster_ok ? 0xFFFFFFFFu : 0u;            // (as ape_streams_frame_host: a sentinel where a kernel writes the word)
     SubsetRowsParams rp{};
     rp.rows = h_rows; rp.desc = h_desc; rp.xring = b->xring; rp.xw = b->sub_x;
     rp.K = K; rp.width = width; rp.kind = kind & ~APE_PARSE_BIG_ENDIAN; rp.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0; rp.T = b->T; rp.I = I;
@@ -3019,8 +2685,8 @@ static int replay_entry(ape_model_t* m, const ApeJournalEntry& e) {
 
 // internal diagnostic accessor (not part of the public header): copies the 2 stamp words
 int ape_debug_read_stamps(ape_model_t* m, unsigned long long out[14]) {
-    if (!m || !m->cluster_ok) return APE_ERR_INVALID_ARG;
-    HIP_TRY(hipMemcpy(out, m->xflags + m->xflag_bytes / sizeof(unsigned) + 4, 112, hipMemcpyDeviceToHost));
+    if (!m || !m->caps.cluster_ok) return APE_ERR_INVALID_ARG;
+    HIP_TRY(hipMemcpy(out, ctl_words(m).status + 4, 112, hipMemcpyDeviceToHost));
     return APE_OK;
 }
 
@@ -3045,54 +2711,25 @@ int ape_debug_pack_c32_split(const float* w_ih, int in_l, const float* w_hh, int
     return pack_c32_split(w_ih, in_l, w_hh, H, KXl, kx_f32, out);
 }
 
-// internal: the batch split of lstm_forward for a device with `n_cus` CUs, no GPU needed.
-// out = {rows to the batch-tile kernel, row tiles per cluster, clusters per launch, cluster launches, cluster capacity}
-// `c32`: the model / call is eligible for the second-generation f32 kernel (what lstm_forward_impl passes for an eval-mode,
-// last-step call on a 2 x 256 model); out[5] = the kernel that serves the rest (PLAN_*), with the second-generation kernel out[1]
-// (row tiles) is 2 = its 32-row clusters
+// internal: the batch split of lstm_forward for a device with `n_cus` CUs, no GPU needed: plan_lstm for a healthy model under
+// APE_KERNEL_AUTO, float32, last-step output.  `cdrop`: a dropout call; `c32` = 0: the second-generation kernels switched off.
+// out = {rows to the batch-tile kernel, row tiles per cluster, clusters of the first launch, cluster launches, cluster capacity,
+// the kernel that serves the rest (PLAN_* of ape_plan.h)}; with the second-generation kernels out[1] (row tiles) is 2 = their 32-row clusters.
+// The dims' model_kind counts: an APE_MODEL_FF model has no LSTM route (out = {B, 0, 0, 0, capacity, PLAN_NONE}), ImuPoseLSTM dims are planned
+// with their 256-wide LSTM input and can answer out[5] = PLAN_SPLIT32 (6), a value beyond the six the 2 x 256 / 3 x 128 LSTMs produce
 int ape_debug_plan2(const ape_dims_t* dims, int n_cus, int B, int T, int cdrop, int c32, int out[6]) {
     if (!dims || !out || n_cus < 1 || B < 1 || T < 1) return APE_ERR_INVALID_ARG;
-    const int H = dims->hidden_size;
-    const int cap = cluster_capacity(n_cus, H);
-    out[4] = cap; out[5] = PLAN_NONE;
-    if (cap < 1) { out[0] = B; out[1] = out[2] = out[3] = 0; return APE_OK; }
-    const bool g2 = c32 != 0 && !cdrop && f16v2_capacity(n_cus) > 0;
-    const int gen2 = !g2 ? 0 : ape_cluster32_supported(H, dims->num_layers, padded_input(dims->input_size)) ? 32
-                     : ape_cluster16_supported(H, dims->num_layers, padded_input(dims->input_size))
-                           ? ((ape_level16_supported(H, dims->num_layers, padded_input(dims->input_size)) && ape_level16_max_clusters(n_cus) > 0) ? 48 : 16) : 0;
-    long long n16 = 0;
-    if (B > 4) n16 = (long long)tile16_wave_rows(n_cus) * auto_tile16_waves(dims, n_cus, B, T, cdrop != 0, gen2);
-    if (n16 > B) n16 = B;
-    out[0] = (int)n16;
-    const int rest = B - (int)n16;
-    out[1] = out[2] = out[3] = 0;
-    if (rest > 0) {
-        out[5] = (B <= 4 && !cdrop) ? PLAN_SMALL : rest_kernel(rest, T, gen2, n_cus);
-        if (out[5] == PLAN_C32 || out[5] == PLAN_C16) {
-            const int rpl2 = 32 * f16v2_capacity(n_cus);
-            out[1] = 2;
-            out[3] = (rest + rpl2 - 1) / rpl2;
-            out[2] = ((rest < rpl2 ? rest : rpl2) + 31) / 32;
-        } else if (out[5] == PLAN_LV16) {
-            const int rpl3 = 32 * ape_level16_max_clusters(n_cus);
-            const bool single = rest <= rpl3 / 2;                 // one row tile per cluster (APE_FLAG_LV16_SINGLE)
-            out[1] = single ? 1 : 2;
-            out[3] = (rest + rpl3 - 1) / rpl3;
-            out[2] = single ? (rest + 15) / 16 : ((rest < rpl3 ? rest : rpl3) + 31) / 32;
-        } else {
-            const int nmt = cluster_nmt(n_cus, H, rest, cdrop != 0), rpl = 16 * nmt * cap;
-            out[1] = nmt;
-            out[3] = (rest + rpl - 1) / rpl;
-            const int first = rest < rpl ? rest : rpl;
-            out[2] = (first + 16 * nmt - 1) / (16 * nmt);
-        }
-    }
+    const ApeCaps caps = ape_caps(dims, n_cus);
+    LstmCall call;
+    call.B = B; call.T = T; call.drop = call.philox = cdrop != 0; call.c32_on = c32 != 0;
+    const LstmPlan p = plan_lstm(caps, *dims, call);
+    out[0] = p.n16; out[1] = p.nmt; out[2] = p.clusters; out[3] = p.launches; out[4] = caps.cluster_capacity; out[5] = p.route;
     return APE_OK;
 }
 int ape_debug_bank_chunks(int up128, int S, int T, int n_mc, long long out[3]) {
     if (!out || S < 1 || T < 1 || n_mc < 1) return APE_ERR_INVALID_ARG;
     long long chunk = 0;
-    out[0] = bank_chunk_plan(up128 != 0, S, T, n_mc, &chunk) ? 1 : 0;
+    out[0] = bank_chunk_plan(up128 != 0, S, T, n_mc, bank_l0_bytes(S, T), &chunk) ? 1 : 0;
     out[1] = chunk;
     out[2] = out[0] ? ((long long)S * n_mc + chunk - 1) / chunk : 0;
     return APE_OK;
@@ -3102,19 +2739,8 @@ int ape_debug_bank_chunks(int up128, int S, int T, int n_mc, long long out[3]) {
 // dropout on (pure host arithmetic, for the CPU tests): out = {layer 0 shared 0/1, route BANK_*, launch A's kernel BANK_A_*, chunk rows}
 int ape_debug_bank_route(const ape_dims_t* dims, int n_cus, int S, int T, int n_mc, long long out[4]) {
     if (!dims || !out || n_cus < 1 || S < 1 || T < 1 || n_mc < 1) return APE_ERR_INVALID_ARG;
-    const int H = dims->hidden_size, L = dims->num_layers, O = dims->output_size, KX = padded_input(dims->input_size);
-    const bool lstm = dims->model_kind == APE_MODEL_LSTM;
-    const bool cluster_ok = lstm && ape_cluster_supported(H, L, KX) && cluster_capacity(n_cus, H) >= 1;
-    const bool upper_ok = lstm && ((H == 256 && L == 2) || (H == 128 && L == 3));
-    const bool up32_ok = cluster_ok && ape_cluster32_supported(H, L, KX) && f16v2_capacity(n_cus) > 0 && ape_upper32_supported(H, L, O);
-    const bool up128_ok = cluster_ok && ape_upper128_supported(H, L, O) && (n_cus / 4) / 8 * 8 >= 8;
-    const bool can_up128 = up128_ok, can_up32 = (up32_ok && f16v2_capacity(n_cus) >= 8) || can_up128;
-    const long long rows = (long long)S * n_mc;
-    const bool shared = upper_ok && n_mc >= 2 && bank_shares_layer0(rows, n_cus, can_up32, can_up128);
-    long long chunk = 0;
-    int route = BANK_FUSED;
-    if (shared) route = (can_up32 && bank_chunk_plan(can_up128, S, T, n_mc, &chunk)) ? (can_up128 ? BANK_UPPER128 : BANK_UPPER32) : BANK_SHARED_TILE16;
-    out[0] = shared ? 1 : 0; out[1] = route; out[2] = bank_launch_a_form(route, H, KX, n_cus, S, cluster_ok); out[3] = chunk;
+    const BankPlan p = plan_bank(ape_caps(dims, n_cus), *dims, S, T, n_mc, 0.5f, APE_KERNEL_AUTO, APE_PRECISION_F32, true, bank_l0_bytes(S, T));
+    out[0] = p.shared_l0 ? 1 : 0; out[1] = p.route; out[2] = p.a_form; out[3] = p.chunk_rows;
     return APE_OK;
 }
 
@@ -3127,29 +2753,24 @@ int ape_debug_plan(const ape_dims_t* dims, int n_cus, int B, int T, int cdrop, i
 
 const char* ape_model_last_kernel(const ape_model_t* m) { return m ? m->last_kernel : ""; }
 
+// the kernel that serves an eval-mode call of (B, T) -- under AUTO the one that takes the larger part -- by its instantiation's name
 const char* ape_lstm_kernel_name(const ape_model_t* m, int32_t B, int32_t T) {
     if (!m) return "";
     if (m->dims.model_kind == APE_MODEL_FF)        // (B rows of the last step, eval mode)
         return (m->ffp_ok && m->ffp_on && B >= 64 * m->n_cus) ? "ape_mlp_pipe" : m->kernel_name.c_str();
-    if (m->precision == APE_PRECISION_F16)
-        return (m->f16_v2 && ape_cluster_f16v2_supported(m->dims.hidden_size, m->dims.num_layers, m->KX) &&
-                f16v2_capacity(m->n_cus) > 0 && B > 256) ? "ape_lstm_cluster_f16v2" : "ape_lstm_cluster_f16";
-    if (!m->cluster_ok || m->kernel_choice == APE_KERNEL_TILE16) return m->kernel_name.c_str();
-    // ImuPoseLSTM above 512 windows: one layer per launch on lstm_upper32.hip's persistent clusters (lstm_forward_impl)
-    if (m->split32_ok && B > 512 && m->kernel_choice == APE_KERNEL_AUTO && m->c32_on && m->precision == APE_PRECISION_F32)
-        return "ape_lstm_upper32<32, true> + <32, false>";
-    // under AUTO the kernel that takes the larger part of an eval-mode batch of this shape
-    if (m->kernel_choice == APE_KERNEL_AUTO && B > 4 && T >= 1) {
-        if (2LL * tile16_wave_rows(m->n_cus) * auto_tile16_waves(&m->dims, m->n_cus, B, T, false, gen2_of(m), m->wide_cluster) > B) return m->kernel_name.c_str();
+    if (B < 1 || T < 1) return m->kernel_name.c_str();
+    const LstmPlan p = plan_lstm(m->caps, m->dims, lstm_call(m, B, T, 0, false, 0));
+    if (2LL * p.n16 > B) return m->kernel_name.c_str();
+    switch (p.route) {
+        case PLAN_SPLIT32: return "ape_lstm_upper32<32, true> + <32, false>";
+        case PLAN_F16V2: return "ape_lstm_cluster_f16v2";
+        case PLAN_F16: return "ape_lstm_cluster_f16";
+        case PLAN_C32: return T <= APE_C32_ENDS_MAX_T ? "ape_lstm_cluster32<256, 2, 32, true>" : "ape_lstm_cluster32<256, 2, 32, false>";   // (two instantiations: lstm_cluster32.hip on ENDS)
+        case PLAN_LV16: return "ape_lstm_level16<128, 3, 64>";
+        case PLAN_C16: return "ape_lstm_cluster16<128, 3, 64, 2>";
+        case PLAN_GEN1: case PLAN_SMALL: return m->cluster_name.c_str();      // (the latency kernel shares the first generation's register image)
     }
-    if (m->c32_ok && m->c32_split && m->c32_on && m->precision == APE_PRECISION_F32 && B > 512)      // (two instantiations: lstm_cluster32.hip on ENDS)
-        return T <= APE_C32_ENDS_MAX_T ? "ape_lstm_cluster32<256, 2, 32, true>" : "ape_lstm_cluster32<256, 2, 32, false>";
-    if (m->c16_ok && m->c32_on && m->precision == APE_PRECISION_F32) {
-        const int k = rest_kernel(B, T, gen2_of(m), m->n_cus);
-        if (k == PLAN_LV16) return "ape_lstm_level16<128, 3, 64>";
-        if (k == PLAN_C16) return "ape_lstm_cluster16<128, 3, 64, 2>";
-    }
-    return m->cluster_name.c_str();
+    return m->kernel_name.c_str();
 }
 
 }  // extern "C"

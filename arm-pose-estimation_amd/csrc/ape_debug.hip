@@ -17,30 +17,30 @@ int ape_debug_poke(ape_model_t* m, int which, unsigned value) {
         APE_DBG_TRY(hipMemcpy(m->ffp_ctl + (which == 4 ? 8 * 16 : 0), &value, sizeof(value), hipMemcpyHostToDevice));
         return APE_OK;
     }
-    if (m && m->cluster_ok && which == 6) {
+    if (m && m->caps.cluster_ok && which == 6) {
         APE_DBG_TRY(hipSetDevice(m->dims.device));
         APE_DBG_TRY(hipDeviceSynchronize());
         APE_DBG_TRY(hipMemcpy(m->xcc_slots + 64, &value, sizeof(value), hipMemcpyHostToDevice));
         return APE_OK;
     }
-    if (m && m->mcs_ok && which == 7) {          // the Monte-Carlo latency kernel's launch number (upper bits of its granule tags)
+    if (m && m->caps.mc_small && which == 7) {          // the Monte-Carlo latency kernel's launch number (upper bits of its granule tags)
         APE_DBG_TRY(hipSetDevice(m->dims.device));
         APE_DBG_TRY(hipDeviceSynchronize());
         APE_DBG_TRY(hipMemcpy(m->gxm, &value, sizeof(value), hipMemcpyHostToDevice));
         return APE_OK;
     }
-    if (m && m->lv16_ok && which == 8) {         // the level-synchronous kernel's launch number (upper bits of its granule tags)
+    if (m && m->caps.lv16 && which == 8) {         // the level-synchronous kernel's launch number (upper bits of its granule tags)
         APE_DBG_TRY(hipSetDevice(m->dims.device));
         APE_DBG_TRY(hipDeviceSynchronize());
         APE_DBG_TRY(hipMemcpy(m->gx16, &value, sizeof(value), hipMemcpyHostToDevice));
         return APE_OK;
     }
-    if (!m || !m->cluster_ok || which < 0 || which > 3) return APE_ERR_INVALID_ARG;
+    if (!m || !m->caps.cluster_ok || which < 0 || which > 3) return APE_ERR_INVALID_ARG;
     APE_DBG_TRY(hipSetDevice(m->dims.device));
     APE_DBG_TRY(hipDeviceSynchronize());
-    unsigned* status = m->xflags + m->xflag_bytes / sizeof(unsigned);
+    const CtlWords cw = ctl_words(m);
     // (3: the latency kernel's launch number, the upper bits of its granule tags -- to stage the 20-bit wrap)
-    unsigned* word = which == 0 ? status : (which == 1 ? status - 4 : which == 2 ? status - 3 : reinterpret_cast<unsigned*>(m->hxs));
+    unsigned* word = which == 0 ? cw.status : (which == 1 ? cw.ticket : which == 2 ? cw.done : reinterpret_cast<unsigned*>(m->hxs));
     APE_DBG_TRY(hipMemcpy(word, &value, sizeof(value), hipMemcpyHostToDevice));
     return APE_OK;
 }
@@ -49,8 +49,8 @@ int ape_debug_poke(ape_model_t* m, int which, unsigned value) {
 // shrink the chunk of sample rows a Monte-Carlo bank's weight-stationary route handles per launch (a multiple of 32, never
 // above what the bank's workspaces were sized for): lets a test run the multi-chunk path at a size that otherwise fits one
 int ape_debug_set_chunk_rows(ape_streams_t* b, int rows) {
-    if (!b || !(b->up32 || b->up128) || rows < 32 || rows % 32 != 0 || rows > b->chunk_rows) return APE_ERR_INVALID_ARG;
-    b->chunk_rows = rows;
+    if (!b || !(b->plan.route == BANK_UPPER32 || b->plan.route == BANK_UPPER128) || rows < 32 || rows % 32 != 0 || rows > b->plan.chunk_rows) return APE_ERR_INVALID_ARG;
+    b->plan.chunk_rows = rows;
     return APE_OK;
 }
 
@@ -77,7 +77,7 @@ int ape_debug_bank_targets(ape_streams_t* b, float* out_host) {
 int ape_debug_bank_buffer(ape_streams_t* b, int which, void* out_host, size_t bytes, size_t* copied) {
     if (!b || !out_host || which < 0 || which > 3) return APE_ERR_INVALID_ARG;
     const int I = b->model->dims.input_size;
-    const size_t tiles = (size_t)(b->S + 31) / 32, ctiles = (size_t)(b->chunk_rows + 31) / 32;
+    const size_t tiles = (size_t)(b->S + 31) / 32, ctiles = (size_t)(b->plan.chunk_rows + 31) / 32;
     const void* src = which == 0 ? (const void*)b->xring : which == 1 ? (const void*)b->xfrag0 : which == 2 ? (const void*)b->hfrag : (const void*)b->xfrag;
     size_t have = which == 0 ? (size_t)b->S * b->n_mc * b->T * I * sizeof(float) : which == 1 ? tiles * b->T * 4096 : which == 2 ? tiles * b->T * 32768 : ctiles * b->T * 32768;
     if (!src) return APE_ERR_NOT_READY;

@@ -6,6 +6,7 @@
 
 #include "../../include/ape_hip.h"
 #include "ape_internal.h"
+#include "ape_plan.h"
 #include "body_table.h"
 
 struct ape_streams;
@@ -35,6 +36,7 @@ struct ape_model {
     void* slab = nullptr;          // the one device allocation every fixed-size buffer below points into
     size_t slab_bytes = 0;
     int n_cus = 0;                 // hipDeviceProp_t::multiProcessorCount of the model's device (256 on a whole MI355X)
+    ApeCaps caps;                  // what this model can run there (ape_plan.h): ape_caps(dims, n_cus) minus what failed to set up
     int KX = 0;                    // LSTM layer-0 input width, padded to the kernels' k-blocking
     int lstm_in = 0;               // LSTM layer-0 input width (input_size; 256 behind ImuPoseLSTM's input layer)
     int KXpre = 0;                 // ImuPoseLSTM: padded width of the input layer's input
@@ -52,7 +54,6 @@ struct ape_model {
     float* y_ws = nullptr;         // [cap, O] intermediate of ape_infer
     int y_cap = 0;
     // weight-stationary cluster kernel (lstm_cluster.hip)
-    bool cluster_ok = false;
     int kernel_choice = APE_KERNEL_AUTO;
     float* wcl[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};
     void* wcl16[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};   // binary16 fragments of the fp16 variant
@@ -60,7 +61,6 @@ struct ape_model {
     unsigned* wcl32s[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};  // ... the same image with the recurrent columns as f16 hi / lo (lstm_cluster32.hip)
     float c32_scale[APE_MAX_LAYERS] = {1.0f, 1.0f, 1.0f};          // ... 2^S per layer (pack_c32_split)
     float c32_descale[APE_MAX_LAYERS] = {1.0f, 1.0f, 1.0f};
-    bool c32_split = true;          // the loaded weights took the split (finite, scale in range); else the model stays off lstm_cluster32.hip
     float* wcls[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};   // the latency kernel's H/8-member form (two units per wave)
     char* hxs = nullptr;             // latency kernel: [256 B: launch number][granules {h, tag}: layer, parity, 4 rows, H units]
     size_t hxs_bytes = 0;
@@ -68,24 +68,15 @@ struct ape_model {
     float* wmc16[APE_MAX_LAYERS] = {nullptr, nullptr, nullptr};  // ... and as 16 x 16 x 4 fragments (16-row clusters: wave = column tile x K half)
     char* gxm = nullptr;             // ... [256 B: launch number][8 clusters of granules]
     size_t gxm_cluster_bytes = 0;
-    bool mcs_ok = false;             // lstm_mc_small.hip covers this model on this device
     int small_uw = 4;                // hidden units per wave of the latency kernel: 2 when one XCD holds H/8 members
-    bool c32_ok = false;            // lstm_cluster32.hip covers this model (2 x 256) on this device
     bool c32_on = true;             // ... and is not switched off (APE_KERNEL_CLUSTER_GEN1)
     bool gen1_classes = true;       // first-generation f32 kernel: XCD-class cluster formation where the grid allows it
-    bool c16_ok = false;            // lstm_cluster16.hip covers this model (3 x 128) on this device (switched with c32_on)
-    bool lv16_ok = false;           // ... and lstm_level16.hip its short windows (switched with c32_on too)
-    char* gx16 = nullptr;           // ... [256 B: launch number][granules {h, tag}: cluster, row tile, parity, layer]
+    char* gx16 = nullptr;           // lstm_level16.hip: [256 B: launch number][granules {h, tag}: cluster, row tile, parity, layer]
     size_t gx16_bytes = 0;
     int precision = APE_PRECISION_F32;
-    bool wide_cluster = false;      // ImuPoseLSTM: the f32 first-generation cluster kernel with a 256-wide layer-0 input, nothing else
     bool small_batch_path = true;   // B <= 4 on the VALU/shuffle variant of the cluster kernel
     bool f16_v2 = true;             // fp16 precision: batches > 256 rows on the row-set-pipelined kernel (lstm_cluster_f16v2.hip)
-    bool upper_ok = false;          // layers 1.. can run on their own over a shared layer-0 sequence (stream bank, MC mode)
-    bool up32_ok = false;           // ... and on the weight-stationary upper-layer kernel (lstm_upper32.hip: 2 x 256 models)
-    bool up128_ok = false;          // ... or on lstm_upper128.hip (the 3 x 128 model: layers 1 and 2 in four-member clusters)
-    bool split32_ok = false;        // ImuPoseLSTM: the 2 x 256 LSTM behind the input layer, one layer per launch on lstm_upper32.hip's persistent clusters
-    float* zfrag_ws = nullptr;      // ... its workspaces: the input layer's activations in fragment order [tiles][T][32 KB],
+    float* zfrag_ws = nullptr;      // ImuPoseLSTM on lstm_upper32.hip (caps.split32), its workspaces: the input layer's activations in fragment order [tiles][T][32 KB],
     float* hfrag_ws = nullptr;      //     layer 0's output sequence (same shape, layer 1's input),
     float* ypart_ws = nullptr;      //     head partial sums [tiles * 32][8][16]
     size_t split_tiles_cap = 0, split_steps_cap = 0;      // tiles x steps the first two hold
@@ -115,6 +106,13 @@ struct ape_model {
     ape_model_stats_t stats_counts{};
 };
 
+// the control words behind the flag block: the only place that knows where they sit
+struct CtlWords { unsigned *status, *ticket, *done; };
+inline CtlWords ctl_words(const ape_model* m) {
+    unsigned* status = m->xflags + m->xflag_bytes / sizeof(unsigned);
+    return {status, status - 4, status - 3};
+}
+
 #define APE_SUBSET_STAGES 8      // pinned descriptor slots of a bank's subset frames
 
 struct ape_streams {
@@ -122,7 +120,6 @@ struct ape_streams {
     int S = 0, T = 0, smooth = 0;
     int n_mc = 1;                // Monte-Carlo samples per stream and step
     bool mc = false;             // dropout on (ape_streams_set_mc was called)
-    bool shared_l0 = false;      // MC mode with layer 0 computed once per stream (two launches per step)
     float dropout_p = 0.0f;
     unsigned long long seed = 0, mc_calls = 0;
     float* xring = nullptr;      // [S,n_mc,T,I] feature rows, slot = frame mod T (a stream's n_mc windows are copies)
@@ -132,12 +129,10 @@ struct ape_streams {
     unsigned* post_cnt = nullptr; //   nullptr where every stream keeps a workgroup of its own (many streams, or stacks of <= 64 rows)
     int last_post_form = -1;     // ape_streams_last_post_form: -1 no frame yet, 0 wide, 1 one workgroup per stream, c > 1 split over c
     double* post_spread = nullptr; // ... and, in the same allocation, [S][chunks][72] partial spread sums (APE_FLAG_SPREAD frames)
-    // shared-layer-0 route on the weight-stationary upper-layer kernel (lstm_upper32.hip): the sample rows go through it in
-    // chunks of `chunk_rows` (a multiple of 32), each expand -> LSTM -> head reduce over the two workspaces below
-    bool up32 = false;
-    bool up128 = false;          // the same route for the 3 x 128 model (lstm_upper128.hip; launch A stays on the batch-tile kernel)
+    // what ape_streams_set_mc planned (ape_plan.h) -- the weight-stationary routes (lstm_upper32.hip / lstm_upper128.hip) only once their
+    // workspaces below exist: the sample rows go through them in chunks of plan.chunk_rows (a multiple of 32), each expand -> LSTM -> head reduce
+    BankPlan plan;
     unsigned* maskbits = nullptr;   // ... keep bits of layer 1's outputs [chunk tiles][T][128]
-    int chunk_rows = 0;
     float* xfrag = nullptr;      // [chunk tiles][T][32 KB] masked layer-0 output in MFMA fragment order
     float* ypart = nullptr;      // [chunk rows][8][16] head partial sums
     float* xfrag0 = nullptr;     // [S / 32][T][4 KB] layer 0's input tiles, fragment order
