@@ -25,6 +25,11 @@ What is restated:
 
 Every random draw is an explicit argument (``noise``), so that the HIP path can be compared with injected draws bit for
 tolerance; ``draw_noise`` makes them from a numpy generator for the statistical tests.
+
+Precision.  ``kalman_forward`` and everything below it take ``dtype`` (default float32: the pinned checker, bit for bit what it
+was before the argument existed).  ``dtype=np.float64`` is the REFERENCE of tests/test_kalman_numerics_*.py; the float32
+evaluation with ``inverse="gj"`` (the kernel's own Gauss-Jordan, in numpy) is their yardstick: its distance from the float64
+reference is what float32 arithmetic of this algorithm costs, and the kernels are held to a small multiple of it.
 """
 from __future__ import annotations
 
@@ -67,26 +72,26 @@ def make_state_dict(win_size: int = 10, seed: int = 0) -> Dict[str, np.ndarray]:
     return sd
 
 
-def softplus(x):
-    return np.log1p(np.exp(x.astype(F))).astype(F)
+def softplus(x, dtype=F):
+    return np.log1p(np.exp(x.astype(dtype))).astype(dtype)
 
 
-def leaky_relu(x, slope=0.01):          # torch.nn.functional.leaky_relu default negative_slope
-    return np.where(x >= 0, x, F(slope) * x).astype(F)
+def leaky_relu(x, slope=0.01, dtype=F):          # torch.nn.functional.leaky_relu default negative_slope
+    return np.where(x >= 0, x, dtype(slope) * x).astype(dtype)
 
 
-def linear(x, w, b):
-    return (x.astype(F) @ w.T.astype(F) + b.astype(F)).astype(F)
+def linear(x, w, b, dtype=F):
+    return (x.astype(dtype) @ w.T.astype(dtype) + b.astype(dtype)).astype(dtype)
 
 
-def linear_flipout(x, sd, name, nz):
+def linear_flipout(x, sd, name, nz, dtype=F):
     """bayesian-torch LinearFlipout.forward (see the module docstring); nz = {"eps_w" [N,K], "eps_b" [N], "sign_in" [R,K],
     "sign_out" [R,N]}"""
-    out = linear(x, sd[name + ".mu_weight"], sd[name + ".mu_bias"])
-    dw = (softplus(sd[name + ".rho_weight"]) * nz["eps_w"].astype(F)).astype(F)
-    db = (softplus(sd[name + ".rho_bias"]) * nz["eps_b"].astype(F)).astype(F)
-    pert = linear((x * nz["sign_in"]).astype(F), dw, db)
-    return (out + pert * nz["sign_out"]).astype(F)
+    out = linear(x, sd[name + ".mu_weight"], sd[name + ".mu_bias"], dtype)
+    dw = (softplus(sd[name + ".rho_weight"], dtype) * nz["eps_w"].astype(dtype)).astype(dtype)
+    db = (softplus(sd[name + ".rho_bias"], dtype) * nz["eps_b"].astype(dtype)).astype(dtype)
+    pert = linear((x * nz["sign_in"]).astype(dtype), dw, db, dtype)
+    return (out + pert * nz["sign_out"]).astype(dtype)
 
 
 def draw_noise(rng, win_size: int, rows: int) -> Dict[str, Dict[str, np.ndarray]]:
@@ -100,59 +105,92 @@ def draw_noise(rng, win_size: int, rows: int) -> Dict[str, Dict[str, np.ndarray]
     return nz
 
 
-def process_model(sd, x, nz):
+def process_model(sd, x, nz, dtype=F):
     """kalman_models.py:37-50: x [bs, E, W, 14] -> [bs, E, 14]"""
     bs, E = x.shape[0], x.shape[1]
-    h = x.reshape(bs * E, -1).astype(F)
-    h = leaky_relu(linear_flipout(h, sd, "process_model.bayes1", nz["process_model.bayes1"]))
-    h = leaky_relu(linear_flipout(h, sd, "process_model.bayes3", nz["process_model.bayes3"]))
-    h = linear(h, sd["process_model.bayes_m2.weight"], sd["process_model.bayes_m2.bias"])
+    h = x.reshape(bs * E, -1).astype(dtype)
+    h = leaky_relu(linear_flipout(h, sd, "process_model.bayes1", nz["process_model.bayes1"], dtype), dtype=dtype)
+    h = leaky_relu(linear_flipout(h, sd, "process_model.bayes3", nz["process_model.bayes3"], dtype), dtype=dtype)
+    h = linear(h, sd["process_model.bayes_m2.weight"], sd["process_model.bayes_m2.bias"], dtype)
     return h.reshape(bs, E, DIM_X)
 
 
-def sensor_model(sd, x, E, nz):
+def sensor_model(sd, x, E, nz, dtype=F):
     """kalman_models.py:117-136: x [bs, W, 1, 22] -> (ensemble [bs, E, 14], mean [bs, 1, 14]).  NB the reference's
     ``x.repeat(E,1,1,1)`` + reshape to (bs*E, ...) orders the rows member-major (row = e*bs + b) while its final reshape
     reads them batch-major; for the deployed batch size 1 the two coincide.  Restated batch-major (row = b*E + e reads stream
     b), which is the reference for bs = 1 and the only consistent reading for a bank of streams."""
     bs = x.shape[0]
-    h = np.repeat(x.reshape(bs, -1), E, axis=0).astype(F)
-    h = leaky_relu(linear(h, sd["sensor_model.fc2.weight"], sd["sensor_model.fc2.bias"]))
-    h = leaky_relu(linear_flipout(h, sd, "sensor_model.fc3", nz["sensor_model.fc3"]))
-    h = leaky_relu(linear_flipout(h, sd, "sensor_model.fc5", nz["sensor_model.fc5"]))
-    h = linear_flipout(h, sd, "sensor_model.fc6", nz["sensor_model.fc6"])
+    h = np.repeat(x.reshape(bs, -1), E, axis=0).astype(dtype)
+    h = leaky_relu(linear(h, sd["sensor_model.fc2.weight"], sd["sensor_model.fc2.bias"], dtype), dtype=dtype)
+    h = leaky_relu(linear_flipout(h, sd, "sensor_model.fc3", nz["sensor_model.fc3"], dtype), dtype=dtype)
+    h = leaky_relu(linear_flipout(h, sd, "sensor_model.fc5", nz["sensor_model.fc5"], dtype), dtype=dtype)
+    h = linear_flipout(h, sd, "sensor_model.fc6", nz["sensor_model.fc6"], dtype)
     ens = h.reshape(bs, E, DIM_X)
-    return ens, ens.mean(axis=1, dtype=F)[:, None, :].astype(F)
+    return ens, ens.mean(axis=1, dtype=dtype)[:, None, :].astype(dtype)
 
 
-def observation_noise(sd, z):
+def observation_noise(sd, z, dtype=F):
     """kalman_models.py:73-80: z [bs, 1, 14] -> diagonal of R [bs, 14] (the reference returns diag_embed of it)"""
-    h = np.maximum(linear(z.reshape(-1, DIM_X), sd["observation_noise.fc1.weight"], sd["observation_noise.fc1.bias"]), 0).astype(F)
-    h = linear(h, sd["observation_noise.fc2.weight"], sd["observation_noise.fc2.bias"])
-    return (np.square(h + F(1e-3)) + F(0.038729833)).astype(F)
+    h = np.maximum(linear(z.reshape(-1, DIM_X), sd["observation_noise.fc1.weight"], sd["observation_noise.fc1.bias"], dtype), 0).astype(dtype)
+    h = linear(h, sd["observation_noise.fc2.weight"], sd["observation_noise.fc2.bias"], dtype)
+    return (np.square(h + dtype(1e-3)) + dtype(0.038729833)).astype(dtype)
 
 
-def kalman_forward(sd, raw_obs, state_prev, nz):
+def gauss_jordan_inverse(a, dtype=F):
+    """the inverse as ``kf_update_kernel`` computes it (csrc/kalman.hip), in ``dtype``: on the augmented [n, 2n] matrix, per column
+    pivot on the largest |entry| at or below the diagonal (the first of equals), swap that row into place, divide the pivot row by
+    the pivot, eliminate the column from every other row.  -> (inverse [n,n], number of row swaps)"""
+    n = a.shape[0]
+    m = np.concatenate([a.astype(dtype), np.eye(n, dtype=dtype)], axis=1)
+    swaps = 0
+    for c in range(n):
+        piv = c + int(np.argmax(np.abs(m[c:, c])))
+        if piv != c:
+            m[[c, piv]] = m[[piv, c]]
+            swaps += 1
+        m[c] = m[c] / m[c, c]
+        others = np.arange(n) != c
+        m[others] = m[others] - np.outer(m[others, c], m[c])
+    return m[:, n:].copy(), swaps
+
+
+def kalman_forward(sd, raw_obs, state_prev, nz, dtype=F, inverse="inv64", info=None):
     """kalman_models.py:175-220 for batch size 1 per stream (``A = state_pred - state_m`` broadcasts [bs,E,14] - [bs,14],
     which only is the ensemble anomaly for bs = 1 -- the deployed case, watch_phone_pocket_kalman.py:135; a bank of
     streams is therefore restated as independent bs = 1 updates over a shared flipout draw).
     raw_obs [S, W, 1, 22], state_prev [S, E, W, 14] -> (state_corrected [S,E,14], m_state_corrected [S,1,14],
-    m_state_pred [S,1,14], z [S,1,14], ensemble_z [S,E,14])"""
+    m_state_pred [S,1,14], z [S,1,14], ensemble_z [S,E,14])
+    ``dtype``: the arithmetic of every step (float32: the pinned checker; float64: the reference the numerics tests hold the
+    kernels to).  ``inverse``: "inv64" = LAPACK in float64 whatever the dtype, "gj" = ``gauss_jordan_inverse`` in ``dtype``.
+    ``info``: a dict that receives "swaps" (row swaps of "gj", summed over the streams; 0 for "inv64") and "cond" (the largest
+    2-norm condition number of an innovation matrix)."""
+    if inverse not in ("inv64", "gj"):
+        raise ValueError(f"inverse must be 'inv64' or 'gj', got {inverse!r}")
     S, E = state_prev.shape[0], state_prev.shape[1]
-    state_pred = process_model(sd, state_prev, nz)                                     # :181
-    state_m = state_pred.mean(axis=1, dtype=F)                                         # :183
-    ens_z, z = sensor_model(sd, raw_obs, E, nz)                                        # :194
-    r_diag = observation_noise(sd, z)                                                  # :198
+    state_pred = process_model(sd, state_prev, nz, dtype)                              # :181
+    state_m = state_pred.mean(axis=1, dtype=dtype)                                     # :183
+    ens_z, z = sensor_model(sd, raw_obs, E, nz, dtype)                                 # :194
+    r_diag = observation_noise(sd, z, dtype)                                           # :198
     corrected = np.empty_like(state_pred)
+    swaps, cond = 0, 0.0
     for s in range(S):
-        A = (state_pred[s] - state_m[s]).astype(F)                                     # [E,14]  :184
-        P = (F(1.0 / (E - 1)) * (A.T @ A)).astype(F)                                   # :200, :203
-        innovation = (P + np.diag(r_diag[s])).astype(F)
-        inv = np.linalg.inv(innovation.astype(np.float64)).astype(F)                   # :201 (float64 here: the checker)
-        K = (P @ inv).astype(F)                                                        # :202-204
-        gain = (K @ (ens_z[s].T - state_pred[s].T)).T.astype(F)                        # :206
+        A = (state_pred[s] - state_m[s]).astype(dtype)                                 # [E,14]  :184
+        P = (dtype(1.0 / (E - 1)) * (A.T @ A)).astype(dtype)                           # :200, :203
+        innovation = (P + np.diag(r_diag[s])).astype(dtype)
+        if inverse == "gj":
+            inv, n_swaps = gauss_jordan_inverse(innovation, dtype)
+            swaps += n_swaps
+        else:
+            inv = np.linalg.inv(innovation.astype(np.float64)).astype(dtype)           # :201 (float64 here: the checker)
+        if info is not None:
+            cond = max(cond, float(np.linalg.cond(innovation.astype(np.float64))))
+        K = (P @ inv).astype(dtype)                                                    # :202-204
+        gain = (K @ (ens_z[s].T - state_pred[s].T)).T.astype(dtype)                    # :206
         corrected[s] = state_pred[s] + gain                                            # :208
-    return (corrected, corrected.mean(axis=1, dtype=F)[:, None, :], state_m[:, None, :], z, ens_z)
+    if info is not None:
+        info["swaps"], info["cond"] = swaps, cond
+    return (corrected, corrected.mean(axis=1, dtype=dtype)[:, None, :], state_m[:, None, :], z, ens_z)
 
 
 def format_state(state, init_noise):

@@ -3,9 +3,11 @@
 published LinearFlipout algorithm but nothing of the reference could be run for this path (see the oracle's header); these
 tests therefore prove HIP == restatement, not HIP == reference.
 
-Tolerances (float32 path, stated per test): layer outputs and the corrected ensemble within 2e-4 absolute of the oracle on
-injected draws (the oracle inverts the 14 x 14 innovation in float64, the kernel by float32 Gauss-Jordan with partial
-pivoting); device-side draws (Philox) only statistically."""
+Tolerances (float32 path, stated per test): on injected draws every output of a forward within ``max(1e-6, 4 e_ref)`` of the
+oracle's float64 evaluation, ``e_ref`` being the distance of the oracle's own float32 evaluation (with the kernel's algorithm
+for the inverse, float32 Gauss-Jordan with partial pivoting) from that reference on the same inputs -- the rule, the shapes at
+the kernels' edges and the hostile regimes are in tests/test_kalman_numerics_gpu.py; chained frames (feedback of the state)
+keep their absolute bounds; device-side draws (Philox) only statistically."""
 import ctypes as C
 
 import numpy as np
@@ -14,8 +16,6 @@ import torch
 
 from oracle import kalman_oracle as ko
 from tests import mc_check
-
-TOL = 2e-4
 
 
 def pack_noise(nz, order=ko.FLIPOUT_LAYERS):
@@ -92,7 +92,9 @@ def make_model(E, W, seed=0):
 @pytest.mark.gpu
 @pytest.mark.parametrize("S,E,W", [(1, 32, 10), (1, 48, 10), (3, 32, 10), (2, 16, 4), (1, 40, 6)])
 def test_forward_injected_draws(S, E, W):
-    """every output of KalmanSmartwatchModel.forward on injected draws, within 2e-4 of the oracle"""
+    """every output of KalmanSmartwatchModel.forward on injected draws against the oracle's float64 evaluation, within
+    max(1e-6, 4 e_ref) of it (e_ref: the oracle's float32 evaluation against the same reference; tests/kalman_cases.py)"""
+    from tests import kalman_cases as kc
     rng = np.random.default_rng(10 * S + E)
     m, sd = make_model(E, W, 4)
     for rep in range(2):
@@ -101,10 +103,12 @@ def test_forward_injected_draws(S, E, W):
         blob = pack_noise(nz)
         assert blob.size == m.noise_floats(S)
         got = [t.cpu().numpy() for t in m.forward(torch.from_numpy(raw), torch.from_numpy(state), noise=torch.from_numpy(blob))]
-        want = ko.kalman_forward(sd, raw, state, nz)
-        for name, g, w in zip(("state_corrected", "m_state_corrected", "m_state_pred", "z", "ensemble_z"), got, want):
+        want = ko.kalman_forward(sd, raw, state, nz, dtype=np.float64, inverse="gj")
+        e_ref = kc.errors(ko.kalman_forward(sd, raw, state, nz, dtype=np.float32, inverse="gj"), want)
+        for name, g, w, e in zip(kc.OUTPUTS, got, want, e_ref):
             assert g.shape == w.shape, name
-            assert np.abs(g - w).max() < TOL, (name, S, E, W, float(np.abs(g - w).max()))
+            err = float(np.abs(g - w).max())
+            assert err <= kc.budget(e), (name, S, E, W, err, kc.budget(e))
     m.check()
 
 
