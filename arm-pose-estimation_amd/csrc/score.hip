@@ -1,4 +1,5 @@
-// Scoring replayed poses against ground truth (ape_score_rows; the reference has no counterpart).
+// Scoring replayed poses against ground truth (ape_score_rows; over a sweep of time lags: ape_score_lags, 4.32, further
+// down; the reference has no counterpart).
 //
 // ape_score_kernel      one lane per frame: the truth pose (est columns as given, or NN targets through the float64 forward kinematics of
 //                       fk_device.h, its quaternions refined to the reference's eigenvector: truth_six_drr_to_quat), the five errors of
@@ -334,6 +335,274 @@ __global__ __launch_bounds__(SC_BLOCK) void ape_score_acc_kernel(const double* _
     }
 }
 
+// ---- the lag sweep (ape_score_lags) --------------------------------------------------------------------------------------
+// ape_score_lags_kernel      256 frames per workgroup and one lane per message frame, as above.  The workgroup first converts every truth
+//                            row its frames can be paired with -- its own 256 and the halo its recordings' lags reach, at most 512 -- to a
+//                            pose (hand, elbow, three quaternions, usable flag) exactly once and keeps the poses in LDS; a lane then holds
+//                            its message and spread row in registers and walks the L lags, taking the pose of row f - l from LDS.  One
+//                            partial record per (workgroup, recording, lag), reduced as above.
+// ape_score_lags_acc_kernel  one workgroup per (recording, lag): ape_score_acc_kernel's order over that lag's partial records.
+// For the sweep {0} without offsets the window is the workgroup's own 256 rows, the support is `f - start >= skip`, and every value and
+// every sum is formed by the operations of ape_score_kernel in their order: the bits are those of ape_score_rows.
+constexpr int SL_POSE = 19;                             // 18 pose values + the usable flag; odd: no bank conflicts
+constexpr int SL_WINDOW = SC_BLOCK + 2 * APE_SCORE_MAX_LAG;
+
+struct LagParams {
+    ScoreParams s;                                      // score [F, L, 7]; part [(workgroups + R), L, 25], pair (b, r) at rows (b + r) * L ..
+    const int* offs;                                    // [R] the recordings' offsets o_r
+    int lag_min, L;
+    int back, fwd;                                      // how far below / above its own rows a workgroup's truth window reaches:
+};                                                      // max(0, max_r(o_r + lag_max)) and max(0, -min_r(o_r + lag_min)), each <= 128
+
+__device__ __forceinline__ int find_rec(const int* starts, int R, long long f) {      // the last start <= f
+    int lo = 0, hi = R - 1;
+    while (lo < hi) {
+        const int mid = (lo + hi + 1) >> 1;
+        if ((long long)starts[mid] <= f) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+// one truth row -> pose[0:18] = hand, elbow, lower-arm, upper-arm and hips quaternion, pose[18] = 1.0 iff every value used is finite.
+// (The statements of ape_score_kernel's truth section, which keeps its own copy so that its code stays as it was.)
+template <int KIND>
+__device__ __forceinline__ void truth_pose(const double* t, int tw, int layout, const double* body, double* pose) {
+    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
+    Vec3 t_hand, t_elbow;
+    Quat t_lq, t_uq, t_hq{1.0, 0.0, 0.0, 0.0};
+    bool ok = true;
+    if constexpr (KIND == APE_TRUTH_TARGETS) {
+#pragma unroll
+        for (int c = 0; c < 20; ++c)
+            if (c < tw) ok = ok && fin(t[c]);
+        const Vec3 larm_vec{body[0], body[1], body[2]}, uarm_vec{body[3], body[4], body[5]}, uarm_orig{body[6], body[7], body[8]};
+        if (layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS) {
+            t_lq = truth_six_drr_to_quat(t + 3); t_uq = truth_six_drr_to_quat(t + 12); t_hq = hips_quat(t[18], t[19]);
+            t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[9], t[10], t[11]};
+        } else {
+            t_lq = truth_six_drr_to_quat(t); t_uq = truth_six_drr_to_quat(t + 6);
+            Vec3 uo = uarm_orig;
+            if (hips) { t_hq = hips_quat(t[12], t[13]); uo = qrot(t_hq, uarm_orig); }
+            const Vec3 r1 = qrot(t_uq, uarm_vec);
+            t_elbow = Vec3{r1.x + uo.x, r1.y + uo.y, r1.z + uo.z};
+            const Vec3 r2 = qrot(t_lq, larm_vec);
+            t_hand = Vec3{r2.x + t_elbow.x, r2.y + t_elbow.y, r2.z + t_elbow.z};
+        }
+    } else {
+        const int ql = hips ? 9 : 6, qu = hips ? 13 : 10;
+        t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[3], t[4], t[5]};
+        t_lq = Quat{t[ql], t[ql + 1], t[ql + 2], t[ql + 3]};
+        t_uq = Quat{t[qu], t[qu + 1], t[qu + 2], t[qu + 3]};
+        if (hips) t_hq = Quat{t[17], t[18], t[19], t[20]};
+    }
+    ok = ok && fin(t_hand.x) && fin(t_hand.y) && fin(t_hand.z) && fin(t_elbow.x) && fin(t_elbow.y) && fin(t_elbow.z) &&
+         fin(t_lq.w) && fin(t_lq.x) && fin(t_lq.y) && fin(t_lq.z) && fin(t_uq.w) && fin(t_uq.x) && fin(t_uq.y) && fin(t_uq.z) &&
+         fin(t_hq.w) && fin(t_hq.x) && fin(t_hq.y) && fin(t_hq.z);
+    pose[0] = t_hand.x; pose[1] = t_hand.y; pose[2] = t_hand.z; pose[3] = t_elbow.x; pose[4] = t_elbow.y; pose[5] = t_elbow.z;
+    pose[6] = t_lq.w; pose[7] = t_lq.x; pose[8] = t_lq.y; pose[9] = t_lq.z;
+    pose[10] = t_uq.w; pose[11] = t_uq.x; pose[12] = t_uq.y; pose[13] = t_uq.z;
+    pose[14] = t_hq.w; pose[15] = t_hq.x; pose[16] = t_hq.y; pose[17] = t_hq.z;
+    pose[18] = ok ? 1.0 : 0.0;
+}
+
+template <typename TM, typename TT, int KIND, bool SPR>
+__global__ __launch_bounds__(SC_BLOCK) void ape_score_lags_kernel(const LagParams q) {
+    __shared__ double stage[SC_WAVES][64 * SC_LDS_ROW];
+    __shared__ double poses[SL_WINDOW * SL_POSE];
+    __shared__ double wfirst[2][SC_WAVES][ACC];         // two buffers: one barrier per lag
+    __shared__ int wrec[SC_WAVES][2];
+    const ScoreParams& p = q.s;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long tile0 = (long long)blockIdx.x * SC_BLOCK;
+    const long long row0 = tile0 + wave * 64;
+    const long long f = row0 + lane;
+    const bool valid = f < p.F;
+    const long long left = (long long)p.F - row0;
+    const int nrows = left >= 64 ? 64 : (left > 0 ? (int)left : 0);
+    double* lds = stage[wave];
+
+    // the frame's recording [start, end) and offset; lanes past F form a recording of their own
+    int rec = p.R, start = 0, end = 0, off = 0;
+    if (valid) {
+        rec = find_rec(p.starts, p.R, f);
+        start = p.starts[rec];
+        end = rec + 1 < p.R ? p.starts[rec + 1] : p.F;
+        off = q.offs[rec];
+    }
+
+    // ---- truth poses of the window [wlo, whi), 256 rows a round, each row converted once with its own recording's body ----
+    const long long wlo = tile0 - q.back > 0 ? tile0 - q.back : 0;
+    const long long whi = tile0 + SC_BLOCK + q.fwd < (long long)p.F ? tile0 + SC_BLOCK + q.fwd : (long long)p.F;
+    const int tw = p.truth_w, tls = tw | 1;
+    for (long long base = wlo; base < whi; base += SC_BLOCK) {                         // (uniform; at most twice)
+        const long long r0 = base + wave * 64, lw = whi - r0;
+        const int nr = lw >= 64 ? 64 : (lw > 0 ? (int)lw : 0);
+        if (nr > 0) stage_rows(lds, static_cast<const TT*>(p.truth), (long long)tw, tw, tls, r0, nr, lane);
+        __syncthreads();
+        const bool tv = lane < nr;
+        double t[21];
+#pragma unroll
+        for (int c = 0; c < 21; ++c) t[c] = (tv && c < tw) ? lds[lane * tls + c] : 0.0;
+        __syncthreads();
+        if (tv) {
+            const long long tr = r0 + lane;
+            const int trec = (KIND == APE_TRUTH_TARGETS && p.n_bodies > 1) ? find_rec(p.starts, p.R, tr) : 0;
+            truth_pose<KIND>(t, tw, p.layout, p.bodies + 9 * (size_t)trec, poses + (size_t)(tr - wlo) * SL_POSE);
+        }
+    }
+
+    // ---- the message and its spread record, held in registers over the lags ----
+    const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
+    bool ok_m = valid;
+    if (nrows > 0) stage_rows(lds, static_cast<const TM*>(p.msg), p.msg_stride, 25, 25, row0, nrows, lane);
+    __syncthreads();                                    // (also: every pose is written)
+    double m[25];
+#pragma unroll
+    for (int c = 0; c < 25; ++c) { m[c] = valid ? lds[lane * 25 + c] : 0.0; ok_m = ok_m && fin(m[c]); }
+    __syncthreads();
+    double r18[18];
+    if constexpr (SPR) {
+        if (nrows > 0) stage_rows(lds, static_cast<const TM*>(p.spread), p.spread_stride, 21, 21, row0, nrows, lane);
+        __syncthreads();
+#pragma unroll
+        for (int c = 0; c < 18; ++c) r18[c] = valid ? lds[lane * 21 + c] : 0.0;
+        __syncthreads();
+    }
+    if (lane == 0) wrec[wave][0] = rec;
+    if (lane == 63) wrec[wave][1] = rec;                // (read behind the first barrier of the lag loop)
+
+    // the support: past the skipped frames, and paired at every lag of the sweep
+    const int l_lo = off + q.lag_min, l_hi = l_lo + q.L - 1;
+    const bool sup = valid && (f - start) >= (long long)p.skip && f - l_hi >= (long long)start && f - l_lo < (long long)end;
+
+    for (int j = 0; j < q.L; ++j) {                     // (uniform)
+        const long long tr = f - (l_lo + j);
+        const bool ex = valid && tr >= (long long)start && tr < (long long)end;        // the pair exists: tr is inside [wlo, whi)
+        const double* ps = poses + (ex ? (size_t)(tr - wlo) : 0) * SL_POSE;
+        double t[SL_POSE];
+#pragma unroll
+        for (int c = 0; c < SL_POSE; ++c) t[c] = ex ? ps[c] : 0.0;
+        const Vec3 t_hand{t[0], t[1], t[2]}, t_elbow{t[3], t[4], t[5]};
+        const Quat t_lq{t[6], t[7], t[8], t[9]}, t_uq{t[10], t[11], t[12], t[13]}, t_hq{t[14], t[15], t[16], t[17]};
+        const bool ok = ok_m && ex && t[18] != 0.0;
+        double s[APE_SCORE_WIDTH];
+        s[0] = dist3(m + 4, t_hand);
+        s[1] = dist3(m + 11, t_elbow);
+        s[2] = ang_err(m + 7, t_lq);
+        s[3] = ang_err(m + 14, t_uq);
+        s[4] = hips ? ang_err(m + 21, t_hq) : 0.0;
+        s[5] = NAN; s[6] = NAN;
+        if constexpr (SPR) {
+            s[5] = mahalanobis(r18, t_hand);
+            s[6] = mahalanobis(r18 + 9, t_elbow);
+        }
+        if (!ok) {
+#pragma unroll
+            for (int c = 0; c < APE_SCORE_WIDTH; ++c) s[c] = NAN;
+        }
+
+        // per-frame rows [f, j, 0:7]: through LDS, neighbouring lanes write neighbouring values of a frame's run of seven
+        if (p.score != nullptr) {
+#pragma unroll
+            for (int c = 0; c < APE_SCORE_WIDTH; ++c) lds[lane * APE_SCORE_WIDTH + c] = s[c];
+            __syncthreads();
+            const int total = nrows * APE_SCORE_WIDTH;
+#pragma unroll
+            for (int it = 0; it < APE_SCORE_WIDTH; ++it) {
+                const int idx = it * 64 + lane;
+                if (idx < total) {
+                    const int r = idx / APE_SCORE_WIDTH, c = idx - r * APE_SCORE_WIDTH;
+                    const size_t o = ((size_t)(row0 + r) * (size_t)q.L + (size_t)j) * APE_SCORE_WIDTH + c;
+                    if (p.score_f32) static_cast<float*>(p.score)[o] = (float)lds[idx];
+                    else static_cast<double*>(p.score)[o] = lds[idx];
+                }
+            }
+            __syncthreads();
+        }
+        if (p.part == nullptr) continue;                // (uniform)
+
+        const bool in = sup && ok;
+        double v[ACC];
+#pragma unroll
+        for (int c = 0; c < 5; ++c) {
+            const double e = in ? s[c] : 0.0;
+            v[3 * c] = e; v[3 * c + 1] = e * e; v[3 * c + 2] = e;
+        }
+        v[15] = in ? 1.0 : 0.0;
+        v[16] = (sup && !ok) ? 1.0 : 0.0;
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const double d2 = s[5 + k];
+            const bool has = in && fin(d2);
+            v[17 + 4 * k] = has ? 1.0 : 0.0;
+            v[18 + 4 * k] = has ? d2 : 0.0;
+            v[19 + 4 * k] = (has && d2 <= CHI2_3_Q50) ? 1.0 : 0.0;
+            v[20 + 4 * k] = (has && d2 <= CHI2_3_Q90) ? 1.0 : 0.0;
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {              // the segmented tree of ape_score_kernel
+            const int orec = __shfl_down(rec, o, 64);
+            const bool take = lane + o < 64 && orec == rec;
+            double w[ACC];
+#pragma unroll
+            for (int c = 0; c < ACC; ++c) w[c] = __shfl_down(v[c], o, 64);
+            if (take) acc_combine(v, w);
+        }
+        double (*wf)[ACC] = wfirst[j & 1];
+        if (lane == 0) {
+#pragma unroll
+            for (int c = 0; c < ACC; ++c) wf[wave][c] = v[c];
+        }
+        __syncthreads();
+        if (valid && (f == start || threadIdx.x == 0)) {
+            if (wrec[wave][1] == rec) {
+                for (int w = wave + 1; w < SC_WAVES; ++w) {
+                    if (wrec[w][0] != rec) break;
+                    acc_combine(v, wf[w]);
+                    if (wrec[w][1] != rec) break;
+                }
+            }
+            double* dst = p.part + (((size_t)blockIdx.x + (size_t)rec) * (size_t)q.L + (size_t)j) * ACC;
+#pragma unroll
+            for (int c = 0; c < ACC; ++c) dst[c] = v[c];
+        }
+    }
+}
+
+// workgroup (r, j): recording r at sweep index j, its pairs (b, r) at rows (b + r) * L + j, combined as ape_score_acc_kernel combines
+__global__ __launch_bounds__(SC_BLOCK) void ape_score_lags_acc_kernel(const double* __restrict__ part, const int* __restrict__ starts, int R, int F,
+                                                                      int L, double* __restrict__ acc) {
+    __shared__ double grp[SC_BLOCK / 32][32];
+    const int r = blockIdx.x, j = blockIdx.y, c = threadIdx.x & 31, g = threadIdx.x >> 5;
+    const int s = starts[r], e = (r + 1 < R ? starts[r + 1] : F) - 1;
+    const int b0 = s / SC_BLOCK, n = e / SC_BLOCK - b0 + 1;
+    const size_t step = (size_t)L * ACC;
+    const bool mx = is_max_col(c);
+    double a = 0.0;
+    if (c < ACC) {
+        const double* src = part + (((size_t)b0 + (size_t)r) * (size_t)L + (size_t)j) * ACC + c;
+        int i = g;
+        for (; i + 24 < n; i += 32) {
+            const double x0 = src[(size_t)i * step], x1 = src[(size_t)(i + 8) * step], x2 = src[(size_t)(i + 16) * step],
+                         x3 = src[(size_t)(i + 24) * step];
+            if (mx) a = fmax(fmax(fmax(fmax(a, x0), x1), x2), x3);
+            else a = (((a + x0) + x1) + x2) + x3;
+        }
+        for (; i < n; i += 8) {
+            const double x = src[(size_t)i * step];
+            a = mx ? fmax(a, x) : a + x;
+        }
+    }
+    grp[g][c] = a;
+    __syncthreads();
+    if (g == 0 && c < ACC) {
+        double o = grp[0][c];
+#pragma unroll
+        for (int k = 1; k < SC_BLOCK / 32; ++k) o = mx ? fmax(o, grp[k][c]) : o + grp[k][c];
+        acc[((size_t)r * (size_t)L + (size_t)j) * ACC + c] = o;
+    }
+}
+
 int sfail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
@@ -422,30 +691,53 @@ void launch_score_kind(const ScoreParams& p, int kind, unsigned blocks, hipStrea
     else launch_score<TM, TT, APE_TRUTH_EST>(p, blocks, st);
 }
 
+template <typename TM, typename TT, int KIND>
+void launch_lags(const LagParams& q, unsigned blocks, hipStream_t st) {
+    if (q.s.spread != nullptr) hipLaunchKernelGGL((ape_score_lags_kernel<TM, TT, KIND, true>), dim3(blocks), dim3(SC_BLOCK), 0, st, q);
+    else hipLaunchKernelGGL((ape_score_lags_kernel<TM, TT, KIND, false>), dim3(blocks), dim3(SC_BLOCK), 0, st, q);
+}
+
+template <typename TM, typename TT>
+void launch_lags_kind(const LagParams& q, int kind, unsigned blocks, hipStream_t st) {
+    if (kind == APE_TRUTH_TARGETS) launch_lags<TM, TT, APE_TRUTH_TARGETS>(q, blocks, st);
+    else launch_lags<TM, TT, APE_TRUTH_EST>(q, blocks, st);
+}
+
+// what ape_score_rows and ape_score_lags both refuse; `who` names the entry in the message
+int check_score_args(const char* who, int32_t layout, const void* msg_dev, int32_t msg_stride, const void* spread_dev, int32_t spread_stride,
+                     int32_t msg_dtype, const void* truth_dev, int32_t truth_kind, int32_t truth_dtype, int32_t F, const int32_t* seg_starts_host,
+                     int32_t R, int32_t skip, const double* bodies_host, int32_t n_bodies, const void* score_dev, int32_t score_dtype,
+                     const void* acc_dev) {
+    if (!msg_dev || !truth_dev || !seg_starts_host || !bodies_host) return sfail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (!score_dev && !acc_dev) return sfail(APE_ERR_INVALID_ARG, "%s: score_dev and acc_dev are both NULL", who);
+    if (layout != APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS && layout != APE_LAYOUT_ORI_CAL_LARM_UARM && layout != APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS)
+        return sfail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to score", who, layout);
+    if (truth_kind != APE_TRUTH_TARGETS && truth_kind != APE_TRUTH_EST) return sfail(APE_ERR_INVALID_ARG, "%s: unknown truth kind %d", who, truth_kind);
+    if ((msg_dtype != APE_F32 && msg_dtype != APE_F64) || (truth_dtype != APE_F32 && truth_dtype != APE_F64) ||
+        (score_dtype != APE_F32 && score_dtype != APE_F64))
+        return sfail(APE_ERR_INVALID_ARG, "%s: unknown dtype selector", who);
+    if (F < 1) return sfail(APE_ERR_INVALID_ARG, "%s: F=%d must be >= 1", who, F);
+    if (R < 1 || R > F) return sfail(APE_ERR_INVALID_ARG, "%s: %d recording starts for %d frames (1 <= R <= F)", who, R, F);
+    if (seg_starts_host[0] != 0) return sfail(APE_ERR_INVALID_ARG, "%s: seg_starts[0] = %d, must be 0", who, seg_starts_host[0]);
+    for (int i = 1; i < R; ++i)
+        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
+            return sfail(APE_ERR_INVALID_ARG, "%s: seg_starts[%d] = %d (strictly rising, below F = %d)", who, i, seg_starts_host[i], F);
+    if (msg_stride < 25) return sfail(APE_ERR_INVALID_ARG, "%s: msg_stride %d below 25", who, msg_stride);
+    if (spread_dev && spread_stride < APE_SPREAD_WIDTH) return sfail(APE_ERR_INVALID_ARG, "%s: spread_stride %d below %d", who, spread_stride, APE_SPREAD_WIDTH);
+    if (skip < 0) return sfail(APE_ERR_INVALID_ARG, "%s: skip %d is negative", who, skip);
+    if (n_bodies != 1 && n_bodies != R) return sfail(APE_ERR_INVALID_ARG, "%s: n_bodies %d is neither 1 nor R = %d", who, n_bodies, R);
+    return APE_OK;
+}
+
 }  // namespace
 
 int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, const void* spread_dev, int32_t spread_stride,
                    int32_t msg_dtype, const void* truth_dev, int32_t truth_kind, int32_t truth_dtype, int32_t F,
                    const int32_t* seg_starts_host, int32_t R, int32_t skip, const double* bodies_host, int32_t n_bodies,
                    void* score_dev, int32_t score_dtype, double* acc_dev, void* stream) {
-    if (!msg_dev || !truth_dev || !seg_starts_host || !bodies_host) return sfail(APE_ERR_INVALID_ARG, "score_rows: NULL argument");
-    if (!score_dev && !acc_dev) return sfail(APE_ERR_INVALID_ARG, "score_rows: score_dev and acc_dev are both NULL");
-    if (layout != APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS && layout != APE_LAYOUT_ORI_CAL_LARM_UARM && layout != APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS)
-        return sfail(APE_ERR_INVALID_ARG, "score_rows: layout %d has no pose to score", layout);
-    if (truth_kind != APE_TRUTH_TARGETS && truth_kind != APE_TRUTH_EST) return sfail(APE_ERR_INVALID_ARG, "score_rows: unknown truth kind %d", truth_kind);
-    if ((msg_dtype != APE_F32 && msg_dtype != APE_F64) || (truth_dtype != APE_F32 && truth_dtype != APE_F64) ||
-        (score_dtype != APE_F32 && score_dtype != APE_F64))
-        return sfail(APE_ERR_INVALID_ARG, "score_rows: unknown dtype selector");
-    if (F < 1) return sfail(APE_ERR_INVALID_ARG, "score_rows: F=%d must be >= 1", F);
-    if (R < 1 || R > F) return sfail(APE_ERR_INVALID_ARG, "score_rows: %d recording starts for %d frames (1 <= R <= F)", R, F);
-    if (seg_starts_host[0] != 0) return sfail(APE_ERR_INVALID_ARG, "score_rows: seg_starts[0] = %d, must be 0", seg_starts_host[0]);
-    for (int i = 1; i < R; ++i)
-        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
-            return sfail(APE_ERR_INVALID_ARG, "score_rows: seg_starts[%d] = %d (strictly rising, below F = %d)", i, seg_starts_host[i], F);
-    if (msg_stride < 25) return sfail(APE_ERR_INVALID_ARG, "score_rows: msg_stride %d below 25", msg_stride);
-    if (spread_dev && spread_stride < APE_SPREAD_WIDTH) return sfail(APE_ERR_INVALID_ARG, "score_rows: spread_stride %d below %d", spread_stride, APE_SPREAD_WIDTH);
-    if (skip < 0) return sfail(APE_ERR_INVALID_ARG, "score_rows: skip %d is negative", skip);
-    if (n_bodies != 1 && n_bodies != R) return sfail(APE_ERR_INVALID_ARG, "score_rows: n_bodies %d is neither 1 nor R = %d", n_bodies, R);
+    if (int rc = check_score_args("score_rows", layout, msg_dev, msg_stride, spread_dev, spread_stride, msg_dtype, truth_dev, truth_kind, truth_dtype, F,
+                                  seg_starts_host, R, skip, bodies_host, n_bodies, score_dev, score_dtype, acc_dev))
+        return rc;
     const hipStream_t st = (hipStream_t)stream;
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     SC_TRY(hipStreamIsCapturing(st, &cap));
@@ -493,6 +785,86 @@ int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     if (er != hipSuccess) {
         (void)hipStreamSynchronize(st);
         return sfail(APE_ERR_HIP, "score_rows: hipEventRecord failed: %s", hipGetErrorString(er));
+    }
+    return APE_OK;
+}
+
+int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, const void* spread_dev, int32_t spread_stride,
+                   int32_t msg_dtype, const void* truth_dev, int32_t truth_kind, int32_t truth_dtype, int32_t F,
+                   const int32_t* seg_starts_host, int32_t R, int32_t skip, const double* bodies_host, int32_t n_bodies,
+                   int32_t lag_min, int32_t lag_max, const int32_t* rec_lag_host, void* score_dev, int32_t score_dtype, double* acc_dev,
+                   void* stream) {
+    if (int rc = check_score_args("score_lags", layout, msg_dev, msg_stride, spread_dev, spread_stride, msg_dtype, truth_dev, truth_kind, truth_dtype, F,
+                                  seg_starts_host, R, skip, bodies_host, n_bodies, score_dev, score_dtype, acc_dev))
+        return rc;
+    if (lag_min > lag_max) return sfail(APE_ERR_INVALID_ARG, "score_lags: lag_min %d above lag_max %d", lag_min, lag_max);
+    const long long span = (long long)lag_max - (long long)lag_min + 1;
+    if (span > APE_SCORE_MAX_LAGS) return sfail(APE_ERR_INVALID_ARG, "score_lags: %lld lags in the sweep, at most %d", span, APE_SCORE_MAX_LAGS);
+    const int L = (int)span;
+    long long top = lag_max, bottom = lag_min;          // the largest and the smallest lag of any pair
+    for (int r = 0; r < R; ++r) {
+        const long long o = rec_lag_host ? rec_lag_host[r] : 0, lo = o + lag_min, hi = o + lag_max;
+        if (lo < -APE_SCORE_MAX_LAG || lo > APE_SCORE_MAX_LAG || hi < -APE_SCORE_MAX_LAG || hi > APE_SCORE_MAX_LAG)
+            return sfail(APE_ERR_INVALID_ARG, "score_lags: recording %d: lags %lld .. %lld, |lag| is at most %d", r, lo, hi, APE_SCORE_MAX_LAG);
+        top = r == 0 || hi > top ? hi : top;
+        bottom = r == 0 || lo < bottom ? lo : bottom;
+    }
+    const hipStream_t st = (hipStream_t)stream;
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    SC_TRY(hipStreamIsCapturing(st, &cap));
+    if (cap != hipStreamCaptureStatusNone) return sfail(APE_ERR_INVALID_ARG, "score_lags: the stream is capturing (host arrays are staged per call)");
+    int device = 0;
+    SC_TRY(hipGetDevice(&device));
+
+    const unsigned blocks = (unsigned)(((long long)F + SC_BLOCK - 1) / SC_BLOCK);
+    const size_t starts_bytes = (((size_t)R * sizeof(int)) + 7) & ~(size_t)7;       // starts, then the offsets, then the bodies
+    const size_t bodies_bytes = (size_t)n_bodies * 9 * sizeof(double);
+    const size_t host_bytes = 2 * starts_bytes + bodies_bytes;
+    const size_t part_bytes = acc_dev ? ((size_t)blocks + (size_t)R) * (size_t)L * ACC * sizeof(double) : 0;
+
+    std::lock_guard<std::mutex> lock(g_mu);
+    Slot* slot = nullptr;
+    if (int rc = take_slot(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
+    char* pin = static_cast<char*>(slot->pinned);
+    memcpy(pin, seg_starts_host, (size_t)R * sizeof(int));
+    if (rec_lag_host) memcpy(pin + starts_bytes, rec_lag_host, (size_t)R * sizeof(int));
+    else memset(pin + starts_bytes, 0, (size_t)R * sizeof(int));
+    memcpy(pin + 2 * starts_bytes, bodies_host, bodies_bytes);
+    SC_TRY(hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
+
+    LagParams q{};
+    ScoreParams& p = q.s;
+    char* dev = static_cast<char*>(slot->dev);
+    p.msg = msg_dev; p.spread = spread_dev; p.truth = truth_dev; p.score = score_dev;
+    p.starts = reinterpret_cast<const int*>(dev);
+    q.offs = reinterpret_cast<const int*>(dev + starts_bytes);
+    p.bodies = reinterpret_cast<const double*>(dev + 2 * starts_bytes);
+    p.part = acc_dev ? reinterpret_cast<double*>(dev + host_bytes) : nullptr;
+    p.msg_stride = msg_stride; p.spread_stride = spread_stride;
+    p.F = F; p.R = R; p.skip = skip; p.layout = layout; p.n_bodies = n_bodies;
+    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
+    if (truth_kind == APE_TRUTH_TARGETS) p.truth_w = layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS ? 20 : (hips ? 14 : 12);
+    else p.truth_w = hips ? 21 : 14;
+    p.score_f32 = score_dtype == APE_F32 ? 1 : 0;
+    q.lag_min = lag_min; q.L = L;
+    q.back = top > 0 ? (int)top : 0;
+    q.fwd = bottom < 0 ? (int)-bottom : 0;
+
+    if (msg_dtype == APE_F32 && truth_dtype == APE_F32) launch_lags_kind<float, float>(q, truth_kind, blocks, st);
+    else if (msg_dtype == APE_F32) launch_lags_kind<float, double>(q, truth_kind, blocks, st);
+    else if (truth_dtype == APE_F32) launch_lags_kind<double, float>(q, truth_kind, blocks, st);
+    else launch_lags_kind<double, double>(q, truth_kind, blocks, st);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess && acc_dev) {
+        hipLaunchKernelGGL(ape_score_lags_acc_kernel, dim3((unsigned)R, (unsigned)L), dim3(SC_BLOCK), 0, st, p.part, p.starts, R, F, L, acc_dev);
+        e = hipGetLastError();
+    }
+    const hipError_t er = hipEventRecord(slot->done, st);  // the slot is in flight whatever became of the launches
+    slot->used = er == hipSuccess;
+    if (e != hipSuccess) return sfail(APE_ERR_HIP, "score_lags: launch failed: %s", hipGetErrorString(e));
+    if (er != hipSuccess) {
+        (void)hipStreamSynchronize(st);
+        return sfail(APE_ERR_HIP, "score_lags: hipEventRecord failed: %s", hipGetErrorString(er));
     }
     return APE_OK;
 }

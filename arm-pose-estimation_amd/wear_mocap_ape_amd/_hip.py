@@ -28,6 +28,7 @@ FLAG_SPREAD = 0x40                # frames, banks, replays: every output row end
 SPREAD_WIDTH = 21                 # APE_SPREAD_WIDTH
 SCORE_WIDTH, SCORE_ACC_WIDTH = 7, 25        # APE_SCORE_WIDTH, APE_SCORE_ACC_WIDTH (ape_score_rows)
 TRUTH_TARGETS, TRUTH_EST = 0, 1             # APE_TRUTH_*
+SCORE_MAX_LAG, SCORE_MAX_LAGS = 128, 65      # APE_SCORE_MAX_LAG, APE_SCORE_MAX_LAGS (ape_score_lags)
 FLAG_ANY_PLACEMENT, FLAG_NO_XCD_CLASSES, FLAG_ALT_FORM = 0x08000000, 0x02000000, 0x01000000    # exchange-form selectors (A/B runs, tests)
 FLAG_IN_XCD_PLAIN = 0x00400000      # opt-in: plain hand-over stores inside an XCD-pure cluster (the default is write-through)
 KERNEL_AUTO, KERNEL_TILE16, KERNEL_CLUSTER, KERNEL_CLUSTER_GEN1, KERNEL_AUTO_GEN1 = 0, 1, 2, 3, 4
@@ -190,6 +191,10 @@ SIGNATURES["ape_kalman_bank_frame_subset_host"] = (C.c_int, [C.c_void_p, C.c_int
 SIGNATURES["ape_score_rows"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
                                           C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                           C.c_void_p, C.c_void_p])
+# the same over a sweep of lags: ... n_bodies, lag_min, lag_max, rec_lag_host, score + dtype, acc, HIP stream
+SIGNATURES["ape_score_lags"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32,
+                                          C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
 
 _lib = None
 

@@ -625,14 +625,22 @@ class Estimator:
         return res
 
     # ---- scoring a replay against ground truth (the reference has no counterpart) ----
-    def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets"):
+    def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=None,
+                        rec_lags=None):
         """``score.score_rows`` with this estimator's layout and body: ``out`` (and ``spread``) as ``process_recording`` returned them,
         ``truth`` device ``[F, O]`` de-normalised targets (or est rows with ``truth_kind="est"``); ``skip`` defaults to the
         ``sequence_len - 1`` cold-start frames of every recording; ``bonemaps``: one bonemap-like object for all recordings or one entry
-        per recording (default: this estimator's body).  Returns ``(score [F, 7], acc [R, 25])`` on the device."""
+        per recording (default: this estimator's body).  Returns ``(score [F, 7], acc [R, 25])`` on the device.
+        ``lags=(lo, hi)``: ``score.score_lags`` over that sweep of time lags instead (``rec_lags``: per-recording offsets; DESIGN.md
+        4.32), returning ``(score [F, L, 7], acc [R, L, 25])``."""
         from wear_mocap_ape_amd import score
-        return score.score_rows(self._layout, out, truth, truth_kind, spread, starts, self._sequence_len - 1 if skip is None else skip,
-                                self._body_measurements if bonemaps is None else bonemaps)
+        skip = self._sequence_len - 1 if skip is None else skip
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        if lags is None:
+            if rec_lags is not None:
+                raise UserWarning("rec_lags are offsets of a sweep: give lags=(lo, hi) with them")
+            return score.score_rows(self._layout, out, truth, truth_kind, spread, starts, skip, bodies)
+        return score.score_lags(self._layout, out, truth, lags, truth_kind, spread, starts, skip, bodies, rec_lags, per_frame=True)
 
     # read-only views, same names as the reference's properties (estimator.py:188-218)
     sequence_len = property(lambda self: self._sequence_len)

@@ -347,7 +347,8 @@ class WatchPhonePocketKalman(Estimator):
             res = res + (rec,)
         return res + (s_out, a_out) if return_state else res
 
-    def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets"):
+    def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=None, rec_lags=None):
         """``Estimator.score_recording`` for Kalman replays: ``skip`` defaults to the ``window_size + 1`` frames every recording runs on
         its first row alone, whose spread records have no usable covariance"""
-        return super().score_recording(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind)
+        return super().score_recording(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind, lags,
+                                       rec_lags)

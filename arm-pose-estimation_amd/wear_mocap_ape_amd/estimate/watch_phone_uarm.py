@@ -137,6 +137,6 @@ class WatchPhoneUarm(Estimator):
                                                        C.c_void_p(bodies.ctypes.data) if bodies is not None else None), "ape_fk_replay_bodies")
         return out
 
-    def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets"):
+    def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=None, rec_lags=None):
         """``Estimator.score_recording`` for ``[F, 25]`` FK replays (no cold-start frames: ``skip`` defaults to 0; no spread record)"""
-        return super().score_recording(out, truth, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind)
+        return super().score_recording(out, truth, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind, lags, rec_lags)

@@ -1,9 +1,14 @@
-"""Scoring replayed poses against ground truth (``ape_score_rows``, include/ape_hip.h).
+"""Scoring replayed poses against ground truth (``ape_score_rows``, ``ape_score_lags``, include/ape_hip.h).
 
 The reference has no counterpart: it never compares a message with the mocap truth its recordings carry.  ``score_rows`` does it on
 the device for every frame of a replay -- five errors and, with the frames' spread records, two squared Mahalanobis distances -- and
 accumulates them per recording; ``score_rows_numpy`` is the plain numpy statement of the per-frame values, ``summarise`` and
-``merge`` work on the raw accumulators on the host."""
+``merge`` work on the raw accumulators on the host.
+
+A smoothed estimate trails the motion and the mocap and IMU clocks are not aligned to the frame, so frame ``f`` of a replay need not
+belong to frame ``f`` of the truth: ``score_lags`` scores every frame against the truth of a whole sweep of lags in one pass (never across
+a recording boundary, and on the same frames for every lag), ``best_lag`` reads each recording's lag off the accumulators, ``align`` does
+both and scores once more at the lags found; ``score_lags_numpy`` is the host statement."""
 import ctypes as C
 
 import numpy as np
@@ -93,26 +98,29 @@ def accumulate_numpy(score, starts=None, skip: int = 0) -> np.ndarray:
     return acc
 
 
-def _as_host(acc) -> np.ndarray:
+def _as_host(acc, ndims=(2,)) -> np.ndarray:
     a = acc.detach().cpu().numpy() if isinstance(acc, torch.Tensor) else np.asarray(acc)
     a = np.asarray(a, dtype=np.float64)
-    if a.ndim != 2 or a.shape[1] != ACC_WIDTH:
-        raise UserWarning(f"expected accumulators [R,{ACC_WIDTH}], got {tuple(a.shape)}")
+    if a.ndim not in ndims or a.shape[-1] != ACC_WIDTH:
+        raise UserWarning(f"expected accumulators {' or '.join('[R,L,25]' if n == 3 else '[R,25]' for n in ndims)}, got {tuple(a.shape)}")
     return a
 
 
 def merge(acc_a, acc_b) -> np.ndarray:
-    """the accumulators of two pieces of the same recordings as one: sums and counts added, the larger of the maxima"""
-    a, b = _as_host(acc_a), _as_host(acc_b)
+    """the accumulators ``[R, 25]``, or ``[R, L, 25]`` of the same sweep, of two pieces of the same recordings as one: sums and counts
+    added, the larger of the maxima.  Of a lag sweep this is the union of the two pieces' supports: a pair whose message lies in one
+    piece and whose truth row in the other is in neither, so the frames within the sweep's reach of the cut are not scored."""
+    a, b = _as_host(acc_a, (2, 3)), _as_host(acc_b, (2, 3))
     if a.shape != b.shape:
         raise UserWarning(f"merge: {tuple(a.shape)} and {tuple(b.shape)} accumulators")
     out = a + b
-    out[:, _MAX_COLS] = np.maximum(a[:, _MAX_COLS], b[:, _MAX_COLS])
+    out[..., _MAX_COLS] = np.maximum(a[..., _MAX_COLS], b[..., _MAX_COLS])
     return out
 
 
 def summarise(acc) -> list:
-    """per recording a dict: ``scored`` / ``unscored`` frame counts, ``mean``, ``rms`` and ``max`` of the five errors (dicts keyed by
+    """``acc [R, 25]`` (of a lag sweep: one lag's slice ``acc[:, j]``) -> per recording a dict: ``scored`` / ``unscored`` frame
+    counts, ``mean``, ``rms`` and ``max`` of the five errors (dicts keyed by
     ``ERROR_NAMES``; NaN where nothing was scored), and for ``hand`` and ``elbow`` the number of frames with a usable ``d2``, its
     mean, and the fraction of those frames inside the 50 % and 90 % regions of their covariance (``coverage50`` / ``coverage90``)."""
     res = []
@@ -143,16 +151,13 @@ def _rows_view(t, width: int, what: str):
     return t, max(int(t.stride(0)), width)
 
 
-def score_rows(layout: int, msg, truth, truth_kind: str = "targets", spread=None, starts=None, skip: int = 0, bodies=None,
-               out_dtype=torch.float64, per_frame: bool = True):
-    """``msg`` device ``[F, >= 25]`` (the message at the front of every row: plain, packed or spread-flagged replay and bank rows, or
-    a strided view of them) scored against ``truth`` device ``[F, O]`` NN targets (``truth_kind="targets"``, de-normalised, through
-    the float64 FK with ``bodies``) or ``[F, 21 | 14]`` est rows (``"est"``).  ``spread``: device ``[F, >= 21]`` spread records
-    of ``msg``'s dtype (the second view ``process_recording(spread=True)`` returns goes in as it is).  ``starts``: the recordings'
-    first frames (default one recording); ``skip``: leading frames of every recording left out of the accumulators; ``bodies``:
-    float64 ``[9]`` / ``[1, 9]`` / ``[R, 9]`` values, one bonemap-like object (for all recordings) or a sequence of R (default: the default bonemap).
-    Returns ``(score, acc)``: ``[F, 7]`` of ``out_dtype`` (None with ``per_frame=False``) and float64 ``[R, 25]`` raw accumulators
-    (``summarise``, ``merge``), both on the device.  The call does not wait for the device."""
+def _f64(t):
+    return _hip.F64 if t == torch.float64 else _hip.F32
+
+
+def _prepared(layout, msg, truth, truth_kind, spread, starts, bodies, out_dtype):
+    """the checked views and host arrays of one scoring call: (msg view, its stride, spread view | None, its stride, truth, starts int32
+    ``[R]``, bodies float64 ``[1 | R, 9]``)"""
     from wear_mocap_ape_amd.data_types.bone_map import bodies_from, body9_from_bonemap
     if truth_kind not in TRUTH_KINDS:
         raise UserWarning(f"truth_kind must be one of {sorted(TRUTH_KINDS)}, got {truth_kind!r}")
@@ -183,14 +188,146 @@ def score_rows(layout: int, msg, truth, truth_kind: str = "targets", spread=None
         body = body9_from_bonemap(bodies)[np.newaxis, :]              # one bonemap-like object: that body for every recording
     else:
         body = bodies_from(bodies, R, "score_rows bodies")
-    f64 = lambda t: _hip.F64 if t == torch.float64 else _hip.F32          # noqa: E731
+    return md, ms, sd, ss, td, st, body
+
+
+def score_rows(layout: int, msg, truth, truth_kind: str = "targets", spread=None, starts=None, skip: int = 0, bodies=None,
+               out_dtype=torch.float64, per_frame: bool = True):
+    """``msg`` device ``[F, >= 25]`` (the message at the front of every row: plain, packed or spread-flagged replay and bank rows, or
+    a strided view of them) scored against ``truth`` device ``[F, O]`` NN targets (``truth_kind="targets"``, de-normalised, through
+    the float64 FK with ``bodies``) or ``[F, 21 | 14]`` est rows (``"est"``).  ``spread``: device ``[F, >= 21]`` spread records
+    of ``msg``'s dtype (the second view ``process_recording(spread=True)`` returns goes in as it is).  ``starts``: the recordings'
+    first frames (default one recording); ``skip``: leading frames of every recording left out of the accumulators; ``bodies``:
+    float64 ``[9]`` / ``[1, 9]`` / ``[R, 9]`` values, one bonemap-like object (for all recordings) or a sequence of R (default: the default bonemap).
+    Returns ``(score, acc)``: ``[F, 7]`` of ``out_dtype`` (None with ``per_frame=False``) and float64 ``[R, 25]`` raw accumulators
+    (``summarise``, ``merge``), both on the device.  The call does not wait for the device."""
+    md, ms, sd, ss, td, st, body = _prepared(layout, msg, truth, truth_kind, spread, starts, bodies, out_dtype)
+    F, R, dev = int(md.shape[0]), int(st.shape[0]), md.device
     with torch.cuda.device(dev):
         score = torch.empty((F, SCORE_WIDTH), dtype=out_dtype, device=dev) if per_frame else None
         acc = torch.empty((max(R, 1), ACC_WIDTH), dtype=torch.float64, device=dev)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _hip.check(_hip.lib().ape_score_rows(int(layout), C.c_void_p(md.data_ptr()), ms, C.c_void_p(sd.data_ptr()) if sd is not None else None,
-                                             ss, f64(md.dtype), C.c_void_p(td.data_ptr()), TRUTH_KINDS[truth_kind], f64(td.dtype), F,
+                                             ss, _f64(md.dtype), C.c_void_p(td.data_ptr()), TRUTH_KINDS[truth_kind], _f64(td.dtype), F,
                                              C.c_void_p(st.ctypes.data), R, int(skip), C.c_void_p(body.ctypes.data), int(body.shape[0]),
-                                             C.c_void_p(score.data_ptr()) if score is not None else None, f64(out_dtype),
+                                             C.c_void_p(score.data_ptr()) if score is not None else None, _f64(out_dtype),
                                              C.c_void_p(acc.data_ptr()), stream), "ape_score_rows")
     return score, acc
+
+
+# ---- the same over a sweep of time lags (ape_score_lags, DESIGN.md 4.32) ---------------------------------------------------------------------
+def _sweep(lags, R: int, rec_lags):
+    """(lag_min, lag_max, offsets int32 [R]) of ``lags=(lo, hi)`` and per-recording offsets"""
+    lo, hi = (int(v) for v in lags)
+    off = np.zeros(R, dtype=np.int32) if rec_lags is None else np.ascontiguousarray(np.asarray(rec_lags, dtype=np.int32).reshape(-1))
+    if off.shape[0] != R:
+        raise UserWarning(f"rec_lags: {off.shape[0]} offsets for {R} recordings")
+    return lo, hi, off
+
+
+def score_lags(layout: int, msg, truth, lags=(0, 0), truth_kind: str = "targets", spread=None, starts=None, skip: int = 0, bodies=None,
+               rec_lags=None, out_dtype=torch.float64, per_frame: bool = False):
+    """``score_rows`` over the sweep of lags ``lags=(lo, hi)`` (both inclusive, ``L = hi - lo + 1 <= 65``) in one pass.  In recording
+    ``r`` sweep index ``j`` stands for the lag ``l = rec_lags[r] + lo + j`` (``rec_lags``: integer offsets ``[R]``, default zeros;
+    every ``|l| <= 128``); a positive lag means the estimate is late: message and spread row ``f`` are scored against truth row
+    ``f - l`` of the same recording, and a pair that would leave the recording does not exist.  The other arguments, the views and the
+    dtypes are ``score_rows``'s.  Returns ``(score, acc)`` on the device: ``[F, L, 7]`` of ``out_dtype`` (NaN rows where the pair
+    does not exist or cannot be scored; None unless ``per_frame``) and float64 ``[R, L, 25]`` raw accumulators over the frames that
+    have a pair at every lag of the sweep and lie past the recording's first ``skip`` frames -- the same frames for every lag, so
+    ``acc[r, j]`` compare across ``j`` (``best_lag``; ``summarise(acc[:, j])``).  The call does not wait for the device."""
+    md, ms, sd, ss, td, st, body = _prepared(layout, msg, truth, truth_kind, spread, starts, bodies, out_dtype)
+    F, R, dev = int(md.shape[0]), int(st.shape[0]), md.device
+    lo, hi, off = _sweep(lags, R, rec_lags)
+    L = hi - lo + 1
+    if not 1 <= L <= _hip.SCORE_MAX_LAGS:
+        raise UserWarning(f"lags=({lo}, {hi}): between 1 and {_hip.SCORE_MAX_LAGS} lags")
+    with torch.cuda.device(dev):
+        score = torch.empty((F, L, SCORE_WIDTH), dtype=out_dtype, device=dev) if per_frame else None
+        acc = torch.empty((max(R, 1), L, ACC_WIDTH), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_score_lags(int(layout), C.c_void_p(md.data_ptr()), ms, C.c_void_p(sd.data_ptr()) if sd is not None else None,
+                                             ss, _f64(md.dtype), C.c_void_p(td.data_ptr()), TRUTH_KINDS[truth_kind], _f64(td.dtype), F,
+                                             C.c_void_p(st.ctypes.data), R, int(skip), C.c_void_p(body.ctypes.data), int(body.shape[0]),
+                                             lo, hi, C.c_void_p(off.ctypes.data) if rec_lags is not None else None,
+                                             C.c_void_p(score.data_ptr()) if score is not None else None, _f64(out_dtype),
+                                             C.c_void_p(acc.data_ptr()), stream), "ape_score_lags")
+    return score, acc
+
+
+def score_lags_numpy(msg, truth_est, layout: int, lags, starts=None, skip: int = 0, spread=None, rec_lags=None):
+    """The host statement of ``score_lags`` for est-kind truth: ``(score [F, L, 7], acc [R, L, 25])`` float64, made of
+    ``score_rows_numpy`` on every recording's and lag's pair rows (message ``f``, truth ``f - l``) and ``accumulate_numpy`` over the
+    support."""
+    msg, truth_est = np.asarray(msg), np.asarray(truth_est)
+    st = np.asarray([0] if starts is None else starts, dtype=np.int64).reshape(-1)
+    F, R = msg.shape[0], st.shape[0]
+    lo, hi, off = _sweep(lags, R, rec_lags)
+    L = hi - lo + 1
+    ends = np.r_[st[1:], F]
+    score = np.full((F, L, SCORE_WIDTH), np.nan)
+    acc = np.zeros((R, L, ACC_WIDTH))
+    for r in range(R):
+        s, e, o = int(st[r]), int(ends[r]), int(off[r])
+        a, b = max(s + skip, s + o + hi), min(e, e + o + lo)                # the support: a pair at every lag, past the skipped frames
+        for j in range(L):
+            l = o + lo + j
+            f0, f1 = max(s, s + l), min(e, e + l)                            # the frames with s <= f - l < e
+            if f0 < f1:
+                score[f0:f1, j] = score_rows_numpy(msg[f0:f1], truth_est[f0 - l:f1 - l], layout, None if spread is None else spread[f0:f1])
+            if a < b:
+                acc[r, j] = accumulate_numpy(score[a:b, j])[0]
+    return score, acc
+
+
+def best_lag(acc, lags, error: str = "hand_pos", rec_lags=None) -> list:
+    """Each recording's lag, read off the accumulators ``acc [R, L, 25]`` of a sweep ``lags=(lo, hi)`` (with the ``rec_lags`` the sweep
+    was made with).  Per recording a dict:
+    ``lag``       the lag ``l`` with the smallest mean square of ``error`` (one of ``ERROR_NAMES``) over the support; ties go to the
+                  smaller ``|l|``, then to the smaller ``l``
+    ``refined``   the vertex of the parabola through the mean squares at ``l - 1, l, l + 1``, clamped to ``l +- 0.5``, where both
+                  neighbours are in the sweep (and scored) and the second difference is > 0; ``float(lag)`` otherwise
+    ``at_edge``   ``lag`` is the first or the last of the sweep: the minimum may lie outside it
+    ``scored``    frames scored at ``lag``;  ``rms`` of ``error`` there;  ``rms_lag0``: at lag 0 (NaN where 0 is not in the sweep)
+    A recording with nothing scored at any lag (an empty support): ``lag`` and ``at_edge`` None, ``scored`` 0, the others NaN."""
+    if error not in ERROR_NAMES:
+        raise UserWarning(f"error must be one of {ERROR_NAMES}, got {error!r}")
+    a = _as_host(acc, (3,))
+    R, L = a.shape[0], a.shape[1]
+    lo, hi, off = _sweep(lags, R, rec_lags)
+    if hi - lo + 1 != L:
+        raise UserWarning(f"best_lag: lags=({lo}, {hi}) for accumulators of {L} lags")
+    c = 3 * ERROR_NAMES.index(error) + 1
+    res = []
+    for r in range(R):
+        n = a[r, :, 15]
+        with np.errstate(all="ignore"):
+            ms = np.where(n > 0, a[r, :, c] / n, np.nan)
+        ls = int(off[r]) + lo + np.arange(L)
+        cand = [j for j in range(L) if np.isfinite(ms[j])]
+        if not cand:
+            res.append({"lag": None, "refined": float("nan"), "at_edge": None, "scored": 0, "rms": float("nan"), "rms_lag0": float("nan")})
+            continue
+        j = min(cand, key=lambda k: (ms[k], abs(int(ls[k])), int(ls[k])))
+        l = int(ls[j])
+        refined = float(l)
+        if 0 < j < L - 1 and np.isfinite(ms[j - 1]) and np.isfinite(ms[j + 1]):
+            curve = ms[j - 1] - 2.0 * ms[j] + ms[j + 1]
+            if curve > 0.0:
+                refined = l + float(np.clip(0.5 * (ms[j - 1] - ms[j + 1]) / curve, -0.5, 0.5))
+        j0 = -int(ls[0])
+        res.append({"lag": l, "refined": refined, "at_edge": j in (0, L - 1), "scored": int(n[j]), "rms": float(np.sqrt(ms[j])),
+                    "rms_lag0": float(np.sqrt(ms[j0])) if 0 <= j0 < L else float("nan")})
+    return res
+
+
+def align(layout: int, msg, truth, lags, error: str = "hand_pos", truth_kind: str = "targets", spread=None, starts=None, skip: int = 0,
+          bodies=None, rec_lags=None, out_dtype=torch.float64):
+    """Find each recording's lag and score at it: a ``score_lags`` sweep (accumulators only), ``best_lag`` on it (this waits for the
+    device), then one more pass with ``lags=(0, 0)`` and the lags found as offsets (0 for a recording with an empty support).
+    Returns ``(best, score [F, 7], acc [R, 25])``: ``best_lag``'s list, and the per-frame rows and accumulators at every recording's own
+    lag, as ``score_rows`` would return them for aligned rows."""
+    _, sweep = score_lags(layout, msg, truth, lags, truth_kind, spread, starts, skip, bodies, rec_lags, out_dtype, per_frame=False)
+    best = best_lag(sweep, lags, error, rec_lags)
+    found = [0 if b["lag"] is None else b["lag"] for b in best]
+    score, acc = score_lags(layout, msg, truth, (0, 0), truth_kind, spread, starts, skip, bodies, found, out_dtype, per_frame=True)
+    return best, score[:, 0], acc[:, 0]

@@ -841,6 +841,40 @@ int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
                    const int32_t* seg_starts_host, int32_t R, int32_t skip, const double* bodies_host, int32_t n_bodies,
                    void* score_dev, int32_t score_dtype, double* acc_dev, void* stream);
 
+/* ---- scoring over a sweep of time lags (additive in ABI 7) ---------------------------------------------------------------
+ * replaces: nothing; the reference has no counterpart.  ape_score_rows pairs message f with truth f.  A smoothed estimate trails the
+ * motion (the mean of the last `smooth` frames by (smooth - 1) / 2 frames) and the mocap and IMU clocks are not aligned to the frame;
+ * ape_score_lags scores every message against the truth rows of L = lag_max - lag_min + 1 lags in one pass, within recordings only.
+ * Arguments up to n_bodies, score_dtype and stream: those of ape_score_rows, with the same meaning.
+ *   Lag.   Recording r holds the frames [s_r, e_r) (s_r = seg_starts_host[r], e_r = the next start or F).  Its offset is
+ *          o_r = rec_lag_host ? rec_lag_host[r] : 0.  Sweep index j = 0 .. L-1 stands, in recording r, for the lag l = o_r + lag_min + j.
+ *          A positive lag means the estimate is late: message row f and spread row f are compared with truth row f - l.
+ *   Pair.  The pair (f, l) of a frame f of recording r exists iff s_r <= f - l < e_r: a pair never crosses a recording boundary, and
+ *          the truth row is converted (APE_TRUTH_TARGETS) with the body of that same recording.
+ *   score_dev [F, L, APE_SCORE_WIDTH] of score_dtype, or NULL: [f, j, 0:7] are the seven values ape_score_rows defines, computed for the
+ *          pair (f, l_j) -- message f, spread record f, truth f - l_j.  All seven are NaN if the pair does not exist or is not scorable
+ *          (a non-finite value among the 25 of the message, or a non-finite truth value that is used).
+ *   acc_dev f64 [R, L, APE_SCORE_ACC_WIDTH], or NULL (not both NULL): the accumulators run over a support common to all L lags, so
+ *          that lags are compared on the same frames.  Frame f of recording r is in the support iff f - s_r >= skip and
+ *          f - (o_r + lag_max) >= s_r and f - (o_r + lag_min) < e_r (then every one of its L pairs exists).  acc[r, j, 0:25] are the 25
+ *          raw accumulators of ape_score_rows over the pairs (f, l_j), f in the support; [15] + [16] is therefore the same for every j
+ *          of a recording (the size of its support) while a gap in the truth meets a different f at every lag.  A recording with an
+ *          empty support (shorter than skip, or than the span of the sweep) gives zeros.
+ * No floating-point atomics and a fixed order of summation: the same inputs give the same bits.  With lag_min = lag_max = 0 and no
+ * offsets, score_dev and acc_dev receive the bits ape_score_rows writes for the same arguments.
+ * Needs no model handle, runs on the current HIP device, does not wait; the host arrays (seg_starts_host, bodies_host, rec_lag_host)
+ * have been consumed when it returns; the staging slots are those of ape_score_rows, taken and reused in the same way.
+ * Refused with APE_ERR_INVALID_ARG on the host, before anything is written: everything ape_score_rows refuses; lag_min > lag_max;
+ * L > APE_SCORE_MAX_LAGS; any |o_r + lag_min| or |o_r + lag_max| above APE_SCORE_MAX_LAG. */
+#define APE_SCORE_MAX_LAG  128   /* bound on |lag| of any pair */
+#define APE_SCORE_MAX_LAGS 65    /* bound on L = lag_max - lag_min + 1 */
+int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, const void* spread_dev, int32_t spread_stride,
+                   int32_t msg_dtype, const void* truth_dev, int32_t truth_kind, int32_t truth_dtype, int32_t F,
+                   const int32_t* seg_starts_host, int32_t R, int32_t skip, const double* bodies_host, int32_t n_bodies,
+                   int32_t lag_min, int32_t lag_max, const int32_t* rec_lag_host /* [R] or NULL */,
+                   void* score_dev /* [F, L, 7] or NULL */, int32_t score_dtype, double* acc_dev /* f64 [R, L, 25] or NULL */,
+                   void* stream);
+
 #ifdef __cplusplus
 }
 #endif
