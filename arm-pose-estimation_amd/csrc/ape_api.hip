@@ -17,10 +17,10 @@
 #include "ape_model.h"
 
 namespace {
-
 thread_local std::string g_err;
+}
 
-int fail(int code, const char* fmt, ...) {
+int ape_fail(int code, const char* fmt, ...) {
     char buf[512];
     va_list ap;
     va_start(ap, fmt);
@@ -30,11 +30,7 @@ int fail(int code, const char* fmt, ...) {
     return code;
 }
 
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t _e = (expr);                                                              \
-        if (_e != hipSuccess) return fail(APE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
+namespace {
 
 int layout_targets(int layout) {
     switch (layout) {
@@ -47,27 +43,27 @@ int layout_targets(int layout) {
 int layout_est_width(int layout) { return layout == APE_LAYOUT_ORI_CAL_LARM_UARM ? 14 : 21; }
 
 int check_dims(const ape_dims_t* d) {
-    if (!d) return fail(APE_ERR_INVALID_ARG, "dims is NULL");
+    if (!d) return ape_fail(APE_ERR_INVALID_ARG, "dims is NULL");
     if (d->input_size < 1 || d->input_size > APE_MAX_INPUT)
-        return fail(APE_ERR_UNSUPPORTED, "input_size %d outside 1..%d", d->input_size, APE_MAX_INPUT);
+        return ape_fail(APE_ERR_UNSUPPORTED, "input_size %d outside 1..%d", d->input_size, APE_MAX_INPUT);
     if (d->hidden_size != 128 && d->hidden_size != 256)
-        return fail(APE_ERR_UNSUPPORTED, "hidden_size %d: kernels are built for 128 and 256", d->hidden_size);
+        return ape_fail(APE_ERR_UNSUPPORTED, "hidden_size %d: kernels are built for 128 and 256", d->hidden_size);
     if (d->model_kind != APE_MODEL_LSTM && d->model_kind != APE_MODEL_FF && d->model_kind != APE_MODEL_IMUPOSE)
-        return fail(APE_ERR_INVALID_ARG, "unknown model_kind %d", d->model_kind);
+        return ape_fail(APE_ERR_INVALID_ARG, "unknown model_kind %d", d->model_kind);
     if (d->model_kind == APE_MODEL_IMUPOSE && (d->hidden_size != 256 || d->num_layers != 2))
-        return fail(APE_ERR_INVALID_ARG, "ImuPoseLSTM is a fixed 2 x 256 LSTM behind a 256-wide input layer "
+        return ape_fail(APE_ERR_INVALID_ARG, "ImuPoseLSTM is a fixed 2 x 256 LSTM behind a 256-wide input layer "
                     "(nn_models.py:222-229), got hidden_size %d num_layers %d", d->hidden_size, d->num_layers);
     if (d->model_kind != APE_MODEL_FF && (d->num_layers < 1 || d->num_layers > APE_MAX_LAYERS))
-        return fail(APE_ERR_UNSUPPORTED, "num_layers %d outside 1..%d", d->num_layers, APE_MAX_LAYERS);
+        return ape_fail(APE_ERR_UNSUPPORTED, "num_layers %d outside 1..%d", d->num_layers, APE_MAX_LAYERS);
     if (d->model_kind == APE_MODEL_FF && (d->num_layers < 0 || d->num_layers > APE_MAX_FF_LAYERS - 1))
-        return fail(APE_ERR_UNSUPPORTED, "hidden_layer_count %d outside 0..%d", d->num_layers, APE_MAX_FF_LAYERS - 1);
+        return ape_fail(APE_ERR_UNSUPPORTED, "hidden_layer_count %d outside 0..%d", d->num_layers, APE_MAX_FF_LAYERS - 1);
     if (d->output_size < 1 || d->output_size > APE_MAX_OUTPUT)
-        return fail(APE_ERR_UNSUPPORTED, "output_size %d outside 1..%d", d->output_size, APE_MAX_OUTPUT);
+        return ape_fail(APE_ERR_UNSUPPORTED, "output_size %d outside 1..%d", d->output_size, APE_MAX_OUTPUT);
     if (d->target_layout == APE_LAYOUT_NONE) return APE_OK;      // regressor only, no post-filter
     const int want = layout_targets(d->target_layout);
-    if (want < 0) return fail(APE_ERR_INVALID_ARG, "unknown target_layout %d", d->target_layout);
+    if (want < 0) return ape_fail(APE_ERR_INVALID_ARG, "unknown target_layout %d", d->target_layout);
     if (want != d->output_size)
-        return fail(APE_ERR_INVALID_ARG, "target_layout %d needs output_size %d, got %d", d->target_layout, want,
+        return ape_fail(APE_ERR_INVALID_ARG, "target_layout %d needs output_size %d, got %d", d->target_layout, want,
                     d->output_size);
     return APE_OK;
 }
@@ -176,9 +172,9 @@ static bool stream_capturing(void* stream) {
 // `what_fmt`, a format with exactly one %zu, which receives `need`
 static int grow_ws(void* stream, void** ptr, size_t* cap, size_t need, size_t elem_bytes, const char* what_fmt) {
     if (need <= *cap) return APE_OK;
-    if (stream_capturing(stream)) return fail(APE_ERR_CAPACITY, what_fmt, need);
-    if (*ptr) { HIP_TRY(hipFree(*ptr)); *ptr = nullptr; *cap = 0; }
-    HIP_TRY(hipMalloc(ptr, need * elem_bytes));
+    if (stream_capturing(stream)) return ape_fail(APE_ERR_CAPACITY, what_fmt, need);
+    if (*ptr) { APE_TRY(hipFree(*ptr)); *ptr = nullptr; *cap = 0; }
+    APE_TRY(hipMalloc(ptr, need * elem_bytes));
     *cap = need;
     return APE_OK;
 }
@@ -193,8 +189,6 @@ static U upper_params(const ape_model* m, int T, int tiles, uint32_t flags) {
     u.T = T; u.O = m->dims.output_size; u.n_tiles = tiles; u.flags = flags;
     return u;
 }
-
-int ape_set_error(int code, const char* msg) { return fail(code, "%s", msg); }
 
 // every successfully enqueued compute call of a handle is remembered until its next successful check (ape_model_recover)
 static void journal_add(ape_model* m, const ApeJournalEntry& e) {
@@ -297,24 +291,24 @@ double ape_flops_per_window(const ape_dims_t* d, int32_t T) {
 }
 
 int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
-    if (!out) return fail(APE_ERR_INVALID_ARG, "out_model is NULL");
+    if (!out) return ape_fail(APE_ERR_INVALID_ARG, "out_model is NULL");
     *out = nullptr;
     if (int rc = check_dims(dims)) return rc;
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
         (void)hipGetLastError();
-        return fail(APE_ERR_NO_DEVICE, "no HIP device visible: libape_hip has no CPU fallback");
+        return ape_fail(APE_ERR_NO_DEVICE, "no HIP device visible: libape_hip has no CPU fallback");
     }
-    if (dims->device < 0 || dims->device >= n) return fail(APE_ERR_INVALID_ARG, "device %d of %d", dims->device, n);
+    if (dims->device < 0 || dims->device >= n) return ape_fail(APE_ERR_INVALID_ARG, "device %d of %d", dims->device, n);
     hipDeviceProp_t prop;
-    HIP_TRY(hipGetDeviceProperties(&prop, dims->device));
+    APE_TRY(hipGetDeviceProperties(&prop, dims->device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return fail(APE_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", dims->device,
+        return ape_fail(APE_ERR_NO_DEVICE, "device %d is %s; this library is built for gfx950 only", dims->device,
                     prop.gcnArchName);
-    HIP_TRY(hipSetDevice(dims->device));
+    APE_TRY(hipSetDevice(dims->device));
 
     ape_model* m = new (std::nothrow) ape_model();
-    if (!m) return fail(APE_ERR_HIP, "out of host memory");
+    if (!m) return ape_fail(APE_ERR_HIP, "out of host memory");
     m->dims = *dims;
     m->n_cus = prop.multiProcessorCount;            // 256 on a whole MI355X; fewer on a partitioned / CU-masked device
     m->caps = ape_caps(dims, m->n_cus);             // (below: the bits whose set-up fails are cleared again)
@@ -369,7 +363,7 @@ int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
         if (e == hipSuccess) e = commit_plan();
         if (e != hipSuccess) {
             ape_model_destroy(m);
-            return fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
+            return ape_fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
         }
         m->kernel_name = H == 256 ? "ape_mlp_tile16<256>" : "ape_mlp_tile16<128>";
         *out = m;
@@ -395,13 +389,13 @@ int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
     else if (e == hipSuccess) e = ape_prepare_lstm_tile16(H, L, ape_lstm_tile16_smem_bytes(H, L, m->KX, O, false));
     if (e != hipSuccess) {
         ape_model_destroy(m);
-        return fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
+        return ape_fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
     }
     if (m->caps.upper_ok) {
         e = ape_prepare_lstm_tile16_upper(H, L - 1, ape_lstm_tile16_smem_bytes(H, L - 1, H, O, true));
         if (e != hipSuccess) {
             ape_model_destroy(m);
-            return fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
+            return ape_fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
         }
     }
     char nm[64];
@@ -485,13 +479,13 @@ int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
         }
         if (e != hipSuccess) {
             ape_model_destroy(m);
-            return fail(APE_ERR_HIP, "cluster kernel set-up failed: %s", hipGetErrorString(e));
+            return ape_fail(APE_ERR_HIP, "cluster kernel set-up failed: %s", hipGetErrorString(e));
         }
     }
     e = commit_plan();
     if (e != hipSuccess) {
         ape_model_destroy(m);
-        return fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
+        return ape_fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));
     }
     *out = m;
     return APE_OK;
@@ -512,11 +506,11 @@ int ape_model_destroy(ape_model_t* m) {
 }
 
 int ape_model_reserve(ape_model_t* m, int32_t max_batch) {
-    if (!m || max_batch < 1) return fail(APE_ERR_INVALID_ARG, "reserve: bad arguments");
+    if (!m || max_batch < 1) return ape_fail(APE_ERR_INVALID_ARG, "reserve: bad arguments");
     if (max_batch <= m->y_cap) return APE_OK;
-    HIP_TRY(hipSetDevice(m->dims.device));
-    if (m->y_ws) { HIP_TRY(hipFree(m->y_ws)); m->y_ws = nullptr; m->y_cap = 0; }
-    HIP_TRY(hipMalloc((void**)&m->y_ws, (size_t)max_batch * m->dims.output_size * sizeof(float)));
+    APE_TRY(hipSetDevice(m->dims.device));
+    if (m->y_ws) { APE_TRY(hipFree(m->y_ws)); m->y_ws = nullptr; m->y_cap = 0; }
+    APE_TRY(hipMalloc((void**)&m->y_ws, (size_t)max_batch * m->dims.output_size * sizeof(float)));
     m->y_cap = max_batch;
     return APE_OK;
 }
@@ -525,12 +519,12 @@ int ape_model_reserve(ape_model_t* m, int32_t max_batch) {
 //   packed[((w*Q + q)*NT + n)*64 + lane][j] = Wcat[gate*H + w*H/4 + u*16 + (lane&15)][16q + 4(lane>>4) + j]
 // with n = gate*UB + u, Wcat columns = input part zero-padded to KXl, then the recurrent part.
 int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
-    if (!m || !blob) return fail(APE_ERR_INVALID_ARG, "load_weights: NULL argument");
+    if (!m || !blob) return ape_fail(APE_ERR_INVALID_ARG, "load_weights: NULL argument");
     const size_t want = ape_weight_blob_floats(&m->dims);
-    if (n_floats != want) return fail(APE_ERR_INVALID_ARG, "weight blob has %zu floats, expected %zu", n_floats, want);
-    HIP_TRY(hipSetDevice(m->dims.device));
+    if (n_floats != want) return ape_fail(APE_ERR_INVALID_ARG, "weight blob has %zu floats, expected %zu", n_floats, want);
+    APE_TRY(hipSetDevice(m->dims.device));
     std::vector<float> host(n_floats);
-    HIP_TRY(hipMemcpy(host.data(), blob, n_floats * sizeof(float), hipMemcpyDefault));   // host or device source
+    APE_TRY(hipMemcpy(host.data(), blob, n_floats * sizeof(float), hipMemcpyDefault));   // host or device source
 
     const int H = m->dims.hidden_size, L = m->dims.num_layers, O = m->dims.output_size, I = m->dims.input_size;
     const int UB = H / 64, NT = 4 * UB;
@@ -555,8 +549,8 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                                     (k < in_j) ? wj[(size_t)col * in_j + k] : 0.0f;
                             }
                         }
-            HIP_TRY(hipMemcpy(m->ff_wpack[j], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-            HIP_TRY(hipMemcpy(m->ff_bias[j], bj, H * sizeof(float), hipMemcpyHostToDevice));
+            APE_TRY(hipMemcpy(m->ff_wpack[j], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+            APE_TRY(hipMemcpy(m->ff_bias[j], bj, H * sizeof(float), hipMemcpyHostToDevice));
         }
         if (!pre_only && m->ffp_ok) {
             // mlp_pipe.hip: v_mfma_f32_32x32x2_f32 A fragments, register 4 kb + j of lane (unit column = lane & 31, hh = lane >> 5) =
@@ -577,7 +571,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                                     const int unit = 64 * w + 32 * ct + (lane & 31), k = 8 * kb + 4 * (lane >> 5) + jj;
                                     pk[((((size_t)w * 2 + ct) * kbl[j] + kb) * 64 + lane) * 4 + jj] = (k < inl[j]) ? wl[j][(size_t)unit * inl[j] + k] : 0.0f;
                                 }
-                HIP_TRY(hipMemcpy(dst[j], pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
+                APE_TRY(hipMemcpy(dst[j], pk.data(), pk.size() * sizeof(float), hipMemcpyHostToDevice));
             }
             std::vector<float> po((size_t)4 * 8 * 64 * 4);
             for (int w = 0; w < 4; ++w)
@@ -587,12 +581,12 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                             const int o = lane & 31, k = 64 * w + 8 * kb + 4 * (lane >> 5) + jj;
                             po[(((size_t)w * 8 + kb) * 64 + lane) * 4 + jj] = (o < O) ? w_out_h[(size_t)o * H + k] : 0.0f;
                         }
-            HIP_TRY(hipMemcpy(m->ffp_wbo, po.data(), po.size() * sizeof(float), hipMemcpyHostToDevice));
+            APE_TRY(hipMemcpy(m->ffp_wbo, po.data(), po.size() * sizeof(float), hipMemcpyHostToDevice));
         }
         if (!pre_only) {
-            HIP_TRY(hipMemcpy(m->w_out, cur, (size_t)O * H * sizeof(float), hipMemcpyHostToDevice));
+            APE_TRY(hipMemcpy(m->w_out, cur, (size_t)O * H * sizeof(float), hipMemcpyHostToDevice));
             cur += (size_t)O * H;
-            HIP_TRY(hipMemcpy(m->b_out, cur, O * sizeof(float), hipMemcpyHostToDevice));
+            APE_TRY(hipMemcpy(m->b_out, cur, O * sizeof(float), hipMemcpyHostToDevice));
             m->has_weights = true;
             return APE_OK;
         }
@@ -640,7 +634,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                             // register i of that lane; stored [k-quad i/4][lane][i%4] so a lane fetches 4 registers per load
                             pc[((((size_t)(mem * 4 + w) * (NW / 4)) + i / 4) * 64 + lane) * 4 + (i % 4)] = v;
                         }
-            HIP_TRY(hipMemcpy(m->wcl[l], pc.data(), pc.size() * sizeof(float), hipMemcpyHostToDevice));
+            APE_TRY(hipMemcpy(m->wcl[l], pc.data(), pc.size() * sizeof(float), hipMemcpyHostToDevice));
             if (m->small_uw == 2) {
                 // latency kernel, H/8 members: a wave owns 2 units = 8 columns, 8 k-groups; lane = (g << 3) | (u << 2) | gate holds
                 // Wcat[gate*H + (member*4 + wave)*2 + u][32q + 4g + j] in register 4q + j; same [i/4][lane][i%4] storage
@@ -658,7 +652,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                                 else v = w_hh[(size_t)row * H + (k - KXl)];
                                 ps[((((size_t)(mem * 4 + w) * (NWS / 4)) + i / 4) * 64 + lane) * 4 + (i % 4)] = v;
                             }
-                HIP_TRY(hipMemcpy(m->wcls[l], ps.data(), ps.size() * sizeof(float), hipMemcpyHostToDevice));
+                APE_TRY(hipMemcpy(m->wcls[l], ps.data(), ps.size() * sizeof(float), hipMemcpyHostToDevice));
             }
             if (m->caps.mc_small && l >= 1) {
                 // Monte-Carlo latency kernel, layers above layer 0 (v_mfma_f32_4x4x1_16b_f32): H/8 members x 4 waves, wave w = K quarter w of
@@ -676,7 +670,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                                 pm[((((size_t)(mem * 4 + w) * (NI4 / 4)) + i / 4) * 64 + lane) * 4 + (i % 4)] =
                                     k < H ? w_ih[(size_t)row * H + k] : w_hh[(size_t)row * H + (k - H)];
                             }
-                HIP_TRY(hipMemcpy(m->wmc[l], pm.data(), pm.size() * sizeof(float), hipMemcpyHostToDevice));
+                APE_TRY(hipMemcpy(m->wmc[l], pm.data(), pm.size() * sizeof(float), hipMemcpyHostToDevice));
                 // ... and the 16 x 16 x 4 image of its 16-row form: wave = (column tile ct = w & 1, K half kh = w >> 1); lane = (g << 4) | (u << 2) |
                 // gate holds Wcat[gate*H + member*8 + ct*4 + u][kh*H + 16q + 4g + j] in register 4q + j; stored [member][wave][q][lane][4]
                 const int NQm = H / 16;
@@ -692,7 +686,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                                         kh == 0 ? w_ih[(size_t)row * H + k] : w_hh[(size_t)row * H + k];
                                 }
                             }
-                HIP_TRY(hipMemcpy(m->wmc16[l], pm.data(), pm.size() * sizeof(float), hipMemcpyHostToDevice));
+                APE_TRY(hipMemcpy(m->wmc16[l], pm.data(), pm.size() * sizeof(float), hipMemcpyHostToDevice));
             }
             // fp16 variant: [member][wave][32-deep k-block q][lane][8]: lane holds Wcat[row][32q + 8g + j] as binary16
             const int NB = (KXl + H) / 32;
@@ -711,7 +705,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                                 ph[((((size_t)(mem * 4 + w) * NB) + q) * 64 + lane) * 8 + j] = (_Float16)v;
                             }
                         }
-            if (m->wcl16[l]) HIP_TRY(hipMemcpy(m->wcl16[l], ph.data(), ph.size() * sizeof(_Float16), hipMemcpyHostToDevice));
+            if (m->wcl16[l]) APE_TRY(hipMemcpy(m->wcl16[l], ph.data(), ph.size() * sizeof(_Float16), hipMemcpyHostToDevice));
         }
         if (m->wcl32[l] != nullptr) {
             // second-generation f32 cluster kernel (v_mfma_f32_32x32x2_f32, weights = A operand): 8 members x 4 waves, a wave owns
@@ -731,7 +725,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                             else v = w_hh[(size_t)row * H + (k - KXl)];
                             pc[((((size_t)(mem * 4 + w) * (NW / 4)) + i / 4) * 64 + lane) * 4 + (i % 4)] = v;
                         }
-            HIP_TRY(hipMemcpy(m->wcl32[l], pc.data(), pc.size() * sizeof(float), hipMemcpyHostToDevice));
+            APE_TRY(hipMemcpy(m->wcl32[l], pc.data(), pc.size() * sizeof(float), hipMemcpyHostToDevice));
         }
         if (m->wcl32s[l] != nullptr) {
             std::vector<unsigned> ps((size_t)8 * 4 * ((KXl + H) / 2) * 64);
@@ -741,7 +735,7 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
             else {
                 m->c32_scale[l] = std::ldexp(1.0f, S);
                 m->c32_descale[l] = std::ldexp(1.0f, -S);
-                HIP_TRY(hipMemcpy(m->wcl32s[l], ps.data(), ps.size() * sizeof(unsigned), hipMemcpyHostToDevice));
+                APE_TRY(hipMemcpy(m->wcl32s[l], ps.data(), ps.size() * sizeof(unsigned), hipMemcpyHostToDevice));
             }
         }
         if (m->caps.up128 && l >= 1) {
@@ -760,23 +754,23 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
                             pc[((((size_t)(mem * 4 + w) * (NW / 4)) + i / 4) * 64 + lane) * 4 + (i % 4)] =
                                 k < KXl ? w_ih[(size_t)row * in_l + k] : w_hh[(size_t)row * H + (k - KXl)];
                         }
-            HIP_TRY(hipMemcpy(m->wup128[l], pc.data(), pc.size() * sizeof(float), hipMemcpyHostToDevice));
+            APE_TRY(hipMemcpy(m->wup128[l], pc.data(), pc.size() * sizeof(float), hipMemcpyHostToDevice));
         }
         std::vector<float> bsum(4 * H);
         for (int i = 0; i < 4 * H; ++i) bsum[i] = b_ih[i] + b_hh[i];
-        HIP_TRY(hipMemcpy(m->wpack[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
-        HIP_TRY(hipMemcpy(m->bias[l], bsum.data(), bsum.size() * sizeof(float), hipMemcpyHostToDevice));
+        APE_TRY(hipMemcpy(m->wpack[l], packed.data(), packed.size() * sizeof(float), hipMemcpyHostToDevice));
+        APE_TRY(hipMemcpy(m->bias[l], bsum.data(), bsum.size() * sizeof(float), hipMemcpyHostToDevice));
     }
-    HIP_TRY(hipMemcpy(m->w_out, cur, (size_t)O * H * sizeof(float), hipMemcpyHostToDevice));
+    APE_TRY(hipMemcpy(m->w_out, cur, (size_t)O * H * sizeof(float), hipMemcpyHostToDevice));
     cur += (size_t)O * H;
-    HIP_TRY(hipMemcpy(m->b_out, cur, O * sizeof(float), hipMemcpyHostToDevice));
+    APE_TRY(hipMemcpy(m->b_out, cur, O * sizeof(float), hipMemcpyHostToDevice));
     m->has_weights = true;
     return APE_OK;
 }
 
 int ape_model_set_norm_stats(ape_model_t* m, const double* xx_m, const double* xx_s, const double* yy_m,
                              const double* yy_s) {
-    if (!m || !xx_m || !xx_s || !yy_m || !yy_s) return fail(APE_ERR_INVALID_ARG, "set_norm_stats: NULL argument");
+    if (!m || !xx_m || !xx_s || !yy_m || !yy_s) return ape_fail(APE_ERR_INVALID_ARG, "set_norm_stats: NULL argument");
     const int I = m->dims.input_size, O = m->dims.output_size;
     std::vector<double> h(3 * I + 2 * O);
     for (int i = 0; i < I; ++i) h[2 * I + 2 * O + i] = 1.0 / xx_s[i];     // reciprocal for the in-kernel z-score
@@ -784,14 +778,14 @@ int ape_model_set_norm_stats(ape_model_t* m, const double* xx_m, const double* x
     memcpy(&h[I], xx_s, I * sizeof(double));
     memcpy(&h[2 * I], yy_m, O * sizeof(double));
     memcpy(&h[2 * I + O], yy_s, O * sizeof(double));
-    HIP_TRY(hipSetDevice(m->dims.device));
-    HIP_TRY(hipMemcpy(m->stats, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
+    APE_TRY(hipSetDevice(m->dims.device));
+    APE_TRY(hipMemcpy(m->stats, h.data(), h.size() * sizeof(double), hipMemcpyHostToDevice));
     m->has_stats = true;
     return APE_OK;
 }
 
 int ape_model_set_body(ape_model_t* m, const double body9[9]) {
-    if (!m || !body9) return fail(APE_ERR_INVALID_ARG, "set_body: NULL argument");
+    if (!m || !body9) return ape_fail(APE_ERR_INVALID_ARG, "set_body: NULL argument");
     memcpy(m->body, body9, 9 * sizeof(double));
     return APE_OK;
 }
@@ -854,7 +848,7 @@ static int mc_small_launch(ape_model_t* m, const float* x, size_t x_stream_strid
     }
     m->last_kernel = "ape_lstm_mc_small";
     hipError_t e = ape_launch_lstm_mc_small(m->dims.hidden_size, L, m->KX, q, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "Monte-Carlo latency kernel launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "Monte-Carlo latency kernel launch failed: %s", hipGetErrorString(e));
     return APE_OK;
 }
 
@@ -864,15 +858,15 @@ static int split32_forward(ape_model_t* m, const LstmPlan& plan, int B, int T, u
     const int tiles_max = ((B < chunk ? B : chunk) + 31) / 32;
     if ((size_t)tiles_max > m->split_tiles_cap || (size_t)T > m->split_steps_cap) {
         if (stream_capturing(stream))
-            return fail(APE_ERR_CAPACITY, "lstm_forward: the layer workspaces (%d tiles x %d steps) cannot grow during stream capture", tiles_max, T);
-        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+            return ape_fail(APE_ERR_CAPACITY, "lstm_forward: the layer workspaces (%d tiles x %d steps) cannot grow during stream capture", tiles_max, T);
+        APE_TRY(hipStreamSynchronize((hipStream_t)stream));
         // (both dimensions only ever grow: a caller alternating between many short and few long windows does not reallocate)
         const size_t tc = std::max((size_t)tiles_max, m->split_tiles_cap), sc = std::max((size_t)T, m->split_steps_cap);
         m->split_tiles_cap = m->split_steps_cap = 0;
         void** const ws[3] = {(void**)&m->zfrag_ws, (void**)&m->hfrag_ws, (void**)&m->ypart_ws};
         const size_t bytes[3] = {tc * sc * 32768, tc * sc * 32768, ape_upper32_ypart_bytes((int)tc * 32)};
-        for (void** w : ws) if (*w) { HIP_TRY(hipFree(*w)); *w = nullptr; }
-        for (int i = 0; i < 3; ++i) HIP_TRY(hipMalloc(ws[i], bytes[i]));
+        for (void** w : ws) if (*w) { APE_TRY(hipFree(*w)); *w = nullptr; }
+        for (int i = 0; i < 3; ++i) APE_TRY(hipMalloc(ws[i], bytes[i]));
         m->split_tiles_cap = tc; m->split_steps_cap = sc;
     }
     for (int b0 = 0; b0 < B; b0 += chunk) {
@@ -888,7 +882,7 @@ static int split32_forward(ape_model_t* m, const LstmPlan& plan, int B, int T, u
         m->last_kernel = plan.last_kernel;
         hipError_t e2 = ape_launch_lstm_split32(m->z_ws + (size_t)b0 * T * H, nb, u0, u1, m->b_out,
                                                 y_dev + (size_t)b0 * m->dims.output_size, m->caps.f16v2_capacity, (hipStream_t)stream);
-        if (e2 != hipSuccess) return fail(APE_ERR_HIP, "layer-split lstm launch failed: %s", hipGetErrorString(e2));
+        if (e2 != hipSuccess) return ape_fail(APE_ERR_HIP, "layer-split lstm launch failed: %s", hipGetErrorString(e2));
     }
     return APE_OK;
 }
@@ -899,35 +893,35 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
                              int x_ring, const float* h0_dev = nullptr, const float* c0_dev = nullptr, FkTail* fk = nullptr,
                              long long row_base = 0) {
     // row_base (DROPOUT_PHILOX, a multiple of 16): the global row of x_dev's row 0 when a caller serves one batch in several calls
-    if (!m || !x_dev || !y_dev) return fail(APE_ERR_INVALID_ARG, "lstm_forward: NULL argument");
-    if (B < 1 || T < 1) return fail(APE_ERR_INVALID_ARG, "lstm_forward: B=%d T=%d must be >= 1", B, T);
+    if (!m || !x_dev || !y_dev) return ape_fail(APE_ERR_INVALID_ARG, "lstm_forward: NULL argument");
+    if (B < 1 || T < 1) return ape_fail(APE_ERR_INVALID_ARG, "lstm_forward: B=%d T=%d must be >= 1", B, T);
     flags &= ~(uint32_t)APE_FLAG_XCD_CLASSES;            // (the launcher's own bit)
 #if !defined(APE_ABLATE) && !defined(APE_CLUSTER_STAMPS)
     // the product library knows the documented flags and the four exchange-form selectors of include/ape_hip.h; the timing-only
     // ablation bits (results are garbage) exist in the diagnostic builds alone
     if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_ALL_STEPS | APE_FLAG_DROPOUT_MASKS | APE_FLAG_DROPOUT_PHILOX | APE_FLAG_BROADCAST_X |
                             APE_FLAG_ANY_PLACEMENT | APE_FLAG_IN_XCD_PLAIN | APE_FLAG_NO_XCD_CLASSES | APE_FLAG_ALT_FORM))
-        return fail(APE_ERR_INVALID_ARG, "lstm_forward: unknown flag bits 0x%x", flags);
+        return ape_fail(APE_ERR_INVALID_ARG, "lstm_forward: unknown flag bits 0x%x", flags);
 #endif
-    if (!m->has_weights) return fail(APE_ERR_NOT_READY, "lstm_forward: weights not loaded");
+    if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "lstm_forward: weights not loaded");
     if ((flags & APE_FLAG_NORMALIZE_INPUT) && !m->has_stats)
-        return fail(APE_ERR_NOT_READY, "lstm_forward: NORMALIZE_INPUT without norm stats");
+        return ape_fail(APE_ERR_NOT_READY, "lstm_forward: NORMALIZE_INPUT without norm stats");
     if ((flags & APE_FLAG_DROPOUT_MASKS) && (flags & APE_FLAG_DROPOUT_PHILOX))
-        return fail(APE_ERR_INVALID_ARG, "lstm_forward: choose one dropout mode");
+        return ape_fail(APE_ERR_INVALID_ARG, "lstm_forward: choose one dropout mode");
     if ((flags & APE_FLAG_DROPOUT_MASKS) && m->dims.num_layers > 1 && !masks_dev)
-        return fail(APE_ERR_INVALID_ARG, "lstm_forward: DROPOUT_MASKS without masks");
+        return ape_fail(APE_ERR_INVALID_ARG, "lstm_forward: DROPOUT_MASKS without masks");
     if ((flags & APE_FLAG_DROPOUT_PHILOX) && !(dropout_p >= 0.0f && dropout_p < 1.0f))
-        return fail(APE_ERR_INVALID_ARG, "lstm_forward: dropout_p %f outside [0,1)", dropout_p);
+        return ape_fail(APE_ERR_INVALID_ARG, "lstm_forward: dropout_p %f outside [0,1)", dropout_p);
     const int H = m->dims.hidden_size, L = m->dims.num_layers;
     const bool drop = (flags & (APE_FLAG_DROPOUT_MASKS | APE_FLAG_DROPOUT_PHILOX)) != 0;
     const bool have_hs = h0_dev != nullptr || c0_dev != nullptr;
-    if (have_hs && (!h0_dev || !c0_dev)) return fail(APE_ERR_INVALID_ARG, "lstm_forward: h0 and c0 come together");
+    if (have_hs && (!h0_dev || !c0_dev)) return ape_fail(APE_ERR_INVALID_ARG, "lstm_forward: h0 and c0 come together");
     if (have_hs && m->dims.model_kind == APE_MODEL_FF)
-        return fail(APE_ERR_INVALID_ARG, "lstm_forward: the MLP regressor has no recurrent state");
+        return ape_fail(APE_ERR_INVALID_ARG, "lstm_forward: the MLP regressor has no recurrent state");
     if (m->dims.model_kind == APE_MODEL_FF) {
-        if (flags & APE_FLAG_BROADCAST_X) return fail(APE_ERR_UNSUPPORTED, "lstm_forward: BROADCAST_X is an LSTM-path flag");
+        if (flags & APE_FLAG_BROADCAST_X) return ape_fail(APE_ERR_UNSUPPORTED, "lstm_forward: BROADCAST_X is an LSTM-path flag");
         if ((flags & APE_FLAG_DROPOUT_MASKS) && !masks_dev)
-            return fail(APE_ERR_INVALID_ARG, "lstm_forward: DROPOUT_MASKS without masks");
+            return ape_fail(APE_ERR_INVALID_ARG, "lstm_forward: DROPOUT_MASKS without masks");
         MlpParams q{};
         const bool all = (flags & APE_FLAG_ALL_STEPS) != 0;
         q.x = x_dev; q.y = y_dev;
@@ -948,17 +942,17 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
         if (m->ffp_ok && m->ffp_on && !m->replaying && !drop && q.hidden_out == nullptr && q.mask == nullptr && one_descriptor && q.N >= 64 * m->n_cus) {
             hipError_t e2 = ape_launch_mlp_pipe(q, m->ffp_wa0, m->ffp_wa1, m->ffp_wb2, m->ffp_wbo, m->ffp_ring, m->ffp_ring_bytes, m->ffp_ctl,
                                                m->n_cus, (hipStream_t)stream);
-            if (e2 != hipSuccess) return fail(APE_ERR_HIP, "mlp pipeline launch failed: %s", hipGetErrorString(e2));
+            if (e2 != hipSuccess) return ape_fail(APE_ERR_HIP, "mlp pipeline launch failed: %s", hipGetErrorString(e2));
             return APE_OK;
         }
         hipError_t e = ape_launch_mlp_tile16(H, q, (hipStream_t)stream, m->n_cus);
-        if (e != hipSuccess) return fail(APE_ERR_HIP, "mlp kernel launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "mlp kernel launch failed: %s", hipGetErrorString(e));
         return APE_OK;
     }
     const float* lstm_x = x_dev;
     if (m->dims.model_kind == APE_MODEL_IMUPOSE) {
         // relu(input_layer(x)) for every row of every window (nn_models.py:242), then the LSTM reads those 256 columns
-        if (drop) return fail(APE_ERR_UNSUPPORTED, "lstm_forward: ImuPoseLSTM has no Monte-Carlo dropout mode "
+        if (drop) return ape_fail(APE_ERR_UNSUPPORTED, "lstm_forward: ImuPoseLSTM has no Monte-Carlo dropout mode "
                               "(its monte_carlo_predictions is the plain forward, nn_models.py:246-251)");
         const size_t rows = (size_t)((flags & APE_FLAG_BROADCAST_X) ? 1 : B) * T;
         if (int rc = grow_ws(stream, (void**)&m->z_ws, &m->z_cap, rows, H * sizeof(float),
@@ -971,7 +965,7 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
         q.N = (int)rows; q.I = m->dims.input_size; q.O = m->dims.output_size; q.KX = m->KXpre; q.n_hidden = 0;
         q.flags = flags & APE_FLAG_NORMALIZE_INPUT; q.neg_slope = 0.0f;
         hipError_t e = ape_launch_mlp_tile16(H, q, (hipStream_t)stream, m->n_cus);
-        if (e != hipSuccess) return fail(APE_ERR_HIP, "input-layer kernel launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "input-layer kernel launch failed: %s", hipGetErrorString(e));
         lstm_x = m->z_ws;
         flags &= ~(uint32_t)APE_FLAG_NORMALIZE_INPUT;        // done in front of the input layer
     }
@@ -980,9 +974,9 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
     const LstmPlan plan = plan_lstm(m->caps, m->dims, call);
     if (plan.route == PLAN_SPLIT32) return split32_forward(m, plan, B, T, flags, y_dev, stream);
     if (ape_lstm_tile16_smem_bytes(H, L, m->KX, m->dims.output_size, drop) > 160 * 1024)
-        return fail(APE_ERR_UNSUPPORTED, "lstm_forward: H=%d L=%d with dropout exceeds the 160 KiB LDS of a CU", H, L);
+        return ape_fail(APE_ERR_UNSUPPORTED, "lstm_forward: H=%d L=%d with dropout exceeds the 160 KiB LDS of a CU", H, L);
     if (plan.route == PLAN_UNSUPPORTED)        // (err == nullptr: the one message that names B)
-        return plan.err ? fail(plan.err_code, "%s", plan.err) : fail(plan.err_code, "lstm_forward: injected masks with B=%d exceed one cluster launch", B);
+        return plan.err ? ape_fail(plan.err_code, "%s", plan.err) : ape_fail(plan.err_code, "lstm_forward: injected masks with B=%d exceed one cluster launch", B);
     if (plan.route == PLAN_MC_SMALL)
         return mc_small_launch(m, x_dev, 0, 1, B, T, flags, masks_dev, dropout_p, seed, y_dev, stream, x_ring);
     if (plan.n16 > 0) {
@@ -995,7 +989,7 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
         p.h0 = h0_dev; p.c0 = c0_dev; p.hs_rows = B; p.row_base = row_base;
         m->last_kernel = "ape_lstm_tile16";
         hipError_t e = ape_launch_lstm_tile16(H, L, p, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(APE_ERR_HIP, "lstm kernel launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "lstm kernel launch failed: %s", hipGetErrorString(e));
         if (plan.n16 == B) return APE_OK;
     }
     // rows [n16, B) in launches of plan.rows_per_launch: each route brings its weight image, its exchange buffer and its launcher
@@ -1054,11 +1048,11 @@ static int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int3
                                              : ape_launch_lstm_cluster(H, L, m->KX, plan.nmt, plan.cdrop, clusters, c, (hipStream_t)stream);
             }
         }
-        if (e != hipSuccess) return fail(APE_ERR_HIP, "%s lstm launch failed: %s", what, hipGetErrorString(e));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s lstm launch failed: %s", what, hipGetErrorString(e));
     }
     if (all_steps) {
         hipError_t e = ape_launch_head_rows(m->hseq_ws, B * T, H, O, m->w_out, m->b_out, y_dev, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(APE_ERR_HIP, "head kernel launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "head kernel launch failed: %s", hipGetErrorString(e));
     }
     return APE_OK;
 }
@@ -1092,16 +1086,16 @@ int ape_lstm_forward_hs(ape_model_t* m, const float* x_dev, int32_t B, int32_t T
 }
 
 int ape_model_set_kernel(ape_model_t* m, int32_t choice) {
-    if (!m) return fail(APE_ERR_INVALID_ARG, "set_kernel: NULL model");
+    if (!m) return ape_fail(APE_ERR_INVALID_ARG, "set_kernel: NULL model");
     if (choice != APE_KERNEL_AUTO && choice != APE_KERNEL_TILE16 && choice != APE_KERNEL_CLUSTER && choice != APE_KERNEL_CLUSTER_GEN1 &&
         choice != APE_KERNEL_AUTO_GEN1)
-        return fail(APE_ERR_INVALID_ARG, "set_kernel: unknown choice %d", choice);
+        return ape_fail(APE_ERR_INVALID_ARG, "set_kernel: unknown choice %d", choice);
     m->c32_on = choice != APE_KERNEL_CLUSTER_GEN1 && choice != APE_KERNEL_AUTO_GEN1;
     m->ffp_on = choice != APE_KERNEL_TILE16;           // (MLP regressor: TILE16 pins the tile kernel)
     if (choice == APE_KERNEL_CLUSTER_GEN1) choice = APE_KERNEL_CLUSTER;
     if (choice == APE_KERNEL_AUTO_GEN1) choice = APE_KERNEL_AUTO;
     if (choice == APE_KERNEL_CLUSTER && !m->caps.cluster_ok)
-        return fail(APE_ERR_UNSUPPORTED, "set_kernel: no cluster kernel for H=%d L=%d on a device with %d CUs (a cluster "
+        return ape_fail(APE_ERR_UNSUPPORTED, "set_kernel: no cluster kernel for H=%d L=%d on a device with %d CUs (a cluster "
                     "needs %d)", m->dims.hidden_size, m->dims.num_layers, m->n_cus, m->dims.hidden_size / 16);
     m->kernel_choice = choice;
     m->small_batch_path = (choice == APE_KERNEL_AUTO);
@@ -1109,13 +1103,13 @@ int ape_model_set_kernel(ape_model_t* m, int32_t choice) {
 }
 
 int ape_model_set_precision(ape_model_t* m, int32_t precision) {
-    if (!m) return fail(APE_ERR_INVALID_ARG, "set_precision: NULL model");
+    if (!m) return ape_fail(APE_ERR_INVALID_ARG, "set_precision: NULL model");
     if (precision != APE_PRECISION_F32 && precision != APE_PRECISION_F16 && precision != APE_PRECISION_F16_GEN1)
-        return fail(APE_ERR_INVALID_ARG, "set_precision: unknown precision %d", precision);
+        return ape_fail(APE_ERR_INVALID_ARG, "set_precision: unknown precision %d", precision);
     m->f16_v2 = precision != APE_PRECISION_F16_GEN1;
     if (precision == APE_PRECISION_F16_GEN1) precision = APE_PRECISION_F16;
     if (precision == APE_PRECISION_F16 && (!m->caps.cluster_ok || m->caps.wide))
-        return fail(APE_ERR_UNSUPPORTED, "set_precision: no fp16 kernel for H=%d L=%d", m->dims.hidden_size,
+        return ape_fail(APE_ERR_UNSUPPORTED, "set_precision: no fp16 kernel for H=%d L=%d", m->dims.hidden_size,
                     m->dims.num_layers);
     m->precision = precision;
     return APE_OK;
@@ -1126,7 +1120,7 @@ int ape_model_set_precision(ape_model_t* m, int32_t precision) {
 static int check_and_reset(ape_model_t* m);
 
 int ape_model_check(ape_model_t* m) {
-    if (!m) return fail(APE_ERR_INVALID_ARG, "check: NULL model");
+    if (!m) return ape_fail(APE_ERR_INVALID_ARG, "check: NULL model");
     const int rc = check_and_reset(m);
     if (rc != APE_OK && rc != APE_ERR_INVALID_ARG) {
         m->stats_counts.aborted_checks += 1;
@@ -1137,7 +1131,7 @@ int ape_model_check(ape_model_t* m) {
 }
 
 int ape_model_stats(const ape_model_t* m, ape_model_stats_t* out) {
-    if (!m || !out) return fail(APE_ERR_INVALID_ARG, "stats: NULL argument");
+    if (!m || !out) return ape_fail(APE_ERR_INVALID_ARG, "stats: NULL argument");
     *out = m->stats_counts;
     return APE_OK;
 }
@@ -1150,7 +1144,7 @@ static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_
                                const SubsetHostWords& hw = SubsetHostWords{});
 
 int ape_model_recover(ape_model_t* m) {
-    if (!m) return fail(APE_ERR_INVALID_ARG, "recover: NULL model");
+    if (!m) return ape_fail(APE_ERR_INVALID_ARG, "recover: NULL model");
     const int rc = check_and_reset(m);
     if (rc == APE_OK) { journal_clear(m); return APE_OK; }
     if (rc == APE_ERR_INVALID_ARG) return rc;
@@ -1170,7 +1164,7 @@ int ape_model_recover(ape_model_t* m) {
         m->stats_counts.lost_calls += (uint64_t)n;
         const bool over = m->journal_overflow;
         journal_clear(m);
-        return fail(APE_ERR_HIP, "%d pending call(s) could not be re-issued (%s) behind an aborted launch: %s", n,
+        return ape_fail(APE_ERR_HIP, "%d pending call(s) could not be re-issued (%s) behind an aborted launch: %s", n,
                     over ? "more than 64 calls since the last check, or a call the journal cannot hold"
                          : "a stream bank has moved on since the aborted step", what.c_str());
     }
@@ -1184,40 +1178,40 @@ int ape_model_recover(ape_model_t* m) {
     const int n = m->journal_n;
     journal_clear(m);
     if (bad != APE_OK) { m->stats_counts.lost_calls += (uint64_t)n; return bad; }
-    HIP_TRY(hipDeviceSynchronize());
+    APE_TRY(hipDeviceSynchronize());
     return APE_OK;
 }
 
 static int check_and_reset(ape_model_t* m) {
-    if (!m) return fail(APE_ERR_INVALID_ARG, "check: NULL model");
+    if (!m) return ape_fail(APE_ERR_INVALID_ARG, "check: NULL model");
     if (m->ffp_ok) {                                // the MLP pipeline's status word (bounded spins between its two stages)
-        HIP_TRY(hipSetDevice(m->dims.device));
-        HIP_TRY(hipDeviceSynchronize());
+        APE_TRY(hipSetDevice(m->dims.device));
+        APE_TRY(hipDeviceSynchronize());
         unsigned st = 0;
-        HIP_TRY(hipMemcpy(&st, m->ffp_ctl + 8 * 16, sizeof(st), hipMemcpyDeviceToHost));
+        APE_TRY(hipMemcpy(&st, m->ffp_ctl + 8 * 16, sizeof(st), hipMemcpyDeviceToHost));
         if (st != 0) {
-            HIP_TRY(hipMemset(m->ffp_ctl, 0, m->ffp_ctl_words * sizeof(unsigned)));
-            HIP_TRY(hipDeviceSynchronize());
-            return fail(APE_ERR_HIP, "mlp pipeline launch aborted (status %u); outputs since the last successful check are invalid; the model "
+            APE_TRY(hipMemset(m->ffp_ctl, 0, m->ffp_ctl_words * sizeof(unsigned)));
+            APE_TRY(hipDeviceSynchronize());
+            return ape_fail(APE_ERR_HIP, "mlp pipeline launch aborted (status %u); outputs since the last successful check are invalid; the model "
                         "is usable again", st);
         }
     }
     if (!m->caps.cluster_ok) return APE_OK;
-    HIP_TRY(hipSetDevice(m->dims.device));
+    APE_TRY(hipSetDevice(m->dims.device));
     // every stream of the device, non-blocking ones included: a launch that is still spinning must have ended (its
     // status word written) before the word is read, and nothing may be in flight when the flags are reset below
-    HIP_TRY(hipDeviceSynchronize());
+    APE_TRY(hipDeviceSynchronize());
     unsigned st = 0;
-    HIP_TRY(hipMemcpy(&st, ctl_words(m).status, sizeof(st), hipMemcpyDeviceToHost));
+    APE_TRY(hipMemcpy(&st, ctl_words(m).status, sizeof(st), hipMemcpyDeviceToHost));
     if (st != 0) {
         // an aborted launch skipped its self-cleaning: reset flags, counters and the status word from the host
-        HIP_TRY(hipMemset(m->xflags, 0, m->xflag_bytes + 16));
-        HIP_TRY(hipMemset(m->xcc_slots, 0, APE_XCC_WORDS * sizeof(unsigned)));
-        HIP_TRY(hipMemset(m->hxs, 0, 256 + m->hxs_bytes));     // the aborted launch's granules carry tags the next launch would await
-        if (m->gxm) HIP_TRY(hipMemset(m->gxm, 0, 256 + 8 * m->gxm_cluster_bytes + 8 * 64 * 8));
-        if (m->gx16) HIP_TRY(hipMemset(m->gx16, 0, 256 + m->gx16_bytes));
-        HIP_TRY(hipDeviceSynchronize());
-        return fail(APE_ERR_HIP, "cluster kernel launch aborted (status %u: %s); outputs of every launch on this model "
+        APE_TRY(hipMemset(m->xflags, 0, m->xflag_bytes + 16));
+        APE_TRY(hipMemset(m->xcc_slots, 0, APE_XCC_WORDS * sizeof(unsigned)));
+        APE_TRY(hipMemset(m->hxs, 0, 256 + m->hxs_bytes));     // the aborted launch's granules carry tags the next launch would await
+        if (m->gxm) APE_TRY(hipMemset(m->gxm, 0, 256 + 8 * m->gxm_cluster_bytes + 8 * 64 * 8));
+        if (m->gx16) APE_TRY(hipMemset(m->gx16, 0, 256 + m->gx16_bytes));
+        APE_TRY(hipDeviceSynchronize());
+        return ape_fail(APE_ERR_HIP, "cluster kernel launch aborted (status %u: %s); outputs of every launch on this model "
                     "since the last successful check are invalid; the model is usable again", st,
                     st == 1 ? "a workgroup gave up waiting for a peer -- not all workgroups of a cluster were resident"
                     : st == 5 ? "the Monte-Carlo latency kernel gave up waiting for the members of a cluster -- not all workgroups were resident"
@@ -1244,12 +1238,12 @@ int ape_fk(ape_model_t* m, const void* preds_dev, int32_t preds_dtype, int32_t N
 
 static int fk_impl(ape_model_t* m, const void* preds_dev, int32_t preds_dtype, int32_t N, int32_t denormalize, void* est_dev,
                    int32_t est_dtype, void* stream, const FkBodyRows* bodies) {
-    if (!m || !preds_dev || !est_dev) return fail(APE_ERR_INVALID_ARG, "fk: NULL argument");
-    if (N < 1) return fail(APE_ERR_INVALID_ARG, "fk: N=%d must be >= 1", N);
+    if (!m || !preds_dev || !est_dev) return ape_fail(APE_ERR_INVALID_ARG, "fk: NULL argument");
+    if (N < 1) return ape_fail(APE_ERR_INVALID_ARG, "fk: N=%d must be >= 1", N);
     if ((preds_dtype != APE_F32 && preds_dtype != APE_F64) || (est_dtype != APE_F32 && est_dtype != APE_F64))
-        return fail(APE_ERR_INVALID_ARG, "fk: unknown dtype selector");
-    if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "fk: model has no target layout");
-    if (denormalize && !m->has_stats) return fail(APE_ERR_NOT_READY, "fk: denormalize without norm stats");
+        return ape_fail(APE_ERR_INVALID_ARG, "fk: unknown dtype selector");
+    if (m->dims.target_layout == APE_LAYOUT_NONE) return ape_fail(APE_ERR_INVALID_ARG, "fk: model has no target layout");
+    if (denormalize && !m->has_stats) return ape_fail(APE_ERR_NOT_READY, "fk: denormalize without norm stats");
     FkParams p{};
     p.preds = preds_dev;
     p.est = est_dev;
@@ -1260,21 +1254,21 @@ static int fk_impl(ape_model_t* m, const void* preds_dev, int32_t preds_dtype, i
     memcpy(p.body, m->body, sizeof(p.body));
     p.N = N; p.O = m->dims.output_size; p.layout = m->dims.target_layout; p.W = layout_est_width(p.layout);
     hipError_t e = ape_launch_fk(p, preds_dtype, est_dtype, (hipStream_t)stream, bodies);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "fk kernel launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "fk kernel launch failed: %s", hipGetErrorString(e));
     return APE_OK;
 }
 
 int ape_msg_reduce(ape_model_t* m, const double* est_dev, int32_t N, double* msg_dev, void* stream) {
-    if (!m || !est_dev || !msg_dev) return fail(APE_ERR_INVALID_ARG, "msg_reduce: NULL argument");
-    if (N < 1) return fail(APE_ERR_INVALID_ARG, "msg_reduce: N=%d must be >= 1", N);
-    if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "msg_reduce: model has no target layout");
+    if (!m || !est_dev || !msg_dev) return ape_fail(APE_ERR_INVALID_ARG, "msg_reduce: NULL argument");
+    if (N < 1) return ape_fail(APE_ERR_INVALID_ARG, "msg_reduce: N=%d must be >= 1", N);
+    if (m->dims.target_layout == APE_LAYOUT_NONE) return ape_fail(APE_ERR_INVALID_ARG, "msg_reduce: model has no target layout");
     MsgParams p{};
     p.est = est_dev;
     p.msg = msg_dev;
     memcpy(p.body, m->body, sizeof(p.body));
     p.N = N; p.layout = m->dims.target_layout; p.W = layout_est_width(p.layout);
     hipError_t e = ape_launch_msg_reduce(p, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "msg kernel launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "msg kernel launch failed: %s", hipGetErrorString(e));
     ApeJournalEntry je{};
     je.kind = ApeJournalEntry::MSG; je.in0 = est_dev; je.out0 = msg_dev; je.B = N; je.stream = stream;
     journal_add(m, je);
@@ -1282,53 +1276,53 @@ int ape_msg_reduce(ape_model_t* m, const double* est_dev, int32_t N, double* msg
 }
 
 int ape_spread_reduce(ape_model_t* m, const double* est_dev, int32_t N, const double* msg_dev, double* spread_dev, void* stream) {
-    if (!m || !est_dev || !msg_dev || !spread_dev) return fail(APE_ERR_INVALID_ARG, "spread_reduce: NULL argument");
-    if (N < 1) return fail(APE_ERR_INVALID_ARG, "spread_reduce: N=%d must be >= 1", N);
-    if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "spread_reduce: model has no target layout");
+    if (!m || !est_dev || !msg_dev || !spread_dev) return ape_fail(APE_ERR_INVALID_ARG, "spread_reduce: NULL argument");
+    if (N < 1) return ape_fail(APE_ERR_INVALID_ARG, "spread_reduce: N=%d must be >= 1", N);
+    if (m->dims.target_layout == APE_LAYOUT_NONE) return ape_fail(APE_ERR_INVALID_ARG, "spread_reduce: model has no target layout");
     MsgParams p{};
     p.est = est_dev;
     p.N = N; p.layout = m->dims.target_layout; p.W = layout_est_width(p.layout);
     // (not journaled: no cooperative kernel in front of it can abort it, and it reads what ape_fk / ape_msg_reduce re-issue into)
     hipError_t e = ape_launch_spread_reduce(p, msg_dev, spread_dev, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "spread kernel launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "spread kernel launch failed: %s", hipGetErrorString(e));
     return APE_OK;
 }
 
 int ape_parse_rows(int32_t kind, const float* rows_dev, int32_t N, void* xx_dev, int32_t xx_dtype, void* stream) {
-    if (!rows_dev || !xx_dev) return fail(APE_ERR_INVALID_ARG, "parse_rows: NULL argument");
-    if (N < 1) return fail(APE_ERR_INVALID_ARG, "parse_rows: N=%d must be >= 1", N);
-    if (xx_dtype != APE_F32 && xx_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "parse_rows: unknown dtype selector");
+    if (!rows_dev || !xx_dev) return ape_fail(APE_ERR_INVALID_ARG, "parse_rows: NULL argument");
+    if (N < 1) return ape_fail(APE_ERR_INVALID_ARG, "parse_rows: N=%d must be >= 1", N);
+    if (xx_dtype != APE_F32 && xx_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "parse_rows: unknown dtype selector");
     int width, I;
     const int big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
     kind &= ~APE_PARSE_BIG_ENDIAN;
-    if (!parse_kind_dims(kind, &width, &I)) return fail(APE_ERR_INVALID_ARG, "parse_rows: unknown kind %d", kind);
+    if (!parse_kind_dims(kind, &width, &I)) return ape_fail(APE_ERR_INVALID_ARG, "parse_rows: unknown kind %d", kind);
     hipError_t e = ape_launch_parse_rows(rows_dev, N, width, kind, xx_dev, xx_dtype, I, (size_t)I, 1, 0, big_endian,
                                          (hipStream_t)stream);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "parse_rows launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "parse_rows launch failed: %s", hipGetErrorString(e));
     return APE_OK;
 }
 
 int ape_infer(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t flags, float* y_dev, void* est_dev,
               int32_t est_dtype, void* stream) {
-    if (!m || !x_dev || !est_dev) return fail(APE_ERR_INVALID_ARG, "infer: NULL argument");
+    if (!m || !x_dev || !est_dev) return ape_fail(APE_ERR_INVALID_ARG, "infer: NULL argument");
     if (flags & (APE_FLAG_ALL_STEPS | APE_FLAG_DROPOUT_MASKS | APE_FLAG_DROPOUT_PHILOX | APE_FLAG_SPREAD))
-        return fail(APE_ERR_INVALID_ARG, "infer: only NORMALIZE_INPUT is accepted (use ape_lstm_forward + ape_fk)");
+        return ape_fail(APE_ERR_INVALID_ARG, "infer: only NORMALIZE_INPUT is accepted (use ape_lstm_forward + ape_fk)");
     float* y = y_dev;
     if (!y) {
         if (B > m->y_cap) {
             hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
             (void)hipStreamIsCapturing((hipStream_t)stream, &st);
             if (st != hipStreamCaptureStatusNone)
-                return fail(APE_ERR_CAPACITY, "infer: B=%d exceeds reserved %d during stream capture", B, m->y_cap);
+                return ape_fail(APE_ERR_CAPACITY, "infer: B=%d exceeds reserved %d during stream capture", B, m->y_cap);
             if (int rc = ape_model_reserve(m, B)) return rc;
         }
         y = m->y_ws;
     }
     // de-normalise exactly when the inputs were normalised (estimator.py:103-109: one switch)
     const bool denorm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
-    if (est_dtype != APE_F32 && est_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "fk: unknown dtype selector");
-    if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "fk: model has no target layout");
-    if (denorm && !m->has_stats) return fail(APE_ERR_NOT_READY, "fk: denormalize without norm stats");
+    if (est_dtype != APE_F32 && est_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "fk: unknown dtype selector");
+    if (m->dims.target_layout == APE_LAYOUT_NONE) return ape_fail(APE_ERR_INVALID_ARG, "fk: model has no target layout");
+    if (denorm && !m->has_stats) return ape_fail(APE_ERR_NOT_READY, "fk: denormalize without norm stats");
     FkTail tail{est_dev, est_dtype, denorm, false};
     if (int rc = lstm_forward_impl(m, x_dev, B, T, flags, nullptr, 0.0f, 0, y, stream, 0, nullptr, nullptr, &tail)) return rc;
     if (!tail.done)                                        // (else the latency kernel finished the rows itself)
@@ -1355,7 +1349,7 @@ static int bank_copies(const ape_streams* b) { return b->model->dims.model_kind 
 static int ff_bank_forward(ape_model* m, const float* x, size_t x_stride, long long row_base, int rows, int n_mc, bool norm, const float* masks,
                            float dropout_p, uint64_t seed, float* hid, float* y, void* stream, hipEvent_t ev_a = nullptr, hipEvent_t ev_z = nullptr,
                            long long philox_base = 0) {
-    if (!m->has_weights) return fail(APE_ERR_NOT_READY, "ff bank: weights not loaded");
+    if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "ff bank: weights not loaded");
     const int H = m->dims.hidden_size, L = m->dims.num_layers, I = m->dims.input_size;
     const long long g_base = row_base / n_mc;
     const int groups = (int)((row_base + rows + n_mc - 1) / n_mc - g_base);
@@ -1370,7 +1364,7 @@ static int ff_bank_forward(ape_model* m, const float* x, size_t x_stride, long l
     q.neg_slope = 0.01f;                      // torch's leaky_relu default (nn_models.py:347,349)
     if (ev_a) (void)hipEventRecord(ev_a, (hipStream_t)stream);
     hipError_t e = ape_launch_mlp_tile16(H, q, (hipStream_t)stream, m->n_cus);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "ff bank: trunk launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "ff bank: trunk launch failed: %s", hipGetErrorString(e));
     FfHeadParams hp{};
     hp.hidden = hid; hp.w_out = m->w_out; hp.b_out = m->b_out; hp.masks = masks; hp.y = y;
     hp.row_base = row_base; hp.g_base = g_base; hp.rows = rows; hp.n_mc = n_mc; hp.H = H; hp.O = m->dims.output_size;
@@ -1378,7 +1372,7 @@ static int ff_bank_forward(ape_model* m, const float* x, size_t x_stride, long l
     m->last_kernel = "ape_ff_bank_head";
     e = ape_launch_ff_bank_head(hp, (hipStream_t)stream);
     if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "ff bank: head launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "ff bank: head launch failed: %s", hipGetErrorString(e));
     return APE_OK;
 }
 
@@ -1420,14 +1414,14 @@ static hipError_t bank_alloc(ape_streams* b) {
 }
 
 int ape_streams_create(ape_model_t* m, int32_t n_streams, int32_t seq_len, int32_t smooth, ape_streams_t** out) {
-    if (!out) return fail(APE_ERR_INVALID_ARG, "streams_create: out is NULL");
+    if (!out) return ape_fail(APE_ERR_INVALID_ARG, "streams_create: out is NULL");
     *out = nullptr;
-    if (!m) return fail(APE_ERR_INVALID_ARG, "streams_create: NULL model");
-    if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "streams_create: model has no target layout");
-    if (n_streams < 1 || seq_len < 1) return fail(APE_ERR_INVALID_ARG, "streams_create: n_streams=%d seq_len=%d", n_streams, seq_len);
-    if (smooth < 1 || smooth > 64) return fail(APE_ERR_UNSUPPORTED, "streams_create: smooth %d outside 1..64", smooth);
+    if (!m) return ape_fail(APE_ERR_INVALID_ARG, "streams_create: NULL model");
+    if (m->dims.target_layout == APE_LAYOUT_NONE) return ape_fail(APE_ERR_INVALID_ARG, "streams_create: model has no target layout");
+    if (n_streams < 1 || seq_len < 1) return ape_fail(APE_ERR_INVALID_ARG, "streams_create: n_streams=%d seq_len=%d", n_streams, seq_len);
+    if (smooth < 1 || smooth > 64) return ape_fail(APE_ERR_UNSUPPORTED, "streams_create: smooth %d outside 1..64", smooth);
     ape_streams* b = new (std::nothrow) ape_streams();
-    if (!b) return fail(APE_ERR_HIP, "out of host memory");
+    if (!b) return ape_fail(APE_ERR_HIP, "out of host memory");
     b->model = m; b->S = n_streams; b->T = seq_len; b->smooth = smooth;
     // DropoutFF (nn_models.py:340-352 behind watch_phone_pocket_nn.py:111): [:, -1, :] of a row-wise MLP -- the window, its length and its
     // cold-start padding have no influence on the output, so the bank keeps the newest row only
@@ -1436,7 +1430,7 @@ int ape_streams_create(ape_model_t* m, int32_t n_streams, int32_t seq_len, int32
     if (e == hipSuccess) e = bank_alloc(b);
     if (e != hipSuccess) {
         ape_streams_destroy(b);
-        return fail(APE_ERR_HIP, "streams_create: allocation failed: %s", hipGetErrorString(e));
+        return ape_fail(APE_ERR_HIP, "streams_create: allocation failed: %s", hipGetErrorString(e));
     }
     *out = b;
     return APE_OK;
@@ -1463,12 +1457,12 @@ static void subset_free(ape_streams* b) {
 }
 
 int ape_streams_set_mc(ape_streams_t* b, int32_t n_mc, float dropout_p, uint64_t seed) {
-    if (!b) return fail(APE_ERR_INVALID_ARG, "streams_set_mc: NULL bank");
+    if (!b) return ape_fail(APE_ERR_INVALID_ARG, "streams_set_mc: NULL bank");
     if (n_mc < 1 || (long long)n_mc * b->smooth > 4096)
-        return fail(APE_ERR_INVALID_ARG, "streams_set_mc: n_mc=%d with smooth=%d (1 <= smooth*n_mc <= 4096)", n_mc, b->smooth);
-    if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return fail(APE_ERR_INVALID_ARG, "streams_set_mc: dropout_p %g outside [0,1)", (double)dropout_p);
-    HIP_TRY(hipSetDevice(b->model->dims.device));
-    HIP_TRY(hipDeviceSynchronize());             // the rings may still be read by an earlier step
+        return ape_fail(APE_ERR_INVALID_ARG, "streams_set_mc: n_mc=%d with smooth=%d (1 <= smooth*n_mc <= 4096)", n_mc, b->smooth);
+    if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return ape_fail(APE_ERR_INVALID_ARG, "streams_set_mc: dropout_p %g outside [0,1)", (double)dropout_p);
+    APE_TRY(hipSetDevice(b->model->dims.device));
+    APE_TRY(hipDeviceSynchronize());             // the rings may still be read by an earlier step
     // ImuPoseLSTM.monte_carlo_predictions(n_samples, x) is self(x, None) (nn_models.py:246-251): the count is ignored and there is no
     // dropout -- the bank keeps one row per stream and frame (the call is still the cold start it is for the other banks)
     if (b->model->dims.model_kind == APE_MODEL_IMUPOSE) { n_mc = 1; dropout_p = 0.0f; }
@@ -1485,7 +1479,7 @@ int ape_streams_set_mc(ape_streams_t* b, int32_t n_mc, float dropout_p, uint64_t
         if (b->y_new) (void)hipFree(b->y_new);
         b->xring = b->yring = b->y_new = nullptr;
         bank_free_regressor_ws(b);
-        return fail(APE_ERR_HIP, "streams_set_mc: allocation failed: %s", hipGetErrorString(e));
+        return ape_fail(APE_ERR_HIP, "streams_set_mc: allocation failed: %s", hipGetErrorString(e));
     }
     // the route (csrc/ape_plan.h).  The [S,T,H] sequence of a shared layer 0 lives in the model's all-steps workspace, sized here so
     // that the step itself never allocates.
@@ -1498,23 +1492,23 @@ int ape_streams_set_mc(ape_streams_t* b, int32_t n_mc, float dropout_p, uint64_t
     if (want.shared_l0) {
         const size_t rows = (size_t)b->S * b->T;
         if (rows > m->hseq_cap) {
-            if (m->hseq_ws) { HIP_TRY(hipFree(m->hseq_ws)); m->hseq_ws = nullptr; m->hseq_cap = 0; }
-            HIP_TRY(hipMalloc((void**)&m->hseq_ws, rows * m->dims.hidden_size * sizeof(float)));
+            if (m->hseq_ws) { APE_TRY(hipFree(m->hseq_ws)); m->hseq_ws = nullptr; m->hseq_cap = 0; }
+            APE_TRY(hipMalloc((void**)&m->hseq_ws, rows * m->dims.hidden_size * sizeof(float)));
             m->hseq_cap = rows;
         }
         const int chunk = (int)want.chunk_rows;
         if (want.route == BANK_UPPER128) {
             // the 3 x 128 model: launch A stays on the batch-tile kernel ([S,T,H] in the model's sequence workspace), launch B =
             // layers 1 and 2 on lstm_upper128.hip
-            HIP_TRY(hipMalloc((void**)&b->xfrag, ape_upper128_xfrag_bytes(chunk, b->T)));
-            HIP_TRY(hipMalloc((void**)&b->ypart, ape_upper128_ypart_bytes(chunk)));
-            HIP_TRY(hipMalloc((void**)&b->maskbits, ape_upper128_maskbits_bytes(chunk, b->T)));
+            APE_TRY(hipMalloc((void**)&b->xfrag, ape_upper128_xfrag_bytes(chunk, b->T)));
+            APE_TRY(hipMalloc((void**)&b->ypart, ape_upper128_ypart_bytes(chunk)));
+            APE_TRY(hipMalloc((void**)&b->maskbits, ape_upper128_maskbits_bytes(chunk, b->T)));
         } else if (want.route == BANK_UPPER32) {
-            HIP_TRY(hipMalloc((void**)&b->xfrag, ape_upper32_xfrag_bytes(chunk, b->T)));
-            HIP_TRY(hipMalloc((void**)&b->ypart, ape_upper32_ypart_bytes(chunk)));
+            APE_TRY(hipMalloc((void**)&b->xfrag, ape_upper32_xfrag_bytes(chunk, b->T)));
+            APE_TRY(hipMalloc((void**)&b->ypart, ape_upper32_ypart_bytes(chunk)));
             // layer 0 on the same cluster structure (its SEQ form): input tiles and the [tile][step] sequence, fragment order
-            HIP_TRY(hipMalloc((void**)&b->xfrag0, ape_lower32_xfrag_bytes(b->S, b->T)));
-            HIP_TRY(hipMalloc((void**)&b->hfrag, ape_lower32_hseq_bytes(b->S, b->T)));
+            APE_TRY(hipMalloc((void**)&b->xfrag0, ape_lower32_xfrag_bytes(b->S, b->T)));
+            APE_TRY(hipMalloc((void**)&b->hfrag, ape_lower32_hseq_bytes(b->S, b->T)));
         }
         b->plan = want;
     }
@@ -1541,8 +1535,7 @@ int ape_streams_destroy(ape_streams_t* b) {
     for (auto ev : b->prof_ev) if (ev) (void)hipEventDestroy(ev);
     subset_free(b);                     // (drops the bank's pending subset frame as below)
     ape_body_table_free(b->bodies);
-    for (auto ev : b->sub_ev) if (ev) { (void)hipEventSynchronize(ev); (void)hipEventDestroy(ev); }
-    if (b->sub_stage) (void)hipHostFree(b->sub_stage);
+    b->sub_stage.free();
     if (b->state_desc) (void)hipFree(b->state_desc);
     if (ape_model* m = b->model) {      // pending steps of this bank can no longer be re-issued
         int k = 0;
@@ -1557,31 +1550,27 @@ int ape_streams_destroy(ape_streams_t* b) {
 }
 
 int ape_streams_reset(ape_streams_t* b) {
-    if (!b) return fail(APE_ERR_INVALID_ARG, "streams_reset: NULL bank");
+    if (!b) return ape_fail(APE_ERR_INVALID_ARG, "streams_reset: NULL bank");
     b->frames = 0; b->steps = 0;
     b->per_stream = false;                       // every stream cold: the lockstep calls serve the bank again
     return APE_OK;
 }
 
-static int subset_check_list(const ape_streams* b, const int32_t* streams_host, int32_t K, const char* what);
-
 // per-stream body measurements: replaces the bonemap every reference Estimator is built with (estimator.py:57-68).
 // No cold start: windows and stacks hold features and NN targets, which do not depend on the body.
 int ape_streams_set_bodies(ape_streams_t* b, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream) {
-    if (!b || !body9s_host) return fail(APE_ERR_INVALID_ARG, "streams_set_bodies: NULL argument");
+    if (!b || !body9s_host) return ape_fail(APE_ERR_INVALID_ARG, "streams_set_bodies: NULL argument");
     if (streams_host) {
-        if (int rc = subset_check_list(b, streams_host, K, "streams_set_bodies")) return rc;
-    } else if (K != b->S) return fail(APE_ERR_INVALID_ARG, "streams_set_bodies: no stream list: K=%d must be S=%d", K, b->S);
-    HIP_TRY(hipSetDevice(b->model->dims.device));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "streams_set_bodies: the stream is capturing (the table's image is staged per call)");
-    HIP_TRY(ape_body_table_set(b->bodies, b->S, false, b->model->body, streams_host, K, body9s_host, (hipStream_t)stream));
+        if (int rc = ape_check_stream_list("streams_set_bodies", streams_host, K, b->S, false)) return rc;
+    } else if (K != b->S) return ape_fail(APE_ERR_INVALID_ARG, "streams_set_bodies: no stream list: K=%d must be S=%d", K, b->S);
+    APE_TRY(hipSetDevice(b->model->dims.device));
+    if (int rc = ape_check_not_capturing((hipStream_t)stream, "streams_set_bodies", "the table's image is staged per call")) return rc;
+    APE_TRY(ape_body_table_set(b->bodies, b->S, false, b->model->body, streams_host, K, body9s_host, (hipStream_t)stream));
     return APE_OK;
 }
 
 int ape_streams_get_bodies(ape_streams_t* b, double* out_host) {
-    if (!b || !out_host) return fail(APE_ERR_INVALID_ARG, "streams_get_bodies: NULL argument");
+    if (!b || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "streams_get_bodies: NULL argument");
     ape_body_table_get(b->bodies, b->S, b->model->body, out_host);
     return APE_OK;
 }
@@ -1597,34 +1586,34 @@ static void next_slot(const ape_streams* b, size_t I, float** out, int* rep, siz
 }
 
 int ape_streams_push_rows(ape_streams_t* b, int32_t kind, const float* rows_dev, void* stream) {
-    if (!b || !rows_dev) return fail(APE_ERR_INVALID_ARG, "streams_push_rows: NULL argument");
-    if (!b->xring) return fail(APE_ERR_NOT_READY, "streams_push_rows: the bank lost its rings in a failed ape_streams_set_mc");
-    if (b->per_stream) return fail(APE_ERR_NOT_READY, "streams_push_rows: the bank is in per-stream mode (subset frames); ape_streams_reset first");
+    if (!b || !rows_dev) return ape_fail(APE_ERR_INVALID_ARG, "streams_push_rows: NULL argument");
+    if (!b->xring) return ape_fail(APE_ERR_NOT_READY, "streams_push_rows: the bank lost its rings in a failed ape_streams_set_mc");
+    if (b->per_stream) return ape_fail(APE_ERR_NOT_READY, "streams_push_rows: the bank is in per-stream mode (subset frames); ape_streams_reset first");
     int width, I;
     const int big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
     kind &= ~APE_PARSE_BIG_ENDIAN;
-    if (!parse_kind_dims(kind, &width, &I)) return fail(APE_ERR_INVALID_ARG, "streams_push_rows: unknown kind %d", kind);
+    if (!parse_kind_dims(kind, &width, &I)) return ape_fail(APE_ERR_INVALID_ARG, "streams_push_rows: unknown kind %d", kind);
     if (I != b->model->dims.input_size)
-        return fail(APE_ERR_INVALID_ARG, "streams_push_rows: kind %d builds %d features, the model takes %d", kind, I,
+        return ape_fail(APE_ERR_INVALID_ARG, "streams_push_rows: kind %d builds %d features, the model takes %d", kind, I,
                     b->model->dims.input_size);
     float* out; int rep; size_t rep_stride;
     next_slot(b, (size_t)I, &out, &rep, &rep_stride);
     hipError_t e = ape_launch_parse_rows(rows_dev, b->S, width, kind, out, APE_F32, I, (size_t)bank_copies(b) * b->T * I, rep,
                                          rep_stride, big_endian, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_push_rows launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_push_rows launch failed: %s", hipGetErrorString(e));
     ++b->frames;
     return APE_OK;
 }
 
 int ape_streams_push_features(ape_streams_t* b, const float* xx_dev, void* stream) {
-    if (!b || !xx_dev) return fail(APE_ERR_INVALID_ARG, "streams_push_features: NULL argument");
-    if (!b->xring) return fail(APE_ERR_NOT_READY, "streams_push_features: the bank lost its rings in a failed ape_streams_set_mc");
-    if (b->per_stream) return fail(APE_ERR_NOT_READY, "streams_push_features: the bank is in per-stream mode (subset frames); ape_streams_reset first");
+    if (!b || !xx_dev) return ape_fail(APE_ERR_INVALID_ARG, "streams_push_features: NULL argument");
+    if (!b->xring) return ape_fail(APE_ERR_NOT_READY, "streams_push_features: the bank lost its rings in a failed ape_streams_set_mc");
+    if (b->per_stream) return ape_fail(APE_ERR_NOT_READY, "streams_push_features: the bank is in per-stream mode (subset frames); ape_streams_reset first");
     const int I = b->model->dims.input_size;
     float* out; int rep; size_t rep_stride;
     next_slot(b, (size_t)I, &out, &rep, &rep_stride);
     hipError_t e = ape_launch_ring_write(xx_dev, b->S, I, out, (size_t)bank_copies(b) * b->T * I, rep, rep_stride, (hipStream_t)stream);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_push_features launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_push_features launch failed: %s", hipGetErrorString(e));
     ++b->frames;
     return APE_OK;
 }
@@ -1647,27 +1636,27 @@ static bool bank_on_mc_small(const ape_streams* b) {
 
 static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, void* tail_dev, int32_t out_dtype, void* stream,
                              unsigned* status_out, const McFrameParts* fuse) {
-    if (!b || !msg_dev) return fail(APE_ERR_INVALID_ARG, "streams_step: NULL argument");
+    if (!b || !msg_dev) return ape_fail(APE_ERR_INVALID_ARG, "streams_step: NULL argument");
     if (!b->xring || !b->yring || !b->y_new)
-        return fail(APE_ERR_NOT_READY, "streams_step: the bank lost its rings in a failed ape_streams_set_mc");
-    if (b->per_stream) return fail(APE_ERR_NOT_READY, "streams_step: the bank is in per-stream mode (subset frames); ape_streams_reset first");
-    if (b->frames == 0) return fail(APE_ERR_NOT_READY, "streams_step: no row pushed since the last reset");
+        return ape_fail(APE_ERR_NOT_READY, "streams_step: the bank lost its rings in a failed ape_streams_set_mc");
+    if (b->per_stream) return ape_fail(APE_ERR_NOT_READY, "streams_step: the bank is in per-stream mode (subset frames); ape_streams_reset first");
+    if (b->frames == 0) return ape_fail(APE_ERR_NOT_READY, "streams_step: no row pushed since the last reset");
     // the exchange-form selectors of include/ape_hip.h travel to the frame's LSTM launches unchanged (same bits whichever is set)
     const uint32_t diag_wt = flags & (APE_FLAG_ANY_PLACEMENT | APE_FLAG_IN_XCD_PLAIN | APE_FLAG_NO_XCD_CLASSES);
     flags &= ~diag_wt;
     if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG | APE_FLAG_SPREAD))
-        return fail(APE_ERR_INVALID_ARG, "streams_step: NORMALIZE_INPUT, PACKED_MSG, SPREAD and the exchange-form selectors ANY_PLACEMENT, "
+        return ape_fail(APE_ERR_INVALID_ARG, "streams_step: NORMALIZE_INPUT, PACKED_MSG, SPREAD and the exchange-form selectors ANY_PLACEMENT, "
                     "IN_XCD_PLAIN, NO_XCD_CLASSES are accepted");
     const bool spread = (flags & APE_FLAG_SPREAD) != 0;     // every msg row APE_SPREAD_WIDTH columns longer (post-filter, SPR forms)
     flags &= ~(uint32_t)APE_FLAG_SPREAD;
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "streams_step: unknown dtype selector");
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "streams_step: unknown dtype selector");
     const bool packed = (flags & APE_FLAG_PACKED_MSG) != 0;
     if (packed && tail_dev)
-        return fail(APE_ERR_INVALID_ARG, "streams_step: PACKED_MSG rows carry the tail themselves (tail_dev must be NULL)");
+        return ape_fail(APE_ERR_INVALID_ARG, "streams_step: PACKED_MSG rows carry the tail themselves (tail_dev must be NULL)");
     flags &= ~(uint32_t)APE_FLAG_PACKED_MSG;
     ape_model* m = b->model;
     const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
-    if (norm && !m->has_stats) return fail(APE_ERR_NOT_READY, "streams_step: NORMALIZE_INPUT without norm stats");
+    if (norm && !m->has_stats) return ape_fail(APE_ERR_NOT_READY, "streams_step: NORMALIZE_INPUT without norm stats");
     // oldest row of every window: the slot after the newest one
     const int x_ring = (int)(b->frames % b->T);
     const bool drop = b->mc && b->dropout_p > 0.0f && m->dims.num_layers > 1;
@@ -1700,9 +1689,9 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
     if (m->dims.model_kind == APE_MODEL_FF) {
         // DropoutFF: the newest row of every stream (T = 1: slot 0) -> trunk once per stream -> n_mc masked heads -> y_new in the row
         // order the post-filter reads.  Masks keyed by (seed + frame counter; row = stream * n_mc + sample; hidden unit)
-        if (!b->ffhid) return fail(APE_ERR_NOT_READY, "streams_step: the bank lost its rings in a failed ape_streams_set_mc");
+        if (!b->ffhid) return ape_fail(APE_ERR_NOT_READY, "streams_step: the bank lost its rings in a failed ape_streams_set_mc");
         if (b->inj_masks && !b->mc)
-            return fail(APE_ERR_UNSUPPORTED, "streams_step: injected masks (test hook) on a DropoutFF bank without ape_streams_set_mc");
+            return ape_fail(APE_ERR_UNSUPPORTED, "streams_step: injected masks (test hook) on a DropoutFF bank without ape_streams_set_mc");
         hipEvent_t ev_a, ev_z;
         prof_pair(&ev_a, &ev_z);
         if (int rc = ff_bank_forward(m, b->xring, (size_t)m->dims.input_size, 0, b->S * b->n_mc, b->n_mc, norm, b->inj_masks,
@@ -1711,17 +1700,17 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
     } else if (m->dims.model_kind == APE_MODEL_IMUPOSE) {
         // ImuPoseLSTM: the rings in time order (cold-start pad included), then the forward a subset frame runs over its compact windows
         // (x_ring = 0: the layer-split route above 512 windows applies) -- the same launches, hence the same bits
-        if (!b->xwin) return fail(APE_ERR_NOT_READY, "streams_step: the bank lost its rings in a failed ape_streams_set_mc");
+        if (!b->xwin) return ape_fail(APE_ERR_NOT_READY, "streams_step: the bank lost its rings in a failed ape_streams_set_mc");
         hipError_t e = ape_launch_ring_windows(b->xring, b->xwin, b->S, b->T, m->dims.input_size, x_ring, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: window launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_step: window launch failed: %s", hipGetErrorString(e));
         hipEvent_t ev_a, ev_z;
         prof_pair(&ev_a, &ev_z);
         if (ev_a) (void)hipEventRecord(ev_a, (hipStream_t)stream);
         if (int rc = lstm_forward_impl(m, b->xwin, b->S, b->T, flags | diag_wt, nullptr, 0.0f, 0, b->y_new, stream, 0)) return rc;
         if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
     } else if (b->plan.shared_l0) {
-        if (!m->has_weights) return fail(APE_ERR_NOT_READY, "streams_step: weights not loaded");
-        if ((size_t)b->S * b->T > m->hseq_cap) return fail(APE_ERR_CAPACITY, "streams_step: the layer-0 sequence workspace is gone");
+        if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "streams_step: weights not loaded");
+        if ((size_t)b->S * b->T > m->hseq_cap) return ape_fail(APE_ERR_CAPACITY, "streams_step: the layer-0 sequence workspace is gone");
         const int H = m->dims.hidden_size, I = m->dims.input_size, O = m->dims.output_size;
         // (the cooperative routes were planned by ape_streams_set_mc; a later set_kernel(TILE16 / AUTO_GEN1 / CLUSTER) or set_precision --
         //  the documented ways to keep persistent clusters off a shared GPU -- sends the step to the batch-tile route like a replay)
@@ -1743,7 +1732,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
             const int clusters = xcd_class_clusters((b->S + 31) / 32, m->caps.cluster_capacity, xcd_classes_on(m, diag_wt), &classes);
             if (classes) c.flags |= APE_FLAG_XCD_CLASSES;
             e = ape_launch_lstm_cluster(H, 1, m->KX, 2, false, clusters, c, (hipStream_t)stream);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: layer-0 cluster launch failed: %s", hipGetErrorString(e));
+            if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_step: layer-0 cluster launch failed: %s", hipGetErrorString(e));
         } else if (a_form == BANK_A_SEQ32) {
             // launch A on the weight-stationary structure (lstm_upper32.hip, SEQ form): S streams in tiles of 32 on the clusters,
             // every step's output in the fragment order launch B's input builder reads
@@ -1756,7 +1745,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
             u.w = m->wcl32[0]; u.bias = m->bias[0];
             u.hseq = b->hfrag; u.hseq_bytes = ape_lower32_hseq_bytes(b->S, b->T);
             e = ape_launch_lstm_lower32(u, xq, m->caps.f16v2_capacity, (hipStream_t)stream);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: layer-0 cluster launch failed: %s", hipGetErrorString(e));
+            if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_step: layer-0 cluster launch failed: %s", hipGetErrorString(e));
         } else {
         // launch A: layer 0 alone over the S windows (first copy of every stream's ring), all steps -> [S,T,H]
         LstmParams a{};
@@ -1767,7 +1756,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         a.B = b->S; a.T = b->T; a.I = I; a.O = O; a.KX = m->KX; a.x_ring = x_ring;
         a.flags = flags & APE_FLAG_NORMALIZE_INPUT;
         e = ape_launch_lstm_tile16(H, 1, a, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: layer-0 launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_step: layer-0 launch failed: %s", hipGetErrorString(e));
         }
         // launch B: the layers above as an LSTM of their own over the S x n_mc sample rows; row r reads stream
         // r / n_mc's sequence under its own Philox mask (the counters of a fused launch over the same rows)
@@ -1802,10 +1791,10 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
                     m->last_kernel = "ape_lstm_upper128";
                     e = ape_launch_lstm_upper128(u, xq, m->b_out, b->y_new + (size_t)r0 * O, m->caps.up128_classes, (hipStream_t)stream, ev_a, ev_z);
                 }
-                if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: upper-layer cluster launch failed: %s", hipGetErrorString(e));
+                if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_step: upper-layer cluster launch failed: %s", hipGetErrorString(e));
             }
         } else {
-        if (b->inj_masks) return fail(APE_ERR_UNSUPPORTED, "streams_step: injected masks (test hook) on the batch-tile shared-layer-0 route");
+        if (b->inj_masks) return ape_fail(APE_ERR_UNSUPPORTED, "streams_step: injected masks (test hook) on the batch-tile shared-layer-0 route");
         LstmParams q{};
         const int LU = m->dims.num_layers - 1;
         q.x = m->hseq_ws; q.y = b->y_new;
@@ -1820,13 +1809,13 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
         m->last_kernel = "ape_lstm_tile16";
         e = ape_launch_lstm_tile16(H, LU, q, (hipStream_t)stream);
         if (ev_z) (void)hipEventRecord(ev_z, (hipStream_t)stream);
-        if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step: upper-layer launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_step: upper-layer launch failed: %s", hipGetErrorString(e));
         }
     } else if (bank_on_mc_small(b)) {
         // a few streams in Monte-Carlo mode (one estimator's frame: S = 1): the latency kernel reads the first copy of every
         // stream's window and deals the sample rows over the XCDs; from ape_streams_frame_host the feature builder rides in the same
         // launch as extra workgroups (`fuse`: the row has NOT been pushed by a launch of its own)
-        if (!m->has_weights) return fail(APE_ERR_NOT_READY, "streams_step: weights not loaded");
+        if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "streams_step: weights not loaded");
         McFrameParts fr{};
         if (fuse) fr = *fuse;
         hipEvent_t ev_a, ev_z;
@@ -1852,7 +1841,7 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
     b->last_post_form = ape_stream_post_form(q, q.part != nullptr && (!spread || b->post_spread != nullptr));
     hipError_t e = spread ? ape_launch_stream_post_spread(q, SpreadArgs{b->post_spread}, b->last_post_form, (hipStream_t)stream, b->bodies.dev)
                           : ape_launch_stream_post(q, (hipStream_t)stream, b->bodies.dev);      // (table mode: row s for stream s, q.body unread)
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_step launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_step launch failed: %s", hipGetErrorString(e));
     ++b->steps;
     journal_add(m, je);
     return APE_OK;
@@ -1863,50 +1852,41 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
 // datagram rows and the model's status word straight into pinned host memory: the frame holds no copy command, just the
 // step's kernels and one stream synchronisation.  An aborted cooperative launch is recovered here (ape_model_recover).
 // The frame call polls words the device writes into pinned memory (h_done, h_status) and reads h_out without a stream synchronisation:
-// the buffers are allocated COHERENT (fine-grained) and mapped explicitly -- with hipHostMallocDefault that property hangs on the
-// HIP_HOST_COHERENT environment variable, and non-coherent pinned memory shows the host a kernel's writes only at its end.
-#define APE_PINNED (hipHostMallocCoherent | hipHostMallocMapped)
+// the buffers are APE_PINNED (bank_host.h).
 static inline double now_us() {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
 int ape_streams_frame_host(ape_streams_t* b, int32_t kind, const float* rows_host, uint32_t flags, void* out_host,
                            int32_t out_dtype, void* stream) {
-    if (!b || !rows_host || !out_host) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: NULL argument");
-    if (b->per_stream) return fail(APE_ERR_NOT_READY, "streams_frame_host: the bank is in per-stream mode (subset frames); ape_streams_reset first");
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: unknown dtype selector");
+    if (!b || !rows_host || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "streams_frame_host: NULL argument");
+    if (b->per_stream) return ape_fail(APE_ERR_NOT_READY, "streams_frame_host: the bank is in per-stream mode (subset frames); ape_streams_reset first");
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "streams_frame_host: unknown dtype selector");
     if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_SPREAD))
-        return fail(APE_ERR_INVALID_ARG, "streams_frame_host: only NORMALIZE_INPUT and SPREAD are accepted");
+        return ape_fail(APE_ERR_INVALID_ARG, "streams_frame_host: only NORMALIZE_INPUT and SPREAD are accepted");
     int width, I;
-    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return fail(APE_ERR_INVALID_ARG, "streams_frame_host: unknown kind %d", kind);
+    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return ape_fail(APE_ERR_INVALID_ARG, "streams_frame_host: unknown kind %d", kind);
     ape_model* m = b->model;
-    HIP_TRY(hipSetDevice(m->dims.device));           // (the consumer thread of an estimator starts on device 0)
+    APE_TRY(hipSetDevice(m->dims.device));           // (the consumer thread of an estimator starts on device 0)
     const size_t N = (size_t)b->smooth * b->n_mc;
     const size_t rows_bytes = (size_t)b->S * width * sizeof(float);
     const size_t out_bytes = (size_t)b->S * (25 + 6 * N + ((flags & APE_FLAG_SPREAD) ? APE_SPREAD_WIDTH : 0)) *
                              (out_dtype == APE_F64 ? sizeof(double) : sizeof(float));
     if (rows_bytes > b->h_rows_bytes) {
-        if (b->h_rows) { HIP_TRY(hipHostFree(b->h_rows)); b->h_rows = nullptr; b->h_rows_bytes = 0; }
-        HIP_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, APE_PINNED));
+        if (b->h_rows) { APE_TRY(hipHostFree(b->h_rows)); b->h_rows = nullptr; b->h_rows_bytes = 0; }
+        APE_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, APE_PINNED));
         b->h_rows_bytes = rows_bytes;
     }
     if (out_bytes > b->h_out_bytes) {
-        if (b->h_out) { HIP_TRY(hipHostFree(b->h_out)); b->h_out = nullptr; b->h_out_bytes = 0; }
-        HIP_TRY(hipHostMalloc(&b->h_out, out_bytes, APE_PINNED));
+        if (b->h_out) { APE_TRY(hipHostFree(b->h_out)); b->h_out = nullptr; b->h_out_bytes = 0; }
+        APE_TRY(hipHostMalloc(&b->h_out, out_bytes, APE_PINNED));
         b->h_out_bytes = out_bytes;
     }
-    if (!b->h_status) {
-        HIP_TRY(hipHostMalloc((void**)&b->h_status, 64, APE_PINNED));
-        *b->h_status = 0u;
-    }
+    APE_TRY(ape_pinned_zeroed(&b->h_status, 64));
     // up to 64 streams: a word per stream that the post kernel's workgroup writes behind its outputs -- the host takes the frame when
     // all are there instead of waiting for the stream's completion signal to travel (a larger bank waits for the stream)
-    if (!b->h_done && b->S <= 64) {
-        HIP_TRY(hipHostMalloc((void**)&b->h_done, 64 * sizeof(unsigned), APE_PINNED));
-        memset(b->h_done, 0, 64 * sizeof(unsigned));
-    }
-    b->h_done_val += 1;
-    if (b->h_done_val == 0) b->h_done_val = 1;
+    if (b->S <= 64) APE_TRY(ape_pinned_zeroed(&b->h_done, 64 * sizeof(unsigned)));
+    ape_done_next(&b->h_done_val);
     const double t_begin = now_us();
     memcpy(b->h_rows, rows_host, rows_bytes);
     // (a sentinel, not zero: in the single-launch frame an aborted launch never reaches the tail that writes the word)
@@ -1928,29 +1908,21 @@ int ape_streams_frame_host(ape_streams_t* b, int32_t kind, const float* rows_hos
         if (int rc = streams_step_impl(b, flags | APE_FLAG_PACKED_MSG, b->h_out, nullptr, out_dtype, stream, b->h_status)) return rc;
     }
     const double t_launched = now_us();
-    bool seen = false, recovered = false;
-    if (b->h_done) {
-        // ~50 ms of looking (a frame is tens of microseconds; a launch that gives up takes seconds: the stream wait below covers it)
-        volatile unsigned* dw = b->h_done;
-        for (long spin = 0; spin < 20000000L && !seen; ++spin) {
-            seen = true;
-            for (int k = 0; k < b->S; ++k) seen = seen && dw[k] == b->h_done_val;
-            if (!seen) __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
+    // (a frame is tens of microseconds; a launch that gives up takes seconds: the stream wait below covers it)
+    const bool seen = b->h_done != nullptr && ape_done_wait(b->h_done, b->S, b->h_done_val);
+    bool recovered = false;
     const bool fell_through = !seen && b->h_done != nullptr;
-    if (!seen) HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    if (!seen) APE_TRY(hipStreamSynchronize((hipStream_t)stream));
     if (*(volatile unsigned*)b->h_status != 0u) {
         recovered = true;
-        HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+        APE_TRY(hipStreamSynchronize((hipStream_t)stream));
         // the regressor launch gave up (bounded spins): the step is still the bank's newest one, so it can be issued again on
         // the kernels that need no co-residency -- into the same pinned rows.  (Single-launch frame: the builder workgroup may not
         // have run; its row goes into the ring by the feature builder's own kernel first -- the same slot, the same values.)
         if (one_launch) {
             hipError_t e = ape_launch_parse_rows(b->h_rows, b->S, width, kind & ~APE_PARSE_BIG_ENDIAN, slot_out, APE_F32, I, (size_t)bank_copies(b) * b->T * I,
                                                  slot_rep, slot_rep_stride, (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0, (hipStream_t)stream);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_host: feature builder launch failed: %s", hipGetErrorString(e));
+            if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_frame_host: feature builder launch failed: %s", hipGetErrorString(e));
         }
         if (int rc = ape_model_recover(m)) return rc;
     } else {
@@ -1971,13 +1943,13 @@ int ape_streams_frame_host(ape_streams_t* b, int32_t kind, const float* rows_hos
 }
 
 int ape_streams_last_post_form(ape_streams_t* b, int32_t* form) {
-    if (!b || !form) return fail(APE_ERR_INVALID_ARG, "streams_last_post_form: NULL argument");
+    if (!b || !form) return ape_fail(APE_ERR_INVALID_ARG, "streams_last_post_form: NULL argument");
     *form = b->last_post_form;
     return APE_OK;
 }
 
 int ape_streams_frame_stats(ape_streams_t* b, ape_frame_stats_t* out, float* trace_us, int32_t capacity_frames, int32_t* n_out, int32_t reset) {
-    if (!b || !out) return fail(APE_ERR_INVALID_ARG, "streams_frame_stats: NULL argument");
+    if (!b || !out) return ape_fail(APE_ERR_INVALID_ARG, "streams_frame_stats: NULL argument");
     out->frames = b->fs_frames; out->fallback_syncs = b->fs_fallback; out->recovered = b->fs_recovered;
     int32_t n = 0;
     if (trace_us && capacity_frames > 0 && !b->fs_trace.empty()) {
@@ -1994,11 +1966,11 @@ int ape_streams_frame_stats(ape_streams_t* b, ape_frame_stats_t* out, float* tra
 }
 
 int ape_streams_profile(ape_streams_t* b, int32_t enable) {
-    if (!b) return fail(APE_ERR_INVALID_ARG, "streams_profile: NULL bank");
-    HIP_TRY(hipSetDevice(b->model->dims.device));
+    if (!b) return ape_fail(APE_ERR_INVALID_ARG, "streams_profile: NULL bank");
+    APE_TRY(hipSetDevice(b->model->dims.device));
     if (enable && b->prof_ev.empty()) {
         b->prof_ev.resize(512, nullptr);
-        for (auto& ev : b->prof_ev) HIP_TRY(hipEventCreate(&ev));
+        for (auto& ev : b->prof_ev) APE_TRY(hipEventCreate(&ev));
     }
     b->prof_on = enable != 0;
     b->prof_n = 0;
@@ -2006,12 +1978,12 @@ int ape_streams_profile(ape_streams_t* b, int32_t enable) {
 }
 
 int ape_streams_profile_read(ape_streams_t* b, double* kernel_ms_sum, int32_t* launches) {
-    if (!b || !kernel_ms_sum || !launches) return fail(APE_ERR_INVALID_ARG, "streams_profile_read: NULL argument");
+    if (!b || !kernel_ms_sum || !launches) return ape_fail(APE_ERR_INVALID_ARG, "streams_profile_read: NULL argument");
     double sum = 0.0;
     for (int i = 0; i < b->prof_n; ++i) {
-        HIP_TRY(hipEventSynchronize(b->prof_ev[2 * i + 1]));
+        APE_TRY(hipEventSynchronize(b->prof_ev[2 * i + 1]));
         float ms = 0.0f;
-        HIP_TRY(hipEventElapsedTime(&ms, b->prof_ev[2 * i], b->prof_ev[2 * i + 1]));
+        APE_TRY(hipEventElapsedTime(&ms, b->prof_ev[2 * i], b->prof_ev[2 * i + 1]));
         sum += ms;
     }
     *kernel_ms_sum = sum; *launches = b->prof_n;
@@ -2025,24 +1997,9 @@ int ape_streams_profile_read(ape_streams_t* b, double* kernel_ms_sum, int32_t* l
 // (lstm_forward_impl, x_ring = 0: every route applies), the indexed post-filter.  Window slot, stack slot and cold flags come from
 // per-stream counters on the host (per-stream mode), sent as one descriptor per entry.
 
-// validates a list of K stream indices of the bank: in range, distinct
-static int subset_check_list(const ape_streams* b, const int32_t* streams_host, int32_t K, const char* what) {
-    if (K < 0 || K > b->S) return fail(APE_ERR_INVALID_ARG, "%s: K=%d outside [0, S=%d]", what, K, b->S);
-    std::vector<char> seen((size_t)b->S, 0);
-    for (int j = 0; j < K; ++j) {
-        const int s = streams_host[j];
-        if (s < 0 || s >= b->S) return fail(APE_ERR_INVALID_ARG, "%s: stream index %d (entry %d) outside [0, %d)", what, s, j, b->S);
-        if (seen[s]) return fail(APE_ERR_INVALID_ARG, "%s: stream %d listed twice", what, s);
-        seen[s] = 1;
-    }
-    return APE_OK;
-}
-
 // the pinned descriptor ring of the subset frames and the state hand-over, on first use
 static int subset_stage_alloc(ape_streams* b) {
-    if (b->sub_stage) return APE_OK;
-    HIP_TRY(hipHostMalloc((void**)&b->sub_stage, (size_t)APE_SUBSET_STAGES * b->S * sizeof(SubsetDesc), hipHostMallocDefault));
-    for (int i = 0; i < APE_SUBSET_STAGES; ++i) HIP_TRY(hipEventCreateWithFlags(&b->sub_ev[i], hipEventDisableTiming));
+    if (!b->sub_stage.on()) APE_TRY(b->sub_stage.alloc(b->S, sizeof(SubsetDesc)));
     return APE_OK;
 }
 
@@ -2055,8 +2012,8 @@ static void subset_enter(ape_streams* b) {
 }
 
 int ape_streams_reset_subset(ape_streams_t* b, const int32_t* streams_host, int32_t K) {
-    if (!b || !streams_host) return fail(APE_ERR_INVALID_ARG, "streams_reset_subset: NULL argument");
-    if (int rc = subset_check_list(b, streams_host, K, "streams_reset_subset")) return rc;
+    if (!b || !streams_host) return ape_fail(APE_ERR_INVALID_ARG, "streams_reset_subset: NULL argument");
+    if (int rc = ape_check_stream_list("streams_reset_subset", streams_host, K, b->S, false)) return rc;
     if (K == 0) return APE_OK;
     subset_enter(b);
     for (int j = 0; j < K; ++j) { b->s_frames[streams_host[j]] = 0; b->s_steps[streams_host[j]] = 0; }
@@ -2094,32 +2051,30 @@ static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_
                        ? ape_launch_stream_post_subset_spread(q, b->sub_desc, SpreadArgs{b->post_spread}, b->last_post_form, (hipStream_t)stream,
                                                               b->bodies.dev)
                        : ape_launch_stream_post_subset(q, b->sub_desc, (hipStream_t)stream, b->bodies.dev);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "%s: post-filter launch failed: %s", hw.what, hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: post-filter launch failed: %s", hw.what, hipGetErrorString(e));
     return APE_OK;
 }
 
 // what both subset entries check before anything is launched or counted; `what` names the entry
 static int subset_frame_check(ape_streams* b, int32_t kind, const void* rows, const int32_t* streams_host, int32_t K, uint32_t flags, const void* out,
                               int32_t out_dtype, void* stream, const char* what, int* width_out, int* I_out) {
-    if (!b || !rows || !streams_host || !out) return fail(APE_ERR_INVALID_ARG, "%s: NULL argument", what);
-    if (int rc = subset_check_list(b, streams_host, K, what)) return rc;
+    if (!b || !rows || !streams_host || !out) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", what);
+    if (int rc = ape_check_stream_list(what, streams_host, K, b->S, false)) return rc;
     int width, I;
-    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return fail(APE_ERR_INVALID_ARG, "%s: unknown kind %d", what, kind);
+    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown kind %d", what, kind);
     ape_model* m = b->model;
     if (I != m->dims.input_size)
-        return fail(APE_ERR_INVALID_ARG, "%s: kind %d builds %d features, the model takes %d", what, kind & ~APE_PARSE_BIG_ENDIAN, I, m->dims.input_size);
+        return ape_fail(APE_ERR_INVALID_ARG, "%s: kind %d builds %d features, the model takes %d", what, kind & ~APE_PARSE_BIG_ENDIAN, I, m->dims.input_size);
     if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG | APE_FLAG_SPREAD))
-        return fail(APE_ERR_INVALID_ARG, "%s: only NORMALIZE_INPUT, PACKED_MSG and SPREAD are accepted", what);
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "%s: unknown dtype selector", what);
+        return ape_fail(APE_ERR_INVALID_ARG, "%s: only NORMALIZE_INPUT, PACKED_MSG and SPREAD are accepted", what);
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown dtype selector", what);
     if (!b->xring || !b->yring || (m->dims.model_kind == APE_MODEL_FF && !b->ffhid))
-        return fail(APE_ERR_NOT_READY, "%s: the bank lost its rings in a failed ape_streams_set_mc", what);
-    if ((flags & APE_FLAG_NORMALIZE_INPUT) && !m->has_stats) return fail(APE_ERR_NOT_READY, "%s: NORMALIZE_INPUT without norm stats", what);
-    if (!m->has_weights) return fail(APE_ERR_NOT_READY, "%s: weights not loaded", what);
-    if (b->inj_masks) return fail(APE_ERR_UNSUPPORTED, "%s: injected masks (test hook) are indexed by the lockstep rows", what);
-    HIP_TRY(hipSetDevice(m->dims.device));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "%s: the stream is capturing (the descriptors are staged per call)", what);
+        return ape_fail(APE_ERR_NOT_READY, "%s: the bank lost its rings in a failed ape_streams_set_mc", what);
+    if ((flags & APE_FLAG_NORMALIZE_INPUT) && !m->has_stats) return ape_fail(APE_ERR_NOT_READY, "%s: NORMALIZE_INPUT without norm stats", what);
+    if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "%s: weights not loaded", what);
+    if (b->inj_masks) return ape_fail(APE_ERR_UNSUPPORTED, "%s: injected masks (test hook) are indexed by the lockstep rows", what);
+    APE_TRY(hipSetDevice(m->dims.device));
+    if (int rc = ape_check_not_capturing((hipStream_t)stream, what, "the descriptors are staged per call")) return rc;
     *width_out = width; *I_out = I;
     return APE_OK;
 }
@@ -2128,9 +2083,9 @@ static int subset_frame_check(ape_streams* b, int32_t kind, const void* rows, co
 static int subset_workspace(ape_streams* b, int I) {
     if (b->sub_n_mc == b->n_mc && b->sub_x) return APE_OK;
     subset_free(b);
-    HIP_TRY(hipMalloc((void**)&b->sub_x, (size_t)b->S * bank_copies(b) * b->T * I * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&b->sub_y, (size_t)b->S * b->n_mc * b->model->dims.output_size * sizeof(float)));
-    HIP_TRY(hipMalloc((void**)&b->sub_desc, (size_t)b->S * sizeof(SubsetDesc)));
+    APE_TRY(hipMalloc((void**)&b->sub_x, (size_t)b->S * bank_copies(b) * b->T * I * sizeof(float)));
+    APE_TRY(hipMalloc((void**)&b->sub_y, (size_t)b->S * b->n_mc * b->model->dims.output_size * sizeof(float)));
+    APE_TRY(hipMalloc((void**)&b->sub_desc, (size_t)b->S * sizeof(SubsetDesc)));
     b->sub_n_mc = b->n_mc;
     return APE_OK;
 }
@@ -2172,19 +2127,17 @@ int ape_streams_frame_subset(ape_streams_t* b, int32_t kind, const float* rows_d
     if (int rc = subset_stage_alloc(b)) return rc;
     subset_enter(b);
     // the descriptors into the next pinned slot -- once the copy that last read it has completed (frames go back to back, no host sync)
-    const int k = b->sub_next;
-    HIP_TRY(hipEventSynchronize(b->sub_ev[k]));
-    SubsetDesc* h = b->sub_stage + (size_t)k * b->S;
+    hipError_t slot_wait;
+    SubsetDesc* h = static_cast<SubsetDesc*>(b->sub_stage.take(&slot_wait));
+    APE_TRY(slot_wait);
     subset_fill_desc(b, streams_host, K, h);
-    HIP_TRY(hipMemcpyAsync(b->sub_desc, h, (size_t)K * sizeof(SubsetDesc), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(b->sub_ev[k], st));
-    b->sub_next = (k + 1) % APE_SUBSET_STAGES;
+    APE_TRY(b->sub_stage.send(b->sub_desc, (size_t)K * sizeof(SubsetDesc), st));
     SubsetRowsParams rp{};
     rp.rows = rows_dev; rp.desc = b->sub_desc; rp.xring = b->xring; rp.xw = b->sub_x;
     rp.K = K; rp.width = width; rp.kind = kind & ~APE_PARSE_BIG_ENDIAN; rp.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0; rp.T = b->T; rp.I = I;
     rp.n_mc = bank_copies(b);
     hipError_t e = ape_launch_subset_rows(rp, st);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset: row launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_frame_subset: row launch failed: %s", hipGetErrorString(e));
     // the rows are in the rings: the counters move on whatever the regressor does (a failed launch is reported, the rows stay pushed)
     for (int j = 0; j < K; ++j) { b->s_frames[streams_host[j]] += 1; b->s_steps[streams_host[j]] += 1; }
     const unsigned long long mc_call = b->mc_calls++;
@@ -2205,7 +2158,7 @@ int ape_streams_frame_subset_host(ape_streams_t* b, int32_t kind, const float* r
     int width, I;
     if (int rc = subset_frame_check(b, kind, rows_host, streams_host, K, flags, out_host, out_dtype, stream, "streams_frame_subset_host", &width, &I))
         return rc;
-    if (width > SUBSET_HOST_ROW_MAX) return fail(APE_ERR_UNSUPPORTED, "streams_frame_subset_host: rows of %d columns", width);
+    if (width > SUBSET_HOST_ROW_MAX) return ape_fail(APE_ERR_UNSUPPORTED, "streams_frame_subset_host: rows of %d columns", width);
     const hipStream_t st = (hipStream_t)stream;
     if (K == 0) return APE_OK;
     ape_model* m = b->model;
@@ -2214,27 +2167,19 @@ int ape_streams_frame_subset_host(ape_streams_t* b, int32_t kind, const float* r
     const bool packed = (flags & APE_FLAG_PACKED_MSG) != 0 && N > 1;
     const size_t row_w = (packed ? 25 + 6 * N : 25) + ((flags & APE_FLAG_SPREAD) ? APE_SPREAD_WIDTH : 0);
     const size_t esz = out_dtype == APE_F64 ? sizeof(double) : sizeof(float);
-    if (!b->hs_block) {
-        const size_t bytes = 64 * sizeof(unsigned) + (size_t)b->S * sizeof(SubsetDesc) + (size_t)b->S * SUBSET_HOST_ROW_MAX * sizeof(float);
-        HIP_TRY(hipHostMalloc((void**)&b->hs_block, bytes, APE_PINNED));
-        memset(b->hs_block, 0, bytes);
-    }
+    APE_TRY(ape_pinned_zeroed(&b->hs_block, 64 * sizeof(unsigned) + (size_t)b->S * sizeof(SubsetDesc) + (size_t)b->S * SUBSET_HOST_ROW_MAX * sizeof(float)));
     const size_t out_cap = (size_t)b->S * row_w * esz;          // (sized for K = S, so that the buffer settles with the first frame of a kind)
     if (out_cap > b->h_out_bytes) {
-        if (b->h_out) { HIP_TRY(hipHostFree(b->h_out)); b->h_out = nullptr; b->h_out_bytes = 0; }
-        HIP_TRY(hipHostMalloc(&b->h_out, out_cap, APE_PINNED));
+        if (b->h_out) { APE_TRY(hipHostFree(b->h_out)); b->h_out = nullptr; b->h_out_bytes = 0; }
+        APE_TRY(hipHostMalloc(&b->h_out, out_cap, APE_PINNED));
         b->h_out_bytes = out_cap;
     }
-    if (!b->h_status) {
-        HIP_TRY(hipHostMalloc((void**)&b->h_status, 64, APE_PINNED));
-        *b->h_status = 0u;
-    }
+    APE_TRY(ape_pinned_zeroed(&b->h_status, 64));
     unsigned* const h_done = reinterpret_cast<unsigned*>(b->hs_block);
     SubsetDesc* const h_desc = reinterpret_cast<SubsetDesc*>(b->hs_block + 64 * sizeof(unsigned));
     float* const h_rows = reinterpret_cast<float*>(b->hs_block + 64 * sizeof(unsigned) + (size_t)b->S * sizeof(SubsetDesc));
     const bool words = K <= 64;                                  // a word per entry the host can watch; a longer list waits for the stream
-    b->hs_done_val += 1;
-    if (b->hs_done_val == 0) b->hs_done_val = 1;
+    ape_done_next(&b->hs_done_val);
     subset_enter(b);
     const double t_begin = now_us();
     memcpy(h_rows, rows_host, (size_t)K * width * sizeof(float));
@@ -2245,7 +2190,7 @@ int ape_streams_frame_subset_host(ape_streams_t* b, int32_t kind, const float* r
     rp.K = K; rp.width = width; rp.kind = kind & ~APE_PARSE_BIG_ENDIAN; rp.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0; rp.T = b->T; rp.I = I;
     rp.n_mc = bank_copies(b);
     hipError_t e = ape_launch_subset_rows_host(rp, b->sub_desc, st);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "streams_frame_subset_host: row launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_frame_subset_host: row launch failed: %s", hipGetErrorString(e));
     for (int j = 0; j < K; ++j) { b->s_frames[streams_host[j]] += 1; b->s_steps[streams_host[j]] += 1; }
     const unsigned long long mc_call = b->mc_calls++;
     SubsetHostWords hw;
@@ -2256,24 +2201,15 @@ int ape_streams_frame_subset_host(ape_streams_t* b, int32_t kind, const float* r
     }
     subset_journal(b, K, flags, b->h_out, out_dtype, stream, mc_call);
     const double t_launched = now_us();
-    bool seen = false, recovered = false;
-    if (words) {
-        // ~50 ms of looking, then the stream's own completion (as ape_streams_frame_host)
-        volatile unsigned* dw = h_done;
-        for (long spin = 0; spin < 20000000L && !seen; ++spin) {
-            seen = true;
-            for (int k = 0; k < K; ++k) seen = seen && dw[k] == b->hs_done_val;
-            if (!seen) __builtin_ia32_pause();
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-    }
+    const bool seen = words && ape_done_wait(h_done, K, b->hs_done_val);   // else the stream's own completion (as ape_streams_frame_host)
+    bool recovered = false;
     const bool fell_through = !seen && words;
-    if (!seen) HIP_TRY(hipStreamSynchronize(st));
+    if (!seen) APE_TRY(hipStreamSynchronize(st));
     if (*(volatile unsigned*)b->h_status != 0u) {
         // the regressor launch gave up (bounded spins): the frame is the bank's newest, its windows and descriptors are on the device --
         // regressor and post-filter again on the kernels that need no co-residency, into the same pinned rows
         recovered = true;
-        HIP_TRY(hipStreamSynchronize(st));
+        APE_TRY(hipStreamSynchronize(st));
         if (int rc = ape_model_recover(m)) return rc;
     } else {
         journal_clear(m);                                        // (read behind the frame's kernels on the frame's stream: what the journal holds is done)
@@ -2301,7 +2237,7 @@ static void state_desc_of(const ape_streams* b, ape_stream_state_desc_t* d) {
 }
 
 int ape_streams_state_desc(ape_streams_t* b, ape_stream_state_desc_t* out) {
-    if (!b || !out) return fail(APE_ERR_INVALID_ARG, "streams_state_desc: NULL argument");
+    if (!b || !out) return ape_fail(APE_ERR_INVALID_ARG, "streams_state_desc: NULL argument");
     state_desc_of(b, out);
     return APE_OK;
 }
@@ -2309,16 +2245,14 @@ int ape_streams_state_desc(ape_streams_t* b, ape_stream_state_desc_t* out) {
 // the K descriptors `h` (next pinned slot, already filled by `fill`) to the device, then one launch
 extern "C++" template <typename Fill>
 static int state_launch(ape_streams* b, const char* what, int K, float* state, hipStream_t st, bool import, Fill fill) {
-    if (!b->state_desc) HIP_TRY(hipMalloc((void**)&b->state_desc, (size_t)b->S * sizeof(StateDesc)));
+    if (!b->state_desc) APE_TRY(hipMalloc((void**)&b->state_desc, (size_t)b->S * sizeof(StateDesc)));
     if (int rc = subset_stage_alloc(b)) return rc;
     static_assert(sizeof(StateDesc) <= sizeof(SubsetDesc), "a pinned slot holds S descriptors of either kind");
-    const int k = b->sub_next;
-    HIP_TRY(hipEventSynchronize(b->sub_ev[k]));          // (the copy that read this slot APE_SUBSET_STAGES calls ago)
-    StateDesc* h = reinterpret_cast<StateDesc*>(b->sub_stage + (size_t)k * b->S);
+    hipError_t slot_wait;
+    StateDesc* h = static_cast<StateDesc*>(b->sub_stage.take(&slot_wait));     // (waits for the copy that read this slot APE_DESC_STAGES calls ago)
+    APE_TRY(slot_wait);
     for (int j = 0; j < K; ++j) fill(j, h[j]);
-    HIP_TRY(hipMemcpyAsync(b->state_desc, h, (size_t)K * sizeof(StateDesc), hipMemcpyHostToDevice, st));
-    HIP_TRY(hipEventRecord(b->sub_ev[k], st));
-    b->sub_next = (k + 1) % APE_SUBSET_STAGES;
+    APE_TRY(b->sub_stage.send(b->state_desc, (size_t)K * sizeof(StateDesc), st));
     ape_stream_state_desc_t d;
     state_desc_of(b, &d);
     StateParams p{};
@@ -2326,21 +2260,18 @@ static int state_launch(ape_streams* b, const char* what, int K, float* state, h
     p.x_stream_stride = (size_t)bank_copies(b) * d.T * d.I;
     p.K = K; p.T = d.T; p.I = d.I; p.smooth = d.smooth; p.MO = d.n_mc * d.O; p.words = d.words_per_stream;
     const hipError_t e = import ? ape_launch_state_import(p, st) : ape_launch_state_export(p, st);
-    if (e != hipSuccess) return fail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
     return APE_OK;
 }
 
 static int state_check_call(ape_streams* b, const int32_t* streams_host, int32_t K, const void* state_dev, const void* warm_host, void* stream,
                             const char* what) {
-    if (!b || !streams_host || !state_dev || !warm_host) return fail(APE_ERR_INVALID_ARG, "%s: NULL argument", what);
-    if (int rc = subset_check_list(b, streams_host, K, what)) return rc;
-    if (((uintptr_t)state_dev & 15u) != 0) return fail(APE_ERR_INVALID_ARG, "%s: state_dev must be 16-byte aligned", what);
-    if (!b->xring || !b->yring) return fail(APE_ERR_NOT_READY, "%s: the bank lost its rings in a failed ape_streams_set_mc", what);
-    HIP_TRY(hipSetDevice(b->model->dims.device));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "%s: the stream is capturing (the descriptors are staged per call)", what);
-    return APE_OK;
+    if (!b || !streams_host || !state_dev || !warm_host) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", what);
+    if (int rc = ape_check_stream_list(what, streams_host, K, b->S, false)) return rc;
+    if (((uintptr_t)state_dev & 15u) != 0) return ape_fail(APE_ERR_INVALID_ARG, "%s: state_dev must be 16-byte aligned", what);
+    if (!b->xring || !b->yring) return ape_fail(APE_ERR_NOT_READY, "%s: the bank lost its rings in a failed ape_streams_set_mc", what);
+    APE_TRY(hipSetDevice(b->model->dims.device));
+    return ape_check_not_capturing((hipStream_t)stream, what, "the descriptors are staged per call");
 }
 
 int ape_streams_export(ape_streams_t* b, const int32_t* streams_host, int32_t K, void* state_dev, uint8_t* warm_host, void* stream) {
@@ -2360,13 +2291,13 @@ int ape_streams_export(ape_streams_t* b, const int32_t* streams_host, int32_t K,
 
 int ape_streams_import(ape_streams_t* b, const ape_stream_state_desc_t* desc, const int32_t* streams_host, int32_t K,
                        const void* state_dev, const uint8_t* warm_host, void* stream) {
-    if (!desc) return fail(APE_ERR_INVALID_ARG, "streams_import: NULL argument");
+    if (!desc) return ape_fail(APE_ERR_INVALID_ARG, "streams_import: NULL argument");
     if (int rc = state_check_call(b, streams_host, K, state_dev, warm_host, stream, "streams_import")) return rc;
     ape_stream_state_desc_t own;
     state_desc_of(b, &own);
     if (desc->version != own.version || desc->T != own.T || desc->I != own.I || desc->smooth != own.smooth || desc->n_mc != own.n_mc ||
         desc->O != own.O || desc->words_per_stream != own.words_per_stream)
-        return fail(APE_ERR_INVALID_ARG, "streams_import: the records are {v%d T=%d I=%d smooth=%d n_mc=%d O=%d words=%d}, the bank's {v%d T=%d I=%d smooth=%d n_mc=%d O=%d words=%d}",
+        return ape_fail(APE_ERR_INVALID_ARG, "streams_import: the records are {v%d T=%d I=%d smooth=%d n_mc=%d O=%d words=%d}, the bank's {v%d T=%d I=%d smooth=%d n_mc=%d O=%d words=%d}",
                     desc->version, desc->T, desc->I, desc->smooth, desc->n_mc, desc->O, desc->words_per_stream, own.version, own.T, own.I,
                     own.smooth, own.n_mc, own.O, own.words_per_stream);
     if (K == 0) return APE_OK;
@@ -2457,57 +2388,49 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
                        void* out_dev, int32_t out_dtype, float* y_dev, int32_t max_rows_per_launch, void* stream, const double* bodies_host,
                        bool any_regressor, const ApeReplayResume* rs) {
     // the arguments on their own first (no device needed to refuse them)
-    if (!rows_dev || !out_dev) return fail(APE_ERR_INVALID_ARG, "replay: NULL argument");
+    if (!rows_dev || !out_dev) return ape_fail(APE_ERR_INVALID_ARG, "replay: NULL argument");
     int width, I;
     const int big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
-    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return fail(APE_ERR_INVALID_ARG, "replay: unknown kind %d", kind);
-    if (F < 1) return fail(APE_ERR_INVALID_ARG, "replay: F=%d must be >= 1", F);
-    if (R < 1 || R > F) return fail(APE_ERR_INVALID_ARG, "replay: %d recording starts for %d frames (1 <= R <= F)", R, F);
-    if (!seg_starts_host) return fail(APE_ERR_INVALID_ARG, "replay: NULL seg_starts");
-    if (seg_starts_host[0] != 0) return fail(APE_ERR_INVALID_ARG, "replay: seg_starts[0] = %d, must be 0", seg_starts_host[0]);
-    for (int i = 1; i < R; ++i)
-        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
-            return fail(APE_ERR_INVALID_ARG, "replay: seg_starts[%d] = %d (strictly rising, below F = %d)", i, seg_starts_host[i], F);
-    if (seq_len < 1) return fail(APE_ERR_INVALID_ARG, "replay: seq_len=%d must be >= 1", seq_len);
-    if (smooth < 1 || smooth > 64) return fail(APE_ERR_UNSUPPORTED, "replay: smooth %d outside 1..64", smooth);
+    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return ape_fail(APE_ERR_INVALID_ARG, "replay: unknown kind %d", kind);
+    if (int rc = ape_check_segments("replay", F, seg_starts_host, R)) return rc;
+    if (seq_len < 1) return ape_fail(APE_ERR_INVALID_ARG, "replay: seq_len=%d must be >= 1", seq_len);
+    if (smooth < 1 || smooth > 64) return ape_fail(APE_ERR_UNSUPPORTED, "replay: smooth %d outside 1..64", smooth);
     if (n_mc < 1 || (long long)n_mc * smooth > 4096)
-        return fail(APE_ERR_INVALID_ARG, "replay: n_mc=%d with smooth=%d (1 <= smooth*n_mc <= 4096)", n_mc, smooth);
-    if ((long long)F * n_mc >= (1ll << 31)) return fail(APE_ERR_UNSUPPORTED, "replay: F*n_mc = %lld sample rows (< 2^31)", (long long)F * n_mc);
-    if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return fail(APE_ERR_INVALID_ARG, "replay: dropout_p %g outside [0,1)", (double)dropout_p);
+        return ape_fail(APE_ERR_INVALID_ARG, "replay: n_mc=%d with smooth=%d (1 <= smooth*n_mc <= 4096)", n_mc, smooth);
+    if ((long long)F * n_mc >= (1ll << 31)) return ape_fail(APE_ERR_UNSUPPORTED, "replay: F*n_mc = %lld sample rows (< 2^31)", (long long)F * n_mc);
+    if (!(dropout_p >= 0.0f && dropout_p < 1.0f)) return ape_fail(APE_ERR_INVALID_ARG, "replay: dropout_p %g outside [0,1)", (double)dropout_p);
     if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_PACKED_MSG | APE_FLAG_SPREAD))
-        return fail(APE_ERR_INVALID_ARG, "replay: only NORMALIZE_INPUT, PACKED_MSG and SPREAD are accepted");
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return fail(APE_ERR_INVALID_ARG, "replay: unknown dtype selector");
+        return ape_fail(APE_ERR_INVALID_ARG, "replay: only NORMALIZE_INPUT, PACKED_MSG and SPREAD are accepted");
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "replay: unknown dtype selector");
     if (max_rows_per_launch < 0 || (max_rows_per_launch > 0 && max_rows_per_launch < 16))
-        return fail(APE_ERR_INVALID_ARG, "replay: max_rows_per_launch=%d (0 = default, else >= 16)", max_rows_per_launch);
+        return ape_fail(APE_ERR_INVALID_ARG, "replay: max_rows_per_launch=%d (0 = default, else >= 16)", max_rows_per_launch);
     const bool carry_in = rs && rs->state_in, keep_out = rs && rs->state_out;
     const long long pbase = rs ? (long long)rs->sample_row_base : 0;
-    if (carry_in && !rs->warm_in) return fail(APE_ERR_INVALID_ARG, "replay_resume: state_in without warm_in");
-    if (keep_out && !rs->warm_out) return fail(APE_ERR_INVALID_ARG, "replay_resume: state_out without warm_out");
+    if (carry_in && !rs->warm_in) return ape_fail(APE_ERR_INVALID_ARG, "replay_resume: state_in without warm_in");
+    if (keep_out && !rs->warm_out) return ape_fail(APE_ERR_INVALID_ARG, "replay_resume: state_out without warm_out");
     if (rs && (((uintptr_t)rs->state_in | (uintptr_t)rs->state_out) & 15u) != 0)
-        return fail(APE_ERR_INVALID_ARG, "replay_resume: state buffers must be 16-byte aligned");
+        return ape_fail(APE_ERR_INVALID_ARG, "replay_resume: state buffers must be 16-byte aligned");
     if (pbase < 0 || pbase + (long long)F * n_mc >= (1ll << 31))
-        return fail(APE_ERR_INVALID_ARG, "replay_resume: sample_row_base %lld (base + F*n_mc < 2^31)", pbase);
-    if (!m) return fail(ape_device_count() == 0 ? APE_ERR_NO_DEVICE : APE_ERR_INVALID_ARG,
+        return ape_fail(APE_ERR_INVALID_ARG, "replay_resume: sample_row_base %lld (base + F*n_mc < 2^31)", pbase);
+    if (!m) return ape_fail(ape_device_count() == 0 ? APE_ERR_NO_DEVICE : APE_ERR_INVALID_ARG,
                         "replay: NULL model (no gfx950 device: there is no CPU fallback)");
     // ... then against the model
     if (m->dims.model_kind != APE_MODEL_LSTM && !any_regressor)
-        return fail(APE_ERR_UNSUPPORTED, "replay: LSTM estimator models only (not FF / ImuPose: ape_replay_regressor serves those)");
+        return ape_fail(APE_ERR_UNSUPPORTED, "replay: LSTM estimator models only (not FF / ImuPose: ape_replay_regressor serves those)");
     const bool is_ff = m->dims.model_kind == APE_MODEL_FF, is_imu = m->dims.model_kind == APE_MODEL_IMUPOSE;
     if (is_imu) { n_mc = 1; dropout_p = 0.0f; }            // the reference ignores the sample count and has no dropout mode
-    if (m->dims.target_layout == APE_LAYOUT_NONE) return fail(APE_ERR_INVALID_ARG, "replay: model has no target layout");
-    if (m->precision != APE_PRECISION_F32) return fail(APE_ERR_UNSUPPORTED, "replay: fp16 precision is set on the model (float32 only)");
+    if (m->dims.target_layout == APE_LAYOUT_NONE) return ape_fail(APE_ERR_INVALID_ARG, "replay: model has no target layout");
+    if (m->precision != APE_PRECISION_F32) return ape_fail(APE_ERR_UNSUPPORTED, "replay: fp16 precision is set on the model (float32 only)");
     if (I != m->dims.input_size)
-        return fail(APE_ERR_INVALID_ARG, "replay: kind %d builds %d features, the model takes %d", kind & ~APE_PARSE_BIG_ENDIAN, I, m->dims.input_size);
-    if (!m->has_weights) return fail(APE_ERR_NOT_READY, "replay: weights not loaded");
+        return ape_fail(APE_ERR_INVALID_ARG, "replay: kind %d builds %d features, the model takes %d", kind & ~APE_PARSE_BIG_ENDIAN, I, m->dims.input_size);
+    if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "replay: weights not loaded");
     const bool norm = (flags & APE_FLAG_NORMALIZE_INPUT) != 0;
-    if (norm && !m->has_stats) return fail(APE_ERR_NOT_READY, "replay: NORMALIZE_INPUT without norm stats");
+    if (norm && !m->has_stats) return ape_fail(APE_ERR_NOT_READY, "replay: NORMALIZE_INPUT without norm stats");
     // (the LSTM kernels draw their masks per group of 4 rows; without dropout the base is not read)
     if (dropout_p > 0.0f && m->dims.num_layers > 1 && !is_ff && pbase % 4 != 0)
-        return fail(APE_ERR_INVALID_ARG, "replay_resume: sample_row_base %lld must be a multiple of 4 with dropout on", pbase);
-    HIP_TRY(hipSetDevice(m->dims.device));
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    HIP_TRY(hipStreamIsCapturing((hipStream_t)stream, &cap));
-    if (cap != hipStreamCaptureStatusNone) return fail(APE_ERR_INVALID_ARG, "replay: blocking call on a capturing stream");
+        return ape_fail(APE_ERR_INVALID_ARG, "replay_resume: sample_row_base %lld must be a multiple of 4 with dropout on", pbase);
+    APE_TRY(hipSetDevice(m->dims.device));
+    if (int rc = ape_check_not_capturing((hipStream_t)stream, "replay", nullptr)) return rc;
     // what was issued on the handle before is healthy (and off the journal) before the replay's launches follow it
     if (int rc = ape_model_recover(m)) return rc;
 
@@ -2528,21 +2451,21 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
     float *xx, *xw = nullptr, *yws = nullptr, *ffhid = nullptr;
     int *starts_d, *seg_of;
     double* est[2];
-    HIP_TRY(ws.alloc((void**)&xx, (size_t)F * I * sizeof(float)));
-    HIP_TRY(ws.alloc((void**)&seg_of, (size_t)F * sizeof(int)));
-    HIP_TRY(ws.alloc((void**)&starts_d, (size_t)R * sizeof(int)));
-    if (!is_ff) HIP_TRY(ws.alloc((void**)&xw, (size_t)rmax * T * I * sizeof(float)));
-    else HIP_TRY(ws.alloc((void**)&ffhid, (size_t)(rmax / n_mc + 2) * m->dims.hidden_size * sizeof(float)));
-    if (!y_dev) HIP_TRY(ws.alloc((void**)&yws, (size_t)rmax * O * sizeof(float)));
-    HIP_TRY(ws.alloc((void**)&est[0], (size_t)(carry + rmax) * W * sizeof(double)));
-    HIP_TRY(ws.alloc((void**)&est[1], (size_t)(carry + rmax) * W * sizeof(double)));
-    HIP_TRY(hipMemcpyAsync(starts_d, seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st));
+    APE_TRY(ws.alloc((void**)&xx, (size_t)F * I * sizeof(float)));
+    APE_TRY(ws.alloc((void**)&seg_of, (size_t)F * sizeof(int)));
+    APE_TRY(ws.alloc((void**)&starts_d, (size_t)R * sizeof(int)));
+    if (!is_ff) APE_TRY(ws.alloc((void**)&xw, (size_t)rmax * T * I * sizeof(float)));
+    else APE_TRY(ws.alloc((void**)&ffhid, (size_t)(rmax / n_mc + 2) * m->dims.hidden_size * sizeof(float)));
+    if (!y_dev) APE_TRY(ws.alloc((void**)&yws, (size_t)rmax * O * sizeof(float)));
+    APE_TRY(ws.alloc((void**)&est[0], (size_t)(carry + rmax) * W * sizeof(double)));
+    APE_TRY(ws.alloc((void**)&est[1], (size_t)(carry + rmax) * W * sizeof(double)));
+    APE_TRY(hipMemcpyAsync(starts_d, seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st));
     double* bodies_d = nullptr;                   // one body per recording: the values and every frame's recording index
     int* rec_of = nullptr;
     if (bodies_host) {
-        HIP_TRY(ws.alloc((void**)&bodies_d, (size_t)R * 9 * sizeof(double)));
-        HIP_TRY(ws.alloc((void**)&rec_of, (size_t)F * sizeof(int)));
-        HIP_TRY(hipMemcpyAsync(bodies_d, bodies_host, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, st));
+        APE_TRY(ws.alloc((void**)&bodies_d, (size_t)R * 9 * sizeof(double)));
+        APE_TRY(ws.alloc((void**)&rec_of, (size_t)F * sizeof(int)));
+        APE_TRY(hipMemcpyAsync(bodies_d, bodies_host, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, st));
     }
 
     // resumable replay: the carried-in records' stacks as est rows (once per call), the whole call's targets for the records going out
@@ -2554,22 +2477,22 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
     std::vector<unsigned char> warm_h;
     std::vector<int> rec_carry_h;
     if (carry_in || keep_out) {
-        if (!rec_of) HIP_TRY(ws.alloc((void**)&rec_of, (size_t)F * sizeof(int)));
-        if (keep_out && !y_dev) { HIP_TRY(ws.alloc((void**)&y_dev, (size_t)total * O * sizeof(float))); yws = nullptr; }
+        if (!rec_of) APE_TRY(ws.alloc((void**)&rec_of, (size_t)F * sizeof(int)));
+        if (keep_out && !y_dev) { APE_TRY(ws.alloc((void**)&y_dev, (size_t)total * O * sizeof(float))); yws = nullptr; }
     }
     if (carry_in) {
         double* est_in;
-        HIP_TRY(ws.alloc((void**)&est_in, (size_t)R * N * W * sizeof(double)));
-        HIP_TRY(ws.alloc((void**)&y_in, (size_t)R * stack_words * sizeof(float)));
-        HIP_TRY(ws.alloc((void**)&warm_d, (size_t)R));
-        HIP_TRY(ws.alloc((void**)&rec_carry, (size_t)R * smooth * sizeof(int)));
+        APE_TRY(ws.alloc((void**)&est_in, (size_t)R * N * W * sizeof(double)));
+        APE_TRY(ws.alloc((void**)&y_in, (size_t)R * stack_words * sizeof(float)));
+        APE_TRY(ws.alloc((void**)&warm_d, (size_t)R));
+        APE_TRY(ws.alloc((void**)&rec_carry, (size_t)R * smooth * sizeof(int)));
         warm_h.resize((size_t)R);
         for (int r = 0; r < R; ++r)       // (a stack without a window does not exist: as ape_streams_import)
             warm_h[r] = (rs->warm_in[r] & APE_STATE_WINDOW_WARM) ? (rs->warm_in[r] & (APE_STATE_WINDOW_WARM | APE_STATE_STACK_WARM)) : 0;
         rec_carry_h.resize((size_t)R * smooth);
         for (int r = 0; r < R; ++r) for (int j = 0; j < smooth; ++j) rec_carry_h[(size_t)r * smooth + j] = r;
-        HIP_TRY(hipMemcpyAsync(warm_d, warm_h.data(), (size_t)R, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpyAsync(rec_carry, rec_carry_h.data(), (size_t)R * smooth * sizeof(int), hipMemcpyHostToDevice, st));
+        APE_TRY(hipMemcpyAsync(warm_d, warm_h.data(), (size_t)R, hipMemcpyHostToDevice, st));
+        APE_TRY(hipMemcpyAsync(rec_carry, rec_carry_h.data(), (size_t)R * smooth * sizeof(int), hipMemcpyHostToDevice, st));
         cp.state_in = (const float*)rs->state_in; cp.est_in = est_in; cp.rec_of = rec_of; cp.warm = warm_d; cp.words = words;
     }
     const ReplayCarryParams* cin = carry_in ? &cp : nullptr;
@@ -2579,10 +2502,10 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
     auto pass = [&]() -> int {
         hipError_t e = ape_launch_parse_rows(rows_dev, F, width, kind & ~APE_PARSE_BIG_ENDIAN, xx, APE_F32, I, (size_t)I, 1, 0, big_endian, st);
         if (e == hipSuccess) e = ape_launch_replay_segments(starts_d, R, F, seg_of, st, rec_of);
-        if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: feature launch failed: %s", hipGetErrorString(e));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "replay: feature launch failed: %s", hipGetErrorString(e));
         if (cin) {                        // the carried stacks through the same de-normalisation and FK as fresh rows, once
             e = ape_launch_replay_carry_rows(cp.state_in, R, words, x_words, stack_words, y_in, st);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "replay_resume: carry launch failed: %s", hipGetErrorString(e));
+            if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "replay_resume: carry launch failed: %s", hipGetErrorString(e));
             const FkBodyRows fc{bodies_d, rec_carry, 0, n_mc};
             if (int rc = fk_impl(m, y_in, APE_F32, R * N, norm ? 1 : 0, const_cast<double*>(cp.est_in), APE_F64, stream, bodies_d ? &fc : nullptr))
                 return rc;
@@ -2599,14 +2522,14 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
             ReplayWindowParams wp{};
             wp.xx = xx; wp.seg_of = seg_of; wp.xw = xw; wp.r0 = r0; wp.R = rows; wp.T = T; wp.I = I; wp.n_mc = n_mc;
             e = ape_launch_replay_windows(wp, st, cin);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: window launch failed: %s", hipGetErrorString(e));
+            if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "replay: window launch failed: %s", hipGetErrorString(e));
             if (int rc = lstm_forward_impl(m, xw, rows, T, lflags, nullptr, drop ? dropout_p : 0.0f, seed, y, stream, 0, nullptr, nullptr,
                                            nullptr, r0 + pbase))
                 return rc;
             }
             double* cur = est[c & 1];
             if (c > 0)
-                HIP_TRY(hipMemcpyAsync(cur, est[(c + 1) & 1] + (size_t)prev_rows * W, (size_t)carry * W * sizeof(double),
+                APE_TRY(hipMemcpyAsync(cur, est[(c + 1) & 1] + (size_t)prev_rows * W, (size_t)carry * W * sizeof(double),
                                        hipMemcpyDeviceToDevice, st));
             const FkBodyRows fb{bodies_d, rec_of, r0, n_mc};
             if (int rc = fk_impl(m, y, APE_F32, rows, norm ? 1 : 0, cur + (size_t)carry * W, APE_F64, stream, bodies_d ? &fb : nullptr)) return rc;
@@ -2616,7 +2539,7 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
             memcpy(mp.body, m->body, sizeof(mp.body));
             mp.W = W; mp.layout = m->dims.target_layout; mp.smooth = smooth; mp.n_mc = n_mc; mp.out_dtype = out_dtype;
             e = ape_launch_replay_msg(mp, tail, st, bodies_d, bodies_d ? rec_of : nullptr, cin, spread);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "replay: message launch failed: %s", hipGetErrorString(e));
+            if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "replay: message launch failed: %s", hipGetErrorString(e));
             prev_rows = rows;
         }
         if (keep_out) {
@@ -2625,12 +2548,12 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
             sp.state_out = (float*)rs->state_out;
             sp.R = R; sp.F = F; sp.T = T; sp.I = I; sp.smooth = smooth; sp.n_mc = n_mc; sp.O = O; sp.words = words;
             e = ape_launch_replay_state_out(sp, st);
-            if (e != hipSuccess) return fail(APE_ERR_HIP, "replay_resume: state launch failed: %s", hipGetErrorString(e));
+            if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "replay_resume: state launch failed: %s", hipGetErrorString(e));
         }
         return APE_OK;
     };
     if (int rc = pass()) return rc;
-    HIP_TRY(hipStreamSynchronize(st));
+    APE_TRY(hipStreamSynchronize(st));
     // blocking and healthy on return: a weight-stationary launch that gave up is run again on the kernels that need no co-residency
     int rc = check_and_reset(m);
     if (rc == APE_ERR_HIP) {
@@ -2639,7 +2562,7 @@ static int replay_impl(ape_model_t* m, int32_t kind, const float* rows_dev, int3
         rc = pass();
         m->replaying = false;
         if (rc != APE_OK) { m->stats_counts.lost_calls += 1; return rc; }
-        HIP_TRY(hipStreamSynchronize(st));
+        APE_TRY(hipStreamSynchronize(st));
         m->stats_counts.reissued_calls += 1;
         rc = check_and_reset(m);
     }
@@ -2680,28 +2603,28 @@ static int replay_entry(ape_model_t* m, const ApeJournalEntry& e) {
         case ApeJournalEntry::SUBSET:        // regressor + post-filter again over the windows and descriptors the frame left behind
             return subset_regress_post(e.bank, e.B, e.flags, e.out0, e.i2, e.stream, e.bank_mc_calls);
     }
-    return fail(APE_ERR_INVALID_ARG, "recover: unknown journal entry");
+    return ape_fail(APE_ERR_INVALID_ARG, "recover: unknown journal entry");
 }
 
 // internal diagnostic accessor (not part of the public header): copies the 2 stamp words
 int ape_debug_read_stamps(ape_model_t* m, unsigned long long out[14]) {
     if (!m || !m->caps.cluster_ok) return APE_ERR_INVALID_ARG;
-    HIP_TRY(hipMemcpy(out, ctl_words(m).status + 4, 112, hipMemcpyDeviceToHost));
+    APE_TRY(hipMemcpy(out, ctl_words(m).status + 4, 112, hipMemcpyDeviceToHost));
     return APE_OK;
 }
 
 int ape_debug_read_wg(ape_model_t* m, unsigned long long out[256 * 8]) {
     if (!m || !m->dbg_wg) return APE_ERR_INVALID_ARG;
-    HIP_TRY(hipMemcpy(out, m->dbg_wg, 256 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+    APE_TRY(hipMemcpy(out, m->dbg_wg, 256 * 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
     return APE_OK;
 }
 
 // internal: read `n` control words of the MLP pipeline from word `first` on (its segment stamps, tests/tools/pipe_stamps.py)
 int ape_debug_peek_pipe(ape_model_t* m, int first, unsigned* out, int n) {
     if (!m || !m->ffp_ok || !out || first < 0 || n < 1 || (size_t)(first + n) > m->ffp_ctl_words) return APE_ERR_INVALID_ARG;
-    HIP_TRY(hipSetDevice(m->dims.device));
-    HIP_TRY(hipDeviceSynchronize());
-    HIP_TRY(hipMemcpy(out, m->ffp_ctl + first, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));
+    APE_TRY(hipSetDevice(m->dims.device));
+    APE_TRY(hipDeviceSynchronize());
+    APE_TRY(hipMemcpy(out, m->ffp_ctl + first, (size_t)n * sizeof(unsigned), hipMemcpyDeviceToHost));
     return APE_OK;
 }
 

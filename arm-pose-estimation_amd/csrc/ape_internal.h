@@ -409,8 +409,13 @@ __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2
 
 #endif
 
-// sets the thread's error string (ape_last_error) and returns `code`: for the entry points outside ape_api.hip
-int ape_set_error(int code, const char* msg);
+// formats the thread's error string (ape_last_error) and returns `code`; defined in ape_api.hip, where the string lives
+int ape_fail(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+#define APE_TRY(expr)                                                                                     \
+    do {                                                                                                  \
+        hipError_t _e = (expr);                                                                           \
+        if (_e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
 
 // kalman.hip's model as kalman_bank.hip sees it
 struct ape_kalman;

@@ -8,6 +8,7 @@
 #include "ape_internal.h"
 #include "ape_plan.h"
 #include "body_table.h"
+#include "bank_host.h"
 
 struct ape_streams;
 
@@ -113,8 +114,6 @@ inline CtlWords ctl_words(const ape_model* m) {
     return {status, status - 4, status - 3};
 }
 
-#define APE_SUBSET_STAGES 8      // pinned descriptor slots of a bank's subset frames
-
 struct ape_streams {
     ape_model* model = nullptr;
     int S = 0, T = 0, smooth = 0;
@@ -166,9 +165,7 @@ struct ape_streams {
     SubsetDesc* sub_desc = nullptr;   // [S] its descriptors on the device
     int sub_n_mc = 0;            // n_mc the three were sized for
     // host staging of the descriptors: a ring of pinned slots, each reused only once the copy out of it has completed
-    SubsetDesc* sub_stage = nullptr;  // [APE_SUBSET_STAGES][S]
-    hipEvent_t sub_ev[APE_SUBSET_STAGES] = {};
-    int sub_next = 0;
+    ApeDescStage sub_stage;      // slots of S SubsetDesc (bank_host.h)
     // host subset frames (ape_streams_frame_subset_host): ONE pinned, device-visible block the host writes and launch 1 reads --
     // [64] completion words the post kernel writes, [S] descriptors, [S, 57] raw rows; reused every frame (the call is blocking)
     char* hs_block = nullptr;

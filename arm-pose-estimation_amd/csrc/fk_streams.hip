@@ -11,8 +11,6 @@
 // the same inputs, so the bits are those of recomputing it.  Lane per stream, not a workgroup per stream: one-lane waves of float64
 // chains are issue-bound (stream_post_wide).  No co-residency: no journal, no recovery.
 // float64 with separate roundings for a * b + c, like numpy: contraction is off in this file.
-#include <cstdarg>
-#include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -22,6 +20,7 @@
 #include "parse_device.h"
 #include "stream_post_device.h"
 #include "body_table.h"
+#include "bank_host.h"
 
 #pragma clang fp contract(off)
 
@@ -31,7 +30,6 @@ using namespace ape_postdev;
 
 constexpr int FK_BLOCK = 64;          // lanes = streams (frames); one wave per workgroup spreads the chains over the CUs
 constexpr int FK_WIDTH = 55;          // APE_PARSE_WATCH_PHONE_UARM message
-constexpr int FK_STAGES = 4;          // pinned descriptor slots (frames go back to back)
 
 struct FkDesc { int stream, pos, cold, pad; };
 
@@ -183,47 +181,28 @@ __global__ __launch_bounds__(FK_BLOCK) void ape_fk_state_kernel(double* __restri
 
 unsigned blocks_for(long long n) { return (unsigned)((n + FK_BLOCK - 1) / FK_BLOCK); }
 
-int ffail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return ape_set_error(code, buf);
-}
-
-#define FK_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) return ffail(APE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
 int check_device(int32_t device, const char* what) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess || n == 0) {
         (void)hipGetLastError();
-        return ffail(APE_ERR_NO_DEVICE, "%s: no HIP device visible: libape_hip has no CPU fallback", what);
+        return ape_fail(APE_ERR_NO_DEVICE, "%s: no HIP device visible: libape_hip has no CPU fallback", what);
     }
-    if (device < 0 || device >= n) return ffail(APE_ERR_INVALID_ARG, "%s: device %d of %d", what, device, n);
+    if (device < 0 || device >= n) return ape_fail(APE_ERR_INVALID_ARG, "%s: device %d of %d", what, device, n);
     hipDeviceProp_t prop;
-    FK_TRY(hipGetDeviceProperties(&prop, device));
+    APE_TRY(hipGetDeviceProperties(&prop, device));
     if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-        return ffail(APE_ERR_NO_DEVICE, "%s: device %d is %s; this library is built for gfx950 only", what, device, prop.gcnArchName);
+        return ape_fail(APE_ERR_NO_DEVICE, "%s: device %d is %s; this library is built for gfx950 only", what, device, prop.gcnArchName);
     return APE_OK;
 }
 
 int check_kind(int32_t kind, const char* what) {
     if ((kind & ~APE_PARSE_BIG_ENDIAN) != APE_PARSE_WATCH_PHONE_UARM)
-        return ffail(APE_ERR_INVALID_ARG, "%s: kind %d: the forward-kinematics estimator reads APE_PARSE_WATCH_PHONE_UARM rows only", what, kind);
+        return ape_fail(APE_ERR_INVALID_ARG, "%s: kind %d: the forward-kinematics estimator reads APE_PARSE_WATCH_PHONE_UARM rows only", what, kind);
     return APE_OK;
 }
 
 int check_capture(hipStream_t st, const char* what) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    FK_TRY(hipStreamIsCapturing(st, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return ffail(APE_ERR_INVALID_ARG, "%s: the stream is capturing (ring positions and stream lists are staged per call)", what);
-    return APE_OK;
+    return ape_check_not_capturing(st, what, "ring positions and stream lists are staged per call");
 }
 
 template <typename K32, typename K64, typename... Args>
@@ -245,9 +224,7 @@ struct ape_fk_bank {
     bool uniform = true;
     long long ucount = 0;
     std::vector<long long> cnt;        // per stream, once the history is not uniform
-    FkDesc* stage = nullptr;           // FK_STAGES pinned slots of S descriptors
-    hipEvent_t ev[FK_STAGES] = {};
-    int next = 0;
+    ApeDescStage stage;                // pinned slots of S descriptors (bank_host.h)
     float* h_rows = nullptr;           // frame_host: pinned rows, message words and completion words
     void* h_out = nullptr;
     unsigned* h_done = nullptr;
@@ -262,30 +239,12 @@ void bank_free(ape_fk_bank* b) {
     ape_body_table_free(b->bodies);
     if (b->ring) (void)hipFree(b->ring);
     if (b->desc) (void)hipFree(b->desc);
-    if (b->stage) (void)hipHostFree(b->stage);
-    for (int i = 0; i < FK_STAGES; ++i)
-        if (b->ev[i]) (void)hipEventDestroy(b->ev[i]);
+    b->stage.free();
     if (b->h_rows) (void)hipHostFree(b->h_rows);
     if (b->h_out) (void)hipHostFree(b->h_out);
     if (b->h_done) (void)hipHostFree(b->h_done);
     if (b->hs_block) (void)hipHostFree(b->hs_block);
     delete b;
-}
-
-int check_list(const ape_fk_bank* b, const int32_t* streams_host, int32_t K, const char* what) {
-    if (K < 0 || K > b->S) return ffail(APE_ERR_INVALID_ARG, "%s: K=%d outside [0, S=%d]", what, K, b->S);
-    if (!streams_host) {
-        if (K != b->S) return ffail(APE_ERR_INVALID_ARG, "%s: no stream list: K=%d must be S=%d", what, K, b->S);
-        return APE_OK;
-    }
-    std::vector<char> seen((size_t)b->S, 0);
-    for (int j = 0; j < K; ++j) {
-        const int s = streams_host[j];
-        if (s < 0 || s >= b->S) return ffail(APE_ERR_INVALID_ARG, "%s: stream index %d (entry %d) outside [0, %d)", what, s, j, b->S);
-        if (seen[s]) return ffail(APE_ERR_INVALID_ARG, "%s: stream %d listed twice", what, s);
-        seen[s] = 1;
-    }
-    return APE_OK;
 }
 
 void leave_uniform(ape_fk_bank* b) {
@@ -309,9 +268,9 @@ int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* s
     } else {
         if (streams_host) leave_uniform(b);
         // the descriptors into the next pinned slot -- once the copy that last read it has completed
-        const int k = b->next;
-        if (!pinned_desc) FK_TRY(hipEventSynchronize(b->ev[k]));
-        FkDesc* h = pinned_desc ? pinned_desc : b->stage + (size_t)k * b->S;
+        hipError_t slot_wait = hipSuccess;
+        FkDesc* h = pinned_desc ? pinned_desc : static_cast<FkDesc*>(b->stage.take(&slot_wait));
+        APE_TRY(slot_wait);
         for (int j = 0; j < K; ++j) {
             const int s = streams_host ? streams_host[j] : j;
             const long long c = b->cnt[s];
@@ -319,16 +278,14 @@ int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* s
         }
         if (pinned_desc) p.desc = pinned_desc;
         else {
-            FK_TRY(hipMemcpyAsync(b->desc, h, (size_t)K * sizeof(FkDesc), hipMemcpyHostToDevice, st));
-            FK_TRY(hipEventRecord(b->ev[k], st));
-            b->next = (k + 1) % FK_STAGES;
+            APE_TRY(b->stage.send(b->desc, (size_t)K * sizeof(FkDesc), st));
             p.desc = b->desc;
         }
     }
     const double* const none = nullptr;
     const hipError_t e = b->bodies.on() ? launch_typed(ape_fk_bank_kernel<float, true>, ape_fk_bank_kernel<double, true>, out_dtype, K, st, p, (const double*)b->bodies.dev, b->S)
                                         : launch_typed(ape_fk_bank_kernel<float, false>, ape_fk_bank_kernel<double, false>, out_dtype, K, st, p, none, 0);
-    if (e != hipSuccess) return ffail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
     if (p.desc == nullptr) b->ucount += 1;
     else if (streams_host) for (int j = 0; j < K; ++j) b->cnt[streams_host[j]] += 1;
     else for (int j = 0; j < K; ++j) b->cnt[j] += 1;
@@ -338,24 +295,23 @@ int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* s
 }  // namespace
 
 int ape_fk_bank_create(int32_t n_streams, int32_t smooth, const double body9[9], int32_t device, ape_fk_bank_t** out) {
-    if (!out || !body9) return ffail(APE_ERR_INVALID_ARG, "fk_bank_create: NULL argument");
+    if (!out || !body9) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_create: NULL argument");
     *out = nullptr;
-    if (n_streams < 1) return ffail(APE_ERR_INVALID_ARG, "fk_bank_create: n_streams=%d must be >= 1", n_streams);
+    if (n_streams < 1) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_create: n_streams=%d must be >= 1", n_streams);
     if (smooth < 1) smooth = 1;                                 // estimator.py:45: max(1, smooth)
-    if (smooth > 64) return ffail(APE_ERR_UNSUPPORTED, "fk_bank_create: smooth %d outside 1..64", smooth);
+    if (smooth > 64) return ape_fail(APE_ERR_UNSUPPORTED, "fk_bank_create: smooth %d outside 1..64", smooth);
     if (int rc = check_device(device, "fk_bank_create")) return rc;
-    FK_TRY(hipSetDevice(device));
+    APE_TRY(hipSetDevice(device));
     ape_fk_bank* b = new (std::nothrow) ape_fk_bank();
-    if (!b) return ffail(APE_ERR_HIP, "fk_bank_create: out of host memory");
+    if (!b) return ape_fail(APE_ERR_HIP, "fk_bank_create: out of host memory");
     b->S = n_streams; b->smooth = smooth; b->device = device;
     memcpy(b->body, body9, sizeof(b->body));
     hipError_t e = hipMalloc((void**)&b->ring, (size_t)n_streams * smooth * 8 * sizeof(double));
     if (e == hipSuccess) e = hipMalloc((void**)&b->desc, (size_t)n_streams * sizeof(FkDesc));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&b->stage, (size_t)FK_STAGES * n_streams * sizeof(FkDesc), hipHostMallocDefault);
-    for (int i = 0; i < FK_STAGES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&b->ev[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = b->stage.alloc(n_streams, sizeof(FkDesc));
     if (e != hipSuccess) {
         bank_free(b);
-        return ffail(APE_ERR_HIP, "fk_bank_create: allocation failed: %s", hipGetErrorString(e));
+        return ape_fail(APE_ERR_HIP, "fk_bank_create: allocation failed: %s", hipGetErrorString(e));
     }
     *out = b;
     return APE_OK;
@@ -370,7 +326,7 @@ int ape_fk_bank_destroy(ape_fk_bank_t* b) {
 }
 
 int ape_fk_bank_reset(ape_fk_bank_t* b) {
-    if (!b) return ffail(APE_ERR_INVALID_ARG, "fk_bank_reset: NULL bank");
+    if (!b) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_reset: NULL bank");
     b->uniform = true;
     b->ucount = 0;
     b->cnt.clear();
@@ -378,8 +334,8 @@ int ape_fk_bank_reset(ape_fk_bank_t* b) {
 }
 
 int ape_fk_bank_reset_subset(ape_fk_bank_t* b, const int32_t* streams_host, int32_t K) {
-    if (!b || !streams_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_reset_subset: NULL argument");
-    if (int rc = check_list(b, streams_host, K, "fk_bank_reset_subset")) return rc;
+    if (!b || !streams_host) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_reset_subset: NULL argument");
+    if (int rc = ape_check_stream_list("fk_bank_reset_subset", streams_host, K, b->S, true)) return rc;
     if (K == 0) return APE_OK;
     leave_uniform(b);
     for (int j = 0; j < K; ++j) b->cnt[streams_host[j]] = 0;
@@ -388,11 +344,11 @@ int ape_fk_bank_reset_subset(ape_fk_bank_t* b, const int32_t* streams_host, int3
 
 int ape_fk_bank_frame(ape_fk_bank_t* b, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K, void* out_dev,
                       int32_t out_dtype, void* stream) {
-    if (!b || !rows_dev || !out_dev) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame: NULL argument");
+    if (!b || !rows_dev || !out_dev) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_frame: NULL argument");
     if (int rc = check_kind(kind, "fk_bank_frame")) return rc;
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame: unknown dtype selector");
-    if (int rc = check_list(b, streams_host, K, "fk_bank_frame")) return rc;
-    FK_TRY(hipSetDevice(b->device));
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_frame: unknown dtype selector");
+    if (int rc = ape_check_stream_list("fk_bank_frame", streams_host, K, b->S, true)) return rc;
+    APE_TRY(hipSetDevice(b->device));
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "fk_bank_frame")) return rc;
     if (K == 0) return APE_OK;
@@ -400,38 +356,23 @@ int ape_fk_bank_frame(ape_fk_bank_t* b, int32_t kind, const float* rows_dev, con
 }
 
 int ape_fk_bank_frame_host(ape_fk_bank_t* b, int32_t kind, const float* rows_host, void* out_host, int32_t out_dtype, void* stream) {
-    if (!b || !rows_host || !out_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame_host: NULL argument");
+    if (!b || !rows_host || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_frame_host: NULL argument");
     if (int rc = check_kind(kind, "fk_bank_frame_host")) return rc;
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame_host: unknown dtype selector");
-    FK_TRY(hipSetDevice(b->device));                         // (the consumer thread of an estimator starts on device 0)
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_frame_host: unknown dtype selector");
+    APE_TRY(hipSetDevice(b->device));                         // (the consumer thread of an estimator starts on device 0)
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "fk_bank_frame_host")) return rc;
     const size_t rows_bytes = (size_t)b->S * FK_WIDTH * sizeof(float);
     const size_t out_bytes = (size_t)b->S * 25 * sizeof(double);
     // the kernel reads the rows from and writes the messages to pinned host memory; up to 64 streams it writes a word per stream
     // behind its message, and the host takes the frame when all are there instead of waiting for the stream (as ape_streams_frame_host)
-    if (!b->h_rows) FK_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, hipHostMallocCoherent | hipHostMallocMapped));
-    if (!b->h_out) FK_TRY(hipHostMalloc(&b->h_out, out_bytes, hipHostMallocCoherent | hipHostMallocMapped));
-    if (!b->h_done && b->S <= 64) {
-        FK_TRY(hipHostMalloc((void**)&b->h_done, 64 * sizeof(unsigned), hipHostMallocCoherent | hipHostMallocMapped));
-        memset(b->h_done, 0, 64 * sizeof(unsigned));
-    }
-    b->done_val += 1;
-    if (b->done_val == 0) b->done_val = 1;
+    if (!b->h_rows) APE_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, APE_PINNED));
+    if (!b->h_out) APE_TRY(hipHostMalloc(&b->h_out, out_bytes, APE_PINNED));
+    if (b->S <= 64) APE_TRY(ape_pinned_zeroed(&b->h_done, 64 * sizeof(unsigned)));
+    ape_done_next(&b->done_val);
     memcpy(b->h_rows, rows_host, rows_bytes);
     if (int rc = bank_frame(b, kind, b->h_rows, nullptr, b->S, b->h_out, out_dtype, st, b->h_done, "fk_bank_frame_host")) return rc;
-    bool seen = false;
-    if (b->h_done) {
-        // ~50 ms of looking (a frame takes microseconds); then the stream's own completion
-        volatile unsigned* dw = b->h_done;
-        for (long spin = 0; spin < 20000000L && !seen; ++spin) {
-            seen = true;
-            for (int k = 0; k < b->S; ++k) seen = seen && dw[k] == b->done_val;
-            if (!seen) __builtin_ia32_pause();
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    }
-    if (!seen) FK_TRY(hipStreamSynchronize(st));
+    if (!(b->h_done && ape_done_wait(b->h_done, b->S, b->done_val))) APE_TRY(hipStreamSynchronize(st));
     memcpy(out_host, b->h_out, (size_t)b->S * 25 * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
     return APE_OK;
 }
@@ -441,57 +382,41 @@ int ape_fk_bank_frame_host(ape_fk_bank_t* b, int32_t kind, const float* rows_hos
 // descriptors need not land in b->desc.  Layout of the block: [64] words, [S] descriptors, [S, 55] rows; messages in h_out.
 int ape_fk_bank_frame_subset_host(ape_fk_bank_t* b, int32_t kind, const float* rows_host, const int32_t* streams_host, int32_t K,
                                   void* out_host, int32_t out_dtype, void* stream) {
-    if (!b || !rows_host || !out_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame_subset_host: NULL argument");
+    if (!b || !rows_host || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_frame_subset_host: NULL argument");
     if (int rc = check_kind(kind, "fk_bank_frame_subset_host")) return rc;
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ffail(APE_ERR_INVALID_ARG, "fk_bank_frame_subset_host: unknown dtype selector");
-    if (int rc = check_list(b, streams_host, K, "fk_bank_frame_subset_host")) return rc;
-    FK_TRY(hipSetDevice(b->device));
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_frame_subset_host: unknown dtype selector");
+    if (int rc = ape_check_stream_list("fk_bank_frame_subset_host", streams_host, K, b->S, true)) return rc;
+    APE_TRY(hipSetDevice(b->device));
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "fk_bank_frame_subset_host")) return rc;
     if (K == 0) return APE_OK;
-    if (!b->hs_block) {
-        const size_t bytes = 64 * sizeof(unsigned) + (size_t)b->S * sizeof(FkDesc) + (size_t)b->S * FK_WIDTH * sizeof(float);
-        FK_TRY(hipHostMalloc((void**)&b->hs_block, bytes, hipHostMallocCoherent | hipHostMallocMapped));
-        memset(b->hs_block, 0, bytes);
-    }
-    if (!b->h_out) FK_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * 25 * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
+    APE_TRY(ape_pinned_zeroed(&b->hs_block, 64 * sizeof(unsigned) + (size_t)b->S * sizeof(FkDesc) + (size_t)b->S * FK_WIDTH * sizeof(float)));
+    if (!b->h_out) APE_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * 25 * sizeof(double), APE_PINNED));
     unsigned* const h_done = reinterpret_cast<unsigned*>(b->hs_block);
     FkDesc* const h_desc = reinterpret_cast<FkDesc*>(b->hs_block + 64 * sizeof(unsigned));
     float* const h_rows = reinterpret_cast<float*>(b->hs_block + 64 * sizeof(unsigned) + (size_t)b->S * sizeof(FkDesc));
     const bool words = K <= 64;
-    b->done_val += 1;
-    if (b->done_val == 0) b->done_val = 1;
+    ape_done_next(&b->done_val);
     memcpy(h_rows, rows_host, (size_t)K * FK_WIDTH * sizeof(float));
     if (int rc = bank_frame(b, kind, h_rows, streams_host, K, b->h_out, out_dtype, st, words ? h_done : nullptr, "fk_bank_frame_subset_host", h_desc))
         return rc;
-    bool seen = false;
-    if (words) {
-        // ~50 ms of looking (a frame takes microseconds); then the stream's own completion
-        volatile unsigned* dw = h_done;
-        for (long spin = 0; spin < 20000000L && !seen; ++spin) {
-            seen = true;
-            for (int k = 0; k < K; ++k) seen = seen && dw[k] == b->done_val;
-            if (!seen) __builtin_ia32_pause();
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    }
-    if (!seen) FK_TRY(hipStreamSynchronize(st));
+    if (!(words && ape_done_wait(h_done, K, b->done_val))) APE_TRY(hipStreamSynchronize(st));
     memcpy(out_host, b->h_out, (size_t)K * 25 * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
     return APE_OK;
 }
 
 int ape_fk_bank_set_bodies(ape_fk_bank_t* b, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream) {
-    if (!b || !body9s_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_set_bodies: NULL argument");
-    if (int rc = check_list(b, streams_host, K, "fk_bank_set_bodies")) return rc;
-    FK_TRY(hipSetDevice(b->device));
+    if (!b || !body9s_host) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_set_bodies: NULL argument");
+    if (int rc = ape_check_stream_list("fk_bank_set_bodies", streams_host, K, b->S, true)) return rc;
+    APE_TRY(hipSetDevice(b->device));
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "fk_bank_set_bodies")) return rc;
-    FK_TRY(ape_body_table_set(b->bodies, b->S, true, b->body, streams_host, K, body9s_host, st));
+    APE_TRY(ape_body_table_set(b->bodies, b->S, true, b->body, streams_host, K, body9s_host, st));
     return APE_OK;
 }
 
 int ape_fk_bank_get_bodies(ape_fk_bank_t* b, double* out_host) {
-    if (!b || !out_host) return ffail(APE_ERR_INVALID_ARG, "fk_bank_get_bodies: NULL argument");
+    if (!b || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_get_bodies: NULL argument");
     ape_body_table_get(b->bodies, b->S, b->body, out_host);
     return APE_OK;
 }
@@ -508,33 +433,31 @@ void fk_state_desc_of(const ape_fk_bank* b, ape_stream_state_desc_t* d) {
 // descriptors through the next pinned slot (as bank_frame), then the one launch; fill(stream) -> {oldest slot, cold}
 template <bool IMPORT, typename Fill>
 int fk_state_launch(ape_fk_bank* b, const int32_t* streams_host, int32_t K, double* state, hipStream_t st, const char* what, Fill fill) {
-    const int k = b->next;
-    FK_TRY(hipEventSynchronize(b->ev[k]));
-    FkDesc* h = b->stage + (size_t)k * b->S;
+    hipError_t slot_wait;
+    FkDesc* h = static_cast<FkDesc*>(b->stage.take(&slot_wait));
+    APE_TRY(slot_wait);
     for (int j = 0; j < K; ++j) h[j] = fill(j, streams_host[j]);
-    FK_TRY(hipMemcpyAsync(b->desc, h, (size_t)K * sizeof(FkDesc), hipMemcpyHostToDevice, st));
-    FK_TRY(hipEventRecord(b->ev[k], st));
-    b->next = (k + 1) % FK_STAGES;
+    APE_TRY(b->stage.send(b->desc, (size_t)K * sizeof(FkDesc), st));
     hipLaunchKernelGGL(ape_fk_state_kernel<IMPORT>, dim3(blocks_for((long long)K * b->smooth * 4)), dim3(FK_BLOCK), 0, st, b->ring, state,
                        (const FkDesc*)b->desc, (int)K, b->smooth);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return ffail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
     return APE_OK;
 }
 
 int fk_state_check_call(ape_fk_bank* b, const int32_t* streams_host, int32_t K, const void* state_dev, const void* warm_host, hipStream_t st,
                         const char* what) {
-    if (!b || !streams_host || !state_dev || !warm_host) return ffail(APE_ERR_INVALID_ARG, "%s: NULL argument", what);
-    if (int rc = check_list(b, streams_host, K, what)) return rc;
-    if (((uintptr_t)state_dev & 15u) != 0) return ffail(APE_ERR_INVALID_ARG, "%s: state_dev must be 16-byte aligned", what);
-    FK_TRY(hipSetDevice(b->device));
+    if (!b || !streams_host || !state_dev || !warm_host) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", what);
+    if (int rc = ape_check_stream_list(what, streams_host, K, b->S, true)) return rc;
+    if (((uintptr_t)state_dev & 15u) != 0) return ape_fail(APE_ERR_INVALID_ARG, "%s: state_dev must be 16-byte aligned", what);
+    APE_TRY(hipSetDevice(b->device));
     return check_capture(st, what);
 }
 
 }  // namespace
 
 int ape_fk_bank_state_desc(ape_fk_bank_t* b, ape_stream_state_desc_t* out) {
-    if (!b || !out) return ffail(APE_ERR_INVALID_ARG, "fk_bank_state_desc: NULL argument");
+    if (!b || !out) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_state_desc: NULL argument");
     fk_state_desc_of(b, out);
     return APE_OK;
 }
@@ -554,13 +477,13 @@ int ape_fk_bank_export(ape_fk_bank_t* b, const int32_t* streams_host, int32_t K,
 int ape_fk_bank_import(ape_fk_bank_t* b, const ape_stream_state_desc_t* desc, const int32_t* streams_host, int32_t K,
                        const void* state_dev, const uint8_t* warm_host, void* stream) {
     const hipStream_t st = (hipStream_t)stream;
-    if (!desc) return ffail(APE_ERR_INVALID_ARG, "fk_bank_import: NULL argument");
+    if (!desc) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_import: NULL argument");
     if (int rc = fk_state_check_call(b, streams_host, K, state_dev, warm_host, st, "fk_bank_import")) return rc;
     ape_stream_state_desc_t own;
     fk_state_desc_of(b, &own);
     if (desc->version != own.version || desc->T != own.T || desc->I != own.I || desc->smooth != own.smooth || desc->n_mc != own.n_mc ||
         desc->O != own.O || desc->words_per_stream != own.words_per_stream)
-        return ffail(APE_ERR_INVALID_ARG, "fk_bank_import: the records are {v%d T=%d I=%d smooth=%d n_mc=%d O=%d words=%d}, the bank's {v%d T=0 I=0 smooth=%d n_mc=1 O=8 words=%d}",
+        return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_import: the records are {v%d T=%d I=%d smooth=%d n_mc=%d O=%d words=%d}, the bank's {v%d T=0 I=0 smooth=%d n_mc=1 O=8 words=%d}",
                      desc->version, desc->T, desc->I, desc->smooth, desc->n_mc, desc->O, desc->words_per_stream, own.version, own.smooth,
                      own.words_per_stream);
     if (K == 0) return APE_OK;
@@ -581,41 +504,33 @@ int ape_fk_replay(int32_t kind, const float* rows_dev, int32_t F, const int32_t*
 
 int ape_fk_replay_bodies(int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t smooth,
                          const double body9[9], int32_t device, void* out_dev, int32_t out_dtype, void* stream, const double* bodies_host) {
-    if (!rows_dev || !out_dev || (!body9 && !bodies_host)) return ffail(APE_ERR_INVALID_ARG, "fk_replay: NULL argument");
+    if (!rows_dev || !out_dev || (!body9 && !bodies_host)) return ape_fail(APE_ERR_INVALID_ARG, "fk_replay: NULL argument");
     if (int rc = check_kind(kind, "fk_replay")) return rc;
-    if (F < 1) return ffail(APE_ERR_INVALID_ARG, "fk_replay: F=%d must be >= 1", F);
-    if (R < 1 || R > F) return ffail(APE_ERR_INVALID_ARG, "fk_replay: %d recording starts for %d frames (1 <= R <= F)", R, F);
-    if (!seg_starts_host) return ffail(APE_ERR_INVALID_ARG, "fk_replay: NULL seg_starts");
-    if (seg_starts_host[0] != 0) return ffail(APE_ERR_INVALID_ARG, "fk_replay: seg_starts[0] = %d, must be 0", seg_starts_host[0]);
-    for (int i = 1; i < R; ++i)
-        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
-            return ffail(APE_ERR_INVALID_ARG, "fk_replay: seg_starts[%d] = %d (strictly rising, below F = %d)", i, seg_starts_host[i], F);
+    if (int rc = ape_check_segments("fk_replay", F, seg_starts_host, R)) return rc;
     if (smooth < 1) smooth = 1;
-    if (smooth > 64) return ffail(APE_ERR_UNSUPPORTED, "fk_replay: smooth %d outside 1..64", smooth);
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ffail(APE_ERR_INVALID_ARG, "fk_replay: unknown dtype selector");
+    if (smooth > 64) return ape_fail(APE_ERR_UNSUPPORTED, "fk_replay: smooth %d outside 1..64", smooth);
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "fk_replay: unknown dtype selector");
     if (int rc = check_device(device, "fk_replay")) return rc;
-    FK_TRY(hipSetDevice(device));
+    APE_TRY(hipSetDevice(device));
     const hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    FK_TRY(hipStreamIsCapturing(st, &cap));
-    if (cap != hipStreamCaptureStatusNone) return ffail(APE_ERR_INVALID_ARG, "fk_replay: blocking call on a capturing stream");
+    if (int rc = ape_check_not_capturing(st, "fk_replay", nullptr)) return rc;
     // workspaces: the frames' quaternions, their recording starts; freed behind the call's own synchronisation
     struct Scratch {
         void* p[5] = {};
         ~Scratch() { for (void* q : p) if (q) (void)hipFree(q); }
     } ws;
-    FK_TRY(hipMalloc(&ws.p[0], (size_t)F * 8 * sizeof(double)));
-    FK_TRY(hipMalloc(&ws.p[1], (size_t)F * sizeof(int)));
-    FK_TRY(hipMalloc(&ws.p[2], (size_t)R * sizeof(int)));
-    FK_TRY(hipMemcpyAsync(ws.p[2], seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st));
+    APE_TRY(hipMalloc(&ws.p[0], (size_t)F * 8 * sizeof(double)));
+    APE_TRY(hipMalloc(&ws.p[1], (size_t)F * sizeof(int)));
+    APE_TRY(hipMalloc(&ws.p[2], (size_t)R * sizeof(int)));
+    APE_TRY(hipMemcpyAsync(ws.p[2], seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st));
     FkReplayParams p{};
     p.rows = rows_dev; p.seg_of = (const int*)ws.p[1]; p.ws = (double*)ws.p[0]; p.out = out_dev;
     p.F = F; p.smooth = smooth; p.big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
     if (body9) memcpy(p.body, body9, sizeof(p.body));
     if (bodies_host) {                                        // one body per recording: the values and every frame's recording index
-        FK_TRY(hipMalloc(&ws.p[3], (size_t)R * 9 * sizeof(double)));
-        FK_TRY(hipMalloc(&ws.p[4], (size_t)F * sizeof(int)));
-        FK_TRY(hipMemcpyAsync(ws.p[3], bodies_host, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, st));
+        APE_TRY(hipMalloc(&ws.p[3], (size_t)R * 9 * sizeof(double)));
+        APE_TRY(hipMalloc(&ws.p[4], (size_t)F * sizeof(int)));
+        APE_TRY(hipMemcpyAsync(ws.p[3], bodies_host, (size_t)R * 9 * sizeof(double), hipMemcpyHostToDevice, st));
     }
     hipError_t e = ape_launch_replay_segments((const int*)ws.p[2], R, F, (int*)ws.p[1], st, (int*)ws.p[4]);
     if (e == hipSuccess) {
@@ -629,8 +544,8 @@ int ape_fk_replay_bodies(int32_t kind, const float* rows_dev, int32_t F, const i
                                        (const double*)nullptr, (const int*)nullptr);
     if (e != hipSuccess) {
         (void)hipStreamSynchronize(st);
-        return ffail(APE_ERR_HIP, "fk_replay: launch failed: %s", hipGetErrorString(e));
+        return ape_fail(APE_ERR_HIP, "fk_replay: launch failed: %s", hipGetErrorString(e));
     }
-    FK_TRY(hipStreamSynchronize(st));
+    APE_TRY(hipStreamSynchronize(st));
     return APE_OK;
 }

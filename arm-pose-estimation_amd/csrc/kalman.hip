@@ -338,7 +338,6 @@ size_t blob_floats(int W) {
     return t;
 }
 
-int kfail(int code, const char* msg) { return ape_set_error(code, msg); }
 
 hipError_t launch_linear(const ape_kalman* m, int li, const float* X, int x_group, int R, const float* sin_, const float* sout,
                          unsigned long long seed, int act, float* Y, hipStream_t st) {
@@ -365,17 +364,17 @@ void ape_kalman_info(const ape_kalman* m, ApeKalmanInfo* out) {
 extern "C" {
 
 int ape_kalman_create(const ape_kalman_dims_t* dims, ape_kalman_t** out) {
-    if (!dims || !out) return kfail(APE_ERR_INVALID_ARG, "kalman_create: NULL argument");
+    if (!dims || !out) return ape_fail(APE_ERR_INVALID_ARG, "kalman_create: NULL argument");
     if (dims->num_ensemble < 2 || dims->num_ensemble > MAXE)
-        return kfail(APE_ERR_INVALID_ARG, "kalman_create: num_ensemble must be in [2, 128]");
+        return ape_fail(APE_ERR_INVALID_ARG, "kalman_create: num_ensemble must be in [2, 128]");
     if (dims->win_size < 2 || dims->win_size > 22 || dims->win_size % 2 != 0)   // 22 W <= 512 (the LDS tile of kf_linear); 16-byte rows
-        return kfail(APE_ERR_INVALID_ARG, "kalman_create: win_size must be even and in [2, 22]");
+        return ape_fail(APE_ERR_INVALID_ARG, "kalman_create: win_size must be even and in [2, 22]");
     int n_dev = 0;
     if (hipGetDeviceCount(&n_dev) != hipSuccess || dims->device < 0 || dims->device >= n_dev)
-        return kfail(APE_ERR_HIP, "kalman_create: no such HIP device (no CPU fallback)");
-    if (hipSetDevice(dims->device) != hipSuccess) return kfail(APE_ERR_HIP, "kalman_create: hipSetDevice failed");
+        return ape_fail(APE_ERR_HIP, "kalman_create: no such HIP device (no CPU fallback)");
+    if (hipSetDevice(dims->device) != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_create: hipSetDevice failed");
     ape_kalman* m = new (std::nothrow) ape_kalman;
-    if (!m) return kfail(APE_ERR_HIP, "kalman_create: out of host memory");
+    if (!m) return ape_fail(APE_ERR_HIP, "kalman_create: out of host memory");
     m->E = dims->num_ensemble; m->W = dims->win_size; m->device = dims->device;
     int N[NLAYERS], K[NLAYERS];
     layer_dims(m->W, N, K);
@@ -384,7 +383,7 @@ int ape_kalman_create(const ape_kalman_dims_t* dims, ape_kalman_t** out) {
         total += (size_t)(IS_FLIP[i] ? 3 : 1) * (((size_t)N[i] * K[i] + 63) / 64 * 64 + ((size_t)N[i] + 63) / 64 * 64);
     if (hipMalloc(&m->slab, total * sizeof(float)) != hipSuccess || hipMemset(m->slab, 0, total * sizeof(float)) != hipSuccess) {
         delete m;
-        return kfail(APE_ERR_HIP, "kalman_create: device allocation failed");
+        return ape_fail(APE_ERR_HIP, "kalman_create: device allocation failed");
     }
     float* cur = static_cast<float*>(m->slab);
     m->singular = reinterpret_cast<int*>(cur);
@@ -424,9 +423,9 @@ size_t ape_kalman_noise_floats(const ape_kalman_t* m, int32_t S) {
 }
 
 int ape_kalman_load_weights(ape_kalman_t* m, const float* blob, size_t n_floats) {
-    if (!m || !blob) return kfail(APE_ERR_INVALID_ARG, "kalman_load_weights: NULL argument");
-    if (n_floats != blob_floats(m->W)) return kfail(APE_ERR_INVALID_ARG, "kalman_load_weights: blob size does not match the model");
-    if (hipSetDevice(m->device) != hipSuccess) return kfail(APE_ERR_HIP, "kalman_load_weights: hipSetDevice failed");
+    if (!m || !blob) return ape_fail(APE_ERR_INVALID_ARG, "kalman_load_weights: NULL argument");
+    if (n_floats != blob_floats(m->W)) return ape_fail(APE_ERR_INVALID_ARG, "kalman_load_weights: blob size does not match the model");
+    if (hipSetDevice(m->device) != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_load_weights: hipSetDevice failed");
     const float* cur = blob;
     for (int i = 0; i < NLAYERS; ++i) {
         KfLayer& L = m->layer[i];
@@ -442,7 +441,7 @@ int ape_kalman_load_weights(ape_kalman_t* m, const float* blob, size_t n_floats)
             if (e == hipSuccess) e = hipMemcpy(L.rho_b, cur, L.N * sizeof(float), hipMemcpyHostToDevice);
             cur += L.N;
         }
-        if (e != hipSuccess) return kfail(APE_ERR_HIP, "kalman_load_weights: copy to the device failed");
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_load_weights: copy to the device failed");
     }
     m->has_weights = true;
     return APE_OK;
@@ -453,19 +452,19 @@ int ape_kalman_forward(ape_kalman_t* m, const float* raw_obs_dev, const float* s
                        float* m_state_pred_dev, float* z_dev, float* ensemble_z_dev, void* stream) {
     if (!m || !raw_obs_dev || !state_prev_dev || !state_corrected_dev || !m_state_corrected_dev || !m_state_pred_dev || !z_dev ||
         !ensemble_z_dev)
-        return kfail(APE_ERR_INVALID_ARG, "kalman_forward: NULL argument");
-    if (S < 1 || S > 65535) return kfail(APE_ERR_INVALID_ARG, "kalman_forward: S must be in [1, 65535]");
-    if (!m->has_weights) return kfail(APE_ERR_NOT_READY, "kalman_forward: weights not loaded");
-    if (hipSetDevice(m->device) != hipSuccess) return kfail(APE_ERR_HIP, "kalman_forward: hipSetDevice failed");
+        return ape_fail(APE_ERR_INVALID_ARG, "kalman_forward: NULL argument");
+    if (S < 1 || S > 65535) return ape_fail(APE_ERR_INVALID_ARG, "kalman_forward: S must be in [1, 65535]");
+    if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "kalman_forward: weights not loaded");
+    if (hipSetDevice(m->device) != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_forward: hipSetDevice failed");
     hipStream_t st = (hipStream_t)stream;
     const int E = m->E, R = S * E;
     if (S > m->ws_S) {                                  // activations: h1 [R,256] h2 [R,512] pred [R,14] s1 [S,256] s2 [R,256] s3 [R,64]
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
         if (st && hipStreamIsCapturing(st, &cs) == hipSuccess && cs != hipStreamCaptureStatusNone)
-            return kfail(APE_ERR_CAPACITY, "kalman_forward: the workspace cannot grow during stream capture");
+            return ape_fail(APE_ERR_CAPACITY, "kalman_forward: the workspace cannot grow during stream capture");
         if (m->ws) { (void)hipFree(m->ws); m->ws = nullptr; m->ws_S = 0; }
         const size_t fl = (size_t)S * E * (256 + 512 + 16 + 256 + 64) + (size_t)S * 256;
-        if (hipMalloc((void**)&m->ws, fl * sizeof(float)) != hipSuccess) return kfail(APE_ERR_HIP, "kalman_forward: workspace allocation failed");
+        if (hipMalloc((void**)&m->ws, fl * sizeof(float)) != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_forward: workspace allocation failed");
         m->ws_S = S;
     }
     float* h1 = m->ws;
@@ -499,7 +498,7 @@ int ape_kalman_forward(ape_kalman_t* m, const float* raw_obs_dev, const float* s
         pp.start[10] = run;
         pp.seed = seed;
         hipLaunchKernelGGL(kf_perturb_kernel, dim3((run + 255) / 256), dim3(256), 0, st, pp);
-        if (hipGetLastError() != hipSuccess) return kfail(APE_ERR_HIP, "kalman_forward: perturbation launch failed");
+        if (hipGetLastError() != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_forward: perturbation launch failed");
     }
     hipError_t e = launch_linear(m, P_B1, state_prev_dev, 1, R, sin_[P_B1], sout[P_B1], seed, 1, h1, st);
     if (e == hipSuccess) e = launch_linear(m, P_B3, h1, 1, R, sin_[P_B3], sout[P_B3], seed, 1, h2, st);
@@ -508,37 +507,37 @@ int ape_kalman_forward(ape_kalman_t* m, const float* raw_obs_dev, const float* s
     if (e == hipSuccess) e = launch_linear(m, S_FC3, s1, E, R, sin_[S_FC3], sout[S_FC3], seed, 1, s2, st);
     if (e == hipSuccess) e = launch_linear(m, S_FC5, s2, 1, R, sin_[S_FC5], sout[S_FC5], seed, 1, s3, st);
     if (e == hipSuccess) e = launch_linear(m, S_FC6, s3, 1, R, sin_[S_FC6], sout[S_FC6], seed, 0, ensemble_z_dev, st);
-    if (e != hipSuccess) return kfail(APE_ERR_HIP, "kalman_forward: layer launch failed");
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_forward: layer launch failed");
     KfUpdateParams u{};
     u.pred = pred; u.ensz = ensemble_z_dev;
     u.w1 = m->layer[O_FC1].mu_w; u.b1 = m->layer[O_FC1].mu_b; u.w2 = m->layer[O_FC2].mu_w; u.b2 = m->layer[O_FC2].mu_b;
     u.corrected = state_corrected_dev; u.m_corrected = m_state_corrected_dev; u.m_pred = m_state_pred_dev; u.z = z_dev;
     u.S = S; u.E = E; u.singular = m->singular;
     hipLaunchKernelGGL(kf_update_kernel, dim3(S), dim3(64), 0, st, u);
-    if (hipGetLastError() != hipSuccess) return kfail(APE_ERR_HIP, "kalman_forward: update launch failed");
+    if (hipGetLastError() != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_forward: update launch failed");
     return APE_OK;
 }
 
 int ape_kalman_format_state(ape_kalman_t* m, const float* state_dev, int32_t S, uint64_t seed, const float* noise_dev,
                             float* out_dev, void* stream) {
-    if (!m || !state_dev || !out_dev) return kfail(APE_ERR_INVALID_ARG, "kalman_format_state: NULL argument");
-    if (S < 1) return kfail(APE_ERR_INVALID_ARG, "kalman_format_state: S must be >= 1");
-    if (hipSetDevice(m->device) != hipSuccess) return kfail(APE_ERR_HIP, "kalman_format_state: hipSetDevice failed");
+    if (!m || !state_dev || !out_dev) return ape_fail(APE_ERR_INVALID_ARG, "kalman_format_state: NULL argument");
+    if (S < 1) return ape_fail(APE_ERR_INVALID_ARG, "kalman_format_state: S must be >= 1");
+    if (hipSetDevice(m->device) != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_format_state: hipSetDevice failed");
     const unsigned n = (unsigned)(S * m->E * DX);
     hipLaunchKernelGGL(kf_format_state_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, state_dev, noise_dev, out_dev,
                        S, m->E, (unsigned long long)seed);
-    if (hipGetLastError() != hipSuccess) return kfail(APE_ERR_HIP, "kalman_format_state: launch failed");
+    if (hipGetLastError() != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_format_state: launch failed");
     return APE_OK;
 }
 
 int ape_kalman_check(ape_kalman_t* m) {
-    if (!m) return kfail(APE_ERR_INVALID_ARG, "kalman_check: NULL model");
-    if (hipSetDevice(m->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return kfail(APE_ERR_HIP, "kalman_check: synchronise failed");
+    if (!m) return ape_fail(APE_ERR_INVALID_ARG, "kalman_check: NULL model");
+    if (hipSetDevice(m->device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_check: synchronise failed");
     int s = 0;
-    if (hipMemcpy(&s, m->singular, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return kfail(APE_ERR_HIP, "kalman_check: copy failed");
+    if (hipMemcpy(&s, m->singular, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_check: copy failed");
     if (s != 0) {
         (void)hipMemset(m->singular, 0, sizeof(int));
-        return kfail(APE_ERR_HIP, "kalman forward: a singular innovation matrix was inverted since the last check (torch.linalg.inv raises there)");
+        return ape_fail(APE_ERR_HIP, "kalman forward: a singular innovation matrix was inverted since the last check (torch.linalg.inv raises there)");
     }
     return APE_OK;
 }

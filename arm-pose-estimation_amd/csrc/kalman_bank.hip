@@ -22,7 +22,6 @@
 //                                 (ape_kalman_bank_export / _import, ape_kalman_replay_resume); for it the host also keeps each
 //                                 stream's age, min(frames since the cold start, W + 1)
 // float64 with separate roundings for a * b + c, like numpy: contraction is off in this file.
-#include <cstdarg>
 #include <cstdint>
 #include <cstdio>
 #include <cstring>
@@ -34,6 +33,7 @@
 #include "parse_device.h"
 #include "stream_post_device.h"
 #include "body_table.h"
+#include "bank_host.h"
 #include "kalman_device.h"
 
 #pragma clang fp contract(off)
@@ -45,7 +45,6 @@ using namespace ape_postdev;
 constexpr int DX = 14, RAW = 22;
 constexpr int KB_WIDTH = 55;          // APE_PARSE_WATCH_PHONE_POCKET message
 constexpr int KB_BLOCK = 256;
-constexpr int KB_STAGES = 4;          // pinned stream-list slots (frames go back to back)
 constexpr int KB_MAX_SMOOTH = 64;     // the post-filter's limits (ape_streams_create)
 constexpr int KB_MAX_ROWS = 4096;
 constexpr uint32_t KB_FLAGS = APE_FLAG_PACKED_MSG | APE_FLAG_SPREAD;      // what the frame and replay entries accept
@@ -428,33 +427,14 @@ __global__ __launch_bounds__(KB_BLOCK) void ape_kalman_state_kernel(const KsPara
 }
 
 
-int bfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return ape_set_error(code, buf);
-}
-
-#define KB_TRY(expr)                                                                                   \
-    do {                                                                                               \
-        hipError_t _e = (expr);                                                                        \
-        if (_e != hipSuccess) return bfail(APE_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
-
 int check_kind(int32_t kind, const char* what) {
     if ((kind & ~APE_PARSE_BIG_ENDIAN) != APE_PARSE_WATCH_PHONE_POCKET)
-        return bfail(APE_ERR_INVALID_ARG, "%s: kind %d: the Kalman estimator reads APE_PARSE_WATCH_PHONE_POCKET rows only", what, kind);
+        return ape_fail(APE_ERR_INVALID_ARG, "%s: kind %d: the Kalman estimator reads APE_PARSE_WATCH_PHONE_POCKET rows only", what, kind);
     return APE_OK;
 }
 
 int check_capture(hipStream_t st, const char* what) {
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    KB_TRY(hipStreamIsCapturing(st, &cap));
-    if (cap != hipStreamCaptureStatusNone)
-        return bfail(APE_ERR_INVALID_ARG, "%s: the stream is capturing (stream lists and draw keys are staged per call)", what);
-    return APE_OK;
+    return ape_check_not_capturing(st, what, "stream lists and draw keys are staged per call");
 }
 
 }  // namespace
@@ -477,9 +457,7 @@ struct ape_kalman_bank {
     std::vector<char> pending;
     int n_pending = 0;
     KbDesc* desc = nullptr;
-    KbDesc* stage = nullptr;
-    hipEvent_t ev[KB_STAGES] = {};
-    int next = 0;
+    ApeDescStage stage;               // pinned slots of S KbDesc (bank_host.h)
     // frame_host: pinned rows, messages and row counts
     float* h_rows = nullptr;
     void* h_out = nullptr;
@@ -492,9 +470,7 @@ struct ape_kalman_bank {
     // export / import kernel's own descriptors (b->desc may still be read by a frame in flight); allocated by the first hand-over
     std::vector<int> age;
     KsDesc* ks_desc = nullptr;
-    KsDesc* ks_stage = nullptr;
-    hipEvent_t ks_ev[KB_STAGES] = {};
-    int ks_next = 0;
+    ApeDescStage ks_stage;            // pinned slots of S KsDesc
 };
 
 namespace {
@@ -504,28 +480,26 @@ void bank_free(ape_kalman_bank* b) {
     void* dev[] = {b->xwin, b->state, b->yring, b->nring, b->cnt, b->raw, b->dense, b->corrected, b->ensz, b->mcorr, b->mpred, b->z, b->desc,
                    b->ks_desc};
     for (void* q : dev) if (q) (void)hipFree(q);
-    void* host[] = {b->stage, b->h_rows, b->h_out, b->h_n, b->ks_stage, b->hs_block};
+    void* host[] = {b->h_rows, b->h_out, b->h_n, b->hs_block};
     for (void* q : host) if (q) (void)hipHostFree(q);
-    for (int i = 0; i < KB_STAGES; ++i) {
-        if (b->ev[i]) (void)hipEventDestroy(b->ev[i]);
-        if (b->ks_ev[i]) (void)hipEventDestroy(b->ks_ev[i]);
-    }
+    b->stage.free();
+    b->ks_stage.free();
     delete b;
 }
 
 // argument checks that need no device, then the allocations; `what` names the entry in messages
 int bank_make(ape_kalman* model, int32_t n_streams, int32_t smooth, const char* what, ape_kalman_bank** out) {
-    if (n_streams < 1 || n_streams > 65535) return bfail(APE_ERR_INVALID_ARG, "%s: n_streams=%d outside [1, 65535]", what, n_streams);
+    if (n_streams < 1 || n_streams > 65535) return ape_fail(APE_ERR_INVALID_ARG, "%s: n_streams=%d outside [1, 65535]", what, n_streams);
     if (smooth < 1) smooth = 1;                                 // estimator.py:45: max(1, smooth)
-    if (smooth > KB_MAX_SMOOTH) return bfail(APE_ERR_UNSUPPORTED, "%s: smooth %d outside 1..%d", what, smooth, KB_MAX_SMOOTH);
+    if (smooth > KB_MAX_SMOOTH) return ape_fail(APE_ERR_UNSUPPORTED, "%s: smooth %d outside 1..%d", what, smooth, KB_MAX_SMOOTH);
     ApeKalmanInfo mi;
     ape_kalman_info(model, &mi);
-    if (!mi.has_weights) return bfail(APE_ERR_NOT_READY, "%s: the model's weights are not loaded", what);
+    if (!mi.has_weights) return ape_fail(APE_ERR_NOT_READY, "%s: the model's weights are not loaded", what);
     if (smooth * mi.E > KB_MAX_ROWS)
-        return bfail(APE_ERR_UNSUPPORTED, "%s: smooth %d x %d members = %d stacked rows, more than %d", what, smooth, mi.E, smooth * mi.E, KB_MAX_ROWS);
-    KB_TRY(hipSetDevice(mi.device));
+        return ape_fail(APE_ERR_UNSUPPORTED, "%s: smooth %d x %d members = %d stacked rows, more than %d", what, smooth, mi.E, smooth * mi.E, KB_MAX_ROWS);
+    APE_TRY(hipSetDevice(mi.device));
     ape_kalman_bank* b = new (std::nothrow) ape_kalman_bank();
-    if (!b) return bfail(APE_ERR_HIP, "%s: out of host memory", what);
+    if (!b) return ape_fail(APE_ERR_HIP, "%s: out of host memory", what);
     b->model = model; b->S = n_streams; b->E = mi.E; b->W = mi.W; b->smooth = smooth; b->device = mi.device;
     b->pending.assign((size_t)n_streams, 1);
     b->n_pending = n_streams;
@@ -544,29 +518,12 @@ int bank_make(ape_kalman* model, int32_t n_streams, int32_t smooth, const char* 
     if (e == hipSuccess) e = hipMalloc((void**)&b->mpred, S * DX * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&b->z, S * DX * sizeof(float));
     if (e == hipSuccess) e = hipMalloc((void**)&b->desc, S * sizeof(KbDesc));
-    if (e == hipSuccess) e = hipHostMalloc((void**)&b->stage, (size_t)KB_STAGES * S * sizeof(KbDesc), hipHostMallocDefault);
-    for (int i = 0; i < KB_STAGES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&b->ev[i], hipEventDisableTiming);
+    if (e == hipSuccess) e = b->stage.alloc(n_streams, sizeof(KbDesc));
     if (e != hipSuccess) {
         bank_free(b);
-        return bfail(APE_ERR_HIP, "%s: allocation failed: %s", what, hipGetErrorString(e));
+        return ape_fail(APE_ERR_HIP, "%s: allocation failed: %s", what, hipGetErrorString(e));
     }
     *out = b;
-    return APE_OK;
-}
-
-int check_list(const ape_kalman_bank* b, const int32_t* streams_host, int32_t K, const char* what) {
-    if (K < 0 || K > b->S) return bfail(APE_ERR_INVALID_ARG, "%s: K=%d outside [0, S=%d]", what, K, b->S);
-    if (!streams_host) {
-        if (K != b->S) return bfail(APE_ERR_INVALID_ARG, "%s: no stream list: K=%d must be S=%d", what, K, b->S);
-        return APE_OK;
-    }
-    std::vector<char> seen((size_t)b->S, 0);
-    for (int j = 0; j < K; ++j) {
-        const int s = streams_host[j];
-        if (s < 0 || s >= b->S) return bfail(APE_ERR_INVALID_ARG, "%s: stream index %d (entry %d) outside [0, %d)", what, s, j, b->S);
-        if (seen[s]) return bfail(APE_ERR_INVALID_ARG, "%s: stream %d listed twice", what, s);
-        seen[s] = 1;
-    }
     return APE_OK;
 }
 
@@ -588,7 +545,7 @@ int frame_launch(ape_kalman_bank* b, int big_endian, const float* rows, const Kb
         hipLaunchKernelGGL(ape_kalman_bank_head_kernel<true>, dim3(K), dim3(KB_BLOCK), 0, st, h, const_cast<KbDesc*>(desc_dev));
     } else hipLaunchKernelGGL(ape_kalman_bank_head_kernel<false>, dim3(K), dim3(KB_BLOCK), 0, st, h, (KbDesc*)nullptr);
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: head launch failed: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: head launch failed: %s", what, hipGetErrorString(e));
     if (int rc = ape_kalman_forward(b->model, b->raw, b->dense, K, seed, noise, b->corrected, b->mcorr, b->mpred, b->z, b->ensz, st)) return rc;
     KbTailParams t{};
     t.desc = desc_dev; t.cnt = b->cnt; t.z = b->z; t.corrected = b->corrected; t.init_noise = init_noise; t.seed = seed;
@@ -619,7 +576,7 @@ int frame_launch(ape_kalman_bank* b, int big_endian, const float* rows, const Kb
     hipLaunchKernelGGL((done ? tails_done : tails)[out_dtype == APE_F32 ? 1 : 0][tab ? 1 : 0][spr ? 1 : 0], dim3(K), dim3(KB_BLOCK), 0, st, t,
                        tab ? (const double*)b->bodies.dev : (const double*)nullptr, done ? KbDone{hf->done, hf->done_val} : KbDone{nullptr, 0u});
     e = hipGetLastError();
-    if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: tail launch failed: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: tail launch failed: %s", what, hipGetErrorString(e));
     return APE_OK;
 }
 
@@ -640,16 +597,14 @@ int bank_frame(ape_kalman_bank* b, int32_t kind, const float* rows, const int32_
     } else if (!streams_host && (b->n_pending == 0 || b->n_pending == b->S)) cold_all = b->n_pending ? 1 : 0;
     else {
         // the list into the next pinned slot -- once the copy that last read it has completed
-        const int k = b->next;
-        KB_TRY(hipEventSynchronize(b->ev[k]));
-        KbDesc* h = b->stage + (size_t)k * b->S;
+        hipError_t slot_wait;
+        KbDesc* h = static_cast<KbDesc*>(b->stage.take(&slot_wait));
+        APE_TRY(slot_wait);
         for (int j = 0; j < K; ++j) {
             const int s = streams_host ? streams_host[j] : j;
             h[j] = KbDesc{s, b->pending[s] ? 1 : 0, j, j};
         }
-        KB_TRY(hipMemcpyAsync(b->desc, h, (size_t)K * sizeof(KbDesc), hipMemcpyHostToDevice, st));
-        KB_TRY(hipEventRecord(b->ev[k], st));
-        b->next = (k + 1) % KB_STAGES;
+        APE_TRY(b->stage.send(b->desc, (size_t)K * sizeof(KbDesc), st));
         desc_dev = b->desc;
     }
     if (int rc = frame_launch(b, (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0, rows, desc_dev, cold_all, K, noise, init_noise, flags, out, out_dtype,
@@ -687,32 +642,29 @@ int state_launch(ape_kalman_bank* b, const int32_t* streams_host, int32_t K, con
                  const char* what) {
     if (!b->ks_desc) {
         hipError_t e = hipMalloc((void**)&b->ks_desc, (size_t)b->S * sizeof(KsDesc));
-        if (e == hipSuccess) e = hipHostMalloc((void**)&b->ks_stage, (size_t)KB_STAGES * b->S * sizeof(KsDesc), hipHostMallocDefault);
-        for (int i = 0; i < KB_STAGES && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&b->ks_ev[i], hipEventDisableTiming);
-        if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: allocation failed: %s", what, hipGetErrorString(e));
+        if (e == hipSuccess) e = b->ks_stage.alloc(b->S, sizeof(KsDesc));
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: allocation failed: %s", what, hipGetErrorString(e));
     }
     // the descriptors into the next pinned slot -- once the copy that last read it has completed (as bank_frame's lists)
-    const int k = b->ks_next;
-    KB_TRY(hipEventSynchronize(b->ks_ev[k]));
-    KsDesc* h = b->ks_stage + (size_t)k * b->S;
+    hipError_t slot_wait;
+    KsDesc* h = static_cast<KsDesc*>(b->ks_stage.take(&slot_wait));
+    APE_TRY(slot_wait);
     for (int j = 0; j < K; ++j) h[j] = KsDesc{streams_host ? streams_host[j] : j, ages_host[j], IMPORT ? import_count(b, ages_host[j]) : 0, 0};
-    KB_TRY(hipMemcpyAsync(b->ks_desc, h, (size_t)K * sizeof(KsDesc), hipMemcpyHostToDevice, st));
-    KB_TRY(hipEventRecord(b->ks_ev[k], st));
-    b->ks_next = (k + 1) % KB_STAGES;
+    APE_TRY(b->ks_stage.send(b->ks_desc, (size_t)K * sizeof(KsDesc), st));
     KsParams p{};
     p.desc = b->ks_desc; p.cnt = b->cnt; p.xwin = b->xwin; p.state = b->state; p.yring = b->yring; p.nring = b->nring; p.rec = rec;
     p.K = K; p.E = b->E; p.W = b->W; p.smooth = b->smooth; p.units = state_words(b->E, b->W, b->smooth) / 4;
     const unsigned blocks = (unsigned)(((long long)K * p.units + KB_BLOCK - 1) / KB_BLOCK);
     hipLaunchKernelGGL(ape_kalman_state_kernel<IMPORT>, dim3(blocks), dim3(KB_BLOCK), 0, st, p);
     const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bfail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
     return APE_OK;
 }
 
 int check_ages(const ape_kalman_bank* b, const int32_t* ages_host, int32_t K, const char* what) {
     for (int j = 0; j < K; ++j)
         if (ages_host[j] < 0 || ages_host[j] > b->W + 1)
-            return bfail(APE_ERR_INVALID_ARG, "%s: age %d (entry %d) outside [0, W + 1 = %d]", what, ages_host[j], j, b->W + 1);
+            return ape_fail(APE_ERR_INVALID_ARG, "%s: age %d (entry %d) outside [0, W + 1 = %d]", what, ages_host[j], j, b->W + 1);
     return APE_OK;
 }
 
@@ -721,7 +673,7 @@ int check_state_desc(const ape_kalman_bank* b, const ape_kalman_state_desc_t* de
     state_desc_of(b, &own);
     if (desc->version != own.version || desc->E != own.E || desc->W != own.W || desc->smooth != own.smooth ||
         desc->words_per_stream != own.words_per_stream)
-        return bfail(APE_ERR_INVALID_ARG, "%s: the records are {v%d E=%d W=%d smooth=%d words=%d}, the bank's {v%d E=%d W=%d smooth=%d words=%d}", what,
+        return ape_fail(APE_ERR_INVALID_ARG, "%s: the records are {v%d E=%d W=%d smooth=%d words=%d}, the bank's {v%d E=%d W=%d smooth=%d words=%d}", what,
                      desc->version, desc->E, desc->W, desc->smooth, desc->words_per_stream, own.version, own.E, own.W, own.smooth,
                      own.words_per_stream);
     return APE_OK;
@@ -743,7 +695,7 @@ void adopt_ages(ape_kalman_bank* b, const int32_t* streams_host, int32_t K, cons
 extern "C" {
 
 int ape_kalman_bank_create(ape_kalman_t* model, int32_t n_streams, int32_t smooth, ape_kalman_bank_t** out) {
-    if (!model || !out) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_create: NULL argument");
+    if (!model || !out) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_create: NULL argument");
     *out = nullptr;
     return bank_make(model, n_streams, smooth, "kalman_bank_create", out);
 }
@@ -757,7 +709,7 @@ int ape_kalman_bank_destroy(ape_kalman_bank_t* b) {
 }
 
 int ape_kalman_bank_reset(ape_kalman_bank_t* b) {
-    if (!b) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_reset: NULL bank");
+    if (!b) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_reset: NULL bank");
     b->pending.assign((size_t)b->S, 1);
     b->n_pending = b->S;
     b->age.assign((size_t)b->S, 0);
@@ -765,8 +717,8 @@ int ape_kalman_bank_reset(ape_kalman_bank_t* b) {
 }
 
 int ape_kalman_bank_reset_subset(ape_kalman_bank_t* b, const int32_t* streams_host, int32_t K) {
-    if (!b || !streams_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_reset_subset: NULL argument");
-    if (int rc = check_list(b, streams_host, K, "kalman_bank_reset_subset")) return rc;
+    if (!b || !streams_host) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_reset_subset: NULL argument");
+    if (int rc = ape_check_stream_list("kalman_bank_reset_subset", streams_host, K, b->S, true)) return rc;
     for (int j = 0; j < K; ++j) {
         if (!b->pending[streams_host[j]]) { b->pending[streams_host[j]] = 1; b->n_pending += 1; }
         b->age[streams_host[j]] = 0;
@@ -775,7 +727,7 @@ int ape_kalman_bank_reset_subset(ape_kalman_bank_t* b, const int32_t* streams_ho
 }
 
 int ape_kalman_bank_set_norm_stats(ape_kalman_bank_t* b, const double* xx_m, const double* xx_s, const double* yy_m, const double* yy_s) {
-    if (!b || !xx_m || !xx_s || !yy_m || !yy_s) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_norm_stats: NULL argument");
+    if (!b || !xx_m || !xx_s || !yy_m || !yy_s) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_set_norm_stats: NULL argument");
     memcpy(b->xx_m, xx_m, sizeof(b->xx_m));
     memcpy(b->xx_s, xx_s, sizeof(b->xx_s));
     memcpy(b->yy_m, yy_m, sizeof(b->yy_m));
@@ -785,65 +737,65 @@ int ape_kalman_bank_set_norm_stats(ape_kalman_bank_t* b, const double* xx_m, con
 }
 
 int ape_kalman_bank_set_body(ape_kalman_bank_t* b, const double body9[9]) {
-    if (!b || !body9) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_body: NULL argument");
+    if (!b || !body9) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_set_body: NULL argument");
     memcpy(b->body, body9, sizeof(b->body));
     if (b->bodies.on()) {                          // table mode: every row (ordered on the null stream: behind every blocking stream's frames)
         std::vector<double> all((size_t)b->S * 9);
         for (int s = 0; s < b->S; ++s) memcpy(&all[(size_t)s * 9], body9, 9 * sizeof(double));
-        KB_TRY(hipSetDevice(b->device));
-        KB_TRY(ape_body_table_set(b->bodies, b->S, false, b->body, nullptr, b->S, all.data(), nullptr));
+        APE_TRY(hipSetDevice(b->device));
+        APE_TRY(ape_body_table_set(b->bodies, b->S, false, b->body, nullptr, b->S, all.data(), nullptr));
     }
     return APE_OK;
 }
 
 int ape_kalman_bank_set_bodies(ape_kalman_bank_t* b, const int32_t* streams_host, int32_t K, const double* body9s_host, void* stream) {
-    if (!b || !body9s_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_bodies: NULL argument");
-    if (int rc = check_list(b, streams_host, K, "kalman_bank_set_bodies")) return rc;
-    KB_TRY(hipSetDevice(b->device));
+    if (!b || !body9s_host) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_set_bodies: NULL argument");
+    if (int rc = ape_check_stream_list("kalman_bank_set_bodies", streams_host, K, b->S, true)) return rc;
+    APE_TRY(hipSetDevice(b->device));
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "kalman_bank_set_bodies")) return rc;
-    KB_TRY(ape_body_table_set(b->bodies, b->S, false, b->body, streams_host, K, body9s_host, st));
+    APE_TRY(ape_body_table_set(b->bodies, b->S, false, b->body, streams_host, K, body9s_host, st));
     return APE_OK;
 }
 
 int ape_kalman_bank_get_bodies(ape_kalman_bank_t* b, double* out_host) {
-    if (!b || !out_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_get_bodies: NULL argument");
+    if (!b || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_get_bodies: NULL argument");
     ape_body_table_get(b->bodies, b->S, b->body, out_host);
     return APE_OK;
 }
 
 int ape_kalman_bank_set_seed(ape_kalman_bank_t* b, uint64_t seed) {
-    if (!b) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_seed: NULL bank");
+    if (!b) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_set_seed: NULL bank");
     b->seed = seed;
     b->calls = 0;
     return APE_OK;
 }
 
 int ape_kalman_bank_get_draw_position(ape_kalman_bank_t* b, uint64_t* seed, uint64_t* calls) {
-    if (!b || !seed || !calls) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_get_draw_position: NULL argument");
+    if (!b || !seed || !calls) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_get_draw_position: NULL argument");
     *seed = b->seed;
     *calls = b->calls;
     return APE_OK;
 }
 
 int ape_kalman_bank_set_draw_position(ape_kalman_bank_t* b, uint64_t seed, uint64_t calls) {
-    if (!b) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_set_draw_position: NULL bank");
+    if (!b) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_set_draw_position: NULL bank");
     b->seed = seed;
     b->calls = calls;
     return APE_OK;
 }
 
 int ape_kalman_bank_state_desc(ape_kalman_bank_t* b, ape_kalman_state_desc_t* out) {
-    if (!b || !out) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_state_desc: NULL argument");
+    if (!b || !out) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_state_desc: NULL argument");
     state_desc_of(b, out);
     return APE_OK;
 }
 
 int ape_kalman_bank_export(ape_kalman_bank_t* b, const int32_t* streams_host, int32_t K, void* state_dev, int32_t* age_host, void* stream) {
-    if (!b || !streams_host || !state_dev || !age_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_export: NULL argument");
-    if (int rc = check_list(b, streams_host, K, "kalman_bank_export")) return rc;
-    if (((uintptr_t)state_dev & 15u) != 0) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_export: state_dev must be 16-byte aligned");
-    KB_TRY(hipSetDevice(b->device));
+    if (!b || !streams_host || !state_dev || !age_host) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_export: NULL argument");
+    if (int rc = ape_check_stream_list("kalman_bank_export", streams_host, K, b->S, true)) return rc;
+    if (((uintptr_t)state_dev & 15u) != 0) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_export: state_dev must be 16-byte aligned");
+    APE_TRY(hipSetDevice(b->device));
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "kalman_bank_export")) return rc;
     if (K == 0) return APE_OK;
@@ -853,12 +805,12 @@ int ape_kalman_bank_export(ape_kalman_bank_t* b, const int32_t* streams_host, in
 
 int ape_kalman_bank_import(ape_kalman_bank_t* b, const ape_kalman_state_desc_t* desc, const int32_t* streams_host, int32_t K,
                            const void* state_dev, const int32_t* age_host, void* stream) {
-    if (!b || !desc || !streams_host || !state_dev || !age_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_import: NULL argument");
+    if (!b || !desc || !streams_host || !state_dev || !age_host) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_import: NULL argument");
     if (int rc = check_state_desc(b, desc, "kalman_bank_import")) return rc;
-    if (int rc = check_list(b, streams_host, K, "kalman_bank_import")) return rc;
+    if (int rc = ape_check_stream_list("kalman_bank_import", streams_host, K, b->S, true)) return rc;
     if (int rc = check_ages(b, age_host, K, "kalman_bank_import")) return rc;
-    if (((uintptr_t)state_dev & 15u) != 0) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_import: state_dev must be 16-byte aligned");
-    KB_TRY(hipSetDevice(b->device));
+    if (((uintptr_t)state_dev & 15u) != 0) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_import: state_dev must be 16-byte aligned");
+    APE_TRY(hipSetDevice(b->device));
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "kalman_bank_import")) return rc;
     bool carried = false;
@@ -872,12 +824,12 @@ int ape_kalman_bank_import(ape_kalman_bank_t* b, const ape_kalman_state_desc_t* 
 int ape_kalman_bank_frame(ape_kalman_bank_t* b, int32_t kind, const float* rows_dev, const int32_t* streams_host, int32_t K,
                           const float* noise_dev, const float* init_noise_dev, uint32_t flags, void* out_dev, int32_t out_dtype,
                           int32_t* n_rows_dev, float* y_dev, void* stream) {
-    if (!b || !rows_dev || !out_dev || !n_rows_dev) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: NULL argument");
+    if (!b || !rows_dev || !out_dev || !n_rows_dev) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_frame: NULL argument");
     if (int rc = check_kind(kind, "kalman_bank_frame")) return rc;
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: unknown dtype selector");
-    if (flags & ~KB_FLAGS) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
-    if (int rc = check_list(b, streams_host, K, "kalman_bank_frame")) return rc;
-    KB_TRY(hipSetDevice(b->device));
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_frame: unknown dtype selector");
+    if (flags & ~KB_FLAGS) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_frame: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
+    if (int rc = ape_check_stream_list("kalman_bank_frame", streams_host, K, b->S, true)) return rc;
+    APE_TRY(hipSetDevice(b->device));
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "kalman_bank_frame")) return rc;
     if (K == 0) return APE_OK;
@@ -887,24 +839,24 @@ int ape_kalman_bank_frame(ape_kalman_bank_t* b, int32_t kind, const float* rows_
 
 int ape_kalman_bank_frame_host(ape_kalman_bank_t* b, int32_t kind, const float* rows_host, uint32_t flags, void* out_host, int32_t out_dtype,
                                int32_t* n_rows_host, void* stream) {
-    if (!b || !rows_host || !out_host || !n_rows_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: NULL argument");
+    if (!b || !rows_host || !out_host || !n_rows_host) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: NULL argument");
     if (int rc = check_kind(kind, "kalman_bank_frame_host")) return rc;
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: unknown dtype selector");
-    if (flags & ~KB_FLAGS) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
-    KB_TRY(hipSetDevice(b->device));                         // (the consumer thread of an estimator starts on device 0)
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: unknown dtype selector");
+    if (flags & ~KB_FLAGS) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_frame_host: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
+    APE_TRY(hipSetDevice(b->device));                         // (the consumer thread of an estimator starts on device 0)
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "kalman_bank_frame_host")) return rc;
     // the head kernel reads the rows from and the tail kernel writes the messages to pinned host memory: no copy commands in the frame
     const size_t rows_bytes = (size_t)b->S * KB_WIDTH * sizeof(float);
     const size_t width = 25 + 6 * (size_t)b->smooth * b->E;                      // (h_out: room for the widest row, record included)
-    if (!b->h_rows) KB_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, hipHostMallocCoherent | hipHostMallocMapped));
-    if (!b->h_out) KB_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * (width + APE_SPREAD_WIDTH) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
-    if (!b->h_n) KB_TRY(hipHostMalloc((void**)&b->h_n, (size_t)b->S * sizeof(int), hipHostMallocCoherent | hipHostMallocMapped));
+    if (!b->h_rows) APE_TRY(hipHostMalloc((void**)&b->h_rows, rows_bytes, APE_PINNED));
+    if (!b->h_out) APE_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * (width + APE_SPREAD_WIDTH) * sizeof(double), APE_PINNED));
+    if (!b->h_n) APE_TRY(hipHostMalloc((void**)&b->h_n, (size_t)b->S * sizeof(int), APE_PINNED));
     memcpy(b->h_rows, rows_host, rows_bytes);
     if (int rc = bank_frame(b, kind, b->h_rows, nullptr, b->S, nullptr, nullptr, flags, b->h_out, out_dtype, b->h_n, nullptr, st,
                             "kalman_bank_frame_host"))
         return rc;
-    KB_TRY(hipStreamSynchronize(st));
+    APE_TRY(hipStreamSynchronize(st));
     const size_t w = ((flags & APE_FLAG_PACKED_MSG) ? width : 25) + ((flags & APE_FLAG_SPREAD) ? APE_SPREAD_WIDTH : 0);
     memcpy(out_host, b->h_out, (size_t)b->S * w * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
     memcpy(n_rows_host, b->h_n, (size_t)b->S * sizeof(int));
@@ -915,48 +867,32 @@ int ape_kalman_bank_frame_host(ape_kalman_bank_t* b, int32_t kind, const float* 
 // tail, which writes rows, counts and -- K <= 64 -- a completion word per entry into pinned memory.  BLOCKING; the block is reused.
 int ape_kalman_bank_frame_subset_host(ape_kalman_bank_t* b, int32_t kind, const float* rows_host, const int32_t* streams_host, int32_t K,
                                       uint32_t flags, void* out_host, int32_t out_dtype, int32_t* n_rows_host, void* stream) {
-    if (!b || !rows_host || !out_host || !n_rows_host) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_subset_host: NULL argument");
+    if (!b || !rows_host || !out_host || !n_rows_host) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_frame_subset_host: NULL argument");
     if (int rc = check_kind(kind, "kalman_bank_frame_subset_host")) return rc;
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_subset_host: unknown dtype selector");
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_frame_subset_host: unknown dtype selector");
     if (flags & ~KB_FLAGS)
-        return bfail(APE_ERR_INVALID_ARG, "kalman_bank_frame_subset_host: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
-    if (int rc = check_list(b, streams_host, K, "kalman_bank_frame_subset_host")) return rc;
-    KB_TRY(hipSetDevice(b->device));
+        return ape_fail(APE_ERR_INVALID_ARG, "kalman_bank_frame_subset_host: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
+    if (int rc = ape_check_stream_list("kalman_bank_frame_subset_host", streams_host, K, b->S, true)) return rc;
+    APE_TRY(hipSetDevice(b->device));
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = check_capture(st, "kalman_bank_frame_subset_host")) return rc;
     if (K == 0) return APE_OK;
     const size_t width = 25 + 6 * (size_t)b->smooth * b->E;                      // (h_out: room for the widest row, record included)
-    if (!b->hs_block) {
-        const size_t bytes = 64 * sizeof(unsigned) + (size_t)b->S * sizeof(KbDesc) + (size_t)b->S * KB_WIDTH * sizeof(float);
-        KB_TRY(hipHostMalloc((void**)&b->hs_block, bytes, hipHostMallocCoherent | hipHostMallocMapped));
-        memset(b->hs_block, 0, bytes);
-    }
-    if (!b->h_out) KB_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * (width + APE_SPREAD_WIDTH) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped));
-    if (!b->h_n) KB_TRY(hipHostMalloc((void**)&b->h_n, (size_t)b->S * sizeof(int), hipHostMallocCoherent | hipHostMallocMapped));
+    APE_TRY(ape_pinned_zeroed(&b->hs_block, 64 * sizeof(unsigned) + (size_t)b->S * sizeof(KbDesc) + (size_t)b->S * KB_WIDTH * sizeof(float)));
+    if (!b->h_out) APE_TRY(hipHostMalloc(&b->h_out, (size_t)b->S * (width + APE_SPREAD_WIDTH) * sizeof(double), APE_PINNED));
+    if (!b->h_n) APE_TRY(hipHostMalloc((void**)&b->h_n, (size_t)b->S * sizeof(int), APE_PINNED));
     unsigned* const h_done = reinterpret_cast<unsigned*>(b->hs_block);
     KbDesc* const h_desc = reinterpret_cast<KbDesc*>(b->hs_block + 64 * sizeof(unsigned));
     float* const h_rows = reinterpret_cast<float*>(b->hs_block + 64 * sizeof(unsigned) + (size_t)b->S * sizeof(KbDesc));
     const bool words = K <= 64;
-    b->hs_done_val += 1;
-    if (b->hs_done_val == 0) b->hs_done_val = 1;
+    ape_done_next(&b->hs_done_val);
     memcpy(h_rows, rows_host, (size_t)K * KB_WIDTH * sizeof(float));
     if (int rc = bank_frame(b, kind, h_rows, streams_host, K, nullptr, nullptr, flags, b->h_out, out_dtype, b->h_n, nullptr, st,
                             "kalman_bank_frame_subset_host", h_desc, words ? h_done : nullptr, b->hs_done_val)) {
         (void)hipStreamSynchronize(st);                                          // (a launched head may still read the block the next call rewrites)
         return rc;
     }
-    bool seen = false;
-    if (words) {
-        // ~50 ms of looking, then the stream's own completion (as ape_streams_frame_host)
-        volatile unsigned* dw = h_done;
-        for (long spin = 0; spin < 20000000L && !seen; ++spin) {
-            seen = true;
-            for (int k = 0; k < K; ++k) seen = seen && dw[k] == b->hs_done_val;
-            if (!seen) __builtin_ia32_pause();
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
-    }
-    if (!seen) KB_TRY(hipStreamSynchronize(st));
+    if (!(words && ape_done_wait(h_done, K, b->hs_done_val))) APE_TRY(hipStreamSynchronize(st));   // (as ape_streams_frame_host)
     const size_t w = ((flags & APE_FLAG_PACKED_MSG) ? width : 25) + ((flags & APE_FLAG_SPREAD) ? APE_SPREAD_WIDTH : 0);
     memcpy(out_host, b->h_out, (size_t)K * w * (out_dtype == APE_F64 ? sizeof(double) : sizeof(float)));
     memcpy(n_rows_host, b->h_n, (size_t)K * sizeof(int));
@@ -983,25 +919,19 @@ int ape_kalman_replay_resume(ape_kalman_t* model, int32_t kind, const float* row
                              const double body9[9], uint64_t seed, uint32_t flags, void* out_dev, int32_t out_dtype, int32_t* n_rows_dev,
                              float* y_dev, void* stream, const double* bodies_host, const void* state_in_dev, const int32_t* age_in_host,
                              void* state_out_dev, int32_t* age_out_host, uint64_t call_base) {
-    if (!model || !rows_dev || !out_dev || !n_rows_dev || (!body9 && !bodies_host)) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: NULL argument");
+    if (!model || !rows_dev || !out_dev || !n_rows_dev || (!body9 && !bodies_host)) return ape_fail(APE_ERR_INVALID_ARG, "kalman_replay: NULL argument");
     if (int rc = check_kind(kind, "kalman_replay")) return rc;
-    if (F < 1) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: F=%d must be >= 1", F);
-    if (R < 1 || R > F) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: %d recording starts for %d frames (1 <= R <= F)", R, F);
-    if (!seg_starts_host) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: NULL seg_starts");
-    if (seg_starts_host[0] != 0) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: seg_starts[0] = %d, must be 0", seg_starts_host[0]);
-    for (int i = 1; i < R; ++i)
-        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
-            return bfail(APE_ERR_INVALID_ARG, "kalman_replay: seg_starts[%d] = %d (strictly rising, below F = %d)", i, seg_starts_host[i], F);
-    if (smooth > KB_MAX_SMOOTH) return bfail(APE_ERR_UNSUPPORTED, "kalman_replay: smooth %d outside 1..%d", smooth, KB_MAX_SMOOTH);
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: unknown dtype selector");
-    if (flags & ~KB_FLAGS) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
+    if (int rc = ape_check_segments("kalman_replay", F, seg_starts_host, R)) return rc;
+    if (smooth > KB_MAX_SMOOTH) return ape_fail(APE_ERR_UNSUPPORTED, "kalman_replay: smooth %d outside 1..%d", smooth, KB_MAX_SMOOTH);
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "kalman_replay: unknown dtype selector");
+    if (flags & ~KB_FLAGS) return ape_fail(APE_ERR_INVALID_ARG, "kalman_replay: flags 0x%x: APE_FLAG_PACKED_MSG and / or APE_FLAG_SPREAD, or 0", flags);
     const bool any = xx_m || xx_s || yy_m || yy_s;
-    if (any && !(xx_m && xx_s && yy_m && yy_s)) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: all four statistics or none");
-    if (R > 65535) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: %d recordings, at most 65535 in one call", R);
-    if (!state_in_dev != !age_in_host) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: state_in and age_in come together or not at all");
-    if (!state_out_dev != !age_out_host) return bfail(APE_ERR_INVALID_ARG, "kalman_replay: state_out and age_out come together or not at all");
+    if (any && !(xx_m && xx_s && yy_m && yy_s)) return ape_fail(APE_ERR_INVALID_ARG, "kalman_replay: all four statistics or none");
+    if (R > 65535) return ape_fail(APE_ERR_INVALID_ARG, "kalman_replay: %d recordings, at most 65535 in one call", R);
+    if (!state_in_dev != !age_in_host) return ape_fail(APE_ERR_INVALID_ARG, "kalman_replay: state_in and age_in come together or not at all");
+    if (!state_out_dev != !age_out_host) return ape_fail(APE_ERR_INVALID_ARG, "kalman_replay: state_out and age_out come together or not at all");
     if ((((uintptr_t)state_in_dev) | ((uintptr_t)state_out_dev)) & 15u)
-        return bfail(APE_ERR_INVALID_ARG, "kalman_replay: the record buffers must be 16-byte aligned");
+        return ape_fail(APE_ERR_INVALID_ARG, "kalman_replay: the record buffers must be 16-byte aligned");
     // ---- from here on the model is read.  The replay is a fresh bank of R streams: frame t lists the recordings that have a row t
     struct Holder {
         ape_kalman_bank* b = nullptr;
@@ -1017,7 +947,7 @@ int ape_kalman_replay_resume(ape_kalman_t* model, int32_t kind, const float* row
     if (any) (void)ape_kalman_bank_set_norm_stats(b, xx_m, xx_s, yy_m, yy_s);
     if (body9) memcpy(b->body, body9, sizeof(b->body));
     // one body per recording: the replay's bank has a stream per recording, so the table's row r is recording r's
-    if (bodies_host) KB_TRY(ape_body_table_set(b->bodies, R, false, b->body, nullptr, R, bodies_host, st));
+    if (bodies_host) APE_TRY(ape_body_table_set(b->bodies, R, false, b->body, nullptr, R, bodies_host, st));
     b->seed = seed;
     b->calls = call_base;
     // recordings that carry a state continue from it: the import writes their rings and counts, their first frame is no cold start
@@ -1040,8 +970,8 @@ int ape_kalman_replay_resume(ape_kalman_t* model, int32_t kind, const float* row
                 descs.push_back(KbDesc{r, t == 0 && !(age_in_host && age_in_host[r] > 0) ? 1 : 0, seg_starts_host[r] + t, seg_starts_host[r] + t});
         first[t + 1] = (int)descs.size();
     }
-    KB_TRY(hipMalloc(&hold.descs, descs.size() * sizeof(KbDesc)));
-    KB_TRY(hipMemcpyAsync(hold.descs, descs.data(), descs.size() * sizeof(KbDesc), hipMemcpyHostToDevice, st));
+    APE_TRY(hipMalloc(&hold.descs, descs.size() * sizeof(KbDesc)));
+    APE_TRY(hipMemcpyAsync(hold.descs, descs.data(), descs.size() * sizeof(KbDesc), hipMemcpyHostToDevice, st));
     int rc = APE_OK;
     for (int t = 0; t < longest && rc == APE_OK; ++t)
         rc = frame_launch(b, (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0, rows_dev, (const KbDesc*)hold.descs + first[t], 0, first[t + 1] - first[t],
@@ -1055,7 +985,7 @@ int ape_kalman_replay_resume(ape_kalman_t* model, int32_t kind, const float* row
     }
     const hipError_t e = hipStreamSynchronize(st);            // the bank and the lists are freed behind this
     if (rc != APE_OK) return rc;
-    if (e != hipSuccess) return bfail(APE_ERR_HIP, "kalman_replay: synchronise failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "kalman_replay: synchronise failed: %s", hipGetErrorString(e));
     return APE_OK;
 }
 

@@ -17,9 +17,9 @@
 #include "ape_internal.h"
 #include "../../include/ape_hip.h"
 #include "fk_device.h"
+#include "bank_host.h"
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <mutex>
@@ -603,20 +603,8 @@ __global__ __launch_bounds__(SC_BLOCK) void ape_score_lags_acc_kernel(const doub
     }
 }
 
-int sfail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof(buf), fmt, ap);
-    va_end(ap);
-    return ape_set_error(code, buf);
-}
-
-#define SC_TRY(expr)                                                                                              \
-    do {                                                                                                          \
-        hipError_t _e = (expr);                                                                                   \
-        if (_e != hipSuccess) return sfail(APE_ERR_HIP, "score_rows: %s failed: %s", #expr, hipGetErrorString(_e)); \
-    } while (0)
+// (APE_TRY with the entry's name in front)
+#define SC_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return ape_fail(APE_ERR_HIP, "score_rows: %s failed: %s", #expr, hipGetErrorString(_e)); } while (0)
 
 // The call's staging: a pinned block the host arrays are copied into (so they are consumed when the call returns and the copy to the
 // device needs no wait) and the device block behind it (starts, bodies, partial records).  A slot is taken again once the event recorded
@@ -657,7 +645,7 @@ int take_slot(int device, size_t pbytes, size_t dbytes, Slot** out) {
         const hipError_t e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
         if (e != hipSuccess) {
             delete s;
-            return sfail(APE_ERR_HIP, "score_rows: hipEventCreate failed: %s", hipGetErrorString(e));
+            return ape_fail(APE_ERR_HIP, "score_rows: hipEventCreate failed: %s", hipGetErrorString(e));
         }
         g_slots.push_back(s);
     }
@@ -708,24 +696,19 @@ int check_score_args(const char* who, int32_t layout, const void* msg_dev, int32
                      int32_t msg_dtype, const void* truth_dev, int32_t truth_kind, int32_t truth_dtype, int32_t F, const int32_t* seg_starts_host,
                      int32_t R, int32_t skip, const double* bodies_host, int32_t n_bodies, const void* score_dev, int32_t score_dtype,
                      const void* acc_dev) {
-    if (!msg_dev || !truth_dev || !seg_starts_host || !bodies_host) return sfail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (!score_dev && !acc_dev) return sfail(APE_ERR_INVALID_ARG, "%s: score_dev and acc_dev are both NULL", who);
+    if (!msg_dev || !truth_dev || !seg_starts_host || !bodies_host) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (!score_dev && !acc_dev) return ape_fail(APE_ERR_INVALID_ARG, "%s: score_dev and acc_dev are both NULL", who);
     if (layout != APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS && layout != APE_LAYOUT_ORI_CAL_LARM_UARM && layout != APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS)
-        return sfail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to score", who, layout);
-    if (truth_kind != APE_TRUTH_TARGETS && truth_kind != APE_TRUTH_EST) return sfail(APE_ERR_INVALID_ARG, "%s: unknown truth kind %d", who, truth_kind);
+        return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to score", who, layout);
+    if (truth_kind != APE_TRUTH_TARGETS && truth_kind != APE_TRUTH_EST) return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown truth kind %d", who, truth_kind);
     if ((msg_dtype != APE_F32 && msg_dtype != APE_F64) || (truth_dtype != APE_F32 && truth_dtype != APE_F64) ||
         (score_dtype != APE_F32 && score_dtype != APE_F64))
-        return sfail(APE_ERR_INVALID_ARG, "%s: unknown dtype selector", who);
-    if (F < 1) return sfail(APE_ERR_INVALID_ARG, "%s: F=%d must be >= 1", who, F);
-    if (R < 1 || R > F) return sfail(APE_ERR_INVALID_ARG, "%s: %d recording starts for %d frames (1 <= R <= F)", who, R, F);
-    if (seg_starts_host[0] != 0) return sfail(APE_ERR_INVALID_ARG, "%s: seg_starts[0] = %d, must be 0", who, seg_starts_host[0]);
-    for (int i = 1; i < R; ++i)
-        if (seg_starts_host[i] <= seg_starts_host[i - 1] || seg_starts_host[i] >= F)
-            return sfail(APE_ERR_INVALID_ARG, "%s: seg_starts[%d] = %d (strictly rising, below F = %d)", who, i, seg_starts_host[i], F);
-    if (msg_stride < 25) return sfail(APE_ERR_INVALID_ARG, "%s: msg_stride %d below 25", who, msg_stride);
-    if (spread_dev && spread_stride < APE_SPREAD_WIDTH) return sfail(APE_ERR_INVALID_ARG, "%s: spread_stride %d below %d", who, spread_stride, APE_SPREAD_WIDTH);
-    if (skip < 0) return sfail(APE_ERR_INVALID_ARG, "%s: skip %d is negative", who, skip);
-    if (n_bodies != 1 && n_bodies != R) return sfail(APE_ERR_INVALID_ARG, "%s: n_bodies %d is neither 1 nor R = %d", who, n_bodies, R);
+        return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown dtype selector", who);
+    if (int rc = ape_check_segments(who, F, seg_starts_host, R)) return rc;      // (NULL starts: refused above)
+    if (msg_stride < 25) return ape_fail(APE_ERR_INVALID_ARG, "%s: msg_stride %d below 25", who, msg_stride);
+    if (spread_dev && spread_stride < APE_SPREAD_WIDTH) return ape_fail(APE_ERR_INVALID_ARG, "%s: spread_stride %d below %d", who, spread_stride, APE_SPREAD_WIDTH);
+    if (skip < 0) return ape_fail(APE_ERR_INVALID_ARG, "%s: skip %d is negative", who, skip);
+    if (n_bodies != 1 && n_bodies != R) return ape_fail(APE_ERR_INVALID_ARG, "%s: n_bodies %d is neither 1 nor R = %d", who, n_bodies, R);
     return APE_OK;
 }
 
@@ -739,9 +722,7 @@ int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
                                   seg_starts_host, R, skip, bodies_host, n_bodies, score_dev, score_dtype, acc_dev))
         return rc;
     const hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    SC_TRY(hipStreamIsCapturing(st, &cap));
-    if (cap != hipStreamCaptureStatusNone) return sfail(APE_ERR_INVALID_ARG, "score_rows: the stream is capturing (host arrays are staged per call)");
+    if (int rc = ape_check_not_capturing(st, "score_rows", "host arrays are staged per call")) return rc;
     int device = 0;
     SC_TRY(hipGetDevice(&device));
 
@@ -781,10 +762,10 @@ int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     }
     const hipError_t er = hipEventRecord(slot->done, st);  // the slot is in flight whatever became of the launches
     slot->used = er == hipSuccess;
-    if (e != hipSuccess) return sfail(APE_ERR_HIP, "score_rows: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "score_rows: launch failed: %s", hipGetErrorString(e));
     if (er != hipSuccess) {
         (void)hipStreamSynchronize(st);
-        return sfail(APE_ERR_HIP, "score_rows: hipEventRecord failed: %s", hipGetErrorString(er));
+        return ape_fail(APE_ERR_HIP, "score_rows: hipEventRecord failed: %s", hipGetErrorString(er));
     }
     return APE_OK;
 }
@@ -797,22 +778,20 @@ int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     if (int rc = check_score_args("score_lags", layout, msg_dev, msg_stride, spread_dev, spread_stride, msg_dtype, truth_dev, truth_kind, truth_dtype, F,
                                   seg_starts_host, R, skip, bodies_host, n_bodies, score_dev, score_dtype, acc_dev))
         return rc;
-    if (lag_min > lag_max) return sfail(APE_ERR_INVALID_ARG, "score_lags: lag_min %d above lag_max %d", lag_min, lag_max);
+    if (lag_min > lag_max) return ape_fail(APE_ERR_INVALID_ARG, "score_lags: lag_min %d above lag_max %d", lag_min, lag_max);
     const long long span = (long long)lag_max - (long long)lag_min + 1;
-    if (span > APE_SCORE_MAX_LAGS) return sfail(APE_ERR_INVALID_ARG, "score_lags: %lld lags in the sweep, at most %d", span, APE_SCORE_MAX_LAGS);
+    if (span > APE_SCORE_MAX_LAGS) return ape_fail(APE_ERR_INVALID_ARG, "score_lags: %lld lags in the sweep, at most %d", span, APE_SCORE_MAX_LAGS);
     const int L = (int)span;
     long long top = lag_max, bottom = lag_min;          // the largest and the smallest lag of any pair
     for (int r = 0; r < R; ++r) {
         const long long o = rec_lag_host ? rec_lag_host[r] : 0, lo = o + lag_min, hi = o + lag_max;
         if (lo < -APE_SCORE_MAX_LAG || lo > APE_SCORE_MAX_LAG || hi < -APE_SCORE_MAX_LAG || hi > APE_SCORE_MAX_LAG)
-            return sfail(APE_ERR_INVALID_ARG, "score_lags: recording %d: lags %lld .. %lld, |lag| is at most %d", r, lo, hi, APE_SCORE_MAX_LAG);
+            return ape_fail(APE_ERR_INVALID_ARG, "score_lags: recording %d: lags %lld .. %lld, |lag| is at most %d", r, lo, hi, APE_SCORE_MAX_LAG);
         top = r == 0 || hi > top ? hi : top;
         bottom = r == 0 || lo < bottom ? lo : bottom;
     }
     const hipStream_t st = (hipStream_t)stream;
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    SC_TRY(hipStreamIsCapturing(st, &cap));
-    if (cap != hipStreamCaptureStatusNone) return sfail(APE_ERR_INVALID_ARG, "score_lags: the stream is capturing (host arrays are staged per call)");
+    if (int rc = ape_check_not_capturing(st, "score_lags", "host arrays are staged per call")) return rc;
     int device = 0;
     SC_TRY(hipGetDevice(&device));
 
@@ -861,10 +840,10 @@ int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     }
     const hipError_t er = hipEventRecord(slot->done, st);  // the slot is in flight whatever became of the launches
     slot->used = er == hipSuccess;
-    if (e != hipSuccess) return sfail(APE_ERR_HIP, "score_lags: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "score_lags: launch failed: %s", hipGetErrorString(e));
     if (er != hipSuccess) {
         (void)hipStreamSynchronize(st);
-        return sfail(APE_ERR_HIP, "score_lags: hipEventRecord failed: %s", hipGetErrorString(er));
+        return ape_fail(APE_ERR_HIP, "score_lags: hipEventRecord failed: %s", hipGetErrorString(er));
     }
     return APE_OK;
 }

@@ -159,6 +159,36 @@ def test_bank_subset_frames_against_fresh_estimators():
         np.testing.assert_array_equal(got[s], ests[s].process_row(rows[s]))
 
 
+def test_bank_subset_frames_back_to_back():
+    """20 subset frames enqueued with no host synchronisation in between (rows already on the device): the pinned descriptor ring
+    (csrc/bank_host.h) wraps more than twice, and a slot rewritten before its copy had run would hand a frame another frame's list.
+    Bit-equal to the same frames with a device synchronisation after each, and to fresh estimators fed each stream's rows."""
+    from wear_mocap_ape_amd.streams import FkStreamBank
+    S, smooth, frames = 5, 2, 20
+    rng = np.random.default_rng(21)
+    lists = [rng.choice(S, size=int(rng.integers(1, S + 1)), replace=False) for _ in range(frames)]
+    rows = [_random_rows(rng, len(l)) for l in lists]
+    rows_dev = [torch.from_numpy(r).cuda() for r in rows]
+
+    def run(sync):
+        bank = FkStreamBank(S, smooth=smooth, dtype=torch.float64)
+        torch.cuda.synchronize()
+        outs = []
+        for rd, l in zip(rows_dev, lists):
+            outs.append(bank.frame(rd, l).clone())          # (the bank's buffer is overwritten by the next frame)
+            if sync:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        return [o.cpu().numpy() for o in outs]
+
+    queued, synced = run(False), run(True)
+    ests = [_est(smooth=smooth) for _ in range(S)]
+    for f, l in enumerate(lists):
+        np.testing.assert_array_equal(queued[f], synced[f], err_msg=f"frame {f}")
+        for j, s in enumerate(l):
+            np.testing.assert_array_equal(queued[f][j], ests[s].process_row(rows[f][j]), err_msg=f"frame {f} stream {s}")
+
+
 def test_bank_unlisted_streams_untouched_and_refusals():
     from wear_mocap_ape_amd import _hip
     from wear_mocap_ape_amd.streams import FkStreamBank

@@ -188,6 +188,49 @@ def test_unlisted_streams_are_untouched(norm_stats):
     a.check()
 
 
+def test_subset_frames_back_to_back(norm_stats):
+    """20 subset frames enqueued with no host synchronisation in between (rows and draws already on the device): the pinned ring of
+    stream lists (csrc/bank_host.h) wraps more than twice.  Bit-equal to the same frames with a device synchronisation after each,
+    and every stream within the suite's bounds of its own oracle chain."""
+    E, W, S, smooth, frames = 16, 4, 3, 2, 20
+    stats = pocket_stats(norm_stats)
+    m, sd = make_model(E, W, 24)
+    rng = np.random.default_rng(24)
+    # two of the three streams per frame, scrambled: 13, 13 and 14 frames per stream (the feedback length the target bound is stated for)
+    lists = [[int(s) for s in rng.permutation([s for s in range(S) if s != f % S])] for f in range(frames)]
+    rows = [make_rows(rng, 2) for _ in lists]
+    draws = [(ko.draw_noise(rng, W, 2 * E), rng.standard_normal((2, E, 14)).astype(np.float32)) for _ in lists]
+    dev = [(torch.from_numpy(r).cuda(), torch.from_numpy(pack_noise(nz)).cuda(), torch.from_numpy(init).cuda())
+           for r, (nz, init) in zip(rows, draws)]
+
+    def run(sync):
+        bank = make_bank(m, S, smooth, stats)
+        torch.cuda.synchronize()
+        res = []
+        for (rd, blob, ini), order in zip(dev, lists):
+            res.append(tuple(t.clone() for t in bank.frame(rd, order, datagrams=True, noise=blob, init_noise=ini, return_targets=True)))
+            if sync:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        bank.check()
+        return [tuple(t.cpu().numpy() for t in r) for r in res]
+
+    queued, synced = run(False), run(True)
+    oracles = [new_oracle(sd, E, W, smooth, stats) for _ in range(S)]
+    seen = [0] * S
+    for f, order in enumerate(lists):
+        (out, n, y), (out_s, n_s, y_s) = queued[f], synced[f]
+        np.testing.assert_array_equal(out, out_s, err_msg=f"frame {f}")
+        np.testing.assert_array_equal(n, n_s, err_msg=f"frame {f}")
+        nz, init = draws[f]
+        for j, s in enumerate(order):
+            k = 1 if seen[s] <= W else E                        # (an init frame's prediction is row 0 of y alone)
+            np.testing.assert_array_equal(y[j, :k], y_s[j, :k], err_msg=f"frame {f} stream {s}")
+            oracles[s].check(rows[f][j], slice_noise(nz, j, E), init[j], y[j], int(n[j]), out[j], f"back to back frame {f} stream {s}")
+            seen[s] += 1
+    assert seen == [13, 13, 14]
+
+
 def _frame_host(bank, rows, big_endian=False, packed=True):
     from wear_mocap_ape_amd import _hip
     S, w = bank.n_streams, bank.packed_width if packed else 25

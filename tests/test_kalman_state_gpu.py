@@ -132,6 +132,52 @@ def test_the_record_is_canonical(norm_stats, E, W, smooth, n):
     m.check()
 
 
+def test_exports_back_to_back(norm_stats):
+    """12 exports of two of three streams, each into its own buffer, with no host synchronisation in between: the hand-over's pinned
+    descriptor ring (csrc/bank_host.h) wraps.  Bit-equal to the same calls with a device synchronisation after each, and every
+    record is the canonical one of its stream (the checks of test_the_record_is_canonical)."""
+    from wear_mocap_ape_amd import stream_state as ss
+    E, W, S, smooth = 16, 4, 3, 2
+    stats = pocket_stats(norm_stats)
+    m, _ = make_model(E, W, 35)
+    a = make_bank(m, S, smooth, stats)
+    desc = a.state_desc()
+    rng = np.random.default_rng(35)
+    ages = [2, 6, 9]                                        # init phase, the first ensemble frame behind it, mature
+    last = {}
+    for s, n in enumerate(ages):
+        rows = make_rows(rng, n)
+        for f in range(n):
+            nz, init = draws(rng, W, E)
+            out, cnt, y = run_frame(a, rows[f:f + 1], [s], nz, init)
+        last[s] = (rows[n - 1], int(cnt[0]), y[0])
+    pairs = [[t % S, (t + 1 + t // S % 2) % S] for t in range(12)]
+
+    def run(sync):
+        torch.cuda.synchronize()
+        res = []
+        for p in pairs:
+            res.append(a.export_state(p))
+            if sync:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        return [(state.cpu().numpy(), age.copy()) for state, age in res]
+
+    queued, synced = run(False), run(True)
+    for p, (sq, aq), (sy, ay) in zip(pairs, queued, synced):
+        np.testing.assert_array_equal(sq.view(np.int32), sy.view(np.int32), err_msg=str(p))
+        assert aq.tolist() == ay.tolist() == [min(ages[s], W + 1) for s in p]
+        for j, s in enumerate(p):
+            row, cnt, y = last[s]
+            window, history, stack, counts, pad = ss.kalman_unpack(sq[j], desc)
+            k = n_new(ages[s] - 1, W, E)
+            assert counts.tolist() == expected_counts(ages[s], W, E, smooth) and cnt == int(counts.sum()), (p, s)
+            np.testing.assert_array_equal(stack[-1, :k], y[:k])
+            assert np.abs(window[-1] - features(row)).max() < 1e-6           # (test_the_record_is_canonical's bound)
+            assert not pad.view(np.int32).any()
+    m.check()
+
+
 # ---- 3. untouched streams -------------------------------------------------------------------------------------------------------------
 def test_import_and_export_leave_other_streams_untouched(norm_stats):
     E, W, S, smooth = 16, 4, 5, 2

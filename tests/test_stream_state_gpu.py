@@ -106,6 +106,43 @@ def test_migration_across_slot_phase(golden, tmp_path, monkeypatch):
     model.set_kernel("auto")
 
 
+def test_exports_back_to_back(golden, tmp_path, monkeypatch):
+    """12 exports of two of three streams, each into its own buffer, with no host synchronisation in between: the pinned descriptor
+    ring the hand-over shares with the subset frames (csrc/bank_host.h) wraps, and a slot rewritten before its copy had run would
+    export another call's streams.  Bit-equal to the same calls with a device synchronisation after each and to the bank's full
+    export; a twin that imports the last call's records continues with the bank's bits."""
+    est = _estimator(tmp_path, monkeypatch, "pocket", 8, 0.0, smooth=5, add_mc_samples=True, monte_carlo_samples=1)
+    model, kind = est._hip_model(), est._parse_kind
+    model.set_kernel("tile16")
+    S, T, smooth = 3, 6, 5
+    pool = _synthetic_rows(golden, "pocket", S * 8, 8).reshape(8, S, -1)
+    a = _bank(model, S, T, smooth)
+    for t in range(7):                                      # every stream at a ring phase of its own
+        _frame(a, kind, pool[t, _schedule(S, t)], _schedule(S, t))
+    pairs = [[t % S, (t + 1 + t // S % 2) % S] for t in range(12)]
+
+    def run(sync):
+        torch.cuda.synchronize()
+        res = []
+        for p in pairs:
+            res.append(a.export_state(p))
+            if sync:
+                torch.cuda.synchronize()
+        torch.cuda.synchronize()
+        return [(state.cpu().numpy(), warm.copy()) for state, warm in res]
+
+    queued, synced = run(False), run(True)
+    whole, warm_all = _all(a)
+    for p, (sq, wq), (ss, ws) in zip(pairs, queued, synced):
+        assert np.array_equal(sq.view(np.uint32), ss.view(np.uint32)) and np.array_equal(wq, ws), p
+        assert np.array_equal(sq.view(np.uint32), whole[p].view(np.uint32)) and np.array_equal(wq, warm_all[p]), p
+    b = _bank(model, S, T, smooth)
+    b.import_state(pairs[-1], queued[-1][0], queued[-1][1], a.state_desc())
+    rows = pool[7, pairs[-1]]
+    assert np.array_equal(_frame(a, kind, rows, pairs[-1]), _frame(b, kind, rows, pairs[-1]))
+    model.set_kernel("auto")
+
+
 def test_cold_and_half_warm_streams(golden, tmp_path, monkeypatch):
     est = _estimator(tmp_path, monkeypatch, "pocket", 5, 0.0, smooth=5, add_mc_samples=True, monte_carlo_samples=1)
     model, kind = est._hip_model(), est._parse_kind
