@@ -83,6 +83,31 @@ enum { APE_F32 = 0, APE_F64 = 1 };   /* element type selector for preds / est bu
                                          after monte_carlo_predictions, nn_models.py:204)               */
 #define APE_FLAG_DROPOUT_PHILOX  0x8u /* inter-layer dropout with an in-kernel counter-based generator  */
 
+/* ---- Random numbers: the counter and key layout of every device-side draw (PART OF THE CONTRACT) ------------------------------------
+ * Every draw is Philox4x32-10 (Salmon et al. 2011; multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85) of a
+ * 128-bit counter (c0, c1, c2, c3) under the 64-bit key of the call: k0 = seed & 0xFFFFFFFF, k1 = seed >> 32.  A draw is therefore a
+ * function of (row, step, unit, layer, seed) alone -- never of the kernel, the launch split or the placement -- which is what
+ * sample_row_base, the chunked launches and the stream-state hand-over rely on, and what lets a host compute the very numbers
+ * (oracle/philox.py; tests/test_philox_routes_gpu.py and tests/test_kalman_draws_gpu.py hold every route to it).
+ *   LSTM dropout     multiplier on the output of model layer l < L-1, global row b of the call, step t, hidden unit u:
+ *                    counter (b & ~3, t, u, l), word b & 3;  uf = float(w >> 8) * 2^-24;  keep iff uf >= dropout_p, multiplier
+ *                    1.0f / (1.0f - dropout_p).  Global row: the row of the caller's batch whatever the launch split; stream * n_mc + sample
+ *                    in a lockstep bank frame; list position * n_mc + sample in a subset frame; frame * n_mc + sample (+ sample_row_base)
+ *                    in a replay.  Keys: `seed` as given to ape_lstm_forward / ape_replay*; seed + c in a bank, c = the Monte-Carlo
+ *                    frames the bank has issued since ape_streams_set_mc (lockstep and subset frames count alike; no reset rewinds it).
+ *   DropoutFF        batch kernel: counter (row & ~3, 0, column, 0xFF), word row & 3, row = the row of the call;
+ *                    bank / replay head: counter (lo32(r), hi32(r), unit >> 2, 0xFE), word unit & 3, r = global sample row + sample_row_base.
+ *                    Same uf, comparison and multiplier.
+ *   Kalman normals   standard normal number idx of stream `tag`: counter (idx >> 2, tag, 0x4B414C4D, 0), Box-Muller on the word pair
+ *                    (idx >> 1) & 1:  u = (float(w[2 pair] >> 8) + 1) * 2^-24,  r = sqrtf(-2 logf(u)),
+ *                    a = (6.2831855f * float(w[2 pair + 1])) * 2^-32,  r cosf(a) for even idx, r sinf(a) for odd.
+ *                    tag 0x100 + 2 j: weight perturbation of flipout layer j (idx = n * K + k), 0x101 + 2 j: its bias perturbation;
+ *                    tag 0x300: format_state and the bank's init draws (idx = flat index of [K, E, 14]).
+ *   Kalman signs     +-1 number (row r, column c) of sign stream `tag`: counter (c >> 7, r, tag, 0x5349474E), word (c >> 5) & 3,
+ *                    bit c & 31, set = -1.  tag 0x200 + 2 i: sign_in of the layer with blob index i, 0x201 + 2 i: its sign_out.
+ *   Kalman keys      call number n (1 for the first) after the seed was set: seed + 0xD1342543DE82EF95 * n mod 2^64; one key for all
+ *                    draws of a forward / format_state / bank frame. */
+
 /* LSTM kernel selection (ape_model_set_kernel).  AUTO = the weight-stationary cluster kernel where it is
  * built (H=256/L=2/I<=32 and H=128/L=3/32<I<=64; dropout up to 32 windows per cluster), else the batch-tile kernel. */
 enum { APE_KERNEL_AUTO = 0, APE_KERNEL_TILE16 = 1, APE_KERNEL_CLUSTER = 2,
@@ -255,7 +280,7 @@ int ape_parse_rows(int32_t kind, const float* rows_dev, int32_t N, void* xx_dev,
  *   ape_streams_set_mc         Monte-Carlo dropout per stream, as every reference estimator runs it
  *                              (monte_carlo_samples, watch_phone_pocket_nn.py:105-110 -> nn_models.py:191-207): each
  *                              frame runs every stream's window n_mc times with independent inter-layer dropout
- *                              masks (in-kernel Philox, keyed by `seed` + a per-step counter), the smoothing stack
+ *                              masks (in-kernel Philox, keyed by `seed` + the bank's frame counter: "Random numbers" above), the smoothing stack
  *                              holds smooth x n_mc rows per stream in the reference's order (estimator.py:112-118:
  *                              oldest prediction first, its n_mc samples in order), tail_dev becomes
  *                              [S, smooth*n_mc, 6].  dropout_p = 0 gives n_mc identical samples.  Call it before the

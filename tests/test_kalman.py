@@ -7,7 +7,8 @@ Tolerances (float32 path, stated per test): on injected draws every output of a 
 oracle's float64 evaluation, ``e_ref`` being the distance of the oracle's own float32 evaluation (with the kernel's algorithm
 for the inverse, float32 Gauss-Jordan with partial pivoting) from that reference on the same inputs -- the rule, the shapes at
 the kernels' edges and the hostile regimes are in tests/test_kalman_numerics_gpu.py; chained frames (feedback of the state)
-keep their absolute bounds; device-side draws (Philox) only statistically."""
+keep their absolute bounds; device-side draws (Philox) statistically here, and draw for draw against the host replica in
+tests/test_kalman_draws_gpu.py."""
 import ctypes as C
 
 import numpy as np
