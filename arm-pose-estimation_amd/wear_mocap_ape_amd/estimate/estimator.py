@@ -530,7 +530,8 @@ class Estimator:
     # ---- offline replay: every frame of recorded sessions in one call ----
     def process_recording(self, rows, starts=None, big_endian: bool = False, out_dtype=torch.float64,
                           return_targets: bool = False, seed: int = 0x5EED, max_rows_per_launch: int = 0, bonemaps=None,
-                          state_in=None, warm_in=None, return_state: bool = False, sample_row_base: int = 0, spread: bool = False):
+                          state_in=None, warm_in=None, return_state: bool = False, sample_row_base: int = 0, spread: bool = False,
+                          _config=None):
         """rows: float32 ``[F, 55|28]`` raw messages of one or more recordings back to back (host array or CUDA
         tensor); ``starts``: the recordings' first rows (default ``[0]``: one recording).  Returns, on the device,
         what ``process_row`` returns for every row of a fresh estimator fed each recording in order (no row skipped):
@@ -556,7 +557,10 @@ class Estimator:
 
         ``spread``: the result becomes ``(out, spread)`` (``(out, y, spread)`` with ``return_targets``; the state pair stays last) with
         ``spread`` ``[F, 21]`` of ``out_dtype``, every frame's spread record (``_post.spread_rows``); both are views
-        of one wider device tensor.  Chained pieces give the records of the one call."""
+        of one wider device tensor.  Chained pieces give the records of the one call.
+
+        ``_config`` (``sweep_recording``): ``(smooth, samples)`` for this call in place of the estimator's own, which stay as they
+        are; the rows are then never packed."""
         import ctypes as C
         from wear_mocap_ape_amd import _hip
         model, n_mc = self._hip_model(), self._frame_samples()
@@ -566,8 +570,11 @@ class Estimator:
         if out_dtype not in (torch.float32, torch.float64):
             raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
         from wear_mocap_ape_amd.estimate.nn_models import DropoutFF, ImuPoseLSTM, effective_mc
+        smooth = self._smooth
+        if _config is not None:
+            smooth, n_mc = int(_config[0]), int(_config[1])
         n_mc = effective_mc(model, n_mc)
-        n_rows = self._smooth * n_mc
+        n_rows = smooth * n_mc
         # (DropoutLSTM models keep the entry they always took)
         entry = "ape_replay_regressor" if isinstance(model, (DropoutFF, ImuPoseLSTM)) else "ape_replay_bodies"
         dev = model.torch_device
@@ -577,7 +584,7 @@ class Estimator:
                 raise UserWarning(f"expected rows [F>=1,{width}], got {tuple(rd.shape)}")
             F = int(rd.shape[0])
             st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
-            packed = self._add_mc_samples and n_rows > 1
+            packed = self._add_mc_samples and n_rows > 1 and _config is None
             out = torch.empty((F, (25 + 6 * n_rows if packed else 25) + (_hip.SPREAD_WIDTH if spread else 0)), dtype=out_dtype, device=dev)
             y = torch.empty((F, n_mc, model.output_size), dtype=torch.float32, device=dev) if return_targets else None
             flags = (_hip.FLAG_NORMALIZE_INPUT if self._normalize else 0) | (_hip.FLAG_PACKED_MSG if packed else 0) | \
@@ -589,7 +596,7 @@ class Estimator:
             if state_in is not None or return_state or sample_row_base:
                 from wear_mocap_ape_amd import stream_state as ss
                 entry, n_rec = "ape_replay_resume", int(st.shape[0])
-                words = ss.words_per_stream(1 if isinstance(model, DropoutFF) else self._sequence_len, model.input_size, self._smooth,
+                words = ss.words_per_stream(1 if isinstance(model, DropoutFF) else self._sequence_len, model.input_size, smooth,
                                             n_mc, model.output_size)
                 sin = win = None
                 if state_in is not None:
@@ -607,7 +614,7 @@ class Estimator:
                          C.c_void_p(state_out.data_ptr()) if return_state else None,
                          C.c_void_p(warm_out.ctypes.data) if return_state else None, int(sample_row_base))
             _hip.check(getattr(_hip.lib(), entry)(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
-                                                    int(st.shape[0]), self._sequence_len, self._smooth, n_mc, float(model.dropout),
+                                                    int(st.shape[0]), self._sequence_len, smooth, n_mc, float(model.dropout),
                                                     int(seed) & (2 ** 64 - 1), flags, C.c_void_p(out.data_ptr()),
                                                     _hip.F64 if out_dtype == torch.float64 else _hip.F32,
                                                     C.c_void_p(y.data_ptr()) if y is not None else None,
@@ -641,6 +648,49 @@ class Estimator:
                 raise UserWarning("rec_lags are offsets of a sweep: give lags=(lo, hi) with them")
             return score.score_rows(self._layout, out, truth, truth_kind, spread, starts, skip, bodies)
         return score.score_lags(self._layout, out, truth, lags, truth_kind, spread, starts, skip, bodies, rec_lags, per_frame=True)
+
+    # ---- post-filter sweep (the reference has no counterpart) ----
+    def repost(self, y, configs, starts=None, bonemaps=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
+        """``score.post_sweep`` with this estimator's model and body: ``y`` device float32 ``[F, M, O]`` as
+        ``process_recording(return_targets=True)`` returned it, ``configs`` a list of ``(smooth, samples)`` pairs (``score.grid``) ->
+        ``out [C, F, 25]`` (``(out, spread [C, F, 21])`` with ``spread``), ``out[c]`` the first 25 columns an estimator with configuration
+        ``c`` would have returned for the same recordings.  ``bonemaps``: one entry per recording (default: this estimator's body)."""
+        from wear_mocap_ape_amd import score
+        model = self._hip_model()
+        if model is None or self._frame_samples() is None:
+            raise UserWarning("this estimator has no HIP regressor")
+        if not self._normalize:
+            raise UserWarning("repost de-normalises its targets: this estimator does not normalise")
+        if bonemaps is not None:
+            R = len(np.asarray([0] if starts is None else starts).reshape(-1))
+            bonemaps = bodies_from(bonemaps, R, "repost bonemaps")
+        return score.post_sweep(model, y, configs, starts, bonemaps, spread, out_dtype, workspace_bytes)
+
+    def sweep_recording(self, rows, truth, smooths, samples, starts=None, lags=(0, 0), truth_kind="targets", bonemaps=None,
+                        seed: int = 0x5EED, skip=None, big_endian: bool = False):
+        """Which ``smooth`` and how many Monte-Carlo samples: ONE ``process_recording(return_targets=True)`` at ``max(samples)`` samples
+        (this estimator's own ``smooth`` and sample count stay what they are), one ``score.post_sweep`` of
+        ``score.grid(smooths, samples)`` with the spread records, then one ``score.score_lags`` over ``lags`` per configuration against
+        ``truth`` (device ``[F, O]`` de-normalised targets, or est rows with ``truth_kind="est"``).  Over an ``ImuPoseLSTM`` every sample
+        count is 1 (``nn_models.effective_mc``).  ``skip`` defaults to the ``sequence_len - 1`` cold-start frames of every recording.
+        Returns ``{"configs": [(smooth, samples), ...], "acc": ndarray [C, R, L, 25], "best": [score.best_lag(acc[c], lags) per
+        configuration]}`` (waits for the device)."""
+        from wear_mocap_ape_amd import score
+        from wear_mocap_ape_amd.estimate.nn_models import effective_mc
+        model = self._hip_model()
+        if model is None or self._frame_samples() is None:
+            raise UserWarning("this estimator has no HIP regressor or no batched feature builder")
+        configs = score.grid(smooths, [effective_mc(model, int(m)) for m in samples])
+        if not configs:
+            raise UserWarning("sweep_recording: no configuration")
+        top = max(m for _, m in configs)
+        _, y = self.process_recording(rows, starts=starts, big_endian=big_endian, return_targets=True, seed=seed, bonemaps=bonemaps,
+                                      _config=(1, top))
+        out, rec = self.repost(y, configs, starts=starts, bonemaps=bonemaps, spread=True)
+        skip = self._sequence_len - 1 if skip is None else skip
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        return score.score_configs(self._layout, out, rec, truth, configs, lags, truth_kind, starts, skip, bodies)
+
 
     # read-only views, same names as the reference's properties (estimator.py:188-218)
     sequence_len = property(lambda self: self._sequence_len)

@@ -8,7 +8,11 @@ accumulates them per recording; ``score_rows_numpy`` is the plain numpy statemen
 A smoothed estimate trails the motion and the mocap and IMU clocks are not aligned to the frame, so frame ``f`` of a replay need not
 belong to frame ``f`` of the truth: ``score_lags`` scores every frame against the truth of a whole sweep of lags in one pass (never across
 a recording boundary, and on the same frames for every lag), ``best_lag`` reads each recording's lag off the accumulators, ``align`` does
-both and scores once more at the lags found; ``score_lags_numpy`` is the host statement."""
+both and scores once more at the lags found; ``score_lags_numpy`` is the host statement.
+
+Which ``smooth`` and how many Monte-Carlo samples to run is answered from ONE replay: ``post_sweep`` runs the float64 post-filter from
+the replay's stored targets for many ``(smooth, samples)`` configurations in one pass (``ape_post_sweep``), ``grid``
+builds the list, ``score_configs`` scores every configuration over a sweep of lags."""
 import ctypes as C
 
 import numpy as np
@@ -331,3 +335,105 @@ def align(layout: int, msg, truth, lags, error: str = "hand_pos", truth_kind: st
     found = [0 if b["lag"] is None else b["lag"] for b in best]
     score, acc = score_lags(layout, msg, truth, (0, 0), truth_kind, spread, starts, skip, bodies, found, out_dtype, per_frame=True)
     return best, score[:, 0], acc[:, 0]
+
+
+# ---- post-filter sweep: one replay's targets at many (smooth, samples) (ape_post_sweep) ----------------------------------
+def grid(smooths, samples) -> list:
+    """the configurations ``(smooth, samples)`` of the product ``smooths x samples``: smooth-major (every sample count of the first
+    smooth in the order given, then the second smooth, ...), a pair that occurs again is dropped (the first occurrence keeps its place)"""
+    out, seen = [], set()
+    for s in smooths:
+        for m in samples:
+            pair = (int(s), int(m))
+            if pair not in seen:
+                seen.add(pair)
+                out.append(pair)
+    return out
+
+
+def _configs(configs) -> np.ndarray:
+    """int32 ``[C, 2]`` of a list of ``(smooth, samples)`` pairs"""
+    try:
+        cf = np.ascontiguousarray(np.asarray(list(configs), dtype=np.int32))
+    except (TypeError, ValueError):
+        raise UserWarning("configs: a list of (smooth, samples) pairs")
+    if cf.ndim != 2 or cf.shape[1] != 2 or not 1 <= cf.shape[0] <= _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"configs: between 1 and {_hip.POST_MAX_CONFIGS} (smooth, samples) pairs, got shape {tuple(cf.shape)}")
+    return cf
+
+
+def post_sweep(model, y, configs, starts=None, bodies=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
+    """The float64 post-filter of a replay -- de-normalise, forward kinematics, the clamped sliding stack, the sign-aligned quaternion
+    mean, the spread record -- from stored targets, for many configurations in one pass (``ape_post_sweep``).  ``model``: the HIP
+    regressor whose replay made ``y`` (its layout, ``yy_m`` / ``yy_s`` and body are used, its weights are not); ``y``: device float32
+    ``[F, M, O]``, the normalised targets ``process_recording(return_targets=True)`` returns; ``configs``: a list of
+    ``(smooth, samples)`` pairs with ``samples <= M`` (``grid``): configuration ``c`` stacks the first ``samples`` samples of the last
+    ``smooth`` frames.  ``starts``: the recordings' first frames (default one recording); ``bodies``: float64 ``[9]`` / ``[1, 9]`` /
+    ``[R, 9]`` values or a sequence of R bonemap-like objects (default: the model's body); ``workspace_bytes``: bound on the device
+    workspace (0: 128 MiB; include/ape_hip.h states the rule), which does not change the result.
+    Returns ``out [C, F, 25]`` of ``out_dtype`` on the device -- ``out[c]`` is what ``process_recording`` of an estimator with
+    configuration ``c`` returns in its first 25 columns, bit for bit where ``samples == M`` -- or, with ``spread``, ``(out, spread)``
+    with ``spread [C, F, 21]``: two views of one tensor, as ``process_recording(spread=True)`` returns them.  Does not wait."""
+    from wear_mocap_ape_amd.data_types.bone_map import bodies_from
+    if out_dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+    if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 3 or y.shape[0] < 1:
+        raise UserWarning("y: a float32 device tensor [F >= 1, M, O] (process_recording(return_targets=True))")
+    if y.shape[2] != model.output_size:
+        raise UserWarning(f"y: {y.shape[2]} targets per row, the model has {model.output_size}")
+    cf = _configs(configs)
+    st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
+    F, M, R, C_ = int(y.shape[0]), int(y.shape[1]), int(st.shape[0]), int(cf.shape[0])
+    body = None
+    if bodies is not None:
+        body = np.ascontiguousarray(bodies.reshape(1, 9), dtype=np.float64) if isinstance(bodies, np.ndarray) and bodies.size == 9 \
+            else bodies_from(bodies, R, "post_sweep bodies")
+    yd = y.contiguous()
+    dev = yd.device
+    with torch.cuda.device(dev):
+        width = 25 + (_hip.SPREAD_WIDTH if spread else 0)
+        out = torch.empty((C_, F, width), dtype=out_dtype, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_post_sweep(model.handle, C.c_void_p(yd.data_ptr()), F, M, C.c_void_p(st.ctypes.data), R,
+                                             C.c_void_p(cf.ctypes.data), C_, _hip.FLAG_SPREAD if spread else 0,
+                                             C.c_void_p(body.ctypes.data) if body is not None else None,
+                                             int(body.shape[0]) if body is not None else 0, C.c_void_p(out.data_ptr()), _f64(out_dtype),
+                                             int(workspace_bytes), stream), "ape_post_sweep")
+    if spread:
+        return out[:, :, :25], out[:, :, 25:]
+    return out
+
+
+def post_sweep_last() -> dict:
+    """the plan of this thread's last ``post_sweep`` (debug counter): passes over the workspace, frames per pass, frames per workgroup
+    tile, and whether the tiles were staged in LDS"""
+    v = (C.c_int32 * 4)()
+    _hip.check(_hip.lib().ape_post_sweep_last(v), "ape_post_sweep_last")
+    return {"passes": int(v[0]), "chunk_frames": int(v[1]), "tile_frames": int(v[2]), "lds": bool(v[3])}
+
+
+def post_sweep_plan(layout: int, F: int, configs, workspace_bytes: int = 0) -> dict:
+    """the workspace rule of include/ape_hip.h on the host: frames per pass and passes of a ``post_sweep`` over ``F`` frames"""
+    cf = _configs(configs)
+    H, frame_bytes = int(cf[:, 0].max()) - 1, 8 * _hip.EST_WIDTH[layout] * int(cf[:, 1].max())
+    bound = int(workspace_bytes) if workspace_bytes else 128 << 20
+    chunk = min(int(F), bound // (2 * frame_bytes) - H)
+    if chunk < 1:
+        raise UserWarning(f"workspace_bytes {bound} holds no frame (at least {2 * frame_bytes * (H + 1)})")
+    return {"passes": -(-int(F) // chunk), "chunk_frames": chunk, "frame_bytes": frame_bytes, "halo_frames": H}
+
+
+def score_configs(layout: int, out, spread, truth, configs, lags=(0, 0), truth_kind: str = "targets", starts=None, skip: int = 0,
+                  bodies=None, error: str = "hand_pos") -> dict:
+    """The scoring half of ``Estimator.sweep_recording``: one ``score_lags`` sweep per configuration on the strided views ``out[c]``
+    (and ``spread[c]``; ``spread`` may be None) of a ``post_sweep`` result, assembled into ``{"configs": [(smooth, samples), ...],
+    "acc": ndarray [C, R, L, 25], "best": [best_lag(acc[c], lags, error) per configuration]}`` (waits for the device)."""
+    configs = [(int(s), int(m)) for s, m in configs]
+    if not configs or len(out) != len(configs) or (spread is not None and len(spread) != len(configs)):
+        raise UserWarning(f"score_configs: {len(configs)} configurations for {len(out)} results")
+    accs = [_as_host(score_lags(layout, out[c], truth, lags, truth_kind, None if spread is None else spread[c], starts, skip, bodies)[1], (3,))
+            for c in range(len(configs))]
+    if any(a.shape != accs[0].shape for a in accs):
+        raise UserWarning("score_configs: accumulators of different sweeps")
+    acc = np.stack(accs)
+    return {"configs": configs, "acc": acc, "best": [best_lag(acc[c], lags, error) for c in range(len(configs))]}

@@ -900,6 +900,49 @@ int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
                    void* score_dev /* [F, L, 7] or NULL */, int32_t score_dtype, double* acc_dev /* f64 [R, L, 25] or NULL */,
                    void* stream);
 
+/* ---- post-filter sweep: one replay's targets re-smoothed at many (smooth, samples) (additive in ABI 7) ------------------
+ * replaces: for every configuration c and frame f, the tail of Estimator.add_xx_to_row_hist_and_make_prediction and
+ * Estimator.msg_from_pred (estimate/estimator.py:108-118,122-137) of an estimator built with smooth = smooth_c and m_c Monte-Carlo
+ * samples, incl. compose_msg.msg_from_nn_targets_est (estimate/compose_msg.py:13-108) and average_quaternions
+ * (utility/transformations.py:32-51) -- from the normalised targets a replay returned (ape_replay*'s y_dev), without the regressor.
+ *   y_dev f32 [F, n_mc, O]: frame f, sample k is row f * n_mc + k.  Sample k of a frame is the same draw whatever smooth is, and the
+ *   first m samples of a frame are a valid m-sample estimate: one replay at the largest sample count holds every smaller configuration.
+ *   configs_host int32 [C, 2]: (smooth_c, m_c), 1 <= smooth_c <= 64, 1 <= m_c <= n_mc, smooth_c * m_c <= 4096 (the limits of ape_replay).
+ *   Stack.  Stack row i < smooth_c * m_c of frame f of a recording starting at s is sample i % m_c of frame
+ *          max(s, f - smooth_c + 1 + i / m_c): ape_replay's rule with n_mc = m_c; samples k >= m_c of any frame are never read, and
+ *          samples k >= max_c m_c are not even converted.  Every row goes through pred * yy_s + yy_m in float64 and the forward
+ *          kinematics of ape_fk (the recording's body), once per call whatever C is; the sums run in ape_replay's order (row 0 first,
+ *          the strict `dot < 0.0` flip against row 0, the FMA chain for the dot, one more in-order pass for the spread record).
+ *   out_dev [C, F, 25] of out_dtype, with APE_FLAG_SPREAD [C, F, 25 + APE_SPREAD_WIDTH] (the record in the last 21 columns of a row).
+ *          For m_c == n_mc, out[c] holds the bits ape_replay_bodies(smooth_c, n_mc, the same flag) writes into those columns.
+ *   bodies_host f64 [n_bodies, 9] with n_bodies 1 or R, or NULL with n_bodies 0: the model's body (ape_model_set_body).
+ *   workspace_bytes: bound on the device workspace for converted rows, whatever F is; 0 = 128 MiB.  With W = 21 (14 without hips),
+ *          Mx = max_c m_c, H = max_c smooth_c - 1 and frame_bytes = 8 W Mx, a pass covers chunk = min(F, workspace_bytes /
+ *          (2 frame_bytes) - H) frames (two buffers of H carried-over + chunk frames); ceil(F / chunk) passes; chunk < 1 is refused.
+ *          Beside it the call keeps copies of its host arrays (4 R + 72 n_bodies bytes).  The result does not depend on the bound.
+ *          Within a pass a workgroup stages its tile of frames and the H frames before it in LDS where that fits (and the tile gives
+ *          its lanes enough (frame, configuration) pairs); otherwise the rows are read from the workspace.  Same bits either way.
+ * The model handle supplies the target layout, yy_m / yy_s and the default body; no weights are read, and a DropoutFF or ImuPoseLSTM
+ * handle serves as a DropoutLSTM one.  Not journaled: there is nothing for ape_model_recover to re-issue.  No floating-point atomics
+ * and a fixed order of summation: the same inputs give the same bits.  The launches go on `stream` and the call does not wait for
+ * them; the host arrays (seg_starts_host, configs_host, bodies_host) have been consumed when it returns.  (The workspace is kept per
+ * device and grows on demand, which may wait for the device; a call on another stream is ordered behind the last user by an event.)
+ * Refused on the host before anything is written: NULL model / y_dev / out_dev / seg_starts_host / configs_host; F < 1, R < 1, bad
+ * starts; F * n_mc >= 2^31; C < 1 or C > APE_POST_MAX_CONFIGS; smooth outside [1, 64], m outside [1, n_mc], smooth * m > 4096;
+ * n_bodies not 0 / 1 / R (0 iff bodies_host is NULL); flags other than APE_FLAG_SPREAD; an unknown dtype; workspace_bytes < 0 or too
+ * small for one frame (APE_ERR_INVALID_ARG); norm stats not set (APE_ERR_NOT_READY); APE_LAYOUT_NONE; a capturing stream.
+ * ape_post_sweep_last: debug counter -- the plan of this thread's last successful ape_post_sweep: out4 = {passes, frames per pass,
+ * frames per tile, 1 if the tiles were staged in LDS}. */
+#define APE_POST_MAX_CONFIGS 64
+int ape_post_sweep(ape_model_t* model, const float* y_dev, int32_t F, int32_t n_mc,
+                   const int32_t* seg_starts_host, int32_t R,
+                   const int32_t* configs_host /* [C,2]: smooth, samples */, int32_t C,
+                   uint32_t flags /* APE_FLAG_SPREAD or 0 */,
+                   const double* bodies_host /* [n_bodies,9] or NULL: the model's body */, int32_t n_bodies,
+                   void* out_dev /* [C, F, 25 (+21)] */, int32_t out_dtype,
+                   int64_t workspace_bytes, void* stream);
+int ape_post_sweep_last(int32_t out4[4]);
+
 #ifdef __cplusplus
 }
 #endif
