@@ -11,8 +11,14 @@
 //     c >= 0:  cos(a/2) = big,   |sin(a/2)| = small;     c < 0:  cos(a/2) = small, |sin(a/2)| = big;     sin(a/2) carries y's sign
 // (|a/2| <= pi/2, so the cosine is never negative; the division is always by the well-conditioned one of the pair).  Each result is
 // within a few 1e-16 of the routine's (the tests hold the feature builder to the reference's float32 / float64 outputs at 1e-6 / 1e-12 and
-// the messages at 1e-10).  Whatever the identities cannot state -- r = 0 with its signed-zero cases, an overflowing or underflowing
-// square, infinities, NaN -- takes the reference's own route through atan2, so degenerate messages give what they always gave.
+// the messages at 1e-10) -- as long as the squares are NORMAL numbers.  A square that underflows gradually keeps only a few bits (|x|, |y|
+// around 1e-160: r is good to 1e-3, where atan2 is exact), and nothing about r says so: r is positive and finite.  So the identities serve
+// the band 1e-140 <= r <= 1e140 only, inside which x^2 + y^2 lies in [1e-280, 1e280] and each square is either normal or below the
+// sum's last bit.  Whatever lies outside -- r = 0 with its signed-zero cases, a square that overflows, underflows or flushes, infinities,
+// NaN (no compare holds) -- takes the reference's own route through atan2, so degenerate messages give what they always gave.  Float32
+// sources cannot leave the band (the smallest float32 subnormal squared is 2e-90; ape_post_sweep takes float32 targets only); the float64
+// entries (ape_fk, ape_score_rows and ape_score_lags with float64 truth given as targets) can: tests/test_fk_magnitudes_gpu.py walks them
+// over every decade of the exponent range.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -20,7 +26,7 @@ namespace ape_angledev {
 
 struct CS { double c, s; };
 
-__device__ __forceinline__ bool plain_radius(double r) { return r > 0.0 && r <= 1.7976931348623157e308; }
+__device__ __forceinline__ bool plain_radius(double r) { return r >= 1e-140 && r <= 1e140; }
 
 // (cos(a / 2), sin(a / 2)) of a = atan2(y, x)
 __device__ inline CS half_of_atan2(double y, double x) {

@@ -117,7 +117,8 @@ static ApeCaps ape_caps(const ape_dims_t* dims, int n_cus) {
     // the Monte-Carlo bank's weight-stationary route for the 3 x 128 model (lstm_upper128.hip): four-member clusters, whole classes of 8
     c.up128 = ape_upper128_supported(H, L, O) && c.up128_classes >= 8 && !imupose;
     c.c16 = ape_cluster16_supported(H, L, KX) && c.f16v2_capacity > 0 && !imupose;
-    // short windows: the level-synchronous kernel, if the device holds two of its workgroups per CU (else the first generation serves them)
+    // the level-synchronous kernel (one workgroup of two agents per CU, 32-window clusters of 8 members), if the device holds a whole
+    // block-index class of its clusters -- 64 CUs -- (else the first generation serves those calls)
     c.lv16 = c.c16 && ape_level16_supported(H, L, KX) && c.level16_max_clusters > 0;
     return c;
 }
@@ -2665,6 +2666,20 @@ int ape_debug_bank_route(const ape_dims_t* dims, int n_cus, int S, int T, int n_
     const BankPlan p = plan_bank(ape_caps(dims, n_cus), *dims, S, T, n_mc, 0.5f, APE_KERNEL_AUTO, APE_PRECISION_F32, true, bank_l0_bytes(S, T));
     out[0] = p.shared_l0 ? 1 : 0; out[1] = p.route; out[2] = p.a_form; out[3] = p.chunk_rows;
     return APE_OK;
+}
+
+// internal: what the launcher of a kernel with 12-bit phase tags answers to a window that does not fit them, no GPU needed (the launchers
+// refuse in front of every HIP call).  kernel 0: lstm_level16.hip (3 x 128), 1: lstm_cluster_small.hip (2 x 256), 2: the same (3 x 128).
+// Nothing is ever launched from here: where the window fits, the answer is -1 and the launcher is not called; else its hipError_t.
+int ape_debug_launch_refusal(int kernel, int T) {
+    if (kernel < 0 || kernel > 2) return -2;
+    const int L = kernel == 1 ? 2 : 3;
+    if (plan_tag_phases_fit(T, L)) return -1;
+    ClusterParams p{};
+    p.T = T;
+    if (kernel == 0) return (int)ape_launch_lstm_level16(128, 3, 64, 16, p, nullptr);
+    if (kernel == 1) return (int)ape_launch_lstm_cluster_small(256, 2, 32, 1, 4, p, nullptr);
+    return (int)ape_launch_lstm_cluster_small(128, 3, 64, 1, 4, p, nullptr);
 }
 
 int ape_debug_plan(const ape_dims_t* dims, int n_cus, int B, int T, int cdrop, int out[5]) {

@@ -444,7 +444,8 @@ hipError_t ape_launch_lstm_cluster32(int H, int L, int KX, int clusters, const C
 bool ape_cluster16_supported(int H, int L, int KX);
 hipError_t ape_prepare_lstm_cluster16(int H, int L, int KX);
 hipError_t ape_launch_lstm_cluster16(int H, int L, int KX, int rows, const ClusterParams& p, hipStream_t stream);
-// level-synchronous kernel for short windows of the 3 x 128 model (lstm_level16.hip: 16-window clusters, two workgroups per CU)
+// level-synchronous kernel for short windows of the 3 x 128 model (lstm_level16.hip: 32-window clusters of 8 members, ONE
+// eight-wave workgroup per CU -- __launch_bounds__(512, 1), 115 KB of LDS; T + L - 1 <= APE_TAG_MAX_PHASES or the launcher refuses)
 bool ape_level16_supported(int H, int L, int KX);
 int ape_level16_max_clusters(int n_cus);
 size_t ape_level16_gx_bytes(int n_cus);

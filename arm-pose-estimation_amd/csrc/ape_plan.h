@@ -98,11 +98,29 @@ enum { PLAN_NONE = 0, PLAN_GEN1 = 1, PLAN_C32 = 2, PLAN_SMALL = 3, PLAN_C16 = 4,
 #define APE_LV16_COST_US_T 6.8
 #define APE_LV16_COST1_US0 13.0     // ... of up to 512 rows (one row tile per cluster)
 #define APE_LV16_COST1_US_T 4.5
+// the most phases (hand-overs) a launch of the kernels with 12-bit phase tags may run: lstm_level16.hip, lstm_cluster_small.hip and
+// lstm_mc_small.hip tag a granule (launch number << 12) | (phase + 1), phase + 1 <= T + L - 1 -- one phase more and the count spills
+// into the launch number, where it collides with the stale granules of other launches.  The planner keeps every such route below it and
+// the launchers refuse what is above (hipErrorInvalidValue, nothing launched).
+#define APE_TAG_MAX_PHASES 4095
+// does a window of T steps on an L-layer model fit the 12-bit phase count?  The ONE comparison: the planner's gate of the latency kernel, the
+// launchers' refusal and ape_debug_launch_refusal (tests/test_long_windows_cpu.py walks both sides of it) ask here
+// (written without T + L: a window length near INT_MAX must not wrap into the range)
+inline bool plan_tag_phases_fit(int T, int L) { return T >= 1 && L >= 1 && T <= APE_TAG_MAX_PHASES - (L - 1); }
+inline int plan_clamp(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+// the overrides move thresholds between routes that all serve the shape; none of them can send a window to a kernel beyond its limits:
+// lv16_max_t stays within the one-tile form's own limit, the others within the ranges their comparisons have a meaning for
+inline void plan_clamp_overrides(ApeCaps* caps) {
+    caps->c16_min_t = plan_clamp(caps->c16_min_t, 1, 1 << 20);
+    caps->lv16_max_t = plan_clamp(caps->lv16_max_t, 0, APE_LV16_MAX_T_SINGLE);
+    caps->lv16_min_rows = plan_clamp(caps->lv16_min_rows, 1, 1 << 20);
+}
 inline void plan_read_overrides(ApeCaps* caps) {
     static const int c16_min_t = getenv("APE_C16_MIN_T") ? atoi(getenv("APE_C16_MIN_T")) : 12;      // (diagnostic overrides for A/B runs)
     static const int lv16_max_t = getenv("APE_LV16_MAX_T") ? atoi(getenv("APE_LV16_MAX_T")) : APE_LV16_MAX_T;
     static const int lv16_min_rows = getenv("APE_LV16_MIN_ROWS") ? atoi(getenv("APE_LV16_MIN_ROWS")) : APE_LV16_MIN_ROWS;
     caps->c16_min_t = c16_min_t; caps->lv16_max_t = lv16_max_t; caps->lv16_min_rows = lv16_min_rows;
+    plan_clamp_overrides(caps);
 }
 inline int rest_kernel(const ApeCaps& caps, int rest, int T, int gen2) {
     if (rest <= 0) return PLAN_NONE;
@@ -264,7 +282,7 @@ inline LstmPlan plan_lstm(const ApeCaps& caps, const ape_dims_t& dims, const Lst
     p.last_kernel = "ape_lstm_tile16";
     if (p.n16 == B) return p;
     const int rest = B - p.n16;
-    const bool small = !f16 && !cdrop && !c.all_steps && B <= 4 && T + L <= 4096 && c.small_batch_path && !caps.wide;   // latency path: VALU GEMV, one exchange per phase
+    const bool small = !f16 && !cdrop && !c.all_steps && B <= 4 && plan_tag_phases_fit(T, L) && c.small_batch_path && !caps.wide;   // latency path: VALU GEMV, one exchange per phase
     p.route = f16 ? PLAN_F16 : small ? PLAN_SMALL : rest_kernel(caps, rest, T, gen2);
     // second-generation fp16 kernel: 8-member clusters x 2 row sets of 16 that take turns (lstm_cluster_f16v2.hip)
     if (f16 && c.f16_v2 && caps.f16v2 && caps.f16v2_capacity > 0 && B > 256) p.route = PLAN_F16V2;
@@ -276,7 +294,7 @@ inline LstmPlan plan_lstm(const ApeCaps& caps, const ape_dims_t& dims, const Lst
             p.last_kernel = p.route == PLAN_C32 ? "ape_lstm_cluster32" : p.route == PLAN_C16 ? "ape_lstm_cluster16" :
                             plan_f16v2_duo(caps, c, rest - (p.launches - 1) * p.rows_per_launch) ? "ape_lstm_cluster_f16v2<duo>" : "ape_lstm_cluster_f16v2";
             break;
-        case PLAN_LV16:       // short windows of the 3 x 128 model: level-synchronous 16-window clusters, two workgroups per CU (lstm_level16.hip)
+        case PLAN_LV16:       // short windows of the 3 x 128 model: level-synchronous 32-window clusters, one eight-wave workgroup per CU (lstm_level16.hip)
             // up to 16 rows per cluster of the device: one row tile per cluster, so that the rows spread over every CU
             p.lv16_single = rest <= 16 * caps.level16_max_clusters;
             chunks(16 * (p.lv16_single ? 1 : 2) * caps.level16_max_clusters, p.lv16_single ? 1 : 2, caps.level16_max_clusters);

@@ -21,6 +21,7 @@
 // Same arithmetic as the other kernels up to float32 summation order.
 #include <type_traits>
 #include "ape_internal.h"
+#include "ape_plan.h"
 #include "lstm_latency_common.h"
 #include "fk_device.h"
 #include "../../include/ape_hip.h"
@@ -487,7 +488,9 @@ hipError_t launch_small_nr(int nr, const ClusterParams& p, hipStream_t stream) {
 
 // one cluster, B <= 4 windows (nr = 1, 2 or 4 rows computed); uw = hidden units per wave (4: H/16 members, weights p.wcl in
 // the MFMA cluster kernel's order; 2: H/8 members, weights in the [member][wave][k-quad][lane][4] order of 8-column waves)
+// A phase's tag holds 12 bits of phase count (ph + 1 <= T + L - 1): a longer window is refused here, nothing is launched
 hipError_t ape_launch_lstm_cluster_small(int H, int L, int KX, int nr, int uw, const ClusterParams& p, hipStream_t stream) {
+    if (!plan_tag_phases_fit(p.T, L)) return hipErrorInvalidValue;
     if (H == 256 && L == 2 && KX == 32) return uw == 2 ? launch_small_nr<256, 2, 32, 2>(nr, p, stream) : launch_small_nr<256, 2, 32, 4>(nr, p, stream);
     if (H == 128 && L == 3 && KX == 64) return uw == 2 ? launch_small_nr<128, 3, 64, 2>(nr, p, stream) : launch_small_nr<128, 3, 64, 4>(nr, p, stream);
     return hipErrorInvalidValue;

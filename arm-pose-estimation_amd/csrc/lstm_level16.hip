@@ -37,6 +37,7 @@
 #include <type_traits>
 
 #include "ape_internal.h"
+#include "ape_plan.h"
 #include "async_look.h"
 #include "../../include/ape_hip.h"
 
@@ -545,9 +546,11 @@ hipError_t ape_prepare_lstm_level16(int H, int L, int KX) {
 }
 
 // `rows` windows, at most 32 x ape_level16_max_clusters(n_cus) (16 x with APE_FLAG_LV16_SINGLE in p.flags: one row tile per cluster); the grid is
-// rounded up to whole block-index classes (8 clusters x 8 members)
+// rounded up to whole block-index classes (8 clusters x 8 members).  A level's tag holds 12 bits of level count (k + 1 <= T + L - 1): a
+// longer window is refused here, nothing is launched
 hipError_t ape_launch_lstm_level16(int H, int L, int KX, int rows, const ClusterParams& p, hipStream_t stream) {
     if (!ape_level16_supported(H, L, KX)) return hipErrorInvalidValue;
+    if (!plan_tag_phases_fit(p.T, L)) return hipErrorInvalidValue;
     const bool single = (p.flags & APE_FLAG_LV16_SINGLE) != 0;
     const int grid_clusters = single ? ((rows + 15) / 16 + 7) / 8 * 8 : ((rows + 31) / 32 + 7) / 8 * 8;
     constexpr size_t smem = smem_level16<128, 3, 64>();

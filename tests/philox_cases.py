@@ -47,13 +47,25 @@ LSTM_ROUTES = {
 }
 
 
+# the Monte-Carlo latency kernel at the ends of its window range (tests/test_long_windows_gpu.py): lstm_mc_small.hip sizes its LDS masks by T
+# and is gated at T <= 64 -- one step more and the first-generation dropout kernel serves the call (from the same counters)
+LONG_LSTM_ROUTES = {
+    "mc_small-T64": ("pocket", "auto", 25, 64, 0x6789B, "ape_lstm_mc_small", True),
+    "mc_small-T65": ("pocket", "auto", 25, 65, 0x6789C, "ape_lstm_cluster", True),
+}
+
+
+def lstm_route(route):
+    return LSTM_ROUTES[route] if route in LSTM_ROUTES else LONG_LSTM_ROUTES[route]
+
+
 def wave_rows(n_cus):
     return 16 * n_cus
 
 
 def lstm_inputs(norm_stats, route, n_cus=MI355X_CUS):
     """-> dict: raw x [nb,T,I] as the model takes it, float32 z-scores xn [B,T,I] per row, B, key"""
-    model, kernel, B, T, mseed, last, shared = LSTM_ROUTES[route]
+    model, kernel, B, T, mseed, last, shared = lstm_route(route)
     B = wave_rows(n_cus) + 37 if B is None else B
     I = orc.MODEL_CONFIGS[model]["I"]
     z = hi.case_z("benign", 1 if shared else B, T, I, SEED_X)
@@ -109,14 +121,34 @@ BANKS = {
     "shared-tile16-330x25": ("lstm", "pocket", 330, 25, 1, 0x4_0123_4567, "tile16", "ape_lstm_tile16"),
     "ff-7x25": ("ff", "pocket", 7, 25, 1, 0x5_0000_0003, "auto", "ape_ff_bank_head"),
 }
+# one estimator's bank (S = 1) with windows of 32 .. 65 frames instead of the deployed 6: a ninth field, the window length.  The bank steps on
+# the Monte-Carlo latency kernel up to 64 frames (up to 32 its extra workgroups could also build the features) and on the fused
+# first-generation dropout kernel from 65 (tests/test_long_windows_gpu.py checks LONG_BANK_FRAMES of each)
+LONG_BANKS = {
+    "mc_small-1x25-T32": ("lstm", "pocket", 1, 25, 1, 0x8_0000_0020, "auto", "ape_lstm_mc_small", 32),
+    "mc_small-1x25-T33": ("lstm", "pocket", 1, 25, 1, 0x8_0000_0021, "auto", "ape_lstm_mc_small", 33),
+    "mc_small-1x25-T64": ("lstm", "pocket", 1, 25, 1, 0x8_0000_0040, "auto", "ape_lstm_mc_small", 64),
+    "mc_small-1x25-T65": ("lstm", "pocket", 1, 25, 1, 0x8_0000_0041, "auto", "ape_lstm_cluster", 65),
+}
 RESET_AT = 2
 CHECK_ALL_ROWS = 2600
 
 
+def bank_entry(bank):
+    return BANKS[bank] if bank in BANKS else LONG_BANKS[bank][:8]
+
+
+def long_bank_frames(bank):
+    """the checked frames of a LONG_BANKS entry: the cold start, the reset, a half-filled window, the first full window and the first
+    frame whose window has dropped a row"""
+    T = LONG_BANKS[bank][8]
+    return [0, RESET_AT, RESET_AT + T // 2, RESET_AT + T - 1, RESET_AT + T]
+
+
 def bank_dims(bank):
-    reg, name, S, n_mc, smooth, seed, kernel, last = BANKS[bank]
-    T = orc.MODEL_CONFIGS[name]["T"]
-    return reg, name, S, n_mc, smooth, seed, T, T + 2
+    reg, name, S, n_mc, smooth, seed, kernel, last = bank_entry(bank)
+    T = LONG_BANKS[bank][8] if bank in LONG_BANKS else orc.MODEL_CONFIGS[name]["T"]
+    return reg, name, S, n_mc, smooth, seed, T, T + (RESET_AT + 1 if bank in LONG_BANKS else 2)
 
 
 def bank_checked_frames(bank):
@@ -173,14 +205,15 @@ def post_filter(name, stacks):
     return np.array(tails), np.array(msgs)
 
 
-def bank_reference(norm_stats, bank, frames=None, variant=ph.CONTRACT, streams=None, with32=False):
+def bank_reference(norm_stats, bank, frames=None, variant=ph.CONTRACT, streams=None, with32=False, feats=None):
     """lockstep frames of a bank: {frame: [(tail, msg) float64 reference, (tail, msg) of the float32 oracle]} for `frames` (default: the
     checked ones) and `streams` (default: all).  Frame f is Monte-Carlo call f of the bank whatever reset() did in between: key
-    seed + f; sample row = stream * n_mc + sample."""
+    seed + f; sample row = stream * n_mc + sample.  `feats` float32 [F, S, I]: the frames' feature rows where they are not
+    `bank_features` (host frames: what the device's feature builder made of the raw messages)."""
     reg, name, S, n_mc, smooth, seed, T, F = bank_dims(bank)
     frames = bank_checked_frames(bank) if frames is None else frames
     streams = np.arange(S) if streams is None else np.asarray(streams)
-    feats = bank_features(norm_stats, bank)[:, streams]
+    feats = (bank_features(norm_stats, bank) if feats is None else feats)[:, streams]
     rows = (streams[:, None] * n_mc + np.arange(n_mc)[None, :]).reshape(-1)
     start = lambda f: RESET_AT if f >= RESET_AT else 0
     need = sorted({g for f in frames for g in _clamped(f, start(f), smooth)})

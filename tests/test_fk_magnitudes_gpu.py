@@ -1,0 +1,135 @@
+"""Float64 geometry across the exponent range on the device: every entry that takes float64 targets, on the sweep of
+tests/test_fk_magnitudes_cpu.py -- (sin, cos) hips pairs scaled by every power of ten from 1e-323 to 1e308 (quarter decades where the squares
+underflow and overflow), mixed magnitudes, subnormals and signed zeros, and the same scales spliced into the 6D rotation columns.
+
+Entries  : `ape_fk` (`_post.fk_rows`) on the three target layouts; `ape_score_rows` and `ape_score_lags` (which `align` and `score_configs`
+           run as well) with float64 truth given as NN targets: csrc/score.hip's two copies of the truth route, hips pairs and 6D scales alike.  `ape_post_sweep` takes float32 targets only (wear_mocap_ape_amd/score.py post_sweep,
+           csrc/post_sweep.hip) and float32 cannot reach the band where the squares are subnormal (2e-90 at the least), like the
+           feature builder and the banks: the existing tests of those hold them.
+Expected : `orc.arm_pose_from_targets(..., "closed")`, NaN exactly where the oracle has NaN, infinities where it has them, 1e-11 elsewhere;
+           the scores against `score.score_rows_numpy` on the oracle's reference-route ("eigh") truth, likewise.
+tests/test_fk_magnitudes_cpu.py proves that this sweep fails on the identities without their safe band by a factor of 1e5 and more."""
+import numpy as np
+import pytest
+import torch
+
+from oracle import ape_oracle as orc
+from tests import test_fk_magnitudes_cpu as fm
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _built():
+    import __graft_entry__ as entry
+    entry.build()
+
+
+@pytest.mark.parametrize("layout", [0, 1, 2])
+def test_ape_fk_over_the_exponent_range(layout):
+    from wear_mocap_ape_amd.estimate import _post
+    preds, n_hips = fm.preds_of(layout)
+    ref = fm.expected(preds, layout)
+    ctx = _post.context(layout)
+    est = _post.fk_rows(ctx.handle, layout, ctx.device, preds, orc.DEFAULT_BODY)
+    assert est.shape == ref.shape
+    parts = {"hips sweep": slice(0, n_hips), "6D sweep": slice(n_hips, None)}
+    lines, ok = [], True
+    for what, rows in parts.items():
+        if ref[rows].shape[0] == 0:
+            continue
+        nan_ok, inf_ok, err = fm.compare(est[rows], ref[rows])
+        lines.append(f"FAREND|fk|ape_fk layout {layout}|{what}: {ref[rows].shape[0]} rows, {int(np.isnan(ref[rows]).any(axis=1).sum())} with NaN|"
+                     f"NaN pattern {'equal' if nan_ok else 'DIFFERS'}|infinities {'equal' if inf_ok else 'DIFFER'}|err {err:.2e}|bound {fm.TOL:.0e}")
+        ok = ok and nan_ok and inf_ok and err <= fm.TOL
+    print("\n" + "\n".join(lines))
+    if n_hips:
+        # the worst row by decade of the radius around the band's lower edge and where the squares underflow
+        c_h = fm.layout_columns(layout)[2]
+        with np.errstate(all="ignore"):
+            r = np.hypot(preds[:n_hips, c_h], preds[:n_hips, c_h + 1])
+        fin = np.isfinite(ref[:n_hips]) & np.isfinite(est[:n_hips])
+        d = np.where(fin, np.abs(est[:n_hips] - np.where(fin, ref[:n_hips], 0.0)), 0.0).max(axis=1)
+        print("FAREND|fk|ape_fk layout %d|err by decade of r: " % layout +
+              ", ".join(f"1e{e}: {d[(r >= 10.0 ** e) & (r < 10.0 ** (e + 1))].max(initial=0.0):.1e}" for e in (-310, -200, -163, -162, -161, -160, -159, -158, -141, -140, 0, 139, 140, 153, 154, 200)))
+    assert ok, lines
+
+
+# ---------------- scoring with float64 truth given as targets -----------------------------------------------------------------------------
+# csrc/score.hip turns a truth row into a pose in two places (ape_score_kernel's truth section and truth_pose<APE_TRUTH_TARGETS> of the lag
+# sweep, which keeps its own copy): both call hips_quat and truth_six_drr_to_quat, the closed form of fk_device.h refined towards the
+# reference's eigenvector by two power steps on K + I.  A step multiplies the distance to the eigenvector by defect / 4 (K + I has the
+# eigenvalues 4 and three of the size of R's defect from orthonormal, delta = max |R'R - I|) and the closed form starts within delta, so
+# the refined quaternion is within delta^3 / 16 of the reference's: rows with delta <= PIN_DEFECT = 1e-4 (6e-14, and the scores amplify a
+# quaternion by at most 2) are held to 1e-11; rows beyond it -- 6D columns whose squares are subnormal, where Gram-Schmidt in plain float64
+# is off by 1e-3 in numpy and on the device alike, or whose norms flush or overflow to a singular R -- are held to the NaN pattern only,
+# and counted in the printed line.
+PIN_DEFECT = 1e-4
+ENTRIES = {"score_rows": None, "score_lags-lag0": (0, 0), "score_lags-lag3": (3, 3)}
+
+
+def _defect(s6):
+    with np.errstate(all="ignore"):
+        R = orc.six_drr_to_rotmat(s6).reshape(-1, 3, 3)
+        d = np.abs(np.einsum("nji,njk->nik", R, R) - np.eye(3)).max(axis=(1, 2))
+    return R.reshape(-1, 9), np.where(np.isfinite(d), d, np.inf)
+
+
+def truth_est(truth, layout):
+    """-> (the reference-route ("eigh") est rows of float64 truth targets -- NaN rows where a target or a Gram-Schmidt matrix is not finite: the
+    eigenvector has no answer there --, the larger orthonormality defect of the row's two rotation matrices)"""
+    c_l, c_u, _ = fm.layout_columns(layout)
+    (Rl, dl), (Ru, du) = _defect(truth[:, c_l:c_l + 6]), _defect(truth[:, c_u:c_u + 6])
+    ok = np.isfinite(truth).all(axis=1) & np.isfinite(Rl).all(axis=1) & np.isfinite(Ru).all(axis=1)
+    est = np.full((truth.shape[0], orc.LAYOUT_EST_WIDTH[layout]), np.nan)
+    with np.errstate(all="ignore"):
+        est[ok] = orc.arm_pose_from_targets(truth[ok], orc.DEFAULT_BODY, layout, "eigh")
+    return est, np.maximum(dl, du)
+
+
+@pytest.mark.parametrize("entry", sorted(ENTRIES))
+@pytest.mark.parametrize("layout", [0, 1, 2])
+def test_score_truth_targets_over_the_exponent_range(layout, entry):
+    """every row of the sweep (hips pairs AND 6D scales) as float64 truth targets through `score_rows` and through `score_lags` at lag 0 and
+    at lag 3 (message f against truth f - 3), every frame scored against ONE ordinary pose's message; reference `score_rows_numpy` /
+    `score_lags_numpy` on the oracle's reference-route truth.  A frame with a non-finite truth target is an all-NaN row (include/ape_hip.h)."""
+    from tests.test_score_gpu import msgs_from_est
+    from wear_mocap_ape_amd import score
+    truth, n_hips = fm.preds_of(layout)
+    F = truth.shape[0]
+    c_h = fm.layout_columns(layout)[2]
+    base = truth[:1].copy() if n_hips else np.random.default_rng(3).normal(size=(1, truth.shape[1]))
+    if c_h is not None:
+        base[0, c_h:c_h + 2] = np.sin(0.7), np.cos(0.7)
+    msg = np.repeat(msgs_from_est(fm.expected(base, layout), layout), F, axis=0)
+    t_est, defect = truth_est(truth, layout)
+    pinned = defect <= PIN_DEFECT
+    md, td, body = torch.from_numpy(msg).cuda(), torch.from_numpy(np.ascontiguousarray(truth)).cuda(), orc.DEFAULT_BODY.reshape(9)
+    lags = ENTRIES[entry]
+    if lags is None:
+        ref = score.score_rows_numpy(msg, t_est, layout)
+        got, _ = score.score_rows(layout, md, td, "targets", bodies=body)
+        pin = pinned
+    else:
+        ref = score.score_lags_numpy(msg, t_est, layout, lags)[0][:, 0]
+        got, _ = score.score_lags(layout, md, td, lags, "targets", bodies=body, per_frame=True)
+        got = got[:, 0]
+        src = np.arange(F) - lags[0]                     # the truth row of frame f
+        pin = (src >= 0) & (src < F) & pinned[np.clip(src, 0, F - 1)]
+    torch.cuda.synchronize()
+    got = got.cpu().numpy()
+    assert got.shape == ref.shape
+    nan_ok = np.array_equal(np.isnan(got[:, :5]), np.isnan(ref[:, :5]))
+    fin = np.isfinite(ref[:, 0]) & np.isfinite(got[:, 0])
+    err = float(np.abs(got[fin & pin, :5] - ref[fin & pin, :5]).max())
+    loose = fin & ~pin
+    err_loose = float(np.abs(got[loose, :5] - ref[loose, :5]).max(initial=0.0))
+    line = (f"FAREND|fk|{entry} targets layout {layout}|{F} frames ({n_hips} hips sweep, {F - n_hips} 6D sweep), {int(np.isnan(ref[:, 0]).sum())} all-NaN|"
+            f"NaN pattern {'equal' if nan_ok else 'DIFFERS'}|err {err:.2e} on {int((fin & pin).sum())} rows with defect <= {PIN_DEFECT:g}|bound {fm.TOL:.0e}|"
+            f"{int(loose.sum())} finite rows beyond that defect, not pinned: err {err_loose:.2e}")
+    print("\n" + line)
+    if not nan_ok:
+        bad = np.flatnonzero(np.isnan(got[:, 0]) != np.isnan(ref[:, 0]))
+        print("FAREND|fk|NaN pattern differs on frames", bad[:12], "defect", defect[np.clip(bad - (lags[0] if lags else 0), 0, F - 1)][:12])
+    assert n_hips == 0 or int((fin & pin)[:n_hips].sum()) >= n_hips - 16        # the whole hips sweep is pinned (its 6D columns are ordinary)
+    assert nan_ok and err <= fm.TOL, line

@@ -8,6 +8,8 @@ fraction of one.  The cases here are what a trained checkpoint and a misbehaving
   sat30         inputs at +-30 standard deviations, weights x 4: |h| reaches 1
   z1e3          |z| uniform up to 1e3 (1e2 for the binary16 routes), weights x 1
   benign        the control: same shape and seed, weights x 1, standard inputs
+  long4k        weights x 4 on standard inputs, for windows of thousands of steps (tests/test_long_windows_cpu.py): the largest scale at which
+                the recurrence is still conditioned over 4000 steps (see LONG4K_SCALE)
 They must be hostile to kernels, not to the mathematics: the float64 reference stays finite on all of them (asserted below)."""
 import numpy as np
 import pytest
@@ -28,7 +30,11 @@ TRAINED_SCALE = {"pocket": 16.0, "watch": 16.0, "uarm": 16.0, "imupose": 16.0, "
 # with 16 % of layer 0's pre-activations beyond 4 and pre-activations of several units throughout: that is the case the long-window
 # routes are HELD to; their `trained` row at x 16 is run and recorded.  test_the_long_case_is_conditioned holds e_ref <= 1e-3 for it.
 LONG_SCALE = 8.0
-CASE_WSCALE = {"sat30": 4.0, "z1e3": 1.0, "benign": 1.0, LONG_CASE: LONG_SCALE}
+# Windows of thousands of steps (the far ends of tests/test_long_windows_*.py).  At x 8 the recurrence is chaotic over 4000 steps (the float32
+# oracle ends about 1 from the float64 reference); at x 4 it forgets: e_ref 4.9e-7 (pocket, 4094 steps) and 6.8e-7 (uarm, 4000 steps) over all
+# steps on outputs up to 0.7, against 4e-8 at x 1.  tests/test_long_windows_cpu.py holds e_ref <= 1e-5 for every case its GPU half uses.
+LONG4K_CASE, LONG4K_SCALE = "long4k", 4.0
+CASE_WSCALE = {"sat30": 4.0, "z1e3": 1.0, "benign": 1.0, LONG_CASE: LONG_SCALE, LONG4K_CASE: LONG4K_SCALE}
 ONE_LAYER = {"one_22_256": (22, 256, 14), "one_32_256": (32, 256, 12), "one_38_128": (38, 128, 12), "one_64_128": (64, 128, 6)}
 SEED_W = 3            # tests/test_c32_split_gpu._model's default weight seed
 
