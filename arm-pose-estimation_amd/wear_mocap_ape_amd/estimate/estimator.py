@@ -649,6 +649,18 @@ class Estimator:
             return score.score_rows(self._layout, out, truth, truth_kind, spread, starts, skip, bodies)
         return score.score_lags(self._layout, out, truth, lags, truth_kind, spread, starts, skip, bodies, rec_lags, per_frame=True)
 
+    def align_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=(0, 0),
+                        mode="yaw", weights=(1, 1, 1, 0, 0)):
+        """``score.align_frame`` with this estimator's layout and body and ``score_recording``'s defaults: each recording's lag (over the
+        sweep ``lags=(lo, hi)``) and constant world-side rotation against the truth (``mode`` ``"yaw"`` or ``"full"``, ``weights`` of the
+        lower-arm, upper-arm and hips rotations and the hand and elbow positions) are found together, the rows (and
+        ``spread``) are turned by it and scored at the lags found.  Returns ``(score [F, 7], acc [R, 25], found)``, ``found`` being
+        ``score.best_frame``'s list (``lag``, ``quat``, ``yaw``, ...)."""
+        from wear_mocap_ape_amd import score
+        skip = self._sequence_len - 1 if skip is None else skip
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        return score.align_frame(self._layout, out, truth, lags, mode, weights, truth_kind, spread, starts, skip, bodies)
+
     # ---- post-filter sweep (DESIGN.md 4.33; the reference has no counterpart) ----
     def repost(self, y, configs, starts=None, bonemaps=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
         """``score.post_sweep`` with this estimator's model and body: ``y`` device float32 ``[F, M, O]`` as

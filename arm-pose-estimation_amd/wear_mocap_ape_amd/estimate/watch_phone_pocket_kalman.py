@@ -352,3 +352,9 @@ class WatchPhonePocketKalman(Estimator):
         its first row alone, whose spread records have no usable covariance"""
         return super().score_recording(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind, lags,
                                        rec_lags)
+
+    def align_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=(0, 0), mode="yaw",
+                        weights=(1, 1, 1, 0, 0)):
+        """``Estimator.align_recording`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
+        return super().align_recording(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind, lags,
+                                       mode, weights)

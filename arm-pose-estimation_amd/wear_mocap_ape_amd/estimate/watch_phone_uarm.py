@@ -140,3 +140,8 @@ class WatchPhoneUarm(Estimator):
     def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=None, rec_lags=None):
         """``Estimator.score_recording`` for ``[F, 25]`` FK replays (no cold-start frames: ``skip`` defaults to 0; no spread record)"""
         return super().score_recording(out, truth, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind, lags, rec_lags)
+
+    def align_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=(0, 0), mode="yaw",
+                        weights=(1, 1, 1, 0, 0)):
+        """``Estimator.align_recording`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
+        return super().align_recording(out, truth, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind, lags, mode, weights)

@@ -1,4 +1,4 @@
-"""Scoring replayed poses against ground truth (``ape_score_rows``, ``ape_score_lags``, include/ape_hip.h; DESIGN.md 4.31, 4.32).
+"""Scoring replayed poses against ground truth (``ape_score_rows``, ``ape_score_lags``, include/ape_hip.h; DESIGN.md 4.31 - 4.34).
 
 The reference has no counterpart: it never compares a message with the mocap truth its recordings carry.  ``score_rows`` does it on
 the device for every frame of a replay -- five errors and, with the frames' spread records, two squared Mahalanobis distances -- and
@@ -12,7 +12,12 @@ both and scores once more at the lags found; ``score_lags_numpy`` is the host st
 
 Which ``smooth`` and how many Monte-Carlo samples to run is answered from ONE replay: ``post_sweep`` runs the float64 post-filter from
 the replay's stored targets for many ``(smooth, samples)`` configurations in one pass (``ape_post_sweep``), ``grid``
-builds the list, ``score_configs`` scores every configuration over a sweep of lags."""
+builds the list, ``score_configs`` scores every configuration over a sweep of lags.
+
+A recording whose wearer stood a few degrees off during the calibration pose is turned as a whole against the truth: ``frame_sums``
+takes, for every lag of a sweep, the sums the least-squares rotation is read off (``ape_frame_sums``), ``best_frame``
+finds lag and rotation together on the host, ``rotate_rows`` applies it (``ape_rotate_rows``), ``align_frame`` does all of it and scores
+what remains; ``frame_sums_numpy`` and ``rotate_rows_numpy`` are the host statements."""
 import ctypes as C
 
 import numpy as np
@@ -437,3 +442,294 @@ def score_configs(layout: int, out, spread, truth, configs, lags=(0, 0), truth_k
         raise UserWarning("score_configs: accumulators of different sweeps")
     acc = np.stack(accs)
     return {"configs": configs, "acc": acc, "best": [best_lag(acc[c], lags, error) for c in range(len(configs))]}
+
+
+# ---- each recording's heading and frame offset against the truth (ape_frame_sums, ape_rotate_rows) -------------------------
+# A wearer who stood a few degrees off during the calibration pose, or a mocap frame that is not levelled, leaves a recording's whole
+# estimate turned against the truth by a constant world-side rotation G, truth ~ G . estimate.  ``frame_sums`` takes the sums the
+# least-squares G is read off, for every lag of a sweep in one pass; ``best_frame`` reads lag and rotation off them on the host;
+# ``rotate_rows`` applies the rotation; ``align_frame`` does all three and scores the turned rows at the lags found.
+FRAME_ACC_WIDTH = _hip.FRAME_ACC_WIDTH
+JOINT_NAMES = ("larm", "uarm", "hips")
+
+
+def _quat_matrix(q) -> np.ndarray:
+    """``[..., 4]`` quaternions ``[w, x, y, z]`` -> ``[..., 3, 3]``, with the factor ``2 / |q|^2`` (an unnormalised quaternion is the
+    rotation it stands for; the zero quaternion gives non-finite entries) -- the operations of csrc/frame_fit.hip in their order"""
+    q = np.asarray(q, dtype=np.float64)
+    w, x, y, z = q[..., 0], q[..., 1], q[..., 2], q[..., 3]
+    with np.errstate(all="ignore"):
+        s = 2.0 / (w * w + x * x + y * y + z * z)
+        xx, yy, zz, xy, xz, yz, wx, wy, wz = x * x, y * y, z * z, x * y, x * z, y * z, w * x, w * y, w * z
+        m = np.stack([1.0 - s * (yy + zz), s * (xy - wz), s * (xz + wy),
+                      s * (xy + wz), 1.0 - s * (xx + zz), s * (yz - wx),
+                      s * (xz - wy), s * (yz + wx), 1.0 - s * (xx + yy)], axis=-1)
+    return m.reshape(q.shape[:-1] + (3, 3))
+
+
+def _abt(t, e):
+    """``T E'`` for stacks of 3x3 matrices, each entry ``t0 e0 + t1 e1 + t2 e2`` added left to right"""
+    return (t[:, :, None, 0] * e[:, None, :, 0] + t[:, :, None, 1] * e[:, None, :, 1]) + t[:, :, None, 2] * e[:, None, :, 2]
+
+
+def _dot3(a, b):
+    return (a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]
+
+
+def _pair_terms(m, t, layout: int):
+    """the 49 terms ``[n, 49]`` of message rows ``m [n, 25]`` paired with est rows ``t``, and which pairs are summed ``[n]``"""
+    hips = layout != _hip.LAYOUT_ORI_CAL_LARM_UARM
+    ql, qu = (9, 13) if hips else (6, 10)
+    used = np.r_[0:6, ql:ql + 4, qu:qu + 4, 17:21] if hips else np.r_[0:6, ql:ql + 4, qu:qu + 4]
+    n = m.shape[0]
+    v = np.zeros((n, 49))
+    with np.errstate(all="ignore"):
+        v[:, 0:9] = _abt(_quat_matrix(t[:, ql:ql + 4]), _quat_matrix(m[:, 7:11])).reshape(n, 9)
+        v[:, 9:18] = _abt(_quat_matrix(t[:, qu:qu + 4]), _quat_matrix(m[:, 14:18])).reshape(n, 9)
+        if hips:
+            v[:, 18:27] = _abt(_quat_matrix(t[:, 17:21]), _quat_matrix(m[:, 21:25])).reshape(n, 9)
+        v[:, 27:36] = (t[:, 0:3, None] * m[:, None, 4:7]).reshape(n, 9)
+        v[:, 36:45] = (t[:, 3:6, None] * m[:, None, 11:14]).reshape(n, 9)
+        v[:, 45], v[:, 46] = _dot3(t[:, 0:3], t[:, 0:3]), _dot3(m[:, 4:7], m[:, 4:7])
+        v[:, 47], v[:, 48] = _dot3(t[:, 3:6], t[:, 3:6]), _dot3(m[:, 11:14], m[:, 11:14])
+    ok = np.isfinite(m).all(axis=1) & np.isfinite(t[:, used]).all(axis=1) & np.isfinite(v).all(axis=1)
+    return v, ok
+
+
+def frame_sums_numpy(msg, truth_est, layout: int, lags, starts=None, skip: int = 0, rec_lags=None) -> np.ndarray:
+    """The host statement of ``frame_sums`` for est-kind truth: float64 ``[R, L, 51]`` (include/ape_hip.h states the columns), over
+    ``score_lags_numpy``'s pairs and support; every column is summed pairwise (an error of a few ulps of the sum, where adding row by
+    row would leave ~sqrt(n) of them)."""
+    m = np.asarray(msg, dtype=np.float64)[:, :25]
+    t = np.asarray(truth_est, dtype=np.float64)
+    st = np.asarray([0] if starts is None else starts, dtype=np.int64).reshape(-1)
+    F, R = m.shape[0], st.shape[0]
+    lo, hi, off = _sweep(lags, R, rec_lags)
+    L = hi - lo + 1
+    ends = np.r_[st[1:], F]
+    acc = np.zeros((R, L, FRAME_ACC_WIDTH))
+    for r in range(R):
+        s, e, o = int(st[r]), int(ends[r]), int(off[r])
+        a, b = max(s + skip, s + o + hi), min(e, e + o + lo)                # the support: a pair at every lag, past the skipped frames
+        if a >= b:
+            continue
+        for j in range(L):
+            l = o + lo + j
+            v, ok = _pair_terms(m[a:b], t[a - l:b - l], layout)
+            acc[r, j, :49] = np.ascontiguousarray(v[ok].T).sum(axis=1)       # along the contiguous axis: numpy's pairwise summation
+            acc[r, j, 49], acc[r, j, 50] = ok.sum(), (~ok).sum()
+    return acc
+
+
+def frame_sums(layout: int, msg, truth, lags=(0, 0), truth_kind: str = "targets", starts=None, skip: int = 0, bodies=None, rec_lags=None):
+    """The sums each recording's heading is read off, for the sweep of lags ``lags=(lo, hi)`` in one pass (``ape_frame_sums``).
+    ``msg``, ``truth``, ``truth_kind``, ``starts``, ``skip``, ``bodies``, ``rec_lags``, the pairing and the support: ``score_lags``'s.
+    Returns float64 ``[R, L, 51]`` on the device: ``[0:27]`` the sums of ``T_j E_j'`` over the matrices of the truth's and the
+    message's lower-arm, upper-arm and hips quaternions (the hips block exactly 0 for the layout without hips), ``[27:45]`` the sums of
+    ``t e'`` for hand and elbow, ``[45:49]`` the sums of their squared norms, ``[49]`` / ``[50]`` the pairs summed / not summed
+    (``best_frame``).  The call does not wait for the device."""
+    md, ms, _, _, td, st, body = _prepared(layout, msg, truth, truth_kind, None, starts, bodies, torch.float64)
+    F, R, dev = int(md.shape[0]), int(st.shape[0]), md.device
+    lo, hi, off = _sweep(lags, R, rec_lags)
+    L = hi - lo + 1
+    if not 1 <= L <= _hip.SCORE_MAX_LAGS:
+        raise UserWarning(f"lags=({lo}, {hi}): between 1 and {_hip.SCORE_MAX_LAGS} lags")
+    with torch.cuda.device(dev):
+        acc = torch.empty((max(R, 1), L, FRAME_ACC_WIDTH), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_frame_sums(int(layout), C.c_void_p(md.data_ptr()), ms, _f64(md.dtype), C.c_void_p(td.data_ptr()),
+                                             TRUTH_KINDS[truth_kind], _f64(td.dtype), F, C.c_void_p(st.ctypes.data), R, int(skip),
+                                             C.c_void_p(body.ctypes.data), int(body.shape[0]), lo, hi,
+                                             C.c_void_p(off.ctypes.data) if rec_lags is not None else None, C.c_void_p(acc.data_ptr()),
+                                             stream), "ape_frame_sums")
+    return acc
+
+
+def _matrix_quat(G) -> np.ndarray:
+    """unit quaternion ``[w, x, y, z]``, ``w >= 0``, of a rotation matrix (the largest of the four pivots)"""
+    G = np.asarray(G, dtype=np.float64)
+    tr = G[0, 0] + G[1, 1] + G[2, 2]
+    piv = [tr, G[0, 0], G[1, 1], G[2, 2]]
+    k = int(np.argmax(piv))
+    if k == 0:
+        q = np.array([1.0 + tr, G[2, 1] - G[1, 2], G[0, 2] - G[2, 0], G[1, 0] - G[0, 1]])
+    elif k == 1:
+        q = np.array([G[2, 1] - G[1, 2], 1.0 + G[0, 0] - G[1, 1] - G[2, 2], G[0, 1] + G[1, 0], G[0, 2] + G[2, 0]])
+    elif k == 2:
+        q = np.array([G[0, 2] - G[2, 0], G[0, 1] + G[1, 0], 1.0 + G[1, 1] - G[0, 0] - G[2, 2], G[1, 2] + G[2, 1]])
+    else:
+        q = np.array([G[1, 0] - G[0, 1], G[0, 2] + G[2, 0], G[1, 2] + G[2, 1], 1.0 + G[2, 2] - G[0, 0] - G[1, 1]])
+    q = q / np.sqrt((q * q).sum())
+    return -q if q[0] < 0.0 else q
+
+
+def _fit(M, mode: str):
+    """(objective, G [3, 3], yaw | None) of the rotation that maximises ``tr(G' M)``"""
+    if mode == "yaw":
+        sn, cs = M[0, 2] - M[2, 0], M[0, 0] + M[2, 2]
+        psi = float(np.arctan2(sn, cs))
+        c, s = np.cos(psi), np.sin(psi)
+        return float(M[1, 1] + np.hypot(sn, cs)), np.array([[c, 0.0, s], [0.0, 1.0, 0.0], [-s, 0.0, c]]), psi
+    U, S, Vt = np.linalg.svd(M)
+    d = 1.0 if np.linalg.det(U @ Vt) >= 0.0 else -1.0
+    return float(S[0] + S[1] + d * S[2]), U @ np.diag([1.0, 1.0, d]) @ Vt, None
+
+
+def best_frame(acc, lags, mode: str = "yaw", weights=(1, 1, 1, 0, 0), rec_lags=None) -> list:
+    """Each recording's lag and world-side rotation ``G`` (truth ~ G . estimate), read off the accumulators ``acc [R, L, 51]`` of a
+    ``frame_sums`` sweep ``lags=(lo, hi)`` (with the ``rec_lags`` the sweep was made with).  ``weights``: of the lower-arm, upper-arm
+    and hips rotation sums and of the hand and elbow position sums in ``M = sum_j w_j M_j + w_hand P_hand + w_elbow P_elbow``;
+    the rotation maximises ``tr(G' M)``.
+    ``mode="yaw"``   a turn about the vertical (y): ``psi = atan2(M[0,2] - M[2,0], M[0,0] + M[2,2])``, ``g = [cos psi/2, 0, sin psi/2, 0]``
+                     (the hips quaternion's convention), objective ``M[1,1] + hypot(M[0,2] - M[2,0], M[0,0] + M[2,2])``
+    ``mode="full"``  ``M = U S V'``, ``d = sign det(U V')``, ``G = U diag(1, 1, d) V'``, objective ``S0 + S1 + d S2``
+    Per recording a dict: ``lag`` the lag with the largest objective (ties: the smaller ``|l|``, then the smaller ``l``), ``quat``
+    ``[w, x, y, z]`` with ``w >= 0``, ``matrix`` ``G``, ``yaw`` (``"yaw"`` mode; None otherwise), ``objective`` ``[L]`` (NaN where a lag has no pair),
+    ``pairs`` summed at ``lag``, and ``mean_cos_before`` / ``mean_cos_after``: per joint of ``JOINT_NAMES`` the mean cosine of the residual angle
+    between truth and estimate before and after the rotation, ``(tr(G' M_j) / pairs - 1) / 2`` (NaN for a joint whose block is zero).
+    A recording with no pairs: ``lag`` None, the identity, ``pairs`` 0."""
+    if mode not in ("yaw", "full"):
+        raise UserWarning(f"mode must be 'yaw' or 'full', got {mode!r}")
+    a = acc.detach().cpu().numpy() if isinstance(acc, torch.Tensor) else np.asarray(acc)
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 3 or a.shape[-1] != FRAME_ACC_WIDTH:
+        raise UserWarning(f"expected accumulators [R,L,{FRAME_ACC_WIDTH}], got {tuple(a.shape)}")
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != 5 or not np.isfinite(w).all() or (w < 0.0).any() or not (w > 0.0).any():
+        raise UserWarning("weights: five finite values >= 0 (lower arm, upper arm, hips, hand, elbow), not all zero")
+    R, L = a.shape[0], a.shape[1]
+    lo, hi, off = _sweep(lags, R, rec_lags)
+    if hi - lo + 1 != L:
+        raise UserWarning(f"best_frame: lags=({lo}, {hi}) for accumulators of {L} lags")
+    res = []
+    for r in range(R):
+        ls = int(off[r]) + lo + np.arange(L)
+        blocks = a[r, :, :45].reshape(L, 5, 3, 3)
+        M = (blocks * w[None, :, None, None]).sum(axis=1)
+        fits = [_fit(M[j], mode) if a[r, j, 49] > 0 else None for j in range(L)]
+        obj = np.array([np.nan if f is None else f[0] for f in fits])
+        cand = [j for j in range(L) if fits[j] is not None and np.isfinite(obj[j])]
+        if not cand:
+            nan3 = {k: float("nan") for k in JOINT_NAMES}
+            res.append({"lag": None, "quat": np.array([1.0, 0.0, 0.0, 0.0]), "matrix": np.eye(3), "yaw": 0.0 if mode == "yaw" else None,
+                        "objective": obj, "pairs": 0, "mean_cos_before": dict(nan3), "mean_cos_after": dict(nan3)})
+            continue
+        j = min(cand, key=lambda k: (-obj[k], abs(int(ls[k])), int(ls[k])))
+        _, G, psi = fits[j]
+        n = float(a[r, j, 49])
+        before, after = {}, {}
+        for k, name in enumerate(JOINT_NAMES):
+            Mj = blocks[j, k]
+            zero = not Mj.any()
+            before[name] = float("nan") if zero else float((np.trace(Mj) / n - 1.0) / 2.0)
+            after[name] = float("nan") if zero else float(((G * Mj).sum() / n - 1.0) / 2.0)
+        quat = np.array([np.cos(psi / 2.0), 0.0, np.sin(psi / 2.0), 0.0]) if mode == "yaw" else _matrix_quat(G)
+        res.append({"lag": int(ls[j]), "quat": quat, "matrix": G, "yaw": psi, "objective": obj, "pairs": int(n),
+                    "mean_cos_before": before, "mean_cos_after": after})
+    return res
+
+
+def _qmul(a, b):
+    """the quaternion product of utility/transformations.py, term order as in csrc/fk_device.h"""
+    return np.stack([a[..., 0] * b[..., 0] - a[..., 1] * b[..., 1] - a[..., 2] * b[..., 2] - a[..., 3] * b[..., 3],
+                     a[..., 0] * b[..., 1] + a[..., 1] * b[..., 0] + a[..., 2] * b[..., 3] - a[..., 3] * b[..., 2],
+                     a[..., 0] * b[..., 2] - a[..., 1] * b[..., 3] + a[..., 2] * b[..., 0] + a[..., 3] * b[..., 1],
+                     a[..., 0] * b[..., 3] + a[..., 1] * b[..., 2] - a[..., 2] * b[..., 1] + a[..., 3] * b[..., 0]], axis=-1)
+
+
+def _mat_vec(G, p):
+    """``G p`` per row, each entry added left to right"""
+    return (G[:, :, 0] * p[:, None, 0] + G[:, :, 1] * p[:, None, 1]) + G[:, :, 2] * p[:, None, 2]
+
+
+def _unit_quats(quats, R: int) -> np.ndarray:
+    """float64 ``[1 | R, 4]`` of one quaternion or one per recording, normalised; zero and non-finite quaternions are refused"""
+    q = np.asarray(quats, dtype=np.float64)
+    q = q.reshape(1, 4) if q.size == 4 else q
+    if q.ndim != 2 or q.shape[1] != 4 or q.shape[0] not in (1, R):
+        raise UserWarning(f"quats: one quaternion [4] or one per recording [{R}, 4], got {tuple(q.shape)}")
+    with np.errstate(all="ignore"):
+        n = np.sqrt(((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]) + q[:, 3] * q[:, 3])
+    if not (np.isfinite(n).all() and (n > 0.0).all()):
+        raise UserWarning("quats: a zero or non-finite quaternion")
+    return np.ascontiguousarray(q / n[:, None])
+
+
+def rotate_rows_numpy(msg, quats, spread=None, starts=None):
+    """The host statement of ``rotate_rows``: float64 ``out [F, 25]`` or ``(out, spread [F, 21])``.  With ``g`` the recording's
+    quaternion (normalised) and ``G`` its matrix: message quaternions ``g (x) q``, origins ``G p``, spread means ``G m``, covariances
+    ``G S G'``, angular spreads as they are."""
+    m = np.asarray(msg, dtype=np.float64)[:, :25]
+    st = np.asarray([0] if starts is None else starts, dtype=np.int64).reshape(-1)
+    F, R = m.shape[0], st.shape[0]
+    unit = _unit_quats(quats, R)
+    rec = np.searchsorted(st, np.arange(F), side="right") - 1 if unit.shape[0] > 1 else np.zeros(F, dtype=np.int64)
+    g = unit[rec]
+    G = _quat_matrix(g)
+    out = np.empty((F, 25))
+    with np.errstate(all="ignore"):
+        for c in (0, 7, 14, 21):
+            out[:, c:c + 4] = _qmul(g, m[:, c:c + 4])
+        for c in (4, 11, 18):
+            out[:, c:c + 3] = _mat_vec(G, m[:, c:c + 3])
+        if spread is None:
+            return out
+        s = np.asarray(spread, dtype=np.float64)[:, :_hip.SPREAD_WIDTH]
+        rot = np.empty((F, _hip.SPREAD_WIDTH))
+        for o in (0, 9):
+            rot[:, o:o + 3] = _mat_vec(G, s[:, o:o + 3])
+            S = s[:, o + 3:o + 9][:, [0, 1, 2, 1, 3, 4, 2, 4, 5]].reshape(F, 3, 3)
+            A = (G[:, :, None, 0] * S[:, None, 0, :] + G[:, :, None, 1] * S[:, None, 1, :]) + G[:, :, None, 2] * S[:, None, 2, :]     # G S
+            full = _abt(A, G)                                                                                                       # (G S) G'
+            rot[:, o + 3:o + 9] = full.reshape(F, 9)[:, [0, 1, 2, 4, 5, 8]]
+        rot[:, 18:] = s[:, 18:]
+    return out, rot
+
+
+def rotate_rows(layout: int, msg, quats, spread=None, starts=None, out_dtype=None):
+    """Replay rows turned by a world-side rotation per recording (``ape_rotate_rows``): ``msg`` device ``[F, >= 25]`` (nothing past
+    column 24 is read), ``quats`` ``[4]`` or ``[R, 4]`` ``[w, x, y, z]`` (normalised here; ``best_frame``'s ``quat``), ``spread``
+    device ``[F, >= 21]`` of ``msg``'s dtype or None, ``starts`` the recordings' first frames.  Returns ``out [F, 25]`` of ``out_dtype``
+    (default: ``msg``'s), or with ``spread`` ``(out, spread [F, 21])``, two views of one ``[F, 46]`` tensor as
+    ``process_recording(spread=True)`` returns them.  The call does not wait for the device."""
+    if layout not in _hip.EST_WIDTH:
+        raise UserWarning(f"layout {layout} has no pose to rotate")
+    md, ms = _rows_view(msg, 25, "msg")
+    out_dtype = md.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+    F, dev = int(md.shape[0]), md.device
+    sd, ss = (None, 0)
+    if spread is not None:
+        sd, ss = _rows_view(spread, _hip.SPREAD_WIDTH, "spread")
+        if sd.dtype != md.dtype or sd.shape[0] != F or sd.device != dev:
+            raise UserWarning("spread: the dtype, device and frame count of msg")
+    st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
+    R = int(st.shape[0])
+    unit = _unit_quats(quats, R)
+    with torch.cuda.device(dev):
+        width = 25 + (_hip.SPREAD_WIDTH if sd is not None else 0)
+        out = torch.empty((F, width), dtype=out_dtype, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_rotate_rows(int(layout), C.c_void_p(md.data_ptr()), ms, C.c_void_p(sd.data_ptr()) if sd is not None else None,
+                                              ss, _f64(md.dtype), F, C.c_void_p(st.ctypes.data), R, C.c_void_p(unit.ctypes.data),
+                                              int(unit.shape[0]), C.c_void_p(out.data_ptr()), _f64(out_dtype), stream), "ape_rotate_rows")
+    if sd is not None:
+        return out[:, :25], out[:, 25:]
+    return out
+
+
+def align_frame(layout: int, msg, truth, lags, mode: str = "yaw", weights=(1, 1, 1, 0, 0), truth_kind: str = "targets", spread=None,
+                starts=None, skip: int = 0, bodies=None):
+    """Find each recording's lag and heading together and score with both removed: a ``frame_sums`` sweep, ``best_frame`` on it (this
+    waits for the device), ``rotate_rows`` by the rotations found, then ``score_lags`` of the turned rows with ``lags=(0, 0)`` and the
+    lags found as offsets (lag 0 and no turn for a recording with an empty support).  Returns ``(score, acc, found)``: the per-frame
+    rows ``[F, 7]`` and accumulators ``[R, 25]`` at every recording's own lag and heading, and ``best_frame``'s list."""
+    sums = frame_sums(layout, msg, truth, lags, truth_kind, starts, skip, bodies)
+    found = best_frame(sums, lags, mode, weights)
+    quats = np.stack([b["quat"] for b in found])
+    rec_lags = [0 if b["lag"] is None else b["lag"] for b in found]
+    turned = rotate_rows(layout, msg, quats, spread, starts)
+    out, rec = turned if spread is not None else (turned, None)
+    score, acc = score_lags(layout, out, truth, (0, 0), truth_kind, rec, starts, skip, bodies, rec_lags, per_frame=True)
+    return score[:, 0], acc[:, 0], found

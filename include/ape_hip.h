@@ -943,6 +943,55 @@ int ape_post_sweep(ape_model_t* model, const float* y_dev, int32_t F, int32_t n_
                    int64_t workspace_bytes, void* stream);
 int ape_post_sweep_last(int32_t out4[4]);
 
+/* ---- each recording's heading and frame offset against the truth (additive in ABI 7) -------------------------------------
+ * replaces: nothing; the reference has no counterpart.  Every input is calibrated against a forward direction taken from a calibration
+ * pose; a wearer who stood a few degrees off, or a mocap frame that is not levelled, leaves the whole estimate of a recording turned
+ * against the truth by a constant world-side rotation G, truth ~ G . estimate, which ape_score_rows books as error on every frame and
+ * which ape_score_lags fits a lag to.  The least-squares G of a recording is read off sums of 3x3 products (score.py: best_frame);
+ * ape_frame_sums takes those sums for every lag of a sweep in one pass, ape_rotate_rows applies a rotation to replay rows.
+ * ape_frame_sums.  Arguments: those of ape_score_lags up to rec_lag_host with the same meaning, without spread_dev / spread_stride
+ * (no spread record is read).  Pairing, the sign of a lag, the per-recording offsets, the support of the accumulators (skip, lag_max,
+ * lag_min) and the bounds APE_SCORE_MAX_LAG / APE_SCORE_MAX_LAGS are ape_score_lags's; truth rows go through the same conversion; all
+ * three layouts are served.
+ *   Rotation of a quaternion q = [w, x, y, z]: with s = 2 / (w^2 + x^2 + y^2 + z^2), the rows [1 - s (yy + zz), s (xy - wz), s (xz + wy)],
+ *   [s (xy + wz), 1 - s (xx + zz), s (yz - wx)], [s (xz - wy), s (yz + wx), 1 - s (xx + yy)]: an unnormalised quaternion is used as the
+ *   rotation it stands for.  float64 with separate roundings.
+ *   Per pair (message f, truth f - l), with E_j the matrices of msg[7:11], msg[14:18], msg[21:25], T_j those of the truth's lower-arm,
+ *   upper-arm and hips quaternions, e_hand = msg[4:7], e_elbow = msg[11:14], t_hand and t_elbow the truth's positions,
+ *   acc_dev f64 [R, L, APE_FRAME_ACC_WIDTH] receives over the support:
+ *     [0:9], [9:18], [18:27]  sum of T_j E_j', row-major, j = lower arm, upper arm, hips.  APE_LAYOUT_ORI_CAL_LARM_UARM (no hips): the
+ *                             hips block is exactly 0 (both sides are the identity there and would pull every fit towards "no turn")
+ *     [27:36], [36:45]        sum of t_hand e_hand', sum of t_elbow e_elbow'
+ *     [45:49]                 sum of |t_hand|^2, |e_hand|^2, |t_elbow|^2, |e_elbow|^2
+ *     [49], [50]              pairs of the support that were summed / that were not
+ *   A pair is summed iff ape_score_lags would score it (25 finite message values, every used truth value finite) and all of its 49
+ *   terms are finite (a zero quaternion makes them non-finite).  [49] + [50] is the same for every lag of a recording; a recording
+ *   with an empty support gives zeros.  No floating-point atomics and a fixed order of summation: the same inputs give the same bits.
+ * Needs no model handle, runs on the current HIP device, does not wait; the host arrays have been consumed when it returns; staging
+ * slots as ape_score_rows keeps them (its own: the first call of a size allocates, later ones do not).  Refused with
+ * APE_ERR_INVALID_ARG on the host, before anything is written: everything ape_score_lags refuses (less the spread arguments and the
+ * score dtype), a NULL acc_dev, a capturing stream.
+ * ape_rotate_rows.  With g = quats_host[r] (one for all recordings, or one per recording), normalised on the host, and G its matrix:
+ *   the four message quaternions [0:4], [7:11], [14:18], [21:25] become g (x) q (no sign flip: scoring is sign-blind); the three origins
+ *   [4:7], [11:14], [18:21] become G p; of a spread record (spread_dev, or NULL) the two means become G m, the two covariances G S G'
+ *   (six stored entries each, APE_SPREAD_WIDTH's order), the three angular spreads are copied.  NaN propagates.  Nothing past column 24
+ *   of a message row is read (a packed row's cloud is not carried over).  APE_LAYOUT_ORI_CAL_LARM_UARM: the message's hips quaternion
+ *   and constant shoulder origin are rotated like the rest -- the result describes the pose in the truth's frame.
+ *   out_dev [F, 25] of out_dtype, with spread_dev [F, 25 + APE_SPREAD_WIDTH] (the record in the last 21 columns); it must not alias the
+ *   inputs.  float64 arithmetic whatever the storage; one lane per frame, one launch.
+ * Host behaviour as above.  Refused with APE_ERR_INVALID_ARG before anything is written: NULL msg_dev / seg_starts_host / quats_host /
+ * out_dev, F < 1, R < 1, bad starts, strides too small, n_quats not 1 or R, a zero or non-finite quaternion, APE_LAYOUT_NONE or an
+ * unknown layout / dtype, out_dev equal to an input, a capturing stream. */
+#define APE_FRAME_ACC_WIDTH 51
+int ape_frame_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int32_t msg_dtype, const void* truth_dev, int32_t truth_kind,
+                   int32_t truth_dtype, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t skip, const double* bodies_host,
+                   int32_t n_bodies, int32_t lag_min, int32_t lag_max, const int32_t* rec_lag_host /* [R] or NULL */,
+                   double* acc_dev /* f64 [R, L, 51] */, void* stream);
+int ape_rotate_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, const void* spread_dev, int32_t spread_stride,
+                    int32_t msg_dtype, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                    const double* quats_host /* [n_quats, 4], n_quats 1 or R, [w,x,y,z] */, int32_t n_quats,
+                    void* out_dev /* [F, 25] or, with spread_dev, [F, 25 + 21] */, int32_t out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
