@@ -1536,6 +1536,7 @@ int ape_streams_destroy(ape_streams_t* b) {
     for (auto ev : b->prof_ev) if (ev) (void)hipEventDestroy(ev);
     subset_free(b);                     // (drops the bank's pending subset frame as below)
     ape_body_table_free(b->bodies);
+    ape_smooth_table_free(b->smooths);
     b->sub_stage.free();
     if (b->state_desc) (void)hipFree(b->state_desc);
     if (ape_model* m = b->model) {      // pending steps of this bank can no longer be re-issued
@@ -1573,6 +1574,27 @@ int ape_streams_set_bodies(ape_streams_t* b, const int32_t* streams_host, int32_
 int ape_streams_get_bodies(ape_streams_t* b, double* out_host) {
     if (!b || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "streams_get_bodies: NULL argument");
     ape_body_table_get(b->bodies, b->S, b->model->body, out_host);
+    return APE_OK;
+}
+
+// per-stream smoothing lengths: replaces the `smooth` every reference Estimator is built with (estimator.py:45,112-118).
+// A cold start of the listed streams: the reference fixes the value at construction, a change has no defined transition.
+// (a capacity of one row holds nothing but ones: such a bank keeps its table and goes on running the forms it ran)
+static bool bank_smooths_on(const ape_streams* b) { return b->smooths.on() && b->smooth > 1; }
+static int bank_smooth_of(const ape_streams* b, int s) { return bank_smooths_on(b) ? b->smooths.host[(size_t)s] : b->smooth; }
+
+int ape_streams_set_smooths(ape_streams_t* b, const int32_t* streams_host, int32_t K, const int32_t* smooths_host, void* stream) {
+    if (int rc = ape_smooth_table_check("streams_set_smooths", b, streams_host, K, b ? b->S : 0, smooths_host, b ? b->smooth : 0)) return rc;
+    APE_TRY(hipSetDevice(b->model->dims.device));
+    if (int rc = ape_check_not_capturing((hipStream_t)stream, "streams_set_smooths", "the table's image is staged per call")) return rc;
+    APE_TRY(ape_smooth_table_set(b->smooths, b->S, b->smooth, streams_host, K, smooths_host, (hipStream_t)stream));
+    if (!streams_host) return ape_streams_reset(b);
+    return ape_streams_reset_subset(b, streams_host, K);
+}
+
+int ape_streams_get_smooths(ape_streams_t* b, int32_t* out_host) {
+    if (!b || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "streams_get_smooths: NULL argument");
+    ape_smooth_table_get(b->smooths, b->S, b->smooth, out_host);
     return APE_OK;
 }
 
@@ -1840,8 +1862,13 @@ static int streams_step_impl(ape_streams_t* b, uint32_t flags, void* msg_dev, vo
     ++b->mc_calls;       // (every branch above enqueued one forward under seed + mc_calls)
     StreamPostParams q = post_params();
     b->last_post_form = ape_stream_post_form(q, q.part != nullptr && (!spread || b->post_spread != nullptr));
-    hipError_t e = spread ? ape_launch_stream_post_spread(q, SpreadArgs{b->post_spread}, b->last_post_form, (hipStream_t)stream, b->bodies.dev)
-                          : ape_launch_stream_post(q, (hipStream_t)stream, b->bodies.dev);      // (table mode: row s for stream s, q.body unread)
+    const SpreadArgs spa{b->post_spread};
+    // (per-stream smoothing lengths: the table forms, with the count itself -- n mod k differs from stream to stream; a re-issued step
+    //  comes through here with b->steps set back, and reads the bank's table like any frame)
+    hipError_t e = bank_smooths_on(b) ? ape_launch_stream_post_smooths(q, SmoothArgs{b->smooths.dev, (unsigned long long)b->steps}, spread ? &spa : nullptr,
+                                                                       b->last_post_form, (hipStream_t)stream, b->bodies.dev)
+                   : spread       ? ape_launch_stream_post_spread(q, spa, b->last_post_form, (hipStream_t)stream, b->bodies.dev)
+                                  : ape_launch_stream_post(q, (hipStream_t)stream, b->bodies.dev);      // (table mode: row s for stream s, q.body unread)
     if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "streams_step launch failed: %s", hipGetErrorString(e));
     ++b->steps;
     journal_add(m, je);
@@ -2048,7 +2075,11 @@ static int subset_regress_post(ape_streams* b, int K, uint32_t flags, void* out_
     if (hw.status_out != nullptr && m->caps.cluster_ok) { q.status_in = ctl_words(m).status; q.status_out = hw.status_out; }
     if (hw.done_out != nullptr) { q.done_out = hw.done_out; q.done_val = hw.done_val; }      // (word j behind list entry j's row)
     b->last_post_form = ape_stream_post_form(q, q.part != nullptr && (!(flags & APE_FLAG_SPREAD) || b->post_spread != nullptr));
-    hipError_t e = (flags & APE_FLAG_SPREAD)
+    const SpreadArgs spa{b->post_spread};
+    hipError_t e = bank_smooths_on(b)
+                       ? ape_launch_stream_post_subset_smooths(q, b->sub_desc, SmoothArgs{b->smooths.dev, 0ull}, (flags & APE_FLAG_SPREAD) ? &spa : nullptr,
+                                                               b->last_post_form, (hipStream_t)stream, b->bodies.dev)
+                   : (flags & APE_FLAG_SPREAD)
                        ? ape_launch_stream_post_subset_spread(q, b->sub_desc, SpreadArgs{b->post_spread}, b->last_post_form, (hipStream_t)stream,
                                                               b->bodies.dev)
                        : ape_launch_stream_post_subset(q, b->sub_desc, (hipStream_t)stream, b->bodies.dev);
@@ -2098,7 +2129,7 @@ static void subset_fill_desc(const ape_streams* b, const int32_t* streams_host, 
         const long long f = b->s_frames[s], p = b->s_steps[s];
         h[j].stream = s;
         h[j].slot = (int)(f % b->T); h[j].cold = f == 0 ? 1 : 0;
-        h[j].pos = (int)(p % b->smooth); h[j].pcold = p == 0 ? 1 : 0;
+        h[j].pos = (int)(p % bank_smooth_of(b, s)); h[j].pcold = p == 0 ? 1 : 0;
     }
 }
 
@@ -2260,7 +2291,8 @@ static int state_launch(ape_streams* b, const char* what, int K, float* state, h
     p.xring = b->xring; p.yring = b->yring; p.state = state; p.desc = b->state_desc;
     p.x_stream_stride = (size_t)bank_copies(b) * d.T * d.I;
     p.K = K; p.T = d.T; p.I = d.I; p.smooth = d.smooth; p.MO = d.n_mc * d.O; p.words = d.words_per_stream;
-    const hipError_t e = import ? ape_launch_state_import(p, st) : ape_launch_state_export(p, st);
+    const hipError_t e = bank_smooths_on(b) ? ape_launch_state_smooths(p, b->smooths.dev, import, st)
+                         : import           ? ape_launch_state_import(p, st) : ape_launch_state_export(p, st);
     if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
     return APE_OK;
 }
@@ -2283,7 +2315,7 @@ int ape_streams_export(ape_streams_t* b, const int32_t* streams_host, int32_t K,
         const int s = streams_host[j];
         const long long f = b->per_stream ? b->s_frames[s] : b->frames, p = b->per_stream ? b->s_steps[s] : b->steps;
         // the newest row sits in slot (f - 1) mod T, so the oldest of the T rows in slot f mod T (all T slots are filled from the first row on)
-        d.stream = s; d.wslot = (int)(f % b->T); d.sslot = (int)(p % b->smooth);
+        d.stream = s; d.wslot = (int)(f % b->T); d.sslot = (int)(p % bank_smooth_of(b, s));
         d.warm = (f > 0 ? APE_STATE_WINDOW_WARM : 0) | (f > 0 && p > 0 ? APE_STATE_STACK_WARM : 0);
         warm_host[j] = (uint8_t)d.warm;
     };
@@ -2314,7 +2346,7 @@ int ape_streams_import(ape_streams_t* b, const ape_stream_state_desc_t* desc, co
         const int s = streams_host[j];
         const bool w = (warm_host[j] & APE_STATE_WINDOW_WARM) != 0, p = w && (warm_host[j] & APE_STATE_STACK_WARM) != 0;
         b->s_frames[s] = w ? b->T : 0;
-        b->s_steps[s] = p ? b->smooth : 0;
+        b->s_steps[s] = p ? bank_smooth_of(b, s) : 0;        // (the record was read with the slot's own length: that many predictions)
     }
     // the rings changed behind the bank's pending frame: like a newer frame, the import takes it off the journal
     ape_model* m = b->model;

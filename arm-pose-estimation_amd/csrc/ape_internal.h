@@ -260,6 +260,13 @@ struct SpreadArgs {
     double* part;        // split form: [S][chunks][4 role waves][18] partial spread sums beside p.part, or nullptr
 };
 
+// Per-stream smoothing lengths (stream_post_device.h, SMT): what the table forms need beyond StreamPostParams, as a kernel
+// argument of their own -- the struct above and the other forms' object code stay what they were
+struct SmoothArgs {
+    const int* smooths;          // [S] device table, each in [1, p.smooth]; indexed by the stream
+    unsigned long long count;    // lockstep frames: predictions since the cold start (subset frames: the descriptors carry the slots)
+};
+
 // the form the post-filter's launchers pick for a frame: 0 = wide (lanes = streams), 1 = one workgroup per stream, c > 1 = split over c
 // workgroups per stream (have_part: the bank holds the split form's workspaces)
 static inline int ape_stream_post_form(const StreamPostParams& p, bool have_part) {
@@ -519,6 +526,7 @@ hipError_t ape_launch_subset_rows_host(const SubsetRowsParams& p, SubsetDesc* la
 // ring order <-> the canonical time-ordered records of the listed streams, one launch each (stream_state.hip)
 hipError_t ape_launch_state_export(const StateParams& p, hipStream_t stream);
 hipError_t ape_launch_state_import(const StateParams& p, hipStream_t stream);
+hipError_t ape_launch_state_smooths(const StateParams& p, const int* smooths, bool import, hipStream_t stream);
 // DropoutFF / ImuPoseLSTM banks (ff_bank.hip): the n_mc masked heads over a trunk computed once per stream; the time-ordered copy of the
 // window rings [S][T][I] (step t in slot (t + x_ring) mod T)
 hipError_t ape_launch_ff_bank_head(const FfHeadParams& p, hipStream_t stream);
@@ -528,3 +536,9 @@ hipError_t ape_launch_ring_windows(const float* xring, float* xw, int S, int T, 
 hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const SubsetDesc* desc, hipStream_t stream, const double* bodies = nullptr);
 hipError_t ape_launch_stream_post_subset_spread(const StreamPostParams& p, const SubsetDesc* desc, const SpreadArgs& sp, int form, hipStream_t stream,
                                                 const double* bodies = nullptr);
+// ... of a bank with per-stream smoothing lengths (stream_post_device.h, SMT): form = 1 or the split's chunk count, sp = nullptr without
+// APE_FLAG_SPREAD, bodies = the bank's table or nullptr (p.body); the subset form reads sm.smooths[desc[j].stream]
+hipError_t ape_launch_stream_post_smooths(const StreamPostParams& p, const SmoothArgs& sm, const SpreadArgs* sp, int form, hipStream_t stream,
+                                          const double* bodies = nullptr);
+hipError_t ape_launch_stream_post_subset_smooths(const StreamPostParams& p, const SubsetDesc* desc, const SmoothArgs& sm, const SpreadArgs* sp, int form,
+                                                 hipStream_t stream, const double* bodies = nullptr);

@@ -8,6 +8,7 @@
 #include "ape_internal.h"
 #include "ape_plan.h"
 #include "body_table.h"
+#include "smooth_table.h"
 #include "bank_host.h"
 
 struct ape_streams;
@@ -175,4 +176,6 @@ struct ape_streams {
     StateDesc* state_desc = nullptr;  // [S]
     // per-stream body measurements (ape_streams_set_bodies): off until the first call -- the frames then read model->body
     ApeBodyTable bodies;         // [S,9] on the device
+    // per-stream smoothing lengths (ape_streams_set_smooths): off until the first call -- `smooth` is then the capacity
+    ApeSmoothTable smooths;      // [S] on the device
 };

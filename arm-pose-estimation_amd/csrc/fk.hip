@@ -303,6 +303,27 @@ hipError_t launch_stream_post_spread(const StreamPostParams& p, const SpreadArgs
     return hipGetLastError();
 }
 
+// ... and the forms of a bank with per-stream smoothing lengths (stream_post_device.h, SMT): one workgroup per stream or
+// the split over the capacity's chunks; the bodies are the bank's table or, nullptr, p.body
+template <typename TMsg, bool SPR>
+__global__ __launch_bounds__(256) void ape_stream_post_smooths_kernel(const StreamPostParams p, const double* bodies, const SpreadArgs sp,
+                                                                      const SmoothArgs sm) {
+    stream_post<TMsg, false, false, false, SPR, true>(p, (int)blockIdx.x, 0, 1, nullptr, bodies, sp, sm);
+}
+template <typename TMsg, bool SPR>
+__global__ __launch_bounds__(256) void ape_stream_post_split_smooths_kernel(const StreamPostParams p, const int chunks, const double* bodies,
+                                                                            const SpreadArgs sp, const SmoothArgs sm) {
+    stream_post<TMsg, true, false, false, SPR, true>(p, (int)blockIdx.x / chunks, (int)blockIdx.x % chunks, chunks, nullptr, bodies, sp, sm);
+}
+
+template <typename TMsg, bool SPR>
+hipError_t launch_stream_post_smooths(const StreamPostParams& p, const SmoothArgs& sm, const SpreadArgs& sp, int form, const double* bodies,
+                                      hipStream_t stream) {
+    if (form > 1) hipLaunchKernelGGL((ape_stream_post_split_smooths_kernel<TMsg, SPR>), dim3(p.S * form), dim3(256), 0, stream, p, form, bodies, sp, sm);
+    else hipLaunchKernelGGL((ape_stream_post_smooths_kernel<TMsg, SPR>), dim3(p.S), dim3(256), 0, stream, p, bodies, sp, sm);
+    return hipGetLastError();
+}
+
 template <typename TIn, typename TOut>
 hipError_t launch_fk(const FkParams& p, hipStream_t stream) {
     hipLaunchKernelGGL((ape_fk3_kernel<TIn, TOut, false>), dim3((p.N + FK3_ROWS - 1) / FK3_ROWS), dim3(128), 0, stream, p, FkBodyRows{});
@@ -381,4 +402,17 @@ hipError_t ape_launch_stream_post(const StreamPostParams& p, hipStream_t stream,
     if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_stream_post_kernel<float>, dim3(grid), dim3(256), 0, stream, p);
     else hipLaunchKernelGGL(ape_stream_post_kernel<double>, dim3(grid), dim3(256), 0, stream, p);
     return hipGetLastError();
+}
+
+// the table forms (SMT): `form` is ape_stream_post_form's answer for the capacity, 1 or the split's chunk count -- never the wide form,
+// which only exists at a capacity of one row, where a table changes nothing; sp: nullptr without APE_FLAG_SPREAD
+hipError_t ape_launch_stream_post_smooths(const StreamPostParams& p, const SmoothArgs& sm, const SpreadArgs* sp, int form, hipStream_t stream,
+                                          const double* bodies) {
+    if (form < 1 || sm.smooths == nullptr) return hipErrorInvalidValue;
+    if (form > 1 && (p.part == nullptr || (sp != nullptr && sp->part == nullptr))) return hipErrorInvalidValue;
+    if (sp != nullptr)
+        return p.msg_dtype == APE_F32 ? launch_stream_post_smooths<float, true>(p, sm, *sp, form, bodies, stream)
+                                      : launch_stream_post_smooths<double, true>(p, sm, *sp, form, bodies, stream);
+    return p.msg_dtype == APE_F32 ? launch_stream_post_smooths<float, false>(p, sm, SpreadArgs{}, form, bodies, stream)
+                                  : launch_stream_post_smooths<double, false>(p, sm, SpreadArgs{}, form, bodies, stream);
 }

@@ -20,6 +20,7 @@
 #include "parse_device.h"
 #include "stream_post_device.h"
 #include "body_table.h"
+#include "smooth_table.h"
 #include "bank_host.h"
 
 #pragma clang fp contract(off)
@@ -133,6 +134,41 @@ __global__ __launch_bounds__(FK_BLOCK) void ape_fk_bank_kernel(const FkBankParam
     }
 }
 
+// The same frame for a bank with per-stream smoothing lengths: stream s stacks its last k = sm.smooths[s] rows instead
+// of p.smooth -- the S estimators of the reference built with S values of `smooth` (estimator.py:45,112-118).  p.smooth stays the capacity
+// and the ring's stride; the stream lives in slots 0 .. k-1.  Lockstep frames without descriptors take the slot from the count itself
+// (sm.count mod k: not uniform over the streams); descriptors carry a slot taken mod k on the host.  A kernel of its own (the frame is
+// thirty lines): the kernel above keeps its instruction stream.
+template <typename TMsg, bool TAB = false>
+__global__ __launch_bounds__(FK_BLOCK) void ape_fk_bank_smooths_kernel(const FkBankParams p, const double* __restrict__ bodies, const int S,
+                                                                       const SmoothArgs sm) {
+    const int j = blockIdx.x * FK_BLOCK + threadIdx.x;
+    if (j >= p.K) return;
+    const int s = p.desc ? p.desc[j].stream : j;
+    const int k = sm.smooths[s];
+    const int pos = p.desc ? p.desc[j].pos : (int)(sm.count % (unsigned long long)k);
+    const bool cold = p.desc ? p.desc[j].cold != 0 : p.cold != 0;
+    double* ring = p.ring + (size_t)s * (p.smooth * 8);
+    double q8[8];
+    row_quats(p.rows + (size_t)j * FK_WIDTH, p.big_endian, q8);
+    for (int t = cold ? 0 : pos; t < (cold ? k : pos + 1); ++t)
+#pragma unroll
+        for (int c = 0; c < 8; ++c) ring[t * 8 + c] = q8[c];
+    double m[25], own[9];
+    if constexpr (TAB) {
+#pragma unroll
+        for (int c = 0; c < 9; ++c) own[c] = bodies[(size_t)c * S + s];
+    }
+    stack_msg(k, [&](int i) -> const double* { int t = pos + 1 + i; if (t >= k) t -= k; return ring + t * 8; }, TAB ? own : p.body, m);
+    TMsg* dst = static_cast<TMsg*>(p.out) + (size_t)j * 25;
+#pragma unroll
+    for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
+    if (p.done != nullptr) {
+        __threadfence_system();
+        __hip_atomic_store(p.done + j, p.done_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+}
+
 __global__ __launch_bounds__(FK_BLOCK) void ape_fk_replay_rows_kernel(const FkReplayParams p) {
     const int f = blockIdx.x * FK_BLOCK + threadIdx.x;
     if (f >= p.F) return;
@@ -176,6 +212,32 @@ __global__ __launch_bounds__(FK_BLOCK) void ape_fk_state_kernel(double* __restri
     } else {
         const f64x2 zero = {0.0, 0.0};
         *s = d.cold ? zero : *r;
+    }
+}
+
+// ... of a bank with per-stream smoothing lengths: the record keeps the capacity's [smooth][8], stream s's k = smooths[s] rows oldest
+// first and zeros behind them; in the ring the stream lives in slots 0 .. k-1 (desc.pos was taken mod k)
+template <bool IMPORT>
+__global__ __launch_bounds__(FK_BLOCK) void ape_fk_state_smooths_kernel(double* __restrict__ ring, double* __restrict__ state,
+                                                                        const FkDesc* __restrict__ desc, const int K, const int smooth,
+                                                                        const int* __restrict__ smooths) {
+    const int units = smooth * 4;
+    const long long idx = (long long)blockIdx.x * FK_BLOCK + threadIdx.x;
+    if (idx >= (long long)K * units) return;
+    const int j = (int)(idx / units), u = (int)(idx - (long long)j * units);
+    const FkDesc d = desc[j];
+    const int k = smooths[d.stream];
+    const int i = u >> 2, c = (u & 3) * 2;
+    int slot = d.pos + i;
+    if (slot >= k) slot -= k;
+    const bool live = i < k && !d.cold;
+    f64x2* r = reinterpret_cast<f64x2*>(ring + ((size_t)d.stream * smooth + (live ? slot : 0)) * 8 + c);
+    f64x2* s = reinterpret_cast<f64x2*>(state) + idx;
+    if constexpr (IMPORT) {
+        if (live) *r = *s;
+    } else {
+        const f64x2 zero = {0.0, 0.0};
+        *s = live ? *r : zero;
     }
 }
 
@@ -231,12 +293,15 @@ struct ape_fk_bank {
     unsigned done_val = 0;
     char* hs_block = nullptr;          // frame_subset_host: ONE pinned block of completion words, descriptors and rows
     ApeBodyTable bodies;               // per-stream bodies, component-major [9,S] on the device (off until ape_fk_bank_set_bodies)
+    ApeSmoothTable smooths;            // per-stream smoothing lengths [S] (off until ape_fk_bank_set_smooths: `smooth` is then the capacity)
+    int smooth_of(int s) const { return smooths.of(s, smooth); }
 };
 
 namespace {
 
 void bank_free(ape_fk_bank* b) {
     ape_body_table_free(b->bodies);
+    ape_smooth_table_free(b->smooths);
     if (b->ring) (void)hipFree(b->ring);
     if (b->desc) (void)hipFree(b->desc);
     b->stage.free();
@@ -264,7 +329,7 @@ int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* s
     memcpy(p.body, b->body, sizeof(p.body));
     if (!streams_host && b->uniform) {
         p.desc = nullptr;
-        p.pos = (int)(b->ucount % b->smooth); p.cold = b->ucount == 0 ? 1 : 0;
+        p.pos = (int)(b->ucount % b->smooth); p.cold = b->ucount == 0 ? 1 : 0;      // (a table bank: the kernel takes ucount mod k itself)
     } else {
         if (streams_host) leave_uniform(b);
         // the descriptors into the next pinned slot -- once the copy that last read it has completed
@@ -274,7 +339,7 @@ int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* s
         for (int j = 0; j < K; ++j) {
             const int s = streams_host ? streams_host[j] : j;
             const long long c = b->cnt[s];
-            h[j] = FkDesc{s, (int)(c % b->smooth), c == 0 ? 1 : 0, 0};
+            h[j] = FkDesc{s, (int)(c % b->smooth_of(s)), c == 0 ? 1 : 0, 0};
         }
         if (pinned_desc) p.desc = pinned_desc;
         else {
@@ -283,7 +348,13 @@ int bank_frame(ape_fk_bank* b, int32_t kind, const float* rows, const int32_t* s
         }
     }
     const double* const none = nullptr;
-    const hipError_t e = b->bodies.on() ? launch_typed(ape_fk_bank_kernel<float, true>, ape_fk_bank_kernel<double, true>, out_dtype, K, st, p, (const double*)b->bodies.dev, b->S)
+    const SmoothArgs sm{b->smooths.dev, (unsigned long long)b->ucount};
+    const hipError_t e = b->smooths.on()
+                             ? (b->bodies.on() ? launch_typed(ape_fk_bank_smooths_kernel<float, true>, ape_fk_bank_smooths_kernel<double, true>, out_dtype, K, st, p,
+                                                              (const double*)b->bodies.dev, b->S, sm)
+                                               : launch_typed(ape_fk_bank_smooths_kernel<float, false>, ape_fk_bank_smooths_kernel<double, false>, out_dtype, K, st, p,
+                                                              none, 0, sm))
+                         : b->bodies.on() ? launch_typed(ape_fk_bank_kernel<float, true>, ape_fk_bank_kernel<double, true>, out_dtype, K, st, p, (const double*)b->bodies.dev, b->S)
                                         : launch_typed(ape_fk_bank_kernel<float, false>, ape_fk_bank_kernel<double, false>, out_dtype, K, st, p, none, 0);
     if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", what, hipGetErrorString(e));
     if (p.desc == nullptr) b->ucount += 1;
@@ -415,6 +486,23 @@ int ape_fk_bank_set_bodies(ape_fk_bank_t* b, const int32_t* streams_host, int32_
     return APE_OK;
 }
 
+// per-stream smoothing lengths (semantics at ape_streams_set_smooths): a cold start of the listed streams
+int ape_fk_bank_set_smooths(ape_fk_bank_t* b, const int32_t* streams_host, int32_t K, const int32_t* smooths_host, void* stream) {
+    if (int rc = ape_smooth_table_check("fk_bank_set_smooths", b, streams_host, K, b ? b->S : 0, smooths_host, b ? b->smooth : 0)) return rc;
+    APE_TRY(hipSetDevice(b->device));
+    const hipStream_t st = (hipStream_t)stream;
+    if (int rc = check_capture(st, "fk_bank_set_smooths")) return rc;
+    APE_TRY(ape_smooth_table_set(b->smooths, b->S, b->smooth, streams_host, K, smooths_host, st));
+    if (!streams_host) return ape_fk_bank_reset(b);
+    return ape_fk_bank_reset_subset(b, streams_host, K);
+}
+
+int ape_fk_bank_get_smooths(ape_fk_bank_t* b, int32_t* out_host) {
+    if (!b || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_get_smooths: NULL argument");
+    ape_smooth_table_get(b->smooths, b->S, b->smooth, out_host);
+    return APE_OK;
+}
+
 int ape_fk_bank_get_bodies(ape_fk_bank_t* b, double* out_host) {
     if (!b || !out_host) return ape_fail(APE_ERR_INVALID_ARG, "fk_bank_get_bodies: NULL argument");
     ape_body_table_get(b->bodies, b->S, b->body, out_host);
@@ -438,6 +526,10 @@ int fk_state_launch(ape_fk_bank* b, const int32_t* streams_host, int32_t K, doub
     APE_TRY(slot_wait);
     for (int j = 0; j < K; ++j) h[j] = fill(j, streams_host[j]);
     APE_TRY(b->stage.send(b->desc, (size_t)K * sizeof(FkDesc), st));
+    if (b->smooths.on())
+        hipLaunchKernelGGL(ape_fk_state_smooths_kernel<IMPORT>, dim3(blocks_for((long long)K * b->smooth * 4)), dim3(FK_BLOCK), 0, st, b->ring, state,
+                           (const FkDesc*)b->desc, (int)K, b->smooth, (const int*)b->smooths.dev);
+    else
     hipLaunchKernelGGL(ape_fk_state_kernel<IMPORT>, dim3(blocks_for((long long)K * b->smooth * 4)), dim3(FK_BLOCK), 0, st, b->ring, state,
                        (const FkDesc*)b->desc, (int)K, b->smooth);
     const hipError_t e = hipGetLastError();
@@ -470,7 +562,7 @@ int ape_fk_bank_export(ape_fk_bank_t* b, const int32_t* streams_host, int32_t K,
     return fk_state_launch<false>(b, streams_host, K, (double*)state_dev, st, "fk_bank_export", [&](int j, int s) {
         const long long c = b->uniform ? b->ucount : b->cnt[s];
         warm_host[j] = c > 0 ? (uint8_t)(APE_STATE_WINDOW_WARM | APE_STATE_STACK_WARM) : (uint8_t)0;
-        return FkDesc{s, (int)(c % b->smooth), c == 0 ? 1 : 0, 0};
+        return FkDesc{s, (int)(c % b->smooth_of(s)), c == 0 ? 1 : 0, 0};
     });
 }
 
@@ -493,7 +585,7 @@ int ape_fk_bank_import(ape_fk_bank_t* b, const ape_stream_state_desc_t* desc, co
                                        [&](int j, int s) { return FkDesc{s, 0, warm(j) ? 0 : 1, 0}; }))
         return rc;
     leave_uniform(b);
-    for (int j = 0; j < K; ++j) b->cnt[streams_host[j]] = warm(j) ? b->smooth : 0;
+    for (int j = 0; j < K; ++j) b->cnt[streams_host[j]] = warm(j) ? b->smooth_of(streams_host[j]) : 0;
     return APE_OK;
 }
 

@@ -132,9 +132,20 @@ __device__ __forceinline__ double spread_single(const double* e0, int c) {
 // order, the wave tree, SPLIT: the chunks in order through sp.part, a buffer of its own beside p.part.  Lane 0 of a quaternion role
 // holds qm the moment it has normalised it.  A parameter of the template and an argument of its own: StreamPostParams and the other
 // forms' object code stay what they were.
-template <typename TMsg, bool SPLIT, bool IDX = false, bool TAB = false, bool SPR = false>
+// SMT (per-stream smoothing lengths): the stream stacks its last sm.smooths[stream] predictions instead of p.smooth -- the
+// S estimators of the reference built with S values of `smooth` (estimator.py:45,112-118).  p.smooth stays the CAPACITY: ring, tail and
+// packed rows keep its strides, the stream lives in ring slots 0 .. k-1, and what lies between its 25 + 6 k n_mc live values and the end
+// of its row (the spread record apart) is written as zeros every frame.  The value is uniform over the workgroup, indexed by the STREAM
+// like the bodies, and read where p.smooth was: the other forms' object code stays what it was.  Lockstep: the slot is sm.count mod k
+// (the predictions since the cold start, 64-bit: n mod k is not uniform over the streams and a count that wraps breaks it for every k
+// that is no power of two); IDX: d[s].pos was taken mod k on the host.  The bodies are the table's when there is one (no TAB x SMT
+// product).  SPLIT: the grid and the ticket stay those of the capacity; a chunk past the stream's rows does no row and arrives with
+// zero partial sums, which change no bit of the sums they are added to (the sums start at +0) -- so a stream of k gives the bits of a
+// uniform bank of k in the one-workgroup form (N <= 64: chunk 0 alone) and in the split form alike.
+template <typename TMsg, bool SPLIT, bool IDX = false, bool TAB = false, bool SPR = false, bool SMT = false>
 __device__ inline void stream_post(const StreamPostParams& p, const int s, const int chunk, const int C, const SubsetDesc* d = nullptr,
-                                   const double* __restrict__ bodies = nullptr, const SpreadArgs sp = SpreadArgs{}) {
+                                   const double* __restrict__ bodies = nullptr, const SpreadArgs sp = SpreadArgs{},
+                                   const SmoothArgs sm = SmoothArgs{}) {
 #pragma clang fp contract(off)
 
     __shared__ double rot[64][3][3];                        // per row of a 64-row chunk: rotated lower-arm bone, upper-arm bone, shoulder origin
@@ -145,14 +156,22 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
     __shared__ int last_s;
     __shared__ double spr_s[SPR ? APE_SPREAD_WIDTH : 1];    // SPR: the record (unused otherwise)
     const int lane = threadIdx.x & 63, role = threadIdx.x >> 6;
-    const int M = p.n_mc, N = p.smooth * M, O = p.O;
+    // (two local macros instead of a variable: the SMT = false instantiations must see the expressions they always saw -- naming the
+    //  length first rescheduled every existing kernel)
+    const int k_tab = SMT ? sm.smooths[IDX ? d[s].stream : s] : 0;          // SMT: the stream's smoothing length (p.smooth is the capacity)
+#define APE_POST_KS (SMT ? k_tab : p.smooth)
+    const int M = p.n_mc, N = APE_POST_KS * M, O = p.O;
+#define APE_POST_NS (SMT ? p.smooth * M : N)                /* rows a tail / packed row has room for */
+    if constexpr (SMT && SPLIT) {
+        if (N == 1 && chunk > 0) return;                    // a single row: chunk 0 copies it, no ticket is taken
+    }
     const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
     const bool full = p.layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS;
     const int nq = hips ? 3 : 2;
     const int qc[3] = {hips ? 9 : 6, hips ? 13 : 10, 17};
     const int c_in[3] = {full ? 3 : 0, full ? 12 : 6, full ? 18 : 12};     // first input column of the role's chain
     const double wgt = 1.0 / (double)N;
-    const double* const body = TAB ? bodies + 9 * (size_t)(IDX ? d[s].stream : s) : p.body;
+    const double* const body = (TAB || (SMT && bodies != nullptr)) ? bodies + 9 * (size_t)(IDX ? d[s].stream : s) : p.body;
     double acc[4] = {0, 0, 0, 0};
     double osum[6] = {0, 0, 0, 0, 0, 0};
     double ss[18] = {};                                     // SPR: the role's spread sums
@@ -182,8 +201,8 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
             j = i / M; k = i - j * M;
             // the newest prediction sits in ring slot `pos`, the oldest one slot further
             // (IDX: read at the point of use, so that the lockstep form's object code stays what it was)
-            fresh = (IDX ? d[s].pcold : p.cold) || j == p.smooth - 1;
-            const int slot = ((IDX ? d[s].pos : p.pos) + 1 + j) % p.smooth;
+            fresh = (IDX ? d[s].pcold : p.cold) || j == APE_POST_KS - 1;
+            const int slot = ((IDX ? d[s].pos : (SMT ? (int)(sm.count % (unsigned long long)k_tab) : p.pos)) + 1 + j) % APE_POST_KS;
             src = fresh ? p.y_new + ((size_t)s * M + k) * O
                         : p.yring + (((size_t)(IDX ? d[s].stream : s) * p.smooth + slot) * M + k) * O;
         }
@@ -217,7 +236,7 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
                 if (i == 0 && act && hips) { e0_s[6] = uo.x; e0_s[7] = uo.y; e0_s[8] = uo.z; }
             }
         } else if (act && fresh) {                          // keep the prediction for the next frames
-            float* dst = p.yring + (((size_t)(IDX ? d[s].stream : s) * p.smooth + ((IDX ? d[s].pcold : p.cold) ? j : (IDX ? d[s].pos : p.pos))) * M + k) * O;
+            float* dst = p.yring + (((size_t)(IDX ? d[s].stream : s) * p.smooth + ((IDX ? d[s].pcold : p.cold) ? j : (IDX ? d[s].pos : (SMT ? (int)(sm.count % (unsigned long long)k_tab) : p.pos)))) * M + k) * O;
 #pragma unroll
             for (int c = 0; c < 20; ++c)
                 if (c < O) dst[c] = src[c];
@@ -260,13 +279,19 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
             }
             if constexpr (SPR) { spread_add_pos(ss, e6); spread_add_pos(ss + 9, e6 + 3); }
             if (p.tail || p.packed) {                       // estimator.py:131-137: est[i, :6] of every row
-                TMsg* t = p.packed ? static_cast<TMsg*>(p.msg) + (size_t)s * (25 + 6 * N) + spr_off + 25 + (size_t)i * 6
-                                   : static_cast<TMsg*>(p.tail) + ((size_t)s * N + i) * 6;
+                TMsg* t = p.packed ? static_cast<TMsg*>(p.msg) + (size_t)s * (25 + 6 * APE_POST_NS) + spr_off + 25 + (size_t)i * 6
+                                   : static_cast<TMsg*>(p.tail) + ((size_t)s * APE_POST_NS + i) * 6;
 #pragma unroll
                 for (int c = 0; c < 6; ++c) t[c] = (TMsg)e6[c];
             }
         }
         __syncthreads();                                    // ... and read: the next chunk may overwrite them
+    }
+    if constexpr (SMT) {                                    // the rest of the fixed-stride row: exact zeros, every frame
+        if ((p.tail || p.packed) && (!SPLIT || chunk == 0)) {
+            TMsg* t = p.packed ? static_cast<TMsg*>(p.msg) + (size_t)s * (25 + 6 * APE_POST_NS) + spr_off + 25 : static_cast<TMsg*>(p.tail) + (size_t)s * APE_POST_NS * 6;
+            for (int c = 6 * N + (int)threadIdx.x; c < 6 * APE_POST_NS; c += 256) t[c] = (TMsg)0;
+        }
     }
     if (N > 1) {
         double a0 = 0, a1 = 0, a2 = 0, a3 = 0;
@@ -346,7 +371,7 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
         if (threadIdx.x >= 64 && threadIdx.x < 64 + APE_SPREAD_WIDTH) {
             const int c = threadIdx.x - 64;
             const double v = N == 1 ? spread_single(e0_s, c) : spr_s[c];
-            TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 25 + 6 * N : 25) + spr_off + (p.packed ? 25 + 6 * N : 25);
+            TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 25 + 6 * APE_POST_NS : 25) + spr_off + (p.packed ? 25 + 6 * APE_POST_NS : 25);
             dst[c] = (TMsg)v;
         }
     }
@@ -361,7 +386,7 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
 #pragma unroll
     for (int c = 0; c < 21; ++c) e0[c] = e0_s[c];
     finish_msg(p.layout, N, out_q, orig_mean, e0, body, m);
-    TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 25 + 6 * N : 25) + spr_off;
+    TMsg* dst = static_cast<TMsg*>(p.msg) + (size_t)s * (p.packed ? 25 + 6 * APE_POST_NS : 25) + spr_off;
 #pragma unroll
     for (int c = 0; c < 25; ++c) dst[c] = (TMsg)m[c];
     }
@@ -370,6 +395,8 @@ __device__ inline void stream_post(const StreamPostParams& p, const int s, const
         __syncthreads();
         if (threadIdx.x == 0) __hip_atomic_store(p.done_out + s, p.done_val, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
+#undef APE_POST_KS
+#undef APE_POST_NS
 }
 
 // The same step for banks WITHOUT stacking (smooth = 1, one sample per stream: the deterministic bank of configs[3]): lane = stream, 64 streams

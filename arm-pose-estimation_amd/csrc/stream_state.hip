@@ -17,7 +17,10 @@ namespace {
 constexpr int ST_BLOCK = 256;
 
 // word w of stream d's record <-> its place in the rings (nullptr: padding, or a cold part)
-__device__ __forceinline__ float* ring_word(const StateParams& p, const StateDesc& d, int w) {
+// k: the stream's smoothing length (a bank with per-stream lengths, DESIGN.md 4.35: the record keeps the capacity's size, the stream's k
+// predictions oldest first, zeros behind them; the ring keeps the capacity's stride and the stream lives in its slots 0 .. k-1)
+template <bool SMT>
+__device__ __forceinline__ float* ring_word(const StateParams& p, const StateDesc& d, int w, const int k) {
     const int nx = p.T * p.I;
     if (w < nx) {
         if (!(d.warm & APE_STATE_WINDOW_WARM)) return nullptr;
@@ -29,9 +32,32 @@ __device__ __forceinline__ float* ring_word(const StateParams& p, const StateDes
     w -= nx;
     if (w >= p.smooth * p.MO || !(d.warm & APE_STATE_STACK_WARM)) return nullptr;
     const int j = w / p.MO, r = w - j * p.MO;
+    if (SMT && j >= k) return nullptr;
     int slot = d.sslot + j;
-    if (slot >= p.smooth) slot -= p.smooth;
+    if (slot >= k) slot -= k;
     return p.yring + ((size_t)d.stream * p.smooth + slot) * p.MO + r;
+}
+
+__device__ __forceinline__ float* ring_word(const StateParams& p, const StateDesc& d, int w) { return ring_word<false>(p, d, w, p.smooth); }
+
+// SMT: the stream's length is smooths[d.stream] (the bank's device table) instead of p.smooth
+template <bool IMPORT>
+__global__ __launch_bounds__(ST_BLOCK) void ape_state_smooths_kernel(const StateParams p, const int* __restrict__ smooths) {
+    const int units = p.words / 4;
+    const long long idx = (long long)blockIdx.x * ST_BLOCK + threadIdx.x;
+    if (idx >= (long long)p.K * units) return;
+    const int j = (int)(idx / units), u = (int)(idx - (long long)j * units);
+    const StateDesc d = p.desc[j];
+    const int k = smooths[d.stream];
+    f32x4 v;
+    if constexpr (IMPORT) v = reinterpret_cast<const f32x4*>(p.state)[idx];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+        float* r = ring_word<true>(p, d, 4 * u + c, k);
+        if constexpr (IMPORT) { if (r) *r = v[c]; }
+        else v[c] = r ? *r : 0.0f;
+    }
+    if constexpr (!IMPORT) reinterpret_cast<f32x4*>(p.state)[idx] = v;
 }
 
 __global__ __launch_bounds__(ST_BLOCK) void ape_state_export_kernel(const StateParams p) {
@@ -76,5 +102,14 @@ hipError_t ape_launch_state_export(const StateParams& p, hipStream_t stream) {
 hipError_t ape_launch_state_import(const StateParams& p, hipStream_t stream) {
     if (p.K < 1) return hipSuccess;
     hipLaunchKernelGGL(ape_state_import_kernel, dim3(blocks_for((long long)p.K * (p.words / 4))), dim3(ST_BLOCK), 0, stream, p);
+    return hipGetLastError();
+}
+
+// ... of a bank with per-stream smoothing lengths (smooths: its device table [S])
+hipError_t ape_launch_state_smooths(const StateParams& p, const int* smooths, bool import, hipStream_t stream) {
+    if (p.K < 1) return hipSuccess;
+    const dim3 grid(blocks_for((long long)p.K * (p.words / 4)));
+    if (import) hipLaunchKernelGGL(ape_state_smooths_kernel<true>, grid, dim3(ST_BLOCK), 0, stream, p, smooths);
+    else hipLaunchKernelGGL(ape_state_smooths_kernel<false>, grid, dim3(ST_BLOCK), 0, stream, p, smooths);
     return hipGetLastError();
 }

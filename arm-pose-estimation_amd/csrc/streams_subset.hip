@@ -132,6 +132,26 @@ hipError_t launch_subset_post_spread(const StreamPostParams& p, const SubsetDesc
     return hipGetLastError();
 }
 
+// ... and of a bank with per-stream smoothing lengths (stream_post_device.h, SMT): the length of entry j is sm.smooths[d[j].stream]
+template <typename TMsg, bool SPR>
+__global__ __launch_bounds__(256) void ape_subset_post_smooths_kernel(const StreamPostParams p, const SubsetDesc* d, const double* bodies,
+                                                                      const SpreadArgs sp, const SmoothArgs sm) {
+    stream_post<TMsg, false, true, false, SPR, true>(p, (int)blockIdx.x, 0, 1, d, bodies, sp, sm);
+}
+template <typename TMsg, bool SPR>
+__global__ __launch_bounds__(256) void ape_subset_post_split_smooths_kernel(const StreamPostParams p, const int chunks, const SubsetDesc* d,
+                                                                            const double* bodies, const SpreadArgs sp, const SmoothArgs sm) {
+    stream_post<TMsg, true, true, false, SPR, true>(p, (int)blockIdx.x / chunks, (int)blockIdx.x % chunks, chunks, d, bodies, sp, sm);
+}
+
+template <typename TMsg, bool SPR>
+hipError_t launch_subset_post_smooths(const StreamPostParams& p, const SubsetDesc* d, const SmoothArgs& sm, const SpreadArgs& sp, int form,
+                                      const double* bodies, hipStream_t stream) {
+    if (form > 1) hipLaunchKernelGGL((ape_subset_post_split_smooths_kernel<TMsg, SPR>), dim3(p.S * form), dim3(256), 0, stream, p, form, d, bodies, sp, sm);
+    else hipLaunchKernelGGL((ape_subset_post_smooths_kernel<TMsg, SPR>), dim3(p.S), dim3(256), 0, stream, p, d, bodies, sp, sm);
+    return hipGetLastError();
+}
+
 hipError_t launch_subset_post_bodies(const StreamPostParams& p, const SubsetDesc* d, const double* bodies, hipStream_t stream) {
     if (p.smooth == 1 && p.n_mc == 1 && p.S >= 8) {
         const int wide = (p.S + 63) / 64;
@@ -196,4 +216,17 @@ hipError_t ape_launch_stream_post_subset(const StreamPostParams& p, const Subset
     if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_subset_post_kernel<float>, dim3(p.S), dim3(256), 0, stream, p, d);
     else hipLaunchKernelGGL(ape_subset_post_kernel<double>, dim3(p.S), dim3(256), 0, stream, p, d);
     return hipGetLastError();
+}
+
+// the table forms over a list (as ape_launch_stream_post_smooths, fk.hip)
+hipError_t ape_launch_stream_post_subset_smooths(const StreamPostParams& p, const SubsetDesc* d, const SmoothArgs& sm, const SpreadArgs* sp, int form,
+                                                 hipStream_t stream, const double* bodies) {
+    if (p.S < 1) return hipSuccess;
+    if (form < 1 || sm.smooths == nullptr) return hipErrorInvalidValue;
+    if (form > 1 && (p.part == nullptr || (sp != nullptr && sp->part == nullptr))) return hipErrorInvalidValue;
+    if (sp != nullptr)
+        return p.msg_dtype == APE_F32 ? launch_subset_post_smooths<float, true>(p, d, sm, *sp, form, bodies, stream)
+                                      : launch_subset_post_smooths<double, true>(p, d, sm, *sp, form, bodies, stream);
+    return p.msg_dtype == APE_F32 ? launch_subset_post_smooths<float, false>(p, d, sm, SpreadArgs{}, form, bodies, stream)
+                                  : launch_subset_post_smooths<double, false>(p, d, sm, SpreadArgs{}, form, bodies, stream);
 }

@@ -129,6 +129,11 @@ SIGNATURES = {
     "ape_fk_bank_get_bodies": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ape_kalman_bank_set_bodies": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "ape_kalman_bank_get_bodies": (C.c_int, [C.c_void_p, C.c_void_p]),
+    # per-stream smoothing lengths: bank, stream list, K, [K] int32 values, HIP stream / bank, [S] int32 out
+    "ape_streams_set_smooths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ape_streams_get_smooths": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "ape_fk_bank_set_smooths": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
+    "ape_fk_bank_get_smooths": (C.c_int, [C.c_void_p, C.c_void_p]),
     "ape_model_set_kernel": (C.c_int, [C.c_void_p, C.c_int32]),
     "ape_model_set_precision": (C.c_int, [C.c_void_p, C.c_int32]),
     "ape_model_check": (C.c_int, [C.c_void_p]),

@@ -108,13 +108,17 @@ EXPORT_DOC = """-> ``(state, warm)``: float32 ``[K, words_per_stream]`` on the d
         ``streams[j]`` (``stream_state.unpack`` gives its time-ordered window and stack), and ``np.uint8 [K]`` warm bits
         (``stream_state.WINDOW_WARM``, ``STACK_WARM``).  Read-only, one launch on the current stream, no synchronisation; a lockstep
         bank stays in lockstep mode.  Bodies are NOT part of the record (``bodies`` / ``set_bodies`` move them), nor is the
-        Monte-Carlo seed or call counter."""
+        Monte-Carlo seed or call counter.  A bank with per-stream smoothing lengths (``set_smooths``, DESIGN.md 4.35) keeps the record
+        size of its capacity: the stack part holds stream s's ``smooths[s]`` predictions oldest first, followed by zeros; the length
+        itself is NOT part of the record."""
 IMPORT_DOC = """the reverse of ``export_state``: the listed streams continue from the given records (from this bank, another
         bank or GPU, a replay, or ``Estimator.get_state``); ``desc`` (default: this bank's own) must equal this bank's
         ``state_desc()``.  A stream whose ``WINDOW_WARM`` bit is clear is cold-started, one with only ``STACK_WARM`` clear keeps the
         window and gets a cold stack.  Puts the bank into per-stream mode like ``frame``; streams not listed stay untouched.  Bodies
         are NOT part of the record: move them with ``set_bodies``.  A pending frame that ``recover`` could still re-issue is dropped
-        from the journal: recover first if its outputs are still wanted."""
+        from the journal: recover first if its outputs are still wanted.  In a bank with per-stream smoothing lengths the record is
+        read with the TARGET slot's length: to move a stream, first ``set_smooths`` the slot to the source's value (a cold start of the
+        slot), then ``import_state`` (which warms it)."""
 
 
 # ---- the Kalman bank's record (C ABI ``ape_kalman_state_desc_t``, DESIGN.md 4.27) -------------------------------------------------------

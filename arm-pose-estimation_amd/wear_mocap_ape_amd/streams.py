@@ -82,6 +82,60 @@ def _get_bodies(bank, entry: str) -> np.ndarray:
     return out
 
 
+def _set_smooths(bank, entry: str, values, streams):
+    """the ``set_smooths`` of the NN and FK banks (C ABI ``ape_*_set_smooths``)"""
+    C = bank._C
+    idx = None if streams is None else bank._indices(streams)
+    K = bank._n if idx is None else int(idx.shape[0])
+    a = np.asarray(values)
+    if a.ndim != 1 or a.shape[0] != K or (a.size and not np.issubdtype(a.dtype, np.integer)):
+        raise UserWarning(f"set_smooths wants {K} integer smoothing lengths, got {values!r}")
+    if a.size and (a.min() < 1 or a.max() > bank._smooth):
+        raise UserWarning(f"smoothing lengths must lie in [1, {bank._smooth}], the smooth the bank was built with")
+    vals = np.ascontiguousarray(a, dtype=np.int32)
+    bank._hip.check(getattr(bank._hip.lib(), entry)(bank._handle, C.c_void_p(idx.ctypes.data) if idx is not None else None, K,
+                                                    C.c_void_p(vals.ctypes.data), bank._stream()), entry)
+
+
+def _get_smooths(bank, entry: str) -> np.ndarray:
+    out = np.empty((bank._n,), dtype=np.int32)
+    bank._hip.check(getattr(bank._hip.lib(), entry)(bank._handle, bank._C.c_void_p(out.ctypes.data)), entry)
+    return out
+
+
+def datagram_lengths_of(smooths, n_mc: int) -> np.ndarray:
+    """int ``[S]``: floats of each stream's datagram -- ``25 + 6 N_s`` with ``N_s = smooths[s] * n_mc`` stacked rows, or 25 where
+    ``N_s == 1`` (the reference appends est[i, :6] only when there is more than one stacked row, estimator.py:131-137).  Pure."""
+    k = np.asarray(smooths)
+    if k.ndim != 1 or (k.size and not np.issubdtype(k.dtype, np.integer)) or int(n_mc) < 1 or (k.size and k.min() < 1):
+        raise UserWarning(f"datagram_lengths wants integer smoothing lengths >= 1 and n_mc >= 1, got {smooths!r}, {n_mc!r}")
+    n = k.astype(np.int64) * int(n_mc)
+    return np.where(n > 1, 25 + 6 * n, 25)
+
+
+def split_datagrams_of(rows, lengths):
+    """rows ``[K, >= max(lengths)]`` (fixed stride: a table bank's datagram rows) -> a list of K views, row j cut to ``lengths[j]``.
+    Pure: numpy arrays and tensors alike."""
+    ln = np.asarray(lengths)
+    if ln.ndim != 1 or (ln.size and not np.issubdtype(ln.dtype, np.integer)):
+        raise UserWarning(f"split_datagrams wants one integer length per row, got {lengths!r}")
+    if getattr(rows, "ndim", None) != 2 or rows.shape[0] != ln.shape[0]:
+        raise UserWarning(f"split_datagrams wants one row per length: {ln.shape[0]} lengths, rows {getattr(rows, 'shape', None)}")
+    if ln.size and (ln.min() < 0 or ln.max() > rows.shape[1]):
+        raise UserWarning(f"datagram lengths must lie in [0, {rows.shape[1]}]")
+    return [rows[j, :int(ln[j])] for j in range(ln.shape[0])]
+
+
+_SET_SMOOTHS_DOC = """Per-stream smoothing lengths (DESIGN.md 4.35): ``values`` K integers in ``[1, smooth]`` -- the constructor's ``smooth``
+        is the bank's CAPACITY --, ``streams`` K distinct indices, or ``None`` for all S streams in order.  From the next frame enqueued on
+        the current stream on, stream s behaves like a reference estimator BUILT with ``smooth = values[s]`` (frames already enqueued keep
+        the old values).  A COLD START of the listed streams, window and stack (the reference fixes ``smooth`` at construction): with a
+        list what ``reset(streams=...)`` does for them, with ``None`` a ``reset()``.  Buffers keep the capacity's shapes: stream s's tail
+        and datagram rows hold ``N_s = values[s] * samples`` live rows followed by exact zeros (``datagram_lengths``, ``split_datagrams``).
+        ``export_state`` / ``import_state`` records keep the capacity's size and do NOT carry the length: to move a stream, first
+        ``set_smooths`` the target slot to the source's value (that cold-starts the slot), then ``import_state`` (that warms it)."""
+
+
 def _host_rows(rows, K: int, width: int) -> np.ndarray:
     """the rows of a ``frame_host`` call: a contiguous float32 host array ``[K, width]``"""
     if isinstance(rows, torch.Tensor):
@@ -209,6 +263,25 @@ class StreamBank:
 
     bodies = property(lambda self: _get_bodies(self, "ape_streams_get_bodies"),
                       doc="float64 [S, 9] mirror of the per-stream bodies; S copies of the model's body before the first set_bodies")
+
+    def set_smooths(self, values, streams=None):
+        _set_smooths(self, "ape_streams_set_smooths", values, streams)
+    set_smooths.__doc__ = _SET_SMOOTHS_DOC
+
+    smooths = property(lambda self: _get_smooths(self, "ape_streams_get_smooths"),
+                       doc="int32 [S] mirror of the per-stream smoothing lengths; S copies of the bank's ``smooth`` before the first set_smooths")
+
+    def datagram_lengths(self) -> np.ndarray:
+        """int ``[S]``: the floats of each stream's datagram, ``25 + 6 N_s`` (``N_s = smooths[s] * samples``), or 25 where ``N_s == 1``:
+        what the reference sends for an estimator built with that ``smooth``"""
+        return datagram_lengths_of(self.smooths, self._n_mc)
+
+    def split_datagrams(self, rows, streams=None):
+        """datagram rows of ``step_datagrams`` (``streams=None``: row s is stream s) or of ``frame`` / ``frame_host`` with ``datagrams``
+        (row j is stream ``streams[j]``), with or without the spread record behind them -> a list of per-stream float32 views, each cut
+        to its stream's ``datagram_lengths()`` entry: byte for byte the reference's payload for that stream"""
+        ln = self.datagram_lengths()
+        return split_datagrams_of(rows, ln if streams is None else ln[self._indices(streams)])
 
     def _indices(self, streams) -> np.ndarray:
         a = np.asarray(streams)
@@ -466,6 +539,24 @@ class FkStreamBank:
 
     bodies = property(lambda self: _get_bodies(self, "ape_fk_bank_get_bodies"),
                       doc="float64 [S, 9] mirror of the per-stream bodies; S copies of ``body_measurements`` before the first set_bodies")
+
+    def set_smooths(self, values, streams=None):
+        _set_smooths(self, "ape_fk_bank_set_smooths", values, streams)
+    set_smooths.__doc__ = _SET_SMOOTHS_DOC
+
+    smooths = property(lambda self: _get_smooths(self, "ape_fk_bank_get_smooths"),
+                       doc="int32 [S] mirror of the per-stream smoothing lengths; S copies of the bank's ``smooth`` before the first set_smooths")
+
+    def datagram_lengths(self) -> np.ndarray:
+        """int ``[S]``: ``25 + 6 smooths[s]``, or 25 where ``smooths[s] == 1`` -- the floats the reference sends for an estimator built
+        with that ``smooth``.  The bank's own frames return the 25-value messages only."""
+        return datagram_lengths_of(self.smooths, 1)
+
+    def split_datagrams(self, rows, streams=None):
+        """rows ``[K, w]``, row j for stream ``streams[j]`` (``None``: row s for stream s) -> a list of views cut to each stream's
+        ``datagram_lengths()`` entry"""
+        ln = self.datagram_lengths()
+        return split_datagrams_of(rows, ln if streams is None else ln[self._indices(streams)])
 
     def _stream(self):
         return self._C.c_void_p(torch.cuda.current_stream(self._device).cuda_stream)

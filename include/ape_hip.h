@@ -547,6 +547,45 @@ int ape_replay_resume(ape_model_t* model, int32_t kind, const float* rows_dev, i
                       const double* bodies_host, const void* state_in_dev, const uint8_t* warm_in_host, void* state_out_dev,
                       uint8_t* warm_out_host, uint64_t sample_row_base);
 
+/* ---- per-stream smoothing lengths (additive in ABI 7) -----------------------------------------------------------------
+ * replaces: the `smooth` every reference Estimator is built with (estimator.py:45, max(1, smooth)), the stack of that many predictions
+ * (estimator.py:112-118) and the tail of est[i, :6] of every stacked row (estimator.py:131-137) -- S estimators built with S values of
+ * `smooth` in one bank, on ONE regressor launch: stream s of the bank behaves like an estimator built with smooth = smooths[s].
+ * CAPACITY: the smooth a bank was created with is its capacity `cap`.  Rings, tails and packed rows keep the sizes and strides they
+ * have (yring [S,cap,n_mc,O], FK ring [S,cap,8]); every limit (cap <= 64, cap * n_mc <= 4096) is stated on cap.
+ * A bank that was never given smooths runs exactly what it ran.  The first ape_*_set_smooths call gives the bank a device table of S
+ * int32 values, initialised to cap, plus a host mirror, and overwrites the listed rows; the table survives ape_streams_reset and
+ * ape_streams_set_mc.
+ *   streams_host   K DISTINCT stream indices (host memory), or NULL: all S streams in order, K == S
+ *   smooths_host   int32 [K] (host memory), each in [1, cap]; free for reuse on return
+ * COLD START: the reference fixes smooth at construction, so a change has no defined transition -- the call cold-starts the listed
+ * streams, window and stack: with a list what ape_streams_reset_subset / ape_fk_bank_reset_subset do for them (the NN bank's mode rules
+ * apply), with NULL an ape_streams_reset / ape_fk_bank_reset (every stream cold, the NN bank in lockstep).  K = 0 changes no row and still
+ * switches the bank to its table.  Ordered on `stream`: frames enqueued before the call see the old values, frames after it the new.
+ * EVERY FRAME of a table bank (lockstep step, ape_streams_frame_host, subset frames on device and host, the FK bank's four frame
+ * entries, and the frames ape_model_recover issues again -- a re-issued step goes through ape_streams_step, a re-issued subset frame
+ * through its post-filter launch, and both read the bank's table), with k = smooths[s], M = n_mc, N_s = k * M:
+ *   stream s uses ring slots 0 .. k-1 of its cap slots; its newest prediction goes to slot n_s mod k (n_s: predictions since its cold
+ *   start), its first prediction after a cold start to all k slots; stack row i is sample i % M of the prediction k - 1 - i / M frames
+ *   back, weight 1 / N_s, flip against row 0, the summation order of a uniform bank of k; N_s == 1 takes the single-row copy path.
+ *   tail_dev and APE_FLAG_PACKED_MSG rows keep the stride of cap: row s holds 25 + 6 N_s live values (tail: N_s rows of 6), everything
+ *   between them and the end of the row is written as exact zeros every frame; with APE_FLAG_SPREAD the record stays in the last
+ *   APE_SPREAD_WIDTH columns of the fixed-stride row.  As APE_F32 the first 25 + 6 N_s floats of a packed row are byte for byte the
+ *   payload the reference sends for an estimator built with smooth = k.
+ * Post-filter form of a table bank (ape_streams_last_post_form): 1, or -- where the bank holds the split form's workspaces -- the chunk
+ * count of cap * n_mc; chunks past a stream's rows arrive with zero partial sums.  A bank of cap == 1 accepts the call and keeps its forms.
+ * STATE HAND-OVER: records keep words_per_stream of cap and ape_*_state_desc's smooth stays cap.  Export of stream s: the stack part holds
+ * its k predictions oldest first, followed by zeros.  Import into stream t: the record is read with smooths[t] -- the records do not carry
+ * k.  A caller who moves a stream FIRST gives the target slot the source's value (set_smooths cold-starts the slot) and THEN imports
+ * (the import warms it).
+ * ape_*_get_smooths: the host mirror [S]; S copies of cap before the first set.
+ * Refused (non-zero, ape_last_error) before anything is written: NULL bank or values, K < 0 or K > S, a NULL list with K != S, an index
+ * outside [0, S), a duplicate index, a value outside [1, cap], a capturing stream. */
+int ape_streams_set_smooths(ape_streams_t* bank, const int32_t* streams_host, int32_t K, const int32_t* smooths_host, void* stream);
+int ape_streams_get_smooths(ape_streams_t* bank, int32_t* out_host /* [S] */);
+int ape_fk_bank_set_smooths(ape_fk_bank_t* bank, const int32_t* streams_host, int32_t K, const int32_t* smooths_host, void* stream);
+int ape_fk_bank_get_smooths(ape_fk_bank_t* bank, int32_t* out_host);
+
 /* ---- Monte-Carlo spread record (additive in ABI 7) --------------------------------------------------------------------
  * replaces: nothing.  The reference has NO counterpart of this record: the only form in which it lets the sample spread out is the raw
  * cloud, est[i, :6] of every stacked row appended to the message (estimator.py:131-137; APE_FLAG_PACKED_MSG / tail_dev here).  The
