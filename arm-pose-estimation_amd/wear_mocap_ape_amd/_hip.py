@@ -214,6 +214,13 @@ SIGNATURES["ape_frame_sums"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_
                                           C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
 SIGNATURES["ape_rotate_rows"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                            C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p])
+# mocap truth on each frame's clock.  The clock: dt + stride + dtype, flags, F, starts_host, R, times, HIP stream.  The
+# rows: layout, truth + kind + dtype, Ft, truth_starts_host, truth_times, times, F, starts_host, R, shift_host, max_gap, bodies_host,
+# n_bodies, out + dtype, HIP stream
+SIGNATURES["ape_frame_times"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
+SIGNATURES["ape_resample_truth"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                              C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                              C.c_void_p])
 
 _lib = None
 

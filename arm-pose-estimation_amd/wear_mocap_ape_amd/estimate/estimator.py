@@ -661,6 +661,16 @@ class Estimator:
         bodies = self._body_measurements if bonemaps is None else bonemaps
         return score.align_frame(self._layout, out, truth, lags, mode, weights, truth_kind, spread, starts, skip, bodies)
 
+    def truth_on_frames(self, rows, truth, truth_times, truth_starts=None, starts=None, shifts=None, max_gap: float = 0.0,
+                        truth_kind="targets", bonemaps=None, big_endian: bool = False):
+        """``score.truth_on_frames`` with this estimator's layout and body: the mocap ``truth`` (device ``[Ft, O]`` de-normalised targets,
+        or est rows with ``truth_kind="est"``) with its stamps ``truth_times`` resampled onto the clock that the raw ``rows``' ``sw_dt``
+        column states, less ``shifts``.  Returns float64 est rows ``[F, 21 | 14]`` on the device, for
+        ``score_recording(..., truth_kind="est")``.  ``bonemaps``: as in ``score_recording``."""
+        from wear_mocap_ape_amd import score
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        return score.truth_on_frames(self._layout, rows, truth, truth_times, truth_starts, starts, shifts, max_gap, truth_kind, bodies, big_endian)
+
     # ---- post-filter sweep (DESIGN.md 4.33; the reference has no counterpart) ----
     def repost(self, y, configs, starts=None, bonemaps=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
         """``score.post_sweep`` with this estimator's model and body: ``y`` device float32 ``[F, M, O]`` as

@@ -358,3 +358,8 @@ class WatchPhonePocketKalman(Estimator):
         """``Estimator.align_recording`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
         return super().align_recording(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind, lags,
                                        mode, weights)
+
+    def truth_on_frames(self, rows, truth, truth_times, truth_starts=None, starts=None, shifts=None, max_gap: float = 0.0,
+                        truth_kind="targets", bonemaps=None, big_endian: bool = False):
+        """``Estimator.truth_on_frames`` for raw ``[F, 28]`` pocket rows"""
+        return super().truth_on_frames(rows, truth, truth_times, truth_starts, starts, shifts, max_gap, truth_kind, bonemaps, big_endian)

@@ -145,3 +145,8 @@ class WatchPhoneUarm(Estimator):
                         weights=(1, 1, 1, 0, 0)):
         """``Estimator.align_recording`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
         return super().align_recording(out, truth, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind, lags, mode, weights)
+
+    def truth_on_frames(self, rows, truth, truth_times, truth_starts=None, starts=None, shifts=None, max_gap: float = 0.0,
+                        truth_kind="targets", bonemaps=None, big_endian: bool = False):
+        """``Estimator.truth_on_frames`` for raw ``[F, 55]`` watch-and-phone rows"""
+        return super().truth_on_frames(rows, truth, truth_times, truth_starts, starts, shifts, max_gap, truth_kind, bonemaps, big_endian)

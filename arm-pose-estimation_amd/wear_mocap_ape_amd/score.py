@@ -17,7 +17,12 @@ builds the list, ``score_configs`` scores every configuration over a sweep of la
 A recording whose wearer stood a few degrees off during the calibration pose is turned as a whole against the truth: ``frame_sums``
 takes, for every lag of a sweep, the sums the least-squares rotation is read off (``ape_frame_sums``), ``best_frame``
 finds lag and rotation together on the host, ``rotate_rows`` applies it (``ape_rotate_rows``), ``align_frame`` does all of it and scores
-what remains; ``frame_sums_numpy`` and ``rotate_rows_numpy`` are the host statements."""
+what remains; ``frame_sums_numpy`` and ``rotate_rows_numpy`` are the host statements.
+
+Watch frames sit on a jittered clock and a mocap system runs at its own rate: ``frame_times`` builds a recording's clock from its
+``sw_dt`` column, ``resample_truth`` gives est-kind truth rows at each frame's time less a shift (``ape_frame_times``,
+``ape_resample_truth``), ``truth_on_frames`` does both from raw rows, ``align(refine=True)`` scores at ``best_lag``'s
+fractional lag; ``frame_times_numpy`` and ``resample_truth_numpy`` are the host statements."""
 import ctypes as C
 
 import numpy as np
@@ -167,7 +172,6 @@ def _f64(t):
 def _prepared(layout, msg, truth, truth_kind, spread, starts, bodies, out_dtype):
     """the checked views and host arrays of one scoring call: (msg view, its stride, spread view | None, its stride, truth, starts int32
     ``[R]``, bodies float64 ``[1 | R, 9]``)"""
-    from wear_mocap_ape_amd.data_types.bone_map import bodies_from, body9_from_bonemap
     if truth_kind not in TRUTH_KINDS:
         raise UserWarning(f"truth_kind must be one of {sorted(TRUTH_KINDS)}, got {truth_kind!r}")
     if layout not in _hip.EST_WIDTH:
@@ -189,15 +193,7 @@ def _prepared(layout, msg, truth, truth_kind, spread, starts, bodies, out_dtype)
     td = truth.contiguous()
     st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
     R = int(st.shape[0])
-    if bodies is None:
-        body = body9_from_bonemap(None)[np.newaxis, :]
-    elif isinstance(bodies, np.ndarray) and bodies.size == 9:
-        body = np.ascontiguousarray(bodies.reshape(1, 9), dtype=np.float64)
-    elif not isinstance(bodies, np.ndarray) and not hasattr(bodies, "__len__"):
-        body = body9_from_bonemap(bodies)[np.newaxis, :]              # one bonemap-like object: that body for every recording
-    else:
-        body = bodies_from(bodies, R, "score_rows bodies")
-    return md, ms, sd, ss, td, st, body
+    return md, ms, sd, ss, td, st, _body_rows(bodies, R, "score_rows bodies")
 
 
 def score_rows(layout: int, msg, truth, truth_kind: str = "targets", spread=None, starts=None, skip: int = 0, bodies=None,
@@ -330,13 +326,22 @@ def best_lag(acc, lags, error: str = "hand_pos", rec_lags=None) -> list:
 
 
 def align(layout: int, msg, truth, lags, error: str = "hand_pos", truth_kind: str = "targets", spread=None, starts=None, skip: int = 0,
-          bodies=None, rec_lags=None, out_dtype=torch.float64):
+          bodies=None, rec_lags=None, out_dtype=torch.float64, refine: bool = False):
     """Find each recording's lag and score at it: a ``score_lags`` sweep (accumulators only), ``best_lag`` on it (this waits for the
     device), then one more pass with ``lags=(0, 0)`` and the lags found as offsets (0 for a recording with an empty support).
     Returns ``(best, score [F, 7], acc [R, 25])``: ``best_lag``'s list, and the per-frame rows and accumulators at every recording's own
-    lag, as ``score_rows`` would return them for aligned rows."""
+    lag, as ``score_rows`` would return them for aligned rows.
+    ``refine=True``: the second pass is at ``best_lag``'s fractional ``refined`` lag instead: ``resample_truth`` on the index clock with
+    each recording's ``refined`` as its shift (0 for an empty support), then ``score_rows`` against the resampled est rows -- a frame whose
+    shifted time leaves its recording's truth is not scored (``acc[:, 16]``)."""
     _, sweep = score_lags(layout, msg, truth, lags, truth_kind, spread, starts, skip, bodies, rec_lags, out_dtype, per_frame=False)
     best = best_lag(sweep, lags, error, rec_lags)
+    if refine:
+        shifts = [0.0 if b["lag"] is None else b["refined"] for b in best]
+        frames = int(truth.shape[0])
+        moved = resample_truth(layout, truth, truth_kind, starts, None, None, frames, starts, shifts, 0.0, bodies, check_times=False)
+        score, acc = score_rows(layout, msg, moved, "est", spread, starts, skip, bodies, out_dtype)
+        return best, score, acc
     found = [0 if b["lag"] is None else b["lag"] for b in best]
     score, acc = score_lags(layout, msg, truth, (0, 0), truth_kind, spread, starts, skip, bodies, found, out_dtype, per_frame=True)
     return best, score[:, 0], acc[:, 0]
@@ -733,3 +738,229 @@ def align_frame(layout: int, msg, truth, lags, mode: str = "yaw", weights=(1, 1,
     out, rec = turned if spread is not None else (turned, None)
     score, acc = score_lags(layout, out, truth, (0, 0), truth_kind, rec, starts, skip, bodies, rec_lags, per_frame=True)
     return score[:, 0], acc[:, 0], found
+
+
+# ---- mocap truth on each frame's clock (ape_frame_times, ape_resample_truth) -------------------------------------------------
+# Every scorer above pairs message row f with truth row f - l for an integer l and expects one truth row per frame.  ``frame_times``
+# builds a recording's clock from its sw_dt column, ``resample_truth`` produces est-kind truth rows at each frame's time (less a shift
+# per recording) from truth on a clock of its own; a row it cannot produce is all NaN, which the scorers count as not scorable.
+def _recording_starts(starts) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
+
+
+def frame_times_numpy(dt, starts=None) -> np.ndarray:
+    """The host statement of ``frame_times``: float64 ``[F]``, per recording ``t[s] = 0`` and ``t[f] = t[f - 1] + float64(dt[f])`` (a
+    ``np.cumsum`` whose first term is 0: the first row's ``dt`` points before the recording)."""
+    d = np.asarray(dt).reshape(-1).astype(np.float64)
+    st = _recording_starts(starts).astype(np.int64)
+    out = np.empty(d.shape[0])
+    with np.errstate(all="ignore"):
+        for a, b in zip(st, np.r_[st[1:], d.shape[0]]):
+            seg = d[a:b].copy()
+            seg[0] = 0.0
+            out[a:b] = np.cumsum(seg)
+    return out
+
+
+def frame_times(dt, starts=None, big_endian: bool = False):
+    """Each recording's clock from its ``sw_dt`` column (``ape_frame_times``): ``dt`` a 1-D float32 or float64 device tensor or a
+    strided column view (``rows[:, 0]`` of raw ``[F, 55 | 28]`` rows goes in without a copy), ``starts`` the recordings' first frames,
+    ``big_endian``: the float32 values are UDP payload bytes as received.  Returns float64 ``[F]`` on the device: 0 at a recording's
+    first frame, then the running sum of the following ``dt`` (a non-finite ``dt`` spoils the rest of its own recording only).  The
+    same inputs give the same bits.  The call does not wait for the device."""
+    if not isinstance(dt, torch.Tensor) or not dt.is_cuda or dt.dim() != 1 or dt.shape[0] < 1 or dt.dtype not in (torch.float32, torch.float64):
+        raise UserWarning("dt: a 1-D float32 or float64 device tensor [F >= 1] (a column view of raw rows is fine)")
+    if big_endian and dt.dtype != torch.float32:
+        raise UserWarning("big_endian: the rows are float32 payloads")
+    if dt.shape[0] > 1 and dt.stride(0) < 1:
+        dt = dt.contiguous()
+    F, stride, dev = int(dt.shape[0]), max(int(dt.stride(0)), 1), dt.device
+    st = _recording_starts(starts)
+    with torch.cuda.device(dev):
+        times = torch.empty((F,), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_frame_times(C.c_void_p(dt.data_ptr()), stride, _f64(dt.dtype), _hip.PARSE_BIG_ENDIAN if big_endian else 0, F,
+                                              C.c_void_p(st.ctypes.data), int(st.shape[0]), C.c_void_p(times.data_ptr()), stream),
+                   "ape_frame_times")
+    return times
+
+
+def _slerp(a, b, w):
+    """the quaternion between ``a`` and ``b [n, 4]`` at weights ``w [n]``, the operations of csrc/resample.hip in their order: both
+    normalised, ``b`` flipped where ``a . b < 0.0``, ``theta = 2 asin(min(1, |a - s b| / 2))``, the chord below 1e-6 rad and the arc
+    ``(sin((1 - w) theta) a + sin(w theta) s b) / sin(theta)`` otherwise, normalised again"""
+    def norm(v):
+        return np.sqrt(((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2]) + v[:, 3] * v[:, 3])
+
+    a, b, w = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64), np.asarray(w, dtype=np.float64)[:, None]
+    with np.errstate(all="ignore"):
+        a, b = a / norm(a)[:, None], b / norm(b)[:, None]
+        dot = ((a[:, 0] * b[:, 0] + a[:, 1] * b[:, 1]) + a[:, 2] * b[:, 2]) + a[:, 3] * b[:, 3]
+        b = np.where(dot < 0.0, -1.0, 1.0)[:, None] * b
+        theta = (2.0 * np.arcsin(np.minimum(norm(a - b) / 2.0, 1.0)))[:, None]
+        chord = a + w * (b - a)
+        arc = (np.sin((1.0 - w) * theta) * a + np.sin(w * theta) * b) / np.sin(theta)
+        q = np.where(theta < 1e-6, chord, arc)
+        return q / norm(q)[:, None]
+
+
+def resample_truth_numpy(layout: int, truth_est, truth_starts=None, truth_times=None, times=None, frames=None, starts=None, shifts=None,
+                         max_gap: float = 0.0) -> np.ndarray:
+    """The host statement of ``resample_truth`` for est-kind truth ``[Ft, 21 | 14]``: float64 ``[F, 21 | 14]`` by the seven rules of
+    include/ape_hip.h in their order -- a non-finite query, no truth row at or before it, an exact hit (the row itself), past the last
+    sample, a gap above ``max_gap``, a non-finite value in either neighbour, else positions ``a + w (b - a)`` and quaternions by
+    ``_slerp``.  Clocks, recordings and shifts as ``resample_truth`` takes them (host arrays)."""
+    if layout not in _hip.EST_WIDTH:
+        raise UserWarning(f"layout {layout} has no pose to resample")
+    t = np.asarray(truth_est, dtype=np.float64)
+    W = _hip.EST_WIDTH[layout]
+    if t.ndim != 2 or t.shape[1] != W:
+        raise UserWarning(f"truth_est: expected [Ft,{W}], got {tuple(t.shape)}")
+    hips = layout != _hip.LAYOUT_ORI_CAL_LARM_UARM
+    Ft = t.shape[0]
+    tts = None if truth_times is None else np.asarray(truth_times, dtype=np.float64).reshape(-1)
+    tqs = None if times is None else np.asarray(times, dtype=np.float64).reshape(-1)
+    if tqs is None and frames is None:
+        raise UserWarning("frames: the number of output frames, where times is None")
+    F = int(frames) if tqs is None else tqs.shape[0]
+    st, tst = _recording_starts(starts).astype(np.int64), _recording_starts(truth_starts).astype(np.int64)
+    R = st.shape[0]
+    if tst.shape[0] != R:
+        raise UserWarning(f"truth_starts: {tst.shape[0]} recordings of truth for {R} of frames")
+    sh = np.zeros(R) if shifts is None else np.broadcast_to(np.asarray(shifts, dtype=np.float64).reshape(-1), (R,))
+    npos = 9 if hips else 6
+    out = np.full((F, W), np.nan)
+    with np.errstate(all="ignore"):
+        for r in range(R):
+            s, e = int(st[r]), int(st[r + 1]) if r + 1 < R else F
+            ts, te = int(tst[r]), int(tst[r + 1]) if r + 1 < R else Ft
+            n = te - ts
+            tt = np.arange(n, dtype=np.float64) if tts is None else tts[ts:te]
+            u = (np.arange(e - s, dtype=np.float64) if tqs is None else tqs[s:e]) - sh[r]
+            rows = t[ts:te]
+            fin = np.isfinite(u)
+            i = np.searchsorted(tt, np.where(fin, u, 0.0), side="right") - 1          # the last row with tt <= u: of equal stamps the last
+            has = fin & (i >= 0)
+            ic = np.clip(i, 0, n - 1)
+            hit = has & (u == tt[ic])
+            seg = out[s:e]
+            seg[hit] = rows[ic[hit]]
+            i1 = np.clip(ic + 1, 0, n - 1)
+            gap = tt[i1] - tt[ic]
+            mid = has & ~hit & (i < n - 1)
+            if max_gap > 0.0:
+                mid &= ~(gap > max_gap)
+            mid &= np.isfinite(rows[ic]).all(axis=1) & np.isfinite(rows[i1]).all(axis=1)
+            a, b = rows[ic[mid]], rows[i1[mid]]
+            w = (u[mid] - tt[ic[mid]]) / gap[mid]
+            res = np.empty((a.shape[0], W))
+            res[:, :npos] = a[:, :npos] + w[:, None] * (b[:, :npos] - a[:, :npos])
+            for c in range(npos, W, 4):
+                res[:, c:c + 4] = _slerp(a[:, c:c + 4], b[:, c:c + 4], w)
+            seg[mid] = res
+    return out
+
+
+def _body_rows(bodies, R: int, what: str) -> np.ndarray:
+    """float64 ``[1 | R, 9]`` of ``score_rows``'s ``bodies`` argument"""
+    from wear_mocap_ape_amd.data_types.bone_map import bodies_from, body9_from_bonemap
+    if bodies is None:
+        return body9_from_bonemap(None)[np.newaxis, :]
+    if isinstance(bodies, np.ndarray) and bodies.size == 9:
+        return np.ascontiguousarray(bodies.reshape(1, 9), dtype=np.float64)
+    if not isinstance(bodies, np.ndarray) and not hasattr(bodies, "__len__"):
+        return body9_from_bonemap(bodies)[np.newaxis, :]              # one bonemap-like object: that body for every recording
+    return bodies_from(bodies, R, what)
+
+
+def _clock(t, n: int, dev, what: str):
+    if not isinstance(t, torch.Tensor) or t.device != dev or t.dim() != 1 or t.shape[0] != n or not t.dtype.is_floating_point:
+        raise UserWarning(f"{what}: a floating-point device tensor [{n}] on {dev}")
+    return t.to(torch.float64).contiguous()
+
+
+def resample_truth(layout: int, truth, truth_kind: str = "est", truth_starts=None, truth_times=None, times=None, frames=None, starts=None,
+                   shifts=None, max_gap: float = 0.0, bodies=None, out_dtype=torch.float64, check_times: bool = True):
+    """Truth rows at each frame's time (``ape_resample_truth``).  ``truth``: device ``[Ft, 21 | 14]`` est rows (``truth_kind="est"``) or
+    ``[Ft, O]`` de-normalised NN targets (``"targets"``, converted as ``score_rows`` converts them, with ``bodies``), float32 or
+    float64, on a clock of its own: ``truth_times`` device float64 ``[Ft]`` (None: the index clock, row ``i`` of a recording at time
+    ``i``), ``truth_starts`` the recordings' first truth rows.  ``times``: device float64 ``[F]``, the frames' clock (``frame_times``;
+    None: the index clock, with ``frames`` giving ``F``); ``starts`` the recordings' first frames, as many as ``truth_starts``.
+    ``shifts``: one value or ``[R]``, frame ``f`` is asked at ``times[f] - shifts[r]`` -- positive: the estimate is late, ``score_lags``'s
+    sign; in frames on two index clocks (``best_lag``'s ``refined``), else in the clocks' unit.  ``max_gap > 0``: two truth samples
+    further apart are not bridged.  Returns device ``[F, 21 | 14]`` est rows of ``out_dtype`` for ``score_rows(..., truth_kind="est")``
+    and the other scorers: the truth row itself on an exact hit, positions interpolated linearly and quaternions along the arc between
+    two samples, all NaN where there is none (before the first or past the last sample, a dropout, a non-finite neighbour or time).
+    ``check_times=True`` verifies on the device that the truth times are finite and non-decreasing inside every recording and raises
+    ``UserWarning`` if not: THIS WAITS FOR THE DEVICE.  With ``check_times=False`` (or without ``truth_times``) the call does not wait;
+    unsorted times then give rows from somewhere inside the recording, never a read outside it."""
+    if truth_kind not in TRUTH_KINDS:
+        raise UserWarning(f"truth_kind must be one of {sorted(TRUTH_KINDS)}, got {truth_kind!r}")
+    if layout not in _hip.EST_WIDTH:
+        raise UserWarning(f"layout {layout} has no pose to resample")
+    if out_dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+    tw = (_hip.NUM_TARGETS if truth_kind == "targets" else _hip.EST_WIDTH)[layout]
+    if not isinstance(truth, torch.Tensor) or not truth.is_cuda or truth.dtype not in (torch.float32, torch.float64) or truth.dim() != 2 \
+            or truth.shape[0] < 1 or truth.shape[1] != tw:
+        raise UserWarning(f"truth: a float32 or float64 device tensor [Ft >= 1, {tw}]")
+    td, dev = truth.contiguous(), truth.device
+    Ft = int(td.shape[0])
+    tst, st = _recording_starts(truth_starts), _recording_starts(starts)
+    R = int(st.shape[0])
+    if tst.shape[0] != R:
+        raise UserWarning(f"truth_starts: {tst.shape[0]} recordings of truth for {R} of frames")
+    if times is None:
+        if frames is None:
+            raise UserWarning("frames: the number of output frames, where times is None")
+        F, tq = int(frames), None
+    else:
+        if frames is not None and int(frames) != int(times.shape[0]):
+            raise UserWarning(f"frames={frames} for {int(times.shape[0])} times")
+        F = int(times.shape[0])
+        tq = _clock(times, F, dev, "times")
+    tt = None if truth_times is None else _clock(truth_times, Ft, dev, "truth_times")
+    sh = None
+    if shifts is not None:
+        sh = np.asarray(shifts, dtype=np.float64).reshape(-1)
+        if sh.shape[0] not in (1, R):
+            raise UserWarning(f"shifts: one value or one per recording [{R}], got {sh.shape[0]}")
+        sh = np.ascontiguousarray(np.broadcast_to(sh, (R,)))
+    body = _body_rows(bodies, R, "resample_truth bodies")
+    with torch.cuda.device(dev):
+        if check_times and tt is not None:
+            ok = torch.isfinite(tt).all()
+            if Ft > 1:
+                rising = tt[1:] >= tt[:-1]
+                if R > 1 and int(tst.max()) < Ft and int(tst[1:].min()) >= 1:
+                    rising[torch.as_tensor(tst[1:].astype(np.int64) - 1, device=dev)] = True      # across a boundary anything goes
+                ok = ok & rising.all()
+            if not bool(ok):
+                raise UserWarning("truth_times: not finite, or decreasing inside a recording")
+        out = torch.empty((F, _hip.EST_WIDTH[layout]), dtype=out_dtype, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_resample_truth(int(layout), C.c_void_p(td.data_ptr()), TRUTH_KINDS[truth_kind], _f64(td.dtype), Ft,
+                                                 C.c_void_p(tst.ctypes.data), C.c_void_p(tt.data_ptr()) if tt is not None else None,
+                                                 C.c_void_p(tq.data_ptr()) if tq is not None else None, F, C.c_void_p(st.ctypes.data), R,
+                                                 C.c_void_p(sh.ctypes.data) if sh is not None else None, float(max_gap),
+                                                 C.c_void_p(body.ctypes.data), int(body.shape[0]), C.c_void_p(out.data_ptr()),
+                                                 _f64(out_dtype), stream), "ape_resample_truth")
+    return out
+
+
+def truth_on_frames(layout: int, rows, truth, truth_times, truth_starts=None, starts=None, shifts=None, max_gap: float = 0.0,
+                    truth_kind: str = "targets", bodies=None, big_endian: bool = False):
+    """The truth of a recording session on its IMU frames.  ``rows``: raw messages ``[F, 55 | 28]``, float32, whose column 0 is
+    ``sw_dt`` -- a device tensor, or a host array that is copied to ``truth``'s device; ``big_endian``: UDP payloads as received.
+    ``truth`` and ``truth_times``: the mocap rows and their stamps on the device, in the unit of ``sw_dt`` (seconds); both clocks start
+    at 0 with each recording (``frame_times``); ``shifts``: what the estimate is late by.  ``frame_times(rows[:, 0])`` and then
+    ``resample_truth``; returns float64 est rows ``[F, 21 | 14]`` on the device.  Checks the truth times, so it waits for the device."""
+    if not isinstance(truth, torch.Tensor) or not truth.is_cuda:
+        raise UserWarning("truth: a device tensor")
+    if isinstance(rows, np.ndarray):
+        rows = torch.from_numpy(np.ascontiguousarray(rows)).to(truth.device)
+    if not isinstance(rows, torch.Tensor) or rows.dim() != 2 or rows.shape[1] not in (55, 28) or rows.dtype != torch.float32 \
+            or rows.device != truth.device:
+        raise UserWarning("rows: float32 raw messages [F, 55 | 28] on truth's device (or a host array)")
+    times = frame_times(rows[:, 0], starts, big_endian)
+    return resample_truth(layout, truth, truth_kind, truth_starts, truth_times, times, None, starts, shifts, max_gap, bodies)

@@ -1031,6 +1031,61 @@ int ape_rotate_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, con
                     const double* quats_host /* [n_quats, 4], n_quats 1 or R, [w,x,y,z] */, int32_t n_quats,
                     void* out_dev /* [F, 25] or, with spread_dev, [F, 25 + 21] */, int32_t out_dtype, void* stream);
 
+/* ---- mocap truth on each frame's clock (additive in ABI 7) -----------------------------------------------------------------
+ * replaces: nothing; the reference has no counterpart.  Every scorer above pairs message row f with truth row f - l for an integer l
+ * and expects one truth row per IMU frame.  A watch's frames sit on a jittered clock (column 0 of every raw row is sw_dt, the seconds
+ * since the previous message) and a mocap system runs at its own rate with its own stamps and dropouts; and the lag best_lag refines
+ * to a fraction of a frame cannot be applied by an integer pairing.  ape_frame_times builds a recording's clock on the device,
+ * ape_resample_truth produces est-kind truth rows at each frame's time, which every scorer accepts; a row it cannot produce is all NaN,
+ * which the scorers count as "could not be scored".  float64 with separate roundings for a * b + c; no floating-point atomics; no
+ * workgroup waits for another inside a launch.
+ * ape_frame_times.  dt_dev: one value per frame, dt_stride (>= 1) elements apart, of dt_dtype APE_F32 or APE_F64: column 0 of raw
+ *   [F, 55 | 28] rows goes in without a copy (dt_stride 55 | 28).  flags: 0 or APE_PARSE_BIG_ENDIAN (APE_F32 only: the rows are UDP
+ *   payloads as received).  For a recording [s_r, e_r) (seg_starts_host as in ape_score_rows): times_dev[s_r] = 0 and times_dev[f] = the
+ *   sum of (double)dt[i] over s_r < i <= f; the first row's dt points before the recording and is not read into any sum.  A segmented
+ *   inclusive scan in float64 whose association is fixed by F and the starts: |t[f] - exact| <= (f - s_r) 2^-53 sum|dt|, and the same
+ *   inputs give the same bits.  A non-finite dt makes the times non-finite from its frame to the end of ITS recording and never reaches
+ *   into the next one.  Three launches (per-tile aggregates, one workgroup scanning them, per-tile scan plus carry-in); one for F <= 1024.
+ *   Refused with APE_ERR_INVALID_ARG on the host before anything is written: NULL dt_dev / seg_starts_host / times_dev, F < 1, R < 1,
+ *   bad starts, dt_stride < 1, an unknown dtype or flag, the big-endian flag with APE_F64, times_dev equal to dt_dev, a capturing stream.
+ * ape_resample_truth.  Recording r is the frames [s_r, e_r) of the estimate (seg_starts_host, F) and the rows [ts_r, te_r) of the truth
+ *   (truth_starts_host, Ft), in the same order on both sides.  Frame clock tq(f) = times_dev[f], or with NULL the index clock
+ *   (double)(f - s_r); truth clock tt(i) = truth_times_dev[i], or with NULL (double)(i - ts_r).  The query is u = tq(f) - shift_r
+ *   (shift_host[r]; 0 with NULL): a positive shift means the estimate is late, the sign convention of ape_score_lags; with both clocks
+ *   NULL the shift is a lag in frames, otherwise it is in the clocks' unit.  Truth times are assumed finite and non-decreasing inside a
+ *   recording (the host cannot see them); whatever they hold, the search stays inside [ts_r, te_r) and nothing outside the buffers is
+ *   read.  Frame times need not be monotonic.
+ *   Conversion.  APE_TRUTH_TARGETS: a truth row [O] is first converted exactly as ape_score_rows converts it (the float64 forward
+ *   kinematics with the recording's body, eigenvector-refined quaternions), est columns [6:9] being the hips quaternion applied to the
+ *   body's shoulder origin, as ape_fk writes them.  APE_TRUTH_EST: the row [21 | 14] is taken as given.  bodies_host f64 [n_bodies, 9],
+ *   n_bodies 1 or R, must be valid for either kind, as for ape_score_rows (it is staged with the other host arrays); its values
+ *   are used for APE_TRUTH_TARGETS only.
+ *   Output row f, out_dev [F, 21 | 14] of out_dtype, by these rules in this order:
+ *     1. u is not finite: all NaN.
+ *     2. i = the last row of [ts_r, te_r) with tt(i) <= u (binary search; of equal stamps the last); none: all NaN.
+ *     3. u == tt(i): the converted row i itself, no arithmetic (est kind, float64 in and out: the bits of the input row, NaN included).
+ *     4. i == te_r - 1 (past the last sample): all NaN.
+ *     5. max_gap > 0 and tt(i+1) - tt(i) > max_gap: all NaN (a mocap dropout is not bridged).
+ *     6. any value of the converted rows i or i + 1 is non-finite: all NaN.
+ *     7. w = (u - tt(i)) / (tt(i+1) - tt(i)); position columns (hand, elbow, shoulder origin) a + w (b - a); each quaternion (lower arm,
+ *        upper arm, and hips where the layout has them): a and b normalised, s = -1 where a . b < 0.0 else +1 (the flip rule of
+ *        average_quaternions), theta = 2 asin(min(1, |a - s b| / 2)) (<= pi / 2 after the flip); theta < 1e-6: q = a + w (s b - a);
+ *        otherwise q = (sin((1 - w) theta) a + sin(w theta) s b) / sin(theta); then q / |q|.
+ *   An APE_F32 output is the float64 row rounded once.  One lane per output frame, one launch.
+ * Both need no model handle, run on the current HIP device and do not wait; the host arrays have been consumed when they return;
+ * staging slots as ape_score_rows keeps them (this file's own: the first call of a size allocates, later ones do not).
+ * ape_resample_truth refuses with APE_ERR_INVALID_ARG on the host, before anything is written: everything ape_score_rows refuses about
+ * layout, kind, dtypes, starts (both lists, each against its own row count) and bodies; Ft < 1; a NaN max_gap; a non-finite shift;
+ * out_dev equal to an input; a capturing stream. */
+int ape_frame_times(const void* dt_dev, int32_t dt_stride, int32_t dt_dtype, uint32_t flags, int32_t F,
+                    const int32_t* seg_starts_host, int32_t R, double* times_dev /* f64 [F] */, void* stream);
+int ape_resample_truth(int32_t layout, const void* truth_dev, int32_t truth_kind, int32_t truth_dtype, int32_t Ft,
+                       const int32_t* truth_starts_host /* [R] */, const double* truth_times_dev /* f64 [Ft] or NULL */,
+                       const double* times_dev /* f64 [F] or NULL */, int32_t F, const int32_t* seg_starts_host /* [R] */, int32_t R,
+                       const double* shift_host /* f64 [R] or NULL */, double max_gap,
+                       const double* bodies_host, int32_t n_bodies,
+                       void* out_dev /* [F, 21 | 14] of out_dtype */, int32_t out_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
