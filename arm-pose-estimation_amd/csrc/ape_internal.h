@@ -1,4 +1,4 @@
-// Internal declarations shared by the C-ABI (ape_api.hip) and the gfx950 kernels.
+// Internal declarations shared by the C-ABI (ape_api.hip, api_*.hip) and the gfx950 kernels.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

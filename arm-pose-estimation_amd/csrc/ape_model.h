@@ -1,4 +1,4 @@
-// The model and stream-bank handles behind the C ABI: shared by ape_api.hip and by the test-hooks translation unit
+// The model and stream-bank handles behind the C ABI: shared by the host files (ape_api.hip, api_*.hip) and by the test-hooks translation unit
 // (ape_debug.hip, linked into lib/diag/libape_hip_testhooks.so only).
 #pragma once
 #include <string>

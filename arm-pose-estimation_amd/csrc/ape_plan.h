@@ -1,6 +1,6 @@
 // Which kernels serve an LSTM call or a Monte-Carlo bank: the whole decision as pure host arithmetic (no HIP here: tests/tools/plan_sweep.cpp
-// compiles this header alone with the host compiler).  ape_api.hip builds an ApeCaps per model (ape_caps), asks plan_lstm / plan_bank and
-// launches what they answer; ape_debug_plan*, ape_debug_bank_* and ape_lstm_kernel_name answer from the same functions.
+// compiles this header alone with the host compiler).  ape_api.hip builds an ApeCaps per model (ape_caps); the host files ask plan_lstm / plan_bank and
+// launch what they answer; ape_debug_plan*, ape_debug_bank_* and ape_lstm_kernel_name answer from the same functions.
 // A new kernel form: a capability bit in ApeCaps, a route here, a case in lstm_forward_impl's launch switch.
 #pragma once
 #include <cstdlib>

@@ -1,4 +1,4 @@
-// Host-side plumbing shared by the stream banks (ape_api.hip, fk_streams.hip, kalman_bank.hip) and score.hip: the
+// Host-side plumbing shared by the stream banks (api_streams.hip, api_subset.hip, fk_streams.hip, kalman_bank.hip) and score.hip: the
 // argument checks every bank entry repeats, the pinned descriptor ring of the staged frames and hand-overs, coherent pinned memory, and
 // the completion words of a host frame.  Inline host functions only, no device code; errors go through ape_fail.
 #pragma once
@@ -104,6 +104,20 @@ inline hipError_t ape_pinned_zeroed(T** p, size_t bytes) {
     if (*p) return hipSuccess;
     const hipError_t e = hipHostMalloc((void**)p, bytes, APE_PINNED);
     if (e == hipSuccess) memset((void*)*p, 0, bytes);
+    return e;
+}
+
+// a coherent block of at least `need` bytes: kept while it is large enough, else freed and allocated anew (contents are not carried over)
+// (hidden: an inline function the compiler keeps out of line would otherwise join the library's exported symbols)
+__attribute__((visibility("hidden"))) inline hipError_t ape_pinned_grow(void** p, size_t* cap, size_t need) {
+    if (need <= *cap) return hipSuccess;
+    if (*p) {
+        const hipError_t e = hipHostFree(*p);
+        if (e != hipSuccess) return e;
+        *p = nullptr; *cap = 0;
+    }
+    const hipError_t e = hipHostMalloc(p, need, APE_PINNED);
+    if (e == hipSuccess) *cap = need;
     return e;
 }
 

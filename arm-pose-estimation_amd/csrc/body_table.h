@@ -1,4 +1,4 @@
-// Per-stream body measurements of a bank: the host side shared by the three banks (ape_api.hip, fk_streams.hip,
+// Per-stream body measurements of a bank: the host side shared by the three banks (api_streams.hip, fk_streams.hip,
 // kalman_bank.hip).  Replaces, for S estimators at once, Estimator._body_measurements (reference estimate/estimator.py:57-68): every
 // reference Estimator is built with its own bonemap, a bank keeps one row of nine float64 values per stream.
 //

@@ -394,7 +394,7 @@ hipError_t ape_launch_stream_post(const StreamPostParams& p, hipStream_t stream,
     }
     const int grid = p.S;                                  // one workgroup (four role waves per row group) per stream
     const int chunks = ape_stream_post_chunks(p.smooth * p.n_mc);
-    if (p.part != nullptr && chunks > 1) {                 // (ape_api.hip hands the workspace over when the bank is small enough)
+    if (p.part != nullptr && chunks > 1) {                 // (api_streams.hip hands the workspace over when the bank is small enough)
         if (p.msg_dtype == APE_F32) hipLaunchKernelGGL(ape_stream_post_split_kernel<float>, dim3(grid * chunks), dim3(256), 0, stream, p, chunks);
         else hipLaunchKernelGGL(ape_stream_post_split_kernel<double>, dim3(grid * chunks), dim3(256), 0, stream, p, chunks);
         return hipGetLastError();

@@ -200,7 +200,7 @@ __global__ __launch_bounds__(256 * RT, 3 - RT) void ape_lstm_cluster16(const Clu
     };
     fetch_x(0);
 
-    // ---- weights: registers for the whole launch; host layout of the first generation (ape_api.hip, wcl):
+    // ---- weights: registers for the whole launch; host layout of the first generation (weight_pack.h, wcl):
     //      [member][wave][register / 4][lane][4], register 4 q + j of lane (row c = lane & 15 = unit * 4 + gate, k-group g) =
     //      [W_ih | W_hh][gate * H + member * 16 + wave * 4 + unit][16 q + 4 g + j]
     float w0[NW0];

@@ -30,7 +30,7 @@
 //     lstm_cluster_f16v2.hip, whose exchange this is.
 //   * split form (end): every product but layer 0's input columns runs on v_mfma_f32_32x32x16_f16 as
 //     W_hi h_hi + W_hi h_lo + W_lo h_hi of power-of-two scaled f16 hi / lo pairs (each product exact in the f32 accumulator), 96 cycles
-//     per K = 16 instead of 512; weights in the split image of ape_api.hip (pack_c32_split), h exchanged in the split layout.
+//     per K = 16 instead of 512; weights in the split image of weight_pack.h (pack_c32_split), h exchanged in the split layout.
 // Eval mode, last-step output (what the estimators' batched path and the benchmark use); dropout, all-steps output and
 // other shapes stay on the first-generation kernels.
 #include <type_traits>
@@ -94,7 +94,7 @@ __device__ __forceinline__ void span32(f32x16& acc, const float* __restrict__ sr
 }
 
 // NS K = 16 slices of h columns in the split form: acc += W_hi h_hi + W_hi h_lo + W_lo h_hi (each f16 x f16 product exact in the f32
-// accumulator).  Weights: groups w[g0 + 2 s] (hi) / w[g0 + 2 s + 1] (lo) in the A-fragment order (ape_api.hip, pack_c32_split).
+// accumulator).  Weights: groups w[g0 + 2 s] (hi) / w[g0 + 2 s + 1] (lo) in the A-fragment order (weight_pack.h, pack_c32_split).
 // Activations: the split exchange layout [block of 8 units][hi, lo][window 32][8 units as f16] (1 KiB per block); slice s = blocks
 // 2 s, 2 s + 1, lane (n, hh) reads block 2 s + hh -- `src` = this lane's hi fragment of slice 0, hi / lo one ds_read_b128 each
 // (conflict-free: 16 consecutive windows per lane group), fetched two slices ahead.  `mid(q)` runs with q = 2 s behind the second

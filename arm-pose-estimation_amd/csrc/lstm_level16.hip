@@ -222,7 +222,7 @@ __global__ __launch_bounds__(512, 1) void ape_lstm_level16(const ClusterParams p
     const unsigned seq = __hip_atomic_load(p.seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 0xFFFFFu;
 
     // ---- weights: registers for the whole launch (both agents hold the member's slices); host layout of the first generation
-    //      (ape_api.hip, wcl): [member][wave][register / 4][lane][4], register 4 q + j of lane (row c = lane & 15 = unit * 4 + gate,
+    //      (weight_pack.h, wcl): [member][wave][register / 4][lane][4], register 4 q + j of lane (row c = lane & 15 = unit * 4 + gate,
     //      k-group g) = [W_ih | W_hh][gate * H + member * 16 + wave * 4 + unit][16 q + 4 g + j]
     float w0[NW0];
     float wu[L - 1][NWU];

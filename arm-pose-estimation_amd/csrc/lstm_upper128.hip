@@ -156,7 +156,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper128(const Upper128Params
     if (tid == 0)
         __hip_atomic_store(xcc_words + cluster * GH + member, 0x10u | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
-    // ---- weights: 2 x 128 registers per lane in the accumulator file, for the whole launch.  Host layout (ape_api.hip, wup128):
+    // ---- weights: 2 x 128 registers per lane in the accumulator file, for the whole launch.  Host layout (weight_pack.h, wup128):
     //      per layer [member 4][wave 4][register / 4][lane][4]; register 4 kb + j of lane (column m = lane & 31 = gate * 8 + unit, half hh)
     //      = [W_ih | W_hh][gate * H + member * 32 + wave * 8 + unit][8 kb + 4 hh + j]
     float w[2 * NWL];

@@ -153,7 +153,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper32(const UpperParams p) 
     if (tid == 0)
         __hip_atomic_store(xcc_words + cluster * GH + member, 0x10u | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
-    // ---- weights: 256 registers per lane in the accumulator file, for the whole launch.  Host layout (ape_api.hip, wcl32):
+    // ---- weights: 256 registers per lane in the accumulator file, for the whole launch.  Host layout (weight_pack.h, wcl32):
     //      [member][wave][register / 4][lane][4]; register 4 kb + j of lane (column m = lane & 31 = gate * 8 + unit, half hh)
     //      = [W_ih | W_hh][gate * H + member * 32 + wave * 8 + unit][8 kb + 4 hh + j]
     float w[NW];

@@ -1,4 +1,4 @@
-// Per-stream smoothing lengths of a bank: the host side shared by the NN bank (ape_api.hip) and the forward-kinematics
+// Per-stream smoothing lengths of a bank: the host side shared by the NN bank (api_streams.hip) and the forward-kinematics
 // bank (fk_streams.hip).  Replaces, for S estimators at once, the `smooth` every reference Estimator is built with (estimate/estimator.py:45,
 // max(1, smooth); the stack of :112-118 holds that many predictions): a bank keeps one int32 per stream.
 //
