@@ -165,6 +165,26 @@ __device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 r
 #ifndef C32_QPD
 #define C32_QPD 0
 #endif
+// long windows, steady state (the sections that carry layer 0's input span of the next step, `XS` in the kernel): C32_QFP = blocks into a layer-0
+// section's recurrent span at which the flag owed for layer 1's publish store goes up; C32_QPX / C32_QJX = layer 1's look at the next section's
+// flags and its judge; C32_XS = 0 builds those sections without the relocated span, for A/B runs
+// (swept on MI355X, 1024 x 64, profiles/r09_cluster32_xspan.md: the look BEHIND the x staging of block 33 -- hipcc's own `vmcnt` waits in front of
+//  the staging otherwise sit out the look's round trip -- and its judge a round trip, 21 blocks, further on)
+#ifndef C32_XS
+#define C32_XS 1
+#endif
+#ifndef C32_QFP
+#define C32_QFP 12
+#endif
+#ifndef C32_QPX
+#define C32_QPX 33
+#endif
+#ifndef C32_QJX
+#define C32_QJX 54
+#endif
+#if defined(APE_C32_COUNTS) && defined(APE_C32_WAITS)
+#error "APE_C32_COUNTS and APE_C32_WAITS write the same words of dbg_wg: one build, one of them"
+#endif
 template <int H, int L, int KX, bool ENDS, int BXU>
 __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams p) {
     constexpr int UPW = 8;                  // hidden units per wave (x 4 gates = the 32 columns of its tile)
@@ -193,9 +213,10 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* hb0 = smem;                      // [2 parity][HL]  h of layer 0, step parity (read by layer 0's recurrence AND layer 1's input)
     float* hb1 = hb0 + 2 * HL;              // [HL]           h of layer 1
-    float* xin = hb1 + HL;                  // [MR][SX]
-    f32x4* bias_s = reinterpret_cast<f32x4*>(xin + MR * SX);     // [wave 4][L][4 gates][lane 64]: the accumulators' start values
-    unsigned* look_s = reinterpret_cast<unsigned*>(bias_s + 4 * L * 4 * 64);   // [wave 4][64]: landing zones of the flag looks (async_look.h)
+    float* xin = hb1 + HL;                  // [2 parity][MR][SX]  x of a step, by step parity in the long-window instantiations (ENDS: buffer 0 only)
+    f32x4* bias_s = reinterpret_cast<f32x4*>(xin + 2 * MR * SX); // [wave 4][L][4 gates][lane 64]: the accumulators' start values
+    f32x4* park_s = bias_s + 4 * L * 4 * 64;                     // [wave 4][4 gates][lane 64]: layer 0's sums behind the input span of the NEXT step (thread-private)
+    unsigned* look_s = reinterpret_cast<unsigned*>(park_s + 4 * 4 * 64);       // [wave 4][64]: landing zones of the flag looks (async_look.h)
     int* ctl = reinterpret_cast<int*>(look_s + 4 * 64);          // [0] abort, [1] class ticket, [2] last-out, [3] same XCD
 
     // control words (all zero between launches): [8 class tickets, one per 64-byte line][n_wg XCD words]
@@ -255,16 +276,21 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     // (opaque from here on: with more section forms in the kernel hipcc preferred to RE-LOAD the three constants inside the staging hook
     //  of every layer-1 section -- a global-memory round trip in the MFMA stream, 450 -> 950 cycles per section by the stamps)
     asm volatile("" : "+v"(x_mean), "+v"(x_std), "+v"(x_rstd));
-    auto stage_x = [&]() {
+    // (the fetched step goes to the buffer of its parity `t`; ENDS: always buffer 0)
+    auto stage_x = [&](int t) {
+        float* const dst = xin + (ENDS ? 0 : (t & 1) * (MR * SX));
 #pragma unroll
         for (int e = 0; e < NE; ++e) {
             const double d = (double)xr[e] - x_mean;
             const double q0 = d * x_rstd;
             const double rr = fma(-q0, x_std, d);
             const double q1 = fma(rr, x_rstd, q0);
-            xin[(xrow + e * (256 / KX)) * SX + xk] = (float)((rr == rr) ? q1 : q0);
+            dst[(xrow + e * (256 / KX)) * SX + xk] = (float)((rr == rr) ? q1 : q0);
         }
     };
+    // XA: how many steps further ahead than the short-window instantiation x is staged.  Long windows: a phase stages x of step ph + 2 and
+    // fetches step ph + 3, because a steady-state layer-1 section runs layer 0's input span of the NEXT step (below); the prologue stages steps 0 and 1.
+    constexpr int XA = ENDS ? 0 : 1;
     fetch_x(0);
 
     // ---- weights: registers, for the whole launch.  Host layout [member][wave][register / 4][lane][4]: register 4 kb + j of
@@ -326,7 +352,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     const unsigned hb0_lds = (unsigned)reinterpret_cast<unsigned long long>(hb0);     // LDS byte addresses
     const unsigned hb1_lds = (unsigned)reinterpret_cast<unsigned long long>(hb1);
 
-    stage_x();
+    stage_x(0);
     if (T > 1) fetch_x(1);
 
     // ---- do all members of this cluster really share an XCD? ------------------------------------------------------
@@ -454,6 +480,11 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     //      for with nothing to do (round 4: ~3 us of the 89 us launch at T = 6).  Phase 0's layer-1 section is idle anyway; the loop
     //      below starts at phase 1.
     if constexpr (!ENDS) {
+        // (x_1, whose loads went out in front of the rendezvous above, into its own buffer; its first reader sits behind phase 0's barriers)
+        if (1 < T) {
+            stage_x(1);
+            if (2 < T) fetch_x(2);
+        }
         load_weights();
     } else {
         f32x16 acc;
@@ -475,7 +506,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         load_weights();
         bar();                                                    // every wave is through with x_0 in LDS
         if (1 < T) {
-            stage_x();
+            stage_x(1);
             if (2 < T) fetch_x(2);
         }
     }
@@ -491,12 +522,28 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     // barrier the store itself is waited for and its flag goes up.
     const int P = T + L - 1;                 // phases 0 .. P-1 compute; "phase" P: the final gather for the head
     bool prefetched = false;
+    // the layer-1 section in front has run layer 0's input span for this step and parked the sixteen sums in park_s (long windows, steady state)
+    bool parked = false;
 #ifdef APE_C32_COUNTS
     // light counters of a product-like build (tests/tools/counts_c32.py): per workgroup (wave 0), per layer -- sections whose gather took the
     // blocking form / was prefetched, shader clocks between a section's entry and the exit of its top barrier
     unsigned lc_block[2] = {0u, 0u}, lc_go[2] = {0u, 0u}, lc_n[2] = {0u, 0u};
     unsigned long long lc_top[2] = {0ull, 0ull}, lc_t0 = 0ull;
     const unsigned long long lc_start = __builtin_amdgcn_s_memtime();
+#endif
+#ifdef APE_C32_WAITS
+    // a switch of its own (tests/tools/waits_c32.py; the record takes the place of APE_C32_COUNTS' in dbg_wg, so not both): shader clocks wave 0
+    // spends in the waits of a steady-state phase, s_memtime around the wait only -- [0] layer 1's `look_landed()` for the own look, [1] the
+    // same for the next section's look, [2] layer 1's wait + barrier between the spans, [3] layer 0's entry -> behind the top barrier;
+    // lw_n: steady-state layer-1 / layer-0 sections, layer-1 sections whose own gather took the blocking form
+    unsigned long long lw[4] = {0ull, 0ull, 0ull, 0ull}, lw_t0 = 0ull;
+    unsigned lw_n[3] = {0u, 0u, 0u};
+    const unsigned long long lw_start = __builtin_amdgcn_s_memtime();
+#define C32_WAIT_T0() do { if (ST) lw_t0 = __builtin_amdgcn_s_memtime(); } while (0)
+#define C32_WAIT_T1(k) do { if (ST) lw[k] += __builtin_amdgcn_s_memtime() - lw_t0; } while (0)
+#else
+#define C32_WAIT_T0() do {} while (0)
+#define C32_WAIT_T1(k) do {} while (0)
 #endif
 #ifdef APE_CLUSTER_STAMPS
     unsigned long long dg_block[2] = {0, 0}, dg_go[2] = {0, 0};      // diagnostic counters per layer (cluster 0, member 0)
@@ -523,6 +570,12 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     //           barrier; layer-0 sections no longer carry a look or a gather.  Outside the steady state (the last step of a short
     //           window sits behind an idle, i.e. empty, layer-0 section) a second look follows at block QF + 13; a wave whose looks
     //           failed blocks in front of the barrier.
+    // and, in the long-window instantiations, ONE more form of the steady-state MODE 3 section (`XS` below; DESIGN.md 4.10, end):
+    //   the section starts with the look at its own layer's flags and, under that look's round trip, layer 0's INPUT span of the next step
+    //   (x W_ih: the one product of a phase that waits for no hand-over); the sums are parked in LDS, the layer-0 section behind starts from
+    //   them and goes straight into its recurrent span.  One `vmcnt(0)` behind the relocated span serves the flag owed for layer 0's publish
+    //   store and the judge of the own look; the own gather's eight pieces go out in blocks 0 .. 7 of the input span.  x is staged one step
+    //   further ahead than in the other forms, in two buffers by step parity.
     auto section = [&](auto steady_tag, auto layer_tag, auto mode_tag, const int ph) -> bool {
         constexpr bool ST = decltype(steady_tag)::value;          // steady state: 1 <= t <= T - 2 for both layers
         constexpr int l = decltype(layer_tag)::value;
@@ -539,6 +592,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
 #ifdef APE_C32_COUNTS
         lc_t0 = __builtin_amdgcn_s_memtime();
 #endif
+        if constexpr (MODE != 3) C32_WAIT_T0();
         // ---- S0: this layer's slices of its last step into LDS ------------------------------------------------------------
         if (MODE == 3) {                                          // (the slices come in under the input span: nothing to wait for here)
         } else if (need) {
@@ -570,6 +624,9 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
 #ifdef APE_C32_COUNTS
         if (ST && MODE != 3) { lc_top[l] += __builtin_amdgcn_s_memtime() - lc_t0; lc_n[l] += 1u; }
 #endif
+#ifdef APE_C32_WAITS
+        if constexpr (MODE != 3) { C32_WAIT_T1(3); if (ST) lw_n[1] += 1u; }
+#endif
         const int abort_word = (MODE == 3) ? 0 : ctl[0];          // (MODE 3 looks behind its own barrier, between the spans)
         C32_TL(8 + 2 * (2 * ph + l));
         // the next section: layer ln on step tn = its phase - ln; the slice set it is missing is h^{ln}_{tn-1}, epoch tn
@@ -588,7 +645,16 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         constexpr int NBL = (l == 0) ? BXU + BH : 2 * BH;
         // (positions swept on MI355X, 1024 x 64: QF 1 / 2 / 3 / 10 / 16 -> 826 / 833 / 819 / 828 / 858 us -- earlier stalls on the store's
         //  acknowledgement, later the peers' look finds nothing; look 12 blocks ahead of the judge instead of 4 -> 840: the flags are not up yet)
-        constexpr int QF = C32_QF, QP = (MODE == 1) ? 16 : NBL / 2 - 2 + C32_QPD, QJ = (MODE == 1) ? 20 : NBL / 2 + 2 + C32_QPD;
+        // XS (long windows, steady state, layer 1): the section starts with layer 0's input span of the NEXT step (see `active` below); the flag owed
+        // goes up behind that span, not at block QF, and the look for the next section / its judge sit at C32_QPX / C32_QJX.  The layer-0 sections
+        // between two such sections start in their recurrent span, 768 cycles closer to the publish store in front: their QF is BXU + C32_QFP.
+        // (C32_XS = 0, for A/B runs: the section keeps its own look at block QF + 1 and layer 0 its input span; C32_QPX / C32_QJX hold all the same)
+        constexpr bool LW = ST && !ENDS && MODE == 3;
+        constexpr bool XS = LW && C32_XS != 0;
+        // (outside the steady state one layer-0 section starts from the park as well, the one behind the last such section: its QF must lie in the recurrent span)
+        constexpr int QF = (!ENDS && l == 0 && C32_XS != 0) ? (ST ? BXU + C32_QFP : (C32_QF > BXU ? C32_QF : BXU)) : C32_QF;
+        constexpr int QP = (MODE == 1) ? 16 : LW ? C32_QPX : NBL / 2 - 2 + C32_QPD, QJ = (MODE == 1) ? 20 : LW ? C32_QJX : NBL / 2 + 2 + C32_QPD;
+        static_assert(!LW || (QP >= 0 && QP < QJ - 1 && QJ + NDMA <= 2 * BH), "the look, its judge and the eight pieces fit the section");
         bool staged = false;
 #ifdef APE_CLUSTER_STAMPS
         unsigned long long hk0 = 0, hk_free = 0;
@@ -604,7 +670,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             if (ST && q == QF + 2) hk_free = now();
             if (ST && q == QF + 10) dgh[l][5] += now() - hk_free;
 #endif
-            if (q == QF) {
+            if (!XS && q == QF) {
                 HK_BEGIN();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 raise_pending();
@@ -613,17 +679,23 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             // x of the next layer-0 step: registers -> LDS (layer 0's readers of xin finished before this section's barrier), and
             // the fetch of the step after it EARLY in the section: issued at its end the loads were the youngest entries but one of
             // the memory queue, and the counted wait at the top of the next section sat out their whole latency (13 us per launch)
-            if (l == L - 1 && q == ((MODE == 3) ? BH + 1 : QF + 1) && (ST || ph + 1 < T)) {
+            // (long windows, XA = 1: one step further ahead, into the buffer of that step's parity -- its last reader, of step ph, is either
+            //  layer 0's section of this phase or the layer-1 section of the phase in front, both behind this section's barrier)
+            if (l == L - 1 && q == ((MODE == 3) ? BH + 1 : QF + 1) && (ST || ph + 1 + XA < T)) {
                 HK_BEGIN();
-                stage_x();
-                if (ST || ph + 2 < T) fetch_x(ph + 2);
+                stage_x(ph + 1 + XA);
+                // (no branch around the loads inside a steady-state section: the last one fetches "step T", which wraps to a step of the ring --
+                //  memory of this cluster's rows -- and is never staged)
+                if (ST || ph + 2 + XA < T) fetch_x(ph + 2 + XA);
                 staged = true;
                 HK_END(1);
             }
             if constexpr (l == L - 1) {
                 if (q == QP) look_issue(look_lds, look_voff, fl_desc, fl_off + (unsigned)(ln * NFL * sizeof(unsigned)));     // (always: no branch around it)
                 if (q == QJ - 1) {                                // (the ds_read's latency passes under the next k-block)
+                    C32_WAIT_T0();
                     look_landed();
+                    C32_WAIT_T1(1);
                     peek = *look_mine;
                 }
                 if (q == QJ) {
@@ -641,28 +713,69 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         float hnew[4] = {0.0f, 0.0f, 0.0f, 0.0f};
         if (active) {
             // ---- stacked-gate product: one dependent chain of 32x32x2 MFMAs ---------------------------------------------------
+            if constexpr (XS) {
+                // ---- layer 0's input span of step ph + 1 (x_{t+2} W_ih: the one product of a phase that waits for no hand-over), under the
+                //      round trip of the look at the own layer's flags.  The sixteen sums wait in this thread's slot of park_s; layer 0's next
+                //      section starts from them instead of from its bias, the sums in the same order.  Only one accumulator is live at a time.
+                look_issue(look_lds, look_voff, fl_desc, fl_off + (unsigned)(l * NFL * sizeof(unsigned)));
+                f32x16 ax;
+#pragma unroll
+                for (int gate = 0; gate < 4; ++gate) {
+                    const f32x4 bv = bias_s[((wave * L + 0) * 4 + gate) * 64 + lane];
+                    ax[4 * gate] = bv[0]; ax[4 * gate + 1] = bv[1]; ax[4 * gate + 2] = bv[2]; ax[4 * gate + 3] = bv[3];
+                }
+                span32<BXU, false, 4 * BXU>(ax, xin + ((ph + 1) & 1) * (MR * SX) + n * SX + hh * 4, 8, w0, 0, [&](int) {});
+                mfma_drain(ax);
+#pragma unroll
+                for (int gate = 0; gate < 4; ++gate)
+                    park_s[(wave * 4 + gate) * 64 + lane] = f32x4{ax[4 * gate], ax[4 * gate + 1], ax[4 * gate + 2], ax[4 * gate + 3]};
+                parked = true;
+            }
+            // the accumulators' start values: the bias, or (layer 0 behind such a section) the parked sums of this step's input span
+            bool from_park = false;
+            if constexpr (l == 0 && !ENDS) {
+                from_park = parked;
+                parked = false;
+            }
+            const f32x4* const start_s = from_park ? park_s + wave * 4 * 64 + lane : bias_s + (wave * L + l) * 4 * 64 + lane;
             f32x16 acc;
 #pragma unroll
             for (int gate = 0; gate < 4; ++gate) {
-                const f32x4 bv = bias_s[((wave * L + l) * 4 + gate) * 64 + lane];
+                const f32x4 bv = start_s[gate * 64];
                 acc[4 * gate] = bv[0]; acc[4 * gate + 1] = bv[1]; acc[4 * gate + 2] = bv[2]; acc[4 * gate + 3] = bv[3];
             }
             const int frag = hh * 2 * MR * 4 + n * 4;             // this lane's hi fragment of slice 0: block hh, window n
             if constexpr (l == 0) {
-                span32<BXU, false, 4 * BXU>(acc, xin + n * SX + hh * 4, 8, w0, 0, [&](int q) { mid(q); });
+                if (!from_park) span32<BXU, false, 4 * BXU>(acc, xin + (ENDS ? 0 : (t & 1) * (MR * SX)) + n * SX + hh * 4, 8, w0, 0, [&](int q) { mid(q); });
                 if (ST || t > 0) span16<BH / 2, false, NW0 / 4 - BX>(acc, hb0 + ((t - 1) & 1) * HL + frag, w0h, 0, [&](int q) { mid(BXU + q); });
             } else if constexpr (MODE == 3) {
                 // input span: the common hooks (flag owed at QF, the look for the NEXT section at QP) + the look at the OWN layer's flags at
                 // QO, the judge four blocks on, the gather behind it; outside the steady state a second look twelve blocks after the first
                 constexpr int QO = QF + 1, QO2 = QO + 12;
-                static_assert(QO2 + 4 + NDMA <= QP && QP < BH, "the own gather's hooks sit in front of the look for the next section");
+                static_assert(XS || (QO2 + 4 + NDMA <= QP && (LW || QP < BH)), "the own gather's hooks sit in front of the look for the next section");
                 unsigned pk = (unsigned)t;
                 bool got1 = false, got2 = false;
+                if constexpr (XS) {
+                    // one wait for both: layer 0's publish store has drained (its flag goes up) and the own look has landed, a relocated span
+                    // behind its issue; the eight pieces go out in the first blocks and have the rest of the span to land in
+                    C32_WAIT_T0();
+                    look_landed();
+                    C32_WAIT_T1(0);
+                    raise_pending();
+                    pk = *look_mine;
+                    got1 = __all((int)(pk >= (unsigned)t)) != 0;
+                    span16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) {
+                        mid(q);
+                        if (q < NDMA && got1) issue_piece(HOT, l, t - 1, q);
+                    });
+                } else
                 span16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) {
                     mid(q);
                     if (q == QO) look_issue(look_lds, look_voff, fl_desc, fl_off + (unsigned)(l * NFL * sizeof(unsigned)));
                     if (q == QO + 3) {
+                        C32_WAIT_T0();
                         look_landed();
+                        C32_WAIT_T1(0);
                         pk = *look_mine;
                     }
                     if (q == QO + 4) got1 = __all((int)(pk >= (unsigned)t)) != 0;
@@ -680,7 +793,11 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
 #ifdef APE_C32_COUNTS
                 lc_t0 = __builtin_amdgcn_s_memtime();
 #endif
+                C32_WAIT_T0();
                 if (!got1 && !got2) {
+#ifdef APE_C32_WAITS
+                    if (ST) lw_n[2] += 1u;
+#endif
 #ifdef APE_CLUSTER_STAMPS
                     dg_block[l] += 1;
 #endif
@@ -697,6 +814,10 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
                 bar();                                            // every wave's pieces of h^1_{t-1} are in LDS; xin's readers are through
 #ifdef APE_C32_COUNTS
                 if (ST) { lc_top[l] += __builtin_amdgcn_s_memtime() - lc_t0; lc_n[l] += 1u; }
+#endif
+#ifdef APE_C32_WAITS
+                C32_WAIT_T1(2);
+                if (ST) lw_n[0] += 1u;
 #endif
                 if (ctl[0] != 0) return false;
                 span16<BH / 2, true, NW1 / 4>(acc, hb1 + frag, w1, BH, [&](int q) { mid(BH + q); });
@@ -730,9 +851,9 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
 #endif
         if constexpr (l == L - 1) {
             // (an idle section, whose hooks did not run: the same here)
-            if (!ST && !staged && ph + 1 < T) {
-                stage_x();
-                if (ph + 2 < T) fetch_x(ph + 2);
+            if (!ST && !staged && ph + 1 + XA < T) {
+                stage_x(ph + 1 + XA);
+                if (ph + 2 + XA < T) fetch_x(ph + 2 + XA);
             }
         }
         // ---- publish: this lane's four fresh h values are one 16-byte piece of the exchange layout ----------------------------
@@ -831,6 +952,13 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         o[4] = lc_top[0]; o[5] = lc_top[1]; o[6] = lc_n[0]; o[7] = __builtin_amdgcn_s_memtime() - lc_start;
     }
 #endif
+#ifdef APE_C32_WAITS
+    if (p.dbg_wg != nullptr && tid == 0 && cluster < 24) {
+        unsigned long long* o = p.dbg_wg + 512 + (cluster * GH + member) * 8;
+        o[0] = lw[0]; o[1] = lw[1]; o[2] = lw[2]; o[3] = lw[3];
+        o[4] = lw_n[0]; o[5] = lw_n[1]; o[6] = lw_n[2]; o[7] = __builtin_amdgcn_s_memtime() - lw_start;
+    }
+#endif
     // ---- head: member m finishes windows 4m .. 4m+3 of the cluster's 32 ----------------------------------------------------------------
     {
         constexpr int RPM = MR / GH;
@@ -875,7 +1003,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
 }
 
 constexpr size_t smem_bytes32() {
-    return ((size_t)3 * 8 * 4 * 32 * 8 + (size_t)32 * 36) * sizeof(float) + (size_t)4 * 2 * 4 * 64 * 16 + (size_t)4 * 64 * sizeof(unsigned) + 16;
+    return ((size_t)3 * 8 * 4 * 32 * 8 + (size_t)2 * 32 * 36) * sizeof(float) + (size_t)4 * (2 + 1) * 4 * 64 * 16 + (size_t)4 * 64 * sizeof(unsigned) + 16;
 }
 
 }  // namespace
