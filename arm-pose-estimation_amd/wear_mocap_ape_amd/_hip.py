@@ -31,6 +31,8 @@ TRUTH_TARGETS, TRUTH_EST = 0, 1             # APE_TRUTH_*
 SCORE_MAX_LAG, SCORE_MAX_LAGS = 128, 65      # APE_SCORE_MAX_LAG, APE_SCORE_MAX_LAGS (ape_score_lags)
 POST_MAX_CONFIGS = 64             # APE_POST_MAX_CONFIGS (ape_post_sweep)
 FRAME_ACC_WIDTH = 51              # APE_FRAME_ACC_WIDTH (ape_frame_sums)
+BODY_ACC_WIDTH = 46               # APE_BODY_ACC_WIDTH (ape_body_sums)
+BODY_ROT_MSG, BODY_ROT_TRUTH = 0, 1         # APE_BODY_ROT_*
 FLAG_ANY_PLACEMENT, FLAG_NO_XCD_CLASSES, FLAG_ALT_FORM = 0x08000000, 0x02000000, 0x01000000    # exchange-form selectors (A/B runs, tests)
 FLAG_IN_XCD_PLAIN = 0x00400000      # opt-in: plain hand-over stores inside an XCD-pure cluster (the default is write-through)
 KERNEL_AUTO, KERNEL_TILE16, KERNEL_CLUSTER, KERNEL_CLUSTER_GEN1, KERNEL_AUTO_GEN1 = 0, 1, 2, 3, 4
@@ -221,6 +223,13 @@ SIGNATURES["ape_frame_times"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c
 SIGNATURES["ape_resample_truth"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
                                               C.c_void_p, C.c_int32, C.c_void_p, C.c_double, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                               C.c_void_p])
+# arm lengths and shoulder origin against the truth.  The sums: layout, msg + stride, msg dtype, truth + kind + dtype, F,
+# starts_host, R, skip, rot_source, lag_min, lag_max, rec_lag_host, acc, HIP stream.  The rows: layout, msg + stride, msg dtype, F,
+# starts_host, R, bodies_host, n_bodies, out + dtype, HIP stream
+SIGNATURES["ape_body_sums"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
+                                         C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+SIGNATURES["ape_rebody_rows"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_int32, C.c_void_p])
 
 _lib = None
 

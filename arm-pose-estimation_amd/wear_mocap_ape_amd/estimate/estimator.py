@@ -661,6 +661,21 @@ class Estimator:
         bodies = self._body_measurements if bonemaps is None else bonemaps
         return score.align_frame(self._layout, out, truth, lags, mode, weights, truth_kind, spread, starts, skip, bodies)
 
+    def fit_bodies(self, out, truth, starts=None, skip=None, truth_kind="est", lags=(0, 0), rec_lags=None, quats=None, mode="vectors",
+                   weights=(1, 1), bonemaps=None):
+        """``score.align_body`` with this estimator's layout and ``score_recording``'s defaults: each recording's arm vectors and shoulder
+        origin (``mode="vectors"``) or the three lengths of the prior body (``"lengths"``) that make ``out``'s positions fit ``truth``
+        (est rows) best, with the rotations ``out`` states.  ``lags`` / ``rec_lags``: the sweep, as in
+        ``score_recording``; ``quats``: ``align_recording``'s headings, taken out first; ``weights``: of the hand and the elbow;
+        ``bonemaps``: the prior -- one bonemap-like object, one per recording or float64 ``[R, 9]`` (default: this estimator's body).
+        Returns ``(score [F, 7], acc [R, 25], found)``: the rows made again under the bodies found and scored at the lags found, and
+        ``score.best_body``'s list; ``score.bodies_of(found)`` goes into ``set_bodies``, ``process_recording(bonemaps=)`` and
+        ``repost(bonemaps=)``."""
+        from wear_mocap_ape_amd import score
+        skip = self._sequence_len - 1 if skip is None else skip
+        prior = self._body_measurements if bonemaps is None else bonemaps
+        return score.align_body(self._layout, out, truth, lags, mode, weights, truth_kind, None, starts, skip, rec_lags, quats, prior)
+
     def truth_on_frames(self, rows, truth, truth_times, truth_starts=None, starts=None, shifts=None, max_gap: float = 0.0,
                         truth_kind="targets", bonemaps=None, big_endian: bool = False):
         """``score.truth_on_frames`` with this estimator's layout and body: the mocap ``truth`` (device ``[Ft, O]`` de-normalised targets,

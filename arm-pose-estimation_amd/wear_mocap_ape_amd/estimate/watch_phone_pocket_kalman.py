@@ -359,6 +359,12 @@ class WatchPhonePocketKalman(Estimator):
         return super().align_recording(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind, lags,
                                        mode, weights)
 
+    def fit_bodies(self, out, truth, starts=None, skip=None, truth_kind="est", lags=(0, 0), rec_lags=None, quats=None, mode="vectors",
+                   weights=(1, 1), bonemaps=None):
+        """``Estimator.fit_bodies`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
+        return super().fit_bodies(out, truth, starts, self.__win_size + 1 if skip is None else skip, truth_kind, lags, rec_lags, quats, mode,
+                                  weights, bonemaps)
+
     def truth_on_frames(self, rows, truth, truth_times, truth_starts=None, starts=None, shifts=None, max_gap: float = 0.0,
                         truth_kind="targets", bonemaps=None, big_endian: bool = False):
         """``Estimator.truth_on_frames`` for raw ``[F, 28]`` pocket rows"""

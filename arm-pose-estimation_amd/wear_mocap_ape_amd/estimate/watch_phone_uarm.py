@@ -146,6 +146,11 @@ class WatchPhoneUarm(Estimator):
         """``Estimator.align_recording`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
         return super().align_recording(out, truth, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind, lags, mode, weights)
 
+    def fit_bodies(self, out, truth, starts=None, skip=None, truth_kind="est", lags=(0, 0), rec_lags=None, quats=None, mode="vectors",
+                   weights=(1, 1), bonemaps=None):
+        """``Estimator.fit_bodies`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
+        return super().fit_bodies(out, truth, starts, 0 if skip is None else skip, truth_kind, lags, rec_lags, quats, mode, weights, bonemaps)
+
     def truth_on_frames(self, rows, truth, truth_times, truth_starts=None, starts=None, shifts=None, max_gap: float = 0.0,
                         truth_kind="targets", bonemaps=None, big_endian: bool = False):
         """``Estimator.truth_on_frames`` for raw ``[F, 55]`` watch-and-phone rows"""

@@ -1,4 +1,4 @@
-"""Scoring replayed poses against ground truth (``ape_score_rows``, ``ape_score_lags``, include/ape_hip.h; DESIGN.md 4.31 - 4.34).
+"""Scoring replayed poses against ground truth (``ape_score_rows``, ``ape_score_lags``, include/ape_hip.h; DESIGN.md 4.31 - 4.37).
 
 The reference has no counterpart: it never compares a message with the mocap truth its recordings carry.  ``score_rows`` does it on
 the device for every frame of a replay -- five errors and, with the frames' spread records, two squared Mahalanobis distances -- and
@@ -22,7 +22,13 @@ what remains; ``frame_sums_numpy`` and ``rotate_rows_numpy`` are the host statem
 Watch frames sit on a jittered clock and a mocap system runs at its own rate: ``frame_times`` builds a recording's clock from its
 ``sw_dt`` column, ``resample_truth`` gives est-kind truth rows at each frame's time less a shift (``ape_frame_times``,
 ``ape_resample_truth``), ``truth_on_frames`` does both from raw rows, ``align(refine=True)`` scores at ``best_lag``'s
-fractional lag; ``frame_times_numpy`` and ``resample_truth_numpy`` are the host statements."""
+fractional lag; ``frame_times_numpy`` and ``resample_truth_numpy`` are the host statements.
+
+The positions of a message are made from its quaternions and the nine values of a body, and the wearer's are rarely the default's:
+``body_sums`` takes, for every lag of a sweep, the sums a recording's least-squares body is read off (``ape_body_sums``, DESIGN.md
+4.37), ``best_body`` solves for nine values or three lengths on the host, ``bodies_of`` gives them to ``set_bodies`` and
+``process_recording(bonemaps=)``, ``rebody_rows`` makes the rows' positions again (``ape_rebody_rows``), ``align_body`` does all of it
+and scores what remains; ``body_sums_numpy`` and ``rebody_rows_numpy`` are the host statements."""
 import ctypes as C
 
 import numpy as np
@@ -964,3 +970,342 @@ def truth_on_frames(layout: int, rows, truth, truth_times, truth_starts=None, st
         raise UserWarning("rows: float32 raw messages [F, 55 | 28] on truth's device (or a host array)")
     times = frame_times(rows[:, 0], starts, big_endian)
     return resample_truth(layout, truth, truth_kind, truth_starts, truth_times, times, None, starts, shifts, max_gap, bodies)
+
+
+# ---- each recording's arm lengths and shoulder origin against the truth (ape_body_sums, ape_rebody_rows) -------------------
+# Every position of a message is forward kinematics of its own quaternions through the nine numbers of a body (larm_vec, uarm_vec,
+# uarm_orig): elbow = R_h o + R_u v_u, hand = elbow + R_l v_l.  The body enters linearly, so a recording's least-squares body solves a
+# 9 x 9 system of sums over its frames: ``body_sums`` takes the sums for every lag of a sweep in one pass, ``best_body`` solves on the
+# host, ``rebody_rows`` makes the rows' positions again under the body found, ``align_body`` does all three and scores what remains.
+BODY_ACC_WIDTH = _hip.BODY_ACC_WIDTH
+ROTATIONS = {"estimate": _hip.BODY_ROT_MSG, "truth": _hip.BODY_ROT_TRUTH}
+
+
+def _atb(x, y):
+    """``X' Y`` for stacks of 3x3 matrices, each entry ``x0 y0 + x1 y1 + x2 y2`` added left to right"""
+    return (x[:, 0, :, None] * y[:, 0, None, :] + x[:, 1, :, None] * y[:, 1, None, :]) + x[:, 2, :, None] * y[:, 2, None, :]
+
+
+def _atv(x, t):
+    """``X' t`` per row, each entry added left to right"""
+    return (x[:, 0, :] * t[:, None, 0] + x[:, 1, :] * t[:, None, 1]) + x[:, 2, :] * t[:, None, 2]
+
+
+def _body_terms(m, t, layout: int, from_truth: bool):
+    """the 44 terms ``[n, 44]`` of message rows ``m [n, 25]`` (None with ``from_truth``) paired with est rows ``t``, and which pairs
+    are summed ``[n]``"""
+    hips = layout != _hip.LAYOUT_ORI_CAL_LARM_UARM
+    ql, qu = (9, 13) if hips else (6, 10)
+    used = np.r_[0:6, ql:ql + 4, qu:qu + 4, 17:21] if hips else np.r_[0:6, ql:ql + 4, qu:qu + 4]
+    n = t.shape[0]
+    if from_truth:
+        quats = [t[:, ql:ql + 4], t[:, qu:qu + 4]] + ([t[:, 17:21]] if hips else [])
+    else:
+        quats = [m[:, 7:11], m[:, 14:18]] + ([m[:, 21:25]] if hips else [])
+    v = np.zeros((n, 44))
+    with np.errstate(all="ignore"):
+        Rl, Ru = _quat_matrix(quats[0]), _quat_matrix(quats[1])
+        Rh = _quat_matrix(quats[2]) if hips else np.broadcast_to(np.eye(3), (n, 3, 3))
+        th, te = t[:, 0:3], t[:, 3:6]
+        v[:, 0:9], v[:, 9:18], v[:, 18:27] = _atb(Rl, Ru).reshape(n, 9), _atb(Rl, Rh).reshape(n, 9), _atb(Ru, Rh).reshape(n, 9)
+        v[:, 27:30], v[:, 30:33], v[:, 33:36] = _atv(Rl, th), _atv(Ru, th), _atv(Rh, th)
+        v[:, 36:39], v[:, 39:42] = _atv(Ru, te), _atv(Rh, te)
+        v[:, 42], v[:, 43] = _dot3(th, th), _dot3(te, te)
+    ok = np.isfinite(t[:, used]).all(axis=1) & np.isfinite(v).all(axis=1)
+    for q in quats:
+        ok &= np.isfinite(q).all(axis=1)
+    return v, ok
+
+
+def _rotations(rotations) -> int:
+    if rotations not in ROTATIONS:
+        raise UserWarning(f"rotations must be one of {sorted(ROTATIONS)}, got {rotations!r}")
+    return ROTATIONS[rotations]
+
+
+def body_sums_numpy(msg, truth_est, layout: int, lags, starts=None, skip: int = 0, rec_lags=None, rotations: str = "estimate") -> np.ndarray:
+    """The host statement of ``body_sums`` for est-kind truth: float64 ``[R, L, 46]`` (include/ape_hip.h states the columns), over
+    ``score_lags_numpy``'s pairs and support; every column is summed pairwise, as in ``frame_sums_numpy``.  ``rotations="truth"``: the
+    matrices are the paired truth row's, ``msg`` is not read (None is fine) and the sweep must be ``(0, 0)`` without ``rec_lags``."""
+    from_truth = _rotations(rotations) == _hip.BODY_ROT_TRUTH
+    t = np.asarray(truth_est, dtype=np.float64)
+    m = None if from_truth else np.asarray(msg, dtype=np.float64)[:, :25]
+    st = np.asarray([0] if starts is None else starts, dtype=np.int64).reshape(-1)
+    F, R = t.shape[0], st.shape[0]
+    lo, hi, off = _sweep(lags, R, rec_lags)
+    if from_truth and ((lo, hi) != (0, 0) or rec_lags is not None):
+        raise UserWarning("rotations='truth': the sweep must be the single lag 0, without rec_lags")
+    L = hi - lo + 1
+    ends = np.r_[st[1:], F]
+    acc = np.zeros((R, L, BODY_ACC_WIDTH))
+    for r in range(R):
+        s, e, o = int(st[r]), int(ends[r]), int(off[r])
+        a, b = max(s + skip, s + o + hi), min(e, e + o + lo)                # the support: a pair at every lag, past the skipped frames
+        if a >= b:
+            continue
+        for j in range(L):
+            l = o + lo + j
+            v, ok = _body_terms(None if from_truth else m[a:b], t[a - l:b - l], layout, from_truth)
+            acc[r, j, :44] = np.ascontiguousarray(v[ok].T).sum(axis=1)       # along the contiguous axis: numpy's pairwise summation
+            acc[r, j, 44], acc[r, j, 45] = ok.sum(), (~ok).sum()
+    return acc
+
+
+def body_sums(layout: int, msg, truth, lags=(0, 0), truth_kind: str = "est", starts=None, skip: int = 0, rec_lags=None,
+              rotations: str = "estimate"):
+    """The sums each recording's body is read off, for the sweep of lags ``lags=(lo, hi)`` in one pass (``ape_body_sums``).  ``msg``,
+    ``truth``, ``starts``, ``skip``, ``rec_lags``, the pairing and the support: ``score_lags``'s.  ``truth_kind``: ``"est"`` rows for
+    every layout; ``"targets"`` only for the layout whose targets carry positions (the two others' positions would be made with the
+    body being fitted).  ``rotations="estimate"``: the matrices are those of the message's quaternions -- the body that makes THIS
+    estimator's positions fit; ``"truth"``: those of the paired truth row -- the wearer's skeleton from mocap alone; ``msg`` may then be
+    None and the sweep must be ``(0, 0)`` without ``rec_lags``.  Returns float64 ``[R, L, 46]`` on the device (``best_body``;
+    include/ape_hip.h states the columns).  The call does not wait for the device."""
+    rot = _rotations(rotations)
+    if truth_kind not in TRUTH_KINDS:
+        raise UserWarning(f"truth_kind must be one of {sorted(TRUTH_KINDS)}, got {truth_kind!r}")
+    if layout not in _hip.EST_WIDTH:
+        raise UserWarning(f"layout {layout} has no pose to fit")
+    tw = (_hip.NUM_TARGETS if truth_kind == "targets" else _hip.EST_WIDTH)[layout]
+    if not isinstance(truth, torch.Tensor) or not truth.is_cuda or truth.dtype not in (torch.float32, torch.float64) or truth.dim() != 2 \
+            or truth.shape[1] != tw:
+        raise UserWarning(f"truth: a float32 or float64 device tensor [F, {tw}]")
+    td, dev = truth.contiguous(), truth.device
+    F = int(td.shape[0])
+    md, ms = (None, 25)
+    if msg is not None:
+        md, ms = _rows_view(msg, 25, "msg")
+        if md.shape[0] != F or md.device != dev:
+            raise UserWarning(f"msg: expected {F} rows on {dev}, got {int(md.shape[0])} on {md.device}")
+    elif rot == _hip.BODY_ROT_MSG:
+        raise UserWarning("msg: a device tensor [F, >= 25] (None only with rotations='truth')")
+    st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
+    R = int(st.shape[0])
+    lo, hi, off = _sweep(lags, R, rec_lags)
+    L = hi - lo + 1
+    if not 1 <= L <= _hip.SCORE_MAX_LAGS:
+        raise UserWarning(f"lags=({lo}, {hi}): between 1 and {_hip.SCORE_MAX_LAGS} lags")
+    with torch.cuda.device(dev):
+        acc = torch.empty((max(R, 1), L, BODY_ACC_WIDTH), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_body_sums(int(layout), C.c_void_p(md.data_ptr()) if md is not None else None, ms,
+                                            _f64(md.dtype) if md is not None else _hip.F64, C.c_void_p(td.data_ptr()),
+                                            TRUTH_KINDS[truth_kind], _f64(td.dtype), F, C.c_void_p(st.ctypes.data), R, int(skip), rot, lo, hi,
+                                            C.c_void_p(off.ctypes.data) if rec_lags is not None else None, C.c_void_p(acc.data_ptr()),
+                                            stream), "ape_body_sums")
+    return acc
+
+
+def _prior_rows(prior, R: int) -> np.ndarray:
+    """float64 ``[R, 9]`` of ``best_body``'s ``prior``"""
+    p = _body_rows(prior, R, "best_body prior")
+    if not np.isfinite(p).all():
+        raise UserWarning("prior: a non-finite value")
+    return np.ascontiguousarray(np.broadcast_to(p, (R, 9)))
+
+
+def _body_systems(rows):
+    """of the 46-value records ``[L, 46]`` of one recording: the unweighted normal matrices ``[L, 9, 9]`` and right sides ``[L, 9]`` of
+    the hand and of the elbow ``(N_h, b_h, N_e, b_e)`` in the unknowns ``x = [larm_vec, uarm_vec, uarm_orig]``"""
+    L = rows.shape[0]
+    A, B, Cm = (rows[:, 9 * k:9 * k + 9].reshape(L, 3, 3) for k in range(3))
+    I = rows[:, 44, None, None] * np.eye(3)
+    Nh, Ne = np.zeros((L, 9, 9)), np.zeros((L, 9, 9))
+    Nh[:, 0:3, 0:3] = Nh[:, 3:6, 3:6] = Nh[:, 6:9, 6:9] = Ne[:, 3:6, 3:6] = Ne[:, 6:9, 6:9] = I
+    Nh[:, 0:3, 3:6], Nh[:, 0:3, 6:9], Nh[:, 3:6, 6:9], Ne[:, 3:6, 6:9] = A, B, Cm, Cm
+    At, Bt, Ct = (np.transpose(m, (0, 2, 1)) for m in (A, B, Cm))
+    Nh[:, 3:6, 0:3], Nh[:, 6:9, 0:3], Nh[:, 6:9, 3:6], Ne[:, 6:9, 3:6] = At, Bt, Ct, Ct
+    bh = rows[:, 27:36].copy()
+    be = np.concatenate([np.zeros((L, 3)), rows[:, 36:42]], axis=1)
+    return Nh, bh, Ne, be
+
+
+def _joint_squares(tt, N, b, x):
+    """``sum |t - prediction|^2 = sum |t|^2 - 2 x'b + x'N x`` per lag, clamped at 0; ``x [L, 9]``"""
+    return np.maximum(tt - 2.0 * np.einsum("lk,lk->l", x, b) + np.einsum("lj,ljk,lk->l", x, N, x), 0.0)
+
+
+def best_body(acc, lags, mode: str = "vectors", weights=(1, 1), prior=None, ridge: float = 0.0, max_cond: float = 1e8, rec_lags=None) -> list:
+    """Each recording's lag and least-squares body, read off the accumulators ``acc [R, L, 46]`` of a ``body_sums`` sweep
+    ``lags=(lo, hi)`` (with the ``rec_lags`` the sweep was made with).  ``weights = (w_hand, w_elbow)``: of the hand's and the elbow's
+    squared residuals.  In the unknowns ``x = [larm_vec, uarm_vec, uarm_orig]`` and with ``n`` pairs, ``A, B, C`` the three product
+    blocks per pair, the normal matrix is ``n [[w_h I, w_h A, w_h B], [., (w_h + w_e) I, (w_h + w_e) C], [., ., (w_h + w_e) I]]``, the
+    right side ``[w_h R_l't_h, w_h R_u't_h + w_e R_u't_e, w_h R_h't_h + w_e R_h't_e]`` summed.  With ``w_hand = 0`` the forearm is not
+    observable: ``larm_vec`` stays the prior's and the other six values are fitted.
+    ``mode="vectors"``  all nine values (six with ``w_hand = 0``)
+    ``mode="lengths"``  three scales ``s`` of the prior body's three vectors, ``x = D s`` with ``D [9, 3]`` holding the prior's vectors:
+                        normal ``D'N D``, right side ``D'b`` (two scales with ``w_hand = 0``) -- for a recording whose motion does not
+                        separate the nine values (an upper arm that is rigid against the hips)
+    ``prior``: float64 ``[9]`` / ``[R, 9]`` values or bonemap-like objects as ``score_rows`` takes ``bodies`` (default: the default
+    bonemap).  ``ridge >= 0`` adds ``ridge n I`` to the system solved, towards the prior (its values, or scales of 1).
+    Per recording a dict: ``lag`` the lag with the smallest weighted mean squared residual after the fit (ties: the smaller ``|l|``,
+    then the smaller ``l``), ``body [9]``, ``larm_length`` / ``uarm_length`` (the norms of its two vectors), ``hand_rms_before`` /
+    ``hand_rms_after`` / ``elbow_rms_before`` / ``elbow_rms_after`` from the sums as ``sqrt(max(0, sum |t|^2 - 2 x'b + x'N x) / n)`` per
+    joint ("before": under the prior), ``pairs`` summed at ``lag``, ``cond`` the condition number of the system solved at ``lag``,
+    ``residual [L]`` the weighted mean squared residual after the fit per lag (NaN where a lag has no usable fit), ``ok``.
+    A lag is usable where it has at least as many pairs as unknowns, a condition number of at most ``max_cond`` and a finite solution.
+    A recording without a usable lag: ``ok`` False, ``body`` the prior, and ``lag`` the lag with the smallest residual under the prior
+    -- None, with ``pairs`` 0 and NaN values, where no lag has a pair."""
+    if mode not in ("vectors", "lengths"):
+        raise UserWarning(f"mode must be 'vectors' or 'lengths', got {mode!r}")
+    a = acc.detach().cpu().numpy() if isinstance(acc, torch.Tensor) else np.asarray(acc)
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim != 3 or a.shape[-1] != BODY_ACC_WIDTH:
+        raise UserWarning(f"expected accumulators [R,L,{BODY_ACC_WIDTH}], got {tuple(a.shape)}")
+    w = np.asarray(weights, dtype=np.float64).reshape(-1)
+    if w.shape[0] != 2 or not np.isfinite(w).all() or (w < 0.0).any() or not (w > 0.0).any():
+        raise UserWarning("weights: two finite values >= 0 (hand, elbow), not both zero")
+    if not (np.isfinite(ridge) and ridge >= 0.0) or not max_cond > 0.0:
+        raise UserWarning("ridge: a finite value >= 0; max_cond: above 0")
+    R, L = a.shape[0], a.shape[1]
+    lo, hi, off = _sweep(lags, R, rec_lags)
+    if hi - lo + 1 != L:
+        raise UserWarning(f"best_body: lags=({lo}, {hi}) for accumulators of {L} lags")
+    priors = _prior_rows(prior, R)
+    wh, we = float(w[0]), float(w[1])
+    res = []
+    for r in range(R):
+        x0 = priors[r]
+        ls = int(off[r]) + lo + np.arange(L)
+        if mode == "vectors":
+            D, u0 = np.eye(9), x0                                            # x = D u, the unknowns u start at the prior's values
+        else:
+            D, u0 = np.zeros((9, 3)), np.ones(3)
+            for k in range(3):
+                D[3 * k:3 * k + 3, k] = x0[3 * k:3 * k + 3]
+        free = np.arange(D.shape[1]) if wh > 0.0 else np.arange(D.shape[1])[3 if mode == "vectors" else 1:]
+        Df, k = D[:, free], free.shape[0]
+        fixed = x0 - Df @ u0[free]                                           # what is not fitted stays the prior's
+        n = a[r, :, 44]
+        Nh, bh, Ne, be = _body_systems(a[r])
+        N, b = wh * Nh + we * Ne, wh * bh + we * be
+        with np.errstate(all="ignore"):
+            safe = np.where(n > 0, n, 1.0)
+            prior_rows = np.broadcast_to(x0, (L, 9))
+            h0, e0 = _joint_squares(a[r, :, 42], Nh, bh, prior_rows), _joint_squares(a[r, :, 43], Ne, be, prior_rows)
+            resid0 = np.where(n > 0, (wh * h0 + we * e0) / safe, np.nan)
+            M = np.einsum("ia,lij,jb->lab", Df, N, Df) + ridge * n[:, None, None] * np.eye(k)
+            rhs = np.einsum("ia,li->la", Df, b - np.einsum("lij,j->li", N, fixed)) + ridge * n[:, None] * u0[free]
+            enough = (n > 0) & (n >= k)
+            finite = np.isfinite(M).all(axis=(1, 2))
+            cond = np.full(L, np.nan)
+            cond[enough & ~finite] = np.inf
+            if (enough & finite).any():
+                cond[enough & finite] = np.linalg.cond(M[enough & finite])
+            good = enough & (cond <= max_cond)
+            X = np.full((L, 9), np.nan)
+            if good.any():
+                try:
+                    X[good] = fixed + np.linalg.solve(M[good], rhs[good][:, :, None])[:, :, 0] @ Df.T
+                except np.linalg.LinAlgError:
+                    pass
+            usable = good & np.isfinite(X).all(axis=1)
+            Xs = np.where(usable[:, None], X, prior_rows)
+            h1, e1 = _joint_squares(a[r, :, 42], Nh, bh, Xs), _joint_squares(a[r, :, 43], Ne, be, Xs)
+            resid = np.where(usable, (wh * h1 + we * e1) / safe, np.nan)
+        ok = bool(usable.any())
+        pick = resid if ok else resid0
+        cand = [j for j in range(L) if np.isfinite(pick[j])]
+        if not cand:
+            nan = float("nan")
+            res.append({"lag": None, "body": x0.copy(), "larm_length": float(np.linalg.norm(x0[0:3])), "uarm_length": float(np.linalg.norm(x0[3:6])),
+                        "hand_rms_before": nan, "hand_rms_after": nan, "elbow_rms_before": nan, "elbow_rms_after": nan, "pairs": 0,
+                        "cond": nan, "residual": resid, "ok": False})
+            continue
+        j = min(cand, key=lambda i: (pick[i], abs(int(ls[i])), int(ls[i])))
+        x = Xs[j].copy()
+        rms = lambda sq: float(np.sqrt(sq[j] / n[j]))                                                         # noqa: E731
+        res.append({"lag": int(ls[j]), "body": x, "larm_length": float(np.linalg.norm(x[0:3])), "uarm_length": float(np.linalg.norm(x[3:6])),
+                    "hand_rms_before": rms(h0), "hand_rms_after": rms(h1), "elbow_rms_before": rms(e0), "elbow_rms_after": rms(e1),
+                    "pairs": int(n[j]), "cond": float(cond[j]), "residual": resid, "ok": ok})
+    return res
+
+
+def bodies_of(found) -> np.ndarray:
+    """float64 ``[R, 9]`` of ``best_body``'s list, ready for ``set_bodies``, ``process_recording(bonemaps=)`` and ``repost(bonemaps=)``"""
+    return np.ascontiguousarray(np.stack([np.asarray(b["body"], dtype=np.float64).reshape(9) for b in found]))
+
+
+def _qrot(q, v):
+    """``q (0, v) q*``, the two products of csrc/fk_device.h's qrot in their order; ``q [n, 4]``, ``v [n, 3]`` -> ``[n, 3]``"""
+    t = _qmul(q, np.concatenate([np.zeros((v.shape[0], 1)), v], axis=1))
+    return _qmul(t, q * np.array([1.0, -1.0, -1.0, -1.0]))[:, 1:]
+
+
+def _bodies(bodies, R: int, what: str) -> np.ndarray:
+    """float64 ``[1 | R, 9]`` of one body or one per recording"""
+    b = np.asarray(bodies, dtype=np.float64)
+    b = b.reshape(1, 9) if b.size == 9 else b
+    if b.ndim != 2 or b.shape[1] != 9 or b.shape[0] not in (1, R):
+        raise UserWarning(f"{what}: one body [9] or one per recording [{R}, 9], got {tuple(b.shape)}")
+    return np.ascontiguousarray(b)
+
+
+def rebody_rows_numpy(msg, bodies, layout: int, starts=None) -> np.ndarray:
+    """The host statement of ``rebody_rows``: float64 ``[F, 25]``.  With the recording's body ``larm_vec, uarm_vec, uarm_orig``: the four
+    quaternions as they are, ``[18:21] = q_hips (x) uarm_orig`` (without hips: ``uarm_orig`` itself), ``[11:14] = q_uarm (x) uarm_vec +
+    [18:21]``, ``[4:7] = q_larm (x) larm_vec + [11:14]``."""
+    if layout not in (_hip.LAYOUT_ORI_CAL_LARM_UARM_HIPS, _hip.LAYOUT_ORI_CAL_LARM_UARM):
+        raise UserWarning(f"layout {layout}: its positions are not made from a body")
+    m = np.asarray(msg, dtype=np.float64)[:, :25]
+    st = np.asarray([0] if starts is None else starts, dtype=np.int64).reshape(-1)
+    F, R = m.shape[0], st.shape[0]
+    b = _bodies(bodies, R, "bodies")
+    rec = np.searchsorted(st, np.arange(F), side="right") - 1 if b.shape[0] > 1 else np.zeros(F, dtype=np.int64)
+    b = b[rec]
+    out = m.copy()
+    with np.errstate(all="ignore"):
+        out[:, 18:21] = _qrot(m[:, 21:25], b[:, 6:9]) if layout == _hip.LAYOUT_ORI_CAL_LARM_UARM_HIPS else b[:, 6:9]
+        out[:, 11:14] = _qrot(m[:, 14:18], b[:, 3:6]) + out[:, 18:21]
+        out[:, 4:7] = _qrot(m[:, 7:11], b[:, 0:3]) + out[:, 11:14]
+    return out
+
+
+def rebody_rows(layout: int, msg, bodies, starts=None, out_dtype=None):
+    """Replay rows with their positions made again under a body per recording (``ape_rebody_rows``): ``msg`` device ``[F, >= 25]``
+    (nothing past column 24 is read), ``bodies`` float64 ``[9]`` or ``[R, 9]`` (``bodies_of(best_body(...))``), ``starts`` the
+    recordings' first frames.  Returns ``out [F, 25]`` of ``out_dtype`` (default: ``msg``'s): the quaternions copied, the shoulder, elbow
+    and hand origins from them and the body.  The layout whose positions are predicted is refused.  A spread record is not rewritten:
+    its covariances cannot be made again from 21 values.  The call does not wait for the device."""
+    if layout not in _hip.EST_WIDTH:
+        raise UserWarning(f"layout {layout} has no pose to rebuild")
+    md, ms = _rows_view(msg, 25, "msg")
+    out_dtype = md.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+    F, dev = int(md.shape[0]), md.device
+    st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
+    R = int(st.shape[0])
+    body = _bodies(bodies, R, "bodies")
+    with torch.cuda.device(dev):
+        out = torch.empty((F, 25), dtype=out_dtype, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_rebody_rows(int(layout), C.c_void_p(md.data_ptr()), ms, _f64(md.dtype), F, C.c_void_p(st.ctypes.data), R,
+                                              C.c_void_p(body.ctypes.data), int(body.shape[0]), C.c_void_p(out.data_ptr()), _f64(out_dtype),
+                                              stream), "ape_rebody_rows")
+    return out
+
+
+def align_body(layout: int, msg, truth, lags=(0, 0), mode: str = "vectors", weights=(1, 1), truth_kind: str = "est", spread=None, starts=None,
+               skip: int = 0, rec_lags=None, quats=None, prior=None):
+    """Find each recording's lag and body together and score with both removed: ``rotate_rows`` by ``quats`` where given
+    (``best_frame``'s, ``[4]`` or ``[R, 4]``: the heading is taken out first), a ``body_sums`` sweep with the message's rotations,
+    ``best_body`` on it (this waits for the device), ``rebody_rows`` under the bodies found (the prior where a recording has no usable
+    fit), then ``score_lags`` of the rewritten rows with ``lags=(0, 0)`` and the lags found as offsets (a recording's own ``rec_lags``
+    entry, or 0, where it has no pair).  Returns ``(score [F, 7], acc [R, 25], found)``, ``found`` being ``best_body``'s list
+    (``bodies_of(found)`` for ``set_bodies`` and ``process_recording(bonemaps=)``).  The spread record (``spread``) passes through
+    unchanged but for the turn by ``quats``: the Mahalanobis columns then describe the OLD body's cloud around positions made with the
+    new one.  ``truth``: est rows; the layout whose positions are predicted cannot be rewritten and is refused."""
+    rec = spread
+    if quats is not None:
+        turned = rotate_rows(layout, msg, quats, spread, starts)
+        msg, rec = turned if spread is not None else (turned, None)
+    sums = body_sums(layout, msg, truth, lags, truth_kind, starts, skip, rec_lags, "estimate")
+    found = best_body(sums, lags, mode, weights, prior, rec_lags=rec_lags)
+    bodies = bodies_of(found)
+    base = np.zeros(len(found), dtype=np.int64) if rec_lags is None else np.asarray(rec_lags, dtype=np.int64).reshape(-1)
+    at = [int(base[r]) if b["lag"] is None else b["lag"] for r, b in enumerate(found)]
+    out = rebody_rows(layout, msg, bodies, starts)
+    if rec is not None and rec.dtype != out.dtype:
+        rec = rec.to(out.dtype)
+    score, acc = score_lags(layout, out, truth, (0, 0), truth_kind, rec, starts, skip, bodies, at, per_frame=True)
+    return score[:, 0], acc[:, 0], found

@@ -1086,6 +1086,57 @@ int ape_resample_truth(int32_t layout, const void* truth_dev, int32_t truth_kind
                        const double* bodies_host, int32_t n_bodies,
                        void* out_dev /* [F, 21 | 14] of out_dtype */, int32_t out_dtype, void* stream);
 
+/* ---- each recording's arm lengths and shoulder origin against the truth (additive in ABI 7) -------------------------------
+ * replaces: nothing; the reference reads a wearer's body from a skeleton file and has no fit.  Every position of a message is forward
+ * kinematics of the message's own quaternions through nine numbers (larm_vec, uarm_vec, uarm_orig): with R_l, R_u, R_h the matrices of
+ * the lower-arm, upper-arm and hips quaternions, elbow = R_h o + R_u v_u and hand = elbow + R_l v_l.  A wearer whose arm is not the
+ * default's is booked as error on every frame.  The body enters linearly: the least-squares body of a recording solves a 9 x 9 system
+ * whose entries are sums over the frames (score.py: best_body).  ape_body_sums takes those sums for every lag of a sweep in one pass,
+ * ape_rebody_rows makes the positions of replay rows again under a body.
+ * ape_body_sums.  Pairing (message f, truth f - l), the sign of a lag, the per-recording offsets, the support of the accumulators (skip,
+ *   lag_max, lag_min), the bounds APE_SCORE_MAX_LAG / APE_SCORE_MAX_LAGS, strided message rows and the dtypes are ape_frame_sums's.
+ *   rot_source APE_BODY_ROT_MSG: R_l, R_u, R_h are the matrices (ape_frame_sums's formula, an unnormalised quaternion is the rotation it
+ *   stands for) of msg[7:11], msg[14:18], msg[21:25] -- the body that makes THIS estimator's positions fit; nothing else of a message
+ *   row is read.  APE_BODY_ROT_TRUTH: they are those of the paired truth row's quaternions -- the wearer's skeleton from mocap alone;
+ *   msg_dev may be NULL and is not read, the sweep must be the single lag 0 with rec_lag_host NULL.  APE_LAYOUT_ORI_CAL_LARM_UARM (no
+ *   hips): R_h = I and msg[21:25] is not read.
+ *   Truth: APE_TRUTH_EST rows [21 | 14] for every scoring layout (est columns [6:9], the shoulder origin, are not read); APE_TRUTH_TARGETS
+ *   only for APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS, whose targets carry positions (converted as ape_score_rows converts them).
+ *   With X'Y: out[3 a + b] = sum_k X[k, a] Y[k, b], X't: out[a] = sum_k X[k, a] t[k], t_h and t_e the truth's hand and elbow origins,
+ *   acc_dev f64 [R, L, APE_BODY_ACC_WIDTH] receives over the support:
+ *     [0:9], [9:18], [18:27]     sum of R_l'R_u, R_l'R_h, R_u'R_h
+ *     [27:30], [30:33], [33:36]  sum of R_l't_h, R_u't_h, R_h't_h
+ *     [36:39], [39:42]           sum of R_u't_e, R_h't_e
+ *     [42], [43]                 sum of |t_h|^2, |t_e|^2
+ *     [44], [45]                 pairs of the support that were summed / that were left out
+ *   A pair is summed iff every quaternion value read for the rotations is finite, the truth row is one ape_score_lags would use (every
+ *   used value finite) and all of its 44 terms are finite (a zero quaternion among the rotations makes them non-finite); a pair that is
+ *   left out contributes exact zeros.  [44] + [45] is the same for every lag of a recording; an empty support gives zeros.  float64
+ *   with separate roundings; no floating-point atomics and a fixed order of summation: the same inputs give the same bits.
+ *   Refused with APE_ERR_INVALID_ARG on the host, before anything is written: what ape_frame_sums refuses about pointers (msg_dev only
+ *   with APE_BODY_ROT_MSG), layout, kind, dtypes, starts, stride, skip and lags; an unknown rot_source; target truth of the two layouts
+ *   whose positions would be made with the body being fitted; APE_BODY_ROT_TRUTH with a sweep or with rec_lag_host; a capturing stream.
+ * ape_rebody_rows.  With b = bodies_host[r] (one for all recordings, or one per recording) = larm_vec, uarm_vec, uarm_orig and q (x) v
+ *   the rotation of fk_device.h (q (0, v) q*, as ape_fk applies it): the four quaternions [0:4], [7:11], [14:18], [21:25] are copied;
+ *   [18:21] = msg[21:25] (x) uarm_orig (APE_LAYOUT_ORI_CAL_LARM_UARM: uarm_orig itself), [11:14] = msg[14:18] (x) uarm_vec + [18:21],
+ *   [4:7] = msg[7:11] (x) larm_vec + [11:14].  A non-finite quaternion makes only the positions that depend on it non-finite.  Nothing
+ *   past column 24 of a message row is read; a spread record is not rewritten (its covariances cannot be made again from 21 values).
+ *   out_dev [F, 25] of out_dtype, float64 arithmetic rounded once; it must not alias the input.  One lane per frame, one launch.
+ *   Refused with APE_ERR_INVALID_ARG before anything is written: NULL msg_dev / seg_starts_host / bodies_host / out_dev, F < 1, R < 1,
+ *   bad starts, msg_stride < 25, n_bodies not 1 or R, APE_LAYOUT_NONE or an unknown layout / dtype, APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS
+ *   (its positions are predicted, not made from a body), out_dev equal to msg_dev, a capturing stream.
+ * Both need no model handle, run on the current HIP device and do not wait; the host arrays have been consumed when they return; staging
+ * slots as ape_score_rows keeps them (this file's own: the first call of a size allocates, later ones do not). */
+#define APE_BODY_ACC_WIDTH 46
+#define APE_BODY_ROT_MSG   0   /* rotations from the message's quaternions: the body that makes THIS estimator's positions fit */
+#define APE_BODY_ROT_TRUTH 1   /* rotations from the truth's quaternions: the wearer's skeleton from mocap alone */
+int ape_body_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int32_t msg_dtype, const void* truth_dev, int32_t truth_kind,
+                  int32_t truth_dtype, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t skip, int32_t rot_source,
+                  int32_t lag_min, int32_t lag_max, const int32_t* rec_lag_host, double* acc_dev /* [R, L, 46] */, void* stream);
+int ape_rebody_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, int32_t msg_dtype, int32_t F, const int32_t* seg_starts_host,
+                    int32_t R, const double* bodies_host, int32_t n_bodies /* 1 | R */, void* out_dev /* [F, 25] */, int32_t out_dtype,
+                    void* stream);
+
 #ifdef __cplusplus
 }
 #endif
