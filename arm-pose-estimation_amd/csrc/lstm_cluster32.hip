@@ -138,7 +138,10 @@ __device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 r
     if constexpr (HOT) {
         unsigned tmp;
         asm volatile("s_add_i32 m0, %1, %5\n\ts_add_i32 %0, %4, %5\n\tbuffer_load_dwordx4 %2, %3, %0 offen sc1 lds"
-                     : "=&s"(tmp) : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff), "i"(piece_bytes) : "memory");
+                     : "=&s"(tmp) : "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff), "i"(piece_bytes) : "memory", "scc");
+        // ("scc": s_add_i32 writes it.  As long as every piece sat behind a branch of its own hipcc never held a condition in SCC across one; with the
+        //  branches gone it kept layer 1's own judge there, from the head of the input span to the branch behind it -- the eight pieces in between
+        //  cleared it, and every section took the blocking refill: same results, 4 % slower; tests/tools/counts_c32.py showed 60 of 60)
     } else {
         asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
                      :: "s"(lds_addr + (unsigned)piece_bytes), "v"(voff), "s"(rsrc), "s"(soff + (unsigned)piece_bytes) : "memory");
@@ -181,6 +184,20 @@ __device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 r
 #endif
 #ifndef C32_QJX
 #define C32_QJX 54
+#endif
+// the hot gaps of the long-window steady-state sections (profiles/r10_cluster32_hot_gaps.md; each switch 0 = the form in front of it, for A/B runs):
+// C32_UG = the eight pieces of both gathers go out without a branch, from a source base derived once per section (see `UG` in the kernel for why
+// a copy nobody asked for harms nobody); C32_RS = the flag owed goes up as one buffer store through the looks' descriptor
+#ifndef C32_UG
+#define C32_UG 1
+#endif
+#ifndef C32_RS
+#define C32_RS 1
+#endif
+// test builds only (lib/diag/libape_hip_c32late.so): the judges of both gathers read "not yet" in every N-th steady-state phase, whatever the flags say --
+// the path of a late peer (0.05-2 sections per 1024 x 64 launch: never in a small test), which ends in the bounded blocking refill
+#ifndef APE_C32_LATE_EVERY
+#define APE_C32_LATE_EVERY 0
 #endif
 #if defined(APE_C32_COUNTS) && defined(APE_C32_WAITS)
 #error "APE_C32_COUNTS and APE_C32_WAITS write the same words of dbg_wg: one build, one of them"
@@ -408,18 +425,36 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     auto issue_piece = [&](auto hot_tag, int l, int step, int k) {       // slices of layer l, step `step` -> hb0[step parity] / hb1
         constexpr bool HOT = decltype(hot_tag)::value;
         const unsigned wk = HOT ? wave_kib : opaque(wave_kib);
-        const unsigned src = hx_base(l, step & 1) + wk;
+        // (long windows, blocking forms: the set's base opaque as well -- hipcc otherwise keeps `base | piece offset` of all eight pieces in scalars
+        //  for the whole launch, and the steady-state sections then reload one of THEIR scalars from a spill lane in the middle of the MFMA stream)
+        const unsigned src = ((HOT || ENDS) ? hx_base(l, step & 1) : opaque(hx_base(l, step & 1))) + wk;
         const unsigned dst = (l == 0 ? hb0_lds + (unsigned)((step & 1) * SET_BYTES) : hb1_lds) + wk;
         dma_1k<HOT>(dst, dma_voff, hx_desc, src, k * 4096);
     };
     constexpr std::true_type HOT{};
     constexpr std::false_type COLD{};
     // the flag a wave owes for the slice it stored last: raised once that store has drained
+    // (EV, long windows with C32_RS: the epoch lives in a vector register from the publish on, for raise_hot() below, and NOT in a scalar beside it --
+    //  the steady-state sections have no scalar register to spare)
+    constexpr bool EV = !ENDS && C32_XS != 0 && C32_RS != 0;
     int pend_idx = -1;
-    unsigned pend_epoch = 0u;
+    unsigned pend_epoch = 0u, pend_epoch_v = 0u;
     auto raise_pending = [&]() {              // caller has waited vmcnt(0)
         if (pend_idx < 0) return;
-        if (lane == 0) __hip_atomic_store(flags_of + pend_idx, pend_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (lane == 0) __hip_atomic_store(flags_of + pend_idx, EV ? pend_epoch_v : pend_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        pend_idx = -1;
+    };
+    // The same for the hooks of the long-window steady-state sections (C32_RS), where the flag owed is always the OTHER layer's (`lo`) and always
+    // this wave's: ONE buffer store through the looks' descriptor, no branch, no 64-bit address.  Lane 0 stores at its flag's offset inside a
+    // layer's row, every other lane points outside the descriptor (the 0x80000000 idiom of the x rows and the idle publishes: dropped by the
+    // range check); `sc1` = the agent-scope store of raise_pending().  The epoch waits in a vector register since the publish (pend_epoch_v).
+    // A wave that came through a blocking path has raised the flag already and stores the same epoch once more -- the word's only writer is this wave.
+    const unsigned raise_voff = (lane == 0) ? (unsigned)((member * 4 + wave) * sizeof(unsigned)) : 0x80000000u;
+    // (the layer's row as the instruction's immediate offset: one scalar, the cluster's `fl_off`, serves both layers)
+    auto raise_hot = [&](auto lo_tag) {       // caller has waited vmcnt(0)
+        constexpr int lo = decltype(lo_tag)::value;
+        asm volatile("buffer_store_dword %0, %1, %2, %3 offen offset:%4 sc1"
+                     :: "v"(pend_epoch_v), "v"(raise_voff), "s"(fl_desc), "s"(fl_off), "i"(lo * NFL * (int)sizeof(unsigned)) : "memory");
         pend_idx = -1;
     };
     // workgroup barrier that waits for this wave's LDS traffic only (not for the publish store or a DMA in flight)
@@ -582,6 +617,9 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         constexpr int MODE = decltype(mode_tag)::value;
         static_assert(MODE == 0 || (l == L - 1 && (MODE == 3 || !ST)), "the special forms are layer 1's");
         const int t = ph - l;
+        // (a comment line in the device assembly, no instruction: tools/tally_c32_gaps.py counts what stands between the MFMAs of the long-window
+        //  steady-state sections, from this line to the matching one in front of the drain)
+        if constexpr (ST && !ENDS) asm volatile("; c32 steady section, layer %0: begin" :: "i"(l));
         const bool active = ST || (t >= 0 && t < T);
         // h^l_{t-1} exists and somebody reads it from here on (layer 0 at t == T: no layer-0 step any more, but layer 1's
         // last step takes h^0_{T-1} as its input)
@@ -655,6 +693,25 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         constexpr int QF = (!ENDS && l == 0 && C32_XS != 0) ? (ST ? BXU + C32_QFP : (C32_QF > BXU ? C32_QF : BXU)) : C32_QF;
         constexpr int QP = (MODE == 1) ? 16 : LW ? C32_QPX : NBL / 2 - 2 + C32_QPD, QJ = (MODE == 1) ? 20 : LW ? C32_QJX : NBL / 2 + 2 + C32_QPD;
         static_assert(!LW || (QP >= 0 && QP < QJ - 1 && QJ + NDMA <= 2 * BH), "the look, its judge and the eight pieces fit the section");
+        // UG (long windows, steady state, layer 1): the eight pieces of BOTH gathers -- the next section's at blocks QJ .. QJ + 7, the own at blocks
+        // 0 .. 7 of the input span -- go out whatever the judge says, at the blocks and addresses they always had: each piece is the three
+        // instructions of dma_1k<true>, with no branch and no mask arithmetic around it, its source base derived ONCE (at the judge) and made opaque so
+        // that hipcc keeps it in one scalar instead of re-deriving it per piece.  `pre` is always true here and a next section always exists, so the
+        // copy has a buffer of its own to land in: hb0[ph & 1] for the next section (this section's input span reads the OTHER parity; layer 0's
+        // recurrent span of phase ph + 1 is the buffer's next reader) resp. hb1 (next reader: this section's recurrent span, behind the barrier
+        // between the spans; the head reads it only behind the final gather).  The judge keeps its place and its meaning: `go` / `got1` decide whether
+        // that reader TRUSTS the copy.  Where a judge failed, the pieces have copied stale or half-written exchange bytes into the very block that the
+        // blocking path then refills -- `vmcnt(0)` (the early pieces have landed), wait_flags, eight COLD pieces, `vmcnt(0)` -- in front of the
+        // barrier every reader sits behind, and every wave refills exactly the KiBs it copied early.  The early copy lands in the same buffer at the same
+        // time as a trusted one would: no reader sees anything new.  Sections outside the steady state keep the conditional form: there a next section
+        // may not exist, and a copy nobody asked for would land in live data.
+        constexpr bool UG = LW && C32_UG != 0;
+        // RS: the hooks of these sections raise the flag owed by raise_hot() (layer 1 in its relocated form, and the layer-0 sections between two such)
+        constexpr bool RS = ST && !ENDS && C32_XS != 0 && C32_RS != 0 && (l == 0 || XS);
+        // (test builds: every APE_C32_LATE_EVERY-th steady-state phase judges "not yet")
+        constexpr int LATE = APE_C32_LATE_EVERY;
+        const bool late = LATE > 0 && ST && (ph % (LATE > 0 ? LATE : 1)) == 0;
+        unsigned ug_src = 0u, ug_dst = 0u;
         bool staged = false;
 #ifdef APE_CLUSTER_STAMPS
         unsigned long long hk0 = 0, hk_free = 0;
@@ -673,7 +730,8 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             if (!XS && q == QF) {
                 HK_BEGIN();
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                raise_pending();
+                if constexpr (RS) raise_hot(std::integral_constant<int, 1 - l>{});
+                else raise_pending();
                 HK_END(0);
             }
             // x of the next layer-0 step: registers -> LDS (layer 0's readers of xin finished before this section's barrier), and
@@ -700,10 +758,23 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
                 }
                 if (q == QJ) {
                     HK_BEGIN();
-                    go = pre && __all((int)(peek >= (unsigned)tn)) != 0;
+                    go = pre && !late && __all((int)(peek >= (unsigned)tn)) != 0;
+                    if constexpr (UG) {
+                        ug_src = hx_base(ln, (tn - 1) & 1) + wave_kib;
+                        // (hb0[parity], counted back from the own gather's LDS base hb1 = hb0 + 2 sets, which hipcc holds in a scalar anyway:
+                        //  `hb0_lds + wave_kib` beside it was one scalar more than the section has)
+                        ug_dst = (hb1_lds + wave_kib) - (unsigned)((2 - ((tn - 1) & 1)) * SET_BYTES);
+                        asm volatile("" : "+s"(ug_src));
+                    }
                     HK_END(2);
                 }
-                if (q >= QJ && q < QJ + NDMA && go) {
+                if constexpr (UG) {
+                    if (q >= QJ && q < QJ + NDMA) {
+                        HK_BEGIN();
+                        dma_1k<true>(ug_dst, dma_voff, hx_desc, ug_src, (q - QJ) * 4096);
+                        HK_END(3);
+                    }
+                } else if (q >= QJ && q < QJ + NDMA && go) {
                     HK_BEGIN();
                     issue_piece(HOT, ln, tn - 1, q - QJ);
                     HK_END(3);
@@ -761,12 +832,18 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
                     C32_WAIT_T0();
                     look_landed();
                     C32_WAIT_T1(0);
-                    raise_pending();
+                    if constexpr (RS) raise_hot(std::integral_constant<int, 1 - l>{});
+                    else raise_pending();
                     pk = *look_mine;
-                    got1 = __all((int)(pk >= (unsigned)t)) != 0;
+                    got1 = !late && __all((int)(pk >= (unsigned)t)) != 0;
+                    // (UG: the own gather's source base, once; the judge above decides only whether the wait between the spans trusts the copy)
+                    unsigned own_src = hx_base(l, (t - 1) & 1) + wave_kib;
+                    if constexpr (UG) asm volatile("" : "+s"(own_src));
                     span16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) {
                         mid(q);
-                        if (q < NDMA && got1) issue_piece(HOT, l, t - 1, q);
+                        if constexpr (UG) {
+                            if (q < NDMA) dma_1k<true>(hb1_lds + wave_kib, dma_voff, hx_desc, own_src, q * 4096);
+                        } else if (q < NDMA && got1) issue_piece(HOT, l, t - 1, q);
                     });
                 } else
                 span16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) {
@@ -778,7 +855,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
                         C32_WAIT_T1(0);
                         pk = *look_mine;
                     }
-                    if (q == QO + 4) got1 = __all((int)(pk >= (unsigned)t)) != 0;
+                    if (q == QO + 4) got1 = !late && __all((int)(pk >= (unsigned)t)) != 0;
                     if (q >= QO + 4 && q < QO + 4 + NDMA && got1) issue_piece(HOT, l, t - 1, q - (QO + 4));
                     if constexpr (!ST) {
                         if (q == QO2 && !got1) look_issue(look_lds, look_voff, fl_desc, fl_off + (unsigned)(l * NFL * sizeof(unsigned)));
@@ -833,6 +910,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             const unsigned long long c3 = ST ? now() : 0ull;
             if (ST) { dgc[l][0] += c1 - c0; dgc[l][1] += c2 - c1; dgc[l][2] += c3 - c2; }
 #endif
+            if constexpr (ST && !ENDS) asm volatile("; c32 steady section, layer %0: end" :: "i"(l));
             mfma_drain(acc);
             cell_update(acc, l, cst[l], hnew);
         }
@@ -868,7 +946,11 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             else __builtin_amdgcn_raw_buffer_store_b128(hv, hx_rsrc, off, 0, 16 /* sc1: write-through */);
             if (active) {
                 pend_idx = l * NFL + member * 4 + wave;
-                pend_epoch = (unsigned)(t + 1);
+                // (long windows: the wave-uniform epoch goes to its vector register HERE, outside any MFMA stream, for raise_hot())
+                if constexpr (EV) {
+                    pend_epoch_v = (unsigned)(t + 1);
+                    asm volatile("" : "+v"(pend_epoch_v));
+                } else pend_epoch = (unsigned)(t + 1);
             }
         }
 #ifdef APE_CLUSTER_STAMPS
@@ -921,7 +1003,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         bar();
         if (pend_idx >= 0) {
             if (wave == 0 && lane < 4)
-                __hip_atomic_store(flags_of + (pend_idx - wave) + lane, pend_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_store(flags_of + (pend_idx - wave) + lane, EV ? pend_epoch_v : pend_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             pend_idx = -1;
         }
         if (!prefetched) {
