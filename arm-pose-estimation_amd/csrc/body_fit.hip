@@ -16,24 +16,24 @@
 //
 // Sums: no atomics and no shuffles.  A wave's 64 x 46 terms are transposed through LDS in two halves (27 + 19 columns, stride 27): lane c
 // adds column c over the wave's frames in frame order and cuts at recording boundaries (a wave-uniform ballot mask); across the four
-// waves in wave order, across workgroups in the order of ape_body_sums_acc_kernel: the same inputs give the same bits.  float64 with
-// separate roundings for a * b + c, like the numpy statement (score.py): contraction is off in this file and in the header it includes.
+// waves in wave order, across workgroups in the order of ape_body_sums_acc_kernel: the same inputs give the same bits.  The helpers the
+// scoring kernels share are score_device.h's, the staging slots and argument checks score_host.h's.  float64 with separate roundings
+// for a * b + c, like the numpy statement (score.py): contraction is off in this file.
 #include "ape_internal.h"
 #include "../../include/ape_hip.h"
 #include "bank_host.h"
+#include "score_host.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <vector>
 
 #pragma clang fp contract(off)
-#include "body_fit_device.h"
+#include "score_device.h"
 
 namespace {
 
-using namespace ape_bodydev;
+using namespace ape_scoredev;
 
 constexpr int BF_BLOCK = 256, BF_WAVES = BF_BLOCK / 64;
 constexpr int ACCW = APE_BODY_ACC_WIDTH;
@@ -68,42 +68,6 @@ __device__ __forceinline__ void mat_atb(const double* x, const double* y, double
 __device__ __forceinline__ void mat_atv(const double* x, const double* t, double* out) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) out[a] = x[a] * t[0] + x[3 + a] * t[1] + x[6 + a] * t[2];
-}
-
-// Column c0 + lane (lane < nc) of the wave's terms tb[frame * BF_TSTRIDE + lane], summed in frame order per run of one recording.
-// A run that continues the previous wave's last recording goes to wf[c0 + lane]; the wave's last run is returned in `held` when a
-// following wave may continue it (*holds, wave-uniform); every other run is a complete (workgroup, recording) pair and goes to its
-// partial record.  rec: the lane's recording (R: past F); bmask: bit i set iff frame i > 0 starts a run.
-__device__ __forceinline__ void sum_columns(const double* tb, int nc, int c0, int rec, unsigned long long bmask, int lane, int wave, int R,
-                                            int prev_last, double* wf, double* part_row0, size_t rec_step, double* held, bool* holds, int* held_rec) {
-    int a = 0;
-    while (a < 64) {                                    // (uniform)
-        const int b = bmask ? __ffsll((long long)bmask) - 1 : 64;
-        bmask &= bmask - 1;
-        const int r = __shfl(rec, a, 64);
-        if (r < R) {
-            double s = 0.0;
-            if (lane < nc) {
-                const double* src = tb + lane;
-                int i = a;
-                for (; i + 8 <= b; i += 8) {            // eight loads in flight, added in frame order
-                    const double x0 = src[(i + 0) * BF_TSTRIDE], x1 = src[(i + 1) * BF_TSTRIDE], x2 = src[(i + 2) * BF_TSTRIDE],
-                                 x3 = src[(i + 3) * BF_TSTRIDE], x4 = src[(i + 4) * BF_TSTRIDE], x5 = src[(i + 5) * BF_TSTRIDE],
-                                 x6 = src[(i + 6) * BF_TSTRIDE], x7 = src[(i + 7) * BF_TSTRIDE];
-                    s = (((((((s + x0) + x1) + x2) + x3) + x4) + x5) + x6) + x7;
-                }
-                for (; i < b; ++i) s = s + src[i * BF_TSTRIDE];
-            }
-            if (a == 0 && wave > 0 && prev_last == r) {
-                if (lane < nc) wf[c0 + lane] = s;
-            } else if (b == 64 && wave + 1 < BF_WAVES) {
-                *held = s; *holds = true; *held_rec = r;
-            } else if (lane < nc) {
-                part_row0[(size_t)r * rec_step + c0 + lane] = s;
-            }
-        }
-        a = b;
-    }
 }
 
 // the three matrices Rm[0:9], Rm[9:18], Rm[18:27] of the lower-arm, upper-arm and hips quaternions at q, q + 4 (and q + 8 with hips; the
@@ -157,7 +121,11 @@ __global__ __launch_bounds__(BF_BLOCK) void ape_body_sums_kernel(const BodyParam
 #pragma unroll
         for (int c = 0; c < 21; ++c) t[c] = (tv && c < tw) ? lds[lane * tls + c] : 0.0;
         __syncthreads();
-        if (tv) truth_pose<KIND>(t, tw, p.layout, poses + (size_t)(r0 + lane - wlo) * POSE);
+        // Target rows carry their positions: the host refuses the two layouts whose positions would be made with the body being fitted,
+        // so the layout of a target row is stated here, and the body truth_pose takes is nine zeros: in that layout it reaches no pose value
+        const int tl = KIND == APE_TRUTH_TARGETS ? (int)APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS : p.layout;
+        const double no_body[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (tv) truth_pose<KIND>(t, tw, tl, no_body, poses + (size_t)(r0 + lane - wlo) * POSE);
     }
 
     // ---- APE_BODY_ROT_MSG: the message's three matrices and their products, formed once and held over the lags ----
@@ -220,12 +188,12 @@ __global__ __launch_bounds__(BF_BLOCK) void ape_body_sums_kernel(const BodyParam
 #pragma unroll
         for (int c = 0; c < BF_HALF_A; ++c) lds[lane * BF_TSTRIDE + c] = v[c];
         __syncthreads();
-        sum_columns(lds, BF_HALF_A, 0, rec, bmask, lane, wave, p.R, prev_last, wfirst[wave], part_row0, rec_step, &held_a, &holds, &held_rec);
+        sum_columns<BF_TSTRIDE, BF_WAVES>(lds, BF_HALF_A, 0, rec, bmask, lane, wave, p.R, prev_last, wfirst[wave], part_row0, rec_step, &held_a, &holds, &held_rec);
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < BF_HALF_B; ++c) lds[lane * BF_TSTRIDE + c] = v[BF_HALF_A + c];
         __syncthreads();
-        sum_columns(lds, BF_HALF_B, BF_HALF_A, rec, bmask, lane, wave, p.R, prev_last, wfirst[wave], part_row0, rec_step, &held_b, &holds, &held_rec);
+        sum_columns<BF_TSTRIDE, BF_WAVES>(lds, BF_HALF_B, BF_HALF_A, rec, bmask, lane, wave, p.R, prev_last, wfirst[wave], part_row0, rec_step, &held_b, &holds, &held_rec);
         __syncthreads();                                // (every wave's leading run is in wfirst; the buffer is free for the next lag)
         // the wave whose last run starts a (workgroup, recording) pair takes the following waves' leading runs in wave order
         if (holds) {                                    // (uniform)
@@ -246,30 +214,7 @@ __global__ __launch_bounds__(BF_BLOCK) void ape_body_sums_kernel(const BodyParam
 // g, g + 4, ... in order; then the four groups in order.
 __global__ __launch_bounds__(BF_BLOCK) void ape_body_sums_acc_kernel(const double* __restrict__ part, const int* __restrict__ starts, int R, int F,
                                                                      int L, double* __restrict__ acc) {
-    __shared__ double grp[BF_BLOCK / 64][64];
-    const int r = blockIdx.x, j = blockIdx.y, c = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int s = starts[r], e = (r + 1 < R ? starts[r + 1] : F) - 1;
-    const int b0 = s / BF_BLOCK, n = e / BF_BLOCK - b0 + 1;
-    const size_t step = (size_t)L * ACCW;
-    double a = 0.0;
-    if (c < ACCW) {
-        const double* src = part + (((size_t)b0 + (size_t)r) * (size_t)L + (size_t)j) * ACCW + c;
-        int i = g;
-        for (; i + 12 < n; i += 16) {                   // four independent loads in flight, added in order
-            const double x0 = src[(size_t)i * step], x1 = src[(size_t)(i + 4) * step], x2 = src[(size_t)(i + 8) * step],
-                         x3 = src[(size_t)(i + 12) * step];
-            a = (((a + x0) + x1) + x2) + x3;
-        }
-        for (; i < n; i += 4) a = a + src[(size_t)i * step];
-    }
-    grp[g][c] = a;
-    __syncthreads();
-    if (g == 0 && c < ACCW) {
-        double o = grp[0][c];
-#pragma unroll
-        for (int k = 1; k < BF_BLOCK / 64; ++k) o = o + grp[k][c];
-        acc[((size_t)r * (size_t)L + (size_t)j) * ACCW + c] = o;
-    }
+    sums_acc<ACCW, BF_BLOCK>(part, starts, R, F, L, acc);
 }
 
 // ---- ape_rebody_rows ---------------------------------------------------------------------------------------------------------------------
@@ -329,79 +274,8 @@ __global__ __launch_bounds__(64) void ape_rebody_rows_kernel(const RebodyParams 
     }
 }
 
-#define BF_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return ape_fail(APE_ERR_HIP, "body_fit: %s failed: %s", #expr, hipGetErrorString(_e)); } while (0)
-
-// The call's staging (score.hip's scheme, this file's own slots): a pinned block the host arrays are copied into, so that they are
-// consumed when the call returns and the copy to the device needs no wait, and the device block behind it (host arrays, partial
-// records).  A slot is taken again once the event recorded behind its last call has completed; slots only grow and live as long as
-// the process: no allocation after the first call of a size.  Up to MAX_SLOTS calls in flight per device; one more waits for the oldest.
-struct Slot {
-    int device = -1;
-    void* pinned = nullptr;
-    void* dev = nullptr;
-    size_t pcap = 0, dcap = 0;
-    hipEvent_t done = nullptr;
-    bool used = false;
-    unsigned long long seq = 0;
-};
-constexpr size_t MAX_SLOTS = 8;
-std::mutex g_mu;
-std::vector<Slot*> g_slots;
-unsigned long long g_seq = 0;
-
-int take_slot(int device, size_t pbytes, size_t dbytes, Slot** out) {
-    Slot* s = nullptr;
-    size_t mine = 0;
-    for (Slot* q : g_slots) {
-        if (q->device != device) continue;
-        ++mine;
-        if (!q->used || hipEventQuery(q->done) == hipSuccess) { s = q; break; }
-    }
-    (void)hipGetLastError();                            // hipErrorNotReady of a busy slot is no error of this call
-    if (s == nullptr && mine >= MAX_SLOTS) {            // every slot in flight: wait for the oldest
-        for (Slot* q : g_slots)
-            if (q->device == device && (s == nullptr || q->seq < s->seq)) s = q;
-        BF_TRY(hipEventSynchronize(s->done));
-    }
-    if (s == nullptr) {
-        s = new Slot();
-        s->device = device;
-        const hipError_t e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            delete s;
-            return ape_fail(APE_ERR_HIP, "body_fit: hipEventCreate failed: %s", hipGetErrorString(e));
-        }
-        g_slots.push_back(s);
-    }
-    s->used = false;
-    if (s->pcap < pbytes) {
-        if (s->pinned) (void)hipHostFree(s->pinned);
-        s->pinned = nullptr; s->pcap = 0;
-        BF_TRY(hipHostMalloc(&s->pinned, pbytes, hipHostMallocDefault));
-        s->pcap = pbytes;
-    }
-    if (s->dcap < dbytes) {
-        if (s->dev) (void)hipFree(s->dev);
-        s->dev = nullptr; s->dcap = 0;
-        BF_TRY(hipMalloc(&s->dev, dbytes));
-        s->dcap = dbytes;
-    }
-    s->seq = ++g_seq;
-    *out = s;
-    return APE_OK;
-}
-
-// records the slot's event behind the launches and reports what became of them; `who` names the entry
-int finish_call(const char* who, Slot* slot, hipError_t launched, hipStream_t st) {
-    const hipError_t er = hipEventRecord(slot->done, st);  // the slot is in flight whatever became of the launches
-    slot->used = er == hipSuccess;
-    if (launched != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(launched));
-    if (er != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return ape_fail(APE_ERR_HIP, "%s: hipEventRecord failed: %s", who, hipGetErrorString(er));
-    }
-    return APE_OK;
-}
+// the staging of both entries: the host arrays in, the partial records behind them (score_host.h)
+ApeSlotPool g_pool("body_fit");
 
 template <typename TM, typename TT>
 void launch_sums_msg(const BodyParams& p, int kind, unsigned blocks, hipStream_t st) {
@@ -417,10 +291,6 @@ void launch_sums_truth(const BodyParams& p, int kind, unsigned blocks, hipStream
     else hipLaunchKernelGGL((ape_body_sums_kernel<double, TT, APE_TRUTH_EST, APE_BODY_ROT_TRUTH>), dim3(blocks), dim3(BF_BLOCK), 0, st, p);
 }
 
-bool scoring_layout(int32_t layout) {
-    return layout == APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS || layout == APE_LAYOUT_ORI_CAL_LARM_UARM || layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS;
-}
-
 }  // namespace
 
 int ape_body_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int32_t msg_dtype, const void* truth_dev, int32_t truth_kind,
@@ -431,7 +301,7 @@ int ape_body_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int32
         return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown rotation source %d", who, rot_source);
     const bool from_msg = rot_source == APE_BODY_ROT_MSG;
     if ((from_msg && !msg_dev) || !truth_dev || !seg_starts_host || !acc_dev) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (!scoring_layout(layout)) return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to fit", who, layout);
+    if (!ape_scoring_layout(layout)) return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to fit", who, layout);
     if (truth_kind != APE_TRUTH_TARGETS && truth_kind != APE_TRUTH_EST) return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown truth kind %d", who, truth_kind);
     if (truth_kind == APE_TRUTH_TARGETS && layout != APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS)
         return ape_fail(APE_ERR_INVALID_ARG, "%s: target truth of layout %d: its positions would be made with the body being fitted (give est rows)",
@@ -441,39 +311,32 @@ int ape_body_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int32
     if (int rc = ape_check_segments(who, F, seg_starts_host, R)) return rc;
     if (msg_dev && msg_stride < 25) return ape_fail(APE_ERR_INVALID_ARG, "%s: msg_stride %d below 25", who, msg_stride);
     if (skip < 0) return ape_fail(APE_ERR_INVALID_ARG, "%s: skip %d is negative", who, skip);
-    if (lag_min > lag_max) return ape_fail(APE_ERR_INVALID_ARG, "%s: lag_min %d above lag_max %d", who, lag_min, lag_max);
-    const long long span = (long long)lag_max - (long long)lag_min + 1;
-    if (span > APE_SCORE_MAX_LAGS) return ape_fail(APE_ERR_INVALID_ARG, "%s: %lld lags in the sweep, at most %d", who, span, APE_SCORE_MAX_LAGS);
-    if (!from_msg && (lag_min != 0 || lag_max != 0))
-        return ape_fail(APE_ERR_INVALID_ARG, "%s: rotations from the truth: the sweep must be the single lag 0, got %d .. %d", who, lag_min, lag_max);
-    if (!from_msg && rec_lag_host) return ape_fail(APE_ERR_INVALID_ARG, "%s: rotations from the truth: rec_lag_host must be NULL", who);
-    const int L = (int)span;
-    long long top = lag_max, bottom = lag_min;          // the largest and the smallest lag of any pair
-    for (int r = 0; r < R; ++r) {
-        const long long o = rec_lag_host ? rec_lag_host[r] : 0, lo = o + lag_min, hi = o + lag_max;
-        if (lo < -APE_SCORE_MAX_LAG || lo > APE_SCORE_MAX_LAG || hi < -APE_SCORE_MAX_LAG || hi > APE_SCORE_MAX_LAG)
-            return ape_fail(APE_ERR_INVALID_ARG, "%s: recording %d: lags %lld .. %lld, |lag| is at most %d", who, r, lo, hi, APE_SCORE_MAX_LAG);
-        top = r == 0 || hi > top ? hi : top;
-        bottom = r == 0 || lo < bottom ? lo : bottom;
+    int L = 0, back = 0, fwd = 0;
+    if (!from_msg) {                                    // (the sweep without recordings first: its shape is judged before this source's rule)
+        if (int rc = ape_check_lag_sweep(who, lag_min, lag_max, nullptr, 0, &L, &back, &fwd)) return rc;
+        if (lag_min != 0 || lag_max != 0)
+            return ape_fail(APE_ERR_INVALID_ARG, "%s: rotations from the truth: the sweep must be the single lag 0, got %d .. %d", who, lag_min, lag_max);
+        if (rec_lag_host) return ape_fail(APE_ERR_INVALID_ARG, "%s: rotations from the truth: rec_lag_host must be NULL", who);
     }
+    if (int rc = ape_check_lag_sweep(who, lag_min, lag_max, rec_lag_host, R, &L, &back, &fwd)) return rc;
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = ape_check_not_capturing(st, who, "host arrays are staged per call")) return rc;
     int device = 0;
-    BF_TRY(hipGetDevice(&device));
+    APE_SCORE_TRY(g_pool.prefix, hipGetDevice(&device));
 
     const unsigned blocks = (unsigned)(((long long)F + BF_BLOCK - 1) / BF_BLOCK);
     const size_t starts_bytes = (((size_t)R * sizeof(int)) + 7) & ~(size_t)7;       // starts, then the offsets
     const size_t host_bytes = 2 * starts_bytes;
     const size_t part_bytes = ((size_t)blocks + (size_t)R) * (size_t)L * ACCW * sizeof(double);
 
-    std::lock_guard<std::mutex> lock(g_mu);
-    Slot* slot = nullptr;
-    if (int rc = take_slot(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
+    std::lock_guard<std::mutex> lock(g_pool.mu);
+    ApeSlot* slot = nullptr;
+    if (int rc = g_pool.take(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
     char* pin = static_cast<char*>(slot->pinned);
     memcpy(pin, seg_starts_host, (size_t)R * sizeof(int));
     if (rec_lag_host) memcpy(pin + starts_bytes, rec_lag_host, (size_t)R * sizeof(int));
     else memset(pin + starts_bytes, 0, (size_t)R * sizeof(int));
-    BF_TRY(hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
+    APE_SCORE_TRY(g_pool.prefix, hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
 
     BodyParams p{};
     char* dev = static_cast<char*>(slot->dev);
@@ -483,11 +346,9 @@ int ape_body_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int32
     p.part = reinterpret_cast<double*>(dev + host_bytes);
     p.msg_stride = msg_stride;
     p.F = F; p.R = R; p.skip = skip; p.layout = layout;
-    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
-    p.truth_w = truth_kind == APE_TRUTH_TARGETS ? 20 : (hips ? 21 : 14);
+    p.truth_w = ape_truth_width(layout, truth_kind);
     p.lag_min = lag_min; p.L = L;
-    p.back = top > 0 ? (int)top : 0;
-    p.fwd = bottom < 0 ? (int)-bottom : 0;
+    p.back = back; p.fwd = fwd;
 
     if (!from_msg) {
         if (truth_dtype == APE_F32) launch_sums_truth<float>(p, truth_kind, blocks, st);
@@ -501,14 +362,14 @@ int ape_body_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int32
         hipLaunchKernelGGL(ape_body_sums_acc_kernel, dim3((unsigned)R, (unsigned)L), dim3(BF_BLOCK), 0, st, p.part, p.starts, R, F, L, acc_dev);
         e = hipGetLastError();
     }
-    return finish_call(who, slot, e, st);
+    return g_pool.finish(who, slot, e, st);
 }
 
 int ape_rebody_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, int32_t msg_dtype, int32_t F, const int32_t* seg_starts_host,
                     int32_t R, const double* bodies_host, int32_t n_bodies, void* out_dev, int32_t out_dtype, void* stream) {
     const char* who = "rebody_rows";
     if (!msg_dev || !seg_starts_host || !bodies_host || !out_dev) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (!scoring_layout(layout)) return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to rebuild", who, layout);
+    if (!ape_scoring_layout(layout)) return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to rebuild", who, layout);
     if (layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS)
         return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d: its positions are predicted, not made from a body", who, layout);
     if ((msg_dtype != APE_F32 && msg_dtype != APE_F64) || (out_dtype != APE_F32 && out_dtype != APE_F64))
@@ -520,19 +381,19 @@ int ape_rebody_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, int
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = ape_check_not_capturing(st, who, "host arrays are staged per call")) return rc;
     int device = 0;
-    BF_TRY(hipGetDevice(&device));
+    APE_SCORE_TRY(g_pool.prefix, hipGetDevice(&device));
 
     const unsigned blocks = (unsigned)(((long long)F + 63) / 64);
     const size_t bodies_bytes = (size_t)n_bodies * 9 * sizeof(double);              // the bodies, then the starts
     const size_t host_bytes = bodies_bytes + (size_t)R * sizeof(int);
 
-    std::lock_guard<std::mutex> lock(g_mu);
-    Slot* slot = nullptr;
-    if (int rc = take_slot(device, host_bytes, host_bytes, &slot)) return rc;
+    std::lock_guard<std::mutex> lock(g_pool.mu);
+    ApeSlot* slot = nullptr;
+    if (int rc = g_pool.take(device, host_bytes, host_bytes, &slot)) return rc;
     char* pin = static_cast<char*>(slot->pinned);
     memcpy(pin, bodies_host, bodies_bytes);
     memcpy(pin + bodies_bytes, seg_starts_host, (size_t)R * sizeof(int));
-    BF_TRY(hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
+    APE_SCORE_TRY(g_pool.prefix, hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
 
     RebodyParams p{};
     char* dev = static_cast<char*>(slot->dev);
@@ -544,5 +405,5 @@ int ape_rebody_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, int
     p.hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM ? 1 : 0;
     if (msg_dtype == APE_F32) hipLaunchKernelGGL(ape_rebody_rows_kernel<float>, dim3(blocks), dim3(64), 0, st, p);
     else hipLaunchKernelGGL(ape_rebody_rows_kernel<double>, dim3(blocks), dim3(64), 0, st, p);
-    return finish_call(who, slot, hipGetLastError(), st);
+    return g_pool.finish(who, slot, hipGetLastError(), st);
 }

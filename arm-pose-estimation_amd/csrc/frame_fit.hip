@@ -17,35 +17,33 @@
 // the walk has no divergence); across the four waves in wave order, across workgroups in the order of ape_frame_sums_acc_kernel: the same
 // inputs give the same bits.  Loads are staged as in score.hip (lanes run along the rows); every staged stride is odd.
 //
-// stage_rows, truth_pose, truth_six_drr_to_quat, find_rec and the staging slots are copies of score.hip's: that file's object code stays
-// what it was.  float64 with separate roundings for a * b + c, like the numpy statement (score.py): contraction is off in this file.
+// The helpers the scoring kernels share (row staging, truth row -> pose, the column sums, the ordered sum of the partial records) are
+// score_device.h's, the staging slots and argument checks score_host.h's.
+// float64 with separate roundings for a * b + c, like the numpy statement (score.py): contraction is off in this file.
 #include "ape_internal.h"
 #include "../../include/ape_hip.h"
-#include "fk_device.h"
 #include "bank_host.h"
+#include "score_host.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <vector>
 
 #pragma clang fp contract(off)
+#include "score_device.h"
 
 namespace {
 
-using namespace ape_fkdev;
+using namespace ape_scoredev;
 
 constexpr int FF_BLOCK = 256, FF_WAVES = FF_BLOCK / 64;
-constexpr int FF_STAGE_COLS = 25;                       // widest staged input row (the message)
 constexpr int ACCW = APE_FRAME_ACC_WIDTH;
 constexpr int FF_HALF_A = 27, FF_HALF_B = ACCW - FF_HALF_A;   // the rotation blocks; the position blocks, the norms and the counts
 constexpr int FF_TSTRIDE = 27;                          // stride of a frame's terms in the transposition buffer; odd
-constexpr int FF_POSE = 19;                             // 18 pose values + the usable flag; odd
 constexpr int FF_WINDOW = FF_BLOCK + 2 * APE_SCORE_MAX_LAG;
 constexpr int RR_OUT_STRIDE = 25 + APE_SPREAD_WIDTH + 1;      // LDS stride of a rotated row (46 values at most); odd
 
-static_assert(FF_HALF_B <= FF_TSTRIDE && FF_STAGE_COLS <= FF_TSTRIDE, "the transposition buffer also stages the input rows");
+static_assert(FF_HALF_B <= FF_TSTRIDE && STAGE_COLS <= FF_TSTRIDE, "the transposition buffer also stages the input rows");
 
 struct FrameParams {
     const void* msg;
@@ -60,111 +58,6 @@ struct FrameParams {
     int back, fwd;                                      // how far below / above its own rows a workgroup's truth window reaches, each <= 128
 };
 
-// rows row0 .. row0 + nrows - 1 (nrows >= 1), columns 0 .. ncols - 1 of src -> lds[r * lstride + c] as float64.  Every lane loads in
-// every round (the index is clamped, a partial wave reads its last element again): no branch between the loads
-template <typename T>
-__device__ __forceinline__ void stage_rows(double* lds, const T* src, long long stride, int ncols, int lstride, long long row0, int nrows,
-                                           int lane) {
-    const int last = nrows * ncols - 1;
-#pragma unroll
-    for (int it = 0; it < FF_STAGE_COLS; ++it) {
-        if (it < ncols) {                               // uniform
-            int idx = it * 64 + lane;
-            idx = idx < last ? idx : last;
-            const int r = idx / ncols, c = idx - r * ncols;
-            lds[r * lstride + c] = (double)src[(row0 + r) * stride + c];
-        }
-    }
-}
-
-__device__ __forceinline__ bool fin(double v) { return isfinite(v); }
-
-__device__ __forceinline__ int find_rec(const int* starts, int R, long long f) {      // the last start <= f
-    int lo = 0, hi = R - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((long long)starts[mid] <= f) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// (score.hip: truth_six_drr_to_quat) the closed form refined by two power steps on K + I to the eigenvector the reference takes
-__device__ inline Quat truth_six_drr_to_quat(const double* s) {
-    const Quat q0 = six_drr_to_quat(s);
-    const double a1x = s[0], a1y = s[2], a1z = s[4], a2x = s[1], a2y = s[3], a2z = s[5];
-    const double n1 = sqrt(a1x * a1x + a1y * a1y + a1z * a1z);
-    const double m00 = a1x / n1, m10 = a1y / n1, m20 = a1z / n1;
-    const double d = m00 * a2x + m10 * a2y + m20 * a2z;
-    const double ux = a2x - d * m00, uy = a2y - d * m10, uz = a2z - d * m20;
-    const double n2 = sqrt(ux * ux + uy * uy + uz * uz);
-    const double m01 = ux / n2, m11 = uy / n2, m21 = uz / n2;
-    const double m02 = m10 * m21 - m20 * m11, m12 = m20 * m01 - m00 * m21, m22 = m00 * m11 - m10 * m01;
-    const double k00 = m00 - m11 - m22 + 1.0, k11 = m11 - m00 - m22 + 1.0, k22 = m22 - m00 - m11 + 1.0, k33 = m00 + m11 + m22 + 1.0;
-    const double k01 = m01 + m10, k02 = m02 + m20, k12 = m12 + m21, k03 = m21 - m12, k13 = m02 - m20, k23 = m10 - m01;
-    double x = q0.x, y = q0.y, z = q0.z, w = q0.w;
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const double nx = k00 * x + k01 * y + k02 * z + k03 * w, ny = k01 * x + k11 * y + k12 * z + k13 * w;
-        const double nz = k02 * x + k12 * y + k22 * z + k23 * w, nw = k03 * x + k13 * y + k23 * z + k33 * w;
-        const double nn = sqrt(nx * nx + ny * ny + nz * nz + nw * nw);
-        x = nx / nn; y = ny / nn; z = nz / nn; w = nw / nn;
-    }
-    return w < 0.0 ? Quat{-w, -x, -y, -z} : Quat{w, x, y, z};
-}
-
-// (score.hip: truth_pose) one truth row -> pose[0:18] = hand, elbow, lower-arm, upper-arm and hips quaternion, pose[18] = 1.0 iff every
-// value used is finite
-template <int KIND>
-__device__ __forceinline__ void truth_pose(const double* t, int tw, int layout, const double* body, double* pose) {
-    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
-    Vec3 t_hand, t_elbow;
-    Quat t_lq, t_uq, t_hq{1.0, 0.0, 0.0, 0.0};
-    bool ok = true;
-    if constexpr (KIND == APE_TRUTH_TARGETS) {
-#pragma unroll
-        for (int c = 0; c < 20; ++c)
-            if (c < tw) ok = ok && fin(t[c]);
-        const Vec3 larm_vec{body[0], body[1], body[2]}, uarm_vec{body[3], body[4], body[5]}, uarm_orig{body[6], body[7], body[8]};
-        if (layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS) {
-            t_lq = truth_six_drr_to_quat(t + 3); t_uq = truth_six_drr_to_quat(t + 12); t_hq = hips_quat(t[18], t[19]);
-            t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[9], t[10], t[11]};
-        } else {
-            t_lq = truth_six_drr_to_quat(t); t_uq = truth_six_drr_to_quat(t + 6);
-            Vec3 uo = uarm_orig;
-            if (hips) { t_hq = hips_quat(t[12], t[13]); uo = qrot(t_hq, uarm_orig); }
-            const Vec3 r1 = qrot(t_uq, uarm_vec);
-            t_elbow = Vec3{r1.x + uo.x, r1.y + uo.y, r1.z + uo.z};
-            const Vec3 r2 = qrot(t_lq, larm_vec);
-            t_hand = Vec3{r2.x + t_elbow.x, r2.y + t_elbow.y, r2.z + t_elbow.z};
-        }
-    } else {
-        const int ql = hips ? 9 : 6, qu = hips ? 13 : 10;
-        t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[3], t[4], t[5]};
-        t_lq = Quat{t[ql], t[ql + 1], t[ql + 2], t[ql + 3]};
-        t_uq = Quat{t[qu], t[qu + 1], t[qu + 2], t[qu + 3]};
-        if (hips) t_hq = Quat{t[17], t[18], t[19], t[20]};
-    }
-    ok = ok && fin(t_hand.x) && fin(t_hand.y) && fin(t_hand.z) && fin(t_elbow.x) && fin(t_elbow.y) && fin(t_elbow.z) &&
-         fin(t_lq.w) && fin(t_lq.x) && fin(t_lq.y) && fin(t_lq.z) && fin(t_uq.w) && fin(t_uq.x) && fin(t_uq.y) && fin(t_uq.z) &&
-         fin(t_hq.w) && fin(t_hq.x) && fin(t_hq.y) && fin(t_hq.z);
-    pose[0] = t_hand.x; pose[1] = t_hand.y; pose[2] = t_hand.z; pose[3] = t_elbow.x; pose[4] = t_elbow.y; pose[5] = t_elbow.z;
-    pose[6] = t_lq.w; pose[7] = t_lq.x; pose[8] = t_lq.y; pose[9] = t_lq.z;
-    pose[10] = t_uq.w; pose[11] = t_uq.x; pose[12] = t_uq.y; pose[13] = t_uq.z;
-    pose[14] = t_hq.w; pose[15] = t_hq.x; pose[16] = t_hq.y; pose[17] = t_hq.z;
-    pose[18] = ok ? 1.0 : 0.0;
-}
-
-// the rotation a quaternion [w, x, y, z] stands for, row-major, with the factor 2 / |q|^2: an unnormalised quaternion gives the same
-// matrix as its unit form, the zero quaternion gives non-finite entries (score.py: _quat_matrix states the same operations)
-__device__ __forceinline__ void quat_matrix(const double* q, double* m) {
-    const double w = q[0], x = q[1], y = q[2], z = q[3];
-    const double s = 2.0 / (w * w + x * x + y * y + z * z);
-    const double xx = x * x, yy = y * y, zz = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-    m[0] = 1.0 - s * (yy + zz); m[1] = s * (xy - wz);       m[2] = s * (xz + wy);
-    m[3] = s * (xy + wz);       m[4] = 1.0 - s * (xx + zz); m[5] = s * (yz - wx);
-    m[6] = s * (xz - wy);       m[7] = s * (yz + wx);       m[8] = 1.0 - s * (xx + yy);
-}
-
 // out[3 a + b] = sum_k t[3 a + k] e[3 b + k]: T E', row-major
 __device__ __forceinline__ void mat_abt(const double* t, const double* e, double* out) {
 #pragma unroll
@@ -173,46 +66,10 @@ __device__ __forceinline__ void mat_abt(const double* t, const double* e, double
         for (int b = 0; b < 3; ++b) out[3 * a + b] = t[3 * a] * e[3 * b] + t[3 * a + 1] * e[3 * b + 1] + t[3 * a + 2] * e[3 * b + 2];
 }
 
-// Column c0 + lane (lane < nc) of the wave's terms tb[frame * FF_TSTRIDE + lane], summed in frame order per run of one recording.
-// A run that continues the previous wave's last recording goes to wf[c0 + lane]; the wave's last run is returned in `held` when a
-// following wave may continue it (*holds, wave-uniform); every other run is a complete (workgroup, recording) pair and goes to its
-// partial record.  rec: the lane's recording (R: past F); bmask: bit i set iff frame i > 0 starts a run.
-__device__ __forceinline__ void sum_columns(const double* tb, int nc, int c0, int rec, unsigned long long bmask, int lane, int wave, int R,
-                                            int prev_last, double* wf, double* part_row0, size_t rec_step, double* held, bool* holds, int* held_rec) {
-    int a = 0;
-    while (a < 64) {                                    // (uniform)
-        const int b = bmask ? __ffsll((long long)bmask) - 1 : 64;
-        bmask &= bmask - 1;
-        const int r = __shfl(rec, a, 64);
-        if (r < R) {
-            double s = 0.0;
-            if (lane < nc) {
-                const double* src = tb + lane;
-                int i = a;
-                for (; i + 8 <= b; i += 8) {            // eight loads in flight, added in frame order
-                    const double x0 = src[(i + 0) * FF_TSTRIDE], x1 = src[(i + 1) * FF_TSTRIDE], x2 = src[(i + 2) * FF_TSTRIDE],
-                                 x3 = src[(i + 3) * FF_TSTRIDE], x4 = src[(i + 4) * FF_TSTRIDE], x5 = src[(i + 5) * FF_TSTRIDE],
-                                 x6 = src[(i + 6) * FF_TSTRIDE], x7 = src[(i + 7) * FF_TSTRIDE];
-                    s = (((((((s + x0) + x1) + x2) + x3) + x4) + x5) + x6) + x7;
-                }
-                for (; i < b; ++i) s = s + src[i * FF_TSTRIDE];
-            }
-            if (a == 0 && wave > 0 && prev_last == r) {
-                if (lane < nc) wf[c0 + lane] = s;
-            } else if (b == 64 && wave + 1 < FF_WAVES) {
-                *held = s; *holds = true; *held_rec = r;
-            } else if (lane < nc) {
-                part_row0[(size_t)r * rec_step + c0 + lane] = s;
-            }
-        }
-        a = b;
-    }
-}
-
 template <typename TM, typename TT, int KIND>
 __global__ __launch_bounds__(FF_BLOCK) void ape_frame_sums_kernel(const FrameParams p) {
     __shared__ double tbuf[FF_WAVES][64 * FF_TSTRIDE];  // input staging, then the transposition buffer of the wave's terms
-    __shared__ double poses[FF_WINDOW * FF_POSE];
+    __shared__ double poses[FF_WINDOW * POSE];
     __shared__ double wfirst[FF_WAVES][ACCW];
     __shared__ int wrec[FF_WAVES][2];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -250,7 +107,7 @@ __global__ __launch_bounds__(FF_BLOCK) void ape_frame_sums_kernel(const FramePar
         if (tv) {
             const long long tr = r0 + lane;
             const int trec = (KIND == APE_TRUTH_TARGETS && p.n_bodies > 1) ? find_rec(p.starts, p.R, tr) : 0;
-            truth_pose<KIND>(t, tw, p.layout, p.bodies + 9 * (size_t)trec, poses + (size_t)(tr - wlo) * FF_POSE);
+            truth_pose<KIND>(t, tw, p.layout, p.bodies + 9 * (size_t)trec, poses + (size_t)(tr - wlo) * POSE);
         }
     }
 
@@ -284,10 +141,10 @@ __global__ __launch_bounds__(FF_BLOCK) void ape_frame_sums_kernel(const FramePar
     for (int j = 0; j < p.L; ++j) {                     // (uniform)
         const long long tr = f - (l_lo + j);
         const bool ex = valid && tr >= (long long)start && tr < (long long)end;        // the pair exists: tr is inside [wlo, whi)
-        const double* ps = poses + (ex ? (size_t)(tr - wlo) : 0) * FF_POSE;
-        double t[FF_POSE];
+        const double* ps = poses + (ex ? (size_t)(tr - wlo) : 0) * POSE;
+        double t[POSE];
 #pragma unroll
-        for (int c = 0; c < FF_POSE; ++c) t[c] = ex ? ps[c] : 0.0;
+        for (int c = 0; c < POSE; ++c) t[c] = ex ? ps[c] : 0.0;
         double T[9], v[ACCW];
         quat_matrix(t + 6, T); mat_abt(T, E, v);
         quat_matrix(t + 10, T); mat_abt(T, E + 9, v + 9);
@@ -320,12 +177,12 @@ __global__ __launch_bounds__(FF_BLOCK) void ape_frame_sums_kernel(const FramePar
 #pragma unroll
         for (int c = 0; c < FF_HALF_A; ++c) lds[lane * FF_TSTRIDE + c] = v[c];
         __syncthreads();
-        sum_columns(lds, FF_HALF_A, 0, rec, bmask, lane, wave, p.R, prev_last, wfirst[wave], part_row0, rec_step, &held_a, &holds, &held_rec);
+        sum_columns<FF_TSTRIDE, FF_WAVES>(lds, FF_HALF_A, 0, rec, bmask, lane, wave, p.R, prev_last, wfirst[wave], part_row0, rec_step, &held_a, &holds, &held_rec);
         __syncthreads();
 #pragma unroll
         for (int c = 0; c < FF_HALF_B; ++c) lds[lane * FF_TSTRIDE + c] = v[FF_HALF_A + c];
         __syncthreads();
-        sum_columns(lds, FF_HALF_B, FF_HALF_A, rec, bmask, lane, wave, p.R, prev_last, wfirst[wave], part_row0, rec_step, &held_b, &holds, &held_rec);
+        sum_columns<FF_TSTRIDE, FF_WAVES>(lds, FF_HALF_B, FF_HALF_A, rec, bmask, lane, wave, p.R, prev_last, wfirst[wave], part_row0, rec_step, &held_b, &holds, &held_rec);
         __syncthreads();                                // (every wave's leading run is in wfirst; the buffer is free for the next lag)
         // the wave whose last run starts a (workgroup, recording) pair takes the following waves' leading runs in wave order
         if (holds) {                                    // (uniform)
@@ -346,30 +203,7 @@ __global__ __launch_bounds__(FF_BLOCK) void ape_frame_sums_kernel(const FramePar
 // g, g + 4, ... in order; then the four groups in order.
 __global__ __launch_bounds__(FF_BLOCK) void ape_frame_sums_acc_kernel(const double* __restrict__ part, const int* __restrict__ starts, int R, int F,
                                                                       int L, double* __restrict__ acc) {
-    __shared__ double grp[FF_BLOCK / 64][64];
-    const int r = blockIdx.x, j = blockIdx.y, c = threadIdx.x & 63, g = threadIdx.x >> 6;
-    const int s = starts[r], e = (r + 1 < R ? starts[r + 1] : F) - 1;
-    const int b0 = s / FF_BLOCK, n = e / FF_BLOCK - b0 + 1;
-    const size_t step = (size_t)L * ACCW;
-    double a = 0.0;
-    if (c < ACCW) {
-        const double* src = part + (((size_t)b0 + (size_t)r) * (size_t)L + (size_t)j) * ACCW + c;
-        int i = g;
-        for (; i + 12 < n; i += 16) {                   // four independent loads in flight, added in order
-            const double x0 = src[(size_t)i * step], x1 = src[(size_t)(i + 4) * step], x2 = src[(size_t)(i + 8) * step],
-                         x3 = src[(size_t)(i + 12) * step];
-            a = (((a + x0) + x1) + x2) + x3;
-        }
-        for (; i < n; i += 4) a = a + src[(size_t)i * step];
-    }
-    grp[g][c] = a;
-    __syncthreads();
-    if (g == 0 && c < ACCW) {
-        double o = grp[0][c];
-#pragma unroll
-        for (int k = 1; k < FF_BLOCK / 64; ++k) o = o + grp[k][c];
-        acc[((size_t)r * (size_t)L + (size_t)j) * ACCW + c] = o;
-    }
+    sums_acc<ACCW, FF_BLOCK>(part, starts, R, F, L, acc);
 }
 
 // ---- ape_rotate_rows ---------------------------------------------------------------------------------------------------------------------
@@ -469,79 +303,8 @@ __global__ __launch_bounds__(64) void ape_rotate_rows_kernel(const RotateParams 
     }
 }
 
-#define FF_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return ape_fail(APE_ERR_HIP, "frame_fit: %s failed: %s", #expr, hipGetErrorString(_e)); } while (0)
-
-// The call's staging (score.hip's scheme, this file's own slots): a pinned block the host arrays are copied into, so that they are
-// consumed when the call returns and the copy to the device needs no wait, and the device block behind it (host arrays, partial
-// records).  A slot is taken again once the event recorded behind its last call has completed; slots only grow and live as long as
-// the process: no allocation after the first call of a size.  Up to MAX_SLOTS calls in flight per device; one more waits for the oldest.
-struct Slot {
-    int device = -1;
-    void* pinned = nullptr;
-    void* dev = nullptr;
-    size_t pcap = 0, dcap = 0;
-    hipEvent_t done = nullptr;
-    bool used = false;
-    unsigned long long seq = 0;
-};
-constexpr size_t MAX_SLOTS = 8;
-std::mutex g_mu;
-std::vector<Slot*> g_slots;
-unsigned long long g_seq = 0;
-
-int take_slot(int device, size_t pbytes, size_t dbytes, Slot** out) {
-    Slot* s = nullptr;
-    size_t mine = 0;
-    for (Slot* q : g_slots) {
-        if (q->device != device) continue;
-        ++mine;
-        if (!q->used || hipEventQuery(q->done) == hipSuccess) { s = q; break; }
-    }
-    (void)hipGetLastError();                            // hipErrorNotReady of a busy slot is no error of this call
-    if (s == nullptr && mine >= MAX_SLOTS) {            // every slot in flight: wait for the oldest
-        for (Slot* q : g_slots)
-            if (q->device == device && (s == nullptr || q->seq < s->seq)) s = q;
-        FF_TRY(hipEventSynchronize(s->done));
-    }
-    if (s == nullptr) {
-        s = new Slot();
-        s->device = device;
-        const hipError_t e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            delete s;
-            return ape_fail(APE_ERR_HIP, "frame_fit: hipEventCreate failed: %s", hipGetErrorString(e));
-        }
-        g_slots.push_back(s);
-    }
-    s->used = false;
-    if (s->pcap < pbytes) {
-        if (s->pinned) (void)hipHostFree(s->pinned);
-        s->pinned = nullptr; s->pcap = 0;
-        FF_TRY(hipHostMalloc(&s->pinned, pbytes, hipHostMallocDefault));
-        s->pcap = pbytes;
-    }
-    if (s->dcap < dbytes) {
-        if (s->dev) (void)hipFree(s->dev);
-        s->dev = nullptr; s->dcap = 0;
-        FF_TRY(hipMalloc(&s->dev, dbytes));
-        s->dcap = dbytes;
-    }
-    s->seq = ++g_seq;
-    *out = s;
-    return APE_OK;
-}
-
-// records the slot's event behind the launches and reports what became of them; `who` names the entry
-int finish_call(const char* who, Slot* slot, hipError_t launched, hipStream_t st) {
-    const hipError_t er = hipEventRecord(slot->done, st);  // the slot is in flight whatever became of the launches
-    slot->used = er == hipSuccess;
-    if (launched != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(launched));
-    if (er != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return ape_fail(APE_ERR_HIP, "%s: hipEventRecord failed: %s", who, hipGetErrorString(er));
-    }
-    return APE_OK;
-}
+// the staging of both entries: the host arrays in, the partial records behind them (score_host.h)
+ApeSlotPool g_pool("frame_fit");
 
 template <typename TM, typename TT>
 void launch_sums(const FrameParams& p, int kind, unsigned blocks, hipStream_t st) {
@@ -555,10 +318,6 @@ void launch_rotate(const RotateParams& p, unsigned blocks, hipStream_t st) {
     else hipLaunchKernelGGL((ape_rotate_rows_kernel<TM, false>), dim3(blocks), dim3(64), 0, st, p);
 }
 
-bool scoring_layout(int32_t layout) {
-    return layout == APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS || layout == APE_LAYOUT_ORI_CAL_LARM_UARM || layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS;
-}
-
 }  // namespace
 
 int ape_frame_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int32_t msg_dtype, const void* truth_dev, int32_t truth_kind,
@@ -566,7 +325,7 @@ int ape_frame_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int3
                    int32_t n_bodies, int32_t lag_min, int32_t lag_max, const int32_t* rec_lag_host, double* acc_dev, void* stream) {
     const char* who = "frame_sums";
     if (!msg_dev || !truth_dev || !seg_starts_host || !bodies_host || !acc_dev) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (!scoring_layout(layout)) return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to score", who, layout);
+    if (!ape_scoring_layout(layout)) return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to score", who, layout);
     if (truth_kind != APE_TRUTH_TARGETS && truth_kind != APE_TRUTH_EST) return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown truth kind %d", who, truth_kind);
     if ((msg_dtype != APE_F32 && msg_dtype != APE_F64) || (truth_dtype != APE_F32 && truth_dtype != APE_F64))
         return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown dtype selector", who);
@@ -574,22 +333,12 @@ int ape_frame_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int3
     if (msg_stride < 25) return ape_fail(APE_ERR_INVALID_ARG, "%s: msg_stride %d below 25", who, msg_stride);
     if (skip < 0) return ape_fail(APE_ERR_INVALID_ARG, "%s: skip %d is negative", who, skip);
     if (n_bodies != 1 && n_bodies != R) return ape_fail(APE_ERR_INVALID_ARG, "%s: n_bodies %d is neither 1 nor R = %d", who, n_bodies, R);
-    if (lag_min > lag_max) return ape_fail(APE_ERR_INVALID_ARG, "%s: lag_min %d above lag_max %d", who, lag_min, lag_max);
-    const long long span = (long long)lag_max - (long long)lag_min + 1;
-    if (span > APE_SCORE_MAX_LAGS) return ape_fail(APE_ERR_INVALID_ARG, "%s: %lld lags in the sweep, at most %d", who, span, APE_SCORE_MAX_LAGS);
-    const int L = (int)span;
-    long long top = lag_max, bottom = lag_min;          // the largest and the smallest lag of any pair
-    for (int r = 0; r < R; ++r) {
-        const long long o = rec_lag_host ? rec_lag_host[r] : 0, lo = o + lag_min, hi = o + lag_max;
-        if (lo < -APE_SCORE_MAX_LAG || lo > APE_SCORE_MAX_LAG || hi < -APE_SCORE_MAX_LAG || hi > APE_SCORE_MAX_LAG)
-            return ape_fail(APE_ERR_INVALID_ARG, "%s: recording %d: lags %lld .. %lld, |lag| is at most %d", who, r, lo, hi, APE_SCORE_MAX_LAG);
-        top = r == 0 || hi > top ? hi : top;
-        bottom = r == 0 || lo < bottom ? lo : bottom;
-    }
+    int L = 0, back = 0, fwd = 0;
+    if (int rc = ape_check_lag_sweep(who, lag_min, lag_max, rec_lag_host, R, &L, &back, &fwd)) return rc;
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = ape_check_not_capturing(st, who, "host arrays are staged per call")) return rc;
     int device = 0;
-    FF_TRY(hipGetDevice(&device));
+    APE_SCORE_TRY(g_pool.prefix, hipGetDevice(&device));
 
     const unsigned blocks = (unsigned)(((long long)F + FF_BLOCK - 1) / FF_BLOCK);
     const size_t starts_bytes = (((size_t)R * sizeof(int)) + 7) & ~(size_t)7;       // starts, then the offsets, then the bodies
@@ -597,15 +346,15 @@ int ape_frame_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int3
     const size_t host_bytes = 2 * starts_bytes + bodies_bytes;
     const size_t part_bytes = ((size_t)blocks + (size_t)R) * (size_t)L * ACCW * sizeof(double);
 
-    std::lock_guard<std::mutex> lock(g_mu);
-    Slot* slot = nullptr;
-    if (int rc = take_slot(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
+    std::lock_guard<std::mutex> lock(g_pool.mu);
+    ApeSlot* slot = nullptr;
+    if (int rc = g_pool.take(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
     char* pin = static_cast<char*>(slot->pinned);
     memcpy(pin, seg_starts_host, (size_t)R * sizeof(int));
     if (rec_lag_host) memcpy(pin + starts_bytes, rec_lag_host, (size_t)R * sizeof(int));
     else memset(pin + starts_bytes, 0, (size_t)R * sizeof(int));
     memcpy(pin + 2 * starts_bytes, bodies_host, bodies_bytes);
-    FF_TRY(hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
+    APE_SCORE_TRY(g_pool.prefix, hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
 
     FrameParams p{};
     char* dev = static_cast<char*>(slot->dev);
@@ -616,12 +365,9 @@ int ape_frame_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int3
     p.part = reinterpret_cast<double*>(dev + host_bytes);
     p.msg_stride = msg_stride;
     p.F = F; p.R = R; p.skip = skip; p.layout = layout; p.n_bodies = n_bodies;
-    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
-    if (truth_kind == APE_TRUTH_TARGETS) p.truth_w = layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS ? 20 : (hips ? 14 : 12);
-    else p.truth_w = hips ? 21 : 14;
+    p.truth_w = ape_truth_width(layout, truth_kind);
     p.lag_min = lag_min; p.L = L;
-    p.back = top > 0 ? (int)top : 0;
-    p.fwd = bottom < 0 ? (int)-bottom : 0;
+    p.back = back; p.fwd = fwd;
 
     if (msg_dtype == APE_F32 && truth_dtype == APE_F32) launch_sums<float, float>(p, truth_kind, blocks, st);
     else if (msg_dtype == APE_F32) launch_sums<float, double>(p, truth_kind, blocks, st);
@@ -632,7 +378,7 @@ int ape_frame_sums(int32_t layout, const void* msg_dev, int32_t msg_stride, int3
         hipLaunchKernelGGL(ape_frame_sums_acc_kernel, dim3((unsigned)R, (unsigned)L), dim3(FF_BLOCK), 0, st, p.part, p.starts, R, F, L, acc_dev);
         e = hipGetLastError();
     }
-    return finish_call(who, slot, e, st);
+    return g_pool.finish(who, slot, e, st);
 }
 
 int ape_rotate_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, const void* spread_dev, int32_t spread_stride, int32_t msg_dtype,
@@ -640,7 +386,7 @@ int ape_rotate_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, con
                     int32_t out_dtype, void* stream) {
     const char* who = "rotate_rows";
     if (!msg_dev || !seg_starts_host || !quats_host || !out_dev) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (!scoring_layout(layout)) return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to rotate", who, layout);
+    if (!ape_scoring_layout(layout)) return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to rotate", who, layout);
     if ((msg_dtype != APE_F32 && msg_dtype != APE_F64) || (out_dtype != APE_F32 && out_dtype != APE_F64))
         return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown dtype selector", who);
     if (int rc = ape_check_segments(who, F, seg_starts_host, R)) return rc;
@@ -658,19 +404,19 @@ int ape_rotate_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, con
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = ape_check_not_capturing(st, who, "host arrays are staged per call")) return rc;
     int device = 0;
-    FF_TRY(hipGetDevice(&device));
+    APE_SCORE_TRY(g_pool.prefix, hipGetDevice(&device));
 
     const unsigned blocks = (unsigned)(((long long)F + 63) / 64);
     const size_t quats_bytes = (size_t)n_quats * 4 * sizeof(double);                 // the quaternions, then the starts
     const size_t host_bytes = quats_bytes + (size_t)R * sizeof(int);
 
-    std::lock_guard<std::mutex> lock(g_mu);
-    Slot* slot = nullptr;
-    if (int rc = take_slot(device, host_bytes, host_bytes, &slot)) return rc;
+    std::lock_guard<std::mutex> lock(g_pool.mu);
+    ApeSlot* slot = nullptr;
+    if (int rc = g_pool.take(device, host_bytes, host_bytes, &slot)) return rc;
     char* pin = static_cast<char*>(slot->pinned);
     memcpy(pin, unit.data(), quats_bytes);
     memcpy(pin + quats_bytes, seg_starts_host, (size_t)R * sizeof(int));
-    FF_TRY(hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
+    APE_SCORE_TRY(g_pool.prefix, hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
 
     RotateParams p{};
     char* dev = static_cast<char*>(slot->dev);
@@ -681,5 +427,5 @@ int ape_rotate_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, con
     p.F = F; p.R = R; p.n_quats = n_quats; p.out_f32 = out_dtype == APE_F32 ? 1 : 0;
     if (msg_dtype == APE_F32) launch_rotate<float>(p, blocks, st);
     else launch_rotate<double>(p, blocks, st);
-    return finish_call(who, slot, hipGetLastError(), st);
+    return g_pool.finish(who, slot, hipGetLastError(), st);
 }

@@ -33,10 +33,12 @@
 #include <vector>
 
 #pragma clang fp contract(off)
+#include "score_device.h"
 
 namespace {
 
 using namespace ape_postdev;
+using ape_scoredev::find_rec;
 
 constexpr int PS_BLOCK = 256;
 constexpr int PS_FK_ROWS = 32;                          // rows per workgroup of the conversion (FK3_ROWS of fk.hip)
@@ -69,15 +71,6 @@ struct PsParams {
     short smooth[APE_POST_MAX_CONFIGS], m[APE_POST_MAX_CONFIGS];      // the configurations by falling smooth * m ...
     unsigned char idx[APE_POST_MAX_CONFIGS];                          // ... and their positions in the caller's list
 };
-
-__device__ __forceinline__ int find_rec(const int* starts, int R, int f) {             // the last start <= f
-    int lo = 0, hi = R - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if (starts[mid] <= f) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(128) void ape_post_sweep_fk_kernel(const PsFkParams p) {
     __shared__ double rot[PS_FK_ROWS][3][3];               // [row][lower arm, upper arm, shoulder origin][xyz]

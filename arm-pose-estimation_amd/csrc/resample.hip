@@ -14,27 +14,26 @@
 //
 // ape_resample_truth: one lane per output frame: the frame's recording by binary search in the starts, its query time, the last truth row
 // at or before it by binary search inside the recording's rows, the two neighbouring rows converted (est columns as given, or NN
-// targets through the float64 forward kinematics, quaternions refined as in score.hip, which keeps its own copy of these statements so
-// that its object stays what it was), positions interpolated linearly and quaternions along the arc.  The rows leave through LDS so
-// that a wave writes its 64 x 21 | 14 values as one run.
+// targets through the float64 forward kinematics with refined quaternions: score_device.h's targets_to_pose, which the scoring
+// kernels use), positions interpolated linearly and quaternions along the arc.  The rows leave through LDS so that a wave writes its
+// 64 x 21 | 14 values as one run.
 //
 // float64 with separate roundings for a * b + c, like the numpy statements (score.py): contraction is off in this file.
 #include "ape_internal.h"
 #include "../../include/ape_hip.h"
-#include "fk_device.h"
 #include "bank_host.h"
+#include "score_host.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <vector>
 
 #pragma clang fp contract(off)
+#include "score_device.h"
 
 namespace {
 
-using namespace ape_fkdev;
+using namespace ape_scoredev;
 
 // ---- ape_frame_times ------------------------------------------------------------------------------------------------------------------------
 constexpr int FT_BLOCK = 256, FT_WAVES = FT_BLOCK / 64, FT_PER = 4, FT_TILE = FT_BLOCK * FT_PER;
@@ -50,15 +49,6 @@ struct TimesParams {
     long long stride;
     int F, R, big_endian;
 };
-
-__device__ __forceinline__ int find_rec(const int* starts, int R, long long f) {      // the last start <= f
-    int lo = 0, hi = R - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((long long)starts[mid] <= f) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
 
 // (head, sum) of a piece followed by the piece (oh, os): a head discards what came before it
 __device__ __forceinline__ void seg_append(bool& head, double& sum, bool oh, double os) {
@@ -231,38 +221,11 @@ struct ResampleParams {
     int F, Ft, R, layout, n_bodies, truth_w, out_w, out_f32;
 };
 
-__device__ __forceinline__ bool fin(double v) { return isfinite(v); }
-
-// The truth's 6D rotation -> unit quaternion in the reference's sense: the closed form refined by two power steps on K + I towards the
-// eigenvector rot_mat_to_quat takes (score.hip states why; this is its statement, kept here so that score.o keeps its code)
-__device__ inline Quat truth_six_drr_to_quat(const double* s) {
-    const Quat q0 = six_drr_to_quat(s);
-    const double a1x = s[0], a1y = s[2], a1z = s[4], a2x = s[1], a2y = s[3], a2z = s[5];
-    const double n1 = sqrt(a1x * a1x + a1y * a1y + a1z * a1z);
-    const double m00 = a1x / n1, m10 = a1y / n1, m20 = a1z / n1;
-    const double d = m00 * a2x + m10 * a2y + m20 * a2z;
-    const double ux = a2x - d * m00, uy = a2y - d * m10, uz = a2z - d * m20;
-    const double n2 = sqrt(ux * ux + uy * uy + uz * uz);
-    const double m01 = ux / n2, m11 = uy / n2, m21 = uz / n2;
-    const double m02 = m10 * m21 - m20 * m11, m12 = m20 * m01 - m00 * m21, m22 = m00 * m11 - m10 * m01;
-    const double k00 = m00 - m11 - m22 + 1.0, k11 = m11 - m00 - m22 + 1.0, k22 = m22 - m00 - m11 + 1.0, k33 = m00 + m11 + m22 + 1.0;
-    const double k01 = m01 + m10, k02 = m02 + m20, k12 = m12 + m21, k03 = m21 - m12, k13 = m02 - m20, k23 = m10 - m01;
-    double x = q0.x, y = q0.y, z = q0.z, w = q0.w;
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const double nx = k00 * x + k01 * y + k02 * z + k03 * w, ny = k01 * x + k11 * y + k12 * z + k13 * w;
-        const double nz = k02 * x + k12 * y + k22 * z + k23 * w, nw = k03 * x + k13 * y + k23 * z + k33 * w;
-        const double nn = sqrt(nx * nx + ny * ny + nz * nz + nw * nw);
-        x = nx / nn; y = ny / nn; z = nz / nn; w = nw / nn;
-    }
-    return w < 0.0 ? Quat{-w, -x, -y, -z} : Quat{w, x, y, z};
-}
-
 __device__ __forceinline__ void put_v(double* e, const Vec3 v) { e[0] = v.x; e[1] = v.y; e[2] = v.z; }
 __device__ __forceinline__ void put_q(double* e, const Quat q) { e[0] = q.w; e[1] = q.x; e[2] = q.y; e[3] = q.z; }
 
-// one truth row -> its est row e[0 : 21 | 14]: as given, or the statements of ape_score_kernel's truth section with the shoulder origin
-// [6:9] that ape_fk writes (the hips quaternion applied to the body's).  NaN propagates.
+// one truth row -> its est row e[0 : 21 | 14]: as given, or the pose its targets stand for (score_device.h: targets_to_pose) with the
+// shoulder origin [6:9] that ape_fk writes (the hips quaternion applied to the body's).  NaN propagates.
 template <typename TT, int KIND>
 __device__ __forceinline__ void converted_row(const TT* row, int tw, int layout, const double* body, double* e) {
     double t[RS_W];
@@ -273,26 +236,12 @@ __device__ __forceinline__ void converted_row(const TT* row, int tw, int layout,
         for (int c = 0; c < RS_W; ++c) e[c] = t[c];
     } else {
         const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
-        const Vec3 larm_vec{body[0], body[1], body[2]}, uarm_vec{body[3], body[4], body[5]}, uarm_orig{body[6], body[7], body[8]};
-        Vec3 t_hand, t_elbow, uo = uarm_orig;
-        Quat t_lq, t_uq, t_hq{1.0, 0.0, 0.0, 0.0};
-        if (layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS) {         // estimate_joints.py:20-45: positions are targets
-            t_lq = truth_six_drr_to_quat(t + 3); t_uq = truth_six_drr_to_quat(t + 12); t_hq = hips_quat(t[18], t[19]);
-            t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[9], t[10], t[11]};
-            uo = qrot(t_hq, uarm_orig);
-        } else {                                                       // estimate_joints.py:48-71, 74-92
-            t_lq = truth_six_drr_to_quat(t); t_uq = truth_six_drr_to_quat(t + 6);
-            if (hips) { t_hq = hips_quat(t[12], t[13]); uo = qrot(t_hq, uarm_orig); }
-            const Vec3 r1 = qrot(t_uq, uarm_vec);
-            t_elbow = Vec3{r1.x + uo.x, r1.y + uo.y, r1.z + uo.z};
-            const Vec3 r2 = qrot(t_lq, larm_vec);
-            t_hand = Vec3{r2.x + t_elbow.x, r2.y + t_elbow.y, r2.z + t_elbow.z};
-        }
+        const TargetPose o = targets_to_pose(t, layout, body);
 #pragma unroll
         for (int c = 0; c < RS_W; ++c) e[c] = 0.0;
-        put_v(e, t_hand); put_v(e + 3, t_elbow);
-        if (hips) { put_v(e + 6, uo); put_q(e + 9, t_lq); put_q(e + 13, t_uq); put_q(e + 17, t_hq); }
-        else { put_q(e + 6, t_lq); put_q(e + 10, t_uq); }
+        put_v(e, o.hand); put_v(e + 3, o.elbow);
+        if (hips) { put_v(e + 6, o.uo); put_q(e + 9, o.lq); put_q(e + 13, o.uq); put_q(e + 17, o.hq); }
+        else { put_q(e + 6, o.lq); put_q(e + 10, o.uq); }
     }
 }
 
@@ -408,79 +357,8 @@ __global__ __launch_bounds__(RS_BLOCK) void ape_resample_kernel(const ResamplePa
     }
 }
 
-#define RS_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return ape_fail(APE_ERR_HIP, "resample: %s failed: %s", #expr, hipGetErrorString(_e)); } while (0)
-
-// The call's staging (score.hip's scheme, this file's own slots): a pinned block the host arrays are copied into, so that they are
-// consumed when the call returns and the copy to the device needs no wait, and the device block behind it (host arrays, tile
-// aggregates).  A slot is taken again once the event recorded behind its last call has completed; slots only grow and live as long as
-// the process: no allocation after the first call of a size.  Up to MAX_SLOTS calls in flight per device; one more waits for the oldest.
-struct Slot {
-    int device = -1;
-    void* pinned = nullptr;
-    void* dev = nullptr;
-    size_t pcap = 0, dcap = 0;
-    hipEvent_t done = nullptr;
-    bool used = false;
-    unsigned long long seq = 0;
-};
-constexpr size_t MAX_SLOTS = 8;
-std::mutex g_mu;
-std::vector<Slot*> g_slots;
-unsigned long long g_seq = 0;
-
-int take_slot(int device, size_t pbytes, size_t dbytes, Slot** out) {
-    Slot* s = nullptr;
-    size_t mine = 0;
-    for (Slot* q : g_slots) {
-        if (q->device != device) continue;
-        ++mine;
-        if (!q->used || hipEventQuery(q->done) == hipSuccess) { s = q; break; }
-    }
-    (void)hipGetLastError();                            // hipErrorNotReady of a busy slot is no error of this call
-    if (s == nullptr && mine >= MAX_SLOTS) {            // every slot in flight: wait for the oldest
-        for (Slot* q : g_slots)
-            if (q->device == device && (s == nullptr || q->seq < s->seq)) s = q;
-        RS_TRY(hipEventSynchronize(s->done));
-    }
-    if (s == nullptr) {
-        s = new Slot();
-        s->device = device;
-        const hipError_t e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            delete s;
-            return ape_fail(APE_ERR_HIP, "resample: hipEventCreate failed: %s", hipGetErrorString(e));
-        }
-        g_slots.push_back(s);
-    }
-    s->used = false;
-    if (s->pcap < pbytes) {
-        if (s->pinned) (void)hipHostFree(s->pinned);
-        s->pinned = nullptr; s->pcap = 0;
-        RS_TRY(hipHostMalloc(&s->pinned, pbytes, hipHostMallocDefault));
-        s->pcap = pbytes;
-    }
-    if (s->dcap < dbytes) {
-        if (s->dev) (void)hipFree(s->dev);
-        s->dev = nullptr; s->dcap = 0;
-        RS_TRY(hipMalloc(&s->dev, dbytes));
-        s->dcap = dbytes;
-    }
-    s->seq = ++g_seq;
-    *out = s;
-    return APE_OK;
-}
-
-// records the slot's event behind the launches and reports what became of them; `who` names the entry
-int finish_call(const char* who, Slot* slot, hipError_t launched, hipStream_t st) {
-    const hipError_t er = hipEventRecord(slot->done, st);  // the slot is in flight whatever became of the launches
-    slot->used = er == hipSuccess;
-    if (launched != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(launched));
-    if (er != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return ape_fail(APE_ERR_HIP, "%s: hipEventRecord failed: %s", who, hipGetErrorString(er));
-    }
-    return APE_OK;
-}
+// the staging of both entries: the host arrays in, the tile aggregates behind them (score_host.h)
+ApeSlotPool g_pool("resample");
 
 size_t pad8(size_t bytes) { return (bytes + 7) & ~(size_t)7; }
 
@@ -519,18 +397,18 @@ int ape_frame_times(const void* dt_dev, int32_t dt_stride, int32_t dt_dtype, uin
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = ape_check_not_capturing(st, who, "host arrays are staged per call")) return rc;
     int device = 0;
-    RS_TRY(hipGetDevice(&device));
+    APE_SCORE_TRY(g_pool.prefix, hipGetDevice(&device));
 
     const unsigned tiles = (unsigned)(((long long)F + FT_TILE - 1) / FT_TILE);
     const size_t starts_bytes = pad8((size_t)R * sizeof(int));
     const size_t heads_bytes = pad8((size_t)tiles * sizeof(int));
     const size_t work_bytes = 2 * (size_t)tiles * sizeof(double) + heads_bytes;      // aggregates' sums, carries, aggregates' heads
 
-    std::lock_guard<std::mutex> lock(g_mu);
-    Slot* slot = nullptr;
-    if (int rc = take_slot(device, starts_bytes, starts_bytes + work_bytes, &slot)) return rc;
+    std::lock_guard<std::mutex> lock(g_pool.mu);
+    ApeSlot* slot = nullptr;
+    if (int rc = g_pool.take(device, starts_bytes, starts_bytes + work_bytes, &slot)) return rc;
     memcpy(slot->pinned, seg_starts_host, (size_t)R * sizeof(int));
-    RS_TRY(hipMemcpyAsync(slot->dev, slot->pinned, starts_bytes, hipMemcpyHostToDevice, st));
+    APE_SCORE_TRY(g_pool.prefix, hipMemcpyAsync(slot->dev, slot->pinned, starts_bytes, hipMemcpyHostToDevice, st));
 
     TimesParams p{};
     char* dev = static_cast<char*>(slot->dev);
@@ -541,7 +419,7 @@ int ape_frame_times(const void* dt_dev, int32_t dt_stride, int32_t dt_dtype, uin
     p.agg_head = reinterpret_cast<int*>(dev + starts_bytes + 2 * (size_t)tiles * sizeof(double));
     p.stride = dt_stride; p.F = F; p.R = R; p.big_endian = flags ? 1 : 0;
     const hipError_t e = dt_dtype == APE_F32 ? launch_times<float>(p, tiles, st) : launch_times<double>(p, tiles, st);
-    return finish_call(who, slot, e, st);
+    return g_pool.finish(who, slot, e, st);
 }
 
 int ape_resample_truth(int32_t layout, const void* truth_dev, int32_t truth_kind, int32_t truth_dtype, int32_t Ft,
@@ -550,7 +428,7 @@ int ape_resample_truth(int32_t layout, const void* truth_dev, int32_t truth_kind
                        int32_t n_bodies, void* out_dev, int32_t out_dtype, void* stream) {
     const char* who = "resample_truth";
     if (!truth_dev || !truth_starts_host || !seg_starts_host || !bodies_host || !out_dev) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
-    if (layout != APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS && layout != APE_LAYOUT_ORI_CAL_LARM_UARM && layout != APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS)
+    if (!ape_scoring_layout(layout))
         return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to resample", who, layout);
     if (truth_kind != APE_TRUTH_TARGETS && truth_kind != APE_TRUTH_EST) return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown truth kind %d", who, truth_kind);
     if ((truth_dtype != APE_F32 && truth_dtype != APE_F64) || (out_dtype != APE_F32 && out_dtype != APE_F64))
@@ -568,7 +446,7 @@ int ape_resample_truth(int32_t layout, const void* truth_dev, int32_t truth_kind
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = ape_check_not_capturing(st, who, "host arrays are staged per call")) return rc;
     int device = 0;
-    RS_TRY(hipGetDevice(&device));
+    APE_SCORE_TRY(g_pool.prefix, hipGetDevice(&device));
 
     const unsigned blocks = (unsigned)(((long long)F + RS_BLOCK - 1) / RS_BLOCK);
     const size_t starts_bytes = pad8((size_t)R * sizeof(int));                       // starts, truth starts, shifts, bodies
@@ -576,16 +454,16 @@ int ape_resample_truth(int32_t layout, const void* truth_dev, int32_t truth_kind
     const size_t bodies_bytes = (size_t)n_bodies * 9 * sizeof(double);
     const size_t host_bytes = 2 * starts_bytes + shifts_bytes + bodies_bytes;
 
-    std::lock_guard<std::mutex> lock(g_mu);
-    Slot* slot = nullptr;
-    if (int rc = take_slot(device, host_bytes, host_bytes, &slot)) return rc;
+    std::lock_guard<std::mutex> lock(g_pool.mu);
+    ApeSlot* slot = nullptr;
+    if (int rc = g_pool.take(device, host_bytes, host_bytes, &slot)) return rc;
     char* pin = static_cast<char*>(slot->pinned);
     memcpy(pin, seg_starts_host, (size_t)R * sizeof(int));
     memcpy(pin + starts_bytes, truth_starts_host, (size_t)R * sizeof(int));
     if (shift_host) memcpy(pin + 2 * starts_bytes, shift_host, shifts_bytes);
     else memset(pin + 2 * starts_bytes, 0, shifts_bytes);
     memcpy(pin + 2 * starts_bytes + shifts_bytes, bodies_host, bodies_bytes);
-    RS_TRY(hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
+    APE_SCORE_TRY(g_pool.prefix, hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
 
     ResampleParams p{};
     const char* dev = static_cast<const char*>(slot->dev);
@@ -596,12 +474,10 @@ int ape_resample_truth(int32_t layout, const void* truth_dev, int32_t truth_kind
     p.bodies = reinterpret_cast<const double*>(dev + 2 * starts_bytes + shifts_bytes);
     p.max_gap = max_gap;
     p.F = F; p.Ft = Ft; p.R = R; p.layout = layout; p.n_bodies = n_bodies;
-    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
-    p.out_w = hips ? 21 : 14;
-    if (truth_kind == APE_TRUTH_TARGETS) p.truth_w = layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS ? 20 : (hips ? 14 : 12);
-    else p.truth_w = p.out_w;
+    p.out_w = ape_truth_width(layout, APE_TRUTH_EST);   // (the rows go out as est rows)
+    p.truth_w = ape_truth_width(layout, truth_kind);
     p.out_f32 = out_dtype == APE_F32 ? 1 : 0;
     if (truth_dtype == APE_F32) launch_resample<float>(p, truth_kind, blocks, st);
     else launch_resample<double>(p, truth_kind, blocks, st);
-    return finish_call(who, slot, hipGetLastError(), st);
+    return g_pool.finish(who, slot, hipGetLastError(), st);
 }

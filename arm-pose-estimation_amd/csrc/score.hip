@@ -2,7 +2,7 @@
 // down; the reference has no counterpart).
 //
 // ape_score_kernel      one lane per frame: the truth pose (est columns as given, or NN targets through the float64 forward kinematics of
-//                       fk_device.h, its quaternions refined to the reference's eigenvector: truth_six_drr_to_quat), the five errors of
+//                       fk_device.h, its quaternions refined to the reference's eigenvector: score_device.h's truth_pose), the five errors of
 //                       the frame's message against it, the two squared Mahalanobis distances under the frame's spread record; then the
 //                       workgroup's 256 frames reduced per recording into one partial record for every (workgroup, recording) pair
 // ape_score_acc_kernel  one workgroup per recording: its partial records combined in a fixed order
@@ -16,23 +16,22 @@
 // float64 with separate roundings for a * b + c, like the numpy statement (score.py): contraction is off in this file.
 #include "ape_internal.h"
 #include "../../include/ape_hip.h"
-#include "fk_device.h"
 #include "bank_host.h"
+#include "score_host.h"
 
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <mutex>
-#include <vector>
 
 #pragma clang fp contract(off)
+#include "score_device.h"
 
 namespace {
 
-using namespace ape_fkdev;
+using namespace ape_scoredev;
 
 constexpr int SC_BLOCK = 256, SC_WAVES = SC_BLOCK / 64;
-constexpr int SC_LDS_ROW = 25;                          // widest staged row (the message); every staged stride is odd: no bank conflicts
+constexpr int SC_LDS_ROW = STAGE_COLS;                  // widest staged row (the message); every staged stride is odd: no bank conflicts
 constexpr int ACC = APE_SCORE_ACC_WIDTH;
 constexpr double CHI2_3_Q50 = 2.3659738843753377, CHI2_3_Q90 = 6.251388631170325;
 
@@ -47,25 +46,6 @@ struct ScoreParams {
     long long msg_stride, spread_stride;
     int F, R, skip, layout, n_bodies, truth_w, score_f32;
 };
-
-// rows row0 .. row0 + nrows - 1 (nrows >= 1), columns 0 .. ncols - 1 of src -> lds[r * lstride + c] as float64.  Every lane loads in
-// every round (the index is clamped, a partial wave reads its last element again): no branch between the loads
-template <typename T>
-__device__ __forceinline__ void stage_rows(double* lds, const T* src, long long stride, int ncols, int lstride, long long row0, int nrows,
-                                           int lane) {
-    const int last = nrows * ncols - 1;
-#pragma unroll
-    for (int it = 0; it < SC_LDS_ROW; ++it) {
-        if (it < ncols) {                               // uniform
-            int idx = it * 64 + lane;
-            idx = idx < last ? idx : last;
-            const int r = idx / ncols, c = idx - r * ncols;
-            lds[r * lstride + c] = (double)src[(row0 + r) * stride + c];
-        }
-    }
-}
-
-__device__ __forceinline__ bool fin(double v) { return isfinite(v); }
 
 __device__ __forceinline__ double dist3(const double* a, const Vec3 t) {
     const double dx = a[0] - t.x, dy = a[1] - t.y, dz = a[2] - t.z;
@@ -96,37 +76,6 @@ __device__ __forceinline__ double mahalanobis(const double* rec, const Vec3 t) {
     return quad / det;
 }
 
-// The truth's 6D rotation -> unit quaternion, in the reference's sense.  rot_mat_to_quat (transformations.py:521-545) takes the dominant
-// eigenvector of the symmetric 4x4 matrix K(R) / 3; six_drr_to_quat (fk_device.h) is its closed form for an orthonormal R.  Where the two
-// 6D columns are nearly parallel, Gram-Schmidt leaves R up to 1e-11 off orthonormal and the two pick quaternions up to 4e-12 apart --
-// nothing beside a prediction's own error, but truth is compared at 1e-13.  So the closed form is the start of two power steps on
-// K + I, whose eigenvalues are 4 and three of the size of R's defect: each step multiplies the distance to the eigenvector by that
-// defect, and the result is the reference's to rounding (7e-16 on the fixtures after one step).  NaN propagates as in six_drr_to_quat.
-__device__ inline Quat truth_six_drr_to_quat(const double* s) {
-    const Quat q0 = six_drr_to_quat(s);
-    // R = [b1 b2 b3] as columns, the arithmetic of six_drr_to_quat (transformations.py:602-637)
-    const double a1x = s[0], a1y = s[2], a1z = s[4], a2x = s[1], a2y = s[3], a2z = s[5];
-    const double n1 = sqrt(a1x * a1x + a1y * a1y + a1z * a1z);
-    const double m00 = a1x / n1, m10 = a1y / n1, m20 = a1z / n1;
-    const double d = m00 * a2x + m10 * a2y + m20 * a2z;
-    const double ux = a2x - d * m00, uy = a2y - d * m10, uz = a2z - d * m20;
-    const double n2 = sqrt(ux * ux + uy * uy + uz * uz);
-    const double m01 = ux / n2, m11 = uy / n2, m21 = uz / n2;
-    const double m02 = m10 * m21 - m20 * m11, m12 = m20 * m01 - m00 * m21, m22 = m00 * m11 - m10 * m01;
-    // K + I in the reference's (x, y, z, w) order (transformations.py:575-584, times 3)
-    const double k00 = m00 - m11 - m22 + 1.0, k11 = m11 - m00 - m22 + 1.0, k22 = m22 - m00 - m11 + 1.0, k33 = m00 + m11 + m22 + 1.0;
-    const double k01 = m01 + m10, k02 = m02 + m20, k12 = m12 + m21, k03 = m21 - m12, k13 = m02 - m20, k23 = m10 - m01;
-    double x = q0.x, y = q0.y, z = q0.z, w = q0.w;
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-        const double nx = k00 * x + k01 * y + k02 * z + k03 * w, ny = k01 * x + k11 * y + k12 * z + k13 * w;
-        const double nz = k02 * x + k12 * y + k22 * z + k23 * w, nw = k03 * x + k13 * y + k23 * z + k33 * w;
-        const double nn = sqrt(nx * nx + ny * ny + nz * nz + nw * nw);
-        x = nx / nn; y = ny / nn; z = nz / nn; w = nw / nn;
-    }
-    return w < 0.0 ? Quat{-w, -x, -y, -z} : Quat{w, x, y, z};
-}
-
 __device__ __forceinline__ bool is_max_col(int c) { return c < 15 && c % 3 == 2; }
 
 __device__ __forceinline__ void acc_combine(double* v, const double* o) {
@@ -150,13 +99,8 @@ __global__ __launch_bounds__(SC_BLOCK) void ape_score_kernel(const ScoreParams p
     // the frame's recording: the last start <= f (starts[0] == 0, strictly rising); lanes past F form a recording of their own
     int rec = p.R, start = 0;
     if (valid) {
-        int lo = 0, hi = p.R - 1;
-        while (lo < hi) {
-            const int mid = (lo + hi + 1) >> 1;
-            if ((long long)p.starts[mid] <= f) lo = mid; else hi = mid - 1;
-        }
-        rec = lo;
-        start = p.starts[lo];
+        rec = find_rec(p.starts, p.R, f);
+        start = p.starts[rec];
     }
 
     // ---- truth pose ----
@@ -170,6 +114,8 @@ __global__ __launch_bounds__(SC_BLOCK) void ape_score_kernel(const ScoreParams p
     for (int c = 0; c < 21; ++c) t[c] = (valid && c < tw) ? lds[lane * tls + c] : 0.0;    // lanes past F, columns past tw: never-written LDS is not read
     __syncthreads();
     const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
+    // truth_pose's statements with `valid` at the head of the chain, not behind its flag: through truth_pose (ok = valid && pose[18] != 0.0)
+    // the est-kind kernel with a spread record takes 176 VGPRs for 148 and loses a wave per SIMD (profiles/score_headers.md)
     Vec3 t_hand, t_elbow;
     Quat t_lq, t_uq, t_hq{1.0, 0.0, 0.0, 0.0};
     bool ok = valid;
@@ -177,20 +123,8 @@ __global__ __launch_bounds__(SC_BLOCK) void ape_score_kernel(const ScoreParams p
 #pragma unroll
         for (int c = 0; c < 20; ++c)
             if (c < tw) ok = ok && fin(t[c]);
-        const double* body = p.bodies + 9 * (size_t)(p.n_bodies > 1 && valid ? rec : 0);
-        const Vec3 larm_vec{body[0], body[1], body[2]}, uarm_vec{body[3], body[4], body[5]}, uarm_orig{body[6], body[7], body[8]};
-        if (p.layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS) {       // estimate_joints.py:20-45: positions are targets
-            t_lq = truth_six_drr_to_quat(t + 3); t_uq = truth_six_drr_to_quat(t + 12); t_hq = hips_quat(t[18], t[19]);
-            t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[9], t[10], t[11]};
-        } else {                                                       // estimate_joints.py:48-71, 74-92
-            t_lq = truth_six_drr_to_quat(t); t_uq = truth_six_drr_to_quat(t + 6);
-            Vec3 uo = uarm_orig;
-            if (hips) { t_hq = hips_quat(t[12], t[13]); uo = qrot(t_hq, uarm_orig); }
-            const Vec3 r1 = qrot(t_uq, uarm_vec);
-            t_elbow = Vec3{r1.x + uo.x, r1.y + uo.y, r1.z + uo.z};
-            const Vec3 r2 = qrot(t_lq, larm_vec);
-            t_hand = Vec3{r2.x + t_elbow.x, r2.y + t_elbow.y, r2.z + t_elbow.z};
-        }
+        const TargetPose o = targets_to_pose(t, p.layout, p.bodies + 9 * (size_t)(p.n_bodies > 1 && valid ? rec : 0));
+        t_hand = o.hand; t_elbow = o.elbow; t_lq = o.lq; t_uq = o.uq; t_hq = o.hq;
     } else {
         const int ql = hips ? 9 : 6, qu = hips ? 13 : 10;
         t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[3], t[4], t[5]};
@@ -344,7 +278,6 @@ __global__ __launch_bounds__(SC_BLOCK) void ape_score_acc_kernel(const double* _
 // ape_score_lags_acc_kernel  one workgroup per (recording, lag): ape_score_acc_kernel's order over that lag's partial records.
 // For the sweep {0} without offsets the window is the workgroup's own 256 rows, the support is `f - start >= skip`, and every value and
 // every sum is formed by the operations of ape_score_kernel in their order: the bits are those of ape_score_rows.
-constexpr int SL_POSE = 19;                             // 18 pose values + the usable flag; odd: no bank conflicts
 constexpr int SL_WINDOW = SC_BLOCK + 2 * APE_SCORE_MAX_LAG;
 
 struct LagParams {
@@ -354,61 +287,10 @@ struct LagParams {
     int back, fwd;                                      // how far below / above its own rows a workgroup's truth window reaches:
 };                                                      // max(0, max_r(o_r + lag_max)) and max(0, -min_r(o_r + lag_min)), each <= 128
 
-__device__ __forceinline__ int find_rec(const int* starts, int R, long long f) {      // the last start <= f
-    int lo = 0, hi = R - 1;
-    while (lo < hi) {
-        const int mid = (lo + hi + 1) >> 1;
-        if ((long long)starts[mid] <= f) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
-// one truth row -> pose[0:18] = hand, elbow, lower-arm, upper-arm and hips quaternion, pose[18] = 1.0 iff every value used is finite.
-// (The statements of ape_score_kernel's truth section, which keeps its own copy so that its code stays as it was.)
-template <int KIND>
-__device__ __forceinline__ void truth_pose(const double* t, int tw, int layout, const double* body, double* pose) {
-    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
-    Vec3 t_hand, t_elbow;
-    Quat t_lq, t_uq, t_hq{1.0, 0.0, 0.0, 0.0};
-    bool ok = true;
-    if constexpr (KIND == APE_TRUTH_TARGETS) {
-#pragma unroll
-        for (int c = 0; c < 20; ++c)
-            if (c < tw) ok = ok && fin(t[c]);
-        const Vec3 larm_vec{body[0], body[1], body[2]}, uarm_vec{body[3], body[4], body[5]}, uarm_orig{body[6], body[7], body[8]};
-        if (layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS) {
-            t_lq = truth_six_drr_to_quat(t + 3); t_uq = truth_six_drr_to_quat(t + 12); t_hq = hips_quat(t[18], t[19]);
-            t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[9], t[10], t[11]};
-        } else {
-            t_lq = truth_six_drr_to_quat(t); t_uq = truth_six_drr_to_quat(t + 6);
-            Vec3 uo = uarm_orig;
-            if (hips) { t_hq = hips_quat(t[12], t[13]); uo = qrot(t_hq, uarm_orig); }
-            const Vec3 r1 = qrot(t_uq, uarm_vec);
-            t_elbow = Vec3{r1.x + uo.x, r1.y + uo.y, r1.z + uo.z};
-            const Vec3 r2 = qrot(t_lq, larm_vec);
-            t_hand = Vec3{r2.x + t_elbow.x, r2.y + t_elbow.y, r2.z + t_elbow.z};
-        }
-    } else {
-        const int ql = hips ? 9 : 6, qu = hips ? 13 : 10;
-        t_hand = Vec3{t[0], t[1], t[2]}; t_elbow = Vec3{t[3], t[4], t[5]};
-        t_lq = Quat{t[ql], t[ql + 1], t[ql + 2], t[ql + 3]};
-        t_uq = Quat{t[qu], t[qu + 1], t[qu + 2], t[qu + 3]};
-        if (hips) t_hq = Quat{t[17], t[18], t[19], t[20]};
-    }
-    ok = ok && fin(t_hand.x) && fin(t_hand.y) && fin(t_hand.z) && fin(t_elbow.x) && fin(t_elbow.y) && fin(t_elbow.z) &&
-         fin(t_lq.w) && fin(t_lq.x) && fin(t_lq.y) && fin(t_lq.z) && fin(t_uq.w) && fin(t_uq.x) && fin(t_uq.y) && fin(t_uq.z) &&
-         fin(t_hq.w) && fin(t_hq.x) && fin(t_hq.y) && fin(t_hq.z);
-    pose[0] = t_hand.x; pose[1] = t_hand.y; pose[2] = t_hand.z; pose[3] = t_elbow.x; pose[4] = t_elbow.y; pose[5] = t_elbow.z;
-    pose[6] = t_lq.w; pose[7] = t_lq.x; pose[8] = t_lq.y; pose[9] = t_lq.z;
-    pose[10] = t_uq.w; pose[11] = t_uq.x; pose[12] = t_uq.y; pose[13] = t_uq.z;
-    pose[14] = t_hq.w; pose[15] = t_hq.x; pose[16] = t_hq.y; pose[17] = t_hq.z;
-    pose[18] = ok ? 1.0 : 0.0;
-}
-
 template <typename TM, typename TT, int KIND, bool SPR>
 __global__ __launch_bounds__(SC_BLOCK) void ape_score_lags_kernel(const LagParams q) {
     __shared__ double stage[SC_WAVES][64 * SC_LDS_ROW];
-    __shared__ double poses[SL_WINDOW * SL_POSE];
+    __shared__ double poses[SL_WINDOW * POSE];
     __shared__ double wfirst[2][SC_WAVES][ACC];         // two buffers: one barrier per lag
     __shared__ int wrec[SC_WAVES][2];
     const ScoreParams& p = q.s;
@@ -447,7 +329,7 @@ __global__ __launch_bounds__(SC_BLOCK) void ape_score_lags_kernel(const LagParam
         if (tv) {
             const long long tr = r0 + lane;
             const int trec = (KIND == APE_TRUTH_TARGETS && p.n_bodies > 1) ? find_rec(p.starts, p.R, tr) : 0;
-            truth_pose<KIND>(t, tw, p.layout, p.bodies + 9 * (size_t)trec, poses + (size_t)(tr - wlo) * SL_POSE);
+            truth_pose<KIND>(t, tw, p.layout, p.bodies + 9 * (size_t)trec, poses + (size_t)(tr - wlo) * POSE);
         }
     }
 
@@ -478,10 +360,10 @@ __global__ __launch_bounds__(SC_BLOCK) void ape_score_lags_kernel(const LagParam
     for (int j = 0; j < q.L; ++j) {                     // (uniform)
         const long long tr = f - (l_lo + j);
         const bool ex = valid && tr >= (long long)start && tr < (long long)end;        // the pair exists: tr is inside [wlo, whi)
-        const double* ps = poses + (ex ? (size_t)(tr - wlo) : 0) * SL_POSE;
-        double t[SL_POSE];
+        const double* ps = poses + (ex ? (size_t)(tr - wlo) : 0) * POSE;
+        double t[POSE];
 #pragma unroll
-        for (int c = 0; c < SL_POSE; ++c) t[c] = ex ? ps[c] : 0.0;
+        for (int c = 0; c < POSE; ++c) t[c] = ex ? ps[c] : 0.0;
         const Vec3 t_hand{t[0], t[1], t[2]}, t_elbow{t[3], t[4], t[5]};
         const Quat t_lq{t[6], t[7], t[8], t[9]}, t_uq{t[10], t[11], t[12], t[13]}, t_hq{t[14], t[15], t[16], t[17]};
         const bool ok = ok_m && ex && t[18] != 0.0;
@@ -603,69 +485,8 @@ __global__ __launch_bounds__(SC_BLOCK) void ape_score_lags_acc_kernel(const doub
     }
 }
 
-// (APE_TRY with the entry's name in front)
-#define SC_TRY(expr) do { hipError_t _e = (expr); if (_e != hipSuccess) return ape_fail(APE_ERR_HIP, "score_rows: %s failed: %s", #expr, hipGetErrorString(_e)); } while (0)
-
-// The call's staging: a pinned block the host arrays are copied into (so they are consumed when the call returns and the copy to the
-// device needs no wait) and the device block behind it (starts, bodies, partial records).  A slot is taken again once the event recorded
-// behind its last call has completed; slots only grow, and live as long as the process.  The first call on a device, and any call whose
-// R or F outgrows the slot it takes, allocates (hipHostMalloc / hipMalloc, which may wait for the device): "the call does not wait" holds
-// from the second call of a size on.  Up to MAX_SLOTS calls may be in flight per device; one more waits for the oldest of them.
-struct Slot {
-    int device = -1;
-    void* pinned = nullptr;
-    void* dev = nullptr;
-    size_t pcap = 0, dcap = 0;
-    hipEvent_t done = nullptr;
-    bool used = false;
-    unsigned long long seq = 0;                         // order of the calls that took the slot
-};
-constexpr size_t MAX_SLOTS = 8;
-std::mutex g_mu;
-std::vector<Slot*> g_slots;
-unsigned long long g_seq = 0;
-
-int take_slot(int device, size_t pbytes, size_t dbytes, Slot** out) {
-    Slot* s = nullptr;
-    size_t mine = 0;
-    for (Slot* q : g_slots) {
-        if (q->device != device) continue;
-        ++mine;
-        if (!q->used || hipEventQuery(q->done) == hipSuccess) { s = q; break; }
-    }
-    (void)hipGetLastError();                            // hipErrorNotReady of a busy slot is no error of this call
-    if (s == nullptr && mine >= MAX_SLOTS) {            // every slot in flight: wait for the oldest
-        for (Slot* q : g_slots)
-            if (q->device == device && (s == nullptr || q->seq < s->seq)) s = q;
-        SC_TRY(hipEventSynchronize(s->done));
-    }
-    if (s == nullptr) {
-        s = new Slot();
-        s->device = device;
-        const hipError_t e = hipEventCreateWithFlags(&s->done, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            delete s;
-            return ape_fail(APE_ERR_HIP, "score_rows: hipEventCreate failed: %s", hipGetErrorString(e));
-        }
-        g_slots.push_back(s);
-    }
-    s->used = false;                                    // (its last call is complete; set again once this call has recorded its event)
-    if (s->pcap < pbytes) {
-        if (s->pinned) (void)hipHostFree(s->pinned);
-        s->pinned = nullptr; s->pcap = 0;
-        SC_TRY(hipHostMalloc(&s->pinned, pbytes, hipHostMallocDefault));
-        s->pcap = pbytes;
-    }
-    if (s->dcap < dbytes) {
-        if (s->dev) (void)hipFree(s->dev);
-        s->dev = nullptr; s->dcap = 0;
-        SC_TRY(hipMalloc(&s->dev, dbytes));
-        s->dcap = dbytes;
-    }
-    s->seq = ++g_seq;
-    *out = s;
-    return APE_OK;
-}
+// the staging of both entries: starts, offsets and bodies in, the partial records behind them (score_host.h)
+ApeSlotPool g_pool("score_rows");
 
 template <typename TM, typename TT, int KIND>
 void launch_score(const ScoreParams& p, unsigned blocks, hipStream_t st) {
@@ -698,7 +519,7 @@ int check_score_args(const char* who, int32_t layout, const void* msg_dev, int32
                      const void* acc_dev) {
     if (!msg_dev || !truth_dev || !seg_starts_host || !bodies_host) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
     if (!score_dev && !acc_dev) return ape_fail(APE_ERR_INVALID_ARG, "%s: score_dev and acc_dev are both NULL", who);
-    if (layout != APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS && layout != APE_LAYOUT_ORI_CAL_LARM_UARM && layout != APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS)
+    if (!ape_scoring_layout(layout))
         return ape_fail(APE_ERR_INVALID_ARG, "%s: layout %d has no pose to score", who, layout);
     if (truth_kind != APE_TRUTH_TARGETS && truth_kind != APE_TRUTH_EST) return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown truth kind %d", who, truth_kind);
     if ((msg_dtype != APE_F32 && msg_dtype != APE_F64) || (truth_dtype != APE_F32 && truth_dtype != APE_F64) ||
@@ -724,7 +545,7 @@ int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = ape_check_not_capturing(st, "score_rows", "host arrays are staged per call")) return rc;
     int device = 0;
-    SC_TRY(hipGetDevice(&device));
+    APE_SCORE_TRY(g_pool.prefix, hipGetDevice(&device));
 
     const unsigned blocks = (unsigned)(((long long)F + SC_BLOCK - 1) / SC_BLOCK);
     const size_t starts_bytes = (((size_t)R * sizeof(int)) + 7) & ~(size_t)7;
@@ -732,12 +553,12 @@ int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     const size_t host_bytes = starts_bytes + bodies_bytes;
     const size_t part_bytes = acc_dev ? ((size_t)blocks + (size_t)R) * ACC * sizeof(double) : 0;
 
-    std::lock_guard<std::mutex> lock(g_mu);
-    Slot* slot = nullptr;
-    if (int rc = take_slot(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
+    std::lock_guard<std::mutex> lock(g_pool.mu);
+    ApeSlot* slot = nullptr;
+    if (int rc = g_pool.take(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
     memcpy(slot->pinned, seg_starts_host, (size_t)R * sizeof(int));
     memcpy(static_cast<char*>(slot->pinned) + starts_bytes, bodies_host, bodies_bytes);
-    SC_TRY(hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
+    APE_SCORE_TRY(g_pool.prefix, hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
 
     ScoreParams p{};
     p.msg = msg_dev; p.spread = spread_dev; p.truth = truth_dev; p.score = score_dev;
@@ -746,9 +567,7 @@ int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     p.part = acc_dev ? reinterpret_cast<double*>(static_cast<char*>(slot->dev) + host_bytes) : nullptr;
     p.msg_stride = msg_stride; p.spread_stride = spread_stride;
     p.F = F; p.R = R; p.skip = skip; p.layout = layout; p.n_bodies = n_bodies;
-    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
-    if (truth_kind == APE_TRUTH_TARGETS) p.truth_w = layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS ? 20 : (hips ? 14 : 12);
-    else p.truth_w = hips ? 21 : 14;
+    p.truth_w = ape_truth_width(layout, truth_kind);
     p.score_f32 = score_dtype == APE_F32 ? 1 : 0;
 
     if (msg_dtype == APE_F32 && truth_dtype == APE_F32) launch_score_kind<float, float>(p, truth_kind, blocks, st);
@@ -760,14 +579,7 @@ int ape_score_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
         hipLaunchKernelGGL(ape_score_acc_kernel, dim3((unsigned)R), dim3(SC_BLOCK), 0, st, p.part, p.starts, R, F, acc_dev);
         e = hipGetLastError();
     }
-    const hipError_t er = hipEventRecord(slot->done, st);  // the slot is in flight whatever became of the launches
-    slot->used = er == hipSuccess;
-    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "score_rows: launch failed: %s", hipGetErrorString(e));
-    if (er != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return ape_fail(APE_ERR_HIP, "score_rows: hipEventRecord failed: %s", hipGetErrorString(er));
-    }
-    return APE_OK;
+    return g_pool.finish("score_rows", slot, e, st);
 }
 
 int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, const void* spread_dev, int32_t spread_stride,
@@ -778,22 +590,12 @@ int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     if (int rc = check_score_args("score_lags", layout, msg_dev, msg_stride, spread_dev, spread_stride, msg_dtype, truth_dev, truth_kind, truth_dtype, F,
                                   seg_starts_host, R, skip, bodies_host, n_bodies, score_dev, score_dtype, acc_dev))
         return rc;
-    if (lag_min > lag_max) return ape_fail(APE_ERR_INVALID_ARG, "score_lags: lag_min %d above lag_max %d", lag_min, lag_max);
-    const long long span = (long long)lag_max - (long long)lag_min + 1;
-    if (span > APE_SCORE_MAX_LAGS) return ape_fail(APE_ERR_INVALID_ARG, "score_lags: %lld lags in the sweep, at most %d", span, APE_SCORE_MAX_LAGS);
-    const int L = (int)span;
-    long long top = lag_max, bottom = lag_min;          // the largest and the smallest lag of any pair
-    for (int r = 0; r < R; ++r) {
-        const long long o = rec_lag_host ? rec_lag_host[r] : 0, lo = o + lag_min, hi = o + lag_max;
-        if (lo < -APE_SCORE_MAX_LAG || lo > APE_SCORE_MAX_LAG || hi < -APE_SCORE_MAX_LAG || hi > APE_SCORE_MAX_LAG)
-            return ape_fail(APE_ERR_INVALID_ARG, "score_lags: recording %d: lags %lld .. %lld, |lag| is at most %d", r, lo, hi, APE_SCORE_MAX_LAG);
-        top = r == 0 || hi > top ? hi : top;
-        bottom = r == 0 || lo < bottom ? lo : bottom;
-    }
+    int L = 0, back = 0, fwd = 0;
+    if (int rc = ape_check_lag_sweep("score_lags", lag_min, lag_max, rec_lag_host, R, &L, &back, &fwd)) return rc;
     const hipStream_t st = (hipStream_t)stream;
     if (int rc = ape_check_not_capturing(st, "score_lags", "host arrays are staged per call")) return rc;
     int device = 0;
-    SC_TRY(hipGetDevice(&device));
+    APE_SCORE_TRY(g_pool.prefix, hipGetDevice(&device));
 
     const unsigned blocks = (unsigned)(((long long)F + SC_BLOCK - 1) / SC_BLOCK);
     const size_t starts_bytes = (((size_t)R * sizeof(int)) + 7) & ~(size_t)7;       // starts, then the offsets, then the bodies
@@ -801,15 +603,15 @@ int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     const size_t host_bytes = 2 * starts_bytes + bodies_bytes;
     const size_t part_bytes = acc_dev ? ((size_t)blocks + (size_t)R) * (size_t)L * ACC * sizeof(double) : 0;
 
-    std::lock_guard<std::mutex> lock(g_mu);
-    Slot* slot = nullptr;
-    if (int rc = take_slot(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
+    std::lock_guard<std::mutex> lock(g_pool.mu);
+    ApeSlot* slot = nullptr;
+    if (int rc = g_pool.take(device, host_bytes, host_bytes + part_bytes, &slot)) return rc;
     char* pin = static_cast<char*>(slot->pinned);
     memcpy(pin, seg_starts_host, (size_t)R * sizeof(int));
     if (rec_lag_host) memcpy(pin + starts_bytes, rec_lag_host, (size_t)R * sizeof(int));
     else memset(pin + starts_bytes, 0, (size_t)R * sizeof(int));
     memcpy(pin + 2 * starts_bytes, bodies_host, bodies_bytes);
-    SC_TRY(hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
+    APE_SCORE_TRY(g_pool.prefix, hipMemcpyAsync(slot->dev, slot->pinned, host_bytes, hipMemcpyHostToDevice, st));
 
     LagParams q{};
     ScoreParams& p = q.s;
@@ -821,13 +623,10 @@ int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
     p.part = acc_dev ? reinterpret_cast<double*>(dev + host_bytes) : nullptr;
     p.msg_stride = msg_stride; p.spread_stride = spread_stride;
     p.F = F; p.R = R; p.skip = skip; p.layout = layout; p.n_bodies = n_bodies;
-    const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
-    if (truth_kind == APE_TRUTH_TARGETS) p.truth_w = layout == APE_LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS ? 20 : (hips ? 14 : 12);
-    else p.truth_w = hips ? 21 : 14;
+    p.truth_w = ape_truth_width(layout, truth_kind);
     p.score_f32 = score_dtype == APE_F32 ? 1 : 0;
     q.lag_min = lag_min; q.L = L;
-    q.back = top > 0 ? (int)top : 0;
-    q.fwd = bottom < 0 ? (int)-bottom : 0;
+    q.back = back; q.fwd = fwd;
 
     if (msg_dtype == APE_F32 && truth_dtype == APE_F32) launch_lags_kind<float, float>(q, truth_kind, blocks, st);
     else if (msg_dtype == APE_F32) launch_lags_kind<float, double>(q, truth_kind, blocks, st);
@@ -838,12 +637,5 @@ int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
         hipLaunchKernelGGL(ape_score_lags_acc_kernel, dim3((unsigned)R, (unsigned)L), dim3(SC_BLOCK), 0, st, p.part, p.starts, R, F, L, acc_dev);
         e = hipGetLastError();
     }
-    const hipError_t er = hipEventRecord(slot->done, st);  // the slot is in flight whatever became of the launches
-    slot->used = er == hipSuccess;
-    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "score_lags: launch failed: %s", hipGetErrorString(e));
-    if (er != hipSuccess) {
-        (void)hipStreamSynchronize(st);
-        return ape_fail(APE_ERR_HIP, "score_lags: hipEventRecord failed: %s", hipGetErrorString(er));
-    }
-    return APE_OK;
+    return g_pool.finish("score_lags", slot, e, st);
 }

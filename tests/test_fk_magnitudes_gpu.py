@@ -57,7 +57,7 @@ def test_ape_fk_over_the_exponent_range(layout):
 
 # ---------------- scoring with float64 truth given as targets -----------------------------------------------------------------------------
 # csrc/score.hip turns a truth row into a pose in two places (ape_score_kernel's truth section and truth_pose<APE_TRUTH_TARGETS> of the lag
-# sweep, which keeps its own copy): both call hips_quat and truth_six_drr_to_quat, the closed form of fk_device.h refined towards the
+# sweep), both through score_device.h's targets_to_pose: hips_quat and truth_six_drr_to_quat, the closed form of fk_device.h refined towards the
 # reference's eigenvector by two power steps on K + I.  A step multiplies the distance to the eigenvector by defect / 4 (K + I has the
 # eigenvalues 4 and three of the size of R's defect from orthonormal, delta = max |R'R - I|) and the closed form starts within delta, so
 # the refined quaternion is within delta^3 / 16 of the reference's: rows with delta <= PIN_DEFECT = 1e-4 (6e-14, and the scores amplify a
