@@ -1,4 +1,4 @@
-// Device helpers of the scoring kernels (score.hip, frame_fit.hip, body_fit.hip, resample.hip, post_sweep.hip), each
+// Device helpers of the scoring kernels (score.hip, frame_fit.hip, body_fit.hip, resample.hip, post_sweep.hip, motion.hip), each
 // stated once: row staging, the recording of a frame, one truth row -> pose, the rotation a quaternion stands for, the ordered column
 // sums of a wave's terms and the ordered sum of a recording's partial records.
 // float64 with separate roundings for a * b + c, like the numpy statements (score.py): the including file turns contraction off BEFORE

@@ -1,4 +1,4 @@
-// Host-side plumbing shared by the scoring entries (score.hip, frame_fit.hip, body_fit.hip, resample.hip): which
+// Host-side plumbing shared by the scoring entries (score.hip, frame_fit.hip, body_fit.hip, resample.hip, motion.hip): which
 // layouts have a pose to score, the width of a truth row, the check of a lag sweep, and the staging slots of a call.  Inline host
 // functions only, no device code; errors go through ape_fail.  The layout, width and lag-sweep checks make no HIP call.
 #pragma once

@@ -33,6 +33,8 @@ POST_MAX_CONFIGS = 64             # APE_POST_MAX_CONFIGS (ape_post_sweep, DESIGN
 FRAME_ACC_WIDTH = 51              # APE_FRAME_ACC_WIDTH (ape_frame_sums)
 BODY_ACC_WIDTH = 46               # APE_BODY_ACC_WIDTH (ape_body_sums)
 BODY_ROT_MSG, BODY_ROT_TRUTH = 0, 1         # APE_BODY_ROT_*
+MOTION_WIDTH, MOTION_ACC_WIDTH = 12, 38     # APE_MOTION_WIDTH, APE_MOTION_ACC_WIDTH (ape_motion_sums)
+ROWS_MSG, ROWS_EST, ROWS_TARGETS = 0, 1, 2  # APE_ROWS_*
 FLAG_ANY_PLACEMENT, FLAG_NO_XCD_CLASSES, FLAG_ALT_FORM = 0x08000000, 0x02000000, 0x01000000    # exchange-form selectors (A/B runs, tests)
 FLAG_IN_XCD_PLAIN = 0x00400000      # opt-in: plain hand-over stores inside an XCD-pure cluster (the default is write-through)
 KERNEL_AUTO, KERNEL_TILE16, KERNEL_CLUSTER, KERNEL_CLUSTER_GEN1, KERNEL_AUTO_GEN1 = 0, 1, 2, 3, 4
@@ -230,6 +232,11 @@ SIGNATURES["ape_body_sums"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_i
                                          C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
 SIGNATURES["ape_rebody_rows"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32,
                                            C.c_void_p, C.c_int32, C.c_void_p])
+# speed, acceleration and jerk of every frame: layout, rows + kind + stride + dtype, n_sets, set_stride (int64), F,
+# starts_host, R, skip, times, bodies_host, n_bodies, motion + dtype, acc, HIP stream
+SIGNATURES["ape_motion_sums"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
+                                           C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
+                                           C.c_void_p])
 
 _lib = None
 

@@ -686,6 +686,24 @@ class Estimator:
         bodies = self._body_measurements if bonemaps is None else bonemaps
         return score.truth_on_frames(self._layout, rows, truth, truth_times, truth_starts, starts, shifts, max_gap, truth_kind, bodies, big_endian)
 
+    # ---- how smooth a replay is (the reference has no counterpart) ----
+    def motion_recording(self, out, starts=None, skip=None, times=None, per_frame=False):
+        """``score.motion_sums`` with this estimator's layout: ``out`` as ``process_recording`` returned it (or ``repost``'s
+        ``[C, F, 25]``), ``times`` device float64 ``[F]`` (``score.frame_times``; None: per-frame units); ``skip`` defaults to
+        ``score_recording``'s.  Returns ``(motion [F, 12] | None, acc [R, 38])`` on the device (``score.summarise_motion``)."""
+        from wear_mocap_ape_amd import score
+        skip = self._sequence_len - 1 if skip is None else skip
+        return score.motion_sums(self._layout, out, "msg", starts, skip, times, None, per_frame)
+
+    def truth_motion(self, truth, truth_kind="targets", starts=None, skip=None, times=None, bonemaps=None):
+        """The floor the truth itself sets: ``score.motion_sums`` of ``truth`` (device ``[F, O]`` de-normalised targets, or est rows
+        with ``truth_kind="est"``) with this estimator's layout and body and ``motion_recording``'s defaults.  Returns
+        ``(None, acc [R, 38])``."""
+        from wear_mocap_ape_amd import score
+        skip = self._sequence_len - 1 if skip is None else skip
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        return score.motion_sums(self._layout, truth, truth_kind, starts, skip, times, bodies)
+
     # ---- post-filter sweep (DESIGN.md 4.33; the reference has no counterpart) ----
     def repost(self, y, configs, starts=None, bonemaps=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
         """``score.post_sweep`` with this estimator's model and body: ``y`` device float32 ``[F, M, O]`` as
@@ -704,14 +722,16 @@ class Estimator:
         return score.post_sweep(model, y, configs, starts, bonemaps, spread, out_dtype, workspace_bytes)
 
     def sweep_recording(self, rows, truth, smooths, samples, starts=None, lags=(0, 0), truth_kind="targets", bonemaps=None,
-                        seed: int = 0x5EED, skip=None, big_endian: bool = False):
+                        seed: int = 0x5EED, skip=None, big_endian: bool = False, motion: bool = False, times=None):
         """Which ``smooth`` and how many Monte-Carlo samples: ONE ``process_recording(return_targets=True)`` at ``max(samples)`` samples
         (this estimator's own ``smooth`` and sample count stay what they are), one ``score.post_sweep`` of
         ``score.grid(smooths, samples)`` with the spread records, then one ``score.score_lags`` over ``lags`` per configuration against
         ``truth`` (device ``[F, O]`` de-normalised targets, or est rows with ``truth_kind="est"``).  Over an ``ImuPoseLSTM`` every sample
         count is 1 (``nn_models.effective_mc``).  ``skip`` defaults to the ``sequence_len - 1`` cold-start frames of every recording.
         Returns ``{"configs": [(smooth, samples), ...], "acc": ndarray [C, R, L, 25], "best": [score.best_lag(acc[c], lags) per
-        configuration]}`` (waits for the device)."""
+        configuration]}`` (waits for the device).  ``motion=True``: the dict also holds ``"motion": ndarray [C, R, 38]``, what every
+        configuration's smoothing buys -- one ``score.motion_sums`` call on the sweep's ``out`` (``times``: the frames' clock, device
+        float64 ``[F]``; None: per-frame units)."""
         from wear_mocap_ape_amd import score
         from wear_mocap_ape_amd.estimate.nn_models import effective_mc
         model = self._hip_model()
@@ -726,7 +746,10 @@ class Estimator:
         out, rec = self.repost(y, configs, starts=starts, bonemaps=bonemaps, spread=True)
         skip = self._sequence_len - 1 if skip is None else skip
         bodies = self._body_measurements if bonemaps is None else bonemaps
-        return score.score_configs(self._layout, out, rec, truth, configs, lags, truth_kind, starts, skip, bodies)
+        res = score.score_configs(self._layout, out, rec, truth, configs, lags, truth_kind, starts, skip, bodies)
+        if motion:
+            res["motion"] = score.motion_sums(self._layout, out, "msg", starts, skip, times)[1].cpu().numpy()
+        return res
 
 
     # read-only views, same names as the reference's properties (estimator.py:188-218)

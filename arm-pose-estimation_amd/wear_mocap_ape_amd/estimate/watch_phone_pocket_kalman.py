@@ -353,6 +353,14 @@ class WatchPhonePocketKalman(Estimator):
         return super().score_recording(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind, lags,
                                        rec_lags)
 
+    def motion_recording(self, out, starts=None, skip=None, times=None, per_frame=False):
+        """``Estimator.motion_recording`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
+        return super().motion_recording(out, starts, self.__win_size + 1 if skip is None else skip, times, per_frame)
+
+    def truth_motion(self, truth, truth_kind="targets", starts=None, skip=None, times=None, bonemaps=None):
+        """``Estimator.truth_motion`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
+        return super().truth_motion(truth, truth_kind, starts, self.__win_size + 1 if skip is None else skip, times, bonemaps)
+
     def align_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=(0, 0), mode="yaw",
                         weights=(1, 1, 1, 0, 0)):
         """``Estimator.align_recording`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""

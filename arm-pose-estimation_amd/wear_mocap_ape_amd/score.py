@@ -28,7 +28,12 @@ The positions of a message are made from its quaternions and the nine values of 
 ``body_sums`` takes, for every lag of a sweep, the sums a recording's least-squares body is read off (``ape_body_sums``, DESIGN.md
 4.37), ``best_body`` solves for nine values or three lengths on the host, ``bodies_of`` gives them to ``set_bodies`` and
 ``process_recording(bonemaps=)``, ``rebody_rows`` makes the rows' positions again (``ape_rebody_rows``), ``align_body`` does all of it
-and scores what remains; ``body_sums_numpy`` and ``rebody_rows_numpy`` are the host statements."""
+and scores what remains; ``body_sums_numpy`` and ``rebody_rows_numpy`` are the host statements.
+
+What a longer ``smooth`` buys is a steadier arm: ``motion_sums`` takes the linear and angular speed, acceleration and jerk of every
+frame of any rows that state a pose -- messages, est rows or targets, many sets at once -- on the frames' own clock and sums them per
+recording (``ape_motion_sums``); it needs no truth.  ``summarise_motion`` and ``merge_motion`` work on the raw
+accumulators, ``motion_sums_numpy`` is the host statement."""
 import ctypes as C
 
 import numpy as np
@@ -1309,3 +1314,283 @@ def align_body(layout: int, msg, truth, lags=(0, 0), mode: str = "vectors", weig
         rec = rec.to(out.dtype)
     score, acc = score_lags(layout, out, truth, (0, 0), truth_kind, rec, starts, skip, bodies, at, per_frame=True)
     return score[:, 0], acc[:, 0], found
+
+
+# ---- how smooth a replay is: speed, acceleration and jerk of every frame (ape_motion_sums) ----------------------------------
+# A longer ``smooth`` makes the arm stop shaking and costs lag: ``score_lags`` measures the lag, ``motion_sums`` what it buys -- the jerk
+# of the joint positions, the literature's jitter -- from the rows alone, on the frames' own clock and never across a recording boundary.
+# It needs no truth: ``truth_motion`` of an estimator is the floor the truth itself sets.
+MOTION_WIDTH = _hip.MOTION_WIDTH
+MOTION_ACC_WIDTH = _hip.MOTION_ACC_WIDTH
+ROWS_KINDS = {"msg": _hip.ROWS_MSG, "est": _hip.ROWS_EST, "targets": _hip.ROWS_TARGETS}
+MOTION_NAMES = ("hand_speed", "hand_acc", "hand_jerk", "elbow_speed", "elbow_acc", "elbow_jerk",
+                "larm_ang_speed", "uarm_ang_speed", "hips_ang_speed", "larm_ang_acc", "uarm_ang_acc", "hips_ang_acc")
+_MOTION_MAX_COLS = tuple(range(2, 3 * MOTION_WIDTH, 3))
+
+
+def _rows_width(layout: int, kind: str) -> int:
+    if kind not in ROWS_KINDS:
+        raise UserWarning(f"kind must be one of {sorted(ROWS_KINDS)}, got {kind!r}")
+    if layout not in _hip.EST_WIDTH:
+        raise UserWarning(f"layout {layout} has no pose to difference")
+    return 25 if kind == "msg" else (_hip.NUM_TARGETS if kind == "targets" else _hip.EST_WIDTH)[layout]
+
+
+def _norm3(v):
+    return np.sqrt((v[:, 0] * v[:, 0] + v[:, 1] * v[:, 1]) + v[:, 2] * v[:, 2])
+
+
+def _six_drr_quat(s):
+    """truth_six_drr_to_quat of csrc/score_device.h operation for operation: ``s [n, 6]`` -> unit quaternions ``[n, 4]`` with
+    ``w >= 0`` -- Gram-Schmidt, the closed form of fk_device.h's six_drr_to_quat with its four pivots, two power steps on ``K + I``"""
+    a1x, a1y, a1z, a2x, a2y, a2z = s[:, 0], s[:, 2], s[:, 4], s[:, 1], s[:, 3], s[:, 5]
+    n1 = np.sqrt((a1x * a1x + a1y * a1y) + a1z * a1z)
+    m00, m10, m20 = a1x / n1, a1y / n1, a1z / n1
+    d = (m00 * a2x + m10 * a2y) + m20 * a2z
+    ux, uy, uz = a2x - d * m00, a2y - d * m10, a2z - d * m20
+    n2 = np.sqrt((ux * ux + uy * uy) + uz * uz)
+    m01, m11, m21 = ux / n2, uy / n2, uz / n2
+    m02, m12, m22 = m10 * m21 - m20 * m11, m20 * m01 - m00 * m21, m00 * m11 - m10 * m01
+    tr = (m00 + m11) + m22
+    s0, s1 = 2.0 * np.sqrt(tr + 1.0), 2.0 * np.sqrt(((1.0 + m00) - m11) - m22)
+    s2, s3 = 2.0 * np.sqrt(((1.0 + m11) - m00) - m22), 2.0 * np.sqrt(((1.0 + m22) - m00) - m11)
+    forms = [np.stack([0.25 * s0, (m21 - m12) / s0, (m02 - m20) / s0, (m10 - m01) / s0], axis=1),
+             np.stack([(m21 - m12) / s1, 0.25 * s1, (m01 + m10) / s1, (m02 + m20) / s1], axis=1),
+             np.stack([(m02 - m20) / s2, (m01 + m10) / s2, 0.25 * s2, (m12 + m21) / s2], axis=1),
+             np.stack([(m10 - m01) / s3, (m02 + m20) / s3, (m12 + m21) / s3, 0.25 * s3], axis=1)]
+    c0 = ~(tr < m00) & ~(tr < m11) & ~(tr < m22)           # the trace is the pivot (also the NaN path)
+    c1 = ~c0 & (m00 >= m11) & (m00 >= m22)
+    c2 = ~c0 & ~c1 & (m11 >= m22)
+    q = np.where(c0[:, None], forms[0], np.where(c1[:, None], forms[1], np.where(c2[:, None], forms[2], forms[3])))
+    q = np.where((q[:, 0] < 0.0)[:, None], -q, q)
+    k00, k11, k22, k33 = ((m00 - m11) - m22) + 1.0, ((m11 - m00) - m22) + 1.0, ((m22 - m00) - m11) + 1.0, ((m00 + m11) + m22) + 1.0
+    k01, k02, k12, k03, k13, k23 = m01 + m10, m02 + m20, m12 + m21, m21 - m12, m02 - m20, m10 - m01
+    w, x, y, z = q[:, 0], q[:, 1], q[:, 2], q[:, 3]
+    for _ in range(2):
+        nx, ny = ((k00 * x + k01 * y) + k02 * z) + k03 * w, ((k01 * x + k11 * y) + k12 * z) + k13 * w
+        nz, nw = ((k02 * x + k12 * y) + k22 * z) + k23 * w, ((k03 * x + k13 * y) + k23 * z) + k33 * w
+        nn = np.sqrt(((nx * nx + ny * ny) + nz * nz) + nw * nw)
+        x, y, z, w = nx / nn, ny / nn, nz / nn, nw / nn
+    q = np.stack([w, x, y, z], axis=1)
+    return np.where((w < 0.0)[:, None], -q, q)
+
+
+def _hips_quat(sn, cs):
+    """hips_quat of csrc/fk_device.h: ``(cos(a / 2), 0, sin(a / 2), 0)`` of ``a = atan2(sn, cs)`` by angle_device.h's half-angle identities
+    (the routine's own route outside the band 1e-140 <= r <= 1e140)"""
+    r = np.sqrt(cs * cs + sn * sn)
+    plain = (r >= 1e-140) & (r <= 1e140)
+    rr = np.where(plain, r, 1.0)
+    c, sa = cs / rr, np.abs(sn) / rr
+    big = np.sqrt(0.5 * (1.0 + np.abs(c)))
+    small = sa / (2.0 * big)
+    hc, hs = np.where(c >= 0.0, big, small), np.copysign(np.where(c >= 0.0, small, big), sn)
+    h = 0.5 * np.arctan2(sn, cs)
+    hc, hs = np.where(plain, hc, np.cos(h)), np.where(plain, hs, np.sin(h))
+    zero = np.zeros_like(hc)
+    return np.stack([hc, zero, hs, zero], axis=1)
+
+
+def _pose_rows(rows, layout: int, kind: str, body):
+    """``(pose [F, 18], usable [F])`` of rows of a kind: hand, elbow, lower-arm, upper-arm and hips quaternion (the identity without
+    hips), by the operations of csrc/score_device.h's truth_pose (targets: targets_to_pose with the frames' bodies ``body [F, 9]``);
+    usable: every value the pose is made of is finite"""
+    n = rows.shape[0]
+    hips = layout != _hip.LAYOUT_ORI_CAL_LARM_UARM
+    ident = np.tile([1.0, 0.0, 0.0, 0.0], (n, 1))
+    ok = np.ones(n, dtype=bool)
+    if kind == "msg":
+        hand, elbow, lq, uq, hq = rows[:, 4:7], rows[:, 11:14], rows[:, 7:11], rows[:, 14:18], rows[:, 21:25] if hips else ident
+    elif kind == "est":
+        ql, qu = (9, 13) if hips else (6, 10)
+        hand, elbow, lq, uq, hq = rows[:, 0:3], rows[:, 3:6], rows[:, ql:ql + 4], rows[:, qu:qu + 4], rows[:, 17:21] if hips else ident
+    else:
+        ok = np.isfinite(rows).all(axis=1)
+        larm_vec, uarm_vec, uarm_orig = body[:, 0:3], body[:, 3:6], body[:, 6:9]
+        if layout == _hip.LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS:
+            lq, uq, hq = _six_drr_quat(rows[:, 3:9]), _six_drr_quat(rows[:, 12:18]), _hips_quat(rows[:, 18], rows[:, 19])
+            hand, elbow = rows[:, 0:3], rows[:, 9:12]
+        else:
+            lq, uq = _six_drr_quat(rows[:, 0:6]), _six_drr_quat(rows[:, 6:12])
+            hq = _hips_quat(rows[:, 12], rows[:, 13]) if hips else ident
+            uo = _qrot(hq, uarm_orig) if hips else uarm_orig
+            elbow = _qrot(uq, uarm_vec) + uo
+            hand = _qrot(lq, larm_vec) + elbow
+    pose = np.concatenate([hand, elbow, lq, uq, hq], axis=1)
+    return pose, ok & np.isfinite(pose).all(axis=1)
+
+
+def _unit4(q):
+    n = np.sqrt(((q[:, 0] * q[:, 0] + q[:, 1] * q[:, 1]) + q[:, 2] * q[:, 2]) + q[:, 3] * q[:, 3])
+    return q / n[:, None]
+
+
+def _ang_vel(a, b, h):
+    """the world-frame angular velocity over the step ``h`` from unit quaternions ``b`` to ``a``: ``d = a (x) conj(b)``, negated where
+    ``d.w < 0.0``, ``v`` its vector part, ``n = |v|``: ``(s v) / h`` with ``s = (2 atan2(n, d.w)) / n`` for ``n >= 1e-8``, else 2"""
+    d = _qmul(a, b * np.array([1.0, -1.0, -1.0, -1.0]))
+    d = np.where((d[:, 0] < 0.0)[:, None], -d, d)
+    n = _norm3(d[:, 1:])
+    big = n >= 1e-8
+    s = np.where(big, (2.0 * np.arctan2(n, d[:, 0])) / np.where(big, n, 1.0), 2.0)
+    return (s[:, None] * d[:, 1:]) / h[:, None]
+
+
+def motion_sums_numpy(rows, layout: int, kind: str = "msg", starts=None, skip: int = 0, times=None, bodies=None):
+    """The host statement of ``motion_sums`` for one set of rows: ``(motion [F, 12], acc [R, 38])`` float64, plain numpy with the
+    operations of include/ape_hip.h in their order.  ``rows [F, >= w]`` of ``kind`` ``"msg"`` (w = 25), ``"est"`` (21 | 14) or
+    ``"targets"`` (O; through the numpy statement of the device's truth FK with ``bodies``); float32 rows are widened exactly.
+    ``times`` float64 ``[F]`` or None (the index clock).  A frame holds its 12 values iff it lies at least three frames into its
+    recording, the poses of ``f-3 .. f`` are finite, the three steps are finite and positive and all 12 results are finite; else NaN.
+    ``acc``: sum, sum of squares and maximum of every value over the frames with ``f - s_r >= skip + 3``, then the frames summed and
+    the frames left out (numpy's summation order, so sums agree with the device to rounding)."""
+    w = _rows_width(layout, kind)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] < w:
+        raise UserWarning(f"rows: expected [F, >= {w}], got {tuple(rows.shape)}")
+    rows = rows[:, :w].astype(np.float64)
+    F = rows.shape[0]
+    st = _recording_starts(starts).astype(np.int64)
+    R = st.shape[0]
+    hips = layout != _hip.LAYOUT_ORI_CAL_LARM_UARM
+    rec = np.searchsorted(st, np.arange(F), side="right") - 1
+    idx = np.arange(F) - st[rec]
+    t = idx.astype(np.float64) if times is None else np.asarray(times, dtype=np.float64).reshape(-1)
+    if t.shape[0] != F:
+        raise UserWarning(f"times: {t.shape[0]} stamps for {F} frames")
+    body = None
+    if kind == "targets":
+        b = _body_rows(bodies, R, "motion_sums bodies")
+        body = b[rec] if b.shape[0] > 1 else np.broadcast_to(b, (F, 9))
+    motion = np.full((F, MOTION_WIDTH), np.nan)
+    with np.errstate(all="ignore"):
+        pose, ok = _pose_rows(rows, layout, kind, body)
+        pose = np.concatenate([pose[:, 0:6], _unit4(pose[:, 6:10]), _unit4(pose[:, 10:14]), _unit4(pose[:, 14:18])], axis=1)
+        if F > 3:
+            t0, t1, t2, t3 = t[3:], t[2:-1], t[1:-2], t[:-3]
+            h1, h2, h3 = t0 - t1, t1 - t2, t2 - t3
+            s2a, s2b, s3 = t0 - t2, t1 - t3, t0 - t3
+            val = np.zeros((F - 3, MOTION_WIDTH))
+            for k, c in enumerate((0, 3)):
+                p = pose[:, c:c + 3]
+                a, b, e = (p[3:] - p[2:-1]) / h1[:, None], (p[2:-1] - p[1:-2]) / h2[:, None], (p[1:-2] - p[:-3]) / h3[:, None]
+                a2, b2 = (a - b) / s2a[:, None], (b - e) / s2b[:, None]
+                d3 = (a2 - b2) / s3[:, None]
+                val[:, 3 * k], val[:, 3 * k + 1], val[:, 3 * k + 2] = _norm3(a), 2.0 * _norm3(a2), 6.0 * _norm3(d3)
+            half = s2a / 2.0
+            for j in range(3 if hips else 2):
+                q = pose[:, 6 + 4 * j:10 + 4 * j]
+                wa, wb = _ang_vel(q[3:], q[2:-1], h1), _ang_vel(q[2:-1], q[1:-2], h2)
+                val[:, 6 + j], val[:, 9 + j] = _norm3(wa), _norm3(wa - wb) / half
+            good = (idx[3:] >= 3) & ok[3:] & ok[2:-1] & ok[1:-2] & ok[:-3]
+            for h in (h1, h2, h3):
+                good &= np.isfinite(h) & (h > 0.0)
+            good &= np.isfinite(val).all(axis=1)
+            motion[3:][good] = val[good]
+    acc = np.zeros((R, MOTION_ACC_WIDTH))
+    ends = np.r_[st[1:], F]
+    for r, (a, b) in enumerate(zip(st, ends)):
+        seg = motion[min(a + int(skip) + 3, b):b]
+        use = seg[np.isfinite(seg[:, 0])]
+        if use.shape[0]:
+            acc[r, 0:36:3], acc[r, 1:36:3], acc[r, 2:36:3] = use.sum(axis=0), (use * use).sum(axis=0), use.max(axis=0)
+        acc[r, 36], acc[r, 37] = use.shape[0], seg.shape[0] - use.shape[0]
+    return motion, acc
+
+
+def _sets_view(t, width: int, what: str):
+    """(tensor, row stride, set stride, C | None) of a device view ``[F, >= width]`` or ``[C, F, >= width]`` whose rows are contiguous
+    and whose sets do not overlap; anything else is copied"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() not in (2, 3) or t.shape[-1] < width or t.shape[-2] < 1:
+        raise UserWarning(f"{what}: expected a device tensor [F, >= {width}] or [C, F, >= {width}]")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"{what}: float32 or float64, got {t.dtype}")
+    F = int(t.shape[-2])
+    if t.dim() == 2:
+        t, rs = _rows_view(t, width, what)
+        return t, rs, 0, None
+    n = int(t.shape[0])
+    if not 1 <= n <= _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"{what}: between 1 and {_hip.POST_MAX_CONFIGS} sets, got {n}")
+    rs = max(int(t.stride(1)), width) if F > 1 else width
+    if t.stride(2) != 1 or (F > 1 and t.stride(1) < width) or (n > 1 and t.stride(0) < F * rs):
+        t = t[:, :, :width].contiguous()
+        rs = width
+    return t, rs, (int(t.stride(0)) if n > 1 else 0), n
+
+
+def motion_sums(layout: int, rows, kind: str = "msg", starts=None, skip: int = 0, times=None, bodies=None, per_frame: bool = False,
+                out_dtype=None):
+    """Speed, acceleration and jerk of every frame and their sums per recording (``ape_motion_sums``).  ``rows``: device ``[F, >= w]``
+    or ``[C, F, >= w]`` (C sets of the same recordings, at most 64: ``repost``'s ``out`` goes in as it is), float32 or float64, a
+    strided view is taken without a copy; ``kind``: ``"msg"`` messages (w = 25), ``"est"`` est rows (21 | 14), ``"targets"``
+    de-normalised NN targets (O), converted with ``bodies`` as ``score_rows`` converts truth.  ``starts``: the recordings' first
+    frames; ``skip``: leading frames of every recording left out of the accumulators, on top of the three a third difference needs;
+    ``times``: device float64 ``[F]`` (``frame_times``; None: the index clock, results per frame).  Returns ``(motion, acc)`` on the
+    device: ``[F, 12]`` of ``out_dtype`` (default: the rows'; None unless ``per_frame``) in ``MOTION_NAMES``' order, NaN rows where a
+    frame is not differenced, and float64 ``[R, 38]`` raw accumulators (``summarise_motion``, ``merge_motion``); both with a leading
+    ``C`` for ``[C, F, w]`` rows.  The same inputs give the same bits.  The call does not wait for the device."""
+    w = _rows_width(layout, kind)
+    rd, rs, ss, n = _sets_view(rows, w, "rows")
+    if rs > 2 ** 31 - 1:
+        raise UserWarning(f"rows: a row stride of {rs} elements does not fit the entry's int32 (copy the view)")
+    out_dtype = rd.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+    F, dev, sets = int(rd.shape[-2]), rd.device, 1 if n is None else n
+    st = _recording_starts(starts)
+    R = int(st.shape[0])
+    body = _body_rows(bodies, R, "motion_sums bodies") if kind == "targets" else None
+    tq = None if times is None else _clock(times, F, dev, "times")
+    with torch.cuda.device(dev):
+        motion = torch.empty((sets, F, MOTION_WIDTH), dtype=out_dtype, device=dev) if per_frame else None
+        acc = torch.empty((sets, max(R, 1), MOTION_ACC_WIDTH), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_motion_sums(int(layout), C.c_void_p(rd.data_ptr()), ROWS_KINDS[kind], rs, _f64(rd.dtype), sets, ss, F,
+                                              C.c_void_p(st.ctypes.data), R, int(skip), C.c_void_p(tq.data_ptr()) if tq is not None else None,
+                                              C.c_void_p(body.ctypes.data) if body is not None else None,
+                                              int(body.shape[0]) if body is not None else 0,
+                                              C.c_void_p(motion.data_ptr()) if motion is not None else None, _f64(out_dtype),
+                                              C.c_void_p(acc.data_ptr()), stream), "ape_motion_sums")
+    if n is None:
+        return (None if motion is None else motion[0]), acc[0]
+    return motion, acc
+
+
+def _motion_host(acc, ndims=(2,)) -> np.ndarray:
+    a = acc.detach().cpu().numpy() if isinstance(acc, torch.Tensor) else np.asarray(acc)
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim not in ndims or a.shape[-1] != MOTION_ACC_WIDTH:
+        raise UserWarning(f"expected motion accumulators [..., R, {MOTION_ACC_WIDTH}] of {' or '.join(str(n) for n in ndims)} dimensions, "
+                          f"got {tuple(a.shape)}")
+    return a
+
+
+def summarise_motion(acc) -> list:
+    """``acc [R, 38]`` (of several sets: one set's slice ``acc[c]``) -> per recording a dict: ``scored`` and ``left_out`` frame counts
+    and ``mean``, ``rms`` and ``max`` of the 12 values, dicts keyed by ``MOTION_NAMES`` (NaN where nothing was summed)."""
+    res = []
+    with np.errstate(all="ignore"):
+        for row in _motion_host(acc):
+            n = row[36]
+            d = {"scored": int(n), "left_out": int(row[37]), "mean": {}, "rms": {}, "max": {}}
+            for k, name in enumerate(MOTION_NAMES):
+                d["mean"][name] = float(row[3 * k] / n) if n else float("nan")
+                d["rms"][name] = float(np.sqrt(row[3 * k + 1] / n)) if n else float("nan")
+                d["max"][name] = float(row[3 * k + 2]) if n else float("nan")
+            res.append(d)
+    return res
+
+
+def merge_motion(acc_a, acc_b) -> np.ndarray:
+    """the accumulators ``[R, 38]`` (or ``[C, R, 38]``) of two pieces of the same recordings as one: sums and counts added, the larger
+    of the maxima.  Where the pieces are chained -- the second continues the first's recording -- the second piece's first three
+    frames have no three frames below them in their own piece: the three frames at a joint are in neither piece's support, so the
+    merged counts are three short of the whole recording's per joint."""
+    a, b = _motion_host(acc_a, (2, 3)), _motion_host(acc_b, (2, 3))
+    if a.shape != b.shape:
+        raise UserWarning(f"merge_motion: {tuple(a.shape)} and {tuple(b.shape)} accumulators")
+    out = a + b
+    cols = list(_MOTION_MAX_COLS)
+    out[..., cols] = np.maximum(a[..., cols], b[..., cols])
+    return out

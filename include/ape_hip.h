@@ -1137,6 +1137,63 @@ int ape_rebody_rows(int32_t layout, const void* msg_dev, int32_t msg_stride, int
                     int32_t R, const double* bodies_host, int32_t n_bodies /* 1 | R */, void* out_dev /* [F, 25] */, int32_t out_dtype,
                     void* stream);
 
+/* ---- how smooth a replay is: speed, acceleration and jerk of every frame (additive in ABI 7) ---------------------------------
+ * replaces: nothing; the reference has no counterpart.  A longer `smooth` makes the arm stop shaking and costs lag; ape_score_lags measures
+ * the lag, ape_motion_sums what it buys: the jerk of the joint positions (the literature's jitter), with the speeds and accelerations
+ * beside it.  It needs no truth, so it is also the one score of a recording made without a mocap system.  It takes any rows that state an
+ * arm pose, on the frames' own clock, for up to 64 sets of rows in one pass, and never pairs frames across a recording boundary.
+ *   Sets.   Set c = 0 .. n_sets-1 (1 <= n_sets <= APE_POST_MAX_CONFIGS) is the F rows that start c * set_stride elements after rows_dev,
+ *           rows_stride (>= the row width) elements apart, of rows_dtype: ape_post_sweep's out [C, F, 25] goes in as one call, strided
+ *           views go in without a copy.  set_stride is not read with n_sets == 1.  The recordings (seg_starts_host, as ape_score_rows:
+ *           recording r holds the frames [s_r, e_r)), the clock and the bodies are shared by all sets.
+ *   Clock.  t(f) = times_dev[f] (ape_frame_times's output); with NULL the index clock (double)(f - s_r), and the results are in per-frame
+ *           units (ape_resample_truth's convention).
+ *   Pose of a row: hand p_h, elbow p_e, quaternions q_l, q_u, q_h of the lower arm, the upper arm and the hips.
+ *           APE_ROWS_MSG      [25] message columns [4:7], [11:14], [7:11], [14:18], [21:25]; nothing else of the row is read
+ *           APE_ROWS_EST      [21 | 14] est rows, as APE_TRUTH_EST (the shoulder origin [6:9] is not read)
+ *           APE_ROWS_TARGETS  [O] de-normalised NN targets, converted as ape_score_rows converts truth, with the recording's body:
+ *                             bodies_host f64 [n_bodies, 9], n_bodies 1 or R; read for this kind only, may be NULL otherwise
+ *           APE_LAYOUT_ORI_CAL_LARM_UARM has no hips: q_h is the identity (message columns [21:25] are not read) and its three hips
+ *           values are exactly 0.  Every quaternion is normalised before use: n = sqrt(w*w + x*x + y*y + z*z), each component / n.
+ *   Per frame, APE_MOTION_WIDTH values.  h1 = t(f) - t(f-1), h2 = t(f-1) - t(f-2), h3 = t(f-2) - t(f-3).  All arithmetic is float64 with
+ *           separate roundings, in the order written here (score.py: motion_sums_numpy repeats it operation for operation).  For a
+ *           position p, per component, the divided differences
+ *             d1(f) = (p(f) - p(f-1)) / h1,  d2(f) = (d1(f) - d1(f-1)) / (t(f) - t(f-2)),  d3(f) = (d2(f) - d2(f-1)) / (t(f) - t(f-3))
+ *           (d1(f-1), d1(f-2) and d2(f-1) the same expressions one and two frames down, with h2, h3 and t(f-1) - t(f-3)) give the speed
+ *           |d1(f)|, the acceleration 2 |d2(f)| and the jerk 6 |d3(f)|, |v| = sqrt(x*x + y*y + z*z) summed left to right.  On a uniform
+ *           clock the jerk is |p(f) - 3 p(f-1) + 3 p(f-2) - p(f-3)| / h^3.  For a joint with unit quaternion q: d = q(f) (x) conj(q(f-1))
+ *           (the product of fk_device.h), negated where d.w < 0.0; v its vector part, n = |v|; the world-frame angular velocity over the
+ *           step is w(f) = (s v) / h1 with s = (2 atan2(n, d.w)) / n for n >= 1e-8 and s = 2 otherwise.  The angular speed is |w(f)|, the
+ *           angular acceleration |w(f) - w(f-1)| / ((t(f) - t(f-2)) / 2), w(f-1) from q(f-1), q(f-2) and h2.
+ *             [0:3]  hand speed, acceleration, jerk            [3:6]   elbow speed, acceleration, jerk
+ *             [6:9]  angular speed of q_l, q_u, q_h            [9:12]  angular acceleration of q_l, q_u, q_h
+ *   Row validity.  A row is all or nothing: it holds the 12 values iff f - s_r >= 3, every pose value used from rows f-3 .. f is finite
+ *           (for target rows: every target of those rows), h1, h2 and h3 are finite and > 0 (a repeated or backward stamp is not
+ *           differenced) and all 12 results are finite; otherwise all 12 are NaN.
+ *   motion_dev [n_sets, F, APE_MOTION_WIDTH] of out_dtype (APE_F32: the float64 value rounded once), or NULL.
+ *   acc_dev f64 [n_sets, R, APE_MOTION_ACC_WIDTH]: [3k], [3k+1], [3k+2] for k = 0..11 the sum, the sum of squares and the maximum of value
+ *           k over the support of recording r, the frames with f - s_r >= skip + 3; [36] frames of the support that were summed, [37]
+ *           frames of the support that were left out (NaN rows), which contribute exact zeros.  [36] + [37] = max(0, e_r - s_r - skip - 3),
+ *           the same in every set; an empty support gives zeros.  No floating-point atomics; the order of summation is fixed by F, the
+ *           starts and n_sets only, so the same inputs give the same bits, and each set's record has the bits of a call with n_sets = 1 on
+ *           that set alone.  Raw accumulators, so pieces of a recording merge on the host (score.py: merge_motion).
+ * Needs no model handle, runs on the current HIP device and does not wait; the host arrays have been consumed when it returns; staging
+ * slots as ape_score_rows keeps them (this file's own: the first call of a size allocates, later ones do not).  Two launches; no
+ * workgroup waits for another.  Refused with APE_ERR_INVALID_ARG on the host, before anything is written: NULL rows_dev / seg_starts_host /
+ * acc_dev; F < 1, R < 1, bad starts, skip < 0; an unknown kind, dtype or layout, APE_LAYOUT_NONE; rows_stride below the row width; n_sets
+ * outside 1 .. 64; n_sets > 1 with set_stride < F * rows_stride; APE_ROWS_TARGETS with NULL bodies_host or n_bodies not 1 or R; motion_dev
+ * or acc_dev equal to an input (or to each other); a capturing stream. */
+#define APE_MOTION_WIDTH      12
+#define APE_MOTION_ACC_WIDTH  38
+#define APE_ROWS_MSG      0   /* [25] message columns (compose_msg.py:72-78) */
+#define APE_ROWS_EST      1   /* [21 | 14] est rows, as APE_TRUTH_EST */
+#define APE_ROWS_TARGETS  2   /* [O] de-normalised NN targets, converted as ape_score_rows converts truth */
+int ape_motion_sums(int32_t layout, const void* rows_dev, int32_t rows_kind, int32_t rows_stride, int32_t rows_dtype,
+                    int32_t n_sets, int64_t set_stride, int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t skip,
+                    const double* times_dev /* f64 [F] or NULL */, const double* bodies_host, int32_t n_bodies,
+                    void* motion_dev /* [n_sets, F, 12] of out_dtype, or NULL */, int32_t out_dtype,
+                    double* acc_dev /* f64 [n_sets, R, 38] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
