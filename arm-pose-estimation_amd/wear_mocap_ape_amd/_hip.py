@@ -35,6 +35,7 @@ BODY_ACC_WIDTH = 46               # APE_BODY_ACC_WIDTH (ape_body_sums, DESIGN.md
 BODY_ROT_MSG, BODY_ROT_TRUTH = 0, 1         # APE_BODY_ROT_*
 MOTION_WIDTH, MOTION_ACC_WIDTH = 12, 38     # APE_MOTION_WIDTH, APE_MOTION_ACC_WIDTH (ape_motion_sums)
 ROWS_MSG, ROWS_EST, ROWS_TARGETS = 0, 1, 2  # APE_ROWS_*
+HIST_MAX_BINS, HIST_MAX_WIDTH = 256, 16     # APE_HIST_MAX_BINS, APE_HIST_MAX_WIDTH (ape_score_hist)
 FLAG_ANY_PLACEMENT, FLAG_NO_XCD_CLASSES, FLAG_ALT_FORM = 0x08000000, 0x02000000, 0x01000000    # exchange-form selectors (A/B runs, tests)
 FLAG_IN_XCD_PLAIN = 0x00400000      # opt-in: plain hand-over stores inside an XCD-pure cluster (the default is write-through)
 KERNEL_AUTO, KERNEL_TILE16, KERNEL_CLUSTER, KERNEL_CLUSTER_GEN1, KERNEL_AUTO_GEN1 = 0, 1, 2, 3, 4
@@ -237,6 +238,10 @@ SIGNATURES["ape_rebody_rows"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c
 SIGNATURES["ape_motion_sums"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_void_p,
                                            C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p,
                                            C.c_void_p])
+# counts of per-frame values over fixed edges: values + dtype, width, n_sets, set_stride (int64), F, frame_stride (int64),
+# n_groups, group_stride (int64), starts_host, R, trim_host, edges_host, n_bins, hist, HIP stream
+SIGNATURES["ape_score_hist"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
+                                          C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
 
 _lib = None
 

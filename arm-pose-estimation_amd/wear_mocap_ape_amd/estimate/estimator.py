@@ -649,6 +649,25 @@ class Estimator:
             return score.score_rows(self._layout, out, truth, truth_kind, spread, starts, skip, bodies)
         return score.score_lags(self._layout, out, truth, lags, truth_kind, spread, starts, skip, bodies, rec_lags, per_frame=True)
 
+    def error_distribution(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
+                           edges=None, bins=64):
+        """The shape of a replay's errors: ``score_recording``'s per-frame rows -- with ``rec_lags`` at each recording's
+        own lag, the sweep ``(0, 0)`` with offsets -- counted over ``edges`` per recording on the device (``score.hist_rows`` over
+        ``score.lag_trim``'s windows: the frames the accumulators cover).  ``edges``: ``[B + 1]`` or ``[7, B + 1]``, default
+        ``score.default_edges("score", bins)``; the other arguments are ``score_recording``'s.  Returns ``(hist, edges, acc)``: int64
+        ``[R, 7, B + 3]`` and float64 ``[R, 25]`` on the device, the edges float64 ``[7, B + 1]`` on the host (``score.quantiles``,
+        ``fraction_within``, ``pit``, ``summarise_hist``, ``merge_hist``)."""
+        from wear_mocap_ape_amd import score
+        skip = self._sequence_len - 1 if skip is None else skip
+        if rec_lags is None:
+            rows, acc = self.score_recording(out, truth, spread, starts, skip, bonemaps, truth_kind)
+        else:
+            rows, acc = self.score_recording(out, truth, spread, starts, skip, bonemaps, truth_kind, (0, 0), rec_lags)
+            rows, acc = rows[:, 0], acc[:, 0]
+        edges = score.default_edges("score", bins) if edges is None else score._edges(edges, score.SCORE_WIDTH)
+        trim = score.lag_trim(starts, int(rows.shape[0]), (0, 0), skip, rec_lags)
+        return score.hist_rows(rows, edges, starts, 0, trim), edges, acc
+
     def align_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=(0, 0),
                         mode="yaw", weights=(1, 1, 1, 0, 0)):
         """``score.align_frame`` with this estimator's layout and body and ``score_recording``'s defaults: each recording's lag (over the

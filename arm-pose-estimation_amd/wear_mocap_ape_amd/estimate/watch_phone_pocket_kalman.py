@@ -353,6 +353,12 @@ class WatchPhonePocketKalman(Estimator):
         return super().score_recording(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind, lags,
                                        rec_lags)
 
+    def error_distribution(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
+                           edges=None, bins=64):
+        """``Estimator.error_distribution`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
+        return super().error_distribution(out, truth, spread, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind,
+                                          rec_lags, edges, bins)
+
     def motion_recording(self, out, starts=None, skip=None, times=None, per_frame=False):
         """``Estimator.motion_recording`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
         return super().motion_recording(out, starts, self.__win_size + 1 if skip is None else skip, times, per_frame)

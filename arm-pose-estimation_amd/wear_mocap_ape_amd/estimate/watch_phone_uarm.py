@@ -141,6 +141,11 @@ class WatchPhoneUarm(Estimator):
         """``Estimator.score_recording`` for ``[F, 25]`` FK replays (no cold-start frames: ``skip`` defaults to 0; no spread record)"""
         return super().score_recording(out, truth, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind, lags, rec_lags)
 
+    def error_distribution(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
+                           edges=None, bins=64):
+        """``Estimator.error_distribution`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
+        return super().error_distribution(out, truth, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind, rec_lags, edges, bins)
+
     def motion_recording(self, out, starts=None, skip=None, times=None, per_frame=False):
         """``Estimator.motion_recording`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
         return super().motion_recording(out, starts, 0 if skip is None else skip, times, per_frame)

@@ -33,7 +33,14 @@ and scores what remains; ``body_sums_numpy`` and ``rebody_rows_numpy`` are the h
 What a longer ``smooth`` buys is a steadier arm: ``motion_sums`` takes the linear and angular speed, acceleration and jerk of every
 frame of any rows that state a pose -- messages, est rows or targets, many sets at once -- on the frames' own clock and sums them per
 recording (``ape_motion_sums``); it needs no truth.  ``summarise_motion`` and ``merge_motion`` work on the raw
-accumulators, ``motion_sums_numpy`` is the host statement."""
+accumulators, ``motion_sums_numpy`` is the host statement.
+
+A mean, an RMS and one worst frame say nothing of the shape between them: ``hist_rows`` counts any per-frame rows that lie on the
+device -- score rows, a lag sweep's, motion rows -- over fixed edges per recording and column (``ape_score_hist``).  The
+counts are integers and add across the pieces of a chained replay (``merge_hist``); ``quantiles``, ``fraction_within``, ``pit`` and
+``summarise_hist`` read medians, percentiles, the share of frames within 5 cm and the spread record's reliability curve off them on the
+host; ``default_edges`` and ``pit_edges`` make edges, ``lag_trim`` the windows of a lag sweep's common support; ``hist_numpy`` is the host
+statement."""
 import ctypes as C
 
 import numpy as np
@@ -1594,3 +1601,337 @@ def merge_motion(acc_a, acc_b) -> np.ndarray:
     cols = list(_MOTION_MAX_COLS)
     out[..., cols] = np.maximum(a[..., cols], b[..., cols])
     return out
+
+
+# ---- the shape of the errors: counts over fixed edges (ape_score_hist) --------------------------------------------------------
+# A histogram [..., W, B + 3] holds, per column, the B bins (e[b], e[b + 1]], then the slots below (v <= e[0]), above (v > e[B]) and NaN.
+HIST_MAX_BINS, HIST_MAX_WIDTH = _hip.HIST_MAX_BINS, _hip.HIST_MAX_WIDTH
+SCORE_HIST_NAMES = ERROR_NAMES + ("hand_d2", "elbow_d2")
+# default_edges' ranges, first and last edge per column.  "score": positions in metres, angles in radians (4 asin reaches 2 pi).  "motion":
+# speed, acceleration and jerk of a position in m / s^k, angular speed and acceleration in rad / s^k; on the index clock the same
+# numbers are per frame, and the edges want scaling by the frame rate's powers.
+_SCORE_RANGES = ((1e-4, 10.0), (1e-4, 10.0), (1e-5, 6.4), (1e-5, 6.4), (1e-5, 6.4))
+_MOTION_RANGES = ((1e-4, 1e2), (1e-3, 1e4), (1e-2, 1e6)) * 2 + ((1e-4, 1e3),) * 3 + ((1e-3, 1e5),) * 3
+_POSITION_MARKS = (0.05, 0.10)                          # the thresholds pose papers print: edges of the position columns, bit for bit
+
+
+def chi2_3_cdf(x: float) -> float:
+    """the CDF of chi^2 with 3 degrees of freedom in closed form: erf(sqrt(x / 2)) - sqrt(2 x / pi) exp(-x / 2)"""
+    import math
+    return math.erf(math.sqrt(x / 2.0)) - math.sqrt(2.0 * x / math.pi) * math.exp(-x / 2.0) if x > 0.0 else 0.0
+
+
+def pit_edges(cells: int) -> np.ndarray:
+    """``cells`` edges (``cells - 1`` bins): the chi^2(3) quantiles at the levels ``k / cells``, ``k = 0 .. cells - 1`` (the first is
+    0), by bisection on ``chi2_3_cdf``; a level of 0.5 or 0.9 gives ``CHI2_3_Q50`` / ``CHI2_3_Q90`` themselves.  A ``d^2`` column counted
+    over them is the probability integral transform of the spread record in ``cells`` cells of equal probability (``pit``)."""
+    cells = int(cells)
+    if not 2 <= cells <= HIST_MAX_BINS + 1:
+        raise UserWarning(f"pit_edges: between 2 and {HIST_MAX_BINS + 1} cells, got {cells}")
+    e = np.zeros(cells)
+    for k in range(1, cells):
+        level = k / cells
+        if level == 0.5 or level == 0.9:
+            e[k] = CHI2_3_Q50 if level == 0.5 else CHI2_3_Q90
+            continue
+        lo, hi = 0.0, 128.0
+        while True:
+            mid = 0.5 * (lo + hi)
+            if mid <= lo or mid >= hi:
+                break
+            if chi2_3_cdf(mid) < level:
+                lo = mid
+            else:
+                hi = mid
+        e[k] = hi
+    return e
+
+
+def default_edges(kind: str, bins: int = 64) -> np.ndarray:
+    """float64 ``[W, bins + 1]`` edges for ``kind`` ``"score"`` (``score_rows``' 7 columns) or ``"motion"`` (``motion_sums``' 12):
+    geometric spacing per column in that column's unit -- positions 1e-4 .. 10 m, angles 1e-5 .. 6.4 rad, speeds 1e-4 .. 1e2 m/s,
+    accelerations 1e-3 .. 1e4 m/s^2, jerks 1e-2 .. 1e6 m/s^3, angular speeds 1e-4 .. 1e3 rad/s, angular accelerations 1e-3 .. 1e5
+    rad/s^2 (what lies outside is counted below and above).  The inner edge nearest to 0.05 and to 0.10 of the position columns is moved
+    onto them, so that ``fraction_within`` answers 5 cm and 10 cm.  The two ``d^2`` columns of ``"score"`` get ``pit_edges(bins + 1)``."""
+    bins = int(bins)
+    if kind not in ("score", "motion"):
+        raise UserWarning(f"default_edges: kind must be 'score' or 'motion', got {kind!r}")
+    if not 8 <= bins <= HIST_MAX_BINS:
+        raise UserWarning(f"default_edges: between 8 and {HIST_MAX_BINS} bins, got {bins}")
+    ranges = _SCORE_RANGES if kind == "score" else _MOTION_RANGES
+    rows = []
+    for c, (a, b) in enumerate(ranges):
+        e = np.exp(np.linspace(np.log(a), np.log(b), bins + 1))
+        e[0], e[-1] = a, b
+        if kind == "score" and c < 2:
+            at = [1 + int(np.argmin(np.abs(np.log(e[1:-1]) - np.log(mark)))) for mark in _POSITION_MARKS]
+            if len(set(at)) != len(at):
+                raise UserWarning(f"default_edges: {bins} bins do not keep the marks {_POSITION_MARKS} apart")
+            e[at] = _POSITION_MARKS
+        rows.append(e)
+    if kind == "score":
+        rows += [pit_edges(bins + 1)] * 2
+    out = np.ascontiguousarray(np.stack(rows))
+    if not (np.diff(out, axis=1) > 0.0).all():
+        raise UserWarning(f"default_edges: {bins} bins do not keep the marks apart")
+    return out
+
+
+def _edges(edges, W: int) -> np.ndarray:
+    """float64 ``[W, B + 1]`` of ``[B + 1]`` (for all columns) or ``[W, B + 1]``"""
+    e = np.asarray(edges, dtype=np.float64)
+    if e.ndim == 1:
+        e = np.broadcast_to(e, (W, e.shape[0]))
+    if e.ndim != 2 or e.shape[0] != W or e.shape[1] < 2:
+        raise UserWarning(f"edges: expected [B+1] or [{W}, B+1] with B >= 1, got {tuple(np.shape(edges))}")
+    return np.ascontiguousarray(e)
+
+
+def _trims(R: int, skip: int, trim) -> np.ndarray:
+    """int32 ``[R, 2]``: ``trim`` (None: zeros) with ``skip`` added at the head"""
+    if int(skip) < 0:
+        raise UserWarning(f"skip {skip} is negative")
+    t = np.zeros((R, 2), dtype=np.int64) if trim is None else np.asarray(trim, dtype=np.int64).reshape(-1, 2).copy()
+    if t.shape[0] != R:
+        raise UserWarning(f"trim: {t.shape[0]} rows for {R} recordings")
+    t[:, 0] += int(skip)
+    if (t < 0).any() or (t > 2 ** 31 - 1).any():
+        raise UserWarning("trim: between 0 and 2^31 - 1")
+    return np.ascontiguousarray(t.astype(np.int32))
+
+
+def lag_trim(starts, F: int, lags, skip: int = 0, rec_lags=None) -> np.ndarray:
+    """int32 ``[R, 2]``: what to trim off the head and the tail of every recording so that its window is the common support of the
+    sweep ``lags=(lo, hi)`` with offsets ``rec_lags`` (``score_lags``): ``max(skip, o_r + hi, 0)`` and ``max(0, -(o_r + lo))``.  With
+    it the slots of ``hist_rows(score, ..., trim=)`` add up to ``acc[r, j, 15] + acc[r, j, 16]`` for every ``j``."""
+    st = _recording_starts(starts)
+    if st.shape[0] < 1 or int(F) < 1:
+        raise UserWarning("lag_trim: at least one recording and one frame")
+    lo, hi, off = _sweep(lags, int(st.shape[0]), rec_lags)
+    o = off.astype(np.int64)
+    out = np.stack([np.maximum(np.maximum(int(skip), o + hi), 0), np.maximum(0, -(o + lo))], axis=1)
+    return np.ascontiguousarray(out.astype(np.int32))
+
+
+def _slots(v, e) -> np.ndarray:
+    """the slot of every value of ``v`` over the edges ``e [B + 1]``: searchsorted from the left counts the edges below ``v``"""
+    B = e.shape[0] - 1
+    i = np.searchsorted(e, v, side="left")
+    return np.where(np.isnan(v), B + 2, np.where(i == 0, B, np.where(i > B, B + 1, i - 1)))
+
+
+def hist_numpy(values, edges, starts=None, skip: int = 0, trim=None) -> np.ndarray:
+    """The host statement of ``hist_rows``: ``np.searchsorted(e, v, side="left")`` and ``np.bincount`` per recording, group and column.
+    ``values``: ``[F, W]``, ``[F, G, W]`` or ``[C, F, G, W]`` (float32 is widened); returns int64 ``[(C,) R, (G,) W, B + 3]``."""
+    v = np.asarray(values)
+    if v.ndim not in (2, 3, 4):
+        raise UserWarning(f"values: expected [F, W], [F, G, W] or [C, F, G, W], got {tuple(v.shape)}")
+    nd = v.ndim
+    v = v.astype(np.float64)
+    v = v[:, None, :] if nd == 2 else v
+    v = v[None] if nd < 4 else v
+    Cn, F, G, W = v.shape
+    e = _edges(edges, W)
+    B = e.shape[1] - 1
+    st = _recording_starts(starts).astype(np.int64)
+    R = st.shape[0]
+    tr = _trims(R, skip, trim).astype(np.int64)
+    ends = np.r_[st[1:], F]
+    out = np.zeros((Cn, R, G, W, B + 3), dtype=np.int64)
+    for r in range(R):
+        a, b = int(st[r] + tr[r, 0]), int(ends[r] - tr[r, 1])
+        if a >= b:
+            continue
+        for c in range(Cn):
+            for g in range(G):
+                for w in range(W):
+                    out[c, r, g, w] = np.bincount(_slots(v[c, a:b, g, w], e[w]), minlength=B + 3)
+    out = out[0] if nd < 4 else out
+    return out[:, 0] if nd == 2 else out
+
+
+def _hist_view(t):
+    """(tensor, C, F, G, W, set / frame / group stride in elements) of a device view ``[F, W]``, ``[F, G, W]`` or ``[C, F, G, W]`` whose
+    last dimension is contiguous and whose frames, groups and sets lie apart (``_rows_view``'s rules); anything else is copied"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() not in (2, 3, 4) or min(t.shape) < 1:
+        raise UserWarning("values: expected a device tensor [F, W], [F, G, W] or [C, F, G, W]")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"values: float32 or float64, got {t.dtype}")
+    v = t[:, None, :] if t.dim() == 2 else t
+    v = v[None] if v.dim() == 3 else v
+    Cn, F, G, W = (int(n) for n in v.shape)
+    if not 1 <= W <= HIST_MAX_WIDTH:
+        raise UserWarning(f"values: between 1 and {HIST_MAX_WIDTH} columns, got {W}")
+    if not 1 <= G <= _hip.SCORE_MAX_LAGS or not 1 <= Cn <= _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"values: at most {_hip.SCORE_MAX_LAGS} groups and {_hip.POST_MAX_CONFIGS} sets, got {G} and {Cn}")
+    ss, fs, gs, ws = (int(s) for s in v.stride())
+    fs = fs if F > 1 else max(fs, W)
+    if (W > 1 and ws != 1) or fs < W or (G > 1 and gs < W) or (Cn > 1 and ss < F * fs):
+        v = v.contiguous()
+        ss, fs, gs, ws = (int(s) for s in v.stride())
+        fs = max(fs, W)
+    return v, Cn, F, G, W, (ss if Cn > 1 else 0), fs, (gs if G > 1 else 0)
+
+
+def hist_rows(values, edges, starts=None, skip: int = 0, trim=None):
+    """Counts of per-frame values over fixed edges, per recording and column, on the device (``ape_score_hist``).  ``values``: a device
+    ``[F, W]``, ``[F, G, W]`` or ``[C, F, G, W]`` view, float32 or float64, ``W <= 16``, ``G <= 65``, ``C <= 64``: ``score_rows``'
+    ``[F, 7]``, ``score_lags``' ``[F, L, 7]``, ``motion_sums``' ``[C, F, 12]`` (as ``values[:, :, None]``), column slices and strided
+    views go in without a copy.  ``edges``: float64 ``[B + 1]`` for all columns or ``[W, B + 1]``, strictly increasing, ``B <= 256``
+    (``default_edges``, ``pit_edges``).  ``starts``: the recordings' first frames; recording ``r``'s window is its frames less
+    ``skip + trim[r, 0]`` at the head and ``trim[r, 1]`` at the tail (``trim``: ``[R, 2]``, ``lag_trim``).  Returns int64
+    ``[(C,) R, (G,) W, B + 3]`` on the device: per column the ``B`` bins ``(e[b], e[b + 1]]``, then the counts below (``v <= e[0]``),
+    above (``v > e[B]``) and NaN; every row sums to the window's length.  Integer counts: the same inputs give the same bits, and pieces
+    add (``merge_hist``).  The call does not wait for the device."""
+    nd = values.dim() if isinstance(values, torch.Tensor) else 0
+    v, Cn, F, G, W, ss, fs, gs = _hist_view(values)
+    e = _edges(edges, W)
+    B = int(e.shape[1]) - 1
+    if B > HIST_MAX_BINS:
+        raise UserWarning(f"edges: at most {HIST_MAX_BINS} bins, got {B}")
+    st = _recording_starts(starts)
+    R = int(st.shape[0])
+    tr = _trims(R, skip, trim)
+    dev = v.device
+    with torch.cuda.device(dev):
+        hist = torch.empty((Cn, max(R, 1), G, W, B + 3), dtype=torch.int64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_score_hist(C.c_void_p(v.data_ptr()), _f64(v.dtype), W, Cn, ss, F, fs, G, gs, C.c_void_p(st.ctypes.data), R,
+                                             C.c_void_p(tr.ctypes.data), C.c_void_p(e.ctypes.data), B, C.c_void_p(hist.data_ptr()), stream),
+                   "ape_score_hist")
+    hist = hist[0] if nd < 4 else hist
+    return hist[:, 0] if nd == 2 else hist
+
+
+def _hist_host(hist) -> np.ndarray:
+    h = hist.detach().cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
+    if h.ndim < 1 or h.shape[-1] < 4 or not np.issubdtype(h.dtype, np.integer):
+        raise UserWarning(f"expected an integer histogram [..., B + 3], got {h.dtype} {tuple(h.shape)}")
+    return h.astype(np.int64)
+
+
+def merge_hist(hist_a, hist_b) -> np.ndarray:
+    """the histograms of two pieces of the same recordings over the same edges as one: the sum (int64, on the host)"""
+    a, b = _hist_host(hist_a), _hist_host(hist_b)
+    if a.shape != b.shape:
+        raise UserWarning(f"merge_hist: {tuple(a.shape)} and {tuple(b.shape)} histograms")
+    return a + b
+
+
+def _hist_and_edges(hist, edges):
+    """(h int64 [..., W, B + 3], e float64 [W, B + 1], the ordered counts below | bins | above [..., W, B + 2])"""
+    h = _hist_host(hist)
+    if h.ndim < 2:
+        raise UserWarning(f"expected a histogram [..., W, B + 3], got {tuple(h.shape)}")
+    e = _edges(edges, h.shape[-2])
+    B = e.shape[1] - 1
+    if h.shape[-1] != B + 3:
+        raise UserWarning(f"a histogram of {h.shape[-1] - 3} bins against {B + 1} edges")
+    return h, e, np.concatenate([h[..., B:B + 1], h[..., :B], h[..., B + 1:B + 2]], axis=-1)
+
+
+def quantiles(hist, edges, q) -> dict:
+    """Quantiles read off a histogram ``[..., W, B + 3]`` over ``edges`` (``[B + 1]`` or ``[W, B + 1]``).  ``q``: a level in [0, 1] or a
+    sequence of them (the results then end in a dimension over them).  Over the ``n`` counted values that are not NaN, the value of
+    rank ``max(1, ceil(q n))`` in ascending order -- ``np.quantile(..., method="inverted_cdf")`` -- lies in a known bin ``(lo, hi]``.
+    Returns a dict of arrays ``[..., W(, Q)]``: ``lo`` and ``hi``, that bin's edges (the quantile of the values themselves lies between
+    them, always); ``value``, the rank placed linearly within the bin (the ``j``-th of the bin's ``c`` values at ``(j - 0.5) / c`` of
+    its width); ``clipped``: None, or ``"below"`` / ``"above"`` where the rank falls outside the edges, with ``e[0]`` / ``e[B]`` for all
+    three; and ``n [..., W]``.  NaN where ``n == 0``."""
+    h, e, ordered = _hist_and_edges(hist, edges)
+    B = e.shape[1] - 1
+    qs = np.atleast_1d(np.asarray(q, dtype=np.float64))
+    if qs.ndim != 1 or not ((qs >= 0.0) & (qs <= 1.0)).all():
+        raise UserWarning("quantiles: levels in [0, 1]")
+    n = ordered.sum(axis=-1)
+    cum = np.cumsum(ordered, axis=-1)
+    shape = n.shape + (qs.shape[0],)
+    value, lo, hi = (np.full(shape, np.nan) for _ in range(3))
+    clipped = np.full(shape, None, dtype=object)
+    for idx in np.ndindex(*n.shape):
+        if n[idx] == 0:
+            continue
+        ew = e[idx[-1]]
+        for k, level in enumerate(qs):
+            rank = max(1, int(np.ceil(level * n[idx])))
+            pos = int(np.searchsorted(cum[idx], rank, side="left"))      # the first slot whose cumulative count reaches the rank
+            if pos == 0 or pos == B + 1:
+                value[idx + (k,)] = lo[idx + (k,)] = hi[idx + (k,)] = ew[0] if pos == 0 else ew[B]
+                clipped[idx + (k,)] = "below" if pos == 0 else "above"
+                continue
+            a, b = ew[pos - 1], ew[pos]
+            j, c = rank - (cum[idx][pos - 1]), ordered[idx][pos]
+            lo[idx + (k,)], hi[idx + (k,)] = a, b
+            value[idx + (k,)] = min(max(a + (b - a) * ((j - 0.5) / c), a), b)
+    res = {"value": value, "lo": lo, "hi": hi, "clipped": clipped}
+    if np.ndim(q) == 0:
+        res = {k: v[..., 0] for k, v in res.items()}
+    res["n"] = n
+    return res
+
+
+def fraction_within(hist, edges, thresholds) -> np.ndarray:
+    """The share of the counted values that are not NaN with ``v <=`` each threshold: float64 ``[..., W, T]`` of a histogram
+    ``[..., W, B + 3]``.  ``thresholds``: ``[T]`` for all columns or ``[W, T]``; each must be one of its column's edges bit for bit --
+    a threshold between edges is refused, not interpolated (choose the edges to hold it).  NaN where nothing was counted."""
+    h, e, ordered = _hist_and_edges(hist, edges)
+    W, B = e.shape[0], e.shape[1] - 1
+    t = np.asarray(thresholds, dtype=np.float64)
+    t = np.broadcast_to(np.atleast_1d(t), (W, np.atleast_1d(t).shape[0])) if t.ndim < 2 else t
+    if t.ndim != 2 or t.shape[0] != W:
+        raise UserWarning(f"thresholds: expected [T] or [{W}, T], got {tuple(np.shape(thresholds))}")
+    n = ordered.sum(axis=-1).astype(np.float64)
+    cum = np.cumsum(ordered, axis=-1)                                    # cum[..., i]: values <= e[i], i = 0 .. B
+    out = np.full(n.shape + (t.shape[1],), np.nan)
+    ebits = np.ascontiguousarray(e).view(np.int64)
+    for w in range(W):
+        for k in range(t.shape[1]):
+            hit = np.flatnonzero(ebits[w] == np.float64(t[w, k]).view(np.int64))
+            if hit.shape[0] != 1:
+                raise UserWarning(f"fraction_within: {t[w, k]!r} is not an edge of column {w} (no interpolation between edges)")
+            with np.errstate(all="ignore"):
+                out[..., w, k] = np.where(n[..., w] > 0, cum[..., w, int(hit[0])] / n[..., w], np.nan)
+    return out
+
+
+def pit(hist_column) -> dict:
+    """The probability integral transform of a ``d^2`` column counted over ``pit_edges(cells)``: ``hist_column [..., cells + 2]`` (one
+    column of a histogram) -> a dict: ``cells`` int64 ``[..., cells]``, the counts per cell of equal probability (below and the first
+    bin, the inner bins, above); ``levels [cells - 1]`` = ``k / cells``; ``cumulative`` int64 ``[..., cells - 1]``, the values with
+    ``d^2 <=`` the quantile of each level, and ``coverage``, their share of ``n`` (NaN where ``n == 0``): the reliability curve of which
+    ``summarise``'s ``coverage50`` / ``coverage90`` are two points; ``n [...]`` values that are not NaN.  An honest spread record gives
+    flat cells and ``coverage == levels``."""
+    h = _hist_host(hist_column)
+    B = h.shape[-1] - 3
+    cells = np.concatenate([h[..., B:B + 1] + h[..., 0:1], h[..., 1:B], h[..., B + 1:B + 2]], axis=-1)
+    n = cells.sum(axis=-1)
+    cumulative = np.cumsum(cells, axis=-1)[..., :-1]
+    with np.errstate(all="ignore"):
+        coverage = np.where(n[..., None] > 0, cumulative / n[..., None].astype(np.float64), np.nan)
+    return {"cells": cells, "levels": np.arange(1, B + 1) / (B + 1), "cumulative": cumulative, "coverage": coverage, "n": n}
+
+
+def summarise_hist(hist, edges, names=None) -> list:
+    """``hist [R, W, B + 3]`` (one set's, one group's slice) over ``edges`` -> per recording a dict: ``window``, the frames of the
+    recording's window, and per column name ``nan`` (frames counted as NaN), ``median``, ``p90`` and ``p95`` (``quantiles``' ``value``;
+    NaN where nothing was counted) with ``median_bin`` / ``p90_bin`` / ``p95_bin``, the ``(lo, hi)`` they lie between.  ``names``
+    defaults to ``SCORE_HIST_NAMES`` for 7 columns and ``MOTION_NAMES`` for 12."""
+    h, e, _ = _hist_and_edges(hist, edges)
+    if h.ndim != 3:
+        raise UserWarning(f"summarise_hist: expected [R, W, B + 3], got {tuple(h.shape)}")
+    W = h.shape[1]
+    if names is None:
+        names = {len(SCORE_HIST_NAMES): SCORE_HIST_NAMES, len(MOTION_NAMES): MOTION_NAMES}.get(W)
+    if names is None or len(names) != W:
+        raise UserWarning(f"summarise_hist: {W} names for {W} columns")
+    qt = quantiles(h, e, (0.5, 0.9, 0.95))
+    res = []
+    for r in range(h.shape[0]):
+        d = {"window": int(h[r, 0].sum()), "nan": {}}
+        for k, key in enumerate(("median", "p90", "p95")):
+            d[key] = {name: float(qt["value"][r, w, k]) for w, name in enumerate(names)}
+            d[key + "_bin"] = {name: (float(qt["lo"][r, w, k]), float(qt["hi"][r, w, k])) for w, name in enumerate(names)}
+        for w, name in enumerate(names):
+            d["nan"][name] = int(h[r, w, -1])
+        res.append(d)
+    return res

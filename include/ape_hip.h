@@ -1194,6 +1194,46 @@ int ape_motion_sums(int32_t layout, const void* rows_dev, int32_t rows_kind, int
                     void* motion_dev /* [n_sets, F, 12] of out_dtype, or NULL */, int32_t out_dtype,
                     double* acc_dev /* f64 [n_sets, R, 38] */, void* stream);
 
+/* ---- the shape of the errors: a histogram per recording and column over fixed edges (additive in ABI 7) ----------------------
+ * replaces: nothing; the reference has no counterpart.  The accumulators of ape_score_rows and ape_motion_sums give a mean, an RMS and one
+ * worst frame; a median, a 95th percentile, the share of frames within 5 cm and the coverage of the spread record at every level are read
+ * off counts over fixed edges.  Counts are raw, integers, and add across the pieces of a chained replay (score.py: merge_hist, quantiles,
+ * fraction_within, pit).  ape_score_hist counts any per-frame rows that lie on the device: ape_score_rows' [F, 7], ape_score_lags'
+ * [F, L, 7], ape_motion_sums' [n_sets, F, 12], strided views of wider rows.
+ *   Values.  Value (c, f, g, w), c < n_sets, f < F, g < n_groups, w < width, is the element c * set_stride + f * frame_stride +
+ *           g * group_stride + w of values_dev, of values_dtype (APE_F32 is widened exactly).  set_stride is not read with n_sets == 1,
+ *           group_stride is not read with n_groups == 1.
+ *   Window. Recording r holds the frames [s_r, e_r) (seg_starts_host, as ape_score_rows); its window is [s_r + trim[r][0], e_r - trim[r][1])
+ *           (trim_host i32 [R, 2], both >= 0; NULL: zeros).  A window that is empty or inverted gives exact zeros.  The entry knows nothing
+ *           of lags: the trims of a lag sweep's common support are made by the caller (score.py: lag_trim).
+ *   Bins.   Column w has its own strictly increasing finite edges e[0 .. B] = edges_host[w][0 .. n_bins], B = n_bins.  Bins are closed on
+ *           the right.  A value v is counted in exactly one of the B + 3 slots of its column:
+ *             slot b, 0 <= b < B   e[b] < v <= e[b+1]
+ *             slot B   (below)     v <= e[0]
+ *             slot B+1 (above)     v > e[B], +inf included
+ *             slot B+2             v is NaN
+ *           Comparisons only, no arithmetic on v: -inf and -0.0 fall where <= puts them.  On the host: np.searchsorted(e, v, side="left").
+ *           Every row [c][r][g][w][:] of the output therefore sums to the length of recording r's window.
+ *   hist_dev i64 [n_sets, R, n_groups, width, n_bins + 3], all of it written by the call (the caller need not zero it: the zeroing is
+ *           ordered on the stream in front of the kernel).  Integer counts, added with 64-bit integer atomics: the same inputs give the same
+ *           bits whatever the order, and each (set, group) slice has the bits of a call on that slice alone.
+ * Needs no model handle, runs on the current HIP device and does not wait; the host arrays have been consumed when it returns; staging
+ * slots as ape_score_rows keeps them (this file's own).  One memset and one launch; no workgroup waits for another.  Refused with
+ * APE_ERR_INVALID_ARG on the host, before anything is written: NULL values_dev / seg_starts_host / edges_host / hist_dev; F < 1, R < 1, bad
+ * starts, a negative trim; width outside 1 .. APE_HIST_MAX_WIDTH; n_bins outside 1 .. APE_HIST_MAX_BINS; n_sets outside 1 ..
+ * APE_POST_MAX_CONFIGS; n_groups outside 1 .. APE_SCORE_MAX_LAGS; frame_stride < width; n_groups > 1 with group_stride < width; n_sets > 1
+ * with set_stride < F * frame_stride; an unknown dtype; a pointer not aligned to its element; edges that are not finite or not strictly
+ * increasing; more than 2^31 - 1 output elements; values whose extent does not fit 63 bits; hist_dev overlapping values_dev; a capturing
+ * stream. */
+#define APE_HIST_MAX_BINS   256
+#define APE_HIST_MAX_WIDTH  16
+int ape_score_hist(const void* values_dev, int32_t values_dtype, int32_t width,
+                   int32_t n_sets, int64_t set_stride, int32_t F, int64_t frame_stride,
+                   int32_t n_groups, int64_t group_stride,
+                   const int32_t* seg_starts_host, int32_t R, const int32_t* trim_host /* [R, 2] or NULL */,
+                   const double* edges_host /* f64 [width, n_bins + 1] */, int32_t n_bins,
+                   int64_t* hist_dev /* [n_sets, R, n_groups, width, n_bins + 3] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
