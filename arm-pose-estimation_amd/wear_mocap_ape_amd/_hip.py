@@ -36,6 +36,7 @@ BODY_ROT_MSG, BODY_ROT_TRUTH = 0, 1         # APE_BODY_ROT_*
 MOTION_WIDTH, MOTION_ACC_WIDTH = 12, 38     # APE_MOTION_WIDTH, APE_MOTION_ACC_WIDTH (ape_motion_sums)
 ROWS_MSG, ROWS_EST, ROWS_TARGETS = 0, 1, 2  # APE_ROWS_*
 HIST_MAX_BINS, HIST_MAX_WIDTH = 256, 16     # APE_HIST_MAX_BINS, APE_HIST_MAX_WIDTH (ape_score_hist)
+ANGLE_WIDTH, ANGLE_ACC_WIDTH = 7, 71        # APE_ANGLE_WIDTH, APE_ANGLE_ACC_WIDTH (ape_joint_angles)
 FLAG_ANY_PLACEMENT, FLAG_NO_XCD_CLASSES, FLAG_ALT_FORM = 0x08000000, 0x02000000, 0x01000000    # exchange-form selectors (A/B runs, tests)
 FLAG_IN_XCD_PLAIN = 0x00400000      # opt-in: plain hand-over stores inside an XCD-pure cluster (the default is write-through)
 KERNEL_AUTO, KERNEL_TILE16, KERNEL_CLUSTER, KERNEL_CLUSTER_GEN1, KERNEL_AUTO_GEN1 = 0, 1, 2, 3, 4
@@ -242,6 +243,12 @@ SIGNATURES["ape_motion_sums"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c
 # n_groups, group_stride (int64), starts_host, R, trim_host, edges_host, n_bins, hist, HIP stream
 SIGNATURES["ape_score_hist"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_int32, C.c_int64,
                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
+# joint angles of every frame and their errors against truth: layout, rows + kind + stride + dtype, n_sets, set_stride
+# (int64), truth + kind + stride + dtype, rec_lag_host, F, starts_host, R, skip, bodies_host, n_bodies, min_swing, angles, errors, out dtype,
+# acc, HIP stream
+SIGNATURES["ape_joint_angles"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
+                                            C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
+                                            C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
 
 _lib = None
 

@@ -723,6 +723,27 @@ class Estimator:
         bodies = self._body_measurements if bonemaps is None else bonemaps
         return score.motion_sums(self._layout, truth, truth_kind, starts, skip, times, bodies)
 
+    # ---- joint angles (the reference has no counterpart) ----
+    def angles_recording(self, out, truth=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
+                         per_frame=False, min_swing=0.05):
+        """``score.joint_angles`` with this estimator's layout and body: the joint angles of ``out`` as ``process_recording`` returned it
+        (or ``repost``'s ``[C, F, 25]``) and, with ``truth`` (device ``[F, O]`` de-normalised targets, or est rows with
+        ``truth_kind="est"``), their errors, each recording at its own lag ``rec_lags``; ``skip`` defaults to ``score_recording``'s.
+        Returns ``(angles [F, 7] | None, errors [F, 7] | None, acc [R, 71])`` on the device (``score.summarise_angles``)."""
+        from wear_mocap_ape_amd import score
+        skip = self._sequence_len - 1 if skip is None else skip
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        return score.joint_angles(self._layout, out, "msg", truth, truth_kind, starts, skip, rec_lags, bodies, min_swing, per_frame)
+
+    def truth_angles(self, truth, truth_kind="targets", starts=None, skip=None, bonemaps=None, per_frame=False, min_swing=0.05):
+        """The truth's own joint angles -- its range of motion: ``score.joint_angles`` of ``truth`` (device ``[F, O]`` de-normalised
+        targets, or est rows with ``truth_kind="est"``) with this estimator's layout and body and ``angles_recording``'s defaults.
+        Returns ``(angles [F, 7] | None, None, acc [R, 71])``."""
+        from wear_mocap_ape_amd import score
+        skip = self._sequence_len - 1 if skip is None else skip
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        return score.joint_angles(self._layout, truth, truth_kind, None, "est", starts, skip, None, bodies, min_swing, per_frame)
+
     # ---- post-filter sweep (DESIGN.md 4.33; the reference has no counterpart) ----
     def repost(self, y, configs, starts=None, bonemaps=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
         """``score.post_sweep`` with this estimator's model and body: ``y`` device float32 ``[F, M, O]`` as

@@ -367,6 +367,16 @@ class WatchPhonePocketKalman(Estimator):
         """``Estimator.truth_motion`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
         return super().truth_motion(truth, truth_kind, starts, self.__win_size + 1 if skip is None else skip, times, bonemaps)
 
+    def angles_recording(self, out, truth=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
+                         per_frame=False, min_swing=0.05):
+        """``Estimator.angles_recording`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
+        return super().angles_recording(out, truth, starts, self.__win_size + 1 if skip is None else skip, bonemaps, truth_kind, rec_lags,
+                                        per_frame, min_swing)
+
+    def truth_angles(self, truth, truth_kind="targets", starts=None, skip=None, bonemaps=None, per_frame=False, min_swing=0.05):
+        """``Estimator.truth_angles`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
+        return super().truth_angles(truth, truth_kind, starts, self.__win_size + 1 if skip is None else skip, bonemaps, per_frame, min_swing)
+
     def align_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=(0, 0), mode="yaw",
                         weights=(1, 1, 1, 0, 0)):
         """``Estimator.align_recording`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""

@@ -154,6 +154,15 @@ class WatchPhoneUarm(Estimator):
         """``Estimator.truth_motion`` for FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
         return super().truth_motion(truth, truth_kind, starts, 0 if skip is None else skip, times, bonemaps)
 
+    def angles_recording(self, out, truth=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
+                         per_frame=False, min_swing=0.05):
+        """``Estimator.angles_recording`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
+        return super().angles_recording(out, truth, starts, 0 if skip is None else skip, bonemaps, truth_kind, rec_lags, per_frame, min_swing)
+
+    def truth_angles(self, truth, truth_kind="targets", starts=None, skip=None, bonemaps=None, per_frame=False, min_swing=0.05):
+        """``Estimator.truth_angles`` for FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
+        return super().truth_angles(truth, truth_kind, starts, 0 if skip is None else skip, bonemaps, per_frame, min_swing)
+
     def align_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=(0, 0), mode="yaw",
                         weights=(1, 1, 1, 0, 0)):
         """``Estimator.align_recording`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""

@@ -40,8 +40,13 @@ device -- score rows, a lag sweep's, motion rows -- over fixed edges per recordi
 counts are integers and add across the pieces of a chained replay (``merge_hist``); ``quantiles``, ``fraction_within``, ``pit`` and
 ``summarise_hist`` read medians, percentiles, the share of frames within 5 cm and the spread record's reliability curve off them on the
 host; ``default_edges`` and ``pit_edges`` make edges, ``lag_trim`` the windows of a lag sweep's common support; ``hist_numpy`` is the host
-statement."""
+statement.
+
+``joint_angles`` states every frame as the angles its users ask in (elbow flexion, forearm twist, shoulder elevation and its plane,
+humeral twist, hips yaw) with their errors against truth and their sums per recording; ``summarise_angles``,
+``merge_angles`` and ``angle_edges`` go with it, ``joint_angles_numpy`` is the host statement."""
 import ctypes as C
+import math
 
 import numpy as np
 import torch
@@ -1935,3 +1940,234 @@ def summarise_hist(hist, edges, names=None) -> list:
             d["nan"][name] = int(h[r, w, -1])
         res.append(d)
     return res
+
+
+# ---- joint angles of every frame, and their errors against truth (ape_joint_angles) ----------------------------------------
+# ``score_rows`` speaks in metres and whole-rotation angles; these state a pose as elbow flexion, forearm twist, shoulder elevation and its
+# plane, humeral twist and hips yaw -- a swing-twist split of each joint about the bone's long axis (local -x), NaN where an angle is not
+# conditioned (``min_swing``).
+ANGLE_WIDTH = _hip.ANGLE_WIDTH
+ANGLE_ACC_WIDTH = _hip.ANGLE_ACC_WIDTH
+ANGLE_NAMES = ("elbow_flexion", "hinge_azimuth", "forearm_twist", "shoulder_elevation", "elevation_plane", "humeral_twist", "hips_yaw")
+ANGLE_PERIODIC = (False, True, True, False, True, True, True)
+_ANGLE_MIN_COLS = tuple(range(2, 5 * ANGLE_WIDTH, 5))
+_ANGLE_MAX_COLS = tuple(range(3, 5 * ANGLE_WIDTH, 5)) + tuple(range(5 * ANGLE_WIDTH + 3, 10 * ANGLE_WIDTH, 5))
+
+
+def _min_swing(min_swing) -> float:
+    m = float(min_swing)
+    if not 0.0 <= m < np.pi / 2.0:
+        raise UserWarning(f"min_swing must lie in [0, pi / 2), got {min_swing!r}")
+    return m
+
+
+def _swing_twist(r):
+    """``(rho, n, swing, twist, azimuth)`` of quaternions ``r [n, 4]``, negated first where ``w < 0.0``: ``r = swing (x) twist`` about x"""
+    r = np.where((r[:, 0] < 0.0)[:, None], -r, r)
+    w, x, y, z = r[:, 0], r[:, 1], r[:, 2], r[:, 3]
+    rho, n = np.sqrt(w * w + x * x), np.sqrt(y * y + z * z)
+    return rho, n, 2.0 * np.arctan2(n, rho), 2.0 * np.arctan2(x, w), np.arctan2(y * x + z * w, y * w - z * x)
+
+
+def _row_angles(rows, layout: int, kind: str, body, min_swing: float) -> np.ndarray:
+    """the seven angles ``[F, 7]`` of rows of a kind, by the operations of include/ape_hip.h in their order (csrc/joint_angles.hip:
+    row_angles)"""
+    sh, sf = math.sin(min_swing / 2.0), math.sin(min_swing)    # (the C library's, as the entry computes them)
+    conj = np.array([1.0, -1.0, -1.0, -1.0])
+    with np.errstate(all="ignore"):
+        pose, ok = _pose_rows(rows, layout, kind, body)
+        q = [pose[:, 6:10], pose[:, 10:14], pose[:, 14:18]]
+        if kind != "targets":                               # only the quaternions of a message or an est row are read
+            ok = np.isfinite(pose[:, 6:18]).all(axis=1)
+        for j in range(3):
+            n = np.sqrt(((q[j][:, 0] * q[j][:, 0] + q[j][:, 1] * q[j][:, 1]) + q[j][:, 2] * q[j][:, 2]) + q[j][:, 3] * q[j][:, 3])
+            ok = ok & np.isfinite(n) & (n > 0.0)
+            q[j] = _unit4(q[j])
+        ql, qu, qh = q
+        e_rho, e_n, e_swing, e_twist, e_az = _swing_twist(_qmul(qu * conj, ql))
+        s = _qmul(qh * conj, qu)
+        s_rho, _, _, s_twist, _ = _swing_twist(s)
+        w, x, y, z = s[:, 0], s[:, 1], s[:, 2], s[:, 3]
+        dx = -((w * w + x * x) - (y * y + z * z))
+        dy = -(2.0 * (x * y + w * z))
+        dz = -(2.0 * (x * z - w * y))
+        h = np.sqrt(dx * dx + dz * dz)
+        qh = np.where((qh[:, 0] < 0.0)[:, None], -qh, qh)
+        nan = np.nan
+        a = np.stack([e_swing, np.where(e_n < sh, nan, e_az), np.where(e_rho < sh, nan, e_twist), np.arctan2(h, -dy),
+                      np.where(h < sf, nan, np.arctan2(dz, -dx)), np.where(s_rho < sh, nan, s_twist), 2.0 * np.arctan2(qh[:, 2], qh[:, 0])],
+                     axis=1)
+    a[~ok] = np.nan
+    return a
+
+
+def _kind_rows(rows, layout: int, kind: str, what: str):
+    w = _rows_width(layout, kind)
+    rows = np.asarray(rows)
+    if rows.ndim != 2 or rows.shape[1] < w:
+        raise UserWarning(f"{what}: expected [F, >= {w}], got {tuple(rows.shape)}")
+    return rows[:, :w].astype(np.float64)
+
+
+def joint_angles_numpy(rows, layout: int, kind: str = "msg", truth=None, truth_kind: str = "est", starts=None, skip: int = 0, rec_lags=None,
+                       bodies=None, min_swing: float = 0.05):
+    """The host statement of ``joint_angles`` for one set of rows: ``(angles [F, 7], errors [F, 7] | None, acc [R, 71])`` float64, plain
+    numpy with the operations of include/ape_hip.h in their order.  ``rows [F, >= w]`` of ``kind`` ``"msg"``, ``"est"`` or ``"targets"``
+    (through the numpy statement of the device's truth FK with ``bodies``), ``truth [F, >= w']`` of ``truth_kind`` likewise; float32 is
+    widened exactly.  Frame ``f`` of recording ``r`` is paired with truth row ``f - rec_lags[r]`` where that lies in the recording.
+    ``acc``: per angle the sum, sum of squares, minimum, maximum and count of its finite values over the frames with ``f - s_r >=
+    skip``, per error the sum, sum of magnitudes, sum of squares, largest magnitude and count, then the frames of the support (numpy's
+    summation order, so sums agree with the device to rounding)."""
+    m = _min_swing(min_swing)
+    rows = _kind_rows(rows, layout, kind, "rows")
+    F = rows.shape[0]
+    st = _recording_starts(starts).astype(np.int64)
+    R = st.shape[0]
+    rec = np.searchsorted(st, np.arange(F), side="right") - 1
+    ends = np.r_[st[1:], F]
+    b = None
+    if kind == "targets" or (truth is not None and truth_kind == "targets"):
+        b = _body_rows(bodies, R, "joint_angles bodies")
+        b = b[rec] if b.shape[0] > 1 else np.broadcast_to(b, (F, 9))
+    angles = _row_angles(rows, layout, kind, b, m)
+    errors = None
+    if truth is not None:
+        truth = _kind_rows(truth, layout, truth_kind, "truth")
+        if truth.shape[0] != F:
+            raise UserWarning(f"truth: {truth.shape[0]} rows for {F} frames")
+        tang = _row_angles(truth, layout, truth_kind, b, m)
+        _, _, off = _sweep((0, 0), R, rec_lags)
+        tf = np.arange(F) - off.astype(np.int64)[rec]
+        paired = (tf >= st[rec]) & (tf < ends[rec])
+        ta = np.where(paired[:, None], tang[np.clip(tf, 0, F - 1)], np.nan)
+        with np.errstate(all="ignore"):
+            errors = angles - ta
+            for k in range(ANGLE_WIDTH):
+                if ANGLE_PERIODIC[k]:
+                    d = errors[:, k]
+                    errors[:, k] = np.where(d > np.pi, d - 2.0 * np.pi, np.where(d <= -np.pi, d + 2.0 * np.pi, d))
+    acc = np.zeros((R, ANGLE_ACC_WIDTH))
+    for r, (s0, e0) in enumerate(zip(st, ends)):
+        lo = min(s0 + int(skip), e0)
+        acc[r, 70] = e0 - lo
+        for k in range(ANGLE_WIDTH):
+            v = angles[lo:e0, k]
+            v = v[np.isfinite(v)]
+            acc[r, 5 * k:5 * k + 5] = [v.sum(), (v * v).sum(), v.min(initial=np.inf), v.max(initial=-np.inf), v.shape[0]]
+            if errors is not None:
+                d = errors[lo:e0, k]
+                d = d[np.isfinite(d)]
+                acc[r, 35 + 5 * k:40 + 5 * k] = [d.sum(), np.abs(d).sum(), (d * d).sum(), np.abs(d).max(initial=0.0), d.shape[0]]
+    return angles, errors, acc
+
+
+def joint_angles(layout: int, rows, kind: str = "msg", truth=None, truth_kind: str = "est", starts=None, skip: int = 0, rec_lags=None,
+                 bodies=None, min_swing: float = 0.05, per_frame: bool = True, out_dtype=None):
+    """The joint angles of every frame, their errors against truth and their sums per recording (``ape_joint_angles``).  ``rows``: device
+    ``[F, >= w]`` or ``[C, F, >= w]`` (C sets of the same recordings, at most 64), float32 or float64, a strided view is taken without a
+    copy; ``kind``: ``"msg"``, ``"est"`` or ``"targets"`` (converted with ``bodies``), as ``motion_sums`` takes them.  ``truth``: device
+    ``[F, >= w']`` rows of ``truth_kind`` (any of the three; shared by all sets), or None; ``rec_lags``: int ``[R]``, frame ``f`` of
+    recording ``r`` is paired with truth row ``f - rec_lags[r]``.  ``starts``: the recordings' first frames; ``skip``: leading frames of
+    every recording left out of the accumulators.  ``min_swing`` (radians, in ``[0, pi / 2)``): below it the azimuth and twist angles of
+    a joint are NaN.  Returns ``(angles, errors, acc)`` on the device: ``[F, 7]`` of ``out_dtype`` (default: the rows'; None unless
+    ``per_frame``; errors None without truth) in ``ANGLE_NAMES``' order, radians, and float64 ``[R, 71]`` raw accumulators
+    (``summarise_angles``, ``merge_angles``); all with a leading ``C`` for ``[C, F, w]`` rows.  The same inputs give the same bits.  The
+    call does not wait for the device."""
+    m = _min_swing(min_swing)
+    w = _rows_width(layout, kind)
+    rd, rs, ss, n = _sets_view(rows, w, "rows")
+    if rs > 2 ** 31 - 1:
+        raise UserWarning(f"rows: a row stride of {rs} elements does not fit the entry's int32 (copy the view)")
+    out_dtype = rd.dtype if out_dtype is None else out_dtype
+    if out_dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+    F, dev, sets = int(rd.shape[-2]), rd.device, 1 if n is None else n
+    st = _recording_starts(starts)
+    R = int(st.shape[0])
+    td, ts, off = None, 0, None
+    if truth is not None:
+        td, ts = _rows_view(truth, _rows_width(layout, truth_kind), "truth")
+        if td.shape[0] != F or td.device != dev or ts > 2 ** 31 - 1:
+            raise UserWarning(f"truth: {F} rows on {dev} with a stride that fits int32, got {tuple(td.shape)} on {td.device}")
+        off = _sweep((0, 0), R, rec_lags)[2]
+    elif rec_lags is not None:
+        raise UserWarning("rec_lags pair rows with truth: give truth with them")
+    body = _body_rows(bodies, R, "joint_angles bodies") if kind == "targets" or (td is not None and truth_kind == "targets") else None
+    ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())                       # noqa: E731
+    with torch.cuda.device(dev):
+        angles = torch.empty((sets, F, ANGLE_WIDTH), dtype=out_dtype, device=dev) if per_frame else None
+        errors = torch.empty((sets, F, ANGLE_WIDTH), dtype=out_dtype, device=dev) if per_frame and td is not None else None
+        acc = torch.empty((sets, max(R, 1), ANGLE_ACC_WIDTH), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_joint_angles(int(layout), ptr(rd), ROWS_KINDS[kind], rs, _f64(rd.dtype), sets, ss,
+                                               ptr(td), ROWS_KINDS[truth_kind] if td is not None else 0, ts,
+                                               _f64(td.dtype) if td is not None else _hip.F64,
+                                               C.c_void_p(off.ctypes.data) if off is not None else None, F, C.c_void_p(st.ctypes.data), R, int(skip),
+                                               C.c_void_p(body.ctypes.data) if body is not None else None,
+                                               int(body.shape[0]) if body is not None else 0, m, ptr(angles), ptr(errors), _f64(out_dtype),
+                                               ptr(acc), stream), "ape_joint_angles")
+    if n is None:
+        return (None if angles is None else angles[0]), (None if errors is None else errors[0]), acc[0]
+    return angles, errors, acc
+
+
+def _angles_host(acc, ndims=(2,)) -> np.ndarray:
+    a = acc.detach().cpu().numpy() if isinstance(acc, torch.Tensor) else np.asarray(acc)
+    a = np.asarray(a, dtype=np.float64)
+    if a.ndim not in ndims or a.shape[-1] != ANGLE_ACC_WIDTH:
+        raise UserWarning(f"expected angle accumulators [..., R, {ANGLE_ACC_WIDTH}] of {' or '.join(str(n) for n in ndims)} dimensions, "
+                          f"got {tuple(a.shape)}")
+    return a
+
+
+def summarise_angles(acc) -> list:
+    """``acc [R, 71]`` (of several sets: one set's slice ``acc[c]``) -> per recording a dict: ``frames`` of the support and, under
+    ``"rad"`` and ``"deg"``, per name of ``ANGLE_NAMES`` a dict with ``mean``, ``std``, ``min``, ``max`` and ``rom`` (range of motion,
+    max - min) of the angle and ``bias`` (mean signed error), ``mae``, ``rmse`` and ``worst`` (largest magnitude) of its error against
+    truth, NaN where nothing was counted; ``count`` and ``error_count`` are the frames behind them.  The mean and the standard deviation
+    of a periodic angle are those of its values in ``(-pi, pi]``, not circular statistics."""
+    res = []
+    nan = float("nan")
+    with np.errstate(all="ignore"):
+        for row in _angles_host(acc):
+            d = {"frames": int(row[70]), "rad": {}, "deg": {}}
+            for k, name in enumerate(ANGLE_NAMES):
+                s1, s2, lo, hi, n = row[5 * k:5 * k + 5]
+                e1, ea, e2, ew, m = row[35 + 5 * k:40 + 5 * k]
+                mean = s1 / n if n else nan
+                v = {"count": int(n), "mean": mean, "std": float(np.sqrt(max(s2 / n - mean * mean, 0.0))) if n else nan,
+                     "min": lo if n else nan, "max": hi if n else nan, "rom": hi - lo if n else nan,
+                     "error_count": int(m), "bias": e1 / m if m else nan, "mae": ea / m if m else nan,
+                     "rmse": float(np.sqrt(e2 / m)) if m else nan, "worst": ew if m else nan}
+                d["rad"][name] = {key: (val if key.endswith("count") else float(val)) for key, val in v.items()}
+                d["deg"][name] = {key: (val if key.endswith("count") else float(np.degrees(val))) for key, val in v.items()}
+            res.append(d)
+    return res
+
+
+def merge_angles(acc_a, acc_b) -> np.ndarray:
+    """the accumulators ``[R, 71]`` (or ``[C, R, 71]``) of two pieces of the same recordings as one: sums, counts and frames added, the
+    smaller of the minima, the larger of the maxima and of the largest error magnitudes.  An angle needs no frames below it, so chained
+    pieces merge to the whole recording's counts."""
+    a, b = _angles_host(acc_a, (2, 3)), _angles_host(acc_b, (2, 3))
+    if a.shape != b.shape:
+        raise UserWarning(f"merge_angles: {tuple(a.shape)} and {tuple(b.shape)} accumulators")
+    out = a + b
+    lo, hi = list(_ANGLE_MIN_COLS), list(_ANGLE_MAX_COLS)
+    out[..., lo] = np.minimum(a[..., lo], b[..., lo])
+    out[..., hi] = np.maximum(a[..., hi], b[..., hi])
+    return out
+
+
+def angle_edges(bins: int = 72) -> np.ndarray:
+    """float64 ``[14, bins + 1]`` linear edges for ``hist_rows`` over ``[angles | errors]`` (the two ``[F, 7]`` outputs of
+    ``joint_angles`` side by side): ``[0, pi]`` for elbow flexion and shoulder elevation, ``[-pi, pi]`` for the other angles and for the
+    seven errors.  With the default 72 bins an edge lies every 2.5 and every 5 degrees: ``fraction_within`` at the edges ``e[k, 35]`` and
+    ``e[k, 37]`` of an error column (-5 and +5 degrees; thresholds must be edges bit for bit) gives the shares whose difference is the
+    share of frames within 5 degrees."""
+    bins = int(bins)
+    if not 1 <= bins <= HIST_MAX_BINS:
+        raise UserWarning(f"angle_edges: between 1 and {HIST_MAX_BINS} bins, got {bins}")
+    half, full = np.linspace(0.0, np.pi, bins + 1), np.linspace(-np.pi, np.pi, bins + 1)
+    rows = [full if ANGLE_PERIODIC[k] else half for k in range(ANGLE_WIDTH)] + [full] * ANGLE_WIDTH
+    return np.ascontiguousarray(np.stack(rows))

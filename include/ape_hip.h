@@ -1234,6 +1234,66 @@ int ape_score_hist(const void* values_dev, int32_t values_dtype, int32_t width,
                    const double* edges_host /* f64 [width, n_bins + 1] */, int32_t n_bins,
                    int64_t* hist_dev /* [n_sets, R, n_groups, width, n_bins + 3] */, void* stream);
 
+/* ---- joint angles of every frame, and their errors against truth (additive in ABI 7) -------------------------------------
+ * replaces: nothing; the reference has no counterpart.  ape_score_rows speaks in metres and whole-rotation angles; ape_joint_angles states
+ * a pose as the angles its users ask in: elbow flexion, forearm twist, shoulder elevation and its plane, humeral twist, hips yaw.
+ *   Sets, recordings, rows.  As ape_motion_sums: set c is the F rows c * set_stride elements after rows_dev, rows_stride apart, of
+ *           rows_dtype; rows_kind APE_ROWS_MSG / APE_ROWS_EST / APE_ROWS_TARGETS (the last converted with bodies_host f64 [n_bodies, 9],
+ *           n_bodies 1 or R, as ape_score_rows converts truth).  Only the quaternions q_l, q_u, q_h are used: of a message columns [7:11],
+ *           [14:18], [21:25], of an est row [9:13], [13:17], [17:21] (without hips [6:10], [10:14]); no other column of such a row is
+ *           read.  APE_LAYOUT_ORI_CAL_LARM_UARM has no hips: q_h is the identity.  Every quaternion is normalised before use:
+ *           n = sqrt(w*w + x*x + y*y + z*z), each component / n.  A row states no pose, and all its seven values are NaN, where one of the
+ *           twelve components is not finite (a target row: one of its targets or of the pose they convert to) or one of the three norms is
+ *           not finite or not > 0.
+ *   Conventions.  A bone's long axis is its local -x (larm_vec and uarm_vec are (-L, 0, 0)); the world is X right, Y up, Z forward.  With
+ *           (x) the product of fk_device.h:  e = conj(q_u) (x) q_l, the forearm in the upper arm's frame;  s = conj(q_h) (x) q_u, the upper
+ *           arm in the thorax frame.  All arithmetic is float64 with separate roundings, sums left to right, in the order written here
+ *           (score.py: joint_angles_numpy repeats it operation for operation).
+ *   Swing and twist of r = (w, x, y, z), all four negated first where w < 0.0:  rho = sqrt(w*w + x*x),  n = sqrt(y*y + z*z),
+ *           swing = 2 atan2(n, rho) in [0, pi],  twist = 2 atan2(x, w) in [-pi, pi],  azimuth = atan2(y*x + z*w, y*w - z*x): the direction of
+ *           the swing axis in the parent's y-z plane, r = swing (x) twist.
+ *   Upper-arm direction in the thorax frame, from s = (w, x, y, z) as the product gave it:  dx = -((w*w + x*x) - (y*y + z*z)),
+ *           dy = -(2 (x*y + w*z)),  dz = -(2 (x*z - w*y)),  h = sqrt(dx*dx + dz*dz).
+ *   Per frame, APE_ANGLE_WIDTH values in radians:
+ *             [0] elbow flexion = swing of e; 0 is a straight arm; the angle between the two bone axes         [0, pi]
+ *             [1] hinge azimuth = azimuth of e                                                                  periodic
+ *             [2] forearm twist = twist of e                                                                    periodic
+ *             [3] shoulder elevation = atan2(h, -dy); 0 is hanging down                                         [0, pi]
+ *             [4] plane of elevation = atan2(dz, -dx); 0 is out to the left, +pi/2 forward                      periodic
+ *             [5] humeral twist = twist of s                                                                    periodic
+ *             [6] hips yaw = 2 atan2(y_h, w_h), q_h negated first where w_h < 0.0; exactly 0 without hips       periodic
+ *   Conditioning.  sh = sin(min_swing / 2), sf = sin(min_swing), computed on the host.  [1] is NaN iff n(e) < sh; [2] iff rho(e) < sh; [5]
+ *           iff rho(s) < sh; [4] iff h < sf; every other value of a row that states a pose is stated.  min_swing = 0 states everything
+ *           (atan2(0, 0) = 0).
+ *   Errors, with truth_dev only: F truth rows of truth_kind (any of the three, whatever rows_kind is), truth_stride apart, of truth_dtype,
+ *           shared by all sets; rec_lag_host i32 [R] (NULL: zeros).  Frame f of recording r is paired with truth row f - l_r, which must lie
+ *           in [s_r, e_r), else its seven errors are NaN.  err_k = a_k(row) - a_k(truth); for the periodic columns it is folded once (> pi:
+ *           less 2 pi; <= -pi: plus 2 pi); NaN where either side is NaN.
+ *   angles_dev, errors_dev [n_sets, F, APE_ANGLE_WIDTH] of out_dtype (APE_F32: the float64 value rounded once), or NULL.
+ *   acc_dev f64 [n_sets, R, APE_ANGLE_ACC_WIDTH] or NULL, over the support f - s_r >= skip:  [5k .. 5k+4] the sum, the sum of squares, the
+ *           minimum, the maximum and the count of the finite values of angle k (none: +inf and -inf);  [35+5k .. 35+5k+4] the sum of the
+ *           finite errors of angle k, the sum of their magnitudes, the sum of their squares, the largest magnitude and their count (all
+ *           zeros without truth);  [70] the frames of the support, max(0, e_r - s_r - skip).  Counts are exact.  No floating-point atomics;
+ *           the order of summation is fixed by F and the starts, so the same inputs give the same bits, and each set's record has the bits
+ *           of a call on that set alone.  Raw accumulators: pieces of a recording merge on the host (score.py: merge_angles).
+ * A frame of a live bank is the same call: [S, 25] messages, R = 1, no accumulators.  Needs no model handle, runs on the current HIP device
+ * and does not wait; the host arrays have been consumed when it returns; staging slots as ape_score_rows keeps them (this file's own).  At
+ * most three launches (the truth's angles once for all sets, the frames, the accumulators); no workgroup waits for another.  Refused with
+ * APE_ERR_INVALID_ARG on the host, before anything is written: NULL rows_dev / seg_starts_host; all three outputs NULL; errors_dev without
+ * truth_dev; F < 1, R < 1, bad starts, skip < 0; an unknown kind, dtype or layout, APE_LAYOUT_NONE; rows_stride or truth_stride below the
+ * row width; n_sets outside 1 .. 64; n_sets > 1 with set_stride < F * rows_stride; APE_ROWS_TARGETS on either side with NULL bodies_host or
+ * n_bodies not 1 or R; min_swing not in [0, pi / 2); an output equal to an input or to another output; a capturing stream. */
+#define APE_ANGLE_WIDTH      7
+#define APE_ANGLE_ACC_WIDTH  71
+int ape_joint_angles(int32_t layout, const void* rows_dev, int32_t rows_kind, int32_t rows_stride, int32_t rows_dtype,
+                     int32_t n_sets, int64_t set_stride,
+                     const void* truth_dev /* or NULL */, int32_t truth_kind, int32_t truth_stride, int32_t truth_dtype,
+                     const int32_t* rec_lag_host /* [R] or NULL */,
+                     int32_t F, const int32_t* seg_starts_host, int32_t R, int32_t skip,
+                     const double* bodies_host, int32_t n_bodies, double min_swing,
+                     void* angles_dev /* [n_sets, F, 7] or NULL */, void* errors_dev /* [n_sets, F, 7] or NULL */, int32_t out_dtype,
+                     double* acc_dev /* f64 [n_sets, R, 71] or NULL */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
