@@ -1,5 +1,5 @@
 // Device helpers of the scoring kernels (score.hip, frame_fit.hip, body_fit.hip, resample.hip, post_sweep.hip, motion.hip), each
-// stated once: row staging, the recording of a frame, one truth row -> pose, the rotation a quaternion stands for, the ordered column
+// stated once: row staging, the recording of a frame, the slot of a value over edges, one truth row -> pose, the rotation a quaternion stands for, the ordered column
 // sums of a wave's terms and the ordered sum of a recording's partial records.
 // float64 with separate roundings for a * b + c, like the numpy statements (score.py): the including file turns contraction off BEFORE
 // it includes this header (there is no pragma here: a file that forgot would contract these statements, not half of them).
@@ -40,6 +40,17 @@ __device__ __forceinline__ int find_rec(const int* starts, int R, long long f) {
         if ((long long)starts[mid] <= f) lo = mid; else hi = mid - 1;
     }
     return lo;
+}
+
+// the slot of v over the edges e[0 .. B] (LDS), as include/ape_hip.h states it for ape_score_hist: comparisons only
+__device__ __forceinline__ int find_slot(const double* e, int B, double v) {
+    if (v != v) return B + 2;
+    int lo = 0, n = B + 1;                              // the edges below v are e[0 .. lo) once n == 0
+    while (n > 0) {                                     // (at most 9 rounds for 257 edges)
+        const int half = n >> 1;
+        if (e[lo + half] < v) { lo += half + 1; n -= half + 1; } else n = half;
+    }
+    return lo == 0 ? B : (lo > B ? B + 1 : lo - 1);
 }
 
 // The truth's 6D rotation -> unit quaternion, in the reference's sense.  rot_mat_to_quat (transformations.py:521-545) takes the dominant

@@ -54,17 +54,6 @@ __host__ __device__ constexpr int sh_hist_at(int cw, int B) { return sh_stage_at
 __host__ __device__ constexpr size_t sh_lds_bytes(int cw, int B) { return (size_t)sh_hist_at(cw, B) * sizeof(double) + (size_t)cw * (B + 3) * sizeof(unsigned); }
 static_assert(sh_lds_bytes(SH_CW, APE_HIST_MAX_BINS) <= 64 * 1024, "the largest workgroup's LDS");
 
-// the slot of v over the edges e[0 .. B] (LDS): comparisons only
-__device__ __forceinline__ int find_slot(const double* e, int B, double v) {
-    if (v != v) return B + 2;
-    int lo = 0, n = B + 1;                              // the edges below v are e[0 .. lo) once n == 0
-    while (n > 0) {                                     // (at most 9 rounds for 257 edges)
-        const int half = n >> 1;
-        if (e[lo + half] < v) { lo += half + 1; n -= half + 1; } else n = half;
-    }
-    return lo == 0 ? B : (lo > B ? B + 1 : lo - 1);
-}
-
 template <typename T>
 __global__ __launch_bounds__(SH_BLOCK) void ape_score_hist_kernel(const HistParams p) {
     extern __shared__ double sh_mem[];                  // edges [ncols][B + 1] | staging [4][64][lstride] | counts u32 [ncols][B + 3]

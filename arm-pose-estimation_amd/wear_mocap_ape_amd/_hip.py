@@ -37,6 +37,7 @@ MOTION_WIDTH, MOTION_ACC_WIDTH = 12, 38     # APE_MOTION_WIDTH, APE_MOTION_ACC_W
 ROWS_MSG, ROWS_EST, ROWS_TARGETS = 0, 1, 2  # APE_ROWS_*
 HIST_MAX_BINS, HIST_MAX_WIDTH = 256, 16     # APE_HIST_MAX_BINS, APE_HIST_MAX_WIDTH (ape_score_hist)
 ANGLE_WIDTH, ANGLE_ACC_WIDTH = 7, 71        # APE_ANGLE_WIDTH, APE_ANGLE_ACC_WIDTH (ape_joint_angles)
+BY_MAX_KEYS, BY_MAX_VALUES, BY_MAX_BINS, BY_PIECE = 8, 16, 125, 1024    # APE_BY_* (ape_score_by)
 FLAG_ANY_PLACEMENT, FLAG_NO_XCD_CLASSES, FLAG_ALT_FORM = 0x08000000, 0x02000000, 0x01000000    # exchange-form selectors (A/B runs, tests)
 FLAG_IN_XCD_PLAIN = 0x00400000      # opt-in: plain hand-over stores inside an XCD-pure cluster (the default is write-through)
 KERNEL_AUTO, KERNEL_TILE16, KERNEL_CLUSTER, KERNEL_CLUSTER_GEN1, KERNEL_AUTO_GEN1 = 0, 1, 2, 3, 4
@@ -249,6 +250,11 @@ SIGNATURES["ape_score_hist"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_
 SIGNATURES["ape_joint_angles"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_void_p, C.c_int32,
                                             C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32,
                                             C.c_double, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
+# per-slot sums of value columns keyed by other columns: keys + dtype, n_keys, set and frame stride (int64), values + dtype,
+# n_values, set and frame stride (int64), n_sets, F, starts_host, R, trim_host, edges_host, n_bins, by, HIP stream
+SIGNATURES["ape_score_by"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
+                                        C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
+                                        C.c_void_p])
 
 _lib = None
 

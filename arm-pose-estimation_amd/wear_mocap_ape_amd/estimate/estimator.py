@@ -744,6 +744,56 @@ class Estimator:
         bodies = self._body_measurements if bonemaps is None else bonemaps
         return score.joint_angles(self._layout, truth, truth_kind, None, "est", starts, skip, None, bodies, min_swing, per_frame)
 
+    # ---- errors by condition (the reference has no counterpart) ----
+    def errors_by(self, out, truth, by, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
+                  edges=None, bins=36, times=None):
+        """Where a replay is wrong: ``score_recording``'s per-frame ``[F, 7]`` rows (with ``rec_lags`` at each recording's own lag, as in
+        ``error_distribution``) as the values of ``score.stats_by``, keyed per frame by ``by``:
+        ``"angles"``: ``angles_recording(per_frame=True)`` of ``out``, the seven joint angles, over ``score.angle_edges(bins)``;
+        ``"truth_angles"``: ``truth_angles(per_frame=True)``, the truth's own angles (refused with ``rec_lags``: the truth frame of a pair
+        is then another frame than the keyed one);
+        ``"motion"``: ``motion_recording(per_frame=True)`` on the clock ``times``, twelve columns over
+        ``score.default_edges("motion", bins)``;
+        ``"spread"``: ``score.spread_sigma(spread)`` over the position and angle columns of ``score.default_edges("score", bins)`` -- the
+        reliability curve of the spread record;
+        a device tensor ``[F, K]``: any keys, with ``edges`` (``[B + 1]`` or ``[K, B + 1]``) required.
+        The window is ``score.lag_trim``'s, the frames the accumulators cover.  Returns ``(by, edges, key_names)``: float64
+        ``[R, K, B + 3, 7, 4]`` on the device, the edges float64 ``[K, B + 1]`` on the host, the key columns' names
+        (``score.summarise_by``, ``pool_by``, ``merge_by``; the value columns are ``score.SCORE_HIST_NAMES``)."""
+        from wear_mocap_ape_amd import score
+        skip = self._sequence_len - 1 if skip is None else skip
+        if rec_lags is None:
+            rows, _ = self.score_recording(out, truth, spread, starts, skip, bonemaps, truth_kind)
+        else:
+            rows, _ = self.score_recording(out, truth, spread, starts, skip, bonemaps, truth_kind, (0, 0), rec_lags)
+            rows = rows[:, 0]
+        default = None
+        if isinstance(by, torch.Tensor):
+            if edges is None:
+                raise UserWarning("errors_by: keys given as a tensor need edges")
+            keys, names = by, tuple(f"key{k}" for k in range(int(by.shape[-1])))
+        elif by == "angles":
+            keys, names = self.angles_recording(out, None, starts, skip, bonemaps, truth_kind, None, True)[0], score.ANGLE_NAMES
+            default = lambda: score.angle_edges(bins)[:score.ANGLE_WIDTH]      # noqa: E731
+        elif by == "truth_angles":
+            if rec_lags is not None:
+                raise UserWarning("errors_by: by='truth_angles' with rec_lags: the truth frame of a pair is another frame than the keyed one")
+            keys, names = self.truth_angles(truth, truth_kind, starts, skip, bonemaps, True)[0], score.ANGLE_NAMES
+            default = lambda: score.angle_edges(bins)[:score.ANGLE_WIDTH]      # noqa: E731
+        elif by == "motion":
+            keys, names = self.motion_recording(out, starts, skip, times, True)[0], score.MOTION_NAMES
+            default = lambda: score.default_edges("motion", bins)              # noqa: E731
+        elif by == "spread":
+            if spread is None:
+                raise UserWarning("errors_by: by='spread' needs the spread records")
+            keys, names = score.spread_sigma(spread), score.SIGMA_NAMES
+            default = lambda: score.default_edges("score", bins)[:5]           # noqa: E731
+        else:
+            raise UserWarning(f"errors_by: by must be 'angles', 'truth_angles', 'motion', 'spread' or a device tensor, got {by!r}")
+        edges = default() if edges is None else score._edges(edges, int(keys.shape[-1]))
+        trim = score.lag_trim(starts, int(rows.shape[0]), (0, 0), skip, rec_lags)
+        return score.stats_by(keys, rows, edges, starts, 0, trim), edges, names
+
     # ---- post-filter sweep (DESIGN.md 4.33; the reference has no counterpart) ----
     def repost(self, y, configs, starts=None, bonemaps=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
         """``score.post_sweep`` with this estimator's model and body: ``y`` device float32 ``[F, M, O]`` as

@@ -163,6 +163,11 @@ class WatchPhoneUarm(Estimator):
         """``Estimator.truth_angles`` for FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
         return super().truth_angles(truth, truth_kind, starts, 0 if skip is None else skip, bonemaps, per_frame, min_swing)
 
+    def errors_by(self, out, truth, by, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
+                  edges=None, bins=36, times=None):
+        """``Estimator.errors_by`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
+        return super().errors_by(out, truth, by, spread, starts, 0 if skip is None else skip, bonemaps, truth_kind, rec_lags, edges, bins, times)
+
     def align_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=(0, 0), mode="yaw",
                         weights=(1, 1, 1, 0, 0)):
         """``Estimator.align_recording`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""

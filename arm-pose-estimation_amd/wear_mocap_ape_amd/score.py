@@ -44,7 +44,12 @@ statement.
 
 ``joint_angles`` states every frame as the angles its users ask in (elbow flexion, forearm twist, shoulder elevation and its plane,
 humeral twist, hips yaw) with their errors against truth and their sums per recording; ``summarise_angles``,
-``merge_angles`` and ``angle_edges`` go with it, ``joint_angles_numpy`` is the host statement."""
+``merge_angles`` and ``angle_edges`` go with it, ``joint_angles_numpy`` is the host statement.
+
+All of these state their numbers per recording.  ``stats_by`` states one per-frame column as a function of another: the count, sum, sum
+of squares and maximum of any value columns over the bins of any key columns -- the hand error over the elbow flexion, over the hand
+speed, over the predicted sigma (``spread_sigma``; ``ape_score_by``) -- in a stated order of summation, so the same
+inputs give the same bits; ``merge_by``, ``pool_by`` and ``summarise_by`` work on the records, ``stats_by_numpy`` is the host statement."""
 import ctypes as C
 import math
 
@@ -2171,3 +2176,197 @@ def angle_edges(bins: int = 72) -> np.ndarray:
     half, full = np.linspace(0.0, np.pi, bins + 1), np.linspace(-np.pi, np.pi, bins + 1)
     rows = [full if ANGLE_PERIODIC[k] else half for k in range(ANGLE_WIDTH)] + [full] * ANGLE_WIDTH
     return np.ascontiguousarray(np.stack(rows))
+
+
+# ---- errors by condition: per-slot sums of any per-frame column keyed by any other (ape_score_by) ---------------------------
+# A record [..., K, B + 3, V, 4] holds, per key column, slot of its edges (``hist_rows``' slots) and value column: n, the sum, the sum of
+# squares and the maximum of the values of the window's frames whose key lies in the slot (NaN values left out of their own cell).
+BY_MAX_KEYS, BY_MAX_VALUES, BY_MAX_BINS, BY_PIECE = _hip.BY_MAX_KEYS, _hip.BY_MAX_VALUES, _hip.BY_MAX_BINS, _hip.BY_PIECE
+SIGMA_NAMES = ("hand_sigma", "elbow_sigma", "larm_spread", "uarm_spread", "hips_spread")
+
+
+def _by_sides(keys, values):
+    """(keys [Ck, F, K], values [Cv, F, V] float64, C, whether the result has a set dimension) of host arrays [F, .] or [C, F, .]"""
+    k, v = np.asarray(keys), np.asarray(values)
+    if k.ndim not in (2, 3) or v.ndim not in (2, 3) or min(k.shape) < 1 or min(v.shape) < 1:
+        raise UserWarning(f"keys and values: expected [F, K] or [C, F, K] and [F, V] or [C, F, V], got {tuple(k.shape)} and {tuple(v.shape)}")
+    sets = k.ndim == 3 or v.ndim == 3
+    k3, v3 = (k if k.ndim == 3 else k[None]).astype(np.float64), (v if v.ndim == 3 else v[None]).astype(np.float64)
+    if k3.shape[1] != v3.shape[1] or (k.ndim == 3 and v.ndim == 3 and k3.shape[0] != v3.shape[0]):
+        raise UserWarning(f"keys {tuple(k.shape)} and values {tuple(v.shape)}: the same frames, and the same sets where both have sets")
+    return k3, v3, max(k3.shape[0], v3.shape[0]), sets
+
+
+def stats_by_numpy(keys, values, edges, starts=None, skip: int = 0, trim=None) -> np.ndarray:
+    """The host statement of ``stats_by``, order included: ``_slots`` per key column; the window cut into pieces of ``BY_PIECE`` frames
+    from its first frame; per piece and cell ``np.cumsum`` (which adds one by one in frame order; ``np.sum`` adds pairwise) over ``+0.0``
+    and then the cell's terms; the piece sums added in a loop from ``+0.0``.  A NaN value is a term of ``+0.0``, which a sum that started
+    at ``+0.0`` cannot see.  ``keys``: ``[F, K]`` or ``[C, F, K]``, ``values``: ``[F, V]`` or ``[C, F, V]`` (float32 is widened; a side
+    without sets is shared); returns float64 ``[(C,) R, K, B + 3, V, 4]``."""
+    k3, v3, Cn, sets = _by_sides(keys, values)
+    F, K, V = k3.shape[1], k3.shape[2], v3.shape[2]
+    e = _edges(edges, K)
+    B = e.shape[1] - 1
+    st = _recording_starts(starts).astype(np.int64)
+    R = st.shape[0]
+    tr = _trims(R, skip, trim).astype(np.int64)
+    ends = np.r_[st[1:], F]
+    out = np.zeros((Cn, R, K, B + 3, V, 4))
+    out[..., 3] = -np.inf
+    zero = np.zeros((1, V))
+    with np.errstate(all="ignore"):
+        for r in range(R):
+            a, b = int(st[r] + tr[r, 0]), int(ends[r] - tr[r, 1])
+            for c in range(Cn if a < b else 0):
+                kc, vc = k3[c if k3.shape[0] > 1 else 0], v3[c if v3.shape[0] > 1 else 0]
+                for kk in range(K):
+                    slots = _slots(kc[a:b, kk], e[kk])
+                    for p0 in range(a, b, BY_PIECE):
+                        p1 = min(b, p0 + BY_PIECE)
+                        sl, x = slots[p0 - a:p1 - a], vc[p0:p1]
+                        for s in np.unique(sl):
+                            rows = x[sl == s]                       # the cell's frames of the piece, in frame order
+                            ok = ~np.isnan(rows)
+                            t = np.where(ok, rows, 0.0)
+                            cell = out[c, r, kk, s]
+                            cell[:, 0] = cell[:, 0] + ok.sum(axis=0)
+                            cell[:, 1] = cell[:, 1] + np.cumsum(np.concatenate([zero, t]), axis=0)[-1]
+                            cell[:, 2] = cell[:, 2] + np.cumsum(np.concatenate([zero, t * t]), axis=0)[-1]
+                            cell[:, 3] = np.maximum(cell[:, 3], np.where(ok, rows, -np.inf).max(axis=0))
+    return out if sets else out[0]
+
+
+def _by_view(t, what: str):
+    """(tensor [C, F, W], C, F, W, set / frame stride in elements, whether it has sets) of a device view ``[F, W]`` or ``[C, F, W]`` under
+    ``_hist_view``'s rules: the last dimension contiguous, frames and sets apart; anything else is copied"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() not in (2, 3) or min(t.shape) < 1:
+        raise UserWarning(f"{what}: expected a device tensor [F, W] or [C, F, W]")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"{what}: float32 or float64, got {t.dtype}")
+    v = t[None] if t.dim() == 2 else t
+    Cn, F, W = (int(n) for n in v.shape)
+    ss, fs, ws = (int(s) for s in v.stride())
+    fs = fs if F > 1 else max(fs, W)
+    if (W > 1 and ws != 1) or fs < W or (Cn > 1 and ss < F * fs):
+        v = v.contiguous()
+        ss, fs, ws = (int(s) for s in v.stride())
+        fs = max(fs, W)
+    return v, Cn, F, W, (ss if Cn > 1 else 0), fs, t.dim() == 3
+
+
+def stats_by(keys, values, edges, starts=None, skip: int = 0, trim=None):
+    """Per-slot count, sum, sum of squares and maximum of value columns keyed by other columns, per recording, on the device
+    (``ape_score_by``).  ``keys``: a device ``[F, K]`` or ``[C, F, K]`` view, ``values``: ``[F, V]`` or ``[C, F, V]``, ``V <= 16``,
+    ``C <= 64``, float32 or float64 per side; a side without sets is shared by all sets of the other.  ``joint_angles``' ``[C, F, 7]``,
+    ``score_rows``' ``[F, 7]``, ``motion_sums``' ``[C, F, 12]``, ``spread_sigma``'s ``[F, 5]``, column slices and strided views go in
+    without a copy (``_hist_view``'s rules).  ``edges``: float64 ``[B + 1]`` for all key columns or ``[K, B + 1]``, ``B <= 125``;
+    ``starts``, ``skip``, ``trim``: the windows, as in ``hist_rows``.  More than 8 key columns are taken 8 to a call (a key column's
+    record does not depend on the others).  Returns float64 ``[(C,) R, K, B + 3, V, 4]`` on the device: ``n``, the sum, the sum of
+    squares, the maximum (``-inf`` for an empty cell).  The order of every sum is stated (``stats_by_numpy``): the same inputs give the
+    same bits, a recording's record does not depend on the batch around it.  The call does not wait for the device."""
+    kv, Ck, F, K, kss, kfs, ksets = _by_view(keys, "keys")
+    vv, Cv, Fv, V, vss, vfs, vsets = _by_view(values, "values")
+    if F != Fv or (ksets and vsets and Ck != Cv) or kv.device != vv.device:
+        raise UserWarning(f"keys {tuple(keys.shape)} and values {tuple(values.shape)}: the same frames on one device, and the same sets "
+                          "where both have sets")
+    Cn = max(Ck, Cv)
+    if not 1 <= V <= BY_MAX_VALUES or not 1 <= Cn <= _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"values: between 1 and {BY_MAX_VALUES} columns and at most {_hip.POST_MAX_CONFIGS} sets, got {V} and {Cn}")
+    e = _edges(edges, K)
+    B = int(e.shape[1]) - 1
+    if B > BY_MAX_BINS:
+        raise UserWarning(f"edges: at most {BY_MAX_BINS} bins, got {B}")
+    st = _recording_starts(starts)
+    R = int(st.shape[0])
+    tr = _trims(R, skip, trim)
+    dev = kv.device
+    outs = []
+    with torch.cuda.device(dev):
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        for k0 in range(0, K, BY_MAX_KEYS):
+            nk = min(BY_MAX_KEYS, K - k0)
+            by = torch.empty((Cn, max(R, 1), nk, B + 3, V, 4), dtype=torch.float64, device=dev)
+            ek = np.ascontiguousarray(e[k0:k0 + nk])
+            _hip.check(_hip.lib().ape_score_by(C.c_void_p(kv.data_ptr() + k0 * kv.element_size()), _f64(kv.dtype), nk, kss, kfs,
+                                               C.c_void_p(vv.data_ptr()), _f64(vv.dtype), V, vss, vfs, Cn, F, C.c_void_p(st.ctypes.data), R,
+                                               C.c_void_p(tr.ctypes.data), C.c_void_p(ek.ctypes.data), B, C.c_void_p(by.data_ptr()), stream),
+                       "ape_score_by")
+            outs.append(by)
+    by = outs[0] if len(outs) == 1 else torch.cat(outs, dim=2)
+    return by if (ksets or vsets) else by[0]
+
+
+def _by_host(by) -> np.ndarray:
+    b = by.detach().cpu().numpy() if isinstance(by, torch.Tensor) else np.asarray(by)
+    if b.ndim < 4 or b.shape[-1] != 4 or b.shape[-3] < 4:
+        raise UserWarning(f"expected a record [..., K, B + 3, V, 4], got {tuple(b.shape)}")
+    return b.astype(np.float64)
+
+
+def merge_by(by_a, by_b) -> np.ndarray:
+    """the records of two pieces of the same recordings over the same edges as one (float64, on the host): ``n``, sums and sums of squares
+    added, the larger of the maxima.  For chained pieces: ``n`` and the maxima are the one call's exactly, a sum of ``n`` terms lies within
+    ``n 2^-53 sum|x|`` of it (another order of the same terms)."""
+    a, b = _by_host(by_a), _by_host(by_b)
+    if a.shape != b.shape:
+        raise UserWarning(f"merge_by: {tuple(a.shape)} and {tuple(b.shape)} records")
+    with np.errstate(all="ignore"):
+        out = a + b
+    out[..., 3] = np.maximum(a[..., 3], b[..., 3])
+    return out
+
+
+def pool_by(by) -> np.ndarray:
+    """``by [(C,) R, K, B + 3, V, 4]`` -> ``[(C,) K, B + 3, V, 4]``: the recordings folded in order, from ``+0.0`` (the maxima from
+    ``-inf``)"""
+    b = _by_host(by)
+    if b.ndim not in (5, 6):
+        raise UserWarning(f"pool_by: expected [(C,) R, K, B + 3, V, 4], got {tuple(b.shape)}")
+    out = np.zeros(b.shape[:-5] + b.shape[-4:])
+    out[..., 3] = -np.inf
+    with np.errstate(all="ignore"):
+        for r in range(b.shape[-5]):
+            piece = b[..., r, :, :, :, :]
+            top = np.maximum(out[..., 3], piece[..., 3])
+            out = out + piece
+            out[..., 3] = top
+    return out
+
+
+def summarise_by(by, edges, key_names=None, value_names=None) -> dict:
+    """A record ``[..., K, B + 3, V, 4]`` over ``edges`` -> a dict of float64 arrays ``[..., K, B + 3, V]``: ``n``, ``mean``, ``rms`` and
+    ``max`` per cell (``mean`` and ``rms`` NaN where ``n == 0``, ``max`` ``-inf`` there), with ``edges [K, B + 1]``, ``key_names`` and
+    ``value_names`` (default ``key0 ..`` / ``value0 ..``) and ``slots``, the names of the ``B + 3`` slots (``"(lo, hi]"`` per bin, then
+    ``"below"``, ``"above"``, ``"nan"``) per key column.  For a reliability curve: keys ``spread_sigma``, the same sigma among the
+    values; each bin's ``rms`` of an error beside its ``mean`` of the sigma."""
+    b = _by_host(by)
+    K, S, V = b.shape[-4], b.shape[-3], b.shape[-2]
+    e = _edges(edges, K)
+    if e.shape[1] + 2 != S:
+        raise UserWarning(f"a record of {S - 3} bins against {e.shape[1]} edges")
+    key_names = tuple(f"key{k}" for k in range(K)) if key_names is None else tuple(key_names)
+    value_names = tuple(f"value{v}" for v in range(V)) if value_names is None else tuple(value_names)
+    if len(key_names) != K or len(value_names) != V:
+        raise UserWarning(f"summarise_by: {len(key_names)} and {len(value_names)} names for {K} key and {V} value columns")
+    n = b[..., 0]
+    with np.errstate(all="ignore"):
+        some = n > 0
+        div = np.where(some, n, 1.0)
+        mean = np.where(some, b[..., 1] / div, np.nan)
+        rms = np.where(some, np.sqrt(b[..., 2] / div), np.nan)
+    slots = [[f"({e[k, i]:g}, {e[k, i + 1]:g}]" for i in range(S - 3)] + ["below", "above", "nan"] for k in range(K)]
+    return {"n": n, "mean": mean, "rms": rms, "max": b[..., 3].copy(), "edges": e, "key_names": key_names, "value_names": value_names,
+            "slots": slots}
+
+
+def spread_sigma(spread):
+    """``spread [..., >= 21]`` (the spread records of a replay in its first 21 columns, a device tensor) -> ``[..., 5]`` of the same dtype by torch operations on
+    the device: ``sqrt(xx + yy + zz)`` of the hand covariance (columns 3, 6, 8; added left to right), the same of the elbow covariance
+    (12, 15, 17), and the three angular spreads (18:21).  The keys of a reliability curve (``SIGMA_NAMES``); a covariance with a
+    negative or NaN trace gives NaN."""
+    if not isinstance(spread, torch.Tensor) or spread.dim() < 1 or spread.shape[-1] < _hip.SPREAD_WIDTH:
+        raise UserWarning(f"spread: expected a tensor [..., >= {_hip.SPREAD_WIDTH}]")
+    s = spread
+    hand = torch.sqrt((s[..., 3] + s[..., 6]) + s[..., 8])
+    elbow = torch.sqrt((s[..., 12] + s[..., 15]) + s[..., 17])
+    return torch.cat([hand[..., None], elbow[..., None], s[..., 18:21]], dim=-1)

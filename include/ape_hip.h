@@ -1294,6 +1294,52 @@ int ape_joint_angles(int32_t layout, const void* rows_dev, int32_t rows_kind, in
                      void* angles_dev /* [n_sets, F, 7] or NULL */, void* errors_dev /* [n_sets, F, 7] or NULL */, int32_t out_dtype,
                      double* acc_dev /* f64 [n_sets, R, 71] or NULL */, void* stream);
 
+/* ---- errors by condition: per-slot sums of any per-frame column keyed by any other (additive in ABI 7) --------------------
+ * replaces: nothing; the reference has no counterpart.  The scorers state their numbers per recording; ape_score_by states one per-frame
+ * column as a function of another: the hand error over the elbow flexion, the error over the hand speed, each sigma bin's RMS error (a
+ * reliability curve).  Keys are binned over fixed edges as ape_score_hist bins values; per slot, every value column gets a count, a sum, a
+ * sum of squares and a maximum.
+ *   Keys.   Key (c, f, k), c < n_sets, f < F, k < n_keys <= APE_BY_MAX_KEYS, is the element c * keys_set_stride + f * keys_frame_stride + k
+ *           of keys_dev, of keys_dtype (APE_F32 is widened exactly).  A set stride of 0 shares the one key set among all sets; it is not
+ *           read with n_sets == 1.
+ *   Values. Value (c, f, v), v < n_values <= APE_BY_MAX_VALUES, is the element c * values_set_stride + f * values_frame_stride + v of
+ *           values_dev, of values_dtype; its set stride may be 0 as well.
+ *   Window. Recordings, seg_starts_host, trim_host [R, 2] and empty or inverted windows exactly as ape_score_hist states them.
+ *   Slots.  Key column k has its own strictly increasing finite edges e[0 .. B] = edges_host[k][0 .. n_bins], B = n_bins <=
+ *           APE_BY_MAX_BINS.  A key falls into one of B + 3 slots by ape_score_hist's rule -- bins closed on the right, then below (B),
+ *           above (B + 1), NaN (B + 2) -- by comparisons only.  (125 bins: ape_score_hist's 72 angle bins fit, and B + 3 <= 128.)
+ *   Cell.   For every (set, recording, key column, slot, value column), four float64 accumulators over the frames f of the recording's
+ *           window whose key k lies in the slot and whose value x = value (c, f, v) is not NaN:
+ *             [0] n, the count of such frames          [1] the sum of x
+ *             [2] the sum of x * x, the product rounded to float64, then added (no fused multiply-add)
+ *             [3] the maximum of x; -inf for an empty cell
+ *           A NaN value is left out of its own cell only.  +-inf are counted and follow IEEE (a cell that holds both has a NaN sum).
+ *   Order.  This is part of the contract.  The window is cut into pieces of APE_BY_PIECE consecutive frames, counted from the window's
+ *           first frame (not from the batch's or the recording's).  Within a piece a cell's terms are added in frame order, starting from
+ *           +0.0; a cell's piece sums are added in piece order, starting from +0.0.  A recording's record therefore has the same bits
+ *           wherever it lies in the batch, whatever else is in the batch and whatever the grid is; a call with a trim has the bits of a
+ *           call on the sliced tensors; each set has the bits of a call on that set alone.  On the host: score.py, stats_by_numpy.
+ *   by_dev  f64 [n_sets, R, n_keys, n_bins + 3, n_values, 4], all of it written by the call (no zeroing needed).  No floating-point
+ *           atomics; no workgroup waits for another.
+ * Needs no model handle, runs on the current HIP device and does not wait; the host arrays have been consumed when it returns.  The piece
+ * records, n_sets * pieces * n_keys * (n_bins + 3) * n_values * 4 doubles, live in the staging slot's device block (slots as
+ * ape_score_rows keeps them, this file's own), as ape_motion_sums' partial records do.  Two launches.  Refused with APE_ERR_INVALID_ARG on
+ * the host, before anything is written: NULL keys_dev / values_dev / seg_starts_host / edges_host / by_dev; F < 1, R < 1, bad starts, a
+ * negative trim; n_sets outside 1 .. APE_POST_MAX_CONFIGS; n_bins outside 1 .. APE_BY_MAX_BINS; n_keys outside 1 .. APE_BY_MAX_KEYS;
+ * n_values outside 1 .. APE_BY_MAX_VALUES; an unknown dtype; a frame stride below its side's columns; n_sets > 1 with a set stride that is
+ * neither 0 nor at least F * frame_stride; an extent that does not fit 63 bits; a pointer not aligned to its element; edges that are not
+ * finite or not strictly increasing; more than 2^31 - 1 output elements; more than 1 GiB of piece records (the message states the size);
+ * by_dev overlapping keys_dev or values_dev; a capturing stream. */
+#define APE_BY_MAX_KEYS    8
+#define APE_BY_MAX_VALUES  16
+#define APE_BY_MAX_BINS    125
+#define APE_BY_PIECE       1024
+int ape_score_by(const void* keys_dev, int32_t keys_dtype, int32_t n_keys, int64_t keys_set_stride, int64_t keys_frame_stride,
+                 const void* values_dev, int32_t values_dtype, int32_t n_values, int64_t values_set_stride, int64_t values_frame_stride,
+                 int32_t n_sets, int32_t F, const int32_t* seg_starts_host, int32_t R, const int32_t* trim_host /* [R, 2] or NULL */,
+                 const double* edges_host /* f64 [n_keys, n_bins + 1] */, int32_t n_bins,
+                 double* by_dev /* f64 [n_sets, R, n_keys, n_bins + 3, n_values, 4] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
