@@ -4,7 +4,7 @@
 // per-frame arithmetic (estimator.py:108-118,122-137; compose_msg.py:13-108; transformations.py:32-51).
 //
 // ape_post_sweep_fk_kernel  the work the configurations share: sample rows k < Mx = max m_c of a chunk of frames -> est rows, once per
-//                           call.  ape_fk3_kernel's decomposition (fk.hip: a row's three chains side by side, 32 rows per workgroup of two
+//                           call (its body, post_fk_rows, is in post_common.h: post_window.hip runs it too).  ape_fk3_kernel's decomposition (fk.hip: a row's three chains side by side, 32 rows per workgroup of two
 //                           waves) and its statements, with the row index mapped: compact row r = frame r / Mx, sample r % Mx.
 // ape_post_sweep_kernel     all C reductions of a tile of frames.  A lane takes (frame, configuration) pairs, the configurations in the
 //                           order of falling stack height so that a wave's lanes run stacks of like length, frames fastest so that a
@@ -34,29 +34,17 @@
 
 #pragma clang fp contract(off)
 #include "score_device.h"
+#include "post_common.h"
 
 namespace {
 
 using namespace ape_postdev;
 using ape_scoredev::find_rec;
+using namespace ape_postcommon;
 
 constexpr int PS_BLOCK = 256;
-constexpr int PS_FK_ROWS = 32;                          // rows per workgroup of the conversion (FK3_ROWS of fk.hip)
 constexpr int PS_LDS_WORDS = APE_LDS_BYTES / 8;         // float64 words of a CU's LDS
 constexpr long long PS_DEFAULT_BYTES = 128ll << 20;
-
-struct PsFkParams {
-    const float* y;                                     // [F, M, O]
-    double* est;                                        // the chunk's first fresh row (behind the carried-over frames)
-    const double* yy_m;
-    const double* yy_s;
-    const int* starts;                                  // [R]
-    const double* bodies;                               // [R, 9] or nullptr: `body` for every row
-    double body[9];
-    int rows;                                           // frames of the chunk x Mx
-    int f_lo;                                           // the chunk's first frame
-    int R, M, Mx, O, W, layout;
-};
 
 struct PsParams {
     const double* est;                                  // the chunk buffer: frame f_lo - H at est[0], Mx rows of W per frame
@@ -72,82 +60,7 @@ struct PsParams {
     unsigned char idx[APE_POST_MAX_CONFIGS];                          // ... and their positions in the caller's list
 };
 
-__global__ __launch_bounds__(128) void ape_post_sweep_fk_kernel(const PsFkParams p) {
-    __shared__ double rot[PS_FK_ROWS][3][3];               // [row][lower arm, upper arm, shoulder origin][xyz]
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const bool hips = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
-    const bool full = p.layout != APE_LAYOUT_ORI_CAL_LARM_UARM_HIPS && hips;
-    const int c_l = full ? 3 : 0, c_u = full ? 12 : 6, c_h = full ? 18 : 12;
-    const int e_lq = hips ? 9 : 6, e_uq = hips ? 13 : 10, e_hq = 17;
-    auto load = [&](const float* src, int c) -> double {
-        double v = (double)src[c];
-        v = v * p.yy_s[c] + p.yy_m[c];                     // de-normalisation in f64: estimator.py:108-109
-        return v;
-    };
-    auto src_of = [&](int row, int* frame) -> const float* {
-        const int fc = row / p.Mx, k = row - fc * p.Mx;
-        *frame = p.f_lo + fc;
-        return p.y + ((size_t)(p.f_lo + fc) * p.M + k) * p.O;
-    };
-    auto body_of = [&](int frame) -> const double* {
-        return p.bodies != nullptr ? p.bodies + 9 * (size_t)find_rec(p.starts, p.R, frame) : p.body;
-    };
-    if (wave == 0) {
-        const int r = lane >> 1, sub = lane & 1;
-        const int row = blockIdx.x * PS_FK_ROWS + r;
-        if (row < p.rows) {
-            int frame;
-            const float* src = src_of(row, &frame);
-            double* dst = p.est + (size_t)row * p.W;
-            double s6[6];
-#pragma unroll
-            for (int c = 0; c < 6; ++c) s6[c] = load(src, (sub ? c_u : c_l) + c);
-            const Quat q = six_drr_to_quat(s6);
-            const double* const body = body_of(frame);
-            const Vec3 bone = sub ? Vec3{body[3], body[4], body[5]} : Vec3{body[0], body[1], body[2]};
-            const Vec3 v = qrot(q, bone);
-            rot[r][sub][0] = v.x; rot[r][sub][1] = v.y; rot[r][sub][2] = v.z;
-            const int eq = sub ? e_uq : e_lq;
-            dst[eq] = q.w; dst[eq + 1] = q.x; dst[eq + 2] = q.y; dst[eq + 3] = q.z;
-        }
-    } else {
-        const int r = lane & 31;
-        const int row = blockIdx.x * PS_FK_ROWS + r;
-        if (row < p.rows) {
-            int frame;
-            const float* src = src_of(row, &frame);
-            double* dst = p.est + (size_t)row * p.W;
-            if (lane < 32) {
-                const double* const body = body_of(frame);
-                Vec3 uo{body[6], body[7], body[8]};
-                if (hips) {
-                    const Quat hq = hips_quat(load(src, c_h), load(src, c_h + 1));
-                    uo = qrot(hq, uo);
-                    dst[e_hq] = hq.w; dst[e_hq + 1] = hq.x; dst[e_hq + 2] = hq.y; dst[e_hq + 3] = hq.z;
-                    dst[6] = uo.x; dst[7] = uo.y; dst[8] = uo.z;
-                }
-                rot[r][2][0] = uo.x; rot[r][2][1] = uo.y; rot[r][2][2] = uo.z;
-            } else if (full) {                               // hand and lower-arm positions are network outputs here
-#pragma unroll
-                for (int c = 0; c < 3; ++c) { dst[c] = load(src, c); dst[3 + c] = load(src, 9 + c); }
-            }
-        }
-    }
-    __syncthreads();
-    if (wave == 0 && !full) {
-        const int r = lane >> 1, c = lane & 1;             // two lanes per row: the lower-arm origin / the hand origin
-        const int row = blockIdx.x * PS_FK_ROWS + r;
-        if (row < p.rows) {
-            double* dst = p.est + (size_t)row * p.W;
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                const double lo = rot[r][1][k] + rot[r][2][k];                 // qrot(uq, uarm_vec) + uo
-                if (c == 0) dst[3 + k] = lo;
-                else dst[k] = rot[r][0][k] + lo;                               // qrot(lq, larm_vec) + lo
-            }
-        }
-    }
-}
+__global__ __launch_bounds__(128) void ape_post_sweep_fk_kernel(const PostFkParams p) { post_fk_rows(p); }
 
 // One (frame, configuration) pair: the stack of frame f at (smooth, M) -> 25 message values and, SPR, the 21 of its spread record.
 // `fb` is the first row of frame `fbase` (fbase <= every frame the stack reaches), frames `fs` words apart, a frame's samples W apart.
@@ -306,41 +219,10 @@ int make_plan(int layout, int F, const int32_t* cfg, int C, long long bound, Pla
     return APE_OK;
 }
 
-// The workspace of a device: the two chunk buffers and the staged host arrays.  Kept and grown on demand; a call waits (on its stream)
-// for the event recorded behind the last one, so calls on different streams do not share it at the same time.
-struct Workspace {
-    void* dev = nullptr;
-    size_t cap = 0;
-    hipEvent_t done = nullptr;
-    bool used = false;
-};
+// The workspace of a device (post_common.h): the two chunk buffers and the staged host arrays.
 std::mutex g_mu;
-std::vector<Workspace*> g_ws;                           // by device index
+std::vector<PostWorkspace*> g_ws;                          // by device index
 thread_local int g_last[4] = {0, 0, 0, 0};
-
-int take_workspace(int device, size_t bytes, hipStream_t st, Workspace** out) {
-    if ((size_t)device >= g_ws.size()) g_ws.resize((size_t)device + 1, nullptr);
-    Workspace*& w = g_ws[(size_t)device];
-    if (w == nullptr) {
-        w = new Workspace();
-        const hipError_t e = hipEventCreateWithFlags(&w->done, hipEventDisableTiming);
-        if (e != hipSuccess) {
-            delete w; w = nullptr;
-            return ape_fail(APE_ERR_HIP, "post_sweep: hipEventCreate failed: %s", hipGetErrorString(e));
-        }
-    }
-    if (w->cap < bytes) {
-        if (w->used) PS_TRY(hipEventSynchronize(w->done));
-        if (w->dev) (void)hipFree(w->dev);
-        w->dev = nullptr; w->cap = 0; w->used = false;
-        PS_TRY(hipMalloc(&w->dev, bytes));
-        w->cap = bytes;
-    } else if (w->used) {
-        PS_TRY(hipStreamWaitEvent(st, w->done, 0));
-    }
-    *out = w;
-    return APE_OK;
-}
 
 template <typename TMsg, bool SPR>
 hipError_t launch_sweep(const PsParams& p, unsigned blocks, size_t lds_bytes, hipStream_t st) {
@@ -403,8 +285,8 @@ int ape_post_sweep(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc, 
     const size_t total = 2 * buf_words * sizeof(double) + bodies_bytes + starts_bytes;
 
     std::lock_guard<std::mutex> lock(g_mu);
-    Workspace* ws = nullptr;
-    if (int rc = take_workspace(m->dims.device, total, st, &ws)) return rc;
+    PostWorkspace* ws = nullptr;
+    if (int rc = take_post_workspace(g_ws, "post_sweep", m->dims.device, total, st, &ws)) return rc;
     double* est[2] = {static_cast<double*>(ws->dev), static_cast<double*>(ws->dev) + buf_words};
     double* bodies_d = reinterpret_cast<double*>(static_cast<char*>(ws->dev) + 2 * buf_words * sizeof(double));
     int* starts_d = reinterpret_cast<int*>(reinterpret_cast<char*>(bodies_d) + bodies_bytes);
@@ -412,7 +294,7 @@ int ape_post_sweep(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc, 
     hipError_t e = hipMemcpyAsync(starts_d, seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st);
     if (e == hipSuccess && table) e = hipMemcpyAsync(bodies_d, bodies_host, bodies_bytes, hipMemcpyHostToDevice, st);
 
-    PsFkParams fk{};
+    PostFkParams fk{};
     fk.y = y_dev;
     fk.yy_m = m->stats + 2 * m->dims.input_size;
     fk.yy_s = fk.yy_m + m->dims.output_size;
@@ -446,7 +328,7 @@ int ape_post_sweep(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc, 
             e = hipMemcpyAsync(cur, est[(c + 1) & 1] + (size_t)prev_frames * q.Mx * q.W, carry_words * sizeof(double), hipMemcpyDeviceToDevice, st);
         if (e != hipSuccess) break;
         fk.est = cur + carry_words; fk.rows = frames * q.Mx; fk.f_lo = f_lo;
-        hipLaunchKernelGGL(ape_post_sweep_fk_kernel, dim3((unsigned)((fk.rows + PS_FK_ROWS - 1) / PS_FK_ROWS)), dim3(128), 0, st, fk);
+        hipLaunchKernelGGL(ape_post_sweep_fk_kernel, dim3((unsigned)((fk.rows + POST_FK_ROWS - 1) / POST_FK_ROWS)), dim3(128), 0, st, fk);
         e = hipGetLastError();
         if (e != hipSuccess) break;
         p.est = cur; p.f_lo = f_lo; p.f_hi = f_lo + frames;

@@ -30,6 +30,7 @@ SCORE_WIDTH, SCORE_ACC_WIDTH = 7, 25        # APE_SCORE_WIDTH, APE_SCORE_ACC_WID
 TRUTH_TARGETS, TRUTH_EST = 0, 1             # APE_TRUTH_*
 SCORE_MAX_LAG, SCORE_MAX_LAGS = 128, 65      # APE_SCORE_MAX_LAG, APE_SCORE_MAX_LAGS (ape_score_lags)
 POST_MAX_CONFIGS = 64             # APE_POST_MAX_CONFIGS (ape_post_sweep)
+POST_MAX_WINDOW = 64              # APE_POST_MAX_WINDOW (ape_post_window)
 FRAME_ACC_WIDTH = 51              # APE_FRAME_ACC_WIDTH (ape_frame_sums)
 BODY_ACC_WIDTH = 46               # APE_BODY_ACC_WIDTH (ape_body_sums)
 BODY_ROT_MSG, BODY_ROT_TRUTH = 0, 1         # APE_BODY_ROT_*
@@ -214,6 +215,11 @@ SIGNATURES["ape_score_lags"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.c_
 SIGNATURES["ape_post_sweep"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_uint32,
                                           C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p])
 SIGNATURES["ape_post_sweep_last"] = (C.c_int, [C.POINTER(C.c_int32)])
+# windowed post-filter: model, y, F, n_mc, starts_host, R, windows_host [C,3], weights_host [C,64] or NULL, C, flags,
+# bodies_host, n_bodies, out + dtype, workspace_bytes, HIP stream; and the debug counter of the last call's plan
+SIGNATURES["ape_post_window"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p])
+SIGNATURES["ape_post_window_last"] = (C.c_int, [C.POINTER(C.c_int32)])
 # heading and frame offset against the truth.  The sums: layout, msg + stride, msg dtype, truth + kind + dtype, F,
 # starts_host, R, skip, bodies_host, n_bodies, lag_min, lag_max, rec_lag_host, acc, HIP stream.  The rotation: layout, msg + stride,
 # spread + stride, msg dtype, F, starts_host, R, quats_host, n_quats, out + dtype, HIP stream

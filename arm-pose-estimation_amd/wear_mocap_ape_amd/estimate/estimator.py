@@ -841,6 +841,47 @@ class Estimator:
             res["motion"] = score.motion_sums(self._layout, out, "msg", starts, skip, times)[1].cpu().numpy()
         return res
 
+    # ---- windowed post-filter: windows that look ahead, tapered weights (the reference has no counterpart) ----
+    def repost_windows(self, y, windows, starts=None, bonemaps=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
+        """``score.post_window`` with this estimator's model and body: ``y`` as for ``repost``, ``windows`` a list of
+        ``score.window(back, ahead, samples, shape_or_weights)`` entries -> ``out [C, F, 25]`` (``(out, spread [C, F, 21])`` with
+        ``spread``): frame ``f`` of ``out[c]`` is smoothed over the frames ``f - back .. f + ahead`` of its recording.  A uniform
+        ``(smooth - 1, 0, samples)`` is ``repost``'s ``(smooth, samples)``, bit for bit.  ``bonemaps``: one entry per recording."""
+        from wear_mocap_ape_amd import score
+        model = self._hip_model()
+        if model is None or self._frame_samples() is None:
+            raise UserWarning("this estimator has no HIP regressor")
+        if not self._normalize:
+            raise UserWarning("repost_windows de-normalises its targets: this estimator does not normalise")
+        if bonemaps is not None:
+            R = len(np.asarray([0] if starts is None else starts).reshape(-1))
+            bonemaps = bodies_from(bonemaps, R, "repost_windows bonemaps")
+        return score.post_window(model, y, windows, starts, bonemaps, spread, out_dtype, workspace_bytes)
+
+    def sweep_windows(self, rows, truth, windows, starts=None, lags=(0, 0), truth_kind="targets", bonemaps=None, seed: int = 0x5EED,
+                      skip=None, big_endian: bool = False, motion: bool = False, times=None):
+        """What looking ahead and tapering buy, for a recording processed offline: ONE ``process_recording(return_targets=True)`` at the
+        largest sample count of ``windows`` (``score.window`` entries; this estimator's own ``smooth`` and sample count stay what they
+        are), one ``score.post_window`` with the spread records, then one ``score.score_lags`` over ``lags`` per window against
+        ``truth``.  Over an ``ImuPoseLSTM`` every sample count is 1.  ``skip``, ``truth_kind``, ``bonemaps``, ``motion``, ``times``:
+        ``sweep_recording``'s.  Returns ``sweep_recording``'s dict with ``"configs"`` holding the windows as ``score.window`` returns
+        them (waits for the device)."""
+        from wear_mocap_ape_amd import score
+        from wear_mocap_ape_amd.estimate.nn_models import effective_mc
+        model = self._hip_model()
+        if model is None or self._frame_samples() is None:
+            raise UserWarning("this estimator has no HIP regressor or no batched feature builder")
+        windows = [(b, a, effective_mc(model, int(m)), w) for b, a, m, w in score._windows(windows)[0]]
+        top = max(m for _, _, m, _ in windows)
+        _, y = self.process_recording(rows, starts=starts, big_endian=big_endian, return_targets=True, seed=seed, bonemaps=bonemaps,
+                                      _config=(1, top))
+        out, rec = self.repost_windows(y, windows, starts=starts, bonemaps=bonemaps, spread=True)
+        skip = self._sequence_len - 1 if skip is None else skip
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        res = score.score_windows(self._layout, out, rec, truth, windows, lags, truth_kind, starts, skip, bodies)
+        if motion:
+            res["motion"] = score.motion_sums(self._layout, out, "msg", starts, skip, times)[1].cpu().numpy()
+        return res
 
     # read-only views, same names as the reference's properties (estimator.py:188-218)
     sequence_len = property(lambda self: self._sequence_len)

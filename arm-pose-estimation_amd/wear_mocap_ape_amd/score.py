@@ -49,7 +49,12 @@ humeral twist, hips yaw) with their errors against truth and the
 All of these state their numbers per recording.  ``stats_by`` states one per-frame column as a function of another: the count, sum, sum
 of squares and maximum of any value columns over the bins of any key columns -- the hand error over the elbow flexion, over the hand
 speed, over the predicted sigma (``spread_sigma``; ``ape_score_by``) -- in a stated order of summation, so the same
-inputs give the same bits; ``merge_by``, ``pool_by`` and ``summarise_by`` work on the records, ``stats_by_numpy`` is the host statement."""
+inputs give the same bits; ``merge_by``, ``pool_by`` and ``summarise_by`` work on the records, ``stats_by_numpy`` is the host statement.
+
+Every smoothing route looks backwards and pays for it in lag.  A recording processed offline need not: ``post_window`` runs the
+post-filter from one replay's stored targets at windows that look ahead as far as they look back, with per-frame weights that taper
+(``ape_post_window``); ``window`` and ``window_weights`` make the configurations, ``score_windows`` scores every window
+over a sweep of lags, ``post_window_numpy`` is the host statement."""
 import ctypes as C
 import math
 
@@ -466,15 +471,289 @@ def score_configs(layout: int, out, spread, truth, configs, lags=(0, 0), truth_k
     """The scoring half of ``Estimator.sweep_recording``: one ``score_lags`` sweep per configuration on the strided views ``out[c]``
     (and ``spread[c]``; ``spread`` may be None) of a ``post_sweep`` result, assembled into ``{"configs": [(smooth, samples), ...],
     "acc": ndarray [C, R, L, 25], "best": [best_lag(acc[c], lags, error) per configuration]}`` (waits for the device)."""
-    configs = [(int(s), int(m)) for s, m in configs]
+    return _score_sets("score_configs", [(int(s), int(m)) for s, m in configs], layout, out, spread, truth, lags, truth_kind, starts, skip,
+                       bodies, error)
+
+
+def _score_sets(who: str, configs: list, layout: int, out, spread, truth, lags, truth_kind, starts, skip, bodies, error) -> dict:
+    """one ``score_lags`` sweep per set ``out[c]`` (with ``spread[c]``), assembled: what ``score_configs`` and ``score_windows`` share"""
     if not configs or len(out) != len(configs) or (spread is not None and len(spread) != len(configs)):
-        raise UserWarning(f"score_configs: {len(configs)} configurations for {len(out)} results")
+        raise UserWarning(f"{who}: {len(configs)} configurations for {len(out)} results")
     accs = [_as_host(score_lags(layout, out[c], truth, lags, truth_kind, None if spread is None else spread[c], starts, skip, bodies)[1], (3,))
             for c in range(len(configs))]
     if any(a.shape != accs[0].shape for a in accs):
-        raise UserWarning("score_configs: accumulators of different sweeps")
+        raise UserWarning(f"{who}: accumulators of different sweeps")
     acc = np.stack(accs)
     return {"configs": configs, "acc": acc, "best": [best_lag(acc[c], lags, error) for c in range(len(configs))]}
+
+
+# ---- windowed post-filter: centred and tapered windows over one replay's targets (ape_post_window, DESIGN.md 4.43) -------------------------
+# ``smooth = n`` stacks the last n frames, so the estimate trails the motion by (n - 1) / 2 frames.  A recording processed offline can
+# look ahead as far as it looks back: a window ``(back, ahead)`` with ``back == ahead`` has no group delay, and per-frame weights that
+# fall off towards its ends keep the motion's curvature where a boxcar of the same width flattens it.  The same window is what a live
+# estimator delayed by ``ahead`` frames could emit, so one call also answers what k frames of look-ahead would buy.
+POST_MAX_WINDOW = _hip.POST_MAX_WINDOW
+WINDOW_SHAPES = ("uniform", "triangle", "hann")
+
+
+def window_weights(shape: str, back: int, ahead: int):
+    """The frame weights of a window of ``back`` frames behind and ``ahead`` frames ahead of its frame, oldest frame first: float64
+    ``[back + ahead + 1]`` summing to 1, or None for ``"uniform"``.  With ``d = j - back`` and ``D = max(back, ahead)``: ``"triangle"``
+    is ``1 - |d| / (D + 1)``, ``"hann"`` is ``0.5 (1 + cos(pi d / (D + 1)))``, each divided by its sum.  Every weight is > 0 and the
+    largest sits on the frame itself (index ``back``): a one-sided window peaks at its newest (``ahead == 0``) or oldest frame."""
+    back, ahead = int(back), int(ahead)
+    if back < 0 or ahead < 0 or back + ahead + 1 > POST_MAX_WINDOW:
+        raise UserWarning(f"window ({back}, {ahead}): back, ahead >= 0 and back + ahead + 1 <= {POST_MAX_WINDOW}")
+    if shape not in WINDOW_SHAPES:
+        raise UserWarning(f"shape must be one of {WINDOW_SHAPES}, got {shape!r}")
+    if shape == "uniform":
+        return None
+    d, D = np.arange(back + ahead + 1, dtype=np.float64) - back, max(back, ahead)
+    w = 1.0 - np.abs(d) / (D + 1) if shape == "triangle" else 0.5 * (1.0 + np.cos(np.pi * d / (D + 1)))
+    return w / w.sum()
+
+
+def window(back: int, ahead: int, samples: int, shape_or_weights="uniform") -> tuple:
+    """one configuration of ``post_window``: ``(back, ahead, samples, weights)`` with ``weights`` None (uniform) or float64
+    ``[back + ahead + 1]``; ``shape_or_weights``: one of ``WINDOW_SHAPES`` or the frame weights themselves, oldest frame first, which
+    must sum to 1 (they are passed on as they are)"""
+    back, ahead, samples = int(back), int(ahead), int(samples)
+    if isinstance(shape_or_weights, str):
+        return (back, ahead, samples, window_weights(shape_or_weights, back, ahead))
+    if shape_or_weights is None:
+        return (back, ahead, samples, None)
+    w = np.array(shape_or_weights, dtype=np.float64).reshape(-1)
+    if back < 0 or ahead < 0 or w.shape[0] != back + ahead + 1:
+        raise UserWarning(f"window ({back}, {ahead}): {w.shape[0]} weights for {back + ahead + 1} frames")
+    return (back, ahead, samples, w)
+
+
+def _windows(windows):
+    """``(windows, int32 [C, 3], float64 [C, 64] | None)`` of a list of ``(back, ahead, samples[, shape or weights])`` entries: the list
+    with every entry as ``window`` returns it, and the two arrays of the C ABI (no weight table where every window is uniform; the row
+    of a uniform window in a table holds ``1 / n``, bit-equal entries)"""
+    try:
+        ws = [window(*w) for w in windows]
+    except TypeError:
+        raise UserWarning("windows: a list of (back, ahead, samples[, shape or weights]) entries (score.window)")
+    if not 1 <= len(ws) <= _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"windows: between 1 and {_hip.POST_MAX_CONFIGS} windows, got {len(ws)}")
+    wn = np.ascontiguousarray(np.asarray([w[:3] for w in ws], dtype=np.int32).reshape(-1, 3))
+    if (wn[:, :2] < 0).any() or (wn[:, 0] + wn[:, 1] + 1 > POST_MAX_WINDOW).any():
+        raise UserWarning(f"windows: back, ahead >= 0 and back + ahead + 1 <= {POST_MAX_WINDOW}")
+    if all(w[3] is None for w in ws):
+        return ws, wn, None
+    table = np.zeros((len(ws), POST_MAX_WINDOW), dtype=np.float64)
+    for c, (b, a, _, w) in enumerate(ws):
+        table[c, :b + a + 1] = 1.0 / (b + a + 1) if w is None else w
+    return ws, wn, table
+
+
+def post_window(model, y, windows, starts=None, bodies=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
+    """The float64 post-filter of a replay from stored targets, as ``post_sweep``, at windows that may look ahead and may be tapered
+    (``ape_post_window``).  ``model``, ``y``, ``starts``, ``bodies``, ``workspace_bytes``: ``post_sweep``'s; ``windows``: a list of
+    ``window(back, ahead, samples, shape_or_weights)`` entries (plain ``(back, ahead, samples)`` tuples are uniform): window ``c`` stacks the
+    first ``samples`` samples of the frames ``f - back .. f + ahead``, both ends clamped to the frame's recording, frame ``j`` weighted by
+    ``weights[j]``.  A uniform ``(smooth - 1, 0, samples)`` gives the bits of ``post_sweep``'s ``(smooth, samples)``.
+    Returns ``out [C, F, 25]`` of ``out_dtype`` on the device or, with ``spread``, ``(out, spread)`` with ``spread [C, F, 21]``: two
+    views of one tensor.  Does not wait."""
+    from wear_mocap_ape_amd.data_types.bone_map import bodies_from
+    if out_dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
+    if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 3 or y.shape[0] < 1:
+        raise UserWarning("y: a float32 device tensor [F >= 1, M, O] (process_recording(return_targets=True))")
+    if y.shape[2] != model.output_size:
+        raise UserWarning(f"y: {y.shape[2]} targets per row, the model has {model.output_size}")
+    _, wn, table = _windows(windows)
+    st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
+    F, M, R, C_ = int(y.shape[0]), int(y.shape[1]), int(st.shape[0]), int(wn.shape[0])
+    body = None
+    if bodies is not None:
+        body = np.ascontiguousarray(bodies.reshape(1, 9), dtype=np.float64) if isinstance(bodies, np.ndarray) and bodies.size == 9 \
+            else bodies_from(bodies, R, "post_window bodies")
+    yd = y.contiguous()
+    dev = yd.device
+    with torch.cuda.device(dev):
+        width = 25 + (_hip.SPREAD_WIDTH if spread else 0)
+        out = torch.empty((C_, F, width), dtype=out_dtype, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_post_window(model.handle, C.c_void_p(yd.data_ptr()), F, M, C.c_void_p(st.ctypes.data), R,
+                                              C.c_void_p(wn.ctypes.data), C.c_void_p(table.ctypes.data) if table is not None else None, C_,
+                                              _hip.FLAG_SPREAD if spread else 0, C.c_void_p(body.ctypes.data) if body is not None else None,
+                                              int(body.shape[0]) if body is not None else 0, C.c_void_p(out.data_ptr()), _f64(out_dtype),
+                                              int(workspace_bytes), stream), "ape_post_window")
+    if spread:
+        return out[:, :, :25], out[:, :, 25:]
+    return out
+
+
+def post_window_last() -> dict:
+    """the plan of this thread's last ``post_window`` (debug counter): passes over the workspace, frames per pass, frames per workgroup
+    tile, and whether the tiles were staged in LDS"""
+    v = (C.c_int32 * 4)()
+    _hip.check(_hip.lib().ape_post_window_last(v), "ape_post_window_last")
+    return {"passes": int(v[0]), "chunk_frames": int(v[1]), "tile_frames": int(v[2]), "lds": bool(v[3])}
+
+
+def post_window_plan(layout: int, F: int, windows, workspace_bytes: int = 0) -> dict:
+    """the workspace rule of include/ape_hip.h on the host: frames per pass and passes of a ``post_window`` over ``F`` frames"""
+    _, wn, _ = _windows(windows)
+    H, A, frame_bytes = int(wn[:, 0].max()), int(wn[:, 1].max()), 8 * _hip.EST_WIDTH[layout] * int(wn[:, 2].max())
+    bound = int(workspace_bytes) if workspace_bytes else 128 << 20
+    chunk = min(int(F), bound // (2 * frame_bytes) - H - A)
+    if chunk < 1:
+        raise UserWarning(f"workspace_bytes {bound} holds no frame (at least {2 * frame_bytes * (H + A + 1)})")
+    return {"passes": -(-int(F) // chunk), "chunk_frames": chunk, "frame_bytes": frame_bytes, "back_frames": H, "ahead_frames": A}
+
+
+def _targets_est(pred, body, layout: int) -> np.ndarray:
+    """de-normalised targets ``[n, O]`` -> est rows ``[n, 21 | 14]`` under one body ``[9]``: the forward kinematics of
+    estimate_joints.py:16-92 in numpy, with the closed-form quaternion of csrc/fk_device.h (the largest of trace, m00, m11, m22 as the
+    pivot, then ``w >= 0``) where the reference takes an eigenvector"""
+    def quat(s):
+        a1, a2 = s[:, [0, 2, 4]], s[:, [1, 3, 5]]
+        b1 = a1 / np.linalg.norm(a1, axis=1, keepdims=True)
+        u2 = a2 - np.sum(b1 * a2, axis=1, keepdims=True) * b1
+        b2 = u2 / np.linalg.norm(u2, axis=1, keepdims=True)
+        b3 = np.cross(b1, b2, axis=1)
+        m00, m01, m02, m10, m11, m12, m20, m21, m22 = b1[:, 0], b2[:, 0], b3[:, 0], b1[:, 1], b2[:, 1], b3[:, 1], b1[:, 2], b2[:, 2], b3[:, 2]
+        tr = m00 + m11 + m22
+        cand = np.stack([tr, m00, m11, m22], axis=1)
+        piv = np.where(np.isnan(cand).any(axis=1), 0, np.argmax(np.nan_to_num(cand, nan=-np.inf), axis=1))
+        s0, s1 = np.sqrt(tr + 1.0) * 2.0, np.sqrt(1.0 + m00 - m11 - m22) * 2.0
+        s2, s3 = np.sqrt(1.0 + m11 - m00 - m22) * 2.0, np.sqrt(1.0 + m22 - m00 - m11) * 2.0
+        forms = [np.stack([0.25 * s0, (m21 - m12) / s0, (m02 - m20) / s0, (m10 - m01) / s0], axis=1),
+                 np.stack([(m21 - m12) / s1, 0.25 * s1, (m01 + m10) / s1, (m02 + m20) / s1], axis=1),
+                 np.stack([(m02 - m20) / s2, (m01 + m10) / s2, 0.25 * s2, (m12 + m21) / s2], axis=1),
+                 np.stack([(m10 - m01) / s3, (m02 + m20) / s3, (m12 + m21) / s3, 0.25 * s3], axis=1)]
+        q = np.choose(piv[:, None], forms)
+        return np.where(q[:, :1] < 0, -q, q)
+
+    def hips_quat(sn, cs):
+        half = 0.5 * np.arctan2(sn, cs)
+        zero = np.zeros_like(half)
+        return np.stack([np.cos(half), zero, np.sin(half), zero], axis=-1)
+
+    n = pred.shape[0]
+    larm_vec, uarm_vec, uarm_orig = (np.tile(body[i:i + 3], (n, 1)) for i in (0, 3, 6))
+    with np.errstate(all="ignore"):
+        if layout == _hip.LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS:
+            uq, lq, hq = quat(pred[:, 12:18]), quat(pred[:, 3:9]), hips_quat(pred[:, 18], pred[:, 19])
+            return np.concatenate([pred[:, 0:3], pred[:, 9:12], _qrot(hq, uarm_orig), lq, uq, hq], axis=1)
+        uq, lq = quat(pred[:, 6:12]), quat(pred[:, 0:6])
+        if layout == _hip.LAYOUT_ORI_CAL_LARM_UARM:
+            lo = _qrot(uq, uarm_vec) + uarm_orig
+            return np.concatenate([_qrot(lq, larm_vec) + lo, lo, lq, uq], axis=1)
+        hq = hips_quat(pred[:, 12], pred[:, 13])
+        uo = _qrot(hq, uarm_orig)
+        lo = _qrot(uq, uarm_vec) + uo
+        return np.concatenate([_qrot(lq, larm_vec) + lo, lo, uo, lq, uq, hq], axis=1)
+
+
+def _stack_quat(qs, u=None) -> np.ndarray:
+    """the sign-aligned mean of utility/transformations.py:32-51 over stacked quaternions ``[N, 4]``: row 0 is the reference direction,
+    a row whose dot product with it is < 0.0 is subtracted, rows added in order, the sum normalised; ``u [N]``: the rows' weights
+    (None: ``1 / N`` each)"""
+    w = 1 / len(qs)
+    acc = qs[0] * (w if u is None else u[0])
+    for i in range(1, len(qs)):
+        wi = w if u is None else u[i]
+        acc = acc + qs[i] * (-wi if float(np.dot(qs[i], qs[0])) < 0.0 else wi)
+    return acc / np.linalg.norm(acc)
+
+
+def _stack_msg(stack, body, layout: int, u=None) -> np.ndarray:
+    """the 25-value message of stacked est rows ``[N, W]`` (compose_msg.py:13-108; one row is copied): mean quaternions by ``_stack_quat``,
+    the origins made again from them and the body ``[9]`` -- for the 20-target layout the means of the rows' origins, weighted:
+    ``sum u_i e_i`` from +0.0 in stack order"""
+    hips = layout != _hip.LAYOUT_ORI_CAL_LARM_UARM
+    ql, qu = (9, 13) if hips else (6, 10)
+    larm_vec, uarm_vec, uarm_orig = body[np.newaxis, 0:3], body[np.newaxis, 3:6], body[np.newaxis, 6:9]
+    if stack.shape[0] == 1:
+        ho, lo, lq, uq = stack[0, 0:3], stack[0, 3:6], stack[0, ql:ql + 4], stack[0, qu:qu + 4]
+        uo, hq = (stack[0, 6:9], stack[0, 17:21]) if hips else (body[6:9], np.array([1.0, 0.0, 0.0, 0.0]))
+        return np.concatenate([lq, ho, lq, lo, uq, uo, hq])
+    hq = _stack_quat(stack[:, 17:21], u) if hips else np.array([1.0, 0.0, 0.0, 0.0])
+    lq, uq = _stack_quat(stack[:, ql:ql + 4], u), _stack_quat(stack[:, qu:qu + 4], u)
+    if layout == _hip.LAYOUT_ORI_POS_CAL_LARM_UARM_HIPS:
+        if u is None:
+            uo, lo, ho = stack[:, 6:9].mean(axis=0), stack[:, 3:6].mean(axis=0), stack[:, 0:3].mean(axis=0)
+        else:
+            o = np.zeros(9)
+            for i in range(stack.shape[0]):
+                o = o + u[i] * stack[i, 0:9]
+            ho, lo, uo = o[0:3], o[3:6], o[6:9]
+    else:
+        uo = _qrot(hq[np.newaxis], uarm_orig)[0] if hips else body[6:9]
+        lo = _qrot(uq[np.newaxis], uarm_vec)[0] + uo
+        ho = _qrot(lq[np.newaxis], larm_vec)[0] + lo
+    return np.concatenate([lq, ho, lq, lo, uq, uo, hq])
+
+
+def _taper_record(stack, msg, layout: int, u) -> np.ndarray:
+    """the spread record of a tapered stack (``u [N]`` row weights summing to 1) from the weighted sums ``sum u p``, ``sum u (p_a p_b)``
+    and ``sum u (q_a q_b)``, the rows in order: the mean is the first sum, the covariance ``sum u p p' - mean mean'``, the angle
+    ``2 asin(sqrt(clip(1 - qm' (sum u q q') qm, 0, 1)))``"""
+    out = np.zeros(_hip.SPREAD_WIDTH)
+    ia, ib = np.triu_indices(3)
+    for c0, o0 in ((0, 0), (3, 9)):
+        s1, s2 = np.zeros(3), np.zeros(6)
+        for i in range(stack.shape[0]):
+            p = stack[i, c0:c0 + 3]
+            s1, s2 = s1 + u[i] * p, s2 + u[i] * (p[ia] * p[ib])
+        out[o0:o0 + 3], out[o0 + 3:o0 + 9] = s1, s2 - s1[ia] * s1[ib]
+    ja, jb = np.triu_indices(4)
+    diag = ja == jb
+    for k, c in enumerate((9, 13, 17) if layout != _hip.LAYOUT_ORI_CAL_LARM_UARM else (6, 10)):
+        s = np.zeros(10)
+        for i in range(stack.shape[0]):
+            q = stack[i, c:c + 4]
+            s = s + u[i] * (q[ja] * q[jb])
+        qm = msg[7 + 7 * k:11 + 7 * k]
+        t = s * (qm[ja] * qm[jb])
+        a = 1.0 - (t[diag].sum() + 2.0 * t[~diag].sum())
+        out[18 + k] = 2.0 * np.arcsin(np.sqrt(np.clip(a, 0.0, 1.0)))
+    return out
+
+
+def post_window_numpy(y, yy_m, yy_s, bodies, layout: int, starts, windows):
+    """The host statement of ``post_window``: ``y [F, M, O]`` normalised targets -> ``(out [C, F, 25], spread [C, F, 21])`` float64.
+    Every sample row is de-normalised in float64 and taken through ``_targets_est`` with its recording's body (``bodies [1 | R, 9]``)
+    once.  Stack row ``i`` of frame ``f`` of the recording ``[s, e)`` at window ``(back, ahead, m, weights)`` is sample ``i % m`` of
+    frame ``min(e - 1, max(s, f - back + i // m))``.  A uniform window (no weights, or bit-equal ones) is the message ``_stack_msg`` of
+    the stack at ``1 / N`` per row and the record ``_post.spread_rows`` of it; a tapered one weighs row ``i`` by
+    ``u_i = weights[i // m] / m`` in ``_stack_msg`` and takes its record from ``_taper_record``."""
+    from wear_mocap_ape_amd.estimate import _post
+    y = np.asarray(y)
+    F, M, O = y.shape
+    st = [int(s) for s in ([0] if starts is None else starts)]
+    ends = st[1:] + [F]
+    bodies = np.asarray(bodies, dtype=np.float64).reshape(-1, 9)
+    ws = _windows(windows)[0]
+    pred = y.reshape(-1, O).astype(np.float64) * yy_s + yy_m
+    E = np.zeros((F, M, _hip.EST_WIDTH[layout]))
+    for r, (a, b) in enumerate(zip(st, ends)):
+        E[a:b] = _targets_est(pred[a * M:b * M], bodies[r if bodies.shape[0] > 1 else 0], layout).reshape(b - a, M, -1)
+    out, spread = np.zeros((len(ws), F, 25)), np.zeros((len(ws), F, _hip.SPREAD_WIDTH))
+    with np.errstate(all="ignore"):
+        for c, (back, ahead, m, w) in enumerate(ws):
+            n = back + ahead + 1
+            u = None if w is None or bool((w.view(np.int64) == w.view(np.int64)[0]).all()) else np.repeat(w / float(m), m)
+            for r, (a, b) in enumerate(zip(st, ends)):
+                body = bodies[r if bodies.shape[0] > 1 else 0]
+                for f in range(a, b):
+                    stack = np.concatenate([E[min(b - 1, max(a, f - back + j)), :m] for j in range(n)])
+                    out[c, f] = _stack_msg(stack, body, layout, u)
+                    spread[c, f] = _post.spread_rows(stack, out[c, f], layout) if u is None else _taper_record(stack, out[c, f], layout, u)
+    return out, spread
+
+
+def score_windows(layout: int, out, spread, truth, windows, lags=(0, 0), truth_kind: str = "targets", starts=None, skip: int = 0,
+                  bodies=None, error: str = "hand_pos") -> dict:
+    """The scoring half of ``Estimator.sweep_windows``: ``score_configs`` for the views ``out[c]`` (and ``spread[c]``; ``spread`` may be
+    None) of a ``post_window`` result -> ``{"configs": [window(...) per window], "acc": ndarray [C, R, L, 25], "best":
+    [best_lag(acc[c], lags, error) per window]}`` (waits for the device)."""
+    return _score_sets("score_windows", _windows(windows)[0], layout, out, spread, truth, lags, truth_kind, starts, skip, bodies, error)
 
 
 # ---- each recording's heading and frame offset against the truth (ape_frame_sums, ape_rotate_rows, DESIGN.md 4.34) -------------------------

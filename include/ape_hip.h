@@ -982,6 +982,71 @@ int ape_post_sweep(ape_model_t* model, const float* y_dev, int32_t F, int32_t n_
                    int64_t workspace_bytes, void* stream);
 int ape_post_sweep_last(int32_t out4[4]);
 
+/* ---- windowed post-filter: centred and tapered windows over one replay's targets (additive in ABI 7) -------------------
+ * replaces: nothing; the reference smooths over the past alone (estimate/estimator.py:112-118), so its estimate trails the motion by
+ * (smooth - 1) / 2 frames.  A recording processed offline can look ahead as far as it looks back (no group delay), and a window that
+ * tapers towards its ends follows the motion's curvature where a boxcar of the same width flattens it.  ape_post_window re-smooths the
+ * stored targets of ONE replay (ape_replay*'s y_dev, as ape_post_sweep) at C windows (back_c, ahead_c, m_c, weights_c) in one call.
+ *   y_dev f32 [F, n_mc, O], seg_starts_host, bodies_host / n_bodies, flags, out_dtype, stream: those of ape_post_sweep.
+ *   windows_host int32 [C, 3]: (back_c, ahead_c, m_c).  Window c takes n_c = back_c + ahead_c + 1 frames and m_c samples of each.
+ *   Limits. back_c, ahead_c >= 0, n_c <= APE_POST_MAX_WINDOW, 1 <= m_c <= n_mc, n_c * m_c <= 4096, 1 <= C <= APE_POST_MAX_CONFIGS.
+ *   Stack.  Frame f belongs to a recording [s, e).  Stack row i < N = n_c * m_c is sample i % m_c of frame
+ *          min(e - 1, max(s, f - back_c + i / m_c)): both ends are clamped -- ape_replay's cold-start rule and its mirror image -- so N
+ *          is the same for every frame and nothing is ever read across a recording boundary.  Samples k >= m_c of any frame are never
+ *          read, and samples k >= max_c m_c are not converted.  Every row goes through pred * yy_s + yy_m in float64 and the forward
+ *          kinematics of ape_fk (the recording's body), once per call whatever C is.
+ *   Weights.  weights_host f64 [C, APE_POST_MAX_WINDOW], or NULL: uniform weights in every window.  The first n_c entries of row c are
+ *          the weights w_0 .. w_{n_c - 1} of the window's frames, oldest frame first; the rest of the row is not read.  Every entry
+ *          read must be finite and >= 0, and |sum_j w_j - 1| <= 1e-9 (summed in order, in float64), else the call is refused: the
+ *          library does not normalise, the sum is a condition on the caller.  The weight of stack row i is u_i = w_{i / m_c} / m_c,
+ *          one float64 division done on the host.
+ *   Uniform windows.  A window is uniform if weights_host is NULL or the n_c entries of its row are bit-equal.  It runs the statements
+ *          of ape_post_sweep / ape_replay unchanged apart from the two-sided clamp: row 0 times 1.0 / N first, every further row added
+ *          with +-1/N by the strict `dot < 0.0` rule against row 0 (the dot as the FMA chain), the 20-target layout's origins summed in
+ *          an in-order pass of their own and divided by N, one more in-order pass for the spread record.  So a uniform (smooth - 1, 0, m)
+ *          holds the bits ape_post_sweep writes for (smooth, m), and a uniform (b, a, m) at frame f those of (b + a + 1, m) at frame
+ *          f + a wherever f + a is a frame of the same recording.
+ *   Tapered windows.  The same order and the same sign rule with u_i in place of 1/N: a = q_0 u_0, then a += q_i (+-u_i), i = 1 ..
+ *          N - 1, the sign by `dot(q_i, q_0) < 0.0`; a row 0 of weight zero is still the sign reference.  The message's quaternions are
+ *          a / |a|.  The 20-target layout's origins are sum_i u_i e_i, summed from +0.0 in stack order.  The spread record comes from
+ *          the weighted sums sum u p, sum u (p_a p_b) and sum u (q_a q_b) taken in one in-order pass: the mean is the first sum, the
+ *          covariance sum u p p' - mean mean', the angle 2 asin(sqrt(clip(1 - qm' (sum u q q') qm, 0, 1))) with the clamp by
+ *          comparisons (a NaN passes, as through numpy.clip).  The weights sum to 1, so these are the weighted mean, the weighted
+ *          population covariance and the weighted angular spread.
+ *          N == 1 (a window of one frame and one sample; its one weight is 1): the row is copied, the record has zeros by rule.
+ *   out_dev [C, F, 25] of out_dtype, with APE_FLAG_SPREAD [C, F, 25 + APE_SPREAD_WIDTH] (the record in the last 21 columns of a row).
+ *   workspace_bytes: bound on the device workspace for converted rows, whatever F is; 0 = 128 MiB.  With W = 21 (14 without hips),
+ *          Mx = max_c m_c, H = max_c back_c, A = max_c ahead_c and frame_bytes = 8 W Mx, a pass covers chunk = min(F, workspace_bytes /
+ *          (2 frame_bytes) - H - A) frames (two buffers of H + chunk + A frames); ceil(F / chunk) passes; chunk < 1 is refused and the
+ *          message names the smallest bound that works, 2 frame_bytes (H + A + 1).  The last H + A frames of a pass are carried to the
+ *          front of the other buffer, so a row is converted once per call.  Beside the buffers the call keeps copies of its host arrays
+ *          (4 R + 72 n_bodies bytes, and 8 APE_POST_MAX_WINDOW C bytes of row weights when a window is tapered).  The result does not
+ *          depend on the bound.  Within a pass a workgroup stages its tile of frames, the H frames before and the A frames after it
+ *          (clipped to [0, F)) and the weight table in LDS where that fits (and the tile gives its lanes enough (frame, window) pairs);
+ *          otherwise rows and weights are read from the workspace.  Same statements and same bits either way.
+ * The model handle supplies the target layout, yy_m / yy_s and the default body; no weights of the network are read.  Not journaled:
+ * there is nothing for ape_model_recover to re-issue.  No floating-point atomics and a fixed order of summation: the same inputs give
+ * the same bits.  The launches go on `stream` and the call does not wait for them; the host arrays (seg_starts_host, windows_host,
+ * weights_host, bodies_host) have been consumed when it returns.  (The workspace is kept per device, apart from ape_post_sweep's, and
+ * grows on demand, which may wait for the device; a call on another stream is ordered behind the last user by an event.)
+ * Refused on the host before anything is written: NULL model / y_dev / out_dev / seg_starts_host / windows_host; F < 1, R < 1, bad
+ * starts; n_mc < 1; F * n_mc >= 2^31; C < 1 or C > APE_POST_MAX_CONFIGS; back < 0, ahead < 0, n > APE_POST_MAX_WINDOW, m outside
+ * [1, n_mc], n * m > 4096; a weight that is not finite or negative, a row that does not sum to 1 within 1e-9; n_bodies not 0 / 1 / R
+ * (0 iff bodies_host is NULL); flags other than APE_FLAG_SPREAD; an unknown dtype; workspace_bytes < 0 or too small for one frame
+ * (APE_ERR_INVALID_ARG); norm stats not set (APE_ERR_NOT_READY); APE_LAYOUT_NONE; a capturing stream.
+ * ape_post_window_last: debug counter -- the plan of this thread's last successful ape_post_window: out4 = {passes, frames per pass,
+ * frames per tile, 1 if the tiles were staged in LDS}. */
+#define APE_POST_MAX_WINDOW 64
+int ape_post_window(ape_model_t* model, const float* y_dev, int32_t F, int32_t n_mc,
+                    const int32_t* seg_starts_host, int32_t R,
+                    const int32_t* windows_host /* [C,3]: back, ahead, samples */,
+                    const double* weights_host /* [C, APE_POST_MAX_WINDOW] or NULL */, int32_t C,
+                    uint32_t flags /* APE_FLAG_SPREAD or 0 */,
+                    const double* bodies_host /* [n_bodies,9] or NULL: the model's body */, int32_t n_bodies,
+                    void* out_dev /* [C, F, 25 (+21)] */, int32_t out_dtype,
+                    int64_t workspace_bytes, void* stream);
+int ape_post_window_last(int32_t out4[4]);   /* passes, frames per pass, frames per tile, staged in LDS */
+
 /* ---- each recording's heading and frame offset against the truth (additive in ABI 7) -------------------------------------
  * replaces: nothing; the reference has no counterpart.  Every input is calibrated against a forward direction taken from a calibration
  * pose; a wearer who stood a few degrees off, or a mocap frame that is not levelled, leaves the whole estimate of a recording turned
