@@ -1,13 +1,17 @@
-// What the post-filter passes over a replay's stored targets share (post_sweep.hip; post_window.hip):
-// the conversion of sample rows to est rows, done once per call, and the per-device workspace the converted rows live in.
+// The post-filter pass over a replay's stored targets, behind its two entries ape_post_sweep (post_sweep.hip) and
+// ape_post_window (post_window.hip): the driver both fronts call, the conversion of sample rows to est rows, done once
+// per call, and the per-device workspace the converted rows live in.
 //
-// post_fk_rows  the body of each file's conversion kernel: sample rows k < Mx of a run of frames -> est rows.  ape_fk3_kernel's
+// post_filter   the one plan and host driver, defined in post_window.hip beside the kernels.  A front checks its own arguments, states
+//               its configurations as windows (back, ahead, samples) and calls it under its own name.
+// post_fk_rows  the body of the conversion kernel: sample rows k < Mx of a run of frames -> est rows.  ape_fk3_kernel's
 //               decomposition (fk.hip: a row's three chains side by side, 32 rows per workgroup of two waves) and its statements, with
 //               the row index mapped: compact row r = frame r / Mx, sample r % Mx.  Launch with 128 threads and
 //               ceil(rows / POST_FK_ROWS) workgroups.
 // PostWorkspace the chunk buffers and the staged host arrays of one device.  Kept and grown on demand; a call waits (on its stream) for
-//               the event recorded behind the last one, so calls on different streams do not share it at the same time.  Each entry
-//               point keeps a list of its own.
+//               the event recorded behind the last one, so calls on different streams do not share it at the same time.  post_filter
+//               owns the one list and its mutex: the library keeps one buffer per device, and a sweep and a window call on different
+//               streams of one device are ordered after one another, as two sweeps are.
 //
 // float64 with separate roundings for a * b + c, like numpy: contraction is off inside every device function here.
 #pragma once
@@ -116,6 +120,15 @@ __device__ __forceinline__ void post_fk_rows(const PostFkParams& p) {
 }
 
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
+// The pass itself, for arguments the front has checked on their own: refuses what the model does not allow, plans, stages the host
+// arrays and launches.  `who` / `sets`: the front's name and its word for its list, for the error texts.  windows_host int32 [C, 3]
+// (back, ahead, samples); weights_host [C, APE_POST_MAX_WINDOW] frame weights or nullptr; tapered [C] (nullptr: none): which windows
+// take their row of the weights, every other one is uniform.  workspace_bytes 0: the default bound.  On success last4 receives the
+// plan: passes, frames per pass, frames per tile, staged in LDS.
+int post_filter(const char* who, const char* sets, ape_model_t* m, const float* y_dev, int F, int n_mc, const int32_t* seg_starts_host, int R,
+                const int32_t* windows_host, const double* weights_host, const bool* tapered, int C, uint32_t flags, const double* bodies_host,
+                int n_bodies, void* out_dev, int out_dtype, long long workspace_bytes, void* stream, int last4[4]);
+
 struct PostWorkspace {
     void* dev = nullptr;
     size_t cap = 0;

@@ -4,8 +4,12 @@
 // reference smooths over the past alone (estimator.py:112-118) and has no counterpart beyond the per-frame arithmetic
 // (estimator.py:108-118,122-137; compose_msg.py:13-108; transformations.py:32-51).
 //
+// This file holds the one implementation of the post-filter pass over stored targets: the kernels, the plan and the host driver
+// post_filter (declared in post_common.h).  ape_post_window below and ape_post_sweep (post_sweep.hip, DESIGN.md 4.33: configuration
+// (smooth, m) is the uniform window (smooth - 1, 0, m)) are fronts that check their arguments and call it.
+//
 // ape_post_window_fk_kernel  the work the windows share (post_common.h): sample rows k < Mx = max m_c -> est rows, once per call.
-// ape_post_window_kernel     all C reductions of a tile of frames, after ape_post_sweep_kernel.  A lane takes (frame, window) pairs, the
+// ape_post_window_kernel     all C reductions of a tile of frames.  A lane takes (frame, window) pairs, the
 //                            windows in the order of falling stack height so that a wave's lanes run stacks of like length, frames fastest
 //                            so that a wave's lanes read neighbouring frames.  LDS = true: the workgroup first copies the tile's est
 //                            rows, the H = max back frames before and the A = max ahead frames after them (clipped to [0, F): one
@@ -17,8 +21,13 @@
 // The chunk: est rows of H carried-over frames, `chunk` frames and A frames ahead, two buffers used in turn: the last H + A frames of a
 // buffer are copied to the front of the other one, so a row is converted once per call.  Both sizes follow from the caller's byte bound.
 //
-// Uniform windows run the statements of post_sweep.hip's sweep_pair with both ends of the frame index clamped: the same bits for the
-// same stack.  Tapered windows keep the order and the sign rule and put the row weight u_i = w_{i / m} / m where 1 / N stands.
+// Order of the sums (uniform windows): ape_replay_msg_kernel's -- row 0 times 1/N first, every further row added with +-1/N by the
+// strict `dot < 0.0` rule against row 0 (the dot as ape_msg_kernel's FMA chain), the origin means summed and then divided by N, then one
+// more in-order pass for the spread record.  The three quaternions share one pass over the rows (each accumulator still sees its own
+// additions in the same order: the same bits).  Tapered windows keep the order and the sign rule and put the row weight
+// u_i = w_{i / m} / m where 1 / N stands.  A call whose windows are all uniform with ahead = 0 (every sweep) runs the SWEEP
+// instantiations, which hold neither the tapered form nor the upper clamp of the frame index (it cannot act there: the same bits);
+// profiles/post_window.md has the figures that decided it.
 // No inline assembly, no read-modify-write on shared memory between lanes: every output value is one lane's own in-order sum.
 //
 // float64 with separate roundings for a * b + c, like numpy (and replay.hip): contraction is off in this file.
@@ -98,17 +107,20 @@ __device__ __forceinline__ double taper_angle_out(const double* t, const double*
 
 // One (frame, window) pair: the stack of frame f of the recording [seg, end) at (back, n - back - 1, M) -> 25 message values and, SPR,
 // the 21 of its spread record.  `fb` is the first row of frame `fbase` (fbase <= every frame the stack reaches), frames `fs` words
-// apart, a frame's samples W apart.  TAP: `u` holds the n row weights of the window's frames; otherwise every row weighs 1 / N and the
-// statements are sweep_pair's (post_sweep.hip).  (Inlined into both of its call sites: out of line, `body` -- which may point into the
-// kernel's parameters -- made every lane keep a private copy of PwParams, 560 bytes of scratch.)
-template <typename TMsg, bool SPR, bool TAP>
+// apart, a frame's samples W apart.  TAP: `u` holds the n row weights of the window's frames; otherwise every row weighs 1 / N.
+// CAUSAL: no window of the call looks ahead, so no frame index reaches `end` (which is then not read).  (Inlined into each of its
+// call sites: out of line, `body` -- which may point into the kernel's parameters -- made every lane keep a private copy of PwParams,
+// 560 bytes of scratch.)
+template <typename TMsg, bool SPR, bool TAP, bool CAUSAL>
 __device__ __forceinline__ void window_pair(const double* fb, int fbase, int fs, int W, int layout, int f, int seg, int end, int back, int n, int M,
                             const double* u, const double* body, TMsg* dst, int out_stride) {
     const int N = n * M;
     auto frame_rows = [&](int j) -> const double* {
         int h = f - back + j;
         if (h < seg) h = seg;
-        if (h > end - 1) h = end - 1;
+        if constexpr (!CAUSAL) {
+            if (h > end - 1) h = end - 1;
+        }
         return fb + (long long)(h - fbase) * fs;
     };
     const bool hips = layout != APE_LAYOUT_ORI_CAL_LARM_UARM;
@@ -215,7 +227,8 @@ __device__ __forceinline__ void window_pair(const double* fb, int fbase, int fs,
     }
 }
 
-template <typename TMsg, bool SPR, bool LDS>
+// SWEEP: the host's choice for a call in which no window looks ahead and none is tapered (A = 0, wts = nullptr): the kernel a sweep runs
+template <typename TMsg, bool SPR, bool LDS, bool SWEEP>
 __global__ __launch_bounds__(PW_BLOCK) void ape_post_window_kernel(const PwParams p) {
     extern __shared__ __attribute__((aligned(16))) double tile[];
     const int t0 = p.f_lo + (int)blockIdx.x * p.TF;
@@ -249,14 +262,14 @@ __global__ __launch_bounds__(PW_BLOCK) void ape_post_window_kernel(const PwParam
         const int ci = pr / nf, f = t0 + (pr - ci * nf);
         const int rec = find_rec(p.starts, p.R, f);
         const int seg = p.starts[rec];
-        const int end = rec + 1 < p.R ? p.starts[rec + 1] : p.F;
+        const int end = SWEEP ? 0 : (rec + 1 < p.R ? p.starts[rec + 1] : p.F);
         const double* body = p.bodies != nullptr ? p.bodies + 9 * (size_t)rec : p.body;
         TMsg* dst = static_cast<TMsg*>(p.out) + ((size_t)p.idx[ci] * (size_t)p.F + (size_t)f) * (size_t)p.out_stride;
         const int back = (int)p.back[ci], n = back + (int)p.ahead[ci] + 1;
-        if (p.tapered[ci])
-            window_pair<TMsg, SPR, true>(fb, fbase, fs, p.W, p.layout, f, seg, end, back, n, (int)p.m[ci], wt + ci * NW, body, dst, p.out_stride);
+        if (!SWEEP && p.tapered[ci])
+            window_pair<TMsg, SPR, true, false>(fb, fbase, fs, p.W, p.layout, f, seg, end, back, n, (int)p.m[ci], wt + ci * NW, body, dst, p.out_stride);
         else
-            window_pair<TMsg, SPR, false>(fb, fbase, fs, p.W, p.layout, f, seg, end, back, n, (int)p.m[ci], nullptr, body, dst, p.out_stride);
+            window_pair<TMsg, SPR, false, SWEEP>(fb, fbase, fs, p.W, p.layout, f, seg, end, back, n, (int)p.m[ci], nullptr, body, dst, p.out_stride);
     }
 }
 
@@ -269,7 +282,7 @@ struct Plan {
     int TF, lds, lds_fs, table_words;                   // frames per tile; staged in LDS; LDS words between frames; words of the weight table
 };
 
-int make_plan(int layout, int F, const int32_t* win, int C, bool any_tapered, long long bound, Plan* out) {
+int make_plan(const char* who, const char* sets, int layout, int F, const int32_t* win, int C, bool any_tapered, long long bound, Plan* out) {
     Plan q{};
     q.W = layout == APE_LAYOUT_ORI_CAL_LARM_UARM ? 14 : 21;
     for (int c = 0; c < C; ++c) {
@@ -278,8 +291,8 @@ int make_plan(int layout, int F, const int32_t* win, int C, bool any_tapered, lo
     q.frame_bytes = 8ll * q.W * q.Mx;
     const long long fit = bound / (2 * q.frame_bytes) - q.H - q.A;
     if (fit < 1)
-        return ape_fail(APE_ERR_INVALID_ARG, "post_window: workspace_bytes %lld holds no frame (at least %lld for these windows)", bound,
-                        2 * q.frame_bytes * (q.H + q.A + 1));
+        return ape_fail(APE_ERR_INVALID_ARG, "%s: workspace_bytes %lld holds no frame (at least %lld for these %s)", who, bound,
+                        2 * q.frame_bytes * (q.H + q.A + 1), sets);
     q.chunk = (int)std::min<long long>(fit, F);
     q.passes = (F + q.chunk - 1) / q.chunk;
     q.lds_fs = (q.Mx * q.W) | 1;
@@ -292,81 +305,50 @@ int make_plan(int layout, int F, const int32_t* win, int C, bool any_tapered, lo
     return APE_OK;
 }
 
+// The workspace of a device (post_common.h): one list and one mutex for every caller of post_filter.
 std::mutex g_mu;
-std::vector<PostWorkspace*> g_ws;                       // by device index (post_common.h)
-thread_local int g_last[4] = {0, 0, 0, 0};
+std::vector<PostWorkspace*> g_ws;                       // by device index
 
-template <typename TMsg, bool SPR>
+template <typename TMsg, bool SPR, bool SWEEP>
 hipError_t launch_window(const PwParams& p, unsigned blocks, size_t lds_bytes, hipStream_t st) {
     if (lds_bytes > 0) {
-        static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_post_window_kernel<TMsg, SPR, true>),
+        static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_post_window_kernel<TMsg, SPR, true, SWEEP>),
                                                      hipFuncAttributeMaxDynamicSharedMemorySize, APE_LDS_BYTES);
         if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL((ape_post_window_kernel<TMsg, SPR, true>), dim3(blocks), dim3(PW_BLOCK), lds_bytes, st, p);
+        hipLaunchKernelGGL((ape_post_window_kernel<TMsg, SPR, true, SWEEP>), dim3(blocks), dim3(PW_BLOCK), lds_bytes, st, p);
     } else {
-        hipLaunchKernelGGL((ape_post_window_kernel<TMsg, SPR, false>), dim3(blocks), dim3(PW_BLOCK), 0, st, p);
+        hipLaunchKernelGGL((ape_post_window_kernel<TMsg, SPR, false, SWEEP>), dim3(blocks), dim3(PW_BLOCK), 0, st, p);
     }
     return hipGetLastError();
 }
 
-}  // namespace
-
-int ape_post_window_last(int32_t out4[4]) {
-    if (!out4) return ape_fail(APE_ERR_INVALID_ARG, "post_window_last: NULL argument");
-    for (int i = 0; i < 4; ++i) out4[i] = g_last[i];
-    return APE_OK;
+template <bool SWEEP>
+hipError_t launch_window(bool spread, int out_dtype, const PwParams& p, unsigned blocks, size_t lds_bytes, hipStream_t st) {
+    if (spread) return out_dtype == APE_F32 ? launch_window<float, true, SWEEP>(p, blocks, lds_bytes, st) : launch_window<double, true, SWEEP>(p, blocks, lds_bytes, st);
+    return out_dtype == APE_F32 ? launch_window<float, false, SWEEP>(p, blocks, lds_bytes, st) : launch_window<double, false, SWEEP>(p, blocks, lds_bytes, st);
 }
 
-int ape_post_window(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc, const int32_t* seg_starts_host, int32_t R,
-                    const int32_t* windows_host, const double* weights_host, int32_t C, uint32_t flags, const double* bodies_host,
-                    int32_t n_bodies, void* out_dev, int32_t out_dtype, int64_t workspace_bytes, void* stream) {
-    // the arguments on their own first (no device needed to refuse them)
-    if (!y_dev || !out_dev || !seg_starts_host || !windows_host) return ape_fail(APE_ERR_INVALID_ARG, "post_window: NULL argument");
-    if (int rc = ape_check_segments("post_window", F, seg_starts_host, R)) return rc;
-    if (n_mc < 1) return ape_fail(APE_ERR_INVALID_ARG, "post_window: n_mc=%d must be >= 1", n_mc);
-    if ((long long)F * n_mc >= (1ll << 31)) return ape_fail(APE_ERR_UNSUPPORTED, "post_window: F*n_mc = %lld sample rows (< 2^31)", (long long)F * n_mc);
-    if (C < 1 || C > APE_POST_MAX_CONFIGS) return ape_fail(APE_ERR_INVALID_ARG, "post_window: C=%d windows (1 .. %d)", C, APE_POST_MAX_CONFIGS);
-    bool tapered[APE_POST_MAX_CONFIGS] = {};
-    bool any_tapered = false;
-    for (int c = 0; c < C; ++c) {
-        const int b = windows_host[3 * c], a = windows_host[3 * c + 1], k = windows_host[3 * c + 2];
-        if (b < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: back %d is negative", c, b);
-        if (a < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: ahead %d is negative", c, a);
-        const long long n = (long long)b + a + 1;
-        if (n > NW) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: back + ahead + 1 = %lld frames above %d", c, n, NW);
-        if (k < 1 || k > n_mc) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: %d samples outside 1..n_mc = %d", c, k, n_mc);
-        if (n * k > 4096) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: frames*samples = %lld above 4096", c, n * k);
-        if (weights_host != nullptr) {
-            const double* w = weights_host + (size_t)c * NW;
-            double sum = 0.0;
-            for (int j = 0; j < (int)n; ++j) {
-                if (!std::isfinite(w[j]) || w[j] < 0.0)
-                    return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: weight %d = %g is not a finite value >= 0", c, j, w[j]);
-                sum += w[j];
-                if (memcmp(&w[j], &w[0], sizeof(double)) != 0) tapered[c] = true;      // uniform: all n entries bit-equal
-            }
-            if (!(std::fabs(sum - 1.0) <= 1e-9))
-                return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: weights sum to %.17g, not to 1 within 1e-9 (the library does not normalise)", c, sum);
-            any_tapered = any_tapered || tapered[c];
-        }
-    }
-    if ((bodies_host == nullptr) != (n_bodies == 0) || (n_bodies != 0 && n_bodies != 1 && n_bodies != R))
-        return ape_fail(APE_ERR_INVALID_ARG, "post_window: n_bodies %d is neither 0 (NULL bodies), 1 nor R = %d", n_bodies, R);
-    if (flags & ~(uint32_t)APE_FLAG_SPREAD) return ape_fail(APE_ERR_INVALID_ARG, "post_window: only the SPREAD flag is accepted");
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "post_window: unknown dtype selector");
-    if (workspace_bytes < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_window: workspace_bytes %lld is negative (0 = default)", (long long)workspace_bytes);
+thread_local int g_last[4] = {0, 0, 0, 0};
+
+}  // namespace
+
+int ape_postcommon::post_filter(const char* who, const char* sets, ape_model_t* m, const float* y_dev, int F, int n_mc, const int32_t* seg_starts_host,
+                                int R, const int32_t* windows_host, const double* weights_host, const bool* tapered, int C, uint32_t flags,
+                                const double* bodies_host, int n_bodies, void* out_dev, int out_dtype, long long workspace_bytes, void* stream,
+                                int last4[4]) {
     if (!m) return ape_fail(ape_device_count() == 0 ? APE_ERR_NO_DEVICE : APE_ERR_INVALID_ARG,
-                            "post_window: NULL model (no gfx950 device: there is no CPU fallback)");
-    // ... then against the model
+                            "%s: NULL model (no gfx950 device: there is no CPU fallback)", who);
     const int layout = m->dims.target_layout;
-    if (layout == APE_LAYOUT_NONE) return ape_fail(APE_ERR_INVALID_ARG, "post_window: model has no target layout");
-    if (!m->has_stats) return ape_fail(APE_ERR_NOT_READY, "post_window: norm stats not set (y is normalised)");
+    if (layout == APE_LAYOUT_NONE) return ape_fail(APE_ERR_INVALID_ARG, "%s: model has no target layout", who);
+    if (!m->has_stats) return ape_fail(APE_ERR_NOT_READY, "%s: norm stats not set (y is normalised)", who);
+    bool any_tapered = false;
+    for (int c = 0; c < C && tapered != nullptr; ++c) any_tapered = any_tapered || tapered[c];
     Plan q;
-    if (int rc = make_plan(layout, F, windows_host, C, any_tapered, workspace_bytes > 0 ? (long long)workspace_bytes : PW_DEFAULT_BYTES, &q)) return rc;
+    if (int rc = make_plan(who, sets, layout, F, windows_host, C, any_tapered, workspace_bytes > 0 ? workspace_bytes : PW_DEFAULT_BYTES, &q)) return rc;
     hipError_t e = hipSetDevice(m->dims.device);
-    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "post_window: hipSetDevice failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: hipSetDevice failed: %s", who, hipGetErrorString(e));
     const hipStream_t st = (hipStream_t)stream;
-    if (int rc = ape_check_not_capturing(st, "post_window", "host arrays are staged per call")) return rc;
+    if (int rc = ape_check_not_capturing(st, who, "host arrays are staged per call")) return rc;
 
     const bool spread = (flags & APE_FLAG_SPREAD) != 0;
     const bool table = n_bodies > 1;                    // (n_bodies == R == 1: one body for all, by value)
@@ -386,15 +368,15 @@ int ape_post_window(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc,
     for (int c = 0; c < C; ++c) {
         const int o = order[(size_t)c];
         p.back[c] = (unsigned char)windows_host[3 * o]; p.ahead[c] = (unsigned char)windows_host[3 * o + 1];
-        p.m[c] = (short)windows_host[3 * o + 2]; p.idx[c] = (unsigned char)o; p.tapered[c] = tapered[o] ? 1 : 0;
-        if (tapered[o])
+        p.m[c] = (short)windows_host[3 * o + 2]; p.idx[c] = (unsigned char)o; p.tapered[c] = any_tapered && tapered[o] ? 1 : 0;
+        if (p.tapered[c])
             for (int j = 0; j <= (int)p.back[c] + (int)p.ahead[c]; ++j)
                 wts[(size_t)c * NW + j] = weights_host[(size_t)o * NW + j] / (double)p.m[c];
     }
 
     std::lock_guard<std::mutex> lock(g_mu);
     PostWorkspace* ws = nullptr;
-    if (int rc = take_post_workspace(g_ws, "post_window", m->dims.device, total, st, &ws)) return rc;
+    if (int rc = take_post_workspace(g_ws, who, m->dims.device, total, st, &ws)) return rc;
     double* est[2] = {static_cast<double*>(ws->dev), static_cast<double*>(ws->dev) + buf_words};
     double* bodies_d = reinterpret_cast<double*>(static_cast<char*>(ws->dev) + 2 * buf_words * sizeof(double));
     double* wts_d = reinterpret_cast<double*>(reinterpret_cast<char*>(bodies_d) + bodies_bytes);
@@ -418,6 +400,7 @@ int ape_post_window(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc,
     p.H = q.H; p.A = q.A; p.Mx = q.Mx; p.W = q.W; p.layout = layout; p.C = C; p.TF = q.TF; p.lds_fs = q.lds_fs;
     p.out_stride = 25 + (spread ? APE_SPREAD_WIDTH : 0);
     const size_t lds_bytes = q.lds ? ((size_t)(q.TF + q.H + q.A) * q.lds_fs + q.table_words) * sizeof(double) : 0;
+    const bool sweep = q.A == 0 && !any_tapered;        // every sweep: the instantiations without the upper clamp and the tapered form
 
     const size_t carry_words = (size_t)(q.H + q.A) * fw;
     int prev_frames = 0;
@@ -438,17 +421,62 @@ int ape_post_window(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc,
         }
         p.est = cur; p.f_lo = f_lo; p.f_hi = f_lo + frames;
         const unsigned blocks = (unsigned)((frames + q.TF - 1) / q.TF);
-        if (spread) e = out_dtype == APE_F32 ? launch_window<float, true>(p, blocks, lds_bytes, st) : launch_window<double, true>(p, blocks, lds_bytes, st);
-        else e = out_dtype == APE_F32 ? launch_window<float, false>(p, blocks, lds_bytes, st) : launch_window<double, false>(p, blocks, lds_bytes, st);
+        e = sweep ? launch_window<true>(spread, out_dtype, p, blocks, lds_bytes, st) : launch_window<false>(spread, out_dtype, p, blocks, lds_bytes, st);
         prev_frames = frames;
     }
     const hipError_t er = hipEventRecord(ws->done, st);    // the workspace is in flight whatever became of the launches
     ws->used = er == hipSuccess;
-    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "post_window: launch failed: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
     if (er != hipSuccess) {
         (void)hipStreamSynchronize(st);
-        return ape_fail(APE_ERR_HIP, "post_window: hipEventRecord failed: %s", hipGetErrorString(er));
+        return ape_fail(APE_ERR_HIP, "%s: hipEventRecord failed: %s", who, hipGetErrorString(er));
     }
-    g_last[0] = q.passes; g_last[1] = q.chunk; g_last[2] = q.TF; g_last[3] = q.lds;
+    last4[0] = q.passes; last4[1] = q.chunk; last4[2] = q.TF; last4[3] = q.lds;
     return APE_OK;
+}
+
+int ape_post_window_last(int32_t out4[4]) {
+    if (!out4) return ape_fail(APE_ERR_INVALID_ARG, "post_window_last: NULL argument");
+    for (int i = 0; i < 4; ++i) out4[i] = g_last[i];
+    return APE_OK;
+}
+
+int ape_post_window(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc, const int32_t* seg_starts_host, int32_t R,
+                    const int32_t* windows_host, const double* weights_host, int32_t C, uint32_t flags, const double* bodies_host,
+                    int32_t n_bodies, void* out_dev, int32_t out_dtype, int64_t workspace_bytes, void* stream) {
+    // the arguments on their own (no device needed to refuse them); post_filter checks them against the model
+    if (!y_dev || !out_dev || !seg_starts_host || !windows_host) return ape_fail(APE_ERR_INVALID_ARG, "post_window: NULL argument");
+    if (int rc = ape_check_segments("post_window", F, seg_starts_host, R)) return rc;
+    if (n_mc < 1) return ape_fail(APE_ERR_INVALID_ARG, "post_window: n_mc=%d must be >= 1", n_mc);
+    if ((long long)F * n_mc >= (1ll << 31)) return ape_fail(APE_ERR_UNSUPPORTED, "post_window: F*n_mc = %lld sample rows (< 2^31)", (long long)F * n_mc);
+    if (C < 1 || C > APE_POST_MAX_CONFIGS) return ape_fail(APE_ERR_INVALID_ARG, "post_window: C=%d windows (1 .. %d)", C, APE_POST_MAX_CONFIGS);
+    bool tapered[APE_POST_MAX_CONFIGS] = {};
+    for (int c = 0; c < C; ++c) {
+        const int b = windows_host[3 * c], a = windows_host[3 * c + 1], k = windows_host[3 * c + 2];
+        if (b < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: back %d is negative", c, b);
+        if (a < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: ahead %d is negative", c, a);
+        const long long n = (long long)b + a + 1;
+        if (n > NW) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: back + ahead + 1 = %lld frames above %d", c, n, NW);
+        if (k < 1 || k > n_mc) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: %d samples outside 1..n_mc = %d", c, k, n_mc);
+        if (n * k > 4096) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: frames*samples = %lld above 4096", c, n * k);
+        if (weights_host != nullptr) {
+            const double* w = weights_host + (size_t)c * NW;
+            double sum = 0.0;
+            for (int j = 0; j < (int)n; ++j) {
+                if (!std::isfinite(w[j]) || w[j] < 0.0)
+                    return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: weight %d = %g is not a finite value >= 0", c, j, w[j]);
+                sum += w[j];
+                if (memcmp(&w[j], &w[0], sizeof(double)) != 0) tapered[c] = true;      // uniform: all n entries bit-equal
+            }
+            if (!(std::fabs(sum - 1.0) <= 1e-9))
+                return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: weights sum to %.17g, not to 1 within 1e-9 (the library does not normalise)", c, sum);
+        }
+    }
+    if ((bodies_host == nullptr) != (n_bodies == 0) || (n_bodies != 0 && n_bodies != 1 && n_bodies != R))
+        return ape_fail(APE_ERR_INVALID_ARG, "post_window: n_bodies %d is neither 0 (NULL bodies), 1 nor R = %d", n_bodies, R);
+    if (flags & ~(uint32_t)APE_FLAG_SPREAD) return ape_fail(APE_ERR_INVALID_ARG, "post_window: only the SPREAD flag is accepted");
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "post_window: unknown dtype selector");
+    if (workspace_bytes < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_window: workspace_bytes %lld is negative (0 = default)", (long long)workspace_bytes);
+    return post_filter("post_window", "windows", m, y_dev, F, n_mc, seg_starts_host, R, windows_host, weights_host, tapered, C, flags, bodies_host,
+                       n_bodies, out_dev, out_dtype, workspace_bytes, stream, g_last);
 }

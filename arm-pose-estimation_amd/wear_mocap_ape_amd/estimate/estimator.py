@@ -801,15 +801,20 @@ class Estimator:
         ``out [C, F, 25]`` (``(out, spread [C, F, 21])`` with ``spread``), ``out[c]`` the first 25 columns an estimator with configuration
         ``c`` would have returned for the same recordings.  ``bonemaps``: one entry per recording (default: this estimator's body)."""
         from wear_mocap_ape_amd import score
+        return self._repost("repost", score.post_sweep, y, configs, starts, bonemaps, spread, out_dtype, workspace_bytes)
+
+    def _repost(self, who: str, post, y, sets, starts, bonemaps, spread, out_dtype, workspace_bytes):
+        """``repost`` and ``repost_windows``: their guard and the bodies of ``bonemaps``, then ``post`` (``score.post_sweep`` /
+        ``score.post_window``) with this estimator's model"""
         model = self._hip_model()
         if model is None or self._frame_samples() is None:
             raise UserWarning("this estimator has no HIP regressor")
         if not self._normalize:
-            raise UserWarning("repost de-normalises its targets: this estimator does not normalise")
+            raise UserWarning(f"{who} de-normalises its targets: this estimator does not normalise")
         if bonemaps is not None:
             R = len(np.asarray([0] if starts is None else starts).reshape(-1))
-            bonemaps = bodies_from(bonemaps, R, "repost bonemaps")
-        return score.post_sweep(model, y, configs, starts, bonemaps, spread, out_dtype, workspace_bytes)
+            bonemaps = bodies_from(bonemaps, R, f"{who} bonemaps")
+        return post(model, y, sets, starts, bonemaps, spread, out_dtype, workspace_bytes)
 
     def sweep_recording(self, rows, truth, smooths, samples, starts=None, lags=(0, 0), truth_kind="targets", bonemaps=None,
                         seed: int = 0x5EED, skip=None, big_endian: bool = False, motion: bool = False, times=None):
@@ -830,13 +835,21 @@ class Estimator:
         configs = score.grid(smooths, [effective_mc(model, int(m)) for m in samples])
         if not configs:
             raise UserWarning("sweep_recording: no configuration")
-        top = max(m for _, m in configs)
+        return self._sweep(self.repost, score.score_configs, configs, max(m for _, m in configs), rows, truth, starts, lags, truth_kind,
+                           bonemaps, seed, skip, big_endian, motion, times)
+
+    def _sweep(self, repost, score_sets, configs, top: int, rows, truth, starts, lags, truth_kind, bonemaps, seed, skip, big_endian, motion,
+               times):
+        """``sweep_recording`` and ``sweep_windows`` once their list is made: the replay at ``top`` samples, ``repost`` (``self.repost``
+        / ``self.repost_windows``) of ``configs`` with the spread records, the defaults of ``skip`` and the bodies, ``score_sets``
+        (``score.score_configs`` / ``score.score_windows``), and ``motion``"""
+        from wear_mocap_ape_amd import score
         _, y = self.process_recording(rows, starts=starts, big_endian=big_endian, return_targets=True, seed=seed, bonemaps=bonemaps,
                                       _config=(1, top))
-        out, rec = self.repost(y, configs, starts=starts, bonemaps=bonemaps, spread=True)
+        out, rec = repost(y, configs, starts=starts, bonemaps=bonemaps, spread=True)
         skip = self._sequence_len - 1 if skip is None else skip
         bodies = self._body_measurements if bonemaps is None else bonemaps
-        res = score.score_configs(self._layout, out, rec, truth, configs, lags, truth_kind, starts, skip, bodies)
+        res = score_sets(self._layout, out, rec, truth, configs, lags, truth_kind, starts, skip, bodies)
         if motion:
             res["motion"] = score.motion_sums(self._layout, out, "msg", starts, skip, times)[1].cpu().numpy()
         return res
@@ -848,15 +861,7 @@ class Estimator:
         ``spread``): frame ``f`` of ``out[c]`` is smoothed over the frames ``f - back .. f + ahead`` of its recording.  A uniform
         ``(smooth - 1, 0, samples)`` is ``repost``'s ``(smooth, samples)``, bit for bit.  ``bonemaps``: one entry per recording."""
         from wear_mocap_ape_amd import score
-        model = self._hip_model()
-        if model is None or self._frame_samples() is None:
-            raise UserWarning("this estimator has no HIP regressor")
-        if not self._normalize:
-            raise UserWarning("repost_windows de-normalises its targets: this estimator does not normalise")
-        if bonemaps is not None:
-            R = len(np.asarray([0] if starts is None else starts).reshape(-1))
-            bonemaps = bodies_from(bonemaps, R, "repost_windows bonemaps")
-        return score.post_window(model, y, windows, starts, bonemaps, spread, out_dtype, workspace_bytes)
+        return self._repost("repost_windows", score.post_window, y, windows, starts, bonemaps, spread, out_dtype, workspace_bytes)
 
     def sweep_windows(self, rows, truth, windows, starts=None, lags=(0, 0), truth_kind="targets", bonemaps=None, seed: int = 0x5EED,
                       skip=None, big_endian: bool = False, motion: bool = False, times=None):
@@ -872,16 +877,8 @@ class Estimator:
         if model is None or self._frame_samples() is None:
             raise UserWarning("this estimator has no HIP regressor or no batched feature builder")
         windows = [(b, a, effective_mc(model, int(m)), w) for b, a, m, w in score._windows(windows)[0]]
-        top = max(m for _, _, m, _ in windows)
-        _, y = self.process_recording(rows, starts=starts, big_endian=big_endian, return_targets=True, seed=seed, bonemaps=bonemaps,
-                                      _config=(1, top))
-        out, rec = self.repost_windows(y, windows, starts=starts, bonemaps=bonemaps, spread=True)
-        skip = self._sequence_len - 1 if skip is None else skip
-        bodies = self._body_measurements if bonemaps is None else bonemaps
-        res = score.score_windows(self._layout, out, rec, truth, windows, lags, truth_kind, starts, skip, bodies)
-        if motion:
-            res["motion"] = score.motion_sums(self._layout, out, "msg", starts, skip, times)[1].cpu().numpy()
-        return res
+        return self._sweep(self.repost_windows, score.score_windows, windows, max(m for _, _, m, _ in windows), rows, truth, starts, lags,
+                           truth_kind, bonemaps, seed, skip, big_endian, motion, times)
 
     # read-only views, same names as the reference's properties (estimator.py:188-218)
     sequence_len = property(lambda self: self._sequence_len)

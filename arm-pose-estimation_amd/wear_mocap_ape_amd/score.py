@@ -417,6 +417,13 @@ def post_sweep(model, y, configs, starts=None, bodies=None, spread: bool = False
     Returns ``out [C, F, 25]`` of ``out_dtype`` on the device -- ``out[c]`` is what ``process_recording`` of an estimator with
     configuration ``c`` returns in its first 25 columns, bit for bit where ``samples == M`` -- or, with ``spread``, ``(out, spread)``
     with ``spread [C, F, 21]``: two views of one tensor, as ``process_recording(spread=True)`` returns them.  Does not wait."""
+    return _post_call("post_sweep", lambda: (_configs(configs),), model, y, starts, bodies, spread, out_dtype, workspace_bytes)
+
+
+def _post_call(entry: str, lists_of, model, y, starts, bodies, spread, out_dtype, workspace_bytes):
+    """what ``post_sweep`` and ``post_window`` share: the checks of ``out_dtype`` and ``y``, ``starts``, the bodies rule, the allocation,
+    the call of ``ape_<entry>`` and the ``(out, spread)`` split.  ``lists_of()``: the arrays (or None) the entry takes between ``R`` and
+    ``C``, the first with one row per configuration"""
     from wear_mocap_ape_amd.data_types.bone_map import bodies_from
     if out_dtype not in (torch.float32, torch.float64):
         raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
@@ -424,46 +431,57 @@ def post_sweep(model, y, configs, starts=None, bodies=None, spread: bool = False
         raise UserWarning("y: a float32 device tensor [F >= 1, M, O] (process_recording(return_targets=True))")
     if y.shape[2] != model.output_size:
         raise UserWarning(f"y: {y.shape[2]} targets per row, the model has {model.output_size}")
-    cf = _configs(configs)
+    lists = lists_of()
     st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
-    F, M, R, C_ = int(y.shape[0]), int(y.shape[1]), int(st.shape[0]), int(cf.shape[0])
+    F, M, R, C_ = int(y.shape[0]), int(y.shape[1]), int(st.shape[0]), int(lists[0].shape[0])
     body = None
     if bodies is not None:
         body = np.ascontiguousarray(bodies.reshape(1, 9), dtype=np.float64) if isinstance(bodies, np.ndarray) and bodies.size == 9 \
-            else bodies_from(bodies, R, "post_sweep bodies")
+            else bodies_from(bodies, R, f"{entry} bodies")
     yd = y.contiguous()
     dev = yd.device
     with torch.cuda.device(dev):
         width = 25 + (_hip.SPREAD_WIDTH if spread else 0)
         out = torch.empty((C_, F, width), dtype=out_dtype, device=dev)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _hip.check(_hip.lib().ape_post_sweep(model.handle, C.c_void_p(yd.data_ptr()), F, M, C.c_void_p(st.ctypes.data), R,
-                                             C.c_void_p(cf.ctypes.data), C_, _hip.FLAG_SPREAD if spread else 0,
-                                             C.c_void_p(body.ctypes.data) if body is not None else None,
-                                             int(body.shape[0]) if body is not None else 0, C.c_void_p(out.data_ptr()), _f64(out_dtype),
-                                             int(workspace_bytes), stream), "ape_post_sweep")
+        _hip.check(getattr(_hip.lib(), "ape_" + entry)(model.handle, C.c_void_p(yd.data_ptr()), F, M, C.c_void_p(st.ctypes.data), R,
+                                                       *(C.c_void_p(a.ctypes.data) if a is not None else None for a in lists), C_,
+                                                       _hip.FLAG_SPREAD if spread else 0, C.c_void_p(body.ctypes.data) if body is not None else None,
+                                                       int(body.shape[0]) if body is not None else 0, C.c_void_p(out.data_ptr()), _f64(out_dtype),
+                                                       int(workspace_bytes), stream), "ape_" + entry)
     if spread:
         return out[:, :, :25], out[:, :, 25:]
     return out
 
 
+def _post_last(entry: str) -> dict:
+    """the four plan numbers ``ape_<entry>_last`` returns, named"""
+    v = (C.c_int32 * 4)()
+    _hip.check(getattr(_hip.lib(), f"ape_{entry}_last")(v), f"ape_{entry}_last")
+    return {"passes": int(v[0]), "chunk_frames": int(v[1]), "tile_frames": int(v[2]), "lds": bool(v[3])}
+
+
+def _post_plan(layout: int, F: int, back: int, ahead: int, samples: int, workspace_bytes: int) -> dict:
+    """the workspace rule of include/ape_hip.h: the buffers hold ``back + chunk + ahead`` frames of ``samples`` rows twice"""
+    frame_bytes = 8 * _hip.EST_WIDTH[layout] * samples
+    bound = int(workspace_bytes) if workspace_bytes else 128 << 20
+    chunk = min(int(F), bound // (2 * frame_bytes) - back - ahead)
+    if chunk < 1:
+        raise UserWarning(f"workspace_bytes {bound} holds no frame (at least {2 * frame_bytes * (back + ahead + 1)})")
+    return {"passes": -(-int(F) // chunk), "chunk_frames": chunk, "frame_bytes": frame_bytes}
+
+
 def post_sweep_last() -> dict:
     """the plan of this thread's last ``post_sweep`` (debug counter): passes over the workspace, frames per pass, frames per workgroup
     tile, and whether the tiles were staged in LDS"""
-    v = (C.c_int32 * 4)()
-    _hip.check(_hip.lib().ape_post_sweep_last(v), "ape_post_sweep_last")
-    return {"passes": int(v[0]), "chunk_frames": int(v[1]), "tile_frames": int(v[2]), "lds": bool(v[3])}
+    return _post_last("post_sweep")
 
 
 def post_sweep_plan(layout: int, F: int, configs, workspace_bytes: int = 0) -> dict:
     """the workspace rule of include/ape_hip.h on the host: frames per pass and passes of a ``post_sweep`` over ``F`` frames"""
     cf = _configs(configs)
-    H, frame_bytes = int(cf[:, 0].max()) - 1, 8 * _hip.EST_WIDTH[layout] * int(cf[:, 1].max())
-    bound = int(workspace_bytes) if workspace_bytes else 128 << 20
-    chunk = min(int(F), bound // (2 * frame_bytes) - H)
-    if chunk < 1:
-        raise UserWarning(f"workspace_bytes {bound} holds no frame (at least {2 * frame_bytes * (H + 1)})")
-    return {"passes": -(-int(F) // chunk), "chunk_frames": chunk, "frame_bytes": frame_bytes, "halo_frames": H}
+    H = int(cf[:, 0].max()) - 1
+    return dict(_post_plan(layout, F, H, 0, int(cf[:, 1].max()), workspace_bytes), halo_frames=H)
 
 
 def score_configs(layout: int, out, spread, truth, configs, lags=(0, 0), truth_kind: str = "targets", starts=None, skip: int = 0,
@@ -557,53 +575,20 @@ def post_window(model, y, windows, starts=None, bodies=None, spread: bool = Fals
     ``weights[j]``.  A uniform ``(smooth - 1, 0, samples)`` gives the bits of ``post_sweep``'s ``(smooth, samples)``.
     Returns ``out [C, F, 25]`` of ``out_dtype`` on the device or, with ``spread``, ``(out, spread)`` with ``spread [C, F, 21]``: two
     views of one tensor.  Does not wait."""
-    from wear_mocap_ape_amd.data_types.bone_map import bodies_from
-    if out_dtype not in (torch.float32, torch.float64):
-        raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
-    if not isinstance(y, torch.Tensor) or not y.is_cuda or y.dtype != torch.float32 or y.dim() != 3 or y.shape[0] < 1:
-        raise UserWarning("y: a float32 device tensor [F >= 1, M, O] (process_recording(return_targets=True))")
-    if y.shape[2] != model.output_size:
-        raise UserWarning(f"y: {y.shape[2]} targets per row, the model has {model.output_size}")
-    _, wn, table = _windows(windows)
-    st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
-    F, M, R, C_ = int(y.shape[0]), int(y.shape[1]), int(st.shape[0]), int(wn.shape[0])
-    body = None
-    if bodies is not None:
-        body = np.ascontiguousarray(bodies.reshape(1, 9), dtype=np.float64) if isinstance(bodies, np.ndarray) and bodies.size == 9 \
-            else bodies_from(bodies, R, "post_window bodies")
-    yd = y.contiguous()
-    dev = yd.device
-    with torch.cuda.device(dev):
-        width = 25 + (_hip.SPREAD_WIDTH if spread else 0)
-        out = torch.empty((C_, F, width), dtype=out_dtype, device=dev)
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-        _hip.check(_hip.lib().ape_post_window(model.handle, C.c_void_p(yd.data_ptr()), F, M, C.c_void_p(st.ctypes.data), R,
-                                              C.c_void_p(wn.ctypes.data), C.c_void_p(table.ctypes.data) if table is not None else None, C_,
-                                              _hip.FLAG_SPREAD if spread else 0, C.c_void_p(body.ctypes.data) if body is not None else None,
-                                              int(body.shape[0]) if body is not None else 0, C.c_void_p(out.data_ptr()), _f64(out_dtype),
-                                              int(workspace_bytes), stream), "ape_post_window")
-    if spread:
-        return out[:, :, :25], out[:, :, 25:]
-    return out
+    return _post_call("post_window", lambda: _windows(windows)[1:], model, y, starts, bodies, spread, out_dtype, workspace_bytes)
 
 
 def post_window_last() -> dict:
     """the plan of this thread's last ``post_window`` (debug counter): passes over the workspace, frames per pass, frames per workgroup
     tile, and whether the tiles were staged in LDS"""
-    v = (C.c_int32 * 4)()
-    _hip.check(_hip.lib().ape_post_window_last(v), "ape_post_window_last")
-    return {"passes": int(v[0]), "chunk_frames": int(v[1]), "tile_frames": int(v[2]), "lds": bool(v[3])}
+    return _post_last("post_window")
 
 
 def post_window_plan(layout: int, F: int, windows, workspace_bytes: int = 0) -> dict:
     """the workspace rule of include/ape_hip.h on the host: frames per pass and passes of a ``post_window`` over ``F`` frames"""
     _, wn, _ = _windows(windows)
-    H, A, frame_bytes = int(wn[:, 0].max()), int(wn[:, 1].max()), 8 * _hip.EST_WIDTH[layout] * int(wn[:, 2].max())
-    bound = int(workspace_bytes) if workspace_bytes else 128 << 20
-    chunk = min(int(F), bound // (2 * frame_bytes) - H - A)
-    if chunk < 1:
-        raise UserWarning(f"workspace_bytes {bound} holds no frame (at least {2 * frame_bytes * (H + A + 1)})")
-    return {"passes": -(-int(F) // chunk), "chunk_frames": chunk, "frame_bytes": frame_bytes, "back_frames": H, "ahead_frames": A}
+    H, A = int(wn[:, 0].max()), int(wn[:, 1].max())
+    return dict(_post_plan(layout, F, H, A, int(wn[:, 2].max()), workspace_bytes), back_frames=H, ahead_frames=A)
 
 
 def _targets_est(pred, body, layout: int) -> np.ndarray:

@@ -965,7 +965,8 @@ int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
  * handle serves as a DropoutLSTM one.  Not journaled: there is nothing for ape_model_recover to re-issue.  No floating-point atomics
  * and a fixed order of summation: the same inputs give the same bits.  The launches go on `stream` and the call does not wait for
  * them; the host arrays (seg_starts_host, configs_host, bodies_host) have been consumed when it returns.  (The workspace is kept per
- * device and grows on demand, which may wait for the device; a call on another stream is ordered behind the last user by an event.)
+ * device, shared with ape_post_window, and grows on demand, which may wait for the device; a call on another stream is ordered behind
+ * the last user of either entry by an event.)
  * Refused on the host before anything is written: NULL model / y_dev / out_dev / seg_starts_host / configs_host; F < 1, R < 1, bad
  * starts; F * n_mc >= 2^31; C < 1 or C > APE_POST_MAX_CONFIGS; smooth outside [1, 64], m outside [1, n_mc], smooth * m > 4096;
  * n_bodies not 0 / 1 / R (0 iff bodies_host is NULL); flags other than APE_FLAG_SPREAD; an unknown dtype; workspace_bytes < 0 or too
@@ -1027,7 +1028,7 @@ int ape_post_sweep_last(int32_t out4[4]);
  * The model handle supplies the target layout, yy_m / yy_s and the default body; no weights of the network are read.  Not journaled:
  * there is nothing for ape_model_recover to re-issue.  No floating-point atomics and a fixed order of summation: the same inputs give
  * the same bits.  The launches go on `stream` and the call does not wait for them; the host arrays (seg_starts_host, windows_host,
- * weights_host, bodies_host) have been consumed when it returns.  (The workspace is kept per device, apart from ape_post_sweep's, and
+ * weights_host, bodies_host) have been consumed when it returns.  (The workspace is kept per device, the one ape_post_sweep uses, and
  * grows on demand, which may wait for the device; a call on another stream is ordered behind the last user by an event.)
  * Refused on the host before anything is written: NULL model / y_dev / out_dev / seg_starts_host / windows_host; F < 1, R < 1, bad
  * starts; n_mc < 1; F * n_mc >= 2^31; C < 1 or C > APE_POST_MAX_CONFIGS; back < 0, ahead < 0, n > APE_POST_MAX_WINDOW, m outside

@@ -70,9 +70,10 @@ def test_header_declares_and_hip_binds_the_entry():
     mk = (REPO / "arm-pose-estimation_amd" / "csrc" / "Makefile").read_text()
     assert "post_sweep.hip" in mk.split("SRCS", 1)[1].split("\n", 1)[0]
     assert "post_sweep.hip" not in mk.split("HAZARD_SRCS :=", 1)[1].split("\n", 1)[0]
-    src = (REPO / "arm-pose-estimation_amd" / "csrc" / "post_sweep.hip").read_text()
-    assert "#pragma clang fp contract(off)" in src and "asm" not in src                       # contraction off, no inline assembly
-    assert "atomic" not in src.replace("No atomics", "") and "hipLaunchCooperativeKernel" not in src
+    for name in ("post_sweep.hip", "post_window.hip", "post_common.h"):                         # the front; the kernels it runs
+        src = (REPO / "arm-pose-estimation_amd" / "csrc" / name).read_text()
+        assert "#pragma clang fp contract(off)" in src and "asm" not in src, name              # contraction off, no inline assembly
+        assert "atomic" not in src.replace("No atomics", "") and "hipLaunchCooperativeKernel" not in src, name
 
 
 def test_refusals_are_made_on_the_host():
