@@ -1,9 +1,10 @@
-// The post-filter pass over a replay's stored targets, behind its two entries ape_post_sweep (post_sweep.hip) and
-// ape_post_window (post_window.hip): the driver both fronts call, the conversion of sample rows to est rows, done once
-// per call, and the per-device workspace the converted rows live in.
+// The post-filter pass over a replay's stored targets, behind its three entries ape_post_sweep (post_sweep.hip),
+// ape_post_window (post_window.hip) and ape_post_select (post_select.hip): the driver the fronts call, the
+// conversion of sample rows to est rows, done once per call, and the per-device workspace the converted rows live in.
 //
 // post_filter   the one plan and host driver, defined in post_window.hip beside the kernels.  A front checks its own arguments, states
 //               its configurations as windows (back, ahead, samples) and calls it under its own name.
+// post_window_args  the checks of a list of windows and of what goes with it, for the two fronts that take one.
 // post_fk_rows  the body of the conversion kernel: sample rows k < Mx of a run of frames -> est rows.  ape_fk3_kernel's
 //               decomposition (fk.hip: a row's three chains side by side, 32 rows per workgroup of two waves) and its statements, with
 //               the row index mapped: compact row r = frame r / Mx, sample r % Mx.  Launch with 128 threads and
@@ -123,11 +124,22 @@ __device__ __forceinline__ void post_fk_rows(const PostFkParams& p) {
 // The pass itself, for arguments the front has checked on their own: refuses what the model does not allow, plans, stages the host
 // arrays and launches.  `who` / `sets`: the front's name and its word for its list, for the error texts.  windows_host int32 [C, 3]
 // (back, ahead, samples); weights_host [C, APE_POST_MAX_WINDOW] frame weights or nullptr; tapered [C] (nullptr: none): which windows
-// take their row of the weights, every other one is uniform.  workspace_bytes 0: the default bound.  On success last4 receives the
-// plan: passes, frames per pass, frames per tile, staged in LDS.
+// take their row of the weights, every other one is uniform.  sel_dev nullptr: every frame at every window, out [C, F, ...].  sel_dev
+// uint8 [S, F] on the device: the windows are a ladder kept in the caller's order, frame f of set s runs window sel[s, f] alone, out
+// [S, F, ...], a value >= C gives a row of NaN; the plan counts S where it counts lanes and C where it sizes the weight table.
+// workspace_bytes 0: the default bound.  On success last4 receives the plan: passes, frames per pass, frames per tile, staged in LDS.
 int post_filter(const char* who, const char* sets, ape_model_t* m, const float* y_dev, int F, int n_mc, const int32_t* seg_starts_host, int R,
-                const int32_t* windows_host, const double* weights_host, const bool* tapered, int C, uint32_t flags, const double* bodies_host,
-                int n_bodies, void* out_dev, int out_dtype, long long workspace_bytes, void* stream, int last4[4]);
+                const int32_t* windows_host, const double* weights_host, const bool* tapered, int C, const unsigned char* sel_dev, int S,
+                uint32_t flags, const double* bodies_host, int n_bodies, void* out_dev, int out_dtype, long long workspace_bytes, void* stream,
+                int last4[4]);
+
+// What ape_post_window refuses on the arguments alone (no device needed), under the name `who`: the recordings, n_mc, the C windows
+// windows_host [C, 3] with weights_host [C, APE_POST_MAX_WINDOW] or nullptr, the bodies rule, flags, out_dtype, workspace_bytes.
+// tapered [APE_POST_MAX_CONFIGS], all false on entry, receives which windows take their row of the weights (not all of its entries
+// bit-equal).
+int post_window_args(const char* who, const void* y_dev, const void* out_dev, int F, int n_mc, const int32_t* seg_starts_host, int R,
+                     const int32_t* windows_host, const double* weights_host, int C, uint32_t flags, const double* bodies_host, int n_bodies,
+                     int out_dtype, long long workspace_bytes, bool* tapered);
 
 struct PostWorkspace {
     void* dev = nullptr;

@@ -49,6 +49,6 @@ int ape_post_sweep(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc, 
     if (flags & ~(uint32_t)APE_FLAG_SPREAD) return ape_fail(APE_ERR_INVALID_ARG, "post_sweep: only the SPREAD flag is accepted");
     if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "post_sweep: unknown dtype selector");
     if (workspace_bytes < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_sweep: workspace_bytes %lld is negative (0 = default)", (long long)workspace_bytes);
-    return ape_postcommon::post_filter("post_sweep", "configurations", m, y_dev, F, n_mc, seg_starts_host, R, windows, nullptr, nullptr, C, flags,
-                                       bodies_host, n_bodies, out_dev, out_dtype, workspace_bytes, stream, g_last);
+    return ape_postcommon::post_filter("post_sweep", "configurations", m, y_dev, F, n_mc, seg_starts_host, R, windows, nullptr, nullptr, C, nullptr, 0,
+                                       flags, bodies_host, n_bodies, out_dev, out_dtype, workspace_bytes, stream, g_last);
 }

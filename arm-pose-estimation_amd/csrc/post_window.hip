@@ -5,8 +5,9 @@
 // (estimator.py:108-118,122-137; compose_msg.py:13-108; transformations.py:32-51).
 //
 // This file holds the one implementation of the post-filter pass over stored targets: the kernels, the plan and the host driver
-// post_filter (declared in post_common.h).  ape_post_window below and ape_post_sweep (post_sweep.hip, DESIGN.md 4.33: configuration
-// (smooth, m) is the uniform window (smooth - 1, 0, m)) are fronts that check their arguments and call it.
+// post_filter (declared in post_common.h).  ape_post_window below, ape_post_sweep (post_sweep.hip, DESIGN.md 4.33: configuration
+// (smooth, m) is the uniform window (smooth - 1, 0, m)) and ape_post_select (post_select.hip, DESIGN.md 4.44: a window per frame from a
+// ladder) are fronts that check their arguments and call it.
 //
 // ape_post_window_fk_kernel  the work the windows share (post_common.h): sample rows k < Mx = max m_c -> est rows, once per call.
 // ape_post_window_kernel     all C reductions of a tile of frames.  A lane takes (frame, window) pairs, the
@@ -18,6 +19,11 @@
 //                            lanes of a wave mostly share a window, so a weight is read as a broadcast.  LDS = false (a tile with
 //                            its halos does not fit, or C is so small that a tile would leave lanes idle): rows and weights come from
 //                            the workspace in device memory.  Same statements and same bits either way.
+// ape_post_select_kernel     the selecting sibling (ape_post_select, post_select.hip): the windows are a ladder in the
+//                            caller's order, a lane takes (frame, set) pairs and looks its window up in sel [S, F]; the same tile, the
+//                            same pair function, so row (s, f) holds the bits the kernel above writes for window sel[s, f] at frame f.
+//                            A selector value >= C fills its own row with NaN.  Any frame may pick any rung: the halos are the ladder's
+//                            longest, and the lanes of a wave run stacks of whatever lengths the selector gives them.
 // The chunk: est rows of H carried-over frames, `chunk` frames and A frames ahead, two buffers used in turn: the last H + A frames of a
 // buffer are copied to the front of the other one, so a row is converted once per call.  Both sizes follow from the caller's byte bound.
 //
@@ -228,12 +234,16 @@ __device__ __forceinline__ void window_pair(const double* fb, int fbase, int fs,
 }
 
 // SWEEP: the host's choice for a call in which no window looks ahead and none is tapered (A = 0, wts = nullptr): the kernel a sweep runs
-template <typename TMsg, bool SPR, bool LDS, bool SWEEP>
-__global__ __launch_bounds__(PW_BLOCK) void ape_post_window_kernel(const PwParams p) {
-    extern __shared__ __attribute__((aligned(16))) double tile[];
-    const int t0 = p.f_lo + (int)blockIdx.x * p.TF;
-    const int t1 = t0 + p.TF < p.f_hi ? t0 + p.TF : p.f_hi;
-    const int nf = t1 - t0;
+// where the lanes of a workgroup find the rows of the tile [t0, t1) and the weight table
+struct TileRows {
+    const double* fb;                                   // the first row of frame fbase
+    const double* wt;
+    int fbase, fs;                                      // float64 words between frames
+};
+
+// LDS: copies the tile's rows with their halos and the weight table into `tile` and waits for the workgroup; otherwise the chunk itself
+template <bool LDS>
+__device__ __forceinline__ TileRows tile_rows(const PwParams& p, int t0, int t1, double* tile) {
     const int MW = p.Mx * p.W;
     const double* fb = p.est;
     const double* wt = p.wts;
@@ -257,6 +267,19 @@ __global__ __launch_bounds__(PW_BLOCK) void ape_post_window_kernel(const PwParam
         __syncthreads();
         fb = tile; fbase = t0 - p.H; fs = p.lds_fs;
     }
+    return TileRows{fb, wt, fbase, fs};
+}
+
+template <typename TMsg, bool SPR, bool LDS, bool SWEEP>
+__global__ __launch_bounds__(PW_BLOCK) void ape_post_window_kernel(const PwParams p) {
+    extern __shared__ __attribute__((aligned(16))) double tile[];
+    const int t0 = p.f_lo + (int)blockIdx.x * p.TF;
+    const int t1 = t0 + p.TF < p.f_hi ? t0 + p.TF : p.f_hi;
+    const int nf = t1 - t0;
+    const TileRows tr = tile_rows<LDS>(p, t0, t1, tile);
+    const double* fb = tr.fb;
+    const double* wt = tr.wt;
+    const int fbase = tr.fbase, fs = tr.fs;
     const int pairs = nf * p.C;
     for (int pr = threadIdx.x; pr < pairs; pr += PW_BLOCK) {
         const int ci = pr / nf, f = t0 + (pr - ci * nf);
@@ -273,6 +296,41 @@ __global__ __launch_bounds__(PW_BLOCK) void ape_post_window_kernel(const PwParam
     }
 }
 
+// The selecting form: p's windows are the ladder in the caller's order (p.idx is not read), sel [S, F] names the rung of every
+// (set, frame), out [S, F, out_stride].  Sets slowest, frames fastest: a wave's lanes read neighbouring frames and neighbouring selector
+// bytes.  The general form of the pair alone (two-sided clamp, tapered where the rung is): the bits ape_post_window_kernel writes.
+template <typename TMsg, bool SPR, bool LDS>
+__global__ __launch_bounds__(PW_BLOCK) void ape_post_select_kernel(const PwParams p, const unsigned char* sel, int S) {
+    extern __shared__ __attribute__((aligned(16))) double tile[];
+    const int t0 = p.f_lo + (int)blockIdx.x * p.TF;
+    const int t1 = t0 + p.TF < p.f_hi ? t0 + p.TF : p.f_hi;
+    const int nf = t1 - t0;
+    const TileRows tr = tile_rows<LDS>(p, t0, t1, tile);
+    const double* fb = tr.fb;
+    const double* wt = tr.wt;
+    const int fbase = tr.fbase, fs = tr.fs;
+    const int pairs = nf * S;
+    for (int pr = threadIdx.x; pr < pairs; pr += PW_BLOCK) {
+        const int s = pr / nf, f = t0 + (pr - s * nf);
+        const size_t at = (size_t)s * (size_t)p.F + (size_t)f;
+        TMsg* dst = static_cast<TMsg*>(p.out) + at * (size_t)p.out_stride;
+        const int ci = (int)sel[at];
+        if (ci >= p.C) {                                // no such rung: the row says so, nothing else is touched
+            for (int c = 0; c < p.out_stride; ++c) dst[c] = (TMsg)__builtin_nan("");
+            continue;
+        }
+        const int rec = find_rec(p.starts, p.R, f);
+        const int seg = p.starts[rec];
+        const int end = rec + 1 < p.R ? p.starts[rec + 1] : p.F;
+        const double* body = p.bodies != nullptr ? p.bodies + 9 * (size_t)rec : p.body;
+        const int back = (int)p.back[ci], n = back + (int)p.ahead[ci] + 1;
+        if (p.tapered[ci])
+            window_pair<TMsg, SPR, true, false>(fb, fbase, fs, p.W, p.layout, f, seg, end, back, n, (int)p.m[ci], wt + ci * NW, body, dst, p.out_stride);
+        else
+            window_pair<TMsg, SPR, false, false>(fb, fbase, fs, p.W, p.layout, f, seg, end, back, n, (int)p.m[ci], nullptr, body, dst, p.out_stride);
+    }
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------------
 // what follows from the arguments alone (include/ape_hip.h states the rule)
 struct Plan {
@@ -282,7 +340,8 @@ struct Plan {
     int TF, lds, lds_fs, table_words;                   // frames per tile; staged in LDS; LDS words between frames; words of the weight table
 };
 
-int make_plan(const char* who, const char* sets, int layout, int F, const int32_t* win, int C, bool any_tapered, long long bound, Plan* out) {
+// `lanes`: what a frame of a tile gives the workgroup's lanes to do -- the C windows, or the S sets of a selecting call
+int make_plan(const char* who, const char* sets, int layout, int F, const int32_t* win, int C, int lanes, bool any_tapered, long long bound, Plan* out) {
     Plan q{};
     q.W = layout == APE_LAYOUT_ORI_CAL_LARM_UARM ? 14 : 21;
     for (int c = 0; c < C; ++c) {
@@ -298,9 +357,9 @@ int make_plan(const char* who, const char* sets, int layout, int F, const int32_
     q.lds_fs = (q.Mx * q.W) | 1;
     q.table_words = any_tapered ? C * NW : 0;
     const int tf_fit = (PW_LDS_WORDS - q.table_words) / q.lds_fs - q.H - q.A;       // the tile is sized for the table beside it
-    q.lds = tf_fit >= 1 && (long long)tf_fit * C >= PW_BLOCK;
-    if (q.lds) q.TF = std::min(tf_fit, std::max((1024 + C - 1) / C, q.H + q.A + 1));   // enough pairs for every lane, halos no longer than the tile
-    else q.TF = std::max(1, PW_BLOCK / C);
+    q.lds = tf_fit >= 1 && (long long)tf_fit * lanes >= PW_BLOCK;
+    if (q.lds) q.TF = std::min(tf_fit, std::max((1024 + lanes - 1) / lanes, q.H + q.A + 1));   // enough pairs for every lane, halos no longer than the tile
+    else q.TF = std::max(1, PW_BLOCK / lanes);
     *out = q;
     return APE_OK;
 }
@@ -328,14 +387,32 @@ hipError_t launch_window(bool spread, int out_dtype, const PwParams& p, unsigned
     return out_dtype == APE_F32 ? launch_window<float, false, SWEEP>(p, blocks, lds_bytes, st) : launch_window<double, false, SWEEP>(p, blocks, lds_bytes, st);
 }
 
+template <typename TMsg, bool SPR>
+hipError_t launch_select(const PwParams& p, const unsigned char* sel, int S, unsigned blocks, size_t lds_bytes, hipStream_t st) {
+    if (lds_bytes > 0) {
+        static hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_post_select_kernel<TMsg, SPR, true>),
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, APE_LDS_BYTES);
+        if (attr != hipSuccess) return attr;
+        hipLaunchKernelGGL((ape_post_select_kernel<TMsg, SPR, true>), dim3(blocks), dim3(PW_BLOCK), lds_bytes, st, p, sel, S);
+    } else {
+        hipLaunchKernelGGL((ape_post_select_kernel<TMsg, SPR, false>), dim3(blocks), dim3(PW_BLOCK), 0, st, p, sel, S);
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_select(bool spread, int out_dtype, const PwParams& p, const unsigned char* sel, int S, unsigned blocks, size_t lds_bytes, hipStream_t st) {
+    if (spread) return out_dtype == APE_F32 ? launch_select<float, true>(p, sel, S, blocks, lds_bytes, st) : launch_select<double, true>(p, sel, S, blocks, lds_bytes, st);
+    return out_dtype == APE_F32 ? launch_select<float, false>(p, sel, S, blocks, lds_bytes, st) : launch_select<double, false>(p, sel, S, blocks, lds_bytes, st);
+}
+
 thread_local int g_last[4] = {0, 0, 0, 0};
 
 }  // namespace
 
 int ape_postcommon::post_filter(const char* who, const char* sets, ape_model_t* m, const float* y_dev, int F, int n_mc, const int32_t* seg_starts_host,
-                                int R, const int32_t* windows_host, const double* weights_host, const bool* tapered, int C, uint32_t flags,
-                                const double* bodies_host, int n_bodies, void* out_dev, int out_dtype, long long workspace_bytes, void* stream,
-                                int last4[4]) {
+                                int R, const int32_t* windows_host, const double* weights_host, const bool* tapered, int C,
+                                const unsigned char* sel_dev, int S, uint32_t flags, const double* bodies_host, int n_bodies, void* out_dev,
+                                int out_dtype, long long workspace_bytes, void* stream, int last4[4]) {
     if (!m) return ape_fail(ape_device_count() == 0 ? APE_ERR_NO_DEVICE : APE_ERR_INVALID_ARG,
                             "%s: NULL model (no gfx950 device: there is no CPU fallback)", who);
     const int layout = m->dims.target_layout;
@@ -344,7 +421,7 @@ int ape_postcommon::post_filter(const char* who, const char* sets, ape_model_t* 
     bool any_tapered = false;
     for (int c = 0; c < C && tapered != nullptr; ++c) any_tapered = any_tapered || tapered[c];
     Plan q;
-    if (int rc = make_plan(who, sets, layout, F, windows_host, C, any_tapered, workspace_bytes > 0 ? workspace_bytes : PW_DEFAULT_BYTES, &q)) return rc;
+    if (int rc = make_plan(who, sets, layout, F, windows_host, C, sel_dev != nullptr ? S : C, any_tapered, workspace_bytes > 0 ? workspace_bytes : PW_DEFAULT_BYTES, &q)) return rc;
     hipError_t e = hipSetDevice(m->dims.device);
     if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: hipSetDevice failed: %s", who, hipGetErrorString(e));
     const hipStream_t st = (hipStream_t)stream;
@@ -363,7 +440,8 @@ int ape_postcommon::post_filter(const char* who, const char* sets, ape_model_t* 
     std::vector<int> order((size_t)C);
     for (int c = 0; c < C; ++c) order[(size_t)c] = c;
     auto height = [&](int c) { return (windows_host[3 * c] + windows_host[3 * c + 1] + 1) * windows_host[3 * c + 2]; };
-    std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return height(a) > height(b); });
+    // (a ladder stays in the caller's order: the sort serves the grouping of lanes, which the selector decides there)
+    if (sel_dev == nullptr) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return height(a) > height(b); });
     std::vector<double> wts((size_t)q.table_words, 0.0);    // row weights u = w / m: one float64 division, here
     for (int c = 0; c < C; ++c) {
         const int o = order[(size_t)c];
@@ -421,7 +499,8 @@ int ape_postcommon::post_filter(const char* who, const char* sets, ape_model_t* 
         }
         p.est = cur; p.f_lo = f_lo; p.f_hi = f_lo + frames;
         const unsigned blocks = (unsigned)((frames + q.TF - 1) / q.TF);
-        e = sweep ? launch_window<true>(spread, out_dtype, p, blocks, lds_bytes, st) : launch_window<false>(spread, out_dtype, p, blocks, lds_bytes, st);
+        if (sel_dev != nullptr) e = launch_select(spread, out_dtype, p, sel_dev, S, blocks, lds_bytes, st);
+        else e = sweep ? launch_window<true>(spread, out_dtype, p, blocks, lds_bytes, st) : launch_window<false>(spread, out_dtype, p, blocks, lds_bytes, st);
         prev_frames = frames;
     }
     const hipError_t er = hipEventRecord(ws->done, st);    // the workspace is in flight whatever became of the launches
@@ -435,6 +514,43 @@ int ape_postcommon::post_filter(const char* who, const char* sets, ape_model_t* 
     return APE_OK;
 }
 
+int ape_postcommon::post_window_args(const char* who, const void* y_dev, const void* out_dev, int F, int n_mc, const int32_t* seg_starts_host,
+                                     int R, const int32_t* windows_host, const double* weights_host, int C, uint32_t flags,
+                                     const double* bodies_host, int n_bodies, int out_dtype, long long workspace_bytes, bool* tapered) {
+    if (!y_dev || !out_dev || !seg_starts_host || !windows_host) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (int rc = ape_check_segments(who, F, seg_starts_host, R)) return rc;
+    if (n_mc < 1) return ape_fail(APE_ERR_INVALID_ARG, "%s: n_mc=%d must be >= 1", who, n_mc);
+    if ((long long)F * n_mc >= (1ll << 31)) return ape_fail(APE_ERR_UNSUPPORTED, "%s: F*n_mc = %lld sample rows (< 2^31)", who, (long long)F * n_mc);
+    if (C < 1 || C > APE_POST_MAX_CONFIGS) return ape_fail(APE_ERR_INVALID_ARG, "%s: C=%d windows (1 .. %d)", who, C, APE_POST_MAX_CONFIGS);
+    for (int c = 0; c < C; ++c) {
+        const int b = windows_host[3 * c], a = windows_host[3 * c + 1], k = windows_host[3 * c + 2];
+        if (b < 0) return ape_fail(APE_ERR_INVALID_ARG, "%s: window %d: back %d is negative", who, c, b);
+        if (a < 0) return ape_fail(APE_ERR_INVALID_ARG, "%s: window %d: ahead %d is negative", who, c, a);
+        const long long n = (long long)b + a + 1;
+        if (n > NW) return ape_fail(APE_ERR_INVALID_ARG, "%s: window %d: back + ahead + 1 = %lld frames above %d", who, c, n, NW);
+        if (k < 1 || k > n_mc) return ape_fail(APE_ERR_INVALID_ARG, "%s: window %d: %d samples outside 1..n_mc = %d", who, c, k, n_mc);
+        if (n * k > 4096) return ape_fail(APE_ERR_INVALID_ARG, "%s: window %d: frames*samples = %lld above 4096", who, c, n * k);
+        if (weights_host != nullptr) {
+            const double* w = weights_host + (size_t)c * NW;
+            double sum = 0.0;
+            for (int j = 0; j < (int)n; ++j) {
+                if (!std::isfinite(w[j]) || w[j] < 0.0)
+                    return ape_fail(APE_ERR_INVALID_ARG, "%s: window %d: weight %d = %g is not a finite value >= 0", who, c, j, w[j]);
+                sum += w[j];
+                if (memcmp(&w[j], &w[0], sizeof(double)) != 0) tapered[c] = true;      // uniform: all n entries bit-equal
+            }
+            if (!(std::fabs(sum - 1.0) <= 1e-9))
+                return ape_fail(APE_ERR_INVALID_ARG, "%s: window %d: weights sum to %.17g, not to 1 within 1e-9 (the library does not normalise)", who, c, sum);
+        }
+    }
+    if ((bodies_host == nullptr) != (n_bodies == 0) || (n_bodies != 0 && n_bodies != 1 && n_bodies != R))
+        return ape_fail(APE_ERR_INVALID_ARG, "%s: n_bodies %d is neither 0 (NULL bodies), 1 nor R = %d", who, n_bodies, R);
+    if (flags & ~(uint32_t)APE_FLAG_SPREAD) return ape_fail(APE_ERR_INVALID_ARG, "%s: only the SPREAD flag is accepted", who);
+    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "%s: unknown dtype selector", who);
+    if (workspace_bytes < 0) return ape_fail(APE_ERR_INVALID_ARG, "%s: workspace_bytes %lld is negative (0 = default)", who, (long long)workspace_bytes);
+    return APE_OK;
+}
+
 int ape_post_window_last(int32_t out4[4]) {
     if (!out4) return ape_fail(APE_ERR_INVALID_ARG, "post_window_last: NULL argument");
     for (int i = 0; i < 4; ++i) out4[i] = g_last[i];
@@ -445,38 +561,9 @@ int ape_post_window(ape_model_t* m, const float* y_dev, int32_t F, int32_t n_mc,
                     const int32_t* windows_host, const double* weights_host, int32_t C, uint32_t flags, const double* bodies_host,
                     int32_t n_bodies, void* out_dev, int32_t out_dtype, int64_t workspace_bytes, void* stream) {
     // the arguments on their own (no device needed to refuse them); post_filter checks them against the model
-    if (!y_dev || !out_dev || !seg_starts_host || !windows_host) return ape_fail(APE_ERR_INVALID_ARG, "post_window: NULL argument");
-    if (int rc = ape_check_segments("post_window", F, seg_starts_host, R)) return rc;
-    if (n_mc < 1) return ape_fail(APE_ERR_INVALID_ARG, "post_window: n_mc=%d must be >= 1", n_mc);
-    if ((long long)F * n_mc >= (1ll << 31)) return ape_fail(APE_ERR_UNSUPPORTED, "post_window: F*n_mc = %lld sample rows (< 2^31)", (long long)F * n_mc);
-    if (C < 1 || C > APE_POST_MAX_CONFIGS) return ape_fail(APE_ERR_INVALID_ARG, "post_window: C=%d windows (1 .. %d)", C, APE_POST_MAX_CONFIGS);
     bool tapered[APE_POST_MAX_CONFIGS] = {};
-    for (int c = 0; c < C; ++c) {
-        const int b = windows_host[3 * c], a = windows_host[3 * c + 1], k = windows_host[3 * c + 2];
-        if (b < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: back %d is negative", c, b);
-        if (a < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: ahead %d is negative", c, a);
-        const long long n = (long long)b + a + 1;
-        if (n > NW) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: back + ahead + 1 = %lld frames above %d", c, n, NW);
-        if (k < 1 || k > n_mc) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: %d samples outside 1..n_mc = %d", c, k, n_mc);
-        if (n * k > 4096) return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: frames*samples = %lld above 4096", c, n * k);
-        if (weights_host != nullptr) {
-            const double* w = weights_host + (size_t)c * NW;
-            double sum = 0.0;
-            for (int j = 0; j < (int)n; ++j) {
-                if (!std::isfinite(w[j]) || w[j] < 0.0)
-                    return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: weight %d = %g is not a finite value >= 0", c, j, w[j]);
-                sum += w[j];
-                if (memcmp(&w[j], &w[0], sizeof(double)) != 0) tapered[c] = true;      // uniform: all n entries bit-equal
-            }
-            if (!(std::fabs(sum - 1.0) <= 1e-9))
-                return ape_fail(APE_ERR_INVALID_ARG, "post_window: window %d: weights sum to %.17g, not to 1 within 1e-9 (the library does not normalise)", c, sum);
-        }
-    }
-    if ((bodies_host == nullptr) != (n_bodies == 0) || (n_bodies != 0 && n_bodies != 1 && n_bodies != R))
-        return ape_fail(APE_ERR_INVALID_ARG, "post_window: n_bodies %d is neither 0 (NULL bodies), 1 nor R = %d", n_bodies, R);
-    if (flags & ~(uint32_t)APE_FLAG_SPREAD) return ape_fail(APE_ERR_INVALID_ARG, "post_window: only the SPREAD flag is accepted");
-    if (out_dtype != APE_F32 && out_dtype != APE_F64) return ape_fail(APE_ERR_INVALID_ARG, "post_window: unknown dtype selector");
-    if (workspace_bytes < 0) return ape_fail(APE_ERR_INVALID_ARG, "post_window: workspace_bytes %lld is negative (0 = default)", (long long)workspace_bytes);
-    return post_filter("post_window", "windows", m, y_dev, F, n_mc, seg_starts_host, R, windows_host, weights_host, tapered, C, flags, bodies_host,
-                       n_bodies, out_dev, out_dtype, workspace_bytes, stream, g_last);
+    if (int rc = post_window_args("post_window", y_dev, out_dev, F, n_mc, seg_starts_host, R, windows_host, weights_host, C, flags, bodies_host,
+                                  n_bodies, out_dtype, workspace_bytes, tapered)) return rc;
+    return post_filter("post_window", "windows", m, y_dev, F, n_mc, seg_starts_host, R, windows_host, weights_host, tapered, C, nullptr, 0, flags,
+                       bodies_host, n_bodies, out_dev, out_dtype, workspace_bytes, stream, g_last);
 }

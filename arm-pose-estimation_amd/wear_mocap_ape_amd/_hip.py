@@ -31,6 +31,7 @@ TRUTH_TARGETS, TRUTH_EST = 0, 1             # APE_TRUTH_*
 SCORE_MAX_LAG, SCORE_MAX_LAGS = 128, 65      # APE_SCORE_MAX_LAG, APE_SCORE_MAX_LAGS (ape_score_lags)
 POST_MAX_CONFIGS = 64             # APE_POST_MAX_CONFIGS (ape_post_sweep)
 POST_MAX_WINDOW = 64              # APE_POST_MAX_WINDOW (ape_post_window)
+SELECT_MAX_EDGES, SELECT_MAX_SLOPE = 256, 8    # APE_SELECT_MAX_EDGES, APE_SELECT_MAX_SLOPE (ape_select_rungs)
 FRAME_ACC_WIDTH = 51              # APE_FRAME_ACC_WIDTH (ape_frame_sums)
 BODY_ACC_WIDTH = 46               # APE_BODY_ACC_WIDTH (ape_body_sums)
 BODY_ROT_MSG, BODY_ROT_TRUTH = 0, 1         # APE_BODY_ROT_*
@@ -220,6 +221,14 @@ SIGNATURES["ape_post_sweep_last"] = (C.c_int, [C.POINTER(C.c_int32)])
 SIGNATURES["ape_post_window"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
                                            C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p])
 SIGNATURES["ape_post_window_last"] = (C.c_int, [C.POINTER(C.c_int32)])
+# a window per frame from a ladder.  The post-filter: ape_post_window's arguments with sel [S, F] (device) and S behind the
+# ladder's L; and the debug counter of the last call's plan.  The selector: keys + dtype, n_sets, set_stride (int64), F, frame_stride
+# (int64), starts_host, R, edges_host [B], B, rung_of_slot_host [B + 1], nan_rung, reach_host [L], L, slope, sel, HIP stream
+SIGNATURES["ape_post_select"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32,
+                                           C.c_void_p, C.c_int32, C.c_uint32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int64, C.c_void_p])
+SIGNATURES["ape_post_select_last"] = (C.c_int, [C.POINTER(C.c_int32)])
+SIGNATURES["ape_select_rungs"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                            C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p])
 # heading and frame offset against the truth.  The sums: layout, msg + stride, msg dtype, truth + kind + dtype, F,
 # starts_host, R, skip, bodies_host, n_bodies, lag_min, lag_max, rec_lag_host, acc, HIP stream.  The rotation: layout, msg + stride,
 # spread + stride, msg dtype, F, starts_host, R, quats_host, n_quats, out + dtype, HIP stream

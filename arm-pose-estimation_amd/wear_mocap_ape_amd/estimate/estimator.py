@@ -880,6 +880,83 @@ class Estimator:
         return self._sweep(self.repost_windows, score.score_windows, windows, max(m for _, _, m, _ in windows), rows, truth, starts, lags,
                            truth_kind, bonemaps, seed, skip, big_endian, motion, times)
 
+    # ---- speed-adaptive smoothing: a window per frame from a ladder (the reference has no counterpart) ----
+    def repost_selected(self, y, ladder, sel, starts=None, bonemaps=None, spread: bool = False, out_dtype=torch.float64,
+                        workspace_bytes: int = 0):
+        """``score.post_select`` with this estimator's model and body: ``y`` as for ``repost``, ``ladder`` as ``score.ladder`` returns it (or
+        a list of ``score.window`` entries), ``sel`` uint8 device ``[F]`` or ``[S, F]`` (``score.select_rungs``) -> ``out [(S,) F, 25]``
+        (``(out, spread [(S,) F, 21])`` with ``spread``): frame ``f`` of set ``s`` is ``repost_windows``' frame ``f`` of window
+        ``sel[s, f]``, bit for bit.  ``bonemaps``: one entry per recording."""
+        from wear_mocap_ape_amd import score
+        return self._repost("repost_selected", lambda model, y_, lad, *rest: score.post_select(model, y_, lad, sel, *rest), y, ladder, starts,
+                            bonemaps, spread, out_dtype, workspace_bytes)
+
+    def _adaptive_ladder(self, ladder):
+        """(windows at this model's effective sample counts, reach) of ``score.ladder``'s pair, a list of windows or None (the default
+        ladder at this estimator's sample count)"""
+        from wear_mocap_ape_amd import score
+        from wear_mocap_ape_amd.estimate.nn_models import effective_mc
+        model = self._hip_model()
+        if model is None or self._frame_samples() is None:
+            raise UserWarning("this estimator has no HIP regressor or no batched feature builder")
+        wins = score.ladder(samples=self._frame_samples())[0] if ladder is None else score._ladder_windows(ladder)
+        wins = [(b, a, effective_mc(model, int(m)), w) for b, a, m, w in score._windows(wins)[0]]
+        return wins, score._reach(wins)
+
+    def _rule_selector(self, pilot_rows, edges, slope, reach, starts, times):
+        """the selector of one rule: the hand speed of the pilot's rows (``score.motion_sums``, column 0; per frame, or per unit of
+        ``times``) binned over ``edges`` (None: ``score.speed_edges``, one edge per step of the ladder) with the envelope ``slope``"""
+        from wear_mocap_ape_amd import score
+        motion = score.motion_sums(self._layout, pilot_rows, "msg", starts, 0, times, per_frame=True)[0]
+        edges = score.speed_edges(count=max(1, len(reach) - 1)) if edges is None else edges
+        return score.select_rungs(motion[:, 0], edges, reach, slope, starts=starts)
+
+    def smooth_adaptive(self, rows, ladder=None, pilot: int = 3, edges=None, slope: int = 2, times=None, starts=None, bonemaps=None,
+                        seed: int = 0x5EED, big_endian: bool = False, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
+        """Offline smoothing whose window follows the hand speed: ONE ``process_recording(return_targets=True)`` at the ladder's largest
+        sample count, one ``score.post_window`` of rung ``pilot`` of the ladder, ``score.motion_sums(per_frame=True)`` of it for the
+        hand-speed column, ``score.select_rungs`` (``edges``, ``slope``: its arguments; the default edges are metres per frame, so give
+        edges with ``times``), then ``score.post_select``.  ``ladder``: ``score.ladder``'s pair (default: centred Hann windows of
+        half-widths ``score.LADDER_HALVES`` at this estimator's sample count).  Returns ``(out [F, 25], sel uint8 [F])`` on the device,
+        ``(out, sel, spread [F, 21])`` with ``spread``.  Does not wait."""
+        wins, reach = self._adaptive_ladder(ladder)
+        if not 0 <= int(pilot) < len(wins):
+            raise UserWarning(f"smooth_adaptive: pilot {pilot} is no rung of a ladder of {len(wins)}")
+        _, y = self.process_recording(rows, starts=starts, big_endian=big_endian, return_targets=True, seed=seed, bonemaps=bonemaps,
+                                      _config=(1, max(m for _, _, m, _ in wins)))
+        first = self.repost_windows(y, [wins[int(pilot)]], starts=starts, bonemaps=bonemaps, workspace_bytes=workspace_bytes)[0]
+        sel = self._rule_selector(first, edges, slope, reach, starts, times)
+        got = self.repost_selected(y, wins, sel, starts=starts, bonemaps=bonemaps, spread=spread, out_dtype=out_dtype,
+                                   workspace_bytes=workspace_bytes)
+        return (got[0], sel, got[1]) if spread else (got, sel)
+
+    def sweep_adaptive(self, rows, truth, ladder, rules, starts=None, lags=(0, 0), truth_kind="targets", bonemaps=None, seed: int = 0x5EED,
+                       skip=None, big_endian: bool = False, motion: bool = False, times=None):
+        """Does adapting beat the best fixed window on this recording: ONE replay, ``sweep_windows`` of the ladder's rungs, and one more
+        set per rule ``(pilot, edges, slope)`` of ``rules`` -- the selector ``smooth_adaptive`` makes from rung ``pilot`` (its rows are
+        the fixed sweep's), all rules in one ``score.post_select``.  Returns ``sweep_windows``' dict with ``"configs"`` holding the
+        ladder's windows and then the rules, ``"acc" [L + S, R, lags, 25]`` and ``"best"`` in that order (``"motion" [L + S, R, 38]``
+        with ``motion=True``), and ``"sel"``: the selectors, uint8 ``[S, F]`` on the host (waits for the device)."""
+        from wear_mocap_ape_amd import score
+        wins, reach = self._adaptive_ladder(ladder)
+        rules = [(int(p), None if e is None else np.asarray(e, dtype=np.float64), int(k)) for p, e, k in rules]
+        if not rules or len(rules) > 64 or any(not 0 <= p < len(wins) for p, _, _ in rules):
+            raise UserWarning(f"sweep_adaptive: between 1 and 64 rules (pilot, edges, slope) with pilot a rung of the ladder of {len(wins)}")
+        _, y = self.process_recording(rows, starts=starts, big_endian=big_endian, return_targets=True, seed=seed, bonemaps=bonemaps,
+                                      _config=(1, max(m for _, _, m, _ in wins)))
+        out, rec = self.repost_windows(y, wins, starts=starts, bonemaps=bonemaps, spread=True)
+        skip = self._sequence_len - 1 if skip is None else skip
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        res = score.score_windows(self._layout, out, rec, truth, wins, lags, truth_kind, starts, skip, bodies)
+        sel = torch.stack([self._rule_selector(out[p], e, k, reach, starts, times) for p, e, k in rules])
+        aout, arec = self.repost_selected(y, wins, sel, starts=starts, bonemaps=bonemaps, spread=True)
+        ada = score.score_selected(self._layout, aout, arec, truth, rules, lags, truth_kind, starts, skip, bodies)
+        res = {"configs": res["configs"] + ada["configs"], "acc": np.concatenate([res["acc"], ada["acc"]]), "best": res["best"] + ada["best"],
+               "sel": sel.cpu().numpy()}
+        if motion:
+            res["motion"] = np.concatenate([score.motion_sums(self._layout, o, "msg", starts, skip, times)[1].cpu().numpy() for o in (out, aout)])
+        return res
+
     # read-only views, same names as the reference's properties (estimator.py:188-218)
     sequence_len = property(lambda self: self._sequence_len)
     body_measurements = property(lambda self: self._body_measurements)

@@ -54,7 +54,12 @@ inputs give the same bits; ``merge_by``, ``pool_by`` and ``summarise_by`` work o
 Every smoothing route looks backwards and pays for it in lag.  A recording processed offline need not: ``post_window`` runs the
 post-filter from one replay's stored targets at windows that look ahead as far as they look back, with per-frame weights that taper
 (``ape_post_window``); ``window`` and ``window_weights`` make the configurations, ``score_windows`` scores every window
-over a sweep of lags, ``post_window_numpy`` is the host statement."""
+over a sweep of lags, ``post_window_numpy`` is the host statement.
+
+A window that is the same on every frame is a compromise for arm motion, which is holds joined by reaches.  ``select_rungs`` picks a rung
+of a ``ladder`` of windows for every frame from a per-frame key (the hand speed) under an envelope, and ``post_select`` runs the
+post-filter at the rung chosen (``ape_select_rungs``, ``ape_post_select``); ``select_rungs_numpy`` and
+``post_select_numpy`` are the host statements, ``score_selected`` scores the sets."""
 import ctypes as C
 import math
 
@@ -420,10 +425,11 @@ def post_sweep(model, y, configs, starts=None, bodies=None, spread: bool = False
     return _post_call("post_sweep", lambda: (_configs(configs),), model, y, starts, bodies, spread, out_dtype, workspace_bytes)
 
 
-def _post_call(entry: str, lists_of, model, y, starts, bodies, spread, out_dtype, workspace_bytes):
-    """what ``post_sweep`` and ``post_window`` share: the checks of ``out_dtype`` and ``y``, ``starts``, the bodies rule, the allocation,
-    the call of ``ape_<entry>`` and the ``(out, spread)`` split.  ``lists_of()``: the arrays (or None) the entry takes between ``R`` and
-    ``C``, the first with one row per configuration"""
+def _post_call(entry: str, lists_of, model, y, starts, bodies, spread, out_dtype, workspace_bytes, sel_of=None):
+    """what ``post_sweep``, ``post_window`` and ``post_select`` share: the checks of ``out_dtype`` and ``y``, ``starts``, the bodies rule,
+    the allocation, the call of ``ape_<entry>`` and the ``(out, spread)`` split.  ``lists_of()``: the arrays (or None) the entry takes
+    between ``R`` and ``C``, the first with one row per configuration; ``sel_of()``: the device selector ``[S, F]`` the entry takes
+    behind ``C`` (with ``S``), which then counts the sets of the result"""
     from wear_mocap_ape_amd.data_types.bone_map import bodies_from
     if out_dtype not in (torch.float32, torch.float64):
         raise UserWarning(f"out_dtype must be torch.float32 or torch.float64, got {out_dtype}")
@@ -432,6 +438,7 @@ def _post_call(entry: str, lists_of, model, y, starts, bodies, spread, out_dtype
     if y.shape[2] != model.output_size:
         raise UserWarning(f"y: {y.shape[2]} targets per row, the model has {model.output_size}")
     lists = lists_of()
+    sel = None if sel_of is None else sel_of()
     st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
     F, M, R, C_ = int(y.shape[0]), int(y.shape[1]), int(st.shape[0]), int(lists[0].shape[0])
     body = None
@@ -442,10 +449,11 @@ def _post_call(entry: str, lists_of, model, y, starts, bodies, spread, out_dtype
     dev = yd.device
     with torch.cuda.device(dev):
         width = 25 + (_hip.SPREAD_WIDTH if spread else 0)
-        out = torch.empty((C_, F, width), dtype=out_dtype, device=dev)
+        out = torch.empty((C_ if sel is None else int(sel.shape[0]), F, width), dtype=out_dtype, device=dev)
         stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
         _hip.check(getattr(_hip.lib(), "ape_" + entry)(model.handle, C.c_void_p(yd.data_ptr()), F, M, C.c_void_p(st.ctypes.data), R,
                                                        *(C.c_void_p(a.ctypes.data) if a is not None else None for a in lists), C_,
+                                                       *(() if sel is None else (C.c_void_p(sel.data_ptr()), int(sel.shape[0]))),
                                                        _hip.FLAG_SPREAD if spread else 0, C.c_void_p(body.ctypes.data) if body is not None else None,
                                                        int(body.shape[0]) if body is not None else 0, C.c_void_p(out.data_ptr()), _f64(out_dtype),
                                                        int(workspace_bytes), stream), "ape_" + entry)
@@ -739,6 +747,190 @@ def score_windows(layout: int, out, spread, truth, windows, lags=(0, 0), truth_k
     None) of a ``post_window`` result -> ``{"configs": [window(...) per window], "acc": ndarray [C, R, L, 25], "best":
     [best_lag(acc[c], lags, error) per window]}`` (waits for the device)."""
     return _score_sets("score_windows", _windows(windows)[0], layout, out, spread, truth, lags, truth_kind, starts, skip, bodies, error)
+
+
+# ---- speed-adaptive smoothing: a window per frame from a ladder (ape_select_rungs, ape_post_select, DESIGN.md 4.44) ------------------------
+# Arm motion is holds joined by reaches.  A hold wants a wide window, a reach a narrow one, and any fixed width is a compromise.  A ladder
+# is a list of windows from narrow to wide; ``select_rungs`` picks a rung for every frame from a per-frame key (the hand speed of a pilot
+# smoothing) with an envelope that keeps a wide window from covering a neighbouring reach, and ``post_select`` runs the post-filter at
+# the rung chosen.  ``select_rungs_numpy`` and ``post_select_numpy`` are the host statements.
+SELECT_MAX_EDGES, SELECT_MAX_SLOPE = _hip.SELECT_MAX_EDGES, _hip.SELECT_MAX_SLOPE
+LADDER_HALVES = (0, 1, 2, 3, 4, 6, 8, 12, 16, 24, 31)
+
+
+def ladder(halves=LADDER_HALVES, samples: int = 1, shape: str = "hann") -> tuple:
+    """``(windows, reach)`` of a ladder of centred windows: ``window(h, h, samples, shape)`` per half-width ``h`` of ``halves`` (the single
+    frame ``(0, 0, samples)`` for ``h = 0``) and int32 ``reach [L]``, each rung's ``max(back, ahead)``.  ``halves`` must not decrease:
+    a ladder runs narrow to wide."""
+    hs = [int(h) for h in halves]
+    if not hs or any(b < a for a, b in zip(hs, hs[1:])):
+        raise UserWarning(f"ladder: half-widths that do not decrease, got {hs}")
+    return [window(h, h, samples, shape if h > 0 else "uniform") for h in hs], np.asarray(hs, dtype=np.int32)
+
+
+def _reach(ladder_or_reach) -> np.ndarray:
+    """int32 ``[L]`` reaches of ``ladder``'s pair, of a list of windows, or of the reaches themselves; checked as the C ABI checks them"""
+    lr = ladder_or_reach
+    if isinstance(lr, tuple) and len(lr) == 2 and isinstance(lr[0], list):
+        lr = lr[1]
+    try:
+        if len(lr) and isinstance(lr[0], (tuple, list)):
+            lr = [max(int(w[0]), int(w[1])) for w in lr]
+        reach = np.ascontiguousarray(np.asarray(lr, dtype=np.int32).reshape(-1))
+    except (TypeError, ValueError):
+        raise UserWarning("ladder_or_reach: score.ladder's pair, a list of windows, or the reaches [L]")
+    if not 1 <= reach.shape[0] <= _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"ladder: between 1 and {_hip.POST_MAX_CONFIGS} rungs, got {reach.shape[0]}")
+    if (reach < 0).any() or (reach >= POST_MAX_WINDOW).any() or (np.diff(reach) < 0).any():
+        raise UserWarning(f"ladder: reaches 0 .. {POST_MAX_WINDOW - 1} that do not decrease (narrow to wide), got {reach.tolist()}")
+    return reach
+
+
+def speed_edges(first: float = 0.003, ratio: float = 1.3, count: int = 10) -> np.ndarray:
+    """a geometric ladder of ``count`` speed edges, ``first * ratio ** i``: with ``select_rungs``' default table a key up to ``first``
+    takes the widest rung and every further edge below it one rung narrower"""
+    if not (first > 0 and ratio > 1 and 1 <= int(count) <= SELECT_MAX_EDGES):
+        raise UserWarning(f"speed_edges: first > 0, ratio > 1 and 1 .. {SELECT_MAX_EDGES} edges")
+    return float(first) * float(ratio) ** np.arange(int(count), dtype=np.float64)
+
+
+def _select_tables(edges, reach, slope, rung_of_slot, nan_rung):
+    """the host arrays of ``ape_select_rungs`` with the defaults filled in: slot 0 -> the widest rung, each further slot one rung
+    narrower, clamped at rung 0; a key that is not finite -> the widest rung (the frame then takes its cap from its neighbours)"""
+    e = np.ascontiguousarray(np.asarray(edges, dtype=np.float64).reshape(-1))
+    L, B = int(reach.shape[0]), int(e.shape[0])
+    if not 1 <= B <= SELECT_MAX_EDGES or not np.isfinite(e).all() or (np.diff(e) <= 0).any():
+        raise UserWarning(f"edges: between 1 and {SELECT_MAX_EDGES} finite, strictly increasing values")
+    ros = np.maximum(L - 1 - np.arange(B + 1), 0) if rung_of_slot is None else np.asarray(rung_of_slot).reshape(-1)
+    ros = np.ascontiguousarray(ros, dtype=np.int32)
+    nan_rung = L - 1 if nan_rung is None else int(nan_rung)
+    if ros.shape[0] != B + 1 or (ros < 0).any() or (ros >= L).any() or not 0 <= nan_rung < L:
+        raise UserWarning(f"rung_of_slot: {B + 1} rungs 0 .. {L - 1} (and nan_rung one of them)")
+    if not 0 <= int(slope) <= SELECT_MAX_SLOPE:
+        raise UserWarning(f"slope: 0 .. {SELECT_MAX_SLOPE}, got {slope}")
+    return e, ros, nan_rung, int(slope)
+
+
+def select_rungs_numpy(keys, edges, rung_of_slot, reach, slope: int, starts=None, nan_rung=None) -> np.ndarray:
+    """The host statement of ``select_rungs``: ``keys [(S,) F]`` -> uint8 ``[(S,) F]``.  ``slot`` = the number of edges strictly below the
+    key (right-closed bins), ``r0 = rung_of_slot[slot]``, ``nan_rung`` for a key that is not finite.  ``slope == 0``: ``r0``.  Otherwise,
+    per recording, ``cap[f] = min_g reach[r0[g]] + |f - g| // slope`` and ``sel[f] = min(r0[f], the largest r with reach[r] <= cap[f])``."""
+    k = np.asarray(keys)
+    reach = _reach(reach)
+    e, ros, nan_rung, slope = _select_tables(edges, reach, slope, rung_of_slot, nan_rung)
+    k2 = k.reshape(-1, k.shape[-1]).astype(np.float64)
+    F = k2.shape[1]
+    st = [int(s) for s in ([0] if starts is None else starts)]
+    r0 = np.where(np.isfinite(k2), ros[np.searchsorted(e, np.where(np.isfinite(k2), k2, 0.0), side="left")], nan_rung).astype(np.int64)
+    sel = r0.copy()
+    if slope > 0:
+        for a, b in zip(st, st[1:] + [F]):
+            idx = np.arange(a, b)
+            dist = np.abs(idx[:, None] - idx[None, :]) // slope                               # [f, g]
+            for s in range(k2.shape[0]):
+                cap = (reach[r0[s, a:b]].astype(np.int64)[None, :] + dist).min(axis=1)
+                widest = np.searchsorted(reach, cap, side="right") - 1                        # the largest r with reach[r] <= cap
+                sel[s, a:b] = np.minimum(r0[s, a:b], widest)
+    return sel.astype(np.uint8).reshape(k.shape)
+
+
+def select_rungs(keys, edges, ladder_or_reach, slope: int = 2, rung_of_slot=None, starts=None, nan_rung=None):
+    """A rung of a ladder for every frame, on the device (``ape_select_rungs``).  ``keys``: a device ``[F]`` or ``[S, F]`` view, float32 or
+    float64, ``S <= 64`` -- a column of ``motion_sums``' per-frame rows (``motion[..., 0]``, the hand speed) goes in without a copy;
+    ``edges``: float64 ``[B]``, strictly increasing (``speed_edges``); ``ladder_or_reach``: ``ladder``'s pair, a list of windows or the
+    reaches themselves, narrow to wide; ``slope``: the envelope -- a frame's reach may exceed the reach chosen at frame ``g`` by at most
+    ``|f - g| // slope`` (0: no envelope, the binning alone); ``rung_of_slot``: int ``[B + 1]``, the rung of every bin ``(e[i - 1], e[i]]``
+    (default: slot 0 the widest rung, each further slot one rung narrower, clamped at rung 0); ``nan_rung``: the rung of a key that is
+    not finite (default: the widest, so that such a frame takes its cap from its neighbours); ``starts``: the recordings' first frames
+    -- nothing is read across a boundary.  Returns uint8 ``[(S,) F]`` on the device for ``post_select``.  Integer work: the same inputs
+    give the same bits.  Does not wait."""
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dim() not in (1, 2) or min(keys.shape) < 1:
+        raise UserWarning("keys: a device tensor [F] or [S, F]")
+    if keys.dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"keys: float32 or float64, got {keys.dtype}")
+    reach = _reach(ladder_or_reach)
+    e, ros, nan_rung, slope = _select_tables(edges, reach, slope, rung_of_slot, nan_rung)
+    k = keys[None] if keys.dim() == 1 else keys
+    S, F = int(k.shape[0]), int(k.shape[1])
+    if S > _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"keys: at most {_hip.POST_MAX_CONFIGS} sets, got {S}")
+    ss, fs = int(k.stride(0)), int(k.stride(1))
+    fs = fs if F > 1 else max(fs, 1)
+    if fs < 1 or (S > 1 and ss <= (F - 1) * fs):
+        k = k.contiguous()
+        ss, fs = int(k.stride(0)), max(int(k.stride(1)), 1)
+    st = _recording_starts(starts)
+    dev = k.device
+    with torch.cuda.device(dev):
+        sel = torch.empty((S, F), dtype=torch.uint8, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_select_rungs(C.c_void_p(k.data_ptr()), _f64(k.dtype), S, ss if S > 1 else 0, F, fs, C.c_void_p(st.ctypes.data),
+                                               int(st.shape[0]), C.c_void_p(e.ctypes.data), int(e.shape[0]), C.c_void_p(ros.ctypes.data), nan_rung,
+                                               C.c_void_p(reach.ctypes.data), int(reach.shape[0]), slope, C.c_void_p(sel.data_ptr()), stream),
+                   "ape_select_rungs")
+    return sel[0] if keys.dim() == 1 else sel
+
+
+def _ladder_windows(ladder_):
+    """the windows of ``ladder``'s pair or of a plain list of windows"""
+    return ladder_[0] if isinstance(ladder_, tuple) and len(ladder_) == 2 and isinstance(ladder_[0], list) else ladder_
+
+
+def _selector(sel, F: int):
+    """(uint8 device tensor [S, F] contiguous, whether ``sel`` came as ``[F]``)"""
+    if not isinstance(sel, torch.Tensor) or not sel.is_cuda or sel.dtype != torch.uint8 or sel.dim() not in (1, 2) or sel.shape[-1] != F:
+        raise UserWarning(f"sel: a uint8 device tensor [F] or [S, F] with F = {F} (select_rungs)")
+    s2 = (sel[None] if sel.dim() == 1 else sel).contiguous()
+    if not 1 <= s2.shape[0] <= _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"sel: between 1 and {_hip.POST_MAX_CONFIGS} selector rows, got {s2.shape[0]}")
+    return s2, sel.dim() == 1
+
+
+def post_select(model, y, ladder, sel, starts=None, bodies=None, spread: bool = False, out_dtype=torch.float64, workspace_bytes: int = 0):
+    """``post_window`` with a window per frame (``ape_post_select``).  ``model``, ``y``, ``starts``, ``bodies``, ``workspace_bytes``:
+    ``post_window``'s; ``ladder``: ``ladder()``'s pair or a list of ``window`` entries (``post_window``'s list and limits); ``sel``: uint8
+    device ``[F]`` or ``[S, F]``, the rung of every frame (``select_rungs``), ``S <= 64`` sets.  Row ``(s, f)`` of the result holds the
+    bits ``post_window(ladder)[sel[s, f], f]`` holds; a selector value ``>= len(ladder)`` gives a row of NaN and touches nothing else.
+    Returns ``out [(S,) F, 25]`` of ``out_dtype`` on the device or, with ``spread``, ``(out, spread [(S,) F, 21])``: two views of one
+    tensor.  Does not wait."""
+    F = int(y.shape[0]) if isinstance(y, torch.Tensor) and y.dim() == 3 else -1
+    got = _post_call("post_select", lambda: _windows(_ladder_windows(ladder))[1:], model, y, starts, bodies, spread, out_dtype, workspace_bytes,
+                     sel_of=lambda: _selector(sel, F)[0])
+    if isinstance(sel, torch.Tensor) and sel.dim() == 1:
+        return (got[0][0], got[1][0]) if spread else got[0]
+    return got
+
+
+def post_select_last() -> dict:
+    """the plan of this thread's last ``post_select`` (debug counter), as ``post_window_last``"""
+    return _post_last("post_select")
+
+
+def post_select_plan(layout: int, F: int, ladder, workspace_bytes: int = 0) -> dict:
+    """the workspace rule of include/ape_hip.h on the host: ``post_window_plan`` of the ladder (the halos are its longest reaches)"""
+    return post_window_plan(layout, F, _ladder_windows(ladder), workspace_bytes)
+
+
+def post_select_numpy(y, yy_m, yy_s, bodies, layout: int, starts, ladder, sel):
+    """The host statement of ``post_select``: ``post_window_numpy`` of the ladder, then row ``(s, f)`` is that of window ``sel[s, f]`` at
+    frame ``f`` and all NaN where ``sel[s, f] >= len(ladder)``.  ``sel``: integer ``[(S,) F]``; returns ``(out [(S,) F, 25], spread
+    [(S,) F, 21])`` float64."""
+    out, spread = post_window_numpy(y, yy_m, yy_s, bodies, layout, starts, _ladder_windows(ladder))
+    s = np.asarray(sel).astype(np.int64)
+    L, F = out.shape[0], out.shape[1]
+    if s.ndim not in (1, 2) or s.shape[-1] != F:
+        raise UserWarning(f"sel: [F] or [S, F] with F = {F}")
+    ok = (s >= 0) & (s < L)
+    pick = np.where(ok, s, 0)
+    frames = np.broadcast_to(np.arange(F), s.shape)
+    return (np.where(ok[..., None], out[pick, frames], np.nan), np.where(ok[..., None], spread[pick, frames], np.nan))
+
+
+def score_selected(layout: int, out, spread, truth, names, lags=(0, 0), truth_kind: str = "targets", starts=None, skip: int = 0,
+                   bodies=None, error: str = "hand_pos") -> dict:
+    """``score_windows`` for the ``S`` sets ``out[s]`` (and ``spread[s]``; ``spread`` may be None) of a ``post_select`` result; ``names``:
+    what to list under ``"configs"``, one entry per set (the rules that made the selectors)."""
+    return _score_sets("score_selected", list(names), layout, out, spread, truth, lags, truth_kind, starts, skip, bodies, error)
 
 
 # ---- each recording's heading and frame offset against the truth (ape_frame_sums, ape_rotate_rows, DESIGN.md 4.34) -------------------------

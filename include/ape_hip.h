@@ -1048,6 +1048,67 @@ int ape_post_window(ape_model_t* model, const float* y_dev, int32_t F, int32_t n
                     int64_t workspace_bytes, void* stream);
 int ape_post_window_last(int32_t out4[4]);   /* passes, frames per pass, frames per tile, staged in LDS */
 
+/* ---- speed-adaptive offline smoothing: a window per frame from a ladder (additive in ABI 7) -----------------------------
+ * replaces: nothing; the reference smooths every frame over the same number of past frames (estimate/estimator.py:112-118).  Arm motion
+ * is holds joined by reaches: a hold wants a wide window (noise averages away), a reach a narrow one (a wide one rounds the corner), and
+ * any fixed width is a compromise.  Two device steps: ape_select_rungs chooses a rung of a ladder of windows for every frame from a
+ * per-frame key (the hand speed), ape_post_select runs the post-filter at the rung chosen.
+ *
+ * ape_post_select: ape_post_window with a window per frame.
+ *   y_dev, F, n_mc, seg_starts_host / R, flags, bodies_host / n_bodies, out_dtype, workspace_bytes, stream: those of ape_post_window.
+ *   windows_host int32 [L, 3], weights_host f64 [L, APE_POST_MAX_WINDOW] or NULL: the ladder -- ape_post_window's list of windows under
+ *          ape_post_window's limits and refusals, 1 <= L <= APE_POST_MAX_CONFIGS, kept in the caller's order.
+ *   sel_dev uint8 [S, F] on the device, 1 <= S <= APE_POST_MAX_CONFIGS: sel[s, f] is the rung of frame f in set s.
+ *   out_dev [S, F, 25] of out_dtype, with APE_FLAG_SPREAD [S, F, 25 + APE_SPREAD_WIDTH].  Row (s, f) holds the bits ape_post_window
+ *          writes for window sel[s, f] of the same ladder at frame f, message and record.  A selector value >= L gives a row of NaN
+ *          for that (s, f) and touches nothing else: the selector lives on the device and the call does not wait, so a bad value is
+ *          not refused, it stays in its own row.
+ *   The workspace rule is ape_post_window's with H, A and Mx the ladder's maxima (any frame may pick any rung); the result does not
+ *          depend on the bound.  A tile is staged in LDS where it gives the lanes enough (frame, set) pairs: S counts where
+ *          ape_post_window's C counts lanes, L where it sizes the weight table.
+ * Not journaled; does not wait; the host arrays have been consumed when it returns; the workspace is the one ape_post_sweep and
+ * ape_post_window use.  Refused on the host: everything ape_post_window refuses (under this entry's name); NULL sel_dev; S < 1 or
+ * S > APE_POST_MAX_CONFIGS.
+ * ape_post_select_last: debug counter -- the plan of this thread's last successful ape_post_select, as ape_post_window_last.
+ *
+ * ape_select_rungs: the selector, on the device, from device arrays alone (no model).
+ *   keys_dev [S sets of F values] of keys_dtype (APE_F32 / APE_F64): key (s, f) is element s * set_stride + f * frame_stride, so a
+ *          column of ape_motion_sums' per-frame rows [S, F, 12] goes in as it is (frame_stride 12, set_stride 12 F).
+ *   edges_host f64 [B], finite and strictly increasing, 1 <= B <= APE_SELECT_MAX_EDGES; rung_of_slot_host int32 [B + 1], nan_rung:
+ *          rungs, 0 .. L - 1.  reach_host int32 [L], 1 <= L <= APE_POST_MAX_CONFIGS: max(back, ahead) of every rung, 0 ..
+ *          APE_POST_MAX_WINDOW - 1, non-decreasing -- the ladder runs narrow to wide.  slope k, 0 .. APE_SELECT_MAX_SLOPE.
+ *   Rule.  slot = the number of edges strictly below the key (right-closed bins, ape_score_hist's rule); r0[f] = rung_of_slot[slot],
+ *          or nan_rung for a key that is not finite.  k == 0: sel = r0.  Otherwise, with [s, e) the recording of f,
+ *          cap[f] = min over g in [s, e) of reach[r0[g]] + |f - g| / k (integer division) and
+ *          sel[f] = min(r0[f], the largest r with reach[r] <= cap[f]): a frame's reach does not exceed the reach chosen at g by more
+ *          than |f - g| / k.  Nothing is read across a recording boundary.  Only frames within k (reach[L - 1] - reach[0]) <= 504
+ *          frames of f can lower its cap; a workgroup stages the reaches of its 256 frames and that halo in LDS and every lane takes
+ *          the minimum over its neighbourhood.  All integer: the same inputs give the same bits.
+ *   sel_dev uint8 [S, F].
+ * The launch goes on `stream` and the call does not wait; the host arrays have been consumed when it returns.
+ * Refused on the host: a NULL pointer; an unknown dtype; F < 1, R < 1, bad starts; S or L outside 1 .. APE_POST_MAX_CONFIGS; B < 1 or
+ * B > APE_SELECT_MAX_EDGES; slope outside 0 .. APE_SELECT_MAX_SLOPE; an edge that is not finite or not above the one before; a reach
+ * outside 0 .. APE_POST_MAX_WINDOW - 1 or below the one before; a rung_of_slot entry or nan_rung outside 0 .. L - 1; frame_stride < 1,
+ * a set_stride that does not clear a set; keys_dev not aligned to its element; sel_dev overlapping the keys; a capturing stream. */
+#define APE_SELECT_MAX_EDGES 256
+#define APE_SELECT_MAX_SLOPE 8
+int ape_post_select(ape_model_t* model, const float* y_dev, int32_t F, int32_t n_mc,
+                    const int32_t* seg_starts_host, int32_t R,
+                    const int32_t* windows_host /* [L,3]: back, ahead, samples */,
+                    const double* weights_host /* [L, APE_POST_MAX_WINDOW] or NULL */, int32_t L,
+                    const uint8_t* sel_dev /* [S, F] */, int32_t S,
+                    uint32_t flags /* APE_FLAG_SPREAD or 0 */,
+                    const double* bodies_host /* [n_bodies,9] or NULL: the model's body */, int32_t n_bodies,
+                    void* out_dev /* [S, F, 25 (+21)] */, int32_t out_dtype,
+                    int64_t workspace_bytes, void* stream);
+int ape_post_select_last(int32_t out4[4]);   /* passes, frames per pass, frames per tile, staged in LDS */
+int ape_select_rungs(const void* keys_dev, int32_t keys_dtype, int32_t n_sets, int64_t set_stride, int32_t F, int64_t frame_stride,
+                     const int32_t* seg_starts_host, int32_t R,
+                     const double* edges_host /* [B] */, int32_t n_edges,
+                     const int32_t* rung_of_slot_host /* [B + 1] */, int32_t nan_rung,
+                     const int32_t* reach_host /* [L] */, int32_t L, int32_t slope,
+                     uint8_t* sel_dev /* [S, F] */, void* stream);
+
 /* ---- each recording's heading and frame offset against the truth (additive in ABI 7) -------------------------------------
  * replaces: nothing; the reference has no counterpart.  Every input is calibrated against a forward direction taken from a calibration
  * pose; a wearer who stood a few degrees off, or a mocap frame that is not levelled, leaves the whole estimate of a recording turned
