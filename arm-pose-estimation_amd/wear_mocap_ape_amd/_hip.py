@@ -32,6 +32,7 @@ SCORE_MAX_LAG, SCORE_MAX_LAGS = 128, 65      # APE_SCORE_MAX_LAG, APE_SCORE_MAX_
 POST_MAX_CONFIGS = 64             # APE_POST_MAX_CONFIGS (ape_post_sweep)
 POST_MAX_WINDOW = 64              # APE_POST_MAX_WINDOW (ape_post_window)
 SELECT_MAX_EDGES, SELECT_MAX_SLOPE = 256, 8    # APE_SELECT_MAX_EDGES, APE_SELECT_MAX_SLOPE (ape_select_rungs)
+SEGMENT_MAX_MIN, SEG_TABLE_WIDTH, SEG_MAX_VALUES, SEG_STAT_WIDTH, SEG_PIECE = 256, 4, 16, 5, 1024    # APE_SEGMENT_MAX_MIN, APE_SEG_* (ape_segment_*)
 FRAME_ACC_WIDTH = 51              # APE_FRAME_ACC_WIDTH (ape_frame_sums)
 BODY_ACC_WIDTH = 46               # APE_BODY_ACC_WIDTH (ape_body_sums)
 BODY_ROT_MSG, BODY_ROT_TRUTH = 0, 1         # APE_BODY_ROT_*
@@ -229,6 +230,16 @@ SIGNATURES["ape_post_select"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.
 SIGNATURES["ape_post_select_last"] = (C.c_int, [C.POINTER(C.c_int32)])
 SIGNATURES["ape_select_rungs"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
                                             C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p])
+# reaches and holds.  The labeller: keys + dtype, S, set stride, F, frame stride, starts_host, R, thresholds_host [P, 2],
+# mins_host [P, 2], P, first_label, labels, HIP stream.  The table: labels, S, F, starts_host, R, seg_of_frame | NULL, n_segs, table, cap,
+# HIP stream.  The reductions: values + dtype, value sets, set / frame / column stride, V, S, F, seg_of_frame, table, n_segs, cap, out,
+# HIP stream.
+SIGNATURES["ape_segment_frames"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int32, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p,
+                                              C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p])
+SIGNATURES["ape_segment_runs"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32,
+                                            C.c_void_p])
+SIGNATURES["ape_segment_stats"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_int32,
+                                             C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p])
 # heading and frame offset against the truth.  The sums: layout, msg + stride, msg dtype, truth + kind + dtype, F,
 # starts_host, R, skip, bodies_host, n_bodies, lag_min, lag_max, rec_lag_host, acc, HIP stream.  The rotation: layout, msg + stride,
 # spread + stride, msg dtype, F, starts_host, R, quats_host, n_quats, out + dtype, HIP stream

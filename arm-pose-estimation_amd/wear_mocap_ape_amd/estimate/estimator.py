@@ -723,6 +723,78 @@ class Estimator:
         bodies = self._body_measurements if bonemaps is None else bonemaps
         return score.motion_sums(self._layout, truth, truth_kind, starts, skip, times, bodies)
 
+    # ---- reaches and holds (the reference has no counterpart) ----
+    def _segments_of(self, score, speed, thresholds, mins, times, starts, extra=None):
+        """labels, table and per-segment records of one hand-speed column: the value columns are the speed (its maximum is the peak speed)
+        and ``speed * dt`` (its sum is the path length; ``dt`` is 1 on the index clock), then ``extra``'s"""
+        labels = score.segment_frames(speed, thresholds, mins, starts)
+        sof, n, table = score.segment_runs(labels, starts)
+        path = speed
+        if times is not None:
+            dt = torch.zeros_like(times)
+            dt[1:] = times[1:] - times[:-1]                  # (a recording's first frames have no speed: what dt holds there is not read)
+            path = speed * dt.to(speed.dtype)
+        cols = [speed.to(torch.float64), path.to(torch.float64)] + ([] if extra is None else [c.to(torch.float64) for c in extra])
+        stats = score.segment_stats(torch.stack(cols, dim=1), sof, n, table)
+        return {"labels": labels, "seg_of_frame": sof, "n_segs": n, "table": table, "stats": stats}
+
+    def segment_recording(self, out, pilot_rows=None, thresholds=(0.004, 0.008), mins=(4, 4), times=None, starts=None, truth=None,
+                          truth_kind="targets", truth_thresholds=None, bonemaps=None, truth_mins=(1, 1)):
+        """Where a replay holds and where it reaches, and every segment's figures (``score.segment_frames``, ``segment_runs``,
+        ``segment_stats``).  ``out`` as ``process_recording`` returned it; ``pilot_rows``: the rows whose hand speed is
+        the key (a smoothed rendering of the same replay, e.g. a rung of ``repost_windows``; default ``out`` itself); ``thresholds``
+        ``(lo, hi)`` of the hand speed in metres per frame, or per unit of ``times`` (device float64 ``[F]``, ``score.frame_times``);
+        ``mins`` ``(min_hold, min_move)`` in frames.  A recording's first three frames have no speed and take the label hold.
+        Returns a dict on the device: ``labels`` uint8 ``[F]`` (0 hold, 1 move), ``seg_of_frame`` int32 ``[F]``, ``n_segs``, ``table``
+        int32 ``[n, 4]`` of ``(recording, first frame, length, label)``, ``stats`` float64 ``[n, V, 5]`` (``score.SEG_STAT_NAMES``) over
+        the columns ``names``: ``hand_speed`` (its maximum is the peak speed) and ``path`` (speed times the frame's step: its sum is the
+        path length).  With ``truth`` (device ``[F, O]`` de-normalised targets, or est rows with ``truth_kind="est"``; ``bonemaps`` as in
+        ``score_recording``) the columns ``hand_pos`` and ``elbow_pos`` follow, ``score_recording``'s per-frame errors at lag 0, and
+        the dict holds ``truth``: ``truth_segments``' dict at ``truth_thresholds`` (default: half of ``thresholds``) and ``truth_mins``;
+        ``match``: ``score.match_segments`` of the two tables, moves against moves; ``hold_error`` float64 ``[n_truth]``: for every
+        hold of the truth the distance between the mean estimated and the mean true hand position over its frames (NaN for a move).
+        The table's size is read back: the call waits for the device."""
+        from wear_mocap_ape_amd import score
+        rows = out if pilot_rows is None else pilot_rows
+        speed = score.motion_sums(self._layout, rows, "msg", starts, 0, times, None, True)[0]
+        if speed.dim() != 2:
+            raise UserWarning("segment_recording: one set of rows [F, >= 25] (pick a rung of a [C, F, 25] rendering)")
+        speed = speed[:, 0]
+        names, extra = ["hand_speed", "path"], None
+        if truth is not None:
+            bodies = self._body_measurements if bonemaps is None else bonemaps
+            errors = score.score_rows(self._layout, out, truth, truth_kind, None, starts, 0, bodies)[0]
+            names, extra = names + ["hand_pos", "elbow_pos"], [errors[:, 0], errors[:, 1]]
+        res = self._segments_of(score, speed, thresholds, mins, times, starts, extra)
+        res["names"] = names
+        if truth is None:
+            return res
+        th = np.asarray(thresholds, dtype=np.float64) / 2.0 if truth_thresholds is None else truth_thresholds
+        tr = self.truth_segments(truth, truth_kind, th, truth_mins, times, starts, bonemaps)
+        res["truth"] = tr
+        res["match"] = score.match_segments(res["table"], tr["table"], score.MOVE, 0, times)
+        # the endpoint error of the truth's holds: six more columns over the truth's segments, the hand as estimated and as it was
+        est_rows = truth if truth_kind == "est" else score.resample_truth(self._layout, truth, truth_kind, starts, None, None, int(truth.shape[0]),
+                                                                           starts, None, 0.0, bodies)
+        hands = torch.cat([out[:, 4:7].to(torch.float64), est_rows[:, 0:3].to(torch.float64)], dim=1)
+        hs = score.segment_stats(hands, tr["seg_of_frame"], tr["n_segs"], tr["table"])
+        mean = hs[:, :, 1] / hs[:, :, 0]
+        d = mean[:, 0:3] - mean[:, 3:6]
+        err = torch.sqrt((d * d).sum(dim=1))
+        res["hold_error"] = torch.where(tr["table"][:, 3] == score.HOLD, err, torch.full_like(err, float("nan")))
+        return res
+
+    def truth_segments(self, truth, truth_kind="targets", thresholds=(0.002, 0.004), mins=(1, 1), times=None, starts=None, bonemaps=None):
+        """The truth's own holds and reaches: ``segment_recording``'s dict (``labels``, ``seg_of_frame``, ``n_segs``, ``table``, ``stats``
+        over ``hand_speed`` and ``path``, ``names``) from the hand speed of ``truth`` (device ``[F, O]`` de-normalised targets, or est
+        rows with ``truth_kind="est"``) with this estimator's layout and body."""
+        from wear_mocap_ape_amd import score
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        speed = score.motion_sums(self._layout, truth, truth_kind, starts, 0, times, bodies, True)[0][:, 0]
+        res = self._segments_of(score, speed, thresholds, mins, times, starts)
+        res["names"] = ["hand_speed", "path"]
+        return res
+
     # ---- joint angles (DESIGN.md 4.41; the reference has no counterpart) ----
     def angles_recording(self, out, truth=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
                          per_frame=False, min_swing=0.05):

@@ -59,7 +59,14 @@ over a sweep of lags, ``post_window_numpy`` is the host statement.
 A window that is the same on every frame is a compromise for arm motion, which is holds joined by reaches.  ``select_rungs`` picks a rung
 of a ``ladder`` of windows for every frame from a per-frame key (the hand speed) under an envelope, and ``post_select`` runs the
 post-filter at the rung chosen (``ape_select_rungs``, ``ape_post_select``); ``select_rungs_numpy`` and
-``post_select_numpy`` are the host statements, ``score_selected`` scores the sets."""
+``post_select_numpy`` are the host statements, ``score_selected`` scores the sets.
+
+Where those holds and reaches are, and what each of them was like: ``segment_frames`` labels every frame hold or move from a per-frame
+key with two thresholds and minimum lengths, ``segment_runs`` turns any labels into a table of segments, ``segment_stats`` reduces
+per-frame columns over every segment in a stated order of summation (``ape_segment_frames``, ``ape_segment_runs``,
+``ape_segment_stats``); ``match_segments`` pairs an estimate's moves with the truth's and ``summarise_segments`` reads
+the records per recording and label on the host; ``segment_frames_numpy``, ``segment_runs_numpy`` and ``segment_stats_numpy`` are the
+host statements."""
 import ctypes as C
 import math
 
@@ -2826,3 +2833,336 @@ def spread_sigma(spread):
     hand = torch.sqrt((s[..., 3] + s[..., 6]) + s[..., 8])
     elbow = torch.sqrt((s[..., 12] + s[..., 15]) + s[..., 17])
     return torch.cat([hand[..., None], elbow[..., None], s[..., 18:21]], dim=-1)
+
+
+# ---- reaches and holds: segment a replay and score each segment ----
+# Arm motion is holds joined by reaches, and its users count in movements.  ``segment_frames`` labels every frame hold or move from a
+# per-frame key (the hand speed) with hysteresis and minimum lengths, ``segment_runs`` turns any labels into a table of segments,
+# ``segment_stats`` reduces per-frame columns over every segment in a stated order; ``match_segments`` and ``summarise_segments`` read the
+# tables on the host.  ``segment_frames_numpy``, ``segment_runs_numpy`` and ``segment_stats_numpy`` are the host statements.
+SEGMENT_MAX_MIN, SEG_TABLE_WIDTH, SEG_MAX_VALUES = _hip.SEGMENT_MAX_MIN, _hip.SEG_TABLE_WIDTH, _hip.SEG_MAX_VALUES
+SEG_STAT_WIDTH, SEG_PIECE = _hip.SEG_STAT_WIDTH, _hip.SEG_PIECE
+SEG_STAT_NAMES = ("n", "sum", "sum_sq", "max", "argmax")
+HOLD, MOVE = 0, 1
+
+
+def _segment_rules(thresholds, mins, S: int, first_label):
+    """the host arrays of ``ape_segment_frames``, checked as the C ABI checks them: float64 ``[P, 2]`` of ``(lo, hi)``, int32 ``[P, 2]`` of
+    ``(min_hold, min_move)``, ``P`` 1 or ``S`` (one pair for every set, or a row per set), ``first_label``"""
+    try:
+        th = np.asarray(thresholds, dtype=np.float64).reshape(-1, 2)
+        mn = np.asarray(mins, dtype=np.int32).reshape(-1, 2)
+    except (TypeError, ValueError):
+        raise UserWarning("thresholds: (lo, hi) or [P, 2]; mins: (min_hold, min_move) or [P, 2]")
+    P = max(th.shape[0], mn.shape[0])
+    if P not in (1, S) or th.shape[0] not in (1, P) or mn.shape[0] not in (1, P):
+        raise UserWarning(f"thresholds / mins: one row or one per set ({S}), got {th.shape[0]} and {mn.shape[0]}")
+    th = np.ascontiguousarray(np.broadcast_to(th, (P, 2)))
+    mn = np.ascontiguousarray(np.broadcast_to(mn, (P, 2)))
+    if not np.isfinite(th).all() or (th[:, 1] < th[:, 0]).any():
+        raise UserWarning(f"thresholds: finite (lo, hi) with lo <= hi, got {th.tolist()}")
+    if (mn < 1).any() or (mn > SEGMENT_MAX_MIN).any():
+        raise UserWarning(f"mins: minimum lengths 1 .. {SEGMENT_MAX_MIN}, got {mn.tolist()}")
+    if first_label not in (0, 1):
+        raise UserWarning(f"first_label: 0 (hold) or 1 (move), got {first_label!r}")
+    return th, mn, P, int(first_label)
+
+
+def _runs(lab, a: int, b: int):
+    """the maximal runs of equal values of ``lab[a:b]`` as ``(first, end)`` pairs"""
+    f = a
+    while f < b:
+        g = f + 1
+        while g < b and lab[g] == lab[f]:
+            g += 1
+        yield f, g
+        f = g
+
+
+def segment_frames_numpy(keys, thresholds=(0.004, 0.008), mins=(1, 1), starts=None, first_label: int = 0) -> np.ndarray:
+    """The host statement of ``segment_frames`` as a plain loop: ``keys [(S,) F]`` -> uint8 ``[(S,) F]``, 0 hold and 1 move.  Per set and
+    recording ``[a, b)``, on the key widened to float64: (1) a frame decides 1 if ``v > hi``, 0 if ``v <= lo``, and is undecided otherwise
+    (NaN fails both); (2) ``s[f]`` is the decision of the last decisive frame in ``[a, f]``, ``first_label`` without one; (3) a run of 0
+    shorter than ``min_hold`` with a 1 on both sides inside the recording becomes 1; (4) then a run of 1 shorter than ``min_move`` becomes
+    0, at the recording's ends too."""
+    k = np.asarray(keys)
+    k2 = k.reshape(-1, k.shape[-1]).astype(np.float64)
+    S, F = k2.shape
+    th, mn, P, first_label = _segment_rules(thresholds, mins, S, first_label)
+    st = [int(s) for s in _recording_starts(starts)]
+    out = np.zeros((S, F), dtype=np.uint8)
+    for s in range(S):
+        (lo, hi), (min_hold, min_move) = th[s if P > 1 else 0], mn[s if P > 1 else 0]
+        lab = out[s]
+        for a, b in zip(st, st[1:] + [F]):
+            cur = first_label
+            for f in range(a, b):
+                v = k2[s, f]
+                if v > hi:
+                    cur = 1
+                elif v <= lo:
+                    cur = 0
+                lab[f] = cur
+            for f, g in list(_runs(lab, a, b)):
+                if lab[f] == 0 and g - f < min_hold and f > a and g < b:
+                    lab[f:g] = 1
+            for f, g in list(_runs(lab, a, b)):
+                if lab[f] == 1 and g - f < min_move:
+                    lab[f:g] = 0
+    return out.reshape(k.shape)
+
+
+def _key_sets(keys, what: str):
+    """(tensor [S, F], set stride, frame stride) of a device view ``[F]`` or ``[S, F]`` as the strided entries take it; copied if need be"""
+    if not isinstance(keys, torch.Tensor) or not keys.is_cuda or keys.dim() not in (1, 2) or min(keys.shape) < 1:
+        raise UserWarning(f"{what}: a device tensor [F] or [S, F]")
+    if keys.dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"{what}: float32 or float64, got {keys.dtype}")
+    k = keys[None] if keys.dim() == 1 else keys
+    S, F = int(k.shape[0]), int(k.shape[1])
+    if S > _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"{what}: at most {_hip.POST_MAX_CONFIGS} sets, got {S}")
+    ss, fs = int(k.stride(0)), int(k.stride(1))
+    fs = fs if F > 1 else max(fs, 1)
+    if fs < 1 or (S > 1 and ss <= (F - 1) * fs):
+        k = k.contiguous()
+        ss, fs = int(k.stride(0)), max(int(k.stride(1)), 1)
+    return k, (ss if S > 1 else 0), fs
+
+
+def segment_frames(keys, thresholds=(0.004, 0.008), mins=(1, 1), starts=None, first_label: int = 0):
+    """Hold or move for every frame, on the device (``ape_segment_frames``).  ``keys``: a device ``[F]`` or ``[S, F]`` view, float32 or
+    float64, ``S <= 64`` -- column 0 of ``motion_sums``' per-frame rows, the hand speed, goes in without a copy; ``thresholds``:
+    ``(lo, hi)`` or ``[S, 2]``: a frame above ``hi`` moves, one at or below ``lo`` holds, one between keeps the label of the frame before
+    it (``lo == hi``: a plain threshold); ``mins``: ``(min_hold, min_move)`` or ``[S, 2]``, 1 .. 256: a hold shorter than ``min_hold``
+    between two moves is filled, then a move shorter than ``min_move`` is dropped; ``starts``: the recordings' first frames -- a
+    recording never inherits from the one before; ``first_label``: the label of a recording's frames before its first decisive one (NaN
+    keys, such as the first three motion rows of a recording, are undecided).  Returns uint8 ``[(S,) F]`` on the device, 0 hold and 1
+    move.  Integer work: the same inputs give the same bits.  Does not wait."""
+    k, ss, fs = _key_sets(keys, "keys")
+    S, F = int(k.shape[0]), int(k.shape[1])
+    th, mn, P, first_label = _segment_rules(thresholds, mins, S, first_label)
+    st = _recording_starts(starts)
+    dev = k.device
+    with torch.cuda.device(dev):
+        labels = torch.empty((S, F), dtype=torch.uint8, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_segment_frames(C.c_void_p(k.data_ptr()), _f64(k.dtype), S, ss, F, fs, C.c_void_p(st.ctypes.data), int(st.shape[0]),
+                                                 C.c_void_p(th.ctypes.data), C.c_void_p(mn.ctypes.data), P, first_label,
+                                                 C.c_void_p(labels.data_ptr()), stream), "ape_segment_frames")
+    return labels[0] if keys.dim() == 1 else labels
+
+
+def segment_runs_numpy(labels, starts=None):
+    """The host statement of ``segment_runs``: ``labels [(S,) F]`` of any integers -> ``(seg_of_frame int32 [(S,) F], n_segs, table)``.  A
+    segment is a maximal run of equal labels inside one recording; ids count from 0 per set in frame order; a table row is ``(recording,
+    first frame, length, label)``.  One set: ``n_segs`` an int and ``table`` int32 ``[n_segs, 4]``; ``S`` sets: int32 ``[S]`` and a list."""
+    lab = np.asarray(labels)
+    l2 = lab.reshape(-1, lab.shape[-1])
+    S, F = l2.shape
+    st = [int(s) for s in _recording_starts(starts)]
+    sof, tables = np.zeros((S, F), dtype=np.int32), []
+    for s in range(S):
+        rows = []
+        for r, (a, b) in enumerate(zip(st, st[1:] + [F])):
+            for f, g in _runs(l2[s], a, b):
+                sof[s, f:g] = len(rows)
+                rows.append((r, f, g - f, int(l2[s, f])))
+        tables.append(np.asarray(rows, dtype=np.int32).reshape(-1, SEG_TABLE_WIDTH))
+    if lab.ndim == 1:
+        return sof[0], len(tables[0]), tables[0]
+    return sof, np.asarray([len(t) for t in tables], dtype=np.int32), tables
+
+
+def segment_runs(labels, starts=None, cap=None, seg_of_frame: bool = True):
+    """The table of segments of any labels, on the device (``ape_segment_runs``).  ``labels``: device uint8 ``[F]`` or ``[S, F]``, any
+    values (``segment_frames``' labels, ``select_rungs``' selector); ``starts``: the recordings' first frames -- a segment ends with its
+    recording.  Returns ``(seg_of_frame, n_segs, table)`` on the device: int32 ``[(S,) F]`` (None with ``seg_of_frame=False``), the id of
+    every frame's segment counted from 0 per set; int32 ``[(S)]`` the number of segments; int32 ``[(S,) cap, 4]`` rows of ``(recording,
+    first frame, length, label)``.  ``cap=None``: room for ``F`` segments is made and the table comes back sliced to ``n_segs`` (to the
+    largest of the sets'), which READS ``n_segs`` BACK AND WAITS FOR THE DEVICE; with a ``cap`` the call does not wait, rows at or
+    beyond ``cap`` are dropped (``n_segs`` still counts them: call again with more room) and rows from ``n_segs`` on are not written.
+    Integer work: the same inputs give the same bits."""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda or labels.dim() not in (1, 2) or min(labels.shape) < 1 or labels.dtype != torch.uint8:
+        raise UserWarning("labels: a device uint8 tensor [F] or [S, F]")
+    lab = (labels[None] if labels.dim() == 1 else labels).contiguous()
+    S, F = int(lab.shape[0]), int(lab.shape[1])
+    if S > _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"labels: at most {_hip.POST_MAX_CONFIGS} sets, got {S}")
+    room = F if cap is None else int(cap)
+    if room < 1:
+        raise UserWarning(f"cap: at least 1, got {cap}")
+    st = _recording_starts(starts)
+    dev = lab.device
+    with torch.cuda.device(dev):
+        sof = torch.empty((S, F), dtype=torch.int32, device=dev) if seg_of_frame else None
+        n = torch.empty((S,), dtype=torch.int32, device=dev)
+        table = torch.empty((S, room, SEG_TABLE_WIDTH), dtype=torch.int32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_segment_runs(C.c_void_p(lab.data_ptr()), S, F, C.c_void_p(st.ctypes.data), int(st.shape[0]),
+                                               C.c_void_p(sof.data_ptr()) if sof is not None else None, C.c_void_p(n.data_ptr()),
+                                               C.c_void_p(table.data_ptr()), room, stream), "ape_segment_runs")
+        if cap is None:
+            table = table[:, :int(n.max().item())]          # the one wait
+    if labels.dim() == 1:
+        return (None if sof is None else sof[0]), n[0], table[0]
+    return sof, n, table
+
+
+def _piece_sum(x) -> float:
+    """``x`` float64 ``[n]`` added left to right from ``+0.0``, one rounding per element (``np.add.accumulate`` is that loop)"""
+    return float(np.add.accumulate(np.concatenate([[0.0], x]))[-1])
+
+
+def segment_stats_numpy(values, table) -> np.ndarray:
+    """The host statement of ``segment_stats`` for one set: ``values [F]`` or ``[F, V]`` and ``table [n, 4]`` -> float64 ``[n, V, 5]`` of
+    ``SEG_STAT_NAMES``: the count of values that are not NaN, their sum, the sum of their squares, their maximum (``-inf`` without any)
+    and the batch frame of its first occurrence (``-1``).  The order, bit for bit: a value is widened to float64 and its square rounded
+    before it is added; the segment is cut into pieces of 1024 frames counted from its first frame; a piece is added in frame order from
+    ``+0.0`` and the pieces in order from ``+0.0``."""
+    x = np.asarray(values)
+    x = (x[:, None] if x.ndim == 1 else x).astype(np.float64)
+    tab = np.asarray(table).reshape(-1, SEG_TABLE_WIDTH)
+    out = np.zeros((tab.shape[0], x.shape[1], SEG_STAT_WIDTH))
+    with np.errstate(all="ignore"):
+        for i, (_, first, length, _) in enumerate(tab.tolist()):
+            for v in range(x.shape[1]):
+                n, total, total_sq = 0, 0.0, 0.0
+                for p in range(first, first + length, SEG_PIECE):
+                    piece = x[p:min(p + SEG_PIECE, first + length), v]
+                    piece = piece[piece == piece]
+                    n += piece.shape[0]
+                    total = total + _piece_sum(piece)
+                    total_sq = total_sq + _piece_sum(piece * piece)
+                seg = x[first:first + length, v]
+                live = np.flatnonzero(seg == seg)
+                mx, arg = -np.inf, -1.0
+                if n:
+                    k = live[np.flatnonzero(seg[live] == seg[live].max())[0]]
+                    mx, arg = seg[k], float(first + k)      # the value AT that frame: of +0.0 and -0.0, which compare equal, the earlier
+                out[i, v] = n, total, total_sq, mx, arg
+    return out
+
+
+def segment_stats(values, seg_of_frame, n_segs, table):
+    """Per-segment reductions of per-frame columns, on the device (``ape_segment_stats``).  ``values``: a device view ``[F]``, ``[F, V]``
+    (shared by every set) or ``[S, F, V]``, float32 or float64, ``V <= 16``, any positive strides (columns of motion or score rows go in
+    without a copy); ``seg_of_frame``, ``n_segs``, ``table``: what ``segment_runs`` returned for ``[F]`` or ``[S, F]`` labels (a table
+    sliced to ``n_segs`` or one with a ``cap``).  Returns float64 ``[(S,) cap, V, 5]`` on the device, per segment and column
+    ``SEG_STAT_NAMES``: the count of values that are not NaN, their sum, the sum of their squares, their maximum and the batch frame of its
+    first occurrence; rows from ``n_segs`` on are not written.  The order of summation is ``segment_stats_numpy``'s: a segment's record
+    has the same bits wherever it lies in a batch.  Does not wait."""
+    if not isinstance(values, torch.Tensor) or not values.is_cuda or values.dim() not in (1, 2, 3) or min(values.shape) < 1:
+        raise UserWarning("values: a device tensor [F], [F, V] or [S, F, V]")
+    if values.dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"values: float32 or float64, got {values.dtype}")
+    for t, what in ((seg_of_frame, "seg_of_frame"), (n_segs, "n_segs"), (table, "table")):
+        if not isinstance(t, torch.Tensor) or t.device != values.device or t.dtype != torch.int32:
+            raise UserWarning(f"{what}: segment_runs' int32 device tensor")
+    one = seg_of_frame.dim() == 1
+    sof = (seg_of_frame[None] if one else seg_of_frame).contiguous()
+    tab = (table[None] if table.dim() == 2 else table).contiguous()
+    n = n_segs.reshape(-1).contiguous()
+    x = values[:, None] if values.dim() == 1 else values
+    if sof.dim() != 2 or tab.dim() != 3 or tab.shape[2] != SEG_TABLE_WIDTH or tab.shape[0] != sof.shape[0] or n.shape[0] != sof.shape[0]:
+        raise UserWarning("seg_of_frame [(S,) F], n_segs [(S)] and table [(S,) cap, 4] of one segment_runs call")
+    S, F, cap = int(sof.shape[0]), int(sof.shape[1]), int(tab.shape[1])
+    V = int(x.shape[-1])
+    if x.shape[-2] != F or (x.dim() == 3 and x.shape[0] != S) or not 1 <= V <= SEG_MAX_VALUES:
+        raise UserWarning(f"values: [{F}, V] or [{S}, {F}, V] with V <= {SEG_MAX_VALUES}, got {tuple(values.shape)}")
+    dev = x.device
+    with torch.cuda.device(dev):
+        if cap < 1:
+            return torch.empty((S, 0, V, SEG_STAT_WIDTH), dtype=torch.float64, device=dev)[0 if one else slice(None)]
+        fs, cs = int(x.stride(-2)), int(x.stride(-1))
+        ss = int(x.stride(0)) if x.dim() == 3 else 0
+        fs, cs = (fs if F > 1 else max(fs, 1)), (cs if V > 1 else max(cs, 1))
+        if fs < 1 or cs < 1 or (x.dim() == 3 and S > 1 and ss <= (F - 1) * fs + (V - 1) * cs):
+            x = x.contiguous()
+            fs, cs, ss = V, 1, (F * V if x.dim() == 3 else 0)
+        sets = S if x.dim() == 3 else 1
+        out = torch.empty((S, cap, V, SEG_STAT_WIDTH), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_segment_stats(C.c_void_p(x.data_ptr()), _f64(x.dtype), sets, ss if sets > 1 else 0, fs, cs, V, S, F,
+                                                C.c_void_p(sof.data_ptr()), C.c_void_p(tab.data_ptr()), C.c_void_p(n.data_ptr()), cap,
+                                                C.c_void_p(out.data_ptr()), stream), "ape_segment_stats")
+    return out[0] if one else out
+
+
+def _table_host(table) -> np.ndarray:
+    t = table.detach().cpu().numpy() if isinstance(table, torch.Tensor) else np.asarray(table)
+    if t.ndim != 2 or t.shape[1] != SEG_TABLE_WIDTH:
+        raise UserWarning(f"table: one set's [n, {SEG_TABLE_WIDTH}] rows of (recording, first frame, length, label)")
+    return t.astype(np.int64)
+
+
+def match_segments(table_est, table_truth, label: int = MOVE, lag: int = 0, times=None) -> dict:
+    """The moves of an estimate paired with the truth's, on the host.  ``table_est``, ``table_truth``: one set's ``[n, 4]`` tables
+    (``segment_runs``); ``label``: the segments compared; ``lag``: frame ``f`` of the estimate is held against frame ``f - lag`` of the
+    truth (``score_lags``' sign).  The truth's segments are taken in order; each takes the still unmatched segment of the estimate in its
+    recording that overlaps it in the most frames (at least one), ties to the earlier one.  Returns ``pairs`` (rows of the truth's and the
+    estimate's table), ``onset`` and ``offset`` (the estimate's first frame and end less the truth's, in frames: positive is late),
+    ``onset_s`` and ``offset_s`` with ``times`` (the frames' clock ``[F]``: the same differences on it, the end taken at the last
+    frame), ``matched``, ``missed`` (the truth's without a partner) and ``spurious`` (the estimate's) with the rows of both."""
+    est, tru = _table_host(table_est), _table_host(table_truth)
+    e_rows = [i for i in range(est.shape[0]) if est[i, 3] == label]
+    t_rows = [i for i in range(tru.shape[0]) if tru[i, 3] == label]
+    taken, pairs, missed = set(), [], []
+    for i in t_rows:
+        r, a, n = int(tru[i, 0]), int(tru[i, 1]), int(tru[i, 2])
+        best, most = None, 0
+        for j in e_rows:
+            if j in taken or int(est[j, 0]) != r:
+                continue
+            b = int(est[j, 1]) - int(lag)
+            over = min(a + n, b + int(est[j, 2])) - max(a, b)
+            if over > most:
+                best, most = j, over
+        if best is None:
+            missed.append(i)
+        else:
+            taken.add(best)
+            pairs.append((i, best))
+    on = np.asarray([int(est[j, 1]) - int(lag) - int(tru[i, 1]) for i, j in pairs], dtype=np.int64)
+    off = np.asarray([int(est[j, 1] + est[j, 2]) - int(lag) - int(tru[i, 1] + tru[i, 2]) for i, j in pairs], dtype=np.int64)
+    res = {"pairs": pairs, "onset": on, "offset": off, "matched": len(pairs), "missed": len(missed), "spurious": len(e_rows) - len(taken),
+           "missed_rows": missed, "spurious_rows": [j for j in e_rows if j not in taken]}
+    if times is not None:
+        t = times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else np.asarray(times)
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        at = lambda f: t[np.clip(f, 0, t.shape[0] - 1)]
+        res["onset_s"] = np.asarray([at(int(est[j, 1]) - int(lag)) - at(int(tru[i, 1])) for i, j in pairs], dtype=np.float64)
+        res["offset_s"] = np.asarray([at(int(est[j, 1] + est[j, 2]) - 1 - int(lag)) - at(int(tru[i, 1] + tru[i, 2]) - 1) for i, j in pairs],
+                                     dtype=np.float64)
+    return res
+
+
+def summarise_segments(table, stats, names, times=None) -> list:
+    """One set's segments per recording and label, on the host.  ``table [n, 4]``, ``stats [n, V, 5]`` (``segment_stats``; rows past ``n``
+    are ignored), ``names``: the ``V`` columns' names; ``times``: the frames' clock ``[F]`` -- durations are then the time from a
+    segment's first to its last frame, else its frames.  Returns a list of dicts ordered by ``(recording, label)``: ``recording``,
+    ``label``, ``count``, ``mean_duration``, ``longest_duration``, ``mean`` and ``max`` (by column name: the mean over the segments of
+    each segment's mean of its values that are not NaN, and the largest of their maxima; NaN where no segment has a value)."""
+    tab = _table_host(table)
+    st = stats.detach().cpu().numpy() if isinstance(stats, torch.Tensor) else np.asarray(stats)
+    st = np.asarray(st, dtype=np.float64)[:tab.shape[0]]
+    names = list(names)
+    if st.ndim != 3 or st.shape != (tab.shape[0], len(names), SEG_STAT_WIDTH):
+        raise UserWarning(f"stats: [{tab.shape[0]}, {len(names)}, {SEG_STAT_WIDTH}] for this table and these names, got {st.shape}")
+    dur = tab[:, 2].astype(np.float64)
+    if times is not None:
+        t = times.detach().cpu().numpy() if isinstance(times, torch.Tensor) else np.asarray(times)
+        t = np.asarray(t, dtype=np.float64).reshape(-1)
+        dur = t[tab[:, 1] + tab[:, 2] - 1] - t[tab[:, 1]]
+    res = []
+    for r, lab in sorted({(int(a), int(b)) for a, b in zip(tab[:, 0], tab[:, 3])}):
+        rows = np.flatnonzero((tab[:, 0] == r) & (tab[:, 3] == lab))
+        s = st[rows]
+        with np.errstate(all="ignore"):
+            means = np.where(s[:, :, 0] > 0, s[:, :, 1] / np.where(s[:, :, 0] > 0, s[:, :, 0], 1.0), np.nan)
+            some = (s[:, :, 0] > 0).any(axis=0)
+            mean = np.where(some, np.nansum(means, axis=0) / np.maximum((s[:, :, 0] > 0).sum(axis=0), 1), np.nan)
+            top = np.where(some, s[:, :, 3].max(axis=0), np.nan)
+        res.append({"recording": r, "label": lab, "count": int(rows.shape[0]), "mean_duration": float(dur[rows].mean()),
+                    "longest_duration": float(dur[rows].max()), "mean": dict(zip(names, mean.tolist())), "max": dict(zip(names, top.tolist()))})
+    return res

@@ -1109,6 +1109,74 @@ int ape_select_rungs(const void* keys_dev, int32_t keys_dtype, int32_t n_sets, i
                      const int32_t* reach_host /* [L] */, int32_t L, int32_t slope,
                      uint8_t* sel_dev /* [S, F] */, void* stream);
 
+/* ---- reaches and holds: segment a replay on the device and score each segment (additive in ABI 7) -------------------------
+ * replaces: nothing; the reference has no counterpart.  4.43 and 4.44 treat arm motion as holds joined by reaches; these three entries say
+ * where they are and reduce per-frame columns over each of them.  Device arrays only, no model handle; they run on the current HIP
+ * device, launch on `stream` and do not wait; the host arrays have been consumed when they return.  Integers throughout in the first
+ * two; no atomics on device memory and a stated order of summation in the third: the same inputs give the same bits.
+ *
+ * ape_segment_frames: a label per frame (0 hold, 1 move) from a key with hysteresis and minimum lengths.
+ *   keys_dev, keys_dtype, n_sets S, set_stride, F, frame_stride, seg_starts_host / R: those of ape_select_rungs.
+ *   thresholds_host f64 [P, 2] of (lo, hi), finite, lo <= hi; mins_host int32 [P, 2] of (min_hold, min_move), each 1 ..
+ *          APE_SEGMENT_MAX_MIN; P = 1 (every set) or P = S (row s for set s).  first_label 0 or 1.
+ *   Rule, per set and per recording [a, b), on the key widened to float64:
+ *     1. frame f is decisive with d = 1 if v > hi, with d = 0 if v <= lo, and undecided otherwise.  NaN fails both compares and is
+ *        undecided; infinities decide; lo == hi is a plain threshold.
+ *     2. s[f] = d[g] at the last decisive g in [a, f], or first_label if there is none.  A recording never inherits from the one before.
+ *     3. fill: a maximal run of s == 0 shorter than min_hold with a 1 on both sides inside the recording becomes 1; a run that touches
+ *        either end of the recording stays.
+ *     4. drop: after the fill, a maximal run of 1 shorter than min_move becomes 0, at the ends of the recording too.
+ *   (1, 1) makes steps 3 and 4 no-ops.  Step 2 is a segmented scan in the reduce-then-scan shape of ape_frame_times: tiles of 1024 frames,
+ *   a two-bit aggregate per tile and set, one workgroup per set scanning the aggregates, no workgroup waiting for another.  Steps 3 and 4
+ *   read s within (min_hold - 1) + (min_move - 1) <= 510 frames on either side; a tile stages them in LDS, one byte each, from a scratch
+ *   s in the call's slot.
+ *   labels_dev uint8 [S, F].
+ * ape_segment_runs: the run-length table of any uint8 labels (0 .. 255; ape_select_rungs' sel goes in as well).  A segment is a maximal
+ *   run of equal labels inside one recording.
+ *   seg_of_frame_dev int32 [S, F] or NULL: the id of the frame's segment, counted from 0 per set in frame order.
+ *   n_segs_dev int32 [S]: the number of segments, at most F, whatever cap is.
+ *   table_dev int32 [S, cap, APE_SEG_TABLE_WIDTH]: (recording, first frame, length, label) of segment id < cap.  Rows at or beyond cap are
+ *          not written and nothing else changes: a caller that finds n_segs > cap calls again.  Rows n_segs .. cap - 1 are not written.
+ *   A count of boundary flags gives the id and a running maximum of boundary positions the first frame, both in one reduce-then-scan
+ *   pass; the last frame of a run writes its row.  No lane reads what another lane of the same launch wrote to device memory.
+ * ape_segment_stats: per-segment reductions of V per-frame columns.
+ *   values_dev of values_dtype (APE_F32 / APE_F64): value (s, f, v) is element s * set_stride + f * frame_stride + v * col_stride;
+ *          n_value_sets = 1 (shared by all sets; set_stride is not read) or S.  1 <= V <= APE_SEG_MAX_VALUES.
+ *   seg_of_frame_dev, table_dev, n_segs_dev, cap: what ape_segment_runs wrote for the same S, F and cap.
+ *   out_dev f64 [S, cap, V, APE_SEG_STAT_WIDTH], per segment and column: the count of values that are not NaN; their sum; the sum of
+ *          their squares; their maximum (-inf when the count is 0); the batch frame of the first occurrence of the maximum as a float64
+ *          (-1 when the count is 0); the maximum is the value at that frame (of +0.0 and -0.0, which compare equal, the earlier one).
+ *          A NaN is left out of its own cell only; infinities follow IEEE.  The rows of segments below
+ *          min(n_segs, cap) are written whole and no other byte is touched.
+ *   Order of summation (part of the contract).  A value is widened to float64; its square is rounded before it is added; a segment is cut
+ *          into pieces of APE_SEG_PIECE frames counted from its own first frame; a piece is summed in frame order from +0.0 and the pieces
+ *          are added in order from +0.0.  So a segment's record has the same bits wherever it lies in a batch and whichever set it is
+ *          in, and a segment of up to APE_SEG_PIECE frames is a plain left-to-right sum.  score.py: segment_stats_numpy states it.
+ *   A workgroup per aligned tile of APE_SEG_PIECE batch frames owns the pieces that start in it and its lanes take (piece, column) pairs;
+ *   a first piece goes straight to out_dev, any other (at most one starts in a tile) to a workspace in the call's slot, and a second
+ *   launch folds the pieces of every segment longer than one piece in order.  No atomics on device memory, no memset.
+ * Refused with APE_ERR_INVALID_ARG on the host, before anything is written: a NULL pointer (but seg_of_frame_dev of ape_segment_runs);
+ * an unknown dtype; F < 1, R < 1, bad starts; S outside 1 .. APE_POST_MAX_CONFIGS; P not 1 or S; n_value_sets not 1 or S; V outside
+ * 1 .. APE_SEG_MAX_VALUES; a threshold that is not finite, hi < lo; a minimum length outside 1 .. APE_SEGMENT_MAX_MIN; first_label not 0
+ * or 1; cap < 1; a stride below 1, a set_stride that does not clear a set; an extent past 63 bits; a pointer not aligned to its element;
+ * an output overlapping an input or another output; a capturing stream. */
+#define APE_SEGMENT_MAX_MIN 256
+#define APE_SEG_TABLE_WIDTH 4
+#define APE_SEG_MAX_VALUES 16
+#define APE_SEG_STAT_WIDTH 5
+#define APE_SEG_PIECE 1024
+int ape_segment_frames(const void* keys_dev, int32_t keys_dtype, int32_t n_sets, int64_t set_stride, int32_t F, int64_t frame_stride,
+                       const int32_t* seg_starts_host, int32_t R,
+                       const double* thresholds_host /* [P, 2]: lo, hi */, const int32_t* mins_host /* [P, 2]: min_hold, min_move */,
+                       int32_t P, int32_t first_label, uint8_t* labels_dev /* [S, F] */, void* stream);
+int ape_segment_runs(const uint8_t* labels_dev /* [S, F] */, int32_t n_sets, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                     int32_t* seg_of_frame_dev /* [S, F] or NULL */, int32_t* n_segs_dev /* [S] */,
+                     int32_t* table_dev /* [S, cap, 4] */, int32_t cap, void* stream);
+int ape_segment_stats(const void* values_dev, int32_t values_dtype, int32_t n_value_sets, int64_t set_stride, int64_t frame_stride,
+                      int64_t col_stride, int32_t V, int32_t n_sets, int32_t F,
+                      const int32_t* seg_of_frame_dev /* [S, F] */, const int32_t* table_dev /* [S, cap, 4] */,
+                      const int32_t* n_segs_dev /* [S] */, int32_t cap, double* out_dev /* [S, cap, V, 5] */, void* stream);
+
 /* ---- each recording's heading and frame offset against the truth (additive in ABI 7) -------------------------------------
  * replaces: nothing; the reference has no counterpart.  Every input is calibrated against a forward direction taken from a calibration
  * pose; a wearer who stood a few degrees off, or a mocap frame that is not levelled, leaves the whole estimate of a recording turned
