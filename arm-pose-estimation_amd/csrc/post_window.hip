@@ -42,6 +42,7 @@
 #include "../../include/ape_hip.h"
 #include "stream_post_device.h"
 #include "bank_host.h"
+#include "score_host.h"
 
 #include <algorithm>
 #include <cmath>
@@ -367,6 +368,13 @@ int make_plan(const char* who, const char* sets, int layout, int F, const int32_
 // The workspace of a device (post_common.h): one list and one mutex for every caller of post_filter.
 std::mutex g_mu;
 std::vector<PostWorkspace*> g_ws;                       // by device index
+// The staging of a call (score_host.h): bodies, row weights and starts go through a pinned slot, so that they are consumed when the
+// call returns and the one copy to the workspace neither waits for the stream nor reads the caller's memory later.  (A copy straight
+// from pageable memory is staged by the runtime itself while the call is made, but only up to a size: measured, at once up to 295 KB,
+// and at 1.44 MB -- the bodies of 20 000 recordings -- the call was held until the stream had reached the copy, behind everything
+// queued before it; profiles/calls_in_flight.md.)  The slots have no device block: the device side is the workspace's tail.  Locked
+// inside g_mu.
+ApeSlotPool g_pool("post_filter");
 
 template <typename TMsg, bool SPR, bool SWEEP>
 hipError_t launch_window(const PwParams& p, unsigned blocks, size_t lds_bytes, hipStream_t st) {
@@ -442,27 +450,35 @@ int ape_postcommon::post_filter(const char* who, const char* sets, ape_model_t* 
     auto height = [&](int c) { return (windows_host[3 * c] + windows_host[3 * c + 1] + 1) * windows_host[3 * c + 2]; };
     // (a ladder stays in the caller's order: the sort serves the grouping of lanes, which the selector decides there)
     if (sel_dev == nullptr) std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return height(a) > height(b); });
-    std::vector<double> wts((size_t)q.table_words, 0.0);    // row weights u = w / m: one float64 division, here
     for (int c = 0; c < C; ++c) {
         const int o = order[(size_t)c];
         p.back[c] = (unsigned char)windows_host[3 * o]; p.ahead[c] = (unsigned char)windows_host[3 * o + 1];
         p.m[c] = (short)windows_host[3 * o + 2]; p.idx[c] = (unsigned char)o; p.tapered[c] = any_tapered && tapered[o] ? 1 : 0;
-        if (p.tapered[c])
-            for (int j = 0; j <= (int)p.back[c] + (int)p.ahead[c]; ++j)
-                wts[(size_t)c * NW + j] = weights_host[(size_t)o * NW + j] / (double)p.m[c];
     }
 
     std::lock_guard<std::mutex> lock(g_mu);
     PostWorkspace* ws = nullptr;
     if (int rc = take_post_workspace(g_ws, who, m->dims.device, total, st, &ws)) return rc;
+    // the host arrays in the order of the workspace's tail: bodies, row weights, starts
+    const size_t host_bytes = bodies_bytes + wts_bytes + (size_t)R * sizeof(int);
+    std::lock_guard<std::mutex> pool_lock(g_pool.mu);
+    ApeSlot* slot = nullptr;
+    if (int rc = g_pool.take(m->dims.device, host_bytes, 0, &slot)) return rc;
+    char* const pin = static_cast<char*>(slot->pinned);
+    if (table) memcpy(pin, bodies_host, bodies_bytes);
+    double* const wts = reinterpret_cast<double*>(pin + bodies_bytes);     // row weights u = w / m: one float64 division, here
+    for (size_t i = 0; i < (size_t)q.table_words; ++i) wts[i] = 0.0;
+    for (int c = 0; c < C; ++c)
+        if (p.tapered[c])
+            for (int j = 0; j <= (int)p.back[c] + (int)p.ahead[c]; ++j)
+                wts[(size_t)c * NW + j] = weights_host[(size_t)p.idx[c] * NW + j] / (double)p.m[c];
+    memcpy(pin + bodies_bytes + wts_bytes, seg_starts_host, (size_t)R * sizeof(int));
     double* est[2] = {static_cast<double*>(ws->dev), static_cast<double*>(ws->dev) + buf_words};
     double* bodies_d = reinterpret_cast<double*>(static_cast<char*>(ws->dev) + 2 * buf_words * sizeof(double));
     double* wts_d = reinterpret_cast<double*>(reinterpret_cast<char*>(bodies_d) + bodies_bytes);
     int* starts_d = reinterpret_cast<int*>(reinterpret_cast<char*>(wts_d) + wts_bytes);
-    // (pageable host memory: the copies have read it when they return)
-    e = hipMemcpyAsync(starts_d, seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && table) e = hipMemcpyAsync(bodies_d, bodies_host, bodies_bytes, hipMemcpyHostToDevice, st);
-    if (e == hipSuccess && any_tapered) e = hipMemcpyAsync(wts_d, wts.data(), wts_bytes, hipMemcpyHostToDevice, st);
+    // (one copy from pinned memory; a copy that fails leaves through the records below like a launch that fails)
+    e = hipMemcpyAsync(bodies_d, pin, host_bytes, hipMemcpyHostToDevice, st);
 
     PostFkParams fk{};
     fk.y = y_dev;
@@ -505,7 +521,7 @@ int ape_postcommon::post_filter(const char* who, const char* sets, ape_model_t* 
     }
     const hipError_t er = hipEventRecord(ws->done, st);    // the workspace is in flight whatever became of the launches
     ws->used = er == hipSuccess;
-    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "%s: launch failed: %s", who, hipGetErrorString(e));
+    if (int rc = g_pool.finish(who, slot, e, st)) return rc;      // the slot's event behind the same launches; a failed launch is reported here
     if (er != hipSuccess) {
         (void)hipStreamSynchronize(st);
         return ape_fail(APE_ERR_HIP, "%s: hipEventRecord failed: %s", who, hipGetErrorString(er));

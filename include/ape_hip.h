@@ -966,7 +966,9 @@ int ape_score_lags(int32_t layout, const void* msg_dev, int32_t msg_stride, cons
  * and a fixed order of summation: the same inputs give the same bits.  The launches go on `stream` and the call does not wait for
  * them; the host arrays (seg_starts_host, configs_host, bodies_host) have been consumed when it returns.  (The workspace is kept per
  * device, shared with ape_post_window, and grows on demand, which may wait for the device; a call on another stream is ordered behind
- * the last user of either entry by an event.)
+ * the last user of either entry by an event.  The host arrays travel through pinned staging slots as ape_score_rows keeps them, the
+ * post-filter's own: a call with more recordings or tapered windows than any before allocates its slot first, which may wait for the
+ * device, and up to 8 calls may be in flight per device.)
  * Refused on the host before anything is written: NULL model / y_dev / out_dev / seg_starts_host / configs_host; F < 1, R < 1, bad
  * starts; F * n_mc >= 2^31; C < 1 or C > APE_POST_MAX_CONFIGS; smooth outside [1, 64], m outside [1, n_mc], smooth * m > 4096;
  * n_bodies not 0 / 1 / R (0 iff bodies_host is NULL); flags other than APE_FLAG_SPREAD; an unknown dtype; workspace_bytes < 0 or too
@@ -1029,7 +1031,8 @@ int ape_post_sweep_last(int32_t out4[4]);
  * there is nothing for ape_model_recover to re-issue.  No floating-point atomics and a fixed order of summation: the same inputs give
  * the same bits.  The launches go on `stream` and the call does not wait for them; the host arrays (seg_starts_host, windows_host,
  * weights_host, bodies_host) have been consumed when it returns.  (The workspace is kept per device, the one ape_post_sweep uses, and
- * grows on demand, which may wait for the device; a call on another stream is ordered behind the last user by an event.)
+ * grows on demand, which may wait for the device; a call on another stream is ordered behind the last user by an event.  The host
+ * arrays travel through the pinned staging slots ape_post_sweep names, taken and reused in the same way.)
  * Refused on the host before anything is written: NULL model / y_dev / out_dev / seg_starts_host / windows_host; F < 1, R < 1, bad
  * starts; n_mc < 1; F * n_mc >= 2^31; C < 1 or C > APE_POST_MAX_CONFIGS; back < 0, ahead < 0, n > APE_POST_MAX_WINDOW, m outside
  * [1, n_mc], n * m > 4096; a weight that is not finite or negative, a row that does not sum to 1 within 1e-9; n_bodies not 0 / 1 / R
