@@ -53,3 +53,35 @@ __device__ __forceinline__ void look_landed() { asm volatile("s_waitcnt vmcnt(0)
 // Every asm store of the kernels therefore carries its two wait states inside the statement (APE_STORE_TAIL); tools/check_mfma_hazards.py
 // scans for a wide asm store whose data a VALU instruction writes too early and fails the build on it.
 #define APE_STORE_TAIL "\n\ts_nop 1"
+
+// the publish store of a 16-byte piece through the SAME scalar descriptor tuple as the gathers (a second, compiler-built copy of it costs
+// four more scalar registers in kernels that already spill them); WT: `sc1` = the write-through form for clusters that span XCDs
+template <bool WT>
+__device__ __forceinline__ void store_16(ape_desc_t v, unsigned voff, ape_desc_t rsrc) {
+    if constexpr (WT) asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen sc1" APE_STORE_TAIL :: "v"(v), "v"(voff), "s"(rsrc) : "memory");
+    else asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" APE_STORE_TAIL :: "v"(v), "v"(voff), "s"(rsrc) : "memory");
+}
+
+// One LDS-DMA wave-instruction: 64 lanes x 16 bytes from the buffer (lane offset `voff`, uniform `soff`) to 1 KiB of LDS at the wave-uniform
+// byte address `lds_addr`; sc1 = L1-bypassing, like every load of handed-off bytes.  M0 is written in the same statement that reads it (the
+// compiler does not preserve it across statements), and the s_nop between the two is the only thing the two forms differ in:
+//   * dma_1k, `s_nop 3`: with the s_mov in front of it the five wait states between a VALU write of a scalar register and a vector-memory
+//     instruction that reads it.  hipcc reloads a spilled descriptor or offset by v_readlane_b32 and may do so right in front of the
+//     statement, into which it does not look.  Safe wherever it stands: the form to take unless the three s_nop cycles are measured to cost.
+//   * dma_1k_tight, `s_nop 0`: the one wait state an M0 write needs in front of the LDS-DMA that reads it, nothing for a reload.  For copies
+//     inside or between MFMA spans of kernels whose descriptor and offsets come from scalar arithmetic at that point (in lstm_cluster32.hip's
+//     sections `s_nop 3` in eight copies cost 4.7 us per launch at 1024 x 64).  That no reload stands in front is not a property of the
+//     source: tools/check_mfma_hazards.py scans every build for the adjacency and fails it, and the answer then is dma_1k.
+__device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, ape_desc_t rsrc, unsigned soff) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
+                 :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
+__device__ __forceinline__ void dma_1k_tight(unsigned lds_addr, unsigned voff, ape_desc_t rsrc, unsigned soff) {
+    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
+                 :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
+}
+
+// a uniform value laundered through an empty asm, for the LDS base of the DMA pieces at every use: hipcc otherwise hoists all the
+// `base + k * 4096` sums of a section out of the loop, runs out of scalar registers and parks them in VGPR lanes -- a v_readlane_b32 in
+// front of every copy (lstm_upper32.hip)
+__device__ __forceinline__ unsigned opaque(unsigned v) { asm volatile("" : "+s"(v)); return v; }

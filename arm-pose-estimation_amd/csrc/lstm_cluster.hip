@@ -33,6 +33,7 @@
 //     accumulator registers, so activations and the c/h update are lane-local and spread over all 64 lanes.
 #include "ape_internal.h"
 #include "async_look.h"
+#include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
 // k-block schedule of the exchange work under the MFMAs (see the phase loop); tunable at build time

@@ -27,65 +27,12 @@
 
 #include "ape_internal.h"
 #include "async_look.h"
+#include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-constexpr unsigned SPIN_LIMIT = 1u << 22;
-
-__device__ __forceinline__ float sigm(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
-__device__ __forceinline__ float tanh_(float v) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.885390081777927f * v)) - 1.0f; }
-
-// v_mfma_f32_16x16x4_f32: A = a weight register (row lane & 15 = unit * 4 + gate), B = an activation (column lane & 15 = window of
-// the row tile), k = lane >> 4.  hipcc does not model an asm MFMA's result hazard: accumulators are read only behind mfma16_last().
-// (AG: the weight lives in an accumulation register, read by the matrix core directly.  Never let the compiler park an operand of
-//  these there by itself: its v_accvgpr_read right in front of the MFMA is a VALU write -> SrcA read without the wait states the
-//  hardware needs, which hipcc cannot insert around inline asm -- seen as the first row tile of the top layer off by 2e-3.)
-template <bool AG>
-__device__ __forceinline__ void mfma16(f32x4& acc, float w, float a) {
-    if constexpr (AG) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(a));
-    else asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(a));
-}
-// the last MFMA of a span that ends a section, with the drain in the SAME statement: the compiler, which takes an asm's result for ready,
-// puts the phi copies of a branch merge right behind the MFMA otherwise (seen: the second row tile one k-step short, 1e-4)
-template <bool AG>
-__device__ __forceinline__ void mfma16_last(f32x4& acc, float w, float a) {
-    if constexpr (AG) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0\n\ts_nop 15" : "+v"(acc) : "a"(w), "v"(a));
-    else asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0\n\ts_nop 15" : "+v"(acc) : "v"(w), "v"(a));
-}
-
-// NB k-blocks of 16: acc += W (registers w[w0 + 4 kb + j]) x activations (LDS: block kb at src + kb * stride, this lane's 16 bytes),
-// fragments fetched one block ahead; mid(kb) behind block kb, fine(4 kb + j) behind every single MFMA
-template <int NB, bool AG, bool DR, int NW, typename Mid, typename Fine>
-__device__ __forceinline__ void span16(f32x4& acc, const float* __restrict__ src, int stride, const float (&w)[NW], int w0, Mid&& mid, Fine&& fine) {
-    f32x4 a0 = *reinterpret_cast<const f32x4*>(src);
-    f32x4 a1 = a0;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-        if (kb + 1 < NB) a1 = *reinterpret_cast<const f32x4*>(src + stride * (kb + 1));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (DR && kb == NB - 1 && j == 3) mfma16_last<AG>(acc, w[w0 + 4 * kb + j], a0[j]);
-            else {
-                mfma16<AG>(acc, w[w0 + 4 * kb + j], a0[j]);
-                fine(4 * kb + j);
-            }
-        }
-        mid(kb);
-        a0 = a1;
-    }
-}
-
-__device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 rsrc, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
-                 :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
-template <bool WT>
-__device__ __forceinline__ void store_16(u32x4 v, unsigned voff, u32x4 rsrc) {
-    if constexpr (WT) asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen sc1" APE_STORE_TAIL :: "v"(v), "v"(voff), "s"(rsrc) : "memory");
-    else asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" APE_STORE_TAIL :: "v"(v), "v"(voff), "s"(rsrc) : "memory");
-}
+// (mfma_stream.h: sigm / tanh_, mfma16 / mfma16_last and span16 with its `mid` and `fine` hooks; async_look.h: dma_1k_tight, store_16)
 // (the flag looks: LDS-DMA into the wave's landing zone, async_look.h -- no destination register)
 
 template <int H, int L, int KX, int RT>
@@ -233,6 +180,8 @@ __global__ __launch_bounds__(256 * RT, 3 - RT) void ape_lstm_cluster16(const Clu
 #pragma unroll
     for (int l = 0; l < L; ++l) cst[l] = 0.0f;
 
+    // (ape_make_desc spelled out: through the helper hipcc orders a few scalar selects of this kernel differently, and the rule for moving
+    //  these primitives into headers was byte-identical device code -- profiles/mfma_stream_header.md)
     const unsigned long long hx_addr = reinterpret_cast<unsigned long long>(p.hx);
     u32x4 hx_desc;
     hx_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)hx_addr);
@@ -291,14 +240,13 @@ __global__ __launch_bounds__(256 * RT, 3 - RT) void ape_lstm_cluster16(const Clu
             __builtin_amdgcn_s_sleep(1);
         }
     };
-    auto opaque = [](unsigned v) -> unsigned { asm volatile("" : "+s"(v)); return v; };
     const unsigned dma_voff = (unsigned)(lane * 16);
     const unsigned wave_kib = (unsigned)(wave * 1024);
     // slices of layer l, step `step` -> its LDS buffer; wave w copies KiB w, w + 4, ...
     auto issue_piece = [&](int l, int step, int k) {
         const unsigned src = hx_base(l, step & 1) + wave_kib + (unsigned)(k * NWV * 1024);
         const unsigned buf = (unsigned)(l < L - 1 ? 2 * l + (step & 1) : 2 * (L - 1));
-        dma_1k(opaque(hbase_lds + wave_kib) + buf * SET_BYTES + (unsigned)(k * NWV * 1024), dma_voff, hx_desc, src);
+        dma_1k_tight(opaque(hbase_lds + wave_kib) + buf * SET_BYTES + (unsigned)(k * NWV * 1024), dma_voff, hx_desc, src);
     };
     // The flag of a publish is raised per MEMBER, by the last of its waves whose store has drained (an arrival counter per layer in LDS), as
     // ONE store instruction over the member's NWV flag words: 64 waves each storing its own word of the same two cache lines at about the

@@ -37,13 +37,10 @@
 
 #include "ape_internal.h"
 #include "async_look.h"
+#include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
 namespace {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-constexpr unsigned SPIN_LIMIT = 1u << 22;
 
 // diagnostic builds: timeline of a short launch (cluster 0, member 0, thread 0) in dbg_wg[256 + i] -- 0 entry, 1 rendezvous done, 2 step 0
 // of layer 0 and the weights done, 8 + 2 * (2 * ph + l) / + 1: section (ph, l) behind its top barrier / at its end, 4 final gather, 5 head
@@ -53,44 +50,14 @@ constexpr unsigned SPIN_LIMIT = 1u << 22;
 #define C32_TL(i) do {} while (0)
 #endif
 
-// hardware v_exp_f32 (2^x) and v_rcp_f32, both ~1 ulp -- the formulas of the other kernels (lstm_cluster_common.h)
-__device__ __forceinline__ float sigm(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
-__device__ __forceinline__ float tanh_(float v) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.885390081777927f * v)) - 1.0f; }
+// (mfma_stream.h: sigm / tanh_, mfma32 -- v_mfma_f32_32x32x2_f32 --, mfma_drain and span32, the f32 form of layer 0's input columns)
 
-// v_mfma_f32_32x32x2_f32 with the weight operand (A) in the accumulator file (AG) or in an architectural VGPR.
-// hipcc does not model an asm MFMA's result hazard: the accumulators are read only behind mfma_drain(), which takes
-// them as in/out operands so that nothing that reads them can be scheduled above it.
-template <bool AG>
-__device__ __forceinline__ void mfma32(f32x16& acc, float w, float a) {
-    if constexpr (AG) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(a));
-    else asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(a));
-}
-__device__ __forceinline__ void mfma_drain(f32x16& acc) { asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc)); }
 // v_mfma_f32_32x32x16_f16 on the same accumulator: the recurrent products.  A 32x32x2_f32 in front of it on the same, fully
 // overlapping accumulator needs no wait states (SrcC = the previous vDst exactly; hipcc's hazard recognizer pads none for the builtins)
 template <bool AG>
-__device__ __forceinline__ void mfma16(f32x16& acc, const u32x4& w, const u32x4& b) {
+__device__ __forceinline__ void mfma32_f16(f32x16& acc, const u32x4& w, const u32x4& b) {
     if constexpr (AG) asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(b));
     else asm volatile("v_mfma_f32_32x32x16_f16 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(b));
-}
-
-// NB k-blocks of 8: acc += W (registers w[w0 ...]) x activations (LDS, one ds_read_b128 per block: this lane's window,
-// units 4 hh .. 4 hh + 3 of the block; `stride` floats between blocks), fragments fetched two blocks ahead.
-// `mid(kb)` runs after the MFMAs of block kb (kb a constant after unrolling): the caller hangs exchange work there.
-template <int NB, bool AG, int NW, typename Mid>
-__device__ __forceinline__ void span32(f32x16& acc, const float* __restrict__ src, int stride, const float (&w)[NW], int w0, Mid&& mid) {
-    f32x4 a0 = *reinterpret_cast<const f32x4*>(src);
-    f32x4 a1 = (NB > 1) ? *reinterpret_cast<const f32x4*>(src + stride) : a0;
-    f32x4 a2 = a1;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-        if (kb + 2 < NB) a2 = *reinterpret_cast<const f32x4*>(src + stride * (kb + 2));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mfma32<AG>(acc, w[w0 + 4 * kb + j], a0[j]);
-        mid(kb);
-        a0 = a1;
-        a1 = a2;
-    }
 }
 
 // NS K = 16 slices of h columns in the split form: acc += W_hi h_hi + W_hi h_lo + W_lo h_hi (each f16 x f16 product exact in the f32
@@ -100,7 +67,7 @@ __device__ __forceinline__ void span32(f32x16& acc, const float* __restrict__ sr
 // (conflict-free: 16 consecutive windows per lane group), fetched two slices ahead.  `mid(q)` runs with q = 2 s behind the second
 // MFMA of slice s and q = 2 s + 1 behind the third: the k-block numbering of the f32 form (one slice = two blocks of 8).
 template <int NS, bool AG, int NG, typename Mid>
-__device__ __forceinline__ void span16(f32x16& acc, const float* __restrict__ src, const u32x4 (&w)[NG], int g0, Mid&& mid) {
+__device__ __forceinline__ void span32_f16(f32x16& acc, const float* __restrict__ src, const u32x4 (&w)[NG], int g0, Mid&& mid) {
     constexpr int SL = 2 * 2 * 32 * 4;      // floats per slice (two blocks)
     u32x4 h0 = *reinterpret_cast<const u32x4*>(src), l0 = *reinterpret_cast<const u32x4*>(src + 128);
     u32x4 h1 = (NS > 1) ? *reinterpret_cast<const u32x4*>(src + SL) : h0, l1 = (NS > 1) ? *reinterpret_cast<const u32x4*>(src + SL + 128) : l0;
@@ -111,10 +78,10 @@ __device__ __forceinline__ void span16(f32x16& acc, const float* __restrict__ sr
             h2 = *reinterpret_cast<const u32x4*>(src + SL * (s + 2));
             l2 = *reinterpret_cast<const u32x4*>(src + SL * (s + 2) + 128);
         }
-        mfma16<AG>(acc, w[g0 + 2 * s], h0);
-        mfma16<AG>(acc, w[g0 + 2 * s], l0);
+        mfma32_f16<AG>(acc, w[g0 + 2 * s], h0);
+        mfma32_f16<AG>(acc, w[g0 + 2 * s], l0);
         mid(2 * s);
-        mfma16<AG>(acc, w[g0 + 2 * s + 1], h0);
+        mfma32_f16<AG>(acc, w[g0 + 2 * s + 1], h0);
         mid(2 * s + 1);
         h0 = h1; l0 = l1;
         h1 = h2; l1 = l2;
@@ -143,8 +110,7 @@ __device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 r
         //  branches gone it kept layer 1's own judge there, from the head of the input span to the branch behind it -- the eight pieces in between
         //  cleared it, and every section took the blocking refill: same results, 4 % slower; tests/tools/counts_c32.py showed 60 of 60)
     } else {
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
-                     :: "s"(lds_addr + (unsigned)piece_bytes), "v"(voff), "s"(rsrc), "s"(soff + (unsigned)piece_bytes) : "memory");
+        ::dma_1k(lds_addr + (unsigned)piece_bytes, voff, rsrc, soff + (unsigned)piece_bytes);     // (async_look.h: the `s_nop 3` form)
     }
 }
 
@@ -351,12 +317,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
 
     // exchange buffer: descriptor for the compiler's stores, and the same words as a scalar tuple for the DMA asm
     const __amdgpu_buffer_rsrc_t hx_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.hx, 0, (int)p.hx_bytes, 0x00020000);
-    const unsigned long long hx_addr = reinterpret_cast<unsigned long long>(p.hx);
-    u32x4 hx_desc;
-    hx_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)hx_addr);
-    hx_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(hx_addr >> 32) & 0xFFFFu);
-    hx_desc[2] = __builtin_amdgcn_readfirstlane((unsigned)p.hx_bytes);
-    hx_desc[3] = 0x00020000u;
+    const u32x4 hx_desc = ape_make_desc(p.hx, (unsigned)p.hx_bytes);
     unsigned* const flags_of = p.xflags + (size_t)cluster * L * NFL;       // [layer][member*4 + wave] epoch = steps published
     // the looks at those flags (async_look.h): descriptor over the flag words, this cluster's byte offset, the lane's flag, the wave's zone
     const ape_desc_t fl_desc = ape_make_desc(p.xflags, (unsigned)((gridDim.x / GH) * L * NFL * sizeof(unsigned)));
@@ -420,7 +381,6 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
     const unsigned dma_voff = (unsigned)(lane * 16);
     // (blocking forms: the per-wave offset is laundered through an empty asm at every use, or hipcc hoists the sums of all pieces of all
     //  section forms out of the loop and runs out of scalar registers -- lstm_upper32.hip)
-    auto opaque = [](unsigned v) -> unsigned { asm volatile("" : "+s"(v)); return v; };
     const unsigned wave_kib = (unsigned)(wave * 1024);
     auto issue_piece = [&](auto hot_tag, int l, int step, int k) {       // slices of layer l, step `step` -> hb0[step parity] / hb1
         constexpr bool HOT = decltype(hot_tag)::value;
@@ -484,7 +444,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
         }
     };
     const unsigned pub_off = (unsigned)((((member * 4 + wave) * MR + n) * 8 + 4 * hh) * sizeof(float));    // this lane's 16 bytes of a slice set
-    // The split exchange layout (what span16 reads): per block of 8 units [hi, lo][window][8 units as f16].  A lane's four fresh h
+    // The split exchange layout (what span32_f16 reads): per block of 8 units [hi, lo][window][8 units as f16].  A lane's four fresh h
     // (units 4 hh .. 4 hh + 3) become f16 hi / lo of h * 2^APE_C32_HSHIFT (exact scaling; |h| <= 1), two dwords each; one
     // v_permlane32_swap per dword pair gives lanes 0-31 the hi of all eight units [own | upper's] and lanes 32-63 the lo [lower's | own]:
     // one 16-byte store per lane, at window n of the hi (hh = 0) / lo (hh = 1) half.
@@ -818,7 +778,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
             const int frag = hh * 2 * MR * 4 + n * 4;             // this lane's hi fragment of slice 0: block hh, window n
             if constexpr (l == 0) {
                 if (!from_park) span32<BXU, false, 4 * BXU>(acc, xin + (ENDS ? 0 : (t & 1) * (MR * SX)) + n * SX + hh * 4, 8, w0, 0, [&](int q) { mid(q); });
-                if (ST || t > 0) span16<BH / 2, false, NW0 / 4 - BX>(acc, hb0 + ((t - 1) & 1) * HL + frag, w0h, 0, [&](int q) { mid(BXU + q); });
+                if (ST || t > 0) span32_f16<BH / 2, false, NW0 / 4 - BX>(acc, hb0 + ((t - 1) & 1) * HL + frag, w0h, 0, [&](int q) { mid(BXU + q); });
             } else if constexpr (MODE == 3) {
                 // input span: the common hooks (flag owed at QF, the look for the NEXT section at QP) + the look at the OWN layer's flags at
                 // QO, the judge four blocks on, the gather behind it; outside the steady state a second look twelve blocks after the first
@@ -839,14 +799,14 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
                     // (UG: the own gather's source base, once; the judge above decides only whether the wait between the spans trusts the copy)
                     unsigned own_src = hx_base(l, (t - 1) & 1) + wave_kib;
                     if constexpr (UG) asm volatile("" : "+s"(own_src));
-                    span16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) {
+                    span32_f16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) {
                         mid(q);
                         if constexpr (UG) {
                             if (q < NDMA) dma_1k<true>(hb1_lds + wave_kib, dma_voff, hx_desc, own_src, q * 4096);
                         } else if (q < NDMA && got1) issue_piece(HOT, l, t - 1, q);
                     });
                 } else
-                span16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) {
+                span32_f16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) {
                     mid(q);
                     if (q == QO) look_issue(look_lds, look_voff, fl_desc, fl_off + (unsigned)(l * NFL * sizeof(unsigned)));
                     if (q == QO + 3) {
@@ -897,10 +857,10 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster32(const ClusterParams
                 if (ST) lw_n[0] += 1u;
 #endif
                 if (ctl[0] != 0) return false;
-                span16<BH / 2, true, NW1 / 4>(acc, hb1 + frag, w1, BH, [&](int q) { mid(BH + q); });
+                span32_f16<BH / 2, true, NW1 / 4>(acc, hb1 + frag, w1, BH, [&](int q) { mid(BH + q); });
             } else {
-                span16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) { mid(q); });
-                if (ST || t > 0) span16<BH / 2, true, NW1 / 4>(acc, hb1 + frag, w1, BH, [&](int q) { mid(BH + q); });
+                span32_f16<BH / 2, true, NW1 / 4>(acc, hb0 + (t & 1) * HL + frag, w1, 0, [&](int q) { mid(q); });
+                if (ST || t > 0) span32_f16<BH / 2, true, NW1 / 4>(acc, hb1 + frag, w1, BH, [&](int q) { mid(BH + q); });
                 // (a section without a recurrent span -- step 0 of the long-window instantiation -- issues its look at block QP and never
                 //  reaches the judge at QJ.  With a register destination that look stayed in flight over whatever hipcc gave the register to
                 //  next: 2-4 % of the launches beside a memory-bound kernel returned a 32-window cluster off by 1e-2 at step 0 of layer 1,

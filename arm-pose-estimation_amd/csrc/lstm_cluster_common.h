@@ -1,6 +1,6 @@
 // Device helpers shared by the f32 cluster kernels (lstm_cluster.hip, lstm_cluster_duo.hip): the AGPR-pinned
-// v_mfma_f32_16x16x4_f32 wrapper, the double-buffered layer-step MFMA loop with its per-k-block hook, the gate
-// non-linearity.  Included inside each translation unit's anonymous namespace.
+// v_mfma_f32_16x16x4_f32 wrapper, the double-buffered layer-step MFMA loop with its per-k-block hook (the gate
+// non-linearity: mfma_stream.h).  Included inside each translation unit's anonymous namespace.
 #pragma once
 
 // Diagnostic build (make diag: -DAPE_CLUSTER_STAMPS): per-section shader-cycle sums of workgroup 0,
@@ -28,17 +28,9 @@
 #define STAMP_END(k) do {} while (0)
 #endif
 
-
-constexpr unsigned SPIN_LIMIT = 1u << 22;   // bounded polls (~seconds) before giving up
-
-__device__ __forceinline__ float gate_act(float v, bool is_tanh) {
-    // sigmoid(v), or tanh(v) = 2*sigmoid(2v) - 1 on the g-gate lanes: one branch-free formula so
-    // all 64 lanes (four different gates per 16-lane row) stay converged
-    // hardware v_exp_f32 (2^x) and v_rcp_f32, both ~1 ulp: absolute error of the activation ~1e-7
-    const float e = __builtin_amdgcn_exp2f((is_tanh ? -2.885390081777927f : -1.4426950408889634f) * v);
-    const float s = __builtin_amdgcn_rcpf(1.0f + e);
-    return is_tanh ? 2.0f * s - 1.0f : s;
-}
+// (SPIN_LIMIT, gate_act.  This file is included INSIDE a translation unit's anonymous namespace: the translation unit includes mfma_stream.h
+//  itself, at file scope, and this line then only says what is used from it)
+#include "mfma_stream.h"
 
 // value of the lane D columns up inside the same 16-lane row (wrapping): DPP row rotate right by 16-D
 // (row_ror:n -- lane i reads lane (i - n) mod 16), no LDS round trip

@@ -19,19 +19,13 @@
 // Reference semantics are unchanged (estimate/nn_models.py:169-174,180-189); only the storage precision of
 // W, x and h is reduced, so parity is to a STATED tolerance (tests: <= 5e-3 abs on the NN targets).
 #include "ape_internal.h"
+#include "mfma_stream.h"   // SPIN_LIMIT, gate_act
 #include "../../include/ape_hip.h"
 
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-constexpr unsigned SPIN_LIMIT = 1u << 22;
-
-__device__ __forceinline__ float gate_act(float v, bool is_tanh) {
-    const float e = __builtin_amdgcn_exp2f((is_tanh ? -2.885390081777927f : -1.4426950408889634f) * v);
-    const float s = __builtin_amdgcn_rcpf(1.0f + e);
-    return is_tanh ? 2.0f * s - 1.0f : s;
-}
 
 template <int D>
 __device__ __forceinline__ float row_rot_up(float x) {

@@ -35,20 +35,12 @@
 
 #include "ape_internal.h"
 #include "async_look.h"
+#include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
 namespace {
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-constexpr unsigned SPIN_LIMIT = 1u << 22;
-
-__device__ __forceinline__ float gate_act(float v, bool is_tanh) {
-    const float e = __builtin_amdgcn_exp2f((is_tanh ? -2.885390081777927f : -1.4426950408889634f) * v);
-    const float s = __builtin_amdgcn_rcpf(1.0f + e);
-    return is_tanh ? 2.0f * s - 1.0f : s;
-}
-
 // v_mfma_f32_16x16x32_f16 with the A operand (a weight fragment that lives in AGPRs for the whole launch) pinned to
 // the accumulator register file, so that the 256 architectural VGPRs stay free for a whole section's activation
 // fragments (fetched up front: a single ds_read_b128 feeds only two of these 16-cycle MFMAs, so reads issued one
@@ -71,13 +63,7 @@ __device__ __forceinline__ void load_frags(f32x4 (&a)[NQ], const _Float16* __res
 #pragma unroll
     for (int q = 0; q < NQ; ++q) a[q] = *reinterpret_cast<const f32x4*>(src + stride * q);
 }
-// one LDS-DMA wave-instruction: 64 lanes x 16 bytes from the buffer (lane offset `voff`, uniform `soff`) to 1 KiB of LDS at
-// the wave-uniform byte address `lds_addr`; sc1 = L1-bypassing, like every load of handed-off bytes.  M0 is written in the
-// same statement that reads it (the compiler does not preserve it across statements).
-__device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 rsrc, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
-                 :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
+// (the 1 KiB LDS-DMA copies: async_look.h, dma_1k_tight)
 // acc[t] += W_t (registers) x A over NQ k-blocks
 template <int NTW, int NQ, int NW>
 __device__ __forceinline__ void span(f32x4 (&acc)[NTW], const f32x4 (&a)[NQ], const f32x4 (&w)[NTW][NW], int w_off) {
@@ -223,12 +209,7 @@ __global__ __launch_bounds__(256, (UPW == 4 ? 2 : 1)) void ape_lstm_cluster_f16v
 
     // exchange buffer: descriptor for the compiler's loads / stores, and the same words as a scalar tuple for the DMA asm
     const __amdgpu_buffer_rsrc_t hx_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.hx, 0, (int)p.hx_bytes, 0x00020000);
-    const unsigned long long hx_addr = reinterpret_cast<unsigned long long>(p.hx);
-    u32x4 hx_desc;
-    hx_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)hx_addr);
-    hx_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(hx_addr >> 32) & 0xFFFFu);
-    hx_desc[2] = __builtin_amdgcn_readfirstlane((unsigned)p.hx_bytes);
-    hx_desc[3] = 0x00020000u;
+    const u32x4 hx_desc = ape_make_desc(p.hx, (unsigned)p.hx_bytes);
     unsigned* const flags_of = p.xflags + (size_t)cluster * NS * NFL;      // [set][member*4 + wave] epoch = phases published
     const ape_desc_t fl_desc = ape_make_desc(p.xflags, (unsigned)((gridDim.x / GH) * NS * NFL * sizeof(unsigned)));
     const unsigned fl_off = (unsigned)(cluster * NS * NFL * sizeof(unsigned));
@@ -371,7 +352,7 @@ __global__ __launch_bounds__(256, (UPW == 4 ? 2 : 1)) void ape_lstm_cluster_f16v
     auto issue_gather = [&](int s, int par) {
         const unsigned src = hx_base(s, par) + (unsigned)(wave * 1024), dst = hbuf_lds + (unsigned)(s * L * HL * 2 + wave * 1024);
 #pragma unroll
-        for (int k = 0; k < NDMA; ++k) dma_1k(dst + (unsigned)(k * 4096), dma_voff, hx_desc, src + (unsigned)(k * 4096));
+        for (int k = 0; k < NDMA; ++k) dma_1k_tight(dst + (unsigned)(k * 4096), dma_voff, hx_desc, src + (unsigned)(k * 4096));
     };
     // the flag a wave owes for the slices it stored last: raised once that store has drained
     int pend_set = -1;

@@ -136,12 +136,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster_small(const ClusterPa
     for (int l = 0; l < L; ++l) cst[l] = 0.0f;
 
     const __amdgpu_buffer_rsrc_t hx_rsrc = __builtin_amdgcn_make_buffer_rsrc(p.hx, 0, (int)p.hx_bytes, 0x00020000);
-    const unsigned long long hx_addr = reinterpret_cast<unsigned long long>(p.hx);
-    u32x4 hx_desc;                                 // the same descriptor as a scalar tuple for the polling loads' asm
-    hx_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)hx_addr);
-    hx_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(hx_addr >> 32) & 0xFFFFu);
-    hx_desc[2] = __builtin_amdgcn_readfirstlane((unsigned)p.hx_bytes);
-    hx_desc[3] = 0x00020000u;
+    const u32x4 hx_desc = ape_make_desc(p.hx, (unsigned)p.hx_bytes);                                 // the same descriptor as a scalar tuple for the polling loads' asm
     // exchange: 8-byte granules {h, tag} at [layer][step parity][row][unit]; tag = launch number << 12 | phase + 1.  A granule
     // is written with one 8-byte store and is valid exactly when its tag is the awaited one, so the data IS the flag: one
     // hop (store -> polled load) per phase instead of store -> acknowledge -> flag -> poll -> copy.

@@ -3,13 +3,13 @@
 // register-resident GEMV spans.
 #pragma once
 #include "ape_internal.h"
+#include "async_look.h"    // ape_make_desc
+#include "mfma_stream.h"   // u32x4, SPIN_LIMIT, gate_act
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
 typedef unsigned u32x2 __attribute__((__vector_size__(2 * sizeof(unsigned))));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-constexpr unsigned SPIN_LIMIT = 1u << 22;
 constexpr int MR = 4;                      // rows per cluster of the small-batch kernel (row = lane group)
 
 // NI polling loads (16 bytes per lane, L1-bypassing) and the wait for them in ONE statement: the compiler knows nothing of the
@@ -37,11 +37,6 @@ __device__ __forceinline__ void poll_granules(u32x4 (&v)[NI], const unsigned (&o
                      : "v"(off[0]), "v"(off[1]), "v"(off[2]), "v"(off[3]), "s"(rsrc) : "memory");
 }
 
-__device__ __forceinline__ float gate_act(float v, bool is_tanh) {
-    const float e = __builtin_amdgcn_exp2f((is_tanh ? -2.885390081777927f : -1.4426950408889634f) * v);
-    const float s = __builtin_amdgcn_rcpf(1.0f + e);
-    return is_tanh ? 2.0f * s - 1.0f : s;
-}
 
 // value of lane (quad base + K) for every lane of the quad (DPP quad_perm broadcast)
 template <int K>

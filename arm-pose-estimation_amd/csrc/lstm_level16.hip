@@ -39,55 +39,16 @@
 #include "ape_internal.h"
 #include "ape_plan.h"
 #include "async_look.h"
+#include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
 namespace {
 
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-constexpr unsigned SPIN_LIMIT = 1u << 22;
-
-__device__ __forceinline__ float sigm(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
-__device__ __forceinline__ float tanh_(float v) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.885390081777927f * v)) - 1.0f; }
-
-// v_mfma_f32_16x16x4_f32: A = a weight register (row lane & 15 = unit * 4 + gate), B = an activation (column lane & 15 = window),
-// k = lane >> 4.  AG: the weight lives in an accumulation register, named as such ("a") -- never parked there by the compiler
-// (its v_accvgpr_read in front of an asm MFMA has no wait states: lstm_cluster16.hip)
-template <bool AG>
-__device__ __forceinline__ void mfma16(f32x4& acc, float w, float a) {
-    if constexpr (AG) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(a));
-    else asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(a));
-}
-// the last MFMA of a level-section, with the drain in the SAME statement (hipcc takes an asm's result for ready)
-template <bool AG>
-__device__ __forceinline__ void mfma16_last(f32x4& acc, float w, float a) {
-    if constexpr (AG) asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0\n\ts_nop 15" : "+v"(acc) : "a"(w), "v"(a));
-    else asm volatile("v_mfma_f32_16x16x4_f32 %0, %1, %2, %0\n\ts_nop 15" : "+v"(acc) : "v"(w), "v"(a));
-}
-
-// NB k-blocks of 16: acc += W (registers w[w0 + 4 kb + j]) x activations (LDS: block kb at src + kb * stride, this lane's 16 bytes),
-// fragments fetched one block ahead; DR: the span ends the section -- its last MFMA drains.  (DR is a template argument and the caller
-// branches AROUND whole spans: a branch merge between the last MFMA and its drain is where hipcc puts phi copies of the accumulator.)
-// NB k-blocks of 16: acc += W (registers w[w0 + 4 kb + j]) x activations (LDS: block kb at src + kb * stride, this lane's 16 bytes),
-// fragments fetched one block ahead; DR: the span ends the section -- its last MFMA drains.  (DR is a template argument and the caller
-// branches AROUND whole spans: a branch merge between the last MFMA and its drain is where hipcc puts phi copies of the accumulator.)
+// (mfma_stream.h: sigm / tanh_, mfma16 / mfma16_last and span16 -- here without hooks, every span a whole one: DR is a template argument and
+//  the caller branches AROUND spans)
 // (Measured and dropped, round 6: the first fragment of every span fetched under the span in front -- 55.6 against 54.8 us at 1024 x 6, the
 //  LDS latency at a span's start is covered by the SIMD partner; two or four interleaved accumulator chains -- 55.0 / 56.8 us: the partner's
 //  hand-over instructions issue sooner between independent MFMAs, the matrix work itself gets slower by as much.)
-template <int NB, bool AG, bool DR, int NW>
-__device__ __forceinline__ void span16(f32x4& acc, const float* __restrict__ src, int stride, const float (&w)[NW], int w0) {
-    f32x4 a0 = *reinterpret_cast<const f32x4*>(src);
-    f32x4 a1 = a0;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-        if (kb + 1 < NB) a1 = *reinterpret_cast<const f32x4*>(src + stride * (kb + 1));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            if (DR && kb == NB - 1 && j == 3) mfma16_last<AG>(acc, w[w0 + 4 * kb + j], a0[j]);
-            else mfma16<AG>(acc, w[w0 + 4 * kb + j], a0[j]);
-        }
-        a0 = a1;
-    }
-}
 
 // NI polling loads (16 bytes = two {value, tag} granules per lane, L1-bypassing) and the wait for them in ONE statement: the compiler knows
 // nothing of the asynchronous return, so no use (or copy) of a result may be scheduled between a load and the wait (lstm_latency_common.h;
@@ -254,12 +215,7 @@ __global__ __launch_bounds__(512, 1) void ape_lstm_level16(const ClusterParams p
 #pragma unroll
     for (int l = 0; l < L; ++l) cst[l] = 0.0f;
 
-    const unsigned long long hx_addr = reinterpret_cast<unsigned long long>(p.hx);
-    u32x4 hx_desc;
-    hx_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)hx_addr);
-    hx_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(hx_addr >> 32) & 0xFFFFu);
-    hx_desc[2] = __builtin_amdgcn_readfirstlane((unsigned)p.hx_bytes);
-    hx_desc[3] = 0x00020000u;
+    const u32x4 hx_desc = ape_make_desc(p.hx, (unsigned)p.hx_bytes);
     // exchange: [cluster][agent 2][level parity 2][layer L][member][unit group][lane 64] granules {h of (unit lane >> 4, window lane & 15), tag}:
     // a wave publishes its 64 fresh values as 64 granules (one 8-byte write-through store per lane); nobody raises or reads a flag -- the
     // consumers poll the granules themselves until every tag names this launch and this level (one hop instead of store-ack, flag, look, gather)

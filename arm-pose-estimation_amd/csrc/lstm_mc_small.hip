@@ -201,12 +201,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_mc_small(const McSmallParams 
 
     char* const gx = p.gx + (size_t)cluster * p.gx_cluster_bytes;
     const __amdgpu_buffer_rsrc_t hx_rsrc = __builtin_amdgcn_make_buffer_rsrc(gx, 0, (int)p.gx_cluster_bytes, 0x00020000);
-    const unsigned long long hx_addr = reinterpret_cast<unsigned long long>(gx);
-    u32x4 hx_desc;
-    hx_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)hx_addr);
-    hx_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(hx_addr >> 32) & 0xFFFFu);
-    hx_desc[2] = __builtin_amdgcn_readfirstlane(p.gx_cluster_bytes);
-    hx_desc[3] = 0x00020000u;
+    const u32x4 hx_desc = ape_make_desc(gx, p.gx_cluster_bytes);
 
     // the pairs this thread collects: slot 0 = h_0 pair pr0 (fanned out to the rows of group rg); slots 1.. = pair e1 = tid + 256 (i - 1)
     // of the layers above -> (layer, row, pair of units)

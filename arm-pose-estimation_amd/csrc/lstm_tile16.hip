@@ -23,18 +23,10 @@
 //
 // Work per window: sum_l 2*4H*(in_l+H) FLOP per step.
 #include "ape_internal.h"
+#include "mfma_stream.h"   // gate_act
 #include "../../include/ape_hip.h"
 
 namespace {
-
-// sigmoid(v), or tanh(v) = 2*sigmoid(2v) - 1: hardware v_exp_f32 (2^x) and v_rcp_f32, both ~1 ulp -- the same formula
-// as the cluster kernel's (lstm_cluster_common.h), absolute error of the activation ~1e-7; the libm forms cost about
-// 10x the instructions, a fifth of a step's time beside the MFMAs
-__device__ __forceinline__ float gate_act(float v, bool is_tanh) {
-    const float e = __builtin_amdgcn_exp2f((is_tanh ? -2.885390081777927f : -1.4426950408889634f) * v);
-    const float s = __builtin_amdgcn_rcpf(1.0f + e);
-    return is_tanh ? 2.0f * s - 1.0f : s;
-}
 
 template <int NT>
 __device__ __forceinline__ void load_b(f32x4 (&b)[NT], const f32x4* __restrict__ p) {

@@ -25,40 +25,12 @@
 
 #include "ape_internal.h"
 #include "async_look.h"
+#include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-constexpr unsigned SPIN_LIMIT = 1u << 22;
-
-// v_mfma_f32_32x32x2_f32, weight operand (A) in the accumulator file (AG) or in an architectural VGPR; the accumulators are read
-// only behind mfma_drain() (hipcc does not model an asm MFMA's result hazard)
-template <bool AG>
-__device__ __forceinline__ void mfma32(f32x16& acc, float w, float a) {
-    if constexpr (AG) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(a));
-    else asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(a));
-}
-__device__ __forceinline__ void mfma_drain(f32x16& acc) { asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc)); }
-
-// NB k-blocks of 8: acc += W (registers w[w0 ...]) x activations (LDS, one ds_read_b128 per block, `stride` floats between
-// blocks), fragments fetched two blocks ahead; `mid(kb)` runs after the MFMAs of block kb (a constant after unrolling)
-template <int NB, int NW, typename Mid>
-__device__ __forceinline__ void span32(f32x16& acc, const float* __restrict__ src, int stride, const float (&w)[NW], int w0, Mid&& mid) {
-    f32x4 a0 = *reinterpret_cast<const f32x4*>(src);
-    f32x4 a1 = (NB > 1) ? *reinterpret_cast<const f32x4*>(src + stride) : a0;
-    f32x4 a2 = a1;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-        if (kb + 2 < NB) a2 = *reinterpret_cast<const f32x4*>(src + stride * (kb + 2));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mfma32<true>(acc, w[w0 + 4 * kb + j], a0[j]);
-        mid(kb);
-        a0 = a1;
-        a1 = a2;
-    }
-}
+// (mfma_stream.h: the MFMA statements, their drain and the k-block span)
 
 // a flag look that does not stall the MFMA stream: LDS-DMA into the wave's landing zone, read back behind look_landed() (async_look.h)
 // The mask words of a wave's eight units (32 bytes), requested early in a section and needed at its end.  They land in LDS, not in
@@ -83,11 +55,7 @@ __device__ __forceinline__ void store_16(u32x4 v, unsigned voff, u32x4 rsrc) {
     asm volatile("s_nop 4\n\tbuffer_store_dwordx4 %0, %1, %2, 0 offen sc1" APE_STORE_TAIL :: "v"(v), "v"(voff), "s"(rsrc) : "memory");
 #endif
 }
-// one LDS-DMA wave-instruction: 64 lanes x 16 bytes from the buffer to 1 KiB of LDS at the wave-uniform byte address `lds_addr`
-__device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 rsrc, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 3\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"        // (five wait states, as above)
-                 :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
+// (the 1 KiB LDS-DMA copies are async_look.h's dma_1k: five wait states, as above)
 
 // hook positions of a section (k-block indices 0 .. 63; see `mid` below)
 #ifndef UP128_QF
@@ -188,18 +156,10 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper128(const Upper128Params
     }
 
     // exchange buffer and input: descriptors as scalar tuples for the DMA asm
-    const unsigned long long hx_addr = reinterpret_cast<unsigned long long>(p.hx);
-    u32x4 hx_desc;
-    hx_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)hx_addr);
-    hx_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(hx_addr >> 32) & 0xFFFFu);
-    hx_desc[2] = __builtin_amdgcn_readfirstlane((unsigned)p.hx_bytes);
-    hx_desc[3] = 0x00020000u;
-    const unsigned long long xf_addr = reinterpret_cast<unsigned long long>(p.xfrag);
-    u32x4 xf_desc;
-    xf_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)xf_addr);
-    xf_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(xf_addr >> 32) & 0xFFFFu);
-    xf_desc[2] = __builtin_amdgcn_readfirstlane((unsigned)p.xfrag_bytes);
-    xf_desc[3] = 0x00020000u;
+    const u32x4 hx_desc = ape_make_desc(p.hx, (unsigned)p.hx_bytes);
+    const u32x4 xf_desc = ape_make_desc(p.xfrag, (unsigned)p.xfrag_bytes);
+    // (ape_make_desc spelled out: through the helper four instruction pairs of the diagnostic build with cycle stamps swap places, and the
+    //  rule for moving these primitives into headers was byte-identical device code in every flavour -- profiles/mfma_stream_header.md)
     const unsigned long long mb_addr = reinterpret_cast<unsigned long long>(p.maskbits);
     u32x4 mb_desc;                                               // the keep bits [n_tiles][T][unit 128], one word per (tile, step, unit)
     mb_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)mb_addr);
@@ -271,7 +231,6 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper128(const Upper128Params
     };
     // a 16 KB copy global -> LDS: wave w moves KiB w, w + 4, w + 8, w + 12; piece k on its own so that a copy can be spread over k-blocks
     const unsigned dma_voff = (unsigned)(lane * 16);
-    auto opaque = [](unsigned v) -> unsigned { asm volatile("" : "+s"(v)); return v; };     // (no hoisted address sums: lstm_upper32.hip)
     const unsigned wave_kib = (unsigned)(wave * 1024);
     // (`nrec` = the descriptor's record count: 0 turns the instruction into one that touches no memory -- zeros into an LDS buffer nobody
     //  reads before its real copy -- so that the hooks of a section need no branch on a verdict)
@@ -467,13 +426,13 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper128(const Upper128Params
             accA[4 * gate] = b1[0]; accA[4 * gate + 1] = b1[1]; accA[4 * gate + 2] = b1[2]; accA[4 * gate + 3] = b1[3];
             accB[4 * gate] = b2[0]; accB[4 * gate + 1] = b2[1]; accB[4 * gate + 2] = b2[2]; accB[4 * gate + 3] = b2[3];
         }
-        if (actA) span32<BH, 2 * NWL>(accA, xb + s * HL + frag, MR * 8, w, 0, [&](int q) { mid(q); });
+        if (actA) span32<BH, true, 2 * NWL>(accA, xb + s * HL + frag, MR * 8, w, 0, [&](int q) { mid(q); });
         else hooks(0);
-        if (recA) span32<BH, 2 * NWL>(accA, h1b + s * HL + frag, MR * 8, w, 4 * BH, [&](int q) { mid(BH + q); });
+        if (recA) span32<BH, true, 2 * NWL>(accA, h1b + s * HL + frag, MR * 8, w, 4 * BH, [&](int q) { mid(BH + q); });
         else hooks(BH);
-        if (actB) span32<BH, 2 * NWL>(accB, m1b + s * HL + frag, MR * 8, w, NWL, [&](int q) { mid(2 * BH + q); });
+        if (actB) span32<BH, true, 2 * NWL>(accB, m1b + s * HL + frag, MR * 8, w, NWL, [&](int q) { mid(2 * BH + q); });
         else hooks(2 * BH);
-        if (recB) span32<BH, 2 * NWL>(accB, h2b + s * HL + frag, MR * 8, w, NWL + 4 * BH, [&](int q) { mid(3 * BH + q); });
+        if (recB) span32<BH, true, 2 * NWL>(accB, h2b + s * HL + frag, MR * 8, w, NWL + 4 * BH, [&](int q) { mid(3 * BH + q); });
         else hooks(3 * BH);
         // (the other set idle: THIS set runs the next section too, and its top copies into buffers read above -- every wave must be
         //  through with them first; `o_more` is state, uniform over the workgroup, so the extra barrier pairs up)

@@ -30,62 +30,13 @@
 
 #include "ape_internal.h"
 #include "async_look.h"
+#include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-constexpr unsigned SPIN_LIMIT = 1u << 22;
-
-__device__ __forceinline__ float sigm(float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-1.4426950408889634f * v)); }
-__device__ __forceinline__ float tanh_(float v) { return 2.0f * __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(-2.885390081777927f * v)) - 1.0f; }
-
-// v_mfma_f32_32x32x2_f32, weight operand (A) in the accumulator file (AG) or in an architectural VGPR; the accumulators are read
-// only behind mfma_drain() (hipcc does not model an asm MFMA's result hazard)
-template <bool AG>
-__device__ __forceinline__ void mfma32(f32x16& acc, float w, float a) {
-    if constexpr (AG) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(a));
-    else asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(a));
-}
-__device__ __forceinline__ void mfma_drain(f32x16& acc) { asm volatile("s_nop 15\n\ts_nop 7" : "+v"(acc)); }
-
-// NB k-blocks of 8: acc += W (registers w[w0 ...]) x activations (LDS, one ds_read_b128 per block, `stride` floats between
-// blocks), fragments fetched two blocks ahead; `mid(kb)` runs after the MFMAs of block kb (a constant after unrolling)
-template <int NB, int NW, typename Mid>
-__device__ __forceinline__ void span32(f32x16& acc, const float* __restrict__ src, int stride, const float (&w)[NW], int w0, Mid&& mid) {
-    f32x4 a0 = *reinterpret_cast<const f32x4*>(src);
-    f32x4 a1 = (NB > 1) ? *reinterpret_cast<const f32x4*>(src + stride) : a0;
-    f32x4 a2 = a1;
-#pragma unroll
-    for (int kb = 0; kb < NB; ++kb) {
-        if (kb + 2 < NB) a2 = *reinterpret_cast<const f32x4*>(src + stride * (kb + 2));
-#pragma unroll
-        for (int j = 0; j < 4; ++j) mfma32<true>(acc, w[w0 + 4 * kb + j], a0[j]);
-        mid(kb);
-        a0 = a1;
-        a1 = a2;
-    }
-}
-
-// A flag look that does NOT stall the MFMA stream: hipcc hoists the comparison of a compiler-visible load up to the load and puts
-// `s_waitcnt vmcnt(0)` right behind it (an L2 round trip exposed in every section: found in the disassembly of round 2's kernels).
-// The look is issued as LDS-DMA into the wave's landing zone (async_look.h: no destination register for hipcc to copy or re-use while the
-// load is in flight -- round 5), read back from LDS one k-block in front of the judge.
-
-// one LDS-DMA wave-instruction: 64 lanes x 16 bytes from the buffer (lane offset `voff`, uniform `soff`) to 1 KiB of LDS at
-// the wave-uniform byte address `lds_addr`; sc1 = L1-bypassing, like every load of handed-off bytes
-// the publish store through the SAME scalar descriptor tuple as the gathers (a second, compiler-built copy of it costs four more
-// scalar registers in a kernel that already spills them); `sc1` = write-through form for clusters that span XCDs
-template <bool WT>
-__device__ __forceinline__ void store_16(u32x4 v, unsigned voff, u32x4 rsrc) {
-    if constexpr (WT) asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen sc1" APE_STORE_TAIL :: "v"(v), "v"(voff), "s"(rsrc) : "memory");
-    else asm volatile("buffer_store_dwordx4 %0, %1, %2, 0 offen" APE_STORE_TAIL :: "v"(v), "v"(voff), "s"(rsrc) : "memory");
-}
-__device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 rsrc, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
-                 :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
-}
+// (mfma_stream.h: the MFMA statements, their drain and the k-block span; async_look.h: the flag look -- LDS-DMA into the wave's landing
+//  zone, read back from LDS one k-block in front of the judge --, the publish store and the 1 KiB LDS-DMA copy)
 
 constexpr int UH = 256;                  // hidden units = input width of the layer
 constexpr int GH = 8;                    // members per cluster
@@ -188,18 +139,8 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper32(const UpperParams p) 
     // (ONE exchange buffer per form: the parity slices p.hx, or -- SEQ -- the sequence p.hseq that is both exchange and output)
     float* const ex_ptr = SEQ ? p.hseq : p.hx;
     const size_t ex_bytes = SEQ ? p.hseq_bytes : p.hx_bytes;
-    const unsigned long long hx_addr = reinterpret_cast<unsigned long long>(ex_ptr);
-    u32x4 hx_desc;
-    hx_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)hx_addr);
-    hx_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(hx_addr >> 32) & 0xFFFFu);
-    hx_desc[2] = __builtin_amdgcn_readfirstlane((unsigned)ex_bytes);
-    hx_desc[3] = 0x00020000u;
-    const unsigned long long xf_addr = reinterpret_cast<unsigned long long>(p.xfrag);
-    u32x4 xf_desc;
-    xf_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)xf_addr);
-    xf_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(xf_addr >> 32) & 0xFFFFu);
-    xf_desc[2] = __builtin_amdgcn_readfirstlane((unsigned)p.xfrag_bytes);
-    xf_desc[3] = 0x00020000u;
+    const u32x4 hx_desc = ape_make_desc(ex_ptr, (unsigned)ex_bytes);
+    const u32x4 xf_desc = ape_make_desc(p.xfrag, (unsigned)p.xfrag_bytes);
     unsigned* const flags_of = p.xflags + (size_t)cluster * 2 * NFL;         // [set][member*4 + wave] epoch = slices published
     const ape_desc_t fl_desc = ape_make_desc(p.xflags, (unsigned)((gridDim.x / GH) * 2 * NFL * sizeof(unsigned)));
     const unsigned fl_off = (unsigned)(cluster * 2 * NFL * sizeof(unsigned));
@@ -261,20 +202,19 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper32(const UpperParams p) 
     // the slices published as epoch `epoch` (>= 1) of set s -> hb[s]; SEQ: they are step t - 1 of the set's tile in the sequence buffer
     // (the LDS base is laundered through an empty asm at every use: hipcc otherwise hoists all sixteen `base + k * 4096` sums of a
     //  section out of the loop, runs out of scalar registers and parks them in VGPR lanes -- a v_readlane in front of every copy)
-    auto opaque = [](unsigned v) -> unsigned { asm volatile("" : "+s"(v)); return v; };
     const unsigned wave_kib = (unsigned)(wave * 1024);
     auto issue_h_piece = [&](int buf, int s, unsigned epoch, int tile, int t, int k) {      // -> hb[buf]; `s` names the set's exchange slots
         const unsigned dst = opaque(hb_lds + wave_kib) + (unsigned)buf * SET_BYTES + (unsigned)(k * 4096);
         if constexpr (SEQ) {
-            dma_1k(dst, dma_voff, hx_desc, (unsigned)(((size_t)tile * T + (t - 1)) * SET_BYTES) + (unsigned)(wave * 1024 + k * 4096));
+            dma_1k_tight(dst, dma_voff, hx_desc, (unsigned)(((size_t)tile * T + (t - 1)) * SET_BYTES) + (unsigned)(wave * 1024 + k * 4096));
         } else {
-            dma_1k(dst, dma_voff, hx_desc, hx_base(s, (int)((epoch - 1u) & 1u)) + (unsigned)(wave * 1024 + k * 4096));
+            dma_1k_tight(dst, dma_voff, hx_desc, hx_base(s, (int)((epoch - 1u) & 1u)) + (unsigned)(wave * 1024 + k * 4096));
         }
     };
     auto issue_x_piece = [&](int s, int tile, int t, int k) {     // input of (tile, step t) -> xb[s]: KiB wave + 4 k of its KXB
         if (wave + 4 * k >= KXB) return;
         const unsigned src = (unsigned)(((size_t)tile * T + t) * XT_BYTES) + (unsigned)(wave * 1024 + k * 4096);
-        dma_1k(opaque(xb_lds + wave_kib) + (unsigned)s * SET_BYTES + (unsigned)(k * 4096), dma_voff, xf_desc, src);
+        dma_1k_tight(opaque(xb_lds + wave_kib) + (unsigned)s * SET_BYTES + (unsigned)(k * 4096), dma_voff, xf_desc, src);
     };
     // the flag a wave owes for the slice it stored last: raised once that store has drained
     int pend_idx = -1;
@@ -441,7 +381,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper32(const UpperParams p) 
             acc[4 * gate] = bv[0]; acc[4 * gate + 1] = bv[1]; acc[4 * gate + 2] = bv[2]; acc[4 * gate + 3] = bv[3];
         }
         if (!ab_nomfma) {
-            span32<KXB, NW>(acc, xb + bx * HL + frag, MR * 8, w, 0, [&](int q) { mid(q); });
+            span32<KXB, true, NW>(acc, xb + bx * HL + frag, MR * 8, w, 0, [&](int q) { mid(q); });
             if constexpr (solo && !first) {
                 // the slices h_{t-1}: on their way since block SJ, or -- a peer was late -- fetched now; one barrier and every wave sees them
                 if (!go && !ab_noex) {
@@ -452,7 +392,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper32(const UpperParams p) 
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
                 if (!ab_nobar) bar();
             }
-            if constexpr (!first) span32<BH, NW>(acc, hb + bh * HL + frag, MR * 8, w, 4 * KXB, [&](int q) { mid(KXB + q); });
+            if constexpr (!first) span32<BH, true, NW>(acc, hb + bh * HL + frag, MR * 8, w, 4 * KXB, [&](int q) { mid(KXB + q); });
         }
         // (a section shorter than the hook schedule -- step 0 of the narrow-input form is 4 k-blocks -- runs the rest of it here)
         {

@@ -13,15 +13,14 @@
 // Same arithmetic as mlp_tile16.hip up to float32 summation order.  Eval mode, last-step rows, H = 256, two hidden layers,
 // I <= 32, O <= 32; everything else stays on mlp_tile16.hip.
 #include "ape_internal.h"
+#include "async_look.h"
+#include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 #include <cstdlib>
 
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((__vector_size__(4 * sizeof(unsigned))));
-constexpr unsigned SPIN_LIMIT = 1u << 22;
 constexpr int H = 256, KX = 32, TR = 32;            // hidden width, padded input width, rows per tile
 constexpr int NSLOT = 4;                            // ring slots per pair
 constexpr int HLF = (H / 8) * TR * 8;               // floats of one tile of activations [k-block 32][row 32][8] = 32 KB
@@ -38,11 +37,7 @@ constexpr int KB_FLAG = APE_PIPE_KB_FLAG;   // k-block of layer 1 at which the f
 //  flag during its tile i and the producer raises it during its tile i + 2: early flag + late look is the slack the consumer starts with)
 constexpr int KB_LOOK = APE_PIPE_KB_LOOK;   // k-block of layer 2 at which the next tile's flag is looked at and its copy starts
 
-template <bool AG>
-__device__ __forceinline__ void mfma32(f32x16& acc, float w, float a) {
-    if constexpr (AG) asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "a"(w), "v"(a));
-    else asm volatile("v_mfma_f32_32x32x2_f32 %0, %1, %2, %0" : "+v"(acc) : "v"(w), "v"(a));
-}
+// (mfma32: mfma_stream.h; the 1 KiB LDS-DMA copies: async_look.h, dma_1k_tight)
 // The last MFMA of a stream carries its own drain (20 wait states: its 16 passes and a margin) INSIDE its asm statement.  The
 // compiler knows nothing of an asm MFMA's latency and is free to put register copies of the accumulators right behind it (it
 // did: a v_mov_b64 of the result two instructions after the MFMA read the lanes of the last passes too early); nothing can
@@ -51,10 +46,6 @@ template <bool AG>
 __device__ __forceinline__ void mfma32_last(f32x16& acc, f32x16& other, float w, float a) {
     if constexpr (AG) asm volatile("v_mfma_f32_32x32x2_f32 %0, %2, %3, %0\n\ts_nop 15\n\ts_nop 3" : "+v"(acc), "+v"(other) : "a"(w), "v"(a));
     else asm volatile("v_mfma_f32_32x32x2_f32 %0, %2, %3, %0\n\ts_nop 15\n\ts_nop 3" : "+v"(acc), "+v"(other) : "v"(w), "v"(a));
-}
-__device__ __forceinline__ void dma_1k(unsigned lds_addr, unsigned voff, u32x4 rsrc, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen sc1 lds"
-                 :: "s"(lds_addr), "v"(voff), "s"(rsrc), "s"(soff) : "memory");
 }
 
 // NB k-blocks of 8 for two column tiles at once: acc0 / acc1 += W (registers w[w0 + ct * NWT + ...]) x activations (LDS, one
@@ -160,12 +151,7 @@ __global__ __launch_bounds__(256, 1) void ape_mlp_pipe(const PipeParams pp) {
     const int n_tiles = (p.N + TR - 1) / TR;
     unsigned* const full = pp.ctl + 256 + pair * 32;            // [slot][producer wave] = tiles of that slot written
     unsigned* const empty = full + 16;                          // [slot][consumer wave] = tiles of that slot copied out
-    const unsigned long long ring_addr = reinterpret_cast<unsigned long long>(pp.ring);
-    u32x4 ring_desc;
-    ring_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)ring_addr);
-    ring_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(ring_addr >> 32) & 0xFFFFu);
-    ring_desc[2] = __builtin_amdgcn_readfirstlane((unsigned)pp.ring_bytes);
-    ring_desc[3] = 0x00020000u;
+    const u32x4 ring_desc = ape_make_desc(pp.ring, (unsigned)pp.ring_bytes);
     auto slot_base = [&](int slot) -> unsigned { return (unsigned)(((size_t)pair * NSLOT + slot) * HLF * sizeof(float)); };
     auto bar = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
     // all 4 words of `f` (one per peer wave) have reached `want`
@@ -190,12 +176,7 @@ __global__ __launch_bounds__(256, 1) void ape_mlp_pipe(const PipeParams pp) {
     // LDS-DMA into the wave's landing zone (lane i's word goes to look_s[64 wave + i]; lanes fetch word i & 3).  Round 5: NOT into a
     // compiler-allocated register of an asm statement any more -- hipcc takes such an output for valid at once and may copy it in front of
     // the wait (tools/check_mfma_hazards.py found a v_mov of this very value there; lstm_upper128.hip on what that did to its mask words)
-    const unsigned long long ctl_addr = reinterpret_cast<unsigned long long>(pp.ctl);
-    u32x4 ctl_desc;
-    ctl_desc[0] = __builtin_amdgcn_readfirstlane((unsigned)ctl_addr);
-    ctl_desc[1] = __builtin_amdgcn_readfirstlane((unsigned)(ctl_addr >> 32) & 0xFFFFu);
-    ctl_desc[2] = (unsigned)((256 + (gridDim.x / 2) * 34) * sizeof(unsigned));
-    ctl_desc[3] = 0x00020000u;
+    const u32x4 ctl_desc = ape_make_desc(pp.ctl, (unsigned)((256 + (gridDim.x / 2) * 34) * sizeof(unsigned)));
     const unsigned look_lds = (unsigned)reinterpret_cast<unsigned long long>(look_s) + (unsigned)(wave * 256);
     const unsigned look_voff = (unsigned)((lane & 3) * 4);
     auto poll_begin = [&](const unsigned* f) {
@@ -506,7 +487,7 @@ __global__ __launch_bounds__(256, 1) void ape_mlp_pipe(const PipeParams pp) {
             const unsigned src = slot_base(it_ & (NSLOT - 1)) + (unsigned)(wave * 1024);
             const unsigned dst = inb_lds + (unsigned)((it_ & 1) * HLF * 4 + wave * 1024);
 #pragma unroll
-            for (int k = 0; k < 8; ++k) dma_1k(dst + (unsigned)(k * 4096), dma_voff, ring_desc, src + (unsigned)(k * 4096));
+            for (int k = 0; k < 8; ++k) dma_1k_tight(dst + (unsigned)(k * 4096), dma_voff, ring_desc, src + (unsigned)(k * 4096));
         };
         f32x16 c0, c1, acco;                                   // layer 2's accumulators; the output layer's
 #pragma unroll
