@@ -448,9 +448,9 @@ int check_and_reset(ape_model_t* m) {
         APE_TRY(hipDeviceSynchronize());
         return ape_fail(APE_ERR_HIP, "cluster kernel launch aborted (status %u: %s); outputs of every launch on this model "
                     "since the last successful check are invalid; the model is usable again", st,
-                    st == 1 ? "a workgroup gave up waiting for a peer -- not all workgroups of a cluster were resident"
-                    : st == 5 ? "the Monte-Carlo latency kernel gave up waiting for the members of a cluster -- not all workgroups were resident"
-                    : st >= 16 ? "the Monte-Carlo latency kernel gave up waiting for a peer's values (16 + phase)"
+                    st == APE_ABORT_SPIN ? "a workgroup gave up waiting for a peer -- not all workgroups of a cluster were resident"
+                    : st == APE_ABORT_XCD_RENDEZVOUS ? "the Monte-Carlo latency kernel gave up waiting for the members of a cluster -- not all workgroups were resident"
+                    : st >= APE_ABORT_COLLECT ? "the Monte-Carlo latency kernel gave up waiting for a peer's values (16 + phase)"
                             : "a launch found the state of an earlier aborted launch");
     }
     return APE_OK;

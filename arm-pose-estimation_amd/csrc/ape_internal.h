@@ -30,6 +30,16 @@
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// What a kernel that gives up leaves in its model's sticky status word (cluster_sync.h: ape_give_up).  Zero between
+// launches; the host tests != 0 only (ape_model_check reports the number and resets), the codes are for whoever reads that report.
+enum ApeAbort : unsigned {
+    APE_ABORT_SPIN = 1,             // a bounded spin gave up: a peer's flags, granules or XCD word never came -- not all workgroups were resident
+    APE_ABORT_TICKET = 2,           // a workgroup drew a ticket outside the grid: the counters are those of an earlier aborted launch
+    APE_ABORT_XCD_RENDEZVOUS = 5,   // lstm_mc_small.hip: the members' XCD words never came
+    APE_ABORT_BUILDER_ROW = 6,      // lstm_mc_small.hip: the feature builder's row never came
+    APE_ABORT_COLLECT = 16,         // lstm_mc_small.hip: + phase -- a peer's values of that phase never came
+};
+
 // Kernel arguments of the batch-tile LSTM kernel (passed by value).
 struct LstmParams {
     const float* x;                     // [B,T,I]
@@ -77,7 +87,7 @@ struct ClusterParams {
     unsigned* xflags;                   // [cluster][L][GH] epoch flags, zeroed before every launch
     unsigned* ticket;                   // [1] arrival counter (re-zeroed by the last workgroup out)
     unsigned* done;                     // [1] departure counter
-    unsigned* status;                   // [1] sticky: 1 = a bounded spin gave up
+    unsigned* status;                   // [1] sticky: an ApeAbort code once a launch gave up
     const float* masks;                 // [L-1,B,T,H] injected dropout masks or nullptr
     int B, T, I, O;
     int x_ring;                         // time step t lives in slot (t + x_ring) mod T of a window (0: linear)
@@ -118,7 +128,7 @@ struct UpperParams {
     size_t hx_bytes;
     unsigned* xflags;                   // [cluster][set 2][32] epoch flags, zero between launches
     unsigned* done;                     // [1] departure counter
-    unsigned* status;                   // [1] sticky: 1 = a bounded spin gave up
+    unsigned* status;                   // [1] sticky: an ApeAbort code once a launch gave up
     unsigned* xcc_slots;                // as ClusterParams::xcc_slots (class tickets + per-workgroup XCD words)
     unsigned long long* dbg_wg;         // diagnostic builds only
     float* hseq;                        // layer-0 form only: [n_tiles][T][32 KB] every step's slices (fragment order)
@@ -373,7 +383,7 @@ struct McSmallParams {
     unsigned gx_cluster_bytes;
     unsigned* seq;                      // [1] launch number of this kernel on this model (upper bits of the tags)
     unsigned* done;                     // [1] departure counter
-    unsigned* status;                   // [1] sticky: 1 = a bounded spin gave up
+    unsigned* status;                   // [1] sticky: an ApeAbort code once a launch gave up
     unsigned* xcc_slots;                // as ClusterParams::xcc_slots: words [192, 448) hold (0x10 | XCC id) of the 8 x 32 workgroups
     const float* masks;                 // injected [L-1, rows, T, H] or nullptr
     int rows;                           // n_streams * n_mc

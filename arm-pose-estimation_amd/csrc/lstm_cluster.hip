@@ -33,6 +33,7 @@
 //     accumulator registers, so activations and the c/h update are lane-local and spread over all 64 lanes.
 #include "ape_internal.h"
 #include "async_look.h"
+#include "cluster_sync.h"
 #include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
@@ -131,7 +132,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster(const ClusterParams p
             const unsigned tk = cls_mode ? __hip_atomic_fetch_add(class_ticket + cls * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
                                          : __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (tk < (cls_mode ? gridDim.x / 8 : gridDim.x)) ctl[1] = (int)tk;
-            else __hip_atomic_store(p.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else __hip_atomic_store(p.status, APE_ABORT_TICKET, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     __syncthreads();
@@ -139,9 +140,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster(const ClusterParams p
     const int ticket = __builtin_amdgcn_readfirstlane(ctl[1]);
     const int cluster = cls_mode ? (ticket / GH) * 8 + cls : ticket / GH, member = ticket % GH;
     const int row0 = cluster * MR;
-    unsigned my_xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
-    my_xcc &= 0xFu;
+    const unsigned my_xcc = ape_xcc_id();
     if (cls_mode && threadIdx.x == 0)
         __hip_atomic_store(xcc_words + cluster * GH + member, 0x10u | my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 
@@ -200,22 +199,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster(const ClusterParams p
     auto wait_flags = [&](int l, unsigned want, unsigned peeked) {
         if (diag_noex) return;
         if (__all((int)(peeked >= want))) return;                  // the prefetched look was enough
-        unsigned spins = 0;
-        while (true) {
-            unsigned v = want;
-            if (lane < NFL)
-                v = __hip_atomic_load(myflags + l * NFL + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v >= want))) return;
-            if (++spins > SPIN_LIMIT ||
-                __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                return;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
+        ape_wait_words<NFL, 2, 1>(myflags, l, want, p.status, ctl, lane);
     };
     // EVERY load of handed-off bytes is a 16-byte sc1 buffer load (bypasses this CU's L1)
     // the NGV pieces move in two halves of NGH so that at most NGH*4 registers hold in-flight slices
@@ -262,8 +246,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster(const ClusterParams p
         float* dst = (v == 0) ? hbuf + l * MR * SH : dbuf + l * MR * SH;
         *reinterpret_cast<f32x4*>(dst + g_row * SH + (k * SPP + g_sl) * 16 + 4 * g_quad) = gv[kk];
     };
-    // workgroup barrier that waits for this wave's LDS traffic only (not for loads/stores in flight to memory)
-    auto bar = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    auto bar = [&]() { ape_bar_lds(); };
     // blocking form (pipeline fill/drain and the head): wait, load, barrier (no reader of the target left), commit,
     // barrier
     auto gather_now = [&](int l, unsigned want, int par) -> bool {
@@ -355,6 +338,8 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster(const ClusterParams p
     stage_x();
     if (T > 1) fetch_x(1);
     // ---- class mode: do all members of this cluster really share an XCD?  (behind the weight loads: the peers arrive meanwhile) ------
+    // (ape_same_xcd spelled out: through the helper hipcc numbers the states of this kernel's structurised control flow differently --
+    //  profiles/cluster_sync_header.md)
     if (cls_mode && wave == 0) {
         unsigned spins = 0, v = 0u;
         while (true) {
@@ -362,10 +347,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster(const ClusterParams p
             if (lane < GH) v = __hip_atomic_load(xcc_words + cluster * GH + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (__all((int)(v != 0u))) break;
             if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                ape_give_up(ctl, p.status, APE_ABORT_SPIN, lane);
                 break;
             }
             __builtin_amdgcn_s_sleep(2);
@@ -716,9 +698,8 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster(const ClusterParams p
 #ifdef APE_CLUSTER_STAMPS
     if (tid == 0 && p.dbg_wg != nullptr && blockIdx.x < 256) {
         unsigned long long* d = p.dbg_wg + blockIdx.x * 8;
-        unsigned xcc;
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
-        d[0] = (unsigned long long)ticket; d[1] = xcc & 0xF; d[2] = wg_t0; d[3] = wg_t1; d[4] = wg_t2;
+        const unsigned xcc = ape_xcc_id();
+        d[0] = (unsigned long long)ticket; d[1] = xcc; d[2] = wg_t0; d[3] = wg_t1; d[4] = wg_t2;
         d[5] = __builtin_amdgcn_s_memrealtime();
     }
 #endif

@@ -27,6 +27,7 @@
 
 #include "ape_internal.h"
 #include "async_look.h"
+#include "cluster_sync.h"
 #include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
@@ -82,22 +83,11 @@ __global__ __launch_bounds__(256 * RT, 3 - RT) void ape_lstm_cluster16(const Clu
     unsigned* const class_ticket = p.xcc_slots + 64;
     unsigned* const xcc_words = p.xcc_slots + 64 + 8 * 16;
     const int cls = blockIdx.x & 7;
-    unsigned my_xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
-    my_xcc &= 0xFu;
+    const unsigned my_xcc = ape_xcc_id();
     if (tid < L) arrive[tid] = 0u;
-    if (tid == 0) {
-        ctl[0] = 0;
-        ctl[1] = -1;
-        if (__hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-            const unsigned tk = __hip_atomic_fetch_add(class_ticket + cls * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk < gridDim.x / 8) ctl[1] = (int)tk;
-            else __hip_atomic_store(p.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-    if (ctl[1] < 0) return;
-    const int ticket = __builtin_amdgcn_readfirstlane(ctl[1]);
+    const int drawn = ape_take_class_ticket(ctl, p.status, class_ticket, cls, tid);
+    if (drawn < 0) return;
+    const int ticket = __builtin_amdgcn_readfirstlane(drawn);
     const int cluster = (ticket / GH) * 8 + cls, member = ticket % GH;
     const int row0 = cluster * MR;
     if (tid == 0)
@@ -200,46 +190,14 @@ __global__ __launch_bounds__(256 * RT, 3 - RT) void ape_lstm_cluster16(const Clu
     stage_x();
     if (T > 1) fetch_x(1);
 
-    if (wave == 0) {                        // do all members of this cluster share an XCD?
-        unsigned spins = 0, v = 0u;
-        while (true) {
-            v = 0x10u | my_xcc;
-            if (lane < GH) v = __hip_atomic_load(xcc_words + cluster * GH + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v != 0u))) break;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        const int same = __all((int)((v & 0xFu) == my_xcc));
-        if (lane == 0) ctl[3] = same;
-    }
+    if (wave == 0) ape_same_xcd<GH, 2, APE_ABORT_SPIN>(xcc_words, cluster, my_xcc, p.status, ctl, lane);   // do all members of this cluster share an XCD?
     __syncthreads();
     if (ctl[0] != 0) return;
         // hand-over form (ape_internal.h): write-through (`sc1`) payload stores unless the caller opted into the plain in-XCD form AND the
     // members were verified to share an XCD; uniform over the cluster
     const bool in_l2 = APE_HANDOVER_IN_L2(p.flags, ctl[3] != 0);
 
-    auto wait_flags = [&](int l, unsigned want) {
-        unsigned spins = 0;
-        while (true) {
-            unsigned v = want;
-            if (lane < NFL) v = __hip_atomic_load(flags_of + l * NFL + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v >= want))) return;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                return;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    };
+    auto wait_flags = [&](int l, unsigned want) { ape_wait_words<NFL, 1, 1>(flags_of, l, want, p.status, ctl, lane); };
     const unsigned dma_voff = (unsigned)(lane * 16);
     const unsigned wave_kib = (unsigned)(wave * 1024);
     // slices of layer l, step `step` -> its LDS buffer; wave w copies KiB w, w + 4, ...
@@ -266,7 +224,7 @@ __global__ __launch_bounds__(256 * RT, 3 - RT) void ape_lstm_cluster16(const Clu
             __hip_atomic_store(flags_of + pend_idx * NFL + member * NWV + lane, pend_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         pend_idx = -1;
     };
-    auto bar = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    auto bar = [&]() { ape_bar_lds(); };
 
     // Section (ph, l) = layer l on step t = ph - l, in two spans with the workgroup barrier BETWEEN them:
     //   span A  x_t / h^{l-1}_t: in LDS since before the barrier of the section in front (layer l-1 gathered h^{l-1}_t as ITS recurrent

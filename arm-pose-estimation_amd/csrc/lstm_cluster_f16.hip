@@ -19,6 +19,7 @@
 // Reference semantics are unchanged (estimate/nn_models.py:169-174,180-189); only the storage precision of
 // W, x and h is reduced, so parity is to a STATED tolerance (tests: <= 5e-3 abs on the NN targets).
 #include "ape_internal.h"
+#include "cluster_sync.h"
 #include "mfma_stream.h"   // SPIN_LIMIT, gate_act
 #include "../../include/ape_hip.h"
 
@@ -95,7 +96,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster_f16(const ClusterPara
         if (__hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
             const unsigned tk = __hip_atomic_fetch_add(p.ticket, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (tk < gridDim.x) ctl[1] = (int)tk;
-            else __hip_atomic_store(p.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            else __hip_atomic_store(p.status, APE_ABORT_TICKET, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
     }
     __syncthreads();
@@ -141,24 +142,8 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster_f16(const ClusterPara
 
     const int g_sl = tid / TPS, g_idx = tid - g_sl * TPS;
     const int g_row = g_idx >> 1, g_hq = g_idx & 1;
-    // every wave polls for itself: have all members published phase `want`?  bounded; on give-up raises the
-    // sticky status word and the workgroup abort flag
-    auto wait_flags = [&](unsigned want) {
-        unsigned spins = 0;
-        while (true) {
-            unsigned v = want;
-            if (lane < GH) v = __hip_atomic_load(myflags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v >= want))) return;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                return;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    };
+    // every wave polls for itself: have all members published phase `want`?
+    auto wait_flags = [&](unsigned want) { ape_wait_words<GH, 1, 1>(myflags, 0, want, p.status, ctl, lane); };
     auto issue_gather = [&](int l, int par, f32x4 (&gv)[NGV]) {
         const unsigned base = hx_base(l, par);
 #pragma unroll

@@ -35,6 +35,7 @@
 
 #include "ape_internal.h"
 #include "async_look.h"
+#include "cluster_sync.h"
 #include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
@@ -148,22 +149,10 @@ __global__ __launch_bounds__(256, (UPW == 4 ? 2 : 1)) void ape_lstm_cluster_f16v
     unsigned* const class_ticket = p.xcc_slots + 64;
     unsigned* const xcc_words = p.xcc_slots + 64 + 8 * 16;
     const int cls = blockIdx.x & 7;
-    unsigned my_xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
-    my_xcc &= 0xFu;
-    // a launch that finds the sticky status word set (an earlier launch on this model aborted) leaves at once
-    if (tid == 0) {
-        ctl[0] = 0;
-        ctl[1] = -1;
-        if (__hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-            const unsigned tk = __hip_atomic_fetch_add(class_ticket + cls * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk < gridDim.x / 8) ctl[1] = (int)tk;
-            else __hip_atomic_store(p.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-    if (ctl[1] < 0) return;
-    const int ticket = __builtin_amdgcn_readfirstlane(ctl[1]);
+    const unsigned my_xcc = ape_xcc_id();
+    const int drawn = ape_take_class_ticket(ctl, p.status, class_ticket, cls, tid);
+    if (drawn < 0) return;
+    const int ticket = __builtin_amdgcn_readfirstlane(drawn);
     const int cluster = (ticket / GH) * 8 + cls, member = ticket % GH;
     const int row0 = cluster * (NS * SR);
     if (tid == 0)
@@ -306,24 +295,7 @@ __global__ __launch_bounds__(256, (UPW == 4 ? 2 : 1)) void ape_lstm_cluster_f16v
     }
 
     // ---- do all members of this cluster really share an XCD? ------------------------------------------------------
-    if (wave == 0) {
-        unsigned spins = 0, v = 0u;
-        while (true) {
-            v = 0x10u | my_xcc;
-            if (lane < GH) v = __hip_atomic_load(xcc_words + cluster * GH + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v != 0u))) break;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        const int same = __all((int)((v & 0xFu) == my_xcc));
-        if (lane == 0) ctl[3] = same;
-    }
+    if (wave == 0) ape_same_xcd<GH, 2, APE_ABORT_SPIN>(xcc_words, cluster, my_xcc, p.status, ctl, lane);
     __syncthreads();
     if (ctl[0] != 0) return;
         // hand-over form (ape_internal.h): write-through (`sc1`) payload stores unless the caller opted into the plain in-XCD form AND the
@@ -331,22 +303,7 @@ __global__ __launch_bounds__(256, (UPW == 4 ? 2 : 1)) void ape_lstm_cluster_f16v
     const bool in_l2 = APE_HANDOVER_IN_L2(p.flags, ctl[3] != 0);
 
     // every wave polls for itself: have all member waves published epoch `want` of set s?
-    auto wait_flags = [&](int s, unsigned want) {
-        unsigned spins = 0;
-        while (true) {
-            unsigned v = want;
-            if (lane < NFL) v = __hip_atomic_load(flags_of + s * NFL + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v >= want))) return;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                return;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    };
+    auto wait_flags = [&](int s, unsigned want) { ape_wait_words<NFL, 1, 1>(flags_of, s, want, p.status, ctl, lane); };
     // a set's 16 KB straight from the exchange buffer into its LDS block: wave w copies KiB w, w + 4, w + 8, w + 12
     const unsigned dma_voff = (unsigned)(lane * 16);
     auto issue_gather = [&](int s, int par) {
@@ -376,8 +333,7 @@ __global__ __launch_bounds__(256, (UPW == 4 ? 2 : 1)) void ape_lstm_cluster_f16v
             __hip_atomic_store(flags_of + pend_set * NFL + member * 4 + lane, pend_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         pend_set = -1;
     };
-    // workgroup barrier that waits for this wave's LDS traffic only (not for the publish store or a DMA in flight)
-    auto bar = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    auto bar = [&]() { ape_bar_lds(); };
 
     const int P = T + L - 1;
 #ifdef APE_CLUSTER_STAMPS

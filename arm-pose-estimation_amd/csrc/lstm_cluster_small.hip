@@ -22,6 +22,7 @@
 #include <type_traits>
 #include "ape_internal.h"
 #include "ape_plan.h"
+#include "cluster_sync.h"
 #include "lstm_latency_common.h"
 #include "fk_device.h"
 #include "../../include/ape_hip.h"
@@ -70,9 +71,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster_small(const ClusterPa
 #endif
     const int member = blockIdx.x / 8;
     const int row0 = 0;
-    unsigned my_xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
-    my_xcc &= 0xFu;
+    const unsigned my_xcc = ape_xcc_id();
     // the bias of this lane's gate row: requested ahead of the weights and consumed (see below) before the phase loop, so that
     // the loop carries no pending load of it -- otherwise the first use in the loop waits for everything but the newest
     // memory operation, i.e. for the x fetch issued at the top of the same phase
@@ -121,7 +120,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster_small(const ClusterPa
     }
     for (int i = tid; i < 2 * L * MR * SH; i += 256) hbuf[i] = 0.0f;   // h_{-1} = 0: the first step of a layer reads zeros
     // (barriers that wait for LDS traffic only: the weight loads stay in flight)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    ape_bar_lds();
     if (ctl[0] != 0) return;
 
     // head weights of this thread (16 lanes per target, H / 16 consecutive k each): requested in the last phase, under its exchange
@@ -181,27 +180,10 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster_small(const ClusterPa
     stage_x(0);
     if (T > 1) fetch_x(1);
     // ---- do all members really share an XCD?  (their words have been on the way since the weights were requested)
-    if (wave == 0) {
-        unsigned spins = 0, v = 0u;
-        while (true) {
-            v = 0x10u | my_xcc;
-            if (lane < GH) v = __hip_atomic_load(p.xcc_slots + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v != 0u))) break;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        const int same = __all((int)((v & 0xFu) == my_xcc));
-        if (lane == 0) ctl[3] = same;
-    }
+    if (wave == 0) ape_same_xcd<GH, 1, APE_ABORT_SPIN>(p.xcc_slots, 0, my_xcc, p.status, ctl, lane);
     // (a barrier that waits for LDS traffic only: the weight loads of the layers above may still be in flight, phase 0 needs
     //  layer 0's only)
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    ape_bar_lds();
     if (ctl[0] != 0) return;
     // uniform over the cluster: every member read the same GH words
     const bool in_l2 = ctl[3] != 0 && (p.flags & APE_FLAG_ANY_PLACEMENT) == 0;
@@ -337,10 +319,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_cluster_small(const ClusterPa
                 //  time a late granule costs)
                 if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
                                              __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                    if (lane == 0) {
-                        ctl[0] = 1;
-                        __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
+                    ape_give_up(ctl, p.status, APE_ABORT_SPIN, lane);
                     break;
                 }
                 if (spins > 64u) __builtin_amdgcn_s_sleep(1);

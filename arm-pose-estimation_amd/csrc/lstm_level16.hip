@@ -39,6 +39,7 @@
 #include "ape_internal.h"
 #include "ape_plan.h"
 #include "async_look.h"
+#include "cluster_sync.h"
 #include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
@@ -112,18 +113,9 @@ __global__ __launch_bounds__(512, 1) void ape_lstm_level16(const ClusterParams p
     unsigned* const class_ticket = p.xcc_slots + 64;
     const int cls = blockIdx.x & 7;
     if (tid < 16) bar_cnt[tid] = 0u;                      // (bar_cnt[0..3], fin[0..7], 4 spare words)
-    if (tid == 0) {
-        ctl[0] = 0;
-        ctl[1] = -1;
-        if (__hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-            const unsigned tk = __hip_atomic_fetch_add(class_ticket + cls * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk < gridDim.x / 8) ctl[1] = (int)tk;
-            else __hip_atomic_store(p.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-    if (ctl[1] < 0) return;
-    const int ticket = __builtin_amdgcn_readfirstlane(ctl[1]);
+    const int drawn = ape_take_class_ticket(ctl, p.status, class_ticket, cls, tid);
+    if (drawn < 0) return;
+    const int ticket = __builtin_amdgcn_readfirstlane(drawn);
     const int cluster = (ticket / GH) * 8 + cls, member = ticket % GH;
     // one-agent form (the launcher's choice for up to 16 x max_clusters rows): a cluster owns ONE row tile, agent 1 of every workgroup is idle,
     // so that 512 rows still spread over every CU (32 clusters) -- with nobody to alternate with, a level costs its matrix work plus its
@@ -237,10 +229,7 @@ __global__ __launch_bounds__(512, 1) void ape_lstm_level16(const ClusterParams p
         while (__hip_atomic_load(word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) < want) {
             if (__hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) return;
             if (++spins > SPIN_LIMIT) {
-                if (lane == 0) {
-                    __hip_atomic_store(ctl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                ape_give_up(ctl, p.status, APE_ABORT_SPIN, lane);
                 return;
             }
             __builtin_amdgcn_s_sleep(1);
@@ -366,10 +355,7 @@ __global__ __launch_bounds__(512, 1) void ape_lstm_level16(const ClusterParams p
             auto give_up = [&]() -> bool {           // bounded: somebody in the workgroup has given up, or this wave does
                 if (__hip_atomic_load(ctl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) != 0) return true;
                 if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                    if (lane == 0) {
-                        __hip_atomic_store(ctl, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                        __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
+                    ape_give_up(ctl, p.status, APE_ABORT_SPIN, lane);
                     return true;
                 }
                 __builtin_amdgcn_s_sleep(1);

@@ -29,6 +29,7 @@
 // its own launch (one workgroup's cold float64 chain behind the slowest cluster costs what the launch boundary does) and is not kept.
 #include <type_traits>
 #include "ape_internal.h"
+#include "cluster_sync.h"
 #include "lstm_latency_common.h"
 #include "parse_device.h"
 #include "../../include/ape_hip.h"
@@ -142,9 +143,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_mc_small(const McSmallParams 
         }
     }
     if (!builder && rv > 0) {
-    unsigned my_xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
-    my_xcc &= 0xFu;
+    const unsigned my_xcc = ape_xcc_id();
     unsigned* const xcc_words = p.xcc_slots + 192 + cluster * 32;
 
     // ---- layer 0 (GEMV): lane = (k-group g, column c = unit * 4 + gate) of this wave's two units
@@ -251,10 +250,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_mc_small(const McSmallParams 
                 xg2 = __builtin_amdgcn_raw_buffer_load_b64(xg_rsrc, xg_off, 0, 16 /* sc1 */);
                 if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
                                              __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                    if (lane == 0) {
-                        ctl[0] = 1;
-                        __hip_atomic_store(p.status, 6u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (6: the builder's row)
-                    }
+                    ape_give_up(ctl, p.status, APE_ABORT_BUILDER_ROW, lane);
                     break;
                 }
                 if (spins > 16u) __builtin_amdgcn_s_sleep(2);
@@ -307,28 +303,11 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_mc_small(const McSmallParams 
     fetch_x(0);
     stage_x(0);
     if (T > 1) fetch_x(1);
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    ape_bar_lds();
     if (ctl[0] != 0) return;
 
-    if (wave == 0) {                               // do all members of this cluster share an XCD?
-        unsigned spins = 0, v = 0u;
-        while (true) {
-            v = 0x10u | my_xcc;
-            if (lane < GH) v = __hip_atomic_load(xcc_words + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v != 0u))) break;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 5u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);      // (5: the XCD rendezvous)
-                }
-                break;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-        const int same = __all((int)((v & 0xFu) == my_xcc));
-        if (lane == 0) ctl[3] = same;
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+    if (wave == 0) ape_same_xcd<GH, 1, APE_ABORT_XCD_RENDEZVOUS>(xcc_words, 0, my_xcc, p.status, ctl, lane);   // do all members of this cluster share an XCD?
+    ape_bar_lds();
     if (ctl[0] != 0) return;
     const bool in_l2 = ctl[3] != 0 && (p.flags & APE_FLAG_ANY_PLACEMENT) == 0;
     auto store_granule = [&](float val, unsigned tag, unsigned off) {
@@ -505,10 +484,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_mc_small(const McSmallParams 
                 if (!__any((int)bad)) break;
                 if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u &&
                                              __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                    if (lane == 0) {
-                        ctl[0] = 1;
-                        __hip_atomic_store(p.status, 16u + (unsigned)ph, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // (16 + phase: a collect)
-                    }
+                    ape_give_up(ctl, p.status, APE_ABORT_COLLECT + (unsigned)ph, lane);
                     break;
                 }
                 if (spins > 64u) __builtin_amdgcn_s_sleep(1);

@@ -25,6 +25,7 @@
 
 #include "ape_internal.h"
 #include "async_look.h"
+#include "cluster_sync.h"
 #include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
@@ -104,21 +105,10 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper128(const Upper128Params
     unsigned* const class_ticket = p.xcc_slots + 64;
     unsigned* const xcc_words = p.xcc_slots + 64 + 8 * 16;
     const int cls = blockIdx.x & 7;
-    unsigned my_xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
-    my_xcc &= 0xFu;
-    if (tid == 0) {
-        ctl[0] = 0;
-        ctl[1] = -1;
-        if (__hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-            const unsigned tk = __hip_atomic_fetch_add(class_ticket + cls * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk < gridDim.x / 8) ctl[1] = (int)tk;
-            else __hip_atomic_store(p.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-    if (ctl[1] < 0) return;
-    const int ticket = __builtin_amdgcn_readfirstlane(ctl[1]);
+    const unsigned my_xcc = ape_xcc_id();
+    const int drawn = ape_take_class_ticket(ctl, p.status, class_ticket, cls, tid);
+    if (drawn < 0) return;
+    const int ticket = __builtin_amdgcn_readfirstlane(drawn);
     const int cluster = (ticket / GH) * 8 + cls, member = ticket % GH;
     const int NC = (int)gridDim.x / GH;          // clusters of this launch
     if (tid == 0)
@@ -179,6 +169,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper128(const Upper128Params
     const unsigned h2b_lds = (unsigned)reinterpret_cast<unsigned long long>(h2b);
 
     // ---- do all members of this cluster really share an XCD?
+    // (ape_same_xcd spelled out: through the helper hipcc forms the address of the XCD words in another order -- profiles/cluster_sync_header.md)
     if (wave == 0) {
         unsigned spins = 0, v = 0u;
         while (true) {
@@ -186,10 +177,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper128(const Upper128Params
             if (lane < GH) v = __hip_atomic_load(xcc_words + cluster * GH + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (__all((int)(v != 0u))) break;
             if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
+                ape_give_up(ctl, p.status, APE_ABORT_SPIN, lane);
                 break;
             }
             __builtin_amdgcn_s_sleep(2);
@@ -213,22 +201,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper128(const Upper128Params
     const unsigned look_lds = (unsigned)reinterpret_cast<unsigned long long>(look_s) + (unsigned)(wave * 256);
     const unsigned* const look_mine = look_s + wave * 64 + lane;
     // every wave polls for itself: have all member waves published epoch `want` of set s?
-    auto wait_flags = [&](const unsigned* fl, unsigned want) {
-        unsigned spins = 0;
-        while (true) {
-            unsigned v = want;
-            if (lane < NFL) v = __hip_atomic_load(fl + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v >= want))) return;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                return;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    };
+    auto wait_flags = [&](const unsigned* fl, unsigned want) { ape_wait_words<NFL, 1, 1>(fl, 0, want, p.status, ctl, lane); };
     // a 16 KB copy global -> LDS: wave w moves KiB w, w + 4, w + 8, w + 12; piece k on its own so that a copy can be spread over k-blocks
     const unsigned dma_voff = (unsigned)(lane * 16);
     const unsigned wave_kib = (unsigned)(wave * 1024);
@@ -254,7 +227,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper128(const Upper128Params
         pend_epoch = epoch;
         asm volatile("" : "+v"(pend_ptr), "+v"(pend_epoch));
     };
-    auto bar = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    auto bar = [&]() { ape_bar_lds(); };
 
     // ---- per-set state (uniform over the workgroup AND over the cluster: every member walks the same tiles).  A set's tiles are one
     //      stream of steps: section k of the set = layer 1 on step k of that stream AND layer 2 on step k - 1 (the last step of the tile

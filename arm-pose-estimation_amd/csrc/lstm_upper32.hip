@@ -30,6 +30,7 @@
 
 #include "ape_internal.h"
 #include "async_look.h"
+#include "cluster_sync.h"
 #include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 
@@ -84,21 +85,10 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper32(const UpperParams p) 
     unsigned* const class_ticket = p.xcc_slots + 64;
     unsigned* const xcc_words = p.xcc_slots + 64 + 8 * 16;
     const int cls = blockIdx.x & 7;
-    unsigned my_xcc;
-    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
-    my_xcc &= 0xFu;
-    if (tid == 0) {
-        ctl[0] = 0;
-        ctl[1] = -1;
-        if (__hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-            const unsigned tk = __hip_atomic_fetch_add(class_ticket + cls * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk < gridDim.x / 8) ctl[1] = (int)tk;
-            else __hip_atomic_store(p.status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-    if (ctl[1] < 0) return;
-    const int ticket = __builtin_amdgcn_readfirstlane(ctl[1]);
+    const unsigned my_xcc = ape_xcc_id();
+    const int drawn = ape_take_class_ticket(ctl, p.status, class_ticket, cls, tid);
+    if (drawn < 0) return;
+    const int ticket = __builtin_amdgcn_readfirstlane(drawn);
     const int cluster = (ticket / GH) * 8 + cls, member = ticket % GH;
     const int NC = (int)gridDim.x / GH;          // clusters of this launch
     if (tid == 0)
@@ -152,24 +142,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper32(const UpperParams p) 
     const unsigned hb_lds = (unsigned)reinterpret_cast<unsigned long long>(hb);
 
     // ---- do all members of this cluster really share an XCD? ------------------------------------------------------
-    if (wave == 0) {
-        unsigned spins = 0, v = 0u;
-        while (true) {
-            v = 0x10u | my_xcc;
-            if (lane < GH) v = __hip_atomic_load(xcc_words + cluster * GH + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v != 0u))) break;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        const int same = __all((int)((v & 0xFu) == my_xcc));
-        if (lane == 0) ctl[3] = same;
-    }
+    if (wave == 0) ape_same_xcd<GH, 2, APE_ABORT_SPIN>(xcc_words, cluster, my_xcc, p.status, ctl, lane);
     __syncthreads();
     if (ctl[0] != 0) return;
     // The hand-over is by write-through (sc1) stores whatever the placement: the form the MI355X guide lists as valid wherever the workgroups
@@ -180,22 +153,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper32(const UpperParams p) 
     constexpr bool in_l2 = false;
 
     // every wave polls for itself: have all member waves published epoch `want` of set s?
-    auto wait_flags = [&](int s, unsigned want) {
-        unsigned spins = 0;
-        while (true) {
-            unsigned v = want;
-            if (lane < NFL) v = __hip_atomic_load(flags_of + s * NFL + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v >= want))) return;
-            if (++spins > SPIN_LIMIT || __hip_atomic_load(p.status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) {
-                if (lane == 0) {
-                    ctl[0] = 1;
-                    __hip_atomic_store(p.status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                return;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
-    };
+    auto wait_flags = [&](int s, unsigned want) { ape_wait_words<NFL, 1, 1>(flags_of, s, want, p.status, ctl, lane); };
     // a 32 KB copy global -> LDS: wave w moves KiB w, w + 4, ... (8 of them); piece k on its own so that a copy can be spread
     // over the k-blocks of a span
     const unsigned dma_voff = (unsigned)(lane * 16);
@@ -224,8 +182,7 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_upper32(const UpperParams p) 
         if (lane == 0) __hip_atomic_store(flags_of + pend_idx, pend_epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         pend_idx = -1;
     };
-    // workgroup barrier that waits for this wave's LDS traffic only (not for the publish store or a DMA in flight)
-    auto bar = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    auto bar = [&]() { ape_bar_lds(); };
 
     // ---- per-set state (uniform over the workgroup AND over the cluster: every member walks the same tiles) ------------------
     float cst[2][4];

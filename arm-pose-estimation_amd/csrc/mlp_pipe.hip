@@ -14,6 +14,7 @@
 // I <= 32, O <= 32; everything else stays on mlp_tile16.hip.
 #include "ape_internal.h"
 #include "async_look.h"
+#include "cluster_sync.h"
 #include "mfma_stream.h"
 #include "../../include/ape_hip.h"
 #include <cstdlib>
@@ -101,18 +102,9 @@ __global__ __launch_bounds__(256, 1) void ape_mlp_pipe(const PipeParams pp) {
     unsigned* const status = pp.ctl + 8 * 16;
     unsigned* const done = status + 1;
     const int cls = blockIdx.x & 7;
-    if (tid == 0) {
-        ctl_s[0] = 0;
-        ctl_s[1] = -1;
-        if (__hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == 0u) {
-            const unsigned tk = __hip_atomic_fetch_add(class_ticket + cls * 16, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (tk < gridDim.x / 8) ctl_s[1] = (int)tk;
-            else __hip_atomic_store(status, 2u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-    __syncthreads();
-    if (ctl_s[1] < 0) return;
-    const int ticket = __builtin_amdgcn_readfirstlane(ctl_s[1]);
+    const int drawn = ape_take_class_ticket(ctl_s, status, class_ticket, cls, tid);
+    if (drawn < 0) return;
+    const int ticket = __builtin_amdgcn_readfirstlane(drawn);
     const int pair = (ticket >> 1) * 8 + cls, role = ticket & 1;
     const int n_pairs = gridDim.x / 2;
     // do the pair's two workgroups share an XCD (one L2)?  Block-index classes are XCDs where the dispatcher deals workgroups round
@@ -120,8 +112,7 @@ __global__ __launch_bounds__(256, 1) void ape_mlp_pipe(const PipeParams pp) {
     unsigned* const xcc_words = pp.ctl + 256 + (size_t)n_pairs * 32;
     unsigned my_xcc = 0u;
     if (tid == 0) {
-        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(my_xcc));
-        my_xcc = 0x10u | (my_xcc & 0xFu);
+        my_xcc = 0x10u | ape_xcc_id();
         __hip_atomic_store(xcc_words + pair * 2 + role, my_xcc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // (the producer reads its consumer's id behind its prologue, when it has long been written: stage A below)
@@ -132,8 +123,7 @@ __global__ __launch_bounds__(256, 1) void ape_mlp_pipe(const PipeParams pp) {
                 unsigned spins = 0;
                 while ((peer = __hip_atomic_load(xcc_words + pair * 2 + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) == 0u) {
                     if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                        ctl_s[0] = 1;
-                        __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                        ape_give_up(ctl_s, status, APE_ABORT_SPIN, tid);      // (thread 0 is alone in here)
                         break;
                     }
                     __builtin_amdgcn_s_sleep(1);
@@ -153,24 +143,11 @@ __global__ __launch_bounds__(256, 1) void ape_mlp_pipe(const PipeParams pp) {
     unsigned* const empty = full + 16;                          // [slot][consumer wave] = tiles of that slot copied out
     const u32x4 ring_desc = ape_make_desc(pp.ring, (unsigned)pp.ring_bytes);
     auto slot_base = [&](int slot) -> unsigned { return (unsigned)(((size_t)pair * NSLOT + slot) * HLF * sizeof(float)); };
-    auto bar = [&]() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); };
+    auto bar = [&]() { ape_bar_lds(); };
     // all 4 words of `f` (one per peer wave) have reached `want`
     auto wait_words = [&](const unsigned* f, unsigned want) {
         if (pp.diag & 1u) return;
-        unsigned spins = 0;
-        while (true) {
-            unsigned v = want;
-            if (lane < 4) v = __hip_atomic_load(f + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if (__all((int)(v >= want))) return;
-            if (++spins > SPIN_LIMIT || ((spins & 255u) == 0u && __hip_atomic_load(status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u)) {
-                if (lane == 0) {
-                    ctl_s[0] = 1;
-                    __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                }
-                return;
-            }
-            __builtin_amdgcn_s_sleep(1);
-        }
+        ape_wait_words<4, 1, 256>(f, 0, want, status, ctl_s, lane);
     };
     // the same wait in two halves, so that the L2 round trip of the look runs beside the MFMAs: the four words are fetched here ... by
     // LDS-DMA into the wave's landing zone (lane i's word goes to look_s[64 wave + i]; lanes fetch word i & 3).  Round 5: NOT into a
