@@ -41,6 +41,7 @@ ROWS_MSG, ROWS_EST, ROWS_TARGETS = 0, 1, 2  # APE_ROWS_*
 HIST_MAX_BINS, HIST_MAX_WIDTH = 256, 16     # APE_HIST_MAX_BINS, APE_HIST_MAX_WIDTH (ape_score_hist)
 ANGLE_WIDTH, ANGLE_ACC_WIDTH = 7, 71        # APE_ANGLE_WIDTH, APE_ANGLE_ACC_WIDTH (ape_joint_angles)
 BY_MAX_KEYS, BY_MAX_VALUES, BY_MAX_BINS, BY_PIECE = 8, 16, 125, 1024    # APE_BY_* (ape_score_by)
+SPECTRA_DETREND, SPECTRA_MAX_N, SPECTRA_MAX_COLS = 0x1, 512, 16        # APE_SPECTRA_* (ape_spectra)
 FLAG_ANY_PLACEMENT, FLAG_NO_XCD_CLASSES, FLAG_ALT_FORM = 0x08000000, 0x02000000, 0x01000000    # exchange-form selectors (A/B runs, tests)
 FLAG_IN_XCD_PLAIN = 0x00400000      # opt-in: plain hand-over stores inside an XCD-pure cluster (the default is write-through)
 KERNEL_AUTO, KERNEL_TILE16, KERNEL_CLUSTER, KERNEL_CLUSTER_GEN1, KERNEL_AUTO_GEN1 = 0, 1, 2, 3, 4
@@ -281,6 +282,11 @@ SIGNATURES["ape_joint_angles"] = (C.c_int, [C.c_int32, C.c_void_p, C.c_int32, C.
 SIGNATURES["ape_score_by"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_int32, C.c_int32, C.c_int64,
                                         C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p,
                                         C.c_void_p])
+# Welch sums per frequency: x + dtype, set and frame stride (int64), x_cols_host, y | NULL + dtype, set and frame stride
+# (int64), y_cols_host, V, n_sets, F, starts_host, R, skip, N, hop, taper_host, flags, acc, counts, HIP stream
+SIGNATURES["ape_spectra"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
+                                       C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                       C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
 
 _lib = None
 

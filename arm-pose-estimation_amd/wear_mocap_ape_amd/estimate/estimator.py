@@ -723,6 +723,23 @@ class Estimator:
         bodies = self._body_measurements if bonemaps is None else bonemaps
         return score.motion_sums(self._layout, truth, truth_kind, starts, skip, times, bodies)
 
+    # ---- spectra of a replay (the reference has no counterpart) ----
+    def spectrum_recording(self, out, truth=None, starts=None, skip=None, truth_kind="est", bonemaps=None, n=256, hop=None, taper="hann",
+                           rate=1.0):
+        """At which frequencies a replay follows the arm: ``score.spectra`` of the six hand and elbow position columns
+        (``score.pose_cols``, ``score.POSE_COL_NAMES``) of ``out`` as ``process_recording`` returned it (or ``repost``'s
+        ``[C, F, 25]``), against ``truth`` if given: device est rows ``[F, 21 | 14]`` (``truth_kind="est"``), or de-normalised targets
+        ``[F, O]`` (``"targets"``), which ``score.resample_truth`` turns into est rows on the device, on the frames' own index clock,
+        with this estimator's body or ``bonemaps``.  Welch segments of ``n`` frames every ``hop`` (``n // 2``), ``taper`` and the mean
+        taken off each segment; ``skip`` defaults to ``score_recording``'s; ``rate``: frames per second (the clock is the frame index:
+        jitter of the stamps is ignored).  Returns ``(acc, counts, summary)``: the raw sums on the device and
+        ``score.summarise_spectra`` of them (``score.bandwidth``, ``score.band_power``); waits for the device."""
+        from wear_mocap_ape_amd import score
+        skip = self._sequence_len - 1 if skip is None else skip
+        bodies = self._body_measurements if bonemaps is None else bonemaps
+        acc, counts = score.pose_spectra(self._layout, out, truth, truth_kind, starts, skip, bodies, n, hop, taper)
+        return acc, counts, score.summarise_spectra(acc, counts, score.spectra_taper(taper, n), rate)
+
     # ---- reaches and holds (DESIGN.md 4.45; the reference has no counterpart) ----
     def _segments_of(self, score, speed, thresholds, mins, times, starts, extra=None):
         """labels, table and per-segment records of one hand-speed column: the value columns are the speed (its maximum is the peak speed)
@@ -889,7 +906,7 @@ class Estimator:
         return post(model, y, sets, starts, bonemaps, spread, out_dtype, workspace_bytes)
 
     def sweep_recording(self, rows, truth, smooths, samples, starts=None, lags=(0, 0), truth_kind="targets", bonemaps=None,
-                        seed: int = 0x5EED, skip=None, big_endian: bool = False, motion: bool = False, times=None):
+                        seed: int = 0x5EED, skip=None, big_endian: bool = False, spectra: bool = False, motion: bool = False, times=None):
         """Which ``smooth`` and how many Monte-Carlo samples: ONE ``process_recording(return_targets=True)`` at ``max(samples)`` samples
         (this estimator's own ``smooth`` and sample count stay what they are), one ``score.post_sweep`` of
         ``score.grid(smooths, samples)`` with the spread records, then one ``score.score_lags`` over ``lags`` per configuration against
@@ -898,7 +915,10 @@ class Estimator:
         Returns ``{"configs": [(smooth, samples), ...], "acc": ndarray [C, R, L, 25], "best": [score.best_lag(acc[c], lags) per
         configuration]}`` (waits for the device).  ``motion=True``: the dict also holds ``"motion": ndarray [C, R, 38]``, what every
         configuration's smoothing buys -- one ``score.motion_sums`` call on the sweep's ``out`` (``times``: the frames' clock, device
-        float64 ``[F]``; None: per-frame units)."""
+        float64 ``[F]``; None: per-frame units).  ``spectra=True``: the dict also holds ``"bandwidth"``, ndarray
+        ``[C, R, 6]``: the -3 dB bandwidth in cycles per frame of every configuration's hand and elbow positions against the truth
+        (``spectrum_recording``'s defaults; NaN where a recording is shorter than a segment).  Pass everything after
+        ``big_endian`` by keyword: ``spectra`` stands ahead of ``motion`` and ``times``, which stay the last two."""
         from wear_mocap_ape_amd import score
         from wear_mocap_ape_amd.estimate.nn_models import effective_mc
         model = self._hip_model()
@@ -908,13 +928,13 @@ class Estimator:
         if not configs:
             raise UserWarning("sweep_recording: no configuration")
         return self._sweep(self.repost, score.score_configs, configs, max(m for _, m in configs), rows, truth, starts, lags, truth_kind,
-                           bonemaps, seed, skip, big_endian, motion, times)
+                           bonemaps, seed, skip, big_endian, motion, times, spectra)
 
     def _sweep(self, repost, score_sets, configs, top: int, rows, truth, starts, lags, truth_kind, bonemaps, seed, skip, big_endian, motion,
-               times):
+               times, spectra=False):
         """``sweep_recording`` and ``sweep_windows`` once their list is made: the replay at ``top`` samples, ``repost`` (``self.repost``
         / ``self.repost_windows``) of ``configs`` with the spread records, the defaults of ``skip`` and the bodies, ``score_sets``
-        (``score.score_configs`` / ``score.score_windows``), and ``motion``"""
+        (``score.score_configs`` / ``score.score_windows``), ``motion`` and ``spectra``"""
         from wear_mocap_ape_amd import score
         _, y = self.process_recording(rows, starts=starts, big_endian=big_endian, return_targets=True, seed=seed, bonemaps=bonemaps,
                                       _config=(1, top))
@@ -924,6 +944,9 @@ class Estimator:
         res = score_sets(self._layout, out, rec, truth, configs, lags, truth_kind, starts, skip, bodies)
         if motion:
             res["motion"] = score.motion_sums(self._layout, out, "msg", starts, skip, times)[1].cpu().numpy()
+        if spectra:
+            acc, counts = score.pose_spectra(self._layout, out, truth, truth_kind, starts, skip, bodies)
+            res["bandwidth"] = score.bandwidth(score.summarise_spectra(acc, counts, "hann"))
         return res
 
     # ---- windowed post-filter: windows that look ahead, tapered weights (the reference has no counterpart) ----
@@ -936,12 +959,12 @@ class Estimator:
         return self._repost("repost_windows", score.post_window, y, windows, starts, bonemaps, spread, out_dtype, workspace_bytes)
 
     def sweep_windows(self, rows, truth, windows, starts=None, lags=(0, 0), truth_kind="targets", bonemaps=None, seed: int = 0x5EED,
-                      skip=None, big_endian: bool = False, motion: bool = False, times=None):
+                      skip=None, big_endian: bool = False, spectra: bool = False, motion: bool = False, times=None):
         """What looking ahead and tapering buy, for a recording processed offline: ONE ``process_recording(return_targets=True)`` at the
         largest sample count of ``windows`` (``score.window`` entries; this estimator's own ``smooth`` and sample count stay what they
         are), one ``score.post_window`` with the spread records, then one ``score.score_lags`` over ``lags`` per window against
-        ``truth``.  Over an ``ImuPoseLSTM`` every sample count is 1.  ``skip``, ``truth_kind``, ``bonemaps``, ``motion``, ``times``:
-        ``sweep_recording``'s.  Returns ``sweep_recording``'s dict with ``"configs"`` holding the windows as ``score.window`` returns
+        ``truth``.  Over an ``ImuPoseLSTM`` every sample count is 1.  ``skip``, ``truth_kind``, ``bonemaps``, ``motion``, ``times``,
+        ``spectra``: ``sweep_recording``'s (everything after ``big_endian`` by keyword).  Returns ``sweep_recording``'s dict with ``"configs"`` holding the windows as ``score.window`` returns
         them (waits for the device)."""
         from wear_mocap_ape_amd import score
         from wear_mocap_ape_amd.estimate.nn_models import effective_mc
@@ -950,7 +973,7 @@ class Estimator:
             raise UserWarning("this estimator has no HIP regressor or no batched feature builder")
         windows = [(b, a, effective_mc(model, int(m)), w) for b, a, m, w in score._windows(windows)[0]]
         return self._sweep(self.repost_windows, score.score_windows, windows, max(m for _, _, m, _ in windows), rows, truth, starts, lags,
-                           truth_kind, bonemaps, seed, skip, big_endian, motion, times)
+                           truth_kind, bonemaps, seed, skip, big_endian, motion, times, spectra)
 
     # ---- speed-adaptive smoothing: a window per frame from a ladder (the reference has no counterpart) ----
     def repost_selected(self, y, ladder, sel, starts=None, bonemaps=None, spread: bool = False, out_dtype=torch.float64,

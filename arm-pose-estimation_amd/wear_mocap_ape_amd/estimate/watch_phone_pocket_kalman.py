@@ -367,6 +367,12 @@ class WatchPhonePocketKalman(Estimator):
         """``Estimator.truth_motion`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""
         return super().truth_motion(truth, truth_kind, starts, self.__win_size + 1 if skip is None else skip, times, bonemaps)
 
+    def spectrum_recording(self, out, truth=None, starts=None, skip=None, truth_kind="est", bonemaps=None, n=256, hop=None, taper="hann",
+                           rate=1.0):
+        """``Estimator.spectrum_recording`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``motion_recording``)"""
+        return super().spectrum_recording(out, truth, starts, self.__win_size + 1 if skip is None else skip, truth_kind, bonemaps, n, hop,
+                                          taper, rate)
+
     def angles_recording(self, out, truth=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
                          per_frame=False, min_swing=0.05):
         """``Estimator.angles_recording`` for Kalman replays (``skip`` defaults to ``window_size + 1``, as in ``score_recording``)"""

@@ -154,6 +154,11 @@ class WatchPhoneUarm(Estimator):
         """``Estimator.truth_motion`` for FK replays (``skip`` defaults to 0, as in ``score_recording``)"""
         return super().truth_motion(truth, truth_kind, starts, 0 if skip is None else skip, times, bonemaps)
 
+    def spectrum_recording(self, out, truth=None, starts=None, skip=None, truth_kind="est", bonemaps=None, n=256, hop=None, taper="hann",
+                           rate=1.0):
+        """``Estimator.spectrum_recording`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``motion_recording``)"""
+        return super().spectrum_recording(out, truth, starts, 0 if skip is None else skip, truth_kind, bonemaps, n, hop, taper, rate)
+
     def angles_recording(self, out, truth=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", rec_lags=None,
                          per_frame=False, min_swing=0.05):
         """``Estimator.angles_recording`` for ``[F, 25]`` FK replays (``skip`` defaults to 0, as in ``score_recording``)"""

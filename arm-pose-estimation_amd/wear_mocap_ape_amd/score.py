@@ -66,7 +66,13 @@ key with two thresholds and minimum lengths, ``segment_runs`` turns any labels i
 per-frame columns over every segment in a stated order of summation (``ape_segment_frames``, ``ape_segment_runs``,
 ``ape_segment_stats``); ``match_segments`` pairs an estimate's moves with the truth's and ``summarise_segments`` reads
 the records per recording and label on the host; ``segment_frames_numpy``, ``segment_runs_numpy`` and ``segment_stats_numpy`` are the
-host statements."""
+host statements.
+
+At which frequencies: ``spectra`` takes Welch sums of any per-frame columns against an optional truth per recording, column and
+frequency bin on the float64 matrix cores (``ape_spectra``); ``summarise_spectra`` reads densities, the gain, phase and
+delay of the estimate against the truth, the coherence and the error's spectrum off them, ``bandwidth`` and ``band_power`` reduce those,
+``merge_spectra`` adds records, ``pose_cols`` and ``pose_spectra`` pick the hand and elbow positions; ``spectra_numpy`` is the host
+statement."""
 import ctypes as C
 import math
 
@@ -3166,3 +3172,240 @@ def summarise_segments(table, stats, names, times=None) -> list:
         res.append({"recording": r, "label": lab, "count": int(rows.shape[0]), "mean_duration": float(dur[rows].mean()),
                     "longest_duration": float(dur[rows].max()), "mean": dict(zip(names, mean.tolist())), "max": dict(zip(names, top.tolist()))})
     return res
+
+
+# ---- spectra of a replay: Welch sums per frequency (ape_spectra) ----------------------------------------------------------------
+# The scorers say how wrong a replay is, at which lag and how much it shakes; the spectra say at which frequencies.  The device takes raw
+# sums over a recording's segments -- |X|^2, |Y|^2, conj(Y) X per bin -- and the host reads densities, gain, phase, delay and coherence
+# off them.  The clock is the frame index: a bin is k / n cycles per frame, times ``rate`` in Hz.
+SPECTRA_MAX_N, SPECTRA_MAX_COLS = _hip.SPECTRA_MAX_N, _hip.SPECTRA_MAX_COLS
+TAPERS = ("hann", "boxcar")
+
+
+def spectra_taper(taper, n: int) -> np.ndarray:
+    """float64 ``[n]`` weights: ``"hann"`` (periodic: ``0.5 - 0.5 cos(2 pi i / n)``), ``"boxcar"`` (ones) or the caller's ``n`` finite
+    values"""
+    n = int(n)
+    if isinstance(taper, str):
+        if taper == "hann":
+            return 0.5 - 0.5 * np.cos(2.0 * np.pi * np.arange(n, dtype=np.float64) / n)
+        if taper == "boxcar":
+            return np.ones(n, dtype=np.float64)
+        raise UserWarning(f"taper: one of {TAPERS} or {n} weights, got {taper!r}")
+    w = np.ascontiguousarray(np.asarray(taper, dtype=np.float64).reshape(-1))
+    if w.shape[0] != n or not np.isfinite(w).all():
+        raise UserWarning(f"taper: {n} finite weights, got {w.shape[0]}")
+    return w
+
+
+def _spectra_plan(n, hop):
+    n = int(n)
+    hop = n // 2 if hop is None else int(hop)
+    if n < 16 or n > SPECTRA_MAX_N or n % 16 or not 1 <= hop <= n:
+        raise UserWarning(f"spectra: n a multiple of 16 in 16 .. {SPECTRA_MAX_N} and hop in 1 .. n, got n = {n}, hop = {hop}")
+    return n, hop
+
+
+def _spectra_cols(cols, width: int, what: str) -> np.ndarray:
+    c = np.arange(width, dtype=np.int32) if cols is None else np.ascontiguousarray(np.asarray(cols, dtype=np.int32).reshape(-1))
+    if not 1 <= c.shape[0] <= SPECTRA_MAX_COLS or (c < 0).any() or (c >= width).any():
+        raise UserWarning(f"{what}: between 1 and {SPECTRA_MAX_COLS} columns of the rows' {width}, got {c.tolist()}")
+    return c
+
+
+def pose_cols(layout: int, kind: str = "msg") -> tuple:
+    """the six columns that hold the hand and the elbow position (x, y, z each) in rows of ``kind``: ``"msg"`` messages ``[4:7]`` and
+    ``[11:14]``, ``"est"`` est rows ``[0:3]`` and ``[3:6]``.  Target rows state no positions in every layout: convert them first."""
+    if layout not in _hip.EST_WIDTH:
+        raise UserWarning(f"layout {layout} has no pose")
+    if kind == "msg":
+        return (4, 5, 6, 11, 12, 13)
+    if kind == "est":
+        return (0, 1, 2, 3, 4, 5)
+    raise UserWarning(f"pose_cols: kind 'msg' or 'est', got {kind!r}")
+
+
+POSE_COL_NAMES = ("hand_x", "hand_y", "hand_z", "elbow_x", "elbow_y", "elbow_z")
+
+
+def spectra_numpy(rows, truth=None, cols=None, truth_cols=None, n: int = 256, hop=None, taper="hann", detrend: bool = True, starts=None,
+                  skip: int = 0):
+    """The host statement of ``spectra`` for one set: ``rows [F, w]`` (and ``truth [F, wt]``) -> ``(acc [R, V, n/2 + 1, W], counts
+    [R, V, 2])``, float64 and int32, plain numpy with ``np.fft.rfft`` per segment: segment ``j`` of recording ``r`` is the frames
+    ``s_r + skip + j hop + [0, n)``; ``a = w * (x - mean(x))`` (no mean without ``detrend``), ``X = rfft(a)``; ``acc[..., 0]`` sums
+    ``re(X)^2 + im(X)^2``, with truth ``[1]`` the same of ``Y``, ``[2]`` and ``[3]`` the real and imaginary part of ``conj(Y) X``.  A
+    segment with a value that is not finite on either side is left out for that column."""
+    n, hop = _spectra_plan(n, hop)
+    w = spectra_taper(taper, n)
+    x = np.asarray(rows, dtype=np.float64)
+    y = None if truth is None else np.asarray(truth, dtype=np.float64)
+    F = x.shape[0]
+    xc = _spectra_cols(cols, x.shape[1], "cols")
+    yc = None if y is None else _spectra_cols(xc if truth_cols is None else truth_cols, y.shape[1], "truth_cols")
+    if y is not None and (y.shape[0] != F or yc.shape[0] != xc.shape[0]):
+        raise UserWarning("spectra: rows and truth of the same frames and as many columns")
+    st = _recording_starts(starts)
+    R, V, W = int(st.shape[0]), int(xc.shape[0]), 1 if y is None else 4
+    acc = np.zeros((R, V, n // 2 + 1, W))
+    counts = np.zeros((R, V, 2), dtype=np.int32)
+    for r in range(R):
+        s, e = int(st[r]), int(st[r + 1]) if r + 1 < R else F
+        length = e - s - int(skip)
+        J = (length - n) // hop + 1 if length >= n else 0
+        for j in range(J):
+            f0 = s + int(skip) + j * hop
+            for v in range(V):
+                sx = x[f0:f0 + n, xc[v]]
+                sy = None if y is None else y[f0:f0 + n, yc[v]]
+                if not np.isfinite(sx).all() or (sy is not None and not np.isfinite(sy).all()):
+                    counts[r, v, 1] += 1
+                    continue
+                counts[r, v, 0] += 1
+                X = np.fft.rfft(w * (sx - (sx.mean() if detrend else 0.0)))
+                acc[r, v, :, 0] += X.real * X.real + X.imag * X.imag
+                if sy is not None:
+                    Y = np.fft.rfft(w * (sy - (sy.mean() if detrend else 0.0)))
+                    acc[r, v, :, 1] += Y.real * Y.real + Y.imag * Y.imag
+                    acc[r, v, :, 2] += Y.real * X.real + Y.imag * X.imag
+                    acc[r, v, :, 3] += Y.real * X.imag - Y.imag * X.real
+    return acc, counts
+
+
+def spectra(rows, truth=None, cols=None, truth_cols=None, n: int = 256, hop=None, taper="hann", detrend: bool = True, starts=None,
+            skip: int = 0):
+    """Welch sums per recording, column and frequency bin on the device (``ape_spectra``).  ``rows``: a device ``[F, w]`` or
+    ``[C, F, w]`` view (``C <= 64`` sets), float32 or float64 -- messages, est rows, ``motion_sums``' ``[C, F, 12]``, ``joint_angles``'
+    ``[C, F, 7]`` go in as they lie (``_hist_view``'s rules); ``cols``: up to 16 of its columns (default: all of them).  ``truth``: the
+    same frames, with or without sets (one truth for all sets), its own dtype and ``truth_cols`` (default: ``cols``).  Segments of ``n``
+    frames (a multiple of 16 in 16 .. 512) every ``hop`` (default ``n // 2``) from ``skip`` frames into each recording of ``starts``,
+    never across a boundary; ``taper``: ``"hann"``, ``"boxcar"`` or ``n`` weights; ``detrend`` takes each segment's mean off.  Returns
+    ``(acc, counts)`` on the device: float64 ``[(C,) R, V, n/2 + 1, W]`` -- ``[0]`` the sum of ``|X|^2``, with truth also ``[1]`` of
+    ``|Y|^2`` and ``[2]``, ``[3]`` real and imaginary part of the sum of ``conj(Y) X`` -- and int32 ``[(C,) R, V, 2]``, segments summed
+    and left out (a value that is not finite).  The order of every sum is stated (include/ape_hip.h): the same inputs give the same
+    bits.  ``summarise_spectra`` reads them.  The call does not wait for the device."""
+    n, hop = _spectra_plan(n, hop)
+    w = spectra_taper(taper, n)
+    xv, Cx, F, Wx, xss, xfs, xsets = _by_view(rows, "rows")
+    xc = _spectra_cols(cols, Wx, "cols")
+    V = int(xc.shape[0])
+    yv = None
+    if truth is not None:
+        yv, Cy, Fy, Wy, yss, yfs, ysets = _by_view(truth, "truth")
+        yc = _spectra_cols(xc if truth_cols is None else truth_cols, Wy, "truth_cols")
+        if Fy != F or yv.device != xv.device or yc.shape[0] != V or (ysets and Cy != Cx):
+            raise UserWarning(f"rows {tuple(rows.shape)} and truth {tuple(truth.shape)}: the same frames on one device, as many columns, "
+                              "and the rows' sets or none")
+    if Cx > _hip.POST_MAX_CONFIGS:
+        raise UserWarning(f"rows: at most {_hip.POST_MAX_CONFIGS} sets, got {Cx}")
+    st = _recording_starts(starts)
+    R, dev = int(st.shape[0]), xv.device
+    with torch.cuda.device(dev):
+        acc = torch.empty((Cx, max(R, 1), V, n // 2 + 1, 1 if yv is None else 4), dtype=torch.float64, device=dev)
+        counts = torch.empty((Cx, max(R, 1), V, 2), dtype=torch.int32, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        if yv is None:
+            ya = (None, 0, 0, 0, None)
+        else:
+            ya = (C.c_void_p(yv.data_ptr()), _f64(yv.dtype), yss, yfs, C.c_void_p(yc.ctypes.data))
+        _hip.check(_hip.lib().ape_spectra(C.c_void_p(xv.data_ptr()), _f64(xv.dtype), xss, xfs, C.c_void_p(xc.ctypes.data), *ya, V, Cx, F,
+                                          C.c_void_p(st.ctypes.data), R, int(skip), n, hop, C.c_void_p(w.ctypes.data),
+                                          _hip.SPECTRA_DETREND if detrend else 0, C.c_void_p(acc.data_ptr()),
+                                          C.c_void_p(counts.data_ptr()), stream), "ape_spectra")
+    return (acc, counts) if xsets else (acc[0], counts[0])
+
+
+def _spectra_host(acc, counts):
+    a = acc.detach().cpu().numpy() if isinstance(acc, torch.Tensor) else np.asarray(acc)
+    c = counts.detach().cpu().numpy() if isinstance(counts, torch.Tensor) else np.asarray(counts)
+    a, c = np.asarray(a, dtype=np.float64), np.asarray(c, dtype=np.int64)
+    if a.ndim < 3 or a.shape[-1] not in (1, 4) or c.shape != a.shape[:-2] + (2,):
+        raise UserWarning(f"expected spectra [..., V, bins, 1 | 4] and counts [..., V, 2], got {tuple(a.shape)} and {tuple(c.shape)}")
+    return a, c
+
+
+def merge_spectra(a, b) -> tuple:
+    """the records ``(acc, counts)`` of two pieces of the same recordings, columns and plan as one: sums and counts added (raw sums, so
+    the pieces of a chained replay merge; the segments that would straddle the joint are in neither piece)"""
+    aa, ac = _spectra_host(*a)
+    ba, bc = _spectra_host(*b)
+    if aa.shape != ba.shape:
+        raise UserWarning(f"merge_spectra: {tuple(aa.shape)} and {tuple(ba.shape)} records")
+    return aa + ba, (ac + bc).astype(np.int32)
+
+
+def summarise_spectra(acc, counts, taper, rate: float = 1.0) -> dict:
+    """``(acc [..., V, n/2 + 1, W], counts [..., V, 2])`` of ``spectra`` (any leading dimensions: sets, recordings) -> a dict of float64
+    arrays on the host.  ``taper``: the call's (a name or the weights; its length states ``n``).  ``rate``: frames per second; the
+    clock is the frame index scaled by it -- jitter of the frames' stamps is ignored, a recording with uneven stamps is read as if
+    they were even.  ``freqs [n/2 + 1]`` in Hz (cycles per frame at ``rate`` 1); ``segments [..., V]``; ``psd [..., V, n/2 + 1]``
+    one-sided density, the mean over the segments of ``|X|^2 / (rate sum(w^2))``, doubled except at 0 and at ``rate / 2``
+    (``scipy.signal.welch``'s density scaling).  With truth also ``truth_psd``; ``error_psd``, the density of ``x - y`` from the identity
+    ``Pxx + Pyy - 2 Re Pxy``; ``coherence`` ``|Pxy|^2 / (Pxx Pyy)``; ``gain`` and ``phase`` of ``H = Pyx / Pyy``, the transfer function
+    from the truth to the estimate (phase in radians, negative where the estimate trails); ``delay = -phase / (2 pi f)`` in seconds
+    (frames at ``rate`` 1; NaN at 0).  NaN where no segment was summed."""
+    a, c = _spectra_host(acc, counts)
+    bins = a.shape[-2]
+    n = 2 * (bins - 1)
+    w = spectra_taper(taper, n)
+    rate = float(rate)
+    freqs = np.arange(bins, dtype=np.float64) * (rate / n)
+    side = np.full(bins, 2.0)
+    side[0] = side[-1] = 1.0
+    seg = c[..., 0].astype(np.float64)
+    with np.errstate(all="ignore"):
+        scale = side / (rate * float((w * w).sum())) / np.where(seg > 0, seg, np.nan)[..., None]
+        res = {"freqs": freqs, "segments": c[..., 0].copy(), "psd": a[..., 0] * scale}
+        if a.shape[-1] == 4:
+            pxx, pyy, re, im = a[..., 0], a[..., 1], a[..., 2], a[..., 3]
+            res["truth_psd"] = pyy * scale
+            res["error_psd"] = (pxx + pyy - 2.0 * re) * scale
+            res["coherence"] = np.where(seg[..., None] > 0, (re * re + im * im) / (pxx * pyy), np.nan)
+            h = (re + 1j * im) / np.where(seg[..., None] > 0, pyy, np.nan)
+            res["gain"] = np.abs(h)
+            res["phase"] = np.where(np.isnan(h.real), np.nan, np.angle(h))
+            res["delay"] = -res["phase"] / (2.0 * np.pi * np.where(freqs > 0, freqs, np.nan))
+    return res
+
+
+def bandwidth(summary: dict, level: float = 2.0 ** -0.5) -> np.ndarray:
+    """``[..., V]``: the lowest frequency at which ``summary["gain"]`` falls below ``level`` (default: -3 dB), interpolated linearly
+    between the last bin at or above it and the first below.  Bin 0 is not looked at (a detrended segment has no power there); NaN
+    where the gain is below ``level`` from bin 1 on, never falls below it, or is NaN on the way."""
+    if "gain" not in summary:
+        raise UserWarning("bandwidth: a summary of spectra with truth")
+    g, f = np.asarray(summary["gain"], dtype=np.float64), np.asarray(summary["freqs"], dtype=np.float64)
+    out = np.full(g.shape[:-1], np.nan)
+    for at in np.ndindex(*g.shape[:-1]):
+        row = g[at]
+        for k in range(2, row.shape[0]):
+            if not (row[k - 1] >= level):
+                break
+            if row[k] < level:
+                out[at] = f[k - 1] + (row[k - 1] - level) / (row[k - 1] - row[k]) * (f[k] - f[k - 1])
+                break
+            if np.isnan(row[k]):
+                break
+    return out
+
+
+def band_power(summary: dict, lo: float, hi: float, key: str = "psd") -> np.ndarray:
+    """``[..., V]``: the power of ``summary[key]`` in the band ``lo <= f < hi``, the density times the bin width summed over the band's
+    bins (voluntary motion: below about 2 Hz; tremor and sensor shake: 4 - 12 Hz)"""
+    f = np.asarray(summary["freqs"], dtype=np.float64)
+    d = np.asarray(summary[key], dtype=np.float64)
+    pick = (f >= float(lo)) & (f < float(hi))
+    return d[..., pick].sum(axis=-1) * (f[1] - f[0])
+
+
+def pose_spectra(layout: int, out, truth=None, truth_kind: str = "est", starts=None, skip: int = 0, bodies=None, n: int = 256, hop=None,
+                 taper="hann", detrend: bool = True):
+    """``spectra`` of the six hand and elbow position columns (``pose_cols``, ``POSE_COL_NAMES``) of messages ``out [(C,) F, >= 25]``
+    against those of ``truth``: device est rows ``[F, 21 | 14]``, or with ``truth_kind="targets"`` de-normalised NN targets ``[F, O]``,
+    which ``resample_truth`` turns into est rows on the device (the frames' own index clock, no shift: every row is an exact hit; the
+    recordings' ``bodies``).  Returns ``spectra``'s ``(acc, counts)``."""
+    if truth_kind not in TRUTH_KINDS:
+        raise UserWarning(f"truth_kind must be one of {sorted(TRUTH_KINDS)}, got {truth_kind!r}")
+    if truth is not None and truth_kind == "targets":
+        truth = resample_truth(layout, truth, "targets", starts, None, None, int(out.shape[-2]), starts, None, 0.0, bodies)
+    return spectra(out, truth, pose_cols(layout, "msg"), None if truth is None else pose_cols(layout, "est"), n, hop, taper, detrend, starts,
+                   skip)

@@ -1538,6 +1538,50 @@ int ape_score_by(const void* keys_dev, int32_t keys_dtype, int32_t n_keys, int64
                  const double* edges_host /* f64 [n_keys, n_bins + 1] */, int32_t n_bins,
                  double* by_dev /* f64 [n_sets, R, n_keys, n_bins + 3, n_values, 4] */, void* stream);
 
+/* ---- spectra of a replay: Welch sums of power, truth power and cross spectrum per frequency (additive in ABI 7) --------------
+ * replaces: nothing; the reference has no counterpart.  The scorers say how wrong a replay is, at which lag and how much it shakes;
+ * ape_spectra says at which frequencies: the raw sums from which the host forms a power spectral density, the gain and phase of the
+ * estimate against the truth, the coherence and the spectrum of the error (score.py: summarise_spectra, bandwidth, band_power).  Without
+ * truth it gives the power spectrum of any per-frame column.
+ *   Rows.   Element (s, f, v), s < n_sets, f < F, v < V, of x lies x_set_stride * s + x_frame_stride * f + x_cols_host[v] elements after
+ *           x_dev, of x_dtype (APE_F32 is widened exactly first): messages [C, F, 25], est rows, ape_motion_sums' [C, F, 12] and
+ *           ape_joint_angles' [C, F, 7] go in as they lie.  x_set_stride is not read with n_sets == 1.  y_dev (the truth; NULL: none, and
+ *           the y arguments are not read) is addressed the same way with its own dtype, strides and y_cols_host; y_set_stride == 0 is one
+ *           truth shared by all sets.
+ *   Segments.  Recording r holds the frames [s_r, e_r) (seg_starts_host, as ape_score_rows).  Segment j of recording r is the N frames
+ *           s_r + skip + j * hop + [0, N), j < J_r = max(0, floor((e_r - s_r - skip - N) / hop) + 1): a segment never crosses a recording
+ *           boundary.  N is a multiple of 16 in 16 .. APE_SPECTRA_MAX_N, hop in 1 .. N.
+ *   Per segment and column, in float64.  m = the mean of the segment's N values with APE_SPECTRA_DETREND (the sum of the N values, then
+ *           / N), else 0.  a_n = w_n * (x_n - m), w = taper_host f64 [N].  X(k) = sum_n a_n (cos t - i sin t), t = 2 pi ((k n) mod N) / N,
+ *           k = 0 .. N/2; cos and sin from a table of N entries made on the host (the float64 nearest to each).  Y(k) likewise from y.  The
+ *           sum over n is the chain of v_mfma_f64_16x16x4_f64, fused multiply-adds in rising n from +0.0; where N is a multiple of 32, bin
+ *           N/2 is sum_n a_n (-1)^n (its sine is 0) added on the vector unit, 64 interleaved partial sums and a butterfly over them.
+ *   acc_dev f64 [n_sets, R, V, N/2 + 1, W], raw sums over the recording's segments: [0] sum |X|^2 = re * re + im * im; with truth (W = 4)
+ *           [1] sum |Y|^2, [2] and [3] the real and imaginary part of sum conj(Y) X, re(Y) re(X) + im(Y) im(X) and re(Y) im(X) - im(Y) re(X):
+ *           the cross spectrum from the truth to the estimate.  Without truth W = 1.  Separate roundings in the products and sums.
+ *   counts_dev i32 [n_sets, R, V, 2]: segments summed, segments left out; the two add to J_r.  A segment is left out for a column, and for
+ *           that column only, if any of its N values on either side is not finite; it contributes exact zeros.
+ *   Order.  This is part of the contract.  A recording's segments are taken in tiles of 16, counted from its first.  Within a tile, bin
+ *           k's terms of segments q, q + 4, q + 8, q + 12 are added in that order for q = 0 .. 3, the four sums in the order of q; the
+ *           tile's sum is added to the sum of the tiles before it, the first tile to +0.0.  No floating-point atomics.  The same inputs
+ *           give the same bits; a set's record has the bits of a call with n_sets = 1 on that set; a recording's record has the same bits
+ *           wherever it lies in a batch; [0] of a call with truth whose truth is finite has the bits of the call without.
+ * Needs no model handle, runs on the current HIP device and does not wait; the host arrays have been consumed when it returns; staging
+ * slots as ape_score_rows keeps them (this file's own).  One launch, all of both outputs written; no workgroup waits for another.
+ * Refused with APE_ERR_INVALID_ARG on the host, before anything is written: NULL x_dev / x_cols_host / seg_starts_host / taper_host /
+ * acc_dev / counts_dev, y_dev with NULL y_cols_host; F < 1, R < 1, bad starts, skip < 0; N not a multiple of 16 in 16 .. 512; hop outside
+ * 1 .. N; V outside 1 .. APE_SPECTRA_MAX_COLS; n_sets outside 1 .. APE_POST_MAX_CONFIGS; unknown flags or dtype; a frame stride below 1; a
+ * column offset below 0 or at or beyond its side's frame stride; n_sets > 1 with a set stride below F * frame_stride (x; y unless 0): the
+ * sets overlap; an extent that does not fit 63 bits; an output overlapping an input or the other output; a capturing stream. */
+#define APE_SPECTRA_DETREND   0x1u
+#define APE_SPECTRA_MAX_N     512
+#define APE_SPECTRA_MAX_COLS  16
+int ape_spectra(const void* x_dev, int32_t x_dtype, int64_t x_set_stride, int64_t x_frame_stride, const int32_t* x_cols_host /* [V] */,
+                const void* y_dev /* or NULL */, int32_t y_dtype, int64_t y_set_stride, int64_t y_frame_stride,
+                const int32_t* y_cols_host /* [V] */, int32_t V, int32_t n_sets, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                int32_t skip, int32_t N, int32_t hop, const double* taper_host /* f64 [N] */, uint32_t flags,
+                double* acc_dev /* f64 [n_sets, R, V, N/2 + 1, W] */, int32_t* counts_dev /* i32 [n_sets, R, V, 2] */, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
