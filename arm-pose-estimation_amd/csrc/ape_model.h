@@ -99,7 +99,7 @@ struct ape_model {
     f32x4* ff_wpack[APE_MAX_FF_LAYERS] = {};
     float* ff_bias[APE_MAX_FF_LAYERS] = {};
     std::string kernel_name, cluster_name;
-    const char* last_kernel = "";   // the LSTM kernel the newest compute call launched last (ape_model_last_kernel)
+    const char* last_kernel = "";   // the regressor kernel (LSTM or MLP) the newest compute call launched last (ape_model_last_kernel)
     // calls since the last successful check (ape_model_recover replays them), and what became of aborted launches
     ApeJournalEntry journal[APE_JOURNAL_CAP];
     int journal_n = 0;

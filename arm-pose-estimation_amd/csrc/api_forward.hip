@@ -175,11 +175,13 @@ int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, 
         const bool one_descriptor = ((size_t)(q.N - 1) * q.row_stride + q.row_offset + q.I) * sizeof(float) < 0x80000000ull &&
                                     (size_t)q.N * q.O * sizeof(float) < 0x80000000ull;
         if (m->ffp_ok && m->ffp_on && !m->replaying && !drop && q.hidden_out == nullptr && q.mask == nullptr && one_descriptor && q.N >= 64 * m->n_cus) {
+            m->last_kernel = "ape_mlp_pipe";
             hipError_t e2 = ape_launch_mlp_pipe(q, m->ffp_wa0, m->ffp_wa1, m->ffp_wb2, m->ffp_wbo, m->ffp_ring, m->ffp_ring_bytes, m->ffp_ctl,
                                                m->n_cus, (hipStream_t)stream);
             if (e2 != hipSuccess) return ape_fail(APE_ERR_HIP, "mlp pipeline launch failed: %s", hipGetErrorString(e2));
             return APE_OK;
         }
+        m->last_kernel = "ape_mlp_tile16";
         hipError_t e = ape_launch_mlp_tile16(H, q, (hipStream_t)stream, m->n_cus);
         if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "mlp kernel launch failed: %s", hipGetErrorString(e));
         return APE_OK;

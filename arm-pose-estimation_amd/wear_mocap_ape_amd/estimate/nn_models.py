@@ -323,7 +323,8 @@ class DropoutLSTM:
         return _hip.lib().ape_lstm_kernel_name(self._handle, B, T).decode()
 
     def last_kernel(self) -> str:
-        """the LSTM kernel the newest call on this model launched (``ape_model_last_kernel``)"""
+        """the regressor kernel the newest call on this model launched (``ape_model_last_kernel``): an LSTM kernel, or for a
+        ``DropoutFF`` ``ape_mlp_pipe`` / ``ape_mlp_tile16`` (a forward call) / ``ape_ff_bank_head`` (a bank frame or replay)"""
         return _hip.lib().ape_model_last_kernel(self._handle).decode()
 
     def flops_per_window(self, T: int) -> float:

@@ -156,12 +156,35 @@ def bank_checked_frames(bank):
     return list(range(F)) if S * n_mc <= CHECK_ALL_ROWS else [F - 1]
 
 
-def bank_features(norm_stats, bank):
-    """float32 feature rows [F, S, I]: frame f of stream s"""
+# the banks under their own draws at the magnitudes of tests/test_hostile_inputs_cpu.py (tests/test_hostile_banks_gpu.py): the `lstm.*` tensors
+# scaled by `hi.wscale_of(model, case)` and z-scores from `hi.case_z`; the DropoutFF bank on the like-named case of tests/ff_cases.py
+# (every layer but the output layer scaled).  The windows are 6 or 8 frames: `hi.LONG_SCALE`'s caveat about long windows does not apply
+BANK_CASES = ("trained", "sat30", "z1e3")
+FF_BANK_CASE = {"trained": "w16", "sat30": "sat30", "z1e3": "z1e3"}
+
+
+def bank_state_dict(reg, name, case="benign"):
+    """the weights of a bank's regressor on a case; `benign`: as drawn"""
+    c = orc.MODEL_CONFIGS[name]
+    if reg == "ff":
+        sd = orc.make_ff_state_dict(c["I"], 256, 2, c["O"], W_SEED)
+        if case == "benign":
+            return sd
+        from tests import ff_cases as fc
+        s = np.float32(fc.CASE_WSCALE[FF_BANK_CASE[case]])
+        return {k: v if k.startswith("_output_layer.") else (v * s).astype(np.float32) for k, v in sd.items()}
+    return state_dict(name) if case == "benign" else hi.state_dict(name, hi.wscale_of(name, case), W_SEED)
+
+
+def bank_features(norm_stats, bank, case="benign"):
+    """float32 feature rows [F, S, I]: frame f of stream s (column 0 at 0.02 on every case)"""
     reg, name, S, n_mc, smooth, seed, T, F = bank_dims(bank)
     st, I = norm_stats[name], orc.MODEL_CONFIGS[name]["I"]
-    rng = np.random.default_rng(1000 + S)
-    x = st["xx_m"] + st["xx_s"] * rng.normal(size=(F, S, I))
+    if case == "benign":
+        z = np.random.default_rng(1000 + S).normal(size=(F, S, I))
+    else:
+        z = hi.case_z(case, F, S, I, 1000 + S)
+    x = st["xx_m"] + st["xx_s"] * z
     x[..., 0] = 0.02
     return x.astype(np.float32)
 
@@ -171,7 +194,7 @@ def _clamped(f, start, n):
     return [max(start, f - n + 1 + j) for j in range(n)]
 
 
-def frame_targets(norm_stats, reg, name, feats, windows, key, n_mc, variant, global_rows, with32, ff_base=0):
+def frame_targets(norm_stats, reg, name, feats, windows, key, n_mc, variant, global_rows, with32, ff_base=0, case="benign"):
     """one regressor call of a bank, frame or replay: `windows` [K, T] feature-frame indices per listed window, `feats` [F, K, I] (or
     [F, I] shared by all windows: a replay); sample row k * n_mc + i of the call is global row `global_rows[k * n_mc + i]`
     -> de-normalised targets float64 [K * n_mc, O] (and the float32 oracle's)"""
@@ -183,12 +206,11 @@ def frame_targets(norm_stats, reg, name, feats, windows, key, n_mc, variant, glo
         w = np.stack([feats[windows[k]] for k in range(K)])
     xn = ((w.astype(np.float64) - st["xx_m"]) / st["xx_s"]).astype(np.float32)
     xr = np.repeat(xn, n_mc, axis=0)
+    sd = bank_state_dict(reg, name, case)
     if reg == "ff":
-        sd = orc.make_ff_state_dict(c["I"], 256, 2, c["O"], W_SEED)
         mask = ph.ff_bank_mask(key, global_rows, 256, P, philox_base=ff_base, v=variant)
         ys = [orc.ff_forward(ff_sd64(sd), xr[:, -1], mask=mask)] + ([orc.ff_forward(sd, xr[:, -1], mask=mask)] if with32 else [])
     else:
-        sd = state_dict(name)
         masks = list(ph.lstm_masks(key, global_rows, windows.shape[1], c["H"], c["L"], P, v=variant))
         ys = [hi.forward64(name, sd, xr, masks)[:, -1]] + ([hi.forward32(name, sd, xr, masks)[:, -1]] if with32 else [])
     return [y.astype(np.float64) * st["yy_s"] + st["yy_m"] for y in ys]
@@ -205,15 +227,15 @@ def post_filter(name, stacks):
     return np.array(tails), np.array(msgs)
 
 
-def bank_reference(norm_stats, bank, frames=None, variant=ph.CONTRACT, streams=None, with32=False, feats=None):
+def bank_reference(norm_stats, bank, frames=None, variant=ph.CONTRACT, streams=None, with32=False, feats=None, case="benign"):
     """lockstep frames of a bank: {frame: [(tail, msg) float64 reference, (tail, msg) of the float32 oracle]} for `frames` (default: the
     checked ones) and `streams` (default: all).  Frame f is Monte-Carlo call f of the bank whatever reset() did in between: key
     seed + f; sample row = stream * n_mc + sample.  `feats` float32 [F, S, I]: the frames' feature rows where they are not
-    `bank_features` (host frames: what the device's feature builder made of the raw messages)."""
+    `bank_features` (host frames: what the device's feature builder made of the raw messages).  `case`: weights and features of BANK_CASES."""
     reg, name, S, n_mc, smooth, seed, T, F = bank_dims(bank)
     frames = bank_checked_frames(bank) if frames is None else frames
     streams = np.arange(S) if streams is None else np.asarray(streams)
-    feats = (bank_features(norm_stats, bank) if feats is None else feats)[:, streams]
+    feats = (bank_features(norm_stats, bank, case) if feats is None else feats)[:, streams]
     rows = (streams[:, None] * n_mc + np.arange(n_mc)[None, :]).reshape(-1)
     start = lambda f: RESET_AT if f >= RESET_AT else 0
     need = sorted({g for f in frames for g in _clamped(f, start(f), smooth)})
@@ -221,7 +243,7 @@ def bank_reference(norm_stats, bank, frames=None, variant=ph.CONTRACT, streams=N
     for g in need:
         win = np.array([_clamped(g, start(g), 1 if reg == "ff" else T)] * len(streams))
         y[g] = [t.reshape(len(streams), n_mc, -1) for t in
-                frame_targets(norm_stats, reg, name, feats, win, ph.bank_call_seed(seed, g), n_mc, variant, rows, with32)]
+                frame_targets(norm_stats, reg, name, feats, win, ph.bank_call_seed(seed, g), n_mc, variant, rows, with32, case=case)]
     out = {}
     for f in frames:
         out[f] = [post_filter(name, np.concatenate([y[g][k] for g in _clamped(f, start(f), smooth)], axis=1)) for k in range(2 if with32 else 1)]

@@ -340,8 +340,11 @@ def test_mlp_pipeline_kernel():
         x = rng.normal(size=(N, I)).astype(np.float32)
         xt = torch.from_numpy(x).cuda()
         y_tile = m.set_kernel("tile16")(xt).cpu().numpy()
+        assert m.last_kernel() == "ape_mlp_tile16"
         y_pipe = m.set_kernel("auto")(xt).cpu().numpy()
+        assert m.last_kernel() == "ape_mlp_pipe"
         y_again = m(xt).cpu().numpy()
+        assert m.last_kernel() == "ape_mlp_pipe"
         m.check()
         assert np.abs(y_pipe - y_tile).max() < 1e-6
         assert np.array_equal(y_pipe, y_again)
@@ -352,7 +355,9 @@ def test_mlp_pipeline_kernel():
     raw = (rng.normal(size=(B, T, I)) * st["xx_s"] + st["xx_m"]).astype(np.float32)
     rt = torch.from_numpy(raw).cuda()
     y_tile = m.set_kernel("tile16")(rt, last_step_only=True, normalize_input=True).cpu().numpy()
+    assert m.last_kernel() == "ape_mlp_tile16"
     y_pipe = m.set_kernel("auto")(rt, last_step_only=True, normalize_input=True).cpu().numpy()
+    assert m.last_kernel() == "ape_mlp_pipe"
     m.check()
     assert y_pipe.shape == (B, 1, O) and np.abs(y_pipe - y_tile).max() < 1e-6
     z = ((raw[:, -1].astype(np.float64) - st["xx_m"]) / st["xx_s"]).astype(np.float32)
@@ -361,6 +366,7 @@ def test_mlp_pipeline_kernel():
     x = rng.normal(size=(16384, I)).astype(np.float32)
     mask = ((rng.random((16384, H)) >= 0.2) / 0.8).astype(np.float32)
     ym = m(torch.from_numpy(x).cuda(), masks=torch.from_numpy(mask).cuda()).cpu().numpy()
+    assert m.last_kernel() == "ape_mlp_tile16"
     assert np.abs(ym - orc.ff_forward(sd, x, mask=mask)).max() < 2e-6
 
 

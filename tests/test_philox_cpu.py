@@ -188,6 +188,62 @@ def test_mutants_move_every_bank_case(norm_stats, bank):
         _assert_moved(bank, mut, ph.bank_call_seed(seed, last), pc.quantity_error(got, want), bud)
 
 
+@pytest.mark.parametrize("case", pc.BANK_CASES)
+@pytest.mark.parametrize("bank", sorted(pc.BANKS))
+def test_hostile_bank_cases_are_finite_and_still_tell_a_wrong_counter_reading(norm_stats, bank, case):
+    """the cases of tests/test_hostile_banks_gpu.py: the float64 bank reference stays finite, and at least one wrong reading of the counter
+    contract moves it by MIN_RATIO budgets.  Evaluated on the last frame of up to four streams (rows of one call are independent: those
+    rows of the whole reference), the budget from the same rows; the factor MIN_RATIO covers the whole case's larger e_ref (the GPU test
+    computes that one, and asserts the whole reference finite)"""
+    reg, name, S, n_mc, smooth, seed, T, F = pc.bank_dims(bank)
+    streams = np.arange(S) if S <= 4 else np.array([0, 1, S // 2, S - 1])
+    last = F - 1
+    r64, r32 = pc.bank_reference(norm_stats, bank, [last], streams=streams, with32=True, case=case)[last]
+    assert all(np.isfinite(q).all() for q in r64)
+    bud = pc.budget(pc.quantity_error(r32, r64))
+    moved = {}
+    for mut in MASK_MUTANTS:
+        if (reg == "ff" and mut == "row_unaligned") or not _applies(mut, ph.bank_call_seed(seed, last)):
+            continue
+        got = pc.bank_reference(norm_stats, bank, [last], MUTANTS[mut], streams, case=case)[last][0]
+        moved[mut] = pc.quantity_error(got, r64) / bud
+    print(f"PHILOX|hostile bank|{bank}|{case}|budget {bud:.2e}|" + "|".join(f"{k} {v:.1e}" for k, v in moved.items()))
+    assert max(moved.values()) >= MIN_RATIO, (bank, case, moved)
+
+
+@pytest.mark.parametrize("case", pc.BANK_CASES)
+def test_the_wide_head_bank_cases_tell_a_wrong_counter_reading(norm_stats, case):
+    """the 20-output DropoutFF bank of tests/test_hostile_banks_gpu.py (`ape_ff_bank_head<2>`): whole case, all frames"""
+    from tests.test_hostile_banks_gpu import wide_head_case
+    ref = wide_head_case(norm_stats, case)[3]
+    assert all(np.isfinite(q).all() for f in ref for q in ref[f][0])
+    bud = pc.budget(max(pc.quantity_error(ref[f][1], ref[f][0]) for f in ref))
+    moved = {}
+    for mut in MASK_MUTANTS:
+        if mut != "row_unaligned":
+            other = wide_head_case(norm_stats, case, MUTANTS[mut])[3]
+            moved[mut] = max(pc.quantity_error(other[f][0], ref[f][0]) for f in ref) / bud
+    print(f"PHILOX|hostile bank|ff-wide-head-7x25|{case}|budget {bud:.2e}|" + "|".join(f"{k} {v:.1e}" for k, v in moved.items()))
+    assert max(moved.values()) >= MIN_RATIO, (case, moved)
+
+
+def test_the_default_bank_case_is_the_benign_one(norm_stats):
+    """`case="benign"` of the bank helpers: the weights as drawn and the features of before, bit for bit"""
+    for bank in ("mc_small-3x25", "ff-7x25"):
+        reg, name, S, n_mc, smooth, seed, T, F = pc.bank_dims(bank)
+        st, I = norm_stats[name], pc.orc.MODEL_CONFIGS[name]["I"]
+        x = st["xx_m"] + st["xx_s"] * np.random.default_rng(1000 + S).normal(size=(F, S, I))
+        x[..., 0] = 0.02
+        assert np.array_equal(pc.bank_features(norm_stats, bank), x.astype(np.float32))
+        assert np.array_equal(pc.bank_features(norm_stats, bank, "benign"), pc.bank_features(norm_stats, bank))
+        assert not np.array_equal(pc.bank_features(norm_stats, bank, "z1e3"), pc.bank_features(norm_stats, bank))
+    sd, sd16 = pc.bank_state_dict("lstm", "pocket"), pc.bank_state_dict("lstm", "pocket", "trained")
+    assert all(np.array_equal(sd[k], pc.state_dict("pocket")[k]) for k in sd)
+    assert all(np.array_equal(sd16[k], sd[k] * np.float32(16) if k.startswith("lstm.") else sd[k]) for k in sd)
+    ff, ff16 = pc.bank_state_dict("ff", "pocket"), pc.bank_state_dict("ff", "pocket", "trained")
+    assert all(np.array_equal(ff16[k], ff[k] if k.startswith("_output_layer.") else ff[k] * np.float32(16)) for k in ff)
+
+
 def test_mutants_move_the_subset_frame_and_the_replay(golden, norm_stats):
     q = pc.SUBSET
     feats = pc.host_features(pc.trace_rows(golden, 3 * q["S"], 5)).reshape(3, q["S"], -1)
