@@ -235,6 +235,8 @@ int ape_model_create(const ape_dims_t* dims, ape_model_t** out) {
     if (imupose) {}
     else if (e == hipSuccess && smem <= 160 * 1024) e = ape_prepare_lstm_tile16(H, L, smem);
     else if (e == hipSuccess) e = ape_prepare_lstm_tile16(H, L, ape_lstm_tile16_smem_bytes(H, L, m->KX, O, false));
+    // ... and ape_lstm_features' instantiation of the same body (DropoutLSTM handles only)
+    if (!imupose && e == hipSuccess) e = ape_prepare_lstm_tile16_hout(H, L, ape_lstm_tile16_smem_bytes(H, L, m->KX, O, smem <= 160 * 1024));
     if (e != hipSuccess) {
         ape_model_destroy(m);
         return ape_fail(APE_ERR_HIP, "model allocation failed: %s", hipGetErrorString(e));

@@ -93,6 +93,9 @@ int mc_small_launch(ape_model_t* m, const float* x, size_t x_stream_stride, int 
 int lstm_forward_impl(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t flags, const float* masks_dev, float dropout_p,
                       uint64_t seed, float* y_dev, void* stream, int x_ring, const float* h0_dev = nullptr, const float* c0_dev = nullptr,
                       FkTail* fk = nullptr, long long row_base = 0);
+// ape_lstm_features without its journal entry: h^{L-1}_{T-1} [B,H] and (y_dev != NULL) the head's y [B,O], every row on ape_lstm_tile16<H, L, 4, true>
+int lstm_features_impl(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t flags, const float* masks_dev, float dropout_p,
+                       uint64_t seed, float* h_dev, float* y_dev, void* stream);
 // the regressor of a DropoutFF frame or replay chunk (ff_bank.hip)
 int ff_bank_forward(ape_model* m, const float* x, size_t x_stride, long long row_base, int rows, int n_mc, bool norm, const float* masks,
                     float dropout_p, uint64_t seed, float* hid, float* y, void* stream, hipEvent_t ev_a = nullptr, hipEvent_t ev_z = nullptr,

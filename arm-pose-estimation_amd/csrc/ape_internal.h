@@ -69,6 +69,8 @@ struct LstmParams {
     int hs_rows;                        // batch size of h0 / c0
     long long row_base;                 // DROPOUT_PHILOX: global index of this launch's row 0 in the caller's batch (a multiple of 4;
                                         // 0 for every caller but a chunked one -- ape_replay -- whose chunks must draw the masks of ONE call)
+    float* hout;                        // the HOUT instantiations only: [B,H] the top layer's output of the last step, the vector the head
+                                        // multiplies (last, so that the fields the other instantiations read stay where they were)
 };
 
 // Kernel arguments of the weight-stationary cluster LSTM kernel.
@@ -445,6 +447,8 @@ hipError_t ape_launch_lstm_tile16(int H, int L, const LstmParams& p, hipStream_t
 size_t ape_lstm_tile16_smem_bytes(int H, int L, int KX, int O, bool dropout);
 hipError_t ape_prepare_lstm_tile16(int H, int L, size_t smem_bytes);
 hipError_t ape_prepare_lstm_tile16_wide(size_t smem_bytes);
+hipError_t ape_prepare_lstm_tile16_hout(int H, int L, size_t smem_bytes);     // ape_lstm_features' kernel: the narrow body + p.hout
+hipError_t ape_launch_lstm_tile16_hout(int H, int L, const LstmParams& p, hipStream_t stream);
 hipError_t ape_prepare_lstm_tile16_upper(int H, int L, size_t smem_bytes);   // layers 1.. of a model on their own: <256,1,wide>, <128,2,wide>
 bool ape_cluster_supported(int H, int L, int KX);
 bool ape_cluster_layer0_supported(int H, int KX);

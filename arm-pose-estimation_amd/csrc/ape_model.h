@@ -16,12 +16,12 @@ struct ape_streams;
 // One compute call on a model since its last successful check, kept so that ape_model_recover can re-issue it on the
 // kernels that need no co-residency when a weight-stationary launch gave up (include/ape_hip.h, "Aborted launches").
 struct ApeJournalEntry {
-    enum Kind { FORWARD, FORWARD_HS, FK, MSG, INFER, STEP, SUBSET } kind;
+    enum Kind { FORWARD, FORWARD_HS, FK, MSG, INFER, STEP, SUBSET, FEATURES } kind;
     const void* in0;                 // x / preds / est
     const void* in1;                 // masks / h0
     const void* in2;                 // c0
-    void* out0;                      // y / est / msg
-    void* out1;                      // est (infer) / tail (step)
+    void* out0;                      // y / est / msg / h (features)
+    void* out1;                      // est (infer) / tail (step) / y (features)
     int32_t B, T, i0, i1, i2;        // sizes and dtype selectors
     uint32_t flags;
     float dropout_p;

@@ -306,6 +306,56 @@ int ape_lstm_forward(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, u
     return rc;
 }
 
+// ape_lstm_features behind its journal entry (ape_replay_features runs it per chunk): every row on ape_lstm_tile16<H, L, 4, true>, whatever the
+// planner would pick for (B, T) -- the kernel that has h^{L-1}_{T-1} in LDS at the head, is not cooperative and cannot abort
+int lstm_features_impl(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t flags, const float* masks_dev, float dropout_p,
+                       uint64_t seed, float* h_dev, float* y_dev, void* stream) {
+    if (!m || !x_dev || !h_dev) return ape_fail(APE_ERR_INVALID_ARG, "lstm_features: NULL argument");
+    if (B < 1 || T < 1) return ape_fail(APE_ERR_INVALID_ARG, "lstm_features: B=%d T=%d must be >= 1", B, T);
+    if (flags & APE_FLAG_ALL_STEPS) return ape_fail(APE_ERR_INVALID_ARG, "lstm_features: ALL_STEPS is refused (the last step's vector is the feature)");
+    if (flags & ~(uint32_t)(APE_FLAG_NORMALIZE_INPUT | APE_FLAG_DROPOUT_MASKS | APE_FLAG_DROPOUT_PHILOX))
+        return ape_fail(APE_ERR_INVALID_ARG, "lstm_features: flag bits 0x%x (NORMALIZE_INPUT and the two dropout modes are accepted)", flags);
+    if (m->dims.model_kind != APE_MODEL_LSTM)
+        return ape_fail(APE_ERR_UNSUPPORTED, "lstm_features: DropoutLSTM handles only (not FF / ImuPose)");
+    if (m->precision != APE_PRECISION_F32) return ape_fail(APE_ERR_UNSUPPORTED, "lstm_features: fp16 precision is set on the model (float32 only)");
+    if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "lstm_features: weights not loaded");
+    if ((flags & APE_FLAG_NORMALIZE_INPUT) && !m->has_stats)
+        return ape_fail(APE_ERR_NOT_READY, "lstm_features: NORMALIZE_INPUT without norm stats");
+    if ((flags & APE_FLAG_DROPOUT_MASKS) && (flags & APE_FLAG_DROPOUT_PHILOX))
+        return ape_fail(APE_ERR_INVALID_ARG, "lstm_features: choose one dropout mode");
+    if ((flags & APE_FLAG_DROPOUT_MASKS) && m->dims.num_layers > 1 && !masks_dev)
+        return ape_fail(APE_ERR_INVALID_ARG, "lstm_features: DROPOUT_MASKS without masks");
+    if ((flags & APE_FLAG_DROPOUT_PHILOX) && !(dropout_p >= 0.0f && dropout_p < 1.0f))
+        return ape_fail(APE_ERR_INVALID_ARG, "lstm_features: dropout_p %f outside [0,1)", dropout_p);
+    const int H = m->dims.hidden_size, L = m->dims.num_layers;
+    const bool drop = (flags & (APE_FLAG_DROPOUT_MASKS | APE_FLAG_DROPOUT_PHILOX)) != 0;
+    if (ape_lstm_tile16_smem_bytes(H, L, m->KX, m->dims.output_size, drop) > 160 * 1024)
+        return ape_fail(APE_ERR_UNSUPPORTED, "lstm_features: H=%d L=%d with dropout exceeds the 160 KiB LDS of a CU", H, L);
+    LstmParams p{};
+    p.x = x_dev; p.y = y_dev; p.hout = h_dev;
+    for (int l = 0; l < L; ++l) { p.wpack[l] = m->wpack[l]; p.bias[l] = m->bias[l]; }
+    head_and_stats(m, &p);
+    p.masks = masks_dev; p.flags = flags; p.dropout_p = dropout_p; p.seed = seed;
+    p.B = B; p.T = T; p.I = m->lstm_in; p.O = m->dims.output_size; p.KX = m->KX;
+    p.hs_rows = B;
+    m->last_kernel = "ape_lstm_tile16<hout>";
+    hipError_t e = ape_launch_lstm_tile16_hout(H, L, p, (hipStream_t)stream);
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "lstm features kernel launch failed: %s", hipGetErrorString(e));
+    return APE_OK;
+}
+
+int ape_lstm_features(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t flags, const float* masks_dev, float dropout_p,
+                      uint64_t seed, float* h_dev, float* y_dev, void* stream) {
+    const int rc = lstm_features_impl(m, x_dev, B, T, flags, masks_dev, dropout_p, seed, h_dev, y_dev, stream);
+    if (rc == APE_OK) {      // (reads what an aborted launch in front of it may have left unwritten: re-issued behind it like a forward)
+        ApeJournalEntry e{};
+        e.kind = ApeJournalEntry::FEATURES; e.in0 = x_dev; e.in1 = masks_dev; e.out0 = h_dev; e.out1 = y_dev; e.B = B; e.T = T; e.flags = flags;
+        e.dropout_p = dropout_p; e.seed = seed; e.stream = stream;
+        journal_add(m, e);
+    }
+    return rc;
+}
+
 int ape_lstm_forward_hs(ape_model_t* m, const float* x_dev, int32_t B, int32_t T, uint32_t flags,
                         const float* masks_dev, float dropout_p, uint64_t seed, const float* h0_dev,
                         const float* c0_dev, float* y_dev, void* stream) {

@@ -253,6 +253,64 @@ int ape_replay_resume(ape_model_t* m, int32_t kind, const float* rows_dev, int32
                        max_rows_per_launch, stream, bodies_host, true, &rs);
 }
 
+// The hidden features of every frame of whole recordings: replay_impl's front half -- feature rows, every frame's
+// recording, the windows of a chunk, each recording starting cold as ape_replay starts it -- then ape_lstm_features per chunk.  One row
+// per frame, no dropout, no post-filter, no state in or out.  The batch-tile kernel cannot abort: one pass, then the wait.
+int ape_replay_features(ape_model_t* m, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                        int32_t seq_len, uint32_t flags, float* h_dev, float* y_dev, int32_t max_rows_per_launch, void* stream) {
+    if (!rows_dev || !h_dev) return ape_fail(APE_ERR_INVALID_ARG, "replay_features: NULL argument");
+    int width, I;
+    const int big_endian = (kind & APE_PARSE_BIG_ENDIAN) ? 1 : 0;
+    if (!parse_kind_dims(kind & ~APE_PARSE_BIG_ENDIAN, &width, &I)) return ape_fail(APE_ERR_INVALID_ARG, "replay_features: unknown kind %d", kind);
+    if (int rc = ape_check_segments("replay_features", F, seg_starts_host, R)) return rc;
+    if (seq_len < 1) return ape_fail(APE_ERR_INVALID_ARG, "replay_features: seq_len=%d must be >= 1", seq_len);
+    if (flags & ~(uint32_t)APE_FLAG_NORMALIZE_INPUT) return ape_fail(APE_ERR_INVALID_ARG, "replay_features: only NORMALIZE_INPUT is accepted");
+    if (max_rows_per_launch < 0 || (max_rows_per_launch > 0 && max_rows_per_launch < 16))
+        return ape_fail(APE_ERR_INVALID_ARG, "replay_features: max_rows_per_launch=%d (0 = default, else >= 16)", max_rows_per_launch);
+    if (!m) return ape_fail(ape_device_count() == 0 ? APE_ERR_NO_DEVICE : APE_ERR_INVALID_ARG,
+                        "replay_features: NULL model (no gfx950 device: there is no CPU fallback)");
+    if (m->dims.model_kind != APE_MODEL_LSTM)
+        return ape_fail(APE_ERR_UNSUPPORTED, "replay_features: DropoutLSTM handles only (not FF / ImuPose)");
+    if (m->precision != APE_PRECISION_F32) return ape_fail(APE_ERR_UNSUPPORTED, "replay_features: fp16 precision is set on the model (float32 only)");
+    if (I != m->dims.input_size)
+        return ape_fail(APE_ERR_INVALID_ARG, "replay_features: kind %d builds %d features, the model takes %d", kind & ~APE_PARSE_BIG_ENDIAN, I,
+                        m->dims.input_size);
+    if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "replay_features: weights not loaded");
+    if ((flags & APE_FLAG_NORMALIZE_INPUT) && !m->has_stats) return ape_fail(APE_ERR_NOT_READY, "replay_features: NORMALIZE_INPUT without norm stats");
+    APE_TRY(hipSetDevice(m->dims.device));
+    if (int rc = ape_check_not_capturing((hipStream_t)stream, "replay_features", nullptr)) return rc;
+    if (int rc = ape_model_recover(m)) return rc;
+
+    const hipStream_t st = (hipStream_t)stream;
+    const int T = seq_len, H = m->dims.hidden_size, O = m->dims.output_size;
+    long long rmax = max_rows_per_launch > 0 ? max_rows_per_launch : APE_REPLAY_WINDOW_BYTES / ((long long)T * I * sizeof(float));
+    rmax = rmax / 16 * 16;
+    if (rmax < 16) rmax = 16;
+    if (rmax > ((long long)F + 15) / 16 * 16) rmax = ((long long)F + 15) / 16 * 16;
+    ApeDeviceScratch ws;
+    float *xx, *xw;
+    int *starts_d, *seg_of;
+    APE_TRY(ws.alloc((void**)&xx, (size_t)F * I * sizeof(float)));
+    APE_TRY(ws.alloc((void**)&seg_of, (size_t)F * sizeof(int)));
+    APE_TRY(ws.alloc((void**)&starts_d, (size_t)R * sizeof(int)));
+    APE_TRY(ws.alloc((void**)&xw, (size_t)rmax * T * I * sizeof(float)));
+    APE_TRY(hipMemcpyAsync(starts_d, seg_starts_host, (size_t)R * sizeof(int), hipMemcpyHostToDevice, st));
+    hipError_t e = ape_launch_parse_rows(rows_dev, F, width, kind & ~APE_PARSE_BIG_ENDIAN, xx, APE_F32, I, (size_t)I, 1, 0, big_endian, st);
+    if (e == hipSuccess) e = ape_launch_replay_segments(starts_d, R, F, seg_of, st, nullptr);
+    if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "replay_features: feature launch failed: %s", hipGetErrorString(e));
+    for (long long r0 = 0; r0 < F; r0 += rmax) {
+        const int rows = (int)(F - r0 < rmax ? F - r0 : rmax);
+        ReplayWindowParams wp{};
+        wp.xx = xx; wp.seg_of = seg_of; wp.xw = xw; wp.r0 = r0; wp.R = rows; wp.T = T; wp.I = I; wp.n_mc = 1;
+        e = ape_launch_replay_windows(wp, st, nullptr);
+        if (e != hipSuccess) return ape_fail(APE_ERR_HIP, "replay_features: window launch failed: %s", hipGetErrorString(e));
+        if (int rc = lstm_features_impl(m, xw, rows, T, flags, nullptr, 0.0f, 0, h_dev + (size_t)r0 * H, y_dev ? y_dev + (size_t)r0 * O : nullptr, stream))
+            return rc;
+    }
+    APE_TRY(hipStreamSynchronize(st));
+    return APE_OK;
+}
+
 // one journaled call again, on the kernels that need no co-residency (m->replaying is set)
 int replay_entry(ape_model_t* m, const ApeJournalEntry& e) {
     switch (e.kind) {
@@ -261,6 +319,9 @@ int replay_entry(ape_model_t* m, const ApeJournalEntry& e) {
         case ApeJournalEntry::FORWARD_HS:
             return ape_lstm_forward_hs(m, (const float*)e.in0, e.B, e.T, e.flags, nullptr, e.dropout_p, e.seed, (const float*)e.in1,
                                        (const float*)e.in2, (float*)e.out0, e.stream);
+        case ApeJournalEntry::FEATURES:
+            return ape_lstm_features(m, (const float*)e.in0, e.B, e.T, e.flags, (const float*)e.in1, e.dropout_p, e.seed, (float*)e.out0,
+                                     (float*)e.out1, e.stream);
         case ApeJournalEntry::FK:
             return ape_fk(m, e.in0, e.i0, e.B, e.i1, e.out0, e.i2, e.stream);
         case ApeJournalEntry::MSG:

@@ -105,3 +105,33 @@ int ape_model_load_weights(ape_model_t* m, const float* blob, size_t n_floats) {
     m->has_weights = true;
     return APE_OK;
 }
+
+// ---- the output layer on its own ------------------------------------------------------------------------------------
+// Every kernel of a DropoutLSTM handle reads the head through m->w_out / m->b_out (head_and_stats; no route packs it), so a new head is
+// two copies.  The handle is made healthy and idle first: what was issued before runs on the head it was issued with.
+static int head_ready(ape_model_t* m, const void* w, const void* b, const char* who) {
+    if (!m || !w || !b) return ape_fail(APE_ERR_INVALID_ARG, "%s: NULL argument", who);
+    if (m->dims.model_kind != APE_MODEL_LSTM)
+        return ape_fail(APE_ERR_UNSUPPORTED, "%s: DropoutLSTM handles only (the other kinds' kernels read packed copies of the head)", who);
+    if (!m->has_weights) return ape_fail(APE_ERR_NOT_READY, "%s: weights not loaded", who);
+    APE_TRY(hipSetDevice(m->dims.device));
+    if (int rc = ape_model_recover(m)) return rc;
+    APE_TRY(hipDeviceSynchronize());
+    return APE_OK;
+}
+
+int ape_model_set_head(ape_model_t* m, const float* w_out_host, const float* b_out_host) {
+    if (int rc = head_ready(m, w_out_host, b_out_host, "set_head")) return rc;
+    const size_t O = (size_t)m->dims.output_size, H = (size_t)m->dims.hidden_size;
+    APE_TRY(hipMemcpy(m->w_out, w_out_host, O * H * sizeof(float), hipMemcpyHostToDevice));
+    APE_TRY(hipMemcpy(m->b_out, b_out_host, O * sizeof(float), hipMemcpyHostToDevice));
+    return APE_OK;
+}
+
+int ape_model_get_head(ape_model_t* m, float* w_out_host, float* b_out_host) {
+    if (int rc = head_ready(m, w_out_host, b_out_host, "get_head")) return rc;
+    const size_t O = (size_t)m->dims.output_size, H = (size_t)m->dims.hidden_size;
+    APE_TRY(hipMemcpy(w_out_host, m->w_out, O * H * sizeof(float), hipMemcpyDeviceToHost));
+    APE_TRY(hipMemcpy(b_out_host, m->b_out, O * sizeof(float), hipMemcpyDeviceToHost));
+    return APE_OK;
+}

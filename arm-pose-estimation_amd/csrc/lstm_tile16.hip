@@ -46,7 +46,10 @@ __device__ __forceinline__ void mfma_block(f32x4 (&acc)[NT], const f32x4 a, cons
     }
 }
 
-template <int H, int L, int XE>
+// HOUT (ape_lstm_features' instantiations): the top layer's last hidden state, the vector the head multiplies, goes to p.hout [B,H] too,
+// copied from the LDS rows the head reads, behind the last step's barrier.
+// A template parameter, so that the instantiations without it keep their instruction streams.
+template <int H, int L, int XE, bool HOUT = false>
 __global__ __launch_bounds__(256, 1) void ape_lstm_tile16(const LstmParams p) {
     constexpr int UB = H / 64;        // 16-unit blocks per wave
     constexpr int NT = 4 * UB;        // accumulator tiles per wave (4 gates x UB)
@@ -336,6 +339,15 @@ __global__ __launch_bounds__(256, 1) void ape_lstm_tile16(const LstmParams p) {
             TS(4)                                        // 4: barrier
         }
 
+        // ---- (HOUT) h^{L-1}_{T-1}, the vector the head multiplies: from its LDS rows to p.hout [B,H], 16 bytes per lane ------------
+        if (HOUT && t == T - 1) {
+            for (int idx = tid * 4; idx < APE_TILE_ROWS * H; idx += 256 * 4) {
+                const int row = idx / H, k = idx - row * H, b = row0 + row;
+                if (b < p.B)
+                    *reinterpret_cast<f32x4*>(p.hout + (size_t)b * H + k) =
+                        *reinterpret_cast<const f32x4*>(hbuf + (((L - 1) * 2 + cur) * APE_TILE_ROWS + row) * SH + k);
+            }
+        }
         // ---- linear head on h^{L-1}_t: output_layer of nn_models.py:189 -----------------------------
         if (p.y != nullptr && (all_steps || t == T - 1)) {
             if (tid < APE_TILE_ROWS * O) {
@@ -370,12 +382,27 @@ hipError_t launch(const LstmParams& p, hipStream_t stream) {
     return hipGetLastError();
 }
 
+template <int H, int L>
+hipError_t launch_hout(const LstmParams& p, hipStream_t stream) {
+    const bool drop = (p.flags & (APE_FLAG_DROPOUT_MASKS | APE_FLAG_DROPOUT_PHILOX)) != 0 && L > 1;
+    const size_t smem = ape_lstm_tile16_smem_bytes(H, L, p.KX, p.O, drop);
+    const int grid = (p.B + APE_TILE_ROWS - 1) / APE_TILE_ROWS;
+    hipLaunchKernelGGL((ape_lstm_tile16<H, L, 4, true>), dim3(grid), dim3(256), smem, stream, p);
+    return hipGetLastError();
+}
+
 // the attribute is per kernel instantiation and process-wide: it is raised to the CU's whole LDS, never to one
 // model's own need (a later model with a smaller layout must not lower it under an earlier one's launches)
 template <int H, int L, int XE = 4>
 hipError_t prepare(size_t smem) {
     if (smem > APE_LDS_BYTES) return hipErrorInvalidValue;
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_lstm_tile16<H, L, XE>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, APE_LDS_BYTES);
+}
+template <int H, int L>
+hipError_t prepare_hout(size_t smem) {
+    if (smem > APE_LDS_BYTES) return hipErrorInvalidValue;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&ape_lstm_tile16<H, L, 4, true>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, APE_LDS_BYTES);
 }
 
@@ -413,6 +440,13 @@ hipError_t ape_launch_lstm_tile16(int H, int L, const LstmParams& p, hipStream_t
         return hipErrorInvalidValue;
     }
     APE_DISPATCH(launch, p, stream)
+}
+
+// the features kernel (narrow input only: the LSTM regressors' own x)
+hipError_t ape_prepare_lstm_tile16_hout(int H, int L, size_t smem_bytes) { APE_DISPATCH(prepare_hout, smem_bytes) }
+hipError_t ape_launch_lstm_tile16_hout(int H, int L, const LstmParams& p, hipStream_t stream) {
+    if (p.KX > 64 || p.hout == nullptr) return hipErrorInvalidValue;
+    APE_DISPATCH(launch_hout, p, stream)
 }
 
 hipError_t ape_prepare_lstm_tile16_wide(size_t smem_bytes) { return prepare<256, 2, 16>(smem_bytes); }

@@ -42,6 +42,7 @@ HIST_MAX_BINS, HIST_MAX_WIDTH = 256, 16     # APE_HIST_MAX_BINS, APE_HIST_MAX_WI
 ANGLE_WIDTH, ANGLE_ACC_WIDTH = 7, 71        # APE_ANGLE_WIDTH, APE_ANGLE_ACC_WIDTH (ape_joint_angles)
 BY_MAX_KEYS, BY_MAX_VALUES, BY_MAX_BINS, BY_PIECE = 8, 16, 125, 1024    # APE_BY_* (ape_score_by)
 SPECTRA_DETREND, SPECTRA_MAX_N, SPECTRA_MAX_COLS = 0x1, 512, 16        # APE_SPECTRA_* (ape_spectra)
+FIT_PIECE, FIT_MAX_P, FIT_MAX_Q = 512, 256, 32        # APE_FIT_* (ape_fit_sums)
 FLAG_ANY_PLACEMENT, FLAG_NO_XCD_CLASSES, FLAG_ALT_FORM = 0x08000000, 0x02000000, 0x01000000    # exchange-form selectors (A/B runs, tests)
 FLAG_IN_XCD_PLAIN = 0x00400000      # opt-in: plain hand-over stores inside an XCD-pure cluster (the default is write-through)
 KERNEL_AUTO, KERNEL_TILE16, KERNEL_CLUSTER, KERNEL_CLUSTER_GEN1, KERNEL_AUTO_GEN1 = 0, 1, 2, 3, 4
@@ -287,6 +288,18 @@ SIGNATURES["ape_score_by"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_in
 SIGNATURES["ape_spectra"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p, C.c_int32, C.c_int64, C.c_int64,
                                        C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p])
+# the output layer fitted to a wearer.  Features: ape_lstm_forward's arguments with h in front of y.  Replay features:
+# model, kind, rows, F, starts_host, R, seq_len, flags, h, y | NULL, max_rows_per_launch, HIP stream.  The sums: x + stride (int64) + dtype,
+# P, t + stride (int64) + dtype, Q, shift_host | NULL, scale_host | NULL, F, starts_host, R, skip, rec_lag_host | NULL, acc, HIP stream.
+# The head: model, w_out_host [O, H] float32, b_out_host [O] float32
+SIGNATURES["ape_lstm_features"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32, C.c_void_p, C.c_float, C.c_uint64,
+                                             C.c_void_p, C.c_void_p, C.c_void_p])
+SIGNATURES["ape_replay_features"] = (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_uint32,
+                                               C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p])
+SIGNATURES["ape_fit_sums"] = (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64, C.c_int32, C.c_int32, C.c_void_p,
+                                        C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p])
+SIGNATURES["ape_model_set_head"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
+SIGNATURES["ape_model_get_head"] = (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p])
 
 _lib = None
 

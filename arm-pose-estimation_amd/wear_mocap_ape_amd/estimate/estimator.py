@@ -631,6 +631,75 @@ class Estimator:
             res = (res if isinstance(res, tuple) else (res,)) + ((state_out, warm_out),)
         return res
 
+    # ---- the output layer fitted to a wearer (the reference has no counterpart) ----
+    def features_recording(self, rows, starts=None, big_endian: bool = False, max_rows_per_launch: int = 0, return_targets: bool = False):
+        """rows, ``starts``, ``big_endian``, ``max_rows_per_launch``: as in ``process_recording``.  Returns, on the device, float32
+        ``[F, H]``: for every frame the top LSTM layer's output of the last step of its window, the vector ``output_layer`` multiplies
+        (``ape_replay_features``: one row per frame, no dropout, every recording starts cold as a replay starts it); with
+        ``return_targets`` also the normalised NN targets ``[F, O]`` the present head makes of them.  ``DropoutLSTM`` models only."""
+        import ctypes as C
+        from wear_mocap_ape_amd import _hip
+        model = self._hip_model()
+        if model is None or self._parse_kind is None:
+            raise UserWarning("this estimator has no HIP regressor or no batched feature builder")
+        width = _hip.PARSE_SHAPES[self._parse_kind][0]
+        dev = model.torch_device
+        with torch.cuda.device(dev):
+            rd = torch.as_tensor(rows, dtype=torch.float32).to(dev).contiguous()
+            if rd.dim() != 2 or rd.shape[1] != width or rd.shape[0] < 1:
+                raise UserWarning(f"expected rows [F>=1,{width}], got {tuple(rd.shape)}")
+            F = int(rd.shape[0])
+            st = np.ascontiguousarray(np.asarray([0] if starts is None else starts, dtype=np.int32).reshape(-1))
+            h = torch.empty((F, model.hidden_layer_size), dtype=torch.float32, device=dev)
+            y = torch.empty((F, model.output_size), dtype=torch.float32, device=dev) if return_targets else None
+            kind = self._parse_kind | (_hip.PARSE_BIG_ENDIAN if big_endian else 0)
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _hip.check(_hip.lib().ape_replay_features(model.handle, kind, C.c_void_p(rd.data_ptr()), F, C.c_void_p(st.ctypes.data),
+                                                      int(st.shape[0]), self._sequence_len, _hip.FLAG_NORMALIZE_INPUT if self._normalize else 0,
+                                                      C.c_void_p(h.data_ptr()), C.c_void_p(y.data_ptr()) if y is not None else None,
+                                                      int(max_rows_per_launch), stream), "ape_replay_features")
+            model._pending.clear()         # the call is blocking and checked the handle (its journal is empty)
+        return (h, y) if return_targets else h
+
+    def fit_head(self, rows, truth, starts=None, skip=None, rec_lags=None, ridge: float = 1e-3, install: bool = False,
+                 big_endian: bool = False, max_rows_per_launch: int = 0, min_pairs=None):
+        """A linear probe: the LSTM stays, ``output_layer`` is fitted again to these recordings.  ``rows``, ``starts``: as in
+        ``features_recording``; ``truth``: device ``[F, O]`` de-normalised NN targets, as ``score_recording(truth_kind="targets")`` takes
+        them (this estimator's ``yy_m`` / ``yy_s`` go in as shift and scale when it normalises: the fit is in the head's own units);
+        ``skip`` defaults to the ``sequence_len - 1`` cold-start frames; ``rec_lags``: each recording's lag, as ``score.best_lag`` finds
+        it; ``ridge``: the pull towards the present head, ``min_pairs``: the fewest pairs a fit is made from, ``2 (H + 1)`` by default
+        (``score.best_head``; ``score.sweep_ridge`` prices candidates on the sums this returns).  Returns ``(w [O, H], b [O], report, sums)``; ``install`` also makes it this estimator's head (``set_head``)
+        unless the fit was refused."""
+        from wear_mocap_ape_amd import score
+        h = self.features_recording(rows, starts, big_endian, max_rows_per_launch)
+        td = torch.as_tensor(truth).to(h.device)
+        if td.dtype not in (torch.float32, torch.float64):
+            td = td.to(torch.float64)
+        skip = self._sequence_len - 1 if skip is None else skip
+        shift, scale = (self._yy_m, self._yy_s) if self._normalize else (None, None)
+        sums = score.fit_sums(h, td, starts, skip, rec_lags, shift, scale)
+        w0, b0 = self.head
+        w, b, report = score.best_head(sums, w0, b0, ridge, min_pairs=min_pairs)
+        if install and not report["refused"]:
+            self.set_head(w, b)
+        return w, b, report, sums
+
+    def set_head(self, w, b):
+        """installs ``output_layer.weight`` ``[O, H]`` and ``.bias`` ``[O]`` on the regressor (``DropoutLSTM.set_head``: the device handle and
+        the kept ``state_dict``), so ``process_row``, the banks, replays and the reference-style methods all run on it"""
+        model = self._hip_model()
+        if model is None:
+            raise UserWarning("this estimator has no HIP regressor")
+        model.set_head(w, b)
+
+    @property
+    def head(self):
+        """``(w [O, H], b [O])`` float32: the output layer the regressor runs"""
+        model = self._hip_model()
+        if model is None:
+            raise UserWarning("this estimator has no HIP regressor")
+        return model.get_head()
+
     # ---- scoring a replay against ground truth (DESIGN.md 4.31; the reference has no counterpart) ----
     def score_recording(self, out, truth, spread=None, starts=None, skip=None, bonemaps=None, truth_kind="targets", lags=None,
                         rec_lags=None):

@@ -279,6 +279,72 @@ class DropoutLSTM:
         # x.repeat((n_samples, 1, 1)) of nn_models.py:206 happens inside the kernel (APE_FLAG_BROADCAST_X)
         return self.forward(x, hs, last_step_only=last_step_only, rows=n_samples)
 
+    # ---- the output layer on its own (the reference has no counterpart) ------------
+    def features(self, x, normalize_input=False, masks=None, dropout_p=None, seed=0):
+        """``(h, y)``: float32 ``[B, H]``, the top layer's output of the last step -- the vector ``output_layer`` multiplies -- and
+        ``[B, O]``, what the same launch's head makes of it (``ape_lstm_features``; every row on the batch-tile kernel).  ``masks``
+        as in ``forward``; ``dropout_p`` with ``seed``: in-kernel dropout.  Results are returned where ``x`` was.  ``DropoutFF`` and
+        ``ImuPoseLSTM`` are refused."""
+        import ctypes as C
+        if not isinstance(x, torch.Tensor):
+            x = torch.as_tensor(np.asarray(x), dtype=torch.float32)
+        if x.dim() != 3 or x.shape[2] != self.input_size or x.shape[0] < 1 or x.shape[1] < 1:
+            raise UserWarning(f"expected x of shape [B>=1,T>=1,{self.input_size}], got {tuple(x.shape)}")
+        on_host, dev = not x.is_cuda, self.torch_device
+        flags = _hip.FLAG_NORMALIZE_INPUT if normalize_input else 0
+        with torch.cuda.device(dev):
+            xd = x.to(device=dev, dtype=torch.float32).contiguous()
+            B, T = int(xd.shape[0]), int(xd.shape[1])
+            h = torch.empty((B, self.hidden_layer_size), dtype=torch.float32, device=dev)
+            y = torch.empty((B, self.output_size), dtype=torch.float32, device=dev)
+            mptr = None
+            if masks is not None:
+                masks = masks.to(device=dev, dtype=torch.float32).contiguous()
+                want = self._mask_shape(B, T, True)
+                if tuple(masks.shape) != want:
+                    raise UserWarning(f"masks must have shape {want}, got {tuple(masks.shape)}")
+                mptr = C.c_void_p(masks.data_ptr())
+                flags |= _hip.FLAG_DROPOUT_MASKS
+            elif dropout_p is not None:
+                flags |= _hip.FLAG_DROPOUT_PHILOX
+            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            _hip.check(_hip.lib().ape_lstm_features(self._handle, C.c_void_p(xd.data_ptr()), B, T, flags, mptr,
+                                                    float(dropout_p or 0.0), int(seed), C.c_void_p(h.data_ptr()),
+                                                    C.c_void_p(y.data_ptr()), stream), "ape_lstm_features")
+        self._pending.append((xd, y, masks, h))          # (journaled like a forward: alive until the next check)
+        if len(self._pending) > 64:
+            del self._pending[0]
+        if on_host:
+            self.recover()
+            return h.cpu(), y.cpu()
+        return h, y
+
+    def set_head(self, w, b):
+        """installs ``output_layer.weight`` ``[O, H]`` and ``.bias`` ``[O]`` on the handle (``ape_model_set_head``: synchronous; every
+        route, bank and replay of this model runs on it from here on) and in the kept ``state_dict``.  ``DropoutLSTM`` only."""
+        import ctypes as C
+        O, H = self.output_size, self.hidden_layer_size
+        wa = np.ascontiguousarray(w.detach().cpu().numpy() if isinstance(w, torch.Tensor) else w, dtype=np.float32)
+        ba = np.ascontiguousarray(b.detach().cpu().numpy() if isinstance(b, torch.Tensor) else b, dtype=np.float32).reshape(-1)
+        if tuple(wa.shape) != (O, H) or ba.shape[0] != O:
+            raise UserWarning(f"set_head: expected w [{O},{H}] and b [{O}], got {tuple(wa.shape)} and {tuple(ba.shape)}")
+        if not (np.isfinite(wa).all() and np.isfinite(ba).all()):
+            raise UserWarning("set_head: the head must be finite")
+        _hip.check(_hip.lib().ape_model_set_head(self._handle, C.c_void_p(wa.ctypes.data), C.c_void_p(ba.ctypes.data)), "ape_model_set_head")
+        self._pending.clear()                # (the entry recovered the handle: its journal is empty)
+        if self._state is not None:
+            self._state["output_layer.weight"], self._state["output_layer.bias"] = wa.copy(), ba.copy()
+        return self
+
+    def get_head(self):
+        """``(w [O, H], b [O])`` float32 host arrays: the head the handle runs (``ape_model_get_head``)"""
+        import ctypes as C
+        wa = np.empty((self.output_size, self.hidden_layer_size), dtype=np.float32)
+        ba = np.empty((self.output_size,), dtype=np.float32)
+        _hip.check(_hip.lib().ape_model_get_head(self._handle, C.c_void_p(wa.ctypes.data), C.c_void_p(ba.ctypes.data)), "ape_model_get_head")
+        self._pending.clear()
+        return wa, ba
+
     def set_kernel(self, choice: str = "auto"):
         """'auto' | 'tile16' | 'cluster' | 'cluster_gen1' (cluster kernels of the first generation only) | 'auto_gen1'
         (auto's dispatch without the second-generation kernels): which LSTM kernel ``forward`` launches (A/B runs, tests)"""

@@ -72,6 +72,12 @@ At which frequencies: ``spectra`` takes Welch sums of any per-frame columns agai
 frequency bin on the float64 matrix cores (``ape_spectra``); ``summarise_spectra`` reads densities, the gain, phase and
 delay of the estimate against the truth, the coherence and the error's spectrum off them, ``bandwidth`` and ``band_power`` reduce those,
 ``merge_spectra`` adds records, ``pose_cols`` and ``pose_spectra`` pick the hand and elbow positions; ``spectra_numpy`` is the host
+statement.
+
+Acting on the regressor's own error: ``fit_sums`` takes, per recording, the normal-equation sums of ``[h, 1, t]`` -- the hidden features
+``Estimator.features_recording`` returns, a one, the truth targets -- on the float64 matrix cores (``ape_fit_sums``, DESIGN.md 4.47);
+``best_head`` solves them for an output layer fitted to the wearer under a ridge towards the present one, ``sweep_ridge`` prices ridges
+leave-one-recording-out from the sums alone, ``price_head`` prices any head, ``merge_fit`` adds records; ``fit_sums_numpy`` is the host
 statement."""
 import ctypes as C
 import math
@@ -3409,3 +3415,272 @@ def pose_spectra(layout: int, out, truth=None, truth_kind: str = "est", starts=N
         truth = resample_truth(layout, truth, "targets", starts, None, None, int(out.shape[-2]), starts, None, 0.0, bodies)
     return spectra(out, truth, pose_cols(layout, "msg"), None if truth is None else pose_cols(layout, "est"), n, hop, taper, detrend, starts,
                    skip)
+
+
+# ---- the output layer fitted to a wearer (the reference has no counterpart) ---------------------------------------------
+FIT_PIECE, FIT_MAX_P, FIT_MAX_Q = _hip.FIT_PIECE, _hip.FIT_MAX_P, _hip.FIT_MAX_Q
+
+
+def _fit_affine(shift, scale, Q: int):
+    """(shift, scale) float64 ``[Q]`` or None each: finite, the scale not zero"""
+    out = []
+    for name, v in (("shift", shift), ("scale", scale)):
+        if v is None:
+            out.append(None)
+            continue
+        a = np.ascontiguousarray(np.asarray(v, dtype=np.float64).reshape(-1))
+        if a.shape[0] != Q or not np.isfinite(a).all() or (name == "scale" and (a == 0.0).any()):
+            raise UserWarning(f"{name}: {Q} finite values" + (", none of them zero" if name == "scale" else ""))
+        out.append(a)
+    return out
+
+
+def _fit_lags(rec_lags, R: int):
+    if rec_lags is None:
+        return None
+    l = np.ascontiguousarray(np.asarray(rec_lags, dtype=np.int32).reshape(-1))
+    if l.shape[0] != R:
+        raise UserWarning(f"rec_lags: one lag per recording ({R}), got {l.shape[0]}")
+    return l
+
+
+def fit_sums_numpy(x, t, starts=None, skip: int = 0, rec_lags=None, shift=None, scale=None) -> np.ndarray:
+    """The host statement of ``fit_sums``, the order of the pieces included: float64 ``[R, M * M + 2]``, ``M = P + 1 + Q``.  Per
+    recording ``[s, e)`` with lag ``l`` the support is the frames ``f >= s + skip`` with ``s <= f - l < e``; ``z_f = [x_f, 1,
+    (t_{f-l} - shift) / scale]`` in float64, a row of zeros where any of the pair's ``P + Q`` values is not finite (or a truth value
+    overflows under shift and scale); the support is cut into pieces of ``FIT_PIECE`` frames from its first, a piece's sums are
+    ``Z'Z`` (the device chains fused multiply-adds in frame order: another order of the same terms), the pieces are added in order
+    from ``+0.0``, and ``(j, i)`` is a copy of ``(i, j)``.  ``[M * M]``, ``[M * M + 1]``: pairs summed and left out."""
+    xa, ta = np.asarray(x), np.asarray(t)
+    if xa.ndim != 2 or ta.ndim != 2 or xa.shape[0] != ta.shape[0] or min(xa.shape) < 1 or min(ta.shape) < 1:
+        raise UserWarning(f"x and t: expected [F, P] and [F, Q], got {tuple(xa.shape)} and {tuple(ta.shape)}")
+    xa, ta = xa.astype(np.float64), ta.astype(np.float64)
+    F, P, Q = xa.shape[0], xa.shape[1], ta.shape[1]
+    M = P + 1 + Q
+    sh, sc = _fit_affine(shift, scale, Q)
+    st = _recording_starts(starts).astype(np.int64)
+    R = st.shape[0]
+    lags = _fit_lags(rec_lags, R)
+    ends = np.r_[st[1:], F]
+    out = np.zeros((R, M * M + 2))
+    iu = np.triu_indices(M, 1)
+    with np.errstate(all="ignore"):
+        for r in range(R):
+            s, e, l = int(st[r]), int(ends[r]), int(lags[r]) if lags is not None else 0
+            lo, up = s + max(int(skip), l), e + min(0, l)
+            if up <= lo:
+                continue
+            f = np.arange(lo, up)
+            tt = ta[f - l]
+            tz = (tt - (0.0 if sh is None else sh)) / (1.0 if sc is None else sc)
+            ok = np.isfinite(xa[f]).all(axis=1) & np.isfinite(tt).all(axis=1) & np.isfinite(tz).all(axis=1)
+            Z = np.concatenate([xa[f], np.ones((f.shape[0], 1)), tz], axis=1)
+            Z[~ok] = 0.0
+            G = np.zeros((M, M))
+            for p0 in range(0, Z.shape[0], FIT_PIECE):
+                Zp = Z[p0:p0 + FIT_PIECE]
+                G = G + Zp.T @ Zp
+            G[iu[1], iu[0]] = G[iu]
+            out[r, :M * M] = G.reshape(-1)
+            out[r, M * M], out[r, M * M + 1] = ok.sum(), (~ok).sum()
+    return out
+
+
+def _fit_view(t, what: str):
+    """(tensor, F, W, frame stride in elements) of a device view ``[F, W]`` whose last dimension is contiguous; anything else is copied"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dim() != 2 or min(t.shape) < 1:
+        raise UserWarning(f"{what}: expected a device tensor [F, W]")
+    if t.dtype not in (torch.float32, torch.float64):
+        raise UserWarning(f"{what}: float32 or float64, got {t.dtype}")
+    F, W = (int(n) for n in t.shape)
+    fs, ws = (int(v) for v in t.stride())
+    if (W > 1 and ws != 1) or (F > 1 and fs < W):
+        t = t.contiguous()
+        fs = W
+    return t, F, W, max(fs, W)
+
+
+def fit_sums(x, t, starts=None, skip: int = 0, rec_lags=None, shift=None, scale=None):
+    """The normal-equation sums of ``[x, 1, (t - shift) / scale]`` per recording on the float64 matrix cores (``ape_fit_sums``).  ``x``: a
+    device ``[F, P]`` view, ``P`` a multiple of 16 up to 256 (the hidden features); ``t``: ``[F, Q]``, ``Q <= 32`` (the truth targets);
+    float32 or float64 per side, column slices of wider rows go in without a copy.  ``starts``, ``skip``: the recordings and their
+    cold-start frames, as in ``score_rows``; ``rec_lags``: one lag per recording, ``x`` row ``f`` goes with ``t`` row ``f - l`` (as
+    ``best_lag`` finds it); ``shift``, ``scale``: float64 ``[Q]``, an estimator's ``yy_m`` / ``yy_s``.  Returns float64
+    ``[R, M * M + 2]`` on the device (``fit_sums_numpy`` states the layout and the order): the same inputs give the same bits, a
+    recording's record does not depend on the batch around it.  The call does not wait for the device."""
+    xv, F, P, xs = _fit_view(x, "x")
+    tv, Ft, Q, ts = _fit_view(t, "t")
+    if F != Ft or xv.device != tv.device:
+        raise UserWarning(f"x {tuple(x.shape)} and t {tuple(t.shape)}: the same frames on one device")
+    sh, sc = _fit_affine(shift, scale, Q)
+    st = _recording_starts(starts)
+    R = int(st.shape[0])
+    lags = _fit_lags(rec_lags, R)
+    M = P + 1 + Q
+    dev = xv.device
+    with torch.cuda.device(dev):
+        acc = torch.empty((max(R, 1), M * M + 2), dtype=torch.float64, device=dev)
+        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        _hip.check(_hip.lib().ape_fit_sums(C.c_void_p(xv.data_ptr()), xs, _f64(xv.dtype), P, C.c_void_p(tv.data_ptr()), ts, _f64(tv.dtype), Q,
+                                           C.c_void_p(sh.ctypes.data) if sh is not None else None,
+                                           C.c_void_p(sc.ctypes.data) if sc is not None else None, F, C.c_void_p(st.ctypes.data), R,
+                                           int(skip), C.c_void_p(lags.ctypes.data) if lags is not None else None,
+                                           C.c_void_p(acc.data_ptr()), stream), "ape_fit_sums")
+    return acc
+
+
+def _fit_host(sums) -> tuple:
+    """(records float64 ``[R, M * M + 2]``, M) of ``fit_sums``' result or one record of it"""
+    a = sums.detach().cpu().numpy() if isinstance(sums, torch.Tensor) else np.asarray(sums)
+    a = np.asarray(a, dtype=np.float64)
+    a = a[None] if a.ndim == 1 else a
+    M = math.isqrt(max(a.shape[-1] - 2, 0)) if a.ndim == 2 else 0
+    if a.ndim != 2 or M < 3 or M * M + 2 != a.shape[-1]:
+        raise UserWarning(f"expected fit records [R, M * M + 2], got {tuple(a.shape)}")
+    return a, M
+
+
+def merge_fit(a, b) -> np.ndarray:
+    """the records of two pieces of the same recordings as one (float64, on the host): every sum and both counts added.  For a
+    recording cut at a multiple of ``FIT_PIECE`` frames of its support whose second piece is at most ``FIT_PIECE`` frames long these are
+    the bits of the one call (its pieces, folded in the same order); otherwise another order of the same terms."""
+    x, Ma = _fit_host(a)
+    y, Mb = _fit_host(b)
+    if x.shape != y.shape:
+        raise UserWarning(f"merge_fit: {tuple(x.shape)} and {tuple(y.shape)} records")
+    with np.errstate(all="ignore"):
+        return x + y
+
+
+def _fit_blocks(rec, M: int, P: int):
+    """(A [P + 1, P + 1], C [P + 1, Q], T [Q, Q], n) of one record: the blocks of ``[x, 1]`` against itself, against ``t``, ``t't``"""
+    G = rec[:M * M].reshape(M, M)
+    return G[:P + 1, :P + 1], G[:P + 1, P + 1:], G[P + 1:, P + 1:], float(rec[M * M])
+
+
+def _fit_prior(prior_w, prior_b, M: int):
+    w = np.asarray(prior_w.detach().cpu().numpy() if isinstance(prior_w, torch.Tensor) else prior_w, dtype=np.float64)
+    b = np.asarray(prior_b.detach().cpu().numpy() if isinstance(prior_b, torch.Tensor) else prior_b, dtype=np.float64).reshape(-1)
+    if w.ndim != 2 or w.shape[0] != b.shape[0] or w.shape[0] + w.shape[1] + 1 != M:
+        raise UserWarning(f"prior head: w [Q, P] and b [Q] with P + 1 + Q = {M}, got {tuple(w.shape)} and {tuple(b.shape)}")
+    return w, b
+
+
+def _fit_sse(A, Cx, T, theta) -> np.ndarray:
+    """per-column sum of squared residuals of ``theta [P + 1, Q]`` from the sums alone: ``t't - 2 theta'C + theta'A theta`` (diagonals)"""
+    return np.diag(T) - 2.0 * np.einsum("iq,iq->q", theta, Cx) + np.einsum("iq,ij,jq->q", theta, A, theta)
+
+
+def _fit_pool(a, M: int, keep) -> np.ndarray:
+    rec = np.zeros(M * M + 2)
+    for r in keep:                                      # in recording order, from +0.0
+        rec = rec + a[r]
+    return rec
+
+
+def price_head(sums, w, b, recordings=None) -> tuple:
+    """``(rmse [Q], n)`` of the head ``(w [Q, P], b [Q])`` over the listed recordings' records (default: all), from the sums alone:
+    ``sqrt(max(0, SSE) / n)`` per column, in the units of the fitted targets (``fit_sums``' shift and scale); NaN without a pair."""
+    a, M = _fit_host(sums)
+    wv, bv = _fit_prior(w, b, M)
+    P = wv.shape[1]
+    keep = range(a.shape[0]) if recordings is None else [int(r) for r in recordings]
+    A, Cx, T, n = _fit_blocks(_fit_pool(a, M, keep), M, P)
+    theta = np.concatenate([wv.T, bv[None]], axis=0)
+    with np.errstate(all="ignore"):
+        return (np.sqrt(np.maximum(_fit_sse(A, Cx, T, theta), 0.0) / n) if n > 0 else np.full(wv.shape[0], np.nan)), int(n)
+
+
+def best_head(sums, prior_w, prior_b, ridge: float = 0.0, leave_out=None, min_pairs=None) -> tuple:
+    """The output layer that fits the recordings best, read off ``fit_sums``' records ``[R, M * M + 2]``: ``(w [Q, P], b [Q], report)``
+    in float64.  Over the sum of the records of all recordings but those listed in ``leave_out``, with ``A`` the sums of ``[x, 1]``
+    against itself, ``C`` against ``t`` and ``n`` the pairs summed, it solves ``(A + ridge n D) Theta = C + ridge n D Theta0`` for
+    ``Theta = [W'; b']``: ``Theta0`` is the prior head ``(prior_w [Q, P], prior_b [Q])``, ``D = diag(1, .., 1, 0)`` -- the bias is not
+    penalised, the penalty pulls the weights towards the present head.  ``ridge = inf``: the prior's weights with the bias that fits.
+    ``report``: ``pairs``; ``rmse_prior`` and ``rmse_fit`` ``[Q]`` from the sums alone (``price_head``); ``cond`` of the matrix solved;
+    ``ridge``; ``refused`` with ``reason``.  Refused -- the prior is returned -- with fewer than ``2 (P + 1)`` pairs (``min_pairs``
+    states another floor: under a ridge the system is definite with fewer pairs than unknowns, at the caller's risk), a sum that is not
+    finite, or a matrix that is not positive definite (no Cholesky factor, a pivot within ``(P + 1) eps`` of its diagonal entry, or a
+    solution that is not finite)."""
+    a, M = _fit_host(sums)
+    w0, b0 = _fit_prior(prior_w, prior_b, M)
+    Q, P = w0.shape
+    if not (ridge >= 0.0):
+        raise UserWarning("ridge: a value >= 0 (inf: the prior's weights)")
+    out = set(int(r) for r in ([] if leave_out is None else leave_out))
+    if any(r < 0 or r >= a.shape[0] for r in out):
+        raise UserWarning(f"leave_out: recordings of 0 .. {a.shape[0] - 1}")
+    rec = _fit_pool(a, M, [r for r in range(a.shape[0]) if r not in out])
+    A, Cx, T, n = _fit_blocks(rec, M, P)
+    theta0 = np.concatenate([w0.T, b0[None]], axis=0)
+    nan = np.full(Q, np.nan)
+    report = {"pairs": int(n) if np.isfinite(n) else 0, "rmse_prior": nan, "rmse_fit": nan, "cond": float("nan"), "ridge": float(ridge),
+              "refused": True, "reason": None}
+
+    def refuse(reason):
+        report["reason"] = reason
+        report["rmse_fit"] = report["rmse_prior"]
+        return w0.copy(), b0.copy(), report
+
+    if not np.isfinite(rec).all():
+        return refuse("a sum is not finite")
+    with np.errstate(all="ignore"):
+        if n > 0:
+            report["rmse_prior"] = np.sqrt(np.maximum(_fit_sse(A, Cx, T, theta0), 0.0) / n)
+        floor = 2 * (P + 1) if min_pairs is None else max(1, int(min_pairs))
+        if n < floor:
+            return refuse(f"{int(n)} pairs, fewer than " + (f"2 (P + 1) = {floor}" if min_pairs is None else f"min_pairs = {floor}"))
+        if np.isinf(ridge):                             # the weights stay; the bias that fits them: sum t - W sum x over n
+            theta = theta0.copy()
+            theta[P] = (Cx[P] - w0 @ A[:P, P]) / n
+            report["cond"] = 1.0
+        else:
+            D = np.ones(P + 1)
+            D[P] = 0.0
+            Ms = A + np.diag(ridge * n * D)
+            rhs = Cx + (ridge * n * D)[:, None] * theta0
+            try:
+                Lc = np.linalg.cholesky(Ms)
+            except np.linalg.LinAlgError:
+                return refuse("the matrix is not positive definite")
+            if (np.diag(Lc) ** 2 <= (P + 1) * np.finfo(np.float64).eps * np.diag(Ms)).any():
+                return refuse("the matrix is not positive definite to working precision (a pivot at the rounding of its diagonal)")
+            theta = np.linalg.solve(Lc.T, np.linalg.solve(Lc, rhs))
+            if not np.isfinite(theta).all():
+                return refuse("the matrix is not positive definite (no finite solution)")
+            report["cond"] = float(np.linalg.cond(Ms))
+        report["rmse_fit"] = np.sqrt(np.maximum(_fit_sse(A, Cx, T, theta), 0.0) / n)
+    report["refused"] = False
+    return np.ascontiguousarray(theta[:P].T), theta[P].copy(), report
+
+
+def sweep_ridge(sums, prior_w, prior_b, ridges, min_pairs=None) -> tuple:
+    """Leave-one-recording-out prices of ridges, from the sums alone: for every ridge and recording ``r`` the head fitted on all records
+    but ``r`` (``best_head(leave_out=[r], min_pairs=min_pairs)``; a refused fit is the prior) is priced on record ``r``, the squared residuals are pooled over
+    the recordings that have pairs.  Returns ``(rmse [len(ridges), Q], prior_rmse [Q])``: the held-out RMSE per ridge and column and
+    that of the prior head over the same pairs, which no ridge enters."""
+    a, M = _fit_host(sums)
+    w0, b0 = _fit_prior(prior_w, prior_b, M)
+    Q, P = w0.shape
+    rs = [float(v) for v in np.asarray(ridges, dtype=np.float64).reshape(-1)]
+    R = a.shape[0]
+    if R < 2:
+        raise UserWarning("sweep_ridge: at least two recordings")
+    theta0 = np.concatenate([w0.T, b0[None]], axis=0)
+    blocks = [_fit_blocks(a[r], M, P) for r in range(R)]
+    held = [r for r in range(R) if np.isfinite(a[r]).all() and blocks[r][3] > 0]
+    total = sum(blocks[r][3] for r in held)
+    if not held:
+        raise UserWarning("sweep_ridge: no recording has a pair")
+    with np.errstate(all="ignore"):
+        prior_sse = np.zeros(Q)
+        for r in held:
+            prior_sse = prior_sse + _fit_sse(*blocks[r][:3], theta0)
+        out = np.zeros((len(rs), Q))
+        for k, ridge in enumerate(rs):
+            sse = np.zeros(Q)
+            for r in held:
+                w, b, _ = best_head(a, w0, b0, ridge, leave_out=[r], min_pairs=min_pairs)
+                sse = sse + _fit_sse(*blocks[r][:3], np.concatenate([w.T, b[None]], axis=0))
+            out[k] = np.sqrt(np.maximum(sse, 0.0) / total)
+        return out, np.sqrt(np.maximum(prior_sse, 0.0) / total)

@@ -1583,6 +1583,68 @@ int ape_spectra(const void* x_dev, int32_t x_dtype, int64_t x_set_stride, int64_
                 int32_t skip, int32_t N, int32_t hop, const double* taper_host /* f64 [N] */, uint32_t flags,
                 double* acc_dev /* f64 [n_sets, R, V, N/2 + 1, W] */, int32_t* counts_dev /* i32 [n_sets, R, V, 2] */, void* stream);
 
+/* ---- the output layer fitted to a wearer: hidden features, fit sums, installing a head (additive in ABI 7) -------------------
+ * replaces: nothing; the reference has no counterpart.  The scorers say how wrong a replay is and ape_score_lags / ape_frame_sums /
+ * ape_body_sums take three wearer-specific errors out of it; the regressor's own error stays, its output_layer being the same for every
+ * wearer.  A linear probe keeps the LSTM and fits the head again on a recording of the wearer with truth: the features h of every frame
+ * (ape_lstm_features, ape_replay_features), the normal-equation sums of [h, 1, t] per recording (ape_fit_sums), a small solve on the host
+ * (score.py: best_head, sweep_ridge) and the new head installed (ape_model_set_head).  DropoutLSTM handles only: APE_MODEL_FF and
+ * APE_MODEL_IMUPOSE are refused with APE_ERR_UNSUPPORTED by the four entries that take a handle.
+ * ape_lstm_features.  ape_lstm_forward's arguments and meaning with one more output: h_dev f32 [B, H] receives h^{L-1}_{T-1}, the top
+ *   layer's output of the last step -- the vector the head multiplies -- and y_dev f32 [B, O] (or NULL) what the same launch's head makes
+ *   of it.  Every row runs on ape_lstm_tile16<H, L, 4, true>, the batch-tile kernel with the store (ape_model_last_kernel: "ape_lstm_tile16<hout>"), whatever ape_lstm_forward's planner would
+ *   pick for (B, T): y_dev has the bits of ape_lstm_forward under ape_model_set_kernel(APE_KERNEL_TILE16), with the same Philox masks.
+ *   Flags: APE_FLAG_NORMALIZE_INPUT and the two dropout modes.  Refused: APE_FLAG_ALL_STEPS and every other flag bit
+ *   (APE_ERR_INVALID_ARG), fp16 precision set on the model (APE_ERR_UNSUPPORTED), and what ape_lstm_forward refuses.  Stream, capture,
+ *   journal and recover rules are ape_lstm_forward's: it does not wait, may be captured, and is re-issued behind an aborted launch.
+ * ape_replay_features.  h_dev f32 [F, H] and y_dev f32 [F, O] (or NULL) of every frame of R recordings: ape_replay's feature rows and
+ *   windows (kind, rows_dev, seg_starts_host, seq_len, max_rows_per_launch and APE_FLAG_NORMALIZE_INPUT as there; every recording starts
+ *   cold exactly as ape_replay starts it), then ape_lstm_features per chunk.  One row per frame, no dropout, no post-filter, no state in
+ *   or out: y_dev is ape_replay's y_dev at n_mc = 1 up to the kernels' rounding, and the bits do not depend on the chunking.  Blocking,
+ *   like ape_replay; not on a capturing stream.
+ * ape_fit_sums.  M = P + 1 + Q.  Recording r holds the frames [s_r, e_r) and has the lag l_r = rec_lag_host ? rec_lag_host[r] : 0;
+ *   pairing and the sign of a lag are ape_score_lags's: x row f goes with t row f - l_r.  Its support is the frames f with
+ *   f - s_r >= skip and s_r <= f - l_r < e_r.  With z_f = [x_f (P values), 1, (t_{f - l} - shift) / scale (Q values)] in float64 (f32 is
+ *   widened exactly; shift = t_shift_host or zeros, scale = t_scale_host or ones: an estimator's yy_m / yy_s, so that de-normalised
+ *   targets are fitted in the head's own units), acc_dev f64 [R, M * M + 2] receives
+ *     [i * M + j]     sum over the support of z_f[i] z_f[j], the full symmetric matrix: G = x'x in [0:P, 0:P], sum x in row / column P,
+ *                     the count at [P, P], C = x't in [0:P, P+1:M], sum t in [P, P+1:M], t't in [P+1:M, P+1:M]
+ *     [M * M], [M * M + 1]   pairs of the support that were summed / that were left out
+ *   x element (f, i) lies x_stride * f + i elements after x_dev (x_dtype), t element (f, q) t_stride * f + q after t_dev (t_dtype): any
+ *   columns of wider rows go in as they lie.  A pair is left out iff any of its P + Q values is not finite (or a finite truth value
+ *   overflows under shift and scale); it contributes exact zeros to every sum, the count included.
+ *   Order.  This is part of the contract.  A support is cut into pieces of APE_FIT_PIECE frames counted from its first frame.  Within a
+ *   piece every sum is one chain of v_mfma_f64_16x16x4_f64 from +0.0 in rising f, four frames per instruction (fused multiply-adds);
+ *   the pieces' sums are added in piece order, the first to +0.0.  Entry (i, j) with i > j is a copy of (j, i).  No floating-point
+ *   atomics, no memset: the same inputs give the same bits, a recording's record has the same bits wherever it lies in a batch, and the
+ *   records of a recording cut at a multiple of APE_FIT_PIECE frames of its support add up to the pieces of the whole (score.py:
+ *   merge_fit).
+ *   Needs no model handle, runs on the current HIP device and does not wait; the host arrays have been consumed when it returns; staging
+ *   slots as ape_score_rows keeps them (this file's own).  Two launches, all of acc_dev written.
+ *   Refused with APE_ERR_INVALID_ARG on the host, before anything is written: NULL x_dev / t_dev / seg_starts_host / acc_dev; P not a
+ *   multiple of 16 in 16 .. APE_FIT_MAX_P; Q outside 1 .. APE_FIT_MAX_Q; F < 1, R < 1, bad starts, skip < 0; an unknown dtype; x_stride
+ *   below P or t_stride below Q; a pointer not aligned to its element; a shift that is not finite, a scale that is not finite or zero;
+ *   |l_r| above APE_SCORE_MAX_LAG; acc_dev overlapping an input; more than 1 GiB of piece records; a capturing stream.
+ * ape_model_set_head / ape_model_get_head.  w_out_host f32 [O, H], b_out_host f32 [O]: output_layer.weight and .bias, the tail of
+ *   ape_model_load_weights' blob.  Synchronous, like ape_model_load_weights: the handle is first made healthy and idle (ape_model_recover,
+ *   then a wait for the device), so every call issued before runs on the head it was issued with; every call after runs on the new one,
+ *   on every route, in banks and replays too -- no kernel of a DropoutLSTM handle keeps a packed copy of the head.  APE_ERR_NOT_READY
+ *   before weights are loaded. */
+#define APE_FIT_PIECE  512
+#define APE_FIT_MAX_P  256
+#define APE_FIT_MAX_Q  32
+int ape_lstm_features(ape_model_t* model, const float* x_dev, int32_t B, int32_t T, uint32_t flags, const float* masks_dev,
+                      float dropout_p, uint64_t seed, float* h_dev /* f32 [B, H] */, float* y_dev /* f32 [B, O] or NULL */, void* stream);
+int ape_replay_features(ape_model_t* model, int32_t kind, const float* rows_dev, int32_t F, const int32_t* seg_starts_host, int32_t R,
+                        int32_t seq_len, uint32_t flags, float* h_dev /* f32 [F, H] */, float* y_dev /* f32 [F, O] or NULL */,
+                        int32_t max_rows_per_launch, void* stream);
+int ape_fit_sums(const void* x_dev, int64_t x_stride, int32_t x_dtype, int32_t P, const void* t_dev, int64_t t_stride, int32_t t_dtype,
+                 int32_t Q, const double* t_shift_host /* f64 [Q] or NULL */, const double* t_scale_host /* f64 [Q] or NULL */, int32_t F,
+                 const int32_t* seg_starts_host, int32_t R, int32_t skip, const int32_t* rec_lag_host /* i32 [R] or NULL */,
+                 double* acc_dev /* f64 [R, M * M + 2] */, void* stream);
+int ape_model_set_head(ape_model_t* model, const float* w_out_host /* f32 [O, H] */, const float* b_out_host /* f32 [O] */);
+int ape_model_get_head(ape_model_t* model, float* w_out_host /* f32 [O, H] */, float* b_out_host /* f32 [O] */);
+
 #ifdef __cplusplus
 }
 #endif
